@@ -1,6 +1,6 @@
 """Headline benchmark: Mbp/s gene-called in meta mode (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W [--workload config4|config3|config2|config5]
+    python bench.py --gpus N --steps K --warmup W [--workload config4|config3|config2|config5] [--dump-outputs DIR] [--full]
 
 Workload (config.workload), the same fixed job at every N ("strong" scaling): BASELINE.json configs[3], the
 100 000 x 20 kbp metagenome-like contigs (seed 1 000 000 + c, GC 30..70 %), meta mode over 16 custom
@@ -12,8 +12,12 @@ for every model in the contig's GC window -> winner -> genes in host memory, the
 to rank 0 (RCCL over xGMI; contigs are independent, so there is no collective in the data path).
 `value` = bases of the whole job / max-over-ranks step time of the HOST-TO-HOST loop (SURVEY 8d's definition of the metric:
 ASCII contigs in host memory -> packing into pinned memory -> H2D -> path -> gene records in host memory -> gather), timed over
-all --steps.  `config.resident_Mbp_s` is the same loop with the contigs already resident in HBM (no packing, no upload).
-At N = 1 the other single-GPU configurations of BASELINE.json (configs[1], [2], [4]) are timed as well (`secondary`),
+all --steps.  A plain run does only that: set-up, warmup, the K timed steps, the result line.
+--dump-outputs DIR: after the timed steps, the gene records of the last step (a fixed, seeded sample of the job's contigs) as
+DIR/<field>.npy, and every contig's gene count; the inputs are seeded, so two builds can be compared output for output.
+--full adds what takes runs of its own: `config.resident_Mbp_s` (the same loop with the contigs already resident in HBM: no packing,
+no upload), the same steps back to back, the connection-scoring `roofline` and `pipeline` figures, the CPU baselines and the parity
+check against the CPU oracle, and at N = 1 the other single-GPU configurations of BASELINE.json (configs[1], [2], [4], `secondary`),
 each with its own connection-scoring roofline.
 """
 import argparse
@@ -220,6 +224,29 @@ def timed_steps(lanes, batches, steps, warmup, sync, gather, post=None, **kw):
     return time.perf_counter() - t0, dp_ms, passes, calls, res, genes
 
 
+DUMP_CONTIGS = 4096          # --dump-outputs: the genes of this many contigs of the job (a seeded sample) ...
+DUMP_GENES = 1 << 18         # ... and of at most this many of their genes: 21 columns x 8 B x 2^18 = 44 MB, with the per-contig counts < 64 MB
+
+
+def dump_outputs(out_dir, genes, n_contigs, seed=20261015):
+    """What the timed path handed its caller in its last step: the gene records (job-wide contig numbers), in (contig, begin, end,
+    strand) order, of a fixed seeded sample of the job's contigs -- one DIR/<field>.npy per field of `pga_gene`, float64 (gc_cont
+    float32, as stored; rbs as two columns) -- and DIR/genes_per_contig.npy, every contig's gene count.  The sample depends on the
+    job alone, so two builds write the same rows where they find the same genes."""
+    g = np.concatenate(genes) if len(genes) != 1 else genes[0]
+    g = g[np.lexsort((g["strand"], g["end"], g["begin"], g["contig"]))]
+    rng = np.random.default_rng(seed)
+    picked = np.sort(rng.choice(n_contigs, size=min(n_contigs, DUMP_CONTIGS), replace=False))
+    rows = np.flatnonzero(np.isin(g["contig"], picked))
+    if len(rows) > DUMP_GENES:
+        rows = np.sort(rng.choice(rows, size=DUMP_GENES, replace=False))
+    os.makedirs(out_dir, exist_ok=True)
+    for name in g.dtype.names:
+        col = g[name][rows]
+        np.save(os.path.join(out_dir, name + ".npy"), col.astype(np.float32 if col.dtype == np.float32 else np.float64))
+    np.save(os.path.join(out_dir, "genes_per_contig.npy"), np.bincount(g["contig"], minlength=n_contigs).astype(np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -232,8 +259,12 @@ def main():
     ap.add_argument("--sub-batch", type=int, default=6_250, help="contigs per device call")
     ap.add_argument("--contexts", type=int, default=4, help="device contexts (streams) the calls of a pass are dealt to (four: DESIGN 5.1, round 5)")
     ap.add_argument("--gen-procs", type=int, default=0, help="worker processes generating the synthetic contigs (0: up to 32; 1: none, e.g. under rocprofv3)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: without the CPU baselines and the parity check")
+    ap.add_argument("--no-secondary", action="store_true", help="--full: without the other workloads")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's gene records to DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also the measurements that take runs of their own: resident and back-to-back loops, rooflines, CPU baselines, "
+                         "parity check, other workloads")
     args = ap.parse_args()
 
     rank = int(os.environ.get("RANK", "0"))
@@ -428,47 +459,51 @@ def main():
                     "estimated_work_share": [round(w_ / max(sum(wsum), 1e-9), 4) for w_ in wsum],
                     "lpt_imbalance": round(max(wsum) / max(sum(wsum) / world, 1e-9), 4)}
 
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, all_genes, len(lengths))
+
     # ---- the same K passes issued back to back (one rank only; reported next to `value`, never as it): a step of the loop above ends
     #      with a join of all contexts, so the pipeline of calls drains and refills once per step; a caller that streams batch after
     #      batch does not pay that.  Every pass still ends with its own gather, in order.
     b2b_elapsed = None
-    if dist is None and n_ctx > 1 and len(groups) > 1:
+    if args.full and dist is None and n_ctx > 1 and len(groups) > 1:
         sync()
         t0b = time.perf_counter()
         lanes.run_back_to_back(args.steps, len(groups), h2h_call, gather)
         sync()
         b2b_elapsed = time.perf_counter() - t0b
 
-    # ---- the same loop with the contigs resident in HBM (no packing, no upload): the rate of the path alone
-    batches = [ctxs[k % n_ctx].upload(g) for k, g in enumerate(groups)]
-    res_steps = max(1, min(args.steps, 5))
-    r_elapsed, _, _, _, _, _ = timed_steps(lanes, batches, res_steps, 1, sync, gather, post=renumber, **kw)
-    if dist is not None:
-        t = torch.tensor([r_elapsed], dtype=torch.float64, device=xdev)
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        r_elapsed = float(t.item())
-    # With several contexts a kernel shares the device with the other contexts' kernels and its own duration says little about
-    # the kernel: the connection-scoring roofline is taken from the same calls issued one after the other (same batches, same
-    # HIP events on the library's stream), right after the timed region; the overlapped figure is reported next to it.
-    dp_ms, passes, calls = 0.0, 0, 0
-    topo_ms = sched_ms = 0.0
-    # (with a ramped call plan: the FULL-SIZE calls only -- the launch the PMC passes profile and the earlier rounds report)
-    full_size = max(len(g) for g in groups)
-    for _ in range(max(1, min(args.steps, 3))):
-        for k, b in enumerate(batches):
-            if len(groups[k]) != full_size:
-                continue
-            r = ctxs[k % n_ctx].find_genes(b, **kw)
-            dp_ms += r.t_dp_ms; passes += r.node_passes; calls += 1
-            tmg = ctxs[k % n_ctx].dp_timings()
-            topo_ms += tmg["topo_ms"]; sched_ms += tmg["sched_ms"]
-    sync()
+    batches = []
+    if args.full:
+        # ---- the same loop with the contigs resident in HBM (no packing, no upload): the rate of the path alone
+        batches = [ctxs[k % n_ctx].upload(g) for k, g in enumerate(groups)]
+        res_steps = max(1, min(args.steps, 5))
+        r_elapsed, _, _, _, _, _ = timed_steps(lanes, batches, res_steps, 1, sync, gather, post=renumber, **kw)
+        if dist is not None:
+            t = torch.tensor([r_elapsed], dtype=torch.float64, device=xdev)
+            dist.all_reduce(t, op=dist.ReduceOp.MAX)
+            r_elapsed = float(t.item())
+        # With several contexts a kernel shares the device with the other contexts' kernels and its own duration says little about
+        # the kernel: the connection-scoring roofline is taken from the same calls issued one after the other (same batches, same
+        # HIP events on the library's stream), right after the timed region; the overlapped figure is reported next to it.
+        dp_ms, passes, calls = 0.0, 0, 0
+        topo_ms = sched_ms = 0.0
+        # (with a ramped call plan: the FULL-SIZE calls only -- the launch the PMC passes profile and the earlier rounds report)
+        full_size = max(len(g) for g in groups)
+        for _ in range(max(1, min(args.steps, 3))):
+            for k, b in enumerate(batches):
+                if len(groups[k]) != full_size:
+                    continue
+                r = ctxs[k % n_ctx].find_genes(b, **kw)
+                dp_ms += r.t_dp_ms; passes += r.node_passes; calls += 1
+                tmg = ctxs[k % n_ctx].dp_timings()
+                topo_ms += tmg["topo_ms"]; sched_ms += tmg["sched_ms"]
+        sync()
 
     out = None
     if rank == 0:
         ms_per_step = 1e3 * elapsed / args.steps
         value = job_bases * args.steps / elapsed / 1e6
-        n_chains = max([r.n_chains for r in res], default=0)
         out = {
             "metric": "Mbp/sec gene-called (meta mode)" if not single else "Mbp/sec gene-called (single mode)",
             "value": round(value, 3), "unit": "Mbp/s",
@@ -482,18 +517,20 @@ def main():
                        "parallelism": "contigs packed by estimated work over %d GPU(s), one gather of gene records to rank 0" % world,
                        "steps_issued": "back to back (a rank's contexts go on with step s + 1 while step s is gathered)" if streamed else "a join of the contexts and a gather per step",
                        "timed": "host to host (SURVEY 8d): ASCII contigs in host memory -> pinned packing -> H2D -> path -> gene records in host memory -> gather",
-                       "resident_Mbp_s": round(job_bases * res_steps / r_elapsed / 1e6, 3), "resident_steps": res_steps,
-                       "resident_ms_per_step": round(1e3 * r_elapsed / res_steps, 3),
                        "gather_ms_per_step_rank0": round(1e3 * gather_s / args.steps, 3),
-                       "host_to_host_back_to_back_Mbp_s": round(job_bases * args.steps / b2b_elapsed / 1e6, 3) if b2b_elapsed else None,
                        "generate_s_rank0": round(t_gen, 2)},
-            # one launch = one device call = one sub-batch: the PMC passes profile exactly that (tools/collect_profiles.sh)
-            "roofline": roofline(ctx, dp_ms, passes, calls, n_chains, wname,
-                                 "%dx20kbp_gc30-70_meta" % min(sub, len(seqs)) if args.workload == "config4" else None,
-                                 aux_ms=(topo_ms, sched_ms) if not single and args.workload in ("config4", "config3") else None),
         }
         if per_rank is not None:
             out["config"]["per_rank"] = per_rank
+    if rank == 0 and args.full:
+        n_chains = max([r.n_chains for r in res], default=0)
+        out["config"].update({"resident_Mbp_s": round(job_bases * res_steps / r_elapsed / 1e6, 3), "resident_steps": res_steps,
+                              "resident_ms_per_step": round(1e3 * r_elapsed / res_steps, 3),
+                              "host_to_host_back_to_back_Mbp_s": round(job_bases * args.steps / b2b_elapsed / 1e6, 3) if b2b_elapsed else None})
+        # one launch = one device call = one sub-batch: the PMC passes profile exactly that (tools/collect_profiles.sh)
+        out["roofline"] = roofline(ctx, dp_ms, passes, calls, n_chains, wname,
+                                   "%dx20kbp_gc30-70_meta" % min(sub, len(seqs)) if args.workload == "config4" else None,
+                                   aux_ms=(topo_ms, sched_ms) if not single and args.workload in ("config4", "config3") else None)
         pl = pipeline_entry("%dx20kbp_gc30-70_meta" % min(sub, len(seqs)) if args.workload == "config4" else wname)
         if pl is not None:
             out["pipeline_hbm_bytes_per_bp"] = pl["pipeline_hbm_bytes_per_bp"]         # all kernels of a device call
@@ -510,7 +547,7 @@ def main():
                 # ... and its last row: the job that was timed, checked across every device call and context
                 out["parity"] = parity_sample(seqs, models, res, base_of, n_ctx)
     share_line = None
-    if rank == 0 and world == 1 and args.workload == "config4" and not args.no_secondary and len(seqs) >= 8 * 3125:
+    if args.full and rank == 0 and world == 1 and args.workload == "config4" and not args.no_secondary and len(seqs) >= 8 * 3125:
         # What one rank of the 8-GPU run will do, timed alone here: rank 0's share of the LPT packing (12 500 of the 100 000 contigs) with the
         # call plan bench.py gives a rank (calls of at least 3 125 contigs on up to --contexts contexts), host to host, a join and a gather
         # per step.  predicted_efficiency_at_8 = (this GPU's whole-job step / 8) / the share's step: what per-step fixed costs (first
@@ -546,14 +583,15 @@ def main():
                       "what": "rank 0's share of the job on 8 GPUs (LPT packing), timed alone on this GPU with a rank's own call plan; a prediction of "
                               "per-step fixed costs, not a scaling measurement: no multi-GPU run exists"}
     fasta_line = pool_line = None
-    try:
-        free_b, total_b = torch.cuda.mem_get_info(dev_index)
-        out["config"]["hbm_in_use_GB"] = round((total_b - free_b) / 1e9, 1)        # the contexts' buffers + the resident batches, at their peak
-    except Exception:
-        pass
+    if args.full:
+        try:
+            free_b, total_b = torch.cuda.mem_get_info(dev_index)
+            out["config"]["hbm_in_use_GB"] = round((total_b - free_b) / 1e9, 1)        # the contexts' buffers + the resident batches, at their peak
+        except Exception:
+            pass
     # (the job's contexts hold tens of GB -- 160 GB in round 3 --; the two workloads below add about 30 GB while they run.  Closing the job's
     # contexts first makes the FASTA pass that creates its contexts inside the timed region wait for 160 GB of frees.)
-    if rank == 0 and world == 1 and not single and not args.no_secondary:
+    if args.full and rank == 0 and world == 1 and not single and not args.no_secondary:
         fasta_line = fasta_to_genes(seqs[:min(len(seqs), 20000)], models, dev_index, kw)
         pool_line = threadpool_find_genes(seqs[:min(len(seqs), 8000)], models, dev_index)
     for b in batches:
@@ -561,7 +599,7 @@ def main():
     lanes.close()
     for c in ctxs[1:]:
         c.close()
-    if rank == 0 and world == 1 and not args.no_secondary:
+    if args.full and rank == 0 and world == 1 and not args.no_secondary:
         out["secondary"] = secondary(ctx, _cabi, benchdata, models, args.workload, sync)
         if fasta_line:
             out["secondary"]["fasta_file_to_genes"] = fasta_line

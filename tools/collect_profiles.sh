@@ -11,7 +11,7 @@ REPO=$(pwd)
 OUT=$REPO/gpurun_out/prof_$TAG
 mkdir -p "$OUT"
 export TMPDIR=/tmp
-COMMON="--no-cpu-baseline --no-secondary --contexts 1 --gen-procs 1"
+COMMON="--full --no-cpu-baseline --no-secondary --contexts 1 --gen-procs 1"
 run() { local name=$1; shift; ( cd /tmp && timeout -k 5 240 "$@" ) ; }
 # known-byte-count kernels: what FETCH_SIZE / WRITE_SIZE report for 4 / 8 / 16 bytes per lane and for 64-byte records
 for C in FETCH_SIZE WRITE_SIZE; do

@@ -10,7 +10,7 @@ mkdir -p "$OUT"
 pass() {
   local name=$1; shift
   ( cd /tmp && timeout -k 5 200 rocprofv3 --pmc "$@" --output-format csv -d "$OUT/$name" -o p -- \
-    python "$REPO/bench.py" --workload config4 --contigs 6250 --no-cpu-baseline --no-secondary --contexts 1 --gen-procs 1 --steps 2 --warmup 1 > /dev/null 2> "$OUT/$name.log" )
+    python "$REPO/bench.py" --full --workload config4 --contigs 6250 --no-cpu-baseline --no-secondary --contexts 1 --gen-procs 1 --steps 2 --warmup 1 > /dev/null 2> "$OUT/$name.log" )
   python - <<PY
 import csv,glob,collections,re
 fs=glob.glob("$OUT/$name/**/*counter_collection.csv",recursive=True)

@@ -2,7 +2,7 @@
 # HBM bytes and time of the connection-scoring launch of one config-4 device call (one context), e.g. under PGA_DP_XCD=0 / 1:
 #   gpurun -- 'bash tools/dp_traffic.sh tag'
 TAG=${1:-q}; REPO=$(pwd); OUT=$REPO/gpurun_out/dpt_$TAG; mkdir -p "$OUT"; export TMPDIR=/tmp
-ARGS="--workload config4 --contigs 6250 --no-cpu-baseline --no-secondary --contexts 1 --gen-procs 1 --steps 3 --warmup 1"
+ARGS="--full --workload config4 --contigs 6250 --no-cpu-baseline --no-secondary --contexts 1 --gen-procs 1 --steps 3 --warmup 1"
 python bench.py $ARGS 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('dp ms per launch', d['roofline']['kernel_ms_per_launch'])"
 for C in FETCH_SIZE WRITE_SIZE; do
   ( cd /tmp && timeout -k 5 200 rocprofv3 --pmc $C --output-format csv -d "$OUT/$C" -o p -- python "$REPO/bench.py" $ARGS > /dev/null 2> "$OUT/$C.log" )

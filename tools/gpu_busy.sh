@@ -2,7 +2,7 @@
 # How busy the device is while eight contexts run the job: union of the kernel intervals over the span of the traced run's last
 # second (kernel trace of the default bench, few steps).   gpurun -- 'bash tools/gpu_busy.sh'
 REPO=$(pwd); OUT=$REPO/gpurun_out/busy; mkdir -p "$OUT"; export TMPDIR=/tmp
-( cd /tmp && timeout -k 5 400 rocprofv3 --kernel-trace --memory-copy-trace --output-format csv -d "$OUT/trace" -o t -- python "$REPO/bench.py" --no-cpu-baseline --no-secondary --steps 3 --warmup 1 > "$OUT/bench.json" 2> "$OUT/log.txt" )
+( cd /tmp && timeout -k 5 400 rocprofv3 --kernel-trace --memory-copy-trace --output-format csv -d "$OUT/trace" -o t -- python "$REPO/bench.py" --full --no-cpu-baseline --no-secondary --steps 3 --warmup 1 > "$OUT/bench.json" 2> "$OUT/log.txt" )
 python - <<PY
 import csv, glob
 f = glob.glob("$OUT/trace/**/*kernel_trace.csv", recursive=True)[0]
