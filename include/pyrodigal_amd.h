@@ -209,6 +209,11 @@ int  pga_batch_create(pga_ctx*, int32_t n_contigs, const char* const* seqs, cons
 int  pga_batch_create_packed(pga_ctx*, int32_t n_contigs, const char* packed, const int64_t* offs, const int64_t* lens, pga_batch** out);
 void pga_batch_free(pga_batch*);
 int  pga_find_genes(pga_ctx*, const pga_batch*, const pga_params*, pga_result** out);
+/* Single mode, contig i called with loaded model model_of_contig[i] (an index into the pga_set_models set): every contig's result
+ * is identical to pga_find_genes with that one model loaded -- its nodes extracted under that model's translation table, its genes,
+ * node arrays (want_nodes), contigs[i].model = model_of_contig[i] and score.  params->meta must be 0; PGA_EINVAL for an index
+ * outside [0, n_models).  Many genomes under their own models in one call (ref: the per-genome loop of benches/run_single). */
+int  pga_find_genes_models(pga_ctx*, const pga_batch*, const pga_params*, const int32_t* model_of_contig, pga_result** out);
 
 /* ---- stage level --------------------------------------------------------- */
 /* The node arrays as the reference's Nodes methods leave them, one pga_nodes per contig of the batch
@@ -245,6 +250,13 @@ int pga_translate_genes(pga_ctx*, const pga_batch*, int64_t n_genes, const pga_g
  * start training (partial structs, for validation). */
 int pga_train(pga_ctx*, const pga_batch*, const pga_params*, int translation_table, double start_weight, int force_nonsd,
               int upto, pga_training* out);
+/* Many genomes at once: sequence g of the batch is genome g (its contigs already joined with TTAATTAATTAA by the caller), trained
+ * with translation_table[g], start_weight[g], force_nonsd[g]; closed / min_gene / min_edge_gene / max_overlap / mask from params.
+ * out[g] is byte-identical to pga_train of that genome alone; status[g] is PGA_OK or the code pga_train would return (PGA_EINVAL: no
+ * node).  `upto` as in pga_train.  One device pass per stage or training round for all genomes; at most 4 distinct tables per call
+ * (PGA_EINVAL).  The context's loaded model set is left as it was. */
+int pga_train_batch(pga_ctx*, const pga_batch*, const pga_params*, const int32_t* translation_table, const double* start_weight,
+                    const int32_t* force_nonsd, int upto, pga_training* out, int32_t* status);
 
 /* ---- FASTA ingest (host side) ---------------------------------------------- */
 /* Multi-record FASTA, plain or gzip, read in batches ready for pga_find_genes_batch / pga_batch_create

@@ -20,6 +20,7 @@ EXPORTS = [
     "pga_batch_create", "pga_batch_free", "pga_find_genes", "pga_nodes_stage",
     "pga_fasta_open", "pga_fasta_next", "pga_fasta_error", "pga_fasta_close", "pga_train", "pga_dp_stats", "pga_dp_timings", "pga_extract_stats", "pga_dp_plan_summary", "pga_dp_start_order", "pga_cs_task_summary",
     "pga_fasta_next_packed", "pga_batch_create_packed", "pga_translate_genes", "pga_fasta_open_callback", "pga_fasta_release_spare", "pga_dp_xcd_order", "pga_release_cached",
+    "pga_find_genes_models", "pga_train_batch",
 ]
 STAGE_EXTRACT, STAGE_SCORE, STAGE_OVERLAP, STAGE_SEQUENCE = 1, 2, 3, 4
 
@@ -109,10 +110,13 @@ def load():
     L.pga_batch_create.argtypes = [vp, i32, _P(ctypes.c_char_p), _P(i64), _P(vp)]
     L.pga_batch_free.restype = None; L.pga_batch_free.argtypes = [vp]
     L.pga_find_genes.restype = ctypes.c_int; L.pga_find_genes.argtypes = [vp, vp, _P(Params), _P(_P(Result))]
+    L.pga_find_genes_models.restype = ctypes.c_int; L.pga_find_genes_models.argtypes = [vp, vp, _P(Params), vp, _P(_P(Result))]
     L.pga_nodes_stage.restype = ctypes.c_int
     L.pga_nodes_stage.argtypes = [vp, vp, _P(Params), ctypes.c_int, ctypes.c_int, _P(_P(Result))]
     L.pga_train.restype = ctypes.c_int
     L.pga_train.argtypes = [vp, vp, _P(Params), ctypes.c_int, f64, ctypes.c_int, ctypes.c_int, vp]
+    L.pga_train_batch.restype = ctypes.c_int
+    L.pga_train_batch.argtypes = [vp, vp, _P(Params), vp, vp, vp, ctypes.c_int, vp, vp]
     L.pga_fasta_open.restype = ctypes.c_int; L.pga_fasta_open.argtypes = [ctypes.c_char_p, _P(vp)]
     L.pga_fasta_open_callback.restype = ctypes.c_int; L.pga_fasta_open_callback.argtypes = [FASTA_READ_FN, vp, _P(vp)]
     L.pga_fasta_next.restype = ctypes.c_int
@@ -478,13 +482,23 @@ def _upload_packed(self, pb):
 
 
 def _find_genes(self, batch, meta=True, closed=False, min_gene=90, min_edge_gene=60, max_overlap=60, want_nodes=False,
-                mask=False, min_mask=50):
-    """``GeneFinder.find_genes`` over every contig of a resident :class:`Batch`."""
+                mask=False, min_mask=50, model_of_contig=None):
+    """``GeneFinder.find_genes`` over every contig of a resident :class:`Batch`.
+
+    ``model_of_contig`` (single mode): contig i is called with loaded model ``model_of_contig[i]`` (``pga_find_genes_models``)."""
     p = Params(int(closed), min_gene, min_edge_gene, max_overlap, int(meta), int(want_nodes), int(mask), min_mask)
     res = _P(Result)()
-    rc = self.L.pga_find_genes(self.h, batch.h, ctypes.byref(p), ctypes.byref(res))
+    if model_of_contig is None:
+        rc = self.L.pga_find_genes(self.h, batch.h, ctypes.byref(p), ctypes.byref(res))
+        what = "pga_find_genes"
+    else:
+        moc = np.ascontiguousarray(model_of_contig, dtype=np.int32)
+        if moc.shape != (batch.n,):
+            raise ValueError(f"model_of_contig has {moc.size} entries for {batch.n} contigs")
+        rc = self.L.pga_find_genes_models(self.h, batch.h, ctypes.byref(p), ctypes.c_void_p(moc.ctypes.data), ctypes.byref(res))
+        what = "pga_find_genes_models"
     if rc != PGA_OK:
-        _raise(self.L, self.h, rc, "pga_find_genes")
+        _raise(self.L, self.h, rc, what)
     return _unpack_result(self.L, res, want_nodes)
 
 
@@ -531,6 +545,44 @@ def _train(self, seq, translation_table=11, start_weight=4.35, force_nonsd=False
         b.close()
 
 
+def _per_genome(value, n, dtype, name):
+    a = np.asarray(value, dtype=dtype)
+    a = np.full(n, a, dtype) if a.ndim == 0 else np.ascontiguousarray(a)
+    if a.shape != (n,):
+        raise ValueError(f"{name}: {a.size} values for {n} genomes")
+    return a
+
+
+def _train_batch(self, seqs, translation_table=11, start_weight=4.35, force_nonsd=False, closed=False, min_gene=90, min_edge_gene=60,
+                 max_overlap=60, mask=False, min_mask=50, upto=0):
+    """``GeneFinder.train`` on many genomes in one call (``pga_train_batch``): ``seqs[g]`` is genome g (contigs already joined),
+    the three training options a scalar or one value per genome.  Returns one 558 392-byte ``struct _training`` per genome; raises
+    naming the first genome that could not be trained."""
+    n = len(seqs)
+    if n == 0:
+        return []
+    tts = _per_genome(translation_table, n, np.int32, "translation_table")
+    sws = _per_genome(start_weight, n, np.float64, "start_weight")
+    fns = _per_genome(np.asarray(force_nonsd, dtype=bool).astype(np.int32), n, np.int32, "force_nonsd")
+    b = Batch(self, list(seqs))
+    try:
+        p = Params(int(closed), min_gene, min_edge_gene, max_overlap, 0, 0, int(mask), min_mask)
+        out = np.zeros(n * TRAINING_SIZE, np.uint8)
+        status = np.zeros(n, np.int32)
+        rc = self.L.pga_train_batch(self.h, b.h, ctypes.byref(p), tts.ctypes.data, sws.ctypes.data, fns.ctypes.data, int(upto),
+                                    out.ctypes.data, status.ctypes.data)
+        if rc != PGA_OK:
+            _raise(self.L, self.h, rc, "pga_train_batch")
+        bad = np.flatnonzero(status != PGA_OK)
+        if bad.size:
+            g = int(bad[0])
+            raise (ValueError if status[g] == PGA_EINVAL else PgaError)(
+                f"pga_train_batch: genome {g} could not be trained (no start / stop node; code {int(status[g])})")
+        return [out[g * TRAINING_SIZE:(g + 1) * TRAINING_SIZE].tobytes() for g in range(n)]
+    finally:
+        b.close()
+
+
 def _translate_genes(self, batch, result, tables=None, unknown_residue="X", include_stop=True, strict=True):
     """Proteins of ``result.genes`` (a result of ``find_genes`` on the resident ``batch``), translated on the device.
 
@@ -561,6 +613,7 @@ def _translate_genes(self, batch, result, tables=None, unknown_residue="X", incl
 
 Context.translate_genes = _translate_genes
 Context.train = _train
+Context.train_batch = _train_batch
 Context.upload = _upload
 Context.upload_packed = _upload_packed
 Context.nodes_stage = _nodes_stage

@@ -1367,7 +1367,11 @@ static int publish(ResultOwner* R, ResultOwner*& guarded, const pga_params& P, p
 
 // stage 0 = the whole path; PGA_STAGE_* = stop after that stage and return the node arrays (single chain per
 // contig scored with model 0; P.meta then only selects the meta-mode start penalties of Nodes.score)
-static int find_impl(pga_ctx* c, const pga_batch* batch, const pga_params* pp, const int stage, const int tt_override, pga_result** out) {
+// model_of_contig (single mode: the path and the SCORE / OVERLAP stages; nullptr = model 0 everywhere): contig i is scored with that
+// loaded model, its nodes extracted under that model's translation table -- the groups of meta mode, one chain per contig.
+// tt_of_contig (EXTRACT stage; nullptr = tt_override everywhere): contig i is extracted under that table.  At most 4 tables.
+static int find_impl(pga_ctx* c, const pga_batch* batch, const pga_params* pp, const int stage, const int tt_override, pga_result** out,
+                     const int32_t* model_of_contig, const int32_t* tt_of_contig) {
     if (out) *out = nullptr;
     if (!c || !out || !pp || !batch || batch->ctx != c) {
         if (c) c->err = "pga_find_genes: bad arguments";
@@ -1376,6 +1380,8 @@ static int find_impl(pga_ctx* c, const pga_batch* batch, const pga_params* pp, c
     const int32_t n_contigs = batch->n;
     if (!c->finder) { int rc0 = pga_finder_models_changed(c); if (rc0) return rc0; }
     const bool meta_run = pp->meta && stage == 0;
+    const bool per_contig = model_of_contig != nullptr && !pp->meta && stage != PGA_STAGE_EXTRACT && stage != PGA_STAGE_SEQUENCE;
+    const bool per_contig_tt = tt_of_contig != nullptr && stage == PGA_STAGE_EXTRACT;
     // meta mode over an empty bin collection is legal and finds nothing (ref: tests/test_gene_finder.py:316-324)
     if (c->n_models <= 0 && !meta_run && stage != PGA_STAGE_EXTRACT && stage != PGA_STAGE_SEQUENCE) { c->err = "pga_find_genes: no model loaded (call pga_set_models first)"; return PGA_EINVAL; }
     const pga_params P = *pp;
@@ -1393,7 +1399,20 @@ static int find_impl(pga_ctx* c, const pga_batch* batch, const pga_params* pp, c
     HT(c, hipSetDevice(c->device));
     FinderState* f = c->finder;
     hipStream_t st = c->stream;
-    const int NC = n_contigs, NM = c->n_models, NG = meta_run ? (int)f->group_tt.size() : 1;
+    // a translation-table group per contig (per_contig: its model's group; per_contig_tt: a group per distinct table of the call)
+    const bool multi = per_contig || per_contig_tt;
+    std::vector<int> cgrp, gtt;
+    if (per_contig) {
+        gtt = f->group_tt;
+        for (int i = 0; i < n_contigs; i++) cgrp.push_back(f->model_group[model_of_contig[i]]);
+    } else if (per_contig_tt) {
+        for (int i = 0; i < n_contigs; i++) {
+            int g = (int)(std::find(gtt.begin(), gtt.end(), tt_of_contig[i]) - gtt.begin());
+            if (g == (int)gtt.size()) gtt.push_back(tt_of_contig[i]);
+            cgrp.push_back(g);
+        }
+    }
+    const int NC = n_contigs, NM = c->n_models, NG = meta_run ? (int)f->group_tt.size() : (multi ? std::max(1, (int)gtt.size()) : 1);
     if (NG > 4) { c->err = "pga_find_genes: more than 4 distinct translation tables loaded"; return PGA_EINVAL; }
     if (const char* fault = getenv("PGA_FAULT_CONTIG_LEN")) {
         // diagnostics: a call that carries a contig of exactly this many bases fails (the host layer's error paths under test)
@@ -1495,6 +1514,11 @@ static int find_impl(pga_ctx* c, const pga_batch* batch, const pga_params* pp, c
         }
         // meta mode: a contig is extracted under a translation table only if a model with that table lies in its GC window
         if (meta_run && NM > 0) pga_launch_group_enable(d_ct, NC, d_cnt, f->d_model_gc, f->d_model_grp, NM, NG, d_enabled, st);
+        // per-contig models: a contig is extracted under its own model's translation table only
+        if (multi) {
+            for (int g = 0; g < NG; g++) for (int i = 0; i < NC; i++) h_enabled[(size_t)g * NC + i] = cgrp[i] == g;
+            HT(c, hipMemcpyAsync(d_enabled, h_enabled, (size_t)NG * NC, hipMemcpyHostToDevice, st));
+        }
         // Staging of the extraction: one slot per two positions of a tile (sequence has a node every 25 positions or so; the full
         // two-slots-per-position staging was half of a context's memory).  A tile that does not fit raises a flag, the batch is then
         // extracted again with full staging, and the context keeps that (PGA_STAGE_FULL=1: from the start).
@@ -1513,11 +1537,11 @@ static int find_impl(pga_ctx* c, const pga_batch* batch, const pga_params* pp, c
             }
             if (c->extract_passes > 0) HT(c, hipMemsetAsync(d_st_overflow, 0, sizeof(int32_t), st));      // (the first pass: cleared with the counts)
             for (int g = 0; g < NG; g++) {
-                const int tt = meta_run ? f->group_tt[g] : (stage == PGA_STAGE_EXTRACT ? tt_override : c->models[0].trans_table);
+                const int tt = meta_run ? f->group_tt[g] : multi ? gtt[g] : (stage == PGA_STAGE_EXTRACT ? tt_override : c->models[0].trans_table);
                 pga_launch_extract(d_dig, total, d_ct, NC, tt, P, ga[g], batch->d_tiles, batch->n_tiles, batch->d_tile0, d_tile_first, d_tile_last,
                                    d_tile_count + (size_t)g * (batch->n_tiles + 1), d_tile_off + (size_t)g * (batch->n_tiles + 1), d_cbase + (size_t)g * (NC + 1),
                                    d_tile_scount + (size_t)g * (batch->n_tiles + 1), d_tile_soff + (size_t)g * (batch->n_tiles + 1), d_sbase + (size_t)g * (NC + 1),
-                                   masks, st, (meta_run && NM > 0) ? d_enabled + (size_t)g * NC : nullptr);
+                                   masks, st, ((meta_run && NM > 0) || multi) ? d_enabled + (size_t)g * NC : nullptr);
             }
             HT(c, hipMemcpyAsync(h_xa, d_xa, sizeof(int32_t) * xa_words, hipMemcpyDeviceToHost, st));      // flag, counts, offsets, enabled groups
             HT(c, hipGetLastError());
@@ -1558,9 +1582,11 @@ static int find_impl(pga_ctx* c, const pga_batch* batch, const pga_params* pp, c
             R->contigs[i].gc = gc;
             R->contigs[i].n_unknown = h_cnt[NC + i];
             if (!meta_run) {
-                const int32_t* cb = h_cbase;
-                ChainDesc ch{0, cb[i], cb[i + 1] - cb[i], 0, i, 1};
-                gch[0].push_back(ch);
+                const int m = per_contig ? model_of_contig[i] : 0, g = multi ? cgrp[i] : 0;
+                const int32_t* cb = h_cbase + (size_t)g * (NC + 1);
+                ChainDesc ch{0, cb[i], cb[i + 1] - cb[i], m, i, 1};
+                ch.group = g;
+                gch[g].push_back(ch);
                 continue;
             }
             const double low = fmin(0.65, 0.88495 * gc - 0.0102337), high = fmax(0.35, 0.86596 * gc + 0.1131991);
@@ -1587,7 +1613,7 @@ static int find_impl(pga_ctx* c, const pga_batch* batch, const pga_params* pp, c
             for (ChainDesc& ch : gch[g]) {
                 ch.off = tot_chain_nodes; tot_chain_nodes += ch.n;
                 ch.soff = tot_chain_stops;
-                const int32_t* sb = h_sbase + (size_t)(meta_run ? g : 0) * (NC + 1);
+                const int32_t* sb = h_sbase + (size_t)ch.group * (NC + 1);
                 tot_chain_stops += sb[ch.contig + 1] - sb[ch.contig];
                 chains.push_back(ch);
             }
@@ -1771,7 +1797,7 @@ static int find_impl(pga_ctx* c, const pga_batch* batch, const pga_params* pp, c
         // per group and contig: the contiguous run of chains (models) scored on that contig
         for (size_t k = 0; k < (size_t)2 * NG * NC; k++) h_cc[k] = make_int2(0, 0);
         for (int k = 0; k < NCH; k++) {
-            const int g = meta_run ? f->model_group[chains[k].model] : 0;
+            const int g = chains[k].group;
             int2& e = h_cc[(size_t)g * NC + chains[k].contig];
             if (e.y == 0) e.x = k;
             e.y++;
@@ -1848,7 +1874,7 @@ static int find_impl(pga_ctx* c, const pga_batch* batch, const pga_params* pp, c
             }
             pga_launch_score(d_chains + g_c0[g], nch, g_n0[g], nn, d_dig, d_ct, ga[g], d_models, f->d_msc, c->d_model_const, ca, sp,
                              d_chains, d_cc + (size_t)g * NC, d_cbase + (size_t)g * (NC + 1), NC, (int)group_nodes[g], f->d_sd_lut, st, 0,
-                             (meta_run || n_cs_tasks > 0) ? f->d_gil + f->gil_off[g] : nullptr, (meta_run || n_cs_tasks > 0) ? f->gil_stride[g] : 0, f->d_model_rank,
+                             (meta_run || per_contig || n_cs_tasks > 0) ? f->d_gil + f->gil_off[g] : nullptr, (meta_run || per_contig || n_cs_tasks > 0) ? f->gil_stride[g] : 0, f->d_model_rank,
                              d_cs_tasks, n_cs_tasks, d_cs_entries, &sl);
             if (wave_prep && use_sched) {
                 // (behind the scoring launches: the schedule's headers carry the stop nodes' ranks, which k_ovl_topo writes there)
@@ -1862,19 +1888,25 @@ static int find_impl(pga_ctx* c, const pga_batch* batch, const pga_params* pp, c
         }
         if (stage != 0) {
             // ---- stage-level call: bring the node arrays home as they are now and stop ---------------
-            const int64_t nn = group_nodes[0];
+            const int64_t nn = tot_chain_nodes;          // every group's nodes; a contig's chain sits at the same offset in both layouts
             PINBUF(hs_i32, int32_t, "hs_i32", 6 * nn + 8);         // ndx, stop_val, mot_ndx, star_ptr[3]
             PINBUF(hs_f64, double, "hs_f64", 6 * nn + 8);          // cscore, sscore, rscore, uscore, tscore, mot_score
             PINBUF(hs_u8, uint8_t, "hs_u8", 10 * nn + 8);          // type, strand, edge, rbs[2], mot_len, mot_spacer, mot_spacendx
             PINBUF(hs_f32, float, "hs_f32", nn + 8);
             const bool scored = stage >= PGA_STAGE_SCORE;
+            for (int g = 0; g < NG; g++) {
+                const int64_t gn = group_nodes[g], o = g_n0[g];
+                if (gn == 0) continue;
+                HT(c, hipMemcpyAsync(hs_i32 + o, ga[g].ndx, 4 * gn, hipMemcpyDeviceToHost, st));
+                HT(c, hipMemcpyAsync(hs_i32 + nn + o, ga[g].stop_val, 4 * gn, hipMemcpyDeviceToHost, st));
+                HT(c, hipMemcpyAsync(hs_u8 + o, ga[g].type, gn, hipMemcpyDeviceToHost, st));
+                HT(c, hipMemcpyAsync(hs_u8 + nn + o, ga[g].strand, gn, hipMemcpyDeviceToHost, st));
+                if (!scored) HT(c, hipMemcpyAsync(hs_u8 + 2 * nn + o, ga[g].edge0, gn, hipMemcpyDeviceToHost, st));
+                if (scored) HT(c, hipMemcpyAsync(hs_f32 + o, ga[g].gc_cont, 4 * gn, hipMemcpyDeviceToHost, st));
+            }
             if (nn > 0) {
-                HT(c, hipMemcpyAsync(hs_i32, ga[0].ndx, 4 * nn, hipMemcpyDeviceToHost, st));
-                HT(c, hipMemcpyAsync(hs_i32 + nn, ga[0].stop_val, 4 * nn, hipMemcpyDeviceToHost, st));
-                HT(c, hipMemcpyAsync(hs_u8, ga[0].type, nn, hipMemcpyDeviceToHost, st));
-                HT(c, hipMemcpyAsync(hs_u8 + nn, ga[0].strand, nn, hipMemcpyDeviceToHost, st));
-                HT(c, hipMemcpyAsync(hs_u8 + 2 * nn, scored ? ca.edge : ga[0].edge0, nn, hipMemcpyDeviceToHost, st));
                 if (scored) {
+                    HT(c, hipMemcpyAsync(hs_u8 + 2 * nn, ca.edge, nn, hipMemcpyDeviceToHost, st));
                     HT(c, hipMemcpyAsync(hs_i32 + 2 * nn, ca.mot_ndx, 4 * nn, hipMemcpyDeviceToHost, st));
                     HT(c, hipMemcpyAsync(hs_i32 + 3 * nn, ca.star_ptr, 12 * nn, hipMemcpyDeviceToHost, st));
                     double* const src64[6] = {ca.cscore, ca.sscore, ca.rscore, ca.uscore, ca.tscore, ca.mot_score};
@@ -1883,7 +1915,6 @@ static int find_impl(pga_ctx* c, const pga_batch* batch, const pga_params* pp, c
                     HT(c, hipMemcpyAsync(hs_u8 + 5 * nn, ca.mot_len, nn, hipMemcpyDeviceToHost, st));
                     HT(c, hipMemcpyAsync(hs_u8 + 6 * nn, ca.mot_spacer, nn, hipMemcpyDeviceToHost, st));
                     HT(c, hipMemcpyAsync(hs_u8 + 7 * nn, ca.mot_spacendx, nn, hipMemcpyDeviceToHost, st));
-                    HT(c, hipMemcpyAsync(hs_f32, ga[0].gc_cont, 4 * nn, hipMemcpyDeviceToHost, st));
                 }
             }
             HT(c, hipGetLastError());
@@ -1892,8 +1923,10 @@ static int find_impl(pga_ctx* c, const pga_batch* batch, const pga_params* pp, c
             R->nodes.resize(NC);
             for (int i = 0; i < NC; i++) {
                 pga_nodes& N = R->nodes[i];
-                const int64_t oo = h_cbase[i]; const int n = h_cbase[i + 1] - h_cbase[i];
-                R->contigs[i].model = stage == PGA_STAGE_EXTRACT ? -1 : 0; R->contigs[i].n_nodes = n;
+                const int g = multi ? cgrp[i] : 0;
+                const int32_t* cb = h_cbase + (size_t)g * (NC + 1);
+                const int64_t oo = g_n0[g] + cb[i]; const int n = cb[i + 1] - cb[i];
+                R->contigs[i].model = stage == PGA_STAGE_EXTRACT ? -1 : (per_contig ? model_of_contig[i] : 0); R->contigs[i].n_nodes = n;
                 if (int rc = alloc_nodes(R, N, n)) return rc;
                 memcpy(N.ndx, hs_i32 + oo, 4 * (size_t)n); memcpy(N.stop_val, hs_i32 + nn + oo, 4 * (size_t)n);
                 memcpy(N.type, hs_u8 + oo, n); memcpy(N.strand, hs_u8 + nn + oo, n); memcpy(N.edge, hs_u8 + 2 * nn + oo, n);
@@ -2046,7 +2079,7 @@ static int find_impl(pga_ctx* c, const pga_batch* batch, const pga_params* pp, c
             w_o0[g] = out_nodes;
             for (int i = 0; i < NC; i++) {
                 const int k = win_chain[i];
-                if (k < 0 || (P.meta ? f->model_group[chains[k].model] : 0) != g) continue;
+                if (k < 0 || chains[k].group != g) continue;
                 out_off[i] = out_nodes;
                 wg[g].push_back(WinDesc{out_nodes, chains[k].off, fin_off[i], chains[k].topo_off, chains[k].n, 0});
                 out_nodes += chains[k].n;
@@ -2244,7 +2277,7 @@ static int find_impl(pga_ctx* c, const pga_batch* batch, const pga_params* pp, c
                 d.n = k >= 0 ? chains[k].n : 0; d.mx = k >= 0 ? h_maxidx[k] : -1;
                 d.st_wt = k >= 0 ? c->models[chains[k].model].st_wt : 0.0;
                 d.fin_off = k >= 0 ? fin_off[i] : 0; d.topo_off = k >= 0 ? chains[k].topo_off : 0;
-                d.group = k >= 0 && P.meta ? f->model_group[chains[k].model] : 0; d._pad = 0;
+                d.group = k >= 0 ? chains[k].group : 0; d._pad = 0;
                 d.dp_off = k >= 0 ? chains[k].off : 0;
                 n_slots += d.n / 2 + 2;
             }
@@ -2418,7 +2451,7 @@ static int find_impl(pga_ctx* c, const pga_batch* batch, const pga_params* pp, c
 
 extern "C" int pga_find_genes(pga_ctx* c, const pga_batch* batch, const pga_params* pp, pga_result** out) {
     const auto t0 = std::chrono::steady_clock::now();
-    const int rc = find_impl(c, batch, pp, 0, 0, out);
+    const int rc = find_impl(c, batch, pp, 0, 0, out, nullptr, nullptr);
     if (getenv("PGA_TIMING")) fprintf(stderr, "[pga timing] pga_find_genes wall=%.2fms\n", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
     return rc;
 }
@@ -2429,10 +2462,36 @@ extern "C" int pga_nodes_stage(pga_ctx* c, const pga_batch* batch, const pga_par
         if (c) c->err = "pga_nodes_stage: unknown stage";
         return PGA_EINVAL;
     }
-    return find_impl(c, batch, pp, stage, translation_table, out);
+    return find_impl(c, batch, pp, stage, translation_table, out, nullptr, nullptr);
+}
+
+extern "C" int pga_find_genes_models(pga_ctx* c, const pga_batch* batch, const pga_params* pp, const int32_t* model_of_contig, pga_result** out) {
+    if (out) *out = nullptr;
+    if (!c) return PGA_EINVAL;
+    if (!batch || !pp || !out || !model_of_contig) { c->err = "pga_find_genes_models: bad arguments"; return PGA_EINVAL; }
+    if (pp->meta) { c->err = "pga_find_genes_models: a model per contig is a single-mode call (params->meta must be 0)"; return PGA_EINVAL; }
+    for (int i = 0; i < batch->n; i++)
+        if (model_of_contig[i] < 0 || model_of_contig[i] >= c->n_models) {
+            c->err = "pga_find_genes_models: contig " + std::to_string(i) + " names model " + std::to_string(model_of_contig[i]) + " of " +
+                     std::to_string(c->n_models) + " loaded";
+            return PGA_EINVAL;
+        }
+    return find_impl(c, batch, pp, 0, 0, out, model_of_contig, nullptr);
 }
 
 extern "C" int pga_train(pga_ctx* c, const pga_batch* batch, const pga_params* pp, int translation_table, double start_weight,
                          int force_nonsd, int upto, pga_training* out) {
-    return train_impl(c, batch, pp, translation_table, start_weight, force_nonsd, upto <= 0 ? TR_ALL : upto, out);
+    if (!c) return PGA_EINVAL;
+    if (!batch || batch->n != 1) { c->err = "pga_train: needs a batch of exactly one sequence"; return PGA_EINVAL; }
+    const int32_t tt = translation_table, fn = force_nonsd;
+    int32_t status = PGA_OK;
+    const int rc = train_impl(c, batch, pp, &tt, &start_weight, &fn, upto <= 0 ? TR_ALL : upto, out, &status);
+    if (rc != PGA_OK) return rc;
+    if (status != PGA_OK) { c->err = "pga_train: no start / stop node in the sequence"; return status; }
+    return PGA_OK;
+}
+
+extern "C" int pga_train_batch(pga_ctx* c, const pga_batch* batch, const pga_params* pp, const int32_t* translation_table,
+                               const double* start_weight, const int32_t* force_nonsd, int upto, pga_training* out, int32_t* status) {
+    return train_impl(c, batch, pp, translation_table, start_weight, force_nonsd, upto <= 0 ? TR_ALL : upto, out, status);
 }

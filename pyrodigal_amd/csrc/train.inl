@@ -1,10 +1,14 @@
-// Single-genome training on the device (ref: lib.pyx:5236-5279 GeneFinder._train, TrainingInfo._calc_dicodon_gene
+// Training on the device, many genomes per call (ref: lib.pyx:5236-5279 GeneFinder._train, TrainingInfo._calc_dicodon_gene
 // 4284-4358, _train_starts_sd 4391-4599, _train_starts_nonsd 4601-4827; Prodigal node.c record_gc_bias /
 // determine_sd_usage).  Included by finder.hip: the driver continues from the device arrays that the stage-level
 // runs (extraction, scoring) leave behind.  Everything per base / per node runs in kernels; every accumulation is
 // a count (an exact integer in a double, so the order of additions does not matter); libm's log stays on the host,
 // where the reference calls it.
+// Genome dimension: the nodes of every genome of the batch lie back to back in one set of arrays; node i belongs to genome
+// gof[i], whose nodes are [n0, n1) and whose digits start at `base`.  Weights and counters are per genome.
 namespace {
+
+struct TrGenome { int64_t base; int32_t len, n0, n1, _pad; };
 
 constexpr int TR_GC_HALF = 60;          // GC_WINDOW / 2 (ref: lib.pyx:171)
 
@@ -21,8 +25,13 @@ __device__ inline int tr_mer(const uint8_t* __restrict__ d, int L, int i, int le
 
 // ref: lib.pyx:724-768 (Sequence._max_gc_frame_plot).  The running sums of the reference reduce to
 // tot[i] = sum of gc[i + 3 m] for |m| < 20 inside the sequence; the codon at i (i % 3 == 0) gets the frame with the most.
+// grid.y: genome
 __global__ void __launch_bounds__(256)
-k_gc_frame(const uint8_t* __restrict__ d, int L, int8_t* __restrict__ gp) {
+k_gc_frame(const uint8_t* __restrict__ dig, const TrGenome* __restrict__ gs, int8_t* __restrict__ gp_all) {
+    const TrGenome G = gs[blockIdx.y];
+    const uint8_t* __restrict__ d = dig + G.base;
+    int8_t* __restrict__ gp = gp_all + G.base;
+    const int L = G.len;
     const int c = blockIdx.x * blockDim.x + threadIdx.x;       // codon index
     const int i = 3 * c;
     if (i >= L) return;
@@ -43,10 +52,12 @@ k_gc_frame(const uint8_t* __restrict__ d, int L, int8_t* __restrict__ gp) {
 // Prodigal node.c record_gc_bias: per start node, how often each codon position is the GC-richest one between the
 // start and its stop.
 __global__ void __launch_bounds__(256)
-k_gc_bias(int n, const int32_t* __restrict__ ndx, const int32_t* __restrict__ stop_val, const uint8_t* __restrict__ type,
-          const int8_t* __restrict__ strand, const int8_t* __restrict__ gp, double* __restrict__ gc_score, uint8_t* __restrict__ gc_bias) {
+k_gc_bias(int n, const int32_t* __restrict__ gof, const TrGenome* __restrict__ gs, const int32_t* __restrict__ ndx,
+          const int32_t* __restrict__ stop_val, const uint8_t* __restrict__ type, const int8_t* __restrict__ strand,
+          const int8_t* __restrict__ gp_all, double* __restrict__ gc_score, uint8_t* __restrict__ gc_bias) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
+    const int8_t* __restrict__ gp = gp_all + gs[gof[i]].base;
     gc_score[3 * i] = gc_score[3 * i + 1] = gc_score[3 * i + 2] = 0.0; gc_bias[i] = 0;
     if (type[i] == PGA_T_STOP) return;
     int ctr[3] = {0, 0, 0};
@@ -62,11 +73,16 @@ k_gc_bias(int n, const int32_t* __restrict__ ndx, const int32_t* __restrict__ st
     }
     gc_bias[i] = (uint8_t)tr_max_fr(ctr[0], ctr[1], ctr[2]);
 }
-// the one ordered floating-point sum of the training: node order, one thread
-__global__ void k_bias_sum(int n, const int32_t* __restrict__ ndx, const int32_t* __restrict__ stop_val, const uint8_t* __restrict__ type,
-                           const double* __restrict__ gc_score, const uint8_t* __restrict__ gc_bias, double* __restrict__ bias) {
+// the one ordered floating-point sum of the training: node order within a genome, one thread per genome
+__global__ void __launch_bounds__(64)
+k_bias_sum(int n_genomes, const TrGenome* __restrict__ gs, const int32_t* __restrict__ ndx, const int32_t* __restrict__ stop_val,
+           const uint8_t* __restrict__ type, const double* __restrict__ gc_score, const uint8_t* __restrict__ gc_bias,
+           double* __restrict__ bias_all /* [genome][4] */) {
+    const int g = blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= n_genomes) return;
+    double* __restrict__ bias = bias_all + 4 * g;
     double b[3] = {0.0, 0.0, 0.0};
-    for (int i = 0; i < n; i++) {
+    for (int i = gs[g].n0; i < gs[g].n1; i++) {
         if (type[i] == PGA_T_STOP) continue;
         const int len = abs(stop_val[i] - ndx[i]) + 1;
         b[gc_bias[i]] += (gc_score[3 * i + gc_bias[i]] * len) / 1000.0;
@@ -75,37 +91,42 @@ __global__ void k_bias_sum(int n, const int32_t* __restrict__ ndx, const int32_t
     for (int q = 0; q < 3; q++) bias[q] = b[q] * (3.0 / tot);
 }
 __global__ void __launch_bounds__(256)
-k_gcb(int n, const double* __restrict__ gc_score, const double* __restrict__ bias, double* __restrict__ gcb) {
+k_gcb(int n, const int32_t* __restrict__ gof, const double* __restrict__ gc_score, const double* __restrict__ bias_all, double* __restrict__ gcb) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) gcb[i] = bias[0] * gc_score[3 * i] + bias[1] * gc_score[3 * i + 1] + bias[2] * gc_score[3 * i + 2];
+    if (i >= n) return;
+    const double* __restrict__ bias = bias_all + 4 * gof[i];
+    gcb[i] = bias[0] * gc_score[3 * i] + bias[1] * gc_score[3 * i + 1] + bias[2] * gc_score[3 * i + 2];
 }
 
 // ref: lib.pyx:2279-2329 with flag == 0: the first start of each frame met while walking away from the stop
 __global__ void __launch_bounds__(256)
-k_ovl_starts0(int n, const int32_t* __restrict__ ndx, const int32_t* __restrict__ stop_val, const uint8_t* __restrict__ type,
-              const int8_t* __restrict__ strand, const uint8_t* __restrict__ edge, int maxov, int32_t* __restrict__ star_ptr) {
+k_ovl_starts0(int n_all, const int32_t* __restrict__ gof, const TrGenome* __restrict__ gs, const int32_t* __restrict__ ndx,
+              const int32_t* __restrict__ stop_val, const uint8_t* __restrict__ type, const int8_t* __restrict__ strand,
+              const uint8_t* __restrict__ edge, int maxov, int32_t* __restrict__ star_ptr) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
+    if (i >= n_all) return;
+    // the genome's nodes [lo, n); star_ptr holds genome-local indices, as the connection scorer reads them
+    const int lo = gs[gof[i]].n0, n = gs[gof[i]].n1;
     int sp[3] = {-1, -1, -1};
     if (type[i] == PGA_T_STOP && edge[i] != 1) {
         const int me = ndx[i];
         if (strand[i] == 1) {
-            for (int j = i + 3; j >= 0; j--) {
+            for (int j = i + 3; j >= lo; j--) {
                 if (j >= n || ndx[j] > me + 2) continue;
                 if (ndx[j] + maxov < me) break;
                 if (strand[j] != 1 || type[j] == PGA_T_STOP) continue;
                 if (stop_val[j] <= me) continue;
                 const int f = ndx[j] % 3;
-                if (sp[f] == -1) sp[f] = j;
+                if (sp[f] == -1) sp[f] = j - lo;
             }
         } else {
             for (int j = i - 3; j < n; j++) {
-                if (j < 0 || ndx[j] < me - 2) continue;
+                if (j < lo || ndx[j] < me - 2) continue;
                 if (ndx[j] - maxov > me) break;
                 if (strand[j] != -1 || type[j] == PGA_T_STOP) continue;
                 if (stop_val[j] >= me) continue;
                 const int f = ndx[j] % 3;
-                if (sp[f] == -1) sp[f] = j;
+                if (sp[f] == -1) sp[f] = j - lo;
             }
         }
     }
@@ -114,7 +135,11 @@ k_ovl_starts0(int n, const int32_t* __restrict__ ndx, const int32_t* __restrict_
 
 // hexamer statistics (ref: lib.pyx:4284-4358): every window of both strands, then the codons of the genes of the path
 __global__ void __launch_bounds__(256)
-k_hexamer_bg(const uint8_t* __restrict__ d, int L, unsigned int* __restrict__ counts) {
+k_hexamer_bg(const uint8_t* __restrict__ dig, const TrGenome* __restrict__ gs, unsigned int* __restrict__ counts_all /* [genome][2][4096] */) {
+    const TrGenome G = gs[blockIdx.y];
+    const uint8_t* __restrict__ d = dig + G.base;
+    const int L = G.len;
+    unsigned int* __restrict__ counts = counts_all + (size_t)blockIdx.y * 8192;
     __shared__ unsigned int s_c[4096];
     for (int q = threadIdx.x; q < 4096; q += blockDim.x) s_c[q] = 0;
     __syncthreads();
@@ -125,12 +150,16 @@ k_hexamer_bg(const uint8_t* __restrict__ d, int L, unsigned int* __restrict__ co
     __syncthreads();
     for (int q = threadIdx.x; q < 4096; q += blockDim.x) if (s_c[q]) atomicAdd(&counts[q], s_c[q]);
 }
-struct TrGene { int left, right, strand; };     // strand-local [left, right - 5) step 3
+struct TrGene { int left, right, strand, genome; };     // strand-local [left, right - 5) step 3
 __global__ void __launch_bounds__(256)
-k_hexamer_genes(const uint8_t* __restrict__ d, int L, const TrGene* __restrict__ genes, int n_genes, unsigned int* __restrict__ counts) {
+k_hexamer_genes(const uint8_t* __restrict__ dig, const TrGenome* __restrict__ gs, const TrGene* __restrict__ genes, int n_genes,
+                unsigned int* __restrict__ counts_all) {
     const int g = blockIdx.x;
     if (g >= n_genes) return;
     const TrGene G = genes[g];
+    const uint8_t* __restrict__ d = dig + gs[G.genome].base;
+    const int L = gs[G.genome].len;
+    unsigned int* __restrict__ counts = counts_all + (size_t)G.genome * 8192 + 4096;
     for (int i = G.left + 3 * threadIdx.x; i < G.right - 5; i += 3 * blockDim.x) atomicAdd(&counts[tr_mer(d, L, i, 6, G.strand)], 1u);
 }
 
@@ -138,7 +167,7 @@ k_hexamer_genes(const uint8_t* __restrict__ d, int L, const TrGene* __restrict__
 // ---- start training (ref: lib.pyx:4391-4599 _train_starts_sd, 4601-4827 _train_starts_nonsd) ----------------------
 struct TrWeights {            // what changes from one iteration to the next
     double rbs_wt[28], type_wt[3], st_wt, sthresh, no_mot;
-    int last_iter, stage, uses_sd;
+    int last_iter, stage, uses_sd, skip;     // skip: the genome takes no part in this round
 };
 struct TrCounts {             // everything counted in one iteration (integers)
     unsigned int rbg[28], rreal[28], treal[3], tbg[3], ngenes, zero_bg, zero_real, _pad;
@@ -163,10 +192,13 @@ __device__ inline void tr_count_upstream(const uint8_t* __restrict__ d, int L, i
 }
 // background of one iteration: start types (all starts) and the RBS bin each non-edge start would pick
 __global__ void __launch_bounds__(256)
-k_ts_background(int n, const uint8_t* __restrict__ type, const uint8_t* __restrict__ edge, const uint8_t* __restrict__ rbs,
-                const TrWeights* __restrict__ w, TrCounts* __restrict__ cn, int count_types) {
+k_ts_background(int n, const int32_t* __restrict__ gof, const uint8_t* __restrict__ type, const uint8_t* __restrict__ edge,
+                const uint8_t* __restrict__ rbs, const TrWeights* __restrict__ w_all, TrCounts* __restrict__ cn_all, int count_types) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n || type[i] == PGA_T_STOP) return;
+    const TrWeights* __restrict__ w = w_all + gof[i];
+    TrCounts* __restrict__ cn = cn_all + gof[i];
+    if (w->skip) return;
     if (count_types) atomicAdd(&cn->tbg[type[i]], 1u);
     if (edge[i]) return;
     atomicAdd(&cn->rbg[tr_pick_rbs(w->rbs_wt, rbs[2 * i], rbs[2 * i + 1])], 1u);
@@ -176,19 +208,26 @@ k_ts_background(int n, const uint8_t* __restrict__ type, const uint8_t* __restri
 // the highest index on the forward strand, the lowest on the reverse strand.
 template <bool SD>
 __global__ void __launch_bounds__(256)
-k_ts_best(int n, const int32_t* __restrict__ ndx, const int32_t* __restrict__ stop_val, const uint8_t* __restrict__ type,
-          const int8_t* __restrict__ strand, const uint8_t* __restrict__ edge, const double* __restrict__ cscore,
-          const uint8_t* __restrict__ rbs, const double* __restrict__ mot_score, const uint8_t* __restrict__ d, int L,
-          const TrWeights* __restrict__ w, TrCounts* __restrict__ cn, int32_t* __restrict__ best_of_stop) {
+k_ts_best(int n_all, const int32_t* __restrict__ gof, const TrGenome* __restrict__ gs, const int32_t* __restrict__ ndx,
+          const int32_t* __restrict__ stop_val, const uint8_t* __restrict__ type, const int8_t* __restrict__ strand,
+          const uint8_t* __restrict__ edge, const double* __restrict__ cscore, const uint8_t* __restrict__ rbs,
+          const double* __restrict__ mot_score, const uint8_t* __restrict__ dig, const TrWeights* __restrict__ w_all,
+          TrCounts* __restrict__ cn_all, int32_t* __restrict__ best_of_stop) {
     const int s = blockIdx.x * blockDim.x + threadIdx.x;
-    if (s >= n) return;
+    if (s >= n_all) return;
     if (best_of_stop) best_of_stop[s] = -1;
     if (type[s] != PGA_T_STOP) return;
+    const int gi = gof[s];
+    const TrWeights* __restrict__ w = w_all + gi;
+    TrCounts* __restrict__ cn = cn_all + gi;
+    if (w->skip) return;
+    const int lo = gs[gi].n0, n = gs[gi].n1, L = gs[gi].len;
+    const uint8_t* __restrict__ d = dig + gs[gi].base;
     const int st = strand[s], ph = ndx[s] % 3, sv = stop_val[s];
     const double wt = w->st_wt;
     double best = 0.0; int bndx = -1, brbs = 0;
     const int step = st == 1 ? -1 : 1;
-    for (int j = s + step; j >= 0 && j < n; j += step) {
+    for (int j = s + step; j >= lo && j < n; j += step) {
         if (st == 1 ? ndx[j] <= sv : ndx[j] >= sv) break;            // past the other end of the ORF
         if (strand[j] != st || ndx[j] % 3 != ph) continue;
         if (type[j] == PGA_T_STOP) break;                             // the neighbouring stop of this frame (defensive: sv marks it)
@@ -215,11 +254,18 @@ __device__ inline int tr_spacer_index(int j, int start, int i) {
 }
 // ref: lib.pyx:1556-1616 (Node._find_best_upstream_motif) with the training stages
 __global__ void __launch_bounds__(256)
-k_mot_best(int n, const int32_t* __restrict__ ndx, const uint8_t* __restrict__ type, const int8_t* __restrict__ strand,
-           const uint8_t* __restrict__ edge, const uint8_t* __restrict__ d, int L, const double* __restrict__ mot_wt /* [4][4][4096] */,
-           const TrWeights* __restrict__ w, TrMotifs m) {
+k_mot_best(int n, const int32_t* __restrict__ gof, const TrGenome* __restrict__ gs, const int32_t* __restrict__ ndx,
+           const uint8_t* __restrict__ type, const int8_t* __restrict__ strand, const uint8_t* __restrict__ edge,
+           const uint8_t* __restrict__ dig, const double* __restrict__ mot_wt_all /* [genome][4][4][4096] */,
+           const TrWeights* __restrict__ w_all, TrMotifs m) {
     const int i0 = blockIdx.x * blockDim.x + threadIdx.x;
     if (i0 >= n || type[i0] == PGA_T_STOP || edge[i0]) return;
+    const int gi = gof[i0];
+    const TrWeights* __restrict__ w = w_all + gi;
+    if (w->skip) return;
+    const uint8_t* __restrict__ d = dig + gs[gi].base;
+    const int L = gs[gi].len;
+    const double* __restrict__ mot_wt = mot_wt_all + (size_t)gi * 4 * 4 * 4096;
     const int st = strand[i0], start = st == 1 ? ndx[i0] : L - 1 - ndx[i0];
     int bsp = 0, bsi = 0, blen = 0, bndx = 0; double bsc = -100.0;
     for (int i = 3; i >= 0; i--) {
@@ -262,15 +308,21 @@ __device__ inline void tr_update_motif_counts(int i0, const int32_t* __restrict_
 }
 // background: every non-edge start; real: the start chosen for each confident ORF (best_of_stop from k_ts_best<false>)
 __global__ void __launch_bounds__(256)
-k_mot_counts(int n, const int32_t* __restrict__ ndx, const uint8_t* __restrict__ type, const int8_t* __restrict__ strand,
-             const uint8_t* __restrict__ edge, const uint8_t* __restrict__ d, int L, TrMotifs m, const TrWeights* __restrict__ w,
-             const int32_t* __restrict__ best_of_stop, unsigned int* __restrict__ cnt, unsigned int* __restrict__ zero) {
+k_mot_counts(int n, const int32_t* __restrict__ gof, const TrGenome* __restrict__ gs, const int32_t* __restrict__ ndx,
+             const uint8_t* __restrict__ type, const int8_t* __restrict__ strand, const uint8_t* __restrict__ edge,
+             const uint8_t* __restrict__ dig, TrMotifs m, const TrWeights* __restrict__ w_all, const int32_t* __restrict__ best_of_stop,
+             unsigned int* __restrict__ cnt_all /* [genome][2][4][4][4096] */, unsigned int* __restrict__ zero_all /* [genome][2] */) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     int node = i;
     if (best_of_stop) { node = best_of_stop[i]; if (node < 0) return; }
     if (type[node] == PGA_T_STOP || edge[node] == 1) return;
-    tr_update_motif_counts(node, ndx, strand, d, L, m, w->stage, cnt, zero);
+    const int gi = gof[node], real = best_of_stop != nullptr;
+    const TrWeights* __restrict__ w = w_all + gi;
+    if (w->skip) return;
+    const size_t MT = (size_t)4 * 4 * 4096;
+    tr_update_motif_counts(node, ndx, strand, dig + gs[gi].base, gs[gi].len, m, w->stage, cnt_all + (2 * (size_t)gi + real) * MT,
+                           zero_all + 2 * gi + real);
 }
 
 // stages of the driver, for step-by-step validation against the oracle (PGA_TRAIN_* in the header)
@@ -362,233 +414,345 @@ void tr_build_coverage_map(const unsigned int* real /* [4][4][4096] */, int* goo
 
 }  // namespace
 
-static int find_impl(pga_ctx* c, const pga_batch* batch, const pga_params* pp, const int stage, const int tt_override, pga_result** out);
+static int find_impl(pga_ctx* c, const pga_batch* batch, const pga_params* pp, const int stage, const int tt_override, pga_result** out,
+                     const int32_t* model_of_contig, const int32_t* tt_of_contig);
 
-// ref: lib.pyx:5236-5279 (GeneFinder._train) for ONE sequence (the host layer joins several with the reference's spacer)
-static int train_body(pga_ctx* c, const pga_batch* batch, const pga_params* pp, int tt, double start_weight, int force_nonsd,
-                      int upto, pga_training* t, bool& models_replaced) {
-    if (!c || !batch || !pp || !t || batch->ctx != c || batch->n != 1) { if (c) c->err = "pga_train: needs a batch of exactly one sequence"; return PGA_EINVAL; }
-    memset(t, 0, sizeof *t);
-    t->trans_table = tt; t->st_wt = start_weight; t->uses_sd = 1;
+// ref: lib.pyx:5236-5279 (GeneFinder._train) for every sequence of the batch at once: sequence g is genome g (the host layer
+// joins the contigs of a genome with the reference's spacer), trained with tts[g], sws[g], fns[g].  One device pass per stage or
+// round for all genomes; status[g] is PGA_OK or what a single-genome training would have returned.
+static int train_body(pga_ctx* c, const pga_batch* batch, const pga_params* pp, const int32_t* tts, const double* sws, const int32_t* fns,
+                      int upto, pga_training* out, int32_t* status, bool& models_replaced) {
+    if (!c || !batch || !pp || !out || !status || !tts || !sws || !fns || batch->ctx != c || batch->n < 1) {
+        if (c) c->err = "pga_train_batch: bad arguments";
+        return PGA_EINVAL;
+    }
+    const int G = batch->n;
+    {
+        std::vector<int32_t> seen;
+        for (int g = 0; g < G; g++) if (std::find(seen.begin(), seen.end(), tts[g]) == seen.end()) seen.push_back(tts[g]);
+        if (seen.size() > 4) { c->err = "pga_train_batch: more than 4 distinct translation tables in one call"; return PGA_EINVAL; }
+    }
+    for (int g = 0; g < G; g++) {
+        pga_training* t = &out[g];
+        memset(t, 0, sizeof *t);
+        t->trans_table = tts[g]; t->st_wt = sws[g]; t->uses_sd = 1;
+        status[g] = PGA_OK;
+    }
     pga_params P = *pp; P.meta = 0; P.want_nodes = 1;
     hipStream_t st = c->stream;
-    // ---- nodes (ref: lib.pyx:5252-5257): extraction + sort through the stage-level path; its device arrays stay
+    // ---- nodes (ref: lib.pyx:5252-5257): extraction + sort of every genome under its own table, through the stage-level path
     pga_result* r1 = nullptr;
-    if (int rc = find_impl(c, batch, &P, PGA_STAGE_EXTRACT, tt, &r1)) return rc;
+    if (int rc = find_impl(c, batch, &P, PGA_STAGE_EXTRACT, tts[0], &r1, nullptr, tts)) return rc;
     struct Free { pga_result* r; ~Free() { if (r) pga_result_free(r); } } fr1{r1};
-    t->gc = r1->contigs[0].gc;
-    const int n = r1->nodes[0].n, L = batch->ct[0].len;
-    if (n == 0) { c->err = "pga_train: no start / stop node in the sequence"; return PGA_EINVAL; }
-    const pga_nodes& H = r1->nodes[0];                 // host copies of the topology
     FinderState* f = c->finder;
-    const LastRun lr = f->last;
-    const GroupArrays& ga = lr.ga;
+    const uint8_t* d_dig = f->last.d_dig;            // the batch's digits, genome g at ct[g].base
+    std::vector<TrGenome> gsv((size_t)G);
+    int N = 0, maxL = 0;
+    for (int g = 0; g < G; g++) {
+        out[g].gc = r1->contigs[g].gc;
+        const int n = r1->nodes[g].n;
+        gsv[g] = TrGenome{batch->ct[g].base, batch->ct[g].len, N, N + n, 0};
+        N += n; maxL = std::max(maxL, batch->ct[g].len);
+        if (n == 0) { status[g] = PGA_EINVAL; c->err = "pga_train_batch: genome " + std::to_string(g) + " has no start / stop node"; }
+    }
+    if (N == 0) return PGA_OK;
+    // the genomes' nodes back to back (host copies of the topology: the path walk reads them)
+    std::vector<int32_t> h_ndx((size_t)N), h_sv((size_t)N), h_gof((size_t)N);
+    std::vector<uint8_t> h_type((size_t)N), h_edge((size_t)N);
+    std::vector<int8_t> h_strand((size_t)N);
+    for (int g = 0; g < G; g++) {
+        const pga_nodes& H = r1->nodes[g];
+        const size_t o = (size_t)gsv[g].n0, n = (size_t)H.n;
+        if (n == 0) continue;
+        memcpy(&h_ndx[o], H.ndx, 4 * n); memcpy(&h_sv[o], H.stop_val, 4 * n);
+        memcpy(&h_type[o], H.type, n); memcpy(&h_edge[o], H.edge, n); memcpy(&h_strand[o], H.strand, n);
+        std::fill(h_gof.begin() + o, h_gof.begin() + o + n, g);
+    }
+    DEVBUF(d_gs, TrGenome, "tr_genomes", G);
+    DEVBUF(d_ndx, int32_t, "tr_ndx", N) DEVBUF(d_sv, int32_t, "tr_stop_val", N) DEVBUF(d_gof, int32_t, "tr_genome_of", N)
+    DEVBUF(d_type, uint8_t, "tr_type", N) DEVBUF(d_edge, uint8_t, "tr_edge", N) DEVBUF(d_strand, int8_t, "tr_strand", N)
+    HT(c, hipMemcpyAsync(d_gs, gsv.data(), sizeof(TrGenome) * G, hipMemcpyHostToDevice, st));
+    HT(c, hipMemcpyAsync(d_ndx, h_ndx.data(), 4 * (size_t)N, hipMemcpyHostToDevice, st));
+    HT(c, hipMemcpyAsync(d_sv, h_sv.data(), 4 * (size_t)N, hipMemcpyHostToDevice, st));
+    HT(c, hipMemcpyAsync(d_gof, h_gof.data(), 4 * (size_t)N, hipMemcpyHostToDevice, st));
+    HT(c, hipMemcpyAsync(d_type, h_type.data(), (size_t)N, hipMemcpyHostToDevice, st));
+    HT(c, hipMemcpyAsync(d_edge, h_edge.data(), (size_t)N, hipMemcpyHostToDevice, st));
+    HT(c, hipMemcpyAsync(d_strand, h_strand.data(), (size_t)N, hipMemcpyHostToDevice, st));
+    // host work of different genomes side by side: at most 16 threads, whatever the machine reports
+    const int n_threads = std::max(1, std::min({16, G, (int)std::max(1u, std::thread::hardware_concurrency())}));
+    auto per_genome = [&](const std::function<void(int)>& fn) {
+        std::atomic<int> next(0);
+        std::function<void()> job = [&]() { for (int g; (g = next.fetch_add(1)) < G;) fn(g); };
+        if (n_threads == 1) job(); else f->pool.run(job, n_threads);
+    };
     // ---- GC frame bias (ref: lib.pyx:5259-5261)
-    DEVBUF(d_gp, int8_t, "tr_gp", L + 4);
-    DEVBUF(d_gcs, double, "tr_gc_score", 3 * (size_t)n + 3);
-    DEVBUF(d_gcbias, uint8_t, "tr_gc_bias", n + 1);
-    DEVBUF(d_bias, double, "tr_bias", 4);
-    DEVBUF(d_gcb, double, "tr_gcb", n + 1);
-    DEVBUF(d_star, int32_t, "tr_star", 3 * (size_t)n + 3);
-    const int nb = (n + 255) / 256;
-    hipLaunchKernelGGL(k_gc_frame, dim3((L / 3 + 256) / 256), dim3(256), 0, st, lr.d_dig, L, d_gp);
-    hipLaunchKernelGGL(k_gc_bias, dim3(nb), dim3(256), 0, st, n, ga.ndx, ga.stop_val, ga.type, ga.strand, d_gp, d_gcs, d_gcbias);
-    hipLaunchKernelGGL(k_bias_sum, dim3(1), dim3(1), 0, st, n, ga.ndx, ga.stop_val, ga.type, d_gcs, d_gcbias, d_bias);
-    HT(c, hipMemcpyAsync(t->bias, d_bias, sizeof(double) * 3, hipMemcpyDeviceToHost, st));
+    DEVBUF(d_gp, int8_t, "tr_gp", batch->total + 4);
+    DEVBUF(d_gcs, double, "tr_gc_score", 3 * (size_t)N + 3);
+    DEVBUF(d_gcbias, uint8_t, "tr_gc_bias", N + 1);
+    DEVBUF(d_bias, double, "tr_bias", 4 * (size_t)G);
+    DEVBUF(d_gcb, double, "tr_gcb", N + 1);
+    DEVBUF(d_star, int32_t, "tr_star", 3 * (size_t)N + 3);
+    const int nb = (N + 255) / 256;
+    hipLaunchKernelGGL(k_gc_frame, dim3((maxL / 3 + 256) / 256, G), dim3(256), 0, st, d_dig, d_gs, d_gp);
+    hipLaunchKernelGGL(k_gc_bias, dim3(nb), dim3(256), 0, st, N, d_gof, d_gs, d_ndx, d_sv, d_type, d_strand, d_gp, d_gcs, d_gcbias);
+    hipLaunchKernelGGL(k_bias_sum, dim3((G + 63) / 64), dim3(64), 0, st, G, d_gs, d_ndx, d_sv, d_type, d_gcs, d_gcbias, d_bias);
+    std::vector<double> hb(4 * (size_t)G);
+    HT(c, hipMemcpyAsync(hb.data(), d_bias, sizeof(double) * 4 * G, hipMemcpyDeviceToHost, st));
     HT(c, hipGetLastError());
     HT(c, hipStreamSynchronize(st));
+    for (int g = 0; g < G; g++) memcpy(out[g].bias, &hb[4 * (size_t)g], sizeof out[g].bias);
     if (upto == TR_BIAS) return PGA_OK;
-    // ---- training pass of the dynamic programme (ref: lib.pyx:5263-5267)
-    hipLaunchKernelGGL(k_gcb, dim3(nb), dim3(256), 0, st, n, d_gcs, d_bias, d_gcb);
-    hipLaunchKernelGGL(k_ovl_starts0, dim3(nb), dim3(256), 0, st, n, ga.ndx, ga.stop_val, ga.type, ga.strand, ga.edge0, P.max_overlap, d_star);
+    // ---- training pass of the dynamic programme (ref: lib.pyx:5263-5267): one chain per genome, one launch
+    hipLaunchKernelGGL(k_gcb, dim3(nb), dim3(256), 0, st, N, d_gof, d_gcs, d_bias, d_gcb);
+    hipLaunchKernelGGL(k_ovl_starts0, dim3(nb), dim3(256), 0, st, N, d_gof, d_gs, d_ndx, d_sv, d_type, d_strand, d_edge, P.max_overlap, d_star);
     DpBuffers dp;
     {
-        DEVBUF(b0, DpSrc, "dp_src", n + 1) DEVBUF(b1, DpTgt, "dp_tgt", n + 1) DEVBUF(b2, double, "dp_score", n + 1) DEVBUF(b3, int32_t, "dp_traceb", n + 1)
-        DEVBUF(b4, int32_t, "dp_tbn", n + 1) DEVBUF(b5, int8_t, "dp_ov", n + 1) DEVBUF(b6, int32_t, "dp_maxidx", 2) DEVBUF(b7, double, "dp_maxscore", 2)
-        DEVBUF(b8, int32_t, "dp_ipath", 2)
+        DEVBUF(b0, DpSrc, "dp_src", N + 1) DEVBUF(b1, DpTgt, "dp_tgt", N + 1) DEVBUF(b2, double, "dp_score", N + 1) DEVBUF(b3, int32_t, "dp_traceb", N + 1)
+        DEVBUF(b4, int32_t, "dp_tbn", N + 1) DEVBUF(b5, int8_t, "dp_ov", N + 1) DEVBUF(b6, int32_t, "dp_maxidx", G + 1) DEVBUF(b7, double, "dp_maxscore", G + 1)
+        DEVBUF(b8, int32_t, "dp_ipath", G + 1)
         dp = DpBuffers{b0, b1, b2, b3, b4, b5, b6, b7, b8, nullptr, {nullptr, nullptr, nullptr}, nullptr, nullptr, nullptr};
     }
-    DEVBUF(d_chain, ChainDesc, "tr_chain", 2);
-    DEVBUF(d_mc, ModelConst, "tr_mc", 2);
-    ChainDesc ch{0, 0, n, 0, 0, 1};
-    ModelConst mc; pga_fill_model_const(&mc, start_weight);
-    HT(c, hipMemcpyAsync(d_chain, &ch, sizeof ch, hipMemcpyHostToDevice, st));
-    HT(c, hipMemcpyAsync(d_mc, &mc, sizeof mc, hipMemcpyHostToDevice, st));
-    NodeArrays na{ga.ndx, ga.stop_val, ga.type, ga.strand, d_gcb, d_gcb, d_gcb, d_gcb, d_star, d_gcb};   // scores are not read when final = 0
-    pga_launch_dp_prepare(d_chain, 1, 0, n, na, d_mc, dp, st, 0);
-    pga_launch_dp(d_chain, 1, d_mc, dp, 0, st);
-    std::vector<int32_t> traceb((size_t)n), tracef((size_t)n, -1), star((size_t)3 * n), path((size_t)n + 1);
-    std::vector<int8_t> ovm((size_t)n);
-    std::vector<uint8_t> elim((size_t)n, 0);
-    int32_t mx = -1;
-    HT(c, hipMemcpyAsync(traceb.data(), dp.traceb, sizeof(int32_t) * n, hipMemcpyDeviceToHost, st));
-    HT(c, hipMemcpyAsync(ovm.data(), dp.ov_mark, n, hipMemcpyDeviceToHost, st));
-    HT(c, hipMemcpyAsync(star.data(), d_star, sizeof(int32_t) * 3 * n, hipMemcpyDeviceToHost, st));
-    HT(c, hipMemcpyAsync(&mx, dp.max_index, 4, hipMemcpyDeviceToHost, st));
+    DEVBUF(d_chain, ChainDesc, "tr_chain", G);
+    DEVBUF(d_mc, ModelConst, "tr_mc", G);
+    std::vector<ChainDesc> chv;
+    std::vector<ModelConst> mcv((size_t)G);
+    for (int g = 0; g < G; g++) {
+        ChainDesc ch{gsv[g].n0, gsv[g].n0, gsv[g].n1 - gsv[g].n0, g, g, 1};
+        chv.push_back(ch);
+        pga_fill_model_const(&mcv[g], sws[g]);
+    }
+    HT(c, hipMemcpyAsync(d_chain, chv.data(), sizeof(ChainDesc) * G, hipMemcpyHostToDevice, st));
+    HT(c, hipMemcpyAsync(d_mc, mcv.data(), sizeof(ModelConst) * G, hipMemcpyHostToDevice, st));
+    NodeArrays na{d_ndx, d_sv, d_type, d_strand, d_gcb, d_gcb, d_gcb, d_gcb, d_star, d_gcb};   // scores are not read when final = 0
+    pga_launch_dp_prepare(d_chain, G, 0, N, na, d_mc, dp, st, 0);
+    pga_launch_dp(d_chain, G, d_mc, dp, 0, st);
+    std::vector<int32_t> traceb((size_t)N), tracef((size_t)N, -1), star((size_t)3 * N), path((size_t)N + 1), mx((size_t)G, -1);
+    std::vector<int8_t> ovm((size_t)N);
+    std::vector<uint8_t> elim((size_t)N, 0);
+    HT(c, hipMemcpyAsync(traceb.data(), dp.traceb, sizeof(int32_t) * N, hipMemcpyDeviceToHost, st));
+    HT(c, hipMemcpyAsync(ovm.data(), dp.ov_mark, N, hipMemcpyDeviceToHost, st));
+    HT(c, hipMemcpyAsync(star.data(), d_star, sizeof(int32_t) * 3 * N, hipMemcpyDeviceToHost, st));
+    HT(c, hipMemcpyAsync(mx.data(), dp.max_index, 4 * (size_t)G, hipMemcpyDeviceToHost, st));
     HT(c, hipGetLastError());
     HT(c, hipStreamSynchronize(st));
-    // ---- the genes of the best path (ref: lib.pyx:1253-1311 untangling; 4299-4334 walk from the path's end)
-    std::vector<TrGene> genes;
-    if (mx >= 0) {
-        NodeView v{n, H.ndx, H.stop_val, H.type, H.strand, H.edge, nullptr, nullptr, nullptr, nullptr, nullptr, star.data(), traceb.data(),
-                   tracef.data(), ovm.data(), nullptr, elim.data()};
-        untangle(v, mx, path.data());
-        const int ipath = traceb[mx] == -1 ? -1 : mx;
+    // ---- the genes of every genome's best path (ref: lib.pyx:1253-1311 untangling; 4299-4334 walk from the path's end)
+    std::vector<std::vector<TrGene>> ggenes((size_t)G);
+    per_genome([&](int g) {
+        const int o = gsv[g].n0, n = gsv[g].n1 - o, L = gsv[g].len;
+        if (n == 0 || mx[g] < 0) return;
+        NodeView v{n, &h_ndx[o], &h_sv[o], &h_type[o], &h_strand[o], &h_edge[o], nullptr, nullptr, nullptr, nullptr, nullptr,
+                   &star[3 * (size_t)o], &traceb[o], &tracef[o], &ovm[o], nullptr, &elim[o]};
+        untangle(v, mx[g], &path[o]);
+        const int* tb = &traceb[o];
+        const int ipath = tb[mx[g]] == -1 ? -1 : mx[g];
         int in_gene = 0, left = -1, right = -1;
-        for (int p = ipath; p != -1; p = traceb[p]) {
-            if (H.strand[p] == 1) {
-                if (H.type[p] == PGA_T_STOP) { in_gene = 1; right = H.ndx[p] + 2; }
-                else if (in_gene == 1) { left = H.ndx[p]; genes.push_back(TrGene{left, right, 1}); in_gene = 0; }
+        for (int p = ipath; p != -1; p = tb[p]) {
+            const int q = o + p;
+            if (h_strand[q] == 1) {
+                if (h_type[q] == PGA_T_STOP) { in_gene = 1; right = h_ndx[q] + 2; }
+                else if (in_gene == 1) { left = h_ndx[q]; ggenes[g].push_back(TrGene{left, right, 1, g}); in_gene = 0; }
             } else {
-                if (H.type[p] != PGA_T_STOP) { in_gene = -1; left = L - H.ndx[p] - 1; }
-                else if (in_gene == -1) { right = L - H.ndx[p] + 1; genes.push_back(TrGene{left, right, -1}); in_gene = 0; }
+                if (h_type[q] != PGA_T_STOP) { in_gene = -1; left = L - h_ndx[q] - 1; }
+                else if (in_gene == -1) { right = L - h_ndx[q] + 1; ggenes[g].push_back(TrGene{left, right, -1, g}); in_gene = 0; }
             }
         }
-    }
-    // ---- hexamer statistics (ref: lib.pyx:5269, 4284-4358)
-    DEVBUF(d_cnt, unsigned int, "tr_hex", 2 * 4096);
+    });
+    std::vector<TrGene> genes;
+    for (auto& v : ggenes) genes.insert(genes.end(), v.begin(), v.end());
+    // ---- hexamer statistics (ref: lib.pyx:5269, 4284-4358), [genome][background, genes][4096]
+    DEVBUF(d_cnt, unsigned int, "tr_hex", 8192 * (size_t)G);
     DEVBUF(d_genes, TrGene, "tr_genes", genes.size() + 1);
-    HT(c, hipMemsetAsync(d_cnt, 0, sizeof(unsigned int) * 2 * 4096, st));
+    HT(c, hipMemsetAsync(d_cnt, 0, sizeof(unsigned int) * 8192 * (size_t)G, st));
     if (!genes.empty()) HT(c, hipMemcpyAsync(d_genes, genes.data(), sizeof(TrGene) * genes.size(), hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(k_hexamer_bg, dim3(1024), dim3(256), 0, st, lr.d_dig, L, d_cnt);
-    if (!genes.empty()) hipLaunchKernelGGL(k_hexamer_genes, dim3((unsigned)genes.size()), dim3(64), 0, st, lr.d_dig, L, d_genes, (int)genes.size(), d_cnt + 4096);
-    std::vector<unsigned int> cnt(2 * 4096);
-    HT(c, hipMemcpyAsync(cnt.data(), d_cnt, sizeof(unsigned int) * 2 * 4096, hipMemcpyDeviceToHost, st));
+    hipLaunchKernelGGL(k_hexamer_bg, dim3(std::max(8, 1024 / G), G), dim3(256), 0, st, d_dig, d_gs, d_cnt);
+    if (!genes.empty()) hipLaunchKernelGGL(k_hexamer_genes, dim3((unsigned)genes.size()), dim3(64), 0, st, d_dig, d_gs, d_genes, (int)genes.size(), d_cnt);
+    std::vector<unsigned int> cnt(8192 * (size_t)G);
+    HT(c, hipMemcpyAsync(cnt.data(), d_cnt, sizeof(unsigned int) * 8192 * (size_t)G, hipMemcpyDeviceToHost, st));
     HT(c, hipGetLastError());
     HT(c, hipStreamSynchronize(st));
-    tr_gene_dc(cnt.data(), cnt.data() + 4096, t);
+    per_genome([&](int g) { tr_gene_dc(&cnt[8192 * (size_t)g], &cnt[8192 * (size_t)g + 4096], &out[g]); });
     if (upto == TR_DICODON) return PGA_OK;
-    // ---- coding scores and RBS bins under the new statistics (ref: lib.pyx:5271-5273): the scoring stage of the path
+    // ---- coding scores and RBS bins under the new statistics (ref: lib.pyx:5271-5273): the scoring stage of the path, every
+    //      genome under its own half-trained model
     {
-        const pga_training* tp = t;
+        std::vector<const pga_training*> tp((size_t)G);
+        for (int g = 0; g < G; g++) tp[g] = &out[g];
         models_replaced = true;
-        if (int rc = pga_set_models(c, &tp, 1)) return rc;
+        if (int rc = pga_set_models(c, tp.data(), G)) return rc;
     }
+    std::vector<int32_t> moc((size_t)G);
+    for (int g = 0; g < G; g++) moc[g] = g;
     pga_result* r2 = nullptr;
-    if (int rc = find_impl(c, batch, &P, PGA_STAGE_SCORE, tt, &r2)) return rc;
+    if (int rc = find_impl(c, batch, &P, PGA_STAGE_SCORE, tts[0], &r2, moc.data(), nullptr)) return rc;
     Free fr2{r2};
-    if (r2->nodes[0].n != n) { c->err = "pga_train: node count changed between the stages"; return PGA_EDEVICE; }
     f = c->finder;
-    const LastRun ls = f->last;                       // topology (again) + chain arrays of the scoring stage
-    const GroupArrays& gs = ls.ga;
-    DEVBUF(d_w, TrWeights, "tr_weights", 2);
-    DEVBUF(d_cn, TrCounts, "tr_counts", 2);
-    TrWeights w; memset(&w, 0, sizeof w);
-    w.st_wt = t->st_wt; w.sthresh = 35.0; w.uses_sd = 1;
-    TrCounts cn;
-    double tbg[3] = {0, 0, 0};
-    memset(t->type_wt, 0, sizeof t->type_wt); memset(t->rbs_wt, 0, sizeof t->rbs_wt); memset(t->ups_comp, 0, sizeof t->ups_comp);
+    d_dig = f->last.d_dig;
+    std::vector<double> h_cs((size_t)N);
+    std::vector<uint8_t> h_rbs(2 * (size_t)N);
+    for (int g = 0; g < G; g++) {
+        const pga_nodes& H = r2->nodes[g];
+        const size_t o = (size_t)gsv[g].n0, n = (size_t)(gsv[g].n1 - gsv[g].n0);
+        if (H.n != (int)n) { c->err = "pga_train_batch: node count changed between the stages"; return PGA_EDEVICE; }
+        if (n == 0) continue;
+        memcpy(&h_cs[o], H.cscore, 8 * n); memcpy(&h_rbs[2 * o], H.rbs, 2 * n);
+    }
+    DEVBUF(d_cs, double, "tr_cscore", N) DEVBUF(d_rbs, uint8_t, "tr_rbs", 2 * (size_t)N)
+    HT(c, hipMemcpyAsync(d_cs, h_cs.data(), 8 * (size_t)N, hipMemcpyHostToDevice, st));
+    HT(c, hipMemcpyAsync(d_rbs, h_rbs.data(), 2 * (size_t)N, hipMemcpyHostToDevice, st));
+    DEVBUF(d_w, TrWeights, "tr_weights", G);
+    DEVBUF(d_cn, TrCounts, "tr_counts", G);
+    std::vector<TrWeights> w((size_t)G);
+    std::vector<TrCounts> cn((size_t)G);
+    std::vector<double> tbg(3 * (size_t)G, 0.0);
+    for (int g = 0; g < G; g++) {
+        memset(&w[g], 0, sizeof w[g]);
+        w[g].st_wt = out[g].st_wt; w[g].sthresh = 35.0; w[g].uses_sd = 1; w[g].skip = status[g] != PGA_OK;
+        memset(out[g].type_wt, 0, sizeof out[g].type_wt); memset(out[g].rbs_wt, 0, sizeof out[g].rbs_wt); memset(out[g].ups_comp, 0, sizeof out[g].ups_comp);
+    }
     // ---- Shine-Dalgarno start training: 10 rounds (ref: lib.pyx:4391-4599)
     for (int it = 0; it < 10; it++) {
-        memcpy(w.rbs_wt, t->rbs_wt, sizeof w.rbs_wt); memcpy(w.type_wt, t->type_wt, sizeof w.type_wt);
-        w.last_iter = it == 9;
-        HT(c, hipMemcpyAsync(d_w, &w, sizeof w, hipMemcpyHostToDevice, st));
-        HT(c, hipMemsetAsync(d_cn, 0, sizeof(TrCounts), st));
-        hipLaunchKernelGGL(k_ts_background, dim3(nb), dim3(256), 0, st, n, gs.type, gs.edge0, ls.ca.rbs, d_w, d_cn, 1);
-        hipLaunchKernelGGL(k_ts_best<true>, dim3(nb), dim3(256), 0, st, n, gs.ndx, gs.stop_val, gs.type, gs.strand, gs.edge0, ls.ca.cscore,
-                           ls.ca.rbs, (const double*)nullptr, ls.d_dig, L, d_w, d_cn, (int32_t*)nullptr);
-        HT(c, hipMemcpyAsync(&cn, d_cn, sizeof cn, hipMemcpyDeviceToHost, st));
+        for (int g = 0; g < G; g++) {
+            memcpy(w[g].rbs_wt, out[g].rbs_wt, sizeof w[g].rbs_wt); memcpy(w[g].type_wt, out[g].type_wt, sizeof w[g].type_wt);
+            w[g].last_iter = it == 9;
+        }
+        HT(c, hipMemcpyAsync(d_w, w.data(), sizeof(TrWeights) * G, hipMemcpyHostToDevice, st));
+        HT(c, hipMemsetAsync(d_cn, 0, sizeof(TrCounts) * G, st));
+        hipLaunchKernelGGL(k_ts_background, dim3(nb), dim3(256), 0, st, N, d_gof, d_type, d_edge, d_rbs, d_w, d_cn, 1);
+        hipLaunchKernelGGL(k_ts_best<true>, dim3(nb), dim3(256), 0, st, N, d_gof, d_gs, d_ndx, d_sv, d_type, d_strand, d_edge, d_cs,
+                           d_rbs, (const double*)nullptr, d_dig, d_w, d_cn, (int32_t*)nullptr);
+        HT(c, hipMemcpyAsync(cn.data(), d_cn, sizeof(TrCounts) * G, hipMemcpyDeviceToHost, st));
         HT(c, hipGetLastError());
         HT(c, hipStreamSynchronize(st));
-        if (it == 0) {
-            double sum = 0.0;
-            for (int j = 0; j < 3; j++) { tbg[j] = (double)cn.tbg[j]; sum += tbg[j]; }
-            for (int j = 0; j < 3; j++) tbg[j] /= sum;
+        for (int g = 0; g < G; g++) {
+            if (w[g].skip) continue;
+            pga_training* t = &out[g];
+            const int n = gsv[g].n1 - gsv[g].n0;
+            double* tb = &tbg[3 * (size_t)g];
+            if (it == 0) {
+                double sum = 0.0;
+                for (int j = 0; j < 3; j++) { tb[j] = (double)cn[g].tbg[j]; sum += tb[j]; }
+                for (int j = 0; j < 3; j++) tb[j] /= sum;
+            }
+            double rbg[28], sum = 0.0;
+            for (int j = 0; j < 28; j++) { rbg[j] = (double)cn[g].rbg[j]; sum += rbg[j]; }
+            for (int j = 0; j < 28; j++) rbg[j] /= sum;
+            tr_log_odds(cn[g].rreal, rbg, t->rbs_wt, 28);
+            sum = 0.0; for (int j = 0; j < 3; j++) sum += (double)cn[g].treal[j];
+            tr_log_odds(cn[g].treal, tb, t->type_wt, 3);
+            if (sum * 2000.0 <= n) w[g].sthresh /= 2.0;
         }
-        double rbg[28], sum = 0.0;
-        for (int j = 0; j < 28; j++) { rbg[j] = (double)cn.rbg[j]; sum += rbg[j]; }
-        for (int j = 0; j < 28; j++) rbg[j] /= sum;
-        tr_log_odds(cn.rreal, rbg, t->rbs_wt, 28);
-        sum = 0.0; for (int j = 0; j < 3; j++) sum += (double)cn.treal[j];
-        tr_log_odds(cn.treal, tbg, t->type_wt, 3);
-        if (sum * 2000.0 <= n) w.sthresh /= 2.0;
     }
-    tr_ups_to_log(cn.ups, t);
-    if (force_nonsd) t->uses_sd = 0; else tr_determine_sd_usage(t);
-    if (upto == TR_SD || t->uses_sd) return PGA_OK;
-    // ---- motif-based start training: 20 rounds in three stages (ref: lib.pyx:4601-4827)
+    std::vector<int> motif;                      // genomes that go on to the motif-based start training
+    for (int g = 0; g < G; g++) {
+        if (w[g].skip) continue;
+        pga_training* t = &out[g];
+        tr_ups_to_log(cn[g].ups, t);
+        if (fns[g]) t->uses_sd = 0; else tr_determine_sd_usage(t);
+        if (!t->uses_sd) motif.push_back(g);
+    }
+    if (upto == TR_SD || motif.empty()) return PGA_OK;
+    // ---- motif-based start training: 20 rounds in three stages (ref: lib.pyx:4601-4827); the SD genomes sit these out
     const size_t MT = (size_t)4 * 4 * 4096;
-    DEVBUF(d_motwt, double, "tr_mot_wt", MT);
-    DEVBUF(d_mcnt, unsigned int, "tr_mot_counts", 2 * MT + 8);
-    DEVBUF(d_best, int32_t, "tr_best_of_stop", n + 1);
+    DEVBUF(d_motwt, double, "tr_mot_wt", MT * G);
+    DEVBUF(d_mcnt, unsigned int, "tr_mot_counts", 2 * MT * G);
+    DEVBUF(d_zero, unsigned int, "tr_mot_zero", 2 * (size_t)G);
+    DEVBUF(d_best, int32_t, "tr_best_of_stop", N + 1);
     TrMotifs mot;
     {
-        DEVBUF(m0, int32_t, "tr_mot_ndx", n + 1) DEVBUF(m1, uint8_t, "tr_mot_len", n + 1) DEVBUF(m2, uint8_t, "tr_mot_spacer", n + 1)
-        DEVBUF(m3, uint8_t, "tr_mot_spacendx", n + 1) DEVBUF(m4, double, "tr_mot_score", n + 1)
+        DEVBUF(m0, int32_t, "tr_mot_ndx", N + 1) DEVBUF(m1, uint8_t, "tr_mot_len", N + 1) DEVBUF(m2, uint8_t, "tr_mot_spacer", N + 1)
+        DEVBUF(m3, uint8_t, "tr_mot_spacendx", N + 1) DEVBUF(m4, double, "tr_mot_score", N + 1)
         mot = TrMotifs{m0, m1, m2, m3, m4};
-        HT(c, hipMemsetAsync(m1, 0, (size_t)n + 1, st));
+        HT(c, hipMemsetAsync(m1, 0, (size_t)N + 1, st));
     }
-    std::vector<unsigned int> hc(2 * MT);
-    std::vector<double> mbg(MT), mreal(MT);
-    std::vector<int> mgood(MT, 0);
-    memset(t->ups_comp, 0, sizeof t->ups_comp);
-    memset(t->type_wt, 0, sizeof t->type_wt);
-    w.sthresh = 35.0; w.uses_sd = 0;
+    std::vector<unsigned int> hc(2 * MT * G), zeros(2 * (size_t)G);
+    for (int g = 0; g < G; g++) w[g].skip = 1;
+    for (int g : motif) {
+        memset(out[g].ups_comp, 0, sizeof out[g].ups_comp);
+        memset(out[g].type_wt, 0, sizeof out[g].type_wt);
+        w[g].sthresh = 35.0; w[g].uses_sd = 0; w[g].skip = 0;
+    }
+    struct MotifScratch { std::vector<double> mbg, mreal; std::vector<int> mgood; };
+    std::vector<MotifScratch> scratch((size_t)G);
+    for (int g : motif) { scratch[g].mbg.resize(MT); scratch[g].mreal.resize(MT); scratch[g].mgood.assign(MT, 0); }
+    const int NMOT = (int)motif.size();
     for (int it = 0; it < 20; it++) {
         const int stage = it < 4 ? 0 : (it < 12 ? 1 : 2);
-        memcpy(w.type_wt, t->type_wt, sizeof w.type_wt);
-        w.no_mot = t->no_mot; w.stage = stage; w.last_iter = it == 19;
-        HT(c, hipMemcpyAsync(d_w, &w, sizeof w, hipMemcpyHostToDevice, st));
-        HT(c, hipMemcpyAsync(d_motwt, &t->mot_wt[0][0][0], sizeof(double) * MT, hipMemcpyHostToDevice, st));
-        HT(c, hipMemsetAsync(d_cn, 0, sizeof(TrCounts), st));
-        HT(c, hipMemsetAsync(d_mcnt, 0, sizeof(unsigned int) * (2 * MT + 8), st));
-        unsigned int* d_zero = d_mcnt + 2 * MT;           // [0] background, [1] real
-        hipLaunchKernelGGL(k_mot_best, dim3(nb), dim3(256), 0, st, n, gs.ndx, gs.type, gs.strand, gs.edge0, ls.d_dig, L, d_motwt, d_w, mot);
-        hipLaunchKernelGGL(k_mot_counts, dim3(nb), dim3(256), 0, st, n, gs.ndx, gs.type, gs.strand, gs.edge0, ls.d_dig, L, mot, d_w,
+        for (int g : motif) {
+            memcpy(w[g].type_wt, out[g].type_wt, sizeof w[g].type_wt);
+            w[g].no_mot = out[g].no_mot; w[g].stage = stage; w[g].last_iter = it == 19;
+            HT(c, hipMemcpyAsync(d_motwt + MT * g, &out[g].mot_wt[0][0][0], sizeof(double) * MT, hipMemcpyHostToDevice, st));
+        }
+        HT(c, hipMemcpyAsync(d_w, w.data(), sizeof(TrWeights) * G, hipMemcpyHostToDevice, st));
+        HT(c, hipMemsetAsync(d_cn, 0, sizeof(TrCounts) * G, st));
+        HT(c, hipMemsetAsync(d_mcnt, 0, sizeof(unsigned int) * 2 * MT * G, st));
+        HT(c, hipMemsetAsync(d_zero, 0, sizeof(unsigned int) * 2 * G, st));
+        hipLaunchKernelGGL(k_mot_best, dim3(nb), dim3(256), 0, st, N, d_gof, d_gs, d_ndx, d_type, d_strand, d_edge, d_dig, d_motwt, d_w, mot);
+        hipLaunchKernelGGL(k_mot_counts, dim3(nb), dim3(256), 0, st, N, d_gof, d_gs, d_ndx, d_type, d_strand, d_edge, d_dig, mot, d_w,
                            (const int32_t*)nullptr, d_mcnt, d_zero);
-        hipLaunchKernelGGL(k_ts_best<false>, dim3(nb), dim3(256), 0, st, n, gs.ndx, gs.stop_val, gs.type, gs.strand, gs.edge0, ls.ca.cscore,
-                           ls.ca.rbs, mot.score, ls.d_dig, L, d_w, d_cn, d_best);
-        hipLaunchKernelGGL(k_mot_counts, dim3(nb), dim3(256), 0, st, n, gs.ndx, gs.type, gs.strand, gs.edge0, ls.d_dig, L, mot, d_w,
-                           d_best, d_mcnt + MT, d_zero + 1);
-        unsigned int zeros[2];
-        HT(c, hipMemcpyAsync(hc.data(), d_mcnt, sizeof(unsigned int) * 2 * MT, hipMemcpyDeviceToHost, st));
-        HT(c, hipMemcpyAsync(zeros, d_zero, sizeof zeros, hipMemcpyDeviceToHost, st));
-        HT(c, hipMemcpyAsync(&cn, d_cn, sizeof cn, hipMemcpyDeviceToHost, st));
+        hipLaunchKernelGGL(k_ts_best<false>, dim3(nb), dim3(256), 0, st, N, d_gof, d_gs, d_ndx, d_sv, d_type, d_strand, d_edge, d_cs,
+                           d_rbs, mot.score, d_dig, d_w, d_cn, d_best);
+        hipLaunchKernelGGL(k_mot_counts, dim3(nb), dim3(256), 0, st, N, d_gof, d_gs, d_ndx, d_type, d_strand, d_edge, d_dig, mot, d_w,
+                           d_best, d_mcnt, d_zero);
+        for (int g : motif) HT(c, hipMemcpyAsync(&hc[2 * MT * g], d_mcnt + 2 * MT * g, sizeof(unsigned int) * 2 * MT, hipMemcpyDeviceToHost, st));
+        HT(c, hipMemcpyAsync(zeros.data(), d_zero, sizeof(unsigned int) * 2 * G, hipMemcpyDeviceToHost, st));
+        HT(c, hipMemcpyAsync(cn.data(), d_cn, sizeof(TrCounts) * G, hipMemcpyDeviceToHost, st));
         HT(c, hipGetLastError());
         HT(c, hipStreamSynchronize(st));
-        // ---- the weights of the next round (host: sums of counts, libm log)
-        double zbg = (double)zeros[0], zreal = (double)zeros[1], sum = 0.0;
-        const double ngenes = (double)cn.ngenes;
-        for (size_t q = 0; q < MT; q++) { mbg[q] = (double)hc[q]; sum += mbg[q]; }
-        sum += zbg;
-        for (size_t q = 0; q < MT; q++) mbg[q] /= sum;
-        zbg /= sum;
-        if (stage < 2) tr_build_coverage_map(hc.data() + MT, mgood.data(), ngenes);
-        sum = 0.0;
-        for (size_t q = 0; q < MT; q++) { mreal[q] = (double)hc[MT + q]; sum += mreal[q]; }
-        sum += zreal;
-        if (sum == 0.0) {
-            memset(t->mot_wt, 0, sizeof t->mot_wt); t->no_mot = 0.0;
-        } else {
-            double* wt = &t->mot_wt[0][0][0];
-            for (size_t q = 0; q < MT; q++) {
-                if (mgood[q] == 0) { zreal += mreal[q]; zbg += mreal[q]; mreal[q] = 0.0; mbg[q] = 0.0; }
-                mreal[q] /= sum;
-                double v = mbg[q] != 0 ? log(mreal[q] / mbg[q]) : -4.0;
-                if (v > 4.0) v = 4.0; else if (v < -4.0) v = -4.0;
-                wt[q] = v;
+        // ---- the weights of the next round, genome by genome on the pool (host: sums of counts, libm log)
+        std::atomic<int> next(0);
+        std::function<void()> job = [&]() {
+            for (int k; (k = next.fetch_add(1)) < NMOT;) {
+                const int g = motif[k];
+                pga_training* t = &out[g];
+                const unsigned int* h = &hc[2 * MT * g];
+                std::vector<double>& mbg = scratch[g].mbg; std::vector<double>& mreal = scratch[g].mreal; std::vector<int>& mgood = scratch[g].mgood;
+                const int n = gsv[g].n1 - gsv[g].n0;
+                double zbg = (double)zeros[2 * g], zreal = (double)zeros[2 * g + 1], sum = 0.0;
+                const double ngenes = (double)cn[g].ngenes;
+                for (size_t q = 0; q < MT; q++) { mbg[q] = (double)h[q]; sum += mbg[q]; }
+                sum += zbg;
+                for (size_t q = 0; q < MT; q++) mbg[q] /= sum;
+                zbg /= sum;
+                if (stage < 2) tr_build_coverage_map(h + MT, mgood.data(), ngenes);
+                sum = 0.0;
+                for (size_t q = 0; q < MT; q++) { mreal[q] = (double)h[MT + q]; sum += mreal[q]; }
+                sum += zreal;
+                if (sum == 0.0) {
+                    memset(t->mot_wt, 0, sizeof t->mot_wt); t->no_mot = 0.0;
+                } else {
+                    double* wt = &t->mot_wt[0][0][0];
+                    for (size_t q = 0; q < MT; q++) {
+                        if (mgood[q] == 0) { zreal += mreal[q]; zbg += mreal[q]; mreal[q] = 0.0; mbg[q] = 0.0; }
+                        mreal[q] /= sum;
+                        double v = mbg[q] != 0 ? log(mreal[q] / mbg[q]) : -4.0;
+                        if (v > 4.0) v = 4.0; else if (v < -4.0) v = -4.0;
+                        wt[q] = v;
+                    }
+                }
+                zreal /= sum;
+                t->no_mot = zbg != 0 ? log(zreal / zbg) : -4.0;
+                if (t->no_mot > 4.0) t->no_mot = 4.0; else if (t->no_mot < -4.0) t->no_mot = -4.0;
+                sum = 0.0; for (int j = 0; j < 3; j++) sum += (double)cn[g].treal[j];
+                tr_log_odds(cn[g].treal, &tbg[3 * (size_t)g], t->type_wt, 3);
+                if (sum * 2000.0 <= n) w[g].sthresh /= 2.0;
             }
-        }
-        zreal /= sum;
-        t->no_mot = zbg != 0 ? log(zreal / zbg) : -4.0;
-        if (t->no_mot > 4.0) t->no_mot = 4.0; else if (t->no_mot < -4.0) t->no_mot = -4.0;
-        sum = 0.0; for (int j = 0; j < 3; j++) sum += (double)cn.treal[j];
-        tr_log_odds(cn.treal, tbg, t->type_wt, 3);
-        if (sum * 2000.0 <= n) w.sthresh /= 2.0;
+        };
+        const int k = std::min(n_threads, NMOT);
+        if (k <= 1) job(); else f->pool.run(job, k);
     }
-    tr_ups_to_log(cn.ups, t);
+    for (int g : motif) tr_ups_to_log(cn[g].ups, &out[g]);
     return PGA_OK;
 }
 
-// The scoring stage of the training runs through the context's model slot (the half-trained model is loaded as model 0);
-// the caller's model set is put back afterwards, so that pga_set_models(bins) ... pga_train ... pga_find_genes keeps
+// The scoring stage of the training runs through the context's model slots (the half-trained models are loaded as models
+// 0 .. G - 1); the caller's model set is put back afterwards, so that pga_set_models(bins) ... pga_train ... pga_find_genes keeps
 // scoring with the bins.
-static int train_impl(pga_ctx* c, const pga_batch* batch, const pga_params* pp, int tt, double start_weight, int force_nonsd,
-                      int upto, pga_training* t) {
+static int train_impl(pga_ctx* c, const pga_batch* batch, const pga_params* pp, const int32_t* tts, const double* sws, const int32_t* fns,
+                      int upto, pga_training* out, int32_t* status) {
     if (!c) return PGA_EINVAL;
     const std::vector<pga_training> saved = c->models;
     bool replaced = false;
-    const int rc = train_body(c, batch, pp, tt, start_weight, force_nonsd, upto, t, replaced);
+    const int rc = train_body(c, batch, pp, tts, sws, fns, upto, out, status, replaced);
     if (replaced) {
         const std::string err = c->err;
         std::vector<const pga_training*> ptrs;
@@ -597,6 +761,7 @@ static int train_impl(pga_ctx* c, const pga_batch* batch, const pga_params* pp, 
         // a failed restore must not pass unseen: the context would keep scoring with the half-trained model
         if (rc != PGA_OK) { c->err = rc2 != PGA_OK ? err + "; and the context's models could not be restored: " + c->err : err; return rc; }
         if (rc2 != PGA_OK) return rc2;
+        c->err = err;
     }
     return rc;
 }

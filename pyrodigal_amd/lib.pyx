@@ -112,6 +112,7 @@ cdef extern from "pyrodigal_amd.h" nogil:
                              const pga_params*, pga_result** out)
     void pga_result_free(pga_result*)
     int pga_find_genes(pga_ctx*, const pga_batch*, const pga_params*, pga_result** out)
+    int pga_find_genes_models(pga_ctx*, const pga_batch*, const pga_params*, const int32_t* model_of_contig, pga_result** out)
     int pga_translate_genes(pga_ctx*, const pga_batch*, int64_t n_genes, const pga_gene* genes, const int32_t* table_of_contig,
                             int unknown_residue, int include_stop, int strict, const int64_t* offsets, char* out)
     int pga_batch_create(pga_ctx*, int32_t n, const char* const* seqs, const int64_t* lens, pga_batch** out)
@@ -120,6 +121,8 @@ cdef extern from "pyrodigal_amd.h" nogil:
     int pga_nodes_stage(pga_ctx*, const pga_batch*, const pga_params*, int stage, int translation_table, pga_result** out)
     int pga_train(pga_ctx*, const pga_batch*, const pga_params*, int translation_table, double start_weight, int force_nonsd,
                   int upto, pga_training* out)
+    int pga_train_batch(pga_ctx*, const pga_batch*, const pga_params*, const int32_t* translation_table, const double* start_weight,
+                        const int32_t* force_nonsd, int upto, pga_training* out, int32_t* status)
     int pga_score_connections(pga_ctx*, int32_t n, const int32_t* ndx, const int32_t* stop_val, const uint8_t* type,
                               const int8_t* strand, const double* cscore, const double* sscore, const double* rscore,
                               const double* uscore, const int32_t* star_ptr, double st_wt, int final,
@@ -1521,25 +1524,25 @@ cdef class GeneFinder:
         del self._pending[:k]
         return take
 
-    def find_genes_batch(self, object sequences, *, bint translate=False):
+    def find_genes_batch(self, object sequences, *, bint translate=False, object training_infos=None):
         """`find_genes` for many sequences in one device pass; returns one `Genes` per input, in order.
 
         `translate=True` also translates every gene on the device while the batch is resident (one thread per codon, the
         translation table of the model that called the gene): `Gene.translate()` with its default arguments and
-        `Genes.write_translations` then read those proteins instead of translating codon by codon on the host."""
+        `Genes.write_translations` then read those proteins instead of translating codon by codon on the host.
+
+        `training_infos` (single mode only): one `TrainingInfo` per sequence, sequence i is called with `training_infos[i]`
+        -- the result is that of `GeneFinder(training_infos[i], <same options>).find_genes(sequences[i])`, for many genomes
+        under their own models in a few device calls.  The finder's own `training_info` is not used (nor needed) then."""
+        if training_infos is not None:
+            return self._find_genes_models(sequences, translate, training_infos)
         if not self.meta and self.training_info is None:
             raise RuntimeError("cannot find genes without having trained in single mode")
         # the reference always re-wraps with the finder's masking rule (ref: lib.pyx:5433-5438); a Sequence that already
         # follows it is used as it is
-        cdef list seqs = []
+        cdef list seqs = self._wrap_sequences(sequences)
         cdef int64_t bases = 0
-        for s in sequences:
-            if isinstance(s, Sequence):
-                if (<Sequence> s).mask != self.mask or (self.mask and <int> (<Sequence> s).mask_size != self.min_mask):
-                    s = Sequence((<Sequence> s).data, mask=self.mask, mask_size=self.min_mask)
-            else:
-                s = Sequence(s, mask=self.mask, mask_size=self.min_mask)
-            seqs.append(s)
+        for s in seqs:
             bases += len((<Sequence> s).data)
         if not seqs:
             return []
@@ -1610,6 +1613,74 @@ cdef class GeneFinder:
             raise req.error
         return req.out
 
+    cdef list _wrap_sequences(self, object sequences):
+        """The finder's masking rule on every sequence (the reference always re-wraps, lib.pyx:5433-5438): a Sequence that already
+        follows it is used as it is."""
+        cdef list seqs = []
+        for s in sequences:
+            if isinstance(s, Sequence):
+                if (<Sequence> s).mask != self.mask or (self.mask and <int> (<Sequence> s).mask_size != self.min_mask):
+                    s = Sequence((<Sequence> s).data, mask=self.mask, mask_size=self.min_mask)
+            else:
+                s = Sequence(s, mask=self.mask, mask_size=self.min_mask)
+            seqs.append(s)
+        return seqs
+
+    def _find_genes_models(self, object sequences, bint translate, object training_infos):
+        """`find_genes_batch(..., training_infos=...)`: single mode with a model per sequence (`pga_find_genes_models`).  The
+        sequences go in device calls of at most `coalesce_bases` bases and four translation tables (what one context's model set
+        holds); identical `TrainingInfo` objects are loaded once per call."""
+        if self.meta:
+            raise ValueError("`training_infos` is a single-mode option: this finder is in meta mode")
+        cdef list tinfs = list(training_infos)
+        cdef list seqs = self._wrap_sequences(sequences)
+        if len(tinfs) != len(seqs):
+            raise ValueError("`training_infos` has %d entries for %d sequences" % (len(tinfs), len(seqs)))
+        for i, t in enumerate(tinfs):
+            if not isinstance(t, TrainingInfo):
+                raise TypeError("training_infos[%d] is not a TrainingInfo (%r)" % (i, type(t).__name__))
+        if not seqs:
+            return []
+        # the device calls: consecutive runs of sequences under the base budget and at most four distinct tables
+        cdef list calls = []
+        cdef list cur = []
+        cdef set tables = set()
+        cdef int64_t bases = 0, nb
+        for i in range(len(seqs)):
+            nb = len((<Sequence> seqs[i]).data)
+            tt = (<TrainingInfo> tinfs[i]).translation_table
+            if cur and (bases + nb > self.coalesce_bases or (tt not in tables and len(tables) == 4)):
+                calls.append(cur); cur = []; tables = set(); bases = 0
+            cur.append(i); tables.add(tt); bases += nb
+        calls.append(cur)
+        cdef _FindRequest req
+        cdef _FinderSlot slot
+        cdef list out = []
+        with self._lock:
+            first_id = self._num_seq
+            self._num_seq += len(seqs)
+        # a context for this request alone, like the training takes one
+        with self._cv:
+            while True:
+                slot = self._free_slot()
+                if slot is not None:
+                    break
+                self._cv.wait()
+            slot.busy = True
+        try:
+            for idx in calls:
+                req = _FindRequest.__new__(_FindRequest)
+                req.seqs = [seqs[i] for i in idx]
+                req.first_id = first_id + idx[0]
+                out.extend(self._device_call(slot, req.seqs, translate, [req], [tinfs[i] for i in idx]))
+                with self._lock:
+                    self.stats["device_calls"] += 1
+                    self.stats["sequences"] += len(idx)
+        finally:
+            with self._lock:
+                self._release_slot(slot)
+        return out
+
     cdef int _release_slot(self, _FinderSlot slot) except -1:
         """(lock held) The context goes to the oldest waiting request that has no context yet, or back to the pool."""
         cdef _FindRequest r
@@ -1660,7 +1731,8 @@ cdef class GeneFinder:
             st["max_calls_per_device_call"] = len(take)
         return 0
 
-    cdef list _device_call(self, _FinderSlot slot, list seqs, bint translate, list take):
+    cdef list _device_call(self, _FinderSlot slot, list seqs, bint translate, list take, list tinf_of=None):
+        # tinf_of: one TrainingInfo per sequence (single mode, a model per sequence: pga_find_genes_models), or None
         cdef int n = len(seqs), i, j, rc
         cdef const char** ptrs = <const char**> malloc(sizeof(char*) * max(n, 1))
         cdef int64_t* lens = <int64_t*> malloc(sizeof(int64_t) * max(n, 1))
@@ -1676,6 +1748,9 @@ cdef class GeneFinder:
         cdef size_t p_tab, p_off, p_out
         cdef int64_t ng
         cdef pga_ctx* ctx
+        cdef list loaded = None
+        cdef object moc = None
+        cdef size_t p_moc = 0
         if ptrs == NULL or lens == NULL:
             free(ptrs); free(lens)
             raise MemoryError()
@@ -1689,9 +1764,26 @@ cdef class GeneFinder:
             for i in range(n):
                 ptrs[i] = PyBytes_AS_STRING((<Sequence> seqs[i]).data)
                 lens[i] = len((<Sequence> seqs[i]).data)
-            self._ensure_models(slot)
+            if tinf_of is None:
+                self._ensure_models(slot)
+            else:
+                loaded, moc = self._load_models_of(slot, tinf_of)
+                p_moc = moc.ctypes.data
             ctx = slot.ctx
-            if not translate:
+            if tinf_of is not None:
+                rc = pga_batch_create(ctx, n, ptrs, lens, &batch)
+                if rc != PGA_OK:
+                    _raise_for(ctx, rc, "pga_batch_create")
+                try:
+                    with nogil:
+                        rc = pga_find_genes_models(ctx, batch, &p, <const int32_t*> p_moc, &res)
+                    if rc != PGA_OK:
+                        _raise_for(ctx, rc, "pga_find_genes_models")
+                    if translate:
+                        prot, prot_off, tables = self._translate(ctx, batch, res, n, tinf_of)
+                finally:
+                    pga_batch_free(batch)
+            elif not translate:
                 with nogil:
                     rc = pga_find_genes_batch(ctx, n, ptrs, lens, &p, &res)
                 if rc != PGA_OK:
@@ -1706,24 +1798,7 @@ cdef class GeneFinder:
                     if rc != PGA_OK:
                         _raise_for(ctx, rc, "pga_find_genes")
                     prot_off = np.zeros(res.n_genes + 1, np.int64)
-                    tables = np.full(max(n, 1), 11, np.int32)
-                    for i in range(n):
-                        cr = &res.contigs[i]
-                        if self.meta:
-                            if cr.model >= 0:
-                                tables[i] = (<MetagenomicBin> self.metagenomic_bins[cr.model]).training_info.translation_table
-                        else:
-                            tables[i] = (<TrainingInfo> self.training_info).translation_table
-                    for j in range(res.n_genes):
-                        prot_off[j + 1] = prot_off[j] + (res.genes[j].end - res.genes[j].begin + 1) // 3
-                    prot = np.zeros(max(int(prot_off[res.n_genes]), 1), np.uint8)
-                    p_tab = tables.ctypes.data; p_off = prot_off.ctypes.data; p_out = prot.ctypes.data
-                    ng = res.n_genes
-                    with nogil:
-                        rc = pga_translate_genes(ctx, batch, ng, res.genes, <const int32_t*> p_tab, 88, 1, 1,
-                                                 <const int64_t*> p_off, <char*> p_out)
-                    if rc != PGA_OK:
-                        _raise_for(ctx, rc, "pga_translate_genes")
+                    prot, prot_off, tables = self._translate(ctx, batch, res, n, None)
                 finally:
                     pga_batch_free(batch)
             for i in range(n):
@@ -1748,7 +1823,7 @@ cdef class GeneFinder:
                         genes.metagenomic_bin = genes.training_info = None
                 else:
                     genes.metagenomic_bin = None
-                    genes.training_info = self.training_info
+                    genes.training_info = self.training_info if tinf_of is None else tinf_of[i]
                 genes._nodes = None
                 genes._node_blob = None
                 genes._node_n = 0
@@ -1770,6 +1845,200 @@ cdef class GeneFinder:
                 pga_result_free(res)
         return out
 
+    cdef tuple _translate(self, pga_ctx* ctx, pga_batch* batch, pga_result* res, int n, list tinf_of):
+        """Proteins of every gene of `res` on the device: (letters, offsets, table of every contig)."""
+        cdef int i, rc
+        cdef int64_t j, ng
+        cdef pga_contig_result* cr
+        cdef size_t p_tab, p_off, p_out
+        prot_off = np.zeros(res.n_genes + 1, np.int64)
+        tables = np.full(max(n, 1), 11, np.int32)
+        for i in range(n):
+            cr = &res.contigs[i]
+            if self.meta:
+                if cr.model >= 0:
+                    tables[i] = (<MetagenomicBin> self.metagenomic_bins[cr.model]).training_info.translation_table
+            elif tinf_of is not None:
+                tables[i] = (<TrainingInfo> tinf_of[i]).translation_table
+            else:
+                tables[i] = (<TrainingInfo> self.training_info).translation_table
+        for j in range(res.n_genes):
+            prot_off[j + 1] = prot_off[j] + (res.genes[j].end - res.genes[j].begin + 1) // 3
+        prot = np.zeros(max(int(prot_off[res.n_genes]), 1), np.uint8)
+        p_tab = tables.ctypes.data; p_off = prot_off.ctypes.data; p_out = prot.ctypes.data
+        ng = res.n_genes
+        with nogil:
+            rc = pga_translate_genes(ctx, batch, ng, res.genes, <const int32_t*> p_tab, 88, 1, 1,
+                                     <const int64_t*> p_off, <char*> p_out)
+        if rc != PGA_OK:
+            _raise_for(ctx, rc, "pga_translate_genes")
+        return prot, prot_off, tables
+
+    cdef tuple _load_models_of(self, _FinderSlot slot, list tinf_of):
+        """Load the distinct `TrainingInfo` objects of `tinf_of` (by identity, first-seen order) into the slot's context; returns
+        them and the model index of every sequence.  The slot no longer holds the finder's own model set afterwards."""
+        cdef int rc, i, n
+        cdef const pga_training** ptrs
+        cdef dict index = {}
+        cdef list models = []
+        moc = np.zeros(max(len(tinf_of), 1), np.int32)
+        for i, t in enumerate(tinf_of):
+            k = index.get(id(t))
+            if k is None:
+                k = index[id(t)] = len(models)
+                models.append(t)
+            moc[i] = k
+        if slot.ctx == NULL:
+            rc = pga_create(self.device, &slot.ctx)
+            if rc != PGA_OK:
+                slot.ctx = NULL
+                _raise_for(NULL, rc, "pga_create")
+        n = len(models)
+        blobs = [(<TrainingInfo> t)._raw for t in models]
+        ptrs = <const pga_training**> malloc(sizeof(void*) * max(n, 1))
+        if ptrs == NULL:
+            raise MemoryError()
+        slot.models_loaded = False        # whatever happens now, the next ordinary call loads the finder's models again
+        try:
+            for i in range(n):
+                ptrs[i] = <const pga_training*> <size_t> blobs[i].ctypes.data
+            rc = pga_set_models(slot.ctx, ptrs, n)
+        finally:
+            free(ptrs)
+        if rc != PGA_OK:
+            _raise_for(slot.ctx, rc, "pga_set_models")
+        return models, moc
+
+    cdef Sequence _training_sequence(self, object sequence, tuple sequences, str which):
+        """One genome as `train(sequence, *sequences)` takes it: several contigs joined with `TTAATTAATTAA` linkers like in
+        Prodigal (ref: lib.pyx:5510-5532), then the length rules (`which` names the genome in the messages)."""
+        import warnings
+        cdef Sequence seq
+        if isinstance(sequence, Sequence):
+            if sequences:
+                raise NotImplementedError("cannot use more than one `Sequence` object in `GeneFinder.train`")
+            seq = Sequence(sequence, mask=self.mask, mask_size=self.min_mask)
+        elif isinstance(sequence, str):
+            if sequences:
+                sequence = "TTAATTAATTAA".join(list((sequence,) + sequences) + [""])
+            seq = Sequence(sequence, mask=self.mask, mask_size=self.min_mask)
+        else:
+            if sequences:
+                sequence = b"TTAATTAATTAA".join([bytes(memoryview(x)) for x in (sequence,) + sequences] + [b""])
+            seq = Sequence(sequence, mask=self.mask, mask_size=self.min_mask)
+        if len(seq) < MIN_SINGLE_GENOME:
+            raise ValueError("%ssequence must be at least %d characters (%d found)" % (which, MIN_SINGLE_GENOME, len(seq)))
+        elif len(seq) < IDEAL_SINGLE_GENOME:
+            warnings.warn("%ssequence should be at least %d characters (%d found)" % (which, IDEAL_SINGLE_GENOME, len(seq)))
+        return seq
+
+    def train_batch(self, object genomes, *, object force_nonsd=False, object start_weight=4.35, object translation_table=11):
+        """`train` on many genomes at once, on the device (`pga_train_batch`): every stage and training round runs once for the
+        whole batch.  A genome is one sequence or a list / tuple of contigs (joined as `train(*contigs)` joins them); the
+        keywords take a scalar or one value per genome.  Returns one `TrainingInfo` per genome, identical to
+        `GeneFinder(<same options>).train(genome, ...)`; the finder's own `training_info` is left alone.  Device calls hold at most
+        `coalesce_bases` bases and four translation tables; the results do not depend on that split."""
+        if self.meta:
+            raise RuntimeError("cannot use training sequence in metagenomic mode")
+        cdef list gl = list(genomes)
+        cdef Py_ssize_t G = len(gl), g
+        if G == 0:
+            return []
+        def per_genome(v, name):
+            if isinstance(v, (list, tuple, np.ndarray)):
+                if len(v) != G:
+                    raise ValueError("`%s` has %d values for %d genomes" % (name, len(v), G))
+                return list(v)
+            return [v] * G
+        cdef list fns = [bool(x) for x in per_genome(force_nonsd, "force_nonsd")]
+        cdef list sws = [float(x) for x in per_genome(start_weight, "start_weight")]
+        cdef list tts = per_genome(translation_table, "translation_table")
+        for g in range(G):
+            if tts[g] not in TRANSLATION_TABLES:
+                raise ValueError("genome %d: %r is not a valid translation table index" % (g, tts[g]))
+        cdef list seqs = []
+        for g in range(G):
+            x = gl[g]
+            seqs.append(self._training_sequence(x[0], tuple(x[1:]), "genome %d: " % g) if isinstance(x, (list, tuple))
+                        else self._training_sequence(x, (), "genome %d: " % g))
+        # the device calls: consecutive genomes under the base budget and at most four distinct tables
+        cdef list calls = [], cur = []
+        cdef set tables = set()
+        cdef int64_t bases = 0, nb
+        for g in range(G):
+            nb = len((<Sequence> seqs[g]).data)
+            if cur and (bases + nb > self.coalesce_bases or (tts[g] not in tables and len(tables) == 4)):
+                calls.append(cur); cur = []; tables = set(); bases = 0
+            cur.append(g); tables.add(tts[g]); bases += nb
+        if cur:
+            calls.append(cur)
+        cdef list out = []
+        cdef pga_params p
+        cdef pga_batch* batch = NULL
+        cdef const char** ptrs
+        cdef int64_t* lens
+        cdef int rc, n, k
+        cdef size_t p_tt, p_sw, p_fn, p_out, p_st
+        cdef _FinderSlot slot
+        cdef pga_ctx* ctx
+        p.closed = self.closed; p.min_gene = self.min_gene; p.min_edge_gene = self.min_edge_gene
+        p.max_overlap = self.max_overlap; p.meta = 0; p.want_nodes = 0
+        p.mask = self.mask; p.min_mask = self.min_mask
+        with self._cv:
+            while True:
+                slot = self._free_slot()
+                if slot is not None:
+                    break
+                self._cv.wait()
+            slot.busy = True
+        try:
+            if slot.ctx == NULL:
+                rc = pga_create(self.device, &slot.ctx)
+                if rc != PGA_OK:
+                    slot.ctx = NULL
+                    _raise_for(NULL, rc, "pga_create")
+            ctx = slot.ctx
+            slot.models_loaded = False            # the training loads its own partial models into the context
+            for idx in calls:
+                n = len(idx)
+                a_tt = np.array([tts[g] for g in idx], np.int32)
+                a_sw = np.array([sws[g] for g in idx], np.float64)
+                a_fn = np.array([fns[g] for g in idx], np.int32)
+                raw = np.zeros(n * TRAINING_INFO_SIZE, np.uint8)
+                status = np.zeros(n, np.int32)
+                p_tt = a_tt.ctypes.data; p_sw = a_sw.ctypes.data; p_fn = a_fn.ctypes.data; p_out = raw.ctypes.data; p_st = status.ctypes.data
+                ptrs = <const char**> malloc(sizeof(char*) * n)
+                lens = <int64_t*> malloc(sizeof(int64_t) * n)
+                if ptrs == NULL or lens == NULL:
+                    free(ptrs); free(lens)
+                    raise MemoryError()
+                try:
+                    for k in range(n):
+                        ptrs[k] = PyBytes_AS_STRING((<Sequence> seqs[idx[k]]).data)
+                        lens[k] = len((<Sequence> seqs[idx[k]]).data)
+                    rc = pga_batch_create(ctx, n, ptrs, lens, &batch)
+                finally:
+                    free(ptrs); free(lens)
+                if rc != PGA_OK:
+                    _raise_for(ctx, rc, "pga_batch_create")
+                try:
+                    with nogil:
+                        rc = pga_train_batch(ctx, batch, &p, <const int32_t*> p_tt, <const double*> p_sw, <const int32_t*> p_fn, 0,
+                                             <pga_training*> p_out, <int32_t*> p_st)
+                finally:
+                    pga_batch_free(batch)
+                    batch = NULL
+                if rc != PGA_OK:
+                    _raise_for(ctx, rc, "pga_train_batch")
+                for k in range(n):
+                    if status[k] != PGA_OK:
+                        raise ValueError("genome %d could not be trained: no start / stop node in the sequence" % idx[k])
+                out.extend([TrainingInfo(raw=raw[k * TRAINING_INFO_SIZE:(k + 1) * TRAINING_INFO_SIZE].copy()) for k in range(n)])
+        finally:
+            with self._lock:
+                self._release_slot(slot)
+        return out
+
     def train(self, object sequence, *sequences, bint force_nonsd=False, double start_weight=4.35, int translation_table=11):
         """Train on the given genome, on the device, and use the result for the next `find_genes` (ref: lib.pyx:5471-5575).
 
@@ -1788,22 +2057,7 @@ cdef class GeneFinder:
             raise RuntimeError("cannot use training sequence in metagenomic mode")
         if translation_table not in TRANSLATION_TABLES:
             raise ValueError("%d is not a valid translation table index" % translation_table)
-        if isinstance(sequence, Sequence):
-            if sequences:
-                raise NotImplementedError("cannot use more than one `Sequence` object in `GeneFinder.train`")
-            seq = Sequence(sequence, mask=self.mask, mask_size=self.min_mask)
-        elif isinstance(sequence, str):
-            if sequences:
-                sequence = "TTAATTAATTAA".join(list((sequence,) + sequences) + [""])
-            seq = Sequence(sequence, mask=self.mask, mask_size=self.min_mask)
-        else:
-            if sequences:
-                sequence = b"TTAATTAATTAA".join([bytes(memoryview(x)) for x in (sequence,) + sequences] + [b""])
-            seq = Sequence(sequence, mask=self.mask, mask_size=self.min_mask)
-        if len(seq) < MIN_SINGLE_GENOME:
-            raise ValueError("sequence must be at least %d characters (%d found)" % (MIN_SINGLE_GENOME, len(seq)))
-        elif len(seq) < IDEAL_SINGLE_GENOME:
-            warnings.warn("sequence should be at least %d characters (%d found)" % (IDEAL_SINGLE_GENOME, len(seq)))
+        seq = self._training_sequence(sequence, sequences, "")
         p.closed = self.closed; p.min_gene = self.min_gene; p.min_edge_gene = self.min_edge_gene
         p.max_overlap = self.max_overlap; p.meta = 0; p.want_nodes = 0
         p.mask = self.mask; p.min_mask = self.min_mask
