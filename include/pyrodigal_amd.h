@@ -242,6 +242,51 @@ int pga_nodes_stage(pga_ctx*, const pga_batch*, const pga_params*, int stage, in
 int pga_translate_genes(pga_ctx*, const pga_batch*, int64_t n_genes, const pga_gene* genes, const int32_t* table_of_contig,
                         int unknown_residue, int include_stop, int strict, const int64_t* offsets, char* out);
 
+/* ---- text output ------------------------------------------------------------------ */
+/* GFF, protein FASTA and gene FASTA of gene records, rendered on the device from a resident batch: byte for byte what the
+ * host writers Genes.write_gff / write_translations / write_genes emit, contig after contig (ref: lib.pyx:3534-3792).
+ * A length pass, an exclusive scan and a write pass per format; one text arena per format, copied back once. */
+#define PGA_RENDER_GFF 1
+#define PGA_RENDER_FAA 2
+#define PGA_RENDER_FNA 4
+typedef struct pga_render_opts {
+    int32_t     formats;            /* PGA_RENDER_* bits */
+    int32_t     meta;               /* run_type=Metagenomic (1) or Single (0) in the GFF header */
+    int64_t     first_seqnum;       /* seqnum of contig 0 (the reference counts sequences from 1) */
+    const char* source;             /* GFF column 2, e.g. "pyrodigal_amd_v0.1.0" (tool name + version separator + version) */
+    const char* version;            /* GFF header "version=", e.g. "pyrodigal_amd.v0.1.0" */
+    const char* const* model_desc;  /* [n_models] the model="..." of the GFF header ("Ab initio" in single mode) */
+    int32_t     gff_header, gff_include_translation_table, gff_full_id;
+    int32_t     faa_width, faa_translation_table /* 0: the contig's model's */, faa_include_stop, faa_strict, faa_full_id;
+    int32_t     fna_width, fna_full_id;
+    double      fallback_margin;    /* a line whose confidence lies this close to a %.2f rounding midpoint is left to the host
+                                     * (the device exp may differ from the host's by an ulp); 1e-9 */
+} pga_render_opts;
+typedef struct pga_text {
+    char*    data;          /* `size` bytes in pinned host memory the CONTEXT owns (kept and grown across calls): valid until the
+                             * next pga_render_genes on the context or its pga_destroy -- copy it out before either */
+    int64_t  size;
+    int64_t* contig_off;    /* [n_contigs + 1]: contig i is data[contig_off[i] .. contig_off[i + 1]) */
+    int64_t  n_fallback;    /* lines the caller renders itself and splices in (device text in their place is a best guess) */
+    int64_t* fallback;      /* [3 * n_fallback]: gene index, first byte, end byte of each such line */
+} pga_text;
+typedef struct pga_render_result {
+    int32_t  n_contigs;
+    int32_t  _pad;
+    pga_text text[3];       /* GFF, protein FASTA, gene FASTA; data == NULL for a format that was not asked for */
+    double   t_kernels_ms[3];  /* device time of each format's length pass, scan and write pass */
+} pga_render_result;
+/*   contigs[i]          the result's contig records of THIS batch (gene_begin / n_genes; genes of contig i in order)
+ *   genes               the result's gene records
+ *   model_of_contig[i]  the loaded model (pga_set_models index) that called contig i: 0 in single mode, contigs[i].model in
+ *                       meta mode, the caller's index on the model-per-contig path; -1 only for a contig without genes
+ *                       (and then not with PGA_RENDER_GFF: its header needs a model -- Prodigal reports bin 5 for it)
+ *   ids / id_off        sequence ids: contig i is ids[id_off[i] .. id_off[i + 1]) */
+int  pga_render_genes(pga_ctx*, const pga_batch*, const pga_contig_result* contigs, int64_t n_genes, const pga_gene* genes,
+                      const int32_t* model_of_contig, const char* ids, const int64_t* id_off, const pga_render_opts* opts,
+                      pga_render_result** out);
+void pga_render_free(pga_render_result*);
+
 /* ---- training --------------------------------------------------------------- */
 /* Single-genome training (ref: lib.pyx:5236-5279 `GeneFinder._train`): `batch` holds exactly ONE sequence (several
  * training sequences are joined by the caller with the reference's TTAATTAATTAA spacer, lib.pyx:5510-5532); closed,

@@ -20,7 +20,7 @@ EXPORTS = [
     "pga_batch_create", "pga_batch_free", "pga_find_genes", "pga_nodes_stage",
     "pga_fasta_open", "pga_fasta_next", "pga_fasta_error", "pga_fasta_close", "pga_train", "pga_dp_stats", "pga_dp_timings", "pga_extract_stats", "pga_dp_plan_summary", "pga_dp_start_order", "pga_cs_task_summary",
     "pga_fasta_next_packed", "pga_batch_create_packed", "pga_translate_genes", "pga_fasta_open_callback", "pga_fasta_release_spare", "pga_dp_xcd_order", "pga_release_cached",
-    "pga_find_genes_models", "pga_train_batch",
+    "pga_find_genes_models", "pga_train_batch", "pga_render_genes", "pga_render_free",
 ]
 STAGE_EXTRACT, STAGE_SCORE, STAGE_OVERLAP, STAGE_SEQUENCE = 1, 2, 3, 4
 
@@ -70,6 +70,25 @@ class Result(ctypes.Structure):
                 ("_pad", ctypes.c_int32), ("mask_off", _P(ctypes.c_int32)), ("masks", _P(ctypes.c_int32))]
 
 
+class RenderOpts(ctypes.Structure):
+    _fields_ = [("formats", ctypes.c_int32), ("meta", ctypes.c_int32), ("first_seqnum", ctypes.c_int64),
+                ("source", ctypes.c_char_p), ("version", ctypes.c_char_p), ("model_desc", _P(ctypes.c_char_p)),
+                ("gff_header", ctypes.c_int32), ("gff_include_translation_table", ctypes.c_int32), ("gff_full_id", ctypes.c_int32),
+                ("faa_width", ctypes.c_int32), ("faa_translation_table", ctypes.c_int32), ("faa_include_stop", ctypes.c_int32),
+                ("faa_strict", ctypes.c_int32), ("faa_full_id", ctypes.c_int32), ("fna_width", ctypes.c_int32),
+                ("fna_full_id", ctypes.c_int32), ("fallback_margin", ctypes.c_double)]
+
+
+class Text(ctypes.Structure):
+    _fields_ = [("data", ctypes.c_void_p), ("size", ctypes.c_int64), ("contig_off", _P(ctypes.c_int64)),
+                ("n_fallback", ctypes.c_int64), ("fallback", _P(ctypes.c_int64))]
+
+
+class RenderResult(ctypes.Structure):
+    _fields_ = [("n_contigs", ctypes.c_int32), ("_pad", ctypes.c_int32), ("text", Text * 3), ("t_kernels_ms", ctypes.c_double * 3)]
+
+
+RENDER_FORMATS = ("gff", "faa", "fna")
 GENE_DTYPE = np.dtype(Gene)
 CONTIG_DTYPE = np.dtype(ContigResult)
 
@@ -127,6 +146,9 @@ def load():
     L.pga_batch_create_packed.argtypes = [vp, i32, vp, _P(i64), _P(i64), _P(vp)]
     L.pga_translate_genes.restype = ctypes.c_int
     L.pga_translate_genes.argtypes = [vp, vp, i64, vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, vp]
+    L.pga_render_genes.restype = ctypes.c_int
+    L.pga_render_genes.argtypes = [vp, vp, vp, i64, vp, vp, vp, vp, _P(RenderOpts), _P(_P(RenderResult))]
+    L.pga_render_free.restype = None; L.pga_render_free.argtypes = [_P(RenderResult)]
     L.pga_fasta_error.restype = ctypes.c_char_p; L.pga_fasta_error.argtypes = [vp]
     L.pga_fasta_close.restype = None; L.pga_fasta_close.argtypes = [vp]
     L.pga_fasta_release_spare.restype = None; L.pga_fasta_release_spare.argtypes = []
@@ -611,6 +633,163 @@ def _translate_genes(self, batch, result, tables=None, unknown_residue="X", incl
     return out[:int(off[-1])], off
 
 
+class RenderedText:
+    """One format's text of a :meth:`Context.render_genes` call: ``data`` (bytes), ``contig_offsets`` (contig i is
+    ``data[contig_offsets[i]:contig_offsets[i + 1]]``), ``fallback`` (lines the host rendered itself) and ``kernel_ms`` (device
+    time of the format's passes)."""
+
+    __slots__ = ("data", "contig_offsets", "fallback", "kernel_ms")
+
+    def __init__(self, data, contig_offsets, fallback, kernel_ms):
+        self.data, self.contig_offsets, self.fallback, self.kernel_ms = data, contig_offsets, fallback, kernel_ms
+
+    def contig(self, i):
+        return self.data[self.contig_offsets[i]:self.contig_offsets[i + 1]]
+
+
+# the writers' defaults (Genes.write_gff / write_translations / write_genes)
+_WRITER_DEFAULTS = {
+    "gff": {"header": True, "include_translation_table": False, "full_id": True, "version_separator": "_v"},
+    "faa": {"width": 60, "translation_table": None, "include_stop": True, "strict_translation": True, "full_id": False},
+    "fna": {"width": 70, "full_id": False},
+}
+
+
+def _render_genes(self, batch, result, ids, formats=RENDER_FORMATS, *, meta=False, model_of_contig=None, descriptions=None,
+                  first_seqnum=1, fallback_margin=1e-9, unbinned_model=None, **writer_options):
+    """GFF / protein FASTA / gene FASTA of ``result`` (a result of ``find_genes`` on the resident ``batch``), rendered on the
+    device: byte for byte what ``Genes.write_gff`` / ``write_translations`` / ``write_genes`` write for these genes, contig
+    after contig.
+
+    ``ids``: the sequence id of every contig; ``first_seqnum``: the seqnum of contig 0.  ``formats``: names among "gff", "faa",
+    "fna", or a dict from those names to the writer's keyword arguments (``header``, ``include_translation_table``, ``full_id``,
+    ``version_separator`` / ``width``, ``translation_table``, ``include_stop``, ``strict_translation``, ``full_id`` /
+    ``width``, ``full_id``); ``writer_options`` apply to every format that takes them.  ``meta``: the models are metagenomic
+    bins (``descriptions`` gives theirs) and contig i was called with ``result.contigs[i]["model"]``; else single mode with
+    model 0, or with ``model_of_contig[i]``.  ``unbinned_model`` (meta mode): the model whose data the GFF header of a contig
+    without genes, which no bin won, reports (Prodigal writes bin 5's); None: such a contig is an error for GFF, as it is for
+    ``write_gff``.  Returns ``{name: RenderedText}``."""
+    from . import __version__ as version
+    if isinstance(formats, str):
+        formats = (formats,)
+    fmt_opts = {}
+    for name in formats:
+        if name not in _WRITER_DEFAULTS:
+            raise ValueError("unknown format %r (expected one of %s)" % (name, ", ".join(RENDER_FORMATS)))
+        o = dict(_WRITER_DEFAULTS[name])
+        o.update({k: v for k, v in writer_options.items() if k in o})
+        if isinstance(formats, dict) and formats[name]:
+            bad = set(formats[name]) - set(o)
+            if bad:
+                raise TypeError("%s: unexpected option(s) %s" % (name, ", ".join(sorted(bad))))
+            o.update(formats[name])
+        fmt_opts[name] = o
+    bad = set(writer_options) - set().union(*[set(v) for v in _WRITER_DEFAULTS.values()])
+    if bad:
+        raise TypeError("unexpected option(s) %s" % ", ".join(sorted(bad)))
+    n = batch.n
+    ids = [str(x) for x in ids]
+    if len(ids) != n:
+        raise ValueError("%d ids for %d contigs" % (len(ids), n))
+    contigs = np.ascontiguousarray(result.contigs)
+    genes = np.ascontiguousarray(result.genes)
+    if model_of_contig is None:
+        moc = contigs["model"].astype(np.int32) if meta else np.zeros(n, np.int32)
+        if meta and unbinned_model is not None:
+            if not 0 <= int(unbinned_model) < len(self._models):
+                raise ValueError("`unbinned_model` %r is not a loaded model" % (unbinned_model,))
+            moc[moc < 0] = int(unbinned_model)
+    else:
+        moc = np.ascontiguousarray(model_of_contig, np.int32)
+    moc = np.ascontiguousarray(moc, np.int32)
+    nm = len(self._models)
+    if descriptions is None:
+        descriptions = [""] * nm if meta else ["Ab initio"] * nm
+    if len(descriptions) != nm:
+        raise ValueError("%d descriptions for %d models" % (len(descriptions), nm))
+    id_bytes = [x.encode("utf-8") for x in ids]
+    id_off = np.zeros(n + 1, np.int64)
+    np.cumsum([len(b) for b in id_bytes], out=id_off[1:])
+    id_arena = b"".join(id_bytes)
+    desc = (ctypes.c_char_p * max(nm, 1))(*[d.encode("utf-8") for d in descriptions])
+    o = RenderOpts()
+    o.meta = int(bool(meta))
+    o.first_seqnum = int(first_seqnum)
+    o.model_desc = desc
+    o.fallback_margin = float(fallback_margin)
+    sep = fmt_opts.get("gff", _WRITER_DEFAULTS["gff"])["version_separator"]
+    o.source = ("pyrodigal_amd%s%s" % (sep, version)).encode("utf-8")
+    o.version = ("pyrodigal_amd.v%s" % version).encode("utf-8")
+    for k, name in enumerate(RENDER_FORMATS):
+        if name in fmt_opts:
+            o.formats |= 1 << k
+    if "gff" in fmt_opts:
+        g = fmt_opts["gff"]
+        o.gff_header, o.gff_include_translation_table, o.gff_full_id = int(bool(g["header"])), int(bool(g["include_translation_table"])), int(bool(g["full_id"]))
+    if "faa" in fmt_opts:
+        a = fmt_opts["faa"]
+        tt = a["translation_table"]
+        if tt is not None and (not isinstance(tt, int) or tt <= 0):
+            raise ValueError("%r is not a valid translation table index" % (tt,))
+        o.faa_width, o.faa_translation_table = _width(a["width"]), 0 if tt is None else int(tt)
+        o.faa_include_stop, o.faa_strict, o.faa_full_id = int(bool(a["include_stop"])), int(bool(a["strict_translation"])), int(bool(a["full_id"]))
+    if "fna" in fmt_opts:
+        o.fna_width, o.fna_full_id = _width(fmt_opts["fna"]["width"]), int(bool(fmt_opts["fna"]["full_id"]))
+    res = _P(RenderResult)()
+    rc = self.L.pga_render_genes(self.h, batch.h, contigs.ctypes.data, len(genes), genes.ctypes.data if len(genes) else None,
+                                 moc.ctypes.data, id_arena or None, id_off.ctypes.data, ctypes.byref(o), ctypes.byref(res))
+    if rc != PGA_OK:
+        _raise(self.L, self.h, rc, "pga_render_genes")
+    try:
+        out = {}
+        r = res.contents
+        for k, name in enumerate(RENDER_FORMATS):
+            if name not in fmt_opts:
+                continue
+            t = r.text[k]
+            data = ctypes.string_at(t.data, t.size) if t.size else b""
+            coff = np.ctypeslib.as_array(t.contig_off, (n + 1,)).copy()
+            nf = int(t.n_fallback)
+            if nf:
+                fb = np.ctypeslib.as_array(t.fallback, (3 * nf,)).reshape(nf, 3).copy()
+                data, coff = _splice_fallback(self, name, fmt_opts[name], data, coff, fb, genes, contigs, moc, ids, first_seqnum)
+            out[name] = RenderedText(data, coff, nf, float(r.t_kernels_ms[k]))
+        return out
+    finally:
+        self.L.pga_render_free(res)
+
+
+def _width(w):
+    if not isinstance(w, (int, np.integer)) or w < 1:
+        raise ValueError("`width` must be a positive integer")
+    return int(w)
+
+
+def _splice_fallback(ctx, name, opts, data, coff, fb, genes, contigs, moc, ids, first_seqnum):
+    """The lines the device flagged, rendered by the host writers' own code and put in place of the device's guesses."""
+    from . import lib
+    tinfs = {}
+    pieces, at = [], 0
+    shift = np.zeros(len(coff), np.int64)
+    starts = coff[:-1]
+    for gi, b, e in fb.tolist():
+        c = int(genes["contig"][gi])
+        m = int(moc[c])
+        if m not in tinfs:
+            tinfs[m] = lib.TrainingInfo(raw=ctx._models[m].tobytes())
+        line = lib._render_gene_line(name, genes[gi:gi + 1].tobytes(), tinfs[m], ids[c], first_seqnum + c,
+                                     gi - int(contigs["gene_begin"][c]), full_id=opts["full_id"],
+                                     include_translation_table=opts.get("include_translation_table", False),
+                                     version_separator=opts.get("version_separator", "_v"))
+        new = line.encode("utf-8")
+        pieces.append(data[at:b]); pieces.append(new)
+        at = e
+        shift[np.searchsorted(starts, b, side="right"):] += len(new) - (e - b)
+    pieces.append(data[at:])
+    return b"".join(pieces), coff + shift
+
+
+Context.render_genes = _render_genes
 Context.translate_genes = _translate_genes
 Context.train = _train
 Context.train_batch = _train_batch

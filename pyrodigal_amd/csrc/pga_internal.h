@@ -193,7 +193,14 @@ struct pga_ctx {
     int32_t dp_stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};    // pga_dp_stats
     double dp_timings[4] = {0, 0, 0, 0};               // pga_dp_timings
     int32_t extract_passes = 0;                        // pga_extract_stats: extraction passes of the last call (2: a tile overflowed the half-density staging)
+    // pga_render_genes: buffers kept across calls and grown as needed (render.hip): device scratch, device text, pinned text and
+    // a small pinned block for the totals; the text of a result lives in render_host until the next call on the context
+    char* render_dev = nullptr;  size_t render_dev_cap = 0;
+    char* render_text = nullptr; size_t render_text_cap = 0;
+    char* render_host = nullptr; size_t render_host_cap = 0;
+    unsigned long long* render_small = nullptr;
 };
+void pga_render_release(pga_ctx*);   // render.hip: frees the buffers above
 // summary of a segmented launch's flags (host copy, [PGA_SEG_ROUNDS][stride]) into pga_ctx::dp_stats
 void pga_dp_note_stats(pga_ctx* c, const DpSegPlan* plan, const int32_t* h_flags, int stride);
 

@@ -1,10 +1,9 @@
 // Device-side translation of gene records into proteins: one thread per codon.
-// ref: lib.pyx:2932-3047 (Gene.translate), 770-789 (Sequence._amino), _sequence.h:19-73 (stop / start codons per table),
-// _translation.h:4-42 (the genetic codes; restated here from the NCBI tables in TCAG order and re-indexed by the digit
-// alphabet of this library, A0 G1 C2 T3).
+// ref: lib.pyx:2932-3047 (Gene.translate), 770-789 (Sequence._amino); the codes and codon rules are in translate_rules.h.
 #include "pga_internal.h"
 #include <mutex>
 #include "pipeline.h"
+#include "translate_rules.h"
 
 #include <string.h>
 
@@ -15,55 +14,10 @@ pga_batch_view pga_batch_peek(const pga_batch*);      // finder.hip
 
 namespace {
 
-// NCBI genetic codes, 64 codons in TCAG order (first base slowest)
-struct Code { int tt; const char* aa; };
-const Code NCBI[] = {
-    {1, "FFLLSSSSYY**CC*WLLLLPPPPHHQQRRRRIIIMTTTTNNKKSSRRVVVVAAAADDEEGGGG"}, {2, "FFLLSSSSYY**CCWWLLLLPPPPHHQQRRRRIIMMTTTTNNKKSS**VVVVAAAADDEEGGGG"},
-    {3, "FFLLSSSSYY**CCWWTTTTPPPPHHQQRRRRIIMMTTTTNNKKSSRRVVVVAAAADDEEGGGG"}, {4, "FFLLSSSSYY**CCWWLLLLPPPPHHQQRRRRIIIMTTTTNNKKSSRRVVVVAAAADDEEGGGG"},
-    {5, "FFLLSSSSYY**CCWWLLLLPPPPHHQQRRRRIIMMTTTTNNKKSSSSVVVVAAAADDEEGGGG"}, {6, "FFLLSSSSYYQQCC*WLLLLPPPPHHQQRRRRIIIMTTTTNNKKSSRRVVVVAAAADDEEGGGG"},
-    {9, "FFLLSSSSYY**CCWWLLLLPPPPHHQQRRRRIIIMTTTTNNNKSSSSVVVVAAAADDEEGGGG"}, {10, "FFLLSSSSYY**CCCWLLLLPPPPHHQQRRRRIIIMTTTTNNKKSSRRVVVVAAAADDEEGGGG"},
-    {11, "FFLLSSSSYY**CC*WLLLLPPPPHHQQRRRRIIIMTTTTNNKKSSRRVVVVAAAADDEEGGGG"}, {12, "FFLLSSSSYY**CC*WLLLSPPPPHHQQRRRRIIIMTTTTNNKKSSRRVVVVAAAADDEEGGGG"},
-    {13, "FFLLSSSSYY**CCWWLLLLPPPPHHQQRRRRIIMMTTTTNNKKSSGGVVVVAAAADDEEGGGG"}, {14, "FFLLSSSSYYY*CCWWLLLLPPPPHHQQRRRRIIIMTTTTNNNKSSSSVVVVAAAADDEEGGGG"},
-    {15, "FFLLSSSSYY*QCC*WLLLLPPPPHHQQRRRRIIIMTTTTNNKKSSRRVVVVAAAADDEEGGGG"}, {16, "FFLLSSSSYY*LCC*WLLLLPPPPHHQQRRRRIIIMTTTTNNKKSSRRVVVVAAAADDEEGGGG"},
-    {21, "FFLLSSSSYY**CCWWLLLLPPPPHHQQRRRRIIMMTTTTNNNKSSSSVVVVAAAADDEEGGGG"}, {22, "FFLLSS*SYY*LCC*WLLLLPPPPHHQQRRRRIIIMTTTTNNKKSSRRVVVVAAAADDEEGGGG"},
-    {23, "FF*LSSSSYY**CC*WLLLLPPPPHHQQRRRRIIIMTTTTNNKKSSRRVVVVAAAADDEEGGGG"}, {24, "FFLLSSSSYY**CCWWLLLLPPPPHHQQRRRRIIIMTTTTNNKKSSSKVVVVAAAADDEEGGGG"},
-    {25, "FFLLSSSSYY**CCGWLLLLPPPPHHQQRRRRIIIMTTTTNNKKSSRRVVVVAAAADDEEGGGG"}, {26, "FFLLSSSSYY**CC*WLLLAPPPPHHQQRRRRIIIMTTTTNNKKSSRRVVVVAAAADDEEGGGG"},
-    {29, "FFLLSSSSYYYYCC*WLLLLPPPPHHQQRRRRIIIMTTTTNNKKSSRRVVVVAAAADDEEGGGG"}, {30, "FFLLSSSSYYEECC*WLLLLPPPPHHQQRRRRIIIMTTTTNNKKSSRRVVVVAAAADDEEGGGG"},
-    {32, "FFLLSSSSYY*WCC*WLLLLPPPPHHQQRRRRIIIMTTTTNNKKSSRRVVVVAAAADDEEGGGG"}, {33, "FFLLSSSSYYY*CCWWLLLLPPPPHHQQRRRRIIIMTTTTNNKKSSSKVVVVAAAADDEEGGGG"},
-};
+using namespace pga_tr;
+
 __constant__ char c_code[34][64];      // [table][a << 4 | b << 2 | c] with A0 G1 C2 T3; all-zero rows = unknown tables
 __constant__ unsigned char c_known[34];
-
-__device__ __forceinline__ bool tt_in(const int tt, const unsigned long long set) { return (set >> tt) & 1ull; }
-#define TTS(...) tts_of({__VA_ARGS__})
-__device__ __host__ constexpr unsigned long long tts_of(std::initializer_list<int> l) { unsigned long long m = 0; for (int t : l) m |= 1ull << t; return m; }
-
-// ref: _sequence.h:19-43
-__device__ __forceinline__ bool codon_stop(const int x0, const int x1, const int x2, const int tt) {
-    if (x0 == 0 && tt == 2) return x1 == 1 && (x2 == 0 || x2 == 1);                                   // AGA / AGG
-    if (x0 != 3) return false;
-    if (x1 == 0 && x2 == 1) return tt_in(tt, TTS(1, 2, 3, 4, 5, 9, 10, 11, 12, 13, 14, 21, 23, 24, 25, 26, 33));     // TAG
-    if (x1 == 1 && x2 == 0) return tt_in(tt, TTS(1, 6, 11, 12, 15, 16, 22, 23, 26, 29, 30, 32));                      // TGA
-    if (x1 == 0 && x2 == 0) return tt_in(tt, TTS(1, 2, 3, 4, 5, 9, 10, 11, 12, 13, 15, 16, 21, 22, 23, 24, 25, 26, 32));   // TAA
-    if (tt == 22) return x1 == 2 && x2 == 0;                                                            // TCA
-    if (tt == 23) return x1 == 3 && x2 == 0;                                                            // TTA
-    return false;
-}
-// ref: _sequence.h:45-73
-__device__ __forceinline__ bool codon_start(const int x0, const int x1, const int x2, const int tt) {
-    if (x1 != 3 || x2 != 1) return false;
-    if (x0 == 0) return true;
-    if (tt_in(tt, TTS(6, 10, 14, 15, 16, 2))) return false;
-    if (x0 == 1) return !(tt == 1 || tt == 3 || tt == 12 || tt == 2);
-    if (x0 == 3) return !(tt < 4 || tt == 9 || (tt >= 21 && tt < 25));
-    return false;
-}
-__device__ __forceinline__ int digit_of(const int ch, const bool comp) {
-    int d;
-    switch (ch) { case 'A': case 'a': d = 0; break; case 'G': case 'g': d = 1; break; case 'C': case 'c': d = 2; break;
-                  case 'T': case 't': d = 3; break; default: return 6; }
-    return comp ? 3 - d : d;            // A <-> T, G <-> C
-}
 
 __global__ void __launch_bounds__(256)
 k_translate(const char* __restrict__ seq, const ContigDesc* __restrict__ ct, const pga_gene* __restrict__ genes, const int64_t n_genes,
@@ -88,21 +42,7 @@ k_translate(const char* __restrict__ seq, const ContigDesc* __restrict__ ct, con
     }
     // partial flags are in sequence orientation; the gene's own first codon follows its strand
     const bool start_edge = g.strand == 1 ? g.partial_begin : g.partial_end;
-    int aa;
-    if (x0 <= 3 && x1 <= 3 && x2 <= 3) {
-        if (codon_stop(x0, x1, x2, tt)) aa = '*';
-        else if (i == 0 && !start_edge && codon_start(x0, x1, x2, tt)) aa = 'M';
-        else aa = c_code[tt][(x0 << 4) + (x1 << 2) + x2];
-    } else {
-        aa = 'X';
-        if (!strict && x0 <= 3 && (x1 <= 3) != (x2 <= 3)) {
-            // one unknown base in second or third position: unambiguous when all four completions agree
-            aa = c_code[tt][(x0 << 4) + ((x1 <= 3 ? x1 : 0) << 2) + (x2 <= 3 ? x2 : 0)];
-            for (int y = 1; y < 4; y++)
-                if (c_code[tt][(x0 << 4) + ((x1 <= 3 ? x1 : y) << 2) + (x2 <= 3 ? x2 : y)] != aa) { aa = 'X'; break; }
-        }
-    }
-    out[idx] = (char)(aa == 'X' ? unk : aa);
+    out[idx] = translate_codon(c_code[tt], x0, x1, x2, tt, i, start_edge, strict, unk);
 }
 
 // the tables are __constant__ symbols: one copy per DEVICE, so readiness is tracked per device (several GPUs may be driven
@@ -112,18 +52,11 @@ bool g_tables_ready[64] = {false};
 int upload_tables() {
     static char code[34][64];
     static unsigned char known[34];
-    memset(code, 0, sizeof code); memset(known, 0, sizeof known);
-    const int ncbi_of_digit[4] = {2, 3, 1, 0};        // digit (A G C T) -> position in TCAG
-    for (const Code& c : NCBI) {
-        known[c.tt] = 1;
-        for (int a = 0; a < 4; a++) for (int b = 0; b < 4; b++) for (int d = 0; d < 4; d++)
-            code[c.tt][(a << 4) + (b << 2) + d] = c.aa[ncbi_of_digit[a] * 16 + ncbi_of_digit[b] * 4 + ncbi_of_digit[d]];
-    }
+    code_table(code, known);
     if (hipMemcpyToSymbol(HIP_SYMBOL(c_code), code, sizeof code) != hipSuccess) return PGA_EDEVICE;
     if (hipMemcpyToSymbol(HIP_SYMBOL(c_known), known, sizeof known) != hipSuccess) return PGA_EDEVICE;
     return PGA_OK;
 }
-bool table_known(const int tt) { for (const Code& c : NCBI) if (c.tt == tt) return true; return false; }
 
 }  // namespace
 

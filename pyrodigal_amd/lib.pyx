@@ -137,7 +137,7 @@ MIN_SINGLE_GENOME = 20000
 IDEAL_SINGLE_GENOME = 100000
 TRANSLATION_TABLES = frozenset(set(range(1, 7)) | set(range(9, 17)) | set(range(21, 27)) | {29, 30, 32, 33})
 PRODIGAL_VERSION = "v2.6.3+c1e2d36"
-_VERSION = "0.1.0"
+from pyrodigal_amd import __version__ as _VERSION      # one definition: the package's
 TRAINING_INFO_SIZE = 558392
 
 _RBS_MOTIF = [
@@ -2200,3 +2200,26 @@ def _seq_pointers(list seqs):
         l[i] = len(<bytes> o)
         total += l[i]
     return ptrs, lens, total
+
+
+def _render_gene_line(str fmt, bytes rec, TrainingInfo training_info not None, str sequence_id, ssize_t num_seq, ssize_t index,
+                      bint full_id=False, bint include_translation_table=False, str version_separator="_v"):
+    """One line as the host writers print it, for the device renderer's flagged lines (`_cabi.Context.render_genes`): the
+    gene line of `write_gff` (fmt "gff") or the record header of `write_translations` / `write_genes` (fmt "faa" / "fna"), for
+    gene `index` of its sequence whose packed record is `rec`."""
+    if len(rec) != sizeof(pga_gene):
+        raise ValueError("a gene record is %d bytes" % sizeof(pga_gene))
+    cdef Genes owner = Genes.__new__(Genes)
+    owner.training_info = training_info
+    cdef Gene gene = Gene.__new__(Gene)
+    gene.owner = owner
+    gene.g = (<const pga_gene*> PyBytes_AS_STRING(rec))[0]
+    ident = gene._gene_data(sequence_id if full_id else num_seq, index)
+    if fmt != "gff":
+        return ">%s_%d # %d # %d # %d # %s\n" % (sequence_id, index + 1, gene.g.begin, gene.g.end, gene.g.strand, ident)
+    line = "%s\tpyrodigal_amd%s%s\tCDS\t%d\t%d\t%.1f\t%s\t0\t%s;" % (
+        sequence_id, version_separator, _VERSION, gene.g.begin, gene.g.end, gene.g.sscore + gene.g.cscore,
+        "+" if gene.g.strand > 0 else "-", ident)
+    if include_translation_table:
+        line += "transl_table=%d;" % training_info.translation_table
+    return line + gene._score_data() + "\n"

@@ -147,3 +147,99 @@ def find_genes_fasta(path, model_blobs, n_contexts=2, device=0, max_bases=64 << 
         if own:
             for c in ctxs:
                 c.close()
+
+
+def render_fasta(path, model_blobs, *, gff=None, faa=None, fna=None, n_contexts=2, device=0, max_bases=64 << 20, meta=False,
+                 descriptions=None, first_seqnum=1, gff_options=None, faa_options=None, fna_options=None, unbinned_model=None,
+                 **find_kw):
+    """Call the genes of every record of a FASTA file and write them as text: GFF to ``gff``, protein FASTA to ``faa``, gene
+    FASTA to ``fna`` (binary file objects, or None), in file order -- what ``Genes.write_gff`` / ``write_translations`` /
+    ``write_genes`` write record after record.
+
+    Runs like :func:`find_genes_fasta` (the C reader fills pinned arenas, ``n_contexts`` contexts side by side), but every batch
+    is rendered on the device while it is still resident (``Context.render_genes``) and only its text comes back: memory stays
+    bounded by the batch size.  Sequence ids are the first word of the headers, seqnums count records from ``first_seqnum``.
+    ``*_options``: the writer's keyword arguments of that format; ``unbinned_model``: see ``Context.render_genes``; ``find_kw``
+    goes to ``Context.find_genes``.  Returns
+    ``{"records", "bases", "genes", "fallback", "kernel_ms": {format: ms}}``."""
+    formats = {}
+    for name, fh, opts in (("gff", gff, gff_options), ("faa", faa, faa_options), ("fna", fna, fna_options)):
+        if fh is not None:
+            formats[name] = dict(opts or {})
+    stats = {"records": 0, "bases": 0, "genes": 0, "fallback": 0, "kernel_ms": {k: 0.0 for k in formats}}
+    if not formats:
+        raise ValueError("render_fasta: no output requested")
+    sinks = {"gff": gff, "faa": faa, "fna": fna}
+    ctxs = [_cabi.Context(device) for _ in range(max(1, n_contexts))]
+    for c in ctxs:
+        c.set_models(list(model_blobs))
+    todo = queue.Queue(maxsize=len(ctxs))
+    done, failure = {}, []
+    cv = threading.Condition()
+
+    def worker(ctx):
+        while True:
+            item = todo.get()
+            if item is None:
+                return
+            i, seqnum, pb = item
+            try:
+                ids, n, total = pb.ids, pb.n, pb.total
+                b = ctx.upload_packed(pb)                 # releases the arena
+                try:
+                    r = ctx.find_genes(b, meta=meta, **find_kw)
+                    text = ctx.render_genes(b, r, ids, formats, meta=meta, descriptions=descriptions, first_seqnum=seqnum,
+                                            unbinned_model=unbinned_model)
+                finally:
+                    b.close()
+                res = (n, total, len(r.genes), text)
+            except BaseException as e:
+                pb.release()
+                res = e
+                failure.append(e)
+            with cv:
+                done[i] = res
+                cv.notify_all()
+
+    threads = [threading.Thread(target=worker, args=(c,), daemon=True) for c in ctxs]
+    for t in threads:
+        t.start()
+    reader = _cabi.FastaReader(path)
+    try:
+        nxt, submitted, seqnum = 0, 0, first_seqnum
+        it = reader.packed_batches(max_bases=max_bases, n_arenas=len(ctxs) + 2)
+        exhausted = False
+        while True:
+            while not exhausted and submitted - nxt < len(ctxs) + 1 and not failure:
+                try:
+                    pb = next(it)
+                except StopIteration:
+                    exhausted = True
+                    break
+                todo.put((submitted, seqnum, pb))
+                seqnum += pb.n
+                submitted += 1
+            if nxt == submitted and exhausted:
+                break
+            with cv:
+                while nxt not in done:
+                    cv.wait()
+                res = done.pop(nxt)
+            nxt += 1
+            if isinstance(res, BaseException):
+                raise res
+            n, total, n_genes, text = res
+            for name, t in text.items():
+                sinks[name].write(t.data)
+                stats["fallback"] += t.fallback
+                stats["kernel_ms"][name] += t.kernel_ms
+            stats["records"] += n; stats["bases"] += total; stats["genes"] += n_genes
+        return stats
+    finally:
+        for _ in threads:
+            todo.put(None)
+        for t in threads:
+            t.join()
+        reader.close()
+        for c in ctxs:
+            c.close()
