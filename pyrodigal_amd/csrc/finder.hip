@@ -1862,6 +1862,23 @@ static int find_impl(pga_ctx* c, const pga_batch* batch, const pga_params* pp, c
             sl.starts_only = stage == 0 && !(getenv("PGA_SS_STARTS_ONLY") && atoi(getenv("PGA_SS_STARTS_ONLY")) == 0);
             sl.n_starts = (int32_t)(group_nodes[g] - sl.n_stops);
             sl.blk_chain = d_ovl_blk + ovl_blk0[(size_t)g];
+            // the model-major start scoring: its records, chains and tiles live in the context (PGA_SS_MM=0: the model loop).  With one
+            // model loaded the model loop has nothing to walk (one staging, one barrier per workgroup) and stays: on a 200 Mbp genome the
+            // two kernels took 2 ms more (k_mm_place writes a chain's thousands of tiles from one thread)
+            if (sl.starts_only && sl.n_starts > 0 && NM > 1 && !(getenv("PGA_SS_MM") && atoi(getenv("PGA_SS_MM")) == 0)) {
+                std::vector<int64_t> mm_items;
+                sl.mm_tiles = pga_mm_tiles(chains.data() + g_c0[g], nch, h_cbase + (size_t)g * (NC + 1), h_sbase + (size_t)g * (NC + 1), NM, mm_items);
+                char nm[32];
+                void* p__;
+                snprintf(nm, sizeof nm, "ss_rec%d", g);
+                { int rc__ = ensure_dev(c, nm, PGA_SS_REC_BYTES * (size_t)sl.n_starts + 64, &p__); if (rc__) return rc__; sl.mm_rec = p__; }
+                snprintf(nm, sizeof nm, "ss_mmchain%d", g);
+                { int rc__ = ensure_dev(c, nm, PGA_SS_MMCHAIN_BYTES * (size_t)nch + 64, &p__); if (rc__) return rc__; sl.mm_chain = p__; }
+                snprintf(nm, sizeof nm, "ss_mmtile%d", g);
+                { int rc__ = ensure_dev(c, nm, PGA_SS_MMTILE_BYTES * (size_t)sl.mm_tiles + 64, &p__); if (rc__) return rc__; sl.mm_tile = p__; }
+                snprintf(nm, sizeof nm, "ss_mmscratch%d", g);
+                { int rc__ = ensure_dev(c, nm, pga_mm_scratch_bytes(NM, nch), &p__); if (rc__) return rc__; sl.mm_scratch = p__; }
+            }
             sp.cs_out = nullptr;
             if (wave_prep) {
                 sl.topo_q2 = wgroups.g[g].q2; sl.ext = wbuf.ext; sp.cs_out = wbuf.cs;

@@ -77,7 +77,7 @@ struct ScoreParams {
     uint8_t* conv_flag;      // per contig (of the group being scored), or nullptr: set when the contig holds a start node that the
                              // reference turns into an edge node while scoring (lib.pyx:2424-2434) -- only such contigs are scored
                              // differently by the first and by a later model of a run
-    unsigned long long* prof = nullptr;   // PGA_SS_PROFILE=1: wave-cycles per phase of k_score_starts (16 slots), or nullptr
+    unsigned long long* prof = nullptr;   // PGA_SS_PROFILE=1: wave-cycles per phase of k_score_starts / k_score_starts_mm (16 slots), or nullptr
     int32_t models_per_pass = 512;        // k_score_starts walks a workgroup's models in sets of this many (<= 512; PGA_SS_MODELS_PER_PASS: tests)
     int32_t lean_stops = 0;               // 1: of a stop node's per-chain fields only `edge` is written (round 6).  A stop node carries no start
                                           // scores (reset_node_scores: zeros); the wave-batch connection scorer, the overlapping-start search and the
@@ -117,7 +117,19 @@ struct StopLaunch {
     // per workgroup of k_ovl_stops (256 pairs from soff_begin on): the chain of its first pair, relative to the launch's first chain
     // (the caller's plan; nullptr: the workgroup searches)
     const int32_t* blk_chain = nullptr;
+    // the listed start scoring as a per-start prologue and a model-major pass over (chain, start) items (k_start_prologue,
+    // k_score_starts_mm; PGA_SS_MM=0 or mm_tiles == 0: the model loop of k_score_starts).  The caller sizes the context's buffers:
+    void* mm_rec = nullptr;              // SsStartRec per start node of the group (n_starts)
+    void* mm_chain = nullptr;            // SsMmChain per chain of the launch (n_chains)
+    void* mm_tile = nullptr;             // SsMmTile per tile (mm_tiles)
+    void* mm_scratch = nullptr;          // pga_mm_scratch_bytes(n_models, n_chains)
+    int32_t mm_tiles = 0;                // sum over models of ceil(items of the model / pga_mm_tile_items()) (pga_mm_tiles)
 };
+// (chain, start) items of the model-major start scoring: tiles of pga_mm_tile_items() items of one model each
+int pga_mm_tile_items();
+int32_t pga_mm_tiles(const ChainDesc* h_chains, int n_chains, const int32_t* h_cbase, const int32_t* h_sbase, int n_models, std::vector<int64_t>& scratch);
+size_t pga_mm_scratch_bytes(int n_models, int n_chains);
+constexpr size_t PGA_SS_REC_BYTES = 32, PGA_SS_MMCHAIN_BYTES = 32, PGA_SS_MMTILE_BYTES = 16;
 // per (group, contig): is any model of the group inside the contig's GC window?  (meta mode)
 void pga_launch_group_enable(const ContigDesc* d_ct, int n_contigs, const int32_t* d_gc_count, const double* d_model_gc,
                              const int32_t* d_model_group, int n_models, int n_groups, uint8_t* d_enabled, hipStream_t st);

@@ -2211,6 +2211,418 @@ k_score_starts(const ChainDesc* __restrict__ chains, const int2* __restrict__ co
     }
 }
 
+// ------------------------------------------------------------------- start scoring, model-major (the listed launches)
+// k_score_starts spends a third of its wave-cycles on the per-node prologue (a chain of dependent loads: start_list, contig_of,
+// contig_chains, chains, node_contig_base, the sequence) and another third on its model loop (a barrier round per model of the
+// union of a workgroup's contigs, with the lanes of the contigs that lack the model idle).  The listed launches split it in two:
+// k_start_prologue does what does not depend on the model once per start node and leaves a 32-byte record; k_score_starts_mm takes
+// one (chain, start) item per lane, items in model-major order (model, its contigs, their starts), so a workgroup stages ONE model
+// and crosses one barrier.  The scores are the same expressions in the same order as in k_score_starts.
+struct SsStartRec {
+    unsigned long long ucodes;     // the upstream composition codes (u = 1, 2, 15 .. 44), as k_score_starts packs them
+    unsigned long long w1;         // zm (42) | nups << 42 (6) | min(start, 63) << 48 (6) | type << 54 (2) | reverse << 56 | edge0 << 57 |
+                                   // conv << 58 | ups_near_edge << 59 | ups_first << 60 | ups_later << 61
+    unsigned long long w2;         // isA >> 1 (u = 1 .. 20) | isG >> 1 << 20 | stop3 << 40
+    unsigned long long w3;         // the node's index in its contig | min(orf, 65535) << 32  (every test of orf is below 300)
+};
+static_assert(sizeof(SsStartRec) == PGA_SS_REC_BYTES, "SsStartRec");
+// One chain of the model-major order (the chains with at least one start node): where its fields go, its items
+struct SsMmChain {
+    int64_t off;          // ChainDesc::off
+    int64_t raw;          // where the raw coding scores are (ChainDesc::raw_off, or off)
+    int32_t item0, n;     // its items [item0, item0 + n): the start nodes of its contig
+    int32_t rdelta;       // start rank (entry of GroupArrays::start_list) of item q: q + rdelta
+    uint32_t len_first;   // the contig's length | ChainDesc::first << 31
+};
+static_assert(sizeof(SsMmChain) == PGA_SS_MMCHAIN_BYTES, "SsMmChain");
+// The items of a tile, all of one model: chains [j0, j_last] of the model-major order hold them.  model_sd: the model | its uses_sd << 31
+// (the workgroup knows which tables to stage without waiting for the model)
+struct SsMmTile { int32_t j0, j_last, item0, model_sd; };
+static_assert(sizeof(SsMmTile) == PGA_SS_MMTILE_BYTES, "SsMmTile");
+constexpr unsigned long long SS_ITEM_MASK = (1ull << 40) - 1ull;
+// a model's counter of k_mm_count on a 128-byte line of its own: sixteen counters on two lines serialised 26 000 atomics (41 us per launch)
+constexpr int SS_CNT_STRIDE = 16;
+constexpr int SS_TILE_DEFAULT = 1024;      // items per tile (PGA_SS_MM_TILE: 256 / 512 / 1024)
+
+// The start scorer's model, one per workgroup: the RBS table (SD models) or the small motif tables (the others), never both
+struct StartModelMm {
+    double st_wt, no_mot;
+    int tt, uses_sd;
+    double type_wt[3];
+    double rbs_wt[28];
+    double ups[32][4];      // 0.4 * st_wt * ups_comp
+    union {
+        struct { double mk0[4][64]; double mk1[4][256]; } mot;     // mot_wt[0] / mot_wt[1]
+        unsigned lut[PGA_SD_LUT];                                  // k_sd_lut
+    };
+};
+
+// A thread per start node of the group (its rank in start_list): what k_score_starts computes before its model loop
+__global__ void __launch_bounds__(256)
+k_start_prologue(const int2* __restrict__ contig_chains, const int32_t* __restrict__ node_contig_base, int n_contigs,
+                 const uint8_t* __restrict__ dig, const ContigDesc* __restrict__ ct, GroupArrays ga, ScoreParams sp,
+                 const int32_t* __restrict__ start_list, const int n_starts, SsStartRec* __restrict__ rec) {
+    __shared__ int2 s_edge[SS_EDGE_CONTIGS][2 * SS_EDGE_SPAN];
+    const int tid = threadIdx.x;
+    const int blk0 = blockIdx.x * blockDim.x;
+    const int r = blk0 + tid;
+    const bool in_range = r < n_starts;
+    const int t = start_list[min(r, n_starts - 1)];
+    const bool closed = sp.closed != 0;
+    const int c0 = ga.contig_of[start_list[blk0]];
+    const int c = in_range ? ga.contig_of[t] : c0;
+    const bool has = in_range && contig_chains[c].y > 0;      // (a contig without chains has no items: its starts need no record)
+    if (tid < SS_EDGE_CONTIGS * 2 * SS_EDGE_SPAN) {
+        const int ec = c0 + tid / (2 * SS_EDGE_SPAN), q = tid % (2 * SS_EDGE_SPAN);
+        int2 e = make_int2(0, 0);
+        if (ec < n_contigs) { const int tb = node_contig_base[ec]; e = edge_candidate(ga, tb, node_contig_base[ec + 1] - tb, ct[ec].len, q, closed); }
+        s_edge[tid / (2 * SS_EDGE_SPAN)][q] = e;
+    }
+    const int tbase = node_contig_base[c];
+    const int i = t - tbase, n = has ? node_contig_base[c + 1] - tbase : 1;
+    int L = 3, ndx = 0, sv = 0, strand = 1, start = 0, type = 0, e0 = 0;
+    bool conv = false, ups_first = false, ups_later = false, ups_near_edge = false;
+    UpWin W{0, 0, 0, 0, 0};
+    unsigned long long ucodes = 0ull; int nups = 0;
+    long orf = 1;
+    int stop3 = 0;
+    if (has) {
+        const ContigDesc cd = ct[c];
+        L = cd.len;
+        const uint8_t* __restrict__ d = dig + cd.base;
+        ndx = ga.ndx[t]; sv = ga.stop_val[t]; strand = ga.strand[t]; type = ga.type[t]; e0 = ga.edge0[t];
+        conv = !closed && !e0 && ((ndx <= 2 && strand == 1) || (ndx >= L - 3 && strand == -1));
+        if (conv && sp.conv_flag != nullptr) sp.conv_flag[c] = 1;
+        start = strand == 1 ? ndx : L - 1 - ndx;
+        W = load_upwin(d, L, start, strand);
+        ucodes = ((W.p0 >> 2) & 0xfull) | ((W.p0 >> 30) << 4) | ((W.p1 & 0x3ffffffull) << 38);
+        nups = start >= 2 ? 2 + min(max(start - 14, 0), 30) : (start >= 1 ? 1 : 0);
+        orf = ndx > sv ? ndx - sv : sv - ndx;
+        const int s0 = strand == 1 ? sv : L - 1 - sv;
+        stop3 = sbase(d, L, s0, strand) | (sbase(d, L, s0 + 1, strand) << 8) | (sbase(d, L, s0 + 2, strand) << 16);
+    }
+    __syncthreads();            // the edge candidates are complete
+    if (has) {
+        // (the edge scan of k_score_starts)
+        if (!closed && ndx <= 2 && strand == 1) ups_near_edge = true;
+        else if (!closed && ndx >= L - 3 && strand == -1) ups_near_edge = true;
+        else if ((i < 500 && strand == 1) || (i + 500 >= n && strand == -1)) {
+            const int ecx = c - c0;
+            for (int q = 0; q < 2 * SS_EDGE_SPAN; q++) {
+                const int j = q < SS_EDGE_SPAN ? q : n - 2 * SS_EDGE_SPAN + q;
+                if (strand == 1 ? j >= i : j <= i) continue;
+                const int2 e = ecx < SS_EDGE_CONTIGS ? s_edge[ecx][q] : edge_candidate(ga, tbase, n, L, q, closed);
+                if (!(e.y & 4) || sv != e.x) continue;
+                if (e.y & 1) { ups_first = ups_later = true; }
+                else if (e.y & 2) { if (strand == 1) ups_first = true; ups_later = true; }
+            }
+        }
+        SsStartRec R;
+        R.ucodes = ucodes;
+        R.w1 = (W.zm & ((1ull << 42) - 1ull)) | ((unsigned long long)nups << 42) | ((unsigned long long)min(start, 63) << 48) |
+               ((unsigned long long)(type & 3) << 54) | ((unsigned long long)(strand != 1) << 56) | ((unsigned long long)(e0 != 0) << 57) |
+               ((unsigned long long)conv << 58) | ((unsigned long long)ups_near_edge << 59) | ((unsigned long long)ups_first << 60) |
+               ((unsigned long long)ups_later << 61);
+        R.w2 = (unsigned long long)((W.isA >> 1) & 0xfffffu) | ((unsigned long long)((W.isG >> 1) & 0xfffffu) << 20) |
+               ((unsigned long long)(unsigned)(stop3 & 0xffffff) << 40);
+        R.w3 = (unsigned long long)(unsigned)i | ((unsigned long long)min(orf, 65535L) << 32);
+        ulonglong2* const o = (ulonglong2*)&rec[r];
+        o[0] = make_ulonglong2(R.ucodes, R.w1); o[1] = make_ulonglong2(R.w2, R.w3);
+    }
+}
+
+// The stop nodes of the listed launches: no start scores (reset_node_scores), in every chain of their contig; a thread per entry of
+// GroupArrays::stop_list (with lean_stops only `edge`)
+__global__ void __launch_bounds__(256)
+k_clear_stops(const ChainDesc* __restrict__ chains, const int2* __restrict__ contig_chains, const int32_t* __restrict__ node_contig_base,
+              GroupArrays ga, ChainArrays ca, ScoreParams sp, const int n_stops) {
+    const int k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= n_stops) return;
+    const int z = ga.stop_list[k];
+    const int cz = ga.contig_of[z];
+    const int2 zc = contig_chains[cz];
+    const int zb = node_contig_base[cz];
+    const uint8_t ez = ga.edge0[z];
+    for (int m = 0; m < zc.y; m++) {
+        const int64_t gz = chains[zc.x + m].off + (z - zb);
+        ca.edge[gz] = ez;
+        if (sp.lean_stops) continue;
+        ca.cscore[gz] = 0.0; ca.sscore[gz] = 0.0; ca.rscore[gz] = 0.0; ca.uscore[gz] = 0.0; ca.tscore[gz] = 0.0; ca.mot_score[gz] = 0.0;
+        ca.mot_ndx[gz] = 0; ca.mot_len[gz] = 0; ca.mot_spacer[gz] = 0; ca.mot_spacendx[gz] = 0; ca.rbs[2 * gz] = 0; ca.rbs[2 * gz + 1] = 0;
+        if (sp.cs_out != nullptr) sp.cs_out[gz] = 0.0;
+    }
+}
+
+// The model-major order, built on the device from the launch's chains: k_mm_count takes every chain with start nodes a slot among
+// its model's chains and items (one 64-bit atomic: chain count << 40 | items), k_mm_scan lays the models out, k_mm_place writes the
+// chains and the tiles.  (The order of a model's chains depends on the atomics; every item's stores do not.)
+__device__ __forceinline__ int mm_starts_of(const int32_t* __restrict__ cbase, const int32_t* __restrict__ sbase, const int c) {
+    return (cbase[c + 1] - cbase[c]) - (sbase[c + 1] - sbase[c]);
+}
+// (a workgroup counts its chains in LDS first and adds its sums with one global atomic per model: the chains of sixteen models on their
+//  sixteen counters serialised 26 000 atomics, 27 us per launch even with every counter on a line of its own; more than SS_CNT_LDS models:
+//  the global atomics directly)
+constexpr int SS_CNT_LDS = 2048;
+__global__ void __launch_bounds__(256)
+k_mm_count(const ChainDesc* __restrict__ chains, int n_chains, const int32_t* __restrict__ cbase, const int32_t* __restrict__ sbase,
+           int n_models, unsigned long long* __restrict__ cnt, int2* __restrict__ slot) {
+    __shared__ unsigned long long s_cnt[SS_CNT_LDS];
+    const int tid = threadIdx.x;
+    const int k = blockIdx.x * blockDim.x + tid;
+    const bool lds = n_models <= SS_CNT_LDS;
+    const int model = k < n_chains ? chains[k].model : 0;
+    const int n = k < n_chains ? mm_starts_of(cbase, sbase, chains[k].contig) : 0;
+    const unsigned long long one = (1ull << 40) | (unsigned long long)n;
+    if (lds) {
+        for (int m = tid; m < n_models; m += blockDim.x) s_cnt[m] = 0ull;
+        __syncthreads();
+    }
+    unsigned long long v = 0ull;
+    if (n > 0) v = lds ? atomicAdd(&s_cnt[model], one) : atomicAdd(&cnt[(size_t)model * SS_CNT_STRIDE], one);
+    if (lds) {
+        __syncthreads();
+        for (int m = tid; m < n_models; m += blockDim.x) {
+            const unsigned long long b = s_cnt[m];
+            if (b != 0ull) s_cnt[m] = atomicAdd(&cnt[(size_t)m * SS_CNT_STRIDE], b);     // the workgroup's base among the model's chains / items
+        }
+        __syncthreads();
+        if (n > 0) v += s_cnt[model];
+    }
+    if (k < n_chains) slot[k] = n > 0 ? make_int2((int)(v >> 40), (int)(v & SS_ITEM_MASK)) : make_int2(-1, 0);
+}
+// one workgroup: per model its first chain, first item and first tile (base[0 / 1 / 2][model])
+__global__ void __launch_bounds__(256)
+k_mm_scan(const unsigned long long* __restrict__ cnt, int n_models, const int tile, int32_t* __restrict__ base) {
+    __shared__ int s_part[3][257];
+    const int tid = threadIdx.x;
+    const int per = (n_models + 255) / 256, m0 = min(tid * per, n_models), m1 = min(m0 + per, n_models);
+    int a = 0, b = 0, t = 0;
+    for (int m = m0; m < m1; m++) {
+        const unsigned long long v = cnt[(size_t)m * SS_CNT_STRIDE];
+        const int items = (int)(v & SS_ITEM_MASK);
+        a += (int)(v >> 40); b += items; t += (items + tile - 1) / tile;
+    }
+    s_part[0][tid] = a; s_part[1][tid] = b; s_part[2][tid] = t;
+    __syncthreads();
+    if (tid < 3) {
+        int acc = 0;
+        for (int q = 0; q < 256; q++) { const int v = s_part[tid][q]; s_part[tid][q] = acc; acc += v; }
+    }
+    __syncthreads();
+    a = s_part[0][tid]; b = s_part[1][tid]; t = s_part[2][tid];
+    for (int m = m0; m < m1; m++) {
+        base[m] = a; base[n_models + m] = b; base[2 * n_models + m] = t;
+        const unsigned long long v = cnt[(size_t)m * SS_CNT_STRIDE];
+        const int items = (int)(v & SS_ITEM_MASK);
+        a += (int)(v >> 40); b += items; t += (items + tile - 1) / tile;
+    }
+}
+__global__ void __launch_bounds__(256)
+k_mm_place(const ChainDesc* __restrict__ chains, int n_chains, const int32_t* __restrict__ cbase, const int32_t* __restrict__ sbase,
+           const ContigDesc* __restrict__ ct, const unsigned long long* __restrict__ cnt, const int2* __restrict__ slot,
+           const int32_t* __restrict__ base, int n_models, const int tile, const pga_training* __restrict__ models, SsMmChain* __restrict__ mm,
+           SsMmTile* __restrict__ tiles) {
+    const int k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= n_chains) return;
+    const int2 s = slot[k];
+    if (s.x < 0) return;
+    const ChainDesc& ch = chains[k];
+    const int m = ch.model, c = ch.contig;
+    const int n = mm_starts_of(cbase, sbase, c);
+    const int j = base[m] + s.x, ib = base[n_models + m], tb = base[2 * n_models + m];
+    const int items_m = (int)(cnt[(size_t)m * SS_CNT_STRIDE] & SS_ITEM_MASK);
+    SsMmChain q;
+    q.off = ch.off; q.raw = ch.raw_off >= 0 ? ch.raw_off : ch.off;
+    q.item0 = ib + s.y; q.n = n;
+    q.rdelta = (cbase[c] - sbase[c]) - q.item0;
+    q.len_first = (uint32_t)ct[c].len | (ch.first ? 0x80000000u : 0u);
+    mm[j] = q;
+    // the model's tiles whose first / last item is one of this chain's (model-relative items [s.y, s.y + n))
+    for (int tk = s.y / tile; tk <= (s.y + n - 1) / tile; tk++) {
+        const int f = tile * tk, l = min(f + tile, items_m) - 1;
+        if (f >= s.y) { tiles[tb + tk].j0 = j; tiles[tb + tk].item0 = ib + f; tiles[tb + tk].model_sd = m | (models[m].uses_sd ? (int)0x80000000u : 0); }
+        if (l < s.y + n) tiles[tb + tk].j_last = j;
+    }
+}
+
+// A thread per (chain, start) item of a tile of TILE items: the tile's model and chains are staged in LDS, the lane finds its chain
+// there, reads its start's record and the raw coding score, and scores as k_score_starts does.
+template <int TILE>
+__global__ void __launch_bounds__(TILE, 8)      // (eight waves per SIMD: 64 registers)
+k_score_starts_mm(const SsMmTile* __restrict__ tiles, const SsMmChain* __restrict__ mm, const SsStartRec* __restrict__ rec,
+                  const pga_training* __restrict__ models, ChainArrays ca, ScoreParams sp, const unsigned* __restrict__ sd_lut) {
+    __shared__ StartModelMm SM;
+    __shared__ int32_t s_item0[TILE], s_n[TILE], s_rdelta[TILE];
+    __shared__ uint32_t s_lf[TILE];
+    __shared__ int64_t s_off[TILE], s_raw[TILE];
+    unsigned long long* __restrict__ prof = sp.prof;
+    unsigned long long tp = prof ? __builtin_readcyclecounter() : 0;
+    auto mark = [&](const int slot) {
+        if (!prof) return;
+        const unsigned long long now = __builtin_readcyclecounter();
+        if ((int)(threadIdx.x & 63) == __builtin_ctzll(__ballot(1))) atomicAdd(&prof[slot], now - tp);
+        tp = now;
+    };
+    const int tid = threadIdx.x;
+    const SsMmTile T = tiles[blockIdx.x];
+    const int nj = min(T.j_last - T.j0 + 1, TILE);
+    // ---- the model and the tile's chains
+    const pga_training* __restrict__ tm = &models[T.model_sd & 0x7fffffff];
+    const int uses_sd = T.model_sd < 0;
+    if (tid == 0) { SM.st_wt = tm->st_wt; SM.no_mot = tm->no_mot; SM.tt = tm->trans_table; SM.uses_sd = uses_sd; }
+    else if (tid >= 4 && tid < 7) SM.type_wt[tid - 4] = tm->type_wt[tid - 4];
+    else if (tid >= 32 && tid < 60) SM.rbs_wt[tid - 32] = tm->rbs_wt[tid - 32];
+    else if (tid >= 128 && tid < 256) (&SM.ups[0][0])[tid - 128] = 0.4 * tm->st_wt * (&tm->ups_comp[0][0])[tid - 128];
+    if (uses_sd) {
+        for (int k = tid; k < PGA_SD_LUT; k += TILE) SM.lut[k] = sd_lut[k];
+    } else {
+        if (tid < 256) SM.mot.mk0[tid >> 6][tid & 63] = tm->mot_wt[0][tid >> 6][tid & 63];
+#pragma unroll
+        for (int e = tid; e < 1024; e += TILE) SM.mot.mk1[e >> 8][e & 255] = tm->mot_wt[1][e >> 8][e & 255];
+    }
+    if (tid < nj) {
+        const SsMmChain C = mm[T.j0 + tid];
+        s_item0[tid] = C.item0; s_n[tid] = C.n; s_rdelta[tid] = C.rdelta; s_lf[tid] = C.len_first; s_off[tid] = C.off; s_raw[tid] = C.raw;
+    }
+    __syncthreads();
+    mark(0);
+    // ---- the lane's chain: the last of the tile's chains that starts at or before its item
+    const int item = T.item0 + tid;
+    int lo = 0, hi = nj - 1;
+    while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (s_item0[mid] <= item) lo = mid; else hi = mid - 1; }
+    if (item < s_item0[lo] + s_n[lo]) {             // (not behind the model's last item)
+    const ulonglong2* const rp = (const ulonglong2*)&rec[item + s_rdelta[lo]];
+    const ulonglong2 ra = rp[0], rb = rp[1];
+    const int64_t raw = s_raw[lo], g0 = s_off[lo];
+    const uint32_t len_first = s_lf[lo];
+    const unsigned long long ucodes = ra.x, w1 = ra.y, w2 = rb.x, w3 = rb.y;
+    const int i = (int)(unsigned)w3;
+    const double cs_raw = ca.cscore_raw[raw + i];
+    const int64_t g = g0 + i;
+    const int L = (int)(len_first & 0x7fffffffu);
+    const bool first = (len_first >> 31) != 0;
+    const unsigned long long zm = w1 & ((1ull << 42) - 1ull);
+    const int nups = (int)((w1 >> 42) & 63u), start = (int)((w1 >> 48) & 63u), type = (int)((w1 >> 54) & 3u);
+    const int strand = ((w1 >> 56) & 1u) ? -1 : 1;
+    const bool e0 = (w1 >> 57) & 1u, conv = (w1 >> 58) & 1u, ups_near_edge = (w1 >> 59) & 1u, ups_first = (w1 >> 60) & 1u, ups_later = (w1 >> 61) & 1u;
+    const unsigned isA = (unsigned)(w2 & 0xfffffu) << 1, isG = (unsigned)((w2 >> 20) & 0xfffffu) << 1;
+    const int stop3 = (int)(w2 >> 40);
+    const long orf = (long)(w3 >> 32);
+    const bool is_meta = sp.is_meta != 0;
+    const double st_wt = SM.st_wt;
+    const bool stop_missing = !codon_is_stop(stop3 & 0xff, (stop3 >> 8) & 0xff, (stop3 >> 16) & 0xff, SM.tt);
+    const bool edge_in = e0 || (conv && !first);
+    mark(1);
+    int rbs0 = 0, rbs1 = 0, m_ndx = 0, m_len = 0, m_sp = 0, m_si = 0;
+    double m_score = 0.0;
+    const bool search_sd = !edge_in && SM.uses_sd, search_mot = !edge_in && !SM.uses_sd;
+    auto midx = [&](const int k, const int t2) { return (int)((zm >> (2 * (21 - (18 + k - t2)))) & ((1ull << (2 * (k + 3))) - 1ull)); };
+    auto msi = [](const int t2) { return t2 <= 2 ? 3 : (t2 <= 4 ? 2 : (t2 >= 11 ? 1 : 0)); };
+    auto upstream = [&]() {
+        double v = 0.0;
+        unsigned lo32 = (unsigned)ucodes, hi32 = (unsigned)(ucodes >> 32);
+        if (nups == 32) {
+#pragma unroll
+            for (int q = 0; q < 16; q++) { v += SM.ups[q][(lo32 >> (2 * q)) & 3u]; if ((q & 7) == 7) __builtin_amdgcn_sched_barrier(0); }
+#pragma unroll
+            for (int q = 0; q < 16; q++) { v += SM.ups[16 + q][(hi32 >> (2 * q)) & 3u]; if ((q & 7) == 7) __builtin_amdgcn_sched_barrier(0); }
+        } else {
+            for (int q = 0; q < nups; q++) v += SM.ups[q][(int)(ucodes >> (2 * q)) & 3];
+        }
+        return v;
+    };
+    double u = 0.0;
+    if (search_sd) {
+        unsigned pats[3] = {0u, 0u, 0u};
+#pragma unroll
+        for (int q = 0; q < 15; q++) {
+            const unsigned a6 = (isA >> (15 - q)) & 63u, g6 = (isG >> (15 - q)) & 63u;
+            const unsigned pat = ((a6 >> 5) & 1u) | (((g6 >> 4) & 1u) << 1) | (((g6 >> 3) & 1u) << 2) | (((a6 >> 2) & 1u) << 3) |
+                                 (((g6 >> 1) & 1u) << 4) | ((g6 & 1u) << 5);
+            pats[q / 5] |= pat << (6 * (q % 5));
+        }
+#pragma unroll
+        for (int q = 0; q < 15; q++) {
+            if (start - 20 + q < 0 && strand == 1) continue;
+            const unsigned pat = (pats[q / 5] >> (6 * (q % 5))) & 63u;
+            const unsigned he = SM.lut[(q << 6) | pat], hm = SM.lut[((15 + q) << 6) | pat];
+            if (he > 1u) { const int a = sd_pick(he, SM.rbs_wt); if (a > rbs0) rbs0 = a; }
+            if (hm > 1u) { const int b = sd_pick(hm, SM.rbs_wt); if (b > rbs1) rbs1 = b; }
+        }
+    } else if (search_mot) {
+        double bsc = -100.0; int bsp = 0, bsi = 0, blen = 0, bndx = 0;
+#pragma unroll 1
+        for (int k = 3; k >= 0; k--) {
+            const int stride = k == 0 ? 64 : (k == 1 ? 256 : 4096);
+            const double* __restrict__ gt = &tm->mot_wt[k][0][0];
+            const double* lt = k == 1 ? &SM.mot.mk1[0][0] : &SM.mot.mk0[0][0];
+            double scv[13];
+            if (k >= 2) {
+#pragma unroll
+                for (int t2 = 0; t2 < 13; t2++) scv[t2] = 18 + k - t2 > start ? -1000.0 : gt[msi(t2) * stride + midx(k, t2)];
+            } else {
+#pragma unroll
+                for (int t2 = 0; t2 < 13; t2++) scv[t2] = 18 + k - t2 > start ? -1000.0 : lt[msi(t2) * stride + midx(k, t2)];
+            }
+#pragma unroll
+            for (int t2 = 0; t2 < 13; t2++)
+                if (scv[t2] > bsc) { bsc = scv[t2]; bsi = msi(t2); bsp = 15 - t2; blen = k + 3; bndx = midx(k, t2); }
+        }
+        if (bsc == -4.0 || bsc < SM.no_mot + 0.69) { m_score = SM.no_mot; }
+        else { m_ndx = bndx; m_len = blen; m_si = bsi; m_sp = bsp & 15; m_score = bsc; }
+    }
+    if (!edge_in) u = upstream();
+    mark(2);
+    double edge_gene = 0;
+    if (edge_in) edge_gene += 1;
+    if (stop_missing) edge_gene += 1;
+
+    double tscore, uscore, rscore, sscore, cscore = cs_raw;
+    if (edge_in) {
+        tscore = 0.74 * st_wt / edge_gene; uscore = 0.0; rscore = 0.0;
+    } else {
+        tscore = SM.type_wt[type] * st_wt;
+        const double r1 = SM.rbs_wt[rbs0], r2 = SM.rbs_wt[rbs1];
+        const double sd = fmax(r1, r2) * st_wt;
+        if (SM.uses_sd) rscore = sd;
+        else { rscore = st_wt * m_score; if (rscore < sd && SM.no_mot > -0.5) rscore = sd; }
+        uscore = u;
+        if (ups_near_edge || (first ? ups_first : ups_later)) uscore += -1.00 * st_wt;
+    }
+    bool edge_now = edge_in;
+    if (conv && !edge_in) {
+        edge_gene += 1; edge_now = true; tscore = 0.0;
+        uscore = 0.74 * st_wt / edge_gene; rscore = 0.0;
+    }
+    if (!edge_now && edge_gene == 1) uscore -= 0.5 * 0.74 * st_wt;
+    if (edge_gene == 0 && orf < 250) {
+        const double negf = 250.0 / (float)orf, posf = (float)orf / 250.0;
+        rscore *= rscore < 0 ? negf : posf;
+        uscore *= uscore < 0 ? negf : posf;
+        tscore *= tscore < 0 ? negf : posf;
+    }
+    if (is_meta && L < 3000 && edge_gene == 0 && (cscore < 5.0 || orf < 120))
+        cscore -= 7.5 * fmax(0.0, (3000.0 - L) / 2700.0);
+    sscore = tscore + rscore + uscore;
+    if (cscore < 0.0) {
+        if (edge_gene > 0 && !edge_now) {
+            if (!is_meta || L > 1500) sscore -= st_wt; else sscore -= 10.31 - 0.004 * L;
+        } else if (is_meta && L < 3000 && edge_now) {
+            const double mml = sqrt((double)L) * 5.0;
+            if (orf >= mml) { if (cscore >= 0) cscore = -1.0; sscore = 0.0; uscore = 0.0; }
+        } else sscore -= 0.5;
+    } else if (is_meta && cscore < 5.0 && orf < 120 && sscore < 0.0) sscore -= st_wt;
+    mark(3);
+    ca.cscore[g] = cscore; ca.sscore[g] = sscore; ca.rscore[g] = rscore; ca.uscore[g] = uscore; ca.tscore[g] = tscore;
+    ca.mot_score[g] = m_score; ca.mot_ndx[g] = m_ndx;
+    ca.mot_len[g] = (uint8_t)m_len; ca.mot_spacer[g] = (uint8_t)m_sp; ca.mot_spacendx[g] = (uint8_t)m_si;
+    ca.rbs[2 * g] = (uint8_t)rbs0; ca.rbs[2 * g + 1] = (uint8_t)rbs1;
+    ca.edge[g] = (uint8_t)edge_now;
+    if (sp.cs_out != nullptr) sp.cs_out[g] = cscore + sscore;
+    mark(4);
+    }
+}
+
 // ------------------------------------------------------------------- overlapping starts
 // ref: lib.pyx:2279-2329 (Nodes._record_overlapping_starts with flag = 1)
 // The three overlapping starts of stop node i (not an edge stop) of a chain.
@@ -2661,6 +3073,29 @@ void pga_launch_sd_lut(unsigned* d_lut, hipStream_t st) {
     hipLaunchKernelGGL(k_sd_lut, dim3((PGA_SD_LUT + 255) / 256), dim3(256), 0, st, d_lut);
 }
 
+// Tiles of the model-major start scoring (k_mm_scan lays them out the same way): per model, its items -- the start nodes of the
+// contigs of its chains -- in runs of pga_mm_tile_items().  `items` is the caller's scratch.
+int pga_mm_tile_items() {
+    // PGA_SS_MM_TILE: items (threads) per workgroup of k_score_starts_mm
+    const char* e = getenv("PGA_SS_MM_TILE");
+    const int v = e ? atoi(e) : 0;
+    return v == 256 || v == 512 || v == 1024 ? v : SS_TILE_DEFAULT;
+}
+int32_t pga_mm_tiles(const ChainDesc* h_chains, int n_chains, const int32_t* h_cbase, const int32_t* h_sbase, int n_models, std::vector<int64_t>& items) {
+    const int tile = pga_mm_tile_items();
+    items.assign((size_t)n_models, 0);
+    for (int k = 0; k < n_chains; k++) {
+        const int c = h_chains[k].contig;
+        items[(size_t)h_chains[k].model] += (h_cbase[c + 1] - h_cbase[c]) - (h_sbase[c + 1] - h_sbase[c]);
+    }
+    int64_t tiles = 0;
+    for (int m = 0; m < n_models; m++) tiles += (items[(size_t)m] + tile - 1) / tile;
+    return (int32_t)tiles;
+}
+size_t pga_mm_scratch_bytes(int n_models, int n_chains) {
+    return sizeof(unsigned long long) * SS_CNT_STRIDE * (size_t)n_models + sizeof(int32_t) * (((size_t)3 * n_models + 1) & ~(size_t)1) + sizeof(int2) * (size_t)n_chains + 64;
+}
+
 void pga_launch_score(const ChainDesc* d_chains, int n_chains, int64_t node_begin, int64_t total, const uint8_t* d_dig,
                       const ContigDesc* d_ct, const GroupArrays& ga, const pga_training* d_models,
                       const ModelScoreConst* d_msc, const ModelConst* d_mc, const ChainArrays& ca, ScoreParams sp,
@@ -2726,10 +3161,40 @@ void pga_launch_score(const ChainDesc* d_chains, int n_chains, int64_t node_begi
         // (a fifth wavefront per SIMD costs 96 bytes of scratch per lane and 10 % of the kernel's time: four)
         const bool listed = stops != nullptr && stops->starts_only && ga.start_list != nullptr;
         const int n_items = listed ? stops->n_starts : group_nodes;
-        if (n_items > 0)
+        // the listed launches: prologue, model-major order, scoring, the stop nodes' zeros (PGA_SS_MM=0: the model loop)
+        const bool mm = listed && n_items > 0 && stops->mm_tiles > 0 && stops->mm_rec != nullptr && !(getenv("PGA_SS_MM") && atoi(getenv("PGA_SS_MM")) == 0);
+        if (mm) {
+            const int nm = sp.n_models;
+            unsigned long long* const d_cnt = (unsigned long long*)stops->mm_scratch;
+            int32_t* const d_base = (int32_t*)(d_cnt + (size_t)SS_CNT_STRIDE * nm);
+            int2* const d_slot = (int2*)(d_base + (((size_t)3 * nm + 1) & ~(size_t)1));
+            (void)hipMemsetAsync(d_cnt, 0, sizeof(unsigned long long) * SS_CNT_STRIDE * (size_t)nm, st);
+            hipLaunchKernelGGL(k_start_prologue, dim3(nblocks(n_items, 256)), blk, 0, st, d_contig_chains, d_node_contig_base, n_contigs, d_dig, d_ct, ga, sp,
+                               (const int32_t*)ga.start_list, n_items, (SsStartRec*)stops->mm_rec);
+            hipLaunchKernelGGL(k_mm_count, dim3(nblocks(n_chains, 256)), blk, 0, st, d_chains, n_chains, d_node_contig_base, stops->sbase, nm, d_cnt, d_slot);
+            const int tile = pga_mm_tile_items();
+            hipLaunchKernelGGL(k_mm_scan, dim3(1), blk, 0, st, (const unsigned long long*)d_cnt, nm, tile, d_base);
+            hipLaunchKernelGGL(k_mm_place, dim3(nblocks(n_chains, 256)), blk, 0, st, d_chains, n_chains, d_node_contig_base, stops->sbase, d_ct,
+                               (const unsigned long long*)d_cnt, (const int2*)d_slot, (const int32_t*)d_base, nm, tile, d_models, (SsMmChain*)stops->mm_chain, (SsMmTile*)stops->mm_tile);
+            const SsMmTile* const d_tl = (const SsMmTile*)stops->mm_tile; const SsMmChain* const d_mc = (const SsMmChain*)stops->mm_chain;
+            const SsStartRec* const d_rec = (const SsStartRec*)stops->mm_rec;
+            const dim3 grid_mm((unsigned)stops->mm_tiles);
+            if (tile == 1024) hipLaunchKernelGGL(k_score_starts_mm<1024>, grid_mm, dim3(1024), 0, st, d_tl, d_mc, d_rec, d_models, ca, sp, d_sd_lut);
+            else if (tile == 512) hipLaunchKernelGGL(k_score_starts_mm<512>, grid_mm, dim3(512), 0, st, d_tl, d_mc, d_rec, d_models, ca, sp, d_sd_lut);
+            else hipLaunchKernelGGL(k_score_starts_mm<256>, grid_mm, blk, 0, st, d_tl, d_mc, d_rec, d_models, ca, sp, d_sd_lut);
+            if (stops->n_stops > 0)
+                hipLaunchKernelGGL(k_clear_stops, dim3(nblocks(stops->n_stops, 256)), blk, 0, st, d_all_chains, d_contig_chains, d_node_contig_base, ga, ca, sp,
+                                   stops->n_stops);
+        } else if (n_items > 0)
             hipLaunchKernelGGL(k_score_starts<4>, dim3(nblocks(n_items, 256)), blk, 0, st, d_all_chains, d_contig_chains, d_node_contig_base, n_contigs,
                                group_nodes, d_dig, d_ct, ga, d_models, ca, sp, d_sd_lut, listed ? (const int32_t*)ga.start_list : (const int32_t*)nullptr, n_items);
-        if (ss_profiling) {
+        if (ss_profiling && mm) {
+            unsigned long long h[16];
+            (void)hipStreamSynchronize(st);
+            (void)hipMemcpy(h, sp.prof, sizeof h, hipMemcpyDeviceToHost);
+            fprintf(stderr, "[pga ss-profile] model-major, %d starts, %d tiles: wave-cycles  stage %.3g  chain + record %.3g  upstream + RBS / motif search %.3g  "
+                            "scores %.3g  stores %.3g\n", n_items, stops->mm_tiles, (double)h[0], (double)h[1], (double)h[2], (double)h[3], (double)h[4]);
+        } else if (ss_profiling) {
             unsigned long long h[16];
             (void)hipStreamSynchronize(st);
             (void)hipMemcpy(h, sp.prof, sizeof h, hipMemcpyDeviceToHost);
