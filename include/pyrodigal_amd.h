@@ -50,6 +50,10 @@ typedef struct pga_training {
     double  gene_dc[4096];
 } pga_training;
 
+/* pga_params.want_nodes = PGA_NODES_DEVICE: the winners' node arrays stay in device memory, owned by the context, until the next
+ * call on it that runs the finder (pga_find_genes*, pga_nodes_stage, pga_train*) or loads models; nothing of them is copied back. */
+#define PGA_NODES_DEVICE 2
+
 /* GeneFinder constructor options (ref: lib.pyx:5102-5115). */
 typedef struct pga_params {
     int32_t closed;         /* default 0  */
@@ -57,7 +61,8 @@ typedef struct pga_params {
     int32_t min_edge_gene;  /* default 60 */
     int32_t max_overlap;    /* default 60 */
     int32_t meta;           /* 1: meta mode over all loaded models; 0: single mode with model 0 */
-    int32_t want_nodes;     /* 1: also return the winning model's full node arrays */
+    int32_t want_nodes;     /* 1: also return the winning model's full node arrays; PGA_NODES_DEVICE (2): keep them on the device
+                             * only, for pga_render_genes (PGA_RENDER_SCO), with pga_result.nodes NULL; 0: neither */
     int32_t mask;           /* 1: no gene may run across a masked region (runs of unknown bases), default 0 */
     int32_t min_mask;       /* shortest run of unknown bases that is masked, default 50 (ref: lib.pyx:5102-5115, 699-713) */
 } pga_params;
@@ -243,12 +248,17 @@ int pga_translate_genes(pga_ctx*, const pga_batch*, int64_t n_genes, const pga_g
                         int unknown_residue, int include_stop, int strict, const int64_t* offsets, char* out);
 
 /* ---- text output ------------------------------------------------------------------ */
-/* GFF, protein FASTA and gene FASTA of gene records, rendered on the device from a resident batch: byte for byte what the
- * host writers Genes.write_gff / write_translations / write_genes emit, contig after contig (ref: lib.pyx:3534-3792).
- * A length pass, an exclusive scan and a write pass per format; one text arena per format, copied back once. */
+/* GFF, protein FASTA, gene FASTA, GenBank and the start-score file of gene records, rendered on the device from a resident
+ * batch: byte for byte what the host writers Genes.write_gff / write_translations / write_genes / write_genbank / write_scores
+ * emit, contig after contig (ref: lib.pyx:3405-3894).
+ * A length pass, an exclusive scan and a write pass per format; one text arena per format, copied back once.
+ * PGA_RENDER_SCO reads the node arrays the last finder call on the context kept on the device (want_nodes 1 or
+ * PGA_NODES_DEVICE) for exactly this result (`contigs`) and batch; PGA_EINVAL otherwise. */
 #define PGA_RENDER_GFF 1
 #define PGA_RENDER_FAA 2
 #define PGA_RENDER_FNA 4
+#define PGA_RENDER_GBK 8
+#define PGA_RENDER_SCO 16
 typedef struct pga_render_opts {
     int32_t     formats;            /* PGA_RENDER_* bits */
     int32_t     meta;               /* run_type=Metagenomic (1) or Single (0) in the GFF header */
@@ -261,6 +271,15 @@ typedef struct pga_render_opts {
     int32_t     fna_width, fna_full_id;
     double      fallback_margin;    /* a line whose confidence lies this close to a %.2f rounding midpoint is left to the host
                                      * (the device exp may differ from the host's by an ulp); 1e-9 */
+    /* GenBank (write_genbank): LOCUS division ("BCT"), date as "%d-%b-%y" upper case ("16-OCT-26"), the version in
+     * /inference="ab initio prediction:pyrodigal_amd:<version>", translation table (0: the contig's model's), strict translation */
+    const char* gbk_division;
+    const char* gbk_date;
+    const char* gbk_version;
+    int32_t     gbk_translation_table, gbk_strict;
+    /* start-score file (write_scores): the three header lines of every contig */
+    int32_t     sco_header;
+    int32_t     _pad1;
 } pga_render_opts;
 typedef struct pga_text {
     char*    data;          /* `size` bytes in pinned host memory the CONTEXT owns (kept and grown across calls): valid until the
@@ -273,14 +292,16 @@ typedef struct pga_text {
 typedef struct pga_render_result {
     int32_t  n_contigs;
     int32_t  _pad;
-    pga_text text[3];       /* GFF, protein FASTA, gene FASTA; data == NULL for a format that was not asked for */
-    double   t_kernels_ms[3];  /* device time of each format's length pass, scan and write pass */
+    pga_text text[5];       /* GFF, protein FASTA, gene FASTA, GenBank, start scores (PGA_RENDER_* bit order); data == NULL for a
+                             * format that was not asked for */
+    double   t_kernels_ms[5];  /* device time of each format's length pass, scan and write pass (scores: and the row sort) */
 } pga_render_result;
 /*   contigs[i]          the result's contig records of THIS batch (gene_begin / n_genes; genes of contig i in order)
  *   genes               the result's gene records
  *   model_of_contig[i]  the loaded model (pga_set_models index) that called contig i: 0 in single mode, contigs[i].model in
  *                       meta mode, the caller's index on the model-per-contig path; -1 only for a contig without genes
- *                       (and then not with PGA_RENDER_GFF: its header needs a model -- Prodigal reports bin 5 for it)
+ *                       (and then not with PGA_RENDER_GFF or PGA_RENDER_SCO: their headers need a model -- Prodigal reports
+ *                       bin 5 for it)
  *   ids / id_off        sequence ids: contig i is ids[id_off[i] .. id_off[i + 1]) */
 int  pga_render_genes(pga_ctx*, const pga_batch*, const pga_contig_result* contigs, int64_t n_genes, const pga_gene* genes,
                       const int32_t* model_of_contig, const char* ids, const int64_t* id_off, const pga_render_opts* opts,

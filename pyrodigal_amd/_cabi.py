@@ -76,7 +76,10 @@ class RenderOpts(ctypes.Structure):
                 ("gff_header", ctypes.c_int32), ("gff_include_translation_table", ctypes.c_int32), ("gff_full_id", ctypes.c_int32),
                 ("faa_width", ctypes.c_int32), ("faa_translation_table", ctypes.c_int32), ("faa_include_stop", ctypes.c_int32),
                 ("faa_strict", ctypes.c_int32), ("faa_full_id", ctypes.c_int32), ("fna_width", ctypes.c_int32),
-                ("fna_full_id", ctypes.c_int32), ("fallback_margin", ctypes.c_double)]
+                ("fna_full_id", ctypes.c_int32), ("fallback_margin", ctypes.c_double),
+                ("gbk_division", ctypes.c_char_p), ("gbk_date", ctypes.c_char_p), ("gbk_version", ctypes.c_char_p),
+                ("gbk_translation_table", ctypes.c_int32), ("gbk_strict", ctypes.c_int32), ("sco_header", ctypes.c_int32),
+                ("_pad1", ctypes.c_int32)]
 
 
 class Text(ctypes.Structure):
@@ -85,10 +88,11 @@ class Text(ctypes.Structure):
 
 
 class RenderResult(ctypes.Structure):
-    _fields_ = [("n_contigs", ctypes.c_int32), ("_pad", ctypes.c_int32), ("text", Text * 3), ("t_kernels_ms", ctypes.c_double * 3)]
+    _fields_ = [("n_contigs", ctypes.c_int32), ("_pad", ctypes.c_int32), ("text", Text * 5), ("t_kernels_ms", ctypes.c_double * 5)]
 
 
-RENDER_FORMATS = ("gff", "faa", "fna")
+RENDER_FORMATS = ("gff", "faa", "fna", "gbk", "scores")     # PGA_RENDER_* bit order
+NODES_DEVICE = 2                                            # pga_params.want_nodes: keep the node arrays on the device
 GENE_DTYPE = np.dtype(Gene)
 CONTIG_DTYPE = np.dtype(ContigResult)
 
@@ -503,12 +507,23 @@ def _upload_packed(self, pb):
     return b
 
 
+def _want_nodes(want_nodes):
+    if isinstance(want_nodes, str):
+        if want_nodes != "device":
+            raise ValueError("want_nodes must be a bool or \"device\", not %r" % (want_nodes,))
+        return NODES_DEVICE
+    return int(bool(want_nodes))
+
+
 def _find_genes(self, batch, meta=True, closed=False, min_gene=90, min_edge_gene=60, max_overlap=60, want_nodes=False,
                 mask=False, min_mask=50, model_of_contig=None):
     """``GeneFinder.find_genes`` over every contig of a resident :class:`Batch`.
 
-    ``model_of_contig`` (single mode): contig i is called with loaded model ``model_of_contig[i]`` (``pga_find_genes_models``)."""
-    p = Params(int(closed), min_gene, min_edge_gene, max_overlap, int(meta), int(want_nodes), int(mask), min_mask)
+    ``model_of_contig`` (single mode): contig i is called with loaded model ``model_of_contig[i]`` (``pga_find_genes_models``).
+    ``want_nodes``: True also returns the winning model's node arrays (``nodes``); ``"device"`` keeps them on the device only, for
+    ``render_genes(..., "scores")`` on this result before the next call on the context (``nodes`` stays None)."""
+    wn = _want_nodes(want_nodes)
+    p = Params(int(closed), min_gene, min_edge_gene, max_overlap, int(meta), wn, int(mask), min_mask)
     res = _P(Result)()
     if model_of_contig is None:
         rc = self.L.pga_find_genes(self.h, batch.h, ctypes.byref(p), ctypes.byref(res))
@@ -521,7 +536,7 @@ def _find_genes(self, batch, meta=True, closed=False, min_gene=90, min_edge_gene
         what = "pga_find_genes_models"
     if rc != PGA_OK:
         _raise(self.L, self.h, rc, what)
-    return _unpack_result(self.L, res, want_nodes)
+    return _unpack_result(self.L, res, wn == 1)
 
 
 def _find_genes_batch(self, seqs, **kw):
@@ -647,29 +662,20 @@ class RenderedText:
         return self.data[self.contig_offsets[i]:self.contig_offsets[i + 1]]
 
 
-# the writers' defaults (Genes.write_gff / write_translations / write_genes)
+# the writers' defaults (Genes.write_gff / write_translations / write_genes / write_genbank / write_scores)
 _WRITER_DEFAULTS = {
     "gff": {"header": True, "include_translation_table": False, "full_id": True, "version_separator": "_v"},
     "faa": {"width": 60, "translation_table": None, "include_stop": True, "strict_translation": True, "full_id": False},
     "fna": {"width": 70, "full_id": False},
+    "gbk": {"division": "BCT", "date": None, "translation_table": None, "strict_translation": True},
+    "scores": {"header": True},
 }
 
 
-def _render_genes(self, batch, result, ids, formats=RENDER_FORMATS, *, meta=False, model_of_contig=None, descriptions=None,
-                  first_seqnum=1, fallback_margin=1e-9, unbinned_model=None, **writer_options):
-    """GFF / protein FASTA / gene FASTA of ``result`` (a result of ``find_genes`` on the resident ``batch``), rendered on the
-    device: byte for byte what ``Genes.write_gff`` / ``write_translations`` / ``write_genes`` write for these genes, contig
-    after contig.
-
-    ``ids``: the sequence id of every contig; ``first_seqnum``: the seqnum of contig 0.  ``formats``: names among "gff", "faa",
-    "fna", or a dict from those names to the writer's keyword arguments (``header``, ``include_translation_table``, ``full_id``,
-    ``version_separator`` / ``width``, ``translation_table``, ``include_stop``, ``strict_translation``, ``full_id`` /
-    ``width``, ``full_id``); ``writer_options`` apply to every format that takes them.  ``meta``: the models are metagenomic
-    bins (``descriptions`` gives theirs) and contig i was called with ``result.contigs[i]["model"]``; else single mode with
-    model 0, or with ``model_of_contig[i]``.  ``unbinned_model`` (meta mode): the model whose data the GFF header of a contig
-    without genes, which no bin won, reports (Prodigal writes bin 5's); None: such a contig is an error for GFF, as it is for
-    ``write_gff``.  Returns ``{name: RenderedText}``."""
-    from . import __version__ as version
+def _render_formats(formats, writer_options):
+    """The writer options of every requested format (``formats``: names, or a dict from names to options), checked as the host
+    writers check them; no device needed."""
+    import datetime
     if isinstance(formats, str):
         formats = (formats,)
     fmt_opts = {}
@@ -687,6 +693,45 @@ def _render_genes(self, batch, result, ids, formats=RENDER_FORMATS, *, meta=Fals
     bad = set(writer_options) - set().union(*[set(v) for v in _WRITER_DEFAULTS.values()])
     if bad:
         raise TypeError("unexpected option(s) %s" % ", ".join(sorted(bad)))
+    if "gbk" in fmt_opts:
+        # as write_genbank: a table among the known ones, a datetime.date (today when None), the division as given
+        from .cli import TRANSLATION_TABLES
+        g = fmt_opts["gbk"]
+        tt = g["translation_table"]
+        if tt is not None and tt not in TRANSLATION_TABLES:
+            raise ValueError("%r is not a valid translation table index" % (tt,))
+        date = g["date"]
+        if date is None:
+            date = datetime.date.today()
+        elif not isinstance(date, datetime.date):
+            raise TypeError("Expected datetime.date, found %s" % type(date).__name__)
+        if not isinstance(g["division"], str):
+            raise TypeError("Expected str, found %s" % type(g["division"]).__name__)
+        g["date"] = date
+    return fmt_opts
+
+
+def _render_genes(self, batch, result, ids, formats=RENDER_FORMATS, *, meta=False, model_of_contig=None, descriptions=None,
+                  first_seqnum=1, fallback_margin=1e-9, unbinned_model=None, **writer_options):
+    """GFF / protein FASTA / gene FASTA of ``result`` (a result of ``find_genes`` on the resident ``batch``), rendered on the
+    device: byte for byte what ``Genes.write_gff`` / ``write_translations`` / ``write_genes`` write for these genes, contig
+    after contig.
+
+    ``ids``: the sequence id of every contig; ``first_seqnum``: the seqnum of contig 0.  ``formats``: names among "gff", "faa",
+    "fna", or a dict from those names to the writer's keyword arguments (``header``, ``include_translation_table``, ``full_id``,
+    ``version_separator`` / ``width``, ``translation_table``, ``include_stop``, ``strict_translation``, ``full_id`` /
+    ``width``, ``full_id``); ``writer_options`` apply to every format that takes them.  ``meta``: the models are metagenomic
+    bins (``descriptions`` gives theirs) and contig i was called with ``result.contigs[i]["model"]``; else single mode with
+    model 0, or with ``model_of_contig[i]``.  ``unbinned_model`` (meta mode): the model whose data the GFF header of a contig
+    without genes, which no bin won, reports (Prodigal writes bin 5's); None: such a contig is an error for GFF, as it is for
+    ``write_gff``.  Returns ``{name: RenderedText}``.
+
+    "gbk" (``division``, ``date``, ``translation_table``, ``strict_translation``) is ``Genes.write_genbank``'s record.  "scores"
+    (``header``) is ``Genes.write_scores``' start file: it needs the node arrays of ``result`` on the device, i.e. ``result`` is
+    the last ``find_genes`` on this context and was called with ``want_nodes="device"`` (or True); a contig no bin won gets
+    ``unbinned_model``'s header and an empty body."""
+    from . import __version__ as version
+    fmt_opts = _render_formats(formats, writer_options)
     n = batch.n
     ids = [str(x) for x in ids]
     if len(ids) != n:
@@ -735,6 +780,15 @@ def _render_genes(self, batch, result, ids, formats=RENDER_FORMATS, *, meta=Fals
         o.faa_include_stop, o.faa_strict, o.faa_full_id = int(bool(a["include_stop"])), int(bool(a["strict_translation"])), int(bool(a["full_id"]))
     if "fna" in fmt_opts:
         o.fna_width, o.fna_full_id = _width(fmt_opts["fna"]["width"]), int(bool(fmt_opts["fna"]["full_id"]))
+    if "gbk" in fmt_opts:
+        g = fmt_opts["gbk"]
+        o.gbk_division = g["division"].encode("utf-8")
+        o.gbk_date = g["date"].strftime("%d-%b-%y").upper().encode("utf-8")
+        o.gbk_version = version.encode("utf-8")
+        o.gbk_translation_table = 0 if g["translation_table"] is None else int(g["translation_table"])
+        o.gbk_strict = int(bool(g["strict_translation"]))
+    if "scores" in fmt_opts:
+        o.sco_header = int(bool(fmt_opts["scores"]["header"]))
     res = _P(RenderResult)()
     rc = self.L.pga_render_genes(self.h, batch.h, contigs.ctypes.data, len(genes), genes.ctypes.data if len(genes) else None,
                                  moc.ctypes.data, id_arena or None, id_off.ctypes.data, ctypes.byref(o), ctypes.byref(res))
@@ -750,6 +804,8 @@ def _render_genes(self, batch, result, ids, formats=RENDER_FORMATS, *, meta=Fals
             data = ctypes.string_at(t.data, t.size) if t.size else b""
             coff = np.ctypeslib.as_array(t.contig_off, (n + 1,)).copy()
             nf = int(t.n_fallback)
+            if nf and name in ("gbk", "scores"):
+                raise PgaError("pga_render_genes: %d %s line(s) hold a value the device cannot print exactly" % (nf, name))
             if nf:
                 fb = np.ctypeslib.as_array(t.fallback, (3 * nf,)).reshape(nf, 3).copy()
                 data, coff = _splice_fallback(self, name, fmt_opts[name], data, coff, fb, genes, contigs, moc, ids, first_seqnum)

@@ -1,8 +1,7 @@
 """Prodigal-compatible command line, with the options of pyrodigal's (ref: cli.py:64-323).
 
-GFF, protein FASTA (``-a``) and gene FASTA (``-d``) are rendered on the device (``pipeline.render_fasta``).  GenBank output
-(``-f gbk``) and the start file (``-s``) go through the host writers (``Genes.write_genbank`` / ``write_scores``): correct
-but much slower.  Argument parsing and ``--help`` do not load the HIP library."""
+Every output -- GFF or GenBank (``-f``), protein FASTA (``-a``), gene FASTA (``-d``) and the start file (``-s``) -- is rendered
+on the device (``pipeline.render_fasta``).  Argument parsing and ``--help`` do not load the HIP library."""
 import argparse
 import contextlib
 import os
@@ -23,7 +22,7 @@ def argument_parser(prog="pyrodigal_amd"):
     p.add_argument("-c", action="store_true", default=False, help="Closed ends. Do not allow genes to run off edges.")
     p.add_argument("-d", metavar="nuc_file", help="Write nucleotide sequences of genes to the selected file.")
     p.add_argument("-f", metavar="output_type", choices=("gff", "gbk"), default="gff",
-                   help="Select output format. gbk is written by the host writer: correct but much slower than gff.")
+                   help="Select output format.")
     p.add_argument("-g", metavar="tr_table", type=int, choices=sorted(TRANSLATION_TABLES), default=11,
                    help="Specify a translation table to use.")
     p.add_argument("-i", metavar="input_file", help="Specify FASTA input file (plain, .gz, .bz2 or .xz; default: stdin).")
@@ -31,8 +30,7 @@ def argument_parser(prog="pyrodigal_amd"):
     p.add_argument("-n", action="store_true", default=False, help="Bypass Shine-Dalgarno trainer and force a full motif scan.")
     p.add_argument("-o", metavar="output_file", help="Specify output file (default: stdout).")
     p.add_argument("-p", metavar="mode", choices=("single", "meta"), default="single", help="Select procedure.")
-    p.add_argument("-s", metavar="start_file",
-                   help="Write all potential genes (with scores) to the selected file. Written by the host writer: slow.")
+    p.add_argument("-s", metavar="start_file", help="Write all potential genes (with scores) to the selected file.")
     p.add_argument("-t", metavar="training_file",
                    help="Write a training file (if none exists); otherwise, read and use the specified training file.")
     p.add_argument("-j", "--jobs", type=int, default=2, metavar="jobs",
@@ -54,26 +52,8 @@ def argument_parser(prog="pyrodigal_amd"):
 
 
 # A contig without genes wins no bin in meta mode; its GFF header reports bin 5, as Prodigal's does (ref: lib.pyx:3584-3592), or
-# the last bin when fewer are given.
+# the last bin when fewer are given.  Its start file is that bin's header and an empty body.
 UNBINNED_BIN = 5
-
-
-def _unbinned_gff(genes, seq_id, fallback):
-    """write_gff's text for a meta-mode contig without genes: the header lines, the fallback bin's model data."""
-    t = fallback.training_info
-    return ('##gff-version  3\n# Sequence Data: seqnum=%d;seqlen=%d;seqhdr="%s"\n'
-            '# Model Data: version=pyrodigal_amd.v%s;run_type=Metagenomic;model="%s";gc_cont=%.2f;transl_table=%d;uses_sd=%d\n'
-            % (genes._num_seq, len(genes.sequence), seq_id, __version__, fallback.description, t.gc * 100, t.translation_table,
-               int(t.uses_sd)))
-
-
-def _unbinned_scores(genes, seq_id, fallback):
-    """write_scores' text for a meta-mode contig without genes: no model won, so there are no scored nodes to list."""
-    t = fallback.training_info
-    return ('# Sequence Data: seqnum=%d;seqlen=%d;seqhdr="%s"\n'
-            '# Run Data: version=pyrodigal_amd.v%s;gc_cont=%.2f;transl_table=%d;uses_sd=%d\n'
-            'Beg\tEnd\tStd\tTotal\tCodPot\tStrtSc\tCodon\tRBSMot\tSpacer\tRBSScr\tUpsScr\tTypeScr\tGCCont\n\n'
-            % (genes._num_seq, len(genes.sequence), seq_id, __version__, t.gc * 100, t.translation_table, int(t.uses_sd)))
 
 
 def _check(args):
@@ -123,7 +103,6 @@ def main(argv=None, stdout=None, stderr=None):
             for f in args.meta_bins:
                 with open(f, "rb") as fh:
                     bins.append(lib.MetagenomicBin(lib.TrainingInfo.load(fh), os.path.basename(f)))
-            finder = lib.GeneFinder(meta=True, metagenomic_bins=lib.MetagenomicBins(bins), keep_nodes=args.s is not None, **find_kw)
             blobs = [b.training_info.raw for b in bins]
             descriptions = [b.description for b in bins]
             unbinned = min(UNBINNED_BIN, len(bins) - 1)
@@ -132,47 +111,17 @@ def main(argv=None, stdout=None, stderr=None):
             if args.t is not None and os.path.exists(args.t):
                 with open(args.t, "rb") as fh:
                     tinf = lib.TrainingInfo.load(fh)
-            finder = lib.GeneFinder(tinf, keep_nodes=args.s is not None, **find_kw)
             if tinf is None:
                 seqs = [s for _, _, s in _records(path)]
-                tinf = finder.train(*seqs, force_nonsd=args.n, translation_table=args.g)
+                tinf = lib.GeneFinder(**find_kw).train(*seqs, force_nonsd=args.n, translation_table=args.g)
                 del seqs
                 if args.t is not None:
                     with open(args.t, "wb") as fh:
                         tinf.dump(fh)
             blobs, descriptions, unbinned = [tinf.raw], None, None
-        host_main = args.f == "gbk" or args.s is not None
-        if not host_main:
-            from .pipeline import render_fasta
-            render_fasta(path, blobs, gff=out, faa=faa, fna=fna, n_contexts=args.jobs, max_bases=args.batch_bases, meta=meta,
-                         descriptions=descriptions, faa_options={"include_stop": not args.no_stop_codon}, unbinned_model=unbinned,
-                         **find_kw)
-            return 0
-        # GenBank / start file: the host writers, record by record (ref: cli.py:304-321)
-        import io
-        scores = None if args.s is None else stack.enter_context(open(args.s, "w"))
-        text = io.TextIOWrapper(out, encoding="utf-8", write_through=True)
-        faa_t = None if faa is None else io.TextIOWrapper(faa, encoding="utf-8", write_through=True)
-        fna_t = None if fna is None else io.TextIOWrapper(fna, encoding="utf-8", write_through=True)
-        for seq_id, _, seq in _records(path):
-            genes = finder.find_genes(seq)
-            fallback = bins[unbinned] if meta and genes.metagenomic_bin is None else None
-            if args.f == "gbk":
-                genes.write_genbank(text, sequence_id=seq_id)
-            elif fallback is not None:
-                text.write(_unbinned_gff(genes, seq_id, fallback))
-            else:
-                genes.write_gff(text, sequence_id=seq_id)
-            if fna_t is not None:
-                genes.write_genes(fna_t, sequence_id=seq_id)
-            if faa_t is not None:
-                genes.write_translations(faa_t, sequence_id=seq_id, include_stop=not args.no_stop_codon)
-            if scores is not None and fallback is not None:
-                scores.write(_unbinned_scores(genes, seq_id, fallback))
-            elif scores is not None:
-                genes.write_scores(scores, sequence_id=seq_id)
-        for t in (text, faa_t, fna_t):
-            if t is not None:
-                t.flush()
-                t.detach()
+        scores = None if args.s is None else stack.enter_context(open(args.s, "wb"))
+        from .pipeline import render_fasta
+        render_fasta(path, blobs, gff=out if args.f == "gff" else None, gbk=out if args.f == "gbk" else None, faa=faa, fna=fna,
+                     scores=scores, n_contexts=args.jobs, max_bases=args.batch_bases, meta=meta, descriptions=descriptions,
+                     faa_options={"include_stop": not args.no_stop_codon}, unbinned_model=unbinned, **find_kw)
     return 0

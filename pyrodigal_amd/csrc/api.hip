@@ -146,6 +146,7 @@ extern "C" int pga_set_models(pga_ctx* c, const pga_training* const* models, int
         }
     }
     HIP_TRY(c, hipSetDevice(c->device));
+    c->dev_nodes.clear();               // node arrays kept by the last find belong to the old model set
     if (c->d_models_raw) { hipFree(c->d_models_raw); c->d_models_raw = nullptr; }
     if (c->d_model_const) { hipFree(c->d_model_const); c->d_model_const = nullptr; }
     c->models.clear();

@@ -1373,6 +1373,7 @@ static int publish(ResultOwner* R, ResultOwner*& guarded, const pga_params& P, p
 static int find_impl(pga_ctx* c, const pga_batch* batch, const pga_params* pp, const int stage, const int tt_override, pga_result** out,
                      const int32_t* model_of_contig, const int32_t* tt_of_contig) {
     if (out) *out = nullptr;
+    if (c) c->dev_nodes.clear();        // this call reuses the arena the last one kept on the device
     if (!c || !out || !pp || !batch || batch->ctx != c) {
         if (c) c->err = "pga_find_genes: bad arguments";
         return PGA_EINVAL;
@@ -2169,7 +2170,7 @@ static int find_impl(pga_ctx* c, const pga_batch* batch, const pga_params* pp, c
             tracef.assign((size_t)out_nodes + 1, -1);
             elim.assign((size_t)out_nodes + 1, 0);
             if (out_nodes > 0)
-                HT(c, hipMemcpyAsync(h.ndx, o.ndx, P.want_nodes ? arena_all : arena_dp, hipMemcpyDeviceToHost, st));   // arena starts at `ndx`
+                HT(c, hipMemcpyAsync(h.ndx, o.ndx, P.want_nodes == 1 ? arena_all : arena_dp, hipMemcpyDeviceToHost, st));   // arena starts at `ndx`
             HT(c, hipEventRecord(f->e_stop, st));
             HT(c, hipGetLastError());
             HT(c, hipStreamSynchronize(st));
@@ -2220,6 +2221,9 @@ static int find_impl(pga_ctx* c, const pga_batch* batch, const pga_params* pp, c
                 if (nt == 1) fn(); else f->pool.run(fn, nt);
             };
             run_parallel(worker);
+            // the tail moved start scores (eliminate_bad_genes): the arena kept on the device must say what the host copy says
+            if (P.want_nodes && out_nodes > 0)
+                HT(c, hipMemcpyAsync(o.sscore_dp, h.sscore_dp, sizeof(double) * (size_t)out_nodes, hipMemcpyHostToDevice, st));
             tm.mark("host_tail");
             // ---- results -----------------------------------------------------------------------------------
             int64_t ngenes = 0;
@@ -2420,7 +2424,7 @@ static int find_impl(pga_ctx* c, const pga_batch* batch, const pga_params* pp, c
                                    d_gbegin, P.meta ? 0 : 1, d_genes, lean_gather ? 1 : 0, ca, gcs);
                 HT(c, hipMemcpyAsync(genes_out, d_genes, sizeof(pga_gene) * (size_t)ngenes, hipMemcpyDeviceToHost, st));
             }
-            if (P.want_nodes && out_nodes > 0) {
+            if (P.want_nodes == 1 && out_nodes > 0) {
                 tracef.resize((size_t)out_nodes + 1); elim.resize((size_t)out_nodes + 1);
                 HT(c, hipMemcpyAsync(h.ndx, o.ndx, arena_all, hipMemcpyDeviceToHost, st));   // arena starts at `ndx`
                 HT(c, hipMemcpyAsync(tracef.data(), d_tracef, sizeof(int32_t) * (size_t)out_nodes, hipMemcpyDeviceToHost, st));
@@ -2433,7 +2437,7 @@ static int find_impl(pga_ctx* c, const pga_batch* batch, const pga_params* pp, c
             tm.mark("genes+d2h");
 
         }
-        if (P.want_nodes) {
+        if (P.want_nodes == 1) {
             R->nodes.resize(NC);
             for (int i = 0; i < NC; i++) {
                 pga_nodes& N = R->nodes[i];
@@ -2458,6 +2462,23 @@ static int find_impl(pga_ctx* c, const pga_batch* batch, const pga_params* pp, c
                     for (int j = 0; j < n; j++) { N.traceb[j] = -1; N.tracef[j] = -1; N.ov_mark[j] = -1; }
                 }
             }
+        }
+        if (P.want_nodes) {
+            // the arena stays on the device for pga_render_genes until the next finder call (want_nodes 1 and PGA_NODES_DEVICE)
+            DevNodes& D = c->dev_nodes;
+            D.off.assign(NC, 0); D.n.assign(NC, 0); D.len.resize(NC);
+            for (int i = 0; i < NC; i++) {
+                D.len[i] = batch->ct[i].len;
+                if (win_chain[i] >= 0) { D.off[i] = out_off[i]; D.n[i] = chains[win_chain[i]].n; }
+            }
+            D.total = out_nodes;
+            const bool single = !P.meta;
+            D.a = DevNodeArrays{o.ndx, o.stop_val, o.type, o.strand, o.gc_cont,
+                                single ? o.edge_dp : o.edge, single ? o.cscore_dp : o.cscore, single ? o.sscore_dp : o.sscore,
+                                single ? o.rscore_dp : o.rscore, single ? o.uscore_dp : o.uscore, single ? o.tscore_dp : o.tscore,
+                                o.mot_score, o.mot_ndx, o.rbs, o.mot_len, o.mot_spacer};
+            D.batch = batch;
+            D.contigs = R->contigs.data();
         }
     }
     tm.mark("results");

@@ -180,6 +180,26 @@ void pga_launch_dp(const ChainDesc* d_chains, int n_chains, const ModelConst* d_
 
 struct FinderState;   // finder.hip
 
+// The winners' node arrays of the last finder call that kept them on the device (pga_params.want_nodes 1 or PGA_NODES_DEVICE), for
+// the start-score file of pga_render_genes (render.hip).  Valid while `contigs` is non-null: every call that runs the finder, and
+// pga_set_models, clears it first.  Single mode reports the fields the DP saw (`*_dp` of the gathered arena), meta mode the fresh
+// re-score -- what finder.hip copies into pga_result.nodes.
+struct DevNodeArrays {
+    const int32_t* ndx; const int32_t* stop_val; const uint8_t* type; const int8_t* strand; const float* gc_cont;
+    const uint8_t* edge; const double* cscore; const double* sscore; const double* rscore; const double* uscore; const double* tscore;
+    const double* mot_score; const int32_t* mot_ndx; const uint8_t* rbs /* [n][2] */; const uint8_t* mot_len; const uint8_t* mot_spacer;
+};
+struct DevNodes {
+    const pga_contig_result* contigs = nullptr;   // the result the nodes belong to (its contig array), nullptr: none kept
+    const void* batch = nullptr;                  // and its batch
+    int64_t total = 0;                            // nodes in the arena
+    std::vector<int64_t> off;                     // per contig: its first node in the arena (ordered by table group, then contig)
+    std::vector<int32_t> n;                       // per contig: its nodes (0: no model won)
+    std::vector<int64_t> len;                     // per contig: sequence length (a batch freed and another made at its address is refused)
+    DevNodeArrays a{};
+    void clear() { contigs = nullptr; batch = nullptr; total = 0; off.clear(); n.clear(); len.clear(); a = DevNodeArrays{}; }
+};
+
 struct pga_ctx {
     int device = 0;
     FinderState* finder = nullptr;
@@ -199,6 +219,7 @@ struct pga_ctx {
     char* render_text = nullptr; size_t render_text_cap = 0;
     char* render_host = nullptr; size_t render_host_cap = 0;
     unsigned long long* render_small = nullptr;
+    DevNodes dev_nodes;                                // the last finder call's node arrays, when it kept them (want_nodes != 0)
 };
 void pga_render_release(pga_ctx*);   // render.hip: frees the buffers above
 // summary of a segmented launch's flags (host copy, [PGA_SEG_ROUNDS][stride]) into pga_ctx::dp_stats

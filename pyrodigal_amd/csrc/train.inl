@@ -750,6 +750,7 @@ static int train_body(pga_ctx* c, const pga_batch* batch, const pga_params* pp, 
 static int train_impl(pga_ctx* c, const pga_batch* batch, const pga_params* pp, const int32_t* tts, const double* sws, const int32_t* fns,
                       int upto, pga_training* out, int32_t* status) {
     if (!c) return PGA_EINVAL;
+    c->dev_nodes.clear();               // training runs the finder: it reuses the node arena of the last find
     const std::vector<pga_training> saved = c->models;
     bool replaced = false;
     const int rc = train_body(c, batch, pp, tts, sws, fns, upto, out, status, replaced);

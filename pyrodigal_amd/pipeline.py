@@ -149,12 +149,14 @@ def find_genes_fasta(path, model_blobs, n_contexts=2, device=0, max_bases=64 << 
                 c.close()
 
 
-def render_fasta(path, model_blobs, *, gff=None, faa=None, fna=None, n_contexts=2, device=0, max_bases=64 << 20, meta=False,
-                 descriptions=None, first_seqnum=1, gff_options=None, faa_options=None, fna_options=None, unbinned_model=None,
-                 **find_kw):
+def render_fasta(path, model_blobs, *, gff=None, faa=None, fna=None, gbk=None, scores=None, n_contexts=2, device=0, max_bases=64 << 20,
+                 meta=False, descriptions=None, first_seqnum=1, gff_options=None, faa_options=None, fna_options=None, gbk_options=None,
+                 scores_options=None, unbinned_model=None, **find_kw):
     """Call the genes of every record of a FASTA file and write them as text: GFF to ``gff``, protein FASTA to ``faa``, gene
-    FASTA to ``fna`` (binary file objects, or None), in file order -- what ``Genes.write_gff`` / ``write_translations`` /
-    ``write_genes`` write record after record.
+    FASTA to ``fna``, GenBank to ``gbk``, the start-score file to ``scores`` (binary file objects, or None), in file order --
+    what ``Genes.write_gff`` / ``write_translations`` / ``write_genes`` / ``write_genbank`` / ``write_scores`` write record after
+    record.  With ``scores`` the genes are found with ``want_nodes="device"``: the node arrays stay on the device for the
+    renderer.
 
     Runs like :func:`find_genes_fasta` (the C reader fills pinned arenas, ``n_contexts`` contexts side by side), but every batch
     is rendered on the device while it is still resident (``Context.render_genes``) and only its text comes back: memory stays
@@ -163,13 +165,18 @@ def render_fasta(path, model_blobs, *, gff=None, faa=None, fna=None, n_contexts=
     goes to ``Context.find_genes``.  Returns
     ``{"records", "bases", "genes", "fallback", "kernel_ms": {format: ms}}``."""
     formats = {}
-    for name, fh, opts in (("gff", gff, gff_options), ("faa", faa, faa_options), ("fna", fna, fna_options)):
+    for name, fh, opts in (("gff", gff, gff_options), ("faa", faa, faa_options), ("fna", fna, fna_options), ("gbk", gbk, gbk_options),
+                           ("scores", scores, scores_options)):
         if fh is not None:
             formats[name] = dict(opts or {})
     stats = {"records": 0, "bases": 0, "genes": 0, "fallback": 0, "kernel_ms": {k: 0.0 for k in formats}}
     if not formats:
         raise ValueError("render_fasta: no output requested")
-    sinks = {"gff": gff, "faa": faa, "fna": fna}
+    sinks = {"gff": gff, "faa": faa, "fna": fna, "gbk": gbk, "scores": scores}
+    if "gbk" in formats and formats["gbk"].get("date") is None:
+        import datetime
+        formats["gbk"]["date"] = datetime.date.today()       # one date for the whole file
+    want_nodes = "device" if scores is not None else False
     ctxs = [_cabi.Context(device) for _ in range(max(1, n_contexts))]
     for c in ctxs:
         c.set_models(list(model_blobs))
@@ -187,7 +194,7 @@ def render_fasta(path, model_blobs, *, gff=None, faa=None, fna=None, n_contexts=
                 ids, n, total = pb.ids, pb.n, pb.total
                 b = ctx.upload_packed(pb)                 # releases the arena
                 try:
-                    r = ctx.find_genes(b, meta=meta, **find_kw)
+                    r = ctx.find_genes(b, meta=meta, want_nodes=want_nodes, **find_kw)
                     text = ctx.render_genes(b, r, ids, formats, meta=meta, descriptions=descriptions, first_seqnum=seqnum,
                                             unbinned_model=unbinned_model)
                 finally:

@@ -1,11 +1,12 @@
 """Text output on one MI355X: the device renderer (Context.render_genes) against the host writers (Genes.write_*), and the
-command line from a FASTA file to GFF + protein FASTA.
+command line from a FASTA file to GFF + protein FASTA, and to GenBank + the start-score file.
 
-  (a) render kernels (length pass + scan + write pass) of GFF, protein and gene FASTA of one 6 250 x 20 kbp meta call, next to
-      that call's find_genes device time
-  (b) the host writers' loop (write_gff / write_translations / write_genes) over the same results
-  (c) python -m pyrodigal_amd -p meta from a FASTA file to GFF + .faa, wall time and Gbp/s, next to the Python loop over
-      GeneFinder.find_genes_batch + write_gff + write_translations on the same file
+  (a) render kernels (length pass + scan + write pass; scores: and the row sort) of GFF, protein FASTA, gene FASTA, GenBank and
+      the start scores of one 6 250 x 20 kbp meta call, next to that call's find_genes device time, with the node arrays kept on
+      the device (want_nodes="device") and without (want_nodes=0: the lean gather)
+  (b) the host writers' loop (write_gff / write_translations / write_genes / write_genbank / write_scores) over the same results
+  (c) python -m pyrodigal_amd -p meta from a FASTA file to GFF + .faa and to -f gbk + -s, wall time and Gbp/s, next to the
+      Python loop over GeneFinder.find_genes_batch + the writers on the same file
 
 Prints one JSON line.  Synthetic inputs go to a temporary directory."""
 import argparse
@@ -41,12 +42,14 @@ def main():
     descs = [name.replace(".gz", "") for name, _ in models]      # what the command line reports: the bin files' names
     b = ctx.upload(seqs)
     r = ctx.find_genes(b, meta=True)                   # warm-up
-    fg, rk, rw = [], {"gff": [], "faa": [], "fna": []}, []
+    fmts = _cabi.RENDER_FORMATS
+    fg, fg_lean, rk, rw = [], [], {k: [] for k in fmts}, []
     for _ in range(args.repeats):
-        r = ctx.find_genes(b, meta=True)
+        fg_lean.append(ctx.find_genes(b, meta=True).t_total_ms)
+        r = ctx.find_genes(b, meta=True, want_nodes="device")
         fg.append(r.t_total_ms)
         t0 = time.perf_counter()
-        txt = ctx.render_genes(b, r, ids, ("gff", "faa", "fna"), meta=True, descriptions=descs)
+        txt = ctx.render_genes(b, r, ids, fmts, meta=True, descriptions=descs, unbinned_model=min(5, len(models) - 1))
         rw.append((time.perf_counter() - t0) * 1e3)
         for k, v in txt.items():
             rk[k].append(v.kernel_ms)
@@ -54,6 +57,7 @@ def main():
     med = lambda xs: sorted(xs)[len(xs) // 2]
     out["genes"] = int(len(r.genes))
     out["find_genes_device_ms"] = med(fg)
+    out["find_genes_device_ms_lean"] = med(fg_lean)        # want_nodes=0, what bench.py runs
     out["render_kernel_ms"] = {k: med(v) for k, v in rk.items()}
     out["render_kernel_ms_total"] = sum(out["render_kernel_ms"].values())
     out["render_over_find"] = out["render_kernel_ms_total"] / out["find_genes_device_ms"]
@@ -69,11 +73,12 @@ def main():
     genes = finder.find_genes_batch(seqs)
     t_find = time.perf_counter() - t0
     host = {}
-    for fmt, meth in (("gff", "write_gff"), ("faa", "write_translations"), ("fna", "write_genes")):
+    for fmt, meth in (("gff", "write_gff"), ("faa", "write_translations"), ("fna", "write_genes"), ("gbk", "write_genbank"),
+                      ("scores", "write_scores")):
         s = io.StringIO()
         t0 = time.perf_counter()
         for g, sid in zip(genes, ids):
-            getattr(g, meth)(s, sid)
+            getattr(g, meth)(s, sid)              # (the finder keeps the nodes: write_scores needs them)
         host[fmt] = (time.perf_counter() - t0) * 1e3
         assert s.getvalue().encode() == txt[fmt].data, fmt          # the device text is the writers' text
     out["host_writer_ms"] = host
@@ -97,16 +102,25 @@ def main():
             paths.append(p)
         cmd = [sys.executable, "-m", "pyrodigal_amd", "-p", "meta", "-i", fa, "-o", os.path.join(tmp, "o.gff"), "-a",
                os.path.join(tmp, "o.faa"), "--meta-bins", *paths]
-        walls = []
+        cmd_gbk = [sys.executable, "-m", "pyrodigal_amd", "-p", "meta", "-i", fa, "-o", os.path.join(tmp, "o.gbk"), "-f", "gbk",
+                   "-s", os.path.join(tmp, "o.scores"), "--meta-bins", *paths]
+        walls, walls_gbk = [], []
         for _ in range(3):
             t0 = time.perf_counter()
             subprocess.run(cmd, cwd=ROOT, check=True, timeout=600)
             walls.append(time.perf_counter() - t0)
+            t0 = time.perf_counter()
+            subprocess.run(cmd_gbk, cwd=ROOT, check=True, timeout=600)
+            walls_gbk.append(time.perf_counter() - t0)
         with open(os.path.join(tmp, "o.gff"), "rb") as f:
             assert f.read() == txt["gff"].data
+        with open(os.path.join(tmp, "o.scores"), "rb") as f:
+            assert f.read() == txt["scores"].data
         bases = n * L
         out["cli_wall_s"] = med(walls)
         out["cli_gbps"] = bases / med(walls) / 1e9
+        out["cli_gbk_scores_wall_s"] = med(walls_gbk)
+        out["cli_gbk_scores_gbps"] = bases / med(walls_gbk) / 1e9
         # the Python loop the command line replaces: read, find_genes_batch, write_gff + write_translations
         t0 = time.perf_counter()
         recs = []
@@ -121,6 +135,15 @@ def main():
         out["host_loop_wall_s"] = time.perf_counter() - t0
         out["host_loop_gbps"] = bases / out["host_loop_wall_s"] / 1e9
         out["cli_over_host_loop"] = out["host_loop_wall_s"] / out["cli_wall_s"]
+        # ... and the loop -f gbk -s replaced: find_genes_batch with the nodes, write_genbank + write_scores
+        t0 = time.perf_counter()
+        gl = lib.GeneFinder(meta=True, metagenomic_bins=bins, keep_nodes=True).find_genes_batch([s for _, _, s in recs])
+        with open(os.path.join(tmp, "h.gbk"), "w") as g1, open(os.path.join(tmp, "h.scores"), "w") as g2:
+            for g, (sid, _, _) in zip(gl, recs):
+                g.write_genbank(g1, sid)
+                g.write_scores(g2, sid)
+        out["host_loop_gbk_scores_wall_s"] = time.perf_counter() - t0
+        out["cli_gbk_scores_over_host_loop"] = out["host_loop_gbk_scores_wall_s"] / out["cli_gbk_scores_wall_s"]
     print(json.dumps(out))
 
 
