@@ -219,6 +219,17 @@ int  pga_find_genes(pga_ctx*, const pga_batch*, const pga_params*, pga_result** 
  * node arrays (want_nodes), contigs[i].model = model_of_contig[i] and score.  params->meta must be 0; PGA_EINVAL for an index
  * outside [0, n_models).  Many genomes under their own models in one call (ref: the per-genome loop of benches/run_single). */
 int  pga_find_genes_models(pga_ctx*, const pga_batch*, const pga_params*, const int32_t* model_of_contig, pga_result** out);
+/* A new batch whose entry i is a copy of contig contig_of_entry[i] of the resident batch `src` (of the same context), copied device
+ * to device: the same genome under K models in one call needs one upload, not K.  Entries may repeat contigs and come in any order;
+ * they do not share letters. */
+int  pga_batch_replicate(pga_ctx*, const pga_batch* src, int32_t n, const int32_t* contig_of_entry, pga_batch** out);
+/* What pga_find_genes_models runs, reduced on the device to three numbers per contig: coding_bases[i] = the positions of contig i
+ * (1 .. length) that lie in [begin, end] of at least one of its genes, either strand, overlaps counted once; n_genes[i] and score[i]
+ * as pga_contig_result reports them.  The gene records stay on the device (a bitmap of the batch's bases, a popcount per contig);
+ * params->want_nodes is ignored (no node arrays are kept).  The coding density of a genome under a model is the sum of its contigs'
+ * coding_bases over the sum of their lengths: the measure that tells translation table 4 from 11. */
+int  pga_find_coding_bases(pga_ctx*, const pga_batch*, const pga_params*, const int32_t* model_of_contig, int64_t* coding_bases,
+                           int32_t* n_genes, double* score);
 
 /* ---- stage level --------------------------------------------------------- */
 /* The node arrays as the reference's Nodes methods leave them, one pga_nodes per contig of the batch

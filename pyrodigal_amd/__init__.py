@@ -11,7 +11,9 @@ __version__ = "0.1.0"
 _LIB_NAMES = ("GeneFinder", "Genes", "Gene", "Nodes", "Node", "Sequence", "TrainingInfo", "MetagenomicBin", "MetagenomicBins",
               "ConnectionScorer", "Mask", "METAGENOMIC_BINS", "TRANSLATION_TABLES", "PRODIGAL_VERSION", "MIN_SINGLE_GENOME",
               "IDEAL_SINGLE_GENOME")
-__all__ = list(_LIB_NAMES)
+__all__ = list(_LIB_NAMES) + ["TableSelection"]
+
+from .tables import TableSelection      # pure Python: the result of GeneFinder.select_translation_table
 
 
 def __getattr__(name):

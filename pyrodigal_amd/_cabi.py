@@ -21,6 +21,7 @@ EXPORTS = [
     "pga_fasta_open", "pga_fasta_next", "pga_fasta_error", "pga_fasta_close", "pga_train", "pga_dp_stats", "pga_dp_timings", "pga_extract_stats", "pga_dp_plan_summary", "pga_dp_start_order", "pga_cs_task_summary",
     "pga_fasta_next_packed", "pga_batch_create_packed", "pga_translate_genes", "pga_fasta_open_callback", "pga_fasta_release_spare", "pga_dp_xcd_order", "pga_release_cached",
     "pga_find_genes_models", "pga_train_batch", "pga_render_genes", "pga_render_free",
+    "pga_batch_replicate", "pga_find_coding_bases",
 ]
 STAGE_EXTRACT, STAGE_SCORE, STAGE_OVERLAP, STAGE_SEQUENCE = 1, 2, 3, 4
 
@@ -134,6 +135,8 @@ def load():
     L.pga_batch_free.restype = None; L.pga_batch_free.argtypes = [vp]
     L.pga_find_genes.restype = ctypes.c_int; L.pga_find_genes.argtypes = [vp, vp, _P(Params), _P(_P(Result))]
     L.pga_find_genes_models.restype = ctypes.c_int; L.pga_find_genes_models.argtypes = [vp, vp, _P(Params), vp, _P(_P(Result))]
+    L.pga_batch_replicate.restype = ctypes.c_int; L.pga_batch_replicate.argtypes = [vp, vp, i32, vp, _P(vp)]
+    L.pga_find_coding_bases.restype = ctypes.c_int; L.pga_find_coding_bases.argtypes = [vp, vp, _P(Params), vp, vp, vp, vp]
     L.pga_nodes_stage.restype = ctypes.c_int
     L.pga_nodes_stage.argtypes = [vp, vp, _P(Params), ctypes.c_int, ctypes.c_int, _P(_P(Result))]
     L.pga_train.restype = ctypes.c_int
@@ -539,6 +542,36 @@ def _find_genes(self, batch, meta=True, closed=False, min_gene=90, min_edge_gene
     return _unpack_result(self.L, res, wn == 1)
 
 
+def _replicate(self, batch, contig_of_entry):
+    """A new resident :class:`Batch` whose entry i is a device-side copy of contig ``contig_of_entry[i]`` of ``batch``."""
+    coe = np.ascontiguousarray(contig_of_entry, dtype=np.int32).reshape(-1)
+    h = ctypes.c_void_p()
+    rc = self.L.pga_batch_replicate(self.h, batch.h, int(coe.size), ctypes.c_void_p(coe.ctypes.data), ctypes.byref(h))
+    if rc != PGA_OK:
+        _raise(self.L, self.h, rc, "pga_batch_replicate")
+    b = Batch.__new__(Batch)
+    b.ctx, b.n, b.h = self, int(coe.size), h
+    b.total = None
+    return b
+
+
+def _find_coding_bases(self, batch, model_of_contig, closed=False, min_gene=90, min_edge_gene=60, max_overlap=60, mask=False,
+                       min_mask=50):
+    """Single mode with loaded model ``model_of_contig[i]`` on contig i, reduced on the device (``pga_find_coding_bases``).
+    Returns ``(coding_bases int64, n_genes int32, score float64)``, one entry per contig."""
+    p = Params(int(closed), min_gene, min_edge_gene, max_overlap, 0, 0, int(mask), min_mask)
+    moc = np.ascontiguousarray(model_of_contig, dtype=np.int32)
+    if moc.shape != (batch.n,):
+        raise ValueError(f"model_of_contig has {moc.size} entries for {batch.n} contigs")
+    n = max(batch.n, 1)
+    cov, ng, sc = np.zeros(n, np.int64), np.zeros(n, np.int32), np.zeros(n, np.float64)
+    rc = self.L.pga_find_coding_bases(self.h, batch.h, ctypes.byref(p), ctypes.c_void_p(moc.ctypes.data), cov.ctypes.data,
+                                      ng.ctypes.data, sc.ctypes.data)
+    if rc != PGA_OK:
+        _raise(self.L, self.h, rc, "pga_find_coding_bases")
+    return cov[:batch.n], ng[:batch.n], sc[:batch.n]
+
+
 def _find_genes_batch(self, seqs, **kw):
     """Upload + find + free: ``seqs`` is a list of ASCII ``bytes``/``str`` contigs."""
     b = Batch(self, seqs)
@@ -854,6 +887,8 @@ Context.upload_packed = _upload_packed
 Context.nodes_stage = _nodes_stage
 Context.find_genes = _find_genes
 Context.find_genes_batch = _find_genes_batch
+Context.replicate = _replicate
+Context.find_coding_bases = _find_coding_bases
 
 
 class FastaReader:

@@ -15,6 +15,10 @@ from . import __version__
 TRANSLATION_TABLES = frozenset(set(range(1, 7)) | set(range(9, 17)) | set(range(21, 27)) | {29, 30, 32, 33})
 
 
+def _table_arg(value):
+    return "auto" if value == "auto" else int(value)
+
+
 def argument_parser(prog="pyrodigal_amd"):
     p = argparse.ArgumentParser(prog=prog, add_help=False, formatter_class=argparse.ArgumentDefaultsHelpFormatter,
                                 description="Prodigal gene calling on an AMD Instinct MI355X.")
@@ -23,8 +27,9 @@ def argument_parser(prog="pyrodigal_amd"):
     p.add_argument("-d", metavar="nuc_file", help="Write nucleotide sequences of genes to the selected file.")
     p.add_argument("-f", metavar="output_type", choices=("gff", "gbk"), default="gff",
                    help="Select output format.")
-    p.add_argument("-g", metavar="tr_table", type=int, choices=sorted(TRANSLATION_TABLES), default=11,
-                   help="Specify a translation table to use.")
+    p.add_argument("-g", metavar="tr_table", type=_table_arg, choices=sorted(TRANSLATION_TABLES) + ["auto"], default=11,
+                   help="Specify a translation table to use; auto: 11, or 4 when its genes cover clearly more of the genome "
+                        "(single mode, before training).")
     p.add_argument("-i", metavar="input_file", help="Specify FASTA input file (plain, .gz, .bz2 or .xz; default: stdin).")
     p.add_argument("-m", action="store_true", default=False, help="Treat runs of N as masked sequence; don't build genes across them.")
     p.add_argument("-n", action="store_true", default=False, help="Bypass Shine-Dalgarno trainer and force a full motif scan.")

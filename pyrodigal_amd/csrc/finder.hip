@@ -909,6 +909,50 @@ k_emit_genes(const TailDesc* __restrict__ td, int n_contigs, int64_t n_slots, Ou
     out[gene_begin[c] + g] = G;
 }
 
+// Coding bases (pga_find_coding_bases): the positions [begin, end] of every gene record, clipped to its contig, set in a bitmap of
+// one bit per base of the batch (bit ct[contig].base + position - 1).  A wavefront per gene, its lanes over the 32-bit words the
+// gene touches; neighbouring genes and contigs share words, hence the atomic OR.
+__global__ void __launch_bounds__(256)
+k_cover_genes(const pga_gene* __restrict__ genes, int64_t n_genes, const ContigDesc* __restrict__ ct, int n_contigs, uint32_t* __restrict__ bits) {
+    const int64_t g = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    if (g >= n_genes) return;
+    const int c = genes[g].contig;
+    if (c < 0 || c >= n_contigs) return;
+    const int32_t b = max(genes[g].begin, 1), e = min(genes[g].end, ct[c].len);
+    if (b > e) return;
+    const int64_t b0 = ct[c].base + b - 1, b1 = ct[c].base + e - 1;     // inclusive bit range
+    const int64_t w0 = b0 >> 5, w1 = b1 >> 5;
+    for (int64_t w = w0 + lane; w <= w1; w += 64) {
+        uint32_t m = 0xffffffffu;
+        if (w == w0) m &= 0xffffffffu << (b0 & 31);
+        if (w == w1) m &= 0xffffffffu >> (31 - (b1 & 31));
+        atomicOr(&bits[w], m);
+    }
+}
+
+// A workgroup per contig: the set bits of [base, base + len).
+__global__ void __launch_bounds__(256)
+k_count_cover(const uint32_t* __restrict__ bits, const ContigDesc* __restrict__ ct, int64_t* __restrict__ coding) {
+    __shared__ int64_t part[4];
+    const int c = blockIdx.x;
+    const int64_t lo = ct[c].base, len = ct[c].len;
+    int64_t n = 0;
+    if (len > 0) {
+        const int64_t hi = lo + len - 1, w0 = lo >> 5, w1 = hi >> 5;
+        for (int64_t w = w0 + threadIdx.x; w <= w1; w += blockDim.x) {
+            uint32_t m = bits[w];
+            if (w == w0) m &= 0xffffffffu << (lo & 31);
+            if (w == w1) m &= 0xffffffffu >> (31 - (hi & 31));
+            n += __popc(m);
+        }
+    }
+    for (int d = 32; d > 0; d >>= 1) n += __shfl_down(n, d, 64);
+    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = n;
+    __syncthreads();
+    if (threadIdx.x == 0) coding[c] = part[0] + part[1] + part[2] + part[3];
+}
+
 #include "tail.inl"
 
 struct ResultOwner {
@@ -1370,8 +1414,10 @@ static int publish(ResultOwner* R, ResultOwner*& guarded, const pga_params& P, p
 // model_of_contig (single mode: the path and the SCORE / OVERLAP stages; nullptr = model 0 everywhere): contig i is scored with that
 // loaded model, its nodes extracted under that model's translation table -- the groups of meta mode, one chain per contig.
 // tt_of_contig (EXTRACT stage; nullptr = tt_override everywhere): contig i is extracted under that table.  At most 4 tables.
-static int find_impl(pga_ctx* c, const pga_batch* batch, const pga_params* pp, const int stage, const int tt_override, pga_result** out,
-                     const int32_t* model_of_contig, const int32_t* tt_of_contig) {
+// coding (stage 0, single mode; nullptr otherwise): coding[i] = bases of contig i inside at least one of its genes, counted where the
+// gene records are (pga_find_coding_bases); the records are then not copied back and the result holds no genes.
+static int find_impl_cov(pga_ctx* c, const pga_batch* batch, const pga_params* pp, const int stage, const int tt_override, pga_result** out,
+                         const int32_t* model_of_contig, const int32_t* tt_of_contig, int64_t* coding) {
     if (out) *out = nullptr;
     if (c) c->dev_nodes.clear();        // this call reuses the arena the last one kept on the device
     if (!c || !out || !pp || !batch || batch->ctx != c) {
@@ -2286,6 +2332,27 @@ static int find_impl(pga_ctx* c, const pga_batch* batch, const pga_params* pp, c
                 }
             };
             run_parallel(filler);
+            if (coding) {
+                // host tail (PGA_TAIL=host): the records are on the host already, so they are counted here -- a union of intervals per
+                // contig, the same definition as k_cover_genes / k_count_cover
+                std::vector<std::pair<int32_t, int32_t>> iv;
+                for (int i = 0; i < NC; i++) {
+                    iv.clear();
+                    const int32_t len = ct[i].len;
+                    for (const GeneRec& gr : cg[i]) {
+                        const int32_t b = std::max<int32_t>(gr.begin, 1), e = std::min<int32_t>(gr.end, len);
+                        if (b <= e) iv.emplace_back(b, e);
+                    }
+                    std::sort(iv.begin(), iv.end());
+                    int64_t n = 0; int32_t hi = 0;          // positions 1 .. hi are already counted
+                    for (const auto& x : iv) {
+                        if (x.second <= hi) continue;
+                        n += x.second - std::max(x.first - 1, hi);
+                        hi = x.second;
+                    }
+                    coding[i] = n;
+                }
+            }
         } else {
             tm.mark("gather");
             // ---- tail on the device: traceback untangling, bad-gene elimination, gene list, start tweaks ----------
@@ -2414,15 +2481,32 @@ static int find_impl(pga_ctx* c, const pga_batch* batch, const pga_params* pp, c
                 cr.model = chains[k].model; cr.n_nodes = chains[k].n;
                 cr.score = P.meta ? 0.0 : (h_ipath[k] >= 0 ? h_maxscore[k] : 0.0);
             }
-            pga_gene* const genes_out = R->gene_records((size_t)ngenes);
+            pga_gene* const genes_out = coding ? nullptr : R->gene_records((size_t)ngenes);
+            pga_gene* d_genes = nullptr;
             if (ngenes > 0) {
-                DEVBUF(d_genes, pga_gene, "d_genes_out", ngenes + 1);
+                DEVBUF(d_genes_out, pga_gene, "d_genes_out", ngenes + 1);
+                d_genes = d_genes_out;
                 HT(c, hipMemcpyAsync(d_gbegin, h_gbegin, sizeof(int64_t) * NC, hipMemcpyHostToDevice, st));
                 GcPtrs gcs{};
                 for (int g = 0; g < NG; g++) gcs.p[g] = ga[g].gc_cont;
                 hipLaunchKernelGGL(k_emit_genes, dim3((unsigned)((n_slots + 255) / 256)), dim3(256), 0, st, d_td, NC, n_slots, o, d_gene2, d_ngenes,
                                    d_gbegin, P.meta ? 0 : 1, d_genes, lean_gather ? 1 : 0, ca, gcs);
-                HT(c, hipMemcpyAsync(genes_out, d_genes, sizeof(pga_gene) * (size_t)ngenes, hipMemcpyDeviceToHost, st));
+                if (!coding) HT(c, hipMemcpyAsync(genes_out, d_genes, sizeof(pga_gene) * (size_t)ngenes, hipMemcpyDeviceToHost, st));
+            }
+            if (coding) {
+                // the coverage of the resident records: one bit per base of the batch, then a popcount per contig; NC counts come back
+                const int64_t words = total / 32 + 2;
+                DEVBUF(d_cover, uint32_t, "d_cover", words);
+                DEVBUF(d_coding, int64_t, "d_coding", NC + 1);
+                PINBUF(h_coding, int64_t, "h_coding", NC + 1);
+                HT(c, hipMemsetAsync(d_cover, 0, sizeof(uint32_t) * (size_t)words, st));
+                if (ngenes > 0)
+                    hipLaunchKernelGGL(k_cover_genes, dim3((unsigned)((ngenes + 3) / 4)), dim3(256), 0, st, d_genes, ngenes, d_ct, NC, d_cover);
+                hipLaunchKernelGGL(k_count_cover, dim3((unsigned)NC), dim3(256), 0, st, d_cover, d_ct, d_coding);
+                HT(c, hipMemcpyAsync(h_coding, d_coding, sizeof(int64_t) * NC, hipMemcpyDeviceToHost, st));
+                HT(c, hipGetLastError());
+                HT(c, hipStreamSynchronize(st));
+                memcpy(coding, h_coding, sizeof(int64_t) * NC);
             }
             if (P.want_nodes == 1 && out_nodes > 0) {
                 tracef.resize((size_t)out_nodes + 1); elim.resize((size_t)out_nodes + 1);
@@ -2485,6 +2569,11 @@ static int find_impl(pga_ctx* c, const pga_batch* batch, const pga_params* pp, c
     return publish(R, guard.r, P, out);
 }
 
+static int find_impl(pga_ctx* c, const pga_batch* batch, const pga_params* pp, const int stage, const int tt_override, pga_result** out,
+                     const int32_t* model_of_contig, const int32_t* tt_of_contig) {
+    return find_impl_cov(c, batch, pp, stage, tt_override, out, model_of_contig, tt_of_contig, nullptr);
+}
+
 #include "train.inl"
 
 extern "C" int pga_find_genes(pga_ctx* c, const pga_batch* batch, const pga_params* pp, pga_result** out) {
@@ -2532,4 +2621,71 @@ extern "C" int pga_train(pga_ctx* c, const pga_batch* batch, const pga_params* p
 extern "C" int pga_train_batch(pga_ctx* c, const pga_batch* batch, const pga_params* pp, const int32_t* translation_table,
                                const double* start_weight, const int32_t* force_nonsd, int upto, pga_training* out, int32_t* status) {
     return train_impl(c, batch, pp, translation_table, start_weight, force_nonsd, upto <= 0 ? TR_ALL : upto, out, status);
+}
+
+extern "C" int pga_find_coding_bases(pga_ctx* c, const pga_batch* batch, const pga_params* pp, const int32_t* model_of_contig,
+                                     int64_t* coding_bases, int32_t* n_genes, double* score) {
+    if (!c) return PGA_EINVAL;
+    if (!batch || !pp || !model_of_contig || !coding_bases || !n_genes || !score) { c->err = "pga_find_coding_bases: bad arguments"; return PGA_EINVAL; }
+    if (pp->meta) { c->err = "pga_find_coding_bases: a single-mode call (params->meta must be 0)"; return PGA_EINVAL; }
+    for (int i = 0; i < batch->n; i++)
+        if (model_of_contig[i] < 0 || model_of_contig[i] >= c->n_models) {
+            c->err = "pga_find_coding_bases: contig " + std::to_string(i) + " names model " + std::to_string(model_of_contig[i]) + " of " +
+                     std::to_string(c->n_models) + " loaded";
+            return PGA_EINVAL;
+        }
+    for (int i = 0; i < batch->n; i++) { coding_bases[i] = 0; n_genes[i] = 0; score[i] = 0.0; }
+    pga_params P = *pp;
+    P.want_nodes = 0;                       // nothing of the nodes is kept or gathered for the host
+    pga_result* r = nullptr;
+    const int rc = find_impl_cov(c, batch, &P, 0, 0, &r, model_of_contig, nullptr, coding_bases);
+    if (rc != PGA_OK) return rc;
+    for (int i = 0; i < batch->n; i++) { n_genes[i] = r->contigs[i].n_genes; score[i] = r->contigs[i].score; }
+    pga_result_free(r);
+    return PGA_OK;
+}
+
+extern "C" int pga_batch_replicate(pga_ctx* c, const pga_batch* src, int32_t n, const int32_t* contig_of_entry, pga_batch** out) {
+    if (out) *out = nullptr;
+    if (!c) return PGA_EINVAL;
+    if (!src || !out || n < 0 || (n > 0 && !contig_of_entry) || src->ctx != c) { c->err = "pga_batch_replicate: bad arguments"; return PGA_EINVAL; }
+    for (int i = 0; i < n; i++)
+        if (contig_of_entry[i] < 0 || contig_of_entry[i] >= src->n) {
+            c->err = "pga_batch_replicate: entry " + std::to_string(i) + " names contig " + std::to_string(contig_of_entry[i]) + " of " +
+                     std::to_string(src->n);
+            return PGA_EINVAL;
+        }
+    if (!c->finder) { int rc = pga_finder_models_changed(c); if (rc) return rc; }
+    HT(c, hipSetDevice(c->device));
+    pga_batch* b = new (std::nothrow) pga_batch();
+    if (!b) return PGA_ENOMEM;
+    b->ctx = c; b->n = n; b->d_seq = nullptr; b->d_tiles = nullptr; b->d_tile0 = nullptr; b->n_tiles = 0; b->ct.resize((size_t)n + 1);
+    int64_t total = 0;
+    for (int i = 0; i < n; i++) { b->ct[i].base = total; b->ct[i].len = src->ct[contig_of_entry[i]].len; b->ct[i]._pad = 0; total += b->ct[i].len; }
+    b->ct[n].base = total; b->ct[n].len = 0; b->ct[n]._pad = 0;
+    b->total = total;
+    if (total >= 0x7fffffffLL) { delete b; c->err = "pga_batch_replicate: batch larger than 2^31 bases; split it"; return PGA_EINVAL; }
+    if (total > 0) {
+        std::vector<TileDesc> tiles; std::vector<int32_t> tile0;
+        batch_tiles(b, tiles, tile0);
+        if (batch_take_dev(c, (size_t)total + 16 + batch_tiles_bytes(tiles, tile0), &b->d_seq, &b->d_seq_cap) != hipSuccess) { delete b; c->err = "pga_batch_replicate: hipMalloc failed"; return PGA_ENOMEM; }
+        std::lock_guard<std::mutex> up(c->finder->up_mu);
+        hipStream_t st = nullptr;
+        { const int rc = upload_resources(c, 0, &st, nullptr); if (rc) { batch_give_dev(c, b->d_seq, b->d_seq_cap); delete b; return rc; } }
+        // device to device, one copy per run of entries that are consecutive contigs of the source
+        hipError_t e = hipSuccess;
+        for (int i = 0; i < n && e == hipSuccess;) {
+            int j = i + 1;
+            while (j < n && contig_of_entry[j] == contig_of_entry[j - 1] + 1) j++;
+            const ContigDesc& s0 = src->ct[contig_of_entry[i]];
+            const int64_t bytes = b->ct[j].base - b->ct[i].base;
+            if (bytes > 0) e = hipMemcpyAsync(b->d_seq + b->ct[i].base, src->d_seq + s0.base, (size_t)bytes, hipMemcpyDeviceToDevice, st);
+            i = j;
+        }
+        if (e == hipSuccess) e = batch_upload_tiles(b, b->d_seq + total + 16, tiles, tile0, st);
+        if (e == hipSuccess) e = hipStreamSynchronize(st);
+        if (e != hipSuccess) { batch_give_dev(c, b->d_seq, b->d_seq_cap); delete b; return pga_hip_try_(c, e, "replication of the batch"); }
+    }
+    *out = b;
+    return PGA_OK;
 }

@@ -117,6 +117,9 @@ cdef extern from "pyrodigal_amd.h" nogil:
                             int unknown_residue, int include_stop, int strict, const int64_t* offsets, char* out)
     int pga_batch_create(pga_ctx*, int32_t n, const char* const* seqs, const int64_t* lens, pga_batch** out)
     void pga_batch_free(pga_batch*)
+    int pga_batch_replicate(pga_ctx*, const pga_batch* src, int32_t n, const int32_t* contig_of_entry, pga_batch** out)
+    int pga_find_coding_bases(pga_ctx*, const pga_batch*, const pga_params*, const int32_t* model_of_contig, int64_t* coding_bases,
+                              int32_t* n_genes, double* score)
     int PGA_STAGE_EXTRACT, PGA_STAGE_SCORE, PGA_STAGE_OVERLAP, PGA_STAGE_SEQUENCE
     int pga_nodes_stage(pga_ctx*, const pga_batch*, const pga_params*, int stage, int translation_table, pga_result** out)
     int pga_train(pga_ctx*, const pga_batch*, const pga_params*, int translation_table, double start_weight, int force_nonsd,
@@ -138,7 +141,11 @@ IDEAL_SINGLE_GENOME = 100000
 TRANSLATION_TABLES = frozenset(set(range(1, 7)) | set(range(9, 17)) | set(range(21, 27)) | {29, 30, 32, 33})
 PRODIGAL_VERSION = "v2.6.3+c1e2d36"
 from pyrodigal_amd import __version__ as _VERSION      # one definition: the package's
+from pyrodigal_amd import tables as _tables
+from pyrodigal_amd.tables import TableSelection
 TRAINING_INFO_SIZE = 558392
+# select_translation_table: the most models (TrainingInfo, 558 392 bytes each) one device call loads
+_SELECT_MAX_MODELS = 256
 
 _RBS_MOTIF = [
     None, "GGA/GAG/AGG", "3Base/5BMM", "4Base/6BMM", "AGxAG", "AGxAG", "GGA/GAG/AGG", "GGxGG", "GGxGG",
@@ -1932,6 +1939,190 @@ cdef class GeneFinder:
             warnings.warn("%ssequence should be at least %d characters (%d found)" % (which, IDEAL_SINGLE_GENOME, len(seq)))
         return seq
 
+    def select_translation_table(self, object genomes, *, object candidates=(11, 4), double min_gain=0.05, double min_density=0.7,
+                                 bint force_nonsd=False, double start_weight=4.35):
+        """The translation table of every genome, chosen by coding density (`pyrodigal_amd.tables`), on the device.
+
+        A genome is one sequence or a list / tuple of contigs, as `train_batch` takes it.  For every candidate table it is trained
+        (the contigs joined with linkers, this finder's options, `force_nonsd`, `start_weight`) and its contigs called with that
+        model, one by one; the coding bases -- positions inside at least one gene -- are counted on the device where the gene
+        records are (`pga_find_coding_bases`).  A candidate other than the first (the default) wins when it covers more than
+        `min_gain` more of the genome and more than `min_density` of it; the best such candidate, else the default.
+
+        Returns one read-only `TableSelection` per genome: `translation_table`, its `training_info`, `coding_density` and
+        `coding_bases` of every candidate, `length`.  The genomes are uploaded once per device call and copied on the device for
+        every candidate; only a few numbers per genome come back.  The finder's own `training_info` is left alone."""
+        if self.meta:
+            raise RuntimeError("cannot use training sequence in metagenomic mode")
+        cands = _tables.check_candidates(candidates)
+        min_gain, min_density = _tables.check_thresholds(min_gain, min_density)
+        cdef list gl = list(genomes)
+        return self._select_tables(gl, cands, min_gain, min_density, [bool(force_nonsd)] * len(gl), [float(start_weight)] * len(gl),
+                                   "genome %d: ", list(range(len(gl))))
+
+    def _select_tables(self, list gl, tuple cands, double min_gain, double min_density, list fns, list sws, str which, list names):
+        """`select_translation_table` with one `force_nonsd` / `start_weight` per genome (`names[g]`: the genome's number in messages)."""
+        cdef Py_ssize_t G = len(gl), K = len(cands), g, k
+        if G == 0:
+            return []
+        # per genome: the joined training sequence (train's length rules) and the contigs as find_genes wraps them
+        cdef list train_seqs = [], contigs = [], lengths = []
+        for g in range(G):
+            x = gl[g]
+            parts = list(x) if isinstance(x, (list, tuple)) else [x]
+            if not parts:
+                raise ValueError((which % names[g]) + "no sequence")
+            train_seqs.append(self._training_sequence(parts[0], tuple(parts[1:]), which % names[g]))
+            cs = self._wrap_sequences(parts)
+            contigs.append(cs)
+            lengths.append(sum([len((<Sequence> c).data) for c in cs]))
+        # the device calls: consecutive genomes, every candidate of a genome in the same call; K copies of a genome count against
+        # `coalesce_bases`, and at most _SELECT_MAX_MODELS models are loaded at once
+        cdef list calls = [], cur = []
+        cdef int64_t bases = 0, nb
+        for g in range(G):
+            nb = K * len((<Sequence> train_seqs[g]).data)
+            if cur and (bases + nb > self.coalesce_bases or (len(cur) + 1) * K > _SELECT_MAX_MODELS):
+                calls.append(cur); cur = []; bases = 0
+            cur.append(g); bases += nb
+        calls.append(cur)
+        cdef list out = [None] * G
+        cdef _FinderSlot slot
+        with self._cv:
+            while True:
+                slot = self._free_slot()
+                if slot is not None:
+                    break
+                self._cv.wait()
+            slot.busy = True
+        try:
+            if slot.ctx == NULL:
+                rc = pga_create(self.device, &slot.ctx)
+                if rc != PGA_OK:
+                    slot.ctx = NULL
+                    _raise_for(NULL, rc, "pga_create")
+            slot.models_loaded = False            # the training and the K models of every genome replace the loaded set
+            for idx in calls:
+                raws, cov = self._select_call(slot, idx, train_seqs, contigs, cands, fns, sws, names)
+                for j, g in enumerate(idx):
+                    coding = {cands[k]: int(cov[k, j]) for k in range(K)}
+                    dens = {t: _tables.coding_density(n, lengths[g]) for t, n in coding.items()}
+                    t = _tables.choose_table(dens, cands, min_gain, min_density)
+                    k = cands.index(t)
+                    out[g] = TableSelection(t, TrainingInfo(raw=raws[k][j]), coding, lengths[g])
+        finally:
+            with self._lock:
+                self._release_slot(slot)
+        return out
+
+    cdef tuple _select_call(self, _FinderSlot slot, list idx, list train_seqs, list contigs, tuple cands, list fns, list sws,
+                            list names):
+        """One device call of `_select_tables` over the genomes `idx`: train every genome under every candidate, then call its
+        contigs under each of those models and count the coding bases.  Returns (raws[k][j], coding[k, j]) for cands[k], idx[j]."""
+        cdef Py_ssize_t n = len(idx), K = len(cands), nc, j, k, i, e
+        cdef pga_ctx* ctx = slot.ctx
+        cdef pga_params p
+        cdef pga_batch* up = NULL
+        cdef pga_batch* rep = NULL
+        cdef const char** ptrs = NULL
+        cdef int64_t* lens = NULL
+        cdef const pga_training** mptrs = NULL
+        cdef int rc
+        cdef size_t p_coe, p_tt, p_sw, p_fn, p_out, p_st, p_moc, p_cov, p_ng, p_sc
+        p.closed = self.closed; p.min_gene = self.min_gene; p.min_edge_gene = self.min_edge_gene
+        p.max_overlap = self.max_overlap; p.meta = 0; p.want_nodes = 0
+        p.mask = self.mask; p.min_mask = self.min_mask
+        # 1. the joined genomes, uploaded once and copied K times on the device (entry k * n + j: genome idx[j] under cands[k])
+        coe = np.tile(np.arange(n, dtype=np.int32), K)
+        a_tt = np.repeat(np.array(cands, np.int32), n)
+        a_sw = np.tile(np.array([sws[g] for g in idx], np.float64), K)
+        a_fn = np.tile(np.array([int(fns[g]) for g in idx], np.int32), K)
+        raw = np.zeros(n * K * TRAINING_INFO_SIZE, np.uint8)
+        status = np.zeros(n * K, np.int32)
+        p_coe = coe.ctypes.data; p_tt = a_tt.ctypes.data; p_sw = a_sw.ctypes.data; p_fn = a_fn.ctypes.data
+        p_out = raw.ctypes.data; p_st = status.ctypes.data
+        ptrs = <const char**> malloc(sizeof(char*) * max(n, 1))
+        lens = <int64_t*> malloc(sizeof(int64_t) * max(n, 1))
+        if ptrs == NULL or lens == NULL:
+            free(ptrs); free(lens)
+            raise MemoryError()
+        try:
+            for j in range(n):
+                ptrs[j] = PyBytes_AS_STRING((<Sequence> train_seqs[idx[j]]).data)
+                lens[j] = len((<Sequence> train_seqs[idx[j]]).data)
+            rc = pga_batch_create(ctx, <int32_t> n, ptrs, lens, &up)
+        finally:
+            free(ptrs); free(lens)
+        if rc != PGA_OK:
+            _raise_for(ctx, rc, "pga_batch_create")
+        try:
+            rc = pga_batch_replicate(ctx, up, <int32_t> (n * K), <const int32_t*> p_coe, &rep)
+            if rc != PGA_OK:
+                _raise_for(ctx, rc, "pga_batch_replicate")
+            with nogil:
+                rc = pga_train_batch(ctx, rep, &p, <const int32_t*> p_tt, <const double*> p_sw, <const int32_t*> p_fn, 0,
+                                     <pga_training*> p_out, <int32_t*> p_st)
+            if rc != PGA_OK:
+                _raise_for(ctx, rc, "pga_train_batch")
+        finally:
+            pga_batch_free(rep); rep = NULL
+            pga_batch_free(up); up = NULL
+        for e in range(n * K):
+            if status[e] != PGA_OK:
+                raise ValueError("genome %d could not be trained with translation table %d: no start / stop node in the sequence"
+                                 % (names[idx[e % n]], cands[e // n]))
+        # 2. the contigs, uploaded once and copied K times; contig i of genome j under model k * n + j
+        cdef list cseqs = []
+        cdef list genome_of = []
+        for j in range(n):
+            for c in contigs[idx[j]]:
+                cseqs.append(c); genome_of.append(j)
+        nc = len(cseqs)
+        coe = np.tile(np.arange(nc, dtype=np.int32), K)
+        gof = np.array(genome_of, np.int32)
+        moc = (np.repeat(np.arange(K, dtype=np.int32) * n, nc) + np.tile(gof, K)).astype(np.int32)
+        cov = np.zeros(max(nc * K, 1), np.int64)
+        ng = np.zeros(max(nc * K, 1), np.int32)
+        sc = np.zeros(max(nc * K, 1), np.float64)
+        p_coe = coe.ctypes.data; p_moc = moc.ctypes.data; p_cov = cov.ctypes.data; p_ng = ng.ctypes.data; p_sc = sc.ctypes.data
+        ptrs = <const char**> malloc(sizeof(char*) * max(nc, 1))
+        lens = <int64_t*> malloc(sizeof(int64_t) * max(nc, 1))
+        mptrs = <const pga_training**> malloc(sizeof(void*) * max(n * K, 1))
+        if ptrs == NULL or lens == NULL or mptrs == NULL:
+            free(ptrs); free(lens); free(mptrs)
+            raise MemoryError()
+        try:
+            for i in range(nc):
+                ptrs[i] = PyBytes_AS_STRING((<Sequence> cseqs[i]).data)
+                lens[i] = len((<Sequence> cseqs[i]).data)
+            for e in range(n * K):
+                mptrs[e] = <const pga_training*> <size_t> (p_out + <size_t> e * TRAINING_INFO_SIZE)
+            rc = pga_set_models(ctx, mptrs, <int> (n * K))
+            if rc != PGA_OK:
+                _raise_for(ctx, rc, "pga_set_models")
+            rc = pga_batch_create(ctx, <int32_t> nc, ptrs, lens, &up)
+            if rc != PGA_OK:
+                _raise_for(ctx, rc, "pga_batch_create")
+        finally:
+            free(ptrs); free(lens); free(mptrs)
+        try:
+            rc = pga_batch_replicate(ctx, up, <int32_t> (nc * K), <const int32_t*> p_coe, &rep)
+            if rc != PGA_OK:
+                _raise_for(ctx, rc, "pga_batch_replicate")
+            with nogil:
+                rc = pga_find_coding_bases(ctx, rep, &p, <const int32_t*> p_moc, <int64_t*> p_cov, <int32_t*> p_ng, <double*> p_sc)
+            if rc != PGA_OK:
+                _raise_for(ctx, rc, "pga_find_coding_bases")
+        finally:
+            pga_batch_free(rep)
+            pga_batch_free(up)
+        # 3. per genome and candidate: the sum over its contigs
+        coding = np.zeros((K, n), np.int64)
+        for k in range(K):
+            np.add.at(coding[k], gof, cov[k * nc:(k + 1) * nc])
+        raws = [[raw[(k * n + j) * TRAINING_INFO_SIZE:(k * n + j + 1) * TRAINING_INFO_SIZE].copy() for j in range(n)] for k in range(K)]
+        return raws, coding
+
     def train_batch(self, object genomes, *, object force_nonsd=False, object start_weight=4.35, object translation_table=11):
         """`train` on many genomes at once, on the device (`pga_train_batch`): every stage and training round runs once for the
         whole batch.  A genome is one sequence or a list / tuple of contigs (joined as `train(*contigs)` joins them); the
@@ -1953,9 +2144,25 @@ cdef class GeneFinder:
         cdef list fns = [bool(x) for x in per_genome(force_nonsd, "force_nonsd")]
         cdef list sws = [float(x) for x in per_genome(start_weight, "start_weight")]
         cdef list tts = per_genome(translation_table, "translation_table")
+        cdef list auto = []
         for g in range(G):
-            if tts[g] not in TRANSLATION_TABLES:
+            if isinstance(tts[g], str) and tts[g] == "auto":
+                auto.append(g)
+            elif isinstance(tts[g], (str, bytes)) or tts[g] not in TRANSLATION_TABLES:
                 raise ValueError("genome %d: %r is not a valid translation table index" % (g, tts[g]))
+        if auto:
+            # "auto": the table of `select_translation_table` with its defaults; the other genomes train as they are
+            rest = [g for g in range(G) if g not in set(auto)]
+            picked = self._select_tables([gl[g] for g in auto], _tables.DEFAULT_CANDIDATES, _tables.DEFAULT_MIN_GAIN,
+                                         _tables.DEFAULT_MIN_DENSITY, [fns[g] for g in auto], [sws[g] for g in auto], "genome %d: ", auto)
+            trained = self.train_batch([gl[g] for g in rest], force_nonsd=[fns[g] for g in rest], start_weight=[sws[g] for g in rest],
+                                       translation_table=[tts[g] for g in rest]) if rest else []
+            merged = [None] * G
+            for ga, sel in zip(auto, picked):
+                merged[ga] = sel.training_info
+            for ga, tinf in zip(rest, trained):
+                merged[ga] = tinf
+            return merged
         cdef list seqs = []
         for g in range(G):
             x = gl[g]
@@ -2039,10 +2246,12 @@ cdef class GeneFinder:
                 self._release_slot(slot)
         return out
 
-    def train(self, object sequence, *sequences, bint force_nonsd=False, double start_weight=4.35, int translation_table=11):
+    def train(self, object sequence, *sequences, bint force_nonsd=False, double start_weight=4.35, object translation_table=11):
         """Train on the given genome, on the device, and use the result for the next `find_genes` (ref: lib.pyx:5471-5575).
 
-        Several sequences (the contigs of one genome) are joined with `TTAATTAATTAA` linkers like in Prodigal."""
+        Several sequences (the contigs of one genome) are joined with `TTAATTAATTAA` linkers like in Prodigal.
+        `translation_table="auto"` trains with the table `select_translation_table` chooses with its defaults (11, or 4 when it
+        covers clearly more of the genome); the contigs are then also called one by one, as `find_genes` calls them."""
         import warnings
         cdef Sequence seq
         cdef pga_params p
@@ -2055,8 +2264,15 @@ cdef class GeneFinder:
         cdef pga_ctx* ctx
         if self.meta:
             raise RuntimeError("cannot use training sequence in metagenomic mode")
-        if translation_table not in TRANSLATION_TABLES:
-            raise ValueError("%d is not a valid translation table index" % translation_table)
+        if isinstance(translation_table, str):
+            if translation_table != "auto":
+                raise ValueError("%r is not a valid translation table index (an int, or \"auto\")" % (translation_table,))
+            picked = self.select_translation_table([(sequence,) + sequences], force_nonsd=force_nonsd, start_weight=start_weight)[0]
+            self.training_info = picked.training_info
+            return picked.training_info
+        cdef int tt = translation_table       # an int as before ("auto" above)
+        if tt not in TRANSLATION_TABLES:
+            raise ValueError("%d is not a valid translation table index" % tt)
         seq = self._training_sequence(sequence, sequences, "")
         p.closed = self.closed; p.min_gene = self.min_gene; p.min_edge_gene = self.min_edge_gene
         p.max_overlap = self.max_overlap; p.meta = 0; p.want_nodes = 0
@@ -2086,7 +2302,7 @@ cdef class GeneFinder:
                 _raise_for(ctx, rc, "pga_batch_create")
             try:
                 with nogil:
-                    rc = pga_train(ctx, batch, &p, translation_table, start_weight, force_nonsd, 0, <pga_training*> out_ptr)
+                    rc = pga_train(ctx, batch, &p, tt, start_weight, force_nonsd, 0, <pga_training*> out_ptr)
                 if rc != PGA_OK:
                     _raise_for(ctx, rc, "pga_train")
             finally:
