@@ -115,7 +115,8 @@ typedef struct pga_result {
     int64_t            node_passes;           /* sum over (contig, model) DP passes of node count */
     int32_t            n_chains;              /* number of (contig, model) DP passes */
     int32_t            _pad;
-    /* masked regions when params.mask is set, else NULL: contig i owns masks[2*k], masks[2*k+1] = [begin, end)
+    /* masked regions when params.mask or a mask source of the batch (pga_batch_set_regions / _set_mask_case) is set, else NULL:
+     * the union of the sources, contig i owns masks[2*k], masks[2*k+1] = [begin, end)
      * for k in [mask_off[i], mask_off[i+1])   (ref: lib.pyx:699-713, `Sequence.masks`) */
     int32_t*           mask_off;
     int32_t*           masks;
@@ -213,6 +214,19 @@ int  pga_batch_create(pga_ctx*, int32_t n_contigs, const char* const* seqs, cons
  * (pga_fasta_next_packed): no host-side packing, one DMA of the whole batch.  The buffer may be reused when the call returns. */
 int  pga_batch_create_packed(pga_ctx*, int32_t n_contigs, const char* packed, const int64_t* offs, const int64_t* lens, pga_batch** out);
 void pga_batch_free(pga_batch*);
+/* More mask sources, attached to the resident batch: every call that takes the batch (pga_find_genes*, pga_nodes_stage, pga_train*,
+ * pga_find_coding_bases) honours them, with params.mask on or off, and pga_batch_replicate carries them to its copies.  A region from
+ * any source takes part in the mask test exactly as a masked run of N at the same coordinates would; its bases keep their identity
+ * for everything else (GC content, model choice, scores, the printed sequence).  The extraction sees the UNION of all sources per
+ * contig -- sorted, disjoint, touching intervals joined -- built on the device, and pga_result.masks reports that union.
+ *   pga_batch_set_regions    contig i owns the intervals iv[2 k], iv[2 k + 1] = [begin, end), 0-based, for k in [off[i], off[i + 1]);
+ *                            any order, overlaps and duplicates allowed, no minimum length.  0 <= begin < end <= length is checked:
+ *                            PGA_EINVAL names the sequence and the interval.  NULL, NULL detaches them.
+ *   pga_batch_set_mask_case  1: runs of lower-case letters of at least params.min_mask positions (or that reach the end of their
+ *                            sequence) are masked, by the rule of the runs of unknown bases; the letters still read as their bases.
+ * Not to be called while a call on the batch runs. */
+int  pga_batch_set_regions(pga_batch*, const int32_t* off /* n + 1 */, const int32_t* iv /* 2 per interval */);
+int  pga_batch_set_mask_case(pga_batch*, int lower_case);
 int  pga_find_genes(pga_ctx*, const pga_batch*, const pga_params*, pga_result** out);
 /* Single mode, contig i called with loaded model model_of_contig[i] (an index into the pga_set_models set): every contig's result
  * is identical to pga_find_genes with that one model loaded -- its nodes extracted under that model's translation table, its genes,

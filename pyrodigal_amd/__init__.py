@@ -9,7 +9,7 @@ The names of ``pyrodigal_amd.lib`` are re-exported lazily: importing the package
 __version__ = "0.1.0"
 
 _LIB_NAMES = ("GeneFinder", "Genes", "Gene", "Nodes", "Node", "Sequence", "TrainingInfo", "MetagenomicBin", "MetagenomicBins",
-              "ConnectionScorer", "Mask", "METAGENOMIC_BINS", "TRANSLATION_TABLES", "PRODIGAL_VERSION", "MIN_SINGLE_GENOME",
+              "ConnectionScorer", "Mask", "Masks", "METAGENOMIC_BINS", "TRANSLATION_TABLES", "PRODIGAL_VERSION", "MIN_SINGLE_GENOME",
               "IDEAL_SINGLE_GENOME")
 __all__ = list(_LIB_NAMES) + ["TableSelection"]
 

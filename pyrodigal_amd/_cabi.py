@@ -22,6 +22,7 @@ EXPORTS = [
     "pga_fasta_next_packed", "pga_batch_create_packed", "pga_translate_genes", "pga_fasta_open_callback", "pga_fasta_release_spare", "pga_dp_xcd_order", "pga_release_cached",
     "pga_find_genes_models", "pga_train_batch", "pga_render_genes", "pga_render_free",
     "pga_batch_replicate", "pga_find_coding_bases",
+    "pga_batch_set_regions", "pga_batch_set_mask_case",
 ]
 STAGE_EXTRACT, STAGE_SCORE, STAGE_OVERLAP, STAGE_SEQUENCE = 1, 2, 3, 4
 
@@ -136,6 +137,8 @@ def load():
     L.pga_find_genes.restype = ctypes.c_int; L.pga_find_genes.argtypes = [vp, vp, _P(Params), _P(_P(Result))]
     L.pga_find_genes_models.restype = ctypes.c_int; L.pga_find_genes_models.argtypes = [vp, vp, _P(Params), vp, _P(_P(Result))]
     L.pga_batch_replicate.restype = ctypes.c_int; L.pga_batch_replicate.argtypes = [vp, vp, i32, vp, _P(vp)]
+    L.pga_batch_set_regions.restype = ctypes.c_int; L.pga_batch_set_regions.argtypes = [vp, vp, vp]
+    L.pga_batch_set_mask_case.restype = ctypes.c_int; L.pga_batch_set_mask_case.argtypes = [vp, ctypes.c_int]
     L.pga_find_coding_bases.restype = ctypes.c_int; L.pga_find_coding_bases.argtypes = [vp, vp, _P(Params), vp, vp, vp, vp]
     L.pga_nodes_stage.restype = ctypes.c_int
     L.pga_nodes_stage.argtypes = [vp, vp, _P(Params), ctypes.c_int, ctypes.c_int, _P(_P(Result))]
@@ -382,8 +385,51 @@ def _seq_pointers_fn():
     return _SEQ_POINTERS[0]
 
 
+def pack_regions(regions, n):
+    """The caller's masked regions as ``pga_batch_set_regions`` takes them: ``regions`` holds one entry per sequence, ``None`` or
+    an iterable of ``(begin, end)`` pairs (or objects with ``begin`` / ``end``), 0-based and half-open.  Returns ``(off, iv)``
+    int32 arrays, or ``None`` when no sequence carries one."""
+    if regions is None:
+        return None
+    regions = list(regions)
+    if len(regions) != n:
+        raise ValueError(f"regions has {len(regions)} entries for {n} sequences")
+    off = np.zeros(n + 1, np.int32)
+    flat = []
+    for i, r in enumerate(regions):
+        if r is not None:
+            if isinstance(r, np.ndarray):
+                a = np.asarray(r, dtype=np.int64).reshape(-1, 2)
+            else:
+                a = np.asarray([(m.begin, m.end) if hasattr(m, "begin") else tuple(m) for m in r], dtype=np.int64).reshape(-1, 2)
+            if a.size and (a.min() < -(1 << 31) or a.max() >= (1 << 31)):
+                raise ValueError(f"sequence {i}: an interval lies outside the 32-bit range")
+            flat.append(a.astype(np.int32))
+            off[i + 1] = len(a)
+    np.cumsum(off, out=off)
+    if off[-1] == 0:
+        return None
+    return off, np.ascontiguousarray(np.concatenate(flat), dtype=np.int32)
+
+
 class Batch:
     """Contigs packed and resident in HBM (``pga_batch``)."""
+
+    def set_masks(self, regions=None, mask_lowercase=False):
+        """Attach mask sources to the batch (``pga_batch_set_regions`` / ``pga_batch_set_mask_case``): ``regions`` as
+        :func:`pack_regions` takes them (``None`` detaches), ``mask_lowercase`` masks runs of lower-case letters.  Every later call
+        on the batch honours them; ``ValueError`` names the sequence and the interval that does not lie inside it."""
+        packed = pack_regions(regions, self.n)
+        L = self.ctx.L
+        if packed is None:
+            rc = L.pga_batch_set_regions(self.h, None, None)
+        else:
+            rc = L.pga_batch_set_regions(self.h, ctypes.c_void_p(packed[0].ctypes.data), ctypes.c_void_p(packed[1].ctypes.data))
+        if rc == PGA_OK:
+            rc = L.pga_batch_set_mask_case(self.h, int(bool(mask_lowercase)))
+        if rc != PGA_OK:
+            _raise(L, self.ctx.h, rc, "pga_batch_set_regions")
+        return self
 
     def __init__(self, ctx, seqs):
         self.ctx = ctx
@@ -572,22 +618,28 @@ def _find_coding_bases(self, batch, model_of_contig, closed=False, min_gene=90, 
     return cov[:batch.n], ng[:batch.n], sc[:batch.n]
 
 
-def _find_genes_batch(self, seqs, **kw):
-    """Upload + find + free: ``seqs`` is a list of ASCII ``bytes``/``str`` contigs."""
+def _find_genes_batch(self, seqs, regions=None, mask_lowercase=False, **kw):
+    """Upload + find + free: ``seqs`` is a list of ASCII ``bytes``/``str`` contigs.  ``regions`` (one entry per contig: ``None`` or
+    ``(begin, end)`` pairs) and ``mask_lowercase`` are more mask sources (:meth:`Batch.set_masks`); ``masks`` of the result is their
+    union with the runs of unknown bases of ``mask=True``."""
     b = Batch(self, seqs)
     try:
+        if regions is not None or mask_lowercase:
+            b.set_masks(regions, mask_lowercase)
         return _find_genes(self, b, **kw)
     finally:
         b.close()
 
 
 def _nodes_stage(self, seqs, stage, translation_table=11, closed=False, min_gene=90, min_edge_gene=60, max_overlap=60,
-                 is_meta=False, mask=False, min_mask=50):
+                 is_meta=False, mask=False, min_mask=50, regions=None, mask_lowercase=False):
     """Node arrays after ``Nodes.extract`` (stage 1), ``Nodes.score`` (2) or overlapping starts (3), one dict per contig.
 
     Stages 2 and 3 score with model 0 of the context (``set_models`` first)."""
     b = seqs if isinstance(seqs, Batch) else Batch(self, seqs)
     try:
+        if b is not seqs and (regions is not None or mask_lowercase):
+            b.set_masks(regions, mask_lowercase)
         p = Params(int(closed), min_gene, min_edge_gene, max_overlap, int(is_meta), 1, int(mask), min_mask)
         res = _P(Result)()
         rc = self.L.pga_nodes_stage(self.h, b.h, ctypes.byref(p), int(stage), int(translation_table), ctypes.byref(res))
@@ -601,10 +653,13 @@ def _nodes_stage(self, seqs, stage, translation_table=11, closed=False, min_gene
 
 
 def _train(self, seq, translation_table=11, start_weight=4.35, force_nonsd=False, closed=False, min_gene=90, min_edge_gene=60,
-           max_overlap=60, mask=False, min_mask=50, upto=0):
-    """``GeneFinder.train`` on one sequence: returns the 558 392-byte ``struct _training`` as ``bytes``."""
+           max_overlap=60, mask=False, min_mask=50, upto=0, regions=None, mask_lowercase=False):
+    """``GeneFinder.train`` on one sequence: returns the 558 392-byte ``struct _training`` as ``bytes``.  ``regions``: the masked
+    intervals of that sequence."""
     b = Batch(self, [seq])
     try:
+        if regions is not None or mask_lowercase:
+            b.set_masks(None if regions is None else [regions], mask_lowercase)
         p = Params(int(closed), min_gene, min_edge_gene, max_overlap, 0, 0, int(mask), min_mask)
         out = ctypes.create_string_buffer(TRAINING_SIZE)
         rc = self.L.pga_train(self.h, b.h, ctypes.byref(p), int(translation_table), float(start_weight), int(force_nonsd), int(upto), out)
@@ -624,7 +679,7 @@ def _per_genome(value, n, dtype, name):
 
 
 def _train_batch(self, seqs, translation_table=11, start_weight=4.35, force_nonsd=False, closed=False, min_gene=90, min_edge_gene=60,
-                 max_overlap=60, mask=False, min_mask=50, upto=0):
+                 max_overlap=60, mask=False, min_mask=50, upto=0, regions=None, mask_lowercase=False):
     """``GeneFinder.train`` on many genomes in one call (``pga_train_batch``): ``seqs[g]`` is genome g (contigs already joined),
     the three training options a scalar or one value per genome.  Returns one 558 392-byte ``struct _training`` per genome; raises
     naming the first genome that could not be trained."""
@@ -636,6 +691,8 @@ def _train_batch(self, seqs, translation_table=11, start_weight=4.35, force_nons
     fns = _per_genome(np.asarray(force_nonsd, dtype=bool).astype(np.int32), n, np.int32, "force_nonsd")
     b = Batch(self, list(seqs))
     try:
+        if regions is not None or mask_lowercase:
+            b.set_masks(regions, mask_lowercase)
         p = Params(int(closed), min_gene, min_edge_gene, max_overlap, 0, 0, int(mask), min_mask)
         out = np.zeros(n * TRAINING_SIZE, np.uint8)
         status = np.zeros(n, np.int32)

@@ -53,7 +53,41 @@ def argument_parser(prog="pyrodigal_amd"):
                    help="TrainingInfo dumps to use as the metagenomic bins of -p meta (this build ships none). The GFF header of a "
                         "contig without genes reports the sixth bin, as Prodigal does (the last one when fewer are given).")
     p.add_argument("--batch-bases", type=int, default=64 << 20, metavar="N", help="Bases per device call.")
+    p.add_argument("--mask-lowercase", action="store_true", default=False,
+                   help="Treat runs of lower-case letters (soft-masked sequence) as masked sequence; don't build genes across them.")
+    p.add_argument("--mask-regions", metavar="FILE",
+                   help="Don't build genes across the regions of this BED-like file: tab-separated seqid, start, end (0-based, "
+                        "half-open; seqid is the first word of the FASTA header); further columns, # lines and track lines are ignored.")
     return p
+
+
+def parse_mask_regions(lines, name="<regions>"):
+    """``{seqid: [(start, end), ...]}`` of a BED-like text (an iterable of lines): tab-separated ``seqid  start  end``, 0-based and
+    half-open; further columns, blank lines, ``#`` lines and ``track`` / ``browser`` lines are ignored.  A malformed line is a
+    ``ValueError`` that names it."""
+    regions = {}
+    for no, line in enumerate(lines, 1):
+        if isinstance(line, bytes):
+            line = line.decode("utf-8", "replace")
+        text = line.rstrip("\r\n")
+        if not text.strip() or text.startswith("#") or text.split(None, 1)[0] in ("track", "browser"):
+            continue
+        cols = text.split("\t")
+        try:
+            if len(cols) < 3 or not cols[0]:
+                raise ValueError
+            start, end = int(cols[1]), int(cols[2])
+        except ValueError:
+            raise ValueError("%s, line %d: expected seqid<TAB>start<TAB>end, found %r" % (name, no, text)) from None
+        if start < 0 or end <= start:
+            raise ValueError("%s, line %d: not a region (0 <= start < end): %r" % (name, no, text))
+        regions.setdefault(cols[0], []).append((start, end))
+    return regions
+
+
+def read_mask_regions(path):
+    with open(path, "r", encoding="utf-8", errors="replace") as fh:
+        return parse_mask_regions(fh, path)
 
 
 # A contig without genes wins no bin in meta mode; its GFF header reports bin 5, as Prodigal's does (ref: lib.pyx:3584-3592), or
@@ -90,6 +124,14 @@ def main(argv=None, stdout=None, stderr=None):
     if err:
         print("Error: " + err, file=stderr)
         return 1
+    regions = None
+    if args.mask_regions is not None:
+        try:
+            regions = read_mask_regions(args.mask_regions)
+        except (OSError, ValueError) as e:
+            print("Error: --mask-regions: %s" % e, file=stderr)
+            return 1
+    mask_kw = dict(regions_by_id=regions, mask_lowercase=args.mask_lowercase)
     with contextlib.ExitStack() as stack:
         path = args.i
         if path is None:                        # stdin: the reader needs a file it can sniff and map
@@ -117,16 +159,24 @@ def main(argv=None, stdout=None, stderr=None):
                 with open(args.t, "rb") as fh:
                     tinf = lib.TrainingInfo.load(fh)
             if tinf is None:
-                seqs = [s for _, _, s in _records(path)]
-                tinf = lib.GeneFinder(**find_kw).train(*seqs, force_nonsd=args.n, translation_table=args.g)
-                del seqs
+                records = [(rid, s) for rid, _, s in _records(path)]
+                seqs = [s for _, s in records]
+                train_regions = None            # the training honours the masks too: per contig, through the join
+                if regions:
+                    per = [regions.get(rid) for rid, _ in records]
+                    train_regions = per if len(per) > 1 else per[0]
+                finder = lib.GeneFinder(mask_lowercase=args.mask_lowercase, **find_kw)
+                tinf = finder.train(*seqs, force_nonsd=args.n, translation_table=args.g, regions=train_regions)
+                del seqs, records
                 if args.t is not None:
                     with open(args.t, "wb") as fh:
                         tinf.dump(fh)
             blobs, descriptions, unbinned = [tinf.raw], None, None
         scores = None if args.s is None else stack.enter_context(open(args.s, "wb"))
         from .pipeline import render_fasta
-        render_fasta(path, blobs, gff=out if args.f == "gff" else None, gbk=out if args.f == "gbk" else None, faa=faa, fna=fna,
-                     scores=scores, n_contexts=args.jobs, max_bases=args.batch_bases, meta=meta, descriptions=descriptions,
-                     faa_options={"include_stop": not args.no_stop_codon}, unbinned_model=unbinned, **find_kw)
+        stats = render_fasta(path, blobs, gff=out if args.f == "gff" else None, gbk=out if args.f == "gbk" else None, faa=faa, fna=fna,
+                             scores=scores, n_contexts=args.jobs, max_bases=args.batch_bases, meta=meta, descriptions=descriptions,
+                             faa_options={"include_stop": not args.no_stop_codon}, unbinned_model=unbinned, **mask_kw, **find_kw)
+        for rid in stats.get("regions_unmatched", ()):
+            print("Warning: --mask-regions: no sequence %r in the input" % rid, file=stderr)
     return 0

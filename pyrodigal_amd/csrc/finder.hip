@@ -966,6 +966,7 @@ struct ResultOwner {
     pga_gene* pin_genes = nullptr; size_t pin_cap = 0, pin_n = 0;
     std::vector<pga_nodes> nodes;
     std::vector<int32_t> mask_off, masks;
+    bool has_masks = false;            // a mask source was set: the lists are reported (empty ones too)
     std::vector<void*> blocks;
     ~ResultOwner() {
         for (void* b : blocks) free(b);
@@ -1125,6 +1126,11 @@ struct pga_batch {
     TileDesc* d_tiles;            // extraction tiles of every contig (behind the letters, in their allocation)
     int32_t* d_tile0;             // first tile of every contig, n + 1 entries (behind d_tiles)
     int32_t n_tiles;
+    // mask sources attached to the batch (pga_batch_set_regions / pga_batch_set_mask_case): every call on the batch honours them
+    int mask_case = 0;                // 1: runs of lower-case letters are masked like runs of unknown bases
+    std::vector<int32_t> reg_off;     // the caller's intervals: contig i owns regions[reg_off[i] .. reg_off[i + 1]); empty: none attached
+    std::vector<MaskRun> regions;     // (contig, begin, end) as given: any order, overlaps allowed
+    MaskRun* d_regions = nullptr;     // their device copy
 };
 
 // Tiles of a batch: every position of a contig of at least three bases lies in one tile.  Host vectors for one upload.
@@ -1378,7 +1384,48 @@ pga_batch_view pga_batch_peek(const pga_batch* b) { return pga_batch_view{b->ctx
 extern "C" void pga_batch_free(pga_batch* b) {
     if (!b) return;
     if (b->d_seq) { hipSetDevice(b->ctx->device); batch_give_dev(b->ctx, b->d_seq, b->d_seq_cap); }
+    if (b->d_regions) { hipSetDevice(b->ctx->device); hipFree(b->d_regions); }
     delete b;
+}
+
+// the intervals of a batch, already checked, go to the device (or leave it: none)
+static int batch_upload_regions(pga_ctx* c, pga_batch* b) {
+    HT(c, hipSetDevice(c->device));
+    if (b->d_regions) { HT(c, hipFree(b->d_regions)); b->d_regions = nullptr; }
+    if (b->regions.empty()) return PGA_OK;
+    HT(c, hipMalloc((void**)&b->d_regions, sizeof(MaskRun) * b->regions.size()));
+    HT(c, hipMemcpy(b->d_regions, b->regions.data(), sizeof(MaskRun) * b->regions.size(), hipMemcpyHostToDevice));
+    return PGA_OK;
+}
+
+extern "C" int pga_batch_set_regions(pga_batch* b, const int32_t* off, const int32_t* iv) {
+    if (!b) return PGA_EINVAL;
+    pga_ctx* c = b->ctx;
+    if ((off == nullptr) != (iv == nullptr)) { c->err = "pga_batch_set_regions: offsets and intervals go together"; return PGA_EINVAL; }
+    std::vector<int32_t> reg_off; std::vector<MaskRun> regions;
+    if (off) {
+        for (int i = 0; i < b->n; i++) {
+            if (off[i] < 0 || off[i + 1] < off[i]) { c->err = "pga_batch_set_regions: offsets must not decrease"; return PGA_EINVAL; }
+            for (int32_t k = off[i]; k < off[i + 1]; k++) {
+                const int32_t begin = iv[2 * (size_t)k], end = iv[2 * (size_t)k + 1];
+                if (!(0 <= begin && begin < end && end <= b->ct[i].len)) {          // 0 <= begin < end <= len
+                    c->err = "pga_batch_set_regions: sequence " + std::to_string(i) + ": interval [" + std::to_string(begin) + ", " + std::to_string(end) +
+                             ") is not a non-empty part of [0, " + std::to_string(b->ct[i].len) + ")";
+                    return PGA_EINVAL;
+                }
+                regions.push_back(MaskRun{i, begin, end, 0});
+            }
+        }
+        if (!regions.empty()) { reg_off.resize((size_t)b->n + 1); for (int i = 0; i <= b->n; i++) reg_off[i] = off[i] - off[0]; }
+    }
+    b->reg_off.swap(reg_off); b->regions.swap(regions);
+    return batch_upload_regions(c, b);
+}
+
+extern "C" int pga_batch_set_mask_case(pga_batch* b, int lower_case) {
+    if (!b) return PGA_EINVAL;
+    b->mask_case = lower_case != 0;
+    return PGA_OK;
 }
 
 extern "C" int pga_find_genes_batch(pga_ctx* c, int32_t n_contigs, const char* const* seqs, const int64_t* lens,
@@ -1402,10 +1449,20 @@ static int publish(ResultOwner* R, ResultOwner*& guarded, const pga_params& P, p
     R->pub.genes = R->pin_genes != nullptr ? R->pin_genes : R->genes.data();
     R->pub.n_genes = (int64_t)(R->pin_genes != nullptr ? R->pin_n : R->genes.size());
     R->pub.nodes = !R->nodes.empty() ? R->nodes.data() : nullptr;
-    R->pub.mask_off = P.mask ? R->mask_off.data() : nullptr;
-    R->pub.masks = P.mask ? R->masks.data() : nullptr;
+    R->pub.mask_off = R->has_masks ? R->mask_off.data() : nullptr;
+    R->pub.masks = R->has_masks ? R->masks.data() : nullptr;
     guarded = nullptr;
     *out = &R->pub;
+    return PGA_OK;
+}
+
+// the merged mask list of a call for pga_result.masks: its offsets have arrived with the stream's last synchronisation, the intervals
+// are fetched now that their number is known (the kernels that read them are already queued or done)
+static int fetch_mask_union(pga_ctx* c, ResultOwner* R, const int32_t* h_moff, const int2* d_iv, int n_contigs) {
+    R->mask_off.assign(h_moff, h_moff + n_contigs + 1);
+    const size_t n = (size_t)std::max(h_moff[n_contigs], 0);
+    R->masks.resize(2 * n);
+    if (n > 0) HT(c, hipMemcpy(R->masks.data(), d_iv, sizeof(int2) * n, hipMemcpyDeviceToHost));
     return PGA_OK;
 }
 
@@ -1432,7 +1489,9 @@ static int find_impl_cov(pga_ctx* c, const pga_batch* batch, const pga_params* p
     // meta mode over an empty bin collection is legal and finds nothing (ref: tests/test_gene_finder.py:316-324)
     if (c->n_models <= 0 && !meta_run && stage != PGA_STAGE_EXTRACT && stage != PGA_STAGE_SEQUENCE) { c->err = "pga_find_genes: no model loaded (call pga_set_models first)"; return PGA_EINVAL; }
     const pga_params P = *pp;
-    if (P.mask && P.min_mask < 0) { c->err = "pga_find_genes: min_mask must be positive"; return PGA_EINVAL; }   // ref: lib.pyx:5175-5176
+    // the caller's intervals and runs of lower-case letters (pga_batch_set_regions / _set_mask_case) join the runs of unknown bases
+    const bool mask_union = batch->mask_case != 0 || !batch->regions.empty();
+    if ((P.mask || batch->mask_case) && P.min_mask < 0) { c->err = "pga_find_genes: min_mask must be positive"; return PGA_EINVAL; }   // ref: lib.pyx:5175-5176
     if (!P.closed && P.min_edge_gene > 0 && P.min_edge_gene < 4) {
         // with open ends and min_edge_gene <= 3 the reference emits a start node AND the virtual edge stop node at the same
         // position and strand; the per-position node layout of this path holds one of them.  Nobody calls genes of one codon.
@@ -1472,6 +1531,7 @@ static int find_impl_cov(pga_ctx* c, const pga_batch* batch, const pga_params* p
     struct Guard { ResultOwner* r; ~Guard() { delete r; } } guard{R};
     R->contigs.assign(NC, pga_contig_result{-1, 0, 0, 0, 0, 0.0, 0.0});
     R->mask_off.assign(NC + 1, 0);
+    R->has_masks = P.mask || mask_union;
     memset(&R->pub, 0, sizeof R->pub);
     R->pub.n_contigs = NC;
 
@@ -1523,7 +1583,25 @@ static int find_impl_cov(pga_ctx* c, const pga_batch* batch, const pga_params* p
         pga_launch_digitize(d_seq, d_dig, total, d_ct, NC, d_cnt, d_cnt + NC, st);
         pga_launch_gc_prefix(d_dig, total, d_gc_bsum, d_gc_boff, d_p16, st);
         MaskList masks{nullptr, nullptr};
-        if (P.mask) {
+        int32_t* h_moff = nullptr; const int2* d_union_iv = nullptr;
+        if (mask_union) {
+            // Several sources: their union per contig is built on the device (pga_launch_mask_union) and the extraction is launched behind
+            // it without a word from the host.  The list comes back for pga_result.masks with the extraction's own read-back.
+            const int64_t per_source = total / std::max(1, P.min_mask) + NC + 1;       // qualifying runs of one kind
+            const int64_t most = std::min<int64_t>((P.mask ? per_source : 0) + (batch->mask_case ? per_source : 0) + (int64_t)batch->regions.size(),
+                                                   total / 2 + NC + 1);               // disjoint runs that do not touch
+            const int cap = (int)std::min<int64_t>(most, (int64_t)1 << 28);
+            DEVBUF(d_bits, uint32_t, "d_mask_bits", 2 * pga_mask_words(total) + 2);
+            DEVBUF(d_mcounts, int32_t, "d_mask_counts", 4 * (pga_mask_waves(total) + 1));
+            DEVBUF(d_moff, int32_t, "d_mask_off", NC + 2);
+            DEVBUF(d_miv, int2, "d_mask_iv", cap + 1);
+            PINBUF(h_moff_, int32_t, "h_mask_off", NC + 2);
+            pga_launch_mask_union(d_dig, d_seq, total, d_ct, NC, batch->d_tiles, batch->n_tiles, P.mask, batch->mask_case, P.min_mask, batch->d_regions,
+                                  (int)batch->regions.size(), d_bits, d_mcounts, d_moff, d_miv, cap, st);
+            HT(c, hipMemcpyAsync(h_moff_, d_moff, sizeof(int32_t) * (NC + 1), hipMemcpyDeviceToHost, st));
+            h_moff = h_moff_; d_union_iv = d_miv;
+            masks = MaskList{d_moff, d_miv};
+        } else if (P.mask) {
             // masked regions: found on the device, ordered on the host (a handful of intervals)
             const int cap = (int)std::min<int64_t>(total / std::max(1, P.min_mask) + NC + 1, (int64_t)1 << 28);
             DEVBUF(d_runs, MaskRun, "d_mask_runs", cap + 1);
@@ -1557,6 +1635,7 @@ static int find_impl_cov(pga_ctx* c, const pga_batch* batch, const pga_params* p
                 R->contigs[i].gc = ct[i].len > 0 ? (double)h_cnt[i] / (double)ct[i].len : 0.0;
                 R->contigs[i].n_unknown = h_cnt[NC + i];
             }
+            if (h_moff) { const int rc = fetch_mask_union(c, R, h_moff, d_union_iv, NC); if (rc) return rc; }
             return publish(R, guard.r, P, out);
         }
         // meta mode: a contig is extracted under a translation table only if a model with that table lies in its GC window
@@ -1598,6 +1677,7 @@ static int find_impl_cov(pga_ctx* c, const pga_batch* batch, const pga_params* p
             stage_full = true;
             if (!getenv("PGA_STAGE_SHIFT")) f->stage_full = true;       // (the test knob leaves the context as it was)
         }
+        if (h_moff) { const int rc = fetch_mask_union(c, R, h_moff, d_union_iv, NC); if (rc) return rc; }
 
         tm.mark("extract+sync");
         // ---- topology buffers; the nodes go to their places and get their GC content while the host plans the chains: neither kernel
@@ -2685,6 +2765,19 @@ extern "C" int pga_batch_replicate(pga_ctx* c, const pga_batch* src, int32_t n, 
         if (e == hipSuccess) e = batch_upload_tiles(b, b->d_seq + total + 16, tiles, tile0, st);
         if (e == hipSuccess) e = hipStreamSynchronize(st);
         if (e != hipSuccess) { batch_give_dev(c, b->d_seq, b->d_seq_cap); delete b; return pga_hip_try_(c, e, "replication of the batch"); }
+    }
+    // the mask sources travel with the contigs
+    b->mask_case = src->mask_case;
+    if (!src->regions.empty()) {
+        b->reg_off.assign((size_t)n + 1, 0);
+        for (int i = 0; i < n; i++) {
+            const int s = contig_of_entry[i];
+            for (int32_t k = src->reg_off[s]; k < src->reg_off[s + 1]; k++) b->regions.push_back(MaskRun{i, src->regions[k].begin, src->regions[k].end, 0});
+            b->reg_off[(size_t)i + 1] = (int32_t)b->regions.size();
+        }
+        if (b->regions.empty()) b->reg_off.clear();
+        const int rc = batch_upload_regions(c, b);
+        if (rc) { pga_batch_free(b); return rc; }
     }
     *out = b;
     return PGA_OK;

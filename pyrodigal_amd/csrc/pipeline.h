@@ -136,6 +136,15 @@ void pga_launch_group_enable(const ContigDesc* d_ct, int n_contigs, const int32_
 // runs of unknown bases of at least min_mask positions, unordered, at most `cap` of them; *d_count is reset first
 void pga_launch_find_masks(const uint8_t* d_dig, const ContigDesc* d_ct, int n_contigs, const TileDesc* d_tiles, int n_tiles, int min_mask,
                            MaskRun* d_runs, int32_t* d_count, int cap, hipStream_t st);
+// The union of the mask sources of a call, built on the device (DESIGN.md "Region masks"): runs of unknown bases (d_dig) and / or of
+// lower-case letters (d_seq) of at least min_mask positions, and the caller's intervals (d_regions, any order, overlaps allowed), come
+// out as MaskList{d_moff, d_miv}: per contig sorted, disjoint, touching intervals joined, at most `cap` in all.
+//   d_bits    2 * pga_mask_words(total) words (cleared here)      d_counts  4 * (pga_mask_waves(total) + 1) ints
+int64_t pga_mask_words(int64_t total);
+int64_t pga_mask_waves(int64_t total);
+void pga_launch_mask_union(const uint8_t* d_dig, const char* d_seq, int64_t total, const ContigDesc* d_ct, int n_contigs, const TileDesc* d_tiles,
+                           int n_tiles, int unknown_runs, int lower_case_runs, int min_mask, const MaskRun* d_regions, int n_regions,
+                           uint32_t* d_bits, int32_t* d_counts, int32_t* d_moff, int2* d_miv, int cap, hipStream_t st);
 int pga_extract_tile_size();
 void pga_launch_orf_gc(const ContigDesc* d_ct, int n_contigs, const uint8_t* d_dig, const int32_t* d_p16, const GroupArrays& ga,
                        int n_nodes_total, const int32_t* d_node_contig_base, hipStream_t st);

@@ -2912,46 +2912,69 @@ void pga_launch_digitize(const char* d_seq, uint8_t* d_dig, int64_t total, const
     hipLaunchKernelGGL(k_digitize, dim3(nblocks(total, DG_BLOCK)), dim3(256), 0, st, d_seq, d_dig, total, d_ct, n_contigs, d_gc, d_unk);
 }
 
-// Runs of unknown bases (ref: lib.pyx:699-713, Sequence._mask): the thread that sees the first N of a run walks to
-// its end, 8 bytes at a time, and records it when it is long enough.  Runs are rare and mostly short.
-__global__ void __launch_bounds__(256)
-k_find_masks(const uint8_t* __restrict__ dig, const ContigDesc* __restrict__ ct, const TileDesc* __restrict__ tiles, int n_tiles, int n_contigs,
-             int min_mask, MaskRun* __restrict__ runs, int32_t* __restrict__ count, int cap) {
+// Which bytes make a masked run, and whether eight of them at once all do.
+struct RunOfUnknown {            // digits (k_digitize)
+    static __device__ __forceinline__ bool is(const uint8_t b) { return b == NN; }
+    static __device__ __forceinline__ bool all8(const uint64_t w) { return w == 0x0606060606060606ull; }
+};
+struct RunOfLowerCase {          // the batch's letters as they were handed in
+    static __device__ __forceinline__ bool is(const uint8_t b) { return (unsigned)(b - 'a') < 26u; }
+    static __device__ __forceinline__ bool all8(const uint64_t w) {
+        const uint64_t H = 0x8080808080808080ull;
+        if (w & H) return false;                                    // then no byte sum below carries into its neighbour
+        return ((w + 0x1f1f1f1f1f1f1f1full) & H) == H               // every byte >= 'a' (0x61)
+            && ((w + 0x0505050505050505ull) & H) == 0;              // and <= 'z' (0x7a)
+    }
+};
+
+// Masked runs (ref: lib.pyx:699-713, Sequence._mask): the thread that sees the first byte of a run walks to its end, 8 bytes
+// at a time, and hands it to emit(contig, begin, end) when it is long enough.  Runs are rare and mostly short.  One workgroup
+// per extraction tile, and behind them a thread per contig for the sequences too short to have a tile.
+template <class Run, class Emit>
+__device__ __forceinline__ void find_runs(const uint8_t* __restrict__ src, const ContigDesc* __restrict__ ct, const TileDesc* __restrict__ tiles,
+                                          const int n_tiles, const int n_contigs, const int min_mask, Emit emit) {
     if ((int)blockIdx.x >= n_tiles) {
         // sequences of one or two bases have no extraction tile: one thread each
         const int c = ((int)blockIdx.x - n_tiles) * blockDim.x + threadIdx.x;
         if (c >= n_contigs) return;
         const ContigDesc cd = ct[c];
         if (cd.len < 1 || cd.len > 2) return;
-        const uint8_t* __restrict__ d = dig + cd.base;
+        const uint8_t* __restrict__ d = src + cd.base;
         for (int i = 0; i < cd.len; i++) {
-            if (d[i] != NN || (i > 0 && d[i - 1] == NN)) continue;
+            if (!Run::is(d[i]) || (i > 0 && Run::is(d[i - 1]))) continue;
             int e = i + 1;
-            while (e < cd.len && d[e] == NN) e++;
-            if (e - i >= min_mask || e == cd.len) { const int k = atomicAdd(count, 1); if (k < cap) runs[k] = MaskRun{c, i, e, 0}; }
+            while (e < cd.len && Run::is(d[e])) e++;
+            if (e - i >= min_mask || e == cd.len) emit(c, i, e);
         }
         return;
     }
     const TileDesc td = tiles[blockIdx.x];
     const ContigDesc cd = ct[td.contig];
     const int L = cd.len;
-    const uint8_t* __restrict__ d = dig + cd.base;
+    const uint8_t* __restrict__ d = src + cd.base;
     const int i0 = td.start + threadIdx.x * EX_PER_THREAD;
     for (int q = 0; q < EX_PER_THREAD; q++) {
         const int i = i0 + q;
-        if (i >= L || d[i] != NN || (i > 0 && d[i - 1] == NN)) continue;
+        if (i >= L || !Run::is(d[i]) || (i > 0 && Run::is(d[i - 1]))) continue;
         int e = i + 1;
         while (e + 8 <= L) {
             uint64_t w; memcpy(&w, d + e, 8);
-            if (w != 0x0606060606060606ull) break;
+            if (!Run::all8(w)) break;
             e += 8;
         }
-        while (e < L && d[e] == NN) e++;
-        if (e - i >= min_mask || e == L) {          // a run that reaches the end of the sequence is masked whatever its length (ref: lib.pyx:711-712)
-            const int k = atomicAdd(count, 1);
-            if (k < cap) runs[k] = MaskRun{td.contig, i, e, 0};
-        }
+        while (e < L && Run::is(d[e])) e++;
+        if (e - i >= min_mask || e == L) emit(td.contig, i, e);     // a run that reaches the end of the sequence is masked whatever its length (ref: lib.pyx:711-712)
     }
+}
+
+// Runs of unknown bases as a list in the order the atomics hand out (the caller sorts it).
+__global__ void __launch_bounds__(256)
+k_find_masks(const uint8_t* __restrict__ dig, const ContigDesc* __restrict__ ct, const TileDesc* __restrict__ tiles, int n_tiles, int n_contigs,
+             int min_mask, MaskRun* __restrict__ runs, int32_t* __restrict__ count, int cap) {
+    find_runs<RunOfUnknown>(dig, ct, tiles, n_tiles, n_contigs, min_mask, [&](const int c, const int b, const int e) {
+        const int k = atomicAdd(count, 1);
+        if (k < cap) runs[k] = MaskRun{c, b, e, 0};
+    });
 }
 
 void pga_launch_find_masks(const uint8_t* d_dig, const ContigDesc* d_ct, int n_contigs, const TileDesc* d_tiles, int n_tiles, int min_mask,
@@ -2959,6 +2982,141 @@ void pga_launch_find_masks(const uint8_t* d_dig, const ContigDesc* d_ct, int n_c
     (void)hipMemsetAsync(d_count, 0, sizeof(int32_t), st);
     hipLaunchKernelGGL(k_find_masks, dim3(n_tiles + (n_contigs + 255) / 256), dim3(256), 0, st, d_dig, d_ct, d_tiles, n_tiles, n_contigs, min_mask,
                        d_runs, d_count, cap);
+}
+
+// ---- The union of the mask sources (DESIGN.md "Region masks").  Every source paints its intervals into one bit per base of the
+// batch (bit g & 31 of word g >> 5, g = the base's place in the batch); the maximal runs of set bits inside each contig ARE the
+// sorted, disjoint, joined list the extraction's binary search needs, and they come out in that order without a sort: count the
+// run starts and run ends of every 2048 bases, scan the counts, write each begin and each end to its place.  A second bitmap
+// marks the first base of every contig, so that a run ends where its contig does.
+constexpr int MK_WAVE_BITS = 64 * 32;      // bases per wavefront of the counting and placing kernels: a word per lane
+
+__device__ __forceinline__ void paint_words(uint32_t* __restrict__ bits, const int64_t g0, const int64_t g1 /* > g0 */, const int first, const int step) {
+    const int64_t w0 = g0 >> 5, w1 = (g1 - 1) >> 5;
+    for (int64_t w = w0 + first; w <= w1; w += step) {
+        uint32_t m = 0xffffffffu;
+        if (w == w0) m &= 0xffffffffu << (int)(g0 & 31);
+        if (w == w1) m &= 0xffffffffu >> (31 - (int)((g1 - 1) & 31));
+        atomicOr(bits + w, m);
+    }
+}
+
+template <class Run>
+__global__ void __launch_bounds__(256)
+k_mask_paint_runs(const uint8_t* __restrict__ src, const ContigDesc* __restrict__ ct, const TileDesc* __restrict__ tiles, int n_tiles, int n_contigs,
+                  int min_mask, uint32_t* __restrict__ bits) {
+    find_runs<Run>(src, ct, tiles, n_tiles, n_contigs, min_mask, [&](const int c, const int b, const int e) {
+        const int64_t base = ct[c].base;
+        paint_words(bits, base + b, base + e, 0, 1);
+    });
+}
+
+// The caller's intervals, a wavefront each (lanes take the words of a long one in turn), and behind them the contig marks.
+__global__ void __launch_bounds__(256)
+k_mask_paint_regions(const MaskRun* __restrict__ regions, int n_regions, const ContigDesc* __restrict__ ct, int n_contigs,
+                     uint32_t* __restrict__ bits, uint32_t* __restrict__ cbits) {
+    const int region_blocks = (n_regions + 3) / 4;
+    if ((int)blockIdx.x >= region_blocks) {
+        const int c = ((int)blockIdx.x - region_blocks) * 256 + threadIdx.x;
+        if (c < n_contigs) { const int64_t g = ct[c].base; atomicOr(cbits + (g >> 5), 1u << (int)(g & 31)); }
+        return;
+    }
+    const int k = (int)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (k >= n_regions) return;
+    const MaskRun r = regions[k];
+    const ContigDesc cd = ct[r.contig];
+    const int b = max(r.begin, 0), e = min(r.end, cd.len);          // (checked on the host when they were attached)
+    if (b < e) paint_words(bits, cd.base + b, cd.base + e, threadIdx.x & 63, 64);
+}
+
+// bit i of S: a run begins at base 32 w + i; of E: a run's last base is there
+__device__ __forceinline__ void mask_edges(const uint32_t* __restrict__ bits, const uint32_t* __restrict__ cbits, const int64_t w, const int64_t nw,
+                                           uint32_t& S, uint32_t& E) {
+    S = 0; E = 0;
+    if (w >= nw) return;
+    const uint32_t b = bits[w];
+    if (!b) return;
+    const uint32_t before = w > 0 ? bits[w - 1] >> 31 : 0u, after = w + 1 < nw ? bits[w + 1] & 1u : 0u;
+    const uint32_t c = cbits[w], c_after = w + 1 < nw ? cbits[w + 1] & 1u : 0u;
+    S = b & (~((b << 1) | before) | c);
+    E = b & (~((b >> 1) | (after << 31)) | ((c >> 1) | (c_after << 31)));
+}
+
+__global__ void __launch_bounds__(256)
+k_mask_count(const uint32_t* __restrict__ bits, const uint32_t* __restrict__ cbits, int64_t nw, int32_t* __restrict__ cnt_s, int32_t* __restrict__ cnt_e) {
+    const int64_t w = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    uint32_t S, E;
+    mask_edges(bits, cbits, w, nw, S, E);
+    int ns = __popc(S), ne = __popc(E);
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) { ns += __shfl_xor(ns, m, 64); ne += __shfl_xor(ne, m, 64); }
+    if ((threadIdx.x & 63) == 0 && w < nw) { cnt_s[w >> 6] = ns; cnt_e[w >> 6] = ne; }
+}
+
+// off_s / off_e: the scanned counts.  The k-th run start of the batch and its k-th run end belong to one run (runs cannot nest), so
+// begins and ends are placed independently.  Behind the word blocks, a thread per contig (and one for the end of the batch) counts the
+// run starts before its first base: the contig's first entry of the list.
+__global__ void __launch_bounds__(256)
+k_mask_place(const uint32_t* __restrict__ bits, const uint32_t* __restrict__ cbits, int64_t nw, int word_blocks, const int32_t* __restrict__ off_s,
+             const int32_t* __restrict__ off_e, const ContigDesc* __restrict__ ct, int n_contigs, int32_t* __restrict__ moff, int2* __restrict__ iv, int cap) {
+    if ((int)blockIdx.x >= word_blocks) {
+        const int c = ((int)blockIdx.x - word_blocks) * 256 + threadIdx.x;
+        if (c > n_contigs) return;
+        const int64_t g = ct[c].base, wg = g >> 5;
+        int n = off_s[g / MK_WAVE_BITS];
+        uint32_t S, E;
+        for (int64_t w = (g / MK_WAVE_BITS) * 64; w < wg; w++) { mask_edges(bits, cbits, w, nw, S, E); n += __popc(S); }
+        mask_edges(bits, cbits, wg, nw, S, E);
+        n += __popc(S & ((1u << (int)(g & 31)) - 1u));
+        moff[c] = min(n, cap);
+        return;
+    }
+    const int64_t w = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const int lane = threadIdx.x & 63;
+    uint32_t S, E;
+    mask_edges(bits, cbits, w, nw, S, E);
+    const int ns = __popc(S), ne = __popc(E);
+    int is = ns, ie = ne;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const int x = __shfl_up(is, o, 64), y = __shfl_up(ie, o, 64);
+        if (lane >= o) { is += x; ie += y; }
+    }
+    if (!(S | E)) return;
+    int ks = off_s[w >> 6] + is - ns, ke = off_e[w >> 6] + ie - ne;
+    while (S) {
+        const int64_t g = w * 32 + __builtin_ctz(S);
+        S &= S - 1u;
+        if (ks < cap) iv[ks].x = (int)(g - ct[find_contig(ct, n_contigs, g)].base);
+        ks++;
+    }
+    while (E) {
+        const int64_t g = w * 32 + __builtin_ctz(E);
+        E &= E - 1u;
+        if (ke < cap) iv[ke].y = (int)(g + 1 - ct[find_contig(ct, n_contigs, g)].base);
+        ke++;
+    }
+}
+
+int64_t pga_mask_words(int64_t total) { return (total + 32) / 32; }           // bit `total` (the end of the batch) included
+int64_t pga_mask_waves(int64_t total) { return (pga_mask_words(total) + 63) / 64; }
+
+void pga_launch_mask_union(const uint8_t* d_dig, const char* d_seq, int64_t total, const ContigDesc* d_ct, int n_contigs, const TileDesc* d_tiles,
+                           int n_tiles, int unknown_runs, int lower_case_runs, int min_mask, const MaskRun* d_regions, int n_regions,
+                           uint32_t* d_bits, int32_t* d_counts, int32_t* d_moff, int2* d_miv, int cap, hipStream_t st) {
+    const int64_t nw = pga_mask_words(total), nwv = pga_mask_waves(total);
+    uint32_t* const d_cbits = d_bits + nw;
+    int32_t* const cnt_s = d_counts; int32_t* const cnt_e = cnt_s + (nwv + 1); int32_t* const off_s = cnt_e + (nwv + 1); int32_t* const off_e = off_s + (nwv + 1);
+    (void)hipMemsetAsync(d_bits, 0, sizeof(uint32_t) * 2 * (size_t)nw, st);
+    const dim3 run_grid(n_tiles + (n_contigs + 255) / 256);
+    if (unknown_runs) hipLaunchKernelGGL(k_mask_paint_runs<RunOfUnknown>, run_grid, dim3(256), 0, st, d_dig, d_ct, d_tiles, n_tiles, n_contigs, min_mask, d_bits);
+    if (lower_case_runs) hipLaunchKernelGGL(k_mask_paint_runs<RunOfLowerCase>, run_grid, dim3(256), 0, st, (const uint8_t*)d_seq, d_ct, d_tiles, n_tiles, n_contigs, min_mask, d_bits);
+    hipLaunchKernelGGL(k_mask_paint_regions, dim3((n_regions + 3) / 4 + (n_contigs + 255) / 256), dim3(256), 0, st, d_regions, n_regions, d_ct, n_contigs, d_bits, d_cbits);
+    const int word_blocks = (int)((nw + 255) / 256);
+    hipLaunchKernelGGL(k_mask_count, dim3(word_blocks), dim3(256), 0, st, (const uint32_t*)d_bits, (const uint32_t*)d_cbits, nw, cnt_s, cnt_e);
+    hipLaunchKernelGGL(k_scan_counts, dim3(1), dim3(1024), 0, st, (const int32_t*)cnt_s, (int)nwv, off_s, (const int32_t*)cnt_e, off_e);
+    hipLaunchKernelGGL(k_mask_place, dim3(word_blocks + (n_contigs + 1 + 255) / 256), dim3(256), 0, st, (const uint32_t*)d_bits, (const uint32_t*)d_cbits, nw, word_blocks,
+                       (const int32_t*)off_s, (const int32_t*)off_e, d_ct, n_contigs, d_moff, d_miv, cap);
 }
 
 void pga_launch_gc_prefix(const uint8_t* d_dig, int64_t total, int32_t* d_block_sum, int32_t* d_block_off, int32_t* d_p16, hipStream_t st) {

@@ -117,6 +117,8 @@ cdef extern from "pyrodigal_amd.h" nogil:
                             int unknown_residue, int include_stop, int strict, const int64_t* offsets, char* out)
     int pga_batch_create(pga_ctx*, int32_t n, const char* const* seqs, const int64_t* lens, pga_batch** out)
     void pga_batch_free(pga_batch*)
+    int pga_batch_set_regions(pga_batch*, const int32_t* off, const int32_t* iv)
+    int pga_batch_set_mask_case(pga_batch*, int lower_case)
     int pga_batch_replicate(pga_ctx*, const pga_batch* src, int32_t n, const int32_t* contig_of_entry, pga_batch** out)
     int pga_find_coding_bases(pga_ctx*, const pga_batch*, const pga_params*, const int32_t* model_of_contig, int64_t* coding_bases,
                               int32_t* n_genes, double* score)
@@ -584,18 +586,153 @@ cdef class Mask:
     def __eq__(self, other):
         return isinstance(other, Mask) and (self.begin, self.end) == ((<Mask> other).begin, (<Mask> other).end)
 
+    cpdef bint intersects(self, int begin, int end):
+        """Whether the mask intersects the sequence coordinates `[begin, end)` (ref: lib.pyx:344-365)."""
+        return self.begin < end and begin < self.end
+
+
+cdef tuple _interval_of(object m):
+    """`(begin, end)` of a `Mask` or of a pair."""
+    if isinstance(m, Mask):
+        return ((<Mask> m).begin, (<Mask> m).end)
+    b, e = m
+    return (int(b), int(e))
+
+
+cdef class Masks:
+    """A list of masked regions `[begin, end)` of a sequence (ref: lib.pyx:368-560): what `Sequence.masks` returns, and the type
+    regions are handed over in (`Sequence(..., regions=)`, `GeneFinder.find_genes(..., regions=)`).  Built from any iterable of
+    `Mask` objects or `(begin, end)` pairs; equal to a `Masks`, list or tuple of the same intervals in the same order."""
+    cdef list _items            # (begin, end) tuples
+
+    def __cinit__(self):
+        self._items = []
+
+    def __init__(self, object iterable=()):
+        self._items = [_interval_of(m) for m in iterable]
+
+    def __len__(self):
+        return len(self._items)
+
+    def __getitem__(self, index):
+        if isinstance(index, slice):
+            return Masks(self._items[index])
+        cdef ssize_t i = index
+        if i < 0:
+            i += len(self._items)
+        if i < 0 or i >= len(self._items):
+            raise IndexError("masks index out of range")
+        return Mask(self._items[i][0], self._items[i][1])
+
+    def __iter__(self):
+        for b, e in self._items:
+            yield Mask(b, e)
+
+    def __bool__(self):
+        return len(self._items) > 0
+
+    def __eq__(self, other):
+        if isinstance(other, Masks):
+            return self._items == (<Masks> other)._items
+        if isinstance(other, (list, tuple)):
+            try:
+                return self._items == [_interval_of(m) for m in other]
+            except (TypeError, ValueError):
+                return False
+        return NotImplemented
+
+    def __repr__(self):
+        return "pyrodigal_amd.lib.Masks(%r)" % (self._items,)
+
+    def __copy__(self):
+        return self.copy()
+
+    def __reduce__(self):
+        return Masks, (list(self._items),)
+
+    cpdef Masks copy(self):
+        """A copy of the list."""
+        return Masks(self._items)
+
+    def clear(self):
+        """Remove every mask."""
+        self._items = []
+
+    def intersects(self, int begin, int end):
+        """Whether any mask of the list intersects `[begin, end)`."""
+        for b, e in self._items:
+            if b < end and begin < e:
+                return True
+        return False
+
+
+cdef object _check_regions(object regions, ssize_t length, str which):
+    """The caller's regions of one sequence as an int32 array [k][2], or None for none: every interval must satisfy
+    0 <= begin < end <= length (`which` names the sequence in the message)."""
+    if regions is None:
+        return None
+    cdef list iv = [_interval_of(m) for m in regions]
+    if not iv:
+        return None
+    for b, e in iv:
+        if not (0 <= b < e <= length):
+            raise ValueError("%sregion [%d, %d) is not a non-empty part of the sequence [0, %d)" % (which, b, e, length))
+    return np.array(iv, dtype=np.int32).reshape(-1, 2)
+
+
+cdef int _attach_masks(pga_ctx* ctx, pga_batch* batch, list seqs, bint lower_case) except -1:
+    """The regions the sequences carry and the lower-case rule go to the resident batch (nothing to do: no call at all)."""
+    cdef Py_ssize_t n = len(seqs), i
+    cdef bint any_regions = False
+    cdef size_t p_off, p_iv
+    cdef int rc
+    for i in range(n):
+        if (<Sequence> seqs[i])._regions is not None:
+            any_regions = True
+            break
+    if any_regions:
+        off = np.zeros(n + 1, np.int32)
+        parts = []
+        for i in range(n):
+            r = (<Sequence> seqs[i])._regions
+            off[i + 1] = off[i] + (0 if r is None else len(r))
+            if r is not None:
+                parts.append(r)
+        iv = np.ascontiguousarray(np.concatenate(parts), dtype=np.int32)
+        p_off = off.ctypes.data; p_iv = iv.ctypes.data
+        rc = pga_batch_set_regions(batch, <const int32_t*> p_off, <const int32_t*> p_iv)
+        if rc != PGA_OK:
+            _raise_for(ctx, rc, "pga_batch_set_regions")
+    if lower_case:
+        rc = pga_batch_set_mask_case(batch, 1)
+        if rc != PGA_OK:
+            _raise_for(ctx, rc, "pga_batch_set_mask_case")
+    return 0
+
+
+def _sequence_from_state(data, mask, mask_size, regions, mask_lowercase):
+    return Sequence(data, mask, mask_size, regions=regions, mask_lowercase=mask_lowercase)
+
 
 cdef class Sequence:
     """The input as ASCII bytes.  Digitising, GC content, the unknown-base count and the masked regions are
-    computed on the device (ref: lib.pyx:664-713), on first use."""
+    computed on the device (ref: lib.pyx:664-713), on first use.
+
+    Masked regions come from up to three sources, and `masks` is their union (sorted, disjoint, touching intervals joined): runs
+    of unknown bases of at least `mask_size` (`mask=True`), runs of lower-case letters by the same rule (`mask_lowercase=True`),
+    and `regions`, the caller's own `[begin, end)` intervals (0-based; any order, overlaps allowed, no minimum length).  A region
+    takes part in the mask test exactly as a masked run of `N` at the same coordinates would; its bases keep their identity for
+    everything else."""
     cdef readonly bytes data
     cdef readonly bint mask
     cdef readonly size_t mask_size
+    cdef readonly bint mask_lowercase
+    cdef object _regions        # int32 [k][2] (k > 0) or None
     cdef double _gc
     cdef ssize_t _unknown
     cdef list _masks
 
-    def __init__(self, object sequence, bint mask=False, size_t mask_size=50):
+    def __init__(self, object sequence, bint mask=False, size_t mask_size=50, *, object regions=None, bint mask_lowercase=False):
         if isinstance(sequence, Sequence):
             self.data = (<Sequence> sequence).data
         elif type(sequence) is bytes:
@@ -606,6 +743,11 @@ cdef class Sequence:
             self.data = bytes(memoryview(sequence))
         self.mask = mask
         self.mask_size = mask_size
+        self.mask_lowercase = mask_lowercase
+        if regions is None and isinstance(sequence, Sequence):
+            self._regions = (<Sequence> sequence)._regions
+        else:
+            self._regions = _check_regions(regions, len(self.data), "")
         self._gc = -1.0
         self._unknown = -1
         self._masks = None
@@ -635,6 +777,7 @@ cdef class Sequence:
             if rc != PGA_OK:
                 _raise_for(S.ctx, rc, "pga_batch_create")
             try:
+                _attach_masks(S.ctx, batch, [self], self.mask_lowercase)
                 with nogil:
                     rc = pga_nodes_stage(S.ctx, batch, &p, PGA_STAGE_SEQUENCE, 11, &res)
                 if rc != PGA_OK:
@@ -674,12 +817,20 @@ cdef class Sequence:
 
     @property
     def masks(self):
-        """The masked regions, empty unless `mask=True` (ref: lib.pyx:616-620)."""
+        """The masked regions: the union of every source, empty when none is set (ref: lib.pyx:616-620)."""
         self._build()
-        return list(self._masks)
+        return Masks(self._masks)
+
+    @property
+    def regions(self):
+        """The caller's own regions as they were given (`Masks`), or None."""
+        return None if self._regions is None else Masks(self._regions.tolist())
 
     def __reduce__(self):
-        return Sequence, (self.data, self.mask, self.mask_size)
+        if self._regions is None and not self.mask_lowercase:
+            return Sequence, (self.data, self.mask, self.mask_size)
+        return _sequence_from_state, (self.data, self.mask, self.mask_size,
+                                      None if self._regions is None else [tuple(x) for x in self._regions.tolist()], self.mask_lowercase)
 
 
 cdef class Node:
@@ -763,6 +914,7 @@ cdef class Nodes:
             if rc != PGA_OK:
                 _raise_for(S.ctx, rc, "pga_batch_create")
             try:
+                _attach_masks(S.ctx, batch, [seq], seq.mask_lowercase)
                 with nogil:
                     rc = pga_nodes_stage(S.ctx, batch, &p, stage, tt, &res)
                 if rc != PGA_OK:
@@ -1383,6 +1535,7 @@ cdef class GeneFinder:
     cdef readonly bint closed
     cdef readonly bint mask
     cdef readonly int min_mask
+    cdef readonly bint mask_lowercase
     cdef readonly int min_gene
     cdef readonly int min_edge_gene
     cdef readonly int max_overlap
@@ -1407,7 +1560,7 @@ cdef class GeneFinder:
     def __init__(self, TrainingInfo training_info=None, *, bint meta=False, MetagenomicBins metagenomic_bins=None,
                  bint closed=False, bint mask=False, int min_mask=50, int min_gene=90, int min_edge_gene=60,
                  int max_overlap=60, str backend="detect", int device=0, bint keep_nodes=True, int contexts=2,
-                 int64_t coalesce_bases=64 << 20):
+                 int64_t coalesce_bases=64 << 20, bint mask_lowercase=False):
         # argument validation as in the reference (lib.pyx:5169-5181)
         if meta and training_info is not None:
             raise ValueError("cannot use a training info in meta mode.")
@@ -1431,6 +1584,7 @@ cdef class GeneFinder:
         self.closed = closed
         self.mask = mask
         self.min_mask = min_mask
+        self.mask_lowercase = mask_lowercase
         self.min_gene = min_gene
         self.min_edge_gene = min_edge_gene
         self.max_overlap = max_overlap
@@ -1449,11 +1603,14 @@ cdef class GeneFinder:
         self.stats = {"device_calls": 0, "sequences": 0, "max_calls_per_device_call": 0}
 
     def __reduce__(self):           # ref: lib.pyx:5219-5234
-        return _gene_finder_from_state, (self.training_info, dict(
+        cdef dict kw = dict(
             meta=self.meta, metagenomic_bins=self.metagenomic_bins if self.meta else None, closed=self.closed, mask=self.mask,
             min_mask=self.min_mask, min_gene=self.min_gene, min_edge_gene=self.min_edge_gene, max_overlap=self.max_overlap,
             backend=self.backend, device=self.device, keep_nodes=self.keep_nodes, contexts=self.contexts,
-            coalesce_bases=self.coalesce_bases))
+            coalesce_bases=self.coalesce_bases)
+        if self.mask_lowercase:
+            kw["mask_lowercase"] = True
+        return _gene_finder_from_state, (self.training_info, kw)
 
     def __repr__(self):
         parts = []
@@ -1463,6 +1620,8 @@ cdef class GeneFinder:
             parts.append("meta=True")
         if self.closed:
             parts.append("closed=True")
+        if self.mask_lowercase:
+            parts.append("mask_lowercase=True")
         return "pyrodigal_amd.lib.GeneFinder(%s)" % ", ".join(parts)
 
     cdef int _ensure_models(self, _FinderSlot slot) except -1:
@@ -1500,9 +1659,14 @@ cdef class GeneFinder:
         slot.models_sig = sig
         return 0
 
-    def find_genes(self, object sequence):
-        """Find all the genes in the input DNA sequence (ref: lib.pyx:5400-5469)."""
-        return self.find_genes_batch([sequence])[0]
+    def find_genes(self, object sequence, object regions=None):
+        """Find all the genes in the input DNA sequence (ref: lib.pyx:5400-5469).
+
+        `regions`: `[begin, end)` intervals of the sequence (0-based; a `Masks`, or any iterable of `Mask` objects or pairs) that no
+        gene may run across, exactly as if they were masked runs of `N` -- while the bases keep their identity for the GC content,
+        the model choice, every score and the printed sequence.  They join the runs of unknown bases (`mask=True`), the runs of
+        lower-case letters (`mask_lowercase=True`) and the regions a `Sequence` already carries; `genes.sequence.masks` is the union."""
+        return self.find_genes_batch([sequence], regions=None if regions is None else [regions])[0]
 
     cdef _FinderSlot _free_slot(self):
         # a context that already exists first: a lone caller never makes a second one
@@ -1531,7 +1695,7 @@ cdef class GeneFinder:
         del self._pending[:k]
         return take
 
-    def find_genes_batch(self, object sequences, *, bint translate=False, object training_infos=None):
+    def find_genes_batch(self, object sequences, *, bint translate=False, object training_infos=None, object regions=None):
         """`find_genes` for many sequences in one device pass; returns one `Genes` per input, in order.
 
         `translate=True` also translates every gene on the device while the batch is resident (one thread per codon, the
@@ -1540,14 +1704,16 @@ cdef class GeneFinder:
 
         `training_infos` (single mode only): one `TrainingInfo` per sequence, sequence i is called with `training_infos[i]`
         -- the result is that of `GeneFinder(training_infos[i], <same options>).find_genes(sequences[i])`, for many genomes
-        under their own models in a few device calls.  The finder's own `training_info` is not used (nor needed) then."""
+        under their own models in a few device calls.  The finder's own `training_info` is not used (nor needed) then.
+
+        `regions`: one entry per sequence, `None` or the regions of that sequence as `find_genes` takes them."""
         if training_infos is not None:
-            return self._find_genes_models(sequences, translate, training_infos)
+            return self._find_genes_models(sequences, translate, training_infos, regions)
         if not self.meta and self.training_info is None:
             raise RuntimeError("cannot find genes without having trained in single mode")
         # the reference always re-wraps with the finder's masking rule (ref: lib.pyx:5433-5438); a Sequence that already
         # follows it is used as it is
-        cdef list seqs = self._wrap_sequences(sequences)
+        cdef list seqs = self._wrap_sequences(sequences, regions)
         cdef int64_t bases = 0
         for s in seqs:
             bases += len((<Sequence> s).data)
@@ -1620,27 +1786,49 @@ cdef class GeneFinder:
             raise req.error
         return req.out
 
-    cdef list _wrap_sequences(self, object sequences):
+    cdef list _wrap_sequences(self, object sequences, object regions=None):
         """The finder's masking rule on every sequence (the reference always re-wraps, lib.pyx:5433-5438): a Sequence that already
-        follows it is used as it is."""
+        follows it is used as it is.  The regions a Sequence carries stay with it; `regions` (one entry per sequence or None) are
+        the call's own and join them."""
         cdef list seqs = []
-        for s in sequences:
+        cdef list given = list(sequences)
+        cdef list extra = None
+        cdef Py_ssize_t i
+        cdef Sequence q
+        if regions is not None:
+            extra = list(regions)
+            if len(extra) != len(given):
+                raise ValueError("`regions` has %d entries for %d sequences" % (len(extra), len(given)))
+        for i in range(len(given)):
+            s = given[i]
+            r = extra[i] if extra is not None else None
+            which = "sequence %d: " % i if len(given) > 1 else ""
             if isinstance(s, Sequence):
-                if (<Sequence> s).mask != self.mask or (self.mask and <int> (<Sequence> s).mask_size != self.min_mask):
-                    s = Sequence((<Sequence> s).data, mask=self.mask, mask_size=self.min_mask)
+                q = <Sequence> s
+                if r is not None:
+                    r = _check_regions(r, len(q.data), which)
+                    if r is not None and q._regions is not None:
+                        r = np.concatenate([q._regions, r])
+                rules = self.mask or self.mask_lowercase
+                if (q.mask != self.mask or q.mask_lowercase != self.mask_lowercase or (rules and <int> q.mask_size != self.min_mask)
+                        or r is not None):
+                    s = Sequence(q.data, mask=self.mask, mask_size=self.min_mask, mask_lowercase=self.mask_lowercase)
+                    (<Sequence> s)._regions = r if r is not None else q._regions
             else:
-                s = Sequence(s, mask=self.mask, mask_size=self.min_mask)
+                s = Sequence(s, mask=self.mask, mask_size=self.min_mask, mask_lowercase=self.mask_lowercase)
+                if r is not None:
+                    (<Sequence> s)._regions = _check_regions(r, len((<Sequence> s).data), which)
             seqs.append(s)
         return seqs
 
-    def _find_genes_models(self, object sequences, bint translate, object training_infos):
+    def _find_genes_models(self, object sequences, bint translate, object training_infos, object regions=None):
         """`find_genes_batch(..., training_infos=...)`: single mode with a model per sequence (`pga_find_genes_models`).  The
         sequences go in device calls of at most `coalesce_bases` bases and four translation tables (what one context's model set
         holds); identical `TrainingInfo` objects are loaded once per call."""
         if self.meta:
             raise ValueError("`training_infos` is a single-mode option: this finder is in meta mode")
         cdef list tinfs = list(training_infos)
-        cdef list seqs = self._wrap_sequences(sequences)
+        cdef list seqs = self._wrap_sequences(sequences, regions)
         if len(tinfs) != len(seqs):
             raise ValueError("`training_infos` has %d entries for %d sequences" % (len(tinfs), len(seqs)))
         for i, t in enumerate(tinfs):
@@ -1758,6 +1946,7 @@ cdef class GeneFinder:
         cdef list loaded = None
         cdef object moc = None
         cdef size_t p_moc = 0
+        cdef bint masked = self.mask_lowercase       # a mask source beyond params.mask: the call goes through a resident batch
         if ptrs == NULL or lens == NULL:
             free(ptrs); free(lens)
             raise MemoryError()
@@ -1771,6 +1960,8 @@ cdef class GeneFinder:
             for i in range(n):
                 ptrs[i] = PyBytes_AS_STRING((<Sequence> seqs[i]).data)
                 lens[i] = len((<Sequence> seqs[i]).data)
+                if (<Sequence> seqs[i])._regions is not None:
+                    masked = True
             if tinf_of is None:
                 self._ensure_models(slot)
             else:
@@ -1782,6 +1973,8 @@ cdef class GeneFinder:
                 if rc != PGA_OK:
                     _raise_for(ctx, rc, "pga_batch_create")
                 try:
+                    if masked:
+                        _attach_masks(ctx, batch, seqs, self.mask_lowercase)
                     with nogil:
                         rc = pga_find_genes_models(ctx, batch, &p, <const int32_t*> p_moc, &res)
                     if rc != PGA_OK:
@@ -1790,7 +1983,7 @@ cdef class GeneFinder:
                         prot, prot_off, tables = self._translate(ctx, batch, res, n, tinf_of)
                 finally:
                     pga_batch_free(batch)
-            elif not translate:
+            elif not translate and not masked:
                 with nogil:
                     rc = pga_find_genes_batch(ctx, n, ptrs, lens, &p, &res)
                 if rc != PGA_OK:
@@ -1800,12 +1993,15 @@ cdef class GeneFinder:
                 if rc != PGA_OK:
                     _raise_for(ctx, rc, "pga_batch_create")
                 try:
+                    if masked:
+                        _attach_masks(ctx, batch, seqs, self.mask_lowercase)
                     with nogil:
                         rc = pga_find_genes(ctx, batch, &p, &res)
                     if rc != PGA_OK:
                         _raise_for(ctx, rc, "pga_find_genes")
-                    prot_off = np.zeros(res.n_genes + 1, np.int64)
-                    prot, prot_off, tables = self._translate(ctx, batch, res, n, None)
+                    if translate:
+                        prot_off = np.zeros(res.n_genes + 1, np.int64)
+                        prot, prot_off, tables = self._translate(ctx, batch, res, n, None)
                 finally:
                     pga_batch_free(batch)
             for i in range(n):
@@ -1916,23 +2112,44 @@ cdef class GeneFinder:
             _raise_for(slot.ctx, rc, "pga_set_models")
         return models, moc
 
-    cdef Sequence _training_sequence(self, object sequence, tuple sequences, str which):
+    cdef Sequence _training_sequence(self, object sequence, tuple sequences, str which, object regions=None):
         """One genome as `train(sequence, *sequences)` takes it: several contigs joined with `TTAATTAATTAA` linkers like in
-        Prodigal (ref: lib.pyx:5510-5532), then the length rules (`which` names the genome in the messages)."""
+        Prodigal (ref: lib.pyx:5510-5532), then the length rules (`which` names the genome in the messages).  `regions`: the
+        intervals of the one sequence, or with several contigs one entry (None or intervals) per contig -- they travel with
+        their contig through the join."""
         import warnings
         cdef Sequence seq
+        cdef list joined = None, per
+        cdef Py_ssize_t at = 0, k
+        if regions is not None and sequences:
+            per = list(regions)
+            if len(per) != 1 + len(sequences):
+                raise ValueError("%s`regions` has %d entries for %d contigs" % (which, len(per), 1 + len(sequences)))
+            joined = []
+            for k, x in enumerate((sequence,) + sequences):
+                r = _check_regions(per[k], len(x), "%scontig %d: " % (which, k))
+                if r is not None:
+                    joined.extend([(int(b) + at, int(e) + at) for b, e in r.tolist()])
+                at += len(x) + 12
+            regions = joined
         if isinstance(sequence, Sequence):
             if sequences:
                 raise NotImplementedError("cannot use more than one `Sequence` object in `GeneFinder.train`")
-            seq = Sequence(sequence, mask=self.mask, mask_size=self.min_mask)
+            seq = Sequence(sequence, mask=self.mask, mask_size=self.min_mask, mask_lowercase=self.mask_lowercase)
+            if regions is not None:
+                r = _check_regions(regions, len(seq.data), which)
+                if r is not None:
+                    seq._regions = r if seq._regions is None else np.concatenate([seq._regions, r])
         elif isinstance(sequence, str):
             if sequences:
                 sequence = "TTAATTAATTAA".join(list((sequence,) + sequences) + [""])
-            seq = Sequence(sequence, mask=self.mask, mask_size=self.min_mask)
+            seq = Sequence(sequence, mask=self.mask, mask_size=self.min_mask, mask_lowercase=self.mask_lowercase)
+            seq._regions = _check_regions(regions, len(seq.data), which)
         else:
             if sequences:
                 sequence = b"TTAATTAATTAA".join([bytes(memoryview(x)) for x in (sequence,) + sequences] + [b""])
-            seq = Sequence(sequence, mask=self.mask, mask_size=self.min_mask)
+            seq = Sequence(sequence, mask=self.mask, mask_size=self.min_mask, mask_lowercase=self.mask_lowercase)
+            seq._regions = _check_regions(regions, len(seq.data), which)
         if len(seq) < MIN_SINGLE_GENOME:
             raise ValueError("%ssequence must be at least %d characters (%d found)" % (which, MIN_SINGLE_GENOME, len(seq)))
         elif len(seq) < IDEAL_SINGLE_GENOME:
@@ -1940,8 +2157,11 @@ cdef class GeneFinder:
         return seq
 
     def select_translation_table(self, object genomes, *, object candidates=(11, 4), double min_gain=0.05, double min_density=0.7,
-                                 bint force_nonsd=False, double start_weight=4.35):
+                                 bint force_nonsd=False, double start_weight=4.35, object regions=None):
         """The translation table of every genome, chosen by coding density (`pyrodigal_amd.tables`), on the device.
+
+        `regions`: one entry per genome, as `train` takes them (the intervals of a one-sequence genome, or one entry per contig);
+        every candidate is trained and called under the same masks.
 
         A genome is one sequence or a list / tuple of contigs, as `train_batch` takes it.  For every candidate table it is trained
         (the contigs joined with linkers, this finder's options, `force_nonsd`, `start_weight`) and its contigs called with that
@@ -1957,10 +2177,16 @@ cdef class GeneFinder:
         cands = _tables.check_candidates(candidates)
         min_gain, min_density = _tables.check_thresholds(min_gain, min_density)
         cdef list gl = list(genomes)
+        cdef list rl = None
+        if regions is not None:
+            rl = list(regions)
+            if len(rl) != len(gl):
+                raise ValueError("`regions` has %d entries for %d genomes" % (len(rl), len(gl)))
         return self._select_tables(gl, cands, min_gain, min_density, [bool(force_nonsd)] * len(gl), [float(start_weight)] * len(gl),
-                                   "genome %d: ", list(range(len(gl))))
+                                   "genome %d: ", list(range(len(gl))), rl)
 
-    def _select_tables(self, list gl, tuple cands, double min_gain, double min_density, list fns, list sws, str which, list names):
+    def _select_tables(self, list gl, tuple cands, double min_gain, double min_density, list fns, list sws, str which, list names,
+                       list regions=None):
         """`select_translation_table` with one `force_nonsd` / `start_weight` per genome (`names[g]`: the genome's number in messages)."""
         cdef Py_ssize_t G = len(gl), K = len(cands), g, k
         if G == 0:
@@ -1972,8 +2198,9 @@ cdef class GeneFinder:
             parts = list(x) if isinstance(x, (list, tuple)) else [x]
             if not parts:
                 raise ValueError((which % names[g]) + "no sequence")
-            train_seqs.append(self._training_sequence(parts[0], tuple(parts[1:]), which % names[g]))
-            cs = self._wrap_sequences(parts)
+            rg = regions[g] if regions is not None else None
+            train_seqs.append(self._training_sequence(parts[0], tuple(parts[1:]), which % names[g], rg))
+            cs = self._wrap_sequences(parts, None if rg is None else (list(rg) if len(parts) > 1 else [rg]))
             contigs.append(cs)
             lengths.append(sum([len((<Sequence> c).data) for c in cs]))
         # the device calls: consecutive genomes, every candidate of a genome in the same call; K copies of a genome count against
@@ -2056,6 +2283,7 @@ cdef class GeneFinder:
         if rc != PGA_OK:
             _raise_for(ctx, rc, "pga_batch_create")
         try:
+            _attach_masks(ctx, up, [train_seqs[g] for g in idx], self.mask_lowercase)      # the copies inherit them
             rc = pga_batch_replicate(ctx, up, <int32_t> (n * K), <const int32_t*> p_coe, &rep)
             if rc != PGA_OK:
                 _raise_for(ctx, rc, "pga_batch_replicate")
@@ -2106,6 +2334,7 @@ cdef class GeneFinder:
         finally:
             free(ptrs); free(lens); free(mptrs)
         try:
+            _attach_masks(ctx, up, cseqs, self.mask_lowercase)
             rc = pga_batch_replicate(ctx, up, <int32_t> (nc * K), <const int32_t*> p_coe, &rep)
             if rc != PGA_OK:
                 _raise_for(ctx, rc, "pga_batch_replicate")
@@ -2123,7 +2352,8 @@ cdef class GeneFinder:
         raws = [[raw[(k * n + j) * TRAINING_INFO_SIZE:(k * n + j + 1) * TRAINING_INFO_SIZE].copy() for j in range(n)] for k in range(K)]
         return raws, coding
 
-    def train_batch(self, object genomes, *, object force_nonsd=False, object start_weight=4.35, object translation_table=11):
+    def train_batch(self, object genomes, *, object force_nonsd=False, object start_weight=4.35, object translation_table=11,
+                    object regions=None):
         """`train` on many genomes at once, on the device (`pga_train_batch`): every stage and training round runs once for the
         whole batch.  A genome is one sequence or a list / tuple of contigs (joined as `train(*contigs)` joins them); the
         keywords take a scalar or one value per genome.  Returns one `TrainingInfo` per genome, identical to
@@ -2135,6 +2365,11 @@ cdef class GeneFinder:
         cdef Py_ssize_t G = len(gl), g
         if G == 0:
             return []
+        cdef list rl = None         # `regions`: one entry per genome, as `train` takes them
+        if regions is not None:
+            rl = list(regions)
+            if len(rl) != G:
+                raise ValueError("`regions` has %d entries for %d genomes" % (len(rl), G))
         def per_genome(v, name):
             if isinstance(v, (list, tuple, np.ndarray)):
                 if len(v) != G:
@@ -2154,9 +2389,11 @@ cdef class GeneFinder:
             # "auto": the table of `select_translation_table` with its defaults; the other genomes train as they are
             rest = [g for g in range(G) if g not in set(auto)]
             picked = self._select_tables([gl[g] for g in auto], _tables.DEFAULT_CANDIDATES, _tables.DEFAULT_MIN_GAIN,
-                                         _tables.DEFAULT_MIN_DENSITY, [fns[g] for g in auto], [sws[g] for g in auto], "genome %d: ", auto)
+                                         _tables.DEFAULT_MIN_DENSITY, [fns[g] for g in auto], [sws[g] for g in auto], "genome %d: ", auto,
+                                         None if rl is None else [rl[g] for g in auto])
             trained = self.train_batch([gl[g] for g in rest], force_nonsd=[fns[g] for g in rest], start_weight=[sws[g] for g in rest],
-                                       translation_table=[tts[g] for g in rest]) if rest else []
+                                       translation_table=[tts[g] for g in rest],
+                                       regions=None if rl is None else [rl[g] for g in rest]) if rest else []
             merged = [None] * G
             for ga, sel in zip(auto, picked):
                 merged[ga] = sel.training_info
@@ -2166,8 +2403,9 @@ cdef class GeneFinder:
         cdef list seqs = []
         for g in range(G):
             x = gl[g]
-            seqs.append(self._training_sequence(x[0], tuple(x[1:]), "genome %d: " % g) if isinstance(x, (list, tuple))
-                        else self._training_sequence(x, (), "genome %d: " % g))
+            rg = rl[g] if rl is not None else None
+            seqs.append(self._training_sequence(x[0], tuple(x[1:]), "genome %d: " % g, rg) if isinstance(x, (list, tuple))
+                        else self._training_sequence(x, (), "genome %d: " % g, rg))
         # the device calls: consecutive genomes under the base budget and at most four distinct tables
         cdef list calls = [], cur = []
         cdef set tables = set()
@@ -2229,6 +2467,7 @@ cdef class GeneFinder:
                 if rc != PGA_OK:
                     _raise_for(ctx, rc, "pga_batch_create")
                 try:
+                    _attach_masks(ctx, batch, [seqs[g] for g in idx], self.mask_lowercase)
                     with nogil:
                         rc = pga_train_batch(ctx, batch, &p, <const int32_t*> p_tt, <const double*> p_sw, <const int32_t*> p_fn, 0,
                                              <pga_training*> p_out, <int32_t*> p_st)
@@ -2246,12 +2485,16 @@ cdef class GeneFinder:
                 self._release_slot(slot)
         return out
 
-    def train(self, object sequence, *sequences, bint force_nonsd=False, double start_weight=4.35, object translation_table=11):
+    def train(self, object sequence, *sequences, bint force_nonsd=False, double start_weight=4.35, object translation_table=11,
+              object regions=None):
         """Train on the given genome, on the device, and use the result for the next `find_genes` (ref: lib.pyx:5471-5575).
 
         Several sequences (the contigs of one genome) are joined with `TTAATTAATTAA` linkers like in Prodigal.
         `translation_table="auto"` trains with the table `select_translation_table` chooses with its defaults (11, or 4 when it
-        covers clearly more of the genome); the contigs are then also called one by one, as `find_genes` calls them."""
+        covers clearly more of the genome); the contigs are then also called one by one, as `find_genes` calls them.
+
+        `regions`: masked intervals as `find_genes` takes them -- of the one sequence, or with several contigs one entry (None or
+        intervals) per contig; they travel with their contig through the join."""
         import warnings
         cdef Sequence seq
         cdef pga_params p
@@ -2267,13 +2510,14 @@ cdef class GeneFinder:
         if isinstance(translation_table, str):
             if translation_table != "auto":
                 raise ValueError("%r is not a valid translation table index (an int, or \"auto\")" % (translation_table,))
-            picked = self.select_translation_table([(sequence,) + sequences], force_nonsd=force_nonsd, start_weight=start_weight)[0]
+            picked = self.select_translation_table([(sequence,) + sequences], force_nonsd=force_nonsd, start_weight=start_weight,
+                                                   regions=None if regions is None else [regions])[0]
             self.training_info = picked.training_info
             return picked.training_info
         cdef int tt = translation_table       # an int as before ("auto" above)
         if tt not in TRANSLATION_TABLES:
             raise ValueError("%d is not a valid translation table index" % tt)
-        seq = self._training_sequence(sequence, sequences, "")
+        seq = self._training_sequence(sequence, sequences, "", regions)
         p.closed = self.closed; p.min_gene = self.min_gene; p.min_edge_gene = self.min_edge_gene
         p.max_overlap = self.max_overlap; p.meta = 0; p.want_nodes = 0
         p.mask = self.mask; p.min_mask = self.min_mask
@@ -2301,6 +2545,7 @@ cdef class GeneFinder:
             if rc != PGA_OK:
                 _raise_for(ctx, rc, "pga_batch_create")
             try:
+                _attach_masks(ctx, batch, [seq], self.mask_lowercase)
                 with nogil:
                     rc = pga_train(ctx, batch, &p, tt, start_weight, force_nonsd, 0, <pga_training*> out_ptr)
                 if rc != PGA_OK:

@@ -73,13 +73,36 @@ def find_genes_stream(batches, model_blobs, n_contexts=2, device=0, **find_kw):
             c.close()
 
 
-def find_genes_fasta(path, model_blobs, n_contexts=2, device=0, max_bases=64 << 20, contexts=None, **find_kw):
+def _attach_masks(batch, ids, lens, regions_by_id, mask_lowercase, seen):
+    """The mask sources of one resident batch of a FASTA file: the regions of the records whose id is a key of ``regions_by_id``
+    (checked against the record's length: ``ValueError`` names the record) and the lower-case rule.  ``seen`` collects the keys met."""
+    regions = None
+    if regions_by_id:
+        regions = []
+        for i, rid in enumerate(ids):
+            iv = regions_by_id.get(rid)
+            if iv is not None:
+                seen.add(rid)
+                for b, e in iv:
+                    if not (0 <= b < e <= int(lens[i])):
+                        raise ValueError("sequence %r: region [%d, %d) is not a non-empty part of the sequence [0, %d)" % (rid, b, e, int(lens[i])))
+            regions.append(iv)
+    if regions is not None or mask_lowercase:
+        batch.set_masks(regions, mask_lowercase)
+
+
+def find_genes_fasta(path, model_blobs, n_contexts=2, device=0, max_bases=64 << 20, contexts=None, regions_by_id=None,
+                     mask_lowercase=False, **find_kw):
     """Genes of every record of a (gzipped) FASTA file: yields ``(ids, descriptions, lengths, BatchResult)`` per batch, in file order.
 
     The reader (C, zlib) parses batch k + 1 into a pinned staging arena while batch k is uploaded from its own arena with one
     DMA (no host-side packing) and processed; ``n_contexts`` contexts keep the device busy across batches
     (ref: what the reference's CLI does with a thread pool over records, cli.py:287-302).  `contexts`: contexts the caller keeps
-    across files (models loaded, device buffers grown) instead of `n_contexts` fresh ones."""
+    across files (models loaded, device buffers grown) instead of `n_contexts` fresh ones.
+
+    ``regions_by_id``: ``{sequence id: [(begin, end), ...]}``, masked regions (0-based, half-open) of the records with that id (the
+    first word of the header); ``mask_lowercase``: runs of lower-case letters are masked (``Batch.set_masks``)."""
+    seen = set()
     own = contexts is None             # `contexts`: contexts the caller keeps across files (models loaded, buffers grown)
     ctxs = [_cabi.Context(device) for _ in range(max(1, n_contexts))] if own else list(contexts)
     if own:
@@ -97,8 +120,10 @@ def find_genes_fasta(path, model_blobs, n_contexts=2, device=0, max_bases=64 << 
             i, pb = item
             try:
                 meta = (pb.ids, pb.descriptions, pb.lens)
+                lens = [int(x) for x in pb.lens[:pb.n]]
                 b = ctx.upload_packed(pb)                 # releases the arena
                 try:
+                    _attach_masks(b, meta[0], lens, regions_by_id, mask_lowercase, seen)
                     res = (meta, ctx.find_genes(b, **find_kw))
                 finally:
                     b.close()
@@ -151,7 +176,7 @@ def find_genes_fasta(path, model_blobs, n_contexts=2, device=0, max_bases=64 << 
 
 def render_fasta(path, model_blobs, *, gff=None, faa=None, fna=None, gbk=None, scores=None, n_contexts=2, device=0, max_bases=64 << 20,
                  meta=False, descriptions=None, first_seqnum=1, gff_options=None, faa_options=None, fna_options=None, gbk_options=None,
-                 scores_options=None, unbinned_model=None, **find_kw):
+                 scores_options=None, unbinned_model=None, regions_by_id=None, mask_lowercase=False, **find_kw):
     """Call the genes of every record of a FASTA file and write them as text: GFF to ``gff``, protein FASTA to ``faa``, gene
     FASTA to ``fna``, GenBank to ``gbk``, the start-score file to ``scores`` (binary file objects, or None), in file order --
     what ``Genes.write_gff`` / ``write_translations`` / ``write_genes`` / ``write_genbank`` / ``write_scores`` write record after
@@ -162,8 +187,10 @@ def render_fasta(path, model_blobs, *, gff=None, faa=None, fna=None, gbk=None, s
     is rendered on the device while it is still resident (``Context.render_genes``) and only its text comes back: memory stays
     bounded by the batch size.  Sequence ids are the first word of the headers, seqnums count records from ``first_seqnum``.
     ``*_options``: the writer's keyword arguments of that format; ``unbinned_model``: see ``Context.render_genes``; ``find_kw``
-    goes to ``Context.find_genes``.  Returns
-    ``{"records", "bases", "genes", "fallback", "kernel_ms": {format: ms}}``."""
+    goes to ``Context.find_genes``.  ``regions_by_id`` / ``mask_lowercase``: more mask sources, as :func:`find_genes_fasta` takes
+    them.  Returns ``{"records", "bases", "genes", "fallback", "kernel_ms": {format: ms}, "regions_unmatched": [ids of
+    regions_by_id that no record carried]}``."""
+    seen = set()
     formats = {}
     for name, fh, opts in (("gff", gff, gff_options), ("faa", faa, faa_options), ("fna", fna, fna_options), ("gbk", gbk, gbk_options),
                            ("scores", scores, scores_options)):
@@ -192,8 +219,10 @@ def render_fasta(path, model_blobs, *, gff=None, faa=None, fna=None, gbk=None, s
             i, seqnum, pb = item
             try:
                 ids, n, total = pb.ids, pb.n, pb.total
+                lens = [int(x) for x in pb.lens[:pb.n]]
                 b = ctx.upload_packed(pb)                 # releases the arena
                 try:
+                    _attach_masks(b, ids, lens, regions_by_id, mask_lowercase, seen)
                     r = ctx.find_genes(b, meta=meta, want_nodes=want_nodes, **find_kw)
                     text = ctx.render_genes(b, r, ids, formats, meta=meta, descriptions=descriptions, first_seqnum=seqnum,
                                             unbinned_model=unbinned_model)
@@ -241,6 +270,7 @@ def render_fasta(path, model_blobs, *, gff=None, faa=None, fna=None, gbk=None, s
                 stats["fallback"] += t.fallback
                 stats["kernel_ms"][name] += t.kernel_ms
             stats["records"] += n; stats["bases"] += total; stats["genes"] += n_genes
+        stats["regions_unmatched"] = sorted(set(regions_by_id or ()) - seen)
         return stats
     finally:
         for _ in threads:
