@@ -227,6 +227,31 @@ void pga_batch_free(pga_batch*);
  * Not to be called while a call on the batch runs. */
 int  pga_batch_set_regions(pga_batch*, const int32_t* off /* n + 1 */, const int32_t* iv /* 2 per interval */);
 int  pga_batch_set_mask_case(pga_batch*, int lower_case);
+/* Topology, one more attribute of the resident batch: circular[i] != 0 marks contig i a circle that the record cuts open at an
+ * arbitrary base (NULL: every contig is linear again).  pga_find_genes and pga_find_genes_models then call a flagged contig of L
+ * bases in two passes, the linear contigs of the batch exactly as without flags, in one call and in batch order:
+ *   1. the ordinary call on the record; only the positions its genes cover are used;
+ *   2. cut = pga_circular_cut of those genes: the middle of the widest uncovered stretch in the record's middle half;
+ *   3. the ordinary call, with closed = 1, on the contig rotated to start at base cut (0-based): R = S[cut:] + S[:cut];
+ *   4. a gene begin_R..end_R of R is reported with begin = (begin_R - 1 + cut) % L + 1 and end = begin + (end_R - begin_R): always
+ *      1 <= begin <= L, and end > L exactly for a gene across the origin, which ends at base end - L.  Genes are ordered by begin,
+ *      partial_begin = partial_end = 0, every other field is pass 3's; node arrays (want_nodes) and start_ndx / stop_ndx are those of
+ *      R, in R's coordinates.
+ * Mask sources follow the letters (runs are found on R; the caller's regions are rotated and split at the cut); pga_result.masks
+ * stays in the record's coordinates.  pga_translate_genes and pga_render_genes read positions beyond L of a flagged contig at p - L;
+ * the `# Sequence Data:` line of a flagged contig ends `;topology=circular`.  PGA_RENDER_SCO and PGA_RENDER_GBK refuse a batch
+ * with flags (PGA_EINVAL): nodes live in R's coordinates, and GenBank locations across the origin are the host writer's.
+ * pga_batch_replicate carries the flags; training, pga_nodes_stage and pga_find_coding_bases ignore them.
+ * Not to be called while a call on the batch runs. */
+int  pga_batch_set_circular(pga_batch*, const uint8_t* circular /* n flags, or NULL */);
+/* The cut of every contig of the last pga_find_genes / pga_find_genes_models call on the context: out[i] for i < n, -1 for a linear
+ * contig (and for every contig when the batch carried no flag). */
+int  pga_circular_cuts(const pga_ctx*, int32_t n, int32_t* out);
+/* Step 2 above (host arithmetic only): genes begin[k]..end[k], 1-based inclusive, either strand, any order, on a contig of L bases.
+ * A gap is a maximal run of positions no gene covers, [gb, ge) 0-based, mid = (gb + ge) / 2.  Among the gaps with
+ * L / 4 <= mid < L - L / 4 (all gaps if there is none) the widest wins, then the smallest |mid - L / 2|, then the lowest mid;
+ * returns its mid, L / 2 when there is no gap, or a negative PGA_E* code. */
+int  pga_circular_cut(int32_t L, int32_t n, const int32_t* begin, const int32_t* end);
 int  pga_find_genes(pga_ctx*, const pga_batch*, const pga_params*, pga_result** out);
 /* Single mode, contig i called with loaded model model_of_contig[i] (an index into the pga_set_models set): every contig's result
  * is identical to pga_find_genes with that one model loaded -- its nodes extracted under that model's translation table, its genes,

@@ -23,6 +23,7 @@ EXPORTS = [
     "pga_find_genes_models", "pga_train_batch", "pga_render_genes", "pga_render_free",
     "pga_batch_replicate", "pga_find_coding_bases",
     "pga_batch_set_regions", "pga_batch_set_mask_case",
+    "pga_batch_set_circular", "pga_circular_cuts", "pga_circular_cut",
 ]
 STAGE_EXTRACT, STAGE_SCORE, STAGE_OVERLAP, STAGE_SEQUENCE = 1, 2, 3, 4
 
@@ -139,6 +140,9 @@ def load():
     L.pga_batch_replicate.restype = ctypes.c_int; L.pga_batch_replicate.argtypes = [vp, vp, i32, vp, _P(vp)]
     L.pga_batch_set_regions.restype = ctypes.c_int; L.pga_batch_set_regions.argtypes = [vp, vp, vp]
     L.pga_batch_set_mask_case.restype = ctypes.c_int; L.pga_batch_set_mask_case.argtypes = [vp, ctypes.c_int]
+    L.pga_batch_set_circular.restype = ctypes.c_int; L.pga_batch_set_circular.argtypes = [vp, vp]
+    L.pga_circular_cuts.restype = ctypes.c_int; L.pga_circular_cuts.argtypes = [vp, i32, vp]
+    L.pga_circular_cut.restype = ctypes.c_int; L.pga_circular_cut.argtypes = [i32, i32, vp, vp]
     L.pga_find_coding_bases.restype = ctypes.c_int; L.pga_find_coding_bases.argtypes = [vp, vp, _P(Params), vp, vp, vp, vp]
     L.pga_nodes_stage.restype = ctypes.c_int
     L.pga_nodes_stage.argtypes = [vp, vp, _P(Params), ctypes.c_int, ctypes.c_int, _P(_P(Result))]
@@ -360,8 +364,9 @@ _NODE_FIELDS = [
 class BatchResult:
     """Host copy of a ``pga_result``: ``contigs`` / ``genes`` structured arrays (+ per-contig node dicts)."""
 
-    def __init__(self, contigs, genes, nodes, t_total_ms, t_dp_ms, node_passes, n_chains=0, masks=None):
+    def __init__(self, contigs, genes, nodes, t_total_ms, t_dp_ms, node_passes, n_chains=0, masks=None, cuts=None):
         self.contigs, self.genes, self.nodes = contigs, genes, nodes
+        self.cuts = cuts            # int32 per contig: where a circular contig was cut open (-1: linear), or None when the batch has no flag
         self.masks = masks          # per contig an (k, 2) array of [begin, end) intervals, or None when masking is off
         self.t_total_ms, self.t_dp_ms, self.node_passes, self.n_chains = t_total_ms, t_dp_ms, node_passes, n_chains
 
@@ -429,6 +434,27 @@ class Batch:
             rc = L.pga_batch_set_mask_case(self.h, int(bool(mask_lowercase)))
         if rc != PGA_OK:
             _raise(L, self.ctx.h, rc, "pga_batch_set_regions")
+        return self
+
+    circular = None     # the flags of set_circular (uint8 per contig), or None: every contig is linear
+
+    def set_circular(self, circular=None):
+        """Mark contigs circular (``pga_batch_set_circular``): ``None`` / ``False`` (all linear), ``True`` (all circular) or one flag
+        per contig.  ``find_genes`` then calls the flagged contigs across the origin and reports ``cuts``."""
+        if circular is None or circular is False:
+            flags = None
+        elif circular is True:
+            flags = np.ones(max(self.n, 1), np.uint8)
+        else:
+            flags = np.ascontiguousarray([1 if x else 0 for x in circular], dtype=np.uint8)
+            if flags.shape != (self.n,):
+                raise ValueError(f"circular has {flags.size} entries for {self.n} contigs")
+            if not flags.any():
+                flags = None
+        rc = self.ctx.L.pga_batch_set_circular(self.h, None if flags is None else ctypes.c_void_p(flags.ctypes.data))
+        if rc != PGA_OK:
+            _raise(self.ctx.L, self.ctx.h, rc, "pga_batch_set_circular")
+        self.circular = flags
         return self
 
     def __init__(self, ctx, seqs):
@@ -585,7 +611,14 @@ def _find_genes(self, batch, meta=True, closed=False, min_gene=90, min_edge_gene
         what = "pga_find_genes_models"
     if rc != PGA_OK:
         _raise(self.L, self.h, rc, what)
-    return _unpack_result(self.L, res, wn == 1)
+    out = _unpack_result(self.L, res, wn == 1)
+    if batch.circular is not None:
+        cuts = np.full(max(batch.n, 1), -1, np.int32)
+        rc = self.L.pga_circular_cuts(self.h, batch.n, ctypes.c_void_p(cuts.ctypes.data))
+        if rc != PGA_OK:
+            _raise(self.L, self.h, rc, "pga_circular_cuts")
+        out.cuts = cuts[:batch.n]
+    return out
 
 
 def _replicate(self, batch, contig_of_entry):
@@ -598,6 +631,8 @@ def _replicate(self, batch, contig_of_entry):
     b = Batch.__new__(Batch)
     b.ctx, b.n, b.h = self, int(coe.size), h
     b.total = None
+    if batch.circular is not None and batch.circular[coe].any():        # the flags travel with the contigs
+        b.circular = np.ascontiguousarray(batch.circular[coe])
     return b
 
 
@@ -618,14 +653,16 @@ def _find_coding_bases(self, batch, model_of_contig, closed=False, min_gene=90, 
     return cov[:batch.n], ng[:batch.n], sc[:batch.n]
 
 
-def _find_genes_batch(self, seqs, regions=None, mask_lowercase=False, **kw):
+def _find_genes_batch(self, seqs, regions=None, mask_lowercase=False, circular=None, **kw):
     """Upload + find + free: ``seqs`` is a list of ASCII ``bytes``/``str`` contigs.  ``regions`` (one entry per contig: ``None`` or
     ``(begin, end)`` pairs) and ``mask_lowercase`` are more mask sources (:meth:`Batch.set_masks`); ``masks`` of the result is their
-    union with the runs of unknown bases of ``mask=True``."""
+    union with the runs of unknown bases of ``mask=True``.  ``circular``: as :meth:`Batch.set_circular` takes it."""
     b = Batch(self, seqs)
     try:
         if regions is not None or mask_lowercase:
             b.set_masks(regions, mask_lowercase)
+        if circular is not None and circular is not False:
+            b.set_circular(circular)      # (through a resident batch: the one-step pga_find_genes_batch has none to flag)
         return _find_genes(self, b, **kw)
     finally:
         b.close()

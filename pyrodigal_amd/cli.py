@@ -58,7 +58,58 @@ def argument_parser(prog="pyrodigal_amd"):
     p.add_argument("--mask-regions", metavar="FILE",
                    help="Don't build genes across the regions of this BED-like file: tab-separated seqid, start, end (0-based, "
                         "half-open; seqid is the first word of the FASTA header); further columns, # lines and track lines are ignored.")
+    p.add_argument("--circular", action="store_true", default=False,
+                   help="Every record is a circular sequence cut open at an arbitrary base: genes are called across the origin "
+                        "(a gene across it ends beyond the sequence length).")
+    p.add_argument("--circular-ids", metavar="FILE",
+                   help="The records whose id (first word of the FASTA header) is listed in this file, one per line, are circular.")
+    p.add_argument("--circular-from-header", action="store_true", default=False,
+                   help="The records whose header says circular=true or topology=circular (any letter case) are circular.")
     return p
+
+
+def parse_circular_ids(lines):
+    """The set of sequence ids of a text (an iterable of lines), one id per line: the first word counts, blank lines and
+    ``#`` lines are ignored."""
+    ids = set()
+    for line in lines:
+        if isinstance(line, bytes):
+            line = line.decode("utf-8", "replace")
+        words = line.split()
+        if words and not words[0].startswith("#"):
+            ids.add(words[0])
+    return ids
+
+
+def circular_option(args):
+    """What ``pipeline.render_fasta(circular=...)`` takes for the three options (None: no record is circular).  With several of
+    them a record is circular when any says so."""
+    if args.circular:
+        return True
+    ids = None
+    if args.circular_ids is not None:
+        with open(args.circular_ids, "r", encoding="utf-8", errors="replace") as fh:
+            ids = parse_circular_ids(fh)
+    if args.circular_from_header:
+        from .pipeline import header_says_circular
+        if ids is None:
+            return header_says_circular
+        return _ListedOrHeader(ids)
+    return ids
+
+
+class _ListedOrHeader:
+    """``--circular-ids`` and ``--circular-from-header`` together: a predicate that also remembers the listed ids it met."""
+
+    def __init__(self, ids):
+        self.ids, self.seen = ids, set()
+
+    def __call__(self, seq_id, description):
+        from .pipeline import header_says_circular
+        if seq_id in self.ids:
+            self.seen.add(seq_id)
+            return True
+        return header_says_circular(seq_id, description)
 
 
 def parse_mask_regions(lines, name="<regions>"):
@@ -105,6 +156,8 @@ def _check(args):
         return "-j must be at least 1."
     if args.batch_bases < 1:
         return "--batch-bases must be at least 1."
+    if args.s is not None and (args.circular or args.circular_ids is not None or args.circular_from_header):
+        return "-s cannot be combined with --circular, --circular-ids or --circular-from-header: the start file is not written for circular sequences."
     return None
 
 
@@ -131,7 +184,12 @@ def main(argv=None, stdout=None, stderr=None):
         except (OSError, ValueError) as e:
             print("Error: --mask-regions: %s" % e, file=stderr)
             return 1
-    mask_kw = dict(regions_by_id=regions, mask_lowercase=args.mask_lowercase)
+    try:
+        circular = circular_option(args)
+    except OSError as e:
+        print("Error: --circular-ids: %s" % e, file=stderr)
+        return 1
+    mask_kw = dict(regions_by_id=regions, mask_lowercase=args.mask_lowercase, circular=circular)
     with contextlib.ExitStack() as stack:
         path = args.i
         if path is None:                        # stdin: the reader needs a file it can sniff and map
@@ -179,4 +237,9 @@ def main(argv=None, stdout=None, stderr=None):
                              faa_options={"include_stop": not args.no_stop_codon}, unbinned_model=unbinned, **mask_kw, **find_kw)
         for rid in stats.get("regions_unmatched", ()):
             print("Warning: --mask-regions: no sequence %r in the input" % rid, file=stderr)
+        unmatched = stats.get("circular_unmatched", ())
+        if isinstance(circular, _ListedOrHeader):
+            unmatched = sorted(circular.ids - circular.seen)
+        for rid in unmatched:
+            print("Warning: --circular-ids: no sequence %r in the input" % rid, file=stderr)
     return 0

@@ -1131,6 +1131,8 @@ struct pga_batch {
     std::vector<int32_t> reg_off;     // the caller's intervals: contig i owns regions[reg_off[i] .. reg_off[i + 1]); empty: none attached
     std::vector<MaskRun> regions;     // (contig, begin, end) as given: any order, overlaps allowed
     MaskRun* d_regions = nullptr;     // their device copy
+    // topology (pga_batch_set_circular): one flag per contig, empty: every contig is linear
+    std::vector<uint8_t> circular;
 };
 
 // Tiles of a batch: every position of a contig of at least three bases lies in one tile.  Host vectors for one upload.
@@ -1378,8 +1380,8 @@ extern "C" int pga_batch_create_packed(pga_ctx* c, int32_t n_contigs, const char
 }
 
 // what translate.hip needs of a batch
-struct pga_batch_view { pga_ctx* ctx; int32_t n; int64_t total; const ContigDesc* ct; const char* d_seq; };
-pga_batch_view pga_batch_peek(const pga_batch* b) { return pga_batch_view{b->ctx, b->n, b->total, b->ct.data(), b->d_seq}; }
+struct pga_batch_view { pga_ctx* ctx; int32_t n; int64_t total; const ContigDesc* ct; const char* d_seq; const uint8_t* circular /* or nullptr: all linear */; };
+pga_batch_view pga_batch_peek(const pga_batch* b) { return pga_batch_view{b->ctx, b->n, b->total, b->ct.data(), b->d_seq, b->circular.empty() ? nullptr : b->circular.data()}; }
 
 extern "C" void pga_batch_free(pga_batch* b) {
     if (!b) return;
@@ -1473,8 +1475,11 @@ static int fetch_mask_union(pga_ctx* c, ResultOwner* R, const int32_t* h_moff, c
 // tt_of_contig (EXTRACT stage; nullptr = tt_override everywhere): contig i is extracted under that table.  At most 4 tables.
 // coding (stage 0, single mode; nullptr otherwise): coding[i] = bases of contig i inside at least one of its genes, counted where the
 // gene records are (pga_find_coding_bases); the records are then not copied back and the result holds no genes.
+// keep (stage 0; nullptr otherwise): a pass of a circular call (circular.inl) -- the gene records stay on the device, in the buffer
+// `keep->buf`, and the result holds none; `keep` reports where they are (nothing when the call found no node at all).
+struct GeneKeep { const char* buf; pga_gene* d_genes = nullptr; int64_t n_genes = 0; };
 static int find_impl_cov(pga_ctx* c, const pga_batch* batch, const pga_params* pp, const int stage, const int tt_override, pga_result** out,
-                         const int32_t* model_of_contig, const int32_t* tt_of_contig, int64_t* coding) {
+                         const int32_t* model_of_contig, const int32_t* tt_of_contig, int64_t* coding, GeneKeep* keep = nullptr) {
     if (out) *out = nullptr;
     if (c) c->dev_nodes.clear();        // this call reuses the arena the last one kept on the device
     if (!c || !out || !pp || !batch || batch->ctx != c) {
@@ -2289,6 +2294,7 @@ static int find_impl_cov(pga_ctx* c, const pga_batch* batch, const pga_params* p
         // PGA_TAIL = host | device (one thread per contig) | par (tail.inl, the default)
         const char* tail_env = getenv("PGA_TAIL");
         const bool device_tail = tail_env ? strcmp(tail_env, "host") != 0 : true;
+        if (keep && !device_tail) { c->err = "pga_find_genes: circular contigs are called with the device tail only (PGA_TAIL=host is set)"; return PGA_EINVAL; }
         const bool par_tail = device_tail && !(tail_env && strcmp(tail_env, "device") == 0);
         std::vector<int32_t> tracef;
         std::vector<uint8_t> elim;
@@ -2561,17 +2567,18 @@ static int find_impl_cov(pga_ctx* c, const pga_batch* batch, const pga_params* p
                 cr.model = chains[k].model; cr.n_nodes = chains[k].n;
                 cr.score = P.meta ? 0.0 : (h_ipath[k] >= 0 ? h_maxscore[k] : 0.0);
             }
-            pga_gene* const genes_out = coding ? nullptr : R->gene_records((size_t)ngenes);
+            pga_gene* const genes_out = coding || keep ? nullptr : R->gene_records((size_t)ngenes);
             pga_gene* d_genes = nullptr;
             if (ngenes > 0) {
-                DEVBUF(d_genes_out, pga_gene, "d_genes_out", ngenes + 1);
+                DEVBUF(d_genes_out, pga_gene, keep ? keep->buf : "d_genes_out", ngenes + 1);
                 d_genes = d_genes_out;
                 HT(c, hipMemcpyAsync(d_gbegin, h_gbegin, sizeof(int64_t) * NC, hipMemcpyHostToDevice, st));
                 GcPtrs gcs{};
                 for (int g = 0; g < NG; g++) gcs.p[g] = ga[g].gc_cont;
                 hipLaunchKernelGGL(k_emit_genes, dim3((unsigned)((n_slots + 255) / 256)), dim3(256), 0, st, d_td, NC, n_slots, o, d_gene2, d_ngenes,
                                    d_gbegin, P.meta ? 0 : 1, d_genes, lean_gather ? 1 : 0, ca, gcs);
-                if (!coding) HT(c, hipMemcpyAsync(genes_out, d_genes, sizeof(pga_gene) * (size_t)ngenes, hipMemcpyDeviceToHost, st));
+                if (genes_out) HT(c, hipMemcpyAsync(genes_out, d_genes, sizeof(pga_gene) * (size_t)ngenes, hipMemcpyDeviceToHost, st));
+                if (keep) { keep->d_genes = d_genes; keep->n_genes = ngenes; }
             }
             if (coding) {
                 // the coverage of the resident records: one bit per base of the batch, then a popcount per contig; NC counts come back
@@ -2655,10 +2662,13 @@ static int find_impl(pga_ctx* c, const pga_batch* batch, const pga_params* pp, c
 }
 
 #include "train.inl"
+#include "circular.inl"
 
 extern "C" int pga_find_genes(pga_ctx* c, const pga_batch* batch, const pga_params* pp, pga_result** out) {
     const auto t0 = std::chrono::steady_clock::now();
-    const int rc = find_impl(c, batch, pp, 0, 0, out, nullptr, nullptr);
+    const bool circular = c && batch && batch->ctx == c && !batch->circular.empty();
+    if (c) c->last_cuts.clear();
+    const int rc = circular ? find_circular(c, batch, pp, out, nullptr) : find_impl(c, batch, pp, 0, 0, out, nullptr, nullptr);
     if (getenv("PGA_TIMING")) fprintf(stderr, "[pga timing] pga_find_genes wall=%.2fms\n", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
     return rc;
 }
@@ -2683,6 +2693,8 @@ extern "C" int pga_find_genes_models(pga_ctx* c, const pga_batch* batch, const p
                      std::to_string(c->n_models) + " loaded";
             return PGA_EINVAL;
         }
+    c->last_cuts.clear();
+    if (batch->ctx == c && !batch->circular.empty()) return find_circular(c, batch, pp, out, model_of_contig);
     return find_impl(c, batch, pp, 0, 0, out, model_of_contig, nullptr);
 }
 
@@ -2766,7 +2778,12 @@ extern "C" int pga_batch_replicate(pga_ctx* c, const pga_batch* src, int32_t n, 
         if (e == hipSuccess) e = hipStreamSynchronize(st);
         if (e != hipSuccess) { batch_give_dev(c, b->d_seq, b->d_seq_cap); delete b; return pga_hip_try_(c, e, "replication of the batch"); }
     }
-    // the mask sources travel with the contigs
+    // the mask sources and the topology travel with the contigs
+    if (!src->circular.empty()) {
+        bool any = false;
+        for (int i = 0; i < n; i++) any = any || src->circular[contig_of_entry[i]];
+        if (any) { b->circular.resize((size_t)n); for (int i = 0; i < n; i++) b->circular[i] = src->circular[contig_of_entry[i]]; }
+    }
     b->mask_case = src->mask_case;
     if (!src->regions.empty()) {
         b->reg_off.assign((size_t)n + 1, 0);

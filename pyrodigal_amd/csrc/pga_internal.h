@@ -220,6 +220,7 @@ struct pga_ctx {
     char* render_host = nullptr; size_t render_host_cap = 0;
     unsigned long long* render_small = nullptr;
     DevNodes dev_nodes;                                // the last finder call's node arrays, when it kept them (want_nodes != 0)
+    std::vector<int32_t> last_cuts;                    // pga_circular_cuts: the cut of every contig of the last pga_find_genes / _models call (empty: all linear)
 };
 void pga_render_release(pga_ctx*);   // render.hip: frees the buffers above
 // summary of a segmented launch's flags (host copy, [PGA_SEG_ROUNDS][stride]) into pga_ctx::dp_stats

@@ -29,7 +29,7 @@
 #include <string>
 #include <vector>
 
-struct pga_batch_view { pga_ctx* ctx; int32_t n; int64_t total; const ContigDesc* ct; const char* d_seq; };
+struct pga_batch_view { pga_ctx* ctx; int32_t n; int64_t total; const ContigDesc* ct; const char* d_seq; const uint8_t* circular /* or nullptr: all linear */; };
 pga_batch_view pga_batch_peek(const pga_batch*);      // finder.hip
 
 namespace {
@@ -135,7 +135,7 @@ __device__ void gff_header(Sink& o, const RenderArgs& a, const int c) {
     o.puts("# Sequence Data: seqnum="); pga_fmt::put_i64(o, a.first_seqnum + c);
     o.puts(";seqlen="); pga_fmt::put_i64(o, a.ct[c].len);
     o.puts(";seqhdr=\""); put_id(o, a, c);
-    o.puts("\"\n# Model Data: version="); o.put_n(a.str + a.ver_off, a.ver_len);
+    o.puts(a.ct[c]._pad ? "\";topology=circular\n# Model Data: version=" : "\"\n# Model Data: version="); o.put_n(a.str + a.ver_off, a.ver_len);
     o.puts(a.meta ? ";run_type=Metagenomic;model=\"" : ";run_type=Single;model=\"");
     o.put_n(a.str + m.desc_off, m.desc_len);
     o.puts("\";gc_cont=");
@@ -235,6 +235,7 @@ __global__ void __launch_bounds__(256) k_fa_head(const RenderArgs a, const int p
     }
 }
 
+__device__ __forceinline__ int wrap_at(const int p, const int slen) { return p >= slen ? p - slen : p; }
 __device__ __forceinline__ char base_at(const char* s, const int64_t p, const bool comp) {
     char ch = s[p];
     if (ch >= 'a' && ch <= 'z') ch = (char)(ch - 32);
@@ -252,6 +253,7 @@ __global__ void __launch_bounds__(256) k_fa_body(const RenderArgs a, const int p
     const pga_gene g = a.genes[gi];
     const int c = g.contig;
     const char* __restrict__ s = a.seq + a.ct[c].base;
+    const int slen = a.ct[c].len;                     // a gene across the origin of a circular contig reads position p >= slen at p - slen
     const int L = (int)body_len(a, g, protein);       // < 2^31: a contig's length is an int32
     char* __restrict__ out = a.out + a.off[gi] + a.hdr_len[gi];
     const int w = a.width;
@@ -264,15 +266,16 @@ __global__ void __launch_bounds__(256) k_fa_body(const RenderArgs a, const int p
     for (int i = lane; i < L; i += 64) {
         char ch;
         if (!protein) {
-            ch = g.strand == 1 ? base_at(s, g.begin - 1 + i, false) : base_at(s, g.end - 1 - i, true);
+            const int p = g.strand == 1 ? g.begin - 1 + i : g.end - 1 - i;
+            ch = base_at(s, p >= slen ? p - slen : p, g.strand != 1);
         } else {
             int x0, x1, x2;
             if (g.strand == 1) {
                 const int p = g.begin - 1 + 3 * i;
-                x0 = pga_tr::digit_of(s[p], false); x1 = pga_tr::digit_of(s[p + 1], false); x2 = pga_tr::digit_of(s[p + 2], false);
+                x0 = pga_tr::digit_of(s[wrap_at(p, slen)], false); x1 = pga_tr::digit_of(s[wrap_at(p + 1, slen)], false); x2 = pga_tr::digit_of(s[wrap_at(p + 2, slen)], false);
             } else {
                 const int p = g.end - 1 - 3 * i;
-                x0 = pga_tr::digit_of(s[p], true); x1 = pga_tr::digit_of(s[p - 1], true); x2 = pga_tr::digit_of(s[p - 2], true);
+                x0 = pga_tr::digit_of(s[wrap_at(p, slen)], true); x1 = pga_tr::digit_of(s[wrap_at(p - 1, slen)], true); x2 = pga_tr::digit_of(s[wrap_at(p - 2, slen)], true);
             }
             ch = pga_tr::translate_codon(row, x0, x1, x2, tt, i, start_edge, a.strict, 'X');
         }
@@ -633,6 +636,9 @@ extern "C" int pga_render_genes(pga_ctx* c, const pga_batch* batch, const pga_co
     if (want_gbk && (!O.gbk_division || !O.gbk_date || !O.gbk_version)) BAD("missing GenBank strings (division, date, version)");
     if (!O.source || !O.version || (c->n_models > 0 && !O.model_desc)) BAD("missing tool strings");
     if (!(O.fallback_margin >= 0)) BAD("`fallback_margin` must be >= 0");
+    // circular contigs: their nodes live in the rotated contig's coordinates, and GenBank locations across the origin are the host writer's
+    if (bv.circular && want_sco) BAD("the start-score file is not written for circular contigs (the batch carries pga_batch_set_circular flags)");
+    if (bv.circular && want_gbk) BAD("GenBank records of circular contigs are written by the host writer (the batch carries pga_batch_set_circular flags)");
     // the start-score file reads the node arrays the last finder call kept on the device: only for that result and batch
     const DevNodes& DN = c->dev_nodes;
     if (want_sco) {
@@ -662,7 +668,9 @@ extern "C" int pga_render_genes(pga_ctx* c, const pga_batch* batch, const pga_co
     for (int i = 0; i < NC; i++)
         for (int64_t g = gbeg[i]; g < gbeg[i + 1]; g++) {
             const pga_gene& G = genes[g];
-            if (G.contig != i || G.begin < 1 || G.end > bv.ct[i].len || G.end < G.begin || G.rbs[0] >= 28 || G.rbs[1] >= 28)
+            const bool circ = bv.circular && bv.circular[i];  // a gene across the origin ends beyond the length, and is no longer than the circle
+            const bool inside = circ ? G.begin <= bv.ct[i].len && (int64_t)G.end - G.begin < bv.ct[i].len : G.end <= bv.ct[i].len;
+            if (G.contig != i || G.begin < 1 || !inside || G.end < G.begin || G.rbs[0] >= 28 || G.rbs[1] >= 28)
                 BAD("gene record outside its contig");
         }
     // models and the string arena: ids, then the model descriptions, the source and the version, the GenBank strings
@@ -758,7 +766,10 @@ extern "C" int pga_render_genes(pga_ctx* c, const pga_batch* batch, const pga_co
         for (int k = 0; k < 4 && e == hipSuccess; k++) e = hipEventCreate(&ev[f][k]);
     if (e != hipSuccess) return fail(e);
     if (n_genes > 0) e = hipMemcpyAsync(d + o_genes, genes, sizeof(pga_gene) * (size_t)n_genes, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(d + o_ct, bv.ct, sizeof(ContigDesc) * (NC + 1), hipMemcpyHostToDevice, st);
+    // (the copy of the contig table the kernels read carries the topology in its spare field: 1 = circular)
+    std::vector<ContigDesc> ctv(bv.ct, bv.ct + NC + 1);
+    if (bv.circular) for (int i = 0; i < NC; i++) ctv[i]._pad = bv.circular[i] ? 1 : 0;
+    if (e == hipSuccess) e = hipMemcpyAsync(d + o_ct, ctv.data(), sizeof(ContigDesc) * (NC + 1), hipMemcpyHostToDevice, st);
     if (e == hipSuccess) e = hipMemcpyAsync(d + o_gb, gbeg.data(), sizeof(int64_t) * (NC + 1), hipMemcpyHostToDevice, st);
     if (e == hipSuccess && NC > 0) e = hipMemcpyAsync(d + o_moc, model_of_contig, sizeof(int32_t) * NC, hipMemcpyHostToDevice, st);
     if (e == hipSuccess) e = hipMemcpyAsync(d + o_mod, models.data(), sizeof(RenderModel) * models.size(), hipMemcpyHostToDevice, st);

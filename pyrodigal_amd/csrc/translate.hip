@@ -9,7 +9,7 @@
 
 #include <vector>
 
-struct pga_batch_view { pga_ctx* ctx; int32_t n; int64_t total; const ContigDesc* ct; const char* d_seq; };
+struct pga_batch_view { pga_ctx* ctx; int32_t n; int64_t total; const ContigDesc* ct; const char* d_seq; const uint8_t* circular /* or nullptr: all linear */; };
 pga_batch_view pga_batch_peek(const pga_batch*);      // finder.hip
 
 namespace {
@@ -32,13 +32,15 @@ k_translate(const char* __restrict__ seq, const ContigDesc* __restrict__ ct, con
     const ContigDesc cd = ct[g.contig];
     const char* __restrict__ s = seq + cd.base;
     const int tt = tt_of[g.contig];
+    // a gene across the origin of a circular contig reads position p >= len at p - len (the host checked that only such genes get there)
+    auto at = [&](const int p) { return s[p >= cd.len ? p - cd.len : p]; };
     int x0, x1, x2;
     if (g.strand == 1) {
         const int p = g.begin - 1 + 3 * i;
-        x0 = digit_of(s[p], false); x1 = digit_of(s[p + 1], false); x2 = digit_of(s[p + 2], false);
+        x0 = digit_of(at(p), false); x1 = digit_of(at(p + 1), false); x2 = digit_of(at(p + 2), false);
     } else {
         const int p = g.end - 1 - 3 * i;
-        x0 = digit_of(s[p], true); x1 = digit_of(s[p - 1], true); x2 = digit_of(s[p - 2], true);
+        x0 = digit_of(at(p), true); x1 = digit_of(at(p - 1), true); x2 = digit_of(at(p - 2), true);
     }
     // partial flags are in sequence orientation; the gene's own first codon follows its strand
     const bool start_edge = g.strand == 1 ? g.partial_begin : g.partial_end;
@@ -73,7 +75,10 @@ extern "C" int pga_translate_genes(pga_ctx* c, const pga_batch* batch, int64_t n
     if (offsets[0] != 0) { c->err = "pga_translate_genes: offsets[0] must be 0"; return PGA_EINVAL; }
     for (int64_t g = 0; g < n_genes; g++) {
         const pga_gene& G = genes[g];
-        if (G.contig < 0 || G.contig >= bv.n || G.begin < 1 || G.end > bv.ct[G.contig].len || G.end < G.begin) { c->err = "pga_translate_genes: gene outside its contig"; return PGA_EINVAL; }
+        const bool circ = bv.circular && G.contig >= 0 && G.contig < bv.n && bv.circular[G.contig];
+        const bool inside = G.contig >= 0 && G.contig < bv.n &&
+                            (circ ? G.begin <= bv.ct[G.contig].len && (int64_t)G.end - G.begin < bv.ct[G.contig].len : G.end <= bv.ct[G.contig].len);
+        if (!inside || G.begin < 1 || G.end < G.begin) { c->err = "pga_translate_genes: gene outside its contig"; return PGA_EINVAL; }
         const bool stop_edge = G.strand == 1 ? G.partial_end : G.partial_begin;
         const int64_t want = (G.end - G.begin + 1) / 3 - ((!stop_edge && !include_stop) ? 1 : 0);
         if (offsets[g + 1] - offsets[g] != (want > 0 ? want : 0)) { c->err = "pga_translate_genes: offsets do not match the gene lengths"; return PGA_EINVAL; }

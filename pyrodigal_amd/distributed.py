@@ -73,10 +73,15 @@ def pack_contigs(work, world):
 def find_genes_sharded(ctx, seqs, dist=None, device=None, model_gcs=None, **kw):
     """``ctx.find_genes_batch`` over this rank's share of ``seqs`` (the same list on every rank), then one gather.
 
+    ``regions`` / ``circular`` (``Context.find_genes_batch``) are given for the whole job, one entry per contig.
     Returns (genes with global contig indices from every rank, this rank's BatchResult, this rank's contig indices)."""
     world = dist.get_world_size() if dist is not None and dist.is_initialized() else 1
     rank = dist.get_rank() if world > 1 else 0
     mine = pack_contigs(estimate_work(seqs, model_gcs), world)[rank]
+    for per_contig in ("regions", "circular"):          # one entry per contig of the job: this rank's share goes along
+        v = kw.get(per_contig)
+        if v is not None and not isinstance(v, bool):
+            kw[per_contig] = [v[i] for i in mine]
     res = ctx.find_genes_batch([seqs[i] for i in mine], **kw)
     genes = res.genes.copy()
     if len(genes):

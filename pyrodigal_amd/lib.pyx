@@ -119,6 +119,9 @@ cdef extern from "pyrodigal_amd.h" nogil:
     void pga_batch_free(pga_batch*)
     int pga_batch_set_regions(pga_batch*, const int32_t* off, const int32_t* iv)
     int pga_batch_set_mask_case(pga_batch*, int lower_case)
+    int pga_batch_set_circular(pga_batch*, const uint8_t* circular)
+    int pga_circular_cuts(const pga_ctx*, int32_t n, int32_t* out)
+    int pga_circular_cut(int32_t L, int32_t n, const int32_t* begin, const int32_t* end)
     int pga_batch_replicate(pga_ctx*, const pga_batch* src, int32_t n, const int32_t* contig_of_entry, pga_batch** out)
     int pga_find_coding_bases(pga_ctx*, const pga_batch*, const pga_params*, const int32_t* model_of_contig, int64_t* coding_bases,
                               int32_t* n_genes, double* score)
@@ -1177,10 +1180,19 @@ cdef class Gene:
     cpdef double confidence(self):
         return _confidence(self.g.cscore + self.g.sscore, self.owner.training_info.start_weight)
 
+    cdef bytes _span(self):
+        """The letters begin .. end of the record; a gene across the origin of a circular sequence (end > length) reads on at
+        the record's first base."""
+        cdef bytes data = self.owner.sequence.data
+        cdef ssize_t L = len(data)
+        if self.g.end > L and self.owner.circular:
+            return data[self.g.begin - 1:] + data[:self.g.end - L]
+        return data[self.g.begin - 1:self.g.end]
+
     def sequence(self):
         """The nucleotide sequence of the gene, reverse-complemented on the reverse strand; unknown bases read N
         (ref: lib.pyx:2874-2930)."""
-        cdef bytes s = self.owner.sequence.data[self.g.begin - 1:self.g.end].upper()
+        cdef bytes s = self._span().upper()
         s = bytes(c if c in b"ACGT" else 78 for c in s)
         if self.g.strand != 1:
             s = s.translate(_COMPLEMENT)[::-1]
@@ -1210,7 +1222,7 @@ cdef class Gene:
         if (self.owner._prot is not None and self._index >= 0 and tt == self.owner._prot_tt and unk == b"X" and include_stop and strict):
             # translated on the device together with the gene calls (GeneFinder.find_genes_batch(..., translate=True))
             return self.owner._prot[self.owner._prot_off[self._index]:self.owner._prot_off[self._index + 1]].decode("ascii")
-        cdef bytes nuc = self.owner.sequence.data[self.g.begin - 1:self.g.end]
+        cdef bytes nuc = self._span()
         if self.g.strand != 1:
             nuc = nuc.translate(_COMPLEMENT_ANY)[::-1]
         cdef bytes dig = nuc.translate(_DIGIT_OF)
@@ -1266,6 +1278,9 @@ cdef class Genes:
     cdef readonly bint meta
     cdef readonly double score
     cdef readonly ssize_t _num_seq
+    cdef readonly bint circular   # the sequence was called as a circle (find_genes(..., circular=True)): a gene may end beyond its length
+    cdef readonly object cut      # ... and where the finder cut it open for its second pass (0-based; node indices and `Node.index`
+                                  # are those of sequence[cut:] + sequence[:cut]); None for a linear sequence
     cdef list _genes           # the Gene objects, built from _recs when first asked for
     cdef bytes _recs           # the packed gene records of this sequence as the device call returned them
     cdef ssize_t _n
@@ -1332,7 +1347,8 @@ cdef class Genes:
         run = "Metagenomic" if self.meta else "Single"
         if header:
             n += file.write("##gff-version  3\n")
-        n += file.write('# Sequence Data: seqnum=%d;seqlen=%d;seqhdr="%s"\n' % (self._num_seq, len(self.sequence), sequence_id))
+        n += file.write('# Sequence Data: seqnum=%d;seqlen=%d;seqhdr="%s"%s\n' % (self._num_seq, len(self.sequence), sequence_id,
+                                                                                   ";topology=circular" if self.circular else ""))
         n += file.write('# Model Data: version=pyrodigal_amd.v%s;run_type=%s;model="%s";gc_cont=%.2f;transl_table=%d;uses_sd=%d\n'
                         % (_VERSION, run, desc, tinf.gc * 100, tinf.translation_table, int(tinf.uses_sd)))
         for i, gene in enumerate(self._list()):
@@ -1392,7 +1408,8 @@ cdef class Genes:
         elif not isinstance(date, datetime.date):
             raise TypeError("Expected datetime.date, found %s" % type(date).__name__)
         slen = len(self.sequence)
-        n += file.write("LOCUS       {:<23} {} bp    DNA     linear   {} {}\n".format(sequence_id, slen, division, date.strftime("%d-%b-%y").upper()))
+        n += file.write("LOCUS       {:<23} {} bp    DNA     {} {} {}\n".format(sequence_id, slen, "circular" if self.circular else "linear  ", division,
+                                                                            date.strftime("%d-%b-%y").upper()))
         n += file.write("REFERENCE   1  (bases 1 to %d)\n" % slen)
         n += file.write("  AUTHORS   Hyatt,D., Chen,G-L., LoCascio,P.F., Land,M.L., Larimer,F.W.\n")
         n += file.write("            Hauser,L.J.\n")
@@ -1407,6 +1424,8 @@ cdef class Genes:
             begin = "<%d" % gene.g.begin if start_edge else "%d" % gene.g.begin
             end = ">%d" % gene.g.end if stop_edge else "%d" % gene.g.end
             loc = "%s..%s" % (begin, end)
+            if self.circular and gene.g.end > slen:          # across the origin: two spans in the record's coordinates
+                loc = "join(%d..%d,1..%d)" % (gene.g.begin, slen, gene.g.end - slen)
             n += file.write("     CDS             %s\n" % (loc if gene.g.strand == 1 else "complement(%s)" % loc))
             pad = " " * 21
             n += file.write('%s/codon_start=1\n' % pad)
@@ -1429,6 +1448,9 @@ cdef class Genes:
     def write_scores(self, object file, str sequence_id, bint header=True):
         """Write the scores of every start node, grouped by stop codon, to `file` (ref: lib.pyx:3794-3894)."""
         cdef ssize_t n = 0
+        if self.circular:
+            raise ValueError("write_scores is not available for a circular sequence: its nodes live in the coordinates of the "
+                             "rotated sequence (Genes.cut)")
         if self.nodes is None:
             raise RuntimeError("write_scores needs the nodes: create the GeneFinder with keep_nodes=True")
         tinf, _ = self._model()
@@ -1500,6 +1522,7 @@ cdef class _FinderSlot:
 cdef class _FindRequest:
     """The sequences of one `find_genes` / `find_genes_batch` call, waiting for a device call to ride."""
     cdef list seqs              # Sequence objects
+    cdef list circ              # one bool per sequence: called as a circle; None: all linear
     cdef bint translate
     cdef ssize_t first_id
     cdef int64_t bases
@@ -1659,14 +1682,21 @@ cdef class GeneFinder:
         slot.models_sig = sig
         return 0
 
-    def find_genes(self, object sequence, object regions=None):
+    def find_genes(self, object sequence, object regions=None, bint circular=False):
         """Find all the genes in the input DNA sequence (ref: lib.pyx:5400-5469).
+
+        `circular=True`: the record is a circle cut open at an arbitrary base (a closed chromosome, a plasmid, a phage genome).
+        The linear call only serves to find the widest stretch without a gene in the record's middle half; the sequence is then
+        called again, closed, rotated to start in the middle of that stretch (`genes.cut`), and its genes are reported in the
+        record's coordinates: `1 <= begin <= len(sequence)`, and `end > len(sequence)` exactly for a gene across the origin, which
+        ends at base `end - len(sequence)`.  No gene of a circular sequence is partial.  `genes.nodes`, `Gene.start_node` and
+        `Gene.stop_node` are those of the rotated sequence.
 
         `regions`: `[begin, end)` intervals of the sequence (0-based; a `Masks`, or any iterable of `Mask` objects or pairs) that no
         gene may run across, exactly as if they were masked runs of `N` -- while the bases keep their identity for the GC content,
         the model choice, every score and the printed sequence.  They join the runs of unknown bases (`mask=True`), the runs of
         lower-case letters (`mask_lowercase=True`) and the regions a `Sequence` already carries; `genes.sequence.masks` is the union."""
-        return self.find_genes_batch([sequence], regions=None if regions is None else [regions])[0]
+        return self.find_genes_batch([sequence], regions=None if regions is None else [regions], circular=circular)[0]
 
     cdef _FinderSlot _free_slot(self):
         # a context that already exists first: a lone caller never makes a second one
@@ -1695,7 +1725,8 @@ cdef class GeneFinder:
         del self._pending[:k]
         return take
 
-    def find_genes_batch(self, object sequences, *, bint translate=False, object training_infos=None, object regions=None):
+    def find_genes_batch(self, object sequences, *, bint translate=False, object training_infos=None, object regions=None,
+                         object circular=None):
         """`find_genes` for many sequences in one device pass; returns one `Genes` per input, in order.
 
         `translate=True` also translates every gene on the device while the batch is resident (one thread per codon, the
@@ -1706,9 +1737,23 @@ cdef class GeneFinder:
         -- the result is that of `GeneFinder(training_infos[i], <same options>).find_genes(sequences[i])`, for many genomes
         under their own models in a few device calls.  The finder's own `training_info` is not used (nor needed) then.
 
-        `regions`: one entry per sequence, `None` or the regions of that sequence as `find_genes` takes them."""
+        `regions`: one entry per sequence, `None` or the regions of that sequence as `find_genes` takes them.
+
+        `circular`: `None` / `False` (every sequence is linear), `True` (every sequence is a circle) or one flag per sequence;
+        see `find_genes`.  Circular and linear sequences share a device call."""
+        cdef list circ = None
+        if circular is not None and circular is not False:
+            sequences = list(sequences)
+            if circular is True:
+                circ = [True] * len(sequences)
+            else:
+                circ = [bool(x) for x in circular]
+                if len(circ) != len(sequences):
+                    raise ValueError("`circular` has %d entries for %d sequences" % (len(circ), len(sequences)))
+            if not any(circ):
+                circ = None
         if training_infos is not None:
-            return self._find_genes_models(sequences, translate, training_infos, regions)
+            return self._find_genes_models(sequences, translate, training_infos, regions, circ)
         if not self.meta and self.training_info is None:
             raise RuntimeError("cannot find genes without having trained in single mode")
         # the reference always re-wraps with the finder's masking rule (ref: lib.pyx:5433-5438); a Sequence that already
@@ -1724,6 +1769,7 @@ cdef class GeneFinder:
         cdef _FinderSlot slot = None
         cdef list take
         req.seqs = seqs; req.translate = translate; req.bases = bases; req.out = None; req.error = None; req.done = False
+        req.circ = circ
         req.lead = None
         req.signaled = False
         req.sem = _new_lock()
@@ -1821,7 +1867,7 @@ cdef class GeneFinder:
             seqs.append(s)
         return seqs
 
-    def _find_genes_models(self, object sequences, bint translate, object training_infos, object regions=None):
+    def _find_genes_models(self, object sequences, bint translate, object training_infos, object regions=None, list circ=None):
         """`find_genes_batch(..., training_infos=...)`: single mode with a model per sequence (`pga_find_genes_models`).  The
         sequences go in device calls of at most `coalesce_bases` bases and four translation tables (what one context's model set
         holds); identical `TrainingInfo` objects are loaded once per call."""
@@ -1866,6 +1912,7 @@ cdef class GeneFinder:
             for idx in calls:
                 req = _FindRequest.__new__(_FindRequest)
                 req.seqs = [seqs[i] for i in idx]
+                req.circ = [circ[i] for i in idx] if circ is not None else None
                 req.first_id = first_id + idx[0]
                 out.extend(self._device_call(slot, req.seqs, translate, [req], [tinfs[i] for i in idx]))
                 with self._lock:
@@ -1947,6 +1994,9 @@ cdef class GeneFinder:
         cdef object moc = None
         cdef size_t p_moc = 0
         cdef bint masked = self.mask_lowercase       # a mask source beyond params.mask: the call goes through a resident batch
+        cdef object flags = None                     # uint8 per sequence, or None when no request of the call names a circle
+        cdef object cuts = None
+        cdef size_t p_flags = 0, p_cuts = 0
         if ptrs == NULL or lens == NULL:
             free(ptrs); free(lens)
             raise MemoryError()
@@ -1956,6 +2006,16 @@ cdef class GeneFinder:
         for r in take:
             for j in range(len(r.seqs)):
                 ids.append(r.first_id + j)
+            if r.circ is not None and flags is None:
+                flags = np.zeros(max(n, 1), np.uint8)
+        if flags is not None:
+            i = 0
+            for r in take:
+                if r.circ is not None:
+                    flags[i:i + len(r.seqs)] = r.circ
+                i += len(r.seqs)
+            cuts = np.full(max(n, 1), -1, np.int32)
+            p_flags = flags.ctypes.data; p_cuts = cuts.ctypes.data
         try:
             for i in range(n):
                 ptrs[i] = PyBytes_AS_STRING((<Sequence> seqs[i]).data)
@@ -1975,15 +2035,19 @@ cdef class GeneFinder:
                 try:
                     if masked:
                         _attach_masks(ctx, batch, seqs, self.mask_lowercase)
+                    if flags is not None:
+                        pga_batch_set_circular(batch, <const uint8_t*> p_flags)
                     with nogil:
                         rc = pga_find_genes_models(ctx, batch, &p, <const int32_t*> p_moc, &res)
                     if rc != PGA_OK:
                         _raise_for(ctx, rc, "pga_find_genes_models")
+                    if flags is not None:
+                        pga_circular_cuts(ctx, n, <int32_t*> p_cuts)
                     if translate:
                         prot, prot_off, tables = self._translate(ctx, batch, res, n, tinf_of)
                 finally:
                     pga_batch_free(batch)
-            elif not translate and not masked:
+            elif not translate and not masked and flags is None:
                 with nogil:
                     rc = pga_find_genes_batch(ctx, n, ptrs, lens, &p, &res)
                 if rc != PGA_OK:
@@ -1995,10 +2059,14 @@ cdef class GeneFinder:
                 try:
                     if masked:
                         _attach_masks(ctx, batch, seqs, self.mask_lowercase)
+                    if flags is not None:
+                        pga_batch_set_circular(batch, <const uint8_t*> p_flags)
                     with nogil:
                         rc = pga_find_genes(ctx, batch, &p, &res)
                     if rc != PGA_OK:
                         _raise_for(ctx, rc, "pga_find_genes")
+                    if flags is not None:
+                        pga_circular_cuts(ctx, n, <int32_t*> p_cuts)
                     if translate:
                         prot_off = np.zeros(res.n_genes + 1, np.int64)
                         prot, prot_off, tables = self._translate(ctx, batch, res, n, None)
@@ -2018,6 +2086,8 @@ cdef class GeneFinder:
                 genes.meta = self.meta
                 genes._num_seq = ids[i]
                 genes.score = cr.score
+                genes.circular = flags is not None and flags[i] != 0
+                genes.cut = int(cuts[i]) if genes.circular else None
                 if self.meta:
                     if cr.model >= 0:
                         genes.metagenomic_bin = self.metagenomic_bins[cr.model]
@@ -2684,3 +2754,43 @@ def _render_gene_line(str fmt, bytes rec, TrainingInfo training_info not None, s
     if include_translation_table:
         line += "transl_table=%d;" % training_info.translation_table
     return line + gene._score_data() + "\n"
+
+
+def _genes_from_records(object sequence, bytes recs, TrainingInfo training_info, ssize_t num_seq, bint meta=False,
+                        object metagenomic_bin=None, bint circular=False, object cut=None):
+    """A `Genes` over packed gene records of one sequence (a slice of a `pga_result`'s records, as bytes), for the host writers:
+    what a `GeneFinder` call returns for the sequence, without node arrays."""
+    if len(recs) % sizeof(pga_gene):
+        raise ValueError("a gene record is %d bytes" % sizeof(pga_gene))
+    cdef Genes genes = Genes.__new__(Genes)
+    genes.sequence = sequence if isinstance(sequence, Sequence) else Sequence(sequence)
+    genes.training_info = training_info
+    genes.metagenomic_bin = metagenomic_bin
+    genes.meta = meta
+    genes.score = 0.0
+    genes._num_seq = num_seq
+    genes.circular = circular
+    genes.cut = cut
+    genes._genes = None
+    genes._recs = recs
+    genes._n = len(recs) // sizeof(pga_gene)
+    genes._node_blob = None; genes._node_n = 0; genes._nodes = None
+    genes._prot = None; genes._prot_off = None; genes._prot_tt = 0
+    return genes
+
+
+def circular_cut(ssize_t length, object begins, object ends):
+    """Where a circular sequence of `length` bases whose linear call found genes `begins[k] .. ends[k]` (1-based, inclusive) is cut
+    open for its second pass (`pga_circular_cut`): the middle of the widest stretch no gene covers, in the middle half of the
+    record when there is one there."""
+    b = np.ascontiguousarray(begins, np.int32).reshape(-1)
+    e = np.ascontiguousarray(ends, np.int32).reshape(-1)
+    if b.size != e.size:
+        raise ValueError("%d begins for %d ends" % (b.size, e.size))
+    if length < 0 or length > 0x7fffffff:
+        raise ValueError("`length` must be a 32-bit length")
+    cdef size_t pb = b.ctypes.data, pe = e.ctypes.data
+    cdef int rc = pga_circular_cut(<int32_t> length, <int32_t> b.size, <const int32_t*> pb, <const int32_t*> pe)
+    if rc < 0:
+        raise ValueError("pga_circular_cut: bad arguments")
+    return rc

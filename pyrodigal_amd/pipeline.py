@@ -91,8 +91,31 @@ def _attach_masks(batch, ids, lens, regions_by_id, mask_lowercase, seen):
         batch.set_masks(regions, mask_lowercase)
 
 
+def circular_flags(circular, ids, descriptions, seen=None):
+    """One flag per record from ``circular``: ``None`` / ``False`` (none), ``True`` (every record), a collection of sequence ids,
+    or a predicate ``f(id, description)``.  ``seen`` collects the ids of a collection that were met.  Returns None when no
+    record of the batch is circular."""
+    if circular is None or circular is False:
+        return None
+    if circular is True:
+        return [True] * len(ids)
+    if callable(circular):
+        flags = [bool(circular(i, d)) for i, d in zip(ids, descriptions)]
+    else:
+        flags = [i in circular for i in ids]
+        if seen is not None:
+            seen.update(i for i, f in zip(ids, flags) if f)
+    return flags if any(flags) else None
+
+
+def header_says_circular(seq_id, description):
+    """The predicate of ``--circular-from-header``: the description holds ``circular=true`` or ``topology=circular``, any case."""
+    d = (description or "").lower()
+    return "circular=true" in d or "topology=circular" in d
+
+
 def find_genes_fasta(path, model_blobs, n_contexts=2, device=0, max_bases=64 << 20, contexts=None, regions_by_id=None,
-                     mask_lowercase=False, **find_kw):
+                     mask_lowercase=False, circular=None, **find_kw):
     """Genes of every record of a (gzipped) FASTA file: yields ``(ids, descriptions, lengths, BatchResult)`` per batch, in file order.
 
     The reader (C, zlib) parses batch k + 1 into a pinned staging arena while batch k is uploaded from its own arena with one
@@ -101,7 +124,9 @@ def find_genes_fasta(path, model_blobs, n_contexts=2, device=0, max_bases=64 << 
     across files (models loaded, device buffers grown) instead of `n_contexts` fresh ones.
 
     ``regions_by_id``: ``{sequence id: [(begin, end), ...]}``, masked regions (0-based, half-open) of the records with that id (the
-    first word of the header); ``mask_lowercase``: runs of lower-case letters are masked (``Batch.set_masks``)."""
+    first word of the header); ``mask_lowercase``: runs of lower-case letters are masked (``Batch.set_masks``).
+    ``circular``: the records that are circles, as :func:`circular_flags` takes them; their genes may end beyond the record's
+    length and ``BatchResult.cuts`` says where each was cut open."""
     seen = set()
     own = contexts is None             # `contexts`: contexts the caller keeps across files (models loaded, buffers grown)
     ctxs = [_cabi.Context(device) for _ in range(max(1, n_contexts))] if own else list(contexts)
@@ -124,6 +149,7 @@ def find_genes_fasta(path, model_blobs, n_contexts=2, device=0, max_bases=64 << 
                 b = ctx.upload_packed(pb)                 # releases the arena
                 try:
                     _attach_masks(b, meta[0], lens, regions_by_id, mask_lowercase, seen)
+                    b.set_circular(circular_flags(circular, meta[0], meta[1]))
                     res = (meta, ctx.find_genes(b, **find_kw))
                 finally:
                     b.close()
@@ -174,9 +200,34 @@ def find_genes_fasta(path, model_blobs, n_contexts=2, device=0, max_bases=64 << 
                 c.close()
 
 
+def _host_genbank(ctx, result, ids, letters, flags, options, meta, first_seqnum):
+    """The GenBank text of a batch that holds circular records, by the host writer (the device renderer does not write locations
+    across the origin): one ``Genes.write_genbank`` per record."""
+    import io
+    from . import lib
+    from ._cabi import RenderedText
+    tinfs = {}
+    out = io.StringIO()
+    offs = [0]
+    for i, c in enumerate(result.contigs):
+        m = int(c["model"]) if meta else 0
+        tinf = None
+        if m >= 0:
+            if m not in tinfs:
+                tinfs[m] = lib.TrainingInfo(raw=ctx._models[m].tobytes())
+            tinf = tinfs[m]
+        recs = result.genes[int(c["gene_begin"]):int(c["gene_begin"]) + int(c["n_genes"])].tobytes()
+        circ = bool(flags[i])
+        genes = lib._genes_from_records(letters[i], recs, tinf, first_seqnum + i, meta=meta, circular=circ,
+                                        cut=int(result.cuts[i]) if circ else None)
+        genes.write_genbank(out, ids[i], **options)
+        offs.append(len(out.getvalue().encode("utf-8")))
+    return RenderedText(out.getvalue().encode("utf-8"), offs, 0, 0.0)
+
+
 def render_fasta(path, model_blobs, *, gff=None, faa=None, fna=None, gbk=None, scores=None, n_contexts=2, device=0, max_bases=64 << 20,
                  meta=False, descriptions=None, first_seqnum=1, gff_options=None, faa_options=None, fna_options=None, gbk_options=None,
-                 scores_options=None, unbinned_model=None, regions_by_id=None, mask_lowercase=False, **find_kw):
+                 scores_options=None, unbinned_model=None, regions_by_id=None, mask_lowercase=False, circular=None, **find_kw):
     """Call the genes of every record of a FASTA file and write them as text: GFF to ``gff``, protein FASTA to ``faa``, gene
     FASTA to ``fna``, GenBank to ``gbk``, the start-score file to ``scores`` (binary file objects, or None), in file order --
     what ``Genes.write_gff`` / ``write_translations`` / ``write_genes`` / ``write_genbank`` / ``write_scores`` write record after
@@ -188,9 +239,16 @@ def render_fasta(path, model_blobs, *, gff=None, faa=None, fna=None, gbk=None, s
     bounded by the batch size.  Sequence ids are the first word of the headers, seqnums count records from ``first_seqnum``.
     ``*_options``: the writer's keyword arguments of that format; ``unbinned_model``: see ``Context.render_genes``; ``find_kw``
     goes to ``Context.find_genes``.  ``regions_by_id`` / ``mask_lowercase``: more mask sources, as :func:`find_genes_fasta` takes
-    them.  Returns ``{"records", "bases", "genes", "fallback", "kernel_ms": {format: ms}, "regions_unmatched": [ids of
-    regions_by_id that no record carried]}``."""
+    them.  ``circular``: the records that are circles (:func:`circular_flags`): called across the origin, ``topology=circular``
+    in their GFF header.  The start-score file cannot be written with them (``ValueError``); a GenBank batch that holds one is
+    written by the host writer ``Genes.write_genbank`` (``join()`` locations, ``LOCUS ... circular``), byte for byte what the
+    device writes for its linear records.  Returns ``{"records", "bases", "genes", "fallback", "kernel_ms": {format: ms},
+    "regions_unmatched": [ids of regions_by_id that no record carried], "circular_unmatched": [ids of a ``circular`` collection
+    that no record carried]}``."""
     seen = set()
+    seen_circular = set()
+    if scores is not None and circular is not None and circular is not False:
+        raise ValueError("render_fasta: the start-score file is not written for circular records")
     formats = {}
     for name, fh, opts in (("gff", gff, gff_options), ("faa", faa, faa_options), ("fna", fna, fna_options), ("gbk", gbk, gbk_options),
                            ("scores", scores, scores_options)):
@@ -220,12 +278,21 @@ def render_fasta(path, model_blobs, *, gff=None, faa=None, fna=None, gbk=None, s
             try:
                 ids, n, total = pb.ids, pb.n, pb.total
                 lens = [int(x) for x in pb.lens[:pb.n]]
+                flags = circular_flags(circular, ids, pb.descriptions, seen_circular)
+                host_gbk = flags is not None and "gbk" in formats
+                letters = [pb.sequence(k) for k in range(n)] if host_gbk else None     # (the arena is released by the upload)
                 b = ctx.upload_packed(pb)                 # releases the arena
                 try:
                     _attach_masks(b, ids, lens, regions_by_id, mask_lowercase, seen)
+                    b.set_circular(flags)
                     r = ctx.find_genes(b, meta=meta, want_nodes=want_nodes, **find_kw)
-                    text = ctx.render_genes(b, r, ids, formats, meta=meta, descriptions=descriptions, first_seqnum=seqnum,
-                                            unbinned_model=unbinned_model)
+                    dev_formats = {k: v for k, v in formats.items() if not (host_gbk and k == "gbk")}
+                    text = {}
+                    if dev_formats:
+                        text = ctx.render_genes(b, r, ids, dev_formats, meta=meta, descriptions=descriptions, first_seqnum=seqnum,
+                                                unbinned_model=unbinned_model)
+                    if host_gbk:
+                        text["gbk"] = _host_genbank(ctx, r, ids, letters, flags, formats["gbk"], meta, seqnum)
                 finally:
                     b.close()
                 res = (n, total, len(r.genes), text)
@@ -271,6 +338,8 @@ def render_fasta(path, model_blobs, *, gff=None, faa=None, fna=None, gbk=None, s
                 stats["kernel_ms"][name] += t.kernel_ms
             stats["records"] += n; stats["bases"] += total; stats["genes"] += n_genes
         stats["regions_unmatched"] = sorted(set(regions_by_id or ()) - seen)
+        listed = circular if circular is not None and not isinstance(circular, bool) and not callable(circular) else ()
+        stats["circular_unmatched"] = sorted(set(listed) - seen_circular)
         return stats
     finally:
         for _ in threads:
