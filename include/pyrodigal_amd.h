@@ -247,6 +247,29 @@ int  pga_batch_set_circular(pga_batch*, const uint8_t* circular /* n flags, or N
 /* The cut of every contig of the last pga_find_genes / pga_find_genes_models call on the context: out[i] for i < n, -1 for a linear
  * contig (and for every contig when the batch carried no flag). */
 int  pga_circular_cuts(const pga_ctx*, int32_t n, int32_t* out);
+/* Contig sets, one more attribute of the resident batch (meta mode): set_of_contig[i] >= 0 labels contig i as a member of that set of
+ * contigs known to be one organism (the bins of a binner, the contigs of a draft genome, the segments of a virus); -1 leaves it on its
+ * own.  Labels need not be dense, and the members of a set need not be adjacent in the batch.  NULL clears the labels.
+ * pga_find_genes with params->meta = 1 then chooses ONE model per set:
+ *   1. the GC window of every member is that of gc_A = (sum of the members' G+C counts) / (sum of their lengths), 0.0 for an empty
+ *      set; every member is scored under every model of that window, in model order (contigs[i].gc stays the member's own);
+ *   2. a member contributes under model m iff it has nodes and a path there, and contributes that path's score;
+ *   3. S_m is the sum of the contributions under m, added as doubles in batch order; the set's model W is the one with the largest
+ *      S_m among those with S_m > -100.0, the lowest index among equals;
+ *   4. a member that contributed under W gets exactly the result of a contig whose winner is W (genes, node arrays, translation
+ *      table); any other member, and every member of a set without W, has no genes and model -1.
+ * A set of one contig, labelled or not, is the ordinary meta-mode call, bit for bit; a batch without labels runs the ordinary code.
+ * Refused with PGA_EINVAL: labels below -1; a labelled batch with params->meta = 0 (pga_find_genes); a batch that carries both labels
+ * and circular flags (pass 2 of a circular call holds only the circular members, so a set's sums would change their meaning).
+ * pga_batch_replicate carries the labels; pga_find_genes_models, training, pga_nodes_stage and pga_find_coding_bases ignore them.
+ * Not to be called while a call on the batch runs. */
+int  pga_batch_set_sets(pga_batch*, const int32_t* set_of_contig /* n entries, or NULL */);
+/* The choice of the last pga_find_genes call on the context, when its batch carried labels: per contig i < n the model W of its set
+ * (-1: none) and S_W (NaN: none).  -1 / NaN for every contig after a call without labels. */
+int  pga_set_choice(const pga_ctx*, int32_t n, int32_t* model, double* score);
+/* The contributions behind that choice: out[i * n_models + m] is the path score of contig i under model m, NaN where it did not
+ * contribute (m outside its set's window, no nodes, no path) and everywhere after a call without labels. */
+int  pga_model_scores(const pga_ctx*, int32_t n_contigs, int32_t n_models, double* out);
 /* Step 2 above (host arithmetic only): genes begin[k]..end[k], 1-based inclusive, either strand, any order, on a contig of L bases.
  * A gap is a maximal run of positions no gene covers, [gb, ge) 0-based, mid = (gb + ge) / 2.  Among the gaps with
  * L / 4 <= mid < L - L / 4 (all gaps if there is none) the widest wins, then the smallest |mid - L / 2|, then the lowest mid;
@@ -357,6 +380,10 @@ int  pga_render_genes(pga_ctx*, const pga_batch*, const pga_contig_result* conti
                       const int32_t* model_of_contig, const char* ids, const int64_t* id_off, const pga_render_opts* opts,
                       pga_render_result** out);
 void pga_render_free(pga_render_result*);
+/* The records of a batch need not be consecutive records of their file (contig sets are packed into device calls set by set):
+ * while seqnum (n entries) is attached to the context, pga_render_genes on a batch of n contigs prints seqnum[i] for contig i in
+ * place of opts->first_seqnum + i.  NULL detaches it. */
+int  pga_render_seqnums(pga_ctx*, int32_t n, const int64_t* seqnum /* n entries, or NULL */);
 
 /* ---- training --------------------------------------------------------------- */
 /* Single-genome training (ref: lib.pyx:5236-5279 `GeneFinder._train`): `batch` holds exactly ONE sequence (several

@@ -24,6 +24,7 @@ EXPORTS = [
     "pga_batch_replicate", "pga_find_coding_bases",
     "pga_batch_set_regions", "pga_batch_set_mask_case",
     "pga_batch_set_circular", "pga_circular_cuts", "pga_circular_cut",
+    "pga_batch_set_sets", "pga_set_choice", "pga_model_scores", "pga_render_seqnums",
 ]
 STAGE_EXTRACT, STAGE_SCORE, STAGE_OVERLAP, STAGE_SEQUENCE = 1, 2, 3, 4
 
@@ -143,6 +144,10 @@ def load():
     L.pga_batch_set_circular.restype = ctypes.c_int; L.pga_batch_set_circular.argtypes = [vp, vp]
     L.pga_circular_cuts.restype = ctypes.c_int; L.pga_circular_cuts.argtypes = [vp, i32, vp]
     L.pga_circular_cut.restype = ctypes.c_int; L.pga_circular_cut.argtypes = [i32, i32, vp, vp]
+    L.pga_batch_set_sets.restype = ctypes.c_int; L.pga_batch_set_sets.argtypes = [vp, vp]
+    L.pga_set_choice.restype = ctypes.c_int; L.pga_set_choice.argtypes = [vp, i32, vp, vp]
+    L.pga_model_scores.restype = ctypes.c_int; L.pga_model_scores.argtypes = [vp, i32, i32, vp]
+    L.pga_render_seqnums.restype = ctypes.c_int; L.pga_render_seqnums.argtypes = [vp, i32, vp]
     L.pga_find_coding_bases.restype = ctypes.c_int; L.pga_find_coding_bases.argtypes = [vp, vp, _P(Params), vp, vp, vp, vp]
     L.pga_nodes_stage.restype = ctypes.c_int
     L.pga_nodes_stage.argtypes = [vp, vp, _P(Params), ctypes.c_int, ctypes.c_int, _P(_P(Result))]
@@ -369,6 +374,9 @@ class BatchResult:
         self.cuts = cuts            # int32 per contig: where a circular contig was cut open (-1: linear), or None when the batch has no flag
         self.masks = masks          # per contig an (k, 2) array of [begin, end) intervals, or None when masking is off
         self.t_total_ms, self.t_dp_ms, self.node_passes, self.n_chains = t_total_ms, t_dp_ms, node_passes, n_chains
+        # contig sets (Batch.set_sets), None when the batch carried no labels: per contig the model chosen for its set (-1: none) and
+        # that model's summed score (NaN: none); [contig][model] the path score a contig contributed (NaN: none)
+        self.set_models = self.set_scores = self.model_scores = None
 
     def genes_of(self, i):
         c = self.contigs[i]
@@ -417,6 +425,20 @@ def pack_regions(regions, n):
     return off, np.ascontiguousarray(np.concatenate(flat), dtype=np.int32)
 
 
+def dense_set_ids(labels, n):
+    """Set labels (one per sequence: any hashable, ``None`` or -1 for a sequence on its own) as the int32 array
+    ``pga_batch_set_sets`` takes: dense ids in order of first appearance, -1 for the unlabelled."""
+    labels = list(labels)
+    if len(labels) != n:
+        raise ValueError(f"sets has {len(labels)} entries for {n} sequences")
+    ids, seen = np.full(max(n, 1), -1, np.int32), {}
+    for i, lab in enumerate(labels):
+        if lab is None or (isinstance(lab, (int, np.integer)) and not isinstance(lab, bool) and lab == -1):
+            continue
+        ids[i] = seen.setdefault(lab, len(seen))
+    return ids[:n] if n else ids[:0]
+
+
 class Batch:
     """Contigs packed and resident in HBM (``pga_batch``)."""
 
@@ -455,6 +477,20 @@ class Batch:
         if rc != PGA_OK:
             _raise(self.ctx.L, self.ctx.h, rc, "pga_batch_set_circular")
         self.circular = flags
+        return self
+
+    sets = None         # the dense ids of set_sets (int32 per contig, -1: on its own), or None: no labels
+
+    def set_sets(self, labels=None):
+        """Label contigs as members of sets that are known to be one organism (``pga_batch_set_sets``): one label per contig, any
+        hashable, ``None`` (or -1) for a contig on its own; ``labels=None`` clears them.  Labels become dense ids in order of first
+        appearance.  A meta-mode ``find_genes`` then chooses one model per set and reports ``set_models`` / ``set_scores`` /
+        ``model_scores``."""
+        ids = None if labels is None else dense_set_ids(labels, self.n)
+        rc = self.ctx.L.pga_batch_set_sets(self.h, None if ids is None else ctypes.c_void_p(ids.ctypes.data))
+        if rc != PGA_OK:
+            _raise(self.ctx.L, self.ctx.h, rc, "pga_batch_set_sets")
+        self.sets = ids
         return self
 
     def __init__(self, ctx, seqs):
@@ -618,6 +654,16 @@ def _find_genes(self, batch, meta=True, closed=False, min_gene=90, min_edge_gene
         if rc != PGA_OK:
             _raise(self.L, self.h, rc, "pga_circular_cuts")
         out.cuts = cuts[:batch.n]
+    if batch.sets is not None and model_of_contig is None:
+        n, nm = batch.n, len(self._models)
+        sm, ss = np.full(max(n, 1), -1, np.int32), np.full(max(n, 1), np.nan, np.float64)
+        ms = np.full(max(n * nm, 1), np.nan, np.float64)
+        rc = self.L.pga_set_choice(self.h, n, ctypes.c_void_p(sm.ctypes.data), ctypes.c_void_p(ss.ctypes.data))
+        if rc == PGA_OK:
+            rc = self.L.pga_model_scores(self.h, n, nm, ctypes.c_void_p(ms.ctypes.data))
+        if rc != PGA_OK:
+            _raise(self.L, self.h, rc, "pga_set_choice")
+        out.set_models, out.set_scores, out.model_scores = sm[:n], ss[:n], ms[:n * nm].reshape(n, nm)
     return out
 
 
@@ -633,6 +679,8 @@ def _replicate(self, batch, contig_of_entry):
     b.total = None
     if batch.circular is not None and batch.circular[coe].any():        # the flags travel with the contigs
         b.circular = np.ascontiguousarray(batch.circular[coe])
+    if batch.sets is not None:                                           # and so do the set labels
+        b.sets = np.ascontiguousarray(batch.sets[coe])
     return b
 
 
@@ -653,12 +701,15 @@ def _find_coding_bases(self, batch, model_of_contig, closed=False, min_gene=90, 
     return cov[:batch.n], ng[:batch.n], sc[:batch.n]
 
 
-def _find_genes_batch(self, seqs, regions=None, mask_lowercase=False, circular=None, **kw):
+def _find_genes_batch(self, seqs, regions=None, mask_lowercase=False, circular=None, sets=None, **kw):
     """Upload + find + free: ``seqs`` is a list of ASCII ``bytes``/``str`` contigs.  ``regions`` (one entry per contig: ``None`` or
     ``(begin, end)`` pairs) and ``mask_lowercase`` are more mask sources (:meth:`Batch.set_masks`); ``masks`` of the result is their
-    union with the runs of unknown bases of ``mask=True``.  ``circular``: as :meth:`Batch.set_circular` takes it."""
+    union with the runs of unknown bases of ``mask=True``.  ``circular``: as :meth:`Batch.set_circular` takes it; ``sets``: as
+    :meth:`Batch.set_sets` takes it (meta mode)."""
     b = Batch(self, seqs)
     try:
+        if sets is not None:
+            b.set_sets(sets)
         if regions is not None or mask_lowercase:
             b.set_masks(regions, mask_lowercase)
         if circular is not None and circular is not False:
@@ -839,12 +890,13 @@ def _render_formats(formats, writer_options):
 
 
 def _render_genes(self, batch, result, ids, formats=RENDER_FORMATS, *, meta=False, model_of_contig=None, descriptions=None,
-                  first_seqnum=1, fallback_margin=1e-9, unbinned_model=None, **writer_options):
+                  first_seqnum=1, fallback_margin=1e-9, unbinned_model=None, seqnums=None, **writer_options):
     """GFF / protein FASTA / gene FASTA of ``result`` (a result of ``find_genes`` on the resident ``batch``), rendered on the
     device: byte for byte what ``Genes.write_gff`` / ``write_translations`` / ``write_genes`` write for these genes, contig
     after contig.
 
-    ``ids``: the sequence id of every contig; ``first_seqnum``: the seqnum of contig 0.  ``formats``: names among "gff", "faa",
+    ``ids``: the sequence id of every contig; ``first_seqnum``: the seqnum of contig 0 (``seqnums``: one per contig instead, for a
+    batch whose contigs are not consecutive records of their file).  ``formats``: names among "gff", "faa",
     "fna", or a dict from those names to the writer's keyword arguments (``header``, ``include_translation_table``, ``full_id``,
     ``version_separator`` / ``width``, ``translation_table``, ``include_stop``, ``strict_translation``, ``full_id`` /
     ``width``, ``full_id``); ``writer_options`` apply to every format that takes them.  ``meta``: the models are metagenomic
@@ -917,8 +969,17 @@ def _render_genes(self, batch, result, ids, formats=RENDER_FORMATS, *, meta=Fals
     if "scores" in fmt_opts:
         o.sco_header = int(bool(fmt_opts["scores"]["header"]))
     res = _P(RenderResult)()
-    rc = self.L.pga_render_genes(self.h, batch.h, contigs.ctypes.data, len(genes), genes.ctypes.data if len(genes) else None,
-                                 moc.ctypes.data, id_arena or None, id_off.ctypes.data, ctypes.byref(o), ctypes.byref(res))
+    if seqnums is not None:
+        seqnums = np.ascontiguousarray(seqnums, np.int64)
+        if seqnums.shape != (n,):
+            raise ValueError("%d seqnums for %d contigs" % (seqnums.size, n))
+        self.L.pga_render_seqnums(self.h, n, ctypes.c_void_p(seqnums.ctypes.data))
+    try:
+        rc = self.L.pga_render_genes(self.h, batch.h, contigs.ctypes.data, len(genes), genes.ctypes.data if len(genes) else None,
+                                     moc.ctypes.data, id_arena or None, id_off.ctypes.data, ctypes.byref(o), ctypes.byref(res))
+    finally:
+        if seqnums is not None:
+            self.L.pga_render_seqnums(self.h, 0, None)
     if rc != PGA_OK:
         _raise(self.L, self.h, rc, "pga_render_genes")
     try:
@@ -935,7 +996,7 @@ def _render_genes(self, batch, result, ids, formats=RENDER_FORMATS, *, meta=Fals
                 raise PgaError("pga_render_genes: %d %s line(s) hold a value the device cannot print exactly" % (nf, name))
             if nf:
                 fb = np.ctypeslib.as_array(t.fallback, (3 * nf,)).reshape(nf, 3).copy()
-                data, coff = _splice_fallback(self, name, fmt_opts[name], data, coff, fb, genes, contigs, moc, ids, first_seqnum)
+                data, coff = _splice_fallback(self, name, fmt_opts[name], data, coff, fb, genes, contigs, moc, ids, first_seqnum, seqnums)
             out[name] = RenderedText(data, coff, nf, float(r.t_kernels_ms[k]))
         return out
     finally:
@@ -948,7 +1009,7 @@ def _width(w):
     return int(w)
 
 
-def _splice_fallback(ctx, name, opts, data, coff, fb, genes, contigs, moc, ids, first_seqnum):
+def _splice_fallback(ctx, name, opts, data, coff, fb, genes, contigs, moc, ids, first_seqnum, seqnums=None):
     """The lines the device flagged, rendered by the host writers' own code and put in place of the device's guesses."""
     from . import lib
     tinfs = {}
@@ -960,7 +1021,7 @@ def _splice_fallback(ctx, name, opts, data, coff, fb, genes, contigs, moc, ids, 
         m = int(moc[c])
         if m not in tinfs:
             tinfs[m] = lib.TrainingInfo(raw=ctx._models[m].tobytes())
-        line = lib._render_gene_line(name, genes[gi:gi + 1].tobytes(), tinfs[m], ids[c], first_seqnum + c,
+        line = lib._render_gene_line(name, genes[gi:gi + 1].tobytes(), tinfs[m], ids[c], first_seqnum + c if seqnums is None else int(seqnums[c]),
                                      gi - int(contigs["gene_begin"][c]), full_id=opts["full_id"],
                                      include_translation_table=opts.get("include_translation_table", False),
                                      version_separator=opts.get("version_separator", "_v"))

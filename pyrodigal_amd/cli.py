@@ -65,7 +65,35 @@ def argument_parser(prog="pyrodigal_amd"):
                    help="The records whose id (first word of the FASTA header) is listed in this file, one per line, are circular.")
     p.add_argument("--circular-from-header", action="store_true", default=False,
                    help="The records whose header says circular=true or topology=circular (any letter case) are circular.")
+    p.add_argument("--bin-map", metavar="FILE",
+                   help="With -p meta: choose one model per set of contigs. Tab-separated seqid, bin -- the contig-to-bin table a "
+                        "binner writes (seqid is the first word of the FASTA header); # lines are ignored, a sequence that is not "
+                        "listed is on its own. The input is read whole: a set must sit in one device call.")
     return p
+
+
+def parse_bin_map(lines, name="<bin map>"):
+    """``{seqid: bin}`` of a contig-to-bin table (an iterable of lines): tab-separated ``seqid  bin``; blank lines and ``#`` lines
+    are ignored.  A malformed line, or a sequence listed under two bins, is a ``ValueError`` that names the line."""
+    bins = {}
+    for no, line in enumerate(lines, 1):
+        if isinstance(line, bytes):
+            line = line.decode("utf-8", "replace")
+        text = line.rstrip("\r\n")
+        if not text.strip() or text.startswith("#"):
+            continue
+        cols = text.split("\t")
+        if len(cols) != 2 or not cols[0].strip() or not cols[1].strip():
+            raise ValueError("%s, line %d: expected seqid<TAB>bin, found %r" % (name, no, text))
+        seqid, label = cols[0].strip(), cols[1].strip()
+        if bins.setdefault(seqid, label) != label:
+            raise ValueError("%s, line %d: sequence %r is listed under bin %r and bin %r" % (name, no, seqid, bins[seqid], label))
+    return bins
+
+
+def read_bin_map(path):
+    with open(path, "r", encoding="utf-8", errors="replace") as fh:
+        return parse_bin_map(fh, path)
 
 
 def parse_circular_ids(lines):
@@ -158,6 +186,11 @@ def _check(args):
         return "--batch-bases must be at least 1."
     if args.s is not None and (args.circular or args.circular_ids is not None or args.circular_from_header):
         return "-s cannot be combined with --circular, --circular-ids or --circular-from-header: the start file is not written for circular sequences."
+    if args.bin_map is not None and args.p != "meta":
+        return "--bin-map needs -p meta: one model per set of contigs is a choice among the metagenomic bins."
+    if args.bin_map is not None and (args.circular or args.circular_ids is not None or args.circular_from_header):
+        return ("--bin-map cannot be combined with --circular, --circular-ids or --circular-from-header: the second pass of a circular "
+                "call holds only the circular members of a set.")
     return None
 
 
@@ -190,6 +223,12 @@ def main(argv=None, stdout=None, stderr=None):
         print("Error: --circular-ids: %s" % e, file=stderr)
         return 1
     mask_kw = dict(regions_by_id=regions, mask_lowercase=args.mask_lowercase, circular=circular)
+    if args.bin_map is not None:
+        try:
+            mask_kw["sets_by_id"] = read_bin_map(args.bin_map)
+        except (OSError, ValueError) as e:
+            print("Error: --bin-map: %s" % e, file=stderr)
+            return 1
     with contextlib.ExitStack() as stack:
         path = args.i
         if path is None:                        # stdin: the reader needs a file it can sniff and map
@@ -237,6 +276,8 @@ def main(argv=None, stdout=None, stderr=None):
                              faa_options={"include_stop": not args.no_stop_codon}, unbinned_model=unbinned, **mask_kw, **find_kw)
         for rid in stats.get("regions_unmatched", ()):
             print("Warning: --mask-regions: no sequence %r in the input" % rid, file=stderr)
+        for rid in stats.get("sets_unmatched", ()):
+            print("Warning: --bin-map: no sequence %r in the input" % rid, file=stderr)
         unmatched = stats.get("circular_unmatched", ())
         if isinstance(circular, _ListedOrHeader):
             unmatched = sorted(circular.ids - circular.seen)

@@ -20,11 +20,13 @@
 #include <chrono>
 #include <condition_variable>
 #include <functional>
+#include <limits>
 #include <map>
 #include <memory>
 #include <mutex>
 #include <new>
 #include <thread>
+#include <unordered_map>
 
 namespace {
 
@@ -1133,6 +1135,8 @@ struct pga_batch {
     MaskRun* d_regions = nullptr;     // their device copy
     // topology (pga_batch_set_circular): one flag per contig, empty: every contig is linear
     std::vector<uint8_t> circular;
+    // contig sets (pga_batch_set_sets): the caller's label per contig, -1: on its own; empty: no labels
+    std::vector<int32_t> sets;
 };
 
 // Tiles of a batch: every position of a contig of at least three bases lies in one tile.  Host vectors for one upload.
@@ -1489,6 +1493,7 @@ static int find_impl_cov(pga_ctx* c, const pga_batch* batch, const pga_params* p
     const int32_t n_contigs = batch->n;
     if (!c->finder) { int rc0 = pga_finder_models_changed(c); if (rc0) return rc0; }
     const bool meta_run = pp->meta && stage == 0;
+    const bool use_sets = meta_run && !batch->sets.empty();      // one GC window and one model per set of contigs
     const bool per_contig = model_of_contig != nullptr && !pp->meta && stage != PGA_STAGE_EXTRACT && stage != PGA_STAGE_SEQUENCE;
     const bool per_contig_tt = tt_of_contig != nullptr && stage == PGA_STAGE_EXTRACT;
     // meta mode over an empty bin collection is legal and finds nothing (ref: tests/test_gene_finder.py:316-324)
@@ -1529,6 +1534,25 @@ static int find_impl_cov(pga_ctx* c, const pga_batch* batch, const pga_params* p
         // diagnostics: a call that carries a contig of exactly this many bases fails (the host layer's error paths under test)
         const long fl = atol(fault);
         for (int i = 0; i < NC; i++) if ((long)batch->ct[i].len == fl) { c->err = "pga_find_genes: fault injected by PGA_FAULT_CONTIG_LEN"; return PGA_EDEVICE; }
+    }
+
+    // contig sets: dense ids in order of first appearance, a contig without a label a set of its own
+    std::vector<int32_t> set_of;
+    int NS = 0;
+    if (use_sets) {
+        set_of.resize((size_t)NC);
+        std::unordered_map<int32_t, int32_t> dense;
+        for (int i = 0; i < NC; i++) {
+            const int32_t lab = batch->sets[(size_t)i];
+            if (lab < 0) { set_of[(size_t)i] = NS++; continue; }
+            auto it = dense.find(lab);
+            if (it == dense.end()) it = dense.emplace(lab, NS++).first;
+            set_of[(size_t)i] = it->second;
+        }
+        c->set_model.assign((size_t)NC, -1);
+        c->set_score.assign((size_t)NC, std::numeric_limits<double>::quiet_NaN());
+        c->model_scores.assign((size_t)NC * (size_t)NM, std::numeric_limits<double>::quiet_NaN());
+        c->model_scores_nm = NM;
     }
 
     ResultOwner* R = new (std::nothrow) ResultOwner();
@@ -1644,7 +1668,14 @@ static int find_impl_cov(pga_ctx* c, const pga_batch* batch, const pga_params* p
             return publish(R, guard.r, P, out);
         }
         // meta mode: a contig is extracted under a translation table only if a model with that table lies in its GC window
-        if (meta_run && NM > 0) pga_launch_group_enable(d_ct, NC, d_cnt, f->d_model_gc, f->d_model_grp, NM, NG, d_enabled, st);
+        // (contig sets: in its SET's window -- the labels go up, two integers per set are summed on the device)
+        if (meta_run && NM > 0 && use_sets) {
+            DEVBUF(d_set_of, int32_t, "d_set_of", 3 * (size_t)NC + 1);      // the dense ids, then the pooled (G+C count, length) pairs
+            HT(c, hipMemcpyAsync(d_set_of, set_of.data(), sizeof(int32_t) * (size_t)NC, hipMemcpyHostToDevice, st));
+            pga_launch_group_enable_sets(d_ct, NC, d_cnt, d_set_of, d_set_of + NC, f->d_model_gc, f->d_model_grp, NM, NG, d_enabled, st);
+        } else if (meta_run && NM > 0) {
+            pga_launch_group_enable(d_ct, NC, d_cnt, f->d_model_gc, f->d_model_grp, NM, NG, d_enabled, st);
+        }
         // per-contig models: a contig is extracted under its own model's translation table only
         if (multi) {
             for (int g = 0; g < NG; g++) for (int i = 0; i < NC; i++) h_enabled[(size_t)g * NC + i] = cgrp[i] == g;
@@ -1708,9 +1739,17 @@ static int find_impl_cov(pga_ctx* c, const pga_batch* batch, const pga_params* p
         std::vector<double> mgc((size_t)NM); std::vector<int> mtt((size_t)NM);     // the models are 558 KB apart: keep what the loop reads together
         for (int m = 0; m < NM; m++) { mgc[m] = c->models[m].gc; mtt[m] = c->models[m].trans_table; }
         for (int g = 0; g < NG; g++) gch[g].reserve(meta_run ? (size_t)NC * 6 : (size_t)NC);
+        // contig sets: the same pooled numbers the device summed (integers, exact), one division per set
+        std::vector<double> set_gc;
+        if (use_sets) {
+            std::vector<int64_t> sum((size_t)2 * NS, 0);
+            for (int i = 0; i < NC; i++) { sum[2 * (size_t)set_of[i]] += h_cnt[i]; sum[2 * (size_t)set_of[i] + 1] += ct[i].len; }
+            set_gc.resize((size_t)NS);
+            for (int s = 0; s < NS; s++) set_gc[(size_t)s] = sum[2 * (size_t)s + 1] > 0 ? (double)sum[2 * (size_t)s] / (double)sum[2 * (size_t)s + 1] : 0.0;
+        }
         for (int i = 0; i < NC; i++) {
             const int L = ct[i].len;
-            const double gc = L > 0 ? (double)h_cnt[i] / (double)L : 0.0;
+            double gc = L > 0 ? (double)h_cnt[i] / (double)L : 0.0;
             R->contigs[i].gc = gc;
             R->contigs[i].n_unknown = h_cnt[NC + i];
             if (!meta_run) {
@@ -1721,6 +1760,7 @@ static int find_impl_cov(pga_ctx* c, const pga_batch* batch, const pga_params* p
                 gch[g].push_back(ch);
                 continue;
             }
+            if (use_sets) gc = set_gc[(size_t)set_of[i]];           // (the contig's own gc is in the result already)
             const double low = fmin(0.65, 0.88495 * gc - 0.0102337), high = fmax(0.35, 0.86596 * gc + 0.1131991);
             int tt_prev = -1;
             for (int m = 0; m < NM; m++) {
@@ -2168,6 +2208,40 @@ static int find_impl_cov(pga_ctx* c, const pga_batch* batch, const pga_params* p
             // the reference visits the models of a contig in model order and keeps a strictly better one: the winner is the
             // highest score, the lowest model among equals -- one pass over the chains, whatever group they sit in
             if (!P.meta) { for (int k = NCH - 1; k >= 0; k--) win_chain[chains[k].contig] = k; }
+            else if (use_sets) {
+                // Contig sets: a contig contributes its path score under a model iff it has nodes and a path there; S_m of a set is the
+                // sum of its members' contributions in batch order; the set's model is the largest S_m above -100, the lowest index among
+                // equals; a member that contributed under it is called from that chain, the others have no genes.
+                std::vector<double>& ms = c->model_scores;           // [contig][model], NaN: no contribution
+                std::vector<int32_t> chain_of((size_t)NC * NM, -1);
+                for (int k = 0; k < NCH; k++) {
+                    const ChainDesc& ch = chains[k];
+                    if (ch.n <= 0 || h_ipath[k] < 0) continue;
+                    ms[(size_t)ch.contig * NM + ch.model] = h_maxscore[k];
+                    chain_of[(size_t)ch.contig * NM + ch.model] = k;
+                }
+                std::vector<double> S((size_t)NS * NM, 0.0);
+                std::vector<uint8_t> has((size_t)NS * NM, 0);
+                for (int i = 0; i < NC; i++) {
+                    const size_t s0 = (size_t)set_of[i] * NM;
+                    for (int m = 0; m < NM; m++) {
+                        if (chain_of[(size_t)i * NM + m] < 0) continue;
+                        const double v = ms[(size_t)i * NM + m];
+                        if (has[s0 + m]) S[s0 + m] += v; else { S[s0 + m] = v; has[s0 + m] = 1; }
+                    }
+                }
+                std::vector<int32_t> W((size_t)NS, -1);
+                for (int s = 0; s < NS; s++) {
+                    double best = -100.0;
+                    for (int m = 0; m < NM; m++) if (has[(size_t)s * NM + m] && S[(size_t)s * NM + m] > best) { best = S[(size_t)s * NM + m]; W[(size_t)s] = m; }
+                }
+                for (int i = 0; i < NC; i++) {
+                    const int w = W[(size_t)set_of[i]];
+                    if (w < 0) continue;
+                    c->set_model[(size_t)i] = w; c->set_score[(size_t)i] = S[(size_t)set_of[i] * NM + w];
+                    win_chain[i] = chain_of[(size_t)i * NM + w];
+                }
+            }
             else {
                 std::vector<double> best(NC, -100.0);
                 for (int k = 0; k < NCH; k++) {
@@ -2667,7 +2741,12 @@ static int find_impl(pga_ctx* c, const pga_batch* batch, const pga_params* pp, c
 extern "C" int pga_find_genes(pga_ctx* c, const pga_batch* batch, const pga_params* pp, pga_result** out) {
     const auto t0 = std::chrono::steady_clock::now();
     const bool circular = c && batch && batch->ctx == c && !batch->circular.empty();
-    if (c) c->last_cuts.clear();
+    if (c) { c->last_cuts.clear(); c->set_model.clear(); c->set_score.clear(); c->model_scores.clear(); c->model_scores_nm = 0; }
+    if (out) *out = nullptr;
+    if (c && batch && pp && batch->ctx == c && !batch->sets.empty()) {
+        if (circular) { c->err = "pga_find_genes: the batch carries both set labels (pga_batch_set_sets) and circular flags (pga_batch_set_circular)"; return PGA_EINVAL; }
+        if (!pp->meta) { c->err = "pga_find_genes: set labels (pga_batch_set_sets) are a meta-mode feature (params->meta must be 1)"; return PGA_EINVAL; }
+    }
     const int rc = circular ? find_circular(c, batch, pp, out, nullptr) : find_impl(c, batch, pp, 0, 0, out, nullptr, nullptr);
     if (getenv("PGA_TIMING")) fprintf(stderr, "[pga timing] pga_find_genes wall=%.2fms\n", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
     return rc;
@@ -2693,7 +2772,11 @@ extern "C" int pga_find_genes_models(pga_ctx* c, const pga_batch* batch, const p
                      std::to_string(c->n_models) + " loaded";
             return PGA_EINVAL;
         }
-    c->last_cuts.clear();
+    c->last_cuts.clear(); c->set_model.clear(); c->set_score.clear(); c->model_scores.clear(); c->model_scores_nm = 0;
+    if (batch->ctx == c && !batch->circular.empty() && !batch->sets.empty()) {
+        c->err = "pga_find_genes_models: the batch carries both set labels (pga_batch_set_sets) and circular flags (pga_batch_set_circular)";
+        return PGA_EINVAL;
+    }
     if (batch->ctx == c && !batch->circular.empty()) return find_circular(c, batch, pp, out, model_of_contig);
     return find_impl(c, batch, pp, 0, 0, out, model_of_contig, nullptr);
 }
@@ -2784,6 +2867,7 @@ extern "C" int pga_batch_replicate(pga_ctx* c, const pga_batch* src, int32_t n, 
         for (int i = 0; i < n; i++) any = any || src->circular[contig_of_entry[i]];
         if (any) { b->circular.resize((size_t)n); for (int i = 0; i < n; i++) b->circular[i] = src->circular[contig_of_entry[i]]; }
     }
+    if (!src->sets.empty()) { b->sets.resize((size_t)n); for (int i = 0; i < n; i++) b->sets[(size_t)i] = src->sets[(size_t)contig_of_entry[i]]; }
     b->mask_case = src->mask_case;
     if (!src->regions.empty()) {
         b->reg_off.assign((size_t)n + 1, 0);
@@ -2797,5 +2881,39 @@ extern "C" int pga_batch_replicate(pga_ctx* c, const pga_batch* src, int32_t n, 
         if (rc) { pga_batch_free(b); return rc; }
     }
     *out = b;
+    return PGA_OK;
+}
+
+// ---- contig sets ----------------------------------------------------------------------------------------------------
+extern "C" int pga_batch_set_sets(pga_batch* b, const int32_t* set_of_contig) {
+    if (!b) return PGA_EINVAL;
+    b->sets.clear();
+    if (set_of_contig) {
+        for (int i = 0; i < b->n; i++) if (set_of_contig[i] < -1) {
+            if (b->ctx) b->ctx->err = "pga_batch_set_sets: contig " + std::to_string(i) + " carries label " + std::to_string(set_of_contig[i]) + " (a label is >= 0, -1 means on its own)";
+            return PGA_EINVAL;
+        }
+        b->sets.assign(set_of_contig, set_of_contig + b->n);
+    }
+    return PGA_OK;
+}
+
+extern "C" int pga_set_choice(const pga_ctx* c, int32_t n, int32_t* model, double* score) {
+    if (!c || n < 0 || (n > 0 && (!model || !score))) return PGA_EINVAL;
+    for (int i = 0; i < n; i++) {
+        const bool in = i < (int)c->set_model.size();
+        model[i] = in ? c->set_model[(size_t)i] : -1;
+        score[i] = in ? c->set_score[(size_t)i] : std::numeric_limits<double>::quiet_NaN();
+    }
+    return PGA_OK;
+}
+
+extern "C" int pga_model_scores(const pga_ctx* c, int32_t n_contigs, int32_t n_models, double* out) {
+    if (!c || n_contigs < 0 || n_models < 0 || ((int64_t)n_contigs * n_models > 0 && !out)) return PGA_EINVAL;
+    const int nm = c->model_scores_nm;
+    const int64_t nc = nm > 0 ? (int64_t)(c->model_scores.size() / (size_t)nm) : 0;
+    for (int64_t i = 0; i < n_contigs; i++)
+        for (int m = 0; m < n_models; m++)
+            out[i * n_models + m] = (i < nc && m < nm) ? c->model_scores[(size_t)(i * nm + m)] : std::numeric_limits<double>::quiet_NaN();
     return PGA_OK;
 }

@@ -221,6 +221,12 @@ struct pga_ctx {
     unsigned long long* render_small = nullptr;
     DevNodes dev_nodes;                                // the last finder call's node arrays, when it kept them (want_nodes != 0)
     std::vector<int32_t> last_cuts;                    // pga_circular_cuts: the cut of every contig of the last pga_find_genes / _models call (empty: all linear)
+    // contig sets, of the last pga_find_genes call when its batch carried labels (empty: it carried none)
+    std::vector<int32_t> set_model;                    // pga_set_choice: per contig the model of its set, -1: none
+    std::vector<double> set_score;                     //                 and that model's summed score, NaN: none
+    std::vector<double> model_scores;                  // pga_model_scores: [contig][model_scores_nm] path scores, NaN: no contribution
+    int model_scores_nm = 0;
+    std::vector<int64_t> render_seqnums;               // pga_render_seqnums: the seqnum of every contig of the batches rendered next (empty: first_seqnum + i)
 };
 void pga_render_release(pga_ctx*);   // render.hip: frees the buffers above
 // summary of a segmented launch's flags (host copy, [PGA_SEG_ROUNDS][stride]) into pga_ctx::dp_stats

@@ -133,6 +133,11 @@ constexpr size_t PGA_SS_REC_BYTES = 32, PGA_SS_MMCHAIN_BYTES = 32, PGA_SS_MMTILE
 // per (group, contig): is any model of the group inside the contig's GC window?  (meta mode)
 void pga_launch_group_enable(const ContigDesc* d_ct, int n_contigs, const int32_t* d_gc_count, const double* d_model_gc,
                              const int32_t* d_model_group, int n_models, int n_groups, uint8_t* d_enabled, hipStream_t st);
+// the same flags from the GC window of the contig's SET: d_set_of[i] in [0, n_contigs), d_pool: 2 * n_contigs entries of
+// scratch that hold every set's pooled G+C count and length afterwards
+void pga_launch_group_enable_sets(const ContigDesc* d_ct, int n_contigs, const int32_t* d_gc_count, const int32_t* d_set_of, int32_t* d_pool,
+                                  const double* d_model_gc, const int32_t* d_model_group, int n_models, int n_groups, uint8_t* d_enabled,
+                                  hipStream_t st);
 // runs of unknown bases of at least min_mask positions, unordered, at most `cap` of them; *d_count is reset first
 void pga_launch_find_masks(const uint8_t* d_dig, const ContigDesc* d_ct, int n_contigs, const TileDesc* d_tiles, int n_tiles, int min_mask,
                            MaskRun* d_runs, int32_t* d_count, int cap, hipStream_t st);

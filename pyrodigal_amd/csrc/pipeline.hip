@@ -3218,6 +3218,44 @@ void pga_launch_group_enable(const ContigDesc* d_ct, int n_contigs, const int32_
                        n_models, n_groups, d_enabled);
 }
 
+// Contig sets: the contigs of a set share ONE GC window, that of the set's pooled G+C count over its pooled length.
+// k_set_pool adds every contig's two integers to its set's pair -- integer atomics, so the sums are exact whatever the order -- and
+// k_group_enable_sets is k_group_enable with the set's sums in place of the contig's own.  set_of[i] is dense, in [0, n_contigs);
+// pool[2 * s] = G+C count, pool[2 * s + 1] = length of set s (cleared by the launcher; a batch holds fewer than 2^31 bases).
+__global__ void __launch_bounds__(256)
+k_set_pool(const ContigDesc* __restrict__ ct, int n_contigs, const int32_t* __restrict__ gc_count, const int32_t* __restrict__ set_of,
+           int32_t* __restrict__ pool) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_contigs) return;
+    const int s = set_of[i];
+    if (s < 0 || s >= n_contigs) return;
+    atomicAdd(pool + 2 * (size_t)s, gc_count[i]);
+    atomicAdd(pool + 2 * (size_t)s + 1, (int32_t)ct[i].len);
+}
+__global__ void __launch_bounds__(256)
+k_group_enable_sets(int n_contigs, const int32_t* __restrict__ set_of, const int32_t* __restrict__ pool, const double* __restrict__ model_gc,
+                    const int32_t* __restrict__ model_group, int n_models, int n_groups, uint8_t* __restrict__ enabled /* [group][contig] */) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_contigs) return;
+    const int s = set_of[i];
+    const bool ok = s >= 0 && s < n_contigs;
+    const int L = ok ? pool[2 * (size_t)s + 1] : 0;
+    const double gc = L > 0 ? (double)pool[2 * (size_t)s] / (double)L : 0.0;
+    const double low = fmin(0.65, 0.88495 * gc - 0.0102337), high = fmax(0.35, 0.86596 * gc + 0.1131991);
+    unsigned need = 0;
+    for (int m = 0; m < n_models; m++) if (!(model_gc[m] < low || model_gc[m] > high)) need |= 1u << model_group[m];
+    for (int g = 0; g < n_groups; g++) enabled[(size_t)g * n_contigs + i] = (need >> g) & 1;
+}
+void pga_launch_group_enable_sets(const ContigDesc* d_ct, int n_contigs, const int32_t* d_gc_count, const int32_t* d_set_of, int32_t* d_pool,
+                                  const double* d_model_gc, const int32_t* d_model_group, int n_models, int n_groups, uint8_t* d_enabled,
+                                  hipStream_t st) {
+    if (n_contigs <= 0) return;
+    (void)hipMemsetAsync(d_pool, 0, sizeof(int32_t) * 2 * (size_t)n_contigs, st);
+    hipLaunchKernelGGL(k_set_pool, dim3(nblocks(n_contigs, 256)), dim3(256), 0, st, d_ct, n_contigs, d_gc_count, d_set_of, d_pool);
+    hipLaunchKernelGGL(k_group_enable_sets, dim3(nblocks(n_contigs, 256)), dim3(256), 0, st, n_contigs, d_set_of, d_pool, d_model_gc, d_model_group,
+                       n_models, n_groups, d_enabled);
+}
+
 
 
 void pga_launch_orf_gc(const ContigDesc* d_ct, int n_contigs, const uint8_t* d_dig, const int32_t* d_p16, const GroupArrays& ga,

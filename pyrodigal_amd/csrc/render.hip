@@ -62,6 +62,7 @@ struct RenderArgs {
     int32_t src_off, src_len, ver_off, ver_len;
     int32_t n_contigs, meta;
     int64_t n_genes, first_seqnum;
+    const int64_t* seqnum;          // or nullptr: contig c is sequence first_seqnum + c (pga_render_seqnums)
     int32_t header, incl_tt, full_id, width, tt, include_stop, strict;
     int32_t div_off, div_len, date_off, date_len, infv_off, infv_len;     // GenBank strings in the arena
     double margin;
@@ -82,6 +83,7 @@ struct RenderArgs {
     char* out;
 };
 
+__device__ __forceinline__ int64_t seqnum_of(const RenderArgs& a, const int c) { return a.seqnum ? a.seqnum[c] : a.first_seqnum + c; }
 __device__ __forceinline__ void put_id(Sink& o, const RenderArgs& a, const int c) {
     o.put_n(a.str + a.id_off[c], a.id_off[c + 1] - a.id_off[c]);
 }
@@ -109,7 +111,7 @@ __device__ __forceinline__ void put_motif(Sink& o, const int mot_len, const int3
 // Gene._gene_data (lib.pyx:1091-1095): ID=..;partial=..;start_type=..;rbs_motif=..;rbs_spacer=..;gc_cont=..
 __device__ bool gene_data(Sink& o, const RenderArgs& a, const pga_gene& g, const int c, const int64_t k, const int full_id) {
     o.puts("ID=");
-    if (full_id) put_id(o, a, c); else pga_fmt::put_i64(o, a.first_seqnum + c);
+    if (full_id) put_id(o, a, c); else pga_fmt::put_i64(o, seqnum_of(a, c));
     o.put('_'); pga_fmt::put_i64(o, k + 1);
     o.puts(";partial="); o.put((char)('0' + (g.partial_begin ? 1 : 0))); o.put((char)('0' + (g.partial_end ? 1 : 0)));
     o.puts(";start_type="); o.puts(c_node_type[g.start_type & 3]);
@@ -132,7 +134,7 @@ __device__ bool gene_data(Sink& o, const RenderArgs& a, const pga_gene& g, const
 __device__ void gff_header(Sink& o, const RenderArgs& a, const int c) {
     const RenderModel& m = a.models[a.moc[c]];
     if (a.header) o.puts("##gff-version  3\n");
-    o.puts("# Sequence Data: seqnum="); pga_fmt::put_i64(o, a.first_seqnum + c);
+    o.puts("# Sequence Data: seqnum="); pga_fmt::put_i64(o, seqnum_of(a, c));
     o.puts(";seqlen="); pga_fmt::put_i64(o, a.ct[c].len);
     o.puts(";seqhdr=\""); put_id(o, a, c);
     o.puts(a.ct[c]._pad ? "\";topology=circular\n# Model Data: version=" : "\"\n# Model Data: version="); o.put_n(a.str + a.ver_off, a.ver_len);
@@ -495,7 +497,7 @@ __global__ void __launch_bounds__(256) k_sco_bounds(const RenderArgs a) {
 
 __device__ void sco_header(Sink& o, const RenderArgs& a, const int c) {
     const RenderModel& m = a.models[a.moc[c]];
-    o.puts("# Sequence Data: seqnum="); pga_fmt::put_i64(o, a.first_seqnum + c);
+    o.puts("# Sequence Data: seqnum="); pga_fmt::put_i64(o, seqnum_of(a, c));
     o.puts(";seqlen="); pga_fmt::put_i64(o, a.ct[c].len);
     o.puts(";seqhdr=\""); put_id(o, a, c);
     o.puts("\"\n# Run Data: version="); o.put_n(a.str + a.ver_off, a.ver_len);
@@ -615,6 +617,13 @@ extern "C" void pga_render_free(pga_render_result* r) {
     delete r;
 }
 
+extern "C" int pga_render_seqnums(pga_ctx* c, int32_t n, const int64_t* seqnum) {
+    if (!c || n < 0) return PGA_EINVAL;
+    c->render_seqnums.clear();
+    if (seqnum && n > 0) c->render_seqnums.assign(seqnum, seqnum + n);
+    return PGA_OK;
+}
+
 extern "C" int pga_render_genes(pga_ctx* c, const pga_batch* batch, const pga_contig_result* contigs, int64_t n_genes, const pga_gene* genes,
                                 const int32_t* model_of_contig, const char* ids, const int64_t* id_off, const pga_render_opts* opts,
                                 pga_render_result** out) {
@@ -723,7 +732,9 @@ extern "C" int pga_render_genes(pga_ctx* c, const pga_batch* batch, const pga_co
     size_t o_str = o_idoff + al(sizeof(int64_t) * (NC + 1)), o_code = o_str + al(str.size() + 1);
     size_t o_cnt = o_code + al(sizeof code), o_wg0 = o_cnt + al(sizeof(unsigned long long) * 8);
     size_t o_naoff = o_wg0 + al(sizeof(int64_t) * (NC + 1)), o_ncum = o_naoff + al(sizeof(int64_t) * (NC + 1));
-    size_t o_srow = o_ncum + al(sizeof(int64_t) * (NC + 1)), o_skey = o_srow + al(sizeof(int64_t) * (NC + 1));
+    size_t o_srow = o_ncum + al(sizeof(int64_t) * (NC + 1)), o_seqn = o_srow + al(sizeof(int64_t) * (NC + 1));
+    size_t o_skey = o_seqn + al(sizeof(int64_t) * (NC + 1));
+    const bool own_seqnums = NC > 0 && (int)c->render_seqnums.size() == NC;
     const size_t nn1 = (size_t)std::max<int64_t>(NN, 1);
     size_t o_sval = o_skey + al(sizeof(uint64_t) * 2 * nn1), o_f = o_sval + al(sizeof(uint32_t) * 2 * nn1);
     size_t o_len[NF], o_off[NF], o_flag[NF], o_hdr[NF], o_coff[NF];
@@ -780,6 +791,7 @@ extern "C" int pga_render_genes(pga_ctx* c, const pga_batch* batch, const pga_co
     if (e == hipSuccess && want_gbk) e = hipMemcpyAsync(d + o_wg0, org_wg0.data(), sizeof(int64_t) * (NC + 1), hipMemcpyHostToDevice, st);
     if (e == hipSuccess && want_sco) e = hipMemcpyAsync(d + o_naoff, naoff.data(), sizeof(int64_t) * (NC + 1), hipMemcpyHostToDevice, st);
     if (e == hipSuccess && want_sco) e = hipMemcpyAsync(d + o_ncum, ncum.data(), sizeof(int64_t) * (NC + 1), hipMemcpyHostToDevice, st);
+    if (e == hipSuccess && own_seqnums) e = hipMemcpyAsync(d + o_seqn, c->render_seqnums.data(), sizeof(int64_t) * NC, hipMemcpyHostToDevice, st);
     if (e != hipSuccess) return fail(e);
 
     RenderArgs A{};
@@ -790,6 +802,7 @@ extern "C" int pga_render_genes(pga_ctx* c, const pga_batch* batch, const pga_co
     A.div_off = div_off; A.div_len = div_len; A.date_off = date_off; A.date_len = date_len; A.infv_off = infv_off; A.infv_len = infv_len;
     A.n_contigs = NC; A.meta = O.meta; A.n_genes = n_genes; A.first_seqnum = O.first_seqnum; A.margin = O.fallback_margin;
     A.org_wg0 = (const int64_t*)(d + o_wg0);
+    A.seqnum = own_seqnums ? (const int64_t*)(d + o_seqn) : nullptr;
     if (want_sco) A.nd = DN.a;
     A.naoff = (const int64_t*)(d + o_naoff); A.ncum = (const int64_t*)(d + o_ncum);
     A.skey = (uint64_t*)(d + o_skey); A.skey2 = A.skey + nn1; A.sval = (uint32_t*)(d + o_sval); A.sval2 = A.sval + nn1;

@@ -121,6 +121,9 @@ cdef extern from "pyrodigal_amd.h" nogil:
     int pga_batch_set_mask_case(pga_batch*, int lower_case)
     int pga_batch_set_circular(pga_batch*, const uint8_t* circular)
     int pga_circular_cuts(const pga_ctx*, int32_t n, int32_t* out)
+    int pga_batch_set_sets(pga_batch*, const int32_t* set_of_contig)
+    int pga_set_choice(const pga_ctx*, int32_t n, int32_t* model, double* score)
+    int pga_model_scores(const pga_ctx*, int32_t n_contigs, int32_t n_models, double* out)
     int pga_circular_cut(int32_t L, int32_t n, const int32_t* begin, const int32_t* end)
     int pga_batch_replicate(pga_ctx*, const pga_batch* src, int32_t n, const int32_t* contig_of_entry, pga_batch** out)
     int pga_find_coding_bases(pga_ctx*, const pga_batch*, const pga_params*, const int32_t* model_of_contig, int64_t* coding_bases,
@@ -1281,6 +1284,10 @@ cdef class Genes:
     cdef readonly bint circular   # the sequence was called as a circle (find_genes(..., circular=True)): a gene may end beyond its length
     cdef readonly object cut      # ... and where the finder cut it open for its second pass (0-based; node indices and `Node.index`
                                   # are those of sequence[cut:] + sequence[:cut]); None for a linear sequence
+    cdef readonly object set_score     # find_genes_batch(..., sets=...): the summed score of the model chosen for this sequence's set
+                                       # (None: the set has no model); None for a call without sets
+    cdef readonly object model_scores  # ... and {model index: path score} of this sequence under every model of its set's GC window
+                                       # it has a path under; None for a call without sets
     cdef list _genes           # the Gene objects, built from _recs when first asked for
     cdef bytes _recs           # the packed gene records of this sequence as the device call returned them
     cdef ssize_t _n
@@ -1523,6 +1530,7 @@ cdef class _FindRequest:
     """The sequences of one `find_genes` / `find_genes_batch` call, waiting for a device call to ride."""
     cdef list seqs              # Sequence objects
     cdef list circ              # one bool per sequence: called as a circle; None: all linear
+    cdef object sets            # int32 per sequence: dense set id, -1: on its own; None: no sets (such a request rides alone)
     cdef bint translate
     cdef ssize_t first_id
     cdef int64_t bases
@@ -1726,7 +1734,7 @@ cdef class GeneFinder:
         return take
 
     def find_genes_batch(self, object sequences, *, bint translate=False, object training_infos=None, object regions=None,
-                         object circular=None):
+                         object circular=None, object sets=None):
         """`find_genes` for many sequences in one device pass; returns one `Genes` per input, in order.
 
         `translate=True` also translates every gene on the device while the batch is resident (one thread per codon, the
@@ -1740,8 +1748,32 @@ cdef class GeneFinder:
         `regions`: one entry per sequence, `None` or the regions of that sequence as `find_genes` takes them.
 
         `circular`: `None` / `False` (every sequence is linear), `True` (every sequence is a circle) or one flag per sequence;
-        see `find_genes`.  Circular and linear sequences share a device call."""
+        see `find_genes`.  Circular and linear sequences share a device call.
+
+        `sets` (meta mode only): one label per sequence -- any hashable, `None` for a sequence on its own -- that names the set of
+        sequences it belongs to: the contigs of a bin or a draft genome, the segments of a virus.  One metagenomic model is then
+        chosen per set, from the GC content of the set as a whole and the summed scores of its members, instead of one per
+        sequence; `Genes.set_score` and `Genes.model_scores` say how the choice came out.  A member without a gene path under
+        the set's model has no genes.  The call is a device call of its own and cannot be combined with `circular`."""
         cdef list circ = None
+        cdef object set_ids = None
+        if sets is not None:
+            sequences = list(sequences)
+            if not self.meta:
+                raise ValueError("`sets` is a meta-mode option: this finder is in single mode")
+            if training_infos is not None:
+                raise ValueError("`sets` cannot be combined with `training_infos` (a single-mode option)")
+            if circular is not None and circular is not False:
+                raise ValueError("`sets` cannot be combined with `circular`: the second pass of a circular call holds only the "
+                                 "circular members of a set")
+            labels = list(sets)
+            if len(labels) != len(sequences):
+                raise ValueError("`sets` has %d entries for %d sequences" % (len(labels), len(sequences)))
+            set_ids = np.full(max(len(labels), 1), -1, np.int32)
+            seen = {}
+            for k, lab in enumerate(labels):
+                if lab is not None:
+                    set_ids[k] = seen.setdefault(lab, len(seen))
         if circular is not None and circular is not False:
             sequences = list(sequences)
             if circular is True:
@@ -1768,6 +1800,8 @@ cdef class GeneFinder:
         cdef _FindRequest r
         cdef _FinderSlot slot = None
         cdef list take
+        if set_ids is not None:
+            return self._find_genes_sets(seqs, translate, set_ids)
         req.seqs = seqs; req.translate = translate; req.bases = bases; req.out = None; req.error = None; req.done = False
         req.circ = circ
         req.lead = None
@@ -1923,6 +1957,32 @@ cdef class GeneFinder:
                 self._release_slot(slot)
         return out
 
+    def _find_genes_sets(self, list seqs, bint translate, object set_ids):
+        """`find_genes_batch(..., sets=...)`: every set must sit in one device call, so the request takes a context for itself and is
+        never coalesced with other callers' sequences."""
+        cdef _FindRequest req = _FindRequest.__new__(_FindRequest)
+        cdef _FinderSlot slot
+        with self._lock:
+            req.first_id = self._num_seq
+            self._num_seq += len(seqs)
+        req.seqs = seqs; req.circ = None; req.sets = set_ids
+        with self._cv:
+            while True:
+                slot = self._free_slot()
+                if slot is not None:
+                    break
+                self._cv.wait()
+            slot.busy = True
+        try:
+            out = self._device_call(slot, seqs, translate, [req])
+            with self._lock:
+                self.stats["device_calls"] += 1
+                self.stats["sequences"] += len(seqs)
+        finally:
+            with self._lock:
+                self._release_slot(slot)
+        return out
+
     cdef int _release_slot(self, _FinderSlot slot) except -1:
         """(lock held) The context goes to the oldest waiting request that has no context yet, or back to the pool."""
         cdef _FindRequest r
@@ -1997,6 +2057,10 @@ cdef class GeneFinder:
         cdef object flags = None                     # uint8 per sequence, or None when no request of the call names a circle
         cdef object cuts = None
         cdef size_t p_flags = 0, p_cuts = 0
+        cdef object set_ids = (<_FindRequest> take[0]).sets if len(take) == 1 else None
+        cdef object set_model = None, set_score = None, mscores = None
+        cdef size_t p_sets = 0, p_smodel = 0, p_sscore = 0, p_mscores = 0
+        cdef int n_models = 0
         if ptrs == NULL or lens == NULL:
             free(ptrs); free(lens)
             raise MemoryError()
@@ -2047,7 +2111,7 @@ cdef class GeneFinder:
                         prot, prot_off, tables = self._translate(ctx, batch, res, n, tinf_of)
                 finally:
                     pga_batch_free(batch)
-            elif not translate and not masked and flags is None:
+            elif not translate and not masked and flags is None and set_ids is None:
                 with nogil:
                     rc = pga_find_genes_batch(ctx, n, ptrs, lens, &p, &res)
                 if rc != PGA_OK:
@@ -2061,10 +2125,22 @@ cdef class GeneFinder:
                         _attach_masks(ctx, batch, seqs, self.mask_lowercase)
                     if flags is not None:
                         pga_batch_set_circular(batch, <const uint8_t*> p_flags)
+                    if set_ids is not None:
+                        p_sets = set_ids.ctypes.data
+                        rc = pga_batch_set_sets(batch, <const int32_t*> p_sets)
+                        if rc != PGA_OK:
+                            _raise_for(ctx, rc, "pga_batch_set_sets")
                     with nogil:
                         rc = pga_find_genes(ctx, batch, &p, &res)
                     if rc != PGA_OK:
                         _raise_for(ctx, rc, "pga_find_genes")
+                    if set_ids is not None:
+                        n_models = len(self.metagenomic_bins)
+                        set_model = np.full(max(n, 1), -1, np.int32); set_score = np.full(max(n, 1), np.nan, np.float64)
+                        mscores = np.full(max(n * n_models, 1), np.nan, np.float64)
+                        p_smodel = set_model.ctypes.data; p_sscore = set_score.ctypes.data; p_mscores = mscores.ctypes.data
+                        pga_set_choice(ctx, n, <int32_t*> p_smodel, <double*> p_sscore)
+                        pga_model_scores(ctx, n, n_models, <double*> p_mscores)
                     if flags is not None:
                         pga_circular_cuts(ctx, n, <int32_t*> p_cuts)
                     if translate:
@@ -2088,6 +2164,9 @@ cdef class GeneFinder:
                 genes.score = cr.score
                 genes.circular = flags is not None and flags[i] != 0
                 genes.cut = int(cuts[i]) if genes.circular else None
+                if set_ids is not None:
+                    genes.set_score = float(set_score[i]) if set_model[i] >= 0 else None
+                    genes.model_scores = {j: float(mscores[i * n_models + j]) for j in range(n_models) if mscores[i * n_models + j] == mscores[i * n_models + j]}
                 if self.meta:
                     if cr.model >= 0:
                         genes.metagenomic_bin = self.metagenomic_bins[cr.model]

@@ -200,6 +200,92 @@ def find_genes_fasta(path, model_blobs, n_contexts=2, device=0, max_bases=64 << 
                 c.close()
 
 
+def plan_set_calls(ids, lens, sets_by_id, max_bases):
+    """The device calls of a file whose records come in sets (``sets_by_id``: ``{sequence id: label}``; a record that is not listed
+    is a set of its own).  A set must sit in one device call: the sets, in order of first appearance, fill a call up to
+    ``max_bases`` bases, and a larger set gets a call of its own.  Returns ``(labels, calls, unmatched)``: the label of every record
+    (None: on its own), the record indices of every call in file order, and the listed ids that no record carried."""
+    labels = [sets_by_id.get(rid) for rid in ids]
+    members, order = {}, []
+    for i, lab in enumerate(labels):
+        key = ("own", i) if lab is None else ("set", lab)
+        if key not in members:
+            members[key] = []
+            order.append(key)
+        members[key].append(i)
+    calls, cur, cur_bases = [], [], 0
+    for key in order:
+        bases = sum(int(lens[i]) for i in members[key])
+        if cur and cur_bases + bases > max_bases:
+            calls.append(sorted(cur))
+            cur, cur_bases = [], 0
+        cur.extend(members[key])
+        cur_bases += bases
+    if cur:
+        calls.append(sorted(cur))
+    return labels, calls, sorted(set(sets_by_id) - set(ids))
+
+
+def _render_fasta_sets(path, ctxs, formats, sinks, stats, sets_by_id, *, max_bases, meta, descriptions, first_seqnum, unbinned_model,
+                       regions_by_id, mask_lowercase, want_nodes, seen, find_kw):
+    """:func:`render_fasta` with ``sets_by_id``: the file is read whole, the device calls are packed from whole sets
+    (:func:`plan_set_calls`), every call is rendered while it is resident, and the text is written in file order at the end."""
+    with _cabi.FastaReader(path) as reader:
+        records = [rec for batch in reader.batches() for rec in batch]
+    ids = [r[0] for r in records]
+    lens = [len(r[2]) for r in records]
+    labels, calls, unmatched = plan_set_calls(ids, lens, sets_by_id, max_bases)
+    text = {name: [b""] * len(records) for name in formats}
+    todo = queue.Queue()
+    for call in calls:
+        todo.put(call)
+    failure = []
+    lock = threading.Lock()
+
+    def worker(ctx):
+        while not failure:
+            try:
+                call = todo.get_nowait()
+            except queue.Empty:
+                return
+            try:
+                b = ctx.upload([records[i][2] for i in call])
+                try:
+                    cids = [ids[i] for i in call]
+                    _attach_masks(b, cids, [lens[i] for i in call], regions_by_id, mask_lowercase, seen)
+                    b.set_sets([labels[i] for i in call])
+                    r = ctx.find_genes(b, meta=meta, want_nodes=want_nodes, **find_kw)
+                    out = ctx.render_genes(b, r, cids, formats, meta=meta, descriptions=descriptions, unbinned_model=unbinned_model,
+                                           seqnums=[first_seqnum + i for i in call])
+                finally:
+                    b.close()
+                with lock:
+                    for name, t in out.items():
+                        for k, i in enumerate(call):
+                            text[name][i] = t.contig(k)
+                        stats["fallback"] += t.fallback
+                        stats["kernel_ms"][name] += t.kernel_ms
+                    stats["genes"] += len(r.genes)
+            except BaseException as e:
+                failure.append(e)
+
+    threads = [threading.Thread(target=worker, args=(c,), daemon=True) for c in ctxs]
+    for t in threads:
+        t.start()
+    for t in threads:
+        t.join()
+    if failure:
+        raise failure[0]
+    for name in formats:
+        for piece in text[name]:
+            sinks[name].write(piece)
+    stats["records"] = len(records); stats["bases"] = sum(lens); stats["device_calls"] = len(calls)
+    stats["sets_unmatched"] = unmatched
+    stats["regions_unmatched"] = sorted(set(regions_by_id or ()) - seen)
+    stats["circular_unmatched"] = []
+    return stats
+
+
 def _host_genbank(ctx, result, ids, letters, flags, options, meta, first_seqnum):
     """The GenBank text of a batch that holds circular records, by the host writer (the device renderer does not write locations
     across the origin): one ``Genes.write_genbank`` per record."""
@@ -227,7 +313,8 @@ def _host_genbank(ctx, result, ids, letters, flags, options, meta, first_seqnum)
 
 def render_fasta(path, model_blobs, *, gff=None, faa=None, fna=None, gbk=None, scores=None, n_contexts=2, device=0, max_bases=64 << 20,
                  meta=False, descriptions=None, first_seqnum=1, gff_options=None, faa_options=None, fna_options=None, gbk_options=None,
-                 scores_options=None, unbinned_model=None, regions_by_id=None, mask_lowercase=False, circular=None, **find_kw):
+                 scores_options=None, unbinned_model=None, regions_by_id=None, mask_lowercase=False, circular=None, sets_by_id=None,
+                 **find_kw):
     """Call the genes of every record of a FASTA file and write them as text: GFF to ``gff``, protein FASTA to ``faa``, gene
     FASTA to ``fna``, GenBank to ``gbk``, the start-score file to ``scores`` (binary file objects, or None), in file order --
     what ``Genes.write_gff`` / ``write_translations`` / ``write_genes`` / ``write_genbank`` / ``write_scores`` write record after
@@ -244,9 +331,20 @@ def render_fasta(path, model_blobs, *, gff=None, faa=None, fna=None, gbk=None, s
     written by the host writer ``Genes.write_genbank`` (``join()`` locations, ``LOCUS ... circular``), byte for byte what the
     device writes for its linear records.  Returns ``{"records", "bases", "genes", "fallback", "kernel_ms": {format: ms},
     "regions_unmatched": [ids of regions_by_id that no record carried], "circular_unmatched": [ids of a ``circular`` collection
-    that no record carried]}``."""
+    that no record carried]}``.
+
+    ``sets_by_id`` (meta mode): ``{sequence id: label}``, the set of contigs a record belongs to -- the contig-to-bin table of a
+    binner; a record that is not listed is on its own.  One model is chosen per set (``Batch.set_sets``).  A set must sit in one
+    device call, so the file is then read whole and held in memory together with its output text until the last call is done;
+    the calls are packed from whole sets up to ``max_bases`` (a larger set gets a call of its own) and the output stays in file
+    order.  Not with ``circular``.  The result also holds ``"sets_unmatched"`` and ``"device_calls"`` then."""
     seen = set()
     seen_circular = set()
+    if sets_by_id is not None:
+        if not meta:
+            raise ValueError("render_fasta: `sets_by_id` is a meta-mode option")
+        if circular is not None and circular is not False:
+            raise ValueError("render_fasta: `sets_by_id` cannot be combined with `circular`")
     if scores is not None and circular is not None and circular is not False:
         raise ValueError("render_fasta: the start-score file is not written for circular records")
     formats = {}
@@ -265,6 +363,15 @@ def render_fasta(path, model_blobs, *, gff=None, faa=None, fna=None, gbk=None, s
     ctxs = [_cabi.Context(device) for _ in range(max(1, n_contexts))]
     for c in ctxs:
         c.set_models(list(model_blobs))
+    if sets_by_id is not None:
+        try:
+            return _render_fasta_sets(path, ctxs, formats, sinks, stats, dict(sets_by_id), max_bases=max_bases, meta=meta,
+                                      descriptions=descriptions, first_seqnum=first_seqnum, unbinned_model=unbinned_model,
+                                      regions_by_id=regions_by_id, mask_lowercase=mask_lowercase, want_nodes=want_nodes, seen=seen,
+                                      find_kw=find_kw)
+        finally:
+            for c in ctxs:
+                c.close()
     todo = queue.Queue(maxsize=len(ctxs))
     done, failure = {}, []
     cv = threading.Condition()
