@@ -247,6 +247,24 @@ int  pga_batch_set_circular(pga_batch*, const uint8_t* circular /* n flags, or N
 /* The cut of every contig of the last pga_find_genes / pga_find_genes_models call on the context: out[i] for i < n, -1 for a linear
  * contig (and for every contig when the batch carried no flag). */
 int  pga_circular_cuts(const pga_ctx*, int32_t n, int32_t* out);
+/* Direct terminal repeats: a circular contig that its assembler wrote out with the first bases once more at the end.  For a contig S of
+ * L letters, W = min(max_length, L / 2); match = the largest r with min_length <= r <= W such that S[j] and S[L - r + j] are the same
+ * base for every 0 <= j < r (either case; a letter that is not A, C, G or T matches nothing), 0 when there is none.  With c the count
+ * of the most frequent base of S[0 : match], the repeat is low-complexity when 100 c > max_base_percent * match; trim = match, or 0 for
+ * a low-complexity repeat (a shorter match is not tried; max_base_percent = 100 turns the filter off).
+ *   pga_batch_terminal_repeats       detects only, on the device, and leaves the batch as it is: search[i] != 0 (NULL: every contig)
+ *                                    has contig i searched, match_out[i] / trim_out[i] are 0 for the others; 8 n bytes come back.
+ *                                    PGA_EINVAL unless 1 <= min_length <= max_length <= 1048576 and 25 <= max_base_percent <= 100.
+ *   pga_batch_trim_terminal_repeats  a new batch whose contig i is S[0 : len - trim[i]], copied device to device, flagged circular where
+ *                                    trim[i] > 0 or `src` says so; mask_case and the set labels are copied, the caller's regions are
+ *                                    clipped to the new length (empty ones dropped).  *out = NULL, and nothing is copied, when every
+ *                                    trim[i] is 0.  trim[i] < 0 or 2 trim[i] > len is PGA_EINVAL naming the contig.
+ * pga_find_genes on the new batch is the circular call of the trimmed contigs.  Both are calls on the context like pga_find_genes: one
+ * at a time.  pga_terminal_repeat_chunk: the letters of each window the detection hashes per step (for tests that straddle it). */
+int  pga_batch_terminal_repeats(pga_ctx*, const pga_batch*, const uint8_t* search /* n flags, or NULL */, int32_t min_length,
+                                int32_t max_length, int32_t max_base_percent, int32_t* match_out /* n */, int32_t* trim_out /* n */);
+int  pga_batch_trim_terminal_repeats(pga_ctx*, const pga_batch* src, const int32_t* trim /* n */, pga_batch** out);
+int  pga_terminal_repeat_chunk(void);
 /* Contig sets, one more attribute of the resident batch (meta mode): set_of_contig[i] >= 0 labels contig i as a member of that set of
  * contigs known to be one organism (the bins of a binner, the contigs of a draft genome, the segments of a virus); -1 leaves it on its
  * own.  Labels need not be dense, and the members of a set need not be adjacent in the batch.  NULL clears the labels.

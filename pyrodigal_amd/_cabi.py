@@ -25,6 +25,7 @@ EXPORTS = [
     "pga_batch_set_regions", "pga_batch_set_mask_case",
     "pga_batch_set_circular", "pga_circular_cuts", "pga_circular_cut",
     "pga_batch_set_sets", "pga_set_choice", "pga_model_scores", "pga_render_seqnums",
+    "pga_batch_terminal_repeats", "pga_batch_trim_terminal_repeats", "pga_terminal_repeat_chunk",
 ]
 STAGE_EXTRACT, STAGE_SCORE, STAGE_OVERLAP, STAGE_SEQUENCE = 1, 2, 3, 4
 
@@ -145,6 +146,9 @@ def load():
     L.pga_circular_cuts.restype = ctypes.c_int; L.pga_circular_cuts.argtypes = [vp, i32, vp]
     L.pga_circular_cut.restype = ctypes.c_int; L.pga_circular_cut.argtypes = [i32, i32, vp, vp]
     L.pga_batch_set_sets.restype = ctypes.c_int; L.pga_batch_set_sets.argtypes = [vp, vp]
+    L.pga_batch_terminal_repeats.restype = ctypes.c_int; L.pga_batch_terminal_repeats.argtypes = [vp, vp, vp, i32, i32, i32, vp, vp]
+    L.pga_batch_trim_terminal_repeats.restype = ctypes.c_int; L.pga_batch_trim_terminal_repeats.argtypes = [vp, vp, vp, _P(vp)]
+    L.pga_terminal_repeat_chunk.restype = ctypes.c_int; L.pga_terminal_repeat_chunk.argtypes = []
     L.pga_set_choice.restype = ctypes.c_int; L.pga_set_choice.argtypes = [vp, i32, vp, vp]
     L.pga_model_scores.restype = ctypes.c_int; L.pga_model_scores.argtypes = [vp, i32, i32, vp]
     L.pga_render_seqnums.restype = ctypes.c_int; L.pga_render_seqnums.argtypes = [vp, i32, vp]
@@ -377,6 +381,9 @@ class BatchResult:
         # contig sets (Batch.set_sets), None when the batch carried no labels: per contig the model chosen for its set (-1: none) and
         # that model's summed score (NaN: none); [contig][model] the path score a contig contributed (NaN: none)
         self.set_models = self.set_scores = self.model_scores = None
+        # direct terminal repeats (find_genes_batch(..., trim_terminal_repeats=...)): int32 per contig, the letters taken off its end
+        # before it was called as a circle (0: none, or not searched); None when the call did not ask
+        self.terminal_repeats = None
 
     def genes_of(self, i):
         c = self.contigs[i]
@@ -492,6 +499,49 @@ class Batch:
             _raise(self.ctx.L, self.ctx.h, rc, "pga_batch_set_sets")
         self.sets = ids
         return self
+
+    def terminal_repeats(self, search=None, min_length=20, max_length=65536, max_base_percent=75):
+        """Direct terminal repeats of the resident contigs, found on the device (``pga_batch_terminal_repeats``): ``(match, trim)``,
+        int32 per contig.  ``match`` is the longest r in ``min_length .. min(max_length, L // 2)`` for which the first r bases of
+        the contig are also its last r (0: none); ``trim`` is ``match``, or 0 where one base makes up more than
+        ``max_base_percent`` percent of the repeat.  ``search``: one flag per contig (``None``: all); the others report 0.  The
+        batch is left as it is."""
+        flags = None
+        if search is not None:
+            flags = np.ascontiguousarray([1 if x else 0 for x in search], dtype=np.uint8)
+            if flags.shape != (self.n,):
+                raise ValueError(f"search has {flags.size} entries for {self.n} contigs")
+        match, trim = np.zeros(max(self.n, 1), np.int32), np.zeros(max(self.n, 1), np.int32)
+        rc = self.ctx.L.pga_batch_terminal_repeats(self.ctx.h, self.h, None if flags is None or not self.n else ctypes.c_void_p(flags.ctypes.data),
+                                                   int(min_length), int(max_length), int(max_base_percent),
+                                                   ctypes.c_void_p(match.ctypes.data), ctypes.c_void_p(trim.ctypes.data))
+        if rc != PGA_OK:
+            _raise(self.ctx.L, self.ctx.h, rc, "pga_batch_terminal_repeats")
+        return match[:self.n], trim[:self.n]
+
+    def trim_terminal_repeats(self, trim):
+        """A new resident :class:`Batch` whose contig i has lost its last ``trim[i]`` letters and is flagged circular where
+        ``trim[i] > 0`` (``pga_batch_trim_terminal_repeats``); mask sources, set labels and circular flags travel with the contigs.
+        Returns ``self``, and copies nothing, when every entry is 0."""
+        t = np.ascontiguousarray(trim, dtype=np.int32).reshape(-1)
+        if t.shape != (self.n,):
+            raise ValueError(f"trim has {t.size} entries for {self.n} contigs")
+        h = ctypes.c_void_p()
+        rc = self.ctx.L.pga_batch_trim_terminal_repeats(self.ctx.h, self.h, ctypes.c_void_p(t.ctypes.data) if self.n else None, ctypes.byref(h))
+        if rc != PGA_OK:
+            _raise(self.ctx.L, self.ctx.h, rc, "pga_batch_trim_terminal_repeats")
+        if not h:
+            return self
+        b = Batch.__new__(Batch)
+        b.ctx, b.n, b.h = self.ctx, self.n, h
+        b.total = None if self.total is None else int(self.total) - int(t.sum())
+        flags = (t > 0).astype(np.uint8)
+        if self.circular is not None:
+            flags |= (self.circular[:self.n] != 0).astype(np.uint8)
+        b.circular = np.ascontiguousarray(flags)
+        if self.sets is not None:
+            b.sets = self.sets
+        return b
 
     def __init__(self, ctx, seqs):
         self.ctx = ctx
@@ -701,12 +751,52 @@ def _find_coding_bases(self, batch, model_of_contig, closed=False, min_gene=90, 
     return cov[:batch.n], ng[:batch.n], sc[:batch.n]
 
 
-def _find_genes_batch(self, seqs, regions=None, mask_lowercase=False, circular=None, sets=None, **kw):
+def terminal_repeat_options(n, option):
+    """``trim_terminal_repeats=`` as the finder calls take it -> ``(search, (min_length, max_length, max_base_percent))``, or ``None``
+    when nothing is to be searched.  ``option``: ``None`` / ``False``, ``True`` (the defaults, every sequence), an object with
+    ``min_length`` / ``max_length`` / ``max_base_percent`` (every sequence), or one such entry per sequence -- a call has one set of
+    parameters, so two different parameter objects in one list are a ``ValueError``."""
+    default = (20, 65536, 75)
+
+    def params(o):
+        return (int(o.min_length), int(o.max_length), int(o.max_base_percent))
+
+    if option is None or option is False:
+        return None
+    if option is True:
+        return np.ones(max(n, 1), np.uint8)[:n], default
+    if hasattr(option, "min_length"):
+        return np.ones(max(n, 1), np.uint8)[:n], params(option)
+    entries = list(option)
+    if len(entries) != n:
+        raise ValueError("`trim_terminal_repeats` has %d entries for %d sequences" % (len(entries), n))
+    search, shared = np.zeros(max(n, 1), np.uint8)[:n], None
+    for i, e in enumerate(entries):
+        if e is None or e is False:
+            continue
+        search[i] = 1
+        if e is True:
+            continue
+        if not hasattr(e, "min_length"):
+            raise TypeError("trim_terminal_repeats[%d] is neither a bool nor a TerminalRepeats (%r)" % (i, type(e).__name__))
+        if shared is not None and e is not shared and e != shared:
+            raise ValueError("`trim_terminal_repeats` names two different TerminalRepeats in one call (sequence %d): "
+                             "a call has one set of parameters" % i)
+        shared = shared if shared is not None else e
+    if not search.any():
+        return None
+    return search, (default if shared is None else params(shared))
+
+
+def _find_genes_batch(self, seqs, regions=None, mask_lowercase=False, circular=None, sets=None, trim_terminal_repeats=None, **kw):
     """Upload + find + free: ``seqs`` is a list of ASCII ``bytes``/``str`` contigs.  ``regions`` (one entry per contig: ``None`` or
     ``(begin, end)`` pairs) and ``mask_lowercase`` are more mask sources (:meth:`Batch.set_masks`); ``masks`` of the result is their
     union with the runs of unknown bases of ``mask=True``.  ``circular``: as :meth:`Batch.set_circular` takes it; ``sets``: as
-    :meth:`Batch.set_sets` takes it (meta mode)."""
+    :meth:`Batch.set_sets` takes it (meta mode).  ``trim_terminal_repeats``: as :func:`terminal_repeat_options` takes it -- the
+    searched contigs that end in a copy of their first bases lose it on the device and are called as circles
+    (``terminal_repeats`` of the result: the letters each contig lost)."""
     b = Batch(self, seqs)
+    t = b
     try:
         if sets is not None:
             b.set_sets(sets)
@@ -714,8 +804,18 @@ def _find_genes_batch(self, seqs, regions=None, mask_lowercase=False, circular=N
             b.set_masks(regions, mask_lowercase)
         if circular is not None and circular is not False:
             b.set_circular(circular)      # (through a resident batch: the one-step pga_find_genes_batch has none to flag)
-        return _find_genes(self, b, **kw)
+        tr = terminal_repeat_options(b.n, trim_terminal_repeats)
+        trim = None
+        if tr is not None:
+            _, trim = b.terminal_repeats(tr[0], *tr[1])
+            t = b.trim_terminal_repeats(trim)
+        out = _find_genes(self, t, **kw)
+        if trim_terminal_repeats is not None and trim_terminal_repeats is not False:
+            out.terminal_repeats = trim if trim is not None else np.zeros(b.n, np.int32)
+        return out
     finally:
+        if t is not b:
+            t.close()
         b.close()
 
 

@@ -65,6 +65,16 @@ def argument_parser(prog="pyrodigal_amd"):
                    help="The records whose id (first word of the FASTA header) is listed in this file, one per line, are circular.")
     p.add_argument("--circular-from-header", action="store_true", default=False,
                    help="The records whose header says circular=true or topology=circular (any letter case) are circular.")
+    p.add_argument("--circular-detect", action="store_true", default=False,
+                   help="Look for a direct terminal repeat in every record: a record whose first bases are also its last (what an "
+                        "assembler writes for a circular contig) loses the second copy and is called as a circular sequence. "
+                        "A record --circular, --circular-ids or --circular-from-header names stays circular either way.")
+    p.add_argument("--min-repeat", type=int, default=20, metavar="N", help="The shortest terminal repeat --circular-detect accepts.")
+    p.add_argument("--max-repeat", type=int, default=65536, metavar="N",
+                   help="The longest terminal repeat --circular-detect looks for (at most half of the record).")
+    p.add_argument("--circular-report", metavar="FILE",
+                   help="With --circular-detect: write seqid, length, match, trim and status (trimmed, low_complexity or none) of "
+                        "every record to this file, tab-separated, in input order.")
     p.add_argument("--bin-map", metavar="FILE",
                    help="With -p meta: choose one model per set of contigs. Tab-separated seqid, bin -- the contig-to-bin table a "
                         "binner writes (seqid is the first word of the FASTA header); # lines are ignored, a sequence that is not "
@@ -140,6 +150,34 @@ class _ListedOrHeader:
         return header_says_circular(seq_id, description)
 
 
+class TerminalRepeatOption:
+    """The parameters of ``--circular-detect`` as ``pipeline.render_fasta(trim_terminal_repeats=...)`` takes them."""
+
+    def __init__(self, min_length=20, max_length=65536, max_base_percent=75):
+        self.min_length, self.max_length, self.max_base_percent = min_length, max_length, max_base_percent
+
+    def __eq__(self, other):
+        return (self.min_length, self.max_length, self.max_base_percent) == (other.min_length, other.max_length, other.max_base_percent)
+
+    def __repr__(self):
+        return "TerminalRepeatOption(%d, %d, %d)" % (self.min_length, self.max_length, self.max_base_percent)
+
+
+def terminal_repeat_option(args):
+    """What ``pipeline.render_fasta(trim_terminal_repeats=...)`` takes for ``--circular-detect`` (None: not asked for)."""
+    if not args.circular_detect:
+        return None
+    return TerminalRepeatOption(args.min_repeat, args.max_repeat)
+
+
+def write_circular_report(file, records):
+    """``--circular-report``: one line per record, ``seqid  length  match  trim  status``, tab-separated.  ``records``: the
+    ``"terminal_repeat_records"`` of ``pipeline.render_fasta``, ``(seqid, length, match, trim)`` in input order; ``file`` takes text."""
+    from .pipeline import terminal_repeat_status
+    for seqid, length, match, trim in records:
+        file.write("%s\t%d\t%d\t%d\t%s\n" % (seqid, length, match, trim, terminal_repeat_status(match, trim)))
+
+
 def parse_mask_regions(lines, name="<regions>"):
     """``{seqid: [(start, end), ...]}`` of a BED-like text (an iterable of lines): tab-separated ``seqid  start  end``, 0-based and
     half-open; further columns, blank lines, ``#`` lines and ``track`` / ``browser`` lines are ignored.  A malformed line is a
@@ -186,11 +224,20 @@ def _check(args):
         return "--batch-bases must be at least 1."
     if args.s is not None and (args.circular or args.circular_ids is not None or args.circular_from_header):
         return "-s cannot be combined with --circular, --circular-ids or --circular-from-header: the start file is not written for circular sequences."
+    if args.s is not None and args.circular_detect:
+        return "-s cannot be combined with --circular-detect: the start file is not written for circular sequences."
+    if not args.circular_detect and args.circular_report is not None:
+        return "--circular-report needs --circular-detect."
+    if args.circular_detect and not (1 <= args.min_repeat <= args.max_repeat <= 1048576):
+        return "--min-repeat and --max-repeat must satisfy 1 <= min <= max <= 1048576."
     if args.bin_map is not None and args.p != "meta":
         return "--bin-map needs -p meta: one model per set of contigs is a choice among the metagenomic bins."
     if args.bin_map is not None and (args.circular or args.circular_ids is not None or args.circular_from_header):
         return ("--bin-map cannot be combined with --circular, --circular-ids or --circular-from-header: the second pass of a circular "
                 "call holds only the circular members of a set.")
+    if args.bin_map is not None and args.circular_detect:
+        return ("--bin-map cannot be combined with --circular-detect: the second pass of a circular call holds only the circular "
+                "members of a set.")
     return None
 
 
@@ -223,6 +270,9 @@ def main(argv=None, stdout=None, stderr=None):
         print("Error: --circular-ids: %s" % e, file=stderr)
         return 1
     mask_kw = dict(regions_by_id=regions, mask_lowercase=args.mask_lowercase, circular=circular)
+    detect = terminal_repeat_option(args)
+    if detect is not None:
+        mask_kw["trim_terminal_repeats"] = detect
     if args.bin_map is not None:
         try:
             mask_kw["sets_by_id"] = read_bin_map(args.bin_map)
@@ -270,10 +320,19 @@ def main(argv=None, stdout=None, stderr=None):
                         tinf.dump(fh)
             blobs, descriptions, unbinned = [tinf.raw], None, None
         scores = None if args.s is None else stack.enter_context(open(args.s, "wb"))
+        report = None
+        if args.circular_report is not None:
+            try:
+                report = stack.enter_context(open(args.circular_report, "w", encoding="utf-8"))
+            except OSError as e:
+                print("Error: --circular-report: %s" % e, file=stderr)
+                return 1
         from .pipeline import render_fasta
         stats = render_fasta(path, blobs, gff=out if args.f == "gff" else None, gbk=out if args.f == "gbk" else None, faa=faa, fna=fna,
                              scores=scores, n_contexts=args.jobs, max_bases=args.batch_bases, meta=meta, descriptions=descriptions,
                              faa_options={"include_stop": not args.no_stop_codon}, unbinned_model=unbinned, **mask_kw, **find_kw)
+        if report is not None:
+            write_circular_report(report, stats.get("terminal_repeat_records", ()))
         for rid in stats.get("regions_unmatched", ()):
             print("Warning: --mask-regions: no sequence %r in the input" % rid, file=stderr)
         for rid in stats.get("sets_unmatched", ()):

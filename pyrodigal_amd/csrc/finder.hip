@@ -2737,6 +2737,7 @@ static int find_impl(pga_ctx* c, const pga_batch* batch, const pga_params* pp, c
 
 #include "train.inl"
 #include "circular.inl"
+#include "terminal_repeat.inl"
 
 extern "C" int pga_find_genes(pga_ctx* c, const pga_batch* batch, const pga_params* pp, pga_result** out) {
     const auto t0 = std::chrono::steady_clock::now();

@@ -125,6 +125,10 @@ cdef extern from "pyrodigal_amd.h" nogil:
     int pga_set_choice(const pga_ctx*, int32_t n, int32_t* model, double* score)
     int pga_model_scores(const pga_ctx*, int32_t n_contigs, int32_t n_models, double* out)
     int pga_circular_cut(int32_t L, int32_t n, const int32_t* begin, const int32_t* end)
+    int pga_batch_terminal_repeats(pga_ctx*, const pga_batch*, const uint8_t* search, int32_t min_length, int32_t max_length,
+                                   int32_t max_base_percent, int32_t* match_out, int32_t* trim_out)
+    int pga_batch_trim_terminal_repeats(pga_ctx*, const pga_batch* src, const int32_t* trim, pga_batch** out)
+    int pga_terminal_repeat_chunk()
     int pga_batch_replicate(pga_ctx*, const pga_batch* src, int32_t n, const int32_t* contig_of_entry, pga_batch** out)
     int pga_find_coding_bases(pga_ctx*, const pga_batch*, const pga_params*, const int32_t* model_of_contig, int64_t* coding_bases,
                               int32_t* n_genes, double* score)
@@ -1288,6 +1292,10 @@ cdef class Genes:
                                        # (None: the set has no model); None for a call without sets
     cdef readonly object model_scores  # ... and {model index: path score} of this sequence under every model of its set's GC window
                                        # it has a path under; None for a call without sets
+    cdef readonly object terminal_repeat        # find_genes(..., trim_terminal_repeats=...): the bases taken off the end of the record
+                                                # because they repeat its first bases (0: none, or a low-complexity one); `sequence` is
+                                                # the record without them; None when the sequence was not searched
+    cdef readonly object terminal_repeat_match  # ... and the length of the longest such repeat, low-complexity or not
     cdef list _genes           # the Gene objects, built from _recs when first asked for
     cdef bytes _recs           # the packed gene records of this sequence as the device call returned them
     cdef ssize_t _n
@@ -1526,9 +1534,94 @@ cdef class _FinderSlot:
             self.ctx = NULL
 
 
+cdef class TerminalRepeats:
+    """How `find_genes(..., trim_terminal_repeats=...)` looks for a direct terminal repeat: the longest `r` in
+    `min_length .. min(max_length, len(sequence) // 2)` for which the first `r` bases of the sequence are also its last `r`; a repeat
+    in which one base makes up more than `max_base_percent` percent is low-complexity and is left alone (100: no such filter)."""
+    cdef readonly int min_length
+    cdef readonly int max_length
+    cdef readonly int max_base_percent
+
+    def __init__(self, int min_length=20, int max_length=65536, int max_base_percent=75):
+        if not (1 <= min_length <= max_length <= 1048576):
+            raise ValueError("1 <= min_length <= max_length <= 1048576 does not hold for %d, %d" % (min_length, max_length))
+        if not (25 <= max_base_percent <= 100):
+            raise ValueError("`max_base_percent` must lie in 25 .. 100, not %d" % max_base_percent)
+        self.min_length = min_length
+        self.max_length = max_length
+        self.max_base_percent = max_base_percent
+
+    def _key(self):
+        return (self.min_length, self.max_length, self.max_base_percent)
+
+    def __eq__(self, other):
+        return isinstance(other, TerminalRepeats) and self._key() == (<TerminalRepeats> other)._key()
+
+    def __hash__(self):
+        return hash(self._key())
+
+    def __repr__(self):
+        return "pyrodigal_amd.lib.TerminalRepeats(min_length=%d, max_length=%d, max_base_percent=%d)" % self._key()
+
+    def __reduce__(self):
+        return TerminalRepeats, self._key()
+
+
+cdef tuple _terminal_repeat_option(object option, Py_ssize_t n):
+    """`trim_terminal_repeats=` of a call over n sequences -> (one bool per sequence, (min_length, max_length, max_base_percent)),
+    or (None, None) when no sequence is to be searched."""
+    cdef TerminalRepeats shared = None
+    cdef list search
+    if option is None or option is False:
+        return None, None
+    if option is True:
+        return [True] * n, TerminalRepeats()._key()
+    if isinstance(option, TerminalRepeats):
+        return [True] * n, (<TerminalRepeats> option)._key()
+    entries = list(option)
+    if len(entries) != n:
+        raise ValueError("`trim_terminal_repeats` has %d entries for %d sequences" % (len(entries), n))
+    search = []
+    for i, e in enumerate(entries):
+        if e is None or e is False:
+            search.append(False)
+            continue
+        search.append(True)
+        if e is True:
+            continue
+        if not isinstance(e, TerminalRepeats):
+            raise TypeError("trim_terminal_repeats[%d] is neither a bool nor a TerminalRepeats (%r)" % (i, type(e).__name__))
+        if shared is not None and e is not shared and e != shared:
+            raise ValueError("`trim_terminal_repeats` names two different TerminalRepeats in one call (sequence %d): a call has one "
+                             "set of parameters" % i)
+        if shared is None:
+            shared = <TerminalRepeats> e
+    if not any(search):
+        return None, None
+    return search, (TerminalRepeats() if shared is None else shared)._key()
+
+
+cdef pga_batch* _trimmed_batch(pga_ctx* ctx, pga_batch* whole, size_t p_search, tuple params, size_t p_match, size_t p_trim) except? NULL:
+    """The terminal-repeat step of a device call: the search on the resident batch (`p_search`: a flag per sequence; match and trim go
+    to `p_match` / `p_trim`) and the batch without the repeats, or NULL when no sequence has one to take off."""
+    cdef pga_batch* out = NULL
+    cdef int32_t min_length = params[0], max_length = params[1], max_base_percent = params[2]
+    cdef int rc
+    with nogil:
+        rc = pga_batch_terminal_repeats(ctx, whole, <const uint8_t*> p_search, min_length, max_length, max_base_percent,
+                                        <int32_t*> p_match, <int32_t*> p_trim)
+        if rc == PGA_OK:
+            rc = pga_batch_trim_terminal_repeats(ctx, whole, <const int32_t*> p_trim, &out)
+    if rc != PGA_OK:
+        _raise_for(ctx, rc, "pga_batch_terminal_repeats")
+    return out
+
+
 cdef class _FindRequest:
     """The sequences of one `find_genes` / `find_genes_batch` call, waiting for a device call to ride."""
     cdef list seqs              # Sequence objects
+    cdef list tr_search         # one bool per sequence: searched for a direct terminal repeat; None: none of them
+    cdef object tr_params       # (min_length, max_length, max_base_percent) of that search: requests that ride one device call agree on it
     cdef list circ              # one bool per sequence: called as a circle; None: all linear
     cdef object sets            # int32 per sequence: dense set id, -1: on its own; None: no sets (such a request rides alone)
     cdef bint translate
@@ -1690,7 +1783,7 @@ cdef class GeneFinder:
         slot.models_sig = sig
         return 0
 
-    def find_genes(self, object sequence, object regions=None, bint circular=False):
+    def find_genes(self, object sequence, object regions=None, bint circular=False, object trim_terminal_repeats=False):
         """Find all the genes in the input DNA sequence (ref: lib.pyx:5400-5469).
 
         `circular=True`: the record is a circle cut open at an arbitrary base (a closed chromosome, a plasmid, a phage genome).
@@ -1700,11 +1793,19 @@ cdef class GeneFinder:
         ends at base `end - len(sequence)`.  No gene of a circular sequence is partial.  `genes.nodes`, `Gene.start_node` and
         `Gene.stop_node` are those of the rotated sequence.
 
+        `trim_terminal_repeats`: `True` or a `TerminalRepeats`.  An assembler that closes a circle (or a phage genome with a direct
+        terminal repeat) writes the first bases of the record once more at its end.  The finder looks for that repeat on the device,
+        takes the second copy off and calls what is left as a circle, exactly as `find_genes(sequence[:-n], circular=True)` would:
+        `genes.terminal_repeat` is `n` (0: no repeat, the sequence keeps the topology `circular` gives it), `genes.sequence` is the
+        record without it.  A repeat that is mostly one base (`genes.terminal_repeat_match > 0` with `terminal_repeat == 0`) is
+        not a topology and is left alone.
+
         `regions`: `[begin, end)` intervals of the sequence (0-based; a `Masks`, or any iterable of `Mask` objects or pairs) that no
         gene may run across, exactly as if they were masked runs of `N` -- while the bases keep their identity for the GC content,
         the model choice, every score and the printed sequence.  They join the runs of unknown bases (`mask=True`), the runs of
         lower-case letters (`mask_lowercase=True`) and the regions a `Sequence` already carries; `genes.sequence.masks` is the union."""
-        return self.find_genes_batch([sequence], regions=None if regions is None else [regions], circular=circular)[0]
+        return self.find_genes_batch([sequence], regions=None if regions is None else [regions], circular=circular,
+                                     trim_terminal_repeats=trim_terminal_repeats)[0]
 
     cdef _FinderSlot _free_slot(self):
         # a context that already exists first: a lone caller never makes a second one
@@ -1723,10 +1824,15 @@ cdef class GeneFinder:
         cdef int64_t bases = 0
         cdef list take = []
         cdef ssize_t k = 0
+        cdef object tr_params = None          # the terminal-repeat search of the call: its requests that search at all agree on it
         while k < len(self._pending):
             r = self._pending[k]
             if r.translate != head.translate or (take and bases + r.bases > self.coalesce_bases):
                 break
+            if r.tr_params is not None:
+                if tr_params is not None and tr_params != r.tr_params:
+                    break
+                tr_params = r.tr_params
             take.append(r)
             bases += r.bases
             k += 1
@@ -1734,7 +1840,7 @@ cdef class GeneFinder:
         return take
 
     def find_genes_batch(self, object sequences, *, bint translate=False, object training_infos=None, object regions=None,
-                         object circular=None, object sets=None):
+                         object circular=None, object sets=None, object trim_terminal_repeats=None):
         """`find_genes` for many sequences in one device pass; returns one `Genes` per input, in order.
 
         `translate=True` also translates every gene on the device while the batch is resident (one thread per codon, the
@@ -1754,9 +1860,21 @@ cdef class GeneFinder:
         sequences it belongs to: the contigs of a bin or a draft genome, the segments of a virus.  One metagenomic model is then
         chosen per set, from the GC content of the set as a whole and the summed scores of its members, instead of one per
         sequence; `Genes.set_score` and `Genes.model_scores` say how the choice came out.  A member without a gene path under
-        the set's model has no genes.  The call is a device call of its own and cannot be combined with `circular`."""
+        the set's model has no genes.  The call is a device call of its own and cannot be combined with `circular`.
+
+        `trim_terminal_repeats`: `None` / `False`, `True` (every sequence, the default parameters), a `TerminalRepeats` (every
+        sequence) or one entry per sequence, each `False`, `True` or one shared `TerminalRepeats`; see `find_genes`.  Independent
+        of `circular`: a sequence is called as a circle when either says so."""
         cdef list circ = None
         cdef object set_ids = None
+        cdef list tr_search = None
+        cdef object tr_params = None
+        if trim_terminal_repeats is not None and trim_terminal_repeats is not False:
+            sequences = list(sequences)
+            if sets is not None:
+                raise ValueError("`sets` cannot be combined with `trim_terminal_repeats`: the second pass of a circular call holds only "
+                                 "the circular members of a set")
+            tr_search, tr_params = _terminal_repeat_option(trim_terminal_repeats, len(sequences))
         if sets is not None:
             sequences = list(sequences)
             if not self.meta:
@@ -1785,7 +1903,7 @@ cdef class GeneFinder:
             if not any(circ):
                 circ = None
         if training_infos is not None:
-            return self._find_genes_models(sequences, translate, training_infos, regions, circ)
+            return self._find_genes_models(sequences, translate, training_infos, regions, circ, tr_search, tr_params)
         if not self.meta and self.training_info is None:
             raise RuntimeError("cannot find genes without having trained in single mode")
         # the reference always re-wraps with the finder's masking rule (ref: lib.pyx:5433-5438); a Sequence that already
@@ -1804,6 +1922,7 @@ cdef class GeneFinder:
             return self._find_genes_sets(seqs, translate, set_ids)
         req.seqs = seqs; req.translate = translate; req.bases = bases; req.out = None; req.error = None; req.done = False
         req.circ = circ
+        req.tr_search = tr_search; req.tr_params = tr_params
         req.lead = None
         req.signaled = False
         req.sem = _new_lock()
@@ -1901,7 +2020,8 @@ cdef class GeneFinder:
             seqs.append(s)
         return seqs
 
-    def _find_genes_models(self, object sequences, bint translate, object training_infos, object regions=None, list circ=None):
+    def _find_genes_models(self, object sequences, bint translate, object training_infos, object regions=None, list circ=None,
+                           list tr_search=None, object tr_params=None):
         """`find_genes_batch(..., training_infos=...)`: single mode with a model per sequence (`pga_find_genes_models`).  The
         sequences go in device calls of at most `coalesce_bases` bases and four translation tables (what one context's model set
         holds); identical `TrainingInfo` objects are loaded once per call."""
@@ -1947,6 +2067,8 @@ cdef class GeneFinder:
                 req = _FindRequest.__new__(_FindRequest)
                 req.seqs = [seqs[i] for i in idx]
                 req.circ = [circ[i] for i in idx] if circ is not None else None
+                req.tr_search = [tr_search[i] for i in idx] if tr_search is not None else None
+                req.tr_params = tr_params if tr_search is not None else None
                 req.first_id = first_id + idx[0]
                 out.extend(self._device_call(slot, req.seqs, translate, [req], [tinfs[i] for i in idx]))
                 with self._lock:
@@ -1965,7 +2087,7 @@ cdef class GeneFinder:
         with self._lock:
             req.first_id = self._num_seq
             self._num_seq += len(seqs)
-        req.seqs = seqs; req.circ = None; req.sets = set_ids
+        req.seqs = seqs; req.circ = None; req.sets = set_ids; req.tr_search = None; req.tr_params = None
         with self._cv:
             while True:
                 slot = self._free_slot()
@@ -2058,6 +2180,12 @@ cdef class GeneFinder:
         cdef object cuts = None
         cdef size_t p_flags = 0, p_cuts = 0
         cdef object set_ids = (<_FindRequest> take[0]).sets if len(take) == 1 else None
+        cdef object tr_params = None                 # the terminal-repeat search of this call, or None: no request asks for one
+        cdef object tr_flags = None, tr_match = None, tr_trim = None
+        cdef size_t p_search = 0, p_match = 0, p_trim = 0
+        cdef pga_batch* whole = NULL                 # the batch as uploaded, while `batch` is its trimmed copy
+        cdef pga_batch* trimmed = NULL
+        cdef Sequence tseq
         cdef object set_model = None, set_score = None, mscores = None
         cdef size_t p_sets = 0, p_smodel = 0, p_sscore = 0, p_mscores = 0
         cdef int n_models = 0
@@ -2072,12 +2200,25 @@ cdef class GeneFinder:
                 ids.append(r.first_id + j)
             if r.circ is not None and flags is None:
                 flags = np.zeros(max(n, 1), np.uint8)
+            if r.tr_params is not None:
+                tr_params = r.tr_params
         if flags is not None:
             i = 0
             for r in take:
                 if r.circ is not None:
                     flags[i:i + len(r.seqs)] = r.circ
                 i += len(r.seqs)
+        if tr_params is not None:
+            tr_flags = np.zeros(max(n, 1), np.uint8); tr_match = np.zeros(max(n, 1), np.int32); tr_trim = np.zeros(max(n, 1), np.int32)
+            i = 0
+            for r in take:
+                if r.tr_search is not None:
+                    tr_flags[i:i + len(r.seqs)] = r.tr_search
+                i += len(r.seqs)
+            p_search = tr_flags.ctypes.data; p_match = tr_match.ctypes.data; p_trim = tr_trim.ctypes.data
+            if flags is None:
+                flags = np.zeros(max(n, 1), np.uint8)      # (a trimmed sequence is a circle: the flags are completed after the search)
+        if flags is not None:
             cuts = np.full(max(n, 1), -1, np.int32)
             p_flags = flags.ctypes.data; p_cuts = cuts.ctypes.data
         try:
@@ -2101,6 +2242,10 @@ cdef class GeneFinder:
                         _attach_masks(ctx, batch, seqs, self.mask_lowercase)
                     if flags is not None:
                         pga_batch_set_circular(batch, <const uint8_t*> p_flags)
+                    if tr_params is not None:
+                        trimmed = _trimmed_batch(ctx, batch, p_search, tr_params, p_match, p_trim)
+                        if trimmed != NULL:
+                            whole = batch; batch = trimmed
                     with nogil:
                         rc = pga_find_genes_models(ctx, batch, &p, <const int32_t*> p_moc, &res)
                     if rc != PGA_OK:
@@ -2111,7 +2256,9 @@ cdef class GeneFinder:
                         prot, prot_off, tables = self._translate(ctx, batch, res, n, tinf_of)
                 finally:
                     pga_batch_free(batch)
-            elif not translate and not masked and flags is None and set_ids is None:
+                    if whole != NULL:
+                        pga_batch_free(whole)
+            elif not translate and not masked and flags is None and set_ids is None and tr_params is None:
                 with nogil:
                     rc = pga_find_genes_batch(ctx, n, ptrs, lens, &p, &res)
                 if rc != PGA_OK:
@@ -2130,6 +2277,10 @@ cdef class GeneFinder:
                         rc = pga_batch_set_sets(batch, <const int32_t*> p_sets)
                         if rc != PGA_OK:
                             _raise_for(ctx, rc, "pga_batch_set_sets")
+                    if tr_params is not None:
+                        trimmed = _trimmed_batch(ctx, batch, p_search, tr_params, p_match, p_trim)
+                        if trimmed != NULL:
+                            whole = batch; batch = trimmed
                     with nogil:
                         rc = pga_find_genes(ctx, batch, &p, &res)
                     if rc != PGA_OK:
@@ -2148,6 +2299,24 @@ cdef class GeneFinder:
                         prot, prot_off, tables = self._translate(ctx, batch, res, n, None)
                 finally:
                     pga_batch_free(batch)
+                    if whole != NULL:
+                        pga_batch_free(whole)
+            if tr_params is not None:
+                seqs = list(seqs)                      # (the caller's list keeps the records as they came)
+                for i in range(n):
+                    if tr_trim[i] > 0:
+                        # the record without the second copy of its first bases: what the device called, and what the host writers read
+                        flags[i] = 1
+                        tseq = <Sequence> seqs[i]
+                        r_clip = None
+                        if tseq._regions is not None:
+                            r_clip = np.minimum(tseq._regions, len(tseq.data) - int(tr_trim[i])).astype(np.int32)
+                            r_clip = r_clip[r_clip[:, 0] < r_clip[:, 1]]
+                            if len(r_clip) == 0:
+                                r_clip = None
+                        seqs[i] = Sequence(tseq.data[:len(tseq.data) - int(tr_trim[i])], mask=tseq.mask, mask_size=tseq.mask_size,
+                                           mask_lowercase=tseq.mask_lowercase)
+                        (<Sequence> seqs[i])._regions = r_clip
             for i in range(n):
                 cr = &res.contigs[i]
                 genes = Genes.__new__(Genes)
@@ -2164,6 +2333,9 @@ cdef class GeneFinder:
                 genes.score = cr.score
                 genes.circular = flags is not None and flags[i] != 0
                 genes.cut = int(cuts[i]) if genes.circular else None
+                genes.terminal_repeat = genes.terminal_repeat_match = None
+                if tr_params is not None and tr_flags[i]:
+                    genes.terminal_repeat = int(tr_trim[i]); genes.terminal_repeat_match = int(tr_match[i])
                 if set_ids is not None:
                     genes.set_score = float(set_score[i]) if set_model[i] >= 0 else None
                     genes.model_scores = {j: float(mscores[i * n_models + j]) for j in range(n_models) if mscores[i * n_models + j] == mscores[i * n_models + j]}

@@ -108,6 +108,25 @@ def circular_flags(circular, ids, descriptions, seen=None):
     return flags if any(flags) else None
 
 
+def trim_terminal_repeats_of(batch, option):
+    """The terminal-repeat step of one resident batch of a file.  ``option``: ``None`` / ``False``, ``True`` (the default parameters)
+    or an object with ``min_length`` / ``max_length`` / ``max_base_percent`` (``lib.TerminalRepeats``); every record is searched.
+    Returns ``(batch to call, match, trim)``: the batch itself and ``None, None`` when nothing was asked for; the batch itself when
+    no record has a repeat; else its trimmed copy, which the caller closes."""
+    if not (option is None or isinstance(option, bool) or hasattr(option, "min_length")):
+        raise TypeError("trim_terminal_repeats of a file is True or one TerminalRepeats for every record, not %r" % type(option).__name__)
+    tr = _cabi.terminal_repeat_options(batch.n, option)
+    if tr is None:
+        return batch, None, None
+    match, trim = batch.terminal_repeats(None, *tr[1])
+    return batch.trim_terminal_repeats(trim), match, trim
+
+
+def terminal_repeat_status(match, trim):
+    """The last column of the command line's ``--circular-report``."""
+    return "trimmed" if trim > 0 else "low_complexity" if match > 0 else "none"
+
+
 def header_says_circular(seq_id, description):
     """The predicate of ``--circular-from-header``: the description holds ``circular=true`` or ``topology=circular``, any case."""
     d = (description or "").lower()
@@ -115,7 +134,7 @@ def header_says_circular(seq_id, description):
 
 
 def find_genes_fasta(path, model_blobs, n_contexts=2, device=0, max_bases=64 << 20, contexts=None, regions_by_id=None,
-                     mask_lowercase=False, circular=None, **find_kw):
+                     mask_lowercase=False, circular=None, trim_terminal_repeats=None, **find_kw):
     """Genes of every record of a (gzipped) FASTA file: yields ``(ids, descriptions, lengths, BatchResult)`` per batch, in file order.
 
     The reader (C, zlib) parses batch k + 1 into a pinned staging arena while batch k is uploaded from its own arena with one
@@ -126,8 +145,11 @@ def find_genes_fasta(path, model_blobs, n_contexts=2, device=0, max_bases=64 << 
     ``regions_by_id``: ``{sequence id: [(begin, end), ...]}``, masked regions (0-based, half-open) of the records with that id (the
     first word of the header); ``mask_lowercase``: runs of lower-case letters are masked (``Batch.set_masks``).
     ``circular``: the records that are circles, as :func:`circular_flags` takes them; their genes may end beyond the record's
-    length and ``BatchResult.cuts`` says where each was cut open."""
+    length and ``BatchResult.cuts`` says where each was cut open.  ``trim_terminal_repeats``: ``True`` or a ``TerminalRepeats``: a
+    record that ends in a copy of its first bases loses the copy on the device and is called as a circle
+    (``BatchResult.terminal_repeats``: the bases each record lost; the yielded lengths are those of the file)."""
     seen = set()
+    trim_option = trim_terminal_repeats
     own = contexts is None             # `contexts`: contexts the caller keeps across files (models loaded, buffers grown)
     ctxs = [_cabi.Context(device) for _ in range(max(1, n_contexts))] if own else list(contexts)
     if own:
@@ -150,7 +172,14 @@ def find_genes_fasta(path, model_blobs, n_contexts=2, device=0, max_bases=64 << 
                 try:
                     _attach_masks(b, meta[0], lens, regions_by_id, mask_lowercase, seen)
                     b.set_circular(circular_flags(circular, meta[0], meta[1]))
-                    res = (meta, ctx.find_genes(b, **find_kw))
+                    t, _, trim = trim_terminal_repeats_of(b, trim_option)
+                    try:
+                        r = ctx.find_genes(t, **find_kw)
+                    finally:
+                        if t is not b:
+                            t.close()
+                    r.terminal_repeats = trim
+                    res = (meta, r)
                 finally:
                     b.close()
             except BaseException as e:
@@ -314,7 +343,7 @@ def _host_genbank(ctx, result, ids, letters, flags, options, meta, first_seqnum)
 def render_fasta(path, model_blobs, *, gff=None, faa=None, fna=None, gbk=None, scores=None, n_contexts=2, device=0, max_bases=64 << 20,
                  meta=False, descriptions=None, first_seqnum=1, gff_options=None, faa_options=None, fna_options=None, gbk_options=None,
                  scores_options=None, unbinned_model=None, regions_by_id=None, mask_lowercase=False, circular=None, sets_by_id=None,
-                 **find_kw):
+                 trim_terminal_repeats=None, **find_kw):
     """Call the genes of every record of a FASTA file and write them as text: GFF to ``gff``, protein FASTA to ``faa``, gene
     FASTA to ``fna``, GenBank to ``gbk``, the start-score file to ``scores`` (binary file objects, or None), in file order --
     what ``Genes.write_gff`` / ``write_translations`` / ``write_genes`` / ``write_genbank`` / ``write_scores`` write record after
@@ -333,6 +362,12 @@ def render_fasta(path, model_blobs, *, gff=None, faa=None, fna=None, gbk=None, s
     "regions_unmatched": [ids of regions_by_id that no record carried], "circular_unmatched": [ids of a ``circular`` collection
     that no record carried]}``.
 
+    ``trim_terminal_repeats``: ``True`` or a ``TerminalRepeats``.  Every record is searched on the device for a copy of its first
+    bases at its end; a record that has one loses it and is called, and written, as a circle of the remaining bases, whatever
+    ``circular`` says of it.  Refused with ``scores`` and ``sets_by_id`` like ``circular``.  The result then holds
+    ``"terminal_repeats": [(id, length, match, trim)]`` for the records with ``match > 0`` (``trim == 0``: a low-complexity repeat,
+    left alone) and ``"terminal_repeat_records"``, the same for every record, both in file order; lengths are those of the file.
+
     ``sets_by_id`` (meta mode): ``{sequence id: label}``, the set of contigs a record belongs to -- the contig-to-bin table of a
     binner; a record that is not listed is on its own.  One model is chosen per set (``Batch.set_sets``).  A set must sit in one
     device call, so the file is then read whole and held in memory together with its output text until the last call is done;
@@ -345,7 +380,10 @@ def render_fasta(path, model_blobs, *, gff=None, faa=None, fna=None, gbk=None, s
             raise ValueError("render_fasta: `sets_by_id` is a meta-mode option")
         if circular is not None and circular is not False:
             raise ValueError("render_fasta: `sets_by_id` cannot be combined with `circular`")
-    if scores is not None and circular is not None and circular is not False:
+    trim_option = trim_terminal_repeats if trim_terminal_repeats is not None and trim_terminal_repeats is not False else None
+    if sets_by_id is not None and trim_option is not None:
+        raise ValueError("render_fasta: `sets_by_id` cannot be combined with `trim_terminal_repeats`")
+    if scores is not None and ((circular is not None and circular is not False) or trim_option is not None):
         raise ValueError("render_fasta: the start-score file is not written for circular records")
     formats = {}
     for name, fh, opts in (("gff", gff, gff_options), ("faa", faa, faa_options), ("fna", fna, fna_options), ("gbk", gbk, gbk_options),
@@ -353,6 +391,8 @@ def render_fasta(path, model_blobs, *, gff=None, faa=None, fna=None, gbk=None, s
         if fh is not None:
             formats[name] = dict(opts or {})
     stats = {"records": 0, "bases": 0, "genes": 0, "fallback": 0, "kernel_ms": {k: 0.0 for k in formats}}
+    if trim_option is not None:
+        stats["terminal_repeats"], stats["terminal_repeat_records"] = [], []
     if not formats:
         raise ValueError("render_fasta: no output requested")
     sinks = {"gff": gff, "faa": faa, "fna": fna, "gbk": gbk, "scores": scores}
@@ -386,23 +426,36 @@ def render_fasta(path, model_blobs, *, gff=None, faa=None, fna=None, gbk=None, s
                 ids, n, total = pb.ids, pb.n, pb.total
                 lens = [int(x) for x in pb.lens[:pb.n]]
                 flags = circular_flags(circular, ids, pb.descriptions, seen_circular)
-                host_gbk = flags is not None and "gbk" in formats
+                host_gbk = (flags is not None or trim_option is not None) and "gbk" in formats
                 letters = [pb.sequence(k) for k in range(n)] if host_gbk else None     # (the arena is released by the upload)
                 b = ctx.upload_packed(pb)                 # releases the arena
+                found = None
                 try:
                     _attach_masks(b, ids, lens, regions_by_id, mask_lowercase, seen)
                     b.set_circular(flags)
-                    r = ctx.find_genes(b, meta=meta, want_nodes=want_nodes, **find_kw)
-                    dev_formats = {k: v for k, v in formats.items() if not (host_gbk and k == "gbk")}
-                    text = {}
-                    if dev_formats:
-                        text = ctx.render_genes(b, r, ids, dev_formats, meta=meta, descriptions=descriptions, first_seqnum=seqnum,
-                                                unbinned_model=unbinned_model)
-                    if host_gbk:
-                        text["gbk"] = _host_genbank(ctx, r, ids, letters, flags, formats["gbk"], meta, seqnum)
+                    t, match, trim = trim_terminal_repeats_of(b, trim_option)
+                    try:
+                        if match is not None:
+                            found = [(ids[k], lens[k], int(match[k]), int(trim[k])) for k in range(n)]
+                        if t is not b:                    # a trimmed record is a circle of the bases it keeps
+                            flags = [bool(x) for x in t.circular[:n]]
+                            if letters is not None:
+                                letters = [s[:len(s) - int(x)] for s, x in zip(letters, trim)]
+                        host_gbk = host_gbk and flags is not None
+                        r = ctx.find_genes(t, meta=meta, want_nodes=want_nodes, **find_kw)
+                        dev_formats = {k: v for k, v in formats.items() if not (host_gbk and k == "gbk")}
+                        text = {}
+                        if dev_formats:
+                            text = ctx.render_genes(t, r, ids, dev_formats, meta=meta, descriptions=descriptions, first_seqnum=seqnum,
+                                                    unbinned_model=unbinned_model)
+                        if host_gbk:
+                            text["gbk"] = _host_genbank(ctx, r, ids, letters, flags, formats["gbk"], meta, seqnum)
+                    finally:
+                        if t is not b:
+                            t.close()
                 finally:
                     b.close()
-                res = (n, total, len(r.genes), text)
+                res = (n, total, len(r.genes), text, found)
             except BaseException as e:
                 pb.release()
                 res = e
@@ -438,7 +491,10 @@ def render_fasta(path, model_blobs, *, gff=None, faa=None, fna=None, gbk=None, s
             nxt += 1
             if isinstance(res, BaseException):
                 raise res
-            n, total, n_genes, text = res
+            n, total, n_genes, text, found = res
+            if found is not None:
+                stats["terminal_repeat_records"].extend(found)
+                stats["terminal_repeats"].extend(x for x in found if x[2] > 0)
             for name, t in text.items():
                 sinks[name].write(t.data)
                 stats["fallback"] += t.fallback
