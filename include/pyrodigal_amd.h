@@ -456,6 +456,17 @@ void        pga_release_cached(void);
 int         pga_fasta_next_packed(pga_fasta*, int64_t max_bases, int32_t max_records, int32_t n_arenas, int32_t* n_records,
                                   const char* const** headers, const char** packed, const int64_t** offs, const int64_t** lens);
 
+/* ---- test support ----
+ * Makes memory that an earlier call left behind visible to a test: a call's result depends on its arguments only, so nothing a
+ * call reads may come from a buffer that this call did not write.  Waits for the context's streams, then fills the whole capacity
+ * (slack included) of every workspace buffer of the context whose elements are floating point, device and pinned, with `byte`
+ * (0 .. 255); while it is on, every block such a buffer newly acquires -- from the runtime or from the cache of destroyed contexts --
+ * gets the same fill before it is used, so do the floating-point buffers of pga_score_connections*, and the letters' allocation of
+ * a batch is filled with 'N'.  Buffers of integers are left alone: a pattern read as an index would be a wild address.  byte = -1
+ * switches it off (the state of a new context).  out (optional): buffers and bytes filled by this call.  0xFF is NaN in both
+ * widths, 0x7F a huge positive and 0xFE a huge negative number.  Not for production use: every fill synchronises the device. */
+int         pga_debug_poison(pga_ctx*, int byte, int64_t out[2]);
+
 #ifdef __cplusplus
 }
 #endif

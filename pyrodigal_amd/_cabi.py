@@ -26,6 +26,7 @@ EXPORTS = [
     "pga_batch_set_circular", "pga_circular_cuts", "pga_circular_cut",
     "pga_batch_set_sets", "pga_set_choice", "pga_model_scores", "pga_render_seqnums",
     "pga_batch_terminal_repeats", "pga_batch_trim_terminal_repeats", "pga_terminal_repeat_chunk",
+    "pga_debug_poison",
 ]
 STAGE_EXTRACT, STAGE_SCORE, STAGE_OVERLAP, STAGE_SEQUENCE = 1, 2, 3, 4
 
@@ -176,6 +177,7 @@ def load():
     L.pga_fasta_close.restype = None; L.pga_fasta_close.argtypes = [vp]
     L.pga_fasta_release_spare.restype = None; L.pga_fasta_release_spare.argtypes = []
     L.pga_release_cached.restype = None; L.pga_release_cached.argtypes = []
+    L.pga_debug_poison.restype = ctypes.c_int; L.pga_debug_poison.argtypes = [vp, ctypes.c_int, _P(i64)]
     _lib = L
     return L
 
@@ -304,6 +306,15 @@ class Context:
         if rc != PGA_OK:
             _raise(self.L, self.h, rc, "pga_extract_stats")
         return {"passes": out[0]}
+
+    def debug_poison(self, byte):
+        """Test support (``pga_debug_poison``): fill every floating-point workspace buffer of the context, and every block such a
+        buffer acquires from now on, with ``byte`` (0 .. 255; -1 or None: off).  Returns ``(buffers, bytes)`` filled by this call."""
+        out = (ctypes.c_int64 * 2)()
+        rc = self.L.pga_debug_poison(self.h, -1 if byte is None else int(byte), out)
+        if rc != PGA_OK:
+            _raise(self.L, self.h, rc, "pga_debug_poison")
+        return int(out[0]), int(out[1])
 
     @staticmethod
     def dp_kernel_name():

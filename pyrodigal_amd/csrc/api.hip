@@ -13,6 +13,7 @@
 #include <stdlib.h>
 
 #include <new>
+#include <type_traits>
 
 static int fail(pga_ctx* c, int code, const char* fmt, ...) {
     if (c) {
@@ -168,10 +169,15 @@ extern "C" int pga_set_models(pga_ctx* c, const pga_training* const* models, int
 namespace {
 struct DevBuf {     // frees everything it allocated when the call returns
     std::vector<void*> ptrs;
+    int poison = -1;    // pga_debug_poison: the fill of every new block of floating-point elements
     ~DevBuf() { for (void* p : ptrs) hipFree(p); }
     template <typename T> hipError_t alloc(T** p, size_t count) {
         hipError_t e = hipMalloc((void**)p, sizeof(T) * (count ? count : 1));
         if (e == hipSuccess) ptrs.push_back(*p);
+        if (e == hipSuccess && poison >= 0 && std::is_floating_point<T>::value) {
+            e = hipMemset(*p, poison, sizeof(T) * (count ? count : 1));
+            if (e == hipSuccess) e = hipDeviceSynchronize();
+        }
         return e;
     }
 };
@@ -226,6 +232,7 @@ static int score_connections_impl(pga_ctx* c, int32_t n, const int32_t* ndx, con
         return fail(c, PGA_EINVAL, "pga_score_connections: NULL array");
     HIP_TRY(c, hipSetDevice(c->device));
     DevBuf db;
+    db.poison = c->poison;
     struct { int32_t* ndx; int32_t* stop_val; uint8_t* type; int8_t* strand; double* cscore; double* sscore; double* rscore; double* uscore; int32_t* star_ptr; } nd{};
     DpBuffers buf{};
     ChainDesc* d_chain; ModelConst* d_mc;
@@ -279,16 +286,19 @@ static int score_connections_impl(pga_ctx* c, int32_t n, const int32_t* ndx, con
         HIP_TRY(c, db.alloc(&d_cbase, 2));
         HIP_TRY(c, hipMemcpyAsync(d_cbase, h_cbase, sizeof h_cbase, hipMemcpyHostToDevice, st));
         wg.g[0].ndx = nd.ndx; wg.g[0].stop_val = nd.stop_val;
+        bool sched = pga_dpw_use_sched();
+        const int nbat = (n + 63) >> 6;
+        if (sched) {
+            // the schedule's buffers exist before the topology kernel runs: it is that kernel which clears scur (the overflow count)
+            HIP_TRY(c, db.alloc(&wg.g[0].shdr, (size_t)nbat + 1)); HIP_TRY(c, db.alloc(&wg.g[0].sent, 2 * (size_t)DPW_SCHED_STRIDE * ((size_t)nbat + 1) + 16)); HIP_TRY(c, db.alloc(&wg.g[0].scur, 16));
+        }
         pga_launch_dpw_topo(wg.g[0], nd.type, nd.strand, d_cbase, 1, n, st, n);
         pga_launch_dpw_chain(d_chain, 1, 0, n, na, wg.g[0], d_mc, wb, st);
-        bool sched = pga_dpw_use_sched();
         if (sched) {
             // the step schedule of this one contig (the chain's sched_b0 is 0); a buffer it does not fit sends the launch to k_dpw_dyn
             int32_t* d_bbase;
-            const int nbat = (n + 63) >> 6;
             const int32_t h_bbase[2] = {0, nbat};
             uint32_t h_cur[2] = {0, 0};
-            HIP_TRY(c, db.alloc(&wg.g[0].shdr, (size_t)nbat + 1)); HIP_TRY(c, db.alloc(&wg.g[0].sent, 2 * (size_t)DPW_SCHED_STRIDE * ((size_t)nbat + 1) + 16)); HIP_TRY(c, db.alloc(&wg.g[0].scur, 16));
             HIP_TRY(c, db.alloc(&d_bbase, 2));
             HIP_TRY(c, hipMemcpyAsync(d_bbase, h_bbase, sizeof h_bbase, hipMemcpyHostToDevice, st));
             pga_launch_dpw_sched(wg.g[0], d_cbase, d_bbase, 1, nbat, st);

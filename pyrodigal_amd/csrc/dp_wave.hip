@@ -296,6 +296,13 @@ __device__ __forceinline__ void load_ext(const DpwExt* __restrict__ e, DpwT& T) 
     T.cq0 = d.x; T.cq1 = d.y; T.cq2 = d.z; T.vm = d.w;
 }
 
+// cscore + sscore of node i of a chain.  A stop node carries no start scores, so its sum is 0.0 by definition and the element is not
+// read for it: the start scoring may leave it unwritten (ScoreParams::lean_stops), with whatever an earlier call left there.
+__device__ __forceinline__ double dpw_cs_of(const double* __restrict__ cs, const int i, const int kf) {
+    const double v = cs[i];
+    return (kf & 1) ? 0.0 : v;
+}
+
 __device__ __forceinline__ void load_target_w(DpwT& T, int& kfb, const WavePtrs& P, const int i0, const int lane, const int n, const double negc) {
     const int i = i0 + lane;
     const bool act = i < n;
@@ -304,7 +311,7 @@ __device__ __forceinline__ void load_target_w(DpwT& T, int& kfb, const WavePtrs&
     T.i = act ? i : -1;
     T.kind = act ? DPW_KIND(kfb) : -1; T.frame = DPW_FRAME(kfb);
     T.ndx = P.ndx[ii]; T.stop_val = P.stopv[ii]; T.lo = act ? P.lo[ii] : INT_MAX; T.q1 = P.q1[ii]; T.q2 = P.q2[ii];
-    T.cs = P.cs[ii]; T.csd = T.cs + negc;
+    T.cs = dpw_cs_of(P.cs, ii, kfb); T.csd = T.cs + negc;
     T.vm = 0; T.x0 = T.x1 = T.x2 = 0.0;
     T.dlo0 = T.dlo1 = T.dlo2 = INT_MAX; T.dhi0 = T.dhi1 = T.dhi2 = INT_MIN; T.cq0 = T.cq1 = T.cq2 = DPW_NONE;
     const int er = P.srank != nullptr ? P.srank[ii] : ii;       // asked for with the other topology fields, not behind them
@@ -654,7 +661,7 @@ k_dpw_dyn(const ChainDesc* __restrict__ chains, DpwGroupPtrs groups, const doubl
                 const int s_kf = P.kf[jj];
                 const int sk = DPW_KIND(s_kf);
                 SrcRegs R;
-                R.ndx = P.ndx[jj]; R.stop_val = P.stopv[jj]; R.score = P.score[jj]; R.cs = P.cs[jj];
+                R.ndx = P.ndx[jj]; R.stop_val = P.stopv[jj]; R.score = P.score[jj]; R.cs = dpw_cs_of(P.cs, jj, s_kf);
                 const int s_tbn = P.tbn[jj];
                 const int er = P.srank != nullptr ? P.srank[jj] : jj;
                 int vm = 0; R.x0 = R.x1 = R.x2 = 0.0;
@@ -1012,7 +1019,7 @@ k_dp_wave(const ChainDesc* __restrict__ chains, DpwGroupPtrs groups, const doubl
             kfb = P.kf[ii];
             T.i = in ? i : -1;
             T.ndx = P.ndx[ii]; T.stop_val = P.stopv[ii]; T.lo = in ? P.lo[ii] : INT_MAX; T.q1 = P.q1[ii]; T.q2 = P.q2[ii];
-            T.cs = P.cs[ii];
+            T.cs = dpw_cs_of(P.cs, ii, kfb);
             T.vm = 0; T.x0 = T.x1 = T.x2 = 0.0;
             T.dlo0 = T.dlo1 = T.dlo2 = INT_MAX; T.dhi0 = T.dhi1 = T.dhi2 = INT_MIN; T.cq0 = T.cq1 = T.cq2 = DPW_NONE;
             if (in && ((stops >> lane) & 1ull)) load_ext(P.ext + er, T);
@@ -1312,7 +1319,7 @@ bool pga_dpw_use_sched() {
 }
 
 void pga_launch_dpw_sched(const DpwTopoArrays& ta, const int32_t* d_cbase, const int32_t* d_bbase, int n_contigs, int max_batches, hipStream_t st) {
-    // (ta.scur is cleared by the topology kernel, which always runs in front of this one)
+    // (ta.scur is cleared by the topology kernel, which always runs in front of this one: the caller sets ta.scur before that launch)
     if (n_contigs <= 0 || max_batches <= 0) return;
     const char* fm = getenv("PGA_DPW_SCHED_MISS");
     hipLaunchKernelGGL(k_dpw_sched, dim3((unsigned)n_contigs, (unsigned)((max_batches + 15) / 16)), dim3(256), 0, st, d_cbase, d_bbase, ta, (fm && atoi(fm)) ? 1 : 0);

@@ -26,11 +26,12 @@
 #include <mutex>
 #include <new>
 #include <thread>
+#include <type_traits>
 #include <unordered_map>
 
 namespace {
 
-struct Buf { void* p = nullptr; size_t cap = 0; };
+struct Buf { void* p = nullptr; size_t cap = 0; bool fp = false; /* element type is floating point (pga_debug_poison) */ };
 
 }  // namespace
 
@@ -178,6 +179,28 @@ static void cache_put_result(void* p, size_t cap) {
     for (void* q : drop) (void)hipHostFree(q);
     if (p != nullptr) (void)hipHostFree(p);
 }
+// Test support: see include/pyrodigal_amd.h.  Only buffers of floating-point elements are filled: a pattern read as an index would be a
+// wild address, and a stale read has to show as a wrong answer, not as a fault.
+extern "C" int pga_debug_poison(pga_ctx* c, int byte, int64_t out[2]) {
+    if (out) out[0] = out[1] = 0;
+    if (!c || byte < -1 || byte > 255) { if (c) c->err = "pga_debug_poison: byte must be 0..255, or -1"; return PGA_EINVAL; }
+    HT(c, hipSetDevice(c->device));
+    HT(c, hipDeviceSynchronize());              // every stream of the context: the call's, the upload's
+    c->poison = byte;
+    if (byte < 0 || !c->finder) return PGA_OK;
+    FinderState* f = c->finder;
+    int64_t nb = 0, bytes = 0;
+    for (auto& kv : f->dev) if (kv.second.p && kv.second.fp) { HT(c, hipMemset(kv.second.p, byte, kv.second.cap)); nb++; bytes += (int64_t)kv.second.cap; }
+    for (auto& kv : f->pin) if (kv.second.p && kv.second.fp) { memset(kv.second.p, byte, kv.second.cap); nb++; bytes += (int64_t)kv.second.cap; }
+    {
+        std::lock_guard<std::mutex> g(f->spare_mu);
+        if (f->spare_p) { HT(c, hipMemset(f->spare_p, 'N', f->spare_cap)); nb++; bytes += (int64_t)f->spare_cap; }
+    }
+    HT(c, hipDeviceSynchronize());
+    if (out) { out[0] = nb; out[1] = bytes; }
+    return PGA_OK;
+}
+
 extern "C" void pga_release_cached(void) {
     std::lock_guard<std::mutex> g(g_cache_mu);
     for (auto& b : g_cache[0]) hipFree(b.p);
@@ -201,7 +224,16 @@ static hipError_t alloc_or_evict(int kind, Alloc alloc) {
     return had ? alloc() : e;
 }
 
-int ensure_dev(pga_ctx* c, const char* name, size_t bytes, void** out) {
+// Test support (pga_debug_poison): a block that a float buffer has just acquired -- from the runtime or from the cache, never written by
+// this context -- is filled with the context's poison byte.
+static int poison_fill(pga_ctx* c, void* p, size_t cap, int byte, bool pinned) {
+    if (pinned) { memset(p, byte, cap); return PGA_OK; }
+    HT(c, hipMemset(p, byte, cap));
+    HT(c, hipDeviceSynchronize());
+    return PGA_OK;
+}
+
+int ensure_dev(pga_ctx* c, const char* name, size_t bytes, void** out, bool fp = false) {
     Buf& b = c->finder->dev[name];
     if (b.cap < bytes || !b.p) {
         if (b.p) { hipFree(b.p); b.p = nullptr; b.cap = 0; }     // (not to the cache: kernels of this call may still read it; hipFree waits)
@@ -209,25 +241,27 @@ int ensure_dev(pga_ctx* c, const char* name, size_t bytes, void** out) {
         size_t want = bytes + (bytes >= ((size_t)64 << 20) ? bytes / 16 : bytes / 4) + 256;
         b.p = cache_take(0, c->device, want, &want);
         if (!b.p) HT(c, alloc_or_evict(0, [&] { return hipMalloc(&b.p, want); }));
-        b.cap = want;
+        b.cap = want; b.fp = fp;
+        if (c->poison >= 0 && fp) { const int rc = poison_fill(c, b.p, b.cap, c->poison, false); if (rc) return rc; }
     }
     *out = b.p;
     return PGA_OK;
 }
-int ensure_pin(pga_ctx* c, const char* name, size_t bytes, void** out) {
+int ensure_pin(pga_ctx* c, const char* name, size_t bytes, void** out, bool fp = false) {
     Buf& b = c->finder->pin[name];
     if (b.cap < bytes || !b.p) {
         if (b.p) { hipHostFree(b.p); b.p = nullptr; b.cap = 0; }
         size_t want = bytes + bytes / 4 + 256;
         b.p = cache_take(1, c->device, want, &want);
         if (!b.p) HT(c, alloc_or_evict(1, [&] { return hipHostMalloc(&b.p, want, hipHostMallocDefault); }));
-        b.cap = want;
+        b.cap = want; b.fp = fp;
+        if (c->poison >= 0 && fp) { const int rc = poison_fill(c, b.p, b.cap, c->poison, true); if (rc) return rc; }
     }
     *out = b.p;
     return PGA_OK;
 }
-#define DEVBUF(var, type, name, count) type* var; { void* p__; int rc__ = ensure_dev(c, name, sizeof(type) * (size_t)(count) + 64, &p__); if (rc__) return rc__; var = (type*)p__; }
-#define PINBUF(var, type, name, count) type* var; { void* p__; int rc__ = ensure_pin(c, name, sizeof(type) * (size_t)(count) + 64, &p__); if (rc__) return rc__; var = (type*)p__; }
+#define DEVBUF(var, type, name, count) type* var; { void* p__; int rc__ = ensure_dev(c, name, sizeof(type) * (size_t)(count) + 64, &p__, std::is_floating_point<type>::value); if (rc__) return rc__; var = (type*)p__; }
+#define PINBUF(var, type, name, count) type* var; { void* p__; int rc__ = ensure_pin(c, name, sizeof(type) * (size_t)(count) + 64, &p__, std::is_floating_point<type>::value); if (rc__) return rc__; var = (type*)p__; }
 
 // ---- tail: nodes of one contig for its winning model (device functions; one thread walks a contig's path) ----
 struct NodeView {
@@ -1234,18 +1268,24 @@ extern "C" int pga_cs_task_summary(int32_t n_contigs, const int32_t* nodes_per_c
 // The letters of a batch live in one device allocation.  hipMalloc / hipFree per call cost a device-wide synchronisation each
 // (hipFree waits for every stream of the device, i.e. for the other contexts' kernels), so a context keeps the allocation of the
 // last batch it freed and hands it to the next one that fits.
+// (pga_debug_poison: the letters are bytes, not floats -- 'N', so that the padding behind the last contig is defined and harmless)
+static hipError_t batch_poison(char* p, size_t cap) {
+    const hipError_t e = hipMemset(p, 'N', cap);
+    return e == hipSuccess ? hipDeviceSynchronize() : e;
+}
 static hipError_t batch_take_dev(pga_ctx* c, size_t bytes, char** out, size_t* cap) {
     FinderState* f = c->finder;
     {
         std::lock_guard<std::mutex> g(f->spare_mu);
         if (f->spare_p && f->spare_cap >= bytes && f->spare_cap <= 2 * bytes + (64u << 20)) {
             *out = (char*)f->spare_p; *cap = f->spare_cap; f->spare_p = nullptr; f->spare_cap = 0;
-            return hipSuccess;
+            return c->poison >= 0 ? batch_poison(*out, *cap) : hipSuccess;
         }
     }
     const size_t want = bytes + bytes / 8 + 256;
     *cap = want;
-    return hipMalloc((void**)out, want);
+    const hipError_t e = hipMalloc((void**)out, want);
+    return (e == hipSuccess && c->poison >= 0) ? batch_poison(*out, *cap) : e;
 }
 static void batch_give_dev(pga_ctx* c, char* p, size_t cap) {
     if (!p) return;
@@ -1599,7 +1639,7 @@ static int find_impl_cov(pga_ctx* c, const pga_batch* batch, const pga_params* p
         GroupArrays ga[4];
         for (int g = 0; g < NG; g++) {
             char nm[32];
-#define GBUF(field, type, count) { snprintf(nm, sizeof nm, #field "%d", g); void* p__; int rc__ = ensure_dev(c, nm, sizeof(type) * (size_t)(count) + 64, &p__); if (rc__) return rc__; ga[g].field = (type*)p__; }
+#define GBUF(field, type, count) { snprintf(nm, sizeof nm, #field "%d", g); void* p__; int rc__ = ensure_dev(c, nm, sizeof(type) * (size_t)(count) + 64, &p__, std::is_floating_point<type>::value); if (rc__) return rc__; ga[g].field = (type*)p__; }
             GBUF(df, uint8_t, total + 16)
             GBUF(c16, int32_t, (size_t)batch->n_tiles * 192 + 2)
             ga[g].tile0 = batch->d_tile0;
@@ -1878,7 +1918,7 @@ static int find_impl_cov(pga_ctx* c, const pga_batch* batch, const pga_params* p
             for (int g = 0; g < NG; g++) {
                 char nm[32];
                 const int64_t n = group_nodes[g] + 1;
-#define WBUF(field, type) { snprintf(nm, sizeof nm, "dpw_" #field "%d", g); void* p__; int rc__ = ensure_dev(c, nm, sizeof(type) * (size_t)n + 64, &p__); if (rc__) return rc__; wgroups.g[g].field = (type*)p__; }
+#define WBUF(field, type) { snprintf(nm, sizeof nm, "dpw_" #field "%d", g); void* p__; int rc__ = ensure_dev(c, nm, sizeof(type) * (size_t)n + 64, &p__, std::is_floating_point<type>::value); if (rc__) return rc__; wgroups.g[g].field = (type*)p__; }
                 WBUF(kf, uint8_t) WBUF(lo, int32_t) WBUF(q1, int32_t) WBUF(q2, int32_t)
 #undef WBUF
                 wgroups.g[g].ndx = ga[g].ndx; wgroups.g[g].stop_val = ga[g].stop_val; wgroups.g[g].srank = ga[g].srank;

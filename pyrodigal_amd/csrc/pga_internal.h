@@ -126,7 +126,7 @@ struct DpSegDev {        // device copies + workspace; all owned by the caller
     const struct DpwBuffers* wave_buf = nullptr;
 };
 // false: nothing to segment (plan left empty).  wave_walk: the segments are walked by the wave-batch kernel (a wavefront each: PGA_DP_SEG_WSLOTS,
-// 2048, of them at once) instead of the chain kernel (a workgroup each: PGA_DP_SEG_SLOTS, 256)
+// 4096, of them at once) instead of the chain kernel (a workgroup each: PGA_DP_SEG_SLOTS, 256)
 bool pga_dp_plan(const ChainDesc* h_chains, int n_chains, int64_t tot_nodes, DpSegPlan& plan, bool wave_walk = false);
 // device workspace of a segmented launch: its size, and its layout inside `arena` + the upload of the plan (the plan must
 // stay alive until the copies on `st` are done)
@@ -153,7 +153,8 @@ bool pga_dp_use_wave(int n_chains);
 void pga_launch_dpw_topo(const DpwTopoArrays& ta, const uint8_t* type, const int8_t* strand, const int32_t* d_cbase, int n_contigs, int n_nodes,
                          hipStream_t st, int max_contig_nodes = 0);
 // the step schedule of a group (after pga_launch_dpw_topo): d_bbase[c] = 64-node batches of the contigs before contig c; max_batches: of
-// the contig with the most nodes; ta.sent holds DPW_SCHED_STRIDE slots per batch; clears ta.scur first
+// the contig with the most nodes; ta.sent holds DPW_SCHED_STRIDE slots per batch.  ta.scur is NOT cleared here: the topology
+// kernel clears it, so ta.scur must be set (allocated) when pga_launch_dpw_topo is called
 void pga_launch_dpw_sched(const DpwTopoArrays& ta, const int32_t* d_cbase, const int32_t* d_bbase, int n_contigs, int max_batches, hipStream_t st);
 // chains[0..n_chains) of ONE group, contiguous in `off` from node_begin
 void pga_launch_dpw_chain(const ChainDesc* d_chains, int n_chains, int64_t node_begin, int64_t total_nodes, const NodeArrays& nodes,
@@ -226,6 +227,7 @@ struct pga_ctx {
     std::vector<double> set_score;                     //                 and that model's summed score, NaN: none
     std::vector<double> model_scores;                  // pga_model_scores: [contig][model_scores_nm] path scores, NaN: no contribution
     int model_scores_nm = 0;
+    int poison = -1;                                   // pga_debug_poison: the fill byte of newly acquired float buffers, -1: off
     std::vector<int64_t> render_seqnums;               // pga_render_seqnums: the seqnum of every contig of the batches rendered next (empty: first_seqnum + i)
 };
 void pga_render_release(pga_ctx*);   // render.hip: frees the buffers above
