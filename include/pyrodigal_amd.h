@@ -213,6 +213,35 @@ int  pga_batch_create(pga_ctx*, int32_t n_contigs, const char* const* seqs, cons
 /* The same from contigs that already lie back to back in one host buffer (offs[i + 1] == offs[i] + lens[i]), ideally pinned
  * (pga_fasta_next_packed): no host-side packing, one DMA of the whole batch.  The buffer may be reused when the call returns. */
 int  pga_batch_create_packed(pga_ctx*, int32_t n_contigs, const char* packed, const int64_t* offs, const int64_t* lens, pga_batch** out);
+/* The same from sequences that already lie in DEVICE memory (the samples of a generative model, the output of a GPU assembler or of a
+ * torch preprocessing step): one packing kernel on the device, no copy to the host and back.
+ *   Letters.  Letter j of contig i is f(e), where e is element elem_off[i] + j of d_data.  With elem_bytes == 1, e is read as an
+ *     unsigned byte; with elem_bytes == 4 or 8, as a signed little-endian integer.  With alphabet == NULL, which is allowed only for
+ *     elem_bytes == 1, f(e) = e: the bytes are the letters, as with host input.  Otherwise f(e) = alphabet[e] for 0 <= e < n_alphabet
+ *     (n_alphabet <= 256); every other value gives 'N', negative ones included.  Every alphabet entry must be an ASCII letter; lower
+ *     case is allowed and keeps its meaning for pga_batch_set_mask_case.
+ *   Source ranges.  The ranges of different contigs may overlap, repeat, or come in any order.  Nothing outside
+ *     [elem_off[i], elem_off[i] + lens[i]) is read: the padding of a padded row is never read.
+ *   Validation.  All of it happens on the host, before anything is allocated or launched; a failure returns PGA_EINVAL with a
+ *     pga_last_error that names the contig where one is concerned.  elem_bytes must be 1, 4 or 8.  alphabet may be NULL only with
+ *     elem_bytes == 1, and must hold only letters.  0 <= elem_off[i] and elem_off[i] + lens[i] <= n_elems.  The length limits are
+ *     those of pga_batch_create: a contig of at most 0x7fff0000 bases, a batch below 2^31 bases.  hipPointerGetAttributes must say
+ *     that d_data is device memory of the context's device: a host pointer is refused here, it is never dereferenced on the device.
+ *   Ordering.  The call records an event on producer_stream.  The context's upload stream is non-blocking, so it does not order itself
+ *     after the null stream on its own: the call makes it wait for that event, runs the pack there and synchronises that stream before
+ *     it returns, as the other two pga_batch_create* calls do.  On return the source may be overwritten or freed.  The concurrency
+ *     rule is that of pga_batch_create: one upload at a time per context, and it may run beside a pga_find_genes of the same context.
+ *   The batch cannot be told apart from one that pga_batch_create made from the same letters: every pga_batch_set_*,
+ *     pga_batch_replicate, pga_batch_trim_terminal_repeats, pga_find_genes*, pga_train*, pga_translate_genes and pga_render_genes
+ *     takes it unchanged. */
+int  pga_batch_create_device(pga_ctx*, int32_t n_contigs,
+        const void* d_data, int64_t n_elems, int32_t elem_bytes,          /* device memory of the context's device */
+        const int64_t* elem_off, const int64_t* lens,                     /* HOST arrays, n entries each */
+        const uint8_t* alphabet, int32_t n_alphabet,                      /* HOST, or NULL, 0 */
+        void* producer_stream,                                            /* hipStream_t, NULL = the null stream */
+        pga_batch** out);
+/* The packed letters of a resident batch (of any origin), one device-to-host copy on the upload stream, synchronised. */
+int  pga_batch_read(pga_ctx*, const pga_batch*, int32_t contig, char* out /* HOST, lens[contig] bytes; contig = -1: the whole batch, total bytes */);
 void pga_batch_free(pga_batch*);
 /* More mask sources, attached to the resident batch: every call that takes the batch (pga_find_genes*, pga_nodes_stage, pga_train*,
  * pga_find_coding_bases) honours them, with params.mask on or off, and pga_batch_replicate carries them to its copies.  A region from

@@ -11,12 +11,15 @@ __version__ = "0.1.0"
 _LIB_NAMES = ("GeneFinder", "Genes", "Gene", "Nodes", "Node", "Sequence", "TrainingInfo", "MetagenomicBin", "MetagenomicBins",
               "ConnectionScorer", "Mask", "Masks", "METAGENOMIC_BINS", "TRANSLATION_TABLES", "PRODIGAL_VERSION", "MIN_SINGLE_GENOME",
               "IDEAL_SINGLE_GENOME", "TerminalRepeats")
-__all__ = list(_LIB_NAMES) + ["TableSelection"]
+__all__ = list(_LIB_NAMES) + ["TableSelection", "DeviceSequences"]
 
 from .tables import TableSelection      # pure Python: the result of GeneFinder.select_translation_table
 
 
 def __getattr__(name):
+    if name == "DeviceSequences":       # sequences that already lie in device memory (the raw layer's class: GeneFinder.find_genes_batch takes it too)
+        from ._cabi import DeviceSequences
+        return DeviceSequences
     if name in _LIB_NAMES or name == "lib":
         import importlib
         try:

@@ -27,6 +27,7 @@ EXPORTS = [
     "pga_batch_set_sets", "pga_set_choice", "pga_model_scores", "pga_render_seqnums",
     "pga_batch_terminal_repeats", "pga_batch_trim_terminal_repeats", "pga_terminal_repeat_chunk",
     "pga_debug_poison",
+    "pga_batch_create_device", "pga_batch_read",
 ]
 STAGE_EXTRACT, STAGE_SCORE, STAGE_OVERLAP, STAGE_SEQUENCE = 1, 2, 3, 4
 
@@ -168,6 +169,9 @@ def load():
     L.pga_fasta_next_packed.argtypes = [vp, i64, i32, i32, _P(i32), _P(_P(ctypes.c_char_p)), _P(vp), _P(_P(i64)), _P(_P(i64))]
     L.pga_batch_create_packed.restype = ctypes.c_int
     L.pga_batch_create_packed.argtypes = [vp, i32, vp, _P(i64), _P(i64), _P(vp)]
+    L.pga_batch_create_device.restype = ctypes.c_int
+    L.pga_batch_create_device.argtypes = [vp, i32, vp, i64, i32, vp, vp, vp, i32, vp, _P(vp)]
+    L.pga_batch_read.restype = ctypes.c_int; L.pga_batch_read.argtypes = [vp, vp, i32, vp]
     L.pga_translate_genes.restype = ctypes.c_int
     L.pga_translate_genes.argtypes = [vp, vp, i64, vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, vp]
     L.pga_render_genes.restype = ctypes.c_int
@@ -546,6 +550,7 @@ class Batch:
         b = Batch.__new__(Batch)
         b.ctx, b.n, b.h = self.ctx, self.n, h
         b.total = None if self.total is None else int(self.total) - int(t.sum())
+        b.lengths = np.asarray(self.lengths, np.int64) - t
         flags = (t > 0).astype(np.uint8)
         if self.circular is not None:
             flags |= (self.circular[:self.n] != 0).astype(np.uint8)
@@ -566,11 +571,13 @@ class Batch:
                 arrays = None
         if arrays is not None:
             p_arr, l_arr, self.total = arrays
+            self.lengths = np.array(l_arr[:self.n], np.int64)
             ptrs = p_arr.ctypes.data_as(ctypes.POINTER(ctypes.c_char_p))
             lens = l_arr.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))
         else:
             seqs = [s.encode("ascii") if isinstance(s, str) else bytes(s) for s in seqs]
             self.total = sum(len(s) for s in seqs)
+            self.lengths = np.array([len(s) for s in seqs], np.int64)
             ptrs = (ctypes.c_char_p * max(1, self.n))(*seqs)
             lens = (ctypes.c_int64 * max(1, self.n))(*[len(s) for s in seqs])
         h = ctypes.c_void_p()
@@ -580,6 +587,22 @@ class Batch:
             _raise(ctx.L, ctx.h, rc, "pga_batch_create")
         self.h = h
 
+    def read(self, contig=None):
+        """The packed letters of the resident batch as ``bytes`` (``pga_batch_read``): those of contig ``contig``, or with ``None``
+        those of the whole batch, contig after contig.  One device-to-host copy.  Every way to make a batch records ``lengths``."""
+        if contig is None:
+            size, which = int(np.sum(self.lengths, dtype=np.int64)) if self.n else 0, -1
+        else:
+            which = int(contig)
+            if not 0 <= which < self.n:
+                raise IndexError(f"contig {which} of a batch of {self.n}")
+            size = int(self.lengths[which])
+        buf = ctypes.create_string_buffer(max(size, 1))
+        rc = self.ctx.L.pga_batch_read(self.ctx.h, self.h, which, buf)
+        if rc != PGA_OK:
+            _raise(self.ctx.L, self.ctx.h, rc, "pga_batch_read")
+        return buf.raw[:size]
+
     def close(self):
         if getattr(self, "h", None):
             self.ctx.L.pga_batch_free(self.h)
@@ -587,6 +610,184 @@ class Batch:
 
     def __del__(self):
         self.close()
+
+
+_DEVICE_DTYPES = {"|u1": 1, "|i1": 1, "<i4": 4, "<i8": 8}
+
+
+def _host_ints(values, name):
+    """Host integers of ``lengths`` / ``offsets`` as an int64 array: an object with ``tolist()`` (a tensor, an array) goes through it."""
+    if hasattr(values, "tolist"):
+        values = values.tolist()
+    values = list(values)
+    for v in values:
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+            raise TypeError(f"{name} must hold integers, not {type(v).__name__}")
+    return np.array(values, dtype=np.int64).reshape(-1)
+
+
+def normalise_alphabet(alphabet):
+    """``alphabet=`` of :class:`DeviceSequences` as the table ``pga_batch_create_device`` takes: ``None``, or ``bytes`` of at most 256
+    ASCII letters indexed by token id.  A ``str`` / ``bytes`` is that table; a ``{id: letter}`` dict is filled up with ``N``."""
+    if alphabet is None:
+        return None
+    if isinstance(alphabet, dict):
+        if not alphabet:
+            table = b""
+        else:
+            for k in alphabet:
+                if isinstance(k, bool) or not isinstance(k, (int, np.integer)):
+                    raise TypeError(f"alphabet ids must be integers, not {type(k).__name__}")
+                if not 0 <= int(k) < 256:
+                    raise ValueError(f"alphabet id {k} is outside 0 .. 255: the table has at most 256 entries")
+            t = bytearray(b"N" * (max(int(k) for k in alphabet) + 1))
+            for k, v in alphabet.items():
+                v = v.encode("ascii", "replace") if isinstance(v, str) else (bytes([v]) if isinstance(v, (int, np.integer)) else bytes(v))
+                if len(v) != 1:
+                    raise ValueError(f"alphabet id {k}: {v!r} is not one letter")
+                t[int(k)] = v[0]
+            table = bytes(t)
+    elif isinstance(alphabet, str):
+        table = alphabet.encode("ascii", "replace")
+    else:
+        table = bytes(alphabet)
+    if len(table) > 256:
+        raise ValueError(f"an alphabet has at most 256 entries, not {len(table)}")
+    for k, a in enumerate(table):
+        if not (65 <= a <= 90 or 97 <= a <= 122):
+            raise ValueError(f"alphabet entry {k} ({bytes([a])!r}) is not an ASCII letter")
+    return table
+
+
+class DeviceSequences:
+    """Sequences that already lie in device memory, as ``pga_batch_create_device`` takes them (the rule is in ``pyrodigal_amd.h``).
+
+    ``data``: any object with ``__cuda_array_interface__`` (a torch tensor on a ROCm device has it; a three-line wrapper around a raw
+    pointer also serves), 1-D or 2-D, dtype ``uint8`` / ``int8`` (letters, or token ids with an ``alphabet``), ``int32`` or ``int64``
+    (token ids), last dimension contiguous.  2-D: row i is sequence i, ``lengths[i] <= shape[1]`` of it (the padding is never read).
+    1-D: the sequences lie back to back, or start at ``offsets[i]``.  ``lengths`` / ``offsets``: host integers (an object with
+    ``tolist()`` goes through it).  ``alphabet``: ``None`` (bytes are letters), a ``bytes`` / ``str`` indexed by token id, or a
+    ``{id: letter}`` dict; any id outside it becomes ``N``.  ``stream``: the stream that produces ``data`` -- an int handle, an
+    object with ``.cuda_stream``, or ``None``: torch's current stream of the tensor's device when ``data`` is a torch tensor (and
+    torch is loaded), else the null stream.  The upload waits for the work that stream holds when it is called.
+
+    The object keeps ``data`` alive.  ``ds[k:l]`` and ``ds.take(indices)`` are ``DeviceSequences`` over the same memory with a subset
+    of the (offset, length) pairs: no data moves.  Every shape, dtype and length check raises before any device call."""
+
+    def __init__(self, data, lengths, *, offsets=None, alphabet=None, stream=None):
+        cai = getattr(data, "__cuda_array_interface__", None)
+        if not isinstance(cai, dict):
+            raise TypeError("data must have a __cuda_array_interface__ (a device tensor or array), not %r" % type(data).__name__)
+        typestr = str(cai.get("typestr"))
+        if typestr not in _DEVICE_DTYPES:
+            raise TypeError(f"data has dtype {typestr}: uint8, int8, int32 or int64 (|u1, |i1, <i4, <i8) is needed")
+        eb = _DEVICE_DTYPES[typestr]
+        shape = tuple(int(x) for x in cai["shape"])
+        if len(shape) not in (1, 2):
+            raise ValueError(f"data must be 1-D or 2-D, not {len(shape)}-D")
+        strides = cai.get("strides")
+        strides = None if strides is None else tuple(int(x) for x in strides)
+        if strides is not None and shape[-1] > 1 and strides[-1] != eb:
+            raise ValueError("the last dimension of data is not contiguous: call .contiguous() on it first")
+        lens = _host_ints(lengths, "lengths")
+        n = int(lens.size)
+        if n and lens.min() < 0:
+            raise ValueError(f"sequence {int(np.argmin(lens))} has the negative length {int(lens.min())}")
+        if len(shape) == 2:
+            if offsets is not None:
+                raise ValueError("offsets belong to 1-D data: row i of 2-D data is sequence i")
+            if n != shape[0]:
+                raise ValueError(f"lengths has {n} entries for {shape[0]} rows")
+            if n and lens.max() > shape[1]:
+                i = int(np.argmax(lens))
+                raise ValueError(f"sequence {i}: length {int(lens[i])} is more than the {shape[1]} columns of its row")
+            row = shape[1] if strides is None else strides[0] // eb
+            if strides is not None and shape[0] > 1 and (strides[0] % eb or strides[0] < 0):
+                raise ValueError("the rows of data do not lie a whole, positive number of elements apart: call .contiguous() on it first")
+            offs = np.arange(n, dtype=np.int64) * int(row)
+            n_elems = (shape[0] - 1) * int(row) + shape[1] if shape[0] and shape[1] else 0
+        else:
+            n_elems = shape[0]
+            if offsets is None:
+                offs = np.zeros(n, np.int64)
+                if n > 1:
+                    np.cumsum(lens[:-1], out=offs[1:])
+            else:
+                offs = _host_ints(offsets, "offsets")
+                if offs.size != n:
+                    raise ValueError(f"offsets has {offs.size} entries for {n} lengths")
+            if n:
+                bad = np.nonzero((offs < 0) | (offs + lens > n_elems))[0]
+                if bad.size:
+                    i = int(bad[0])
+                    raise ValueError(f"sequence {i}: elements [{int(offs[i])}, {int(offs[i])} + {int(lens[i])}) do not lie in the {n_elems} elements of data")
+        table = normalise_alphabet(alphabet)
+        if table is None and eb != 1:
+            raise ValueError(f"data of dtype {typestr} holds token ids: an alphabet is needed")
+        if n and lens.max() > 0x7fff0000:
+            raise ValueError(f"sequence {int(np.argmax(lens))} is longer than 0x7fff0000 bases")
+        ptr = cai["data"][0]
+        self.data = data
+        self.ptr = int(ptr) if ptr else 0
+        self.n_elems, self.elem_bytes = int(n_elems), eb
+        self.offsets, self.lengths = np.ascontiguousarray(offs, np.int64), np.ascontiguousarray(lens, np.int64)
+        self.alphabet = table
+        self.total = int(lens.sum()) if n else 0
+        self.stream = self._stream_of(data, stream)
+
+    @staticmethod
+    def _stream_of(data, stream):
+        if stream is None:
+            import sys
+            torch = sys.modules.get("torch")
+            if torch is not None and isinstance(data, torch.Tensor):
+                return int(torch.cuda.current_stream(data.device).cuda_stream)
+            return 0
+        if hasattr(stream, "cuda_stream"):
+            return int(stream.cuda_stream)
+        if isinstance(stream, bool) or not isinstance(stream, (int, np.integer)):
+            raise TypeError("stream must be an int handle, an object with .cuda_stream, or None, not %r" % type(stream).__name__)
+        return int(stream)
+
+    def __len__(self):
+        return int(self.lengths.size)
+
+    def take(self, indices):
+        """The sequences ``indices`` (any order, repeats allowed) as a ``DeviceSequences`` over the same memory."""
+        idx = np.asarray(_host_ints(indices, "indices"), dtype=np.int64)
+        n = len(self)
+        if idx.size and (idx.min() < -n or idx.max() >= n):
+            raise IndexError(f"an index is outside the {n} sequences")
+        sub = DeviceSequences.__new__(DeviceSequences)
+        sub.data, sub.ptr, sub.n_elems, sub.elem_bytes = self.data, self.ptr, self.n_elems, self.elem_bytes
+        sub.alphabet, sub.stream = self.alphabet, self.stream
+        sub.offsets, sub.lengths = np.ascontiguousarray(self.offsets[idx]), np.ascontiguousarray(self.lengths[idx])
+        sub.total = int(sub.lengths.sum()) if idx.size else 0
+        return sub
+
+    def __getitem__(self, index):
+        if isinstance(index, slice):
+            return self.take(range(*index.indices(len(self))))
+        return self.take([index])
+
+
+def _upload_device(self, ds):
+    """A resident :class:`Batch` from sequences that already lie in device memory (``pga_batch_create_device``): one packing kernel,
+    nothing goes through the host.  With ``find_genes`` on that batch only the gene records come home."""
+    if not isinstance(ds, DeviceSequences):
+        raise TypeError("upload_device takes a DeviceSequences, not %r" % type(ds).__name__)
+    b = Batch.__new__(Batch)
+    b.ctx, b.n, b.total, b.lengths = self, len(ds), ds.total, ds.lengths.copy()
+    ab = ds.alphabet
+    h = ctypes.c_void_p()
+    rc = self.L.pga_batch_create_device(self.h, b.n, ctypes.c_void_p(ds.ptr), ds.n_elems, ds.elem_bytes,
+                                        ctypes.c_void_p(ds.offsets.ctypes.data) if b.n else None,
+                                        ctypes.c_void_p(ds.lengths.ctypes.data) if b.n else None,
+                                        ab, 0 if ab is None else len(ab), ctypes.c_void_p(ds.stream), ctypes.byref(h))
+    if rc != PGA_OK:
+        _raise(self.L, self.h, rc, "pga_batch_create_device")
+    b.h = h
+    return b
 
 
 class _ResultOwner:
@@ -668,6 +869,7 @@ def _upload_packed(self, pb):
     """A resident :class:`Batch` straight from a reader's pinned staging arena: no host-side packing, one DMA."""
     b = Batch.__new__(Batch)
     b.ctx, b.n, b.total = self, pb.n, pb.total
+    b.lengths = np.array([int(x) for x in pb.lens[:pb.n]], np.int64)
     offs = (ctypes.c_int64 * max(1, pb.n + 1))(*[int(x) for x in pb.offs[:pb.n + 1]])
     lens = (ctypes.c_int64 * max(1, pb.n))(*[int(x) for x in pb.lens[:pb.n]])
     h = ctypes.c_void_p()
@@ -738,6 +940,7 @@ def _replicate(self, batch, contig_of_entry):
     b = Batch.__new__(Batch)
     b.ctx, b.n, b.h = self, int(coe.size), h
     b.total = None
+    b.lengths = np.asarray(batch.lengths, np.int64)[coe]
     if batch.circular is not None and batch.circular[coe].any():        # the flags travel with the contigs
         b.circular = np.ascontiguousarray(batch.circular[coe])
     if batch.sets is not None:                                           # and so do the set labels
@@ -806,7 +1009,7 @@ def _find_genes_batch(self, seqs, regions=None, mask_lowercase=False, circular=N
     :meth:`Batch.set_sets` takes it (meta mode).  ``trim_terminal_repeats``: as :func:`terminal_repeat_options` takes it -- the
     searched contigs that end in a copy of their first bases lose it on the device and are called as circles
     (``terminal_repeats`` of the result: the letters each contig lost)."""
-    b = Batch(self, seqs)
+    b = _upload_device(self, seqs) if isinstance(seqs, DeviceSequences) else Batch(self, seqs)
     t = b
     try:
         if sets is not None:
@@ -1150,6 +1353,7 @@ Context.train = _train
 Context.train_batch = _train_batch
 Context.upload = _upload
 Context.upload_packed = _upload_packed
+Context.upload_device = _upload_device
 Context.nodes_stage = _nodes_stage
 Context.find_genes = _find_genes
 Context.find_genes_batch = _find_genes_batch

@@ -107,6 +107,7 @@ struct FinderState {
     // while the current one is being worked on: double buffering of H2D against the kernels.  So the upload has a stream, a pinned
     // staging area and a worker pool of its own and touches nothing else of the context; one upload at a time per context (up_mu).
     std::mutex up_mu; WorkerPool up_pool; hipStream_t up_stream = nullptr; void* up_pin = nullptr; size_t up_pin_cap = 0;
+    hipEvent_t up_ev = nullptr;        // pga_batch_create_device: where the producer's stream stood when the call came
     hipEvent_t e_start = nullptr, e_stop = nullptr, e_dp0[4] = {}, e_dp1[4] = {};
     hipEvent_t e_aux[20] = {};      // around the topology / schedule launches of each group (pga_dp_timings), and the first of two connection-scoring launches
 };
@@ -1085,6 +1086,7 @@ void pga_finder_release(pga_ctx* c) {
     if (c->finder->spare_p) hipFree(c->finder->spare_p);
     if (c->finder->up_stream) { (void)hipStreamSynchronize(c->finder->up_stream); (void)hipStreamDestroy(c->finder->up_stream); }
     if (c->finder->up_pin && !cache_put(1, c->device, c->finder->up_pin, c->finder->up_pin_cap)) hipHostFree(c->finder->up_pin);
+    if (c->finder->up_ev) hipEventDestroy(c->finder->up_ev);
     if (c->finder->e_start) hipEventDestroy(c->finder->e_start);
     if (c->finder->e_stop) hipEventDestroy(c->finder->e_stop);
     for (int i = 0; i < 4; i++) { if (c->finder->e_dp0[i]) hipEventDestroy(c->finder->e_dp0[i]); if (c->finder->e_dp1[i]) hipEventDestroy(c->finder->e_dp1[i]); }
@@ -2777,6 +2779,7 @@ static int find_impl(pga_ctx* c, const pga_batch* batch, const pga_params* pp, c
 
 #include "train.inl"
 #include "circular.inl"
+#include "device_input.inl"
 #include "terminal_repeat.inl"
 
 extern "C" int pga_find_genes(pga_ctx* c, const pga_batch* batch, const pga_params* pp, pga_result** out) {

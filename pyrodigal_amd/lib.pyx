@@ -116,6 +116,9 @@ cdef extern from "pyrodigal_amd.h" nogil:
     int pga_translate_genes(pga_ctx*, const pga_batch*, int64_t n_genes, const pga_gene* genes, const int32_t* table_of_contig,
                             int unknown_residue, int include_stop, int strict, const int64_t* offsets, char* out)
     int pga_batch_create(pga_ctx*, int32_t n, const char* const* seqs, const int64_t* lens, pga_batch** out)
+    int pga_batch_create_device(pga_ctx*, int32_t n, const void* d_data, int64_t n_elems, int32_t elem_bytes, const int64_t* elem_off,
+                                const int64_t* lens, const uint8_t* alphabet, int32_t n_alphabet, void* producer_stream, pga_batch** out)
+    int pga_batch_read(pga_ctx*, const pga_batch*, int32_t contig, char* out)
     void pga_batch_free(pga_batch*)
     int pga_batch_set_regions(pga_batch*, const int32_t* off, const int32_t* iv)
     int pga_batch_set_mask_case(pga_batch*, int lower_case)
@@ -155,6 +158,7 @@ PRODIGAL_VERSION = "v2.6.3+c1e2d36"
 from pyrodigal_amd import __version__ as _VERSION      # one definition: the package's
 from pyrodigal_amd import tables as _tables
 from pyrodigal_amd.tables import TableSelection
+from pyrodigal_amd._cabi import DeviceSequences as _DeviceSequences     # sequences that already lie in device memory
 TRAINING_INFO_SIZE = 558392
 # select_translation_table: the most models (TrainingInfo, 558 392 bytes each) one device call loads
 _SELECT_MAX_MODELS = 256
@@ -1617,6 +1621,31 @@ cdef pga_batch* _trimmed_batch(pga_ctx* ctx, pga_batch* whole, size_t p_search, 
     return out
 
 
+cdef int _refuse_device_input(object x, str what) except -1:
+    if isinstance(x, _DeviceSequences):
+        raise TypeError("`%s` does not take sequences in device memory (a DeviceSequences): `find_genes_batch` does" % what)
+    return 0
+
+
+cdef pga_batch* _device_batch(pga_ctx* ctx, object dev) except? NULL:
+    """The resident batch of a `DeviceSequences`, packed on the device (`pga_batch_create_device`)."""
+    cdef pga_batch* batch = NULL
+    cdef int32_t n = len(dev), eb = dev.elem_bytes, n_alpha = 0
+    cdef int64_t n_elems = dev.n_elems
+    cdef size_t p_data = dev.ptr, p_off = dev.offsets.ctypes.data, p_len = dev.lengths.ctypes.data, p_stream = dev.stream
+    cdef bytes table = dev.alphabet
+    cdef const uint8_t* p_alpha = NULL
+    cdef int rc
+    if table is not None:
+        p_alpha = <const uint8_t*> PyBytes_AS_STRING(table); n_alpha = len(table)
+    with nogil:
+        rc = pga_batch_create_device(ctx, n, <const void*> p_data, n_elems, eb, <const int64_t*> p_off, <const int64_t*> p_len, p_alpha, n_alpha,
+                                     <void*> p_stream, &batch)
+    if rc != PGA_OK:
+        _raise_for(ctx, rc, "pga_batch_create_device")
+    return batch
+
+
 cdef class _FindRequest:
     """The sequences of one `find_genes` / `find_genes_batch` call, waiting for a device call to ride."""
     cdef list seqs              # Sequence objects
@@ -1804,6 +1833,7 @@ cdef class GeneFinder:
         gene may run across, exactly as if they were masked runs of `N` -- while the bases keep their identity for the GC content,
         the model choice, every score and the printed sequence.  They join the runs of unknown bases (`mask=True`), the runs of
         lower-case letters (`mask_lowercase=True`) and the regions a `Sequence` already carries; `genes.sequence.masks` is the union."""
+        _refuse_device_input(sequence, "find_genes")
         return self.find_genes_batch([sequence], regions=None if regions is None else [regions], circular=circular,
                                      trim_terminal_repeats=trim_terminal_repeats)[0]
 
@@ -1864,8 +1894,19 @@ cdef class GeneFinder:
 
         `trim_terminal_repeats`: `None` / `False`, `True` (every sequence, the default parameters), a `TerminalRepeats` (every
         sequence) or one entry per sequence, each `False`, `True` or one shared `TerminalRepeats`; see `find_genes`.  Independent
-        of `circular`: a sequence is called as a circle when either says so."""
+        of `circular`: a sequence is called as a circle when either says so.
+
+        `sequences` may be a `DeviceSequences`: sequences that already lie in device memory (a torch tensor of letters or token ids, a
+        raw device pointer), with every option above.  The batch is packed on the device (`pga_batch_create_device`), the request is
+        a device call of its own, and the packed letters come home once per device call (`pga_batch_read`: 1 byte per base, no Python
+        decode, no upload) so that `Genes.sequence`, `Gene.sequence()` and the host writers behave exactly as after host input.  The
+        zero-copy path, where only the gene records come home, is the raw layer: `_cabi.Context.upload_device` and
+        `Context.find_genes`."""
         cdef list circ = None
+        cdef object dev = None
+        if isinstance(sequences, _DeviceSequences):
+            dev = sequences
+            sequences = [None] * len(dev)         # (the options below only count them)
         cdef object set_ids = None
         cdef list tr_search = None
         cdef object tr_params = None
@@ -1902,6 +1943,8 @@ cdef class GeneFinder:
                     raise ValueError("`circular` has %d entries for %d sequences" % (len(circ), len(sequences)))
             if not any(circ):
                 circ = None
+        if dev is not None:
+            return self._find_genes_device(dev, translate, training_infos, regions, circ, set_ids, tr_search, tr_params)
         if training_infos is not None:
             return self._find_genes_models(sequences, translate, training_infos, regions, circ, tr_search, tr_params)
         if not self.meta and self.training_info is None:
@@ -2020,6 +2063,35 @@ cdef class GeneFinder:
             seqs.append(s)
         return seqs
 
+    cdef list _model_calls(self, list lengths, list tinfs):
+        """The device calls of a request with a model per sequence: consecutive runs of sequence indices under the base budget
+        (`coalesce_bases`) and at most four distinct translation tables, what one context's model set holds."""
+        cdef list calls = [], cur = []
+        cdef set tables = set()
+        cdef int64_t bases = 0, nb
+        cdef Py_ssize_t i
+        for i in range(len(lengths)):
+            nb = lengths[i]
+            tt = (<TrainingInfo> tinfs[i]).translation_table
+            if cur and (bases + nb > self.coalesce_bases or (tt not in tables and len(tables) == 4)):
+                calls.append(cur); cur = []; tables = set(); bases = 0
+            cur.append(i); tables.add(tt); bases += nb
+        calls.append(cur)
+        return calls
+
+    cdef _FinderSlot _own_slot(self):
+        """A context for one request alone (never coalesced with other callers', like the training takes one): waits until one is
+        free and marks it busy."""
+        cdef _FinderSlot slot
+        with self._cv:
+            while True:
+                slot = self._free_slot()
+                if slot is not None:
+                    break
+                self._cv.wait()
+            slot.busy = True
+        return slot
+
     def _find_genes_models(self, object sequences, bint translate, object training_infos, object regions=None, list circ=None,
                            list tr_search=None, object tr_params=None):
         """`find_genes_batch(..., training_infos=...)`: single mode with a model per sequence (`pga_find_genes_models`).  The
@@ -2036,32 +2108,14 @@ cdef class GeneFinder:
                 raise TypeError("training_infos[%d] is not a TrainingInfo (%r)" % (i, type(t).__name__))
         if not seqs:
             return []
-        # the device calls: consecutive runs of sequences under the base budget and at most four distinct tables
-        cdef list calls = []
-        cdef list cur = []
-        cdef set tables = set()
-        cdef int64_t bases = 0, nb
-        for i in range(len(seqs)):
-            nb = len((<Sequence> seqs[i]).data)
-            tt = (<TrainingInfo> tinfs[i]).translation_table
-            if cur and (bases + nb > self.coalesce_bases or (tt not in tables and len(tables) == 4)):
-                calls.append(cur); cur = []; tables = set(); bases = 0
-            cur.append(i); tables.add(tt); bases += nb
-        calls.append(cur)
+        cdef list calls = self._model_calls([len((<Sequence> q).data) for q in seqs], tinfs)
         cdef _FindRequest req
         cdef _FinderSlot slot
         cdef list out = []
         with self._lock:
             first_id = self._num_seq
             self._num_seq += len(seqs)
-        # a context for this request alone, like the training takes one
-        with self._cv:
-            while True:
-                slot = self._free_slot()
-                if slot is not None:
-                    break
-                self._cv.wait()
-            slot.busy = True
+        slot = self._own_slot()
         try:
             for idx in calls:
                 req = _FindRequest.__new__(_FindRequest)
@@ -2079,6 +2133,60 @@ cdef class GeneFinder:
                 self._release_slot(slot)
         return out
 
+    def _find_genes_device(self, object dev, bint translate, object training_infos, object regions, list circ, object set_ids,
+                           list tr_search, object tr_params):
+        """`find_genes_batch(DeviceSequences)`: a request of its own, never coalesced with other callers' sequences (as with `sets`).
+        With `training_infos` it splits into device calls as `_find_genes_models` does, each over a subset of the (offset, length)
+        pairs of `dev`: no data moves."""
+        cdef Py_ssize_t n = len(dev), i
+        cdef list tinfs = None, regs = None, calls
+        cdef _FindRequest req
+        cdef _FinderSlot slot
+        cdef list out = []
+        if training_infos is not None:
+            if self.meta:
+                raise ValueError("`training_infos` is a single-mode option: this finder is in meta mode")
+            tinfs = list(training_infos)
+            if len(tinfs) != n:
+                raise ValueError("`training_infos` has %d entries for %d sequences" % (len(tinfs), n))
+            for i, t in enumerate(tinfs):
+                if not isinstance(t, TrainingInfo):
+                    raise TypeError("training_infos[%d] is not a TrainingInfo (%r)" % (i, type(t).__name__))
+        elif not self.meta and self.training_info is None:
+            raise RuntimeError("cannot find genes without having trained in single mode")
+        if regions is not None:
+            regs = list(regions)
+            if len(regs) != n:
+                raise ValueError("`regions` has %d entries for %d sequences" % (len(regs), n))
+            for i in range(n):
+                regs[i] = _check_regions(regs[i], int(dev.lengths[i]), "sequence %d: " % i if n > 1 else "")
+        if n == 0:
+            return []
+        calls = [list(range(n))] if tinfs is None else self._model_calls(dev.lengths.tolist(), tinfs)
+        with self._lock:
+            first_id = self._num_seq
+            self._num_seq += n
+        slot = self._own_slot()
+        try:
+            for idx in calls:
+                whole = len(idx) == n
+                req = _FindRequest.__new__(_FindRequest)
+                req.seqs = [None] * len(idx)           # (the Sequence objects are made from the packed letters, in the device call)
+                req.circ = None if circ is None else (circ if whole else [circ[i] for i in idx])
+                req.sets = set_ids
+                req.tr_search = None if tr_search is None else (tr_search if whole else [tr_search[i] for i in idx])
+                req.tr_params = tr_params if tr_search is not None else None
+                req.first_id = first_id + idx[0]
+                out.extend(self._device_call(slot, req.seqs, translate, [req], None if tinfs is None else [tinfs[i] for i in idx],
+                                             dev if whole else dev.take(idx), None if regs is None else [regs[i] for i in idx]))
+                with self._lock:
+                    self.stats["device_calls"] += 1
+                    self.stats["sequences"] += len(idx)
+        finally:
+            with self._lock:
+                self._release_slot(slot)
+        return out
+
     def _find_genes_sets(self, list seqs, bint translate, object set_ids):
         """`find_genes_batch(..., sets=...)`: every set must sit in one device call, so the request takes a context for itself and is
         never coalesced with other callers' sequences."""
@@ -2088,13 +2196,7 @@ cdef class GeneFinder:
             req.first_id = self._num_seq
             self._num_seq += len(seqs)
         req.seqs = seqs; req.circ = None; req.sets = set_ids; req.tr_search = None; req.tr_params = None
-        with self._cv:
-            while True:
-                slot = self._free_slot()
-                if slot is not None:
-                    break
-                self._cv.wait()
-            slot.busy = True
+        slot = self._own_slot()
         try:
             out = self._device_call(slot, seqs, translate, [req])
             with self._lock:
@@ -2155,8 +2257,11 @@ cdef class GeneFinder:
             st["max_calls_per_device_call"] = len(take)
         return 0
 
-    cdef list _device_call(self, _FinderSlot slot, list seqs, bint translate, list take, list tinf_of=None):
+    cdef list _device_call(self, _FinderSlot slot, list seqs, bint translate, list take, list tinf_of=None, object dev=None,
+                           list dev_regions=None):
         # tinf_of: one TrainingInfo per sequence (single mode, a model per sequence: pga_find_genes_models), or None
+        # dev: the sequences lie in device memory (a DeviceSequences; dev_regions: their checked regions or None) -- the batch is packed
+        #      there, `seqs` holds placeholders and is filled from the packed letters, fetched once
         cdef int n = len(seqs), i, j, rc
         cdef const char** ptrs = <const char**> malloc(sizeof(char*) * max(n, 1))
         cdef int64_t* lens = <int64_t*> malloc(sizeof(int64_t) * max(n, 1))
@@ -2189,6 +2294,9 @@ cdef class GeneFinder:
         cdef object set_model = None, set_score = None, mscores = None
         cdef size_t p_sets = 0, p_smodel = 0, p_sscore = 0, p_mscores = 0
         cdef int n_models = 0
+        cdef object letters = None
+        cdef size_t p_letters = 0
+        cdef int64_t at = 0
         if ptrs == NULL or lens == NULL:
             free(ptrs); free(lens)
             raise MemoryError()
@@ -2222,7 +2330,7 @@ cdef class GeneFinder:
             cuts = np.full(max(n, 1), -1, np.int32)
             p_flags = flags.ctypes.data; p_cuts = cuts.ctypes.data
         try:
-            for i in range(n):
+            for i in range(n if dev is None else 0):
                 ptrs[i] = PyBytes_AS_STRING((<Sequence> seqs[i]).data)
                 lens[i] = len((<Sequence> seqs[i]).data)
                 if (<Sequence> seqs[i])._regions is not None:
@@ -2233,10 +2341,35 @@ cdef class GeneFinder:
                 loaded, moc = self._load_models_of(slot, tinf_of)
                 p_moc = moc.ctypes.data
             ctx = slot.ctx
+            if dev is not None:
+                batch = _device_batch(ctx, dev)
+                try:
+                    # the host copy of the letters: one device-to-host copy of the packed batch, cut into the usual Sequence objects
+                    letters = np.empty(max(int(dev.total), 1), np.uint8)
+                    p_letters = letters.ctypes.data
+                    with nogil:
+                        rc = pga_batch_read(ctx, batch, -1, <char*> p_letters)
+                    if rc != PGA_OK:
+                        _raise_for(ctx, rc, "pga_batch_read")
+                    seqs = []
+                    at = 0
+                    for i in range(n):
+                        tseq = Sequence(letters[at:at + int(dev.lengths[i])].tobytes(), mask=self.mask, mask_size=self.min_mask,
+                                        mask_lowercase=self.mask_lowercase)
+                        at += int(dev.lengths[i])
+                        if dev_regions is not None and dev_regions[i] is not None:
+                            tseq._regions = dev_regions[i]
+                            masked = True
+                        seqs.append(tseq)
+                    letters = None
+                except BaseException:
+                    pga_batch_free(batch)
+                    raise
             if tinf_of is not None:
-                rc = pga_batch_create(ctx, n, ptrs, lens, &batch)
-                if rc != PGA_OK:
-                    _raise_for(ctx, rc, "pga_batch_create")
+                if batch == NULL:
+                    rc = pga_batch_create(ctx, n, ptrs, lens, &batch)
+                    if rc != PGA_OK:
+                        _raise_for(ctx, rc, "pga_batch_create")
                 try:
                     if masked:
                         _attach_masks(ctx, batch, seqs, self.mask_lowercase)
@@ -2258,15 +2391,16 @@ cdef class GeneFinder:
                     pga_batch_free(batch)
                     if whole != NULL:
                         pga_batch_free(whole)
-            elif not translate and not masked and flags is None and set_ids is None and tr_params is None:
+            elif dev is None and not translate and not masked and flags is None and set_ids is None and tr_params is None:
                 with nogil:
                     rc = pga_find_genes_batch(ctx, n, ptrs, lens, &p, &res)
                 if rc != PGA_OK:
                     _raise_for(ctx, rc, "pga_find_genes_batch")
             else:
-                rc = pga_batch_create(ctx, n, ptrs, lens, &batch)
-                if rc != PGA_OK:
-                    _raise_for(ctx, rc, "pga_batch_create")
+                if batch == NULL:
+                    rc = pga_batch_create(ctx, n, ptrs, lens, &batch)
+                    if rc != PGA_OK:
+                        _raise_for(ctx, rc, "pga_batch_create")
                 try:
                     if masked:
                         _attach_masks(ctx, batch, seqs, self.mask_lowercase)
@@ -2493,6 +2627,7 @@ cdef class GeneFinder:
         Returns one read-only `TableSelection` per genome: `translation_table`, its `training_info`, `coding_density` and
         `coding_bases` of every candidate, `length`.  The genomes are uploaded once per device call and copied on the device for
         every candidate; only a few numbers per genome come back.  The finder's own `training_info` is left alone."""
+        _refuse_device_input(genomes, "select_translation_table")
         if self.meta:
             raise RuntimeError("cannot use training sequence in metagenomic mode")
         cands = _tables.check_candidates(candidates)
@@ -2680,6 +2815,7 @@ cdef class GeneFinder:
         keywords take a scalar or one value per genome.  Returns one `TrainingInfo` per genome, identical to
         `GeneFinder(<same options>).train(genome, ...)`; the finder's own `training_info` is left alone.  Device calls hold at most
         `coalesce_bases` bases and four translation tables; the results do not depend on that split."""
+        _refuse_device_input(genomes, "train_batch")
         if self.meta:
             raise RuntimeError("cannot use training sequence in metagenomic mode")
         cdef list gl = list(genomes)
@@ -2819,6 +2955,7 @@ cdef class GeneFinder:
         import warnings
         cdef Sequence seq
         cdef pga_params p
+        _refuse_device_input(sequence, "train")
         cdef pga_batch* batch = NULL
         cdef const char* ptr
         cdef int64_t length
