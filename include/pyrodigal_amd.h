@@ -367,6 +367,55 @@ int pga_nodes_stage(pga_ctx*, const pga_batch*, const pga_params*, int stage, in
 int pga_translate_genes(pga_ctx*, const pga_batch*, int64_t n_genes, const pga_gene* genes, const int32_t* table_of_contig,
                         int unknown_residue, int include_stop, int strict, const int64_t* offsets, char* out);
 
+/* The same proteins left on the device as token ids, in the consumer's layout, in the consumer's device tensor (a protein language
+ * model, an embedding search or a classifier in the same process): nothing of them comes to the host.
+ *   Residues.  For gene g, the residues are exactly what pga_translate_genes yields for that record under table_of_contig,
+ *     include_stop, strict and unknown_residue: M at a non-edge start codon, `*` at a stop, a gene across the origin of a circular
+ *     contig reading on at base 1.  n_g is their number.
+ *   Vocabulary.  vocab[128], int64 ids indexed by the 7-bit residue letter.  The caller builds it complete: every letter the kernel
+ *     can emit under the chosen options -- the 20 amino acids, `*` when include_stop, and the unknown_residue letter -- has an id, its
+ *     own or the caller's id for unknown.  The kernel does a plain look-up and never meets an unmapped letter.
+ *   Tokens of gene g.  [bos] if given, then vocab[r] for the first R_g residues, then [eos] if given.  With s the number of special
+ *     tokens (0 to 2), R_g = n_g without max_length (max_length == 0), otherwise R_g = min(n_g, max_length - s); max_length must be at
+ *     least s + 1.  len_g = s + R_g; a gene with no residues has len_g = s.
+ *   Layouts.  PGA_TOKENS_RAGGED: gene g is out[off[g] .. off[g + 1]), off the exclusive scan of len (the consumer's cu_seqlens);
+ *     elements at or beyond off[G] are not written.  PGA_TOKENS_PADDED: out is G rows of stride S = row_stride >= W = row_width >=
+ *     max(len_g) elements; row g holds its tokens, then pad, up to W: every one of the G x W elements is written, elements W .. S of a
+ *     row are not touched.
+ *   Elements.  uint8, int32 or int64 (elem_bytes 1, 4, 8).  Every id (vocabulary, bos, eos, pad) must fit the element type: 0 .. 255,
+ *     the int32 range, any int64.  d_out need only be element-aligned.
+ *   Sizes.  len and off are computed on the host from the gene coordinates; len_out[g] = len_g.  Nothing about sizes comes back from
+ *     the device.
+ *   Validation.  Everything is checked on the host before anything is allocated or launched; a failure returns PGA_EINVAL and
+ *     pga_last_error names the gene or field: element width, id ranges, max_length, W against the longest gene, n_out_elems against
+ *     the layout (off[G], or (G - 1) S + W), gene records inside their contig (the checks of pga_translate_genes), table validity,
+ *     the alignment of d_out, and hipPointerGetAttributes calling d_out device memory of the context's device: a host pointer is
+ *     refused there and never reaches a kernel.
+ *   Ordering.  d_out may be a fresh block from a caching allocator that earlier work on the caller's stream still uses.  The call
+ *     records an event on `stream`, makes the context's upload stream wait for it, runs the kernel there and synchronises before it
+ *     returns (the discipline of pga_batch_create_device).  On return the tensor is complete for any stream.  The concurrency rule is
+ *     that of pga_batch_create: one such call or upload at a time per context, and it may run beside a pga_find_genes of the context.
+ * Gene records come from the host, as for pga_translate_genes: any subset or reordering of a result's records may be passed. */
+#define PGA_TOKENS_RAGGED 0
+#define PGA_TOKENS_PADDED 1
+#define PGA_TOKEN_NONE    INT64_MIN   /* bos / eos: no such token */
+typedef struct pga_token_opts {
+    int32_t elem_bytes;         /* 1, 4 or 8 */
+    int32_t layout;             /* PGA_TOKENS_RAGGED or PGA_TOKENS_PADDED */
+    int64_t row_width;          /* W, padded layout (ignored for ragged) */
+    int64_t row_stride;         /* S, padded layout (ignored for ragged) */
+    int32_t include_stop, strict;
+    int32_t unknown_residue;    /* a single ASCII character, 'X' in the reference */
+    int32_t _pad;
+    int64_t max_length;         /* 0: no limit */
+    int64_t vocab[128];
+    int64_t bos, eos;           /* PGA_TOKEN_NONE: none */
+    int64_t pad;                /* padded layout */
+} pga_token_opts;
+int pga_translate_genes_tokens(pga_ctx*, const pga_batch*, int64_t n_genes, const pga_gene* genes, const int32_t* table_of_contig,
+                               const pga_token_opts*, void* d_out /* device memory of the context's device */, int64_t n_out_elems,
+                               void* stream /* hipStream_t, NULL = the null stream */, int64_t* len_out /* [n_genes], host */);
+
 /* ---- text output ------------------------------------------------------------------ */
 /* GFF, protein FASTA, gene FASTA, GenBank and the start-score file of gene records, rendered on the device from a resident
  * batch: byte for byte what the host writers Genes.write_gff / write_translations / write_genes / write_genbank / write_scores

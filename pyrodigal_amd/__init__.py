@@ -11,15 +11,16 @@ __version__ = "0.1.0"
 _LIB_NAMES = ("GeneFinder", "Genes", "Gene", "Nodes", "Node", "Sequence", "TrainingInfo", "MetagenomicBin", "MetagenomicBins",
               "ConnectionScorer", "Mask", "Masks", "METAGENOMIC_BINS", "TRANSLATION_TABLES", "PRODIGAL_VERSION", "MIN_SINGLE_GENOME",
               "IDEAL_SINGLE_GENOME", "TerminalRepeats")
-__all__ = list(_LIB_NAMES) + ["TableSelection", "DeviceSequences"]
+_CABI_NAMES = ("DeviceSequences", "ProteinTokens", "DeviceProteins")
+__all__ = list(_LIB_NAMES) + ["TableSelection"] + list(_CABI_NAMES)
 
 from .tables import TableSelection      # pure Python: the result of GeneFinder.select_translation_table
 
 
 def __getattr__(name):
-    if name == "DeviceSequences":       # sequences that already lie in device memory (the raw layer's class: GeneFinder.find_genes_batch takes it too)
-        from ._cabi import DeviceSequences
-        return DeviceSequences
+    if name in _CABI_NAMES:             # device-memory input and output (the raw layer's classes: GeneFinder takes and returns them too)
+        from . import _cabi
+        return getattr(_cabi, name)
     if name in _LIB_NAMES or name == "lib":
         import importlib
         try:

@@ -28,6 +28,7 @@ EXPORTS = [
     "pga_batch_terminal_repeats", "pga_batch_trim_terminal_repeats", "pga_terminal_repeat_chunk",
     "pga_debug_poison",
     "pga_batch_create_device", "pga_batch_read",
+    "pga_translate_genes_tokens",
 ]
 STAGE_EXTRACT, STAGE_SCORE, STAGE_OVERLAP, STAGE_SEQUENCE = 1, 2, 3, 4
 
@@ -98,6 +99,15 @@ class RenderResult(ctypes.Structure):
     _fields_ = [("n_contigs", ctypes.c_int32), ("_pad", ctypes.c_int32), ("text", Text * 5), ("t_kernels_ms", ctypes.c_double * 5)]
 
 
+class TokenOpts(ctypes.Structure):
+    _fields_ = [("elem_bytes", ctypes.c_int32), ("layout", ctypes.c_int32), ("row_width", ctypes.c_int64), ("row_stride", ctypes.c_int64),
+                ("include_stop", ctypes.c_int32), ("strict", ctypes.c_int32), ("unknown_residue", ctypes.c_int32), ("_pad", ctypes.c_int32),
+                ("max_length", ctypes.c_int64), ("vocab", ctypes.c_int64 * 128), ("bos", ctypes.c_int64), ("eos", ctypes.c_int64),
+                ("pad", ctypes.c_int64)]
+
+
+TOKENS_RAGGED, TOKENS_PADDED = 0, 1                         # pga_token_opts.layout
+TOKEN_NONE = -(1 << 63)                                     # pga_token_opts.bos / eos: no such token
 RENDER_FORMATS = ("gff", "faa", "fna", "gbk", "scores")     # PGA_RENDER_* bit order
 NODES_DEVICE = 2                                            # pga_params.want_nodes: keep the node arrays on the device
 GENE_DTYPE = np.dtype(Gene)
@@ -174,6 +184,8 @@ def load():
     L.pga_batch_read.restype = ctypes.c_int; L.pga_batch_read.argtypes = [vp, vp, i32, vp]
     L.pga_translate_genes.restype = ctypes.c_int
     L.pga_translate_genes.argtypes = [vp, vp, i64, vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, vp]
+    L.pga_translate_genes_tokens.restype = ctypes.c_int
+    L.pga_translate_genes_tokens.argtypes = [vp, vp, i64, vp, vp, _P(TokenOpts), vp, i64, vp, vp]
     L.pga_render_genes.restype = ctypes.c_int
     L.pga_render_genes.argtypes = [vp, vp, vp, i64, vp, vp, vp, vp, _P(RenderOpts), _P(_P(RenderResult))]
     L.pga_render_free.restype = None; L.pga_render_free.argtypes = [_P(RenderResult)]
@@ -266,6 +278,7 @@ class Context:
         if rc != PGA_OK:
             _raise(self.L, None, rc, "pga_create")
         self.h = h
+        self.device = int(device)
         self._models = []
 
     def close(self):
@@ -1140,6 +1153,253 @@ def _translate_genes(self, batch, result, tables=None, unknown_residue="X", incl
     return out[:int(off[-1])], off
 
 
+AMINO_ACIDS = "ACDEFGHIKLMNPQRSTVWY"
+_TOKEN_DTYPES = {"uint8": (1, "|u1", 0, 255), "int32": (4, "<i4", -(1 << 31), (1 << 31) - 1), "int64": (8, "<i8", -(1 << 63), (1 << 63) - 1)}
+
+
+def _token_id(value, name):
+    if isinstance(value, bool) or not isinstance(value, (int, np.integer)):
+        raise TypeError(f"{name} must be an integer id, not {type(value).__name__}")
+    return int(value)
+
+
+class ProteinTokens:
+    """How ``translate_tokens`` / ``find_proteins_batch`` write proteins into a device tensor (``pga_token_opts``; the rule is in
+    ``pyrodigal_amd.h``).
+
+    ``vocabulary``: a string (the id of a letter is its position) or a ``{letter: id}`` mapping.  Every letter a translation can hold
+    under the options needs an id -- the 20 amino acids, ``*`` with ``include_stop``, and ``unknown_residue`` -- its own or
+    ``unknown``; any other letter without an id of its own (a ``*`` inside a gene read under a foreign table when ``include_stop`` is
+    off) gets ``unknown``, or the id of ``unknown_residue``.  ``bos`` / ``eos``: ids put before / behind every protein, ``None``:
+    none.  ``pad`` fills the rows of the padded layout.  ``dtype``: ``"uint8"``, ``"int32"`` or ``"int64"``; every id must fit it.
+    ``max_length``: the most tokens of a gene, specials included (``eos`` survives the cut).  ``include_stop``, ``strict`` and
+    ``unknown_residue`` are those of ``translate_genes``.  Everything that needs no device is checked here.  Hashable and picklable."""
+
+    def __init__(self, vocabulary, *, unknown=None, bos=None, eos=None, pad=0, dtype="int64", layout="padded", max_length=None,
+                 include_stop=False, strict=True, unknown_residue="X"):
+        name = dtype if isinstance(dtype, str) else np.dtype(dtype).name
+        if name not in _TOKEN_DTYPES:
+            raise ValueError(f"dtype must be uint8, int32 or int64, not {name!r}")
+        if layout not in ("padded", "ragged"):
+            raise ValueError(f"layout must be \"padded\" or \"ragged\", not {layout!r}")
+        unk = unknown_residue.decode("ascii", "replace") if isinstance(unknown_residue, (bytes, bytearray)) else unknown_residue
+        if not isinstance(unk, str) or len(unk) != 1 or not 0 < ord(unk) < 128:
+            raise ValueError("`unknown_residue` must be a single ASCII character")
+        if isinstance(vocabulary, str):
+            if len(set(vocabulary)) != len(vocabulary):
+                raise ValueError("a letter occurs twice in the vocabulary string")
+            given = {ch: k for k, ch in enumerate(vocabulary)}
+        elif hasattr(vocabulary, "items"):
+            given = {}
+            for ch, v in vocabulary.items():
+                ch = ch.decode("ascii", "replace") if isinstance(ch, (bytes, bytearray)) else ch
+                if not isinstance(ch, str) or len(ch) != 1:
+                    raise ValueError(f"vocabulary key {ch!r} is not one letter")
+                given[ch] = _token_id(v, f"the id of {ch!r}")
+        else:
+            raise TypeError("vocabulary must be a string or a {letter: id} mapping, not %r" % type(vocabulary).__name__)
+        for ch in given:
+            if not 0 < ord(ch) < 128:
+                raise ValueError(f"vocabulary letter {ch!r} is not a 7-bit ASCII character")
+        self.unknown = None if unknown is None else _token_id(unknown, "unknown")
+        self.bos = None if bos is None else _token_id(bos, "bos")
+        self.eos = None if eos is None else _token_id(eos, "eos")
+        self.pad = _token_id(pad, "pad")
+        self.dtype, self.layout = name, layout
+        self.include_stop, self.strict, self.unknown_residue = bool(include_stop), bool(strict), unk
+        for ch in AMINO_ACIDS + ("*" if self.include_stop else "") + unk:
+            if ch not in given and self.unknown is None:
+                raise ValueError(f"the vocabulary has no id for {ch!r}, a letter the translation can hold, and `unknown` is None")
+        rest = self.unknown if self.unknown is not None else given[unk]
+        self.vocab = tuple(given.get(chr(k), rest) for k in range(128))
+        lo, hi = _TOKEN_DTYPES[name][2:]
+        for what, v in [(f"the id of {chr(k)!r}", self.vocab[k]) for k in range(128) if chr(k) in given] + \
+                       [("unknown", self.unknown), ("bos", self.bos), ("eos", self.eos), ("pad", self.pad)]:
+            if v is not None and not lo <= v <= hi:
+                raise ValueError(f"{what}, {v}, does not fit {name}")
+        self.specials = (self.bos is not None) + (self.eos is not None)
+        if max_length is not None:
+            max_length = _token_id(max_length, "max_length")
+            if max_length < self.specials + 1:
+                raise ValueError(f"max_length = {max_length} leaves no room for a residue beside {self.specials} special tokens")
+        self.max_length = max_length
+
+    elem_bytes = property(lambda self: _TOKEN_DTYPES[self.dtype][0])
+    typestr = property(lambda self: _TOKEN_DTYPES[self.dtype][1])
+
+    def _key(self):
+        return (self.vocab, self.unknown, self.bos, self.eos, self.pad, self.dtype, self.layout, self.max_length, self.include_stop,
+                self.strict, self.unknown_residue)
+
+    def __eq__(self, other):
+        return isinstance(other, ProteinTokens) and self._key() == other._key()
+
+    def __hash__(self):
+        return hash(self._key())
+
+    def __repr__(self):
+        return "pyrodigal_amd.ProteinTokens(dtype=%r, layout=%r, bos=%r, eos=%r, max_length=%r)" % (
+            self.dtype, self.layout, self.bos, self.eos, self.max_length)
+
+    def __reduce__(self):
+        return _protein_tokens_from_key, (self._key(),)
+
+    def lengths(self, genes):
+        """Tokens of every gene record, specials included (int64): host arithmetic on the coordinates, as the library does it."""
+        stop_edge = np.where(genes["strand"] == 1, genes["partial_end"], genes["partial_begin"]).astype(bool)
+        r = (genes["end"].astype(np.int64) - genes["begin"] + 1) // 3
+        if not self.include_stop:
+            r = r - (~stop_edge)
+        r = np.maximum(r, 0)
+        if self.max_length is not None:
+            r = np.minimum(r, self.max_length - self.specials)
+        return (r + self.specials).astype(np.int64)
+
+    def opts(self, row_width=0, row_stride=0):
+        o = TokenOpts()
+        o.elem_bytes, o.layout = self.elem_bytes, TOKENS_PADDED if self.layout == "padded" else TOKENS_RAGGED
+        o.row_width, o.row_stride = int(row_width), int(row_stride)
+        o.include_stop, o.strict, o.unknown_residue = int(self.include_stop), int(self.strict), ord(self.unknown_residue)
+        o.max_length = 0 if self.max_length is None else self.max_length
+        o.vocab[:] = self.vocab
+        o.bos = TOKEN_NONE if self.bos is None else self.bos
+        o.eos = TOKEN_NONE if self.eos is None else self.eos
+        o.pad = self.pad
+        return o
+
+
+def _protein_tokens_from_key(key):
+    p = ProteinTokens.__new__(ProteinTokens)
+    (p.vocab, p.unknown, p.bos, p.eos, p.pad, p.dtype, p.layout, p.max_length, p.include_stop, p.strict, p.unknown_residue) = key
+    p.specials = (p.bos is not None) + (p.eos is not None)
+    return p
+
+
+class _ContigProteins:
+    """``DeviceProteins.proteins``: entry i is a view of the rows (padded) or the slice (ragged) of contig i's genes -- no copy."""
+
+    def __init__(self, owner):
+        self.owner = owner
+
+    def __len__(self):
+        return len(self.owner.gene_begin) - 1
+
+    def __getitem__(self, i):
+        d = self.owner
+        i = range(len(self))[i]
+        a, b = int(d.gene_begin[i]), int(d.gene_begin[i + 1])
+        return d.tokens[a:b] if d.offsets is None else d.tokens[int(d.offsets[a]):int(d.offsets[b])]
+
+
+class DeviceProteins:
+    """Proteins of gene records as token ids in device memory.  ``tokens``: the tensor (``[G, W]`` padded, 1-D ragged); ``lengths``:
+    tokens of every gene (numpy int64, host); ``offsets``: ragged only, gene g is ``tokens[offsets[g]:offsets[g + 1]]``;
+    ``gene_begin``: the genes of contig i are rows ``gene_begin[i] .. gene_begin[i + 1]`` (``None`` when the records were not in
+    contig order); ``proteins[i]``: contig i's rows or slice as a view of ``tokens``."""
+
+    def __init__(self, tokens, lengths, offsets, gene_begin, device):
+        self.tokens, self.lengths, self.offsets, self.gene_begin, self.device = tokens, lengths, offsets, gene_begin, device
+
+    @property
+    def proteins(self):
+        if self.gene_begin is None:
+            raise ValueError("the gene records were not in contig order: there are no per-contig views")
+        return _ContigProteins(self)
+
+    def cu_seqlens(self):
+        """The exclusive scan of ``lengths`` as an int32 tensor on the tokens' device (torch)."""
+        import torch
+        cu = np.zeros(len(self.lengths) + 1, np.int64)
+        np.cumsum(self.lengths, out=cu[1:])
+        if cu[-1] >= 1 << 31:
+            raise OverflowError("more than 2^31 tokens do not fit an int32 cu_seqlens")
+        dev = self.tokens.device if isinstance(self.tokens, torch.Tensor) else torch.device("cuda", self.device)
+        return torch.from_numpy(cu.astype(np.int32)).to(dev)
+
+
+def tokens_into(L, ctx_h, batch_h, device, n_contigs, genes, tables, spec, out=None, stream=None):
+    """``pga_translate_genes_tokens`` on raw handles (what ``Context.translate_tokens`` and the finder's device call share): the token
+    ids of ``genes`` (GENE_DTYPE records of the resident batch) under ``tables`` into ``out``, or into a new torch tensor."""
+    if not isinstance(spec, ProteinTokens):
+        raise TypeError("the token rule must be a ProteinTokens, not %r" % type(spec).__name__)
+    genes = np.ascontiguousarray(genes, dtype=GENE_DTYPE)
+    tables = np.ascontiguousarray(tables, np.int32)
+    if tables.shape != (n_contigs,):
+        raise ValueError(f"tables has {tables.size} entries for {n_contigs} contigs")
+    n, eb = len(genes), spec.elem_bytes
+    lens = spec.lengths(genes)
+    off = np.zeros(n + 1, np.int64)
+    np.cumsum(lens, out=off[1:])
+    padded = spec.layout == "padded"
+    longest = int(lens.max()) if n else 0
+    if out is None:
+        try:
+            import torch
+        except ImportError:
+            raise TypeError("torch is not installed: pass out=, a device array with __cuda_array_interface__") from None
+        with torch.cuda.device(device):
+            out = torch.empty((n, longest) if padded else (int(off[-1]),), dtype=getattr(torch, spec.dtype), device="cuda")
+            if stream is None:
+                stream = int(torch.cuda.current_stream().cuda_stream)
+    cai = getattr(out, "__cuda_array_interface__", None)
+    if not isinstance(cai, dict):
+        raise TypeError("out must have a __cuda_array_interface__ (a device tensor or array), not %r" % type(out).__name__)
+    if str(cai.get("typestr")) != spec.typestr:
+        raise TypeError(f"out has dtype {cai.get('typestr')}: the rule writes {spec.dtype} ({spec.typestr})")
+    shape = tuple(int(x) for x in cai["shape"])
+    strides = cai.get("strides")
+    strides = None if strides is None else tuple(int(x) for x in strides)
+    if strides is not None and shape[-1] > 1 and strides[-1] != eb:
+        raise ValueError("the last dimension of out is not contiguous")
+    width = stride = 0
+    if padded:
+        if len(shape) != 2 or shape[0] != n:
+            raise ValueError(f"the padded layout needs a [{n}, W] tensor, not one of shape {shape}")
+        width = shape[1]
+        stride = width if strides is None or n < 2 else strides[0] // eb
+        if strides is not None and n > 1 and (strides[0] % eb or strides[0] < 0):
+            raise ValueError("the rows of out do not lie a whole, positive number of elements apart")
+        if width < longest:
+            raise ValueError(f"out has {width} columns: gene {int(np.argmax(lens))} has {longest} tokens")
+        n_out = (n - 1) * stride + width if n else 0
+    else:
+        if len(shape) != 1:
+            raise ValueError(f"the ragged layout needs a 1-D tensor, not one of shape {shape}")
+        if shape[0] < off[-1]:
+            raise ValueError(f"out has {shape[0]} elements: the genes have {int(off[-1])} tokens")
+        n_out = shape[0]
+    ptr = cai["data"][0]
+    len_out = np.zeros(max(n, 1), np.int64)
+    o = spec.opts(width, stride)
+    rc = L.pga_translate_genes_tokens(ctx_h, batch_h, n, ctypes.c_void_p(genes.ctypes.data), ctypes.c_void_p(tables.ctypes.data),
+                                      ctypes.byref(o), ctypes.c_void_p(int(ptr) if ptr else 0), n_out,
+                                      ctypes.c_void_p(DeviceSequences._stream_of(out, stream)), ctypes.c_void_p(len_out.ctypes.data))
+    if rc != PGA_OK:
+        _raise(L, ctx_h, rc, "pga_translate_genes_tokens")
+    assert np.array_equal(len_out[:n], lens)
+    gene_begin = None
+    if n == 0 or np.all(np.diff(genes["contig"]) >= 0):
+        gene_begin = np.searchsorted(genes["contig"], np.arange(n_contigs + 1)).astype(np.int64)
+    return DeviceProteins(out, lens, None if padded else off, gene_begin, device)
+
+
+def _translate_tokens(self, batch, result_or_genes, spec, out=None, tables=None, stream=None):
+    """Proteins of gene records of the resident ``batch`` as token ids in device memory (``pga_translate_genes_tokens``): nothing of
+    them comes to the host.  ``result_or_genes``: a result of ``find_genes`` on the batch, or gene records of one (any subset or
+    order; then with ``tables``).  ``spec``: a :class:`ProteinTokens`.  ``out``: any object with ``__cuda_array_interface__`` --
+    1-D for the ragged layout, ``[G, W]`` with a contiguous last dimension for the padded one; ``None``: a torch tensor is allocated
+    on the context's device under torch's current stream.  ``tables``: translation table per contig (default: that of the model that
+    won the contig).  ``stream``: the stream that last used ``out``, as in :class:`DeviceSequences`.  Returns a :class:`DeviceProteins`."""
+    genes = getattr(result_or_genes, "genes", result_or_genes)
+    if tables is None:
+        contigs = getattr(result_or_genes, "contigs", None)
+        if contigs is None:
+            raise ValueError("bare gene records carry no models: pass tables=, the translation table of every contig")
+        tts = [int(np.frombuffer(m[8:12].tobytes(), np.int32)[0]) for m in self._models]
+        tables = [tts[c["model"]] if c["model"] >= 0 else 11 for c in contigs]
+    return tokens_into(self.L, self.h, batch.h, self.device, batch.n, genes, tables, spec, out, stream)
+
+
 class RenderedText:
     """One format's text of a :meth:`Context.render_genes` call: ``data`` (bytes), ``contig_offsets`` (contig i is
     ``data[contig_offsets[i]:contig_offsets[i + 1]]``), ``fallback`` (lines the host rendered itself) and ``kernel_ms`` (device
@@ -1349,6 +1609,7 @@ def _splice_fallback(ctx, name, opts, data, coff, fb, genes, contigs, moc, ids, 
 
 Context.render_genes = _render_genes
 Context.translate_genes = _translate_genes
+Context.translate_tokens = _translate_tokens
 Context.train = _train
 Context.train_batch = _train_batch
 Context.upload = _upload

@@ -108,6 +108,7 @@ struct FinderState {
     // staging area and a worker pool of its own and touches nothing else of the context; one upload at a time per context (up_mu).
     std::mutex up_mu; WorkerPool up_pool; hipStream_t up_stream = nullptr; void* up_pin = nullptr; size_t up_pin_cap = 0;
     hipEvent_t up_ev = nullptr;        // pga_batch_create_device: where the producer's stream stood when the call came
+    void* up_dev = nullptr; size_t up_dev_cap = 0;   // pga_translate_genes_tokens: the device copy of its tables, kept and grown across calls
     hipEvent_t e_start = nullptr, e_stop = nullptr, e_dp0[4] = {}, e_dp1[4] = {};
     hipEvent_t e_aux[20] = {};      // around the topology / schedule launches of each group (pga_dp_timings), and the first of two connection-scoring launches
 };
@@ -1087,6 +1088,7 @@ void pga_finder_release(pga_ctx* c) {
     if (c->finder->up_stream) { (void)hipStreamSynchronize(c->finder->up_stream); (void)hipStreamDestroy(c->finder->up_stream); }
     if (c->finder->up_pin && !cache_put(1, c->device, c->finder->up_pin, c->finder->up_pin_cap)) hipHostFree(c->finder->up_pin);
     if (c->finder->up_ev) hipEventDestroy(c->finder->up_ev);
+    if (c->finder->up_dev) hipFree(c->finder->up_dev);
     if (c->finder->e_start) hipEventDestroy(c->finder->e_start);
     if (c->finder->e_stop) hipEventDestroy(c->finder->e_stop);
     for (int i = 0; i < 4; i++) { if (c->finder->e_dp0[i]) hipEventDestroy(c->finder->e_dp0[i]); if (c->finder->e_dp1[i]) hipEventDestroy(c->finder->e_dp1[i]); }
@@ -1315,6 +1317,34 @@ static int upload_resources(pga_ctx* c, size_t pin_bytes, hipStream_t* st, char*
     if (pin) *pin = (char*)f->up_pin;
     return PGA_OK;
 }
+
+// What translate.hip needs of the upload path (pga_translate_genes_tokens): the upload's stream and event, `bytes` of its pinned staging
+// area and as many of a device block that the context keeps and grows across calls.  up_mu is held from _take (when it returns PGA_OK)
+// to _give: one upload or token call at a time per context.
+struct pga_upload_lease { hipStream_t st; hipEvent_t ev; char* pin; char* dev; };
+static int upload_lease_fill(pga_ctx* c, size_t bytes, pga_upload_lease* out) {
+    FinderState* f = c->finder;
+    { const int rc = upload_resources(c, bytes, &out->st, &out->pin); if (rc) return rc; }
+    if (!f->up_ev) HT(c, hipEventCreateWithFlags(&f->up_ev, hipEventDisableTiming));
+    out->ev = f->up_ev;
+    if (f->up_dev_cap < bytes) {
+        // (every call on this stream ends with a synchronise: nothing still reads the old block)
+        if (f->up_dev) { (void)hipFree(f->up_dev); f->up_dev = nullptr; f->up_dev_cap = 0; }
+        const size_t want = bytes + bytes / 4 + 256;
+        HT(c, alloc_or_evict(0, [&] { return hipMalloc(&f->up_dev, want); }));
+        f->up_dev_cap = want;
+    }
+    out->dev = (char*)f->up_dev;
+    return PGA_OK;
+}
+int pga_upload_lease_take(pga_ctx* c, size_t bytes, pga_upload_lease* out) {
+    if (!c->finder) { const int rc = pga_finder_models_changed(c); if (rc) return rc; }
+    c->finder->up_mu.lock();
+    const int rc = upload_lease_fill(c, bytes, out);
+    if (rc) c->finder->up_mu.unlock();
+    return rc;
+}
+void pga_upload_lease_give(pga_ctx* c) { c->finder->up_mu.unlock(); }
 
 extern "C" int pga_batch_create(pga_ctx* c, int32_t n_contigs, const char* const* seqs, const int64_t* lens, pga_batch** out) {
     if (out) *out = nullptr;

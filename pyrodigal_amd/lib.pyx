@@ -13,6 +13,7 @@ works on whole node arrays, not node by node (SURVEY 8b: per-node granularity is
 `Gene.translate` and the `Genes.write_*` writers are host-side formatting, as in the reference.
 `GeneFinder.train` runs on the device too (`pga_train`).
 """
+import ctypes
 import gzip
 import threading
 
@@ -159,6 +160,7 @@ from pyrodigal_amd import __version__ as _VERSION      # one definition: the pac
 from pyrodigal_amd import tables as _tables
 from pyrodigal_amd.tables import TableSelection
 from pyrodigal_amd._cabi import DeviceSequences as _DeviceSequences     # sequences that already lie in device memory
+from pyrodigal_amd import _cabi                                          # proteins left there as token ids (ProteinTokens, tokens_into)
 TRAINING_INFO_SIZE = 558392
 # select_translation_table: the most models (TrainingInfo, 558 392 bytes each) one device call loads
 _SELECT_MAX_MODELS = 256
@@ -1646,6 +1648,13 @@ cdef pga_batch* _device_batch(pga_ctx* ctx, object dev) except? NULL:
     return batch
 
 
+cdef int _one_call_for_tokens(object tokens, list calls) except -1:
+    if tokens is not None and len(calls) > 1:
+        raise ValueError("`training_infos` would split this request into %d device calls (more than `coalesce_bases` bases or four "
+                         "translation tables in a row): find_proteins_batch writes one tensor per request" % len(calls))
+    return 0
+
+
 cdef class _FindRequest:
     """The sequences of one `find_genes` / `find_genes_batch` call, waiting for a device call to ride."""
     cdef list seqs              # Sequence objects
@@ -1654,6 +1663,8 @@ cdef class _FindRequest:
     cdef list circ              # one bool per sequence: called as a circle; None: all linear
     cdef object sets            # int32 per sequence: dense set id, -1: on its own; None: no sets (such a request rides alone)
     cdef bint translate
+    cdef object tokens          # find_proteins_batch: {"spec", "out", "stream"} -- the proteins also go to a device tensor, and the device
+                                # call leaves the DeviceProteins under "proteins" (such a request rides alone); None: no tokens
     cdef ssize_t first_id
     cdef int64_t bases
     cdef list out               # one Genes per sequence, filled in by the thread that ran the device call
@@ -1902,47 +1913,9 @@ cdef class GeneFinder:
         decode, no upload) so that `Genes.sequence`, `Gene.sequence()` and the host writers behave exactly as after host input.  The
         zero-copy path, where only the gene records come home, is the raw layer: `_cabi.Context.upload_device` and
         `Context.find_genes`."""
-        cdef list circ = None
-        cdef object dev = None
-        if isinstance(sequences, _DeviceSequences):
-            dev = sequences
-            sequences = [None] * len(dev)         # (the options below only count them)
-        cdef object set_ids = None
-        cdef list tr_search = None
-        cdef object tr_params = None
-        if trim_terminal_repeats is not None and trim_terminal_repeats is not False:
-            sequences = list(sequences)
-            if sets is not None:
-                raise ValueError("`sets` cannot be combined with `trim_terminal_repeats`: the second pass of a circular call holds only "
-                                 "the circular members of a set")
-            tr_search, tr_params = _terminal_repeat_option(trim_terminal_repeats, len(sequences))
-        if sets is not None:
-            sequences = list(sequences)
-            if not self.meta:
-                raise ValueError("`sets` is a meta-mode option: this finder is in single mode")
-            if training_infos is not None:
-                raise ValueError("`sets` cannot be combined with `training_infos` (a single-mode option)")
-            if circular is not None and circular is not False:
-                raise ValueError("`sets` cannot be combined with `circular`: the second pass of a circular call holds only the "
-                                 "circular members of a set")
-            labels = list(sets)
-            if len(labels) != len(sequences):
-                raise ValueError("`sets` has %d entries for %d sequences" % (len(labels), len(sequences)))
-            set_ids = np.full(max(len(labels), 1), -1, np.int32)
-            seen = {}
-            for k, lab in enumerate(labels):
-                if lab is not None:
-                    set_ids[k] = seen.setdefault(lab, len(seen))
-        if circular is not None and circular is not False:
-            sequences = list(sequences)
-            if circular is True:
-                circ = [True] * len(sequences)
-            else:
-                circ = [bool(x) for x in circular]
-                if len(circ) != len(sequences):
-                    raise ValueError("`circular` has %d entries for %d sequences" % (len(circ), len(sequences)))
-            if not any(circ):
-                circ = None
+        cdef list circ, tr_search
+        cdef object dev, set_ids, tr_params
+        dev, sequences, circ, set_ids, tr_search, tr_params = self._batch_options(sequences, training_infos, circular, sets, trim_terminal_repeats)
         if dev is not None:
             return self._find_genes_device(dev, translate, training_infos, regions, circ, set_ids, tr_search, tr_params)
         if training_infos is not None:
@@ -2028,6 +2001,84 @@ cdef class GeneFinder:
             raise req.error
         return req.out
 
+    def find_proteins_batch(self, object sequences, object tokens, *, object out=None, object stream=None, bint translate=False,
+                            object training_infos=None, object regions=None, object circular=None, object sets=None,
+                            object trim_terminal_repeats=None):
+        """`find_genes_batch`, and the proteins of every gene left in device memory as token ids: returns `(genes, proteins)`, the
+        list of `Genes` that `find_genes_batch` returns for the same arguments and a `DeviceProteins`.
+
+        `tokens`: a `ProteinTokens` -- vocabulary, special tokens, element type, padded or ragged layout.  The tensor is written on
+        the device while the batch is resident, under the translation table of the model that called each gene; row (or slice) g is
+        gene g of the request, contig after contig (`proteins.gene_begin`).  `out`: the device tensor to write (anything with
+        `__cuda_array_interface__`), `None`: a torch tensor allocated under torch's current stream; `stream`: the stream that last
+        used `out`.  Every option of `find_genes_batch` applies and `sequences` may be a `DeviceSequences`.  The request is a device
+        call of its own: one tensor per request, so a request that `training_infos` would split into several device calls is a
+        `ValueError`."""
+        if not isinstance(tokens, _cabi.ProteinTokens):
+            raise TypeError("`tokens` must be a ProteinTokens, not %r" % type(tokens).__name__)
+        cdef dict tok = {"spec": tokens, "out": out, "stream": stream, "proteins": None}
+        cdef list circ, tr_search
+        cdef object dev, set_ids, tr_params
+        dev, sequences, circ, set_ids, tr_search, tr_params = self._batch_options(sequences, training_infos, circular, sets, trim_terminal_repeats)
+        sequences = list(sequences)
+        if not sequences:
+            raise ValueError("find_proteins_batch needs at least one sequence")
+        if dev is not None:
+            genes = self._find_genes_device(dev, translate, training_infos, regions, circ, set_ids, tr_search, tr_params, tok)
+        elif training_infos is not None:
+            genes = self._find_genes_models(sequences, translate, training_infos, regions, circ, tr_search, tr_params, tok)
+        else:
+            if not self.meta and self.training_info is None:
+                raise RuntimeError("cannot find genes without having trained in single mode")
+            genes = self._find_genes_sets(self._wrap_sequences(sequences, regions), translate, set_ids, circ, tr_search, tr_params, tok)
+        return genes, tok["proteins"]
+
+    cdef tuple _batch_options(self, object sequences, object training_infos, object circular, object sets, object trim_terminal_repeats):
+        """The options of `find_genes_batch` / `find_proteins_batch`, checked against each other and against the number of sequences:
+        (the DeviceSequences or None, the sequences, circular flags, set ids, terminal-repeat search and its parameters)."""
+        cdef list circ = None
+        cdef object dev = None
+        if isinstance(sequences, _DeviceSequences):
+            dev = sequences
+            sequences = [None] * len(dev)         # (the options below only count them)
+        cdef object set_ids = None
+        cdef list tr_search = None
+        cdef object tr_params = None
+        if trim_terminal_repeats is not None and trim_terminal_repeats is not False:
+            sequences = list(sequences)
+            if sets is not None:
+                raise ValueError("`sets` cannot be combined with `trim_terminal_repeats`: the second pass of a circular call holds only "
+                                 "the circular members of a set")
+            tr_search, tr_params = _terminal_repeat_option(trim_terminal_repeats, len(sequences))
+        if sets is not None:
+            sequences = list(sequences)
+            if not self.meta:
+                raise ValueError("`sets` is a meta-mode option: this finder is in single mode")
+            if training_infos is not None:
+                raise ValueError("`sets` cannot be combined with `training_infos` (a single-mode option)")
+            if circular is not None and circular is not False:
+                raise ValueError("`sets` cannot be combined with `circular`: the second pass of a circular call holds only the "
+                                 "circular members of a set")
+            labels = list(sets)
+            if len(labels) != len(sequences):
+                raise ValueError("`sets` has %d entries for %d sequences" % (len(labels), len(sequences)))
+            set_ids = np.full(max(len(labels), 1), -1, np.int32)
+            seen = {}
+            for k, lab in enumerate(labels):
+                if lab is not None:
+                    set_ids[k] = seen.setdefault(lab, len(seen))
+        if circular is not None and circular is not False:
+            sequences = list(sequences)
+            if circular is True:
+                circ = [True] * len(sequences)
+            else:
+                circ = [bool(x) for x in circular]
+                if len(circ) != len(sequences):
+                    raise ValueError("`circular` has %d entries for %d sequences" % (len(circ), len(sequences)))
+            if not any(circ):
+                circ = None
+        return dev, sequences, circ, set_ids, tr_search, tr_params
+
     cdef list _wrap_sequences(self, object sequences, object regions=None):
         """The finder's masking rule on every sequence (the reference always re-wraps, lib.pyx:5433-5438): a Sequence that already
         follows it is used as it is.  The regions a Sequence carries stay with it; `regions` (one entry per sequence or None) are
@@ -2093,7 +2144,7 @@ cdef class GeneFinder:
         return slot
 
     def _find_genes_models(self, object sequences, bint translate, object training_infos, object regions=None, list circ=None,
-                           list tr_search=None, object tr_params=None):
+                           list tr_search=None, object tr_params=None, object tokens=None):
         """`find_genes_batch(..., training_infos=...)`: single mode with a model per sequence (`pga_find_genes_models`).  The
         sequences go in device calls of at most `coalesce_bases` bases and four translation tables (what one context's model set
         holds); identical `TrainingInfo` objects are loaded once per call."""
@@ -2109,6 +2160,7 @@ cdef class GeneFinder:
         if not seqs:
             return []
         cdef list calls = self._model_calls([len((<Sequence> q).data) for q in seqs], tinfs)
+        _one_call_for_tokens(tokens, calls)
         cdef _FindRequest req
         cdef _FinderSlot slot
         cdef list out = []
@@ -2123,6 +2175,7 @@ cdef class GeneFinder:
                 req.circ = [circ[i] for i in idx] if circ is not None else None
                 req.tr_search = [tr_search[i] for i in idx] if tr_search is not None else None
                 req.tr_params = tr_params if tr_search is not None else None
+                req.tokens = tokens
                 req.first_id = first_id + idx[0]
                 out.extend(self._device_call(slot, req.seqs, translate, [req], [tinfs[i] for i in idx]))
                 with self._lock:
@@ -2134,7 +2187,7 @@ cdef class GeneFinder:
         return out
 
     def _find_genes_device(self, object dev, bint translate, object training_infos, object regions, list circ, object set_ids,
-                           list tr_search, object tr_params):
+                           list tr_search, object tr_params, object tokens=None):
         """`find_genes_batch(DeviceSequences)`: a request of its own, never coalesced with other callers' sequences (as with `sets`).
         With `training_infos` it splits into device calls as `_find_genes_models` does, each over a subset of the (offset, length)
         pairs of `dev`: no data moves."""
@@ -2163,6 +2216,7 @@ cdef class GeneFinder:
         if n == 0:
             return []
         calls = [list(range(n))] if tinfs is None else self._model_calls(dev.lengths.tolist(), tinfs)
+        _one_call_for_tokens(tokens, calls)
         with self._lock:
             first_id = self._num_seq
             self._num_seq += n
@@ -2176,6 +2230,7 @@ cdef class GeneFinder:
                 req.sets = set_ids
                 req.tr_search = None if tr_search is None else (tr_search if whole else [tr_search[i] for i in idx])
                 req.tr_params = tr_params if tr_search is not None else None
+                req.tokens = tokens
                 req.first_id = first_id + idx[0]
                 out.extend(self._device_call(slot, req.seqs, translate, [req], None if tinfs is None else [tinfs[i] for i in idx],
                                              dev if whole else dev.take(idx), None if regs is None else [regs[i] for i in idx]))
@@ -2187,15 +2242,18 @@ cdef class GeneFinder:
                 self._release_slot(slot)
         return out
 
-    def _find_genes_sets(self, list seqs, bint translate, object set_ids):
+    def _find_genes_sets(self, list seqs, bint translate, object set_ids, list circ=None, list tr_search=None, object tr_params=None,
+                         object tokens=None):
         """`find_genes_batch(..., sets=...)`: every set must sit in one device call, so the request takes a context for itself and is
-        never coalesced with other callers' sequences."""
+        never coalesced with other callers' sequences.  `find_proteins_batch` on host sequences rides the same way, with the options
+        a set cannot have."""
         cdef _FindRequest req = _FindRequest.__new__(_FindRequest)
         cdef _FinderSlot slot
         with self._lock:
             req.first_id = self._num_seq
             self._num_seq += len(seqs)
-        req.seqs = seqs; req.circ = None; req.sets = set_ids; req.tr_search = None; req.tr_params = None
+        req.seqs = seqs; req.circ = circ; req.sets = set_ids; req.tr_search = tr_search; req.tr_params = tr_params if tr_search is not None else None
+        req.tokens = tokens
         slot = self._own_slot()
         try:
             out = self._device_call(slot, seqs, translate, [req])
@@ -2285,6 +2343,7 @@ cdef class GeneFinder:
         cdef object cuts = None
         cdef size_t p_flags = 0, p_cuts = 0
         cdef object set_ids = (<_FindRequest> take[0]).sets if len(take) == 1 else None
+        cdef object tok = (<_FindRequest> take[0]).tokens if len(take) == 1 else None
         cdef object tr_params = None                 # the terminal-repeat search of this call, or None: no request asks for one
         cdef object tr_flags = None, tr_match = None, tr_trim = None
         cdef size_t p_search = 0, p_match = 0, p_trim = 0
@@ -2387,11 +2446,13 @@ cdef class GeneFinder:
                         pga_circular_cuts(ctx, n, <int32_t*> p_cuts)
                     if translate:
                         prot, prot_off, tables = self._translate(ctx, batch, res, n, tinf_of)
+                    if tok is not None:
+                        self._tokens(ctx, batch, res, n, tinf_of, tok)
                 finally:
                     pga_batch_free(batch)
                     if whole != NULL:
                         pga_batch_free(whole)
-            elif dev is None and not translate and not masked and flags is None and set_ids is None and tr_params is None:
+            elif dev is None and not translate and not masked and flags is None and set_ids is None and tr_params is None and tok is None:
                 with nogil:
                     rc = pga_find_genes_batch(ctx, n, ptrs, lens, &p, &res)
                 if rc != PGA_OK:
@@ -2431,6 +2492,8 @@ cdef class GeneFinder:
                     if translate:
                         prot_off = np.zeros(res.n_genes + 1, np.int64)
                         prot, prot_off, tables = self._translate(ctx, batch, res, n, None)
+                    if tok is not None:
+                        self._tokens(ctx, batch, res, n, None, tok)
                 finally:
                     pga_batch_free(batch)
                     if whole != NULL:
@@ -2503,13 +2566,21 @@ cdef class GeneFinder:
                 pga_result_free(res)
         return out
 
-    cdef tuple _translate(self, pga_ctx* ctx, pga_batch* batch, pga_result* res, int n, list tinf_of):
-        """Proteins of every gene of `res` on the device: (letters, offsets, table of every contig)."""
-        cdef int i, rc
-        cdef int64_t j, ng
+    cdef int _tokens(self, pga_ctx* ctx, pga_batch* batch, pga_result* res, int n, list tinf_of, dict tok) except -1:
+        """The proteins of every gene of `res` as token ids into the request's device tensor, while the batch is resident
+        (`pga_translate_genes_tokens` through the raw layer's marshalling): leaves the `DeviceProteins` in `tok`."""
+        genes = np.zeros(0, _cabi.GENE_DTYPE)
+        if res.n_genes > 0:
+            genes = np.frombuffer(PyBytes_FromStringAndSize(<const char*> res.genes, res.n_genes * sizeof(pga_gene)), dtype=_cabi.GENE_DTYPE)
+        tables = self._tables_of(res, n, tinf_of)[:n]
+        tok["proteins"] = _cabi.tokens_into(_cabi.load(), ctypes.c_void_p(<size_t> ctx), ctypes.c_void_p(<size_t> batch), self.device, n,
+                                            genes, tables, tok["spec"], tok["out"], tok["stream"])
+        return 0
+
+    cdef object _tables_of(self, pga_result* res, int n, list tinf_of):
+        """The translation table every contig of `res` was called under (int32; 11 where no model won)."""
+        cdef int i
         cdef pga_contig_result* cr
-        cdef size_t p_tab, p_off, p_out
-        prot_off = np.zeros(res.n_genes + 1, np.int64)
         tables = np.full(max(n, 1), 11, np.int32)
         for i in range(n):
             cr = &res.contigs[i]
@@ -2520,6 +2591,15 @@ cdef class GeneFinder:
                 tables[i] = (<TrainingInfo> tinf_of[i]).translation_table
             else:
                 tables[i] = (<TrainingInfo> self.training_info).translation_table
+        return tables
+
+    cdef tuple _translate(self, pga_ctx* ctx, pga_batch* batch, pga_result* res, int n, list tinf_of):
+        """Proteins of every gene of `res` on the device: (letters, offsets, table of every contig)."""
+        cdef int rc
+        cdef int64_t j, ng
+        cdef size_t p_tab, p_off, p_out
+        prot_off = np.zeros(res.n_genes + 1, np.int64)
+        tables = self._tables_of(res, n, tinf_of)
         for j in range(res.n_genes):
             prot_off[j + 1] = prot_off[j] + (res.genes[j].end - res.genes[j].begin + 1) // 3
         prot = np.zeros(max(int(prot_off[res.n_genes]), 1), np.uint8)
