@@ -1686,6 +1686,53 @@ cdef inline void _signal(_FindRequest r):
         r.sem.release()
 
 
+cdef class _CallState:
+    """One device call: the options of the requests that ride it, per sequence of the call (`_call_options`), and what the call
+    reports back per sequence (`_resident_call`), for `_genes_of_call` to read."""
+    cdef list ids               # the number of every sequence
+    cdef object flags, cuts     # uint8 / int32 per sequence: called as a circle, and where it was cut open; None: no request names a
+                                # circle or searches for terminal repeats
+    cdef object tr_params       # the terminal-repeat search of this call, or None: no request asks for one
+    cdef object tr_flags, tr_match, tr_trim     # uint8 / int32 / int32 per sequence: searched, the longest repeat, the bases taken off
+    cdef object set_ids         # the sets of a request that rides alone, or None
+    cdef object tok             # the tokens of a request that rides alone, or None
+    # reported by the call
+    cdef int n_models           # with sets: the models, and per sequence the model and score of its set and [n_models] path scores
+    cdef object set_model, set_score, model_scores
+    cdef object prot, prot_off, tables          # with translate: the proteins of `_translate`
+
+
+cdef _CallState _call_options(list take, int n):
+    """The state of one device call over n sequences, with the options of the requests in `take`, which ride it."""
+    cdef _CallState o = _CallState.__new__(_CallState)
+    cdef _FindRequest r
+    cdef Py_ssize_t i = 0, j
+    cdef bint circles = False
+    o.ids = []
+    for r in take:
+        for j in range(len(r.seqs)):
+            o.ids.append(r.first_id + j)
+        if r.circ is not None:
+            circles = True
+        if r.tr_params is not None:
+            o.tr_params = r.tr_params
+    if len(take) == 1:
+        o.set_ids = (<_FindRequest> take[0]).sets
+        o.tok = (<_FindRequest> take[0]).tokens
+    if o.tr_params is not None:
+        o.tr_flags = np.zeros(max(n, 1), np.uint8); o.tr_match = np.zeros(max(n, 1), np.int32); o.tr_trim = np.zeros(max(n, 1), np.int32)
+    if circles or o.tr_params is not None:         # (a trimmed sequence is a circle: the flags are completed after the search)
+        o.flags = np.zeros(max(n, 1), np.uint8)
+        o.cuts = np.full(max(n, 1), -1, np.int32)
+        for r in take:
+            if r.circ is not None:
+                o.flags[i:i + len(r.seqs)] = r.circ
+            if r.tr_search is not None and o.tr_params is not None:
+                o.tr_flags[i:i + len(r.seqs)] = r.tr_search
+            i += len(r.seqs)
+    return o
+
+
 cdef class GeneFinder:
     """A configurable gene finder for genomes and metagenomes, running on one MI355X.
 
@@ -2143,48 +2190,77 @@ cdef class GeneFinder:
             slot.busy = True
         return slot
 
+    cdef int _single_mode_only(self) except -1:
+        if self.meta:
+            raise ValueError("`training_infos` is a single-mode option: this finder is in meta mode")
+        return 0
+
+    cdef list _checked_training_infos(self, list tinfs, Py_ssize_t n):
+        """`training_infos=` of a call over n sequences, as a list: one `TrainingInfo` per sequence."""
+        if len(tinfs) != n:
+            raise ValueError("`training_infos` has %d entries for %d sequences" % (len(tinfs), n))
+        for i, t in enumerate(tinfs):
+            if not isinstance(t, TrainingInfo):
+                raise TypeError("training_infos[%d] is not a TrainingInfo (%r)" % (i, type(t).__name__))
+        return tinfs
+
+    cdef list _own_calls(self, list calls, list seqs, list circ, object set_ids, list tr_search, object tr_params, object tokens,
+                         list tinfs=None, object dev=None, list regs=None):
+        """The device calls of a request that takes a context for itself: `calls` holds the sequence indices of every call (runs in
+        input order), the options come per sequence of the request.  Returns (request, tinf_of, dev, dev_regions) per device call,
+        as `_run_alone` takes them; a call over part of a `DeviceSequences` takes its (offset, length) pairs: no data moves."""
+        cdef _FindRequest req
+        cdef list out = []
+        for idx in calls:
+            req = _FindRequest.__new__(_FindRequest)
+            req.seqs = [seqs[i] for i in idx]
+            req.circ = None if circ is None else [circ[i] for i in idx]
+            req.sets = set_ids
+            req.tr_search = None if tr_search is None else [tr_search[i] for i in idx]
+            req.tr_params = tr_params if tr_search is not None else None
+            req.tokens = tokens
+            out.append((req, None if tinfs is None else [tinfs[i] for i in idx],
+                        None if dev is None else (dev if len(idx) == len(seqs) else dev.take(idx)),
+                        None if regs is None else [regs[i] for i in idx]))
+        return out
+
+    cdef list _run_alone(self, list calls, bint translate):
+        """Run the device calls of one request (`_own_calls`) in order on a context taken for it alone, never coalesced with other
+        callers' sequences: numbers the sequences, counts the calls, returns the `Genes` in input order."""
+        cdef _FindRequest req
+        cdef _FinderSlot slot
+        cdef list out = []
+        with self._lock:
+            for call in calls:
+                req = call[0]
+                req.first_id = self._num_seq
+                self._num_seq += len(req.seqs)
+        slot = self._own_slot()
+        try:
+            for req, tinf_of, dev, regs in calls:
+                out.extend(self._device_call(slot, req.seqs, translate, [req], tinf_of, dev, regs))
+                with self._lock:
+                    self.stats["device_calls"] += 1
+                    self.stats["sequences"] += len(req.seqs)
+        finally:
+            with self._lock:
+                self._release_slot(slot)
+        return out
+
     def _find_genes_models(self, object sequences, bint translate, object training_infos, object regions=None, list circ=None,
                            list tr_search=None, object tr_params=None, object tokens=None):
         """`find_genes_batch(..., training_infos=...)`: single mode with a model per sequence (`pga_find_genes_models`).  The
         sequences go in device calls of at most `coalesce_bases` bases and four translation tables (what one context's model set
         holds); identical `TrainingInfo` objects are loaded once per call."""
-        if self.meta:
-            raise ValueError("`training_infos` is a single-mode option: this finder is in meta mode")
+        self._single_mode_only()
         cdef list tinfs = list(training_infos)
         cdef list seqs = self._wrap_sequences(sequences, regions)
-        if len(tinfs) != len(seqs):
-            raise ValueError("`training_infos` has %d entries for %d sequences" % (len(tinfs), len(seqs)))
-        for i, t in enumerate(tinfs):
-            if not isinstance(t, TrainingInfo):
-                raise TypeError("training_infos[%d] is not a TrainingInfo (%r)" % (i, type(t).__name__))
+        self._checked_training_infos(tinfs, len(seqs))
         if not seqs:
             return []
         cdef list calls = self._model_calls([len((<Sequence> q).data) for q in seqs], tinfs)
         _one_call_for_tokens(tokens, calls)
-        cdef _FindRequest req
-        cdef _FinderSlot slot
-        cdef list out = []
-        with self._lock:
-            first_id = self._num_seq
-            self._num_seq += len(seqs)
-        slot = self._own_slot()
-        try:
-            for idx in calls:
-                req = _FindRequest.__new__(_FindRequest)
-                req.seqs = [seqs[i] for i in idx]
-                req.circ = [circ[i] for i in idx] if circ is not None else None
-                req.tr_search = [tr_search[i] for i in idx] if tr_search is not None else None
-                req.tr_params = tr_params if tr_search is not None else None
-                req.tokens = tokens
-                req.first_id = first_id + idx[0]
-                out.extend(self._device_call(slot, req.seqs, translate, [req], [tinfs[i] for i in idx]))
-                with self._lock:
-                    self.stats["device_calls"] += 1
-                    self.stats["sequences"] += len(idx)
-        finally:
-            with self._lock:
-                self._release_slot(slot)
-        return out
+        return self._run_alone(self._own_calls(calls, seqs, circ, None, tr_search, tr_params, tokens, tinfs), translate)
 
     def _find_genes_device(self, object dev, bint translate, object training_infos, object regions, list circ, object set_ids,
                            list tr_search, object tr_params, object tokens=None):
@@ -2193,18 +2269,9 @@ cdef class GeneFinder:
         pairs of `dev`: no data moves."""
         cdef Py_ssize_t n = len(dev), i
         cdef list tinfs = None, regs = None, calls
-        cdef _FindRequest req
-        cdef _FinderSlot slot
-        cdef list out = []
         if training_infos is not None:
-            if self.meta:
-                raise ValueError("`training_infos` is a single-mode option: this finder is in meta mode")
-            tinfs = list(training_infos)
-            if len(tinfs) != n:
-                raise ValueError("`training_infos` has %d entries for %d sequences" % (len(tinfs), n))
-            for i, t in enumerate(tinfs):
-                if not isinstance(t, TrainingInfo):
-                    raise TypeError("training_infos[%d] is not a TrainingInfo (%r)" % (i, type(t).__name__))
+            self._single_mode_only()
+            tinfs = self._checked_training_infos(list(training_infos), n)
         elif not self.meta and self.training_info is None:
             raise RuntimeError("cannot find genes without having trained in single mode")
         if regions is not None:
@@ -2217,53 +2284,15 @@ cdef class GeneFinder:
             return []
         calls = [list(range(n))] if tinfs is None else self._model_calls(dev.lengths.tolist(), tinfs)
         _one_call_for_tokens(tokens, calls)
-        with self._lock:
-            first_id = self._num_seq
-            self._num_seq += n
-        slot = self._own_slot()
-        try:
-            for idx in calls:
-                whole = len(idx) == n
-                req = _FindRequest.__new__(_FindRequest)
-                req.seqs = [None] * len(idx)           # (the Sequence objects are made from the packed letters, in the device call)
-                req.circ = None if circ is None else (circ if whole else [circ[i] for i in idx])
-                req.sets = set_ids
-                req.tr_search = None if tr_search is None else (tr_search if whole else [tr_search[i] for i in idx])
-                req.tr_params = tr_params if tr_search is not None else None
-                req.tokens = tokens
-                req.first_id = first_id + idx[0]
-                out.extend(self._device_call(slot, req.seqs, translate, [req], None if tinfs is None else [tinfs[i] for i in idx],
-                                             dev if whole else dev.take(idx), None if regs is None else [regs[i] for i in idx]))
-                with self._lock:
-                    self.stats["device_calls"] += 1
-                    self.stats["sequences"] += len(idx)
-        finally:
-            with self._lock:
-                self._release_slot(slot)
-        return out
+        # (the Sequence objects are made from the packed letters, in the device call)
+        return self._run_alone(self._own_calls(calls, [None] * n, circ, set_ids, tr_search, tr_params, tokens, tinfs, dev, regs), translate)
 
     def _find_genes_sets(self, list seqs, bint translate, object set_ids, list circ=None, list tr_search=None, object tr_params=None,
                          object tokens=None):
         """`find_genes_batch(..., sets=...)`: every set must sit in one device call, so the request takes a context for itself and is
         never coalesced with other callers' sequences.  `find_proteins_batch` on host sequences rides the same way, with the options
         a set cannot have."""
-        cdef _FindRequest req = _FindRequest.__new__(_FindRequest)
-        cdef _FinderSlot slot
-        with self._lock:
-            req.first_id = self._num_seq
-            self._num_seq += len(seqs)
-        req.seqs = seqs; req.circ = circ; req.sets = set_ids; req.tr_search = tr_search; req.tr_params = tr_params if tr_search is not None else None
-        req.tokens = tokens
-        slot = self._own_slot()
-        try:
-            out = self._device_call(slot, seqs, translate, [req])
-            with self._lock:
-                self.stats["device_calls"] += 1
-                self.stats["sequences"] += len(seqs)
-        finally:
-            with self._lock:
-                self._release_slot(slot)
-        return out
+        return self._run_alone(self._own_calls([list(range(len(seqs)))], seqs, circ, set_ids, tr_search, tr_params, tokens), translate)
 
     cdef int _release_slot(self, _FinderSlot slot) except -1:
         """(lock held) The context goes to the oldest waiting request that has no context yet, or back to the pool."""
@@ -2320,250 +2349,208 @@ cdef class GeneFinder:
         # tinf_of: one TrainingInfo per sequence (single mode, a model per sequence: pga_find_genes_models), or None
         # dev: the sequences lie in device memory (a DeviceSequences; dev_regions: their checked regions or None) -- the batch is packed
         #      there, `seqs` holds placeholders and is filled from the packed letters, fetched once
-        cdef int n = len(seqs), i, j, rc
-        cdef const char** ptrs = <const char**> malloc(sizeof(char*) * max(n, 1))
-        cdef int64_t* lens = <int64_t*> malloc(sizeof(int64_t) * max(n, 1))
+        cdef int n = len(seqs), i, rc
+        cdef const char** ptrs = NULL
+        cdef int64_t* lens = NULL
         cdef pga_params p
         cdef pga_result* res = NULL
-        cdef pga_batch* batch = NULL
-        cdef list out = []
-        cdef list ids = []
-        cdef Genes genes
-        cdef _FindRequest r
-        cdef pga_contig_result* cr
-        cdef object prot = None, prot_off = None, tables = None
-        cdef size_t p_tab, p_off, p_out
-        cdef int64_t ng
-        cdef pga_ctx* ctx
-        cdef list loaded = None
+        cdef _CallState o = _call_options(take, n)
         cdef object moc = None
-        cdef size_t p_moc = 0
         cdef bint masked = self.mask_lowercase       # a mask source beyond params.mask: the call goes through a resident batch
-        cdef object flags = None                     # uint8 per sequence, or None when no request of the call names a circle
-        cdef object cuts = None
-        cdef size_t p_flags = 0, p_cuts = 0
-        cdef object set_ids = (<_FindRequest> take[0]).sets if len(take) == 1 else None
-        cdef object tok = (<_FindRequest> take[0]).tokens if len(take) == 1 else None
-        cdef object tr_params = None                 # the terminal-repeat search of this call, or None: no request asks for one
-        cdef object tr_flags = None, tr_match = None, tr_trim = None
-        cdef size_t p_search = 0, p_match = 0, p_trim = 0
-        cdef pga_batch* whole = NULL                 # the batch as uploaded, while `batch` is its trimmed copy
-        cdef pga_batch* trimmed = NULL
-        cdef Sequence tseq
-        cdef object set_model = None, set_score = None, mscores = None
-        cdef size_t p_sets = 0, p_smodel = 0, p_sscore = 0, p_mscores = 0
-        cdef int n_models = 0
-        cdef object letters = None
-        cdef size_t p_letters = 0
-        cdef int64_t at = 0
-        if ptrs == NULL or lens == NULL:
-            free(ptrs); free(lens)
-            raise MemoryError()
         p.closed = self.closed; p.min_gene = self.min_gene; p.min_edge_gene = self.min_edge_gene
         p.max_overlap = self.max_overlap; p.meta = self.meta; p.want_nodes = self.keep_nodes
         p.mask = self.mask; p.min_mask = self.min_mask
-        for r in take:
-            for j in range(len(r.seqs)):
-                ids.append(r.first_id + j)
-            if r.circ is not None and flags is None:
-                flags = np.zeros(max(n, 1), np.uint8)
-            if r.tr_params is not None:
-                tr_params = r.tr_params
-        if flags is not None:
-            i = 0
-            for r in take:
-                if r.circ is not None:
-                    flags[i:i + len(r.seqs)] = r.circ
-                i += len(r.seqs)
-        if tr_params is not None:
-            tr_flags = np.zeros(max(n, 1), np.uint8); tr_match = np.zeros(max(n, 1), np.int32); tr_trim = np.zeros(max(n, 1), np.int32)
-            i = 0
-            for r in take:
-                if r.tr_search is not None:
-                    tr_flags[i:i + len(r.seqs)] = r.tr_search
-                i += len(r.seqs)
-            p_search = tr_flags.ctypes.data; p_match = tr_match.ctypes.data; p_trim = tr_trim.ctypes.data
-            if flags is None:
-                flags = np.zeros(max(n, 1), np.uint8)      # (a trimmed sequence is a circle: the flags are completed after the search)
-        if flags is not None:
-            cuts = np.full(max(n, 1), -1, np.int32)
-            p_flags = flags.ctypes.data; p_cuts = cuts.ctypes.data
         try:
-            for i in range(n if dev is None else 0):
-                ptrs[i] = PyBytes_AS_STRING((<Sequence> seqs[i]).data)
-                lens[i] = len((<Sequence> seqs[i]).data)
-                if (<Sequence> seqs[i])._regions is not None:
-                    masked = True
+            if dev is None:
+                ptrs = <const char**> malloc(sizeof(char*) * max(n, 1))
+                lens = <int64_t*> malloc(sizeof(int64_t) * max(n, 1))
+                if ptrs == NULL or lens == NULL:
+                    raise MemoryError()
+                for i in range(n):
+                    ptrs[i] = PyBytes_AS_STRING((<Sequence> seqs[i]).data)
+                    lens[i] = len((<Sequence> seqs[i]).data)
+                    if (<Sequence> seqs[i])._regions is not None:
+                        masked = True
+            elif dev_regions is not None:
+                for r in dev_regions:
+                    if r is not None:
+                        masked = True
             if tinf_of is None:
                 self._ensure_models(slot)
             else:
-                loaded, moc = self._load_models_of(slot, tinf_of)
-                p_moc = moc.ctypes.data
-            ctx = slot.ctx
-            if dev is not None:
-                batch = _device_batch(ctx, dev)
-                try:
-                    # the host copy of the letters: one device-to-host copy of the packed batch, cut into the usual Sequence objects
-                    letters = np.empty(max(int(dev.total), 1), np.uint8)
-                    p_letters = letters.ctypes.data
-                    with nogil:
-                        rc = pga_batch_read(ctx, batch, -1, <char*> p_letters)
-                    if rc != PGA_OK:
-                        _raise_for(ctx, rc, "pga_batch_read")
-                    seqs = []
-                    at = 0
-                    for i in range(n):
-                        tseq = Sequence(letters[at:at + int(dev.lengths[i])].tobytes(), mask=self.mask, mask_size=self.min_mask,
-                                        mask_lowercase=self.mask_lowercase)
-                        at += int(dev.lengths[i])
-                        if dev_regions is not None and dev_regions[i] is not None:
-                            tseq._regions = dev_regions[i]
-                            masked = True
-                        seqs.append(tseq)
-                    letters = None
-                except BaseException:
-                    pga_batch_free(batch)
-                    raise
-            if tinf_of is not None:
-                if batch == NULL:
-                    rc = pga_batch_create(ctx, n, ptrs, lens, &batch)
-                    if rc != PGA_OK:
-                        _raise_for(ctx, rc, "pga_batch_create")
-                try:
-                    if masked:
-                        _attach_masks(ctx, batch, seqs, self.mask_lowercase)
-                    if flags is not None:
-                        pga_batch_set_circular(batch, <const uint8_t*> p_flags)
-                    if tr_params is not None:
-                        trimmed = _trimmed_batch(ctx, batch, p_search, tr_params, p_match, p_trim)
-                        if trimmed != NULL:
-                            whole = batch; batch = trimmed
-                    with nogil:
-                        rc = pga_find_genes_models(ctx, batch, &p, <const int32_t*> p_moc, &res)
-                    if rc != PGA_OK:
-                        _raise_for(ctx, rc, "pga_find_genes_models")
-                    if flags is not None:
-                        pga_circular_cuts(ctx, n, <int32_t*> p_cuts)
-                    if translate:
-                        prot, prot_off, tables = self._translate(ctx, batch, res, n, tinf_of)
-                    if tok is not None:
-                        self._tokens(ctx, batch, res, n, tinf_of, tok)
-                finally:
-                    pga_batch_free(batch)
-                    if whole != NULL:
-                        pga_batch_free(whole)
-            elif dev is None and not translate and not masked and flags is None and set_ids is None and tr_params is None and tok is None:
+                moc = self._load_models_of(slot, tinf_of)[1]
+            if (dev is None and moc is None and not translate and not masked and o.flags is None and o.set_ids is None
+                    and o.tr_params is None and o.tok is None):
                 with nogil:
-                    rc = pga_find_genes_batch(ctx, n, ptrs, lens, &p, &res)
+                    rc = pga_find_genes_batch(slot.ctx, n, ptrs, lens, &p, &res)
                 if rc != PGA_OK:
-                    _raise_for(ctx, rc, "pga_find_genes_batch")
+                    _raise_for(slot.ctx, rc, "pga_find_genes_batch")
             else:
-                if batch == NULL:
-                    rc = pga_batch_create(ctx, n, ptrs, lens, &batch)
-                    if rc != PGA_OK:
-                        _raise_for(ctx, rc, "pga_batch_create")
-                try:
-                    if masked:
-                        _attach_masks(ctx, batch, seqs, self.mask_lowercase)
-                    if flags is not None:
-                        pga_batch_set_circular(batch, <const uint8_t*> p_flags)
-                    if set_ids is not None:
-                        p_sets = set_ids.ctypes.data
-                        rc = pga_batch_set_sets(batch, <const int32_t*> p_sets)
-                        if rc != PGA_OK:
-                            _raise_for(ctx, rc, "pga_batch_set_sets")
-                    if tr_params is not None:
-                        trimmed = _trimmed_batch(ctx, batch, p_search, tr_params, p_match, p_trim)
-                        if trimmed != NULL:
-                            whole = batch; batch = trimmed
-                    with nogil:
-                        rc = pga_find_genes(ctx, batch, &p, &res)
-                    if rc != PGA_OK:
-                        _raise_for(ctx, rc, "pga_find_genes")
-                    if set_ids is not None:
-                        n_models = len(self.metagenomic_bins)
-                        set_model = np.full(max(n, 1), -1, np.int32); set_score = np.full(max(n, 1), np.nan, np.float64)
-                        mscores = np.full(max(n * n_models, 1), np.nan, np.float64)
-                        p_smodel = set_model.ctypes.data; p_sscore = set_score.ctypes.data; p_mscores = mscores.ctypes.data
-                        pga_set_choice(ctx, n, <int32_t*> p_smodel, <double*> p_sscore)
-                        pga_model_scores(ctx, n, n_models, <double*> p_mscores)
-                    if flags is not None:
-                        pga_circular_cuts(ctx, n, <int32_t*> p_cuts)
-                    if translate:
-                        prot_off = np.zeros(res.n_genes + 1, np.int64)
-                        prot, prot_off, tables = self._translate(ctx, batch, res, n, None)
-                    if tok is not None:
-                        self._tokens(ctx, batch, res, n, None, tok)
-                finally:
-                    pga_batch_free(batch)
-                    if whole != NULL:
-                        pga_batch_free(whole)
-            if tr_params is not None:
-                seqs = list(seqs)                      # (the caller's list keeps the records as they came)
-                for i in range(n):
-                    if tr_trim[i] > 0:
-                        # the record without the second copy of its first bases: what the device called, and what the host writers read
-                        flags[i] = 1
-                        tseq = <Sequence> seqs[i]
-                        r_clip = None
-                        if tseq._regions is not None:
-                            r_clip = np.minimum(tseq._regions, len(tseq.data) - int(tr_trim[i])).astype(np.int32)
-                            r_clip = r_clip[r_clip[:, 0] < r_clip[:, 1]]
-                            if len(r_clip) == 0:
-                                r_clip = None
-                        seqs[i] = Sequence(tseq.data[:len(tseq.data) - int(tr_trim[i])], mask=tseq.mask, mask_size=tseq.mask_size,
-                                           mask_lowercase=tseq.mask_lowercase)
-                        (<Sequence> seqs[i])._regions = r_clip
-            for i in range(n):
-                cr = &res.contigs[i]
-                genes = Genes.__new__(Genes)
-                genes.sequence = seqs[i]
-                (<Sequence> seqs[i])._gc = cr.gc
-                (<Sequence> seqs[i])._unknown = cr.n_unknown
-                if (<Sequence> seqs[i])._masks is None:
-                    (<Sequence> seqs[i])._masks = []
-                    if res.mask_off != NULL:
-                        for j in range(res.mask_off[i], res.mask_off[i + 1]):
-                            (<Sequence> seqs[i])._masks.append(Mask(res.masks[2 * j], res.masks[2 * j + 1]))
-                genes.meta = self.meta
-                genes._num_seq = ids[i]
-                genes.score = cr.score
-                genes.circular = flags is not None and flags[i] != 0
-                genes.cut = int(cuts[i]) if genes.circular else None
-                genes.terminal_repeat = genes.terminal_repeat_match = None
-                if tr_params is not None and tr_flags[i]:
-                    genes.terminal_repeat = int(tr_trim[i]); genes.terminal_repeat_match = int(tr_match[i])
-                if set_ids is not None:
-                    genes.set_score = float(set_score[i]) if set_model[i] >= 0 else None
-                    genes.model_scores = {j: float(mscores[i * n_models + j]) for j in range(n_models) if mscores[i * n_models + j] == mscores[i * n_models + j]}
-                if self.meta:
-                    if cr.model >= 0:
-                        genes.metagenomic_bin = self.metagenomic_bins[cr.model]
-                        genes.training_info = genes.metagenomic_bin.training_info
-                    else:
-                        genes.metagenomic_bin = genes.training_info = None
-                else:
-                    genes.metagenomic_bin = None
-                    genes.training_info = self.training_info if tinf_of is None else tinf_of[i]
-                genes._nodes = None
-                genes._node_blob = None
-                genes._node_n = 0
-                if self.keep_nodes and res.nodes != NULL:
-                    genes._node_blob = _pack_nodes(&res.nodes[i])
-                    genes._node_n = res.nodes[i].n
-                genes._genes = None
-                genes._n = cr.n_genes
-                genes._recs = PyBytes_FromStringAndSize(<const char*> &res.genes[cr.gene_begin], cr.n_genes * sizeof(pga_gene)) if cr.n_genes > 0 else b""
-                genes._prot = None; genes._prot_off = None; genes._prot_tt = 0
-                if prot is not None:
-                    genes._prot = prot[prot_off[cr.gene_begin]:prot_off[cr.gene_begin + cr.n_genes]].tobytes()
-                    genes._prot_off = (prot_off[cr.gene_begin:cr.gene_begin + cr.n_genes + 1] - prot_off[cr.gene_begin]).copy()
-                    genes._prot_tt = int(tables[i])
-                out.append(genes)
+                seqs = self._resident_call(slot.ctx, &p, o, seqs, masked, translate, moc, tinf_of, ptrs, lens, dev, dev_regions, &res)
+            return self._genes_of_call(o, seqs, res, tinf_of)
         finally:
             free(ptrs); free(lens)
             if res != NULL:
                 pga_result_free(res)
+
+    cdef list _sequences_of_batch(self, pga_ctx* ctx, pga_batch* batch, object dev, list dev_regions):
+        """The host copy of the letters of a batch packed from `dev`: one device-to-host copy of the packed batch, cut into the usual
+        Sequence objects."""
+        cdef int n = len(dev), i, rc
+        cdef int64_t at = 0
+        cdef Sequence tseq
+        cdef list seqs = []
+        letters = np.empty(max(int(dev.total), 1), np.uint8)
+        cdef size_t p_letters = letters.ctypes.data
+        with nogil:
+            rc = pga_batch_read(ctx, batch, -1, <char*> p_letters)
+        if rc != PGA_OK:
+            _raise_for(ctx, rc, "pga_batch_read")
+        for i in range(n):
+            tseq = Sequence(letters[at:at + int(dev.lengths[i])].tobytes(), mask=self.mask, mask_size=self.min_mask,
+                            mask_lowercase=self.mask_lowercase)
+            at += int(dev.lengths[i])
+            if dev_regions is not None and dev_regions[i] is not None:
+                tseq._regions = dev_regions[i]
+            seqs.append(tseq)
+        return seqs
+
+    cdef list _resident_call(self, pga_ctx* ctx, pga_params* p, _CallState o, list seqs, bint masked, bint translate, object moc,
+                             list tinf_of, const char** ptrs, const int64_t* lens, object dev, list dev_regions, pga_result** res):
+        """A device call through a resident batch: made from the host pointers or packed from `dev`, given the options of the call,
+        handed to the finder (`moc`: the loaded model of every sequence, or None), read for what the options report and for
+        translations and tokens, and released.  Fills `res` and the arrays of `o`; returns the Sequence objects of the call -- `seqs`,
+        or with `dev` the ones made from the packed letters."""
+        cdef int n = len(seqs), rc
+        cdef pga_batch* batch = NULL
+        cdef pga_batch* whole = NULL                 # the batch as uploaded, while `batch` is its trimmed copy
+        cdef pga_batch* trimmed = NULL
+        cdef size_t p_moc = 0, p_flags = 0, p_cuts = 0, p_sets = 0, p_smodel = 0, p_sscore = 0, p_mscores = 0
+        try:
+            if dev is not None:
+                batch = _device_batch(ctx, dev)
+                seqs = self._sequences_of_batch(ctx, batch, dev, dev_regions)
+            else:
+                rc = pga_batch_create(ctx, n, ptrs, lens, &batch)
+                if rc != PGA_OK:
+                    _raise_for(ctx, rc, "pga_batch_create")
+            if masked:
+                _attach_masks(ctx, batch, seqs, self.mask_lowercase)
+            if o.flags is not None:
+                p_flags = o.flags.ctypes.data; p_cuts = o.cuts.ctypes.data
+                pga_batch_set_circular(batch, <const uint8_t*> p_flags)
+            if o.set_ids is not None:
+                p_sets = o.set_ids.ctypes.data
+                rc = pga_batch_set_sets(batch, <const int32_t*> p_sets)
+                if rc != PGA_OK:
+                    _raise_for(ctx, rc, "pga_batch_set_sets")
+            if o.tr_params is not None:
+                trimmed = _trimmed_batch(ctx, batch, o.tr_flags.ctypes.data, o.tr_params, o.tr_match.ctypes.data, o.tr_trim.ctypes.data)
+                if trimmed != NULL:
+                    whole = batch; batch = trimmed
+            if moc is not None:
+                p_moc = moc.ctypes.data
+                with nogil:
+                    rc = pga_find_genes_models(ctx, batch, p, <const int32_t*> p_moc, res)
+                if rc != PGA_OK:
+                    _raise_for(ctx, rc, "pga_find_genes_models")
+            else:
+                with nogil:
+                    rc = pga_find_genes(ctx, batch, p, res)
+                if rc != PGA_OK:
+                    _raise_for(ctx, rc, "pga_find_genes")
+            if o.set_ids is not None:
+                o.n_models = len(self.metagenomic_bins)
+                o.set_model = np.full(max(n, 1), -1, np.int32); o.set_score = np.full(max(n, 1), np.nan, np.float64)
+                o.model_scores = np.full(max(n * o.n_models, 1), np.nan, np.float64)
+                p_smodel = o.set_model.ctypes.data; p_sscore = o.set_score.ctypes.data; p_mscores = o.model_scores.ctypes.data
+                pga_set_choice(ctx, n, <int32_t*> p_smodel, <double*> p_sscore)
+                pga_model_scores(ctx, n, o.n_models, <double*> p_mscores)
+            if o.flags is not None:
+                pga_circular_cuts(ctx, n, <int32_t*> p_cuts)
+            if translate:
+                o.prot, o.prot_off, o.tables = self._translate(ctx, batch, res[0], n, tinf_of)
+            if o.tok is not None:
+                self._tokens(ctx, batch, res[0], n, tinf_of, o.tok)
+        finally:
+            if batch != NULL:
+                pga_batch_free(batch)
+            if whole != NULL:
+                pga_batch_free(whole)
+        return seqs
+
+    cdef list _genes_of_call(self, _CallState o, list seqs, pga_result* res, list tinf_of):
+        """One `Genes` per sequence of a device call, from its result and from what the call's options reported."""
+        cdef int n = len(seqs), i, j
+        cdef pga_contig_result* cr
+        cdef Genes genes
+        cdef Sequence seq, tseq
+        cdef list out = []
+        if o.tr_trim is not None:
+            seqs = list(seqs)                      # (the caller's list keeps the records as they came)
+            for i in range(n):
+                if o.tr_trim[i] > 0:
+                    # the record without the second copy of its first bases: what the device called, and what the host writers read
+                    o.flags[i] = 1
+                    tseq = <Sequence> seqs[i]
+                    r_clip = None
+                    if tseq._regions is not None:
+                        r_clip = np.minimum(tseq._regions, len(tseq.data) - int(o.tr_trim[i])).astype(np.int32)
+                        r_clip = r_clip[r_clip[:, 0] < r_clip[:, 1]]
+                        if len(r_clip) == 0:
+                            r_clip = None
+                    seq = Sequence(tseq.data[:len(tseq.data) - int(o.tr_trim[i])], mask=tseq.mask, mask_size=tseq.mask_size,
+                                   mask_lowercase=tseq.mask_lowercase)
+                    seq._regions = r_clip
+                    seqs[i] = seq
+        for i in range(n):
+            cr = &res.contigs[i]
+            seq = <Sequence> seqs[i]
+            genes = Genes.__new__(Genes)
+            genes.sequence = seq
+            seq._gc = cr.gc
+            seq._unknown = cr.n_unknown
+            if seq._masks is None:
+                seq._masks = []
+                if res.mask_off != NULL:
+                    for j in range(res.mask_off[i], res.mask_off[i + 1]):
+                        seq._masks.append(Mask(res.masks[2 * j], res.masks[2 * j + 1]))
+            genes.meta = self.meta
+            genes._num_seq = o.ids[i]
+            genes.score = cr.score
+            genes.circular = o.flags is not None and o.flags[i] != 0
+            genes.cut = int(o.cuts[i]) if genes.circular else None
+            genes.terminal_repeat = genes.terminal_repeat_match = None
+            if o.tr_flags is not None and o.tr_flags[i]:
+                genes.terminal_repeat = int(o.tr_trim[i]); genes.terminal_repeat_match = int(o.tr_match[i])
+            if o.set_model is not None:
+                genes.set_score = float(o.set_score[i]) if o.set_model[i] >= 0 else None
+                ms = o.model_scores[i * o.n_models:(i + 1) * o.n_models]
+                genes.model_scores = {j: float(ms[j]) for j in range(o.n_models) if ms[j] == ms[j]}
+            if self.meta:
+                if cr.model >= 0:
+                    genes.metagenomic_bin = self.metagenomic_bins[cr.model]
+                    genes.training_info = genes.metagenomic_bin.training_info
+                else:
+                    genes.metagenomic_bin = genes.training_info = None
+            else:
+                genes.metagenomic_bin = None
+                genes.training_info = self.training_info if tinf_of is None else tinf_of[i]
+            genes._nodes = None
+            genes._node_blob = None
+            genes._node_n = 0
+            if self.keep_nodes and res.nodes != NULL:
+                genes._node_blob = _pack_nodes(&res.nodes[i])
+                genes._node_n = res.nodes[i].n
+            genes._genes = None
+            genes._n = cr.n_genes
+            genes._recs = PyBytes_FromStringAndSize(<const char*> &res.genes[cr.gene_begin], cr.n_genes * sizeof(pga_gene)) if cr.n_genes > 0 else b""
+            genes._prot = None; genes._prot_off = None; genes._prot_tt = 0
+            if o.prot is not None:
+                genes._prot = o.prot[o.prot_off[cr.gene_begin]:o.prot_off[cr.gene_begin + cr.n_genes]].tobytes()
+                genes._prot_off = (o.prot_off[cr.gene_begin:cr.gene_begin + cr.n_genes + 1] - o.prot_off[cr.gene_begin]).copy()
+                genes._prot_tt = int(o.tables[i])
+            out.append(genes)
         return out
 
     cdef int _tokens(self, pga_ctx* ctx, pga_batch* batch, pga_result* res, int n, list tinf_of, dict tok) except -1:
