@@ -172,7 +172,8 @@ int pga_set_models(pga_ctx*, const pga_training* const* models, int n_models);
 
 /* ---- scorer level ------------------------------------------------------ */
 /* Whole-array connection scoring of one sorted node list (the gene prediction pass, final = 1).
- * Inputs are the node fields _score_connections reads; outputs are the fields it writes. */
+ * Inputs are the node fields _score_connections reads; outputs are the fields it writes.  Scores must be finite: equal values
+ * and exact zeros are decided as the reference decides them, NaN and infinities are outside the contract. */
 int pga_score_connections(pga_ctx*, int32_t n,
                           const int32_t* ndx, const int32_t* stop_val,
                           const uint8_t* type, const int8_t* strand,

@@ -28,6 +28,7 @@ NODE_DTYPE = np.dtype(
     ],
     align=True,
 )
+DP_EVENTS = ("ties", "zero_joins", "frame_ties", "best_end_ties", "ovl_ties", "joins")   # order of PO_EV_* in prodigal_oracle.h
 GENE_DTYPE = np.dtype([("begin", "i4"), ("end", "i4"), ("start_ndx", "i4"), ("stop_ndx", "i4")])
 
 
@@ -78,6 +79,7 @@ def lib():
         L.po_dprog.restype = i32; L.po_dprog.argtypes = [vp, vp, i32, i32]
         L.po_dprog_raw.restype = None; L.po_dprog_raw.argtypes = [vp, vp, i32]
         L.po_find_max_index.restype = i32; L.po_find_max_index.argtypes = [vp]
+        L.po_dp_events.restype = None; L.po_dp_events.argtypes = [vp, vp]
         L.po_eliminate_bad_genes.argtypes = [vp, i32, vp]
         L.po_extract_genes.restype = i32; L.po_extract_genes.argtypes = [vp, i32]
         L.po_tweak_final_starts.argtypes = [vp, vp, i32]
@@ -219,6 +221,13 @@ class Oracle:
 
     def find_max_index(self):
         return self.L.po_find_max_index(self.h)
+
+    def dp_events(self):
+        """How often each tie rule decided something in the last overlapping_starts / dprog_raw / find_max_index of this
+        sequence (po_dp_events): ties, zero_joins, frame_ties, best_end_ties, ovl_ties, joins."""
+        out = np.zeros(len(DP_EVENTS), np.int64)
+        self.L.po_dp_events(self.h, out.ctypes.data)
+        return dict(zip(DP_EVENTS, (int(v) for v in out)))
 
     def eliminate_bad_genes(self, ipath, tinf):
         self.L.po_eliminate_bad_genes(self.h, ipath, tinf.ptr)

@@ -38,6 +38,7 @@ struct po_ctx {
     int      kcap;
     int      ipath;
     double   path_score;
+    int64_t  ev[PO_EV_COUNT];   /* events that the tie rules decided (po_dp_events); no result depends on them */
 };
 
 /* ---------------------------------------------------------------- sequence */
@@ -105,6 +106,7 @@ int po_num_genes(const po_ctx* c) { return c->ng; }
 po_gene* po_genes(po_ctx* c) { return c->gen; }
 double po_last_path_score(const po_ctx* c) { return c->path_score; }
 int po_last_ipath(const po_ctx* c) { return c->ipath; }
+void po_dp_events(const po_ctx* c, int64_t out[PO_EV_COUNT]) { memcpy(out, c->ev, sizeof c->ev); }
 
 /* base `i` of strand-local coordinates; reverse strand is virtual.
  * ref: _sequence.h:45-55 */
@@ -576,11 +578,12 @@ static double igm(const po_node* a, const po_node* b, double st_wt) {  /* ref: _
 /* ref: lib.pyx:2279-2329 (Nodes._record_overlapping_starts) */
 void po_overlapping_starts(po_ctx* c, const po_training* t, int flag, int maxov) {
     const int nn = c->nn; po_node* nod = c->nod;
+    c->ev[PO_EV_OVL_TIES] = 0;
     for (int i = 0; i < nn; i++) {
         po_node* s = &nod[i];
         s->star_ptr[0] = s->star_ptr[1] = s->star_ptr[2] = -1;
         if (s->type != T_STOP || s->edge == 1) continue;
-        double best = -100;
+        double best = -100; int kept = 0;   /* kept: candidates that took the place so far (event counter only) */
         if (s->strand == 1) {
             for (int j = i + 3; j >= 0; j--) {
                 if (j >= nn || nod[j].ndx > s->ndx + 2) continue;
@@ -591,7 +594,8 @@ void po_overlapping_starts(po_ctx* c, const po_training* t, int flag, int maxov)
                 if (flag == 0) { if (s->star_ptr[f] == -1) s->star_ptr[f] = j; }
                 else {
                     double v = nod[j].cscore + nod[j].sscore + igm_same(s, &nod[j], t->st_wt);
-                    if (v > best) { s->star_ptr[f] = j; best = v; }
+                    if (v == best && kept) c->ev[PO_EV_OVL_TIES]++;
+                    if (v > best) { s->star_ptr[f] = j; best = v; kept++; }
                 }
             }
         } else {
@@ -604,7 +608,8 @@ void po_overlapping_starts(po_ctx* c, const po_training* t, int flag, int maxov)
                 if (flag == 0) { if (s->star_ptr[f] == -1) s->star_ptr[f] = j; }
                 else {
                     double v = nod[j].cscore + nod[j].sscore + igm_same(&nod[j], s, t->st_wt);
-                    if (v > best) { s->star_ptr[f] = j; best = v; }
+                    if (v == best && kept) c->ev[PO_EV_OVL_TIES]++;
+                    if (v > best) { s->star_ptr[f] = j; best = v; kept++; }
                 }
             }
         }
@@ -617,7 +622,7 @@ static inline double gc_bias_score(const po_node* n, const po_training* t) {
 
 /* One candidate connection j -> i.  kind of i: 0 fwd start, 1 fwd stop, 2 rev start, 3 rev stop.
  * ref: _connection.h:94-140, 143-202, 205-267, 270-367 (the four split scorers) */
-static void connect(po_node* nod, int j, int i, int kind, const po_training* t, int final) {
+static void connect(po_node* nod, int j, int i, int kind, const po_training* t, int final, int64_t* ev) {
     const po_node* a = &nod[j]; po_node* b = &nod[i]; const po_node* n3;
     const int a_fs = a->strand == 1 && a->type == T_STOP;      /* forward stop  */
     const int a_rb = a->strand != 1 && a->type != T_STOP;      /* reverse start */
@@ -676,6 +681,7 @@ static void connect(po_node* nod, int j, int i, int kind, const po_training* t, 
                 if (a->traceb == -1) continue;
                 if (ovlp >= n3->stop_val - nod[a->traceb].ndx - 2) continue;
                 cur = n3->cscore + n3->sscore + igm(n3, b, t->st_wt);
+                if (maxfr != -1 && (final ? cur : gc_bias_score(n3, t)) == maxval) ev[PO_EV_FRAME_TIES]++;
                 if ((final && cur > maxval) || (!final && gc_bias_score(n3, t) > maxval)) { maxfr = k; maxval = cur; }
             }
             if (maxfr != -1) {
@@ -695,7 +701,8 @@ static void connect(po_node* nod, int j, int i, int kind, const po_training* t, 
         }
     }
     if (!final) score = ((double)(right - left + 1 - ovlp * 2)) * mod;
-    if (a->score + score >= b->score) { b->score = a->score + score; b->traceb = j; b->ov_mark = (int8_t)maxfr; }
+    if (a->score + score == b->score) ev[b->traceb != -1 ? PO_EV_TIES : PO_EV_ZERO_JOINS]++;
+    if (a->score + score >= b->score) { ev[PO_EV_JOINS]++; b->score = a->score + score; b->traceb = j; b->ov_mark = (int8_t)maxfr; }
 }
 
 /* ref: lib.pyx:1126-1162 (BaseConnectionScorer._index) */
@@ -738,6 +745,7 @@ void po_dprog_raw(po_ctx* c, const po_training* t, int final) {
     const int nn = c->nn; po_node* nod = c->nod;
     if (nn == 0) return;
     index_nodes(c);
+    c->ev[PO_EV_TIES] = c->ev[PO_EV_ZERO_JOINS] = c->ev[PO_EV_FRAME_TIES] = c->ev[PO_EV_JOINS] = 0;
     for (int i = 0; i < nn; i++) { nod[i].score = 0; nod[i].traceb = -1; nod[i].tracef = -1; }
     for (int i = 0; i < nn; i++) {
         int lo = i < MAX_NODE_DIST ? 0 : i - MAX_NODE_DIST;
@@ -746,19 +754,21 @@ void po_dprog_raw(po_ctx* c, const po_training* t, int final) {
             while (lo > 0 && nod[lo].ndx != nod[i].stop_val) lo--;
         lo = lo < MAX_NODE_DIST ? 0 : lo - MAX_NODE_DIST;
         skippable(c->k_strand, c->k_type, c->k_frame, lo, i, c->k_skip);
-        for (int j = lo; j < i; j++) if (!c->k_skip[j]) connect(nod, j, i, kind, t, final);
+        for (int j = lo; j < i; j++) if (!c->k_skip[j]) connect(nod, j, i, kind, t, final, c->ev);
     }
 }
 
 /* ref: lib.pyx:1239-1251 (_find_max_index) */
-int po_find_max_index(const po_ctx* c) {
+int po_find_max_index(po_ctx* c) {
     const po_node* nod = c->nod;
-    int mx = -1; double best = -1.0;
+    int mx = -1; double best = -1.0; int64_t equal = 0;
     for (int i = c->nn - 1; i >= 0; i--) {
         if (nod[i].strand == 1 && nod[i].type != T_STOP) continue;
         if (nod[i].strand == -1 && nod[i].type == T_STOP) continue;
-        if (nod[i].score > best) { best = nod[i].score; mx = i; }
+        if (mx != -1 && nod[i].score == best) equal++;
+        if (nod[i].score > best) { best = nod[i].score; mx = i; equal = 0; }
     }
+    c->ev[PO_EV_BEST_END_TIES] = equal;
     return mx;
 }
 

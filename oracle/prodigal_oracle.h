@@ -95,7 +95,7 @@ void po_overlapping_starts(po_ctx*, const po_training*, int flag, int max_overla
 int  po_dprog(po_ctx*, const po_training*, int final, int use_filter);
 void po_record_gc_bias(po_ctx*, po_training*);   /* training: GC frame plot + frame bias of every start */
 void po_dprog_raw(po_ctx*, const po_training*, int final);   /* connection loop only, no fix-ups */
-int  po_find_max_index(const po_ctx*);
+int  po_find_max_index(po_ctx*);
 void po_eliminate_bad_genes(po_ctx*, int ipath, const po_training*);
 int  po_extract_genes(po_ctx*, int ipath);
 void po_tweak_final_starts(po_ctx*, const po_training*, int max_overlap);
@@ -110,6 +110,20 @@ int  po_train(po_ctx*, po_training* out, const po_params*, int force_nonsd,
               double start_weight, int tt);
 int  po_train_upto(po_ctx*, po_training* out, const po_params*, int force_nonsd,
               double start_weight, int tt, int upto);
+
+/* How often the tie rules of the connection scoring decided something in the last calls on this context (counters only: no result
+ * depends on them).  With `v` the value a candidate connection offers (source score + connection score):
+ *   TIES          v == the target's score and the target already had a connection: `>=` lets the later source replace it
+ *                 (ref: _connection.h:135/197 and their siblings)
+ *   ZERO_JOINS    v == the target's score and the target had none: a sum of exactly 0.0 still connects
+ *   FRAME_TIES    triple overlap: a frame's value == the best so far while a frame is chosen: strict `>` keeps the earlier frame
+ *   BEST_END_TIES po_find_max_index: further gene ends whose score equals the best (ref: lib.pyx:1239-1251, the largest index wins)
+ *   OVL_TIES      po_overlapping_starts(flag = 1): a later candidate's value == the best so far (strict `>` keeps the earlier one)
+ *   JOINS         connections made or replaced in all
+ * TIES, ZERO_JOINS, FRAME_TIES and JOINS are cleared by po_dprog_raw, OVL_TIES by po_overlapping_starts; BEST_END_TIES is set by
+ * every po_find_max_index. */
+enum { PO_EV_TIES = 0, PO_EV_ZERO_JOINS, PO_EV_FRAME_TIES, PO_EV_BEST_END_TIES, PO_EV_OVL_TIES, PO_EV_JOINS, PO_EV_COUNT };
+void   po_dp_events(const po_ctx*, int64_t out[PO_EV_COUNT]);
 
 double po_last_path_score(const po_ctx*);  /* nodes[ipath].score of last winning DP */
 int    po_last_ipath(const po_ctx*);

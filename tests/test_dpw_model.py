@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 
 from oracle import oracle as orc
+from tests import dp_inject
 from tests.util import golden_path, read_fasta, synthetic_contig
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -56,14 +57,19 @@ def check(L, seq, tinf, closed=False, is_meta=False, mask=False):
     ref = o.nodes()
     if len(ref) == 0:
         return 0, np.zeros(8, np.int64)
-    score, traceb, ov, mi, stats = run_model(L, before, tinf.st_wt)
+    return len(ref), compare(L, before, ref, o.find_max_index(), tinf.st_wt)
+
+
+def compare(L, before, ref, ref_max, st_wt):
+    """The model on the nodes `before` against the oracle's state `ref` after its connection loop; returns the model's statistics."""
+    score, traceb, ov, mi, stats = run_model(L, before, st_wt)
     bad = np.flatnonzero(traceb != ref["traceb"])
     assert len(bad) == 0, (bad[:10], traceb[bad[:10]], ref["traceb"][bad[:10]], before["type"][bad[:10]], before["strand"][bad[:10]])
     assert np.array_equal(score.view(np.uint64), ref["score"].view(np.uint64))
     reached = ref["traceb"] != -1
     assert np.array_equal(ov[reached], ref["ov_mark"][reached])
-    assert mi == o.find_max_index()
-    return len(ref), stats
+    assert mi == ref_max
+    return stats
 
 
 @pytest.mark.parametrize("name,model_file,closed", [
@@ -131,3 +137,68 @@ def test_model_on_tiny_and_degenerate_inputs(model):
     # masked input
     seq = bytearray(synthetic_contig(30000, 0.5, 3)); seq[5000:5300] = b"N" * 300; seq[20000:20060] = b"N" * 60
     check(model, bytes(seq), tinf, mask=True)
+
+
+# ---- score arrays that tie (tests/dp_inject.py): computed scores never do, so the tie rules are only decided here ----
+
+TIE_TOPOLOGIES = {
+    "SRR492066": lambda: (read_fasta("SRR492066.fna.gz")[0][1], False),
+    "synthetic_20k": lambda: (synthetic_contig(20000, 0.5, 5), False),
+    "synthetic_60k_closed": lambda: (synthetic_contig(60000, 0.62, 6), True),
+    "synthetic_150k": lambda: (synthetic_contig(150000, 0.5, 31), False),
+}
+
+
+@pytest.mark.parametrize("topology", list(TIE_TOPOLOGIES))
+def test_model_on_injected_scores_that_tie(model, topology):
+    """Every family under every start weight: the later source wins a tie, a sum of exactly 0.0 connects, the best gene end is
+    the largest index among equals.  The floors say that the oracle decided those rules on this input (they are conditions
+    on the input, taken from the oracle's counters alone, far below what it counts)."""
+    seq, closed = TIE_TOPOLOGIES[topology]()
+    o = dp_inject.extracted(seq, closed)
+    n = o.num_nodes
+    assert n >= 600
+    best_end_ties = 0
+    for family in dp_inject.FAMILIES:
+        for st_wt in (4.35, 4.0, 0.0):
+            before, ref, ref_max, ev = dp_inject.inject_into(o, family, st_wt, seed=1)
+            assert ev["ties"] >= 100, (family, st_wt, ev)
+            if family == "zero" and st_wt == 0.0:
+                assert ev["zero_joins"] >= n / 2, ev
+                best_end_ties += ev["best_end_ties"]
+            assert ev["frame_ties"] == 0              # see dp_inject.inject: impossible with star_ptr of the gene prediction pass
+            compare(model, before, ref, ref_max, st_wt)
+    assert best_end_ties >= 1
+
+
+def test_model_on_the_smallest_tied_chains(model):
+    # chains around one and two 64-node batches
+    for n in (63, 64, 65, 128, 129):
+        seq = dp_inject.contig_with_nodes(n, 0.5, 40 + n)
+        for family in ("zero", "pm1"):
+            for st_wt in (4.35, 0.0):
+                before, ref, ref_max, ev = dp_inject.inject(seq, family, st_wt, seed=1)
+                assert len(before) == n and ev["ties"] >= 20, (n, family, st_wt, ev)
+                compare(model, before, ref, ref_max, st_wt)
+
+
+def test_model_where_the_frames_of_a_triple_overlap_tie(model):
+    # star_ptr holding the first candidate of every frame (star_flag = 0, see dp_inject.inject) on a real genome's topology; seed 23 is
+    # one of the seeds under which two frames of a reverse stop offer the same value (found by a search over seeds 0..39 on the oracle)
+    seq = read_fasta("GCF_001457455.1_NCTC11397_genomic_100kb.fna.gz")[0][1]
+    before, ref, ref_max, ev = dp_inject.inject(seq, "pm1", 0.0, seed=23, closed=True, star_flag=0)
+    assert ev["frame_ties"] >= 1 and ev["ties"] >= 100, ev
+    compare(model, before, ref, ref_max, 0.0)
+    # and overlapping starts whose values tie, on star_ptr of the gene prediction pass
+    before, ref, ref_max, ev = dp_inject.inject(seq, "zero", 4.35, seed=1, closed=True)
+    assert ev["ovl_ties"] >= 1 and ev["ties"] >= 100, ev
+    compare(model, before, ref, ref_max, 4.35)
+
+
+def test_model_on_the_full_genome_with_tied_scores(model):
+    seq = read_fasta("GCF_001457455.1_NCTC11397_genomic.fna.gz")[0][1]
+    o = dp_inject.extracted(seq, closed=True)
+    for family, st_wt in (("quant", 4.35), ("zero", 4.35)):
+        before, ref, ref_max, ev = dp_inject.inject_into(o, family, st_wt, seed=1)
+        assert len(ref) == 153296 and ev["ties"] >= 100_000, ev
+        compare(model, before, ref, ref_max, st_wt)

@@ -29,3 +29,12 @@ def test_the_check_sees_a_missing_wait_state(tmp_path):
     bad.write_text(src.replace(good, 'a("s_nop 0")'))
     r = subprocess.run([sys.executable, str(bad), "--check"], capture_output=True, text=True)
     assert r.returncode != 0 and "needs 2" in r.stderr
+
+
+def test_no_scalar_compare_of_a_register_with_itself():
+    # two names of the generator's register table once shared a register that one instruction compared ("equal values: the larger index" in
+    # the pull of the forward starts was `s_cmp_gt_i32 s21, s21`, never true: a forward stop never took a forward start that offered exactly
+    # its own value); such a compare has a constant result and is never what was meant
+    import re
+    same = re.findall(r"s_cmp_\w+ (s\d+|s\[\d+:\d+\]), \1\b", open(INC).read())
+    assert not same, same

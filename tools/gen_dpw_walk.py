@@ -46,7 +46,7 @@ def pair(n): return "s[%d:%d]" % (n, n + 1)
 ST = {"SC": pair(18), "SC_lo": "s18", "SC_hi": "s19", "TAGK": "s20", "TMP": "s21", "TM": pair(22), "OK": pair(24),
       "C0": pair(26), "C1": pair(28), "C2": pair(30),
       "SX0": pair(26), "SX0_lo": "s26", "SX0_hi": "s27", "SX1_lo": "s28", "SX1_hi": "s29", "SX2_lo": "s30", "SX2_hi": "s31",
-      "SV": pair(26), "SV_lo": "s26", "SV_hi": "s27", "BVS_lo": "s28", "BVS_hi": "s29", "CM": pair(30), "C2b": pair(22), "BI": "s21", "CI": "s35",
+      "SV": pair(26), "SV_lo": "s26", "SV_hi": "s27", "BVS_lo": "s28", "BVS_hi": "s29", "CM": pair(30), "C2b": pair(22), "BI": "s15", "CI": "s35",          # (BI: not TMP's register -- the pull compares the two; SVM's, which every user loads right before it reads it)
       "TBN": "s35", "LHS": "s14", "SVM": "s15",         # (s32 - s34 and s100 / s101 are the compiler's: stack and frame pointers, scratch)
       "TODO": pair(16),
       "E0": "s36", "E1": "s37", "E3": "s38", "PSL": "s39",      # the source: its lane, its position, its chain index; LDS address of the pull's scratch double
