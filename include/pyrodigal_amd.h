@@ -417,6 +417,50 @@ int pga_translate_genes_tokens(pga_ctx*, const pga_batch*, int64_t n_genes, cons
                                const pga_token_opts*, void* d_out /* device memory of the context's device */, int64_t n_out_elems,
                                void* stream /* hipStream_t, NULL = the null stream */, int64_t* len_out /* [n_genes], host */);
 
+/* The annotation of every base of a resident batch, left on the device as a tensor in the shape of the input: token-classification
+ * targets, codon-phase supervision, loss masks, GC3 or intergenic statistics in the same process.  The letters of the batch are not
+ * read; nothing comes to the host.
+ *   Raw byte.  Take contig i of a resident batch with length L_i.  This is the length the batch holds, so for a record trimmed by
+ *     trim_terminal_repeats it is the trimmed length.  Take position p in [0, L_i).
+ *     A gene record of contig i has 1-based inclusive [b, e], with 1 <= b <= L_i and 3 <= e - b + 1 <= L_i.  e > L_i is allowed only
+ *     on a contig flagged circular.  The record covers p through q = p + 1 or q = p + 1 + L_i, whichever lies in [b, e].  At most one
+ *     of the two does.
+ *     A covering record contributes:
+ *       0x01 / 0x02 / 0x04   forward gene (strand == 1): codon position (q - b) % 3 = 0 / 1 / 2
+ *       0x08 / 0x10 / 0x20   reverse gene: codon position (e - q) % 3 = 0 / 1 / 2, counted in the gene's own reading direction
+ *       0x40 (start codon)   forward: q <= b + 2 and partial_begin == 0.  Reverse: q >= e - 2 and partial_end == 0
+ *       0x80 (stop codon)    forward: q >= e - 2 and partial_end == 0.  Reverse: q <= b + 2 and partial_begin == 0
+ *     The partial flags are in sequence orientation, as translate_tokens.inl already notes.
+ *     raw[p] is the OR over all covering records, and 0 without one.  The rule is a union, so it does not depend on the order of the
+ *     records.  Same-strand overlaps land in different bits because they are in different frames.  A start or stop codon that
+ *     straddles the origin of a circle is handled by q.
+ *   Classes.  class_map[256] holds int64 ids, built complete by the host layer.  The element for p is class_map[raw[p]].  The kernel
+ *     does a plain look-up.
+ *   Layouts.  Padded (PGA_TOKENS_PADDED): B rows of stride S >= W >= max(L_i).  Row i holds its L_i elements, then pad up to W.  All
+ *     B x W elements are written.  Elements W .. S of a row are not touched.  Ragged (PGA_TOKENS_RAGGED): contig i is
+ *     out[off[i] .. off[i + 1]), with off the exclusive scan of L_i.  Nothing at or beyond off[B] is written.
+ *     Elements are uint8, int32 or int64.  Every id and pad must fit the element type.  d_out need only be element-aligned.
+ *     len_out[i] = L_i.  Nothing about sizes comes back from the device.
+ *   Validation.  Everything is checked on the host before anything is allocated or launched.  A failure returns PGA_EINVAL, and
+ *     pga_last_error names the record or field.  The checks are: element width; id ranges; W against the longest contig; n_out_elems
+ *     against the layout (off[B], or (B - 1) S + W); every record inside its contig, with a whole number of codons, and e > L_i only
+ *     where the contig is flagged circular; the alignment of d_out; and hipPointerGetAttributes calling d_out device memory of the
+ *     context's device.
+ *   Ordering and concurrency.  Those of pga_translate_genes_tokens exactly: the call records an event on `stream`, runs on the
+ *     context's upload stream behind it, one such call or upload at a time per context, and synchronises before it returns.
+ * Gene records come from the host.  Any subset or order of a result's records may be passed. */
+typedef struct pga_label_opts {
+    int32_t elem_bytes;         /* 1, 4 or 8 */
+    int32_t layout;             /* PGA_TOKENS_RAGGED or PGA_TOKENS_PADDED */
+    int64_t row_width;          /* W, padded layout (ignored for ragged) */
+    int64_t row_stride;         /* S, padded layout (ignored for ragged) */
+    int64_t class_map[256];     /* the id of every raw byte */
+    int64_t pad;                /* padded layout */
+} pga_label_opts;
+int pga_label_bases(pga_ctx*, const pga_batch*, int64_t n_genes, const pga_gene* genes, const pga_label_opts*,
+                    void* d_out /* device memory of the context's device */, int64_t n_out_elems,
+                    void* stream /* hipStream_t, NULL = the null stream */, int64_t* len_out /* [contigs of the batch], host */);
+
 /* ---- text output ------------------------------------------------------------------ */
 /* GFF, protein FASTA, gene FASTA, GenBank and the start-score file of gene records, rendered on the device from a resident
  * batch: byte for byte what the host writers Genes.write_gff / write_translations / write_genes / write_genbank / write_scores

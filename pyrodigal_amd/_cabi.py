@@ -28,7 +28,7 @@ EXPORTS = [
     "pga_batch_terminal_repeats", "pga_batch_trim_terminal_repeats", "pga_terminal_repeat_chunk",
     "pga_debug_poison",
     "pga_batch_create_device", "pga_batch_read",
-    "pga_translate_genes_tokens",
+    "pga_translate_genes_tokens", "pga_label_bases",
 ]
 STAGE_EXTRACT, STAGE_SCORE, STAGE_OVERLAP, STAGE_SEQUENCE = 1, 2, 3, 4
 
@@ -104,6 +104,11 @@ class TokenOpts(ctypes.Structure):
                 ("include_stop", ctypes.c_int32), ("strict", ctypes.c_int32), ("unknown_residue", ctypes.c_int32), ("_pad", ctypes.c_int32),
                 ("max_length", ctypes.c_int64), ("vocab", ctypes.c_int64 * 128), ("bos", ctypes.c_int64), ("eos", ctypes.c_int64),
                 ("pad", ctypes.c_int64)]
+
+
+class LabelOpts(ctypes.Structure):
+    _fields_ = [("elem_bytes", ctypes.c_int32), ("layout", ctypes.c_int32), ("row_width", ctypes.c_int64), ("row_stride", ctypes.c_int64),
+                ("class_map", ctypes.c_int64 * 256), ("pad", ctypes.c_int64)]
 
 
 TOKENS_RAGGED, TOKENS_PADDED = 0, 1                         # pga_token_opts.layout
@@ -186,6 +191,8 @@ def load():
     L.pga_translate_genes.argtypes = [vp, vp, i64, vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, vp]
     L.pga_translate_genes_tokens.restype = ctypes.c_int
     L.pga_translate_genes_tokens.argtypes = [vp, vp, i64, vp, vp, _P(TokenOpts), vp, i64, vp, vp]
+    L.pga_label_bases.restype = ctypes.c_int
+    L.pga_label_bases.argtypes = [vp, vp, i64, vp, _P(LabelOpts), vp, i64, vp, vp]
     L.pga_render_genes.restype = ctypes.c_int
     L.pga_render_genes.argtypes = [vp, vp, vp, i64, vp, vp, vp, vp, _P(RenderOpts), _P(_P(RenderResult))]
     L.pga_render_free.restype = None; L.pga_render_free.argtypes = [_P(RenderResult)]
@@ -1308,29 +1315,24 @@ class DeviceProteins:
 
     def cu_seqlens(self):
         """The exclusive scan of ``lengths`` as an int32 tensor on the tokens' device (torch)."""
-        import torch
-        cu = np.zeros(len(self.lengths) + 1, np.int64)
-        np.cumsum(self.lengths, out=cu[1:])
-        if cu[-1] >= 1 << 31:
-            raise OverflowError("more than 2^31 tokens do not fit an int32 cu_seqlens")
-        dev = self.tokens.device if isinstance(self.tokens, torch.Tensor) else torch.device("cuda", self.device)
-        return torch.from_numpy(cu.astype(np.int32)).to(dev)
+        return _cu_seqlens(self.lengths, self.tokens, self.device)
 
 
-def tokens_into(L, ctx_h, batch_h, device, n_contigs, genes, tables, spec, out=None, stream=None):
-    """``pga_translate_genes_tokens`` on raw handles (what ``Context.translate_tokens`` and the finder's device call share): the token
-    ids of ``genes`` (GENE_DTYPE records of the resident batch) under ``tables`` into ``out``, or into a new torch tensor."""
-    if not isinstance(spec, ProteinTokens):
-        raise TypeError("the token rule must be a ProteinTokens, not %r" % type(spec).__name__)
-    genes = np.ascontiguousarray(genes, dtype=GENE_DTYPE)
-    tables = np.ascontiguousarray(tables, np.int32)
-    if tables.shape != (n_contigs,):
-        raise ValueError(f"tables has {tables.size} entries for {n_contigs} contigs")
-    n, eb = len(genes), spec.elem_bytes
-    lens = spec.lengths(genes)
-    off = np.zeros(n + 1, np.int64)
-    np.cumsum(lens, out=off[1:])
-    padded = spec.layout == "padded"
+def _cu_seqlens(lengths, tensor, device):
+    import torch
+    cu = np.zeros(len(lengths) + 1, np.int64)
+    np.cumsum(lengths, out=cu[1:])
+    if cu[-1] >= 1 << 31:
+        raise OverflowError("more than 2^31 elements do not fit an int32 cu_seqlens")
+    dev = tensor.device if isinstance(tensor, torch.Tensor) else torch.device("cuda", device)
+    return torch.from_numpy(cu.astype(np.int32)).to(dev)
+
+
+def _device_output(spec, out, stream, device, lens, total, row, unit):
+    """The device tensor a rule writes (``tokens_into`` and ``labels_into`` share this): ``out`` checked against the rule's element
+    type and layout and against ``lens``, the elements of every row, or a new torch tensor under torch's current stream.  Returns
+    (out, stream, its ``__cuda_array_interface__``, W, S, the elements the layout may use)."""
+    n, eb, padded = len(lens), spec.elem_bytes, spec.layout == "padded"
     longest = int(lens.max()) if n else 0
     if out is None:
         try:
@@ -1338,7 +1340,7 @@ def tokens_into(L, ctx_h, batch_h, device, n_contigs, genes, tables, spec, out=N
         except ImportError:
             raise TypeError("torch is not installed: pass out=, a device array with __cuda_array_interface__") from None
         with torch.cuda.device(device):
-            out = torch.empty((n, longest) if padded else (int(off[-1]),), dtype=getattr(torch, spec.dtype), device="cuda")
+            out = torch.empty((n, longest) if padded else (total,), dtype=getattr(torch, spec.dtype), device="cuda")
             if stream is None:
                 stream = int(torch.cuda.current_stream().cuda_stream)
     cai = getattr(out, "__cuda_array_interface__", None)
@@ -1360,14 +1362,32 @@ def tokens_into(L, ctx_h, batch_h, device, n_contigs, genes, tables, spec, out=N
         if strides is not None and n > 1 and (strides[0] % eb or strides[0] < 0):
             raise ValueError("the rows of out do not lie a whole, positive number of elements apart")
         if width < longest:
-            raise ValueError(f"out has {width} columns: gene {int(np.argmax(lens))} has {longest} tokens")
+            raise ValueError(f"out has {width} columns: {row} {int(np.argmax(lens))} has {longest} {unit}")
         n_out = (n - 1) * stride + width if n else 0
     else:
         if len(shape) != 1:
             raise ValueError(f"the ragged layout needs a 1-D tensor, not one of shape {shape}")
-        if shape[0] < off[-1]:
-            raise ValueError(f"out has {shape[0]} elements: the genes have {int(off[-1])} tokens")
+        if shape[0] < total:
+            raise ValueError(f"out has {shape[0]} elements: the {row}s have {total} {unit}")
         n_out = shape[0]
+    return out, stream, cai, width, stride, n_out
+
+
+def tokens_into(L, ctx_h, batch_h, device, n_contigs, genes, tables, spec, out=None, stream=None):
+    """``pga_translate_genes_tokens`` on raw handles (what ``Context.translate_tokens`` and the finder's device call share): the token
+    ids of ``genes`` (GENE_DTYPE records of the resident batch) under ``tables`` into ``out``, or into a new torch tensor."""
+    if not isinstance(spec, ProteinTokens):
+        raise TypeError("the token rule must be a ProteinTokens, not %r" % type(spec).__name__)
+    genes = np.ascontiguousarray(genes, dtype=GENE_DTYPE)
+    tables = np.ascontiguousarray(tables, np.int32)
+    if tables.shape != (n_contigs,):
+        raise ValueError(f"tables has {tables.size} entries for {n_contigs} contigs")
+    n = len(genes)
+    lens = spec.lengths(genes)
+    off = np.zeros(n + 1, np.int64)
+    np.cumsum(lens, out=off[1:])
+    padded = spec.layout == "padded"
+    out, stream, cai, width, stride, n_out = _device_output(spec, out, stream, device, lens, int(off[-1]), "gene", "tokens")
     ptr = cai["data"][0]
     len_out = np.zeros(max(n, 1), np.int64)
     o = spec.opts(width, stride)
@@ -1398,6 +1418,168 @@ def _translate_tokens(self, batch, result_or_genes, spec, out=None, tables=None,
         tts = [int(np.frombuffer(m[8:12].tobytes(), np.int32)[0]) for m in self._models]
         tables = [tts[c["model"]] if c["model"] >= 0 else 11 for c in contigs]
     return tokens_into(self.L, self.h, batch.h, self.device, batch.n, genes, tables, spec, out, stream)
+
+
+LABEL_PRESETS = ("raw", "coding", "strand", "frame")
+
+
+def label_class_map(preset):
+    """The 256 ids of a preset of :class:`BaseLabels`, indexed by the raw byte of the rule in ``pyrodigal_amd.h``."""
+    ids = []
+    for raw in range(256):
+        fwd, rev = raw & 0x07, raw & 0x38
+        if preset == "raw":
+            ids.append(raw)
+        elif preset == "coding":
+            ids.append(1 if raw & 0x3f else 0)
+        elif preset == "strand":
+            ids.append((1 if fwd else 0) + (2 if rev else 0))
+        elif preset == "frame":
+            pos = raw & 0x3f
+            ids.append(0 if not pos else 7 if pos & (pos - 1) else pos.bit_length())
+        else:
+            raise ValueError("classes must be 256 ids or one of %s, not %r" % (", ".join(map(repr, LABEL_PRESETS)), preset))
+    return tuple(ids)
+
+
+class BaseLabels:
+    """How ``label_bases`` / ``find_labels_batch`` write the annotation of every base into a device tensor (``pga_label_opts``; the
+    rule is in ``pyrodigal_amd.h``).
+
+    ``classes``: 256 ids, indexed by the raw byte of a base (codon position per strand, start and stop codon bits), or a preset:
+    ``"raw"`` the byte itself; ``"coding"`` 0 or 1, by ``raw & 0x3f``; ``"strand"`` 0 none, 1 forward only, 2 reverse only, 3 both;
+    ``"frame"`` 0 intergenic, 1-3 forward codon position, 4-6 reverse codon position, 7 when more than one of the six position bits
+    is set.  ``pad`` fills the rows of the padded layout behind a contig's last base: -100 by default for the signed types (torch's
+    ``ignore_index``); it must be given for ``uint8`` in the padded layout.  ``dtype``: ``"uint8"``, ``"int32"`` or ``"int64"``; every
+    id must fit it.  Everything that needs no device is checked here.  Hashable and picklable."""
+
+    def __init__(self, classes="frame", *, pad=None, dtype="int64", layout="padded"):
+        name = dtype if isinstance(dtype, str) else np.dtype(dtype).name
+        if name not in _TOKEN_DTYPES:
+            raise ValueError(f"dtype must be uint8, int32 or int64, not {name!r}")
+        if layout not in ("padded", "ragged"):
+            raise ValueError(f"layout must be \"padded\" or \"ragged\", not {layout!r}")
+        if isinstance(classes, str):
+            self.class_map = label_class_map(classes)
+        else:
+            ids = list(classes)
+            if len(ids) != 256:
+                raise ValueError(f"classes has {len(ids)} ids: there is one for each of the 256 raw bytes")
+            self.class_map = tuple(_token_id(v, f"the id of raw byte {k:#04x}") for k, v in enumerate(ids))
+        self.classes = classes if isinstance(classes, str) else None
+        lo, hi = _TOKEN_DTYPES[name][2:]
+        if pad is None:
+            if layout == "padded" and name == "uint8":
+                raise ValueError("the padded layout of uint8 labels needs `pad`: the default, -100, does not fit")
+            pad = -100 if name != "uint8" else 0
+        self.pad = _token_id(pad, "pad")
+        for what, v in [(f"the id of raw byte {k:#04x}", v) for k, v in enumerate(self.class_map)] + [("pad", self.pad)]:
+            if not lo <= v <= hi:
+                raise ValueError(f"{what}, {v}, does not fit {name}")
+        self.dtype, self.layout = name, layout
+
+    elem_bytes = property(lambda self: _TOKEN_DTYPES[self.dtype][0])
+    typestr = property(lambda self: _TOKEN_DTYPES[self.dtype][1])
+
+    def _key(self):
+        return (self.class_map, self.classes, self.pad, self.dtype, self.layout)
+
+    def __eq__(self, other):
+        return isinstance(other, BaseLabels) and self._key() == other._key()
+
+    def __hash__(self):
+        return hash(self._key())
+
+    def __repr__(self):
+        return "pyrodigal_amd.BaseLabels(%s, pad=%r, dtype=%r, layout=%r)" % (
+            repr(self.classes) if self.classes is not None else "<256 ids>", self.pad, self.dtype, self.layout)
+
+    def __reduce__(self):
+        return _base_labels_from_key, (self._key(),)
+
+    def opts(self, row_width=0, row_stride=0):
+        o = LabelOpts()
+        o.elem_bytes, o.layout = self.elem_bytes, TOKENS_PADDED if self.layout == "padded" else TOKENS_RAGGED
+        o.row_width, o.row_stride = int(row_width), int(row_stride)
+        o.class_map[:] = self.class_map
+        o.pad = self.pad
+        return o
+
+
+def _base_labels_from_key(key):
+    b = BaseLabels.__new__(BaseLabels)
+    b.class_map, b.classes, b.pad, b.dtype, b.layout = key
+    return b
+
+
+class _ContigLabels:
+    """``DeviceLabels.labels_of``: entry i is a view of contig i's row (padded, its first ``lengths[i]`` elements) or slice (ragged)."""
+
+    def __init__(self, owner):
+        self.owner = owner
+
+    def __len__(self):
+        return len(self.owner.lengths)
+
+    def __getitem__(self, i):
+        d = self.owner
+        i = range(len(self))[i]
+        return d.labels[i, :int(d.lengths[i])] if d.offsets is None else d.labels[int(d.offsets[i]):int(d.offsets[i + 1])]
+
+
+class DeviceLabels:
+    """The annotation of every base of a batch in device memory.  ``labels``: the tensor (``[B, W]`` padded, 1-D ragged);
+    ``lengths``: the bases of every contig as the batch holds it (numpy int64, host; the trimmed length of a record trimmed by
+    ``trim_terminal_repeats``); ``offsets``: ragged only, contig i is ``labels[offsets[i]:offsets[i + 1]]``; ``labels_of[i]``:
+    contig i's own elements as a view of ``labels``."""
+
+    def __init__(self, labels, lengths, offsets, device):
+        self.labels, self.lengths, self.offsets, self.device = labels, lengths, offsets, device
+
+    @property
+    def labels_of(self):
+        return _ContigLabels(self)
+
+    def cu_seqlens(self):
+        """The exclusive scan of ``lengths`` as an int32 tensor on the labels' device (torch)."""
+        return _cu_seqlens(self.lengths, self.labels, self.device)
+
+
+def labels_into(L, ctx_h, batch_h, device, lengths, genes, spec, out=None, stream=None):
+    """``pga_label_bases`` on raw handles (what ``Context.label_bases`` and the finder's device call share): the labels of the bases
+    of the resident batch, whose contigs have ``lengths`` bases, under ``genes`` (GENE_DTYPE records) into ``out``, or into a new
+    torch tensor."""
+    if not isinstance(spec, BaseLabels):
+        raise TypeError("the label rule must be a BaseLabels, not %r" % type(spec).__name__)
+    genes = np.ascontiguousarray(genes, dtype=GENE_DTYPE)
+    lens = np.ascontiguousarray(lengths, np.int64)
+    n = len(lens)
+    off = np.zeros(n + 1, np.int64)
+    np.cumsum(lens, out=off[1:])
+    padded = spec.layout == "padded"
+    out, stream, cai, width, stride, n_out = _device_output(spec, out, stream, device, lens, int(off[-1]), "contig", "bases")
+    ptr = cai["data"][0]
+    len_out = np.zeros(max(n, 1), np.int64)
+    o = spec.opts(width, stride)
+    rc = L.pga_label_bases(ctx_h, batch_h, len(genes), ctypes.c_void_p(genes.ctypes.data), ctypes.byref(o),
+                           ctypes.c_void_p(int(ptr) if ptr else 0), n_out, ctypes.c_void_p(DeviceSequences._stream_of(out, stream)),
+                           ctypes.c_void_p(len_out.ctypes.data))
+    if rc != PGA_OK:
+        _raise(L, ctx_h, rc, "pga_label_bases")
+    if not np.array_equal(len_out[:n], lens):
+        raise ValueError("`lengths` are not those of the batch")
+    return DeviceLabels(out, lens, None if padded else off, device)
+
+
+def _label_bases(self, batch, result_or_genes, spec, out=None, stream=None):
+    """The annotation of every base of the resident ``batch`` under gene records, as a device tensor in the shape of the input
+    (``pga_label_bases``): nothing comes to the host.  ``result_or_genes``: a result of ``find_genes`` on the batch, or gene records
+    of one (any subset or order).  ``spec``: a :class:`BaseLabels`.  ``out``: any object with ``__cuda_array_interface__`` -- 1-D for
+    the ragged layout, ``[B, W]`` with a contiguous last dimension for the padded one; ``None``: a torch tensor is allocated on the
+    context's device under torch's current stream.  ``stream``: the stream that last used ``out``, as in :class:`DeviceSequences`.
+    Returns a :class:`DeviceLabels`."""
+    genes = getattr(result_or_genes, "genes", result_or_genes)
+    return labels_into(self.L, self.h, batch.h, self.device, batch.lengths, genes, spec, out, stream)
 
 
 class RenderedText:
@@ -1610,6 +1792,7 @@ def _splice_fallback(ctx, name, opts, data, coff, fb, genes, contigs, moc, ids, 
 Context.render_genes = _render_genes
 Context.translate_genes = _translate_genes
 Context.translate_tokens = _translate_tokens
+Context.label_bases = _label_bases
 Context.train = _train
 Context.train_batch = _train_batch
 Context.upload = _upload

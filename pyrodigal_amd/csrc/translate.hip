@@ -7,6 +7,7 @@
 
 #include <string.h>
 
+#include <algorithm>
 #include <vector>
 
 struct pga_batch_view { pga_ctx* ctx; int32_t n; int64_t total; const ContigDesc* ct; const char* d_seq; const uint8_t* circular /* or nullptr: all linear */; };
@@ -71,6 +72,7 @@ int tables_ready(pga_ctx* c) {
 }
 
 #include "translate_tokens.inl"
+#include "label_bases.inl"
 
 }  // namespace
 
@@ -231,4 +233,104 @@ extern "C" int pga_translate_genes_tokens(pga_ctx* c, const pga_batch* batch, in
     if (e == hipSuccess) e = hipStreamSynchronize(L.st);         // on return the tensor is complete for any stream
     pga_upload_lease_give(c);
     return pga_hip_try_(c, e, "pga_translate_genes_tokens");
+}
+
+extern "C" int pga_label_bases(pga_ctx* c, const pga_batch* batch, int64_t n_genes, const pga_gene* genes, const pga_label_opts* o, void* d_out,
+                               int64_t n_out_elems, void* stream, int64_t* len_out) {
+    if (!c) return PGA_EINVAL;
+    auto bad = [&](std::string msg) { c->err = "pga_label_bases: " + msg; return PGA_EINVAL; };
+    if (!batch || !o || n_genes < 0 || n_out_elems < 0 || (n_genes > 0 && !genes)) return bad("bad arguments");
+    const pga_batch_view bv = pga_batch_peek(batch);
+    if (bv.ctx != c) return bad("the batch belongs to another context");
+    if (bv.n > 0 && !len_out) return bad("bad arguments");
+    // ---- validation: all of it on the host, before anything is allocated or launched ----
+    const int eb = o->elem_bytes;
+    if (eb != 1 && eb != 4 && eb != 8) return bad("elem_bytes must be 1, 4 or 8, not " + std::to_string(eb));
+    if (o->layout != PGA_TOKENS_RAGGED && o->layout != PGA_TOKENS_PADDED) return bad("layout must be PGA_TOKENS_RAGGED or PGA_TOKENS_PADDED, not " + std::to_string(o->layout));
+    const bool padded = o->layout == PGA_TOKENS_PADDED;
+    auto fits = [&](const int64_t v) { return eb == 8 || (eb == 4 ? v >= INT32_MIN && v <= INT32_MAX : v >= 0 && v <= 255); };
+    const char* const elem_name = eb == 1 ? "uint8" : eb == 4 ? "int32" : "int64";
+    for (int k = 0; k < 256; k++)
+        if (!fits(o->class_map[k])) return bad("class_map[" + std::to_string(k) + "] = " + std::to_string(o->class_map[k]) + " does not fit " + elem_name);
+    if (padded && !fits(o->pad)) return bad("pad = " + std::to_string(o->pad) + " does not fit " + elem_name);
+    const size_t B = (size_t)bv.n;
+    std::vector<int64_t> off(B + 1, 0), iv_off(B + 1, 0);
+    int64_t longest = 0, longest_i = -1;
+    for (size_t i = 0; i < B; i++) {
+        const int64_t len = bv.ct[i].len;
+        if (len > INT32_MAX - 16) return bad("contig " + std::to_string(i) + " is too long");
+        off[i + 1] = off[i] + len;
+        if (len > longest) { longest = len; longest_i = (int64_t)i; }
+    }
+    int64_t need = off[B];
+    if (padded) {
+        const int64_t W = o->row_width, S = o->row_stride;
+        if (W < longest) return bad("row_width = " + std::to_string(W) + " is less than the " + std::to_string(longest) + " bases of contig " + std::to_string(longest_i));
+        if (W < 0 || S < W) return bad("row_stride = " + std::to_string(S) + " is less than row_width = " + std::to_string(W));
+        if (B > 1 && S > (INT64_MAX / 8 - W) / (int64_t)(B - 1)) return bad("row_stride = " + std::to_string(S) + " is too large");
+        need = B > 0 ? (int64_t)(B - 1) * S + W : 0;
+    }
+    if (n_out_elems < need) return bad("n_out_elems = " + std::to_string(n_out_elems) + " is less than the " + std::to_string(need) + " elements of the layout");
+    // every record inside its contig, in whole codons; a record across the origin makes two stretches
+    for (int64_t g = 0; g < n_genes; g++) {
+        const pga_gene& G = genes[g];
+        const std::string who = "gene " + std::to_string(g);
+        if (G.contig < 0 || G.contig >= bv.n) return bad(who + " names contig " + std::to_string(G.contig) + " of " + std::to_string(bv.n));
+        const int64_t len = bv.ct[G.contig].len, glen = (int64_t)G.end - G.begin + 1;
+        if (G.begin < 1 || G.begin > len || glen < 3 || glen > len) return bad(who + " lies outside its contig");
+        if (glen % 3) return bad(who + " is " + std::to_string(glen) + " bases long, no whole number of codons");
+        if (G.end > len && !(bv.circular && bv.circular[G.contig])) return bad(who + " ends beyond its contig, which is not flagged circular");
+        iv_off[(size_t)G.contig + 1] += G.end > len ? 2 : 1;
+    }
+    if (need > 0) {
+        if (!d_out) return bad("d_out is NULL");
+        if ((uintptr_t)d_out % (uintptr_t)eb) return bad("d_out is not aligned to its " + std::to_string(eb) + "-byte elements");
+        if (hipSetDevice(c->device) != hipSuccess) return PGA_EDEVICE;
+        // the pointer is asked about, never dereferenced on the host, and never handed to a kernel unless the runtime calls it device memory
+        hipPointerAttribute_t at{};
+        const hipError_t pe = hipPointerGetAttributes(&at, d_out);
+        if (pe != hipSuccess) (void)hipGetLastError();
+        if (pe != hipSuccess || at.type != hipMemoryTypeDevice) return bad("d_out is not device memory (a host pointer?)");
+        if (at.device != c->device) return bad("d_out is not device memory of the context's device " + std::to_string(c->device) + " but of device " + std::to_string(at.device));
+    }
+    for (size_t i = 0; i < B; i++) len_out[i] = bv.ct[i].len;
+    if (need == 0) return PGA_OK;
+    // ---- the kernel's tables: staged in the upload's pinned area as they will lie on the device, one copy ----
+    for (size_t i = 0; i < B; i++) iv_off[i + 1] += iv_off[i];
+    const size_t n_iv = (size_t)iv_off[B];
+    const size_t off_b = sizeof(int64_t) * (B + 1), map_b = sizeof(int64_t) * 256, iv_b = sizeof(LabIv) * n_iv;
+    const size_t tab = 2 * off_b + map_b + iv_b;               // (the stretches begin at a multiple of 16 bytes)
+    pga_upload_lease L{};
+    { const int rc = pga_upload_lease_take(c, tab, &L); if (rc) return rc; }
+    memcpy(L.pin, off.data(), off_b);
+    memcpy(L.pin + off_b, iv_off.data(), off_b);
+    memcpy(L.pin + 2 * off_b, o->class_map, map_b);
+    lab_stretches(genes, n_genes, bv.ct, iv_off.data(), B, (LabIv*)(L.pin + 2 * off_b + map_b));
+    LabArgs a{};
+    a.off = (const int64_t*)L.dev; a.iv_off = (const int64_t*)(L.dev + off_b); a.cmap = (const int64_t*)(L.dev + 2 * off_b);
+    a.iv = (const LabIv*)(L.dev + 2 * off_b + map_b);
+    a.n_contigs = bv.n; a.n_elems = need; a.W = padded ? o->row_width : 0; a.S = padded ? o->row_stride : 0; a.pad = padded ? o->pad : 0;
+    a.out0 = (char*)((uintptr_t)d_out & ~(uintptr_t)15);
+    a.lead = (int32_t)(((uintptr_t)d_out - (uintptr_t)a.out0) / (uintptr_t)eb);
+    const int64_t per = 16 / eb, pieces = (a.lead + need + per - 1) / per;
+    const dim3 grid((unsigned)((pieces + kLabThreads - 1) / kLabThreads)), block(kLabThreads);
+    // the upload stream is non-blocking: it waits for what the caller's stream held when the call came
+    hipError_t e = hipEventRecord(L.ev, (hipStream_t)stream);
+    if (e == hipSuccess) e = hipStreamWaitEvent(L.st, L.ev, 0);
+    if (e == hipSuccess) e = hipMemcpyAsync(L.dev, L.pin, tab, hipMemcpyHostToDevice, L.st);
+    if (e == hipSuccess) {
+        if (padded) {
+            if (eb == 1) hipLaunchKernelGGL((k_label_bases<1, true>), grid, block, 0, L.st, a);
+            else if (eb == 4) hipLaunchKernelGGL((k_label_bases<4, true>), grid, block, 0, L.st, a);
+            else hipLaunchKernelGGL((k_label_bases<8, true>), grid, block, 0, L.st, a);
+        } else {
+            if (eb == 1) hipLaunchKernelGGL((k_label_bases<1, false>), grid, block, 0, L.st, a);
+            else if (eb == 4) hipLaunchKernelGGL((k_label_bases<4, false>), grid, block, 0, L.st, a);
+            else hipLaunchKernelGGL((k_label_bases<8, false>), grid, block, 0, L.st, a);
+        }
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(L.st);         // on return the tensor is complete for any stream
+    pga_upload_lease_give(c);
+    return pga_hip_try_(c, e, "pga_label_bases");
 }

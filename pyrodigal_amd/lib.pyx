@@ -1651,7 +1651,7 @@ cdef pga_batch* _device_batch(pga_ctx* ctx, object dev) except? NULL:
 cdef int _one_call_for_tokens(object tokens, list calls) except -1:
     if tokens is not None and len(calls) > 1:
         raise ValueError("`training_infos` would split this request into %d device calls (more than `coalesce_bases` bases or four "
-                         "translation tables in a row): find_proteins_batch writes one tensor per request" % len(calls))
+                         "translation tables in a row): %s writes one tensor per request" % (len(calls), tokens.get("method", "find_proteins_batch")))
     return 0
 
 
@@ -1664,7 +1664,8 @@ cdef class _FindRequest:
     cdef object sets            # int32 per sequence: dense set id, -1: on its own; None: no sets (such a request rides alone)
     cdef bint translate
     cdef object tokens          # find_proteins_batch: {"spec", "out", "stream"} -- the proteins also go to a device tensor, and the device
-                                # call leaves the DeviceProteins under "proteins" (such a request rides alone); None: no tokens
+                                # call leaves the DeviceProteins under "proteins" (such a request rides alone); None: no tokens.
+                                # find_labels_batch: the same with a BaseLabels as "spec", and the DeviceLabels under "labels"
     cdef ssize_t first_id
     cdef int64_t bases
     cdef list out               # one Genes per sequence, filled in by the thread that ran the device call
@@ -2080,8 +2081,41 @@ cdef class GeneFinder:
             genes = self._find_genes_sets(self._wrap_sequences(sequences, regions), translate, set_ids, circ, tr_search, tr_params, tok)
         return genes, tok["proteins"]
 
+    def find_labels_batch(self, object sequences, object labels, *, object out=None, object stream=None, bint translate=False,
+                          object training_infos=None, object regions=None, object circular=None, object sets=None,
+                          object trim_terminal_repeats=None):
+        """`find_genes_batch`, and the annotation of every base left in device memory as a tensor in the shape of the input: returns
+        `(genes, device_labels)`, the list of `Genes` that `find_genes_batch` returns for the same arguments and a `DeviceLabels`.
+
+        `labels`: a `BaseLabels` -- the class of every raw byte (codon position per strand, start and stop codons), element type,
+        padded or ragged layout.  The tensor is written on the device while the batch is resident, on the batch the finder called:
+        row (or slice) i is sequence i of the request, and with `trim_terminal_repeats` a trimmed record's row ends at its trimmed
+        length (`device_labels.lengths[i]`), the rest of the row being `pad`.  `out`: the device tensor to write (anything with
+        `__cuda_array_interface__`), `None`: a torch tensor allocated under torch's current stream; `stream`: the stream that last
+        used `out`.  Every option of `find_genes_batch` applies and `sequences` may be a `DeviceSequences`.  The request is a device
+        call of its own: one tensor per request, so a request that `training_infos` would split into several device calls is a
+        `ValueError`."""
+        if not isinstance(labels, _cabi.BaseLabels):
+            raise TypeError("`labels` must be a BaseLabels, not %r" % type(labels).__name__)
+        cdef dict tok = {"spec": labels, "out": out, "stream": stream, "labels": None, "method": "find_labels_batch"}
+        cdef list circ, tr_search
+        cdef object dev, set_ids, tr_params
+        dev, sequences, circ, set_ids, tr_search, tr_params = self._batch_options(sequences, training_infos, circular, sets, trim_terminal_repeats)
+        sequences = list(sequences)
+        if not sequences:
+            raise ValueError("find_labels_batch needs at least one sequence")
+        if dev is not None:
+            genes = self._find_genes_device(dev, translate, training_infos, regions, circ, set_ids, tr_search, tr_params, tok)
+        elif training_infos is not None:
+            genes = self._find_genes_models(sequences, translate, training_infos, regions, circ, tr_search, tr_params, tok)
+        else:
+            if not self.meta and self.training_info is None:
+                raise RuntimeError("cannot find genes without having trained in single mode")
+            genes = self._find_genes_sets(self._wrap_sequences(sequences, regions), translate, set_ids, circ, tr_search, tr_params, tok)
+        return genes, tok["labels"]
+
     cdef tuple _batch_options(self, object sequences, object training_infos, object circular, object sets, object trim_terminal_repeats):
-        """The options of `find_genes_batch` / `find_proteins_batch`, checked against each other and against the number of sequences:
+        """The options of `find_genes_batch` / `find_proteins_batch` / `find_labels_batch`, checked against each other and against the number of sequences:
         (the DeviceSequences or None, the sequences, circular flags, set ids, terminal-repeat search and its parameters)."""
         cdef list circ = None
         cdef object dev = None
@@ -2471,7 +2505,14 @@ cdef class GeneFinder:
             if translate:
                 o.prot, o.prot_off, o.tables = self._translate(ctx, batch, res[0], n, tinf_of)
             if o.tok is not None:
-                self._tokens(ctx, batch, res[0], n, tinf_of, o.tok)
+                if isinstance(o.tok["spec"], _cabi.BaseLabels):
+                    # (the batch the finder called: without the bases `_trimmed_batch` took off)
+                    lengths = np.array([len((<Sequence> q).data) for q in seqs], np.int64)
+                    if trimmed != NULL:
+                        lengths -= o.tr_trim[:n]
+                    self._labels(ctx, batch, res[0], lengths, o.tok)
+                else:
+                    self._tokens(ctx, batch, res[0], n, tinf_of, o.tok)
         finally:
             if batch != NULL:
                 pga_batch_free(batch)
@@ -2562,6 +2603,16 @@ cdef class GeneFinder:
         tables = self._tables_of(res, n, tinf_of)[:n]
         tok["proteins"] = _cabi.tokens_into(_cabi.load(), ctypes.c_void_p(<size_t> ctx), ctypes.c_void_p(<size_t> batch), self.device, n,
                                             genes, tables, tok["spec"], tok["out"], tok["stream"])
+        return 0
+
+    cdef int _labels(self, pga_ctx* ctx, pga_batch* batch, pga_result* res, object lengths, dict tok) except -1:
+        """The annotation of every base under the genes of `res` into the request's device tensor, while the batch the finder called
+        is resident (`pga_label_bases` through the raw layer's marshalling): leaves the `DeviceLabels` in `tok`."""
+        genes = np.zeros(0, _cabi.GENE_DTYPE)
+        if res.n_genes > 0:
+            genes = np.frombuffer(PyBytes_FromStringAndSize(<const char*> res.genes, res.n_genes * sizeof(pga_gene)), dtype=_cabi.GENE_DTYPE)
+        tok["labels"] = _cabi.labels_into(_cabi.load(), ctypes.c_void_p(<size_t> ctx), ctypes.c_void_p(<size_t> batch), self.device,
+                                          lengths, genes, tok["spec"], tok["out"], tok["stream"])
         return 0
 
     cdef object _tables_of(self, pga_result* res, int n, list tinf_of):
