@@ -1139,16 +1139,9 @@ def _translate_genes(self, batch, result, tables=None, unknown_residue="X", incl
     ``(letters, offsets)``: gene g is ``letters[offsets[g]:offsets[g + 1]]`` (a uint8 array of ASCII codes)."""
     genes = np.ascontiguousarray(result.genes)
     n = len(genes)
-    if tables is None:
-        tts = [int(np.frombuffer(m[8:12].tobytes(), np.int32)[0]) for m in self._models]
-        tables = [tts[c["model"]] if c["model"] >= 0 else 11 for c in result.contigs]
-    tables = np.ascontiguousarray(tables, np.int32)
-    stop_edge = np.where(genes["strand"] == 1, genes["partial_end"], genes["partial_begin"]).astype(bool)
-    lens = (genes["end"].astype(np.int64) - genes["begin"] + 1) // 3
-    if not include_stop:
-        lens = np.maximum(lens - (~stop_edge), 0)
+    tables = np.ascontiguousarray(_default_tables(self, result.contigs) if tables is None else tables, np.int32)
     off = np.zeros(n + 1, np.int64)
-    np.cumsum(lens, out=off[1:])
+    np.cumsum(_residue_counts(genes, include_stop), out=off[1:])
     out = np.zeros(max(int(off[-1]), 1), np.uint8)
     unk = unknown_residue.encode("ascii") if isinstance(unknown_residue, str) else bytes(unknown_residue)
     if len(unk) != 1:
@@ -1158,6 +1151,19 @@ def _translate_genes(self, batch, result, tables=None, unknown_residue="X", incl
     if rc != PGA_OK:
         _raise(self.L, self.h, rc, "pga_translate_genes")
     return out[:int(off[-1])], off
+
+
+def _default_tables(self, contigs):
+    """The translation table of every contig of a result: that of the model that won it, 11 where none did."""
+    tts = [int(np.frombuffer(m[8:12].tobytes(), np.int32)[0]) for m in self._models]
+    return [tts[c["model"]] if c["model"] >= 0 else 11 for c in contigs]
+
+
+def _residue_counts(genes, include_stop):
+    """Residues of every gene record (int64): host arithmetic on the coordinates, as the library does it."""
+    stop_edge = np.where(genes["strand"] == 1, genes["partial_end"], genes["partial_begin"]).astype(bool)
+    r = (genes["end"].astype(np.int64) - genes["begin"] + 1) // 3
+    return np.maximum(r if include_stop else r - (~stop_edge), 0)
 
 
 AMINO_ACIDS = "ACDEFGHIKLMNPQRSTVWY"
@@ -1170,7 +1176,41 @@ def _token_id(value, name):
     return int(value)
 
 
-class ProteinTokens:
+class _TensorRule:
+    """What ProteinTokens and BaseLabels share: the element type and layout of the device tensor, value semantics over ``_key()``,
+    and the head of the options struct.  A subclass says what one row is (``row`` and its ``unit``), what it needs of every contig
+    of the batch (``per_contig``: ``"tables"`` or ``"lengths"``), and has ``write``, the call on raw handles with just that."""
+
+    def _set_format(self, dtype, layout):
+        name = dtype if isinstance(dtype, str) else np.dtype(dtype).name
+        if name not in _TOKEN_DTYPES:
+            raise ValueError(f"dtype must be uint8, int32 or int64, not {name!r}")
+        if layout not in ("padded", "ragged"):
+            raise ValueError(f"layout must be \"padded\" or \"ragged\", not {layout!r}")
+        self.dtype, self.layout = name, layout
+
+    elem_bytes = property(lambda self: _TOKEN_DTYPES[self.dtype][0])
+    typestr = property(lambda self: _TOKEN_DTYPES[self.dtype][1])
+
+    def _check_fit(self, ids):                           # (what, value or None) of everything that goes into the tensor
+        lo, hi = _TOKEN_DTYPES[self.dtype][2:]
+        for what, v in ids:
+            if v is not None and not lo <= v <= hi:
+                raise ValueError(f"{what}, {v}, does not fit {self.dtype}")
+
+    def __eq__(self, other):
+        return isinstance(other, type(self)) and self._key() == other._key()
+
+    def __hash__(self):
+        return hash(self._key())
+
+    def _opts(self, o, row_width, row_stride):
+        o.elem_bytes, o.layout = self.elem_bytes, TOKENS_PADDED if self.layout == "padded" else TOKENS_RAGGED
+        o.row_width, o.row_stride, o.pad = int(row_width), int(row_stride), self.pad
+        return o
+
+
+class ProteinTokens(_TensorRule):
     """How ``translate_tokens`` / ``find_proteins_batch`` write proteins into a device tensor (``pga_token_opts``; the rule is in
     ``pyrodigal_amd.h``).
 
@@ -1184,11 +1224,7 @@ class ProteinTokens:
 
     def __init__(self, vocabulary, *, unknown=None, bos=None, eos=None, pad=0, dtype="int64", layout="padded", max_length=None,
                  include_stop=False, strict=True, unknown_residue="X"):
-        name = dtype if isinstance(dtype, str) else np.dtype(dtype).name
-        if name not in _TOKEN_DTYPES:
-            raise ValueError(f"dtype must be uint8, int32 or int64, not {name!r}")
-        if layout not in ("padded", "ragged"):
-            raise ValueError(f"layout must be \"padded\" or \"ragged\", not {layout!r}")
+        self._set_format(dtype, layout)
         unk = unknown_residue.decode("ascii", "replace") if isinstance(unknown_residue, (bytes, bytearray)) else unknown_residue
         if not isinstance(unk, str) or len(unk) != 1 or not 0 < ord(unk) < 128:
             raise ValueError("`unknown_residue` must be a single ASCII character")
@@ -1212,18 +1248,14 @@ class ProteinTokens:
         self.bos = None if bos is None else _token_id(bos, "bos")
         self.eos = None if eos is None else _token_id(eos, "eos")
         self.pad = _token_id(pad, "pad")
-        self.dtype, self.layout = name, layout
         self.include_stop, self.strict, self.unknown_residue = bool(include_stop), bool(strict), unk
         for ch in AMINO_ACIDS + ("*" if self.include_stop else "") + unk:
             if ch not in given and self.unknown is None:
                 raise ValueError(f"the vocabulary has no id for {ch!r}, a letter the translation can hold, and `unknown` is None")
         rest = self.unknown if self.unknown is not None else given[unk]
         self.vocab = tuple(given.get(chr(k), rest) for k in range(128))
-        lo, hi = _TOKEN_DTYPES[name][2:]
-        for what, v in [(f"the id of {chr(k)!r}", self.vocab[k]) for k in range(128) if chr(k) in given] + \
-                       [("unknown", self.unknown), ("bos", self.bos), ("eos", self.eos), ("pad", self.pad)]:
-            if v is not None and not lo <= v <= hi:
-                raise ValueError(f"{what}, {v}, does not fit {name}")
+        self._check_fit([(f"the id of {chr(k)!r}", self.vocab[k]) for k in range(128) if chr(k) in given] +
+                        [("unknown", self.unknown), ("bos", self.bos), ("eos", self.eos), ("pad", self.pad)])
         self.specials = (self.bos is not None) + (self.eos is not None)
         if max_length is not None:
             max_length = _token_id(max_length, "max_length")
@@ -1231,47 +1263,36 @@ class ProteinTokens:
                 raise ValueError(f"max_length = {max_length} leaves no room for a residue beside {self.specials} special tokens")
         self.max_length = max_length
 
-    elem_bytes = property(lambda self: _TOKEN_DTYPES[self.dtype][0])
-    typestr = property(lambda self: _TOKEN_DTYPES[self.dtype][1])
+    row, unit, per_contig = "gene", "tokens", "tables"
+
+    def write(self, L, ctx_h, batch_h, device, genes, tables, out=None, stream=None):
+        return tokens_into(L, ctx_h, batch_h, device, len(tables), genes, tables, self, out, stream)
 
     def _key(self):
         return (self.vocab, self.unknown, self.bos, self.eos, self.pad, self.dtype, self.layout, self.max_length, self.include_stop,
                 self.strict, self.unknown_residue)
 
-    def __eq__(self, other):
-        return isinstance(other, ProteinTokens) and self._key() == other._key()
-
-    def __hash__(self):
-        return hash(self._key())
+    def __reduce__(self):
+        return _protein_tokens_from_key, (self._key(),)
 
     def __repr__(self):
         return "pyrodigal_amd.ProteinTokens(dtype=%r, layout=%r, bos=%r, eos=%r, max_length=%r)" % (
             self.dtype, self.layout, self.bos, self.eos, self.max_length)
 
-    def __reduce__(self):
-        return _protein_tokens_from_key, (self._key(),)
-
     def lengths(self, genes):
         """Tokens of every gene record, specials included (int64): host arithmetic on the coordinates, as the library does it."""
-        stop_edge = np.where(genes["strand"] == 1, genes["partial_end"], genes["partial_begin"]).astype(bool)
-        r = (genes["end"].astype(np.int64) - genes["begin"] + 1) // 3
-        if not self.include_stop:
-            r = r - (~stop_edge)
-        r = np.maximum(r, 0)
+        r = _residue_counts(genes, self.include_stop)
         if self.max_length is not None:
             r = np.minimum(r, self.max_length - self.specials)
         return (r + self.specials).astype(np.int64)
 
     def opts(self, row_width=0, row_stride=0):
-        o = TokenOpts()
-        o.elem_bytes, o.layout = self.elem_bytes, TOKENS_PADDED if self.layout == "padded" else TOKENS_RAGGED
-        o.row_width, o.row_stride = int(row_width), int(row_stride)
+        o = self._opts(TokenOpts(), row_width, row_stride)
         o.include_stop, o.strict, o.unknown_residue = int(self.include_stop), int(self.strict), ord(self.unknown_residue)
         o.max_length = 0 if self.max_length is None else self.max_length
         o.vocab[:] = self.vocab
         o.bos = TOKEN_NONE if self.bos is None else self.bos
         o.eos = TOKEN_NONE if self.eos is None else self.eos
-        o.pad = self.pad
         return o
 
 
@@ -1373,6 +1394,23 @@ def _device_output(spec, out, stream, device, lens, total, row, unit):
     return out, stream, cai, width, stride, n_out
 
 
+def _rows_into(L, ctx_h, call, args, spec, lens, device, out, stream):
+    """What ``tokens_into`` and ``labels_into`` share: ``out`` checked against the rows' ``lens`` under ``spec``, and the raw ``call``
+    with ``args`` in front of the options.  Returns (out, offsets or None, the lengths the library reports)."""
+    n = len(lens)
+    off = np.zeros(n + 1, np.int64)
+    np.cumsum(lens, out=off[1:])
+    out, stream, cai, width, stride, n_out = _device_output(spec, out, stream, device, lens, int(off[-1]), spec.row, spec.unit)
+    ptr = cai["data"][0]
+    len_out = np.zeros(max(n, 1), np.int64)
+    o = spec.opts(width, stride)
+    rc = getattr(L, call)(ctx_h, *args, ctypes.byref(o), ctypes.c_void_p(int(ptr) if ptr else 0), n_out,
+                          ctypes.c_void_p(DeviceSequences._stream_of(out, stream)), ctypes.c_void_p(len_out.ctypes.data))
+    if rc != PGA_OK:
+        _raise(L, ctx_h, rc, call)
+    return out, None if spec.layout == "padded" else off, len_out[:n]
+
+
 def tokens_into(L, ctx_h, batch_h, device, n_contigs, genes, tables, spec, out=None, stream=None):
     """``pga_translate_genes_tokens`` on raw handles (what ``Context.translate_tokens`` and the finder's device call share): the token
     ids of ``genes`` (GENE_DTYPE records of the resident batch) under ``tables`` into ``out``, or into a new torch tensor."""
@@ -1382,25 +1420,14 @@ def tokens_into(L, ctx_h, batch_h, device, n_contigs, genes, tables, spec, out=N
     tables = np.ascontiguousarray(tables, np.int32)
     if tables.shape != (n_contigs,):
         raise ValueError(f"tables has {tables.size} entries for {n_contigs} contigs")
-    n = len(genes)
-    lens = spec.lengths(genes)
-    off = np.zeros(n + 1, np.int64)
-    np.cumsum(lens, out=off[1:])
-    padded = spec.layout == "padded"
-    out, stream, cai, width, stride, n_out = _device_output(spec, out, stream, device, lens, int(off[-1]), "gene", "tokens")
-    ptr = cai["data"][0]
-    len_out = np.zeros(max(n, 1), np.int64)
-    o = spec.opts(width, stride)
-    rc = L.pga_translate_genes_tokens(ctx_h, batch_h, n, ctypes.c_void_p(genes.ctypes.data), ctypes.c_void_p(tables.ctypes.data),
-                                      ctypes.byref(o), ctypes.c_void_p(int(ptr) if ptr else 0), n_out,
-                                      ctypes.c_void_p(DeviceSequences._stream_of(out, stream)), ctypes.c_void_p(len_out.ctypes.data))
-    if rc != PGA_OK:
-        _raise(L, ctx_h, rc, "pga_translate_genes_tokens")
-    assert np.array_equal(len_out[:n], lens)
+    n, lens = len(genes), spec.lengths(genes)
+    args = (batch_h, n, ctypes.c_void_p(genes.ctypes.data), ctypes.c_void_p(tables.ctypes.data))
+    out, off, len_out = _rows_into(L, ctx_h, "pga_translate_genes_tokens", args, spec, lens, device, out, stream)
+    assert np.array_equal(len_out, lens)
     gene_begin = None
     if n == 0 or np.all(np.diff(genes["contig"]) >= 0):
         gene_begin = np.searchsorted(genes["contig"], np.arange(n_contigs + 1)).astype(np.int64)
-    return DeviceProteins(out, lens, None if padded else off, gene_begin, device)
+    return DeviceProteins(out, lens, off, gene_begin, device)
 
 
 def _translate_tokens(self, batch, result_or_genes, spec, out=None, tables=None, stream=None):
@@ -1415,8 +1442,7 @@ def _translate_tokens(self, batch, result_or_genes, spec, out=None, tables=None,
         contigs = getattr(result_or_genes, "contigs", None)
         if contigs is None:
             raise ValueError("bare gene records carry no models: pass tables=, the translation table of every contig")
-        tts = [int(np.frombuffer(m[8:12].tobytes(), np.int32)[0]) for m in self._models]
-        tables = [tts[c["model"]] if c["model"] >= 0 else 11 for c in contigs]
+        tables = _default_tables(self, contigs)
     return tokens_into(self.L, self.h, batch.h, self.device, batch.n, genes, tables, spec, out, stream)
 
 
@@ -1442,7 +1468,7 @@ def label_class_map(preset):
     return tuple(ids)
 
 
-class BaseLabels:
+class BaseLabels(_TensorRule):
     """How ``label_bases`` / ``find_labels_batch`` write the annotation of every base into a device tensor (``pga_label_opts``; the
     rule is in ``pyrodigal_amd.h``).
 
@@ -1454,11 +1480,7 @@ class BaseLabels:
     id must fit it.  Everything that needs no device is checked here.  Hashable and picklable."""
 
     def __init__(self, classes="frame", *, pad=None, dtype="int64", layout="padded"):
-        name = dtype if isinstance(dtype, str) else np.dtype(dtype).name
-        if name not in _TOKEN_DTYPES:
-            raise ValueError(f"dtype must be uint8, int32 or int64, not {name!r}")
-        if layout not in ("padded", "ragged"):
-            raise ValueError(f"layout must be \"padded\" or \"ragged\", not {layout!r}")
+        self._set_format(dtype, layout)
         if isinstance(classes, str):
             self.class_map = label_class_map(classes)
         else:
@@ -1467,42 +1489,31 @@ class BaseLabels:
                 raise ValueError(f"classes has {len(ids)} ids: there is one for each of the 256 raw bytes")
             self.class_map = tuple(_token_id(v, f"the id of raw byte {k:#04x}") for k, v in enumerate(ids))
         self.classes = classes if isinstance(classes, str) else None
-        lo, hi = _TOKEN_DTYPES[name][2:]
         if pad is None:
-            if layout == "padded" and name == "uint8":
+            if layout == "padded" and self.dtype == "uint8":
                 raise ValueError("the padded layout of uint8 labels needs `pad`: the default, -100, does not fit")
-            pad = -100 if name != "uint8" else 0
+            pad = -100 if self.dtype != "uint8" else 0
         self.pad = _token_id(pad, "pad")
-        for what, v in [(f"the id of raw byte {k:#04x}", v) for k, v in enumerate(self.class_map)] + [("pad", self.pad)]:
-            if not lo <= v <= hi:
-                raise ValueError(f"{what}, {v}, does not fit {name}")
-        self.dtype, self.layout = name, layout
+        self._check_fit([(f"the id of raw byte {k:#04x}", v) for k, v in enumerate(self.class_map)] + [("pad", self.pad)])
 
-    elem_bytes = property(lambda self: _TOKEN_DTYPES[self.dtype][0])
-    typestr = property(lambda self: _TOKEN_DTYPES[self.dtype][1])
+    row, unit, per_contig = "contig", "bases", "lengths"
+
+    def write(self, L, ctx_h, batch_h, device, genes, lengths, out=None, stream=None):
+        return labels_into(L, ctx_h, batch_h, device, lengths, genes, self, out, stream)
 
     def _key(self):
         return (self.class_map, self.classes, self.pad, self.dtype, self.layout)
 
-    def __eq__(self, other):
-        return isinstance(other, BaseLabels) and self._key() == other._key()
-
-    def __hash__(self):
-        return hash(self._key())
+    def __reduce__(self):
+        return _base_labels_from_key, (self._key(),)
 
     def __repr__(self):
         return "pyrodigal_amd.BaseLabels(%s, pad=%r, dtype=%r, layout=%r)" % (
             repr(self.classes) if self.classes is not None else "<256 ids>", self.pad, self.dtype, self.layout)
 
-    def __reduce__(self):
-        return _base_labels_from_key, (self._key(),)
-
     def opts(self, row_width=0, row_stride=0):
-        o = LabelOpts()
-        o.elem_bytes, o.layout = self.elem_bytes, TOKENS_PADDED if self.layout == "padded" else TOKENS_RAGGED
-        o.row_width, o.row_stride = int(row_width), int(row_stride)
+        o = self._opts(LabelOpts(), row_width, row_stride)
         o.class_map[:] = self.class_map
-        o.pad = self.pad
         return o
 
 
@@ -1551,24 +1562,12 @@ def labels_into(L, ctx_h, batch_h, device, lengths, genes, spec, out=None, strea
     torch tensor."""
     if not isinstance(spec, BaseLabels):
         raise TypeError("the label rule must be a BaseLabels, not %r" % type(spec).__name__)
-    genes = np.ascontiguousarray(genes, dtype=GENE_DTYPE)
-    lens = np.ascontiguousarray(lengths, np.int64)
-    n = len(lens)
-    off = np.zeros(n + 1, np.int64)
-    np.cumsum(lens, out=off[1:])
-    padded = spec.layout == "padded"
-    out, stream, cai, width, stride, n_out = _device_output(spec, out, stream, device, lens, int(off[-1]), "contig", "bases")
-    ptr = cai["data"][0]
-    len_out = np.zeros(max(n, 1), np.int64)
-    o = spec.opts(width, stride)
-    rc = L.pga_label_bases(ctx_h, batch_h, len(genes), ctypes.c_void_p(genes.ctypes.data), ctypes.byref(o),
-                           ctypes.c_void_p(int(ptr) if ptr else 0), n_out, ctypes.c_void_p(DeviceSequences._stream_of(out, stream)),
-                           ctypes.c_void_p(len_out.ctypes.data))
-    if rc != PGA_OK:
-        _raise(L, ctx_h, rc, "pga_label_bases")
-    if not np.array_equal(len_out[:n], lens):
+    genes, lens = np.ascontiguousarray(genes, dtype=GENE_DTYPE), np.ascontiguousarray(lengths, np.int64)
+    args = (batch_h, len(genes), ctypes.c_void_p(genes.ctypes.data))
+    out, off, len_out = _rows_into(L, ctx_h, "pga_label_bases", args, spec, lens, device, out, stream)
+    if not np.array_equal(len_out, lens):
         raise ValueError("`lengths` are not those of the batch")
-    return DeviceLabels(out, lens, None if padded else off, device)
+    return DeviceLabels(out, lens, off, device)
 
 
 def _label_bases(self, batch, result_or_genes, spec, out=None, stream=None):

@@ -121,6 +121,17 @@ k_pack_device(const void* __restrict__ src, const ContigDesc* __restrict__ dct, 
 // (n + 1), the source offsets (n) and the alphabet padded to 256 bytes
 static size_t pack_tables_bytes(int n) { return sizeof(ContigDesc) * ((size_t)n + 1) + sizeof(int64_t) * (size_t)n + 256 + 256; }
 
+int pga_device_memory_(pga_ctx* c, const void* p, const char* fn, const char* name) {
+    hipPointerAttribute_t at{};
+    const hipError_t pe = p ? hipPointerGetAttributes(&at, p) : hipErrorInvalidValue;
+    if (pe != hipSuccess) (void)hipGetLastError();
+    if (pe == hipSuccess && at.type == hipMemoryTypeDevice && at.device == c->device) return PGA_OK;
+    c->err = std::string(fn) + ": " + name + " is not device memory";
+    if (pe != hipSuccess || at.type != hipMemoryTypeDevice) c->err += " (a host pointer?)";
+    else c->err += " of the context's device " + std::to_string(c->device) + " but of device " + std::to_string(at.device);
+    return PGA_EINVAL;
+}
+
 extern "C" int pga_batch_create_device(pga_ctx* c, int32_t n_contigs, const void* d_data, int64_t n_elems, int32_t elem_bytes,
                                        const int64_t* elem_off, const int64_t* lens, const uint8_t* alphabet, int32_t n_alphabet,
                                        void* producer_stream, pga_batch** out) {
@@ -156,17 +167,7 @@ extern "C" int pga_batch_create_device(pga_ctx* c, int32_t n_contigs, const void
         if (total >= 0x7fffffffLL) { c->err = "pga_batch_create_device: batch larger than 2^31 bases; split it"; return PGA_EINVAL; }
     }
     HT(c, hipSetDevice(c->device));
-    if (total > 0) {
-        // the pointer is asked about, never dereferenced on the host, and never handed to a kernel unless the runtime calls it device memory
-        hipPointerAttribute_t at{};
-        const hipError_t pe = d_data ? hipPointerGetAttributes(&at, d_data) : hipErrorInvalidValue;
-        if (pe != hipSuccess) (void)hipGetLastError();
-        if (pe != hipSuccess || at.type != hipMemoryTypeDevice) { c->err = "pga_batch_create_device: d_data is not device memory (a host pointer?)"; return PGA_EINVAL; }
-        if (at.device != c->device) {
-            c->err = "pga_batch_create_device: d_data is not device memory of the context's device " + std::to_string(c->device) + " but of device " + std::to_string(at.device);
-            return PGA_EINVAL;
-        }
-    }
+    if (total > 0) { const int rc = pga_device_memory_(c, d_data, "pga_batch_create_device", "d_data"); if (rc) return rc; }
     if (!c->finder) { int rc = pga_finder_models_changed(c); if (rc) return rc; }
     pga_batch* b = new (std::nothrow) pga_batch();
     if (!b) return PGA_ENOMEM;

@@ -1,8 +1,6 @@
 // The annotation of every base left on the device as a tensor in the shape of the input (pga_label_bases; the rule is in
-// pyrodigal_amd.h).  Included by translate.hip, inside its anonymous namespace, next to translate_tokens.inl, whose
-// element types (TokElem) it shares.  The letters of the batch are not read.
-
-constexpr int kLabThreads = 256;
+// pyrodigal_amd.h).  Included by translate.hip, inside its anonymous namespace, behind device_rows.inl.  The letters
+// of the batch are not read.
 
 // One stretch of one gene record in contig coordinates, built on the host: the record covers positions [lo, hi) of its contig, and
 // position p is base d = p - base of the gene, counted from `begin` (d = q - b of the rule; base = b - 1, or b - 1 - L for the stretch
@@ -43,18 +41,12 @@ static void lab_stretches(const pga_gene* genes, const int64_t n_genes, const Co
     }
 }
 
-// everything the kernel is told, by value.  Element e of the layout lies at out0 + (lead + e) * elem_bytes, as in TokArgs
+// everything the kernel is told, by value
 struct LabArgs {
-    const int64_t* off;        // [n_contigs + 1] exclusive scan of L_i (both layouts: L_i = off[i + 1] - off[i])
     const int64_t* iv_off;     // [n_contigs + 1] the stretches of contig i are iv[iv_off[i] .. iv_off[i + 1])
     const int64_t* cmap;       // [256]
     const LabIv* iv;
-    int64_t n_contigs;
-    int64_t n_elems;           // elements of the layout: off[B], or (B - 1) S + W
-    int64_t W, S;              // padded layout
-    int64_t pad;
-    int32_t lead, _pad;
-    char* out0;
+    RowArgs rows;              // one row per contig (behind the tables: `off` then comes with them in the kernel's first argument load)
 };
 
 // The raw bytes of positions k .. k + N - 1 of a contig whose stretches are iv[ib .. ie), packed four to a word (position k + j is
@@ -93,57 +85,58 @@ __device__ __forceinline__ void lab_raw(const LabIv* __restrict__ iv, const int6
 // reach into a row's W .. S, are partial (the first and the last of the tensor) or cross empty contigs go element by element.
 // Nothing but the elements the rule names is written.
 template <int EB, bool PADDED>
-__global__ void __launch_bounds__(kLabThreads)
+__global__ void __launch_bounds__(kRowThreads)
 k_label_bases(const LabArgs a) {
     static_assert(EB == 1 || EB == 4 || EB == 8, "element width");
     using T = typename TokElem<EB>::type;
     constexpr int PER = 16 / EB;
     __shared__ T s_map[256];
-    s_map[threadIdx.x] = (T)a.cmap[threadIdx.x];               // (kLabThreads == 256)
+    s_map[threadIdx.x] = (T)a.cmap[threadIdx.x];               // (kRowThreads == 256)
     __syncthreads();
+    const RowArgs& r = a.rows;
     const int64_t piece = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const int64_t e0 = piece * PER - a.lead;                   // the piece's first element: below 0 only in piece 0
-    if (e0 >= a.n_elems) return;
-    const int64_t lo = e0 < 0 ? 0 : e0, hi = e0 + PER < a.n_elems ? e0 + PER : a.n_elems;
-    T* __restrict__ out = reinterpret_cast<T*>(a.out0) + a.lead;      // d_out: element e is out[e]
+    const int64_t e0 = piece * PER - r.lead;                   // the piece's first element: below 0 only in piece 0
+    if (e0 >= r.n_elems) return;
+    const int64_t lo = e0 < 0 ? 0 : e0, hi = e0 + PER < r.n_elems ? e0 + PER : r.n_elems;
+    T* __restrict__ out = reinterpret_cast<T*>(r.out0) + r.lead;      // d_out: element e is out[e]
     int64_t g, k;                                              // element lo is position k of contig g (or of its row)
     if (PADDED) {
-        g = lo / a.S; k = lo - g * a.S;
+        g = lo / r.S; k = lo - g * r.S;
     } else {
         // the last contig that begins at or before lo: it is not empty, since the next one begins beyond lo (or lo < off[B])
-        int64_t l = 0, h = a.n_contigs - 1;
-        while (l < h) { const int64_t mid = (l + h + 1) >> 1; if (a.off[mid] <= lo) l = mid; else h = mid - 1; }
-        g = l; k = lo - a.off[g];
+        int64_t l = 0, h = r.n_rows - 1;
+        while (l < h) { const int64_t mid = (l + h + 1) >> 1; if (r.off[mid] <= lo) l = mid; else h = mid - 1; }
+        g = l; k = lo - r.off[g];
     }
-    int64_t len = a.off[g + 1] - a.off[g];
+    int64_t len = r.off[g + 1] - r.off[g];
     // the whole piece lies in one contig (ragged) or in the first W elements of one row (padded): hi == e0 + PER follows
-    if (e0 >= 0 && k + PER <= (PADDED ? a.W : len)) {
-        uint32_t r[(PER + 3) / 4] = {};
-        if (k < len) lab_raw<PER>(a.iv, a.iv_off[g], a.iv_off[g + 1], (int32_t)k, r);
+    if (e0 >= 0 && k + PER <= (PADDED ? r.W : len)) {
+        uint32_t raw[(PER + 3) / 4] = {};
+        if (k < len) lab_raw<PER>(a.iv, a.iv_off[g], a.iv_off[g + 1], (int32_t)k, raw);
         uint32_t w[4] = {0u, 0u, 0u, 0u};
 #pragma unroll
         for (int j = 0; j < PER; j++) {
-            T v = (T)a.pad;
-            if (!PADDED || k + j < len) v = s_map[(r[j >> 2] >> (8 * (j & 3))) & 255u];
+            T v = (T)r.pad;
+            if (!PADDED || k + j < len) v = s_map[(raw[j >> 2] >> (8 * (j & 3))) & 255u];
             if (EB == 1) w[j >> 2] |= (uint32_t)(uint8_t)v << (8 * (j & 3));
             else if (EB == 4) w[j] = (uint32_t)v;
             else { w[2 * j] = (uint32_t)(uint64_t)v; w[2 * j + 1] = (uint32_t)((uint64_t)v >> 32); }
         }
-        *reinterpret_cast<uint4*>(a.out0 + piece * 16) = make_uint4(w[0], w[1], w[2], w[3]);
+        *reinterpret_cast<uint4*>(r.out0 + piece * 16) = make_uint4(w[0], w[1], w[2], w[3]);
         return;
     }
     for (int64_t e = lo; e < hi; e++, k++) {
         if (PADDED) {
-            if (k == a.S) { k = 0; g++; len = a.off[g + 1] - a.off[g]; }          // (e < n_elems: the row exists)
-            if (k >= a.W) continue;
+            if (k == r.S) { k = 0; g++; len = r.off[g + 1] - r.off[g]; }          // (e < n_elems: the row exists)
+            if (k >= r.W) continue;
         } else {
-            while (k == len) { g++; k = 0; len = a.off[g + 1] - a.off[g]; }        // (empty contigs are stepped over; e < off[B] ends it)
+            while (k == len) { g++; k = 0; len = r.off[g + 1] - r.off[g]; }        // (empty contigs are stepped over; e < off[B] ends it)
         }
-        T v = (T)a.pad;
+        T v = (T)r.pad;
         if (k < len) {
-            uint32_t r[1];
-            lab_raw<1>(a.iv, a.iv_off[g], a.iv_off[g + 1], (int32_t)k, r);
-            v = s_map[r[0] & 255u];
+            uint32_t raw[1];
+            lab_raw<1>(a.iv, a.iv_off[g], a.iv_off[g + 1], (int32_t)k, raw);
+            v = s_map[raw[0] & 255u];
         }
         out[e] = v;
     }

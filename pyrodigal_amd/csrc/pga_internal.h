@@ -239,3 +239,6 @@ void pga_finder_release(pga_ctx*);
 int  pga_finder_models_changed(pga_ctx*);
 void pga_fill_model_const(ModelConst* mc, double st_wt);
 int  pga_hip_try_(pga_ctx* c, hipError_t e, const char* what);
+// PGA_OK when the runtime calls `p` device memory of the context's device, else PGA_EINVAL with "<fn>: <name> is not device memory ..."
+// in c->err.  The pointer is asked about, never dereferenced on the host, and never handed to a kernel unless this passes
+int  pga_device_memory_(pga_ctx* c, const void* p, const char* fn, const char* name);

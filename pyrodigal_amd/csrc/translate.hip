@@ -8,6 +8,8 @@
 #include <string.h>
 
 #include <algorithm>
+#include <string>
+#include <type_traits>
 #include <vector>
 
 struct pga_batch_view { pga_ctx* ctx; int32_t n; int64_t total; const ContigDesc* ct; const char* d_seq; const uint8_t* circular /* or nullptr: all linear */; };
@@ -71,6 +73,20 @@ int tables_ready(pga_ctx* c) {
     return PGA_OK;
 }
 
+// a record lies inside its contig; on a contig flagged circular it may run across the origin, over less than the whole circle
+bool gene_inside(const pga_batch_view& bv, const pga_gene& G) {
+    if (G.contig < 0 || G.contig >= bv.n || G.begin < 1 || G.end < G.begin) return false;
+    const int64_t len = bv.ct[G.contig].len;
+    return bv.circular && bv.circular[G.contig] ? G.begin <= len && (int64_t)G.end - G.begin < len : G.end <= len;
+}
+// the residues of a record (ref: lib.pyx:3006-3018): the final stop codon counts only with include_stop, and not at a partial end
+int64_t gene_residues(const pga_gene& G, const int include_stop) {
+    const bool stop_edge = G.strand == 1 ? G.partial_end : G.partial_begin;
+    const int64_t r = ((int64_t)G.end - G.begin + 1) / 3 - ((!stop_edge && !include_stop) ? 1 : 0);
+    return r > 0 ? r : 0;
+}
+
+#include "device_rows.inl"
 #include "translate_tokens.inl"
 #include "label_bases.inl"
 
@@ -85,26 +101,16 @@ extern "C" int pga_translate_genes(pga_ctx* c, const pga_batch* batch, int64_t n
     if (unknown_residue <= 0 || unknown_residue > 127) { c->err = "pga_translate_genes: `unknown_residue` must be a single ASCII character"; return PGA_EINVAL; }
     for (int i = 0; i < bv.n; i++)
         if (!table_known(table_of_contig[i])) { c->err = "pga_translate_genes: not a valid translation table index"; return PGA_EINVAL; }
-    // the caller's layout must be the one the kernel writes (ref: lib.pyx:3006-3018 for the lengths)
+    // the caller's layout must be the one the kernel writes
     if (offsets[0] != 0) { c->err = "pga_translate_genes: offsets[0] must be 0"; return PGA_EINVAL; }
     for (int64_t g = 0; g < n_genes; g++) {
-        const pga_gene& G = genes[g];
-        const bool circ = bv.circular && G.contig >= 0 && G.contig < bv.n && bv.circular[G.contig];
-        const bool inside = G.contig >= 0 && G.contig < bv.n &&
-                            (circ ? G.begin <= bv.ct[G.contig].len && (int64_t)G.end - G.begin < bv.ct[G.contig].len : G.end <= bv.ct[G.contig].len);
-        if (!inside || G.begin < 1 || G.end < G.begin) { c->err = "pga_translate_genes: gene outside its contig"; return PGA_EINVAL; }
-        const bool stop_edge = G.strand == 1 ? G.partial_end : G.partial_begin;
-        const int64_t want = (G.end - G.begin + 1) / 3 - ((!stop_edge && !include_stop) ? 1 : 0);
-        if (offsets[g + 1] - offsets[g] != (want > 0 ? want : 0)) { c->err = "pga_translate_genes: offsets do not match the gene lengths"; return PGA_EINVAL; }
+        if (!gene_inside(bv, genes[g])) { c->err = "pga_translate_genes: gene outside its contig"; return PGA_EINVAL; }
+        if (offsets[g + 1] - offsets[g] != gene_residues(genes[g], include_stop)) { c->err = "pga_translate_genes: offsets do not match the gene lengths"; return PGA_EINVAL; }
     }
     const int64_t total = offsets[n_genes];
     if (total == 0) return PGA_OK;
     if (hipSetDevice(c->device) != hipSuccess) return PGA_EDEVICE;
-    {
-        std::lock_guard<std::mutex> lk(g_tables_mu);
-        const int dev = c->device & 63;
-        if (!g_tables_ready[dev]) { const int rc = upload_tables(); if (rc) return rc; g_tables_ready[dev] = true; }
-    }
+    { const int rc = tables_ready(c); if (rc) return rc; }
     pga_gene* d_genes = nullptr; int32_t* d_tt = nullptr; int64_t* d_off = nullptr; char* d_out = nullptr; ContigDesc* d_ct = nullptr;
     auto cleanup = [&]() { hipFree(d_genes); hipFree(d_tt); hipFree(d_off); hipFree(d_out); hipFree(d_ct); };
     hipStream_t st = c->stream;
@@ -131,66 +137,34 @@ extern "C" int pga_translate_genes(pga_ctx* c, const pga_batch* batch, int64_t n
 extern "C" int pga_translate_genes_tokens(pga_ctx* c, const pga_batch* batch, int64_t n_genes, const pga_gene* genes, const int32_t* table_of_contig,
                                           const pga_token_opts* o, void* d_out, int64_t n_out_elems, void* stream, int64_t* len_out) {
     if (!c) return PGA_EINVAL;
-    auto bad = [&](std::string msg) { c->err = "pga_translate_genes_tokens: " + msg; return PGA_EINVAL; };
-    if (!batch || !o || n_genes < 0 || n_out_elems < 0 || (n_genes > 0 && (!genes || !table_of_contig || !len_out))) return bad("bad arguments");
+    RowDest d{c, "pga_translate_genes_tokens"};
+    if (!batch || !o || n_genes < 0 || n_out_elems < 0 || (n_genes > 0 && (!genes || !table_of_contig || !len_out))) return d.bad("bad arguments");
     const pga_batch_view bv = pga_batch_peek(batch);
-    if (bv.ctx != c) return bad("the batch belongs to another context");
+    if (bv.ctx != c) return d.bad("the batch belongs to another context");
     // ---- validation: all of it on the host, before anything is allocated or launched ----
-    const int eb = o->elem_bytes;
-    if (eb != 1 && eb != 4 && eb != 8) return bad("elem_bytes must be 1, 4 or 8, not " + std::to_string(eb));
-    if (o->layout != PGA_TOKENS_RAGGED && o->layout != PGA_TOKENS_PADDED) return bad("layout must be PGA_TOKENS_RAGGED or PGA_TOKENS_PADDED, not " + std::to_string(o->layout));
-    const bool padded = o->layout == PGA_TOKENS_PADDED;
-    if (o->unknown_residue <= 0 || o->unknown_residue > 127) return bad("`unknown_residue` must be a single ASCII character");
+    if (const int rc = d.format(o->elem_bytes, o->layout)) return rc;
+    if (o->unknown_residue <= 0 || o->unknown_residue > 127) return d.bad("`unknown_residue` must be a single ASCII character");
     const bool has_bos = o->bos != PGA_TOKEN_NONE, has_eos = o->eos != PGA_TOKEN_NONE;
     const int64_t s = (has_bos ? 1 : 0) + (has_eos ? 1 : 0);
-    auto fits = [&](const int64_t v) { return eb == 8 || (eb == 4 ? v >= INT32_MIN && v <= INT32_MAX : v >= 0 && v <= 255); };
-    const char* const elem_name = eb == 1 ? "uint8" : eb == 4 ? "int32" : "int64";
-    for (int k = 0; k < 128; k++)
-        if (!fits(o->vocab[k])) return bad("vocab[" + std::to_string(k) + "] = " + std::to_string(o->vocab[k]) + " does not fit " + elem_name);
-    if (has_bos && !fits(o->bos)) return bad("bos = " + std::to_string(o->bos) + " does not fit " + elem_name);
-    if (has_eos && !fits(o->eos)) return bad("eos = " + std::to_string(o->eos) + " does not fit " + elem_name);
-    if (padded && !fits(o->pad)) return bad("pad = " + std::to_string(o->pad) + " does not fit " + elem_name);
+    if (const int rc = d.fits("vocab", o->vocab, 128)) return rc;
+    if (has_bos) if (const int rc = d.fits("bos", o->bos)) return rc;
+    if (has_eos) if (const int rc = d.fits("eos", o->eos)) return rc;
+    if (d.padded) if (const int rc = d.fits("pad", o->pad)) return rc;
     if (o->max_length < 0 || (o->max_length != 0 && o->max_length < s + 1))
-        return bad("max_length = " + std::to_string(o->max_length) + " leaves no room for a residue beside " + std::to_string(s) + " special tokens (0: no limit)");
+        return d.bad("max_length = " + std::to_string(o->max_length) + " leaves no room for a residue beside " + std::to_string(s) + " special tokens (0: no limit)");
     for (int i = 0; i < (n_genes > 0 ? bv.n : 0); i++)
-        if (!table_known(table_of_contig[i])) return bad("contig " + std::to_string(i) + ": " + std::to_string(table_of_contig[i]) + " is not a valid translation table index");
+        if (!table_known(table_of_contig[i])) return d.bad("contig " + std::to_string(i) + ": " + std::to_string(table_of_contig[i]) + " is not a valid translation table index");
     std::vector<int64_t> off((size_t)n_genes + 1, 0);
-    int64_t longest = 0, longest_g = -1;
     for (int64_t g = 0; g < n_genes; g++) {
-        const pga_gene& G = genes[g];
-        const bool circ = bv.circular && G.contig >= 0 && G.contig < bv.n && bv.circular[G.contig];
-        const bool inside = G.contig >= 0 && G.contig < bv.n &&
-                            (circ ? G.begin <= bv.ct[G.contig].len && (int64_t)G.end - G.begin < bv.ct[G.contig].len : G.end <= bv.ct[G.contig].len);
-        if (!inside || G.begin < 1 || G.end < G.begin) return bad("gene " + std::to_string(g) + " lies outside its contig");
-        const bool stop_edge = G.strand == 1 ? G.partial_end : G.partial_begin;
-        int64_t r = ((int64_t)G.end - G.begin + 1) / 3 - ((!stop_edge && !o->include_stop) ? 1 : 0);
-        if (r < 0) r = 0;
+        if (!gene_inside(bv, genes[g])) return d.bad("gene " + std::to_string(g) + " lies outside its contig");
+        int64_t r = gene_residues(genes[g], o->include_stop);
         if (o->max_length != 0 && r > o->max_length - s) r = o->max_length - s;
         off[(size_t)g + 1] = off[(size_t)g] + s + r;
-        if (s + r > longest) { longest = s + r; longest_g = g; }
     }
-    int64_t need = off[(size_t)n_genes];
-    if (padded) {
-        const int64_t W = o->row_width, S = o->row_stride;
-        if (W < longest) return bad("row_width = " + std::to_string(W) + " is less than the " + std::to_string(longest) + " tokens of gene " + std::to_string(longest_g));
-        if (W < 0 || S < W) return bad("row_stride = " + std::to_string(S) + " is less than row_width = " + std::to_string(W));
-        if (n_genes > 1 && S > (INT64_MAX / 8 - W) / (n_genes - 1)) return bad("row_stride = " + std::to_string(S) + " is too large");
-        need = n_genes > 0 ? (n_genes - 1) * S + W : 0;
-    }
-    if (n_out_elems < need) return bad("n_out_elems = " + std::to_string(n_out_elems) + " is less than the " + std::to_string(need) + " elements of the layout");
-    if (need > 0) {
-        if (!d_out) return bad("d_out is NULL");
-        if ((uintptr_t)d_out % (uintptr_t)eb) return bad("d_out is not aligned to its " + std::to_string(eb) + "-byte elements");
-        if (hipSetDevice(c->device) != hipSuccess) return PGA_EDEVICE;
-        // the pointer is asked about, never dereferenced on the host, and never handed to a kernel unless the runtime calls it device memory
-        hipPointerAttribute_t at{};
-        const hipError_t pe = hipPointerGetAttributes(&at, d_out);
-        if (pe != hipSuccess) (void)hipGetLastError();
-        if (pe != hipSuccess || at.type != hipMemoryTypeDevice) return bad("d_out is not device memory (a host pointer?)");
-        if (at.device != c->device) return bad("d_out is not device memory of the context's device " + std::to_string(c->device) + " but of device " + std::to_string(at.device));
-    }
+    if (const int rc = d.shape(off, "tokens of gene", o->row_width, o->row_stride, o->pad, n_out_elems)) return rc;
+    if (const int rc = d.memory(d_out)) return rc;
     for (int64_t g = 0; g < n_genes; g++) len_out[g] = off[(size_t)g + 1] - off[(size_t)g];
-    if (need == 0) return PGA_OK;
+    if (d.a.n_elems == 0) return PGA_OK;
     { const int rc = tables_ready(c); if (rc) return rc; }
     // ---- the kernel's tables: staged in the upload's pinned area as they will lie on the device, one copy ----
     const size_t G = (size_t)n_genes, n = (size_t)bv.n;
@@ -204,97 +178,52 @@ extern "C" int pga_translate_genes_tokens(pga_ctx* c, const pga_batch* batch, in
     memcpy(L.pin + off_b + voc_b + ct_b, genes, gen_b);
     memcpy(L.pin + off_b + voc_b + ct_b + gen_b, table_of_contig, tt_b);
     TokArgs a{};
+    a.rows = d.a; a.rows.off = (const int64_t*)L.dev;
     a.seq = bv.d_seq;
-    a.off = (const int64_t*)L.dev; a.vocab = (const int64_t*)(L.dev + off_b); a.ct = (const ContigDesc*)(L.dev + off_b + voc_b);
+    a.vocab = (const int64_t*)(L.dev + off_b); a.ct = (const ContigDesc*)(L.dev + off_b + voc_b);
     a.genes = (const pga_gene*)(L.dev + off_b + voc_b + ct_b); a.tt_of = (const int32_t*)(L.dev + off_b + voc_b + ct_b + gen_b);
-    a.n_genes = n_genes; a.n_elems = need; a.W = padded ? o->row_width : 0; a.S = padded ? o->row_stride : 0;
-    a.bos = has_bos ? o->bos : 0; a.eos = has_eos ? o->eos : 0; a.pad = padded ? o->pad : 0;
+    a.bos = has_bos ? o->bos : 0; a.eos = has_eos ? o->eos : 0;
     a.has_bos = has_bos; a.has_eos = has_eos; a.unk = o->unknown_residue; a.strict = o->strict;
-    a.out0 = (char*)((uintptr_t)d_out & ~(uintptr_t)15);
-    a.lead = (int32_t)(((uintptr_t)d_out - (uintptr_t)a.out0) / (uintptr_t)eb);
-    const int64_t per = 16 / eb, pieces = (a.lead + need + per - 1) / per;
-    const dim3 grid((unsigned)((pieces + kTokThreads - 1) / kTokThreads)), block(kTokThreads);
-    // the upload stream is non-blocking: it waits for what the caller's stream held when the call came
-    hipError_t e = hipEventRecord(L.ev, (hipStream_t)stream);
-    if (e == hipSuccess) e = hipStreamWaitEvent(L.st, L.ev, 0);
-    if (e == hipSuccess) e = hipMemcpyAsync(L.dev, L.pin, tab, hipMemcpyHostToDevice, L.st);
-    if (e == hipSuccess) {
-        if (padded) {
-            if (eb == 1) hipLaunchKernelGGL((k_translate_tokens<1, true>), grid, block, 0, L.st, a);
-            else if (eb == 4) hipLaunchKernelGGL((k_translate_tokens<4, true>), grid, block, 0, L.st, a);
-            else hipLaunchKernelGGL((k_translate_tokens<8, true>), grid, block, 0, L.st, a);
-        } else {
-            if (eb == 1) hipLaunchKernelGGL((k_translate_tokens<1, false>), grid, block, 0, L.st, a);
-            else if (eb == 4) hipLaunchKernelGGL((k_translate_tokens<4, false>), grid, block, 0, L.st, a);
-            else hipLaunchKernelGGL((k_translate_tokens<8, false>), grid, block, 0, L.st, a);
-        }
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipStreamSynchronize(L.st);         // on return the tensor is complete for any stream
-    pga_upload_lease_give(c);
-    return pga_hip_try_(c, e, "pga_translate_genes_tokens");
+    return d.run(L, tab, stream, [&](const dim3 grid, const dim3 block, hipStream_t st) {
+        with_elem_layout(d.eb, d.padded, [&](auto EB, auto PADDED) {
+            hipLaunchKernelGGL((k_translate_tokens<decltype(EB)::value, decltype(PADDED)::value>), grid, block, 0, st, a);
+        });
+    });
 }
 
 extern "C" int pga_label_bases(pga_ctx* c, const pga_batch* batch, int64_t n_genes, const pga_gene* genes, const pga_label_opts* o, void* d_out,
                                int64_t n_out_elems, void* stream, int64_t* len_out) {
     if (!c) return PGA_EINVAL;
-    auto bad = [&](std::string msg) { c->err = "pga_label_bases: " + msg; return PGA_EINVAL; };
-    if (!batch || !o || n_genes < 0 || n_out_elems < 0 || (n_genes > 0 && !genes)) return bad("bad arguments");
+    RowDest d{c, "pga_label_bases"};
+    if (!batch || !o || n_genes < 0 || n_out_elems < 0 || (n_genes > 0 && !genes)) return d.bad("bad arguments");
     const pga_batch_view bv = pga_batch_peek(batch);
-    if (bv.ctx != c) return bad("the batch belongs to another context");
-    if (bv.n > 0 && !len_out) return bad("bad arguments");
+    if (bv.ctx != c) return d.bad("the batch belongs to another context");
+    if (bv.n > 0 && !len_out) return d.bad("bad arguments");
     // ---- validation: all of it on the host, before anything is allocated or launched ----
-    const int eb = o->elem_bytes;
-    if (eb != 1 && eb != 4 && eb != 8) return bad("elem_bytes must be 1, 4 or 8, not " + std::to_string(eb));
-    if (o->layout != PGA_TOKENS_RAGGED && o->layout != PGA_TOKENS_PADDED) return bad("layout must be PGA_TOKENS_RAGGED or PGA_TOKENS_PADDED, not " + std::to_string(o->layout));
-    const bool padded = o->layout == PGA_TOKENS_PADDED;
-    auto fits = [&](const int64_t v) { return eb == 8 || (eb == 4 ? v >= INT32_MIN && v <= INT32_MAX : v >= 0 && v <= 255); };
-    const char* const elem_name = eb == 1 ? "uint8" : eb == 4 ? "int32" : "int64";
-    for (int k = 0; k < 256; k++)
-        if (!fits(o->class_map[k])) return bad("class_map[" + std::to_string(k) + "] = " + std::to_string(o->class_map[k]) + " does not fit " + elem_name);
-    if (padded && !fits(o->pad)) return bad("pad = " + std::to_string(o->pad) + " does not fit " + elem_name);
+    if (const int rc = d.format(o->elem_bytes, o->layout)) return rc;
+    if (const int rc = d.fits("class_map", o->class_map, 256)) return rc;
+    if (d.padded) if (const int rc = d.fits("pad", o->pad)) return rc;
     const size_t B = (size_t)bv.n;
     std::vector<int64_t> off(B + 1, 0), iv_off(B + 1, 0);
-    int64_t longest = 0, longest_i = -1;
     for (size_t i = 0; i < B; i++) {
-        const int64_t len = bv.ct[i].len;
-        if (len > INT32_MAX - 16) return bad("contig " + std::to_string(i) + " is too long");
-        off[i + 1] = off[i] + len;
-        if (len > longest) { longest = len; longest_i = (int64_t)i; }
+        if (bv.ct[i].len > INT32_MAX - 16) return d.bad("contig " + std::to_string(i) + " is too long");
+        off[i + 1] = off[i] + bv.ct[i].len;
     }
-    int64_t need = off[B];
-    if (padded) {
-        const int64_t W = o->row_width, S = o->row_stride;
-        if (W < longest) return bad("row_width = " + std::to_string(W) + " is less than the " + std::to_string(longest) + " bases of contig " + std::to_string(longest_i));
-        if (W < 0 || S < W) return bad("row_stride = " + std::to_string(S) + " is less than row_width = " + std::to_string(W));
-        if (B > 1 && S > (INT64_MAX / 8 - W) / (int64_t)(B - 1)) return bad("row_stride = " + std::to_string(S) + " is too large");
-        need = B > 0 ? (int64_t)(B - 1) * S + W : 0;
-    }
-    if (n_out_elems < need) return bad("n_out_elems = " + std::to_string(n_out_elems) + " is less than the " + std::to_string(need) + " elements of the layout");
+    if (const int rc = d.shape(off, "bases of contig", o->row_width, o->row_stride, o->pad, n_out_elems)) return rc;
     // every record inside its contig, in whole codons; a record across the origin makes two stretches
     for (int64_t g = 0; g < n_genes; g++) {
         const pga_gene& G = genes[g];
         const std::string who = "gene " + std::to_string(g);
-        if (G.contig < 0 || G.contig >= bv.n) return bad(who + " names contig " + std::to_string(G.contig) + " of " + std::to_string(bv.n));
+        if (G.contig < 0 || G.contig >= bv.n) return d.bad(who + " names contig " + std::to_string(G.contig) + " of " + std::to_string(bv.n));
         const int64_t len = bv.ct[G.contig].len, glen = (int64_t)G.end - G.begin + 1;
-        if (G.begin < 1 || G.begin > len || glen < 3 || glen > len) return bad(who + " lies outside its contig");
-        if (glen % 3) return bad(who + " is " + std::to_string(glen) + " bases long, no whole number of codons");
-        if (G.end > len && !(bv.circular && bv.circular[G.contig])) return bad(who + " ends beyond its contig, which is not flagged circular");
+        if (G.begin < 1 || G.begin > len || glen < 3 || glen > len) return d.bad(who + " lies outside its contig");
+        if (glen % 3) return d.bad(who + " is " + std::to_string(glen) + " bases long, no whole number of codons");
+        if (G.end > len && !(bv.circular && bv.circular[G.contig])) return d.bad(who + " ends beyond its contig, which is not flagged circular");
         iv_off[(size_t)G.contig + 1] += G.end > len ? 2 : 1;
     }
-    if (need > 0) {
-        if (!d_out) return bad("d_out is NULL");
-        if ((uintptr_t)d_out % (uintptr_t)eb) return bad("d_out is not aligned to its " + std::to_string(eb) + "-byte elements");
-        if (hipSetDevice(c->device) != hipSuccess) return PGA_EDEVICE;
-        // the pointer is asked about, never dereferenced on the host, and never handed to a kernel unless the runtime calls it device memory
-        hipPointerAttribute_t at{};
-        const hipError_t pe = hipPointerGetAttributes(&at, d_out);
-        if (pe != hipSuccess) (void)hipGetLastError();
-        if (pe != hipSuccess || at.type != hipMemoryTypeDevice) return bad("d_out is not device memory (a host pointer?)");
-        if (at.device != c->device) return bad("d_out is not device memory of the context's device " + std::to_string(c->device) + " but of device " + std::to_string(at.device));
-    }
+    if (const int rc = d.memory(d_out)) return rc;
     for (size_t i = 0; i < B; i++) len_out[i] = bv.ct[i].len;
-    if (need == 0) return PGA_OK;
+    if (d.a.n_elems == 0) return PGA_OK;
     // ---- the kernel's tables: staged in the upload's pinned area as they will lie on the device, one copy ----
     for (size_t i = 0; i < B; i++) iv_off[i + 1] += iv_off[i];
     const size_t n_iv = (size_t)iv_off[B];
@@ -307,30 +236,12 @@ extern "C" int pga_label_bases(pga_ctx* c, const pga_batch* batch, int64_t n_gen
     memcpy(L.pin + 2 * off_b, o->class_map, map_b);
     lab_stretches(genes, n_genes, bv.ct, iv_off.data(), B, (LabIv*)(L.pin + 2 * off_b + map_b));
     LabArgs a{};
-    a.off = (const int64_t*)L.dev; a.iv_off = (const int64_t*)(L.dev + off_b); a.cmap = (const int64_t*)(L.dev + 2 * off_b);
+    a.rows = d.a; a.rows.off = (const int64_t*)L.dev;
+    a.iv_off = (const int64_t*)(L.dev + off_b); a.cmap = (const int64_t*)(L.dev + 2 * off_b);
     a.iv = (const LabIv*)(L.dev + 2 * off_b + map_b);
-    a.n_contigs = bv.n; a.n_elems = need; a.W = padded ? o->row_width : 0; a.S = padded ? o->row_stride : 0; a.pad = padded ? o->pad : 0;
-    a.out0 = (char*)((uintptr_t)d_out & ~(uintptr_t)15);
-    a.lead = (int32_t)(((uintptr_t)d_out - (uintptr_t)a.out0) / (uintptr_t)eb);
-    const int64_t per = 16 / eb, pieces = (a.lead + need + per - 1) / per;
-    const dim3 grid((unsigned)((pieces + kLabThreads - 1) / kLabThreads)), block(kLabThreads);
-    // the upload stream is non-blocking: it waits for what the caller's stream held when the call came
-    hipError_t e = hipEventRecord(L.ev, (hipStream_t)stream);
-    if (e == hipSuccess) e = hipStreamWaitEvent(L.st, L.ev, 0);
-    if (e == hipSuccess) e = hipMemcpyAsync(L.dev, L.pin, tab, hipMemcpyHostToDevice, L.st);
-    if (e == hipSuccess) {
-        if (padded) {
-            if (eb == 1) hipLaunchKernelGGL((k_label_bases<1, true>), grid, block, 0, L.st, a);
-            else if (eb == 4) hipLaunchKernelGGL((k_label_bases<4, true>), grid, block, 0, L.st, a);
-            else hipLaunchKernelGGL((k_label_bases<8, true>), grid, block, 0, L.st, a);
-        } else {
-            if (eb == 1) hipLaunchKernelGGL((k_label_bases<1, false>), grid, block, 0, L.st, a);
-            else if (eb == 4) hipLaunchKernelGGL((k_label_bases<4, false>), grid, block, 0, L.st, a);
-            else hipLaunchKernelGGL((k_label_bases<8, false>), grid, block, 0, L.st, a);
-        }
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipStreamSynchronize(L.st);         // on return the tensor is complete for any stream
-    pga_upload_lease_give(c);
-    return pga_hip_try_(c, e, "pga_label_bases");
+    return d.run(L, tab, stream, [&](const dim3 grid, const dim3 block, hipStream_t st) {
+        with_elem_layout(d.eb, d.padded, [&](auto EB, auto PADDED) {
+            hipLaunchKernelGGL((k_label_bases<decltype(EB)::value, decltype(PADDED)::value>), grid, block, 0, st, a);
+        });
+    });
 }

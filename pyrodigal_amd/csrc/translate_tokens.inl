@@ -1,25 +1,14 @@
 // Proteins left on the device as token ids (pga_translate_genes_tokens; the rule is in pyrodigal_amd.h).
-// Included by translate.hip, inside its anonymous namespace: the __constant__ code tables and translate_rules.h are shared with k_translate.
+// Included by translate.hip, inside its anonymous namespace, behind device_rows.inl: the __constant__ code tables and translate_rules.h
+// are shared with k_translate.
 
-constexpr int kTokThreads = 256;
-
-template <int EB> struct TokElem;
-template <> struct TokElem<1> { using type = uint8_t; };
-template <> struct TokElem<4> { using type = int32_t; };
-template <> struct TokElem<8> { using type = int64_t; };
-
-// everything the kernel is told, by value.  Element e of the layout lies at out0 + (lead + e) * elem_bytes: out0 is the 16-byte
-// aligned address at or below d_out, lead the elements between the two (0 .. 16 / elem_bytes - 1)
+// everything the kernel is told, by value
 struct TokArgs {
+    RowArgs rows;              // one row per gene
     const char* seq; const ContigDesc* ct; const pga_gene* genes; const int32_t* tt_of;
-    const int64_t* off;        // [n_genes + 1] exclusive scan of len_g (both layouts: len_g = off[g + 1] - off[g])
     const int64_t* vocab;      // [128]
-    int64_t n_genes;
-    int64_t n_elems;           // elements of the layout: off[G], or (G - 1) S + W
-    int64_t W, S;              // padded layout
-    int64_t bos, eos, pad;
-    int32_t has_bos, has_eos, unk, strict, lead, _pad;
-    char* out0;
+    int64_t bos, eos;
+    int32_t has_bos, has_eos, unk, strict;
 };
 
 // what a thread keeps of the gene it is in
@@ -34,14 +23,14 @@ __device__ __forceinline__ TokGene tok_gene(const TokArgs& a, const int64_t g) {
     t.fwd = gp->strand == 1;
     // partial flags are in sequence orientation; the gene's own first codon follows its strand
     t.start_edge = t.fwd ? gp->partial_begin != 0 : gp->partial_end != 0;
-    t.len = a.off[g + 1] - a.off[g];
+    t.len = a.rows.off[g + 1] - a.rows.off[g];
     return t;
 }
 
-// token k of the gene (k >= 0): bos, the residues' ids, eos -- and pad from len_g on, which only the padded layout asks for
+// token k of the gene (k >= 0): bos, the residues' ids, eos -- and pad from len on, which only the padded layout asks for
 template <typename T>
 __device__ __forceinline__ T tok_at(const TokArgs& a, const TokGene& t, const T* s_vocab, const int64_t k) {
-    if (k >= t.len) return (T)a.pad;
+    if (k >= t.len) return (T)a.rows.pad;
     if (a.has_bos && k == 0) return (T)a.bos;
     if (a.has_eos && k == t.len - 1) return (T)a.eos;
     const int i = (int)k - a.has_bos;
@@ -65,8 +54,10 @@ __device__ __forceinline__ T tok_at(const TokArgs& a, const TokGene& t, const T*
 // once per workgroup in LDS, 128 entries of the element width: the indices diverge per lane) and leaves as one 16-byte store.
 // Pieces that span a seam between genes or rows, reach into a row's W .. S, or are partial (the first and the last of the tensor)
 // go element by element.  Nothing but the elements the rule names is written; of the batch, only the genes' own bases are read.
+// (k_label_bases walks pieces, rows and seams the same way, in its own words: written once over an element source, the walk made
+// the padded instances of this kernel slower, profiles/device_rows_kernel_stats.md.  A change to the seam logic belongs in both.)
 template <int EB, bool PADDED>
-__global__ void __launch_bounds__(kTokThreads)
+__global__ void __launch_bounds__(kRowThreads)
 k_translate_tokens(const TokArgs a) {
     static_assert(EB == 1 || EB == 4 || EB == 8, "element width");
     using T = typename TokElem<EB>::type;
@@ -74,22 +65,23 @@ k_translate_tokens(const TokArgs a) {
     __shared__ T s_vocab[128];
     if (threadIdx.x < 128) s_vocab[threadIdx.x] = (T)a.vocab[threadIdx.x];
     __syncthreads();
+    const RowArgs& r = a.rows;
     const int64_t piece = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const int64_t e0 = piece * PER - a.lead;                   // the piece's first element: below 0 only in piece 0
-    if (e0 >= a.n_elems) return;
-    const int64_t lo = e0 < 0 ? 0 : e0, hi = e0 + PER < a.n_elems ? e0 + PER : a.n_elems;
-    T* __restrict__ out = reinterpret_cast<T*>(a.out0) + a.lead;      // d_out: element e is out[e]
+    const int64_t e0 = piece * PER - r.lead;                   // the piece's first element: below 0 only in piece 0
+    if (e0 >= r.n_elems) return;
+    const int64_t lo = e0 < 0 ? 0 : e0, hi = e0 + PER < r.n_elems ? e0 + PER : r.n_elems;
+    T* __restrict__ out = reinterpret_cast<T*>(r.out0) + r.lead;      // d_out: element e is out[e]
     int64_t g, k;                                              // element lo is token k of gene g
     if (PADDED) {
-        g = lo / a.S; k = lo - g * a.S;
+        g = lo / r.S; k = lo - g * r.S;
     } else {
-        int64_t l = 0, h = a.n_genes - 1;
-        while (l < h) { const int64_t mid = (l + h + 1) >> 1; if (a.off[mid] <= lo) l = mid; else h = mid - 1; }
-        g = l; k = lo - a.off[g];
+        int64_t l = 0, h = r.n_rows - 1;
+        while (l < h) { const int64_t mid = (l + h + 1) >> 1; if (r.off[mid] <= lo) l = mid; else h = mid - 1; }
+        g = l; k = lo - r.off[g];
     }
     TokGene t = tok_gene(a, g);
     // the whole piece lies in one gene (ragged) or in the first W elements of one row (padded): hi == e0 + PER follows
-    if (e0 >= 0 && k + PER <= (PADDED ? a.W : t.len)) {
+    if (e0 >= 0 && k + PER <= (PADDED ? r.W : t.len)) {
         uint32_t w[4] = {0u, 0u, 0u, 0u};
 #pragma unroll
         for (int j = 0; j < PER; j++) {
@@ -98,15 +90,15 @@ k_translate_tokens(const TokArgs a) {
             else if (EB == 4) w[j] = (uint32_t)v;
             else { w[2 * j] = (uint32_t)(uint64_t)v; w[2 * j + 1] = (uint32_t)((uint64_t)v >> 32); }
         }
-        *reinterpret_cast<uint4*>(a.out0 + piece * 16) = make_uint4(w[0], w[1], w[2], w[3]);
+        *reinterpret_cast<uint4*>(r.out0 + piece * 16) = make_uint4(w[0], w[1], w[2], w[3]);
         return;
     }
     for (int64_t e = lo; e < hi; e++, k++) {
         if (PADDED) {
-            if (k == a.S) { k = 0; g++; t = tok_gene(a, g); }            // (e < n_elems: the row exists)
-            if (k < a.W) out[e] = tok_at<T>(a, t, s_vocab, k);
+            if (k == r.S) { k = 0; g++; t = tok_gene(a, g); }            // (e < n_elems: the row exists)
+            if (k < r.W) out[e] = tok_at<T>(a, t, s_vocab, k);
         } else {
-            if (k == t.len) { do g++; while (a.off[g + 1] == a.off[g]); k = 0; t = tok_gene(a, g); }   // (empty genes are stepped over; e < off[G] ends it)
+            if (k == t.len) { do g++; while (r.off[g + 1] == r.off[g]); k = 0; t = tok_gene(a, g); }   // (empty genes are stepped over; e < off[G] ends it)
             out[e] = tok_at<T>(a, t, s_vocab, k);
         }
     }

@@ -1651,7 +1651,7 @@ cdef pga_batch* _device_batch(pga_ctx* ctx, object dev) except? NULL:
 cdef int _one_call_for_tokens(object tokens, list calls) except -1:
     if tokens is not None and len(calls) > 1:
         raise ValueError("`training_infos` would split this request into %d device calls (more than `coalesce_bases` bases or four "
-                         "translation tables in a row): %s writes one tensor per request" % (len(calls), tokens.get("method", "find_proteins_batch")))
+                         "translation tables in a row): %s writes one tensor per request" % (len(calls), tokens["method"]))
     return 0
 
 
@@ -1663,9 +1663,9 @@ cdef class _FindRequest:
     cdef list circ              # one bool per sequence: called as a circle; None: all linear
     cdef object sets            # int32 per sequence: dense set id, -1: on its own; None: no sets (such a request rides alone)
     cdef bint translate
-    cdef object tokens          # find_proteins_batch: {"spec", "out", "stream"} -- the proteins also go to a device tensor, and the device
-                                # call leaves the DeviceProteins under "proteins" (such a request rides alone); None: no tokens.
-                                # find_labels_batch: the same with a BaseLabels as "spec", and the DeviceLabels under "labels"
+    cdef object tokens          # find_proteins_batch / find_labels_batch: {"spec", "out", "stream", "method"} -- the rule's tensor is also
+                                # written on the device, and the device call leaves the DeviceProteins / DeviceLabels under "result"
+                                # (such a request rides alone); None: no tensor
     cdef ssize_t first_id
     cdef int64_t bases
     cdef list out               # one Genes per sequence, filled in by the thread that ran the device call
@@ -2064,22 +2064,8 @@ cdef class GeneFinder:
         `ValueError`."""
         if not isinstance(tokens, _cabi.ProteinTokens):
             raise TypeError("`tokens` must be a ProteinTokens, not %r" % type(tokens).__name__)
-        cdef dict tok = {"spec": tokens, "out": out, "stream": stream, "proteins": None}
-        cdef list circ, tr_search
-        cdef object dev, set_ids, tr_params
-        dev, sequences, circ, set_ids, tr_search, tr_params = self._batch_options(sequences, training_infos, circular, sets, trim_terminal_repeats)
-        sequences = list(sequences)
-        if not sequences:
-            raise ValueError("find_proteins_batch needs at least one sequence")
-        if dev is not None:
-            genes = self._find_genes_device(dev, translate, training_infos, regions, circ, set_ids, tr_search, tr_params, tok)
-        elif training_infos is not None:
-            genes = self._find_genes_models(sequences, translate, training_infos, regions, circ, tr_search, tr_params, tok)
-        else:
-            if not self.meta and self.training_info is None:
-                raise RuntimeError("cannot find genes without having trained in single mode")
-            genes = self._find_genes_sets(self._wrap_sequences(sequences, regions), translate, set_ids, circ, tr_search, tr_params, tok)
-        return genes, tok["proteins"]
+        return self._find_tensor_batch("find_proteins_batch", sequences, tokens, out, stream, translate, training_infos, regions, circular, sets,
+                                       trim_terminal_repeats)
 
     def find_labels_batch(self, object sequences, object labels, *, object out=None, object stream=None, bint translate=False,
                           object training_infos=None, object regions=None, object circular=None, object sets=None,
@@ -2097,13 +2083,19 @@ cdef class GeneFinder:
         `ValueError`."""
         if not isinstance(labels, _cabi.BaseLabels):
             raise TypeError("`labels` must be a BaseLabels, not %r" % type(labels).__name__)
-        cdef dict tok = {"spec": labels, "out": out, "stream": stream, "labels": None, "method": "find_labels_batch"}
+        return self._find_tensor_batch("find_labels_batch", sequences, labels, out, stream, translate, training_infos, regions, circular, sets,
+                                       trim_terminal_repeats)
+
+    cdef tuple _find_tensor_batch(self, str method, object sequences, object spec, object out, object stream, bint translate,
+                                  object training_infos, object regions, object circular, object sets, object trim_terminal_repeats):
+        """`find_proteins_batch` / `find_labels_batch`: (the `Genes` of `find_genes_batch`, what the rule `spec` wrote on the device)."""
+        cdef dict tok = {"spec": spec, "out": out, "stream": stream, "result": None, "method": method}
         cdef list circ, tr_search
         cdef object dev, set_ids, tr_params
         dev, sequences, circ, set_ids, tr_search, tr_params = self._batch_options(sequences, training_infos, circular, sets, trim_terminal_repeats)
         sequences = list(sequences)
         if not sequences:
-            raise ValueError("find_labels_batch needs at least one sequence")
+            raise ValueError("%s needs at least one sequence" % method)
         if dev is not None:
             genes = self._find_genes_device(dev, translate, training_infos, regions, circ, set_ids, tr_search, tr_params, tok)
         elif training_infos is not None:
@@ -2112,7 +2104,7 @@ cdef class GeneFinder:
             if not self.meta and self.training_info is None:
                 raise RuntimeError("cannot find genes without having trained in single mode")
             genes = self._find_genes_sets(self._wrap_sequences(sequences, regions), translate, set_ids, circ, tr_search, tr_params, tok)
-        return genes, tok["labels"]
+        return genes, tok["result"]
 
     cdef tuple _batch_options(self, object sequences, object training_infos, object circular, object sets, object trim_terminal_repeats):
         """The options of `find_genes_batch` / `find_proteins_batch` / `find_labels_batch`, checked against each other and against the number of sequences:
@@ -2505,14 +2497,14 @@ cdef class GeneFinder:
             if translate:
                 o.prot, o.prot_off, o.tables = self._translate(ctx, batch, res[0], n, tinf_of)
             if o.tok is not None:
-                if isinstance(o.tok["spec"], _cabi.BaseLabels):
+                if o.tok["spec"].per_contig == "lengths":
                     # (the batch the finder called: without the bases `_trimmed_batch` took off)
-                    lengths = np.array([len((<Sequence> q).data) for q in seqs], np.int64)
+                    per_contig = np.array([len((<Sequence> q).data) for q in seqs], np.int64)
                     if trimmed != NULL:
-                        lengths -= o.tr_trim[:n]
-                    self._labels(ctx, batch, res[0], lengths, o.tok)
+                        per_contig -= o.tr_trim[:n]
                 else:
-                    self._tokens(ctx, batch, res[0], n, tinf_of, o.tok)
+                    per_contig = self._tables_of(res[0], n, tinf_of)[:n]
+                self._device_tensor(ctx, batch, res[0], per_contig, o.tok)
         finally:
             if batch != NULL:
                 pga_batch_free(batch)
@@ -2594,25 +2586,15 @@ cdef class GeneFinder:
             out.append(genes)
         return out
 
-    cdef int _tokens(self, pga_ctx* ctx, pga_batch* batch, pga_result* res, int n, list tinf_of, dict tok) except -1:
-        """The proteins of every gene of `res` as token ids into the request's device tensor, while the batch is resident
-        (`pga_translate_genes_tokens` through the raw layer's marshalling): leaves the `DeviceProteins` in `tok`."""
+    cdef int _device_tensor(self, pga_ctx* ctx, pga_batch* batch, pga_result* res, object per_contig, dict tok) except -1:
+        """What the request's rule makes of the genes of `res` -- their proteins as token ids, or the annotation of every base -- into
+        the request's device tensor while the batch the finder called is resident (through the raw layer's marshalling); `per_contig`:
+        what the rule needs of every contig, tables or lengths.  Leaves the `DeviceProteins` / `DeviceLabels` in `tok`."""
         genes = np.zeros(0, _cabi.GENE_DTYPE)
         if res.n_genes > 0:
             genes = np.frombuffer(PyBytes_FromStringAndSize(<const char*> res.genes, res.n_genes * sizeof(pga_gene)), dtype=_cabi.GENE_DTYPE)
-        tables = self._tables_of(res, n, tinf_of)[:n]
-        tok["proteins"] = _cabi.tokens_into(_cabi.load(), ctypes.c_void_p(<size_t> ctx), ctypes.c_void_p(<size_t> batch), self.device, n,
-                                            genes, tables, tok["spec"], tok["out"], tok["stream"])
-        return 0
-
-    cdef int _labels(self, pga_ctx* ctx, pga_batch* batch, pga_result* res, object lengths, dict tok) except -1:
-        """The annotation of every base under the genes of `res` into the request's device tensor, while the batch the finder called
-        is resident (`pga_label_bases` through the raw layer's marshalling): leaves the `DeviceLabels` in `tok`."""
-        genes = np.zeros(0, _cabi.GENE_DTYPE)
-        if res.n_genes > 0:
-            genes = np.frombuffer(PyBytes_FromStringAndSize(<const char*> res.genes, res.n_genes * sizeof(pga_gene)), dtype=_cabi.GENE_DTYPE)
-        tok["labels"] = _cabi.labels_into(_cabi.load(), ctypes.c_void_p(<size_t> ctx), ctypes.c_void_p(<size_t> batch), self.device,
-                                          lengths, genes, tok["spec"], tok["out"], tok["stream"])
+        tok["result"] = tok["spec"].write(_cabi.load(), ctypes.c_void_p(<size_t> ctx), ctypes.c_void_p(<size_t> batch), self.device, genes,
+                                          per_contig, tok["out"], tok["stream"])
         return 0
 
     cdef object _tables_of(self, pga_result* res, int n, list tinf_of):

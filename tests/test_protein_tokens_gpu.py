@@ -121,12 +121,12 @@ def spec_of(dtype, layout, bos, eos, **kw):
     return ProteinTokens(VOCAB, bos=BOS if bos else None, eos=EOS if eos else None, pad=PAD, dtype=dtype, layout=layout, **kw)
 
 
-def run(ctx, batch, genes, tables, prot, spec, fill=CANARY, **kw):
-    """One call into a Target; returns (what the allocation holds, what it must hold, the DeviceProteins, the reference lengths)."""
+def run(ctx, batch, genes, tables, prot, spec, fill=CANARY, extra_width=3, extra_stride=5, **kw):
+    """One call into a Target; returns (what the allocation holds, what it must hold, the DeviceProteins, the Target)."""
     ref = dict(bos=spec.bos, eos=spec.eos, pad=spec.pad, max_length=spec.max_length, dtype=DTYPES[spec.dtype])
     _, lens, off = protein_tokens_ref(prot, IDS, layout="ragged", **ref)
-    width = int(lens.max()) + 3
-    t = Target(DTYPES[spec.dtype], spec.layout, len(genes), width, int(off[-1]), fill)
+    width = int(lens.max(initial=0)) + extra_width
+    t = Target(DTYPES[spec.dtype], spec.layout, len(genes), width, int(off[-1]), fill, extra_stride)
     want, _, _ = protein_tokens_ref(prot, IDS, layout=spec.layout, width=width, **ref)
     dp = ctx.translate_tokens(batch, genes, spec, out=t.out, tables=tables, **kw)
     assert dp.lengths.tolist() == lens.tolist() and dp.lengths.dtype == np.int64
@@ -164,6 +164,52 @@ def test_stop_letters_strictness_and_the_unknown_id(ctx, synthetic):
     dp = ctx.translate_tokens(batch, genes, spec, out=t.out, tables=TABLES)
     want, _, _ = protein_tokens_ref(loose, ids, pad=255, width=max(lens) + 1, dtype=np.uint8)
     assert np.array_equal(t.read(), t.expect(want)) and dp.lengths.tolist() == lens and 99 in want
+
+
+def records_where(pick):
+    return [k for k, r in enumerate(synthetic_records()) if pick(r)]
+
+
+def tiny_records():
+    """The records of 0 and 1 codons, the two that keep a residue without specials moved inwards: empty genes lead, lie between, trail."""
+    tiny = records_where(lambda r: (r[2] - r[1] + 1) // 3 <= 1)
+    return tiny[:3] + tiny[-2:-1] + tiny[3:6] + tiny[-1:] + tiny[6:-2]
+
+
+# the degenerate shapes: which of the synthetic records, with bos and eos or without, and the columns beyond the longest gene
+SHAPES = {
+    "no record": (lambda: [], False, 3),
+    "one record": (lambda: [40], True, 3),
+    "empty genes": (tiny_records, False, 3),
+    "empty genes, specials": (tiny_records, True, 3),
+    "across the origin": (lambda: records_where(lambda r: r[0] == 1 and r[2] > len(synthetic_contigs()[1])), False, 3),
+    "wide rows": (lambda: records_where(lambda r: True), True, 50),
+}
+
+
+@pytest.mark.parametrize("shape", sorted(SHAPES))
+@pytest.mark.parametrize("layout", ["ragged", "padded"])
+@pytest.mark.parametrize("dtype", ["uint8", "int32", "int64"])
+def test_smallest_shapes(ctx, synthetic, dtype, layout, shape):
+    """The seams between rows where rows are few, empty or short (the counterpart of test_base_labels_gpu.py::test_smallest_shapes)."""
+    batch, genes, prot = synthetic
+    records, specials, extra_width = SHAPES[shape]
+    pick = records()
+    sub, sub_prot = np.ascontiguousarray(genes[pick]), [prot[False][k] for k in pick]
+    n = [len(p) for p in sub_prot]
+    if shape == "no record":
+        assert n == []
+    elif shape == "one record":
+        assert len(n) == 1 and n[0] > 16
+    elif shape.startswith("empty genes"):
+        assert n == [0, 0, 0, 1, 0, 0, 0, 1, 0, 0, 0, 0]
+    elif shape == "across the origin":
+        assert len(n) == 2 and min(n) >= 19
+    for extra_stride in (0, 5):
+        got, want, _, t = run(ctx, batch, sub, TABLES, sub_prot, spec_of(dtype, layout, specials, specials), extra_width=extra_width,
+                              extra_stride=extra_stride)
+        assert t.ptr % 16 == t.eb
+        assert np.array_equal(got, want), extra_stride
 
 
 # ---- 2. truncation -------------------------------------------------------------------------------------------------------------------
