@@ -461,6 +461,60 @@ int pga_label_bases(pga_ctx*, const pga_batch*, int64_t n_genes, const pga_gene*
                     void* d_out /* device memory of the context's device */, int64_t n_out_elems,
                     void* stream /* hipStream_t, NULL = the null stream */, int64_t* len_out /* [contigs of the batch], host */);
 
+/* The nucleotides of every gene and of the region around it, in the gene's own reading direction, left on the device as token ids,
+ * one row per gene record: coding sequences as codon tokens, fixed start contexts, upstream and downstream flanks for a model in the
+ * same process.  Only the letters the windows name are read; nothing comes to the host.
+ *   Positions.  Gene record g lies on contig i.  L is the length the batch holds for that contig.  It is the trimmed length after
+ *     trim_terminal_repeats, as for pga_label_bases.  The record is [b, e], 1-based and inclusive, n = e - b + 1, with a strand.
+ *     The gene's reading axis gives offset t (any integer) the position q(t) = b + t on the forward strand and q(t) = e - t on the
+ *     reverse strand.  Two anchors are defined: start = 0 and end = n, one past the gene's last base in reading direction.
+ *     A window is from = (anchor, delta) to to = (anchor, delta).  It covers offsets t_lo = anchor_from + delta_from up to but
+ *     excluding t_hi = anchor_to + delta_to.  Its m_g = max(0, t_hi - t_lo) bases are read in reading direction.  An empty or
+ *     inverted window on a short gene is a row without bases.  It is not an error.
+ *     Examples: (start, 0) .. (end, 0) is the gene as -d prints it.  (start, -60) .. (start, +30) is a fixed 90-base start context.
+ *     (end, 0) .. (end, +50) is the downstream region.
+ *   Base class.  On a contig flagged circular, q is taken modulo L: ((q - 1) mod L) + 1, floor modulo.  It is defined for any q, so a
+ *     flank longer than the contig goes round more than once.  On a linear contig, q < 1 or q > L is the class outside.  Otherwise
+ *     the letter reads A, C, G, T in either case.  Anything else reads N.  This is exactly the reading of Gene.sequence().  A reverse
+ *     gene's letter is complemented: A and T swap, C and G swap, N stays N.
+ *   Units.  PGA_WINDOW_BASES: one token per base.  ids[0..3] = A, C, G, T.  ids[4] = N.  ids[5] = outside.
+ *     PGA_WINDOW_CODONS: both deltas must be multiples of 3.  Token j covers offsets t_lo + 3j .. t_lo + 3j + 2.  The id is
+ *     ids[16 c0 + 4 c1 + c2], with A, C, G, T = 0, 1, 2, 3.  This is the public ACGT order.  It is not the internal digit order.
+ *     A codon that touches outside gets ids[65].  Otherwise a codon with an N gets ids[64].  m_g is a multiple of 3, because records
+ *     are whole codons.
+ *   Tokens of a row, layouts, elements.  These follow pga_translate_genes_tokens exactly, with u_g = m_g (bases) or m_g / 3 (codons)
+ *     in the place of the residues n_g: [bos] if given, the ids of the first R_g units, [eos] if given; max_length cuts on the far
+ *     side, and eos survives the cut.  The layout is ragged or padded with W, S and pad.  Elements W .. S of a row are untouched.
+ *     Elements are uint8, int32 or int64.  d_out need only be element-aligned.  len_out[g] is computed on the host.
+ *   Validation.  Everything is checked on the host, before anything is allocated or launched.  A failure returns PGA_EINVAL, and
+ *     pga_last_error names the gene or field.  The checks are: element width and id ranges; unit and anchors; |delta| <= 2^30; deltas
+ *     that are multiples of 3 for codons; max_length; the record checks of pga_label_bases (every record inside its contig, whole
+ *     codons, and e > L only on a circle); W against the longest row; n_out_elems against the layout; the alignment of d_out; and the
+ *     device-pointer query on it.
+ *   Ordering and concurrency.  Those of pga_translate_genes_tokens.
+ * Gene records come from the host, in any subset or order. */
+#define PGA_WINDOW_BASES  0
+#define PGA_WINDOW_CODONS 1
+#define PGA_WINDOW_START  0     /* anchor: offset 0, the gene's first base in reading direction */
+#define PGA_WINDOW_END    1     /* anchor: offset n, one past the gene's last base in reading direction */
+typedef struct pga_window_opts {
+    int32_t elem_bytes;         /* 1, 4 or 8 */
+    int32_t layout;             /* PGA_TOKENS_RAGGED or PGA_TOKENS_PADDED */
+    int64_t row_width;          /* W, padded layout (ignored for ragged) */
+    int64_t row_stride;         /* S, padded layout (ignored for ragged) */
+    int32_t unit;               /* PGA_WINDOW_BASES or PGA_WINDOW_CODONS */
+    int32_t from_anchor, to_anchor;   /* PGA_WINDOW_START or PGA_WINDOW_END */
+    int32_t _pad;
+    int64_t from_delta, to_delta;
+    int64_t max_length;         /* 0: no limit */
+    int64_t ids[66];            /* bases: [0..5] are read.  Codons: all 66 */
+    int64_t bos, eos;           /* PGA_TOKEN_NONE: none */
+    int64_t pad;                /* padded layout */
+} pga_window_opts;
+int pga_gene_windows(pga_ctx*, const pga_batch*, int64_t n_genes, const pga_gene* genes, const pga_window_opts*,
+                     void* d_out /* device memory of the context's device */, int64_t n_out_elems,
+                     void* stream /* hipStream_t, NULL = the null stream */, int64_t* len_out /* [n_genes], host */);
+
 /* ---- text output ------------------------------------------------------------------ */
 /* GFF, protein FASTA, gene FASTA, GenBank and the start-score file of gene records, rendered on the device from a resident
  * batch: byte for byte what the host writers Genes.write_gff / write_translations / write_genes / write_genbank / write_scores

@@ -11,7 +11,8 @@ __version__ = "0.1.0"
 _LIB_NAMES = ("GeneFinder", "Genes", "Gene", "Nodes", "Node", "Sequence", "TrainingInfo", "MetagenomicBin", "MetagenomicBins",
               "ConnectionScorer", "Mask", "Masks", "METAGENOMIC_BINS", "TRANSLATION_TABLES", "PRODIGAL_VERSION", "MIN_SINGLE_GENOME",
               "IDEAL_SINGLE_GENOME", "TerminalRepeats")
-_CABI_NAMES = ("DeviceSequences", "ProteinTokens", "DeviceProteins", "BaseLabels", "DeviceLabels")
+_CABI_NAMES = ("DeviceSequences", "ProteinTokens", "DeviceProteins", "BaseLabels", "DeviceLabels", "GeneWindows",
+               "DeviceWindows")
 __all__ = list(_LIB_NAMES) + ["TableSelection"] + list(_CABI_NAMES)
 
 from .tables import TableSelection      # pure Python: the result of GeneFinder.select_translation_table

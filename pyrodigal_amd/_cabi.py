@@ -28,7 +28,7 @@ EXPORTS = [
     "pga_batch_terminal_repeats", "pga_batch_trim_terminal_repeats", "pga_terminal_repeat_chunk",
     "pga_debug_poison",
     "pga_batch_create_device", "pga_batch_read",
-    "pga_translate_genes_tokens", "pga_label_bases",
+    "pga_translate_genes_tokens", "pga_label_bases", "pga_gene_windows",
 ]
 STAGE_EXTRACT, STAGE_SCORE, STAGE_OVERLAP, STAGE_SEQUENCE = 1, 2, 3, 4
 
@@ -111,7 +111,16 @@ class LabelOpts(ctypes.Structure):
                 ("class_map", ctypes.c_int64 * 256), ("pad", ctypes.c_int64)]
 
 
+class WindowOpts(ctypes.Structure):
+    _fields_ = [("elem_bytes", ctypes.c_int32), ("layout", ctypes.c_int32), ("row_width", ctypes.c_int64), ("row_stride", ctypes.c_int64),
+                ("unit", ctypes.c_int32), ("from_anchor", ctypes.c_int32), ("to_anchor", ctypes.c_int32), ("_pad", ctypes.c_int32),
+                ("from_delta", ctypes.c_int64), ("to_delta", ctypes.c_int64), ("max_length", ctypes.c_int64),
+                ("ids", ctypes.c_int64 * 66), ("bos", ctypes.c_int64), ("eos", ctypes.c_int64), ("pad", ctypes.c_int64)]
+
+
 TOKENS_RAGGED, TOKENS_PADDED = 0, 1                         # pga_token_opts.layout
+WINDOW_BASES, WINDOW_CODONS = 0, 1                          # pga_window_opts.unit
+WINDOW_START, WINDOW_END = 0, 1                             # pga_window_opts.from_anchor / to_anchor
 TOKEN_NONE = -(1 << 63)                                     # pga_token_opts.bos / eos: no such token
 RENDER_FORMATS = ("gff", "faa", "fna", "gbk", "scores")     # PGA_RENDER_* bit order
 NODES_DEVICE = 2                                            # pga_params.want_nodes: keep the node arrays on the device
@@ -193,6 +202,8 @@ def load():
     L.pga_translate_genes_tokens.argtypes = [vp, vp, i64, vp, vp, _P(TokenOpts), vp, i64, vp, vp]
     L.pga_label_bases.restype = ctypes.c_int
     L.pga_label_bases.argtypes = [vp, vp, i64, vp, _P(LabelOpts), vp, i64, vp, vp]
+    L.pga_gene_windows.restype = ctypes.c_int
+    L.pga_gene_windows.argtypes = [vp, vp, i64, vp, _P(WindowOpts), vp, i64, vp, vp]
     L.pga_render_genes.restype = ctypes.c_int
     L.pga_render_genes.argtypes = [vp, vp, vp, i64, vp, vp, vp, vp, _P(RenderOpts), _P(_P(RenderResult))]
     L.pga_render_free.restype = None; L.pga_render_free.argtypes = [_P(RenderResult)]
@@ -1177,7 +1188,7 @@ def _token_id(value, name):
 
 
 class _TensorRule:
-    """What ProteinTokens and BaseLabels share: the element type and layout of the device tensor, value semantics over ``_key()``,
+    """What ProteinTokens, BaseLabels and GeneWindows share: the element type and layout of the device tensor, value semantics over ``_key()``,
     and the head of the options struct.  A subclass says what one row is (``row`` and its ``unit``), what it needs of every contig
     of the batch (``per_contig``: ``"tables"`` or ``"lengths"``), and has ``write``, the call on raw handles with just that."""
 
@@ -1581,6 +1592,195 @@ def _label_bases(self, batch, result_or_genes, spec, out=None, stream=None):
     return labels_into(self.L, self.h, batch.h, self.device, batch.lengths, genes, spec, out, stream)
 
 
+WINDOW_LETTERS = "ACGT"                                      # the public order of pga_window_opts.ids
+WINDOW_CODONS_ACGT = tuple(a + b + c for a in WINDOW_LETTERS for b in WINDOW_LETTERS for c in WINDOW_LETTERS)
+_WINDOW_ANCHORS = {"start": WINDOW_START, "end": WINDOW_END}
+_WINDOW_MAX_DELTA = 1 << 30
+
+
+class GeneWindows(_TensorRule):
+    """How ``gene_windows`` / ``find_windows_batch`` write the nucleotides of every gene, or of a region around it, into a device
+    tensor, one row per gene in the gene's own reading direction (``pga_window_opts``; the rule is in ``pyrodigal_amd.h``).
+
+    ``begin`` / ``end``: ``(anchor, delta)`` with the anchor ``"start"`` (the gene's first base) or ``"end"`` (one past its last
+    base); the window runs from ``begin`` up to but excluding ``end``, so the defaults are the gene itself, ``("start", -60)`` ..
+    ``("start", 30)`` a 90-base start context and ``("end", 0)`` .. ``("end", 50)`` the downstream region.  A window that is empty or
+    inverted on a gene is a row without bases.  ``unit``: ``"base"``, one token per base, or ``"codon"``, one per three bases (both
+    deltas must then be multiples of 3).  ``vocabulary``: ``None`` gives A, C, G, T = 0 .. 3 and N = 4, or the 64 codons = 0 .. 63
+    in ACGT order and unknown = 64; a string (bases only: the id of a letter is its position) or a ``{letter-or-codon: id}`` mapping
+    must cover all four letters or all 64 codons, and may hold ``N`` / ``NNN`` for ``unknown``, the id of a letter that is not A, C,
+    G or T or of a codon with one.  ``outside``: the id of a base (or of a codon that touches one) beyond the ends of a linear
+    contig; by default that of ``unknown``.  On a circular contig a window wraps instead.  ``bos`` / ``eos``: ids put before /
+    behind every row, ``None``: none.  ``pad`` fills the rows of the padded layout and must be given for it.  ``dtype``:
+    ``"uint8"``, ``"int32"`` or ``"int64"``; every id must fit it.  ``max_length``: the most tokens of a row, specials included
+    (``eos`` survives the cut).  Everything that needs no device is checked here.  Hashable and picklable."""
+
+    def __init__(self, begin=("start", 0), end=("end", 0), *, unit="base", vocabulary=None, unknown=None, outside=None, bos=None,
+                 eos=None, pad=None, dtype="int64", layout="padded", max_length=None):
+        self._set_format(dtype, layout)
+        if unit not in ("base", "codon"):
+            raise ValueError(f"unit must be \"base\" or \"codon\", not {unit!r}")
+        self.token_unit = unit                           # (`unit` is what a row is counted in, as for every rule)
+        self.begin, self.end = self._bound("begin", begin), self._bound("end", end)
+        keys = tuple(WINDOW_LETTERS) if unit == "base" else WINDOW_CODONS_ACGT
+        unknown_key = "N" * len(keys[0])
+        unknown = None if unknown is None else _token_id(unknown, "unknown")
+        if vocabulary is None:
+            given = {key: k for k, key in enumerate(keys)}
+            if unknown is None:
+                unknown = len(keys)
+        elif isinstance(vocabulary, str):
+            if unit != "base":
+                raise TypeError("a vocabulary string names bases: the codon unit takes a {codon: id} mapping")
+            if len(set(vocabulary.upper())) != len(vocabulary):
+                raise ValueError("a letter occurs twice in the vocabulary string")
+            given = {ch: k for k, ch in enumerate(vocabulary.upper()) if ch in keys or ch == unknown_key}      # (other letters: specials)
+        elif hasattr(vocabulary, "items"):
+            given = {}
+            for key, v in vocabulary.items():
+                key = key.decode("ascii", "replace") if isinstance(key, (bytes, bytearray)) else key
+                if not isinstance(key, str):
+                    raise ValueError(f"vocabulary key {key!r} is not a string")
+                if key.upper() in given:
+                    raise ValueError(f"vocabulary key {key!r} occurs twice")
+                given[key.upper()] = _token_id(v, f"the id of {key!r}")
+        else:
+            raise TypeError("vocabulary must be None, a string or a {letter-or-codon: id} mapping, not %r" % type(vocabulary).__name__)
+        for key in given:
+            if key not in keys and key != unknown_key:
+                raise ValueError(f"vocabulary key {key!r} is not one of {', '.join(keys[:4])}, ... or {unknown_key}")
+        for key in keys:
+            if key not in given:
+                raise ValueError(f"the vocabulary has no id for {key!r}: it must cover all {len(keys)} {unit}s")
+        if unknown is None:
+            if unknown_key not in given:
+                raise ValueError(f"the vocabulary has no id for {unknown_key!r} and `unknown` is None")
+            unknown = given[unknown_key]
+        self.unknown = unknown
+        self.outside = unknown if outside is None else _token_id(outside, "outside")
+        self.ids = tuple(given[key] for key in keys) + (self.unknown, self.outside)
+        self.bos = None if bos is None else _token_id(bos, "bos")
+        self.eos = None if eos is None else _token_id(eos, "eos")
+        if pad is None:
+            if layout == "padded":
+                raise ValueError("the padded layout needs `pad`, the id that fills the rows behind their tokens")
+            pad = 0
+        self.pad = _token_id(pad, "pad")
+        self._check_fit([(f"the id of {key!r}", v) for key, v in zip(keys, self.ids)] +
+                        [("unknown", self.unknown), ("outside", self.outside), ("bos", self.bos), ("eos", self.eos), ("pad", self.pad)])
+        self.specials = (self.bos is not None) + (self.eos is not None)
+        if max_length is not None:
+            max_length = _token_id(max_length, "max_length")
+            if max_length < self.specials + 1:
+                raise ValueError(f"max_length = {max_length} leaves no room for a {unit} beside {self.specials} special tokens")
+        self.max_length = max_length
+
+    def _bound(self, name, bound):
+        try:
+            anchor, delta = bound
+        except (TypeError, ValueError):
+            raise ValueError(f"{name} must be (anchor, delta), not {bound!r}") from None
+        if anchor not in _WINDOW_ANCHORS:
+            raise ValueError(f"the anchor of {name} must be \"start\" or \"end\", not {anchor!r}")
+        delta = _token_id(delta, f"the delta of {name}")
+        if abs(delta) > _WINDOW_MAX_DELTA:
+            raise ValueError(f"the delta of {name}, {delta}, is beyond 2^30 in size")
+        if self.token_unit == "codon" and delta % 3:
+            raise ValueError(f"the delta of {name}, {delta}, is no multiple of 3, which the codon unit needs")
+        return (anchor, delta)
+
+    row, unit, per_contig = "gene", "tokens", "lengths"
+
+    def write(self, L, ctx_h, batch_h, device, genes, lengths, out=None, stream=None):
+        return windows_into(L, ctx_h, batch_h, device, len(lengths), genes, self, out, stream)
+
+    def _key(self):
+        return (self.begin, self.end, self.token_unit, self.ids, self.bos, self.eos, self.pad, self.dtype, self.layout, self.max_length)
+
+    def __reduce__(self):
+        return _gene_windows_from_key, (self._key(),)
+
+    def __repr__(self):
+        return "pyrodigal_amd.GeneWindows(%r, %r, unit=%r, dtype=%r, layout=%r, bos=%r, eos=%r, max_length=%r)" % (
+            self.begin, self.end, self.token_unit, self.dtype, self.layout, self.bos, self.eos, self.max_length)
+
+    def lengths(self, genes):
+        """Tokens of every gene record's row, specials included (int64): host arithmetic on the coordinates, as the library does it."""
+        n = genes["end"].astype(np.int64) - genes["begin"] + 1
+        t_lo = np.where(self.begin[0] == "end", n, 0) + self.begin[1]
+        t_hi = np.where(self.end[0] == "end", n, 0) + self.end[1]
+        r = np.maximum(t_hi - t_lo, 0) // (3 if self.token_unit == "codon" else 1)
+        if self.max_length is not None:
+            r = np.minimum(r, self.max_length - self.specials)
+        return (r + self.specials).astype(np.int64)
+
+    def opts(self, row_width=0, row_stride=0):
+        o = self._opts(WindowOpts(), row_width, row_stride)
+        o.unit = WINDOW_CODONS if self.token_unit == "codon" else WINDOW_BASES
+        o.from_anchor, o.from_delta = _WINDOW_ANCHORS[self.begin[0]], self.begin[1]
+        o.to_anchor, o.to_delta = _WINDOW_ANCHORS[self.end[0]], self.end[1]
+        o.max_length = 0 if self.max_length is None else self.max_length
+        o.ids[:len(self.ids)] = self.ids
+        o.bos = TOKEN_NONE if self.bos is None else self.bos
+        o.eos = TOKEN_NONE if self.eos is None else self.eos
+        return o
+
+
+def _gene_windows_from_key(key):
+    w = GeneWindows.__new__(GeneWindows)
+    w.begin, w.end, w.token_unit, w.ids, w.bos, w.eos, w.pad, w.dtype, w.layout, w.max_length = key
+    w.unknown, w.outside = w.ids[-2:]
+    w.specials = (w.bos is not None) + (w.eos is not None)
+    return w
+
+
+class DeviceWindows:
+    """Nucleotide windows of gene records as token ids in device memory.  ``tokens``: the tensor (``[G, W]`` padded, 1-D ragged);
+    ``lengths``: tokens of every row (numpy int64, host); ``offsets``: ragged only, gene g is ``tokens[offsets[g]:offsets[g + 1]]``;
+    ``gene_begin``: the genes of contig i are rows ``gene_begin[i] .. gene_begin[i + 1]`` (``None`` when the records were not in
+    contig order); ``windows[i]``: contig i's rows or slice as a view of ``tokens``."""
+
+    def __init__(self, tokens, lengths, offsets, gene_begin, device):
+        self.tokens, self.lengths, self.offsets, self.gene_begin, self.device = tokens, lengths, offsets, gene_begin, device
+
+    @property
+    def windows(self):
+        if self.gene_begin is None:
+            raise ValueError("the gene records were not in contig order: there are no per-contig views")
+        return _ContigProteins(self)
+
+    def cu_seqlens(self):
+        """The exclusive scan of ``lengths`` as an int32 tensor on the tokens' device (torch)."""
+        return _cu_seqlens(self.lengths, self.tokens, self.device)
+
+
+def windows_into(L, ctx_h, batch_h, device, n_contigs, genes, spec, out=None, stream=None):
+    """``pga_gene_windows`` on raw handles (what ``Context.gene_windows`` and the finder's device call share): the windows of
+    ``genes`` (GENE_DTYPE records of the resident batch of ``n_contigs`` contigs) into ``out``, or into a new torch tensor."""
+    if not isinstance(spec, GeneWindows):
+        raise TypeError("the window rule must be a GeneWindows, not %r" % type(spec).__name__)
+    genes = np.ascontiguousarray(genes, dtype=GENE_DTYPE)
+    n, lens = len(genes), spec.lengths(genes)
+    args = (batch_h, n, ctypes.c_void_p(genes.ctypes.data))
+    out, off, len_out = _rows_into(L, ctx_h, "pga_gene_windows", args, spec, lens, device, out, stream)
+    assert np.array_equal(len_out, lens)
+    gene_begin = None
+    if n == 0 or np.all(np.diff(genes["contig"]) >= 0):
+        gene_begin = np.searchsorted(genes["contig"], np.arange(n_contigs + 1)).astype(np.int64)
+    return DeviceWindows(out, lens, off, gene_begin, device)
+
+
+def _gene_windows(self, batch, result_or_genes, spec, out=None, stream=None):
+    """The nucleotides of gene records of the resident ``batch``, or of a region around each, as token ids in device memory, one row
+    per record in the gene's reading direction (``pga_gene_windows``): nothing of them comes to the host.  ``result_or_genes``: a
+    result of ``find_genes`` on the batch, or gene records of one (any subset or order).  ``spec``: a :class:`GeneWindows`.
+    ``out``: any object with ``__cuda_array_interface__`` -- 1-D for the ragged layout, ``[G, W]`` with a contiguous last dimension
+    for the padded one; ``None``: a torch tensor is allocated on the context's device under torch's current stream.  ``stream``:
+    the stream that last used ``out``, as in :class:`DeviceSequences`.  Returns a :class:`DeviceWindows`."""
+    genes = getattr(result_or_genes, "genes", result_or_genes)
+    return windows_into(self.L, self.h, batch.h, self.device, batch.n, genes, spec, out, stream)
+
+
 class RenderedText:
     """One format's text of a :meth:`Context.render_genes` call: ``data`` (bytes), ``contig_offsets`` (contig i is
     ``data[contig_offsets[i]:contig_offsets[i + 1]]``), ``fallback`` (lines the host rendered itself) and ``kernel_ms`` (device
@@ -1792,6 +1992,7 @@ Context.render_genes = _render_genes
 Context.translate_genes = _translate_genes
 Context.translate_tokens = _translate_tokens
 Context.label_bases = _label_bases
+Context.gene_windows = _gene_windows
 Context.train = _train
 Context.train_batch = _train_batch
 Context.upload = _upload

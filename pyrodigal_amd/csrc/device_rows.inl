@@ -1,6 +1,7 @@
 // Rows of 1-, 4- or 8-byte elements written into a caller's device tensor, ragged or padded, at any element alignment (DESIGN.md
-// 4.14): the destination's description and the host side of such a call, which k_translate_tokens (translate_tokens.inl) and
-// k_label_bases (label_bases.inl) share.  Included by translate.hip, inside its anonymous namespace, in front of the two.
+// 4.14): the destination's description and the host side of such a call, which k_translate_tokens (translate_tokens.inl),
+// k_label_bases (label_bases.inl) and k_gene_windows (gene_windows.inl) share.  Included by translate.hip, inside its anonymous
+// namespace, in front of the three.
 
 constexpr int kRowThreads = 256;
 

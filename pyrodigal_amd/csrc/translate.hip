@@ -89,6 +89,7 @@ int64_t gene_residues(const pga_gene& G, const int include_stop) {
 #include "device_rows.inl"
 #include "translate_tokens.inl"
 #include "label_bases.inl"
+#include "gene_windows.inl"
 
 }  // namespace
 
@@ -242,6 +243,80 @@ extern "C" int pga_label_bases(pga_ctx* c, const pga_batch* batch, int64_t n_gen
     return d.run(L, tab, stream, [&](const dim3 grid, const dim3 block, hipStream_t st) {
         with_elem_layout(d.eb, d.padded, [&](auto EB, auto PADDED) {
             hipLaunchKernelGGL((k_label_bases<decltype(EB)::value, decltype(PADDED)::value>), grid, block, 0, st, a);
+        });
+    });
+}
+
+extern "C" int pga_gene_windows(pga_ctx* c, const pga_batch* batch, int64_t n_genes, const pga_gene* genes, const pga_window_opts* o, void* d_out,
+                                int64_t n_out_elems, void* stream, int64_t* len_out) {
+    if (!c) return PGA_EINVAL;
+    RowDest d{c, "pga_gene_windows"};
+    if (!batch || !o || n_genes < 0 || n_out_elems < 0 || (n_genes > 0 && (!genes || !len_out))) return d.bad("bad arguments");
+    const pga_batch_view bv = pga_batch_peek(batch);
+    if (bv.ctx != c) return d.bad("the batch belongs to another context");
+    // ---- validation: all of it on the host, before anything is allocated or launched ----
+    if (const int rc = d.format(o->elem_bytes, o->layout)) return rc;
+    if (o->unit != PGA_WINDOW_BASES && o->unit != PGA_WINDOW_CODONS) return d.bad("unit must be PGA_WINDOW_BASES or PGA_WINDOW_CODONS, not " + std::to_string(o->unit));
+    const bool codons = o->unit == PGA_WINDOW_CODONS;
+    const bool has_bos = o->bos != PGA_TOKEN_NONE, has_eos = o->eos != PGA_TOKEN_NONE;
+    const int64_t s = (has_bos ? 1 : 0) + (has_eos ? 1 : 0);
+    if (const int rc = d.fits("ids", o->ids, codons ? 66 : 6)) return rc;
+    if (has_bos) if (const int rc = d.fits("bos", o->bos)) return rc;
+    if (has_eos) if (const int rc = d.fits("eos", o->eos)) return rc;
+    if (d.padded) if (const int rc = d.fits("pad", o->pad)) return rc;
+    const struct { const char* name; int32_t anchor; int64_t delta; } ends[2] = {{"from", o->from_anchor, o->from_delta}, {"to", o->to_anchor, o->to_delta}};
+    for (const auto& x : ends) {
+        if (x.anchor != PGA_WINDOW_START && x.anchor != PGA_WINDOW_END)
+            return d.bad(std::string(x.name) + "_anchor must be PGA_WINDOW_START or PGA_WINDOW_END, not " + std::to_string(x.anchor));
+        if (x.delta < -((int64_t)1 << 30) || x.delta > ((int64_t)1 << 30))
+            return d.bad(std::string(x.name) + "_delta = " + std::to_string(x.delta) + " is beyond 2^30 in size");
+        if (codons && x.delta % 3) return d.bad(std::string(x.name) + "_delta = " + std::to_string(x.delta) + " is no multiple of 3, which the codon unit needs");
+    }
+    if (o->max_length < 0 || (o->max_length != 0 && o->max_length < s + 1))
+        return d.bad("max_length = " + std::to_string(o->max_length) + " leaves no room for a unit beside " + std::to_string(s) + " special tokens (0: no limit)");
+    // every record inside its contig, in whole codons (the checks of pga_label_bases); the tokens of its row
+    const int64_t per_unit = codons ? 3 : 1;
+    std::vector<int64_t> off((size_t)n_genes + 1, 0);
+    for (int64_t g = 0; g < n_genes; g++) {
+        const pga_gene& G = genes[g];
+        const std::string who = "gene " + std::to_string(g);
+        if (G.contig < 0 || G.contig >= bv.n) return d.bad(who + " names contig " + std::to_string(G.contig) + " of " + std::to_string(bv.n));
+        const int64_t len = bv.ct[G.contig].len, glen = (int64_t)G.end - G.begin + 1;
+        if (G.begin < 1 || G.begin > len || glen < 3 || glen > len) return d.bad(who + " lies outside its contig");
+        if (glen % 3) return d.bad(who + " is " + std::to_string(glen) + " bases long, no whole number of codons");
+        if (G.end > len && !(bv.circular && bv.circular[G.contig])) return d.bad(who + " ends beyond its contig, which is not flagged circular");
+        const int64_t t_lo = (o->from_anchor == PGA_WINDOW_END ? glen : 0) + o->from_delta, t_hi = (o->to_anchor == PGA_WINDOW_END ? glen : 0) + o->to_delta;
+        int64_t r = t_hi > t_lo ? (t_hi - t_lo) / per_unit : 0;
+        if (o->max_length != 0 && r > o->max_length - s) r = o->max_length - s;
+        off[(size_t)g + 1] = off[(size_t)g] + s + r;
+    }
+    if (const int rc = d.shape(off, "tokens of gene", o->row_width, o->row_stride, o->pad, n_out_elems)) return rc;
+    if (const int rc = d.memory(d_out)) return rc;
+    for (int64_t g = 0; g < n_genes; g++) len_out[g] = off[(size_t)g + 1] - off[(size_t)g];
+    if (d.a.n_elems == 0) return PGA_OK;
+    // ---- the kernel's tables: staged in the upload's pinned area as they will lie on the device, one copy ----
+    const size_t G = (size_t)n_genes;
+    const size_t off_b = sizeof(int64_t) * (G + 1), ids_b = sizeof(int64_t) * 66, win_b = sizeof(WinRow) * G;
+    const size_t tab = off_b + ids_b + win_b;
+    pga_upload_lease L{};
+    { const int rc = pga_upload_lease_take(c, tab, &L); if (rc) return rc; }
+    memcpy(L.pin, off.data(), off_b);
+    memcpy(L.pin + off_b, o->ids, ids_b);
+    WinRow* const win = (WinRow*)(L.pin + off_b + ids_b);
+    for (size_t g = 0; g < G; g++) {
+        const pga_gene& R = genes[g];
+        const int64_t glen = (int64_t)R.end - R.begin + 1;
+        win[g] = win_row(R, bv.ct[R.contig], bv.circular && bv.circular[R.contig], (o->from_anchor == PGA_WINDOW_END ? glen : 0) + o->from_delta);
+    }
+    WinArgs a{};
+    a.rows = d.a; a.rows.off = (const int64_t*)L.dev;
+    a.seq = bv.d_seq;
+    a.ids = (const int64_t*)(L.dev + off_b); a.win = (const WinRow*)(L.dev + off_b + ids_b);
+    a.bos = has_bos ? o->bos : 0; a.eos = has_eos ? o->eos : 0;
+    a.has_bos = has_bos; a.has_eos = has_eos; a.codons = codons;
+    return d.run(L, tab, stream, [&](const dim3 grid, const dim3 block, hipStream_t st) {
+        with_elem_layout(d.eb, d.padded, [&](auto EB, auto PADDED) {
+            hipLaunchKernelGGL((k_gene_windows<decltype(EB)::value, decltype(PADDED)::value>), grid, block, 0, st, a);
         });
     });
 }

@@ -54,8 +54,9 @@ __device__ __forceinline__ T tok_at(const TokArgs& a, const TokGene& t, const T*
 // once per workgroup in LDS, 128 entries of the element width: the indices diverge per lane) and leaves as one 16-byte store.
 // Pieces that span a seam between genes or rows, reach into a row's W .. S, or are partial (the first and the last of the tensor)
 // go element by element.  Nothing but the elements the rule names is written; of the batch, only the genes' own bases are read.
-// (k_label_bases walks pieces, rows and seams the same way, in its own words: written once over an element source, the walk made
-// the padded instances of this kernel slower, profiles/device_rows_kernel_stats.md.  A change to the seam logic belongs in both.)
+// (k_label_bases and k_gene_windows, gene_windows.inl, walk pieces, rows and seams the same way, each in its own words: written once
+// over an element source, the walk made the padded instances of this kernel slower, profiles/device_rows_kernel_stats.md.  A change
+// to the seam logic belongs in all three.)
 template <int EB, bool PADDED>
 __global__ void __launch_bounds__(kRowThreads)
 k_translate_tokens(const TokArgs a) {

@@ -2086,9 +2086,31 @@ cdef class GeneFinder:
         return self._find_tensor_batch("find_labels_batch", sequences, labels, out, stream, translate, training_infos, regions, circular, sets,
                                        trim_terminal_repeats)
 
+    def find_windows_batch(self, object sequences, object windows, *, object out=None, object stream=None, bint translate=False,
+                           object training_infos=None, object regions=None, object circular=None, object sets=None,
+                           object trim_terminal_repeats=None):
+        """`find_genes_batch`, and the nucleotides of every gene or of a region around it left in device memory as token ids, one
+        row per gene in the gene's own reading direction: returns `(genes, device_windows)`, the list of `Genes` that
+        `find_genes_batch` returns for the same arguments and a `DeviceWindows`.
+
+        `windows`: a `GeneWindows` -- where a window begins and ends against the gene's start and end, bases or codons, vocabulary,
+        special tokens, element type, padded or ragged layout.  The tensor is written on the device while the batch is resident, on
+        the batch the finder called: row (or slice) g is gene g of the request, contig after contig (`device_windows.gene_begin`);
+        a window wraps at the origin of a circular contig, reads `outside` beyond the ends of a linear one, and with
+        `trim_terminal_repeats` a trimmed record is read in its trimmed coordinates.  `out`: the device tensor to write (anything
+        with `__cuda_array_interface__`), `None`: a torch tensor allocated under torch's current stream; `stream`: the stream that
+        last used `out`.  Every option of `find_genes_batch` applies and `sequences` may be a `DeviceSequences`.  The request is a
+        device call of its own: one tensor per request, so a request that `training_infos` would split into several device calls
+        is a `ValueError`."""
+        if not isinstance(windows, _cabi.GeneWindows):
+            raise TypeError("`windows` must be a GeneWindows, not %r" % type(windows).__name__)
+        return self._find_tensor_batch("find_windows_batch", sequences, windows, out, stream, translate, training_infos, regions, circular, sets,
+                                       trim_terminal_repeats)
+
     cdef tuple _find_tensor_batch(self, str method, object sequences, object spec, object out, object stream, bint translate,
                                   object training_infos, object regions, object circular, object sets, object trim_terminal_repeats):
-        """`find_proteins_batch` / `find_labels_batch`: (the `Genes` of `find_genes_batch`, what the rule `spec` wrote on the device)."""
+        """`find_proteins_batch` / `find_labels_batch` / `find_windows_batch`: (the `Genes` of `find_genes_batch`, what the rule `spec`
+        wrote on the device)."""
         cdef dict tok = {"spec": spec, "out": out, "stream": stream, "result": None, "method": method}
         cdef list circ, tr_search
         cdef object dev, set_ids, tr_params
