@@ -515,6 +515,88 @@ int pga_gene_windows(pga_ctx*, const pga_batch*, int64_t n_genes, const pga_gene
                      void* d_out /* device memory of the context's device */, int64_t n_out_elems,
                      void* stream /* hipStream_t, NULL = the null stream */, int64_t* len_out /* [n_genes], host */);
 
+/* Every candidate start site of a gene record's ORF, with its scores under the winning model, left on the device as three tensors:
+ * positives and hard negatives for a translation-initiation-site model, the input of a re-ranker of the starts or of a start-correction
+ * step in the same process.  Nothing but 8 bytes per gene comes to the host.
+ *   The record.  Gene record g lies on contig i of the batch whose result the context has on record.  On record means: the last finder
+ *     call on the context kept its node arena on the device, with want_nodes 1 or PGA_NODES_DEVICE.  This is exactly the condition
+ *     PGA_RENDER_SCO has.
+ *   Candidates.  Let x = start_ndx be the record's start node within that contig's node arrays.  The candidates of g are all nodes of
+ *     contig i that satisfy three conditions: the node is not a stop node (type != 3); strand == strand[x]; stop_val == stop_val[x].
+ *   Row order.  Rows run in reading direction, outermost (longest ORF) first: ascending ndx on the forward strand, descending ndx on the
+ *     reverse strand.
+ *   Row data.  n_g >= 1 is the number of candidates in the row.  chosen_g is the index of node x within the row.
+ *   Values per candidate node y.  These are the values pga_result.nodes reports with want_nodes = 1: in single mode the *_dp fields, in
+ *     meta mode the fresh re-score, as write_scores prints them.
+ *       position = ndx[y] + 1.  This is the begin the gene would have with this start on the forward strand, and the end on the reverse
+ *         strand.
+ *       type = edge[y] ? 3 : type[y] & 3.  The codes are 0 ATG, 1 GTG, 2 TTG, 3 Edge.
+ *       scores: F columns in the caller's order, drawn from PGA_START_TOTAL (cscore + sscore, added in double), PGA_START_CSCORE,
+ *         _SSCORE, _RSCORE, _USCORE, _TSCORE, and PGA_START_GC_CONT.  A float32 tensor holds the double value rounded once to nearest.
+ *   Two calls.  The row lengths are sizes the host cannot compute from the gene records, so the call is split.
+ *     pga_start_plan_create validates the records, puts the arena in sorted order (the order of the start-score file), finds every
+ *     gene's group, and brings home count_out[g] = n_g and chosen_out[g] = chosen_g.  The plan holds the device memory the second step
+ *     needs: a block the context keeps and hands to the next plan once this one is freed, so a steady run of create / write / free
+ *     allocates nothing.  The plan remembers which recorded result it belongs to.
+ *     pga_start_plan_write writes the three tensors.  It returns PGA_EINVAL if a later finder call, stage call, training or model load
+ *     has replaced the recorded result.  A plan may be written more than once, with other options.
+ *     pga_start_plan_nodes brings home, for every candidate in ragged order, its index in the contig's node arrays (4 bytes per
+ *     candidate): the start_ndx a gene record of that candidate has.  It reads the plan alone, so it works after the recorded result
+ *     has been replaced.
+ *     pga_start_plan_free gives the block back.  pga_destroy orphans the plans that still live: such a plan can only be freed.
+ *   Layouts.  PGA_TOKENS_RAGGED: positions [T], types [T] and scores [T, F], with T = sum n_g; gene g owns candidates off[g] ..
+ *     off[g + 1], off the exclusive scan of n_g.  Nothing at or beyond T is written.  PGA_TOKENS_PADDED: [G, W], [G, W] and [G, W, F]
+ *     with a row stride S >= W >= max n_g, counted in candidates for all three tensors.  All G x W candidates are written: values
+ *     first, then index_pad (positions, types) and score_pad (every column).  Candidates W .. S of a row are untouched.
+ *   Elements.  positions and types are int32 or int64 (index_bytes 4 or 8), scores float32 or float64 (score_bytes 4 or 8).  The
+ *     outputs need only be element-aligned.
+ *   Refusals.  PGA_EINVAL, with pga_last_error naming the gene or field.  pga_start_plan_create, on the host before anything is
+ *     launched: no node arena on record for this batch (the test the score renderer applies); a batch with a contig flagged circular
+ *     or trimmed by trim_terminal_repeats (the nodes of a circle live in the rotated contig's coordinates); a record that names no
+ *     contig of the batch; start_ndx or stop_ndx outside the contig's nodes.  Three checks read the arena, which lies on the device,
+ *     so the look-up kernel makes them and reports with the counts, before any tensor is touched: a start_ndx node that is a stop
+ *     node; a strand that differs from the record's; ndx + 1 that differs from the record's begin (forward) or end (reverse).
+ *     pga_start_plan_write, on the host before anything is launched: element widths; pads that do not fit the element type; an
+ *     unknown or repeated field; W below the longest row; the sizes against the layout; the alignment of the outputs; and the
+ *     device-pointer query on every output.
+ *   Ordering and concurrency.  pga_start_plan_write follows pga_translate_genes_tokens: it waits for what `stream` holds, and on return
+ *     the tensors are complete for any stream.  pga_start_plan_create runs on the context's own stream and shares the renderer's
+ *     scratch, so it follows pga_render_genes.  No call that runs the finder may run on the context between the two.
+ *   The result depends on the arguments alone.
+ * Gene records come from the host, in any subset or order.  They need not be genes the finder called: any start node of the record's
+ * contig makes a valid record. */
+#define PGA_START_TOTAL   0
+#define PGA_START_CSCORE  1
+#define PGA_START_SSCORE  2
+#define PGA_START_RSCORE  3
+#define PGA_START_USCORE  4
+#define PGA_START_TSCORE  5
+#define PGA_START_GC_CONT 6
+typedef struct pga_start_opts {
+    int32_t index_bytes;        /* 4 or 8: positions and types */
+    int32_t score_bytes;        /* 4 or 8: float32 or float64 */
+    int32_t layout;             /* PGA_TOKENS_RAGGED or PGA_TOKENS_PADDED */
+    int32_t n_fields;           /* F, 1 .. 7 */
+    int64_t row_width;          /* W in candidates, padded layout (ignored for ragged) */
+    int64_t row_stride;         /* S in candidates, padded layout (ignored for ragged) */
+    int32_t fields[7];          /* PGA_START_*: the first n_fields are read, none twice */
+    int32_t _pad;
+    int64_t index_pad;          /* padded layout: positions and types behind a row's candidates */
+    double  score_pad;          /* padded layout: every score column behind a row's candidates */
+} pga_start_opts;
+typedef struct pga_start_plan pga_start_plan;
+int  pga_start_plan_create(pga_ctx*, const pga_batch*, int64_t n_genes, const pga_gene* genes, pga_start_plan** plan,
+                           int32_t* count_out /* [n_genes], host */, int32_t* chosen_out /* [n_genes], host */);
+int  pga_start_plan_write(pga_ctx*, const pga_start_plan*, const pga_start_opts*, void* d_positions, void* d_types, void* d_scores,
+                          int64_t n_positions, int64_t n_types, int64_t n_scores /* elements of each */,
+                          void* stream /* hipStream_t, NULL = the null stream */);
+int  pga_start_plan_nodes(pga_ctx*, const pga_start_plan*, int32_t* node_out /* [n_out >= T], host */, int64_t n_out);
+void pga_start_plan_free(pga_ctx* /* unused: the plan knows its context */, pga_start_plan*);
+/* `bytes` of device memory of the context's device to the host (what DeviceStarts.records() reads positions with): waits for what
+ * `stream` holds first.  PGA_EINVAL when the runtime does not call d_src device memory.  The context may be NULL -- a result that
+ * outlives the call that made it reads its tensor this way: the pointer then names its device, and no message is kept. */
+int  pga_device_read(pga_ctx*, const void* d_src, int64_t bytes, void* dst, void* stream /* hipStream_t, NULL = the null stream */);
+
 /* ---- text output ------------------------------------------------------------------ */
 /* GFF, protein FASTA, gene FASTA, GenBank and the start-score file of gene records, rendered on the device from a resident
  * batch: byte for byte what the host writers Genes.write_gff / write_translations / write_genes / write_genbank / write_scores

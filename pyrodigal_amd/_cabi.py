@@ -29,6 +29,7 @@ EXPORTS = [
     "pga_debug_poison",
     "pga_batch_create_device", "pga_batch_read",
     "pga_translate_genes_tokens", "pga_label_bases", "pga_gene_windows",
+    "pga_start_plan_create", "pga_start_plan_write", "pga_start_plan_nodes", "pga_start_plan_free", "pga_device_read",
 ]
 STAGE_EXTRACT, STAGE_SCORE, STAGE_OVERLAP, STAGE_SEQUENCE = 1, 2, 3, 4
 
@@ -118,6 +119,12 @@ class WindowOpts(ctypes.Structure):
                 ("ids", ctypes.c_int64 * 66), ("bos", ctypes.c_int64), ("eos", ctypes.c_int64), ("pad", ctypes.c_int64)]
 
 
+class StartOpts(ctypes.Structure):
+    _fields_ = [("index_bytes", ctypes.c_int32), ("score_bytes", ctypes.c_int32), ("layout", ctypes.c_int32), ("n_fields", ctypes.c_int32),
+                ("row_width", ctypes.c_int64), ("row_stride", ctypes.c_int64), ("fields", ctypes.c_int32 * 7), ("_pad", ctypes.c_int32),
+                ("index_pad", ctypes.c_int64), ("score_pad", ctypes.c_double)]
+
+
 TOKENS_RAGGED, TOKENS_PADDED = 0, 1                         # pga_token_opts.layout
 WINDOW_BASES, WINDOW_CODONS = 0, 1                          # pga_window_opts.unit
 WINDOW_START, WINDOW_END = 0, 1                             # pga_window_opts.from_anchor / to_anchor
@@ -204,6 +211,15 @@ def load():
     L.pga_label_bases.argtypes = [vp, vp, i64, vp, _P(LabelOpts), vp, i64, vp, vp]
     L.pga_gene_windows.restype = ctypes.c_int
     L.pga_gene_windows.argtypes = [vp, vp, i64, vp, _P(WindowOpts), vp, i64, vp, vp]
+    L.pga_start_plan_create.restype = ctypes.c_int
+    L.pga_start_plan_create.argtypes = [vp, vp, i64, vp, _P(vp), vp, vp]
+    L.pga_start_plan_write.restype = ctypes.c_int
+    L.pga_start_plan_write.argtypes = [vp, vp, _P(StartOpts), vp, vp, vp, i64, i64, i64, vp]
+    L.pga_start_plan_nodes.restype = ctypes.c_int
+    L.pga_start_plan_nodes.argtypes = [vp, vp, vp, i64]
+    L.pga_start_plan_free.restype = None; L.pga_start_plan_free.argtypes = [vp, vp]
+    L.pga_device_read.restype = ctypes.c_int
+    L.pga_device_read.argtypes = [vp, vp, i64, vp, vp]
     L.pga_render_genes.restype = ctypes.c_int
     L.pga_render_genes.argtypes = [vp, vp, vp, i64, vp, vp, vp, vp, _P(RenderOpts), _P(_P(RenderResult))]
     L.pga_render_free.restype = None; L.pga_render_free.argtypes = [_P(RenderResult)]
@@ -1188,7 +1204,7 @@ def _token_id(value, name):
 
 
 class _TensorRule:
-    """What ProteinTokens, BaseLabels and GeneWindows share: the element type and layout of the device tensor, value semantics over ``_key()``,
+    """What ProteinTokens, BaseLabels and GeneWindows share (StartCandidates, with two element types, takes the value semantics): the element type and layout of the device tensor, value semantics over ``_key()``,
     and the head of the options struct.  A subclass says what one row is (``row`` and its ``unit``), what it needs of every contig
     of the batch (``per_contig``: ``"tables"`` or ``"lengths"``), and has ``write``, the call on raw handles with just that."""
 
@@ -1781,6 +1797,348 @@ def _gene_windows(self, batch, result_or_genes, spec, out=None, stream=None):
     return windows_into(self.L, self.h, batch.h, self.device, batch.n, genes, spec, out, stream)
 
 
+START_FIELDS = ("total", "cscore", "sscore", "rscore", "uscore", "tscore", "gc_cont")      # PGA_START_* order
+START_TYPES = ("ATG", "GTG", "TTG", "Edge")                                                # the codes of DeviceStarts.types
+_START_INDEX_DTYPES = {"int32": (4, "<i4"), "int64": (8, "<i8")}
+_START_SCORE_DTYPES = {"float32": (4, "<f4"), "float64": (8, "<f8")}
+_NO_START_CANDIDATES = ("start candidates are not available for circular sequences or with trim_terminal_repeats: the nodes of a "
+                        "circle live in the coordinates of the rotated sequence, as for write_scores (-s cannot be combined with "
+                        "--circular either: the start file is not written for circular sequences)")
+
+
+class StartCandidates(_TensorRule):
+    """How ``start_candidates`` / ``find_starts_batch`` write every candidate start site of a gene's ORF into three device tensors
+    (``pga_start_opts``; the rule is in ``pyrodigal_amd.h``): ``positions``, ``types`` (0 ATG, 1 GTG, 2 TTG, 3 Edge) and ``scores``,
+    one candidate after the other in the gene's reading direction, outermost first.
+
+    ``fields``: the score columns, in order, out of ``total`` (``cscore + sscore``), ``cscore``, ``sscore``, ``rscore``, ``uscore``,
+    ``tscore`` and ``gc_cont``; none twice.  ``dtype``: ``"float32"`` or ``"float64"``, the scores; ``index_dtype``: ``"int32"`` or
+    ``"int64"``, positions and types.  ``layout``: ``"ragged"`` (``[T]``, ``[T]``, ``[T, F]``) or ``"padded"`` (``[G, W]``, ``[G, W]``,
+    ``[G, W, F]``), which needs ``pad`` (positions and types behind a row's candidates) and ``score_pad`` (the scores there; NaN is
+    fine).  Everything that needs no device is checked here.  Hashable and picklable."""
+
+    def __init__(self, fields=START_FIELDS, *, dtype="float32", index_dtype="int64", layout="ragged", pad=None, score_pad=None):
+        if isinstance(fields, str):
+            fields = (fields,)
+        fields = tuple(fields)
+        if not 1 <= len(fields) <= len(START_FIELDS):
+            raise ValueError(f"fields names {len(fields)} columns: 1 to {len(START_FIELDS)} are possible")
+        for k, f in enumerate(fields):
+            if f not in START_FIELDS:
+                raise ValueError("field %r is not one of %s" % (f, ", ".join(START_FIELDS)))
+            if f in fields[:k]:
+                raise ValueError(f"field {f!r} occurs twice")
+        dtype = dtype if isinstance(dtype, str) else np.dtype(dtype).name
+        index_dtype = index_dtype if isinstance(index_dtype, str) else np.dtype(index_dtype).name
+        if dtype not in _START_SCORE_DTYPES:
+            raise ValueError(f"dtype must be float32 or float64, not {dtype!r}")
+        if index_dtype not in _START_INDEX_DTYPES:
+            raise ValueError(f"index_dtype must be int32 or int64, not {index_dtype!r}")
+        if layout not in ("padded", "ragged"):
+            raise ValueError(f"layout must be \"padded\" or \"ragged\", not {layout!r}")
+        if layout == "padded" and (pad is None or score_pad is None):
+            raise ValueError("the padded layout needs `pad` and `score_pad`, what fills the rows behind their candidates")
+        pad = 0 if pad is None else _token_id(pad, "pad")
+        if isinstance(score_pad, bool) or not (score_pad is None or isinstance(score_pad, (int, float, np.integer, np.floating))):
+            raise TypeError(f"score_pad must be a number, not {type(score_pad).__name__}")
+        score_pad = 0.0 if score_pad is None else float(score_pad)
+        if index_dtype == "int32" and not -(1 << 31) <= pad < (1 << 31):
+            raise ValueError(f"pad, {pad}, does not fit int32")
+        if not -(1 << 63) <= pad < (1 << 63):
+            raise ValueError(f"pad, {pad}, does not fit int64")
+        if dtype == "float32" and np.isfinite(score_pad) and abs(score_pad) > float(np.finfo(np.float32).max):
+            raise ValueError(f"score_pad, {score_pad}, does not fit float32")
+        self.fields, self.dtype, self.index_dtype, self.layout, self.pad, self.score_pad = fields, dtype, index_dtype, layout, pad, score_pad
+
+    row, unit, per_contig = "gene", "candidates", "lengths"
+    needs_nodes = True                       # the finder keeps the node arena on the device for this rule (PGA_NODES_DEVICE)
+    score_bytes = property(lambda self: _START_SCORE_DTYPES[self.dtype][0])
+    index_bytes = property(lambda self: _START_INDEX_DTYPES[self.index_dtype][0])
+    score_typestr = property(lambda self: _START_SCORE_DTYPES[self.dtype][1])
+    index_typestr = property(lambda self: _START_INDEX_DTYPES[self.index_dtype][1])
+
+    def write(self, L, ctx_h, batch_h, device, genes, lengths, out=None, stream=None):
+        # (the finder's call: its context goes back to the pool when the request returns, so nothing of it may stay with the result)
+        return starts_into(L, ctx_h, batch_h, device, len(lengths), genes, self, out, stream, keep_plan=False)
+
+    def _key(self):
+        # (NaN is a legitimate score_pad and is not equal to itself: the key holds its bits)
+        return (self.fields, self.dtype, self.index_dtype, self.layout, self.pad, np.float64(self.score_pad).tobytes())
+
+    def __reduce__(self):
+        return _start_candidates_from_key, (self._key(),)
+
+    def __repr__(self):
+        return "pyrodigal_amd.StartCandidates(%r, dtype=%r, index_dtype=%r, layout=%r, pad=%r, score_pad=%r)" % (
+            self.fields, self.dtype, self.index_dtype, self.layout, self.pad, self.score_pad)
+
+    def opts(self, row_width=0, row_stride=0):
+        o = StartOpts()
+        o.index_bytes, o.score_bytes = self.index_bytes, self.score_bytes
+        o.layout = TOKENS_PADDED if self.layout == "padded" else TOKENS_RAGGED
+        o.n_fields, o.row_width, o.row_stride = len(self.fields), int(row_width), int(row_stride)
+        for k, f in enumerate(self.fields):
+            o.fields[k] = START_FIELDS.index(f)
+        o.index_pad, o.score_pad = self.pad, self.score_pad
+        return o
+
+
+def _start_candidates_from_key(key):
+    s = StartCandidates.__new__(StartCandidates)
+    s.fields, s.dtype, s.index_dtype, s.layout, s.pad, pad_bits = key
+    s.score_pad = float(np.frombuffer(pad_bits, np.float64)[0])
+    return s
+
+
+class _ContigStarts:
+    """``DeviceStarts.starts``: entry i is ``(positions, types, scores)`` of contig i's genes, views of the three tensors -- no copy."""
+
+    def __init__(self, owner):
+        self.owner = owner
+
+    def __len__(self):
+        return len(self.owner.gene_begin) - 1
+
+    def __getitem__(self, i):
+        d = self.owner
+        i = range(len(self))[i]
+        a, b = int(d.gene_begin[i]), int(d.gene_begin[i + 1])
+        if d.offsets is not None:
+            a, b = int(d.offsets[a]), int(d.offsets[b])
+        return d.positions[a:b], d.types[a:b], d.scores[a:b]
+
+
+class DeviceStarts:
+    """The candidate start sites of gene records in device memory.  ``positions``, ``types`` (``[T]`` ragged, ``[G, W]`` padded) and
+    ``scores`` (``[T, F]`` / ``[G, W, F]``, the columns ``fields``): the tensors; ``lengths``: the candidates of every gene, and
+    ``chosen``: the index of the record's own start among them (numpy int64, host); ``offsets``: ragged only, gene g owns candidates
+    ``offsets[g] .. offsets[g + 1]``; ``gene_begin``: the genes of contig i are rows ``gene_begin[i] .. gene_begin[i + 1]`` (``None``
+    when the records were not in contig order); ``starts[i]``: contig i's part of the three tensors as views."""
+
+    def __init__(self, positions, types, scores, chosen, lengths, offsets, gene_begin, genes, fields, device, plan=None, stream=None,
+                 nodes=None):
+        self.positions, self.types, self.scores, self.chosen, self.lengths = positions, types, scores, chosen, lengths
+        self.offsets, self.gene_begin, self.genes, self.fields, self.device = offsets, gene_begin, genes, fields, device
+        # the node index of every candidate: on the host already (the finder's call), or still behind the plan (a Context's call)
+        self.stream, self._plan, self._nodes, self._records = stream, plan, nodes, None
+
+    @property
+    def starts(self):
+        if self.gene_begin is None:
+            raise ValueError("the gene records were not in contig order: there are no per-contig views")
+        return _ContigStarts(self)
+
+    def cu_seqlens(self):
+        """The exclusive scan of ``lengths`` as an int32 tensor on the tensors' device (torch)."""
+        return _cu_seqlens(self.lengths, self.positions, self.device)
+
+    def records(self):
+        """One ``GENE_DTYPE`` record per candidate, in row order: the gene's record with ``begin`` / ``start_ndx`` (forward) or ``end`` /
+        ``start_ndx`` (reverse) replaced by the candidate's.  ``positions`` comes to the host once for it, and so does the node index
+        of every candidate (4 bytes each, ``pga_start_plan_nodes``).  The records go straight into ``Context.gene_windows`` for the
+        sequence context of every candidate, or back into ``start_candidates``."""
+        if self._records is None:
+            if self._plan is None and self._nodes is None:
+                raise ValueError("this DeviceStarts was released: it has no records any more")
+            lens = self.lengths
+            if self._nodes is None:
+                self._nodes = self._plan.nodes(int(lens.sum()))
+            pos = _read_device(self.positions, self.stream)       # the tensor's elements, host: [T], or [G, W]
+            if self.offsets is None:                               # padded: the first lengths[g] candidates of every row
+                pos = pos[np.arange(pos.shape[1])[None, :] < lens[:, None]] if len(lens) else pos.reshape(0)
+            pos = pos[:int(lens.sum())].astype(np.int64)
+            out = self.genes[np.repeat(np.arange(len(lens)), lens)].copy()
+            fwd = out["strand"] == 1
+            out["begin"] = np.where(fwd, pos, out["begin"])
+            out["end"] = np.where(fwd, out["end"], pos)
+            out["start_ndx"] = self._nodes
+            self._records = out
+            self.release()
+        return self._records
+
+    def release(self):
+        """Gives the plan's device block back to its context now, not when this object is collected (a result of
+        ``Context.start_candidates``: one of ``find_starts_batch`` holds no plan)."""
+        if self._plan is not None:
+            self._plan.close()
+            self._plan = None
+
+
+class _StartPlan:
+    """A ``pga_start_plan`` and the context it was made on: freed when the object is collected.  ``owner``: the :class:`Context`
+    of ``Context.start_candidates``, whose caller owns it and makes one call on it at a time; it is kept alive with the plan, since
+    ``nodes`` goes through the context.  (A plan whose context was destroyed first is an orphan of the library's: freeing it is all
+    that still works.)  The finder's pooled contexts never leave a plan behind: ``starts_into(..., keep_plan=False)``."""
+
+    def __init__(self, L, ctx_h, h, owner=None):
+        self.L, self.ctx_h, self.h, self.owner = L, ctx_h, h, owner
+
+    def _context(self):
+        if self.h is None or (isinstance(self.owner, Context) and self.owner.h is None):
+            raise ValueError("the context that made this DeviceStarts was closed")
+        return self.ctx_h
+
+    def nodes(self, total):
+        self._context()
+        out = np.zeros(max(total, 1), np.int32)
+        rc = self.L.pga_start_plan_nodes(self.ctx_h, self.h, ctypes.c_void_p(out.ctypes.data), total)
+        if rc != PGA_OK:
+            _raise(self.L, self.ctx_h, rc, "pga_start_plan_nodes")
+        return out[:total]
+
+    def close(self):
+        if self.h is not None:
+            self.L.pga_start_plan_free(self.ctx_h, self.h)
+            self.h = None
+
+    def __del__(self):
+        self.close()
+
+
+def _read_device(tensor, stream):
+    """The elements of a device tensor with a contiguous last dimension as a numpy array of its shape (``pga_device_read`` without a
+    context: the pointer names its device)."""
+    cai = tensor.__cuda_array_interface__
+    shape, dt = tuple(int(x) for x in cai["shape"]), np.dtype(str(cai["typestr"]))
+    strides = cai.get("strides")
+    row = shape[-1] if strides is None or len(shape) < 2 else int(strides[0]) // dt.itemsize
+    n = ((shape[0] - 1) * row + shape[1] if shape[0] and shape[1] else 0) if len(shape) == 2 else shape[0]
+    flat = np.zeros(max(n, 1) if len(shape) == 1 else max(shape[0] * row, 1), dt)    # one buffer: whole rows, their gaps included
+    ptr = cai["data"][0]
+    rc = load().pga_device_read(None, ctypes.c_void_p(int(ptr) if ptr else 0), n * dt.itemsize, ctypes.c_void_p(flat.ctypes.data),
+                                ctypes.c_void_p(DeviceSequences._stream_of(tensor, stream)))
+    if rc == PGA_EINVAL:
+        raise ValueError("pga_device_read: the tensor is not device memory")
+    if rc != PGA_OK:
+        raise PgaError(f"pga_device_read failed (code {rc})")
+    if len(shape) == 1:
+        return flat[:n]
+    return flat[:shape[0] * row].reshape(shape[0], row)[:, :shape[1]]
+
+
+def _start_outputs(spec, out, stream, device, lens):
+    """The three device tensors of a :class:`StartCandidates` call: ``out`` checked against the rule's element types and layout and
+    against ``lens``, the candidates of every gene, or new torch tensors under torch's current stream.  Returns (the triple, stream,
+    their pointers, W, S, the elements of each the layout may use)."""
+    n, padded, F = len(lens), spec.layout == "padded", len(spec.fields)
+    total, longest = int(lens.sum()) if n else 0, int(lens.max()) if n else 0
+    if out is None:
+        try:
+            import torch
+        except ImportError:
+            raise TypeError("torch is not installed: pass out=, three device arrays with __cuda_array_interface__") from None
+        with torch.cuda.device(device):
+            shape = (n, longest) if padded else (total,)
+            out = (torch.empty(shape, dtype=getattr(torch, spec.index_dtype), device="cuda"),
+                   torch.empty(shape, dtype=getattr(torch, spec.index_dtype), device="cuda"),
+                   torch.empty(shape + (F,), dtype=getattr(torch, spec.dtype), device="cuda"))
+            if stream is None:
+                stream = int(torch.cuda.current_stream().cuda_stream)
+    try:
+        positions, types, scores = out
+    except (TypeError, ValueError):
+        raise TypeError("out must be a (positions, types, scores) triple of device arrays") from None
+    ptrs, n_elems, width, stride = [], [], 0, None
+    for name, t, typestr, eb, cols in (("positions", positions, spec.index_typestr, spec.index_bytes, 1),
+                                       ("types", types, spec.index_typestr, spec.index_bytes, 1),
+                                       ("scores", scores, spec.score_typestr, spec.score_bytes, F)):
+        cai = getattr(t, "__cuda_array_interface__", None)
+        if not isinstance(cai, dict):
+            raise TypeError("%s must have a __cuda_array_interface__ (a device tensor or array), not %r" % (name, type(t).__name__))
+        if str(cai.get("typestr")) != typestr:
+            raise TypeError(f"{name} has dtype {cai.get('typestr')}: the rule writes {typestr}")
+        shape = tuple(int(x) for x in cai["shape"])
+        strides = cai.get("strides")
+        strides = None if strides is None else tuple(int(x) for x in strides)
+        want_dims = (2 if padded else 1) + (cols > 1 or name == "scores")
+        if len(shape) != want_dims or (name == "scores" and shape[-1] != F):
+            raise ValueError("%s must be %s, not of shape %s" % (name, ("[%d, W" % n if padded else "[T") + (", %d]" % F if name == "scores" else "]"), shape))
+        inner = shape[-1] if name == "scores" else 1                   # elements of one candidate
+        if strides is not None:
+            if name == "scores" and F > 1 and strides[-1] != eb:
+                raise ValueError("the last dimension of scores is not contiguous")
+            cand = strides[-2] if name == "scores" else strides[-1]    # bytes from a candidate to the next
+            if shape[-2 if name == "scores" else -1] > 1 and cand != eb * inner:
+                raise ValueError(f"the candidates of {name} are not contiguous")
+        if padded:
+            if shape[0] != n:
+                raise ValueError(f"the padded layout needs {n} rows: {name} has {shape[0]}")
+            w = shape[1]
+            s_ = w if strides is None or n < 2 else strides[0] // (eb * inner)
+            if strides is not None and n > 1 and (strides[0] % (eb * inner) or strides[0] < 0):
+                raise ValueError(f"the rows of {name} do not lie a whole, positive number of candidates apart")
+            if w < longest:
+                raise ValueError(f"{name} has {w} columns: gene {int(np.argmax(lens))} has {longest} candidates")
+            if stride is None:
+                width, stride = w, s_
+            elif (w, s_) != (width, stride) and n > 0:
+                raise ValueError(f"{name} has {w} columns a stride of {s_} apart: positions has {width}, {stride} apart")
+            n_elems.append(((n - 1) * s_ + w if n else 0) * inner)
+        else:
+            if shape[0] < total:
+                raise ValueError(f"{name} has {shape[0]} candidates: the genes have {total}")
+            n_elems.append(shape[0] * inner)
+        ptr = cai["data"][0]
+        ptrs.append(ctypes.c_void_p(int(ptr) if ptr else 0))
+    return (positions, types, scores), stream, ptrs, width, stride or 0, n_elems
+
+
+def starts_into(L, ctx_h, batch_h, device, n_contigs, genes, spec, out=None, stream=None, owner=None, keep_plan=True):
+    """``pga_start_plan_create`` / ``pga_start_plan_write`` on raw handles (what ``Context.start_candidates`` and the finder's device
+    call share): the candidate starts of ``genes`` (GENE_DTYPE records of the resident batch whose node arrays the context has on
+    record) into ``out``, or into new torch tensors."""
+    if not isinstance(spec, StartCandidates):
+        raise TypeError("the start rule must be a StartCandidates, not %r" % type(spec).__name__)
+    genes = np.ascontiguousarray(genes, dtype=GENE_DTYPE)
+    n = len(genes)
+    count, chosen = np.zeros(max(n, 1), np.int32), np.zeros(max(n, 1), np.int32)
+    h = ctypes.c_void_p()
+    rc = L.pga_start_plan_create(ctx_h, batch_h, n, ctypes.c_void_p(genes.ctypes.data), ctypes.byref(h), ctypes.c_void_p(count.ctypes.data),
+                                 ctypes.c_void_p(chosen.ctypes.data))
+    if rc != PGA_OK:
+        _raise(L, ctx_h, rc, "pga_start_plan_create")
+    plan = _StartPlan(L, ctx_h, h, owner)
+    lens = count[:n].astype(np.int64)
+    nodes = None
+    try:
+        out, stream, ptrs, width, stride, n_elems = _start_outputs(spec, out, stream, device, lens)
+        o = spec.opts(width, stride)
+        rc = L.pga_start_plan_write(ctx_h, plan.h, ctypes.byref(o), ptrs[0], ptrs[1], ptrs[2], n_elems[0], n_elems[1], n_elems[2],
+                                    ctypes.c_void_p(DeviceSequences._stream_of(out[0], stream)))
+        if rc != PGA_OK:
+            _raise(L, ctx_h, rc, "pga_start_plan_write")
+        if not keep_plan:                                          # the node indices now, 4 bytes per candidate
+            nodes = plan.nodes(int(lens.sum()))
+    except BaseException:
+        # the plan never outlives a failed call: a traceback would keep it past the point where a pooled context changes hands
+        plan.close()
+        raise
+    if not keep_plan:
+        plan.close()
+        plan = None
+    off = None
+    if spec.layout == "ragged":
+        off = np.zeros(n + 1, np.int64)
+        np.cumsum(lens, out=off[1:])
+    gene_begin = None
+    if n == 0 or np.all(np.diff(genes["contig"]) >= 0):
+        gene_begin = np.searchsorted(genes["contig"], np.arange(n_contigs + 1)).astype(np.int64)
+    return DeviceStarts(out[0], out[1], out[2], chosen[:n].astype(np.int64), lens, off, gene_begin, genes, spec.fields, device, plan, stream,
+                        nodes)
+
+
+def _start_candidates(self, batch, result_or_genes, spec, out=None, stream=None):
+    """Every candidate start site of gene records of the resident ``batch`` -- all start nodes of the record's ORF, with their scores
+    under the winning model -- as three device tensors (``pga_start_plan_create`` / ``pga_start_plan_write``): 8 bytes per gene come to
+    the host.  The last ``find_genes`` on this context must have been on ``batch`` with ``want_nodes="device"`` (or True).
+    ``result_or_genes``: that result, or gene records of it (any subset or order; any start node of a contig makes a record).
+    ``spec``: a :class:`StartCandidates`.  ``out``: a ``(positions, types, scores)`` triple of objects with
+    ``__cuda_array_interface__``, ``None``: torch tensors are allocated on the context's device under torch's current stream.
+    ``stream``: the stream that last used ``out``, as in :class:`DeviceSequences`.  Returns a :class:`DeviceStarts`."""
+    genes = getattr(result_or_genes, "genes", result_or_genes)
+    return starts_into(self.L, self.h, batch.h, self.device, batch.n, genes, spec, out, stream, owner=self)
+
+
 class RenderedText:
     """One format's text of a :meth:`Context.render_genes` call: ``data`` (bytes), ``contig_offsets`` (contig i is
     ``data[contig_offsets[i]:contig_offsets[i + 1]]``), ``fallback`` (lines the host rendered itself) and ``kernel_ms`` (device
@@ -1993,6 +2351,7 @@ Context.translate_genes = _translate_genes
 Context.translate_tokens = _translate_tokens
 Context.label_bases = _label_bases
 Context.gene_windows = _gene_windows
+Context.start_candidates = _start_candidates
 Context.train = _train
 Context.train_batch = _train_batch
 Context.upload = _upload

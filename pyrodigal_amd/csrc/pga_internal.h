@@ -198,8 +198,33 @@ struct DevNodes {
     std::vector<int32_t> n;                       // per contig: its nodes (0: no model won)
     std::vector<int64_t> len;                     // per contig: sequence length (a batch freed and another made at its address is refused)
     DevNodeArrays a{};
-    void clear() { contigs = nullptr; batch = nullptr; total = 0; off.clear(); n.clear(); len.clear(); a = DevNodeArrays{}; }
+    uint64_t serial = 0;                          // counts the clears: a start plan (translate.hip) belongs to the record it was made on
+    void clear() { contigs = nullptr; batch = nullptr; total = 0; off.clear(); n.clear(); len.clear(); a = DevNodeArrays{}; serial++; }
 };
+
+// The kept nodes in stopcmp_nodes order (render.hip): what the start-score file and the start candidates (start_candidates.inl) share.
+// The sort key of a kept node: contig, stop_val (edge starts lie up to 3 outside [0, seqlen)), + before -; stop nodes last.
+__host__ __device__ inline uint64_t pga_node_order_key(const int n_contigs, const int contig, const int type, const int32_t stop_val, const int strand) {
+    if (type == PGA_T_STOP) return (uint64_t)n_contigs << 33;
+    int64_t sv = (int64_t)stop_val + 16;
+    sv = sv < 0 ? 0 : (sv > 0xffffffffll ? 0xffffffffll : sv);
+    return ((uint64_t)contig << 33) | ((uint64_t)sv << 1) | (strand == 1 ? 0u : 1u);
+}
+// naoff[c] / ncum[c]: arena offset of contig c's nodes and the nodes of the contigs before it (n_contigs + 1 entries each, device).
+// skey / sval (n_nodes entries each, device) hold the sorted keys and the arena index of every sorted row on return -- they are
+// skey2 / sval2 then: the sort writes there.  srow[c] (n_contigs + 1, device): the first sorted row of contig c, srow[n_contigs] =
+// start nodes in all.  The sort is stable and the arena is in ndx order within a contig, so the rows of one key are in ndx order.
+struct NodeOrder {
+    DevNodeArrays nd; const int64_t* naoff; const int64_t* ncum;
+    uint64_t* skey; uint32_t* sval; uint64_t* skey2; uint32_t* sval2; int64_t* srow;
+    int64_t n_nodes; int32_t n_contigs;
+};
+size_t pga_node_order_temp_bytes(int64_t n_nodes, int n_contigs, hipStream_t st);
+hipError_t pga_node_order(NodeOrder& o, void* tmp, size_t tmp_bytes, hipStream_t st);   // launches only: nothing is waited for
+// the test the start-score file applies: nullptr when the context has the node arrays of `batch` (and of the result `contigs`, when
+// one is named) on record, else why not
+struct ContigDesc;
+const char* pga_dev_nodes_refusal(const pga_ctx* c, const void* batch, int n_contigs, const ContigDesc* ct, const pga_contig_result* contigs);
 
 struct pga_ctx {
     int device = 0;
@@ -220,6 +245,9 @@ struct pga_ctx {
     char* render_text = nullptr; size_t render_text_cap = 0;
     char* render_host = nullptr; size_t render_host_cap = 0;
     unsigned long long* render_small = nullptr;
+    // pga_start_plan_create (translate.hip): device blocks that plans give back when they are freed, and the next plan takes
+    std::vector<std::pair<char*, size_t>> start_blocks;
+    std::vector<struct pga_start_plan*> start_plans;   // the plans that live: orphaned by pga_destroy
     DevNodes dev_nodes;                                // the last finder call's node arrays, when it kept them (want_nodes != 0)
     std::vector<int32_t> last_cuts;                    // pga_circular_cuts: the cut of every contig of the last pga_find_genes / _models call (empty: all linear)
     // contig sets, of the last pga_find_genes call when its batch carried labels (empty: it carried none)
@@ -231,6 +259,8 @@ struct pga_ctx {
     std::vector<int64_t> render_seqnums;               // pga_render_seqnums: the seqnum of every contig of the batches rendered next (empty: first_seqnum + i)
 };
 void pga_render_release(pga_ctx*);   // render.hip: frees the buffers above
+hipError_t pga_render_scratch(pga_ctx*, size_t bytes, char** d);   // render.hip: render_dev, grown to at least `bytes`
+void pga_start_release(pga_ctx*);    // translate.hip: frees start_blocks, orphans start_plans
 // summary of a segmented launch's flags (host copy, [PGA_SEG_ROUNDS][stride]) into pga_ctx::dp_stats
 void pga_dp_note_stats(pga_ctx* c, const DpSegPlan* plan, const int32_t* h_flags, int stride);
 

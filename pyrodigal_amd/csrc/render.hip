@@ -468,26 +468,19 @@ __global__ void __launch_bounds__(256) k_gbk_origin(const RenderArgs a) {
 // Units of contig c: its header at c + srow[c] (with the final blank line when the contig has no start node), row r at
 // contig + 1 + r.  Rows r >= srow[n_contigs] (the stop nodes, sorted last) are empty units at n_contigs + r.
 
-// the sort key of every kept node: contig, stop_val (edge starts lie up to 3 outside [0, seqlen)), + before -; stop nodes last
-__global__ void __launch_bounds__(256) k_sco_keys(const RenderArgs a) {
+// the sort key of every kept node (pga_node_order_key) and its arena index
+__global__ void __launch_bounds__(256) k_sco_keys(const NodeOrder a) {
     const int64_t v = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (v >= a.n_nodes) return;
     int lo = 0, hi = a.n_contigs - 1;           // last c with ncum[c] <= v
     while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (a.ncum[mid] <= v) lo = mid; else hi = mid - 1; }
     const int64_t x = a.naoff[lo] + (v - a.ncum[lo]);
-    uint64_t key;
-    if (a.nd.type[x] == 3) key = (uint64_t)a.n_contigs << 33;
-    else {
-        int64_t sv = (int64_t)a.nd.stop_val[x] + 16;
-        sv = sv < 0 ? 0 : (sv > 0xffffffffll ? 0xffffffffll : sv);
-        key = ((uint64_t)lo << 33) | ((uint64_t)sv << 1) | (a.nd.strand[x] == 1 ? 0u : 1u);
-    }
-    a.skey[v] = key;
+    a.skey[v] = pga_node_order_key(a.n_contigs, lo, a.nd.type[x], a.nd.stop_val[x], a.nd.strand[x]);
     a.sval[v] = (uint32_t)x;
 }
 
 // srow[c] = first sorted row of contig c, srow[n_contigs] = start nodes in all (every entry is written by exactly one thread)
-__global__ void __launch_bounds__(256) k_sco_bounds(const RenderArgs a) {
+__global__ void __launch_bounds__(256) k_sco_bounds(const NodeOrder a) {
     const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (r > a.n_nodes) return;
     const int64_t cr = r < a.n_nodes ? (int64_t)(a.skey[r] >> 33) : a.n_contigs;
@@ -598,6 +591,54 @@ static hipError_t grow(char*& p, size_t& cap, const size_t need, const bool pinn
     return e;
 }
 
+hipError_t pga_render_scratch(pga_ctx* c, const size_t bytes, char** d) {
+    const hipError_t e = grow(c->render_dev, c->render_dev_cap, bytes, false);
+    *d = c->render_dev;
+    return e;
+}
+
+// ---- the kept nodes in stopcmp_nodes order: keys, a stable radix sort, where every contig's rows begin ----
+static int node_order_bits(const int n_contigs) {
+    int bits = 33;
+    while (bits < 64 && ((uint64_t)n_contigs >> (bits - 33)) != 0) bits++;
+    return bits;
+}
+
+size_t pga_node_order_temp_bytes(const int64_t n_nodes, const int n_contigs, hipStream_t st) {
+    size_t b = 0;
+    if (n_nodes > 0)
+        hipcub::DeviceRadixSort::SortPairs(nullptr, b, (uint64_t*)nullptr, (uint64_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr,
+                                           (int)n_nodes, 0, node_order_bits(n_contigs), st);
+    return b;
+}
+
+hipError_t pga_node_order(NodeOrder& o, void* tmp, size_t tmp_bytes, hipStream_t st) {
+    const int64_t NN = o.n_nodes;
+    auto blocks = [](const int64_t n) { return dim3((unsigned)((n + 255) / 256)); };
+    hipError_t e = hipSuccess;
+    if (NN > 0) {
+        hipLaunchKernelGGL(k_sco_keys, blocks(NN), dim3(256), 0, st, o);
+        e = hipGetLastError();
+        if (e == hipSuccess)
+            e = hipcub::DeviceRadixSort::SortPairs(tmp, tmp_bytes, o.skey, o.skey2, o.sval, o.sval2, (int)NN, 0, node_order_bits(o.n_contigs), st);
+        o.skey = o.skey2; o.sval = o.sval2;
+    }
+    if (e == hipSuccess) { hipLaunchKernelGGL(k_sco_bounds, blocks(NN + 1), dim3(256), 0, st, o); e = hipGetLastError(); }
+    return e;
+}
+
+const char* pga_dev_nodes_refusal(const pga_ctx* c, const void* batch, const int n_contigs, const ContigDesc* ct, const pga_contig_result* contigs) {
+    const DevNodes& DN = c->dev_nodes;
+    if (!DN.contigs || (contigs && DN.contigs != contigs) || DN.batch != batch || (int)DN.n.size() != n_contigs)
+        return "no node arrays of this result on the device: find the genes with want_nodes = PGA_NODES_DEVICE (or 1), and render "
+               "before the next call on the context that runs the finder or loads models";
+    for (int i = 0; i < n_contigs; i++)
+        if (DN.len[i] != ct[i].len || DN.off[i] < 0 || DN.n[i] < 0 || DN.off[i] + DN.n[i] > DN.total)
+            return "the batch is not the one the node arrays were found on";
+    if (DN.total >= ((int64_t)1 << 31)) return "more than 2^31 - 1 nodes in one call";
+    return nullptr;
+}
+
 void pga_render_release(pga_ctx* c) {
     if (c->render_dev) hipFree(c->render_dev);
     if (c->render_text) hipFree(c->render_text);
@@ -650,15 +691,8 @@ extern "C" int pga_render_genes(pga_ctx* c, const pga_batch* batch, const pga_co
     if (bv.circular && want_gbk) BAD("GenBank records of circular contigs are written by the host writer (the batch carries pga_batch_set_circular flags)");
     // the start-score file reads the node arrays the last finder call kept on the device: only for that result and batch
     const DevNodes& DN = c->dev_nodes;
-    if (want_sco) {
-        if (!DN.contigs || DN.contigs != contigs || DN.batch != (const void*)batch || (int)DN.n.size() != NC)
-            BAD("no node arrays of this result on the device: find the genes with want_nodes = PGA_NODES_DEVICE (or 1), and render "
-                "before the next call on the context that runs the finder or loads models");
-        for (int i = 0; i < NC; i++)
-            if (DN.len[i] != bv.ct[i].len || DN.off[i] < 0 || DN.n[i] < 0 || DN.off[i] + DN.n[i] > DN.total)
-                BAD("the batch is not the one the node arrays were found on");
-        if (DN.total >= ((int64_t)1 << 31)) BAD("more than 2^31 - 1 nodes in one call");
-    }
+    if (want_sco)
+        if (const char* why = pga_dev_nodes_refusal(c, batch, NC, bv.ct, contigs)) { c->err = std::string("pga_render_genes: ") + why; return PGA_EINVAL; }
     // the layout the kernels rely on: genes of contig i are genes[gene_begin .. + n_genes), contig after contig, inside the contig
     int64_t run = 0;
     std::vector<int64_t> gbeg((size_t)NC + 1);
@@ -711,8 +745,6 @@ extern "C" int pga_render_genes(pga_ctx* c, const pga_batch* batch, const pga_co
     std::vector<int64_t> naoff((size_t)NC + 1, 0), ncum((size_t)NC + 1, 0);
     if (want_sco)
         for (int i = 0; i < NC; i++) { naoff[i] = DN.off[i]; ncum[i + 1] = ncum[i] + DN.n[i]; }
-    int sort_bits = 33;
-    while (sort_bits < 64 && ((uint64_t)NC >> (sort_bits - 33)) != 0) sort_bits++;
 
     pga_render_result* R = new pga_render_result();
     R->n_contigs = NC;
@@ -752,12 +784,7 @@ extern "C" int pga_render_genes(pga_ctx* c, const pga_batch* batch, const pga_co
             scan_bytes = std::max(scan_bytes, b);
         }
     }
-    if (want_sco && NN > 0) {
-        size_t b = 0;
-        hipcub::DeviceRadixSort::SortPairs(nullptr, b, (uint64_t*)nullptr, (uint64_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr,
-                                           (int)NN, 0, sort_bits, st);
-        scan_bytes = std::max(scan_bytes, b);
-    }
+    if (want_sco) scan_bytes = std::max(scan_bytes, pga_node_order_temp_bytes(NN, NC, st));
     o_tmp = o_f; o_f += al(scan_bytes + 1);
     char* d = nullptr;
     char* d_text = nullptr;
@@ -827,17 +854,10 @@ extern "C" int pga_render_genes(pga_ctx* c, const pga_batch* batch, const pga_co
         e = hipEventRecord(ev[f][0], st);
         if (e == hipSuccess) e = hipMemsetAsync(a.len + units[f], 0, sizeof(int64_t), st);
         if (e == hipSuccess && f == 4) {
-            // the rows in stopcmp_nodes order: keys, a stable radix sort, where every contig's rows begin
-            if (NN > 0) {
-                hipLaunchKernelGGL(k_sco_keys, blocks(NN), dim3(256), 0, st, a);
-                size_t tb = scan_bytes;
-                e = hipGetLastError();
-                if (e == hipSuccess)
-                    e = hipcub::DeviceRadixSort::SortPairs(d + o_tmp, tb, a.skey, a.skey2, a.sval, a.sval2, (int)NN, 0, sort_bits, st);
-                a.skey = a.skey2; a.sval = a.sval2;
-                fa[4].skey = a.skey; fa[4].sval = a.sval;
-            }
-            if (e == hipSuccess) { hipLaunchKernelGGL(k_sco_bounds, blocks(NN + 1), dim3(256), 0, st, a); e = hipGetLastError(); }
+            // the rows in stopcmp_nodes order (pga_node_order)
+            NodeOrder no{a.nd, a.naoff, a.ncum, a.skey, a.sval, a.skey2, a.sval2, a.srow, NN, NC};
+            e = pga_node_order(no, d + o_tmp, scan_bytes, st);
+            a.skey = no.skey; a.sval = no.sval;
         }
         if (e == hipSuccess && units[f] > 0) {
             if (f == 0) hipLaunchKernelGGL(k_gff, blocks(units[f]), dim3(256), 0, st, a, 0);

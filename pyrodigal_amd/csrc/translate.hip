@@ -5,9 +5,13 @@
 #include "pipeline.h"
 #include "translate_rules.h"
 
+#include <float.h>
 #include <string.h>
 
 #include <algorithm>
+#include <cmath>
+#include <new>
+#include <numeric>
 #include <string>
 #include <type_traits>
 #include <vector>
@@ -90,6 +94,7 @@ int64_t gene_residues(const pga_gene& G, const int include_stop) {
 #include "translate_tokens.inl"
 #include "label_bases.inl"
 #include "gene_windows.inl"
+#include "start_candidates.inl"
 
 }  // namespace
 
@@ -319,4 +324,265 @@ extern "C" int pga_gene_windows(pga_ctx* c, const pga_batch* batch, int64_t n_ge
             hipLaunchKernelGGL((k_gene_windows<decltype(EB)::value, decltype(PADDED)::value>), grid, block, 0, st, a);
         });
     });
+}
+
+// ---- start candidates (start_candidates.inl) ----------------------------------------------------------------------------------
+struct pga_start_plan {
+    pga_ctx* ctx = nullptr;
+    uint64_t serial = 0;                 // DevNodes::serial of the record the plan was made on
+    const void* batch = nullptr;
+    int64_t n_genes = 0, total = 0;      // T = sum n_g
+    int64_t longest = 0, longest_g = -1;
+    char* dev = nullptr; size_t cap = 0; // the context's block while the plan lives
+    const uint32_t* sval = nullptr; const int2* grp = nullptr; const int64_t* off = nullptr;
+    std::vector<int64_t> h_off;          // the scan of n_g, and the arena offset of every record's contig: pga_start_plan_nodes
+    std::vector<int64_t> h_aoff;
+};
+
+// pga_destroy: the blocks go, and a plan that is still alive is orphaned -- it can only be freed
+void pga_start_release(pga_ctx* c) {
+    for (auto& b : c->start_blocks) if (b.first) hipFree(b.first);
+    c->start_blocks.clear();
+    for (pga_start_plan* p : c->start_plans) { if (p->dev) hipFree(p->dev); p->dev = nullptr; p->cap = 0; p->ctx = nullptr; }
+    c->start_plans.clear();
+}
+
+// a block of at least `need` bytes from the ones freed plans gave back: the smallest that fits, else a new one in the place of the largest
+static hipError_t start_block_take(pga_ctx* c, const size_t need, char** p, size_t* cap) {
+    auto& B = c->start_blocks;
+    int best = -1, largest = -1;
+    for (int k = 0; k < (int)B.size(); k++) {
+        if (B[k].second >= need && (best < 0 || B[k].second < B[best].second)) best = k;
+        if (largest < 0 || B[k].second > B[largest].second) largest = k;
+    }
+    if (best >= 0) { *p = B[best].first; *cap = B[best].second; B.erase(B.begin() + best); return hipSuccess; }
+    if (largest >= 0) { (void)hipFree(B[largest].first); B.erase(B.begin() + largest); }
+    const size_t want = need + need / 4 + 4096;
+    const hipError_t e = hipMalloc((void**)p, want);
+    *cap = e == hipSuccess ? want : 0;
+    return e;
+}
+
+extern "C" void pga_start_plan_free(pga_ctx* c, pga_start_plan* p) {
+    if (!p) return;
+    (void)c;                             // (the plan knows its context, and whether it still exists)
+    if (p->ctx) {
+        auto& live = p->ctx->start_plans;
+        live.erase(std::remove(live.begin(), live.end(), p), live.end());
+        if (p->dev) p->ctx->start_blocks.emplace_back(p->dev, p->cap);
+    }
+    delete p;
+}
+
+extern "C" int pga_start_plan_create(pga_ctx* c, const pga_batch* batch, int64_t n_genes, const pga_gene* genes, pga_start_plan** plan,
+                                     int32_t* count_out, int32_t* chosen_out) {
+    if (plan) *plan = nullptr;
+    if (!c) return PGA_EINVAL;
+    auto bad = [&](const std::string& msg) { c->err = "pga_start_plan_create: " + msg; return PGA_EINVAL; };
+    if (!batch || !plan || n_genes < 0 || (n_genes > 0 && (!genes || !count_out || !chosen_out))) return bad("bad arguments");
+    const pga_batch_view bv = pga_batch_peek(batch);
+    if (bv.ctx != c) return bad("the batch belongs to another context");
+    // ---- validation on the host, before anything is allocated or launched ----
+    if (bv.circular) return bad("the start-score file is not written for circular contigs (the batch carries pga_batch_set_circular flags)");
+    if (const char* why = pga_dev_nodes_refusal(c, batch, bv.n, bv.ct, nullptr)) return bad(why);
+    const DevNodes& DN = c->dev_nodes;
+    const int NC = bv.n;
+    std::vector<StartReq> req((size_t)n_genes);
+    for (int64_t g = 0; g < n_genes; g++) {
+        const pga_gene& G = genes[g];
+        const std::string who = "gene " + std::to_string(g);
+        if (G.contig < 0 || G.contig >= NC) return bad(who + " names contig " + std::to_string(G.contig) + " of " + std::to_string(NC));
+        const int32_t n = DN.n[G.contig];
+        if (G.start_ndx < 0 || G.start_ndx >= n) return bad(who + ": start_ndx = " + std::to_string(G.start_ndx) + " lies outside the " + std::to_string(n) + " nodes of contig " + std::to_string(G.contig));
+        if (G.stop_ndx < 0 || G.stop_ndx >= n) return bad(who + ": stop_ndx = " + std::to_string(G.stop_ndx) + " lies outside the " + std::to_string(n) + " nodes of contig " + std::to_string(G.contig));
+        if (G.strand != 1 && G.strand != -1) return bad(who + ": strand = " + std::to_string((int)G.strand) + " is neither 1 nor -1");
+        req[(size_t)g] = StartReq{G.contig, (int32_t)(DN.off[G.contig] + G.start_ndx), G.strand == 1 ? G.begin : G.end, G.strand};
+    }
+    pga_start_plan* P = new (std::nothrow) pga_start_plan();
+    if (!P) return PGA_ENOMEM;
+    P->ctx = c; P->serial = DN.serial; P->batch = batch; P->n_genes = n_genes;
+    P->h_off.assign((size_t)n_genes + 1, 0); P->h_aoff.resize((size_t)n_genes);
+    for (int64_t g = 0; g < n_genes; g++) P->h_aoff[(size_t)g] = DN.off[genes[g].contig];
+    c->start_plans.push_back(P);
+    if (n_genes == 0) { *plan = P; return PGA_OK; }
+    if (hipSetDevice(c->device) != hipSuccess) { pga_start_plan_free(c, P); return PGA_EDEVICE; }
+    // ---- the plan's block (what the write step reads) and the scratch of this call (the renderer's) ----
+    const int64_t NN = std::accumulate(DN.n.begin(), DN.n.end(), (int64_t)0);      // > 0: a record named a node
+    const size_t G = (size_t)n_genes, nn = (size_t)NN;
+    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
+    const size_t p_off = 0, p_grp = p_off + al(sizeof(int64_t) * (G + 1)), p_sval = p_grp + al(sizeof(int2) * G), p_end = p_sval + al(sizeof(uint32_t) * nn);
+    hipStream_t st = c->stream;
+    const size_t tmp_b = pga_node_order_temp_bytes(NN, NC, st);
+    const size_t s_naoff = 0, s_ncum = s_naoff + al(sizeof(int64_t) * (NC + 1)), s_srow = s_ncum + al(sizeof(int64_t) * (NC + 1));
+    const size_t s_req = s_srow + al(sizeof(int64_t) * (NC + 1)), s_res = s_req + al(sizeof(StartReq) * G), s_skey = s_res + al(sizeof(int2) * G);
+    const size_t s_skey2 = s_skey + al(sizeof(uint64_t) * nn), s_sval = s_skey2 + al(sizeof(uint64_t) * nn), s_tmp = s_sval + al(sizeof(uint32_t) * nn);
+    const size_t s_end = s_tmp + al(tmp_b + 1);
+    char* s = nullptr;
+    hipError_t e = start_block_take(c, p_end, &P->dev, &P->cap);
+    if (e == hipSuccess) e = pga_render_scratch(c, s_end, &s);
+    auto fail = [&](const hipError_t err) {
+        hipStreamSynchronize(st);
+        pga_start_plan_free(c, P);
+        return pga_hip_try_(c, err, "pga_start_plan_create");
+    };
+    if (e != hipSuccess) return fail(e);
+    std::vector<int64_t> naoff((size_t)NC + 1, 0), ncum((size_t)NC + 1, 0);
+    for (int i = 0; i < NC; i++) { naoff[i] = DN.off[i]; ncum[i + 1] = ncum[i] + DN.n[i]; }
+    e = hipMemcpyAsync(s + s_naoff, naoff.data(), sizeof(int64_t) * (NC + 1), hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(s + s_ncum, ncum.data(), sizeof(int64_t) * (NC + 1), hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(s + s_req, req.data(), sizeof(StartReq) * G, hipMemcpyHostToDevice, st);
+    NodeOrder no{DN.a, (const int64_t*)(s + s_naoff), (const int64_t*)(s + s_ncum), (uint64_t*)(s + s_skey), (uint32_t*)(s + s_sval),
+                 (uint64_t*)(s + s_skey2), (uint32_t*)(P->dev + p_sval), (int64_t*)(s + s_srow), NN, NC};
+    if (e == hipSuccess) e = pga_node_order(no, s + s_tmp, tmp_b, st);
+    std::vector<int2> res(G);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(k_start_lookup, dim3((unsigned)((n_genes + kRowThreads - 1) / kRowThreads)), dim3(kRowThreads), 0, st, DN.a,
+                           (const uint64_t*)no.skey, (const uint32_t*)no.sval, (const int64_t*)no.srow, NC, (const StartReq*)(s + s_req), n_genes,
+                           (int2*)(P->dev + p_grp), (int2*)(s + s_res));
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(res.data(), s + s_res, sizeof(int2) * G, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) return fail(e);
+    // ---- what the look-up found: the three checks that read the arena, the counts, their scan ----
+    std::vector<int64_t>& off = P->h_off;
+    for (size_t g = 0; g < G; g++) {
+        const pga_gene& R = genes[g];
+        const std::string who = "gene " + std::to_string(g);
+        if (res[g].x <= 0) {
+            pga_start_plan_free(c, P);
+            switch (-res[g].x) {
+                case kStartIsStop:   return bad(who + ": start_ndx = " + std::to_string(R.start_ndx) + " is a stop node of contig " + std::to_string(R.contig));
+                case kStartStrand:   return bad(who + ": strand = " + std::to_string((int)R.strand) + " is not the strand of node start_ndx = " + std::to_string(R.start_ndx));
+                case kStartPosition: return bad(who + ": " + (R.strand == 1 ? "begin = " + std::to_string(R.begin) : "end = " + std::to_string(R.end)) +
+                                                " is not ndx + 1 of node start_ndx = " + std::to_string(R.start_ndx));
+                default:             return bad(who + ": node start_ndx = " + std::to_string(R.start_ndx) + " was not found in the sorted arena");
+            }
+        }
+        count_out[g] = res[g].x; chosen_out[g] = res[g].y;
+        off[g + 1] = off[g] + res[g].x;
+        if (res[g].x > P->longest) { P->longest = res[g].x; P->longest_g = (int64_t)g; }
+    }
+    e = hipMemcpyAsync(P->dev + p_off, off.data(), sizeof(int64_t) * (G + 1), hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) return fail(e);
+    P->total = off[G];
+    P->off = (const int64_t*)(P->dev + p_off); P->grp = (const int2*)(P->dev + p_grp); P->sval = (const uint32_t*)(P->dev + p_sval);
+    *plan = P;
+    return PGA_OK;
+}
+
+extern "C" int pga_start_plan_write(pga_ctx* c, const pga_start_plan* P, const pga_start_opts* o, void* d_positions, void* d_types, void* d_scores,
+                                    int64_t n_positions, int64_t n_types, int64_t n_scores, void* stream) {
+    if (!c) return PGA_EINVAL;
+    auto bad = [&](const std::string& msg) { c->err = "pga_start_plan_write: " + msg; return PGA_EINVAL; };
+    if (!P || !o || n_positions < 0 || n_types < 0 || n_scores < 0) return bad("bad arguments");
+    if (P->ctx != c) return bad("the plan belongs to another context");
+    // ---- validation: all of it on the host, before anything is launched ----
+    if (o->index_bytes != 4 && o->index_bytes != 8) return bad("index_bytes must be 4 or 8, not " + std::to_string(o->index_bytes));
+    if (o->score_bytes != 4 && o->score_bytes != 8) return bad("score_bytes must be 4 or 8, not " + std::to_string(o->score_bytes));
+    if (o->layout != PGA_TOKENS_RAGGED && o->layout != PGA_TOKENS_PADDED) return bad("layout must be PGA_TOKENS_RAGGED or PGA_TOKENS_PADDED, not " + std::to_string(o->layout));
+    const bool padded = o->layout == PGA_TOKENS_PADDED;
+    if (o->n_fields < 1 || o->n_fields > 7) return bad("n_fields must be 1 .. 7, not " + std::to_string(o->n_fields));
+    for (int k = 0; k < o->n_fields; k++) {
+        if (o->fields[k] < PGA_START_TOTAL || o->fields[k] > PGA_START_GC_CONT) return bad("fields[" + std::to_string(k) + "] = " + std::to_string(o->fields[k]) + " is no PGA_START_* field");
+        for (int j = 0; j < k; j++) if (o->fields[j] == o->fields[k]) return bad("fields[" + std::to_string(k) + "] repeats fields[" + std::to_string(j) + "]");
+    }
+    if (padded) {
+        if (o->index_bytes == 4 && (o->index_pad < INT32_MIN || o->index_pad > INT32_MAX)) return bad("index_pad = " + std::to_string(o->index_pad) + " does not fit int32");
+        if (o->score_bytes == 4 && std::isfinite(o->score_pad) && std::fabs(o->score_pad) > (double)FLT_MAX) return bad("score_pad = " + std::to_string(o->score_pad) + " does not fit float32");
+    }
+    const DevNodes& DN = c->dev_nodes;
+    if (!DN.contigs || DN.serial != P->serial || DN.batch != P->batch)
+        return bad("the node arrays the plan was made on are no longer on record: a later call on the context ran the finder or loaded models");
+    const int64_t G = P->n_genes, F = o->n_fields;
+    int64_t W = 0, S = 0, n_layout = P->total, n_cells = P->total;
+    if (padded) {
+        W = o->row_width; S = o->row_stride;
+        if (W < P->longest) return bad("row_width = " + std::to_string(W) + " is less than the " + std::to_string(P->longest) + " candidates of gene " + std::to_string(P->longest_g));
+        if (W < 0 || S < W) return bad("row_stride = " + std::to_string(S) + " is less than row_width = " + std::to_string(W));
+        if (G > 1 && S > (INT64_MAX / 64 - W) / (G - 1)) return bad("row_stride = " + std::to_string(S) + " is too large");
+        if (G > 0 && W > 0 && W > (INT64_MAX / 64) / G) return bad("row_width = " + std::to_string(W) + " is too large");
+        n_layout = G > 0 ? (G - 1) * S + W : 0;
+        n_cells = G * W;
+    }
+    if (n_positions < n_layout) return bad("n_positions = " + std::to_string(n_positions) + " is less than the " + std::to_string(n_layout) + " elements of the layout");
+    if (n_types < n_layout) return bad("n_types = " + std::to_string(n_types) + " is less than the " + std::to_string(n_layout) + " elements of the layout");
+    if (n_scores < n_layout * F) return bad("n_scores = " + std::to_string(n_scores) + " is less than the " + std::to_string(n_layout * F) + " elements of the layout");
+    if (n_cells == 0) return PGA_OK;
+    const struct { const char* name; void* p; int eb; } outs[3] = {{"d_positions", d_positions, o->index_bytes}, {"d_types", d_types, o->index_bytes}, {"d_scores", d_scores, o->score_bytes}};
+    for (const auto& x : outs) {
+        if (!x.p) return bad(std::string(x.name) + " is NULL");
+        if ((uintptr_t)x.p % (uintptr_t)x.eb) return bad(std::string(x.name) + " is not aligned to its " + std::to_string(x.eb) + "-byte elements");
+    }
+    if (hipSetDevice(c->device) != hipSuccess) return PGA_EDEVICE;
+    for (const auto& x : outs) if (const int rc = pga_device_memory_(c, x.p, "pga_start_plan_write", x.name)) return rc;
+    StartArgs a{};
+    a.nd = DN.a; a.sval = P->sval; a.grp = P->grp; a.off = P->off;
+    a.n_genes = G; a.n_cells = n_cells; a.W = W; a.S = S;
+    a.index_pad = o->index_pad; a.score_pad = o->score_pad;
+    a.n_fields = o->n_fields;
+    for (int k = 0; k < 7; k++) a.fields[k] = k < o->n_fields ? o->fields[k] : 0;
+    a.pos = d_positions; a.typ = d_types; a.sco = d_scores;
+    // the tail of a row call (RowDest::run) without tables to send: behind what the caller's stream holds, complete on return
+    pga_upload_lease L{};
+    { const int rc = pga_upload_lease_take(c, 0, &L); if (rc) return rc; }
+    hipError_t e = hipEventRecord(L.ev, (hipStream_t)stream);
+    if (e == hipSuccess) e = hipStreamWaitEvent(L.st, L.ev, 0);
+    if (e == hipSuccess) {
+        const dim3 grid((unsigned)((n_cells + kRowThreads - 1) / kRowThreads)), block(kRowThreads);
+        auto scores = [&](auto IB, auto PADDED) {
+            if (o->score_bytes == 4) hipLaunchKernelGGL((k_start_candidates<decltype(IB)::value, 4, decltype(PADDED)::value>), grid, block, 0, L.st, a);
+            else hipLaunchKernelGGL((k_start_candidates<decltype(IB)::value, 8, decltype(PADDED)::value>), grid, block, 0, L.st, a);
+        };
+        auto layout = [&](auto IB) { if (padded) scores(IB, std::true_type{}); else scores(IB, std::false_type{}); };
+        if (o->index_bytes == 4) layout(std::integral_constant<int, 4>{}); else layout(std::integral_constant<int, 8>{});
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(L.st);
+    pga_upload_lease_give(c);
+    return pga_hip_try_(c, e, "pga_start_plan_write");
+}
+
+extern "C" int pga_start_plan_nodes(pga_ctx* c, const pga_start_plan* P, int32_t* node_out, int64_t n_out) {
+    if (!c) return PGA_EINVAL;
+    auto bad = [&](const std::string& msg) { c->err = "pga_start_plan_nodes: " + msg; return PGA_EINVAL; };
+    if (!P || n_out < 0) return bad("bad arguments");
+    if (P->ctx != c) return bad("the plan belongs to another context");
+    if (n_out < P->total) return bad("n_out = " + std::to_string(n_out) + " is less than the " + std::to_string(P->total) + " candidates of the plan");
+    if (P->total == 0) return PGA_OK;
+    if (!node_out) return bad("node_out is NULL");
+    if (hipSetDevice(c->device) != hipSuccess) return PGA_EDEVICE;
+    char* s = nullptr;
+    hipError_t e = pga_render_scratch(c, sizeof(uint32_t) * (size_t)P->total, &s);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(k_start_nodes, dim3((unsigned)((P->total + kRowThreads - 1) / kRowThreads)), dim3(kRowThreads), 0, c->stream,
+                           P->sval, P->grp, P->off, P->n_genes, P->total, (uint32_t*)s);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(node_out, s, sizeof(uint32_t) * (size_t)P->total, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e != hipSuccess) return pga_hip_try_(c, e, "pga_start_plan_nodes");
+    for (int64_t g = 0; g < P->n_genes; g++)            // arena index -> index in the contig's node arrays
+        for (int64_t k = P->h_off[(size_t)g]; k < P->h_off[(size_t)g + 1]; k++) node_out[k] = (int32_t)((int64_t)(uint32_t)node_out[k] - P->h_aoff[(size_t)g]);
+    return PGA_OK;
+}
+
+extern "C" int pga_device_read(pga_ctx* c, const void* d_src, int64_t bytes, void* dst, void* stream) {
+    if (bytes < 0 || (bytes > 0 && (!d_src || !dst))) { if (c) c->err = "pga_device_read: bad arguments"; return PGA_EINVAL; }
+    if (bytes == 0) return PGA_OK;
+    if (!c) {
+        // without a context (a result that outlives the call that made it): the pointer names its device, and no message is kept
+        hipPointerAttribute_t at{};
+        if (hipPointerGetAttributes(&at, d_src) != hipSuccess) { (void)hipGetLastError(); return PGA_EINVAL; }
+        if (at.type != hipMemoryTypeDevice) return PGA_EINVAL;
+        if (hipSetDevice(at.device) != hipSuccess) return PGA_EDEVICE;
+        if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess) return PGA_EDEVICE;
+        return hipMemcpy(dst, d_src, (size_t)bytes, hipMemcpyDeviceToHost) == hipSuccess ? PGA_OK : PGA_EDEVICE;
+    }
+    if (hipSetDevice(c->device) != hipSuccess) return PGA_EDEVICE;
+    if (const int rc = pga_device_memory_(c, d_src, "pga_device_read", "d_src")) return rc;
+    hipError_t e = hipStreamSynchronize((hipStream_t)stream);
+    if (e == hipSuccess) e = hipMemcpy(dst, d_src, (size_t)bytes, hipMemcpyDeviceToHost);
+    return pga_hip_try_(c, e, "pga_device_read");
 }

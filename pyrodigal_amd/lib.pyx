@@ -2107,9 +2107,34 @@ cdef class GeneFinder:
         return self._find_tensor_batch("find_windows_batch", sequences, windows, out, stream, translate, training_infos, regions, circular, sets,
                                        trim_terminal_repeats)
 
+    def find_starts_batch(self, object sequences, object starts, *, object out=None, object stream=None, bint translate=False,
+                          object training_infos=None, object regions=None, object circular=None, object sets=None,
+                          object trim_terminal_repeats=None):
+        """`find_genes_batch`, and every candidate start site of every gene left in device memory: returns `(genes, device_starts)`,
+        the list of `Genes` that `find_genes_batch` returns for the same arguments and a `DeviceStarts`.
+
+        `starts`: a `StartCandidates` -- the score columns, element types, ragged or padded layout.  For gene g of the request, contig
+        after contig (`device_starts.gene_begin`), the tensors hold all start nodes of its ORF in reading direction, outermost first,
+        with their position, start codon type and scores under the winning model; `device_starts.chosen[g]` is the start the finder
+        chose.  They are written while the request still holds its context, from the node arrays the finder left on the device: the
+        call keeps them there (`PGA_NODES_DEVICE`) also when the finder was created with `keep_nodes=False`.  `out`: a `(positions,
+        types, scores)` triple of device tensors to write (anything with `__cuda_array_interface__`), `None`: torch tensors
+        allocated under torch's current stream; `stream`: the stream that last used `out`.  Every option of `find_genes_batch`
+        applies but `circular` and `trim_terminal_repeats` (the nodes of a circle live in the coordinates of the rotated sequence, as
+        for `write_scores`), and `sequences` may be a `DeviceSequences`.  The request is a device call of its own: one set of
+        tensors per request, so a request that `training_infos` would split into several device calls is a `ValueError`."""
+        if not isinstance(starts, _cabi.StartCandidates):
+            raise TypeError("`starts` must be a StartCandidates, not %r" % type(starts).__name__)
+        if circular is not None and circular is not False and circular is not True:
+            circular = [bool(x) for x in circular]        # (a list that flags nothing asks for nothing: as in find_genes_batch)
+        if (circular is True or (circular and any(circular))) or (trim_terminal_repeats is not None and trim_terminal_repeats is not False):
+            raise ValueError("find_starts_batch: " + _cabi._NO_START_CANDIDATES)
+        return self._find_tensor_batch("find_starts_batch", sequences, starts, out, stream, translate, training_infos, regions, circular, sets,
+                                       None)
+
     cdef tuple _find_tensor_batch(self, str method, object sequences, object spec, object out, object stream, bint translate,
                                   object training_infos, object regions, object circular, object sets, object trim_terminal_repeats):
-        """`find_proteins_batch` / `find_labels_batch` / `find_windows_batch`: (the `Genes` of `find_genes_batch`, what the rule `spec`
+        """`find_proteins_batch` / `find_labels_batch` / `find_windows_batch` / `find_starts_batch`: (the `Genes` of `find_genes_batch`, what the rule `spec`
         wrote on the device)."""
         cdef dict tok = {"spec": spec, "out": out, "stream": stream, "result": None, "method": method}
         cdef list circ, tr_search
@@ -2408,6 +2433,8 @@ cdef class GeneFinder:
         p.closed = self.closed; p.min_gene = self.min_gene; p.min_edge_gene = self.min_edge_gene
         p.max_overlap = self.max_overlap; p.meta = self.meta; p.want_nodes = self.keep_nodes
         p.mask = self.mask; p.min_mask = self.min_mask
+        if o.tok is not None and getattr(o.tok["spec"], "needs_nodes", False) and not self.keep_nodes:
+            p.want_nodes = 2                         # PGA_NODES_DEVICE: the rule reads the node arrays, and only on the device
         try:
             if dev is None:
                 ptrs = <const char**> malloc(sizeof(char*) * max(n, 1))
