@@ -515,6 +515,51 @@ int pga_gene_windows(pga_ctx*, const pga_batch*, int64_t n_genes, const pga_gene
                      void* d_out /* device memory of the context's device */, int64_t n_out_elems,
                      void* stream /* hipStream_t, NULL = the null stream */, int64_t* len_out /* [n_genes], host */);
 
+/* The k-mers of every contig, or of every gene record, counted into integer vectors on the device, one row per contig or per gene:
+ * tetranucleotide frequencies for binning, codon usage, in-frame dicodon counts, amino-acid composition for a model in the same
+ * process.  Only the letters the rows name are read; nothing comes to the host.
+ *   Letters and codes.  A letter reads A, C, G, T in either case; anything else reads N.  This is the reading of pga_gene_windows.
+ *     The code of a k-mer c0 c1 .. c(k-1) is sum c_j * 4^(k-1-j) with A, C, G, T = 0, 1, 2, 3.  This is the public ACGT order, first
+ *     base most significant.  GeneWindows uses the same order for codons (16 c0 + 4 c1 + c2).  A window that holds an N is not
+ *     counted.  1 <= k <= 6.
+ *   Rows.  L is the length the batch holds for a contig.  After trim_terminal_repeats it is the trimmed length.  There are three
+ *     kinds of row.
+ *     PGA_COUNT_CONTIG: one row per contig, forward strand as stored.  step must be 1.  A linear contig has window starts
+ *       p = 0 .. L-k (none if L < k).  A contig flagged circular has p = 0 .. L-1.  Base j of a window is read at (p + j) mod L.  If
+ *       L < k there are no windows.
+ *     PGA_COUNT_GENE: one row per gene record [b, e], n = e - b + 1.  The gene is read in its own direction: complemented on the
+ *       reverse strand, and wrapped modulo L on a circle when e > L.  This is exactly the axis q(t) of pga_gene_windows.  Window
+ *       starts are t = 0, step, 2*step, .. while t + k <= n.  Windows lie wholly inside the gene.  step is 1 or 3.  k = 3, step = 3
+ *       is codon usage, including the start and stop codon the record holds.  k = 6, step = 3 is in-frame dicodons.  Records come
+ *       from the host, in any subset or order.  The record checks are those of pga_label_bases.
+ *     PGA_COUNT_CONTIG_GENES: one row per contig.  It is the sum of the PGA_COUNT_GENE rows of the records given on that contig, and
+ *       zero where there are none.  It uses the same kernel, with the contig's row as destination.
+ *   Bins.  The caller passes bin_of_code: 4^k int32 entries in [-1, n_bins).  -1 means the window is not counted.  n_bins <= 4096.
+ *     The identity table gives the plain counts.
+ *   Output.  d_out holds int32, [R, S] row-major with S = row_stride >= n_bins.  Elements 0 .. n_bins-1 of every row are set to the
+ *     counts.  Whatever the tensor held before does not matter.  Elements n_bins .. S-1 are untouched.  d_out need only be 4-byte
+ *     aligned.  win_out[r] (host, int64) is the number of window positions of row r, whether counted or not.  It is host arithmetic.
+ *   Validation.  Everything is checked on the host before anything is allocated or launched.  A failure returns PGA_EINVAL and
+ *     pga_last_error names the field or gene.  The checks are: k, step and the row kind; the table's range; S and n_out_elems; the
+ *     record checks of pga_label_bases; a row whose window positions exceed INT32_MAX; the alignment of d_out and the device-pointer
+ *     query on it.
+ *   Ordering and concurrency.  Those of pga_translate_genes_tokens.  The result depends on the arguments alone.
+ * pga_kmer_counts_chunk: the window starts of one piece of work (for tests that straddle it). */
+#define PGA_COUNT_CONTIG       0
+#define PGA_COUNT_GENE         1
+#define PGA_COUNT_CONTIG_GENES 2
+typedef struct pga_count_opts {
+    int32_t rows;                 /* PGA_COUNT_CONTIG / PGA_COUNT_GENE / PGA_COUNT_CONTIG_GENES */
+    int32_t k, step, n_bins;
+    int64_t row_stride;           /* S */
+    const int32_t* bin_of_code;   /* host, 4^k entries */
+} pga_count_opts;
+int pga_count_kmers(pga_ctx*, const pga_batch*, int64_t n_genes, const pga_gene* genes /* ignored for PGA_COUNT_CONTIG */,
+                    const pga_count_opts*, void* d_out /* device memory of the context's device */, int64_t n_out_elems,
+                    void* stream /* hipStream_t, NULL = the null stream */,
+                    int64_t* win_out /* [R]: n_genes for PGA_COUNT_GENE, else the contigs of the batch; host */);
+int pga_kmer_counts_chunk(void);
+
 /* Every candidate start site of a gene record's ORF, with its scores under the winning model, left on the device as three tensors:
  * positives and hard negatives for a translation-initiation-site model, the input of a re-ranker of the starts or of a start-correction
  * step in the same process.  Nothing but 8 bytes per gene comes to the host.

@@ -30,6 +30,7 @@ EXPORTS = [
     "pga_batch_create_device", "pga_batch_read",
     "pga_translate_genes_tokens", "pga_label_bases", "pga_gene_windows",
     "pga_start_plan_create", "pga_start_plan_write", "pga_start_plan_nodes", "pga_start_plan_free", "pga_device_read",
+    "pga_count_kmers", "pga_kmer_counts_chunk",
 ]
 STAGE_EXTRACT, STAGE_SCORE, STAGE_OVERLAP, STAGE_SEQUENCE = 1, 2, 3, 4
 
@@ -119,6 +120,11 @@ class WindowOpts(ctypes.Structure):
                 ("ids", ctypes.c_int64 * 66), ("bos", ctypes.c_int64), ("eos", ctypes.c_int64), ("pad", ctypes.c_int64)]
 
 
+class CountOpts(ctypes.Structure):
+    _fields_ = [("rows", ctypes.c_int32), ("k", ctypes.c_int32), ("step", ctypes.c_int32), ("n_bins", ctypes.c_int32),
+                ("row_stride", ctypes.c_int64), ("bin_of_code", ctypes.c_void_p)]
+
+
 class StartOpts(ctypes.Structure):
     _fields_ = [("index_bytes", ctypes.c_int32), ("score_bytes", ctypes.c_int32), ("layout", ctypes.c_int32), ("n_fields", ctypes.c_int32),
                 ("row_width", ctypes.c_int64), ("row_stride", ctypes.c_int64), ("fields", ctypes.c_int32 * 7), ("_pad", ctypes.c_int32),
@@ -128,6 +134,7 @@ class StartOpts(ctypes.Structure):
 TOKENS_RAGGED, TOKENS_PADDED = 0, 1                         # pga_token_opts.layout
 WINDOW_BASES, WINDOW_CODONS = 0, 1                          # pga_window_opts.unit
 WINDOW_START, WINDOW_END = 0, 1                             # pga_window_opts.from_anchor / to_anchor
+COUNT_CONTIG, COUNT_GENE, COUNT_CONTIG_GENES = 0, 1, 2      # pga_count_opts.rows
 TOKEN_NONE = -(1 << 63)                                     # pga_token_opts.bos / eos: no such token
 RENDER_FORMATS = ("gff", "faa", "fna", "gbk", "scores")     # PGA_RENDER_* bit order
 NODES_DEVICE = 2                                            # pga_params.want_nodes: keep the node arrays on the device
@@ -211,6 +218,9 @@ def load():
     L.pga_label_bases.argtypes = [vp, vp, i64, vp, _P(LabelOpts), vp, i64, vp, vp]
     L.pga_gene_windows.restype = ctypes.c_int
     L.pga_gene_windows.argtypes = [vp, vp, i64, vp, _P(WindowOpts), vp, i64, vp, vp]
+    L.pga_count_kmers.restype = ctypes.c_int
+    L.pga_count_kmers.argtypes = [vp, vp, i64, vp, _P(CountOpts), vp, i64, vp, vp]
+    L.pga_kmer_counts_chunk.restype = ctypes.c_int; L.pga_kmer_counts_chunk.argtypes = []
     L.pga_start_plan_create.restype = ctypes.c_int
     L.pga_start_plan_create.argtypes = [vp, vp, i64, vp, _P(vp), vp, vp]
     L.pga_start_plan_write.restype = ctypes.c_int
@@ -1204,7 +1214,7 @@ def _token_id(value, name):
 
 
 class _TensorRule:
-    """What ProteinTokens, BaseLabels and GeneWindows share (StartCandidates, with two element types, takes the value semantics): the element type and layout of the device tensor, value semantics over ``_key()``,
+    """What ProteinTokens, BaseLabels and GeneWindows share (StartCandidates, with two element types, and KmerCounts, whose rows are always int32 ``[R, n_bins]``, take the value semantics): the element type and layout of the device tensor, value semantics over ``_key()``,
     and the head of the options struct.  A subclass says what one row is (``row`` and its ``unit``), what it needs of every contig
     of the batch (``per_contig``: ``"tables"`` or ``"lengths"``), and has ``write``, the call on raw handles with just that."""
 
@@ -1797,6 +1807,240 @@ def _gene_windows(self, batch, result_or_genes, spec, out=None, stream=None):
     return windows_into(self.L, self.h, batch.h, self.device, batch.n, genes, spec, out, stream)
 
 
+_COUNT_ROWS = {"contig": COUNT_CONTIG, "gene": COUNT_GENE, "contig_genes": COUNT_CONTIG_GENES}
+COUNT_MAX_K, COUNT_MAX_BINS = 6, 4096
+CODON_BIN_LETTERS = AMINO_ACIDS + "*"                        # the 21 bins of KmerCounts.codon_bins, in order
+
+
+def kmer_of_code(code, k):
+    """The k letters of a code in the public ACGT order, first base most significant."""
+    return "".join(WINDOW_LETTERS[(code >> (2 * (k - 1 - j))) & 3] for j in range(k))
+
+
+def kmer_rc(code, k):
+    """The code of the reverse complement of a k-mer's code."""
+    rc = 0
+    for _ in range(k):
+        rc = (rc << 2) | (3 - (code & 3))
+        code >>= 2
+    return rc
+
+
+class KmerCounts(_TensorRule):
+    """How ``kmer_counts`` / ``find_counts_batch`` count the k-mers of contigs or genes into an ``int32`` device tensor, one row of
+    ``n_bins`` counts per contig or per gene (``pga_count_opts``; the rule is in ``pyrodigal_amd.h``).
+
+    ``k``: 1 .. 6.  ``rows``: ``"contig"`` -- every window of the contig's forward strand, across the origin of a circular one;
+    ``"gene"`` -- the windows inside every gene, read in the gene's own direction; ``"contig_genes"`` -- one row per contig, the sum
+    of its genes' rows.  ``step``: 1, or 3 for gene rows: ``k=3, step=3`` is codon usage, ``k=6, step=3`` in-frame dicodons.  A
+    window that holds a letter other than A, C, G, T is not counted.  ``canonical=True`` folds a k-mer with its reverse complement:
+    the bin is the rank of ``min(code, rc(code))`` among the canonical codes in ascending order (136 bins for ``k=4``).  ``bins``: a
+    table of the caller's instead, ``4^k`` integers indexed by the k-mer's code (ACGT order, first base most significant), ``-1`` =
+    not counted.  Everything that needs no device is checked here.  Hashable and picklable."""
+
+    def __init__(self, k=4, *, rows="contig", step=1, canonical=False, bins=None):
+        if isinstance(k, bool) or not isinstance(k, (int, np.integer)):
+            raise TypeError(f"k must be an integer, not {type(k).__name__}")
+        if not 1 <= k <= COUNT_MAX_K:
+            raise ValueError(f"k must be 1 .. {COUNT_MAX_K}, not {k}")
+        if rows not in _COUNT_ROWS:
+            raise ValueError("rows must be \"contig\", \"gene\" or \"contig_genes\", not %r" % (rows,))
+        if isinstance(step, bool) or not isinstance(step, (int, np.integer)):
+            raise TypeError(f"step must be an integer, not {type(step).__name__}")
+        if step not in (1, 3):
+            raise ValueError(f"step must be 1 or 3, not {step}")
+        if rows == "contig" and step != 1:
+            raise ValueError("contig rows count every window: step must be 1 (step = 3 reads a gene's frame)")
+        if not isinstance(canonical, (bool, np.bool_)):
+            raise TypeError(f"canonical must be a bool, not {type(canonical).__name__}")
+        self.k, self.rows, self.step, self.canonical, self.custom = int(k), rows, int(step), bool(canonical), bins is not None
+        n_codes = 4 ** self.k
+        if bins is not None:
+            if canonical:
+                raise ValueError("`bins` and `canonical` exclude each other: a table of the caller's says itself what it folds")
+            table = list(bins)
+            if len(table) != n_codes:
+                raise ValueError(f"bins has {len(table)} entries: k = {self.k} has {n_codes} codes")
+            table = tuple(_token_id(v, f"the bin of {kmer_of_code(x, self.k)}") for x, v in enumerate(table))
+            for x, v in enumerate(table):
+                if not -1 <= v < COUNT_MAX_BINS:
+                    raise ValueError(f"the bin of {kmer_of_code(x, self.k)}, {v}, lies outside -1 .. {COUNT_MAX_BINS - 1}")
+            if max(table) < 0:
+                raise ValueError("bins drops every k-mer: there is nothing to count")
+        elif canonical:
+            rank = {c: r for r, c in enumerate(x for x in range(n_codes) if x <= kmer_rc(x, self.k))}
+            table = tuple(rank[min(x, kmer_rc(x, self.k))] for x in range(n_codes))
+        else:
+            table = tuple(range(n_codes))
+        self.table = table
+        self.n_bins = max(table) + 1
+
+    row, unit, per_contig = "row", "bins", "lengths"
+    dtype, typestr, elem_bytes = "int32", "<i4", 4
+
+    @staticmethod
+    def codon_bins(translation_table=11):
+        """The table of ``bins=`` that counts amino acids: the 64 codons onto 21 bins in the order ``ACDEFGHIKLMNPQRSTVWY*``, by the
+        codon-to-residue map of the translation table -- no initiator rule: a GTG start counts as V."""
+        from .tables import NCBI_CODES
+        if isinstance(translation_table, bool) or not isinstance(translation_table, (int, np.integer)) or translation_table not in NCBI_CODES:
+            raise ValueError("%r is not a valid translation table index" % (translation_table,))
+        code, tcag = NCBI_CODES[int(translation_table)], "TCAG"
+        at = lambda x: tcag.index(WINDOW_LETTERS[x])
+        return tuple(CODON_BIN_LETTERS.index(code[16 * at(a) + 4 * at(b) + at(c)]) for a in range(4) for b in range(4) for c in range(4))
+
+    @property
+    def labels(self):
+        """The k-mer of every bin, for folded bins the smaller member; ``None`` under a table of the caller's."""
+        if self.custom:
+            return None
+        first = {}
+        for x, b in enumerate(self.table):
+            first.setdefault(b, x)
+        return tuple(kmer_of_code(first[b], self.k) for b in range(self.n_bins))
+
+    def write(self, L, ctx_h, batch_h, device, genes, lengths, out=None, stream=None):
+        return counts_into(L, ctx_h, batch_h, device, len(lengths), genes, self, out, stream)
+
+    def _key(self):
+        return (self.k, self.rows, self.step, self.canonical, self.custom, self.table)
+
+    def __reduce__(self):
+        return _kmer_counts_from_key, (self._key(),)
+
+    def __repr__(self):
+        return "pyrodigal_amd.KmerCounts(%d, rows=%r, step=%d, %s)" % (
+            self.k, self.rows, self.step, "bins=<%d codes onto %d bins>" % (len(self.table), self.n_bins) if self.custom else "canonical=%r" % self.canonical)
+
+    def windows(self, genes, lengths, circular=None):
+        """The window positions of every row, counted or not (int64): host arithmetic on the lengths and coordinates, as the library
+        does it.  ``genes``: GENE_DTYPE records (not read for contig rows); ``lengths``: the bases of every contig as the batch holds
+        it; ``circular``: the contigs flagged circular (``None``: none, ``True``: all)."""
+        lengths = np.ascontiguousarray(lengths, np.int64)
+        k, step = self.k, self.step
+        if self.rows == "contig":
+            circ = np.zeros(len(lengths), bool) if circular is None or circular is False else np.broadcast_to(np.asarray(circular, bool), lengths.shape)
+            return np.where(lengths < k, 0, np.where(circ, lengths, lengths - k + 1)).astype(np.int64)
+        n = genes["end"].astype(np.int64) - genes["begin"] + 1
+        w = np.where(n >= k, (n - k) // step + 1, 0).astype(np.int64)
+        if self.rows == "gene":
+            return w
+        out = np.zeros(len(lengths), np.int64)
+        np.add.at(out, genes["contig"].astype(np.int64), w)
+        return out
+
+    def opts(self, row_stride=0):
+        o = CountOpts()
+        o.rows, o.k, o.step, o.n_bins, o.row_stride = _COUNT_ROWS[self.rows], self.k, self.step, self.n_bins, int(row_stride)
+        o._table = np.array(self.table, np.int32)            # (kept alive with the struct)
+        o.bin_of_code = o._table.ctypes.data
+        return o
+
+
+def _kmer_counts_from_key(key):
+    c = KmerCounts.__new__(KmerCounts)
+    c.k, c.rows, c.step, c.canonical, c.custom, c.table = key
+    c.n_bins = max(c.table) + 1
+    return c
+
+
+class _ContigCounts:
+    """``DeviceCounts.counts_of``: entry i is a view of contig i's rows -- its genes' rows, or its own row -- no copy."""
+
+    def __init__(self, owner):
+        self.owner = owner
+
+    def __len__(self):
+        return self.owner.n_contigs
+
+    def __getitem__(self, i):
+        d = self.owner
+        i = range(len(self))[i]
+        if d.rows != "gene":
+            return d.counts[i]
+        return d.counts[int(d.gene_begin[i]):int(d.gene_begin[i + 1])]
+
+
+class DeviceCounts:
+    """K-mer counts of contigs or gene records in device memory.  ``counts``: the tensor, ``[R, n_bins]`` int32 (with ``out=``: the
+    caller's ``[R, S]`` object, of which columns ``0 .. n_bins - 1`` were set); ``windows``: the window positions of every row, counted
+    or not (numpy int64, host): the denominator of a frequency; ``gene_begin``: for gene rows, the genes of contig i are rows
+    ``gene_begin[i] .. gene_begin[i + 1]`` (``None`` when the records were not in contig order, and for rows per contig);
+    ``counts_of[i]``: contig i's gene rows, or its own row, as a view of ``counts``."""
+
+    def __init__(self, counts, windows, gene_begin, rows, n_bins, n_contigs, device):
+        self.counts, self.windows, self.gene_begin, self.rows, self.n_bins = counts, windows, gene_begin, rows, n_bins
+        self.n_contigs, self.device = n_contigs, device
+
+    @property
+    def counts_of(self):
+        if self.rows == "gene" and self.gene_begin is None:
+            raise ValueError("the gene records were not in contig order: there are no per-contig views")
+        return _ContigCounts(self)
+
+
+def counts_into(L, ctx_h, batch_h, device, n_contigs, genes, spec, out=None, stream=None):
+    """``pga_count_kmers`` on raw handles (what ``Context.kmer_counts`` and the finder's device call share): the counts of the
+    contigs of the resident batch, or of ``genes`` (GENE_DTYPE records of it), into ``out`` or into a new torch tensor."""
+    if not isinstance(spec, KmerCounts):
+        raise TypeError("the counting rule must be a KmerCounts, not %r" % type(spec).__name__)
+    genes = np.ascontiguousarray(genes, dtype=GENE_DTYPE)
+    n = len(genes)
+    R = n if spec.rows == "gene" else n_contigs
+    if out is None:
+        try:
+            import torch
+        except ImportError:
+            raise TypeError("torch is not installed: pass out=, a device array with __cuda_array_interface__") from None
+        with torch.cuda.device(device):
+            out = torch.empty((R, spec.n_bins), dtype=torch.int32, device="cuda")
+            if stream is None:
+                stream = int(torch.cuda.current_stream().cuda_stream)
+    cai = getattr(out, "__cuda_array_interface__", None)
+    if not isinstance(cai, dict):
+        raise TypeError("out must have a __cuda_array_interface__ (a device tensor or array), not %r" % type(out).__name__)
+    if str(cai.get("typestr")) != spec.typestr:
+        raise TypeError(f"out has dtype {cai.get('typestr')}: the rule writes int32 ({spec.typestr})")
+    shape = tuple(int(x) for x in cai["shape"])
+    strides = cai.get("strides")
+    strides = None if strides is None else tuple(int(x) for x in strides)
+    if len(shape) != 2 or shape[0] != R:
+        raise ValueError(f"the counts need a [{R}, S] tensor, not one of shape {shape}")
+    if shape[1] < spec.n_bins:
+        raise ValueError(f"out has {shape[1]} columns: the rule has {spec.n_bins} bins")
+    if strides is not None and shape[1] > 1 and strides[1] != 4:
+        raise ValueError("the last dimension of out is not contiguous")
+    if strides is not None and R > 1 and (strides[0] % 4 or strides[0] < 4 * shape[1]):
+        raise ValueError("the rows of out do not lie a whole number of elements apart, at least a row's width")
+    stride = shape[1] if strides is None or R < 2 else strides[0] // 4
+    n_out = (R - 1) * stride + shape[1] if R else 0
+    ptr = cai["data"][0]
+    win_out = np.zeros(max(R, 1), np.int64)
+    o = spec.opts(stride)
+    rc = L.pga_count_kmers(ctx_h, batch_h, n, ctypes.c_void_p(genes.ctypes.data), ctypes.byref(o), ctypes.c_void_p(int(ptr) if ptr else 0), n_out,
+                           ctypes.c_void_p(DeviceSequences._stream_of(out, stream)), ctypes.c_void_p(win_out.ctypes.data))
+    if rc != PGA_OK:
+        _raise(L, ctx_h, rc, "pga_count_kmers")
+    gene_begin = None
+    if spec.rows == "gene" and (n == 0 or np.all(np.diff(genes["contig"]) >= 0)):
+        gene_begin = np.searchsorted(genes["contig"], np.arange(n_contigs + 1)).astype(np.int64)
+    return DeviceCounts(out, win_out[:R], gene_begin, spec.rows, spec.n_bins, n_contigs, device)
+
+
+def _kmer_counts(self, batch, result_or_genes, spec, out=None, stream=None):
+    """The k-mers of the contigs of the resident ``batch``, or of gene records on it, counted into an ``int32`` device tensor, one row
+    per contig or per record (``pga_count_kmers``): nothing of them comes to the host.  ``result_or_genes``: a result of
+    ``find_genes`` on the batch, or gene records of one (any subset or order; ``None`` will do for contig rows).  ``spec``: a
+    :class:`KmerCounts`.  ``out``: any 2-D object with ``__cuda_array_interface__``, ``[R, S >= n_bins]`` int32 with a contiguous
+    last dimension, of which columns ``0 .. n_bins - 1`` are set; ``None``: a ``[R, n_bins]`` torch tensor is allocated on the
+    context's device under torch's current stream.  ``stream``: the stream that last used ``out``, as in :class:`DeviceSequences`.
+    Returns a :class:`DeviceCounts`."""
+    genes = getattr(result_or_genes, "genes", result_or_genes)
+    if genes is None:
+        genes = np.zeros(0, GENE_DTYPE)
+    return counts_into(self.L, self.h, batch.h, self.device, batch.n, genes, spec, out, stream)
+
+
 START_FIELDS = ("total", "cscore", "sscore", "rscore", "uscore", "tscore", "gc_cont")      # PGA_START_* order
 START_TYPES = ("ATG", "GTG", "TTG", "Edge")                                                # the codes of DeviceStarts.types
 _START_INDEX_DTYPES = {"int32": (4, "<i4"), "int64": (8, "<i8")}
@@ -2352,6 +2596,7 @@ Context.translate_tokens = _translate_tokens
 Context.label_bases = _label_bases
 Context.gene_windows = _gene_windows
 Context.start_candidates = _start_candidates
+Context.kmer_counts = _kmer_counts
 Context.train = _train
 Context.train_batch = _train_batch
 Context.upload = _upload

@@ -6,6 +6,7 @@
 #include "translate_rules.h"
 
 #include <float.h>
+#include <stdlib.h>
 #include <string.h>
 
 #include <algorithm>
@@ -94,6 +95,7 @@ int64_t gene_residues(const pga_gene& G, const int include_stop) {
 #include "translate_tokens.inl"
 #include "label_bases.inl"
 #include "gene_windows.inl"
+#include "kmer_counts.inl"
 #include "start_candidates.inl"
 
 }  // namespace
@@ -323,6 +325,127 @@ extern "C" int pga_gene_windows(pga_ctx* c, const pga_batch* batch, int64_t n_ge
         with_elem_layout(d.eb, d.padded, [&](auto EB, auto PADDED) {
             hipLaunchKernelGGL((k_gene_windows<decltype(EB)::value, decltype(PADDED)::value>), grid, block, 0, st, a);
         });
+    });
+}
+
+extern "C" int pga_kmer_counts_chunk(void) { return kCntChunk; }
+
+extern "C" int pga_count_kmers(pga_ctx* c, const pga_batch* batch, int64_t n_genes, const pga_gene* genes, const pga_count_opts* o, void* d_out,
+                               int64_t n_out_elems, void* stream, int64_t* win_out) {
+    if (!c) return PGA_EINVAL;
+    RowDest d{c, "pga_count_kmers"};
+    if (!batch || !o || n_genes < 0 || n_out_elems < 0) return d.bad("bad arguments");
+    const pga_batch_view bv = pga_batch_peek(batch);
+    if (bv.ctx != c) return d.bad("the batch belongs to another context");
+    // ---- validation: all of it on the host, before anything is allocated or launched ----
+    if (o->rows != PGA_COUNT_CONTIG && o->rows != PGA_COUNT_GENE && o->rows != PGA_COUNT_CONTIG_GENES)
+        return d.bad("rows must be PGA_COUNT_CONTIG, PGA_COUNT_GENE or PGA_COUNT_CONTIG_GENES, not " + std::to_string(o->rows));
+    const bool by_contig = o->rows == PGA_COUNT_CONTIG, summed = o->rows == PGA_COUNT_CONTIG_GENES;
+    if (by_contig) n_genes = 0;                                    // (contig rows read no records)
+    if (n_genes > 0 && !genes) return d.bad("bad arguments");
+    const int64_t k = o->k, step = o->step;
+    if (k < 1 || k > 6) return d.bad("k must be 1 .. 6, not " + std::to_string(k));
+    if (by_contig ? step != 1 : (step != 1 && step != 3)) return d.bad(std::string("step must be ") + (by_contig ? "1 for contig rows" : "1 or 3") + ", not " + std::to_string(step));
+    if (o->n_bins < 1 || o->n_bins > kCntMaxBins) return d.bad("n_bins must be 1 .. " + std::to_string(kCntMaxBins) + ", not " + std::to_string(o->n_bins));
+    if (!o->bin_of_code) return d.bad("bin_of_code is NULL");
+    const int n_codes = 1 << (2 * (int)k);
+    for (int x = 0; x < n_codes; x++)
+        if (o->bin_of_code[x] < -1 || o->bin_of_code[x] >= o->n_bins)
+            return d.bad("bin_of_code[" + std::to_string(x) + "] = " + std::to_string(o->bin_of_code[x]) + " lies outside -1 .. n_bins - 1 = " + std::to_string(o->n_bins - 1));
+    const int64_t B = bv.n, R = o->rows == PGA_COUNT_GENE ? n_genes : B, S = o->row_stride, n_bins = o->n_bins;
+    if (R > 0 && !win_out) return d.bad("bad arguments");
+    if (S < n_bins) return d.bad("row_stride = " + std::to_string(S) + " is less than n_bins = " + std::to_string(n_bins));
+    if (R > 1 && S > (INT64_MAX / 8 - n_bins) / (R - 1)) return d.bad("row_stride = " + std::to_string(S) + " is too large");
+    d.eb = 4; d.a.n_rows = R; d.a.n_elems = R > 0 ? (R - 1) * S + n_bins : 0;
+    if (n_out_elems < d.a.n_elems) return d.bad("n_out_elems = " + std::to_string(n_out_elems) + " is less than the " + std::to_string(d.a.n_elems) + " elements of the layout");
+    // the rows of work: a contig each, or a checked record each (the checks of pga_label_bases); the windows of every row of d_out
+    const size_t NW = (size_t)(by_contig ? B : n_genes);
+    if (NW > (size_t)INT32_MAX) return d.bad("more than 2^31 - 1 gene records");
+    std::vector<CntRow> rows(NW);
+    std::vector<int64_t> win((size_t)R, 0);
+    auto windows = [&](const int64_t n) { return n >= k ? (n - k) / step + 1 : (int64_t)0; };
+    for (size_t i = 0; i < NW; i++) {
+        CntRow& w = rows[i];
+        w._pad = 0;
+        if (by_contig) {
+            const ContigDesc& cd = bv.ct[i];
+            const bool circ = bv.circular && bv.circular[i];
+            w.base = cd.base; w.q0 = 0; w.L = cd.len; w.dst = (int32_t)i; w.bits = 1u;
+            w.n_win = (int32_t)(cd.len < k ? 0 : circ ? cd.len : cd.len - k + 1);
+            win[i] = w.n_win;
+            continue;
+        }
+        const pga_gene& G = genes[i];
+        const std::string who = "gene " + std::to_string(i);
+        if (G.contig < 0 || G.contig >= bv.n) return d.bad(who + " names contig " + std::to_string(G.contig) + " of " + std::to_string(bv.n));
+        const int64_t len = bv.ct[G.contig].len, glen = (int64_t)G.end - G.begin + 1;
+        if (G.begin < 1 || G.begin > len || glen < 3 || glen > len) return d.bad(who + " lies outside its contig");
+        if (glen % 3) return d.bad(who + " is " + std::to_string(glen) + " bases long, no whole number of codons");
+        const bool circ = bv.circular && bv.circular[G.contig];
+        if (G.end > len && !circ) return d.bad(who + " ends beyond its contig, which is not flagged circular");
+        const WinRow q = win_row(G, bv.ct[G.contig], circ, 0);
+        w.base = q.base; w.q0 = (int32_t)q.q0; w.L = q.L; w.bits = q.bits & 1u;
+        w.n_win = (int32_t)windows(glen);
+        w.dst = summed ? G.contig : (int32_t)i;
+        win[(size_t)w.dst] += w.n_win;
+    }
+    for (int64_t r = 0; r < R; r++)
+        if (win[(size_t)r] > INT32_MAX)
+            return d.bad(std::string(summed ? "contig " : "row ") + std::to_string(r) + " has " + std::to_string(win[(size_t)r]) + " window positions, more than an int32 count holds");
+    if (const int rc = d.memory(d_out)) return rc;
+    for (int64_t r = 0; r < R; r++) win_out[r] = win[(size_t)r];
+    if (R == 0) return PGA_OK;
+    // ---- the pieces, and the form of the kernel ----
+    // A row of d_out that one piece owns whole is set by that piece; every other row is zeroed on the stream and added to.
+    // PGA_KMER_COUNTS_FORM (lds / direct, with -wave / -group) forces a form for measurements and tests.
+    std::vector<int2> piece;                                     // (row, the first of its window starts)
+    piece.reserve(NW);
+    std::vector<char> cut(NW, 0);                                // the row has more than one piece
+    int64_t total_win = 0;
+    for (size_t i = 0; i < NW; i++) {
+        for (int64_t w = 0; w < rows[i].n_win || (w == 0 && !summed); w += kCntChunk) piece.push_back(make_int2((int)i, (int)w));
+        cut[i] = rows[i].n_win > kCntChunk;
+        total_win += rows[i].n_win;
+    }
+    const int64_t pieces = (int64_t)piece.size();
+    // the forms (DESIGN.md 4.18 has the measurements): without a histogram where the rows are shared and hold few windows under
+    // many bins; a piece per wave where the pieces are short and four histograms fit
+    bool direct = summed && pieces > 0 && total_win / pieces < n_bins / 4;
+    bool per_wave = pieces > 0 && total_win / pieces <= kCntSweep;
+    if (const char* e = getenv("PGA_KMER_COUNTS_FORM")) {
+        if (strstr(e, "direct")) direct = true; else if (strstr(e, "lds")) direct = false;
+        if (strstr(e, "wave")) per_wave = true; else if (strstr(e, "group")) per_wave = false;
+    }
+    if (!direct && 4 * n_bins > kCntMaxBins) per_wave = false;
+    std::vector<int32_t> zero;
+    if (summed || direct) { zero.resize((size_t)R); std::iota(zero.begin(), zero.end(), 0); for (auto& w : rows) w.bits |= 2u; }
+    else for (size_t i = 0; i < NW; i++) if (cut[i]) { rows[i].bits |= 2u; zero.push_back(rows[i].dst); }
+    // ---- the kernel's tables: staged in the upload's pinned area as they will lie on the device, one copy ----
+    auto al = [](const size_t x) { return (x + 15) & ~(size_t)15; };
+    const size_t piece_b = al(sizeof(int2) * piece.size()), row_b = al(sizeof(CntRow) * NW), bin_b = al(sizeof(int32_t) * (size_t)n_codes), z_b = al(sizeof(int32_t) * zero.size());
+    const size_t tab = piece_b + row_b + bin_b + z_b;
+    pga_upload_lease L{};
+    { const int rc = pga_upload_lease_take(c, tab, &L); if (rc) return rc; }
+    memcpy(L.pin, piece.data(), sizeof(int2) * piece.size());
+    memcpy(L.pin + piece_b, rows.data(), sizeof(CntRow) * NW);
+    memcpy(L.pin + piece_b + row_b, o->bin_of_code, sizeof(int32_t) * (size_t)n_codes);
+    memcpy(L.pin + piece_b + row_b + bin_b, zero.data(), sizeof(int32_t) * zero.size());
+    CntArgs a{};
+    a.seq = bv.d_seq; a.piece = (const int2*)L.dev; a.row = (const CntRow*)(L.dev + piece_b);
+    a.bin_of_code = (const int32_t*)(L.dev + piece_b + row_b);
+    a.out = (int32_t*)d_out; a.n_pieces = pieces; a.S = S;
+    a.k = (int32_t)k; a.step = (int32_t)step; a.n_bins = (int32_t)n_bins; a.wide = ((uintptr_t)bv.d_seq & 3u) == 0;
+    const int32_t* d_zero = (const int32_t*)(L.dev + piece_b + row_b + bin_b);
+    const int64_t n_zero = (int64_t)zero.size();
+    return d.run(L, tab, stream, [&](const dim3, const dim3 block, hipStream_t st) {
+        if (n_zero > 0) hipLaunchKernelGGL(k_kmer_zero, dim3((unsigned)((n_zero * n_bins + kRowThreads - 1) / kRowThreads)), block, 0, st, a.out, S, a.n_bins, d_zero, n_zero);
+        if (pieces == 0) return;
+        const dim3 grid((unsigned)(per_wave ? (pieces + 3) / 4 : pieces));
+        const size_t lds = cnt_lds_bytes(direct, per_wave ? 4 : 1, (int)n_bins, n_codes);
+        if (direct && per_wave) hipLaunchKernelGGL((k_kmer_counts<true, 4>), grid, block, lds, st, a);
+        else if (direct) hipLaunchKernelGGL((k_kmer_counts<true, 1>), grid, block, lds, st, a);
+        else if (per_wave) hipLaunchKernelGGL((k_kmer_counts<false, 4>), grid, block, lds, st, a);
+        else hipLaunchKernelGGL((k_kmer_counts<false, 1>), grid, block, lds, st, a);
     });
 }
 

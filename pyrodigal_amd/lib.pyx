@@ -178,34 +178,8 @@ _RBS_SPACER = [
 ]
 _NODE_TYPE = ["ATG", "GTG", "TTG", "Edge"]
 
-# NCBI genetic codes: amino acids of the 64 codons in TCAG order (first base slowest).  Table numbers as in
-# the reference (_translation.h; TRANSLATION_TABLES above).
-_NCBI_CODES = {
-    1: "FFLLSSSSYY**CC*WLLLLPPPPHHQQRRRRIIIMTTTTNNKKSSRRVVVVAAAADDEEGGGG",
-    2: "FFLLSSSSYY**CCWWLLLLPPPPHHQQRRRRIIMMTTTTNNKKSS**VVVVAAAADDEEGGGG",
-    3: "FFLLSSSSYY**CCWWTTTTPPPPHHQQRRRRIIMMTTTTNNKKSSRRVVVVAAAADDEEGGGG",
-    4: "FFLLSSSSYY**CCWWLLLLPPPPHHQQRRRRIIIMTTTTNNKKSSRRVVVVAAAADDEEGGGG",
-    5: "FFLLSSSSYY**CCWWLLLLPPPPHHQQRRRRIIMMTTTTNNKKSSSSVVVVAAAADDEEGGGG",
-    6: "FFLLSSSSYYQQCC*WLLLLPPPPHHQQRRRRIIIMTTTTNNKKSSRRVVVVAAAADDEEGGGG",
-    9: "FFLLSSSSYY**CCWWLLLLPPPPHHQQRRRRIIIMTTTTNNNKSSSSVVVVAAAADDEEGGGG",
-    10: "FFLLSSSSYY**CCCWLLLLPPPPHHQQRRRRIIIMTTTTNNKKSSRRVVVVAAAADDEEGGGG",
-    11: "FFLLSSSSYY**CC*WLLLLPPPPHHQQRRRRIIIMTTTTNNKKSSRRVVVVAAAADDEEGGGG",
-    12: "FFLLSSSSYY**CC*WLLLSPPPPHHQQRRRRIIIMTTTTNNKKSSRRVVVVAAAADDEEGGGG",
-    13: "FFLLSSSSYY**CCWWLLLLPPPPHHQQRRRRIIMMTTTTNNKKSSGGVVVVAAAADDEEGGGG",
-    14: "FFLLSSSSYYY*CCWWLLLLPPPPHHQQRRRRIIIMTTTTNNNKSSSSVVVVAAAADDEEGGGG",
-    15: "FFLLSSSSYY*QCC*WLLLLPPPPHHQQRRRRIIIMTTTTNNKKSSRRVVVVAAAADDEEGGGG",
-    16: "FFLLSSSSYY*LCC*WLLLLPPPPHHQQRRRRIIIMTTTTNNKKSSRRVVVVAAAADDEEGGGG",
-    21: "FFLLSSSSYY**CCWWLLLLPPPPHHQQRRRRIIMMTTTTNNNKSSSSVVVVAAAADDEEGGGG",
-    22: "FFLLSS*SYY*LCC*WLLLLPPPPHHQQRRRRIIIMTTTTNNKKSSRRVVVVAAAADDEEGGGG",
-    23: "FF*LSSSSYY**CC*WLLLLPPPPHHQQRRRRIIIMTTTTNNKKSSRRVVVVAAAADDEEGGGG",
-    24: "FFLLSSSSYY**CCWWLLLLPPPPHHQQRRRRIIIMTTTTNNKKSSSKVVVVAAAADDEEGGGG",
-    25: "FFLLSSSSYY**CCGWLLLLPPPPHHQQRRRRIIIMTTTTNNKKSSRRVVVVAAAADDEEGGGG",
-    26: "FFLLSSSSYY**CC*WLLLAPPPPHHQQRRRRIIIMTTTTNNKKSSRRVVVVAAAADDEEGGGG",
-    29: "FFLLSSSSYYYYCC*WLLLLPPPPHHQQRRRRIIIMTTTTNNKKSSRRVVVVAAAADDEEGGGG",
-    30: "FFLLSSSSYYEECC*WLLLLPPPPHHQQRRRRIIIMTTTTNNKKSSRRVVVVAAAADDEEGGGG",
-    32: "FFLLSSSSYY*WCC*WLLLLPPPPHHQQRRRRIIIMTTTTNNKKSSRRVVVVAAAADDEEGGGG",
-    33: "FFLLSSSSYYY*CCWWLLLLPPPPHHQQRRRRIIIMTTTTNNKKSSSKVVVVAAAADDEEGGGG",
-}
+# NCBI genetic codes in TCAG order: one definition, shared with the pure-Python rules (tables.NCBI_CODES)
+_NCBI_CODES = _tables.NCBI_CODES
 
 
 def _digit_order_table(str code):
@@ -2107,6 +2081,27 @@ cdef class GeneFinder:
         return self._find_tensor_batch("find_windows_batch", sequences, windows, out, stream, translate, training_infos, regions, circular, sets,
                                        trim_terminal_repeats)
 
+    def find_counts_batch(self, object sequences, object counts, *, object out=None, object stream=None, bint translate=False,
+                          object training_infos=None, object regions=None, object circular=None, object sets=None,
+                          object trim_terminal_repeats=None):
+        """`find_genes_batch`, and the k-mers of every contig or of every gene counted into an `int32` tensor left in device memory:
+        returns `(genes, device_counts)`, the list of `Genes` that `find_genes_batch` returns for the same arguments and a
+        `DeviceCounts`.
+
+        `counts`: a `KmerCounts` -- k, rows per contig, per gene or per contig over its genes, step, folded or binned by a table.
+        The tensor is written on the device while the batch is resident, on the batch the finder called: a gene row is gene g of the
+        request, contig after contig (`device_counts.gene_begin`), read in the gene's own direction and across the origin of a
+        circular contig; a contig row is sequence i of the request, and with `trim_terminal_repeats` a trimmed record is counted in
+        its trimmed coordinates, as a circle.  `out`: the `[R, S >= n_bins]` device tensor to write (anything with
+        `__cuda_array_interface__`), `None`: a torch tensor allocated under torch's current stream; `stream`: the stream that last
+        used `out`.  Every option of `find_genes_batch` applies and `sequences` may be a `DeviceSequences`.  The request is a device
+        call of its own: one tensor per request, so a request that `training_infos` would split into several device calls is a
+        `ValueError`."""
+        if not isinstance(counts, _cabi.KmerCounts):
+            raise TypeError("`counts` must be a KmerCounts, not %r" % type(counts).__name__)
+        return self._find_tensor_batch("find_counts_batch", sequences, counts, out, stream, translate, training_infos, regions, circular, sets,
+                                       trim_terminal_repeats)
+
     def find_starts_batch(self, object sequences, object starts, *, object out=None, object stream=None, bint translate=False,
                           object training_infos=None, object regions=None, object circular=None, object sets=None,
                           object trim_terminal_repeats=None):
@@ -2134,8 +2129,8 @@ cdef class GeneFinder:
 
     cdef tuple _find_tensor_batch(self, str method, object sequences, object spec, object out, object stream, bint translate,
                                   object training_infos, object regions, object circular, object sets, object trim_terminal_repeats):
-        """`find_proteins_batch` / `find_labels_batch` / `find_windows_batch` / `find_starts_batch`: (the `Genes` of `find_genes_batch`, what the rule `spec`
-        wrote on the device)."""
+        """`find_proteins_batch` / `find_labels_batch` / `find_windows_batch` / `find_counts_batch` / `find_starts_batch`: (the `Genes` of
+        `find_genes_batch`, what the rule `spec` wrote on the device)."""
         cdef dict tok = {"spec": spec, "out": out, "stream": stream, "result": None, "method": method}
         cdef list circ, tr_search
         cdef object dev, set_ids, tr_params
