@@ -642,6 +642,53 @@ void pga_start_plan_free(pga_ctx* /* unused: the plan knows its context */, pga_
  * outlives the call that made it reads its tensor this way: the pointer then names its device, and no message is kept. */
 int  pga_device_read(pga_ctx*, const void* d_src, int64_t bytes, void* dst, void* stream /* hipStream_t, NULL = the null stream */);
 
+/* Gene records with the same predicted protein (or the same nucleotides), grouped on the device, exactly: which records are copies of
+ * each other, one representative of every group, and a portable digest of every record's string.  What a caller that embeds, searches
+ * or catalogues the proteins does first -- drop the copies -- without a letter coming to the host.
+ *   Strings.  With unit = PGA_GROUP_PROTEIN the string of gene g is exactly the residue letters that pga_translate_genes yields for that
+ *     record under table_of_contig, include_stop, strict and unknown_residue: M at a non-edge start codon, * at a stop, a gene across
+ *     the origin of a circular contig reads on at base 1, and a gene with no residues has the empty string.  With unit =
+ *     PGA_GROUP_GENE the string is all end - begin + 1 bases of the record in reading direction, in the reading of pga_gene_windows:
+ *     A, C, G, T in either case give the upper-case letter, anything else gives N, the reverse strand is complemented, and a record
+ *     wraps at the origin of a circle.  table_of_contig, include_stop, strict and unknown_residue are not read for this unit.
+ *   Groups.  Genes g and h are in one group exactly when their strings are equal byte for byte.  A group's representative is its member
+ *     with the smallest index in the array of records passed (any subset or reordering is allowed, as for pga_translate_genes_tokens).
+ *     Groups are numbered 0 .. U - 1 in increasing order of their representatives, which is the order of first appearance.
+ *   Digest.  A property of the string alone, so results of different calls, batches and processes can be merged with it.  M = 2^61 - 1,
+ *     b0 = 0x0123456789ABCDEF, b1 = 0x1BADB002C0FFEE11.  h = 1; for every byte r of the string in order, h = (h * b + r) mod M.
+ *     digest[g] = (h under b0, h under b1), two non-negative int64.  The empty string has (1, 1).  Equal digests are NOT the rule: they
+ *     only drive the grouping, and every pair that is merged has had its strings compared byte for byte.
+ *   Outputs.  All int64 device memory of the context's device, 8-byte aligned; any of d_representative, d_size and d_digest may be NULL.
+ *       d_group          [G], required       the group of gene g
+ *       d_representative [capacity >= G]     first U elements: the gene index of each group's representative
+ *       d_size           [capacity >= G]     first U elements: the members of each group
+ *       d_digest         [G, 2]              the digest of every gene's string
+ *       n_groups         host                U -- the one size that comes back from the device
+ *     Elements beyond U of d_representative and d_size, and everything outside the named elements, are not touched.
+ *   Refusals.  PGA_EINVAL, pga_last_error naming the gene or field, all on the host before anything is allocated or launched: unit and
+ *     unknown_residue; G above INT32_MAX; capacity below G with d_representative or d_size given; the record and table checks of
+ *     pga_translate_genes; a NULL d_group; a pointer that is not 8-byte aligned; and the device-pointer query on every pointer given.
+ *   Ordering and concurrency.  As pga_translate_genes_tokens: the call waits for what `stream` holds, works on the context's upload
+ *     stream, and on return the tensors are complete for any stream.  One such call at a time per context; a steady run allocates
+ *     nothing.
+ *   The result depends on the arguments alone: integers throughout.
+ * PGA_PROTEIN_GROUPS_KEY_BITS = k (1 .. 61) in the environment, read per call, makes the GROUPING sort on the low k bits of digest
+ * word 0 alone and skip the comparison of lengths and of word 1 in front of the comparison of the strings: collisions abound and the
+ * strings alone decide (tests and measurements).  The exported digests are unchanged.  pga_protein_groups_stats: {verification
+ * rounds, pairs whose strings differed} of the context's last pga_group_proteins call. */
+#define PGA_GROUP_PROTEIN 0
+#define PGA_GROUP_GENE    1
+typedef struct pga_group_opts {
+    int32_t unit;               /* PGA_GROUP_PROTEIN or PGA_GROUP_GENE */
+    int32_t include_stop;       /* as in pga_translate_genes */
+    int32_t strict;
+    int32_t unknown_residue;    /* a single ASCII character, e.g. 'X' */
+} pga_group_opts;
+int  pga_group_proteins(pga_ctx*, const pga_batch*, int64_t n_genes, const pga_gene* genes, const int32_t* table_of_contig,
+                        const pga_group_opts*, int64_t* d_group, int64_t* d_representative, int64_t* d_size, int64_t* d_digest,
+                        int64_t capacity, void* stream /* hipStream_t, NULL = the null stream */, int64_t* n_groups /* host */);
+int  pga_protein_groups_stats(pga_ctx*, int64_t out[2]);
+
 /* ---- text output ------------------------------------------------------------------ */
 /* GFF, protein FASTA, gene FASTA, GenBank and the start-score file of gene records, rendered on the device from a resident
  * batch: byte for byte what the host writers Genes.write_gff / write_translations / write_genes / write_genbank / write_scores

@@ -31,6 +31,7 @@ EXPORTS = [
     "pga_translate_genes_tokens", "pga_label_bases", "pga_gene_windows",
     "pga_start_plan_create", "pga_start_plan_write", "pga_start_plan_nodes", "pga_start_plan_free", "pga_device_read",
     "pga_count_kmers", "pga_kmer_counts_chunk",
+    "pga_group_proteins", "pga_protein_groups_stats",
 ]
 STAGE_EXTRACT, STAGE_SCORE, STAGE_OVERLAP, STAGE_SEQUENCE = 1, 2, 3, 4
 
@@ -125,6 +126,10 @@ class CountOpts(ctypes.Structure):
                 ("row_stride", ctypes.c_int64), ("bin_of_code", ctypes.c_void_p)]
 
 
+class GroupOpts(ctypes.Structure):
+    _fields_ = [("unit", ctypes.c_int32), ("include_stop", ctypes.c_int32), ("strict", ctypes.c_int32), ("unknown_residue", ctypes.c_int32)]
+
+
 class StartOpts(ctypes.Structure):
     _fields_ = [("index_bytes", ctypes.c_int32), ("score_bytes", ctypes.c_int32), ("layout", ctypes.c_int32), ("n_fields", ctypes.c_int32),
                 ("row_width", ctypes.c_int64), ("row_stride", ctypes.c_int64), ("fields", ctypes.c_int32 * 7), ("_pad", ctypes.c_int32),
@@ -135,6 +140,7 @@ TOKENS_RAGGED, TOKENS_PADDED = 0, 1                         # pga_token_opts.lay
 WINDOW_BASES, WINDOW_CODONS = 0, 1                          # pga_window_opts.unit
 WINDOW_START, WINDOW_END = 0, 1                             # pga_window_opts.from_anchor / to_anchor
 COUNT_CONTIG, COUNT_GENE, COUNT_CONTIG_GENES = 0, 1, 2      # pga_count_opts.rows
+GROUP_PROTEIN, GROUP_GENE = 0, 1                            # pga_group_opts.unit
 TOKEN_NONE = -(1 << 63)                                     # pga_token_opts.bos / eos: no such token
 RENDER_FORMATS = ("gff", "faa", "fna", "gbk", "scores")     # PGA_RENDER_* bit order
 NODES_DEVICE = 2                                            # pga_params.want_nodes: keep the node arrays on the device
@@ -221,6 +227,9 @@ def load():
     L.pga_count_kmers.restype = ctypes.c_int
     L.pga_count_kmers.argtypes = [vp, vp, i64, vp, _P(CountOpts), vp, i64, vp, vp]
     L.pga_kmer_counts_chunk.restype = ctypes.c_int; L.pga_kmer_counts_chunk.argtypes = []
+    L.pga_group_proteins.restype = ctypes.c_int
+    L.pga_group_proteins.argtypes = [vp, vp, i64, vp, vp, _P(GroupOpts), vp, vp, vp, vp, i64, vp, _P(i64)]
+    L.pga_protein_groups_stats.restype = ctypes.c_int; L.pga_protein_groups_stats.argtypes = [vp, _P(i64)]
     L.pga_start_plan_create.restype = ctypes.c_int
     L.pga_start_plan_create.argtypes = [vp, vp, i64, vp, _P(vp), vp, vp]
     L.pga_start_plan_write.restype = ctypes.c_int
@@ -1214,7 +1223,7 @@ def _token_id(value, name):
 
 
 class _TensorRule:
-    """What ProteinTokens, BaseLabels and GeneWindows share (StartCandidates, with two element types, and KmerCounts, whose rows are always int32 ``[R, n_bins]``, take the value semantics): the element type and layout of the device tensor, value semantics over ``_key()``,
+    """What ProteinTokens, BaseLabels and GeneWindows share (StartCandidates, with two element types, KmerCounts, whose rows are always int32 ``[R, n_bins]``, and ProteinGroups, whose four tensors are always int64, take the value semantics): the element type and layout of the device tensor, value semantics over ``_key()``,
     and the head of the options struct.  A subclass says what one row is (``row`` and its ``unit``), what it needs of every contig
     of the batch (``per_contig``: ``"tables"`` or ``"lengths"``), and has ``write``, the call on raw handles with just that."""
 
@@ -2041,6 +2050,183 @@ def _kmer_counts(self, batch, result_or_genes, spec, out=None, stream=None):
     return counts_into(self.L, self.h, batch.h, self.device, batch.n, genes, spec, out, stream)
 
 
+_GROUP_UNITS = {"protein": GROUP_PROTEIN, "gene": GROUP_GENE}
+DIGEST_MODULUS = (1 << 61) - 1
+DIGEST_BASES = (0x0123456789ABCDEF, 0x1BADB002C0FFEE11)
+
+
+class ProteinGroups(_TensorRule):
+    """How ``protein_groups`` / ``find_groups_batch`` group gene records with the same string (``pga_group_opts``; the rule is in
+    ``pyrodigal_amd.h``).
+
+    ``unit``: ``"protein"`` -- the string of a record is its translation, exactly the letters ``translate_genes`` yields under the
+    contig's table, ``include_stop``, ``strict`` and ``unknown_residue``; ``"gene"`` -- all bases of the record in reading direction,
+    upper case, anything but A, C, G, T as N (the three translation options are not read then).  Two records are in one group exactly
+    when their strings are equal byte for byte.  Everything that needs no device is checked here.  Hashable and picklable."""
+
+    def __init__(self, unit="protein", *, include_stop=False, strict=True, unknown_residue="X"):
+        if unit not in _GROUP_UNITS:
+            raise ValueError("unit must be \"protein\" or \"gene\", not %r" % (unit,))
+        for name, v in (("include_stop", include_stop), ("strict", strict)):
+            if not isinstance(v, (bool, np.bool_)):
+                raise TypeError(f"{name} must be a bool, not {type(v).__name__}")
+        if not isinstance(unknown_residue, str):
+            raise TypeError(f"unknown_residue must be a str, not {type(unknown_residue).__name__}")
+        if len(unknown_residue) != 1 or not 0 < ord(unknown_residue) < 128:
+            raise ValueError("unknown_residue must be a single ASCII character, not %r" % (unknown_residue,))
+        self.of, self.include_stop, self.strict, self.unknown_residue = unit, bool(include_stop), bool(strict), unknown_residue
+
+    row, unit, per_contig = "gene", "groups", "tables"      # (`of` holds the constructor's unit)
+    dtype, typestr, elem_bytes = "int64", "<i8", 8
+
+    @staticmethod
+    def digest_of(letters):
+        """The digest of a string (``bytes`` or ASCII ``str``) as the device computes it, in Python integers: a caller can digest a
+        protein from anywhere else and look it up among ``DeviceGroups.digests``."""
+        if isinstance(letters, str):
+            letters = letters.encode("ascii")
+        out = []
+        for b in DIGEST_BASES:
+            h = 1
+            for r in bytes(letters):
+                h = (h * b + r) % DIGEST_MODULUS
+            out.append(h)
+        return tuple(out)
+
+    def write(self, L, ctx_h, batch_h, device, genes, tables, out=None, stream=None):
+        return groups_into(L, ctx_h, batch_h, device, len(tables), genes, tables, self, out, stream)
+
+    def _key(self):
+        return (self.of, self.include_stop, self.strict, self.unknown_residue)
+
+    def __reduce__(self):
+        return _protein_groups_from_key, (self._key(),)
+
+    def __repr__(self):
+        return "pyrodigal_amd.ProteinGroups(%r, include_stop=%r, strict=%r, unknown_residue=%r)" % self._key()
+
+    def opts(self):
+        o = GroupOpts()
+        o.unit, o.include_stop, o.strict, o.unknown_residue = _GROUP_UNITS[self.of], int(self.include_stop), int(self.strict), ord(self.unknown_residue)
+        return o
+
+
+def _protein_groups_from_key(key):
+    p = ProteinGroups.__new__(ProteinGroups)
+    p.of, p.include_stop, p.strict, p.unknown_residue = key
+    return p
+
+
+class DeviceGroups:
+    """Gene records grouped by their string, in device memory, all int64.  ``group``: ``[G]``, the group of every record, numbered in
+    order of first appearance; ``representatives``: ``[U]``, the first record of every group; ``sizes``: ``[U]``, its members;
+    ``digests``: ``[G, 2]``, the digest of every record's string (``ProteinGroups.digest_of``); ``n_groups``: U (host).
+    ``representatives`` and ``sizes`` are the first U elements of capacity-G tensors (``None`` where ``out=`` gave ``None``, as
+    ``digests``).  ``gene_begin``: the genes of contig i are records ``gene_begin[i] .. gene_begin[i + 1]`` (``None`` when the
+    records were not in contig order)."""
+
+    def __init__(self, group, representatives, sizes, digests, n_groups, gene_begin, device):
+        self.group, self.representatives, self.sizes, self.digests = group, representatives, sizes, digests
+        self.n_groups, self.gene_begin, self.device = n_groups, gene_begin, device
+
+
+def _group_output(x, name, shape, required):
+    """The device pointer of one int64 output of ``pga_group_proteins`` checked against the shape it needs, 0 for ``None``."""
+    if x is None:
+        if required:
+            raise TypeError(f"out: {name} is required")
+        return 0
+    cai = getattr(x, "__cuda_array_interface__", None)
+    if not isinstance(cai, dict):
+        raise TypeError(f"out: {name} must have a __cuda_array_interface__ (a device tensor or array), not %r" % type(x).__name__)
+    if str(cai.get("typestr")) != "<i8":
+        raise TypeError(f"out: {name} has dtype {cai.get('typestr')}: the groups are int64 (<i8)")
+    got = tuple(int(v) for v in cai["shape"])
+    if len(got) != len(shape) or got[1:] != shape[1:] or got[0] < shape[0]:
+        raise ValueError(f"out: {name} needs shape {list(shape)}{' or longer' if len(shape) == 1 else ''}, not {list(got)}")
+    strides = cai.get("strides")
+    if strides is not None and int(np.prod(got)) > 1 and tuple(int(v) for v in strides) != tuple(8 * int(np.prod(got[k + 1:])) for k in range(len(got))):
+        raise ValueError(f"out: {name} is not contiguous")
+    ptr = cai["data"][0]
+    return int(ptr) if ptr else 0
+
+
+def groups_into(L, ctx_h, batch_h, device, n_contigs, genes, tables, spec, out=None, stream=None):
+    """``pga_group_proteins`` on raw handles (what ``Context.protein_groups`` and the finder's device call share): the groups of
+    ``genes`` (GENE_DTYPE records of the resident batch) under ``tables`` into the four tensors of ``out``, or into new torch
+    tensors."""
+    if not isinstance(spec, ProteinGroups):
+        raise TypeError("the grouping rule must be a ProteinGroups, not %r" % type(spec).__name__)
+    genes = np.ascontiguousarray(genes, dtype=GENE_DTYPE)
+    n = len(genes)
+    p_tab = ctypes.c_void_p(0)
+    if tables is not None:
+        tables = np.ascontiguousarray(tables, np.int32)
+        if tables.shape != (n_contigs,):
+            raise ValueError(f"tables has {tables.size} entries for {n_contigs} contigs")
+        p_tab = ctypes.c_void_p(tables.ctypes.data)
+    elif spec.of == "protein":
+        raise ValueError("the protein unit needs tables=, the translation table of every contig")
+    if out is None:
+        try:
+            import torch
+        except ImportError:
+            raise TypeError("torch is not installed: pass out=, four device arrays with __cuda_array_interface__") from None
+        with torch.cuda.device(device):
+            out = (torch.empty(n, dtype=torch.int64, device="cuda"), torch.empty(n, dtype=torch.int64, device="cuda"),
+                   torch.empty(n, dtype=torch.int64, device="cuda"), torch.empty((n, 2), dtype=torch.int64, device="cuda"))
+            if stream is None:
+                stream = int(torch.cuda.current_stream().cuda_stream)
+    out = tuple(out)
+    if len(out) != 4:
+        raise ValueError("out must be (group, representatives, sizes, digests), %d objects were given" % len(out))
+    group, reps, sizes, digests = out
+    p_group = _group_output(group, "group", (n,), True)
+    p_reps, p_sizes = _group_output(reps, "representatives", (n,), False), _group_output(sizes, "sizes", (n,), False)
+    p_dig = _group_output(digests, "digests", (n, 2), False)
+    capacity = min([int(x.__cuda_array_interface__["shape"][0]) for x in (reps, sizes) if x is not None] or [n])
+    n_groups = ctypes.c_int64(0)
+    o = spec.opts()
+    rc = L.pga_group_proteins(ctx_h, batch_h, n, ctypes.c_void_p(genes.ctypes.data), p_tab, ctypes.byref(o), ctypes.c_void_p(p_group),
+                              ctypes.c_void_p(p_reps), ctypes.c_void_p(p_sizes), ctypes.c_void_p(p_dig), capacity,
+                              ctypes.c_void_p(DeviceSequences._stream_of(group, stream)), ctypes.byref(n_groups))
+    if rc != PGA_OK:
+        _raise(L, ctx_h, rc, "pga_group_proteins")
+    U = int(n_groups.value)
+    cut = lambda x: None if x is None else (x[:U] if hasattr(x, "__getitem__") else x)      # noqa: E731
+    gene_begin = None
+    if n == 0 or np.all(np.diff(genes["contig"]) >= 0):
+        gene_begin = np.searchsorted(genes["contig"], np.arange(n_contigs + 1)).astype(np.int64)
+    return DeviceGroups(group, cut(reps), cut(sizes), digests, U, gene_begin, device)
+
+
+def _protein_groups(self, batch, result_or_genes, spec, tables=None, out=None, stream=None):
+    """Gene records of the resident ``batch`` with the same protein (or the same bases) grouped on the device, exactly
+    (``pga_group_proteins``): no letter comes to the host.  ``result_or_genes``: a result of ``find_genes`` on the batch, or gene
+    records of one (any subset or order; then with ``tables`` for the protein unit).  ``spec``: a :class:`ProteinGroups`.  ``tables``:
+    translation table per contig (default: that of the model that won the contig).  ``out``: a 4-tuple ``(group [G], representatives
+    [>= G], sizes [>= G], digests [G, 2])`` of contiguous int64 objects with ``__cuda_array_interface__``, ``None`` allowed for the
+    last three; omitted: torch tensors are allocated on the context's device under torch's current stream.  ``stream``: the stream
+    that last used the outputs, as in :class:`DeviceSequences`.  Returns a :class:`DeviceGroups`."""
+    genes = getattr(result_or_genes, "genes", result_or_genes)
+    if tables is None and isinstance(spec, ProteinGroups) and spec.of == "protein":
+        contigs = getattr(result_or_genes, "contigs", None)
+        if contigs is None:
+            raise ValueError("bare gene records carry no models: pass tables=, the translation table of every contig")
+        tables = _default_tables(self, contigs)
+    return groups_into(self.L, self.h, batch.h, self.device, batch.n, genes, tables, spec, out, stream)
+
+
+def _protein_groups_stats(self):
+    """How the context's last ``protein_groups`` call went (``pga_protein_groups_stats``): the verification rounds, and the pairs the
+    sort put side by side whose strings differed."""
+    out = (ctypes.c_int64 * 2)()
+    rc = self.L.pga_protein_groups_stats(self.h, out)
+    if rc != PGA_OK:
+        _raise(self.L, self.h, rc, "pga_protein_groups_stats")
+    return {"rounds": int(out[0]), "differing_pairs": int(out[1])}
+
+
 START_FIELDS = ("total", "cscore", "sscore", "rscore", "uscore", "tscore", "gc_cont")      # PGA_START_* order
 START_TYPES = ("ATG", "GTG", "TTG", "Edge")                                                # the codes of DeviceStarts.types
 _START_INDEX_DTYPES = {"int32": (4, "<i4"), "int64": (8, "<i8")}
@@ -2597,6 +2783,8 @@ Context.label_bases = _label_bases
 Context.gene_windows = _gene_windows
 Context.start_candidates = _start_candidates
 Context.kmer_counts = _kmer_counts
+Context.protein_groups = _protein_groups
+Context.protein_groups_stats = _protein_groups_stats
 Context.train = _train
 Context.train_batch = _train_batch
 Context.upload = _upload

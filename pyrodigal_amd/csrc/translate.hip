@@ -5,6 +5,8 @@
 #include "pipeline.h"
 #include "translate_rules.h"
 
+#include <hipcub/hipcub.hpp>
+
 #include <float.h>
 #include <stdlib.h>
 #include <string.h>
@@ -96,6 +98,7 @@ int64_t gene_residues(const pga_gene& G, const int include_stop) {
 #include "label_bases.inl"
 #include "gene_windows.inl"
 #include "kmer_counts.inl"
+#include "protein_groups.inl"
 #include "start_candidates.inl"
 
 }  // namespace
@@ -447,6 +450,148 @@ extern "C" int pga_count_kmers(pga_ctx* c, const pga_batch* batch, int64_t n_gen
         else if (per_wave) hipLaunchKernelGGL((k_kmer_counts<false, 4>), grid, block, lds, st, a);
         else hipLaunchKernelGGL((k_kmer_counts<false, 1>), grid, block, lds, st, a);
     });
+}
+
+// ---- identical proteins (protein_groups.inl) ----------------------------------------------------------------------------------
+extern "C" int pga_protein_groups_stats(pga_ctx* c, int64_t out[2]) {
+    if (!c || !out) return PGA_EINVAL;
+    out[0] = c->group_stats[0]; out[1] = c->group_stats[1];
+    return PGA_OK;
+}
+
+extern "C" int pga_group_proteins(pga_ctx* c, const pga_batch* batch, int64_t n_genes, const pga_gene* genes, const int32_t* table_of_contig,
+                                  const pga_group_opts* o, int64_t* d_group, int64_t* d_representative, int64_t* d_size, int64_t* d_digest,
+                                  int64_t capacity, void* stream, int64_t* n_groups) {
+    if (!c) return PGA_EINVAL;
+    const char* const fn = "pga_group_proteins";
+    auto bad = [&](const std::string& msg) { c->err = std::string(fn) + ": " + msg; return PGA_EINVAL; };
+    if (!batch || !o || !n_groups || n_genes < 0 || (n_genes > 0 && !genes)) return bad("bad arguments");
+    const pga_batch_view bv = pga_batch_peek(batch);
+    if (bv.ctx != c) return bad("the batch belongs to another context");
+    // ---- validation: all of it on the host, before anything is allocated or launched ----
+    if (o->unit != PGA_GROUP_PROTEIN && o->unit != PGA_GROUP_GENE) return bad("unit must be PGA_GROUP_PROTEIN or PGA_GROUP_GENE, not " + std::to_string(o->unit));
+    const bool protein = o->unit == PGA_GROUP_PROTEIN;
+    if (o->unknown_residue <= 0 || o->unknown_residue > 127) return bad("`unknown_residue` must be a single ASCII character");
+    if (n_genes > INT32_MAX) return bad("more than 2^31 - 1 gene records");
+    if (capacity < 0 || ((d_representative || d_size) && capacity < n_genes))
+        return bad("capacity = " + std::to_string(capacity) + " is less than the " + std::to_string(n_genes) + " gene records");
+    if (protein && n_genes > 0) {
+        if (!table_of_contig) return bad("table_of_contig is NULL");
+        for (int i = 0; i < bv.n; i++)
+            if (!table_known(table_of_contig[i])) return bad("contig " + std::to_string(i) + ": " + std::to_string(table_of_contig[i]) + " is not a valid translation table index");
+    }
+    for (int64_t g = 0; g < n_genes; g++)
+        if (!gene_inside(bv, genes[g])) return bad("gene " + std::to_string(g) + " lies outside its contig");
+    int key_bits = 61;
+    if (const char* e = getenv("PGA_PROTEIN_GROUPS_KEY_BITS")) {
+        char* end = nullptr;
+        const long k = strtol(e, &end, 10);
+        if (end == e || *end || k < 1 || k > 61) return bad(std::string("PGA_PROTEIN_GROUPS_KEY_BITS must be 1 .. 61, not \"") + e + "\"");
+        key_bits = (int)k;
+    }
+    c->group_stats[0] = c->group_stats[1] = 0;
+    if (n_genes == 0) { *n_groups = 0; return PGA_OK; }
+    const struct { const char* name; const void* p; } outs[4] = {{"d_group", d_group}, {"d_representative", d_representative}, {"d_size", d_size}, {"d_digest", d_digest}};
+    if (!d_group) return bad("d_group is NULL");
+    for (const auto& x : outs) if ((uintptr_t)x.p % 8u) return bad(std::string(x.name) + " is not aligned to its 8-byte elements");
+    if (hipSetDevice(c->device) != hipSuccess) return PGA_EDEVICE;
+    for (const auto& x : outs) if (x.p) if (const int rc = pga_device_memory_(c, x.p, fn, x.name)) return rc;
+    if (protein) { const int rc = tables_ready(c); if (rc) return rc; }
+    // ---- the lease: the records as the kernels read them, staged in the pinned area, and behind them the work arrays of the call ----
+    const size_t G = (size_t)n_genes;
+    const int iG = (int)n_genes;
+    size_t sort_b = 0, max_b = 0, sum_b = 0;
+    hipcub::DeviceRadixSort::SortPairs(nullptr, sort_b, (uint64_t*)nullptr, (uint64_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr, iG, 0, key_bits, (hipStream_t)nullptr);
+    hipcub::DeviceScan::InclusiveScan(nullptr, max_b, (uint32_t*)nullptr, (uint32_t*)nullptr, GrpMax{}, iG, (hipStream_t)nullptr);
+    hipcub::DeviceScan::ExclusiveSum(nullptr, sum_b, (int32_t*)nullptr, (int32_t*)nullptr, iG, (hipStream_t)nullptr);
+    const size_t tmp_b = std::max(sort_b, std::max(max_b, sum_b));
+    auto al = [](const size_t x) { return (x + 255) & ~(size_t)255; };
+    const size_t row_b = sizeof(GrpRow) * G;
+    const size_t p_small = al(row_b), p_w0 = p_small + 256, p_w1 = p_w0 + al(8 * G), p_skey = p_w1 + al(8 * G), p_idx = p_skey + al(8 * G), p_sidx = p_idx + al(4 * G);
+    const size_t p_start = p_sidx + al(4 * G), p_runstart = p_start + al(4 * G), p_cand0 = p_runstart + al(4 * G), p_cand1 = p_cand0 + al(4 * G);
+    const size_t p_head = p_cand1 + al(4 * G), p_tmp = p_head + al(4 * G), p_end = p_tmp + al(tmp_b + 1);
+    pga_upload_lease L{};
+    { const int rc = pga_upload_lease_take(c, p_end, &L); if (rc) return rc; }
+    GrpRow* const rows = (GrpRow*)L.pin;
+    for (size_t g = 0; g < G; g++) {
+        const pga_gene& R = genes[g];
+        const bool fwd = R.strand == 1;
+        GrpRow& w = rows[g];
+        w.base = bv.ct[R.contig].base; w.L = bv.ct[R.contig].len;
+        w.q0 = fwd ? R.begin - 1 : R.end - 1;
+        w.n = protein ? (int32_t)gene_residues(R, o->include_stop) : R.end - R.begin + 1;
+        // partial flags are in sequence orientation; the gene's own first codon follows its strand
+        const bool start_edge = fwd ? R.partial_begin != 0 : R.partial_end != 0;
+        w.bits = (fwd ? 1u : 0u) | (start_edge ? 2u : 0u) | (protein ? (uint32_t)table_of_contig[R.contig] << 8 : 0u);
+    }
+    volatile long long* const h_small = (volatile long long*)(L.pin + p_small);    // [0]: what a round left, [1]: U
+    GrpArgs a{};
+    a.seq = bv.d_seq; a.row = (const GrpRow*)L.dev; a.n = n_genes;
+    a.unk = o->unknown_residue; a.strict = o->strict; a.precheck = key_bits == 61;
+    a.key_mask = (1ull << key_bits) - 1;
+    a.w0 = (uint64_t*)(L.dev + p_w0); a.w1 = (uint64_t*)(L.dev + p_w1); a.idx = (uint32_t*)(L.dev + p_idx);
+    a.skey = (const uint64_t*)(L.dev + p_skey); a.sidx = (const uint32_t*)(L.dev + p_sidx);
+    a.start = (uint32_t*)(L.dev + p_start); a.runstart = (uint32_t*)(L.dev + p_runstart);
+    a.head = (int32_t*)(L.dev + p_head);
+    a.unresolved = (unsigned long long*)(L.dev + p_small);
+    a.d_digest = d_digest;
+    uint32_t* const cand[2] = {(uint32_t*)(L.dev + p_cand0), (uint32_t*)(L.dev + p_cand1)};
+    void* const d_tmp = L.dev + p_tmp;
+    size_t tb = tmp_b;
+    hipStream_t st = L.st;
+    const dim3 block(kRowThreads), per_gene((unsigned)((n_genes + kRowThreads - 1) / kRowThreads));
+    auto launched = [&]() { return hipGetLastError(); };
+    // behind what the caller's stream holds; complete on return
+    hipError_t e = hipEventRecord(L.ev, (hipStream_t)stream);
+    if (e == hipSuccess) e = hipStreamWaitEvent(st, L.ev, 0);
+    if (e == hipSuccess) e = hipMemcpyAsync(L.dev, L.pin, row_b, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemsetAsync(a.head, 0xff, 4 * G, st);
+    if (e == hipSuccess) {
+        // a wave per four records, and several rounds of them per wave where there are many
+        const int64_t quads = (n_genes + 3) / 4, per_block = kRowThreads / 64;
+        const dim3 grid((unsigned)std::min<int64_t>((quads + per_block - 1) / per_block, 8192));
+        if (protein) hipLaunchKernelGGL((k_string_digest<kGrpProtein>), grid, block, 0, st, a);
+        else hipLaunchKernelGGL((k_string_digest<kGrpGene>), grid, block, 0, st, a);
+        e = launched();
+    }
+    if (e == hipSuccess) e = hipcub::DeviceRadixSort::SortPairs(d_tmp, tb, (const uint64_t*)a.w0, (uint64_t*)a.skey, (const uint32_t*)a.idx, (uint32_t*)a.sidx, iG, 0, key_bits, st);
+    a.cand = cand[0];
+    if (e == hipSuccess) { hipLaunchKernelGGL(k_group_runs, per_gene, block, 0, st, a); e = launched(); }
+    tb = tmp_b;
+    if (e == hipSuccess) e = hipcub::DeviceScan::InclusiveScan(d_tmp, tb, (const uint32_t*)a.start, a.runstart, GrpMax{}, iG, st);
+    int64_t rounds = 0, differing = 0;
+    while (e == hipSuccess) {
+        a.cand = cand[rounds & 1]; a.cand_next = cand[(rounds + 1) & 1];
+        e = hipMemsetAsync(a.cand_next, 0xff, 4 * G, st);
+        if (e == hipSuccess) e = hipMemsetAsync(a.unresolved, 0, 8, st);
+        if (e == hipSuccess) {
+            if (protein) hipLaunchKernelGGL((k_group_verify<kGrpProtein>), per_gene, block, 0, st, a);
+            else hipLaunchKernelGGL((k_group_verify<kGrpGene>), per_gene, block, 0, st, a);
+            e = launched();
+        }
+        if (e == hipSuccess) e = hipMemcpyAsync((void*)h_small, a.unresolved, 8, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipStreamSynchronize(st);
+        if (e != hipSuccess) break;
+        rounds++;
+        const int64_t left = h_small[0];
+        differing += left;
+        if (left == 0) break;                                  // (a round resolves the head of every run that has members left: it ends)
+    }
+    // ---- numbering: representatives flagged, an exclusive scan, and the outputs (flags, numbers and counts over the rounds' arrays) ----
+    GrpOut w{};
+    w.head = a.head; w.flag = (int32_t*)a.start; w.num = (const int32_t*)a.runstart; w.cnt = (int32_t*)cand[0]; w.n = n_genes;
+    w.d_group = d_group; w.d_rep = d_representative; w.d_size = d_size; w.n_groups = (long long*)(L.dev + p_small) + 1;
+    if (e == hipSuccess) { hipLaunchKernelGGL(k_group_flags, per_gene, block, 0, st, w); e = launched(); }
+    tb = tmp_b;
+    if (e == hipSuccess) e = hipcub::DeviceScan::ExclusiveSum(d_tmp, tb, (const int32_t*)w.flag, (int32_t*)a.runstart, iG, st);
+    if (e == hipSuccess) { hipLaunchKernelGGL(k_group_count, per_gene, block, 0, st, w); e = launched(); }
+    if (e == hipSuccess && (d_representative || d_size)) { hipLaunchKernelGGL(k_group_emit, per_gene, block, 0, st, w); e = launched(); }
+    if (e == hipSuccess) e = hipMemcpyAsync((void*)(h_small + 1), w.n_groups, 8, hipMemcpyDeviceToHost, st);
+    const hipError_t es = hipStreamSynchronize(st);            // (also after a failure: nothing of the lease is in use when it goes back)
+    if (e == hipSuccess) e = es;
+    if (e == hipSuccess) { *n_groups = h_small[1]; c->group_stats[0] = rounds; c->group_stats[1] = differing; }
+    pga_upload_lease_give(c);
+    return pga_hip_try_(c, e, fn);
 }
 
 // ---- start candidates (start_candidates.inl) ----------------------------------------------------------------------------------

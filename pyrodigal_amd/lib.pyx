@@ -2102,6 +2102,28 @@ cdef class GeneFinder:
         return self._find_tensor_batch("find_counts_batch", sequences, counts, out, stream, translate, training_infos, regions, circular, sets,
                                        trim_terminal_repeats)
 
+    def find_groups_batch(self, object sequences, object groups, *, object out=None, object stream=None, bint translate=False,
+                          object training_infos=None, object regions=None, object circular=None, object sets=None,
+                          object trim_terminal_repeats=None):
+        """`find_genes_batch`, and the genes with the same predicted protein (or the same bases) grouped on the device, exactly:
+        returns `(genes, device_groups)`, the list of `Genes` that `find_genes_batch` returns for the same arguments and a
+        `DeviceGroups`.
+
+        `groups`: a `ProteinGroups` -- proteins or bases, and the translation's options.  Gene g of the request, contig after contig
+        (`device_groups.gene_begin`), gets `group[g]`; the groups are numbered in order of first appearance, `representatives[u]` is
+        the first gene of group u and `sizes[u]` its members; `digests[g]` is the portable digest of the gene's string
+        (`ProteinGroups.digest_of`), with which the results of several requests can be merged.  Two genes share a group exactly when
+        their strings are equal byte for byte.  The tensors are written while the batch is resident, on the batch the finder
+        called, each contig under the table of the model that won it.  `out`: a `(group, representatives, sizes, digests)` tuple of
+        int64 device tensors to write (anything with `__cuda_array_interface__`; `None` for any of the last three), omitted: torch
+        tensors allocated under torch's current stream; `stream`: the stream that last used them.  Every option of
+        `find_genes_batch` applies and `sequences` may be a `DeviceSequences`.  The request is a device call of its own: one set of
+        tensors per request, so a request that `training_infos` would split into several device calls is a `ValueError`."""
+        if not isinstance(groups, _cabi.ProteinGroups):
+            raise TypeError("`groups` must be a ProteinGroups, not %r" % type(groups).__name__)
+        return self._find_tensor_batch("find_groups_batch", sequences, groups, out, stream, translate, training_infos, regions, circular, sets,
+                                       trim_terminal_repeats)
+
     def find_starts_batch(self, object sequences, object starts, *, object out=None, object stream=None, bint translate=False,
                           object training_infos=None, object regions=None, object circular=None, object sets=None,
                           object trim_terminal_repeats=None):
@@ -2129,7 +2151,7 @@ cdef class GeneFinder:
 
     cdef tuple _find_tensor_batch(self, str method, object sequences, object spec, object out, object stream, bint translate,
                                   object training_infos, object regions, object circular, object sets, object trim_terminal_repeats):
-        """`find_proteins_batch` / `find_labels_batch` / `find_windows_batch` / `find_counts_batch` / `find_starts_batch`: (the `Genes` of
+        """`find_proteins_batch` / `find_labels_batch` / `find_windows_batch` / `find_counts_batch` / `find_groups_batch` / `find_starts_batch`: (the `Genes` of
         `find_genes_batch`, what the rule `spec` wrote on the device)."""
         cdef dict tok = {"spec": spec, "out": out, "stream": stream, "result": None, "method": method}
         cdef list circ, tr_search
