@@ -689,6 +689,70 @@ int  pga_group_proteins(pga_ctx*, const pga_batch*, int64_t n_genes, const pga_g
                         int64_t capacity, void* stream /* hipStream_t, NULL = the null stream */, int64_t* n_groups /* host */);
 int  pga_protein_groups_stats(pga_ctx*, int64_t out[2]);
 
+/* Bottom-s MinHash sketches of the gene records' strings, on the device: a fixed [G, size] int64 tensor from which the resemblance and
+ * containment of any two proteins can be estimated, and whose sort yields candidate pairs -- the step behind pga_group_proteins for
+ * proteins that differ in a few residues, a start codon or a truncation.  Defined by the string alone, so sketches of different
+ * calls, batches and processes can be compared.
+ *   Strings.  The string of gene record g is exactly that of pga_group_proteins.  unit = PGA_SKETCH_PROTEIN: the residues
+ *     pga_translate_genes yields under table_of_contig, include_stop, strict and unknown_residue.  unit = PGA_SKETCH_GENE: all bases in
+ *     reading direction, in the reading of pga_gene_windows.  Circular contigs wrap.  Any subset or reordering of a result's records
+ *     may be passed.
+ *   Letter codes.  Protein: a 128-entry byte table `classes` maps a letter to a class 0..254, or to 255 ("skip").  The default table
+ *     (what the Python layer fills in) is the identity with classes[unknown_residue] = 255; a caller-given table (a reduced alphabet)
+ *     decides alone.  A letter at or above 128 is skipped.  8 bits per letter, 1 <= k <= 8.  Gene: A, C, G, T map to 0..3 and N is
+ *     skipped.  2 bits per letter, 1 <= k <= 32.  `classes` is not read.
+ *   Windows.  Window j (0 <= j <= n - k) of a string S of n letters is valid when none of its k letters is skipped.  Its key is
+ *     x = sum_i code(S[j + i]) << (bits * (k - 1 - i)), an unsigned 64-bit number.  windows[g] is the number of valid windows.  It is
+ *     0 when n < k.
+ *   Hash.  All arithmetic is mod 2^64:
+ *       z = x + (seed + 1) * 0x9E3779B97F4A7C15
+ *       z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9
+ *       z = (z ^ (z >> 27)) * 0x94D049BB133111EB
+ *       z ^= z >> 31
+ *       hash = z >> 1, a non-negative int64.
+ *     seed is a uint32.  x = 0, seed = 0 gives z = 0xE220A8397B1DCDAF (the first output of splitmix64 from state 0) and
+ *     hash = 0x7110541CBD8EE6D7.
+ *   Sketch.  H_g is the set of distinct hashes of the valid windows of g.  count[g] = min(size, |H_g|).  sketch[g, 0 .. count[g])
+ *     holds the count[g] smallest elements of H_g in ascending order.  sketch[g, count[g] .. size) is INT64_MAX.  count says which
+ *     entries are real.  A genuine hash that equals INT64_MAX is not special-cased.  1 <= size <= 64.
+ *   Pairs (pga_sketch_pairs).  For a pair (a, b): A and B are the real entries of the two rows.  U is their sorted distinct union.
+ *     m = min(size, |U|).  union[p] = m.  shared[p] is the number of the m smallest elements of U that lie in both A and B.  This is
+ *     the Mash estimator: resemblance is about shared / m, and it is 0 / 0 for two empty rows.  A pair with an index outside
+ *     0 .. G - 1 gets shared = union = -1, and nothing is read for it.
+ *   Outputs.  All int64 device memory of the context's device, 8-byte aligned.  d_sketch [G, size], d_count [G], d_windows [G] or NULL;
+ *     d_shared [P], d_union [P].  Nothing outside the named elements is touched.  pga_sketch_pairs reads d_sketch [G, size], d_count
+ *     [G] and d_pairs [P, 2] as a call of pga_sketch_proteins with the same size left them.
+ *   Refusals.  PGA_EINVAL, pga_last_error naming the gene or field, all on the host before anything is allocated or launched: unit, k
+ *     and size out of range; unknown_residue; G above INT32_MAX; a NULL d_sketch or d_count (d_pairs, d_shared, d_union); a pointer
+ *     that is not 8-byte aligned; the device-pointer query on every pointer given; and the record and table checks of
+ *     pga_translate_genes.  G = 0 and P = 0 return PGA_OK without a launch.
+ *   Ordering and concurrency.  As pga_translate_genes_tokens: the call waits for what `stream` holds, works on the context's upload
+ *     stream, and on return the tensors are complete for any stream.  One such call at a time per context; the records and the class
+ *     table go through the upload lease, and a steady run allocates nothing.
+ *   The result depends on the arguments alone: integers throughout.
+ * pga_sketch_passes: the hashes behind a record's first 64 windows that passed the threshold of the record's sketch -- the insertions
+ * tried, duplicates included -- in the context's last pga_sketch_proteins call, when the library was built with
+ * -DPGA_SKETCH_COUNT_PASSES (measurements); -1 otherwise. */
+#define PGA_SKETCH_PROTEIN 0
+#define PGA_SKETCH_GENE    1
+typedef struct pga_sketch_opts {
+    int32_t unit;               /* PGA_SKETCH_PROTEIN or PGA_SKETCH_GENE */
+    int32_t k;                  /* letters per window */
+    int32_t size;               /* s: the hashes kept per record */
+    uint32_t seed;
+    int32_t include_stop;       /* as in pga_translate_genes */
+    int32_t strict;
+    int32_t unknown_residue;    /* a single ASCII character, e.g. 'X' */
+    int32_t _pad;
+    uint8_t classes[128];       /* protein unit: the class of every letter, 255 = skip */
+} pga_sketch_opts;
+int  pga_sketch_proteins(pga_ctx*, const pga_batch*, int64_t n_genes, const pga_gene* genes, const int32_t* table_of_contig,
+                         const pga_sketch_opts*, int64_t* d_sketch /* [G, size] */, int64_t* d_count /* [G] */,
+                         int64_t* d_windows /* [G] or NULL */, void* stream /* hipStream_t, NULL = the null stream */);
+int  pga_sketch_pairs(pga_ctx*, const int64_t* d_sketch, const int64_t* d_count, int64_t n_genes, int32_t size,
+                      const int64_t* d_pairs /* [P, 2] */, int64_t n_pairs, int64_t* d_shared, int64_t* d_union, void* stream);
+int  pga_sketch_passes(pga_ctx*, int64_t* out);
+
 /* ---- text output ------------------------------------------------------------------ */
 /* GFF, protein FASTA, gene FASTA, GenBank and the start-score file of gene records, rendered on the device from a resident
  * batch: byte for byte what the host writers Genes.write_gff / write_translations / write_genes / write_genbank / write_scores

@@ -12,7 +12,8 @@ _LIB_NAMES = ("GeneFinder", "Genes", "Gene", "Nodes", "Node", "Sequence", "Train
               "ConnectionScorer", "Mask", "Masks", "METAGENOMIC_BINS", "TRANSLATION_TABLES", "PRODIGAL_VERSION", "MIN_SINGLE_GENOME",
               "IDEAL_SINGLE_GENOME", "TerminalRepeats")
 _CABI_NAMES = ("DeviceSequences", "ProteinTokens", "DeviceProteins", "BaseLabels", "DeviceLabels", "GeneWindows",
-               "DeviceWindows", "StartCandidates", "DeviceStarts", "KmerCounts", "DeviceCounts", "ProteinGroups", "DeviceGroups")
+               "DeviceWindows", "StartCandidates", "DeviceStarts", "KmerCounts", "DeviceCounts", "ProteinGroups", "DeviceGroups",
+               "ProteinSketches", "DeviceSketches")
 __all__ = list(_LIB_NAMES) + ["TableSelection"] + list(_CABI_NAMES)
 
 from .tables import TableSelection      # pure Python: the result of GeneFinder.select_translation_table

@@ -32,6 +32,7 @@ EXPORTS = [
     "pga_start_plan_create", "pga_start_plan_write", "pga_start_plan_nodes", "pga_start_plan_free", "pga_device_read",
     "pga_count_kmers", "pga_kmer_counts_chunk",
     "pga_group_proteins", "pga_protein_groups_stats",
+    "pga_sketch_proteins", "pga_sketch_pairs", "pga_sketch_passes",
 ]
 STAGE_EXTRACT, STAGE_SCORE, STAGE_OVERLAP, STAGE_SEQUENCE = 1, 2, 3, 4
 
@@ -130,6 +131,12 @@ class GroupOpts(ctypes.Structure):
     _fields_ = [("unit", ctypes.c_int32), ("include_stop", ctypes.c_int32), ("strict", ctypes.c_int32), ("unknown_residue", ctypes.c_int32)]
 
 
+class SketchOpts(ctypes.Structure):
+    _fields_ = [("unit", ctypes.c_int32), ("k", ctypes.c_int32), ("size", ctypes.c_int32), ("seed", ctypes.c_uint32),
+                ("include_stop", ctypes.c_int32), ("strict", ctypes.c_int32), ("unknown_residue", ctypes.c_int32), ("_pad", ctypes.c_int32),
+                ("classes", ctypes.c_uint8 * 128)]
+
+
 class StartOpts(ctypes.Structure):
     _fields_ = [("index_bytes", ctypes.c_int32), ("score_bytes", ctypes.c_int32), ("layout", ctypes.c_int32), ("n_fields", ctypes.c_int32),
                 ("row_width", ctypes.c_int64), ("row_stride", ctypes.c_int64), ("fields", ctypes.c_int32 * 7), ("_pad", ctypes.c_int32),
@@ -141,6 +148,7 @@ WINDOW_BASES, WINDOW_CODONS = 0, 1                          # pga_window_opts.un
 WINDOW_START, WINDOW_END = 0, 1                             # pga_window_opts.from_anchor / to_anchor
 COUNT_CONTIG, COUNT_GENE, COUNT_CONTIG_GENES = 0, 1, 2      # pga_count_opts.rows
 GROUP_PROTEIN, GROUP_GENE = 0, 1                            # pga_group_opts.unit
+SKETCH_PROTEIN, SKETCH_GENE = 0, 1                          # pga_sketch_opts.unit
 TOKEN_NONE = -(1 << 63)                                     # pga_token_opts.bos / eos: no such token
 RENDER_FORMATS = ("gff", "faa", "fna", "gbk", "scores")     # PGA_RENDER_* bit order
 NODES_DEVICE = 2                                            # pga_params.want_nodes: keep the node arrays on the device
@@ -230,6 +238,11 @@ def load():
     L.pga_group_proteins.restype = ctypes.c_int
     L.pga_group_proteins.argtypes = [vp, vp, i64, vp, vp, _P(GroupOpts), vp, vp, vp, vp, i64, vp, _P(i64)]
     L.pga_protein_groups_stats.restype = ctypes.c_int; L.pga_protein_groups_stats.argtypes = [vp, _P(i64)]
+    L.pga_sketch_proteins.restype = ctypes.c_int
+    L.pga_sketch_proteins.argtypes = [vp, vp, i64, vp, vp, _P(SketchOpts), vp, vp, vp, vp]
+    L.pga_sketch_pairs.restype = ctypes.c_int
+    L.pga_sketch_pairs.argtypes = [vp, vp, vp, i64, ctypes.c_int32, vp, i64, vp, vp, vp]
+    L.pga_sketch_passes.restype = ctypes.c_int; L.pga_sketch_passes.argtypes = [vp, _P(i64)]
     L.pga_start_plan_create.restype = ctypes.c_int
     L.pga_start_plan_create.argtypes = [vp, vp, i64, vp, _P(vp), vp, vp]
     L.pga_start_plan_write.restype = ctypes.c_int
@@ -1223,7 +1236,7 @@ def _token_id(value, name):
 
 
 class _TensorRule:
-    """What ProteinTokens, BaseLabels and GeneWindows share (StartCandidates, with two element types, KmerCounts, whose rows are always int32 ``[R, n_bins]``, and ProteinGroups, whose four tensors are always int64, take the value semantics): the element type and layout of the device tensor, value semantics over ``_key()``,
+    """What ProteinTokens, BaseLabels and GeneWindows share (StartCandidates, with two element types, KmerCounts, whose rows are always int32 ``[R, n_bins]``, and ProteinGroups and ProteinSketches, whose tensors are always int64, take the value semantics): the element type and layout of the device tensor, value semantics over ``_key()``,
     and the head of the options struct.  A subclass says what one row is (``row`` and its ``unit``), what it needs of every contig
     of the batch (``per_contig``: ``"tables"`` or ``"lengths"``), and has ``write``, the call on raw handles with just that."""
 
@@ -2140,7 +2153,7 @@ def _group_output(x, name, shape, required):
     if not isinstance(cai, dict):
         raise TypeError(f"out: {name} must have a __cuda_array_interface__ (a device tensor or array), not %r" % type(x).__name__)
     if str(cai.get("typestr")) != "<i8":
-        raise TypeError(f"out: {name} has dtype {cai.get('typestr')}: the groups are int64 (<i8)")
+        raise TypeError(f"out: {name} has dtype {cai.get('typestr')}: these tensors are int64 (<i8)")
     got = tuple(int(v) for v in cai["shape"])
     if len(got) != len(shape) or got[1:] != shape[1:] or got[0] < shape[0]:
         raise ValueError(f"out: {name} needs shape {list(shape)}{' or longer' if len(shape) == 1 else ''}, not {list(got)}")
@@ -2225,6 +2238,263 @@ def _protein_groups_stats(self):
     if rc != PGA_OK:
         _raise(self.L, self.h, rc, "pga_protein_groups_stats")
     return {"rounds": int(out[0]), "differing_pairs": int(out[1])}
+
+
+_SKETCH_UNITS = {"protein": SKETCH_PROTEIN, "gene": SKETCH_GENE}
+SKETCH_NONE = (1 << 63) - 1                                 # what a sketch row holds behind its count
+SKETCH_SKIP = 255                                           # the class of a letter that no window may hold
+_MASK64 = (1 << 64) - 1
+_BASE_CODES = {"A": 0, "C": 1, "G": 2, "T": 3}
+
+
+def _sketch_classes(classes, unknown_residue):
+    """The 128-entry class table of a ``ProteinSketches``, as a tuple."""
+    if classes is None:
+        table = list(range(128))
+        table[ord(unknown_residue)] = SKETCH_SKIP
+        return tuple(table)
+    if isinstance(classes, (bytes, bytearray)) or (isinstance(classes, (tuple, list, np.ndarray)) and len(classes) == 128
+                                                   and not any(isinstance(v, str) for v in classes)):
+        table = [int(v) for v in bytes(classes)] if isinstance(classes, (bytes, bytearray)) else [int(v) for v in classes]
+        if len(table) != 128:
+            raise ValueError(f"classes has {len(table)} entries: a class table has 128")
+        if not all(0 <= v <= 255 for v in table):
+            raise ValueError("a class is 0 .. 254, or 255 for a letter that is skipped")
+        return tuple(table)
+    if isinstance(classes, str):
+        raise TypeError("classes must be None, 128 bytes or an iterable of strings of letters, not one string")
+    table = [SKETCH_SKIP] * 128
+    n = 0
+    for n, letters in enumerate(classes):
+        if not isinstance(letters, str) or not letters:
+            raise TypeError("classes: every class is a non-empty string of letters, not %r" % (letters,))
+        if n >= SKETCH_SKIP:
+            raise ValueError("classes: more than 255 classes")
+        for ch in letters:
+            if not 0 < ord(ch) < 128:
+                raise ValueError(f"classes: {ch!r} is not a 7-bit ASCII character")
+            if table[ord(ch)] != SKETCH_SKIP:
+                raise ValueError(f"classes: the letter {ch!r} is named twice")
+            table[ord(ch)] = n
+    return tuple(table)
+
+
+class ProteinSketches(_TensorRule):
+    """How ``protein_sketches`` / ``find_sketches_batch`` sketch the strings of gene records (``pga_sketch_opts``; the rule is in
+    ``pyrodigal_amd.h``): the ``size`` smallest distinct hashes of the ``k``-letter windows of every record, a bottom-s MinHash.
+
+    ``unit``: ``"protein"`` -- the string of a record is its translation under the contig's table, ``include_stop``, ``strict`` and
+    ``unknown_residue`` (``1 <= k <= 8``); ``"gene"`` -- its bases in reading direction, N skipped (``1 <= k <= 32``; the three
+    translation options and ``classes`` are not read).  ``classes``: ``None`` -- every letter is its own class and
+    ``unknown_residue`` is skipped; 128 byte values -- the class 0 .. 254 of every letter, 255 to skip it; or an iterable of strings,
+    each one class of a reduced alphabet, letters not named being skipped.  ``seed``: a uint32 that picks the hash function.
+    Everything that needs no device is checked here.  Hashable and picklable."""
+
+    def __init__(self, k=5, size=32, unit="protein", *, seed=0, classes=None, include_stop=False, strict=True, unknown_residue="X"):
+        if unit not in _SKETCH_UNITS:
+            raise ValueError("unit must be \"protein\" or \"gene\", not %r" % (unit,))
+        for name, v in (("k", k), ("size", size), ("seed", seed)):
+            if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)):
+                raise TypeError(f"{name} must be an int, not {type(v).__name__}")
+        kmax = 8 if unit == "protein" else 32
+        if not 1 <= k <= kmax:
+            raise ValueError(f"k must be 1 .. {kmax} for the {unit} unit, not {k}")
+        if not 1 <= size <= 64:
+            raise ValueError(f"size must be 1 .. 64, not {size}")
+        if not 0 <= seed < (1 << 32):
+            raise ValueError(f"seed must be a uint32, not {seed}")
+        for name, v in (("include_stop", include_stop), ("strict", strict)):
+            if not isinstance(v, (bool, np.bool_)):
+                raise TypeError(f"{name} must be a bool, not {type(v).__name__}")
+        if not isinstance(unknown_residue, str):
+            raise TypeError(f"unknown_residue must be a str, not {type(unknown_residue).__name__}")
+        if len(unknown_residue) != 1 or not 0 < ord(unknown_residue) < 128:
+            raise ValueError("unknown_residue must be a single ASCII character, not %r" % (unknown_residue,))
+        self.k, self.size, self.of, self.seed = int(k), int(size), unit, int(seed)
+        self.classes = _sketch_classes(classes, unknown_residue)
+        self.include_stop, self.strict, self.unknown_residue = bool(include_stop), bool(strict), unknown_residue
+
+    row, unit, per_contig = "gene", "sketches", "tables"    # (`of` holds the constructor's unit)
+    dtype, typestr, elem_bytes = "int64", "<i8", 8
+
+    def hash_of(self, x):
+        """The hash of a window's key ``x`` under the rule's seed, in Python integers."""
+        z = (x + (self.seed + 1) * 0x9E3779B97F4A7C15) & _MASK64
+        z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & _MASK64
+        z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & _MASK64
+        return (z ^ (z >> 31)) >> 1
+
+    def sketch_of(self, letters):
+        """``(sketch, windows)`` of a string (``bytes`` or ASCII ``str``) as the device computes it, in Python integers: the
+        ascending list of its at most ``size`` smallest distinct hashes -- ``len(sketch)`` is the device's count -- and its valid
+        windows.  A caller can sketch a protein from anywhere else and compare it with rows of ``DeviceSketches.sketches``."""
+        if isinstance(letters, str):
+            letters = letters.encode("ascii")
+        if self.of == "gene":
+            bits, codes = 2, [_BASE_CODES.get(chr(b), SKETCH_SKIP) for b in bytes(letters)]
+        else:
+            bits, codes = 8, [self.classes[b] if b < 128 else SKETCH_SKIP for b in bytes(letters)]
+        hashes, windows = set(), 0
+        for j in range(len(codes) - self.k + 1):
+            w = codes[j:j + self.k]
+            if SKETCH_SKIP in w:
+                continue
+            x = 0
+            for c in w:
+                x = (x << bits) | c
+            windows += 1
+            hashes.add(self.hash_of(x))
+        return sorted(hashes)[:self.size], windows
+
+    def shared(self, row_a, row_b):
+        """``(shared, m)`` of two sketches (the real entries of two rows): of the ``m = min(size, |union|)`` smallest hashes of their
+        union, those that lie in both -- what ``DeviceSketches.compare`` gives.  Resemblance is about ``shared / m``."""
+        a, b = set(int(v) for v in row_a), set(int(v) for v in row_b)
+        low = sorted(a | b)[:self.size]
+        return sum(1 for v in low if v in a and v in b), len(low)
+
+    def write(self, L, ctx_h, batch_h, device, genes, tables, out=None, stream=None):
+        return sketches_into(L, ctx_h, batch_h, device, len(tables), genes, tables, self, out, stream)
+
+    def _key(self):
+        return (self.k, self.size, self.of, self.seed, self.classes, self.include_stop, self.strict, self.unknown_residue)
+
+    def __reduce__(self):
+        return _protein_sketches_from_key, (self._key(),)
+
+    def __repr__(self):
+        return "pyrodigal_amd.ProteinSketches(%r, %r, %r, seed=%r, include_stop=%r, strict=%r, unknown_residue=%r)" % (
+            self.k, self.size, self.of, self.seed, self.include_stop, self.strict, self.unknown_residue)
+
+    def opts(self):
+        o = SketchOpts()
+        o.unit, o.k, o.size, o.seed = _SKETCH_UNITS[self.of], self.k, self.size, self.seed
+        o.include_stop, o.strict, o.unknown_residue = int(self.include_stop), int(self.strict), ord(self.unknown_residue)
+        o.classes[:] = self.classes
+        return o
+
+
+def _protein_sketches_from_key(key):
+    p = ProteinSketches.__new__(ProteinSketches)
+    p.k, p.size, p.of, p.seed, p.classes, p.include_stop, p.strict, p.unknown_residue = key
+    return p
+
+
+class DeviceSketches:
+    """The sketches of gene records, in device memory, all int64.  ``sketches``: ``[G, size]``, every row ascending, ``INT64_MAX``
+    behind its ``counts[g]`` real entries; ``counts``: ``[G]``; ``windows``: ``[G]``, the valid windows of every record (``None``
+    where ``out=`` gave ``None``); ``spec``: the :class:`ProteinSketches`.  ``gene_begin``: the genes of contig i are records
+    ``gene_begin[i] .. gene_begin[i + 1]`` (``None`` when the records were not in contig order)."""
+
+    def __init__(self, sketches, counts, windows, gene_begin, spec, device, n, L=None, ctx_h=None):
+        self.sketches, self.counts, self.windows, self.gene_begin = sketches, counts, windows, gene_begin
+        self.spec, self.device, self.n = spec, device, n
+        self._L, self._ctx_h = L, ctx_h
+
+    def compare(self, pairs, out=None, stream=None):
+        """``(shared, union)`` of every pair of rows (``pga_sketch_pairs``): ``pairs`` is a contiguous int64 ``[P, 2]`` device
+        tensor of record indices; a pair with an index outside ``0 .. G - 1`` gets -1 in both.  ``out``: two contiguous int64
+        ``[P]`` objects with ``__cuda_array_interface__``, omitted: torch tensors.  The context of the call that made the sketches
+        must still be open."""
+        cai = getattr(pairs, "__cuda_array_interface__", None)
+        if not isinstance(cai, dict):
+            raise TypeError("pairs must have a __cuda_array_interface__ (a device tensor or array), not %r" % type(pairs).__name__)
+        shape = tuple(int(v) for v in cai["shape"])
+        if len(shape) != 2 or shape[1] != 2:
+            raise ValueError(f"pairs needs shape [P, 2], not {list(shape)}")
+        P = shape[0]
+        p_pairs = _group_output(pairs, "pairs", (P, 2), True)
+        if out is None:
+            try:
+                import torch
+            except ImportError:
+                raise TypeError("torch is not installed: pass out=, two device arrays with __cuda_array_interface__") from None
+            with torch.cuda.device(self.device):
+                out = (torch.empty(P, dtype=torch.int64, device="cuda"), torch.empty(P, dtype=torch.int64, device="cuda"))
+                if stream is None:
+                    stream = int(torch.cuda.current_stream().cuda_stream)
+        out = tuple(out)
+        if len(out) != 2:
+            raise ValueError("out must be (shared, union), %d objects were given" % len(out))
+        p_shared, p_union = _group_output(out[0], "shared", (P,), True), _group_output(out[1], "union", (P,), True)
+        p_sk = _group_output(self.sketches, "sketches", (self.n, self.spec.size), True)
+        p_cnt = _group_output(self.counts, "counts", (self.n,), True)
+        rc = self._L.pga_sketch_pairs(self._ctx_h, ctypes.c_void_p(p_sk), ctypes.c_void_p(p_cnt), self.n, self.spec.size, ctypes.c_void_p(p_pairs), P,
+                                      ctypes.c_void_p(p_shared), ctypes.c_void_p(p_union), ctypes.c_void_p(DeviceSequences._stream_of(out[0], stream)))
+        if rc != PGA_OK:
+            _raise(self._L, self._ctx_h, rc, "pga_sketch_pairs")
+        return out
+
+
+def sketches_into(L, ctx_h, batch_h, device, n_contigs, genes, tables, spec, out=None, stream=None):
+    """``pga_sketch_proteins`` on raw handles (what ``Context.protein_sketches`` and the finder's device call share): the sketches of
+    ``genes`` (GENE_DTYPE records of the resident batch) under ``tables`` into the three tensors of ``out``, or into new torch
+    tensors."""
+    if not isinstance(spec, ProteinSketches):
+        raise TypeError("the sketching rule must be a ProteinSketches, not %r" % type(spec).__name__)
+    genes = np.ascontiguousarray(genes, dtype=GENE_DTYPE)
+    n = len(genes)
+    p_tab = ctypes.c_void_p(0)
+    if tables is not None:
+        tables = np.ascontiguousarray(tables, np.int32)
+        if tables.shape != (n_contigs,):
+            raise ValueError(f"tables has {tables.size} entries for {n_contigs} contigs")
+        p_tab = ctypes.c_void_p(tables.ctypes.data)
+    elif spec.of == "protein":
+        raise ValueError("the protein unit needs tables=, the translation table of every contig")
+    s = spec.size
+    if out is None:
+        try:
+            import torch
+        except ImportError:
+            raise TypeError("torch is not installed: pass out=, three device arrays with __cuda_array_interface__") from None
+        with torch.cuda.device(device):
+            out = (torch.empty((n, s), dtype=torch.int64, device="cuda"), torch.empty(n, dtype=torch.int64, device="cuda"),
+                   torch.empty(n, dtype=torch.int64, device="cuda"))
+            if stream is None:
+                stream = int(torch.cuda.current_stream().cuda_stream)
+    out = tuple(out)
+    if len(out) != 3:
+        raise ValueError("out must be (sketches, counts, windows), %d objects were given" % len(out))
+    sketches, counts, windows = out
+    p_sk, p_cnt = _group_output(sketches, "sketches", (n, s), True), _group_output(counts, "counts", (n,), True)
+    p_win = _group_output(windows, "windows", (n,), False)
+    o = spec.opts()
+    rc = L.pga_sketch_proteins(ctx_h, batch_h, n, ctypes.c_void_p(genes.ctypes.data), p_tab, ctypes.byref(o), ctypes.c_void_p(p_sk),
+                               ctypes.c_void_p(p_cnt), ctypes.c_void_p(p_win), ctypes.c_void_p(DeviceSequences._stream_of(sketches, stream)))
+    if rc != PGA_OK:
+        _raise(L, ctx_h, rc, "pga_sketch_proteins")
+    gene_begin = None
+    if n == 0 or np.all(np.diff(genes["contig"]) >= 0):
+        gene_begin = np.searchsorted(genes["contig"], np.arange(n_contigs + 1)).astype(np.int64)
+    return DeviceSketches(sketches, counts, windows, gene_begin, spec, device, n, L, ctx_h)
+
+
+def _protein_sketches(self, batch, result_or_genes, spec, tables=None, out=None, stream=None):
+    """Bottom-s MinHash sketches of gene records of the resident ``batch``, on the device (``pga_sketch_proteins``): no letter comes
+    to the host.  ``result_or_genes``: a result of ``find_genes`` on the batch, or gene records of one (any subset or order -- the
+    representatives of ``protein_groups``, say; then with ``tables`` for the protein unit).  ``spec``: a :class:`ProteinSketches`.
+    ``tables``: translation table per contig (default: that of the model that won the contig).  ``out``: a 3-tuple ``(sketches
+    [G, size], counts [G], windows [G])`` of contiguous int64 objects with ``__cuda_array_interface__``, ``None`` allowed for the
+    last; omitted: torch tensors are allocated on the context's device under torch's current stream.  ``stream``: the stream that
+    last used the outputs, as in :class:`DeviceSequences`.  Returns a :class:`DeviceSketches`."""
+    genes = getattr(result_or_genes, "genes", result_or_genes)
+    if tables is None and isinstance(spec, ProteinSketches) and spec.of == "protein":
+        contigs = getattr(result_or_genes, "contigs", None)
+        if contigs is None:
+            raise ValueError("bare gene records carry no models: pass tables=, the translation table of every contig")
+        tables = _default_tables(self, contigs)
+    return sketches_into(self.L, self.h, batch.h, self.device, batch.n, genes, tables, spec, out, stream)
+
+
+def _protein_sketch_passes(self):
+    """The hashes that passed their record's threshold in the context's last ``protein_sketches`` call (``pga_sketch_passes``), -1
+    unless the library was built with ``-DPGA_SKETCH_COUNT_PASSES``."""
+    out = ctypes.c_int64(0)
+    rc = self.L.pga_sketch_passes(self.h, ctypes.byref(out))
+    if rc != PGA_OK:
+        _raise(self.L, self.h, rc, "pga_sketch_passes")
+    return int(out.value)
 
 
 START_FIELDS = ("total", "cscore", "sscore", "rscore", "uscore", "tscore", "gc_cont")      # PGA_START_* order
@@ -2785,6 +3055,8 @@ Context.start_candidates = _start_candidates
 Context.kmer_counts = _kmer_counts
 Context.protein_groups = _protein_groups
 Context.protein_groups_stats = _protein_groups_stats
+Context.protein_sketches = _protein_sketches
+Context.protein_sketch_passes = _protein_sketch_passes
 Context.train = _train
 Context.train_batch = _train_batch
 Context.upload = _upload

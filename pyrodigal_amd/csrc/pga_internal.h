@@ -256,6 +256,7 @@ struct pga_ctx {
     std::vector<double> model_scores;                  // pga_model_scores: [contig][model_scores_nm] path scores, NaN: no contribution
     int model_scores_nm = 0;
     int64_t group_stats[2] = {0, 0};                   // pga_protein_groups_stats: rounds and differing pairs of the last pga_group_proteins call
+    int64_t sketch_passes = -1;                        // pga_sketch_passes: insertions tried in the last pga_sketch_proteins call (PGA_SKETCH_COUNT_PASSES builds), -1: not counted
     int poison = -1;                                   // pga_debug_poison: the fill byte of newly acquired float buffers, -1: off
     std::vector<int64_t> render_seqnums;               // pga_render_seqnums: the seqnum of every contig of the batches rendered next (empty: first_seqnum + i)
 };

@@ -99,6 +99,7 @@ int64_t gene_residues(const pga_gene& G, const int include_stop) {
 #include "gene_windows.inl"
 #include "kmer_counts.inl"
 #include "protein_groups.inl"
+#include "protein_sketches.inl"
 #include "start_candidates.inl"
 
 }  // namespace
@@ -590,6 +591,133 @@ extern "C" int pga_group_proteins(pga_ctx* c, const pga_batch* batch, int64_t n_
     const hipError_t es = hipStreamSynchronize(st);            // (also after a failure: nothing of the lease is in use when it goes back)
     if (e == hipSuccess) e = es;
     if (e == hipSuccess) { *n_groups = h_small[1]; c->group_stats[0] = rounds; c->group_stats[1] = differing; }
+    pga_upload_lease_give(c);
+    return pga_hip_try_(c, e, fn);
+}
+
+// ---- MinHash sketches (protein_sketches.inl) -----------------------------------------------------------------------------------
+extern "C" int pga_sketch_passes(pga_ctx* c, int64_t* out) {
+    if (!c || !out) return PGA_EINVAL;
+    *out = c->sketch_passes;
+    return PGA_OK;
+}
+
+extern "C" int pga_sketch_proteins(pga_ctx* c, const pga_batch* batch, int64_t n_genes, const pga_gene* genes, const int32_t* table_of_contig,
+                                   const pga_sketch_opts* o, int64_t* d_sketch, int64_t* d_count, int64_t* d_windows, void* stream) {
+    if (!c) return PGA_EINVAL;
+    const char* const fn = "pga_sketch_proteins";
+    auto bad = [&](const std::string& msg) { c->err = std::string(fn) + ": " + msg; return PGA_EINVAL; };
+    if (!batch || !o || n_genes < 0 || (n_genes > 0 && !genes)) return bad("bad arguments");
+    const pga_batch_view bv = pga_batch_peek(batch);
+    if (bv.ctx != c) return bad("the batch belongs to another context");
+    // ---- validation: all of it on the host, before anything is allocated or launched ----
+    if (o->unit != PGA_SKETCH_PROTEIN && o->unit != PGA_SKETCH_GENE) return bad("unit must be PGA_SKETCH_PROTEIN or PGA_SKETCH_GENE, not " + std::to_string(o->unit));
+    const bool protein = o->unit == PGA_SKETCH_PROTEIN;
+    const int kmax = protein ? 8 : 32;
+    if (o->k < 1 || o->k > kmax) return bad("k = " + std::to_string(o->k) + " is outside 1 .. " + std::to_string(kmax) + " for this unit");
+    if (o->size < 1 || o->size > 64) return bad("size = " + std::to_string(o->size) + " is outside 1 .. 64");
+    if (o->unknown_residue <= 0 || o->unknown_residue > 127) return bad("`unknown_residue` must be a single ASCII character");
+    if (n_genes > INT32_MAX) return bad("more than 2^31 - 1 gene records");
+    if (protein && n_genes > 0) {
+        if (!table_of_contig) return bad("table_of_contig is NULL");
+        for (int i = 0; i < bv.n; i++)
+            if (!table_known(table_of_contig[i])) return bad("contig " + std::to_string(i) + ": " + std::to_string(table_of_contig[i]) + " is not a valid translation table index");
+    }
+    for (int64_t g = 0; g < n_genes; g++)
+        if (!gene_inside(bv, genes[g])) return bad("gene " + std::to_string(g) + " lies outside its contig");
+    c->sketch_passes = -1;
+    if (n_genes == 0) return PGA_OK;
+    const struct { const char* name; const void* p; } outs[3] = {{"d_sketch", d_sketch}, {"d_count", d_count}, {"d_windows", d_windows}};
+    if (!d_sketch) return bad("d_sketch is NULL");
+    if (!d_count) return bad("d_count is NULL");
+    for (const auto& x : outs) if ((uintptr_t)x.p % 8u) return bad(std::string(x.name) + " is not aligned to its 8-byte elements");
+    if (hipSetDevice(c->device) != hipSuccess) return PGA_EDEVICE;
+    for (const auto& x : outs) if (x.p) if (const int rc = pga_device_memory_(c, x.p, fn, x.name)) return rc;
+    if (protein) { const int rc = tables_ready(c); if (rc) return rc; }
+    // ---- the lease: the records as the kernel reads them, and behind them the class table and a counter ----
+    const size_t G = (size_t)n_genes;
+    const size_t row_b = sizeof(GrpRow) * G, p_cls = (row_b + 255) & ~(size_t)255, p_small = p_cls + 256, p_end = p_small + 256;
+    pga_upload_lease L{};
+    { const int rc = pga_upload_lease_take(c, p_end, &L); if (rc) return rc; }
+    GrpRow* const rows = (GrpRow*)L.pin;
+    for (size_t g = 0; g < G; g++) {
+        const pga_gene& R = genes[g];
+        const bool fwd = R.strand == 1;
+        GrpRow& w = rows[g];
+        w.base = bv.ct[R.contig].base; w.L = bv.ct[R.contig].len;
+        w.q0 = fwd ? R.begin - 1 : R.end - 1;
+        w.n = protein ? (int32_t)gene_residues(R, o->include_stop) : R.end - R.begin + 1;
+        // partial flags are in sequence orientation; the gene's own first codon follows its strand
+        const bool start_edge = fwd ? R.partial_begin != 0 : R.partial_end != 0;
+        w.bits = (fwd ? 1u : 0u) | (start_edge ? 2u : 0u) | (protein ? (uint32_t)table_of_contig[R.contig] << 8 : 0u);
+    }
+    memcpy(L.pin + p_cls, o->classes, 128);
+    memset(L.pin + p_cls + 128, 0, p_small + 256 - (p_cls + 128));
+    SkArgs a{};
+    a.g.seq = bv.d_seq; a.g.row = (const GrpRow*)L.dev; a.g.n = n_genes; a.g.unk = o->unknown_residue; a.g.strict = o->strict;
+    a.classes = (const uint8_t*)(L.dev + p_cls);
+    a.k = o->k; a.s = o->size; a.bits = protein ? 8 : 2;
+    a.salt = ((uint64_t)o->seed + 1ull) * 0x9E3779B97F4A7C15ull;
+    a.d_sketch = d_sketch; a.d_count = d_count; a.d_windows = d_windows;
+#ifdef PGA_SKETCH_COUNT_PASSES
+    a.passed = (unsigned long long*)(L.dev + p_small);
+#endif
+    hipStream_t st = L.st;
+    // behind what the caller's stream holds; complete on return
+    hipError_t e = hipEventRecord(L.ev, (hipStream_t)stream);
+    if (e == hipSuccess) e = hipStreamWaitEvent(st, L.ev, 0);
+    if (e == hipSuccess) e = hipMemcpyAsync(L.dev, L.pin, p_end, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) {
+        // a wave per record, and several rounds of them per wave where there are many
+        const int64_t per_block = kRowThreads / 64;
+        const dim3 grid((unsigned)std::min<int64_t>((n_genes + per_block - 1) / per_block, 16384)), block(kRowThreads);
+        if (protein) hipLaunchKernelGGL((k_sketch<kGrpProtein>), grid, block, 0, st, a);
+        else hipLaunchKernelGGL((k_sketch<kGrpGene>), grid, block, 0, st, a);
+        e = hipGetLastError();
+    }
+#ifdef PGA_SKETCH_COUNT_PASSES
+    if (e == hipSuccess) e = hipMemcpyAsync(L.pin + p_small, L.dev + p_small, 8, hipMemcpyDeviceToHost, st);
+#endif
+    const hipError_t es = hipStreamSynchronize(st);            // (also after a failure: nothing of the lease is in use when it goes back)
+    if (e == hipSuccess) e = es;
+#ifdef PGA_SKETCH_COUNT_PASSES
+    if (e == hipSuccess) c->sketch_passes = *(volatile long long*)(L.pin + p_small);
+#endif
+    pga_upload_lease_give(c);
+    return pga_hip_try_(c, e, fn);
+}
+
+extern "C" int pga_sketch_pairs(pga_ctx* c, const int64_t* d_sketch, const int64_t* d_count, int64_t n_genes, int32_t size,
+                                const int64_t* d_pairs, int64_t n_pairs, int64_t* d_shared, int64_t* d_union, void* stream) {
+    if (!c) return PGA_EINVAL;
+    const char* const fn = "pga_sketch_pairs";
+    auto bad = [&](const std::string& msg) { c->err = std::string(fn) + ": " + msg; return PGA_EINVAL; };
+    // ---- validation: all of it on the host, before anything is launched ----
+    if (n_genes < 0 || n_pairs < 0) return bad("bad arguments");
+    if (size < 1 || size > 64) return bad("size = " + std::to_string(size) + " is outside 1 .. 64");
+    if (n_genes > INT32_MAX) return bad("more than 2^31 - 1 gene records");
+    if (n_pairs == 0) return PGA_OK;
+    const struct { const char* name; const void* p; bool needed; } ptrs[5] = {{"d_sketch", d_sketch, n_genes > 0}, {"d_count", d_count, n_genes > 0},
+        {"d_pairs", d_pairs, true}, {"d_shared", d_shared, true}, {"d_union", d_union, true}};
+    for (const auto& x : ptrs) if (x.needed && !x.p) return bad(std::string(x.name) + " is NULL");
+    for (const auto& x : ptrs) if ((uintptr_t)x.p % 8u) return bad(std::string(x.name) + " is not aligned to its 8-byte elements");
+    if (hipSetDevice(c->device) != hipSuccess) return PGA_EDEVICE;
+    for (const auto& x : ptrs) if (x.p && x.needed) if (const int rc = pga_device_memory_(c, x.p, fn, x.name)) return rc;
+    SkPairArgs a{};
+    a.sketch = d_sketch; a.count = d_count; a.pairs = d_pairs; a.n_genes = n_genes; a.n_pairs = n_pairs; a.s = size;
+    a.d_shared = d_shared; a.d_union = d_union;
+    pga_upload_lease L{};
+    { const int rc = pga_upload_lease_take(c, 0, &L); if (rc) return rc; }
+    hipError_t e = hipEventRecord(L.ev, (hipStream_t)stream);
+    if (e == hipSuccess) e = hipStreamWaitEvent(L.st, L.ev, 0);
+    if (e == hipSuccess) {
+        const int64_t per_block = kRowThreads / 64;
+        const dim3 grid((unsigned)std::min<int64_t>((n_pairs + per_block - 1) / per_block, 16384)), block(kRowThreads);
+        hipLaunchKernelGGL(k_sketch_pairs, grid, block, 0, L.st, a);
+        e = hipGetLastError();
+    }
+    const hipError_t es = hipStreamSynchronize(L.st);
+    if (e == hipSuccess) e = es;
     pga_upload_lease_give(c);
     return pga_hip_try_(c, e, fn);
 }

@@ -2124,6 +2124,29 @@ cdef class GeneFinder:
         return self._find_tensor_batch("find_groups_batch", sequences, groups, out, stream, translate, training_infos, regions, circular, sets,
                                        trim_terminal_repeats)
 
+    def find_sketches_batch(self, object sequences, object sketches, *, object out=None, object stream=None, bint translate=False,
+                            object training_infos=None, object regions=None, object circular=None, object sets=None,
+                            object trim_terminal_repeats=None):
+        """`find_genes_batch`, and a bottom-s MinHash sketch of every gene's predicted protein (or of its bases) on the device:
+        returns `(genes, device_sketches)`, the list of `Genes` that `find_genes_batch` returns for the same arguments and a
+        `DeviceSketches`.
+
+        `sketches`: a `ProteinSketches` -- window length, sketch size, unit, seed, letter classes and the translation's options.
+        Gene g of the request, contig after contig (`device_sketches.gene_begin`), gets row `sketches[g]`: its at most `size`
+        smallest distinct window hashes in ascending order, `INT64_MAX` behind the `counts[g]` real ones; `windows[g]` is the number
+        of its valid windows.  A sketch is a property of the gene's string alone (`ProteinSketches.sketch_of`), so the rows of
+        several requests can be compared; `device_sketches.compare(pairs)` estimates the resemblance of pairs of rows on the device.
+        The tensors are written while the batch is resident, on the batch the finder called, each contig under the table of the model
+        that won it.  `out`: a `(sketches, counts, windows)` tuple of int64 device tensors to write (anything with
+        `__cuda_array_interface__`; `None` for the last), omitted: torch tensors allocated under torch's current stream; `stream`:
+        the stream that last used them.  Every option of `find_genes_batch` applies and `sequences` may be a `DeviceSequences`.  The
+        request is a device call of its own: one set of tensors per request, so a request that `training_infos` would split into
+        several device calls is a `ValueError`."""
+        if not isinstance(sketches, _cabi.ProteinSketches):
+            raise TypeError("`sketches` must be a ProteinSketches, not %r" % type(sketches).__name__)
+        return self._find_tensor_batch("find_sketches_batch", sequences, sketches, out, stream, translate, training_infos, regions, circular, sets,
+                                       trim_terminal_repeats)
+
     def find_starts_batch(self, object sequences, object starts, *, object out=None, object stream=None, bint translate=False,
                           object training_infos=None, object regions=None, object circular=None, object sets=None,
                           object trim_terminal_repeats=None):
@@ -2151,7 +2174,7 @@ cdef class GeneFinder:
 
     cdef tuple _find_tensor_batch(self, str method, object sequences, object spec, object out, object stream, bint translate,
                                   object training_infos, object regions, object circular, object sets, object trim_terminal_repeats):
-        """`find_proteins_batch` / `find_labels_batch` / `find_windows_batch` / `find_counts_batch` / `find_groups_batch` / `find_starts_batch`: (the `Genes` of
+        """`find_proteins_batch` / `find_labels_batch` / `find_windows_batch` / `find_counts_batch` / `find_groups_batch` / `find_sketches_batch` / `find_starts_batch`: (the `Genes` of
         `find_genes_batch`, what the rule `spec` wrote on the device)."""
         cdef dict tok = {"spec": spec, "out": out, "stream": stream, "result": None, "method": method}
         cdef list circ, tr_search
