@@ -143,7 +143,7 @@ int         pga_dp_stats(const pga_ctx*, int32_t out[8]);
  *   out[2] the step-schedule kernels of every group   out[3] reserved (0) */
 int         pga_dp_timings(const pga_ctx*, double out[4]);
 /* How the node extraction of the last pga_find_genes / pga_find_genes_batch / pga_nodes_stage call on this context ran (diagnostics):
- *   out[0] extraction passes (1; 2 when a tile of the batch did not fit the half-density staging and the batch was extracted again)
+ *   out[0] extraction passes (1; 2 when a tile of the batch did not fit the half-density staging, or its pool of stop values, and the batch was extracted again)
  *   out[1] reserved (0) */
 int         pga_extract_stats(const pga_ctx*, int32_t out[2]);
 /* How a connection-scoring launch over chains of these node counts would be cut (host arithmetic only, no device needed;

@@ -383,7 +383,8 @@ class Context:
         return {"dp_ms": out[0], "topo_ms": out[1], "sched_ms": out[2]}
 
     def extract_stats(self):
-        """How the last node extraction ran: passes (2: a tile overflowed the half-density staging and the batch was extracted again)."""
+        """How the last node extraction ran: passes (2: a tile overflowed the half-density staging, or the pool of stop values of its
+        workgroup, and the batch was extracted again)."""
         out = (ctypes.c_int32 * 2)()
         rc = self.L.pga_extract_stats(self.h, out)
         if rc != PGA_OK:

@@ -1758,6 +1758,13 @@ static int find_impl_cov(pga_ctx* c, const pga_batch* batch, const pga_params* p
         // extracted again with full staging, and the context keeps that (PGA_STAGE_FULL=1: from the start).
         if (getenv("PGA_STAGE_FULL")) f->stage_full = true;
         bool stage_full = f->stage_full;
+        // Stop values of the extraction: a thread of k_extract_tile lists up to four per strand in LDS and a pool of the workgroup takes the
+        // rest; a tile that exhausts the pool (a full tile of (GT)n) raises bit 1 of the flag and the batch is extracted again with a
+        // value for every position.  That choice is the batch's, the context does not keep it.  (PGA_EXTRACT_C=1 .. 4 / PGA_EXTRACT_POOL=
+        // 0 .. 128: fewer list slots / pool entries, so that the tests reach the pool and the second pass on small inputs; PGA_EXTRACT_C=0:
+        // a value for every position from the start)
+        int ex_c = getenv("PGA_EXTRACT_C") ? std::max(0, std::min(4, atoi(getenv("PGA_EXTRACT_C")))) : 4;
+        const int ex_pool = getenv("PGA_EXTRACT_POOL") ? std::max(0, std::min(128, atoi(getenv("PGA_EXTRACT_POOL")))) : 128;
         c->extract_passes = 0;
         for (;;) {
             const bool half = !stage_full;
@@ -1775,15 +1782,19 @@ static int find_impl_cov(pga_ctx* c, const pga_batch* batch, const pga_params* p
                 pga_launch_extract(d_dig, total, d_ct, NC, tt, P, ga[g], batch->d_tiles, batch->n_tiles, batch->d_tile0, d_tile_first, d_tile_last,
                                    d_tile_count + (size_t)g * (batch->n_tiles + 1), d_tile_off + (size_t)g * (batch->n_tiles + 1), d_cbase + (size_t)g * (NC + 1),
                                    d_tile_scount + (size_t)g * (batch->n_tiles + 1), d_tile_soff + (size_t)g * (batch->n_tiles + 1), d_sbase + (size_t)g * (NC + 1),
-                                   masks, st, ((meta_run && NM > 0) || multi) ? d_enabled + (size_t)g * NC : nullptr);
+                                   masks, st, ((meta_run && NM > 0) || multi) ? d_enabled + (size_t)g * NC : nullptr, ex_c, ex_pool);
             }
             HT(c, hipMemcpyAsync(h_xa, d_xa, sizeof(int32_t) * xa_words, hipMemcpyDeviceToHost, st));      // flag, counts, offsets, enabled groups
             HT(c, hipGetLastError());
             HT(c, hipStreamSynchronize(st));
             c->extract_passes++;
-            if (!half || h_st_overflow[0] == 0) break;
-            stage_full = true;
-            if (!getenv("PGA_STAGE_SHIFT")) f->stage_full = true;       // (the test knob leaves the context as it was)
+            const bool staging_overflow = half && (h_st_overflow[0] & 1), pool_exhausted = ex_c > 0 && (h_st_overflow[0] & 2);
+            if (!staging_overflow && !pool_exhausted) break;
+            if (pool_exhausted) ex_c = 0;
+            if (staging_overflow) {
+                stage_full = true;
+                if (!getenv("PGA_STAGE_SHIFT")) f->stage_full = true;       // (the test knob leaves the context as it was)
+            }
         }
         if (h_moff) { const int rc = fetch_mask_union(c, R, h_moff, d_union_iv, NC); if (rc) return rc; }
 

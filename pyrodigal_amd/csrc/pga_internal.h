@@ -238,7 +238,7 @@ struct pga_ctx {
     int n_models = 0;
     int32_t dp_stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};    // pga_dp_stats
     double dp_timings[4] = {0, 0, 0, 0};               // pga_dp_timings
-    int32_t extract_passes = 0;                        // pga_extract_stats: extraction passes of the last call (2: a tile overflowed the half-density staging)
+    int32_t extract_passes = 0;                        // pga_extract_stats: extraction passes of the last call (2: a tile overflowed the half-density staging, or its pool of stop values)
     // pga_render_genes: buffers kept across calls and grown as needed (render.hip): device scratch, device text, pinned text and
     // a small pinned block for the totals; the text of a result lives in render_host until the next call on the context
     char* render_dev = nullptr;  size_t render_dev_cap = 0;

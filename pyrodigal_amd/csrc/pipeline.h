@@ -31,7 +31,8 @@ struct GroupArrays {
     // staging: the nodes of the tile that starts at global position g, packed in order from slot 2 g (two slots per position: every
     // position can hold a node on either strand) -- or, st_half = s > 0, from slot g >> s with room for one node per 2^s positions
     // of the tile (s = 1 in production: sequence has a node every 25 positions or so, periodic worst cases reach one in two); a
-    // tile that does not fit says so in *st_overflow and the caller extracts again with the full staging
+    // tile that does not fit says so in bit 0 of *st_overflow and the caller extracts again with the full staging (bit 1: a tile's
+    // pool of stop values ran out, see pga_launch_extract)
     int32_t* st_ndx; int32_t* st_sv;         // ndx, stop_val
     uint8_t* st_info;                        // type | edge << 2 | reverse << 3
     int32_t st_half = 0; int32_t* st_overflow = nullptr;
@@ -98,7 +99,10 @@ void pga_launch_extract(const uint8_t* d_dig, int64_t total, const ContigDesc* d
                         int32_t* d_tile_first, int32_t* d_tile_last, int32_t* d_tile_count, int32_t* d_tile_off, int32_t* d_cbase,
                         int32_t* d_tile_scount, int32_t* d_tile_soff, int32_t* d_sbase /* the same three for stop nodes only */,
                         MaskList masks, hipStream_t st,
-                        const uint8_t* d_enabled = nullptr /* per contig: extract it in this group?  nullptr = every contig */);
+                        const uint8_t* d_enabled = nullptr /* per contig: extract it in this group?  nullptr = every contig */,
+                        int ex_c = 4 /* stop values a thread lists per strand, 1 .. 4; 0: a value for every position (k_extract_tile<false>) */,
+                        int ex_pool = 128 /* entries of the workgroup's pool for what the lists do not hold, 0 .. 128; a tile that needs
+                                             more raises bit 1 of *ga.st_overflow (bit 0: the half-density staging did not fit) */);
 void pga_launch_place(const ContigDesc* d_ct, const TileDesc* d_tiles, int n_tiles, const int32_t* d_tile_off, const int32_t* d_tile_soff,
                       const GroupArrays& ga, hipStream_t st);
 // Overlapping starts over (chain, stop node) pairs instead of over every chain node (pga_launch_score with `stops`):

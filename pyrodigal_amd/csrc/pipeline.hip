@@ -239,18 +239,74 @@ __device__ __forceinline__ TileGeom tile_geom(const TileDesc td, const int L) { 
 // edge start of an open contig, lib.pyx:1975-1982, 2070-2077).  LSC comes from a third scan over the tile; where it has to
 // look left of the tile (the stop sits in the tile's first min_gene positions) the thread walks back codon by codon -- a
 // start codon turns up every twenty codons or so.
+// The stop values of a thread's nodes wait in LDS for the packing loop (only the thread itself reads them back; they are in LDS because
+// the position is a run-time index).  COMPACT: a thread holds about one node among its twelve positions, so it keeps a LIST of up to
+// EX_C values per strand, appended in the order its candidate loops find them; a nibble per forward position (48 bits per strand, in
+// registers) says which list slot the position's node took, so the packing loop reads them back in position order.  What a thread finds
+// beyond its list -- (GT)n has a GTG start at every second position, six per strand and thread -- goes to a pool of EX_POOL entries that
+// the workgroup shares (nibble EX_IN_POOL: the packing loop searches the pool for its key); a tile that exhausts the pool says so in bit 1
+// of *st_overflow and the caller extracts the batch again with the other instantiation (!COMPACT: a value for every position, 24 KB,
+// five workgroups per CU instead of eight), so results never depend on EX_C, on the pool or on which instantiation ran.
+constexpr int EX_C = 4;                // list slots per thread and strand
+constexpr int EX_POOL = 128;           // pool entries per workgroup
+constexpr unsigned EX_IN_POOL = 15u;   // slot nibble: the value is in the pool
+template <bool COMPACT>
 struct ExShared {
     int lsc[3][256];                   // last start codon of relative frame r at or before the thread's positions (strand-local order)
-    int scm[256];                      // the thread's 12 positions: bit q = start codon at i0 + q
-    int32_t sv[2][EX_PER_THREAD][256]; // stop_val of the node at the thread's k-th forward position, per strand
+    uint16_t scm[256];                 // the thread's 12 positions: bit q = start codon at i0 + q
+    int32_t sv[2][COMPACT ? EX_C : EX_PER_THREAD][256];     // stop_val per strand: the thread's n-th node (COMPACT) / the node at its k-th forward position
+    int32_t pool_key[COMPACT ? EX_POOL : 1], pool_sv[COMPACT ? EX_POOL : 1];       // key: thread | strand << 8 | forward position k << 9
+    int pool_n;                        // entries asked for (past ex_pool: the tile has exhausted the pool)
     int wmin[3][4], wmax[3][4], wlsc[3][4];
-    int carry_ns[3], carry_ps[3];
+    int carry_ns[2][3], carry_ps[2][3];     // per strand (0 forward, 1 reverse) and frame
     int wsum[4];
 };
 
 // stop_codons / start_codons: bit (b0 | b1 << 2 | b2 << 4) set when the codon of 2-bit digits b0 b1 b2 is one (codon_is_stop /
 // codon_is_start tabulated by the host for the translation table; a codon with an unknown base is neither)
-struct ExParams { int tt, closed, min_gene, min_edge_gene; unsigned long long stop_codons, start_codons; };
+// ex_c / ex_pool: list slots and pool entries in use (EX_C and EX_POOL; fewer: the tests' knobs PGA_EXTRACT_C / PGA_EXTRACT_POOL)
+struct ExParams { int tt, closed, min_gene, min_edge_gene; unsigned long long stop_codons, start_codons; int ex_c, ex_pool; };
+
+// Tile carries: the nearest stop of a frame in the tiles that follow (next stop) / precede (previous stop) in strand-local order, same
+// contig.  Threads 0 - 11 fetch the twelve values of both strands at kernel entry -- strand t / 6, next stop for t % 6 < 3, frame t % 3 --
+// the neighbouring tile's contig and its summary with two independent loads issued before the forward strand is decoded (the walk was a
+// chain of three dependent loads at the head of each strand pass, with three wavefronts waiting at the barrier for the first);
+// carry_finish walks on only where the neighbour has no stop of the frame, and stores before the first barrier.
+struct ExCarry { int k, step, v, same; };
+__device__ __forceinline__ ExCarry carry_begin(const int t, const int tile, const int contig, const TileDesc* __restrict__ tiles, const int n_tiles,
+                                               const int32_t* __restrict__ tile_first, const int32_t* __restrict__ tile_last) {
+    ExCarry c{0, 0, 0, 0};
+    if (t < 12) {
+        const int s = t / 6, f = t % 3;
+        const bool ns = t % 6 < 3;
+        const int up = s == 0 ? 1 : -1;                 // tile index step towards larger strand-local positions
+        c.step = ns ? up : -up;
+        c.k = tile + c.step;
+        c.v = ns ? EX_NONE_HI : -1;
+        if (c.k >= 0 && c.k < n_tiles) {
+            c.same = tiles[c.k].contig == contig;
+            c.v = (ns ? tile_first : tile_last)[((int64_t)s * n_tiles + c.k) * 3 + f];
+        }
+    }
+    return c;
+}
+template <bool COMPACT>
+__device__ __forceinline__ void carry_finish(ExShared<COMPACT>& S, ExCarry c, const int t, const int contig, const TileDesc* __restrict__ tiles, const int n_tiles,
+                                             const int32_t* __restrict__ tile_first, const int32_t* __restrict__ tile_last) {
+    if (t < 12) {
+        const int s = t / 6, f = t % 3;
+        const bool ns = t % 6 < 3;
+        const int none = ns ? EX_NONE_HI : -1;
+        const int32_t* __restrict__ arr = ns ? tile_first : tile_last;
+        if (!c.same) c.v = none;
+        else while (c.v == none) {
+            c.k += c.step;
+            if (c.k < 0 || c.k >= n_tiles || tiles[c.k].contig != contig) break;
+            c.v = arr[((int64_t)s * n_tiles + c.k) * 3 + f];
+        }
+        if (ns) S.carry_ns[s][f] = c.v; else S.carry_ps[s][f] = c.v;
+    }
+}
 
 __device__ __forceinline__ unsigned pairrev32(unsigned x) {      // pair t -> pair 15 - t
     x = __brev(x);
@@ -306,43 +362,23 @@ __device__ __forceinline__ void strand_codon_masks(const TileGeom G, const uint8
 }
 
 // The nodes of one strand among the thread's twelve forward positions a + 12 t + k: bit k of `nodes`, type | edge << 2 in the
-// k-th nibble of `infos`, stop_val in S.sv[strand][k][t].  Thread t owns the SAME forward positions on both strands; on the
-// reverse strand they are the strand-local positions i0 .. i0 + 11 with i0 = (L - 1 - a) - 12 t - 11, so strand-local order runs
-// against t.  Frames are counted relative to i0 (r = q % 3; i0 % 3 is the same for every thread of the tile).
-template <int STRAND>
-__device__ __forceinline__ void extract_strand(ExShared& S, const TileGeom G, const uint8_t* __restrict__ d, const int64_t base, const int64_t total,
-                                               const int tile, const TileDesc* __restrict__ tiles, const int n_tiles,
+// k-th nibble of `infos`, stop_val in S.sv (the list slot in the k-th nibble of `slots`; !COMPACT: S.sv[strand][k][t]).  Thread t owns
+// the SAME forward positions on both strands; on the reverse strand they are the strand-local positions i0 .. i0 + 11 with
+// i0 = (L - 1 - a) - 12 t - 11, so strand-local order runs against t.  Frames are counted relative to i0 (r = q % 3; i0 % 3 is the
+// same for every thread of the tile).  `carry`: what carry_begin left in threads 0 - 11; the forward pass finishes and stores it.
+template <int STRAND, bool COMPACT>
+__device__ __forceinline__ void extract_strand(ExShared<COMPACT>& S, const TileGeom G, const uint8_t* __restrict__ d, const int64_t base, const int64_t total,
+                                               const int contig, const TileDesc* __restrict__ tiles, const int n_tiles,
                                                const int32_t* __restrict__ tile_first, const int32_t* __restrict__ tile_last, const ExParams P,
-                                               const int n_masks, const int2* __restrict__ mv, unsigned& nodes, unsigned long long& infos) {
+                                               const int n_masks, const int2* __restrict__ mv, const ExCarry carry,
+                                               unsigned& nodes, unsigned long long& infos, unsigned long long& slots) {
     constexpr bool FWD = STRAND == 1;
     const int t = threadIdx.x, lane = t & 63, w = t >> 6, L = G.L, s = FWD ? 0 : 1;
     const int lo = G.lo(STRAND), end = lo + G.len;
     const int top = FWD ? G.a : L - 1 - G.a - (EX_PER_THREAD - 1);        // i0 of thread 0
     const int i0 = FWD ? top + t * EX_PER_THREAD : top - t * EX_PER_THREAD;
     const int f0 = ((top % 3) + 3) % 3;                                    // absolute frame of relative frame 0
-    nodes = 0; infos = 0;
-    // tile carries: nearest stop of each frame in the tiles that follow / precede in strand-local order (same contig)
-    if (t < 6) {
-        const int f = t % 3;
-        const int64_t so = (int64_t)s * n_tiles;
-        const int contig = tiles[tile].contig;
-        const int up = FWD ? 1 : -1;                    // tile index step towards larger strand-local positions
-        if (t < 3) {
-            int v = EX_NONE_HI;
-            for (int k = tile + up; k >= 0 && k < n_tiles && tiles[k].contig == contig; k += up) {
-                v = tile_first[(so + k) * 3 + f];
-                if (v != EX_NONE_HI) break;
-            }
-            S.carry_ns[f] = v;
-        } else {
-            int v = -1;
-            for (int k = tile - up; k >= 0 && k < n_tiles && tiles[k].contig == contig; k -= up) {
-                v = tile_last[(so + k) * 3 + f];
-                if (v != -1) break;
-            }
-            S.carry_ps[f] = v;
-        }
-    }
+    nodes = 0; infos = 0; slots = 0;
     unsigned inm, cw, stm, scm;
     strand_codon_masks<STRAND>(G, d, base, total, i0, P.stop_codons, P.start_codons, inm, cw, stm, scm);
     int mn[3], mx[3], ls[3];
@@ -381,7 +417,8 @@ __device__ __forceinline__ void extract_strand(ExShared& S, const TileGeom G, co
         const int w_mn = __shfl(mn[r], l_first, 64), w_mx = __shfl(mx[r], l_last, 64), w_ls = __shfl(ls[r], l_lastc, 64);
         if (lane == 0) { S.wmin[r][w] = hs ? w_mn : EX_NONE_HI; S.wmax[r][w] = hs ? w_mx : -1; S.wlsc[r][w] = hc ? w_ls : -1; }
     }
-    S.scm[t] = (int)scm;
+    S.scm[t] = (uint16_t)scm;
+    if (FWD) carry_finish(S, carry, t, contig, tiles, n_tiles, tile_first, tile_last);      // both strands' carries: fetched at kernel entry
     __syncthreads();
     int nxt[3], prv[3];
 #pragma unroll
@@ -395,8 +432,8 @@ __device__ __forceinline__ void extract_strand(ExShared& S, const TileGeom G, co
             if (dn_side) { b = max(b, S.wmax[r][k]); e = max(e, S.wlsc[r][k]); }
         }
         const int f = (f0 + r) % 3;
-        nxt[r] = a == EX_NONE_HI ? S.carry_ns[f] : a;
-        prv[r] = b == -1 ? S.carry_ps[f] : b;
+        nxt[r] = a == EX_NONE_HI ? S.carry_ns[s][f] : a;
+        prv[r] = b == -1 ? S.carry_ps[s][f] : b;
         S.lsc[r][t] = e;
     }
     __syncthreads();
@@ -446,9 +483,19 @@ __device__ __forceinline__ void extract_strand(ExShared& S, const TileGeom G, co
     };
     auto put = [&](const int q, const int info, const int sv) {
         const int k = FWD ? q : EX_PER_THREAD - 1 - q;
+        if constexpr (COMPACT) {
+            const int n = __popc(nodes);           // the thread's nodes of this strand so far
+            if (n < P.ex_c) {
+                S.sv[s][n][t] = sv;
+                slots |= (unsigned long long)n << (4 * k);
+            } else {
+                slots |= (unsigned long long)EX_IN_POOL << (4 * k);
+                const int e = atomicAdd(&S.pool_n, 1);
+                if (e < P.ex_pool) { S.pool_key[e] = t | (s << 8) | (k << 9); S.pool_sv[e] = sv; }
+            }
+        } else S.sv[s][k][t] = sv;
         nodes |= 1u << k;
         infos |= (unsigned long long)info << (4 * k);
-        S.sv[s][k][t] = sv;
     };
     // candidates: stop codons, start codons, the first position of each frame (edge starts) and the last (virtual stops)
     unsigned cand = stm | scm;
@@ -554,25 +601,39 @@ k_tile_stops(const uint8_t* __restrict__ dig, int64_t total, const ContigDesc* _
     }
 }
 
-__global__ void __launch_bounds__(256)
+// (eight workgroups per CU: at 13 KB of LDS the scalar registers were the limit -- 106 of them are seven wavefronts per SIMD; held to
+//  eight the compiler keeps 39 scalars in lanes of vector registers instead, 54 vector registers and no scratch either way)
+template <bool COMPACT>
+__global__ void __launch_bounds__(256, COMPACT ? 8 : 5)
 k_extract_tile(const uint8_t* __restrict__ dig, int64_t total, const ContigDesc* __restrict__ ct, const TileDesc* __restrict__ tiles, int n_tiles,
                const int32_t* __restrict__ tile_first, const int32_t* __restrict__ tile_last, ExParams P, GroupArrays ga, MaskList masks,
                const uint8_t* __restrict__ enabled, int32_t* __restrict__ tile_count, int32_t* __restrict__ tile_scount) {
-    __shared__ ExShared S;
+    __shared__ ExShared<COMPACT> S;
     __shared__ int s_stops;
     const int tile = blockIdx.x, t = threadIdx.x;
     const TileDesc td = tiles[tile];
     if (enabled != nullptr && !enabled[td.contig]) { if (t == 0) { tile_count[tile] = 0; tile_scount[tile] = 0; } return; }     // the contig keeps zero nodes in this group
-    if (t == 0) s_stops = 0;
+    const ExCarry carry = carry_begin(t, tile, td.contig, tiles, n_tiles, tile_first, tile_last);
+    if (t == 0) { s_stops = 0; S.pool_n = 0; }
     const ContigDesc cd = ct[td.contig];
     const TileGeom G = tile_geom(td, cd.len);
     const uint8_t* __restrict__ d = dig + cd.base;
     const int n_masks = masks.off ? masks.off[td.contig + 1] - masks.off[td.contig] : 0;
     const int2* __restrict__ mv = masks.off ? masks.iv + masks.off[td.contig] : nullptr;
-    unsigned nf, nr; unsigned long long inf_f, inf_r;
-    extract_strand<1>(S, G, d, cd.base, total, tile, tiles, n_tiles, tile_first, tile_last, P, n_masks, mv, nf, inf_f);
+    unsigned nf, nr; unsigned long long inf_f, inf_r, sl_f, sl_r;
+    extract_strand<1>(S, G, d, cd.base, total, td.contig, tiles, n_tiles, tile_first, tile_last, P, n_masks, mv, carry, nf, inf_f, sl_f);
     __syncthreads();
-    extract_strand<-1>(S, G, d, cd.base, total, tile, tiles, n_tiles, tile_first, tile_last, P, n_masks, mv, nr, inf_r);
+    extract_strand<-1>(S, G, d, cd.base, total, td.contig, tiles, n_tiles, tile_first, tile_last, P, n_masks, mv, carry, nr, inf_r, sl_r);
+    // the stop_val of the thread's node at forward position k of strand s
+    auto stop_val_at = [&](const int s, const int k, const unsigned long long sl) -> int32_t {
+        if constexpr (COMPACT) {
+            const unsigned slot = (unsigned)(sl >> (4 * k)) & 15u;
+            if (slot != EX_IN_POOL) return S.sv[s][slot][t];           // (slot < ex_c <= EX_C: put())
+            const int key = t | (s << 8) | (k << 9), n = min(S.pool_n, P.ex_pool);
+            for (int e = 0; e < n; e++) if (S.pool_key[e] == key) return S.pool_sv[e];
+            return 0;                               // (the pool was exhausted: the caller extracts again)
+        } else return S.sv[s][k][t];
+    };
     // pack: nodes in (position, strand) order -- forward sorts before reverse at equal ndx (Prodigal compare_nodes;
     // ref: lib.pyx:2489-2493) -- into the tile's staging slots; the per-position flags of the ORF walks
     const int r0 = t * EX_PER_THREAD;
@@ -606,6 +667,7 @@ k_extract_tile(const uint8_t* __restrict__ dig, int64_t total, const ContigDesc*
     const int64_t stage0 = ga.st_half ? (g0 >> ga.st_half) + (int64_t)PGA_STAGE_SLACK * tile : 2 * g0;
     const int room = ga.st_half ? (G.len >> ga.st_half) + PGA_STAGE_SLACK : 2 * G.len;   // staging slots of the tile
     if (t == 255 && nbase + cnt > room) atomicOr(ga.st_overflow, 1);   // (only with st_half) the caller extracts again, full staging
+    if (COMPACT && t == 0 && S.pool_n > P.ex_pool) atomicOr(ga.st_overflow, 2);       // ... with a stop value for every position
     int64_t slot = stage0 + nbase;
     const int64_t slot_end = stage0 + room;
     unsigned both = nf | nr;
@@ -615,12 +677,12 @@ k_extract_tile(const uint8_t* __restrict__ dig, int64_t total, const ContigDesc*
         both &= both - 1u;
         if ((nf >> k) & 1u) {
             const int info = (int)((inf_f >> (4 * k)) & 7);
-            if (slot < slot_end) { ga.st_ndx[slot] = G.a + r0 + k; ga.st_sv[slot] = S.sv[0][k][t]; ga.st_info[slot] = (uint8_t)info; }
+            if (slot < slot_end) { ga.st_ndx[slot] = G.a + r0 + k; ga.st_sv[slot] = stop_val_at(0, k, sl_f); ga.st_info[slot] = (uint8_t)info; }
             slot++; n_stop += (info & 3) == PGA_T_STOP;
         }
         if ((nr >> k) & 1u) {
             const int info = (int)((inf_r >> (4 * k)) & 7);
-            if (slot < slot_end) { ga.st_ndx[slot] = G.a + r0 + k; ga.st_sv[slot] = S.sv[1][k][t]; ga.st_info[slot] = (uint8_t)(info | 8); }
+            if (slot < slot_end) { ga.st_ndx[slot] = G.a + r0 + k; ga.st_sv[slot] = stop_val_at(1, k, sl_r); ga.st_info[slot] = (uint8_t)(info | 8); }
             slot++; n_stop += (info & 3) == PGA_T_STOP;
         }
     }
@@ -3130,17 +3192,22 @@ void pga_launch_gc_prefix(const uint8_t* d_dig, int64_t total, int32_t* d_block_
 void pga_launch_extract(const uint8_t* d_dig, int64_t total, const ContigDesc* d_ct, int n_contigs, int tt,
                         const pga_params& p, const GroupArrays& ga, const TileDesc* d_tiles, int n_tiles, const int32_t* d_tile0,
                         int32_t* d_tile_first, int32_t* d_tile_last, int32_t* d_tile_count, int32_t* d_tile_off, int32_t* d_cbase,
-                        int32_t* d_tile_scount, int32_t* d_tile_soff, int32_t* d_sbase, MaskList masks, hipStream_t st, const uint8_t* d_enabled) {
+                        int32_t* d_tile_scount, int32_t* d_tile_soff, int32_t* d_sbase, MaskList masks, hipStream_t st, const uint8_t* d_enabled,
+                        int ex_c, int ex_pool) {
     if (n_tiles > 0) {
-        ExParams P{tt, p.closed, p.min_gene, p.min_edge_gene, 0ull, 0ull};
+        ExParams P{tt, p.closed, p.min_gene, p.min_edge_gene, 0ull, 0ull, std::min(ex_c, EX_C), std::max(0, std::min(ex_pool, EX_POOL))};
         for (int idx = 0; idx < 64; idx++) {
             const int b0 = idx & 3, b1 = (idx >> 2) & 3, b2 = (idx >> 4) & 3;
             if (codon_is_stop(b0, b1, b2, tt)) P.stop_codons |= 1ull << idx;
             if (codon_is_start(b0, b1, b2, tt)) P.start_codons |= 1ull << idx;
         }
         hipLaunchKernelGGL(k_tile_stops, dim3(n_tiles), dim3(64), 0, st, d_dig, total, d_ct, d_tiles, n_tiles, P.stop_codons, d_tile_first, d_tile_last, d_enabled);
-        hipLaunchKernelGGL(k_extract_tile, dim3(n_tiles), dim3(256), 0, st, d_dig, total, d_ct, d_tiles, n_tiles, d_tile_first, d_tile_last, P, ga, masks,
-                           d_enabled, d_tile_count, d_tile_scount);
+        if (P.ex_c > 0)
+            hipLaunchKernelGGL(k_extract_tile<true>, dim3(n_tiles), dim3(256), 0, st, d_dig, total, d_ct, d_tiles, n_tiles, d_tile_first, d_tile_last, P, ga, masks,
+                               d_enabled, d_tile_count, d_tile_scount);
+        else
+            hipLaunchKernelGGL(k_extract_tile<false>, dim3(n_tiles), dim3(256), 0, st, d_dig, total, d_ct, d_tiles, n_tiles, d_tile_first, d_tile_last, P, ga, masks,
+                               d_enabled, d_tile_count, d_tile_scount);
     }
     hipLaunchKernelGGL(k_scan_counts, dim3(1), dim3(1024), 0, st, d_tile_count, n_tiles, d_tile_off, (const int32_t*)d_tile_scount, d_tile_soff);
     hipLaunchKernelGGL(k_contig_node_base, dim3((n_contigs + 1 + 255) / 256), dim3(256), 0, st, d_tile0, n_contigs, d_tile_off, d_cbase);
