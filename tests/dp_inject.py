@@ -105,17 +105,22 @@ def contig_with_nodes(n, gc, seed):
         if extracted(seq).num_nodes > n + 8 or length > (n + 64) * 4096:
             break
         length *= 2
+    found = trimmed_to_nodes(seq, n)
+    assert found is not None, (n, gc, seed)
+    return found
+
+
+def trimmed_to_nodes(seq, n, closed=False, tt=11):
+    """`seq` trimmed from the right until the oracle extracts exactly `n` nodes from it; None if no cut gives that count."""
+    length = len(seq)
     lo, hi = 0, length                            # the count grows with the length but for a few nodes: bisect near, then go base by base
     while hi - lo > 1:
         mid = (lo + hi) // 2
-        lo, hi = (lo, mid) if extracted(seq[:mid]).num_nodes > n else (mid, hi)
-    found = None
+        lo, hi = (lo, mid) if extracted(seq[:mid], closed, tt).num_nodes > n else (mid, hi)
     for cut in range(min(length, hi + 256), 0, -1):
-        k = extracted(seq[:cut]).num_nodes
+        k = extracted(seq[:cut], closed, tt).num_nodes
         if k == n:
-            found = seq[:cut]
-            break
+            return seq[:cut]
         if k < n - 8:                             # the count falls by a few nodes at a time: far below n it does not come back
             break
-    assert found is not None, (n, gc, seed)
-    return found
+    return None

@@ -38,13 +38,13 @@ def models():
     return m
 
 
-def compare_contig(res, i, seq, o, models, meta, closed=False):
+def compare_contig(res, i, seq, o, models, meta, closed=False, max_overlap=60):
     cr = res.contigs[i]
     if meta:
-        phase = o.find_genes_meta(models, orc.Params(closed=closed))
+        phase = o.find_genes_meta(models, orc.Params(closed=closed, max_overlap=max_overlap))
         assert cr["model"] == phase
     else:
-        o.find_genes_single(models[0], orc.Params(closed=closed))
+        o.find_genes_single(models[0], orc.Params(closed=closed, max_overlap=max_overlap))
     og, on = o.genes(), o.nodes()
     gg = res.genes_of(i)
     assert len(gg) == len(og)
