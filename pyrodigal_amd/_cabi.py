@@ -4,6 +4,7 @@ There is no CPU implementation behind this module: if the shared library is miss
 gfx950 device is visible, calls raise instead of silently computing elsewhere.
 """
 import ctypes
+import functools
 import os
 
 import numpy as np
@@ -1219,6 +1220,37 @@ def _default_tables(self, contigs):
     return [tts[c["model"]] if c["model"] >= 0 else 11 for c in contigs]
 
 
+def _tables_or_default(self, result_or_genes, tables):
+    """``tables`` where the caller gave them, else those of the models that won the result's contigs."""
+    if tables is not None:
+        return tables
+    contigs = getattr(result_or_genes, "contigs", None)
+    if contigs is None:
+        raise ValueError("bare gene records carry no models: pass tables=, the translation table of every contig")
+    return _default_tables(self, contigs)
+
+
+def _tables_arg(tables, n_contigs, unit=None):
+    """The translation table of every contig as the library takes it: (the int32 array, its pointer).  ``unit``: that of a rule which
+    reads ``tables`` only for its protein unit; without them the pointer is NULL for any other."""
+    if tables is None and unit is not None:
+        if unit == "protein":
+            raise ValueError("the protein unit needs tables=, the translation table of every contig")
+        return None, ctypes.c_void_p(0)
+    tables = np.ascontiguousarray(tables, np.int32)
+    if tables.shape != (n_contigs,):
+        raise ValueError(f"tables has {tables.size} entries for {n_contigs} contigs")
+    return tables, ctypes.c_void_p(tables.ctypes.data)
+
+
+def _gene_begin(genes, n_contigs):
+    """The genes of contig i are records ``gene_begin[i] .. gene_begin[i + 1]``: int64, or ``None`` when the records are not in contig
+    order."""
+    if len(genes) and np.any(np.diff(genes["contig"]) < 0):
+        return None
+    return np.searchsorted(genes["contig"], np.arange(n_contigs + 1)).astype(np.int64)
+
+
 def _residue_counts(genes, include_stop):
     """Residues of every gene record (int64): host arithmetic on the coordinates, as the library does it."""
     stop_edge = np.where(genes["strand"] == 1, genes["partial_end"], genes["partial_begin"]).astype(bool)
@@ -1237,9 +1269,14 @@ def _token_id(value, name):
 
 
 class _TensorRule:
-    """What ProteinTokens, BaseLabels and GeneWindows share (StartCandidates, with two element types, KmerCounts, whose rows are always int32 ``[R, n_bins]``, and ProteinGroups and ProteinSketches, whose tensors are always int64, take the value semantics): the element type and layout of the device tensor, value semantics over ``_key()``,
-    and the head of the options struct.  A subclass says what one row is (``row`` and its ``unit``), what it needs of every contig
-    of the batch (``per_contig``: ``"tables"`` or ``"lengths"``), and has ``write``, the call on raw handles with just that."""
+    """What the seven rules of the device-tensor outputs share.  Every rule gets value semantics over ``_key()`` -- the attributes
+    ``_fields`` names -- and pickles through it (``_derive`` restores what the constructor computes from them); it says what one row
+    is (``row`` and its ``unit``) and what it needs of every contig of the batch (``per_contig``: ``"tables"`` or ``"lengths"``),
+    and has ``write``, the call on raw handles with just that.  Only the rules that write rows of one element type in either
+    layout -- ProteinTokens, BaseLabels, GeneWindows -- take the rest: the format (``_set_format``, ``elem_bytes``, ``typestr``),
+    ``_check_fit`` and the head of the options struct (``_opts``)."""
+
+    _fields = ()
 
     def _set_format(self, dtype, layout):
         name = dtype if isinstance(dtype, str) else np.dtype(dtype).name
@@ -1258,16 +1295,33 @@ class _TensorRule:
             if v is not None and not lo <= v <= hi:
                 raise ValueError(f"{what}, {v}, does not fit {self.dtype}")
 
+    def _key(self):
+        return tuple(getattr(self, f) for f in self._fields)
+
+    def _derive(self):
+        pass
+
     def __eq__(self, other):
         return isinstance(other, type(self)) and self._key() == other._key()
 
     def __hash__(self):
         return hash(self._key())
 
+    def __reduce__(self):
+        return _rule_from_key, (type(self), self._key())
+
     def _opts(self, o, row_width, row_stride):
         o.elem_bytes, o.layout = self.elem_bytes, TOKENS_PADDED if self.layout == "padded" else TOKENS_RAGGED
         o.row_width, o.row_stride, o.pad = int(row_width), int(row_stride), self.pad
         return o
+
+
+def _rule_from_key(cls, key):
+    rule = cls.__new__(cls)
+    for f, v in zip(cls._fields, key):
+        setattr(rule, f, v)
+    rule._derive()
+    return rule
 
 
 class ProteinTokens(_TensorRule):
@@ -1316,7 +1370,7 @@ class ProteinTokens(_TensorRule):
         self.vocab = tuple(given.get(chr(k), rest) for k in range(128))
         self._check_fit([(f"the id of {chr(k)!r}", self.vocab[k]) for k in range(128) if chr(k) in given] +
                         [("unknown", self.unknown), ("bos", self.bos), ("eos", self.eos), ("pad", self.pad)])
-        self.specials = (self.bos is not None) + (self.eos is not None)
+        self._derive()
         if max_length is not None:
             max_length = _token_id(max_length, "max_length")
             if max_length < self.specials + 1:
@@ -1324,16 +1378,13 @@ class ProteinTokens(_TensorRule):
         self.max_length = max_length
 
     row, unit, per_contig = "gene", "tokens", "tables"
+    _fields = ("vocab", "unknown", "bos", "eos", "pad", "dtype", "layout", "max_length", "include_stop", "strict", "unknown_residue")
+
+    def _derive(self):
+        self.specials = (self.bos is not None) + (self.eos is not None)
 
     def write(self, L, ctx_h, batch_h, device, genes, tables, out=None, stream=None):
         return tokens_into(L, ctx_h, batch_h, device, len(tables), genes, tables, self, out, stream)
-
-    def _key(self):
-        return (self.vocab, self.unknown, self.bos, self.eos, self.pad, self.dtype, self.layout, self.max_length, self.include_stop,
-                self.strict, self.unknown_residue)
-
-    def __reduce__(self):
-        return _protein_tokens_from_key, (self._key(),)
 
     def __repr__(self):
         return "pyrodigal_amd.ProteinTokens(dtype=%r, layout=%r, bos=%r, eos=%r, max_length=%r)" % (
@@ -1356,27 +1407,29 @@ class ProteinTokens(_TensorRule):
         return o
 
 
-def _protein_tokens_from_key(key):
-    p = ProteinTokens.__new__(ProteinTokens)
-    (p.vocab, p.unknown, p.bos, p.eos, p.pad, p.dtype, p.layout, p.max_length, p.include_stop, p.strict, p.unknown_residue) = key
-    p.specials = (p.bos is not None) + (p.eos is not None)
-    return p
+class _ContigViews:
+    """The per-contig views of a result (``proteins``, ``labels_of``, ``windows``, ``counts_of``, ``starts``): entry i is
+    ``part(a, b)``, views of the tensors -- no copy -- for the rows ``a .. b`` of contig i: ``begin[i] .. begin[i + 1]``, its genes
+    (``gene_begin``), or ``i .. i + 1`` where a contig is a row (``begin=None``: ``n`` of them)."""
 
-
-class _ContigProteins:
-    """``DeviceProteins.proteins``: entry i is a view of the rows (padded) or the slice (ragged) of contig i's genes -- no copy."""
-
-    def __init__(self, owner):
-        self.owner = owner
+    def __init__(self, part, begin, n=0):
+        self.part, self.begin = part, np.arange(n + 1) if begin is None else begin
 
     def __len__(self):
-        return len(self.owner.gene_begin) - 1
+        return len(self.begin) - 1
 
     def __getitem__(self, i):
-        d = self.owner
         i = range(len(self))[i]
-        a, b = int(d.gene_begin[i]), int(d.gene_begin[i + 1])
-        return d.tokens[a:b] if d.offsets is None else d.tokens[int(d.offsets[a]):int(d.offsets[b])]
+        return self.part(int(self.begin[i]), int(self.begin[i + 1]))
+
+
+def _gene_views(d, *tensors):
+    """``_ContigViews`` of the genes' rows (padded) or slice (ragged) of tensors that share ``d.offsets``."""
+    if d.gene_begin is None:
+        raise ValueError("the gene records were not in contig order: there are no per-contig views")
+    cut = (lambda a, b: slice(a, b)) if d.offsets is None else (lambda a, b: slice(int(d.offsets[a]), int(d.offsets[b])))
+    return _ContigViews((lambda a, b: tensors[0][cut(a, b)]) if len(tensors) == 1 else (lambda a, b: tuple(t[cut(a, b)] for t in tensors)),
+                        d.gene_begin)
 
 
 class DeviceProteins:
@@ -1390,9 +1443,7 @@ class DeviceProteins:
 
     @property
     def proteins(self):
-        if self.gene_begin is None:
-            raise ValueError("the gene records were not in contig order: there are no per-contig views")
-        return _ContigProteins(self)
+        return _gene_views(self, self.tokens)
 
     def cu_seqlens(self):
         """The exclusive scan of ``lengths`` as an int32 tensor on the tokens' device (torch)."""
@@ -1409,38 +1460,59 @@ def _cu_seqlens(lengths, tensor, device):
     return torch.from_numpy(cu.astype(np.int32)).to(dev)
 
 
+def _contiguous_strides(shape, elem_bytes):
+    return tuple(elem_bytes * int(np.prod(shape[k + 1:])) for k in range(len(shape)))
+
+
+def _device_array(x, name, typestr=None, expects=None):
+    """The one reader of ``__cuda_array_interface__``: (pointer, shape, strides in bytes -- those of a contiguous array where the
+    interface gives none) of ``x``, which the messages call ``name``.  ``typestr``: the element type it must have, ``expects``: the
+    caller's words for that.  What the shape must be is the caller's to say."""
+    cai = getattr(x, "__cuda_array_interface__", None)
+    if not isinstance(cai, dict):
+        raise TypeError("%s must have a __cuda_array_interface__ (a device tensor or array), not %r" % (name, type(x).__name__))
+    if typestr is not None and str(cai.get("typestr")) != typestr:
+        raise TypeError(f"{name} has dtype {cai.get('typestr')}: {expects}")
+    shape = tuple(int(v) for v in cai["shape"])
+    strides = cai.get("strides")
+    if strides is None:
+        strides = _contiguous_strides(shape, np.dtype(str(cai["typestr"])).itemsize)
+    ptr = cai["data"][0]
+    return int(ptr) if ptr else 0, shape, tuple(int(v) for v in strides)
+
+
+def _torch_outputs(device, stream, shapes_and_dtypes, how_many):
+    """No ``out=``: new torch tensors on ``device``, and torch's current stream there unless the caller named one.  ``how_many``: the
+    caller's words for what ``out=`` would have been."""
+    try:
+        import torch
+    except ImportError:
+        raise TypeError(f"torch is not installed: pass out=, {how_many} with __cuda_array_interface__") from None
+    with torch.cuda.device(device):
+        out = tuple(torch.empty(shape, dtype=getattr(torch, dtype), device="cuda") for shape, dtype in shapes_and_dtypes)
+        if stream is None:
+            stream = int(torch.cuda.current_stream().cuda_stream)
+    return out, stream
+
+
 def _device_output(spec, out, stream, device, lens, total, row, unit):
     """The device tensor a rule writes (``tokens_into`` and ``labels_into`` share this): ``out`` checked against the rule's element
     type and layout and against ``lens``, the elements of every row, or a new torch tensor under torch's current stream.  Returns
-    (out, stream, its ``__cuda_array_interface__``, W, S, the elements the layout may use)."""
+    (out, stream, its device pointer, W, S, the elements the layout may use)."""
     n, eb, padded = len(lens), spec.elem_bytes, spec.layout == "padded"
     longest = int(lens.max()) if n else 0
     if out is None:
-        try:
-            import torch
-        except ImportError:
-            raise TypeError("torch is not installed: pass out=, a device array with __cuda_array_interface__") from None
-        with torch.cuda.device(device):
-            out = torch.empty((n, longest) if padded else (total,), dtype=getattr(torch, spec.dtype), device="cuda")
-            if stream is None:
-                stream = int(torch.cuda.current_stream().cuda_stream)
-    cai = getattr(out, "__cuda_array_interface__", None)
-    if not isinstance(cai, dict):
-        raise TypeError("out must have a __cuda_array_interface__ (a device tensor or array), not %r" % type(out).__name__)
-    if str(cai.get("typestr")) != spec.typestr:
-        raise TypeError(f"out has dtype {cai.get('typestr')}: the rule writes {spec.dtype} ({spec.typestr})")
-    shape = tuple(int(x) for x in cai["shape"])
-    strides = cai.get("strides")
-    strides = None if strides is None else tuple(int(x) for x in strides)
-    if strides is not None and shape[-1] > 1 and strides[-1] != eb:
+        (out,), stream = _torch_outputs(device, stream, [((n, longest) if padded else (total,), spec.dtype)], "a device array")
+    ptr, shape, strides = _device_array(out, "out", spec.typestr, f"the rule writes {spec.dtype} ({spec.typestr})")
+    if shape[-1] > 1 and strides[-1] != eb:
         raise ValueError("the last dimension of out is not contiguous")
     width = stride = 0
     if padded:
         if len(shape) != 2 or shape[0] != n:
             raise ValueError(f"the padded layout needs a [{n}, W] tensor, not one of shape {shape}")
         width = shape[1]
-        stride = width if strides is None or n < 2 else strides[0] // eb
-        if strides is not None and n > 1 and (strides[0] % eb or strides[0] < 0):
+        stride = width if n < 2 else strides[0] // eb
+        if n > 1 and (strides[0] % eb or strides[0] < 0):
             raise ValueError("the rows of out do not lie a whole, positive number of elements apart")
         if width < longest:
             raise ValueError(f"out has {width} columns: {row} {int(np.argmax(lens))} has {longest} {unit}")
@@ -1451,7 +1523,7 @@ def _device_output(spec, out, stream, device, lens, total, row, unit):
         if shape[0] < total:
             raise ValueError(f"out has {shape[0]} elements: the {row}s have {total} {unit}")
         n_out = shape[0]
-    return out, stream, cai, width, stride, n_out
+    return out, stream, ptr, width, stride, n_out
 
 
 def _rows_into(L, ctx_h, call, args, spec, lens, device, out, stream):
@@ -1460,11 +1532,10 @@ def _rows_into(L, ctx_h, call, args, spec, lens, device, out, stream):
     n = len(lens)
     off = np.zeros(n + 1, np.int64)
     np.cumsum(lens, out=off[1:])
-    out, stream, cai, width, stride, n_out = _device_output(spec, out, stream, device, lens, int(off[-1]), spec.row, spec.unit)
-    ptr = cai["data"][0]
+    out, stream, ptr, width, stride, n_out = _device_output(spec, out, stream, device, lens, int(off[-1]), spec.row, spec.unit)
     len_out = np.zeros(max(n, 1), np.int64)
     o = spec.opts(width, stride)
-    rc = getattr(L, call)(ctx_h, *args, ctypes.byref(o), ctypes.c_void_p(int(ptr) if ptr else 0), n_out,
+    rc = getattr(L, call)(ctx_h, *args, ctypes.byref(o), ctypes.c_void_p(ptr), n_out,
                           ctypes.c_void_p(DeviceSequences._stream_of(out, stream)), ctypes.c_void_p(len_out.ctypes.data))
     if rc != PGA_OK:
         _raise(L, ctx_h, rc, call)
@@ -1477,17 +1548,12 @@ def tokens_into(L, ctx_h, batch_h, device, n_contigs, genes, tables, spec, out=N
     if not isinstance(spec, ProteinTokens):
         raise TypeError("the token rule must be a ProteinTokens, not %r" % type(spec).__name__)
     genes = np.ascontiguousarray(genes, dtype=GENE_DTYPE)
-    tables = np.ascontiguousarray(tables, np.int32)
-    if tables.shape != (n_contigs,):
-        raise ValueError(f"tables has {tables.size} entries for {n_contigs} contigs")
+    tables, p_tab = _tables_arg(tables, n_contigs)
     n, lens = len(genes), spec.lengths(genes)
-    args = (batch_h, n, ctypes.c_void_p(genes.ctypes.data), ctypes.c_void_p(tables.ctypes.data))
+    args = (batch_h, n, ctypes.c_void_p(genes.ctypes.data), p_tab)
     out, off, len_out = _rows_into(L, ctx_h, "pga_translate_genes_tokens", args, spec, lens, device, out, stream)
     assert np.array_equal(len_out, lens)
-    gene_begin = None
-    if n == 0 or np.all(np.diff(genes["contig"]) >= 0):
-        gene_begin = np.searchsorted(genes["contig"], np.arange(n_contigs + 1)).astype(np.int64)
-    return DeviceProteins(out, lens, off, gene_begin, device)
+    return DeviceProteins(out, lens, off, _gene_begin(genes, n_contigs), device)
 
 
 def _translate_tokens(self, batch, result_or_genes, spec, out=None, tables=None, stream=None):
@@ -1498,11 +1564,7 @@ def _translate_tokens(self, batch, result_or_genes, spec, out=None, tables=None,
     on the context's device under torch's current stream.  ``tables``: translation table per contig (default: that of the model that
     won the contig).  ``stream``: the stream that last used ``out``, as in :class:`DeviceSequences`.  Returns a :class:`DeviceProteins`."""
     genes = getattr(result_or_genes, "genes", result_or_genes)
-    if tables is None:
-        contigs = getattr(result_or_genes, "contigs", None)
-        if contigs is None:
-            raise ValueError("bare gene records carry no models: pass tables=, the translation table of every contig")
-        tables = _default_tables(self, contigs)
+    tables = _tables_or_default(self, result_or_genes, tables)
     return tokens_into(self.L, self.h, batch.h, self.device, batch.n, genes, tables, spec, out, stream)
 
 
@@ -1557,15 +1619,10 @@ class BaseLabels(_TensorRule):
         self._check_fit([(f"the id of raw byte {k:#04x}", v) for k, v in enumerate(self.class_map)] + [("pad", self.pad)])
 
     row, unit, per_contig = "contig", "bases", "lengths"
+    _fields = ("class_map", "classes", "pad", "dtype", "layout")
 
     def write(self, L, ctx_h, batch_h, device, genes, lengths, out=None, stream=None):
         return labels_into(L, ctx_h, batch_h, device, lengths, genes, self, out, stream)
-
-    def _key(self):
-        return (self.class_map, self.classes, self.pad, self.dtype, self.layout)
-
-    def __reduce__(self):
-        return _base_labels_from_key, (self._key(),)
 
     def __repr__(self):
         return "pyrodigal_amd.BaseLabels(%s, pad=%r, dtype=%r, layout=%r)" % (
@@ -1575,27 +1632,6 @@ class BaseLabels(_TensorRule):
         o = self._opts(LabelOpts(), row_width, row_stride)
         o.class_map[:] = self.class_map
         return o
-
-
-def _base_labels_from_key(key):
-    b = BaseLabels.__new__(BaseLabels)
-    b.class_map, b.classes, b.pad, b.dtype, b.layout = key
-    return b
-
-
-class _ContigLabels:
-    """``DeviceLabels.labels_of``: entry i is a view of contig i's row (padded, its first ``lengths[i]`` elements) or slice (ragged)."""
-
-    def __init__(self, owner):
-        self.owner = owner
-
-    def __len__(self):
-        return len(self.owner.lengths)
-
-    def __getitem__(self, i):
-        d = self.owner
-        i = range(len(self))[i]
-        return d.labels[i, :int(d.lengths[i])] if d.offsets is None else d.labels[int(d.offsets[i]):int(d.offsets[i + 1])]
 
 
 class DeviceLabels:
@@ -1609,7 +1645,10 @@ class DeviceLabels:
 
     @property
     def labels_of(self):
-        return _ContigLabels(self)
+        # contig i's row (padded, its first ``lengths[i]`` elements) or slice (ragged)
+        if self.offsets is None:
+            return _ContigViews(lambda i, _: self.labels[i, :int(self.lengths[i])], None, len(self.lengths))
+        return _ContigViews(lambda i, j: self.labels[int(self.offsets[i]):int(self.offsets[j])], None, len(self.lengths))
 
     def cu_seqlens(self):
         """The exclusive scan of ``lengths`` as an int32 tensor on the labels' device (torch)."""
@@ -1739,15 +1778,14 @@ class GeneWindows(_TensorRule):
         return (anchor, delta)
 
     row, unit, per_contig = "gene", "tokens", "lengths"
+    _fields = ("begin", "end", "token_unit", "ids", "bos", "eos", "pad", "dtype", "layout", "max_length")
+
+    def _derive(self):
+        self.unknown, self.outside = self.ids[-2:]
+        self.specials = (self.bos is not None) + (self.eos is not None)
 
     def write(self, L, ctx_h, batch_h, device, genes, lengths, out=None, stream=None):
         return windows_into(L, ctx_h, batch_h, device, len(lengths), genes, self, out, stream)
-
-    def _key(self):
-        return (self.begin, self.end, self.token_unit, self.ids, self.bos, self.eos, self.pad, self.dtype, self.layout, self.max_length)
-
-    def __reduce__(self):
-        return _gene_windows_from_key, (self._key(),)
 
     def __repr__(self):
         return "pyrodigal_amd.GeneWindows(%r, %r, unit=%r, dtype=%r, layout=%r, bos=%r, eos=%r, max_length=%r)" % (
@@ -1775,14 +1813,6 @@ class GeneWindows(_TensorRule):
         return o
 
 
-def _gene_windows_from_key(key):
-    w = GeneWindows.__new__(GeneWindows)
-    w.begin, w.end, w.token_unit, w.ids, w.bos, w.eos, w.pad, w.dtype, w.layout, w.max_length = key
-    w.unknown, w.outside = w.ids[-2:]
-    w.specials = (w.bos is not None) + (w.eos is not None)
-    return w
-
-
 class DeviceWindows:
     """Nucleotide windows of gene records as token ids in device memory.  ``tokens``: the tensor (``[G, W]`` padded, 1-D ragged);
     ``lengths``: tokens of every row (numpy int64, host); ``offsets``: ragged only, gene g is ``tokens[offsets[g]:offsets[g + 1]]``;
@@ -1794,9 +1824,7 @@ class DeviceWindows:
 
     @property
     def windows(self):
-        if self.gene_begin is None:
-            raise ValueError("the gene records were not in contig order: there are no per-contig views")
-        return _ContigProteins(self)
+        return _gene_views(self, self.tokens)
 
     def cu_seqlens(self):
         """The exclusive scan of ``lengths`` as an int32 tensor on the tokens' device (torch)."""
@@ -1813,10 +1841,7 @@ def windows_into(L, ctx_h, batch_h, device, n_contigs, genes, spec, out=None, st
     args = (batch_h, n, ctypes.c_void_p(genes.ctypes.data))
     out, off, len_out = _rows_into(L, ctx_h, "pga_gene_windows", args, spec, lens, device, out, stream)
     assert np.array_equal(len_out, lens)
-    gene_begin = None
-    if n == 0 or np.all(np.diff(genes["contig"]) >= 0):
-        gene_begin = np.searchsorted(genes["contig"], np.arange(n_contigs + 1)).astype(np.int64)
-    return DeviceWindows(out, lens, off, gene_begin, device)
+    return DeviceWindows(out, lens, off, _gene_begin(genes, n_contigs), device)
 
 
 def _gene_windows(self, batch, result_or_genes, spec, out=None, stream=None):
@@ -1922,14 +1947,13 @@ class KmerCounts(_TensorRule):
             first.setdefault(b, x)
         return tuple(kmer_of_code(first[b], self.k) for b in range(self.n_bins))
 
+    _fields = ("k", "rows", "step", "canonical", "custom", "table")
+
+    def _derive(self):
+        self.n_bins = max(self.table) + 1
+
     def write(self, L, ctx_h, batch_h, device, genes, lengths, out=None, stream=None):
         return counts_into(L, ctx_h, batch_h, device, len(lengths), genes, self, out, stream)
-
-    def _key(self):
-        return (self.k, self.rows, self.step, self.canonical, self.custom, self.table)
-
-    def __reduce__(self):
-        return _kmer_counts_from_key, (self._key(),)
 
     def __repr__(self):
         return "pyrodigal_amd.KmerCounts(%d, rows=%r, step=%d, %s)" % (
@@ -1960,30 +1984,6 @@ class KmerCounts(_TensorRule):
         return o
 
 
-def _kmer_counts_from_key(key):
-    c = KmerCounts.__new__(KmerCounts)
-    c.k, c.rows, c.step, c.canonical, c.custom, c.table = key
-    c.n_bins = max(c.table) + 1
-    return c
-
-
-class _ContigCounts:
-    """``DeviceCounts.counts_of``: entry i is a view of contig i's rows -- its genes' rows, or its own row -- no copy."""
-
-    def __init__(self, owner):
-        self.owner = owner
-
-    def __len__(self):
-        return self.owner.n_contigs
-
-    def __getitem__(self, i):
-        d = self.owner
-        i = range(len(self))[i]
-        if d.rows != "gene":
-            return d.counts[i]
-        return d.counts[int(d.gene_begin[i]):int(d.gene_begin[i + 1])]
-
-
 class DeviceCounts:
     """K-mer counts of contigs or gene records in device memory.  ``counts``: the tensor, ``[R, n_bins]`` int32 (with ``out=``: the
     caller's ``[R, S]`` object, of which columns ``0 .. n_bins - 1`` were set); ``windows``: the window positions of every row, counted
@@ -1995,11 +1995,13 @@ class DeviceCounts:
         self.counts, self.windows, self.gene_begin, self.rows, self.n_bins = counts, windows, gene_begin, rows, n_bins
         self.n_contigs, self.device = n_contigs, device
 
+    offsets = None                                           # (the rows are always padded)
+
     @property
     def counts_of(self):
-        if self.rows == "gene" and self.gene_begin is None:
-            raise ValueError("the gene records were not in contig order: there are no per-contig views")
-        return _ContigCounts(self)
+        if self.rows == "gene":
+            return _gene_views(self, self.counts)
+        return _ContigViews(lambda i, _: self.counts[i], None, self.n_contigs)
 
 
 def counts_into(L, ctx_h, batch_h, device, n_contigs, genes, spec, out=None, stream=None):
@@ -2011,42 +2013,25 @@ def counts_into(L, ctx_h, batch_h, device, n_contigs, genes, spec, out=None, str
     n = len(genes)
     R = n if spec.rows == "gene" else n_contigs
     if out is None:
-        try:
-            import torch
-        except ImportError:
-            raise TypeError("torch is not installed: pass out=, a device array with __cuda_array_interface__") from None
-        with torch.cuda.device(device):
-            out = torch.empty((R, spec.n_bins), dtype=torch.int32, device="cuda")
-            if stream is None:
-                stream = int(torch.cuda.current_stream().cuda_stream)
-    cai = getattr(out, "__cuda_array_interface__", None)
-    if not isinstance(cai, dict):
-        raise TypeError("out must have a __cuda_array_interface__ (a device tensor or array), not %r" % type(out).__name__)
-    if str(cai.get("typestr")) != spec.typestr:
-        raise TypeError(f"out has dtype {cai.get('typestr')}: the rule writes int32 ({spec.typestr})")
-    shape = tuple(int(x) for x in cai["shape"])
-    strides = cai.get("strides")
-    strides = None if strides is None else tuple(int(x) for x in strides)
+        (out,), stream = _torch_outputs(device, stream, [((R, spec.n_bins), "int32")], "a device array")
+    ptr, shape, strides = _device_array(out, "out", spec.typestr, f"the rule writes int32 ({spec.typestr})")
     if len(shape) != 2 or shape[0] != R:
         raise ValueError(f"the counts need a [{R}, S] tensor, not one of shape {shape}")
     if shape[1] < spec.n_bins:
         raise ValueError(f"out has {shape[1]} columns: the rule has {spec.n_bins} bins")
-    if strides is not None and shape[1] > 1 and strides[1] != 4:
+    if shape[1] > 1 and strides[1] != 4:
         raise ValueError("the last dimension of out is not contiguous")
-    if strides is not None and R > 1 and (strides[0] % 4 or strides[0] < 4 * shape[1]):
+    if R > 1 and (strides[0] % 4 or strides[0] < 4 * shape[1]):
         raise ValueError("the rows of out do not lie a whole number of elements apart, at least a row's width")
-    stride = shape[1] if strides is None or R < 2 else strides[0] // 4
+    stride = shape[1] if R < 2 else strides[0] // 4
     n_out = (R - 1) * stride + shape[1] if R else 0
-    ptr = cai["data"][0]
     win_out = np.zeros(max(R, 1), np.int64)
     o = spec.opts(stride)
-    rc = L.pga_count_kmers(ctx_h, batch_h, n, ctypes.c_void_p(genes.ctypes.data), ctypes.byref(o), ctypes.c_void_p(int(ptr) if ptr else 0), n_out,
+    rc = L.pga_count_kmers(ctx_h, batch_h, n, ctypes.c_void_p(genes.ctypes.data), ctypes.byref(o), ctypes.c_void_p(ptr), n_out,
                            ctypes.c_void_p(DeviceSequences._stream_of(out, stream)), ctypes.c_void_p(win_out.ctypes.data))
     if rc != PGA_OK:
         _raise(L, ctx_h, rc, "pga_count_kmers")
-    gene_begin = None
-    if spec.rows == "gene" and (n == 0 or np.all(np.diff(genes["contig"]) >= 0)):
-        gene_begin = np.searchsorted(genes["contig"], np.arange(n_contigs + 1)).astype(np.int64)
+    gene_begin = _gene_begin(genes, n_contigs) if spec.rows == "gene" else None
     return DeviceCounts(out, win_out[:R], gene_begin, spec.rows, spec.n_bins, n_contigs, device)
 
 
@@ -2091,6 +2076,7 @@ class ProteinGroups(_TensorRule):
         self.of, self.include_stop, self.strict, self.unknown_residue = unit, bool(include_stop), bool(strict), unknown_residue
 
     row, unit, per_contig = "gene", "groups", "tables"      # (`of` holds the constructor's unit)
+    _fields = ("of", "include_stop", "strict", "unknown_residue")
     dtype, typestr, elem_bytes = "int64", "<i8", 8
 
     @staticmethod
@@ -2110,12 +2096,6 @@ class ProteinGroups(_TensorRule):
     def write(self, L, ctx_h, batch_h, device, genes, tables, out=None, stream=None):
         return groups_into(L, ctx_h, batch_h, device, len(tables), genes, tables, self, out, stream)
 
-    def _key(self):
-        return (self.of, self.include_stop, self.strict, self.unknown_residue)
-
-    def __reduce__(self):
-        return _protein_groups_from_key, (self._key(),)
-
     def __repr__(self):
         return "pyrodigal_amd.ProteinGroups(%r, include_stop=%r, strict=%r, unknown_residue=%r)" % self._key()
 
@@ -2123,12 +2103,6 @@ class ProteinGroups(_TensorRule):
         o = GroupOpts()
         o.unit, o.include_stop, o.strict, o.unknown_residue = _GROUP_UNITS[self.of], int(self.include_stop), int(self.strict), ord(self.unknown_residue)
         return o
-
-
-def _protein_groups_from_key(key):
-    p = ProteinGroups.__new__(ProteinGroups)
-    p.of, p.include_stop, p.strict, p.unknown_residue = key
-    return p
 
 
 class DeviceGroups:
@@ -2150,19 +2124,12 @@ def _group_output(x, name, shape, required):
         if required:
             raise TypeError(f"out: {name} is required")
         return 0
-    cai = getattr(x, "__cuda_array_interface__", None)
-    if not isinstance(cai, dict):
-        raise TypeError(f"out: {name} must have a __cuda_array_interface__ (a device tensor or array), not %r" % type(x).__name__)
-    if str(cai.get("typestr")) != "<i8":
-        raise TypeError(f"out: {name} has dtype {cai.get('typestr')}: these tensors are int64 (<i8)")
-    got = tuple(int(v) for v in cai["shape"])
+    ptr, got, strides = _device_array(x, f"out: {name}", "<i8", "these tensors are int64 (<i8)")
     if len(got) != len(shape) or got[1:] != shape[1:] or got[0] < shape[0]:
         raise ValueError(f"out: {name} needs shape {list(shape)}{' or longer' if len(shape) == 1 else ''}, not {list(got)}")
-    strides = cai.get("strides")
-    if strides is not None and int(np.prod(got)) > 1 and tuple(int(v) for v in strides) != tuple(8 * int(np.prod(got[k + 1:])) for k in range(len(got))):
+    if int(np.prod(got)) > 1 and strides != _contiguous_strides(got, 8):
         raise ValueError(f"out: {name} is not contiguous")
-    ptr = cai["data"][0]
-    return int(ptr) if ptr else 0
+    return ptr
 
 
 def groups_into(L, ctx_h, batch_h, device, n_contigs, genes, tables, spec, out=None, stream=None):
@@ -2173,24 +2140,9 @@ def groups_into(L, ctx_h, batch_h, device, n_contigs, genes, tables, spec, out=N
         raise TypeError("the grouping rule must be a ProteinGroups, not %r" % type(spec).__name__)
     genes = np.ascontiguousarray(genes, dtype=GENE_DTYPE)
     n = len(genes)
-    p_tab = ctypes.c_void_p(0)
-    if tables is not None:
-        tables = np.ascontiguousarray(tables, np.int32)
-        if tables.shape != (n_contigs,):
-            raise ValueError(f"tables has {tables.size} entries for {n_contigs} contigs")
-        p_tab = ctypes.c_void_p(tables.ctypes.data)
-    elif spec.of == "protein":
-        raise ValueError("the protein unit needs tables=, the translation table of every contig")
+    tables, p_tab = _tables_arg(tables, n_contigs, spec.of)
     if out is None:
-        try:
-            import torch
-        except ImportError:
-            raise TypeError("torch is not installed: pass out=, four device arrays with __cuda_array_interface__") from None
-        with torch.cuda.device(device):
-            out = (torch.empty(n, dtype=torch.int64, device="cuda"), torch.empty(n, dtype=torch.int64, device="cuda"),
-                   torch.empty(n, dtype=torch.int64, device="cuda"), torch.empty((n, 2), dtype=torch.int64, device="cuda"))
-            if stream is None:
-                stream = int(torch.cuda.current_stream().cuda_stream)
+        out, stream = _torch_outputs(device, stream, [(n, "int64"), (n, "int64"), (n, "int64"), ((n, 2), "int64")], "four device arrays")
     out = tuple(out)
     if len(out) != 4:
         raise ValueError("out must be (group, representatives, sizes, digests), %d objects were given" % len(out))
@@ -2198,7 +2150,7 @@ def groups_into(L, ctx_h, batch_h, device, n_contigs, genes, tables, spec, out=N
     p_group = _group_output(group, "group", (n,), True)
     p_reps, p_sizes = _group_output(reps, "representatives", (n,), False), _group_output(sizes, "sizes", (n,), False)
     p_dig = _group_output(digests, "digests", (n, 2), False)
-    capacity = min([int(x.__cuda_array_interface__["shape"][0]) for x in (reps, sizes) if x is not None] or [n])
+    capacity = min([_device_array(x, "out")[1][0] for x in (reps, sizes) if x is not None] or [n])
     n_groups = ctypes.c_int64(0)
     o = spec.opts()
     rc = L.pga_group_proteins(ctx_h, batch_h, n, ctypes.c_void_p(genes.ctypes.data), p_tab, ctypes.byref(o), ctypes.c_void_p(p_group),
@@ -2208,10 +2160,7 @@ def groups_into(L, ctx_h, batch_h, device, n_contigs, genes, tables, spec, out=N
         _raise(L, ctx_h, rc, "pga_group_proteins")
     U = int(n_groups.value)
     cut = lambda x: None if x is None else (x[:U] if hasattr(x, "__getitem__") else x)      # noqa: E731
-    gene_begin = None
-    if n == 0 or np.all(np.diff(genes["contig"]) >= 0):
-        gene_begin = np.searchsorted(genes["contig"], np.arange(n_contigs + 1)).astype(np.int64)
-    return DeviceGroups(group, cut(reps), cut(sizes), digests, U, gene_begin, device)
+    return DeviceGroups(group, cut(reps), cut(sizes), digests, U, _gene_begin(genes, n_contigs), device)
 
 
 def _protein_groups(self, batch, result_or_genes, spec, tables=None, out=None, stream=None):
@@ -2223,11 +2172,8 @@ def _protein_groups(self, batch, result_or_genes, spec, tables=None, out=None, s
     last three; omitted: torch tensors are allocated on the context's device under torch's current stream.  ``stream``: the stream
     that last used the outputs, as in :class:`DeviceSequences`.  Returns a :class:`DeviceGroups`."""
     genes = getattr(result_or_genes, "genes", result_or_genes)
-    if tables is None and isinstance(spec, ProteinGroups) and spec.of == "protein":
-        contigs = getattr(result_or_genes, "contigs", None)
-        if contigs is None:
-            raise ValueError("bare gene records carry no models: pass tables=, the translation table of every contig")
-        tables = _default_tables(self, contigs)
+    if isinstance(spec, ProteinGroups) and spec.of == "protein":
+        tables = _tables_or_default(self, result_or_genes, tables)
     return groups_into(self.L, self.h, batch.h, self.device, batch.n, genes, tables, spec, out, stream)
 
 
@@ -2354,14 +2300,10 @@ class ProteinSketches(_TensorRule):
         low = sorted(a | b)[:self.size]
         return sum(1 for v in low if v in a and v in b), len(low)
 
+    _fields = ("k", "size", "of", "seed", "classes", "include_stop", "strict", "unknown_residue")
+
     def write(self, L, ctx_h, batch_h, device, genes, tables, out=None, stream=None):
         return sketches_into(L, ctx_h, batch_h, device, len(tables), genes, tables, self, out, stream)
-
-    def _key(self):
-        return (self.k, self.size, self.of, self.seed, self.classes, self.include_stop, self.strict, self.unknown_residue)
-
-    def __reduce__(self):
-        return _protein_sketches_from_key, (self._key(),)
 
     def __repr__(self):
         return "pyrodigal_amd.ProteinSketches(%r, %r, %r, seed=%r, include_stop=%r, strict=%r, unknown_residue=%r)" % (
@@ -2373,12 +2315,6 @@ class ProteinSketches(_TensorRule):
         o.include_stop, o.strict, o.unknown_residue = int(self.include_stop), int(self.strict), ord(self.unknown_residue)
         o.classes[:] = self.classes
         return o
-
-
-def _protein_sketches_from_key(key):
-    p = ProteinSketches.__new__(ProteinSketches)
-    p.k, p.size, p.of, p.seed, p.classes, p.include_stop, p.strict, p.unknown_residue = key
-    return p
 
 
 class DeviceSketches:
@@ -2397,23 +2333,13 @@ class DeviceSketches:
         tensor of record indices; a pair with an index outside ``0 .. G - 1`` gets -1 in both.  ``out``: two contiguous int64
         ``[P]`` objects with ``__cuda_array_interface__``, omitted: torch tensors.  The context of the call that made the sketches
         must still be open."""
-        cai = getattr(pairs, "__cuda_array_interface__", None)
-        if not isinstance(cai, dict):
-            raise TypeError("pairs must have a __cuda_array_interface__ (a device tensor or array), not %r" % type(pairs).__name__)
-        shape = tuple(int(v) for v in cai["shape"])
+        shape = _device_array(pairs, "pairs")[1]
         if len(shape) != 2 or shape[1] != 2:
             raise ValueError(f"pairs needs shape [P, 2], not {list(shape)}")
         P = shape[0]
         p_pairs = _group_output(pairs, "pairs", (P, 2), True)
         if out is None:
-            try:
-                import torch
-            except ImportError:
-                raise TypeError("torch is not installed: pass out=, two device arrays with __cuda_array_interface__") from None
-            with torch.cuda.device(self.device):
-                out = (torch.empty(P, dtype=torch.int64, device="cuda"), torch.empty(P, dtype=torch.int64, device="cuda"))
-                if stream is None:
-                    stream = int(torch.cuda.current_stream().cuda_stream)
+            out, stream = _torch_outputs(self.device, stream, [(P, "int64"), (P, "int64")], "two device arrays")
         out = tuple(out)
         if len(out) != 2:
             raise ValueError("out must be (shared, union), %d objects were given" % len(out))
@@ -2435,25 +2361,10 @@ def sketches_into(L, ctx_h, batch_h, device, n_contigs, genes, tables, spec, out
         raise TypeError("the sketching rule must be a ProteinSketches, not %r" % type(spec).__name__)
     genes = np.ascontiguousarray(genes, dtype=GENE_DTYPE)
     n = len(genes)
-    p_tab = ctypes.c_void_p(0)
-    if tables is not None:
-        tables = np.ascontiguousarray(tables, np.int32)
-        if tables.shape != (n_contigs,):
-            raise ValueError(f"tables has {tables.size} entries for {n_contigs} contigs")
-        p_tab = ctypes.c_void_p(tables.ctypes.data)
-    elif spec.of == "protein":
-        raise ValueError("the protein unit needs tables=, the translation table of every contig")
+    tables, p_tab = _tables_arg(tables, n_contigs, spec.of)
     s = spec.size
     if out is None:
-        try:
-            import torch
-        except ImportError:
-            raise TypeError("torch is not installed: pass out=, three device arrays with __cuda_array_interface__") from None
-        with torch.cuda.device(device):
-            out = (torch.empty((n, s), dtype=torch.int64, device="cuda"), torch.empty(n, dtype=torch.int64, device="cuda"),
-                   torch.empty(n, dtype=torch.int64, device="cuda"))
-            if stream is None:
-                stream = int(torch.cuda.current_stream().cuda_stream)
+        out, stream = _torch_outputs(device, stream, [((n, s), "int64"), (n, "int64"), (n, "int64")], "three device arrays")
     out = tuple(out)
     if len(out) != 3:
         raise ValueError("out must be (sketches, counts, windows), %d objects were given" % len(out))
@@ -2465,10 +2376,7 @@ def sketches_into(L, ctx_h, batch_h, device, n_contigs, genes, tables, spec, out
                                ctypes.c_void_p(p_cnt), ctypes.c_void_p(p_win), ctypes.c_void_p(DeviceSequences._stream_of(sketches, stream)))
     if rc != PGA_OK:
         _raise(L, ctx_h, rc, "pga_sketch_proteins")
-    gene_begin = None
-    if n == 0 or np.all(np.diff(genes["contig"]) >= 0):
-        gene_begin = np.searchsorted(genes["contig"], np.arange(n_contigs + 1)).astype(np.int64)
-    return DeviceSketches(sketches, counts, windows, gene_begin, spec, device, n, L, ctx_h)
+    return DeviceSketches(sketches, counts, windows, _gene_begin(genes, n_contigs), spec, device, n, L, ctx_h)
 
 
 def _protein_sketches(self, batch, result_or_genes, spec, tables=None, out=None, stream=None):
@@ -2480,11 +2388,8 @@ def _protein_sketches(self, batch, result_or_genes, spec, tables=None, out=None,
     last; omitted: torch tensors are allocated on the context's device under torch's current stream.  ``stream``: the stream that
     last used the outputs, as in :class:`DeviceSequences`.  Returns a :class:`DeviceSketches`."""
     genes = getattr(result_or_genes, "genes", result_or_genes)
-    if tables is None and isinstance(spec, ProteinSketches) and spec.of == "protein":
-        contigs = getattr(result_or_genes, "contigs", None)
-        if contigs is None:
-            raise ValueError("bare gene records carry no models: pass tables=, the translation table of every contig")
-        tables = _default_tables(self, contigs)
+    if isinstance(spec, ProteinSketches) and spec.of == "protein":
+        tables = _tables_or_default(self, result_or_genes, tables)
     return sketches_into(self.L, self.h, batch.h, self.device, batch.n, genes, tables, spec, out, stream)
 
 
@@ -2562,12 +2467,14 @@ class StartCandidates(_TensorRule):
         # (the finder's call: its context goes back to the pool when the request returns, so nothing of it may stay with the result)
         return starts_into(L, ctx_h, batch_h, device, len(lengths), genes, self, out, stream, keep_plan=False)
 
+    _fields = ("fields", "dtype", "index_dtype", "layout", "pad", "score_pad")
+
     def _key(self):
         # (NaN is a legitimate score_pad and is not equal to itself: the key holds its bits)
-        return (self.fields, self.dtype, self.index_dtype, self.layout, self.pad, np.float64(self.score_pad).tobytes())
+        return _TensorRule._key(self)[:-1] + (np.float64(self.score_pad).tobytes(),)
 
-    def __reduce__(self):
-        return _start_candidates_from_key, (self._key(),)
+    def _derive(self):
+        self.score_pad = float(np.frombuffer(self.score_pad, np.float64)[0])
 
     def __repr__(self):
         return "pyrodigal_amd.StartCandidates(%r, dtype=%r, index_dtype=%r, layout=%r, pad=%r, score_pad=%r)" % (
@@ -2584,29 +2491,14 @@ class StartCandidates(_TensorRule):
         return o
 
 
-def _start_candidates_from_key(key):
-    s = StartCandidates.__new__(StartCandidates)
-    s.fields, s.dtype, s.index_dtype, s.layout, s.pad, pad_bits = key
-    s.score_pad = float(np.frombuffer(pad_bits, np.float64)[0])
-    return s
-
-
-class _ContigStarts:
-    """``DeviceStarts.starts``: entry i is ``(positions, types, scores)`` of contig i's genes, views of the three tensors -- no copy."""
-
-    def __init__(self, owner):
-        self.owner = owner
-
-    def __len__(self):
-        return len(self.owner.gene_begin) - 1
-
-    def __getitem__(self, i):
-        d = self.owner
-        i = range(len(self))[i]
-        a, b = int(d.gene_begin[i]), int(d.gene_begin[i + 1])
-        if d.offsets is not None:
-            a, b = int(d.offsets[a]), int(d.offsets[b])
-        return d.positions[a:b], d.types[a:b], d.scores[a:b]
+# (what pickles name that were made when every rule had a function of its own)
+_protein_tokens_from_key = functools.partial(_rule_from_key, ProteinTokens)
+_base_labels_from_key = functools.partial(_rule_from_key, BaseLabels)
+_gene_windows_from_key = functools.partial(_rule_from_key, GeneWindows)
+_kmer_counts_from_key = functools.partial(_rule_from_key, KmerCounts)
+_protein_groups_from_key = functools.partial(_rule_from_key, ProteinGroups)
+_protein_sketches_from_key = functools.partial(_rule_from_key, ProteinSketches)
+_start_candidates_from_key = functools.partial(_rule_from_key, StartCandidates)
 
 
 class DeviceStarts:
@@ -2625,9 +2517,7 @@ class DeviceStarts:
 
     @property
     def starts(self):
-        if self.gene_begin is None:
-            raise ValueError("the gene records were not in contig order: there are no per-contig views")
-        return _ContigStarts(self)
+        return _gene_views(self, self.positions, self.types, self.scores)
 
     def cu_seqlens(self):
         """The exclusive scan of ``lengths`` as an int32 tensor on the tensors' device (torch)."""
@@ -2699,14 +2589,12 @@ class _StartPlan:
 def _read_device(tensor, stream):
     """The elements of a device tensor with a contiguous last dimension as a numpy array of its shape (``pga_device_read`` without a
     context: the pointer names its device)."""
-    cai = tensor.__cuda_array_interface__
-    shape, dt = tuple(int(x) for x in cai["shape"]), np.dtype(str(cai["typestr"]))
-    strides = cai.get("strides")
-    row = shape[-1] if strides is None or len(shape) < 2 else int(strides[0]) // dt.itemsize
+    ptr, shape, strides = _device_array(tensor, "the tensor")
+    dt = np.dtype(str(tensor.__cuda_array_interface__["typestr"]))
+    row = shape[-1] if len(shape) < 2 else strides[0] // dt.itemsize
     n = ((shape[0] - 1) * row + shape[1] if shape[0] and shape[1] else 0) if len(shape) == 2 else shape[0]
     flat = np.zeros(max(n, 1) if len(shape) == 1 else max(shape[0] * row, 1), dt)    # one buffer: whole rows, their gaps included
-    ptr = cai["data"][0]
-    rc = load().pga_device_read(None, ctypes.c_void_p(int(ptr) if ptr else 0), n * dt.itemsize, ctypes.c_void_p(flat.ctypes.data),
+    rc = load().pga_device_read(None, ctypes.c_void_p(ptr), n * dt.itemsize, ctypes.c_void_p(flat.ctypes.data),
                                 ctypes.c_void_p(DeviceSequences._stream_of(tensor, stream)))
     if rc == PGA_EINVAL:
         raise ValueError("pga_device_read: the tensor is not device memory")
@@ -2724,17 +2612,9 @@ def _start_outputs(spec, out, stream, device, lens):
     n, padded, F = len(lens), spec.layout == "padded", len(spec.fields)
     total, longest = int(lens.sum()) if n else 0, int(lens.max()) if n else 0
     if out is None:
-        try:
-            import torch
-        except ImportError:
-            raise TypeError("torch is not installed: pass out=, three device arrays with __cuda_array_interface__") from None
-        with torch.cuda.device(device):
-            shape = (n, longest) if padded else (total,)
-            out = (torch.empty(shape, dtype=getattr(torch, spec.index_dtype), device="cuda"),
-                   torch.empty(shape, dtype=getattr(torch, spec.index_dtype), device="cuda"),
-                   torch.empty(shape + (F,), dtype=getattr(torch, spec.dtype), device="cuda"))
-            if stream is None:
-                stream = int(torch.cuda.current_stream().cuda_stream)
+        shape = (n, longest) if padded else (total,)
+        out, stream = _torch_outputs(device, stream, [(shape, spec.index_dtype), (shape, spec.index_dtype), (shape + (F,), spec.dtype)],
+                                     "three device arrays")
     try:
         positions, types, scores = out
     except (TypeError, ValueError):
@@ -2743,30 +2623,22 @@ def _start_outputs(spec, out, stream, device, lens):
     for name, t, typestr, eb, cols in (("positions", positions, spec.index_typestr, spec.index_bytes, 1),
                                        ("types", types, spec.index_typestr, spec.index_bytes, 1),
                                        ("scores", scores, spec.score_typestr, spec.score_bytes, F)):
-        cai = getattr(t, "__cuda_array_interface__", None)
-        if not isinstance(cai, dict):
-            raise TypeError("%s must have a __cuda_array_interface__ (a device tensor or array), not %r" % (name, type(t).__name__))
-        if str(cai.get("typestr")) != typestr:
-            raise TypeError(f"{name} has dtype {cai.get('typestr')}: the rule writes {typestr}")
-        shape = tuple(int(x) for x in cai["shape"])
-        strides = cai.get("strides")
-        strides = None if strides is None else tuple(int(x) for x in strides)
+        ptr, shape, strides = _device_array(t, name, typestr, f"the rule writes {typestr}")
         want_dims = (2 if padded else 1) + (cols > 1 or name == "scores")
         if len(shape) != want_dims or (name == "scores" and shape[-1] != F):
             raise ValueError("%s must be %s, not of shape %s" % (name, ("[%d, W" % n if padded else "[T") + (", %d]" % F if name == "scores" else "]"), shape))
         inner = shape[-1] if name == "scores" else 1                   # elements of one candidate
-        if strides is not None:
-            if name == "scores" and F > 1 and strides[-1] != eb:
-                raise ValueError("the last dimension of scores is not contiguous")
-            cand = strides[-2] if name == "scores" else strides[-1]    # bytes from a candidate to the next
-            if shape[-2 if name == "scores" else -1] > 1 and cand != eb * inner:
-                raise ValueError(f"the candidates of {name} are not contiguous")
+        if name == "scores" and F > 1 and strides[-1] != eb:
+            raise ValueError("the last dimension of scores is not contiguous")
+        cand = strides[-2] if name == "scores" else strides[-1]        # bytes from a candidate to the next
+        if shape[-2 if name == "scores" else -1] > 1 and cand != eb * inner:
+            raise ValueError(f"the candidates of {name} are not contiguous")
         if padded:
             if shape[0] != n:
                 raise ValueError(f"the padded layout needs {n} rows: {name} has {shape[0]}")
             w = shape[1]
-            s_ = w if strides is None or n < 2 else strides[0] // (eb * inner)
-            if strides is not None and n > 1 and (strides[0] % (eb * inner) or strides[0] < 0):
+            s_ = w if n < 2 else strides[0] // (eb * inner)
+            if n > 1 and (strides[0] % (eb * inner) or strides[0] < 0):
                 raise ValueError(f"the rows of {name} do not lie a whole, positive number of candidates apart")
             if w < longest:
                 raise ValueError(f"{name} has {w} columns: gene {int(np.argmax(lens))} has {longest} candidates")
@@ -2779,8 +2651,7 @@ def _start_outputs(spec, out, stream, device, lens):
             if shape[0] < total:
                 raise ValueError(f"{name} has {shape[0]} candidates: the genes have {total}")
             n_elems.append(shape[0] * inner)
-        ptr = cai["data"][0]
-        ptrs.append(ctypes.c_void_p(int(ptr) if ptr else 0))
+        ptrs.append(ctypes.c_void_p(ptr))
     return (positions, types, scores), stream, ptrs, width, stride or 0, n_elems
 
 
@@ -2821,11 +2692,8 @@ def starts_into(L, ctx_h, batch_h, device, n_contigs, genes, spec, out=None, str
     if spec.layout == "ragged":
         off = np.zeros(n + 1, np.int64)
         np.cumsum(lens, out=off[1:])
-    gene_begin = None
-    if n == 0 or np.all(np.diff(genes["contig"]) >= 0):
-        gene_begin = np.searchsorted(genes["contig"], np.arange(n_contigs + 1)).astype(np.int64)
-    return DeviceStarts(out[0], out[1], out[2], chosen[:n].astype(np.int64), lens, off, gene_begin, genes, spec.fields, device, plan, stream,
-                        nodes)
+    return DeviceStarts(out[0], out[1], out[2], chosen[:n].astype(np.int64), lens, off, _gene_begin(genes, n_contigs), genes, spec.fields,
+                        device, plan, stream, nodes)
 
 
 def _start_candidates(self, batch, result_or_genes, spec, out=None, stream=None):

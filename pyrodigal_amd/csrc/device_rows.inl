@@ -1,7 +1,10 @@
-// Rows of 1-, 4- or 8-byte elements written into a caller's device tensor, ragged or padded, at any element alignment (DESIGN.md
-// 4.14): the destination's description and the host side of such a call, which k_translate_tokens (translate_tokens.inl),
-// k_label_bases (label_bases.inl) and k_gene_windows (gene_windows.inl) share.  Included by translate.hip, inside its anonymous
-// namespace, in front of the three.
+// The host side that the calls which write device tensors share, and the rows some of them write.  DevCall: the
+// refusals, the shared checks of records, tables and destinations, and the tail of a call -- for all of pga_translate_genes_tokens,
+// pga_label_bases, pga_gene_windows, pga_count_kmers, pga_group_proteins, pga_sketch_proteins, pga_sketch_pairs and the
+// pga_start_plan_* calls.  Staging: the tables of a call laid out in the upload lease.  RowDest, on top of DevCall: rows of 1-, 4- or
+// 8-byte elements in a caller's tensor, ragged or padded, at any element alignment, which k_translate_tokens (translate_tokens.inl),
+// k_label_bases (label_bases.inl) and k_gene_windows (gene_windows.inl) write.  Included by translate.hip, inside its anonymous
+// namespace, in front of the kernel files.
 
 constexpr int kRowThreads = 256;
 
@@ -33,14 +36,103 @@ void with_elem_layout(const int eb, const bool padded, F f) {
     else layout(std::integral_constant<int, 8>{});
 }
 
-// The caller's destination, checked on the host before anything is allocated or launched, and the RowArgs that describe it.  The
-// steps are called in the order in which an entry point refuses: each returns PGA_OK or the refusal, its message in c->err.
-struct RowDest {
+// A call on the context: its refusals, and the steps that every call which writes device tensors takes.  Each check returns PGA_OK
+// or the refusal, its message in c->err; an entry point calls them in the order in which it refuses.
+struct DevCall {
     pga_ctx* c; const char* fn;
+
+    int bad(const std::string& msg) { c->err = std::string(fn) + ": " + msg; return PGA_EINVAL; }
+
+    int contig_known(const pga_batch_view& bv, const pga_gene& G, const int64_t g) {
+        if (G.contig < 0 || G.contig >= bv.n) return bad("gene " + std::to_string(g) + " names contig " + std::to_string(G.contig) + " of " + std::to_string(bv.n));
+        return PGA_OK;
+    }
+    // record g inside its contig (gene_inside: the rule of the calls that read proteins)
+    int record_inside(const pga_batch_view& bv, const pga_gene& G, const int64_t g) {
+        return gene_inside(bv, G) ? PGA_OK : bad("gene " + std::to_string(g) + " lies outside its contig");
+    }
+    // record g inside its contig, in whole codons, across the origin only on a contig flagged circular: the rule of the calls that read
+    // bases, with a message for each way to miss it
+    int whole_codon_record(const pga_batch_view& bv, const pga_gene& G, const int64_t g) {
+        if (const int rc = contig_known(bv, G, g)) return rc;
+        const int64_t len = bv.ct[G.contig].len, glen = (int64_t)G.end - G.begin + 1;
+        if (G.begin < 1 || G.begin > len || glen < 3 || glen > len) return bad("gene " + std::to_string(g) + " lies outside its contig");
+        if (glen % 3) return bad("gene " + std::to_string(g) + " is " + std::to_string(glen) + " bases long, no whole number of codons");
+        if (G.end > len && !(bv.circular && bv.circular[G.contig])) return bad("gene " + std::to_string(g) + " ends beyond its contig, which is not flagged circular");
+        return PGA_OK;
+    }
+    int tables_known(const pga_batch_view& bv, const int32_t* table_of_contig) {
+        for (int i = 0; i < bv.n; i++)
+            if (!table_known(table_of_contig[i])) return bad("contig " + std::to_string(i) + ": " + std::to_string(table_of_contig[i]) + " is not a valid translation table index");
+        return PGA_OK;
+    }
+
+    // The device pointers of a call.  kRequired: refused when NULL; kOptional: NULL leaves it out; kUnread: the call will not read it,
+    // only its alignment is looked at.  First every NULL, then every alignment (`in_turn`: both, pointer after pointer), then every
+    // pointer that is read must be device memory of the context's device.
+    enum Need { kUnread = -1, kOptional = 0, kRequired = 1 };
+    struct Dest { const char* name; const void* p; int elem_bytes; int need; };
+    int destinations(std::initializer_list<Dest> ds, const bool in_turn = false) {
+        auto missing = [](const Dest& x) { return x.need == kRequired && !x.p; };
+        if (!in_turn) for (const Dest& x : ds) if (missing(x)) return bad(std::string(x.name) + " is NULL");
+        for (const Dest& x : ds) {
+            if (in_turn && missing(x)) return bad(std::string(x.name) + " is NULL");
+            if ((uintptr_t)x.p % (uintptr_t)x.elem_bytes) return bad(std::string(x.name) + " is not aligned to its " + std::to_string(x.elem_bytes) + "-byte elements");
+        }
+        if (hipSetDevice(c->device) != hipSuccess) return PGA_EDEVICE;
+        for (const Dest& x : ds) if (x.p && x.need != kUnread) if (const int rc = pga_device_memory_(c, x.p, fn, x.name)) return rc;
+        return PGA_OK;
+    }
+
+    // The tail of a call: the first `bytes` of the lease's pinned area go up behind what the caller's stream held when the call came
+    // (the upload stream is non-blocking), work(L.st) enqueues there and returns what HIP said (it may wait for the stream itself), and
+    // on return the tensors are complete for any stream.  landed() runs once all of it is done and went well: what came back into the
+    // pinned area is read there.  The stream is idle when the lease goes back, also after a failure: nothing of it is still in use.
+    template <typename Work, typename Landed>
+    int run(const pga_upload_lease& L, const size_t bytes, void* stream, Work work, Landed landed) {
+        hipError_t e = hipEventRecord(L.ev, (hipStream_t)stream);
+        if (e == hipSuccess) e = hipStreamWaitEvent(L.st, L.ev, 0);
+        if (e == hipSuccess && bytes > 0) e = hipMemcpyAsync(L.dev, L.pin, bytes, hipMemcpyHostToDevice, L.st);
+        if (e == hipSuccess) e = work(L.st);
+        const hipError_t es = hipStreamSynchronize(L.st);
+        if (e == hipSuccess) e = es;
+        if (e == hipSuccess) landed();
+        pga_upload_lease_give(c);
+        return pga_hip_try_(c, e, fn);
+    }
+    template <typename Work>
+    int run(const pga_upload_lease& L, const size_t bytes, void* stream, Work work) { return run(L, bytes, stream, work, [] {}); }
+};
+
+// The tables of a call as they will lie in the upload lease: consecutive slices, each begun at a multiple of `align`.  The slices are
+// named first -- put: bytes to copy there, take: room only -- and return their offset; lease() takes bytes() of the context's lease
+// and copies what was put into its pinned area; then pin<T>(offset) / dev<T>(offset) are the two addresses of a slice.
+struct Staging {
+    const size_t align;
+    pga_upload_lease L{};
+    explicit Staging(const size_t align_ = 1) : align(align_) {}
+    size_t take(const size_t bytes) { const size_t at = end_; end_ = (at + bytes + align - 1) / align * align; return at; }
+    size_t put(const void* src, const size_t bytes) { src_.push_back({take(bytes), src, bytes}); return src_.back().at; }
+    size_t bytes() const { return end_; }
+    int lease(pga_ctx* c) {
+        if (const int rc = pga_upload_lease_take(c, end_, &L)) return rc;
+        for (const Src& s : src_) if (s.n) memcpy(L.pin + s.at, s.p, s.n);
+        return PGA_OK;
+    }
+    template <typename T> T* pin(const size_t at) const { return (T*)(L.pin + at); }
+    template <typename T> T* dev(const size_t at) const { return (T*)(L.dev + at); }
+private:
+    struct Src { size_t at; const void* p; size_t n; };
+    size_t end_ = 0;
+    std::vector<Src> src_;
+};
+
+// The caller's destination of a call that writes rows, and the RowArgs that describe it.
+struct RowDest : DevCall {
     int eb = 0; bool padded = false;
     RowArgs a{};
 
-    int bad(const std::string& msg) { c->err = std::string(fn) + ": " + msg; return PGA_EINVAL; }
+    RowDest(pga_ctx* ctx, const char* name) : DevCall{ctx, name} {}
     const char* elem_name() const { return eb == 1 ? "uint8" : eb == 4 ? "int32" : "int64"; }
     int format(const int elem_bytes, const int layout) {
         eb = elem_bytes;
@@ -58,6 +150,11 @@ struct RowDest {
         for (int k = 0; k < n; k++) if (!fit(v[k])) return fits(std::string(table) + "[" + std::to_string(k) + "]", v[k]);
         return PGA_OK;
     }
+    // the elements of the layout against what the caller gave
+    int room(const int64_t n_out_elems) {
+        if (n_out_elems < a.n_elems) return bad("n_out_elems = " + std::to_string(n_out_elems) + " is less than the " + std::to_string(a.n_elems) + " elements of the layout");
+        return PGA_OK;
+    }
     // the layout against the rows' lengths (`off`: their exclusive scan), `units of row` naming the longest ("tokens of gene")
     int shape(const std::vector<int64_t>& off, const char* units_of_row, const int64_t W, const int64_t S, const int64_t pad, const int64_t n_out_elems) {
         const int64_t n = (int64_t)off.size() - 1;
@@ -71,33 +168,22 @@ struct RowDest {
             a.n_elems = n > 0 ? (n - 1) * S + W : 0;
             a.W = W; a.S = S; a.pad = pad;
         }
-        if (n_out_elems < a.n_elems) return bad("n_out_elems = " + std::to_string(n_out_elems) + " is less than the " + std::to_string(a.n_elems) + " elements of the layout");
-        return PGA_OK;
+        return room(n_out_elems);
     }
     int memory(void* d_out) {
         if (a.n_elems == 0) return PGA_OK;
-        if (!d_out) return bad("d_out is NULL");
-        if ((uintptr_t)d_out % (uintptr_t)eb) return bad("d_out is not aligned to its " + std::to_string(eb) + "-byte elements");
-        if (hipSetDevice(c->device) != hipSuccess) return PGA_EDEVICE;
-        if (const int rc = pga_device_memory_(c, d_out, fn, "d_out")) return rc;
+        if (const int rc = destinations({{"d_out", d_out, eb, kRequired}})) return rc;
         a.out0 = (char*)((uintptr_t)d_out & ~(uintptr_t)15);
         a.lead = (int32_t)(((uintptr_t)d_out - (uintptr_t)a.out0) / (uintptr_t)eb);
         return PGA_OK;
     }
-    // The tail of the call: the `tab` bytes staged in the lease go up behind what the caller's stream held when the call came (the
-    // upload stream is non-blocking), launch(grid, block, stream) runs there, and on return the tensor is complete for any stream.
+    // the tail (DevCall::run) with launch(grid, block, stream): a thread per 16 bytes of the layout
     template <typename Launch>
-    int run(pga_upload_lease& L, const size_t tab, void* stream, Launch launch) {
+    int run(const Staging& s, void* stream, Launch launch) {
         const int64_t per = 16 / eb, pieces = (a.lead + a.n_elems + per - 1) / per;
-        hipError_t e = hipEventRecord(L.ev, (hipStream_t)stream);
-        if (e == hipSuccess) e = hipStreamWaitEvent(L.st, L.ev, 0);
-        if (e == hipSuccess) e = hipMemcpyAsync(L.dev, L.pin, tab, hipMemcpyHostToDevice, L.st);
-        if (e == hipSuccess) {
-            launch(dim3((unsigned)((pieces + kRowThreads - 1) / kRowThreads)), dim3(kRowThreads), L.st);
-            e = hipGetLastError();
-        }
-        if (e == hipSuccess) e = hipStreamSynchronize(L.st);
-        pga_upload_lease_give(c);
-        return pga_hip_try_(c, e, fn);
+        return DevCall::run(s.L, s.bytes(), stream, [&](hipStream_t st) {
+            launch(dim3((unsigned)((pieces + kRowThreads - 1) / kRowThreads)), dim3(kRowThreads), st);
+            return hipGetLastError();
+        });
     }
 };

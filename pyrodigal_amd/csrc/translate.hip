@@ -102,6 +102,22 @@ int64_t gene_residues(const pga_gene& G, const int include_stop) {
 #include "protein_sketches.inl"
 #include "start_candidates.inl"
 
+// the records as k_string_digest, k_group_verify and k_sketch read them
+void grp_rows(GrpRow* rows, const pga_gene* genes, const int64_t n, const pga_batch_view& bv, const bool protein, const int include_stop,
+              const int32_t* table_of_contig) {
+    for (int64_t g = 0; g < n; g++) {
+        const pga_gene& R = genes[g];
+        const bool fwd = R.strand == 1;
+        GrpRow& w = rows[g];
+        w.base = bv.ct[R.contig].base; w.L = bv.ct[R.contig].len;
+        w.q0 = fwd ? R.begin - 1 : R.end - 1;
+        w.n = protein ? (int32_t)gene_residues(R, include_stop) : R.end - R.begin + 1;
+        // partial flags are in sequence orientation; the gene's own first codon follows its strand
+        const bool start_edge = fwd ? R.partial_begin != 0 : R.partial_end != 0;
+        w.bits = (fwd ? 1u : 0u) | (start_edge ? 2u : 0u) | (protein ? (uint32_t)table_of_contig[R.contig] << 8 : 0u);
+    }
+}
+
 }  // namespace
 
 extern "C" int pga_translate_genes(pga_ctx* c, const pga_batch* batch, int64_t n_genes, const pga_gene* genes, const int32_t* table_of_contig,
@@ -164,11 +180,10 @@ extern "C" int pga_translate_genes_tokens(pga_ctx* c, const pga_batch* batch, in
     if (d.padded) if (const int rc = d.fits("pad", o->pad)) return rc;
     if (o->max_length < 0 || (o->max_length != 0 && o->max_length < s + 1))
         return d.bad("max_length = " + std::to_string(o->max_length) + " leaves no room for a residue beside " + std::to_string(s) + " special tokens (0: no limit)");
-    for (int i = 0; i < (n_genes > 0 ? bv.n : 0); i++)
-        if (!table_known(table_of_contig[i])) return d.bad("contig " + std::to_string(i) + ": " + std::to_string(table_of_contig[i]) + " is not a valid translation table index");
+    if (n_genes > 0) if (const int rc = d.tables_known(bv, table_of_contig)) return rc;
     std::vector<int64_t> off((size_t)n_genes + 1, 0);
     for (int64_t g = 0; g < n_genes; g++) {
-        if (!gene_inside(bv, genes[g])) return d.bad("gene " + std::to_string(g) + " lies outside its contig");
+        if (const int rc = d.record_inside(bv, genes[g], g)) return rc;
         int64_t r = gene_residues(genes[g], o->include_stop);
         if (o->max_length != 0 && r > o->max_length - s) r = o->max_length - s;
         off[(size_t)g + 1] = off[(size_t)g] + s + r;
@@ -180,23 +195,18 @@ extern "C" int pga_translate_genes_tokens(pga_ctx* c, const pga_batch* batch, in
     { const int rc = tables_ready(c); if (rc) return rc; }
     // ---- the kernel's tables: staged in the upload's pinned area as they will lie on the device, one copy ----
     const size_t G = (size_t)n_genes, n = (size_t)bv.n;
-    const size_t off_b = sizeof(int64_t) * (G + 1), voc_b = sizeof(int64_t) * 128, ct_b = sizeof(ContigDesc) * (n + 1), gen_b = sizeof(pga_gene) * G, tt_b = sizeof(int32_t) * n;
-    const size_t tab = off_b + voc_b + ct_b + gen_b + tt_b;
-    pga_upload_lease L{};
-    { const int rc = pga_upload_lease_take(c, tab, &L); if (rc) return rc; }
-    memcpy(L.pin, off.data(), off_b);
-    memcpy(L.pin + off_b, o->vocab, voc_b);
-    memcpy(L.pin + off_b + voc_b, bv.ct, ct_b);
-    memcpy(L.pin + off_b + voc_b + ct_b, genes, gen_b);
-    memcpy(L.pin + off_b + voc_b + ct_b + gen_b, table_of_contig, tt_b);
+    Staging tab;
+    const size_t p_off = tab.put(off.data(), sizeof(int64_t) * (G + 1)), p_voc = tab.put(o->vocab, sizeof(int64_t) * 128), p_ct = tab.put(bv.ct, sizeof(ContigDesc) * (n + 1));
+    const size_t p_gen = tab.put(genes, sizeof(pga_gene) * G), p_tt = tab.put(table_of_contig, sizeof(int32_t) * n);
+    if (const int rc = tab.lease(c)) return rc;
     TokArgs a{};
-    a.rows = d.a; a.rows.off = (const int64_t*)L.dev;
+    a.rows = d.a; a.rows.off = tab.dev<const int64_t>(p_off);
     a.seq = bv.d_seq;
-    a.vocab = (const int64_t*)(L.dev + off_b); a.ct = (const ContigDesc*)(L.dev + off_b + voc_b);
-    a.genes = (const pga_gene*)(L.dev + off_b + voc_b + ct_b); a.tt_of = (const int32_t*)(L.dev + off_b + voc_b + ct_b + gen_b);
+    a.vocab = tab.dev<const int64_t>(p_voc); a.ct = tab.dev<const ContigDesc>(p_ct);
+    a.genes = tab.dev<const pga_gene>(p_gen); a.tt_of = tab.dev<const int32_t>(p_tt);
     a.bos = has_bos ? o->bos : 0; a.eos = has_eos ? o->eos : 0;
     a.has_bos = has_bos; a.has_eos = has_eos; a.unk = o->unknown_residue; a.strict = o->strict;
-    return d.run(L, tab, stream, [&](const dim3 grid, const dim3 block, hipStream_t st) {
+    return d.run(tab, stream, [&](const dim3 grid, const dim3 block, hipStream_t st) {
         with_elem_layout(d.eb, d.padded, [&](auto EB, auto PADDED) {
             hipLaunchKernelGGL((k_translate_tokens<decltype(EB)::value, decltype(PADDED)::value>), grid, block, 0, st, a);
         });
@@ -225,33 +235,24 @@ extern "C" int pga_label_bases(pga_ctx* c, const pga_batch* batch, int64_t n_gen
     // every record inside its contig, in whole codons; a record across the origin makes two stretches
     for (int64_t g = 0; g < n_genes; g++) {
         const pga_gene& G = genes[g];
-        const std::string who = "gene " + std::to_string(g);
-        if (G.contig < 0 || G.contig >= bv.n) return d.bad(who + " names contig " + std::to_string(G.contig) + " of " + std::to_string(bv.n));
-        const int64_t len = bv.ct[G.contig].len, glen = (int64_t)G.end - G.begin + 1;
-        if (G.begin < 1 || G.begin > len || glen < 3 || glen > len) return d.bad(who + " lies outside its contig");
-        if (glen % 3) return d.bad(who + " is " + std::to_string(glen) + " bases long, no whole number of codons");
-        if (G.end > len && !(bv.circular && bv.circular[G.contig])) return d.bad(who + " ends beyond its contig, which is not flagged circular");
-        iv_off[(size_t)G.contig + 1] += G.end > len ? 2 : 1;
+        if (const int rc = d.whole_codon_record(bv, G, g)) return rc;
+        iv_off[(size_t)G.contig + 1] += G.end > bv.ct[G.contig].len ? 2 : 1;
     }
     if (const int rc = d.memory(d_out)) return rc;
     for (size_t i = 0; i < B; i++) len_out[i] = bv.ct[i].len;
     if (d.a.n_elems == 0) return PGA_OK;
     // ---- the kernel's tables: staged in the upload's pinned area as they will lie on the device, one copy ----
     for (size_t i = 0; i < B; i++) iv_off[i + 1] += iv_off[i];
-    const size_t n_iv = (size_t)iv_off[B];
-    const size_t off_b = sizeof(int64_t) * (B + 1), map_b = sizeof(int64_t) * 256, iv_b = sizeof(LabIv) * n_iv;
-    const size_t tab = 2 * off_b + map_b + iv_b;               // (the stretches begin at a multiple of 16 bytes)
-    pga_upload_lease L{};
-    { const int rc = pga_upload_lease_take(c, tab, &L); if (rc) return rc; }
-    memcpy(L.pin, off.data(), off_b);
-    memcpy(L.pin + off_b, iv_off.data(), off_b);
-    memcpy(L.pin + 2 * off_b, o->class_map, map_b);
-    lab_stretches(genes, n_genes, bv.ct, iv_off.data(), B, (LabIv*)(L.pin + 2 * off_b + map_b));
+    Staging tab;
+    const size_t p_off = tab.put(off.data(), sizeof(int64_t) * (B + 1)), p_ivoff = tab.put(iv_off.data(), sizeof(int64_t) * (B + 1));
+    const size_t p_map = tab.put(o->class_map, sizeof(int64_t) * 256), p_iv = tab.take(sizeof(LabIv) * (size_t)iv_off[B]);      // (the stretches begin at a multiple of 16 bytes)
+    if (const int rc = tab.lease(c)) return rc;
+    lab_stretches(genes, n_genes, bv.ct, iv_off.data(), B, tab.pin<LabIv>(p_iv));
     LabArgs a{};
-    a.rows = d.a; a.rows.off = (const int64_t*)L.dev;
-    a.iv_off = (const int64_t*)(L.dev + off_b); a.cmap = (const int64_t*)(L.dev + 2 * off_b);
-    a.iv = (const LabIv*)(L.dev + 2 * off_b + map_b);
-    return d.run(L, tab, stream, [&](const dim3 grid, const dim3 block, hipStream_t st) {
+    a.rows = d.a; a.rows.off = tab.dev<const int64_t>(p_off);
+    a.iv_off = tab.dev<const int64_t>(p_ivoff); a.cmap = tab.dev<const int64_t>(p_map);
+    a.iv = tab.dev<const LabIv>(p_iv);
+    return d.run(tab, stream, [&](const dim3 grid, const dim3 block, hipStream_t st) {
         with_elem_layout(d.eb, d.padded, [&](auto EB, auto PADDED) {
             hipLaunchKernelGGL((k_label_bases<decltype(EB)::value, decltype(PADDED)::value>), grid, block, 0, st, a);
         });
@@ -285,17 +286,13 @@ extern "C" int pga_gene_windows(pga_ctx* c, const pga_batch* batch, int64_t n_ge
     }
     if (o->max_length < 0 || (o->max_length != 0 && o->max_length < s + 1))
         return d.bad("max_length = " + std::to_string(o->max_length) + " leaves no room for a unit beside " + std::to_string(s) + " special tokens (0: no limit)");
-    // every record inside its contig, in whole codons (the checks of pga_label_bases); the tokens of its row
+    // every record inside its contig, in whole codons; the tokens of its row
     const int64_t per_unit = codons ? 3 : 1;
     std::vector<int64_t> off((size_t)n_genes + 1, 0);
     for (int64_t g = 0; g < n_genes; g++) {
         const pga_gene& G = genes[g];
-        const std::string who = "gene " + std::to_string(g);
-        if (G.contig < 0 || G.contig >= bv.n) return d.bad(who + " names contig " + std::to_string(G.contig) + " of " + std::to_string(bv.n));
-        const int64_t len = bv.ct[G.contig].len, glen = (int64_t)G.end - G.begin + 1;
-        if (G.begin < 1 || G.begin > len || glen < 3 || glen > len) return d.bad(who + " lies outside its contig");
-        if (glen % 3) return d.bad(who + " is " + std::to_string(glen) + " bases long, no whole number of codons");
-        if (G.end > len && !(bv.circular && bv.circular[G.contig])) return d.bad(who + " ends beyond its contig, which is not flagged circular");
+        if (const int rc = d.whole_codon_record(bv, G, g)) return rc;
+        const int64_t glen = (int64_t)G.end - G.begin + 1;
         const int64_t t_lo = (o->from_anchor == PGA_WINDOW_END ? glen : 0) + o->from_delta, t_hi = (o->to_anchor == PGA_WINDOW_END ? glen : 0) + o->to_delta;
         int64_t r = t_hi > t_lo ? (t_hi - t_lo) / per_unit : 0;
         if (o->max_length != 0 && r > o->max_length - s) r = o->max_length - s;
@@ -307,25 +304,22 @@ extern "C" int pga_gene_windows(pga_ctx* c, const pga_batch* batch, int64_t n_ge
     if (d.a.n_elems == 0) return PGA_OK;
     // ---- the kernel's tables: staged in the upload's pinned area as they will lie on the device, one copy ----
     const size_t G = (size_t)n_genes;
-    const size_t off_b = sizeof(int64_t) * (G + 1), ids_b = sizeof(int64_t) * 66, win_b = sizeof(WinRow) * G;
-    const size_t tab = off_b + ids_b + win_b;
-    pga_upload_lease L{};
-    { const int rc = pga_upload_lease_take(c, tab, &L); if (rc) return rc; }
-    memcpy(L.pin, off.data(), off_b);
-    memcpy(L.pin + off_b, o->ids, ids_b);
-    WinRow* const win = (WinRow*)(L.pin + off_b + ids_b);
+    Staging tab;
+    const size_t p_off = tab.put(off.data(), sizeof(int64_t) * (G + 1)), p_ids = tab.put(o->ids, sizeof(int64_t) * 66), p_win = tab.take(sizeof(WinRow) * G);
+    if (const int rc = tab.lease(c)) return rc;
+    WinRow* const win = tab.pin<WinRow>(p_win);
     for (size_t g = 0; g < G; g++) {
         const pga_gene& R = genes[g];
         const int64_t glen = (int64_t)R.end - R.begin + 1;
         win[g] = win_row(R, bv.ct[R.contig], bv.circular && bv.circular[R.contig], (o->from_anchor == PGA_WINDOW_END ? glen : 0) + o->from_delta);
     }
     WinArgs a{};
-    a.rows = d.a; a.rows.off = (const int64_t*)L.dev;
+    a.rows = d.a; a.rows.off = tab.dev<const int64_t>(p_off);
     a.seq = bv.d_seq;
-    a.ids = (const int64_t*)(L.dev + off_b); a.win = (const WinRow*)(L.dev + off_b + ids_b);
+    a.ids = tab.dev<const int64_t>(p_ids); a.win = tab.dev<const WinRow>(p_win);
     a.bos = has_bos ? o->bos : 0; a.eos = has_eos ? o->eos : 0;
     a.has_bos = has_bos; a.has_eos = has_eos; a.codons = codons;
-    return d.run(L, tab, stream, [&](const dim3 grid, const dim3 block, hipStream_t st) {
+    return d.run(tab, stream, [&](const dim3 grid, const dim3 block, hipStream_t st) {
         with_elem_layout(d.eb, d.padded, [&](auto EB, auto PADDED) {
             hipLaunchKernelGGL((k_gene_windows<decltype(EB)::value, decltype(PADDED)::value>), grid, block, 0, st, a);
         });
@@ -361,8 +355,8 @@ extern "C" int pga_count_kmers(pga_ctx* c, const pga_batch* batch, int64_t n_gen
     if (S < n_bins) return d.bad("row_stride = " + std::to_string(S) + " is less than n_bins = " + std::to_string(n_bins));
     if (R > 1 && S > (INT64_MAX / 8 - n_bins) / (R - 1)) return d.bad("row_stride = " + std::to_string(S) + " is too large");
     d.eb = 4; d.a.n_rows = R; d.a.n_elems = R > 0 ? (R - 1) * S + n_bins : 0;
-    if (n_out_elems < d.a.n_elems) return d.bad("n_out_elems = " + std::to_string(n_out_elems) + " is less than the " + std::to_string(d.a.n_elems) + " elements of the layout");
-    // the rows of work: a contig each, or a checked record each (the checks of pga_label_bases); the windows of every row of d_out
+    if (const int rc = d.room(n_out_elems)) return rc;
+    // the rows of work: a contig each, or a checked record each; the windows of every row of d_out
     const size_t NW = (size_t)(by_contig ? B : n_genes);
     if (NW > (size_t)INT32_MAX) return d.bad("more than 2^31 - 1 gene records");
     std::vector<CntRow> rows(NW);
@@ -380,16 +374,10 @@ extern "C" int pga_count_kmers(pga_ctx* c, const pga_batch* batch, int64_t n_gen
             continue;
         }
         const pga_gene& G = genes[i];
-        const std::string who = "gene " + std::to_string(i);
-        if (G.contig < 0 || G.contig >= bv.n) return d.bad(who + " names contig " + std::to_string(G.contig) + " of " + std::to_string(bv.n));
-        const int64_t len = bv.ct[G.contig].len, glen = (int64_t)G.end - G.begin + 1;
-        if (G.begin < 1 || G.begin > len || glen < 3 || glen > len) return d.bad(who + " lies outside its contig");
-        if (glen % 3) return d.bad(who + " is " + std::to_string(glen) + " bases long, no whole number of codons");
-        const bool circ = bv.circular && bv.circular[G.contig];
-        if (G.end > len && !circ) return d.bad(who + " ends beyond its contig, which is not flagged circular");
-        const WinRow q = win_row(G, bv.ct[G.contig], circ, 0);
+        if (const int rc = d.whole_codon_record(bv, G, (int64_t)i)) return rc;
+        const WinRow q = win_row(G, bv.ct[G.contig], bv.circular && bv.circular[G.contig], 0);
         w.base = q.base; w.q0 = (int32_t)q.q0; w.L = q.L; w.bits = q.bits & 1u;
-        w.n_win = (int32_t)windows(glen);
+        w.n_win = (int32_t)windows((int64_t)G.end - G.begin + 1);
         w.dst = summed ? G.contig : (int32_t)i;
         win[(size_t)w.dst] += w.n_win;
     }
@@ -425,23 +413,18 @@ extern "C" int pga_count_kmers(pga_ctx* c, const pga_batch* batch, int64_t n_gen
     if (summed || direct) { zero.resize((size_t)R); std::iota(zero.begin(), zero.end(), 0); for (auto& w : rows) w.bits |= 2u; }
     else for (size_t i = 0; i < NW; i++) if (cut[i]) { rows[i].bits |= 2u; zero.push_back(rows[i].dst); }
     // ---- the kernel's tables: staged in the upload's pinned area as they will lie on the device, one copy ----
-    auto al = [](const size_t x) { return (x + 15) & ~(size_t)15; };
-    const size_t piece_b = al(sizeof(int2) * piece.size()), row_b = al(sizeof(CntRow) * NW), bin_b = al(sizeof(int32_t) * (size_t)n_codes), z_b = al(sizeof(int32_t) * zero.size());
-    const size_t tab = piece_b + row_b + bin_b + z_b;
-    pga_upload_lease L{};
-    { const int rc = pga_upload_lease_take(c, tab, &L); if (rc) return rc; }
-    memcpy(L.pin, piece.data(), sizeof(int2) * piece.size());
-    memcpy(L.pin + piece_b, rows.data(), sizeof(CntRow) * NW);
-    memcpy(L.pin + piece_b + row_b, o->bin_of_code, sizeof(int32_t) * (size_t)n_codes);
-    memcpy(L.pin + piece_b + row_b + bin_b, zero.data(), sizeof(int32_t) * zero.size());
+    Staging tab(16);
+    const size_t p_piece = tab.put(piece.data(), sizeof(int2) * piece.size()), p_row = tab.put(rows.data(), sizeof(CntRow) * NW);
+    const size_t p_bin = tab.put(o->bin_of_code, sizeof(int32_t) * (size_t)n_codes), p_zero = tab.put(zero.data(), sizeof(int32_t) * zero.size());
+    if (const int rc = tab.lease(c)) return rc;
     CntArgs a{};
-    a.seq = bv.d_seq; a.piece = (const int2*)L.dev; a.row = (const CntRow*)(L.dev + piece_b);
-    a.bin_of_code = (const int32_t*)(L.dev + piece_b + row_b);
+    a.seq = bv.d_seq; a.piece = tab.dev<const int2>(p_piece); a.row = tab.dev<const CntRow>(p_row);
+    a.bin_of_code = tab.dev<const int32_t>(p_bin);
     a.out = (int32_t*)d_out; a.n_pieces = pieces; a.S = S;
     a.k = (int32_t)k; a.step = (int32_t)step; a.n_bins = (int32_t)n_bins; a.wide = ((uintptr_t)bv.d_seq & 3u) == 0;
-    const int32_t* d_zero = (const int32_t*)(L.dev + piece_b + row_b + bin_b);
+    const int32_t* d_zero = tab.dev<const int32_t>(p_zero);
     const int64_t n_zero = (int64_t)zero.size();
-    return d.run(L, tab, stream, [&](const dim3, const dim3 block, hipStream_t st) {
+    return d.run(tab, stream, [&](const dim3, const dim3 block, hipStream_t st) {
         if (n_zero > 0) hipLaunchKernelGGL(k_kmer_zero, dim3((unsigned)((n_zero * n_bins + kRowThreads - 1) / kRowThreads)), block, 0, st, a.out, S, a.n_bins, d_zero, n_zero);
         if (pieces == 0) return;
         const dim3 grid((unsigned)(per_wave ? (pieces + 3) / 4 : pieces));
@@ -464,39 +447,33 @@ extern "C" int pga_group_proteins(pga_ctx* c, const pga_batch* batch, int64_t n_
                                   const pga_group_opts* o, int64_t* d_group, int64_t* d_representative, int64_t* d_size, int64_t* d_digest,
                                   int64_t capacity, void* stream, int64_t* n_groups) {
     if (!c) return PGA_EINVAL;
-    const char* const fn = "pga_group_proteins";
-    auto bad = [&](const std::string& msg) { c->err = std::string(fn) + ": " + msg; return PGA_EINVAL; };
-    if (!batch || !o || !n_groups || n_genes < 0 || (n_genes > 0 && !genes)) return bad("bad arguments");
+    DevCall d{c, "pga_group_proteins"};
+    if (!batch || !o || !n_groups || n_genes < 0 || (n_genes > 0 && !genes)) return d.bad("bad arguments");
     const pga_batch_view bv = pga_batch_peek(batch);
-    if (bv.ctx != c) return bad("the batch belongs to another context");
+    if (bv.ctx != c) return d.bad("the batch belongs to another context");
     // ---- validation: all of it on the host, before anything is allocated or launched ----
-    if (o->unit != PGA_GROUP_PROTEIN && o->unit != PGA_GROUP_GENE) return bad("unit must be PGA_GROUP_PROTEIN or PGA_GROUP_GENE, not " + std::to_string(o->unit));
+    if (o->unit != PGA_GROUP_PROTEIN && o->unit != PGA_GROUP_GENE) return d.bad("unit must be PGA_GROUP_PROTEIN or PGA_GROUP_GENE, not " + std::to_string(o->unit));
     const bool protein = o->unit == PGA_GROUP_PROTEIN;
-    if (o->unknown_residue <= 0 || o->unknown_residue > 127) return bad("`unknown_residue` must be a single ASCII character");
-    if (n_genes > INT32_MAX) return bad("more than 2^31 - 1 gene records");
+    if (o->unknown_residue <= 0 || o->unknown_residue > 127) return d.bad("`unknown_residue` must be a single ASCII character");
+    if (n_genes > INT32_MAX) return d.bad("more than 2^31 - 1 gene records");
     if (capacity < 0 || ((d_representative || d_size) && capacity < n_genes))
-        return bad("capacity = " + std::to_string(capacity) + " is less than the " + std::to_string(n_genes) + " gene records");
+        return d.bad("capacity = " + std::to_string(capacity) + " is less than the " + std::to_string(n_genes) + " gene records");
     if (protein && n_genes > 0) {
-        if (!table_of_contig) return bad("table_of_contig is NULL");
-        for (int i = 0; i < bv.n; i++)
-            if (!table_known(table_of_contig[i])) return bad("contig " + std::to_string(i) + ": " + std::to_string(table_of_contig[i]) + " is not a valid translation table index");
+        if (!table_of_contig) return d.bad("table_of_contig is NULL");
+        if (const int rc = d.tables_known(bv, table_of_contig)) return rc;
     }
-    for (int64_t g = 0; g < n_genes; g++)
-        if (!gene_inside(bv, genes[g])) return bad("gene " + std::to_string(g) + " lies outside its contig");
+    for (int64_t g = 0; g < n_genes; g++) if (const int rc = d.record_inside(bv, genes[g], g)) return rc;
     int key_bits = 61;
     if (const char* e = getenv("PGA_PROTEIN_GROUPS_KEY_BITS")) {
         char* end = nullptr;
         const long k = strtol(e, &end, 10);
-        if (end == e || *end || k < 1 || k > 61) return bad(std::string("PGA_PROTEIN_GROUPS_KEY_BITS must be 1 .. 61, not \"") + e + "\"");
+        if (end == e || *end || k < 1 || k > 61) return d.bad(std::string("PGA_PROTEIN_GROUPS_KEY_BITS must be 1 .. 61, not \"") + e + "\"");
         key_bits = (int)k;
     }
     c->group_stats[0] = c->group_stats[1] = 0;
     if (n_genes == 0) { *n_groups = 0; return PGA_OK; }
-    const struct { const char* name; const void* p; } outs[4] = {{"d_group", d_group}, {"d_representative", d_representative}, {"d_size", d_size}, {"d_digest", d_digest}};
-    if (!d_group) return bad("d_group is NULL");
-    for (const auto& x : outs) if ((uintptr_t)x.p % 8u) return bad(std::string(x.name) + " is not aligned to its 8-byte elements");
-    if (hipSetDevice(c->device) != hipSuccess) return PGA_EDEVICE;
-    for (const auto& x : outs) if (x.p) if (const int rc = pga_device_memory_(c, x.p, fn, x.name)) return rc;
+    if (const int rc = d.destinations({{"d_group", d_group, 8, d.kRequired}, {"d_representative", d_representative, 8, d.kOptional},
+                                       {"d_size", d_size, 8, d.kOptional}, {"d_digest", d_digest, 8, d.kOptional}})) return rc;
     if (protein) { const int rc = tables_ready(c); if (rc) return rc; }
     // ---- the lease: the records as the kernels read them, staged in the pinned area, and behind them the work arrays of the call ----
     const size_t G = (size_t)n_genes;
@@ -506,93 +483,74 @@ extern "C" int pga_group_proteins(pga_ctx* c, const pga_batch* batch, int64_t n_
     hipcub::DeviceScan::InclusiveScan(nullptr, max_b, (uint32_t*)nullptr, (uint32_t*)nullptr, GrpMax{}, iG, (hipStream_t)nullptr);
     hipcub::DeviceScan::ExclusiveSum(nullptr, sum_b, (int32_t*)nullptr, (int32_t*)nullptr, iG, (hipStream_t)nullptr);
     const size_t tmp_b = std::max(sort_b, std::max(max_b, sum_b));
-    auto al = [](const size_t x) { return (x + 255) & ~(size_t)255; };
+    Staging tab(256);
     const size_t row_b = sizeof(GrpRow) * G;
-    const size_t p_small = al(row_b), p_w0 = p_small + 256, p_w1 = p_w0 + al(8 * G), p_skey = p_w1 + al(8 * G), p_idx = p_skey + al(8 * G), p_sidx = p_idx + al(4 * G);
-    const size_t p_start = p_sidx + al(4 * G), p_runstart = p_start + al(4 * G), p_cand0 = p_runstart + al(4 * G), p_cand1 = p_cand0 + al(4 * G);
-    const size_t p_head = p_cand1 + al(4 * G), p_tmp = p_head + al(4 * G), p_end = p_tmp + al(tmp_b + 1);
-    pga_upload_lease L{};
-    { const int rc = pga_upload_lease_take(c, p_end, &L); if (rc) return rc; }
-    GrpRow* const rows = (GrpRow*)L.pin;
-    for (size_t g = 0; g < G; g++) {
-        const pga_gene& R = genes[g];
-        const bool fwd = R.strand == 1;
-        GrpRow& w = rows[g];
-        w.base = bv.ct[R.contig].base; w.L = bv.ct[R.contig].len;
-        w.q0 = fwd ? R.begin - 1 : R.end - 1;
-        w.n = protein ? (int32_t)gene_residues(R, o->include_stop) : R.end - R.begin + 1;
-        // partial flags are in sequence orientation; the gene's own first codon follows its strand
-        const bool start_edge = fwd ? R.partial_begin != 0 : R.partial_end != 0;
-        w.bits = (fwd ? 1u : 0u) | (start_edge ? 2u : 0u) | (protein ? (uint32_t)table_of_contig[R.contig] << 8 : 0u);
-    }
-    volatile long long* const h_small = (volatile long long*)(L.pin + p_small);    // [0]: what a round left, [1]: U
+    const size_t p_row = tab.take(row_b), p_small = tab.take(256), p_w0 = tab.take(8 * G), p_w1 = tab.take(8 * G), p_skey = tab.take(8 * G), p_idx = tab.take(4 * G), p_sidx = tab.take(4 * G);
+    const size_t p_start = tab.take(4 * G), p_runstart = tab.take(4 * G), p_cand0 = tab.take(4 * G), p_cand1 = tab.take(4 * G), p_head = tab.take(4 * G), p_tmp = tab.take(tmp_b + 1);
+    if (const int rc = tab.lease(c)) return rc;
+    grp_rows(tab.pin<GrpRow>(p_row), genes, n_genes, bv, protein, o->include_stop, table_of_contig);
+    volatile long long* const h_small = tab.pin<volatile long long>(p_small);        // [0]: what a round left, [1]: U
     GrpArgs a{};
-    a.seq = bv.d_seq; a.row = (const GrpRow*)L.dev; a.n = n_genes;
+    a.seq = bv.d_seq; a.row = tab.dev<const GrpRow>(p_row); a.n = n_genes;
     a.unk = o->unknown_residue; a.strict = o->strict; a.precheck = key_bits == 61;
     a.key_mask = (1ull << key_bits) - 1;
-    a.w0 = (uint64_t*)(L.dev + p_w0); a.w1 = (uint64_t*)(L.dev + p_w1); a.idx = (uint32_t*)(L.dev + p_idx);
-    a.skey = (const uint64_t*)(L.dev + p_skey); a.sidx = (const uint32_t*)(L.dev + p_sidx);
-    a.start = (uint32_t*)(L.dev + p_start); a.runstart = (uint32_t*)(L.dev + p_runstart);
-    a.head = (int32_t*)(L.dev + p_head);
-    a.unresolved = (unsigned long long*)(L.dev + p_small);
+    a.w0 = tab.dev<uint64_t>(p_w0); a.w1 = tab.dev<uint64_t>(p_w1); a.idx = tab.dev<uint32_t>(p_idx);
+    a.skey = tab.dev<const uint64_t>(p_skey); a.sidx = tab.dev<const uint32_t>(p_sidx);
+    a.start = tab.dev<uint32_t>(p_start); a.runstart = tab.dev<uint32_t>(p_runstart);
+    a.head = tab.dev<int32_t>(p_head);
+    a.unresolved = tab.dev<unsigned long long>(p_small);
     a.d_digest = d_digest;
-    uint32_t* const cand[2] = {(uint32_t*)(L.dev + p_cand0), (uint32_t*)(L.dev + p_cand1)};
-    void* const d_tmp = L.dev + p_tmp;
+    uint32_t* const cand[2] = {tab.dev<uint32_t>(p_cand0), tab.dev<uint32_t>(p_cand1)};
+    void* const d_tmp = tab.dev<char>(p_tmp);
     size_t tb = tmp_b;
-    hipStream_t st = L.st;
     const dim3 block(kRowThreads), per_gene((unsigned)((n_genes + kRowThreads - 1) / kRowThreads));
     auto launched = [&]() { return hipGetLastError(); };
-    // behind what the caller's stream holds; complete on return
-    hipError_t e = hipEventRecord(L.ev, (hipStream_t)stream);
-    if (e == hipSuccess) e = hipStreamWaitEvent(st, L.ev, 0);
-    if (e == hipSuccess) e = hipMemcpyAsync(L.dev, L.pin, row_b, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipMemsetAsync(a.head, 0xff, 4 * G, st);
-    if (e == hipSuccess) {
-        // a wave per four records, and several rounds of them per wave where there are many
-        const int64_t quads = (n_genes + 3) / 4, per_block = kRowThreads / 64;
-        const dim3 grid((unsigned)std::min<int64_t>((quads + per_block - 1) / per_block, 8192));
-        if (protein) hipLaunchKernelGGL((k_string_digest<kGrpProtein>), grid, block, 0, st, a);
-        else hipLaunchKernelGGL((k_string_digest<kGrpGene>), grid, block, 0, st, a);
-        e = launched();
-    }
-    if (e == hipSuccess) e = hipcub::DeviceRadixSort::SortPairs(d_tmp, tb, (const uint64_t*)a.w0, (uint64_t*)a.skey, (const uint32_t*)a.idx, (uint32_t*)a.sidx, iG, 0, key_bits, st);
-    a.cand = cand[0];
-    if (e == hipSuccess) { hipLaunchKernelGGL(k_group_runs, per_gene, block, 0, st, a); e = launched(); }
-    tb = tmp_b;
-    if (e == hipSuccess) e = hipcub::DeviceScan::InclusiveScan(d_tmp, tb, (const uint32_t*)a.start, a.runstart, GrpMax{}, iG, st);
     int64_t rounds = 0, differing = 0;
-    while (e == hipSuccess) {
-        a.cand = cand[rounds & 1]; a.cand_next = cand[(rounds + 1) & 1];
-        e = hipMemsetAsync(a.cand_next, 0xff, 4 * G, st);
-        if (e == hipSuccess) e = hipMemsetAsync(a.unresolved, 0, 8, st);
+    // the records go up; the rounds wait for the stream themselves
+    return d.run(tab.L, row_b, stream, [&](hipStream_t st) {
+        hipError_t e = hipMemsetAsync(a.head, 0xff, 4 * G, st);
         if (e == hipSuccess) {
-            if (protein) hipLaunchKernelGGL((k_group_verify<kGrpProtein>), per_gene, block, 0, st, a);
-            else hipLaunchKernelGGL((k_group_verify<kGrpGene>), per_gene, block, 0, st, a);
+            // a wave per four records, and several rounds of them per wave where there are many
+            const int64_t quads = (n_genes + 3) / 4, per_block = kRowThreads / 64;
+            const dim3 grid((unsigned)std::min<int64_t>((quads + per_block - 1) / per_block, 8192));
+            if (protein) hipLaunchKernelGGL((k_string_digest<kGrpProtein>), grid, block, 0, st, a);
+            else hipLaunchKernelGGL((k_string_digest<kGrpGene>), grid, block, 0, st, a);
             e = launched();
         }
-        if (e == hipSuccess) e = hipMemcpyAsync((void*)h_small, a.unresolved, 8, hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess) e = hipStreamSynchronize(st);
-        if (e != hipSuccess) break;
-        rounds++;
-        const int64_t left = h_small[0];
-        differing += left;
-        if (left == 0) break;                                  // (a round resolves the head of every run that has members left: it ends)
-    }
-    // ---- numbering: representatives flagged, an exclusive scan, and the outputs (flags, numbers and counts over the rounds' arrays) ----
-    GrpOut w{};
-    w.head = a.head; w.flag = (int32_t*)a.start; w.num = (const int32_t*)a.runstart; w.cnt = (int32_t*)cand[0]; w.n = n_genes;
-    w.d_group = d_group; w.d_rep = d_representative; w.d_size = d_size; w.n_groups = (long long*)(L.dev + p_small) + 1;
-    if (e == hipSuccess) { hipLaunchKernelGGL(k_group_flags, per_gene, block, 0, st, w); e = launched(); }
-    tb = tmp_b;
-    if (e == hipSuccess) e = hipcub::DeviceScan::ExclusiveSum(d_tmp, tb, (const int32_t*)w.flag, (int32_t*)a.runstart, iG, st);
-    if (e == hipSuccess) { hipLaunchKernelGGL(k_group_count, per_gene, block, 0, st, w); e = launched(); }
-    if (e == hipSuccess && (d_representative || d_size)) { hipLaunchKernelGGL(k_group_emit, per_gene, block, 0, st, w); e = launched(); }
-    if (e == hipSuccess) e = hipMemcpyAsync((void*)(h_small + 1), w.n_groups, 8, hipMemcpyDeviceToHost, st);
-    const hipError_t es = hipStreamSynchronize(st);            // (also after a failure: nothing of the lease is in use when it goes back)
-    if (e == hipSuccess) e = es;
-    if (e == hipSuccess) { *n_groups = h_small[1]; c->group_stats[0] = rounds; c->group_stats[1] = differing; }
-    pga_upload_lease_give(c);
-    return pga_hip_try_(c, e, fn);
+        if (e == hipSuccess) e = hipcub::DeviceRadixSort::SortPairs(d_tmp, tb, (const uint64_t*)a.w0, (uint64_t*)a.skey, (const uint32_t*)a.idx, (uint32_t*)a.sidx, iG, 0, key_bits, st);
+        a.cand = cand[0];
+        if (e == hipSuccess) { hipLaunchKernelGGL(k_group_runs, per_gene, block, 0, st, a); e = launched(); }
+        tb = tmp_b;
+        if (e == hipSuccess) e = hipcub::DeviceScan::InclusiveScan(d_tmp, tb, (const uint32_t*)a.start, a.runstart, GrpMax{}, iG, st);
+        while (e == hipSuccess) {
+            a.cand = cand[rounds & 1]; a.cand_next = cand[(rounds + 1) & 1];
+            e = hipMemsetAsync(a.cand_next, 0xff, 4 * G, st);
+            if (e == hipSuccess) e = hipMemsetAsync(a.unresolved, 0, 8, st);
+            if (e == hipSuccess) {
+                if (protein) hipLaunchKernelGGL((k_group_verify<kGrpProtein>), per_gene, block, 0, st, a);
+                else hipLaunchKernelGGL((k_group_verify<kGrpGene>), per_gene, block, 0, st, a);
+                e = launched();
+            }
+            if (e == hipSuccess) e = hipMemcpyAsync((void*)h_small, a.unresolved, 8, hipMemcpyDeviceToHost, st);
+            if (e == hipSuccess) e = hipStreamSynchronize(st);
+            if (e != hipSuccess) break;
+            rounds++;
+            const int64_t left = h_small[0];
+            differing += left;
+            if (left == 0) break;                                  // (a round resolves the head of every run that has members left: it ends)
+        }
+        // ---- numbering: representatives flagged, an exclusive scan, and the outputs (flags, numbers and counts over the rounds' arrays) ----
+        GrpOut w{};
+        w.head = a.head; w.flag = (int32_t*)a.start; w.num = (const int32_t*)a.runstart; w.cnt = (int32_t*)cand[0]; w.n = n_genes;
+        w.d_group = d_group; w.d_rep = d_representative; w.d_size = d_size; w.n_groups = tab.dev<long long>(p_small) + 1;
+        if (e == hipSuccess) { hipLaunchKernelGGL(k_group_flags, per_gene, block, 0, st, w); e = launched(); }
+        tb = tmp_b;
+        if (e == hipSuccess) e = hipcub::DeviceScan::ExclusiveSum(d_tmp, tb, (const int32_t*)w.flag, (int32_t*)a.runstart, iG, st);
+        if (e == hipSuccess) { hipLaunchKernelGGL(k_group_count, per_gene, block, 0, st, w); e = launched(); }
+        if (e == hipSuccess && (d_representative || d_size)) { hipLaunchKernelGGL(k_group_emit, per_gene, block, 0, st, w); e = launched(); }
+        if (e == hipSuccess) e = hipMemcpyAsync((void*)(h_small + 1), w.n_groups, 8, hipMemcpyDeviceToHost, st);
+        return e;
+    }, [&] { *n_groups = h_small[1]; c->group_stats[0] = rounds; c->group_stats[1] = differing; });
 }
 
 // ---- MinHash sketches (protein_sketches.inl) -----------------------------------------------------------------------------------
@@ -605,121 +563,83 @@ extern "C" int pga_sketch_passes(pga_ctx* c, int64_t* out) {
 extern "C" int pga_sketch_proteins(pga_ctx* c, const pga_batch* batch, int64_t n_genes, const pga_gene* genes, const int32_t* table_of_contig,
                                    const pga_sketch_opts* o, int64_t* d_sketch, int64_t* d_count, int64_t* d_windows, void* stream) {
     if (!c) return PGA_EINVAL;
-    const char* const fn = "pga_sketch_proteins";
-    auto bad = [&](const std::string& msg) { c->err = std::string(fn) + ": " + msg; return PGA_EINVAL; };
-    if (!batch || !o || n_genes < 0 || (n_genes > 0 && !genes)) return bad("bad arguments");
+    DevCall d{c, "pga_sketch_proteins"};
+    if (!batch || !o || n_genes < 0 || (n_genes > 0 && !genes)) return d.bad("bad arguments");
     const pga_batch_view bv = pga_batch_peek(batch);
-    if (bv.ctx != c) return bad("the batch belongs to another context");
+    if (bv.ctx != c) return d.bad("the batch belongs to another context");
     // ---- validation: all of it on the host, before anything is allocated or launched ----
-    if (o->unit != PGA_SKETCH_PROTEIN && o->unit != PGA_SKETCH_GENE) return bad("unit must be PGA_SKETCH_PROTEIN or PGA_SKETCH_GENE, not " + std::to_string(o->unit));
+    if (o->unit != PGA_SKETCH_PROTEIN && o->unit != PGA_SKETCH_GENE) return d.bad("unit must be PGA_SKETCH_PROTEIN or PGA_SKETCH_GENE, not " + std::to_string(o->unit));
     const bool protein = o->unit == PGA_SKETCH_PROTEIN;
     const int kmax = protein ? 8 : 32;
-    if (o->k < 1 || o->k > kmax) return bad("k = " + std::to_string(o->k) + " is outside 1 .. " + std::to_string(kmax) + " for this unit");
-    if (o->size < 1 || o->size > 64) return bad("size = " + std::to_string(o->size) + " is outside 1 .. 64");
-    if (o->unknown_residue <= 0 || o->unknown_residue > 127) return bad("`unknown_residue` must be a single ASCII character");
-    if (n_genes > INT32_MAX) return bad("more than 2^31 - 1 gene records");
+    if (o->k < 1 || o->k > kmax) return d.bad("k = " + std::to_string(o->k) + " is outside 1 .. " + std::to_string(kmax) + " for this unit");
+    if (o->size < 1 || o->size > 64) return d.bad("size = " + std::to_string(o->size) + " is outside 1 .. 64");
+    if (o->unknown_residue <= 0 || o->unknown_residue > 127) return d.bad("`unknown_residue` must be a single ASCII character");
+    if (n_genes > INT32_MAX) return d.bad("more than 2^31 - 1 gene records");
     if (protein && n_genes > 0) {
-        if (!table_of_contig) return bad("table_of_contig is NULL");
-        for (int i = 0; i < bv.n; i++)
-            if (!table_known(table_of_contig[i])) return bad("contig " + std::to_string(i) + ": " + std::to_string(table_of_contig[i]) + " is not a valid translation table index");
+        if (!table_of_contig) return d.bad("table_of_contig is NULL");
+        if (const int rc = d.tables_known(bv, table_of_contig)) return rc;
     }
-    for (int64_t g = 0; g < n_genes; g++)
-        if (!gene_inside(bv, genes[g])) return bad("gene " + std::to_string(g) + " lies outside its contig");
+    for (int64_t g = 0; g < n_genes; g++) if (const int rc = d.record_inside(bv, genes[g], g)) return rc;
     c->sketch_passes = -1;
     if (n_genes == 0) return PGA_OK;
-    const struct { const char* name; const void* p; } outs[3] = {{"d_sketch", d_sketch}, {"d_count", d_count}, {"d_windows", d_windows}};
-    if (!d_sketch) return bad("d_sketch is NULL");
-    if (!d_count) return bad("d_count is NULL");
-    for (const auto& x : outs) if ((uintptr_t)x.p % 8u) return bad(std::string(x.name) + " is not aligned to its 8-byte elements");
-    if (hipSetDevice(c->device) != hipSuccess) return PGA_EDEVICE;
-    for (const auto& x : outs) if (x.p) if (const int rc = pga_device_memory_(c, x.p, fn, x.name)) return rc;
+    if (const int rc = d.destinations({{"d_sketch", d_sketch, 8, d.kRequired}, {"d_count", d_count, 8, d.kRequired}, {"d_windows", d_windows, 8, d.kOptional}})) return rc;
     if (protein) { const int rc = tables_ready(c); if (rc) return rc; }
     // ---- the lease: the records as the kernel reads them, and behind them the class table and a counter ----
-    const size_t G = (size_t)n_genes;
-    const size_t row_b = sizeof(GrpRow) * G, p_cls = (row_b + 255) & ~(size_t)255, p_small = p_cls + 256, p_end = p_small + 256;
-    pga_upload_lease L{};
-    { const int rc = pga_upload_lease_take(c, p_end, &L); if (rc) return rc; }
-    GrpRow* const rows = (GrpRow*)L.pin;
-    for (size_t g = 0; g < G; g++) {
-        const pga_gene& R = genes[g];
-        const bool fwd = R.strand == 1;
-        GrpRow& w = rows[g];
-        w.base = bv.ct[R.contig].base; w.L = bv.ct[R.contig].len;
-        w.q0 = fwd ? R.begin - 1 : R.end - 1;
-        w.n = protein ? (int32_t)gene_residues(R, o->include_stop) : R.end - R.begin + 1;
-        // partial flags are in sequence orientation; the gene's own first codon follows its strand
-        const bool start_edge = fwd ? R.partial_begin != 0 : R.partial_end != 0;
-        w.bits = (fwd ? 1u : 0u) | (start_edge ? 2u : 0u) | (protein ? (uint32_t)table_of_contig[R.contig] << 8 : 0u);
-    }
-    memcpy(L.pin + p_cls, o->classes, 128);
-    memset(L.pin + p_cls + 128, 0, p_small + 256 - (p_cls + 128));
+    Staging tab(256);
+    const size_t p_row = tab.take(sizeof(GrpRow) * (size_t)n_genes), p_cls = tab.put(o->classes, 128), p_small = tab.take(256);
+    if (const int rc = tab.lease(c)) return rc;
+    grp_rows(tab.pin<GrpRow>(p_row), genes, n_genes, bv, protein, o->include_stop, table_of_contig);
+    memset(tab.pin<char>(p_cls) + 128, 0, p_small + 256 - (p_cls + 128));       // (the rest of the table's slice, and the counter)
     SkArgs a{};
-    a.g.seq = bv.d_seq; a.g.row = (const GrpRow*)L.dev; a.g.n = n_genes; a.g.unk = o->unknown_residue; a.g.strict = o->strict;
-    a.classes = (const uint8_t*)(L.dev + p_cls);
+    a.g.seq = bv.d_seq; a.g.row = tab.dev<const GrpRow>(p_row); a.g.n = n_genes; a.g.unk = o->unknown_residue; a.g.strict = o->strict;
+    a.classes = tab.dev<const uint8_t>(p_cls);
     a.k = o->k; a.s = o->size; a.bits = protein ? 8 : 2;
     a.salt = ((uint64_t)o->seed + 1ull) * 0x9E3779B97F4A7C15ull;
     a.d_sketch = d_sketch; a.d_count = d_count; a.d_windows = d_windows;
 #ifdef PGA_SKETCH_COUNT_PASSES
-    a.passed = (unsigned long long*)(L.dev + p_small);
+    a.passed = tab.dev<unsigned long long>(p_small);
 #endif
-    hipStream_t st = L.st;
-    // behind what the caller's stream holds; complete on return
-    hipError_t e = hipEventRecord(L.ev, (hipStream_t)stream);
-    if (e == hipSuccess) e = hipStreamWaitEvent(st, L.ev, 0);
-    if (e == hipSuccess) e = hipMemcpyAsync(L.dev, L.pin, p_end, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) {
+    return d.run(tab.L, tab.bytes(), stream, [&](hipStream_t st) {
         // a wave per record, and several rounds of them per wave where there are many
         const int64_t per_block = kRowThreads / 64;
         const dim3 grid((unsigned)std::min<int64_t>((n_genes + per_block - 1) / per_block, 16384)), block(kRowThreads);
         if (protein) hipLaunchKernelGGL((k_sketch<kGrpProtein>), grid, block, 0, st, a);
         else hipLaunchKernelGGL((k_sketch<kGrpGene>), grid, block, 0, st, a);
-        e = hipGetLastError();
-    }
+        hipError_t e = hipGetLastError();
 #ifdef PGA_SKETCH_COUNT_PASSES
-    if (e == hipSuccess) e = hipMemcpyAsync(L.pin + p_small, L.dev + p_small, 8, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipMemcpyAsync(tab.pin<char>(p_small), tab.dev<char>(p_small), 8, hipMemcpyDeviceToHost, st);
 #endif
-    const hipError_t es = hipStreamSynchronize(st);            // (also after a failure: nothing of the lease is in use when it goes back)
-    if (e == hipSuccess) e = es;
+        return e;
+    }, [&] {
 #ifdef PGA_SKETCH_COUNT_PASSES
-    if (e == hipSuccess) c->sketch_passes = *(volatile long long*)(L.pin + p_small);
+        c->sketch_passes = *tab.pin<volatile long long>(p_small);
 #endif
-    pga_upload_lease_give(c);
-    return pga_hip_try_(c, e, fn);
+    });
 }
 
 extern "C" int pga_sketch_pairs(pga_ctx* c, const int64_t* d_sketch, const int64_t* d_count, int64_t n_genes, int32_t size,
                                 const int64_t* d_pairs, int64_t n_pairs, int64_t* d_shared, int64_t* d_union, void* stream) {
     if (!c) return PGA_EINVAL;
-    const char* const fn = "pga_sketch_pairs";
-    auto bad = [&](const std::string& msg) { c->err = std::string(fn) + ": " + msg; return PGA_EINVAL; };
+    DevCall d{c, "pga_sketch_pairs"};
     // ---- validation: all of it on the host, before anything is launched ----
-    if (n_genes < 0 || n_pairs < 0) return bad("bad arguments");
-    if (size < 1 || size > 64) return bad("size = " + std::to_string(size) + " is outside 1 .. 64");
-    if (n_genes > INT32_MAX) return bad("more than 2^31 - 1 gene records");
+    if (n_genes < 0 || n_pairs < 0) return d.bad("bad arguments");
+    if (size < 1 || size > 64) return d.bad("size = " + std::to_string(size) + " is outside 1 .. 64");
+    if (n_genes > INT32_MAX) return d.bad("more than 2^31 - 1 gene records");
     if (n_pairs == 0) return PGA_OK;
-    const struct { const char* name; const void* p; bool needed; } ptrs[5] = {{"d_sketch", d_sketch, n_genes > 0}, {"d_count", d_count, n_genes > 0},
-        {"d_pairs", d_pairs, true}, {"d_shared", d_shared, true}, {"d_union", d_union, true}};
-    for (const auto& x : ptrs) if (x.needed && !x.p) return bad(std::string(x.name) + " is NULL");
-    for (const auto& x : ptrs) if ((uintptr_t)x.p % 8u) return bad(std::string(x.name) + " is not aligned to its 8-byte elements");
-    if (hipSetDevice(c->device) != hipSuccess) return PGA_EDEVICE;
-    for (const auto& x : ptrs) if (x.p && x.needed) if (const int rc = pga_device_memory_(c, x.p, fn, x.name)) return rc;
+    const int rows_read = n_genes > 0 ? d.kRequired : d.kUnread;
+    if (const int rc = d.destinations({{"d_sketch", d_sketch, 8, rows_read}, {"d_count", d_count, 8, rows_read}, {"d_pairs", d_pairs, 8, d.kRequired},
+                                       {"d_shared", d_shared, 8, d.kRequired}, {"d_union", d_union, 8, d.kRequired}})) return rc;
     SkPairArgs a{};
     a.sketch = d_sketch; a.count = d_count; a.pairs = d_pairs; a.n_genes = n_genes; a.n_pairs = n_pairs; a.s = size;
     a.d_shared = d_shared; a.d_union = d_union;
-    pga_upload_lease L{};
-    { const int rc = pga_upload_lease_take(c, 0, &L); if (rc) return rc; }
-    hipError_t e = hipEventRecord(L.ev, (hipStream_t)stream);
-    if (e == hipSuccess) e = hipStreamWaitEvent(L.st, L.ev, 0);
-    if (e == hipSuccess) {
+    Staging tab;                                                 // (no tables to send)
+    if (const int rc = tab.lease(c)) return rc;
+    return d.run(tab.L, 0, stream, [&](hipStream_t st) {
         const int64_t per_block = kRowThreads / 64;
         const dim3 grid((unsigned)std::min<int64_t>((n_pairs + per_block - 1) / per_block, 16384)), block(kRowThreads);
-        hipLaunchKernelGGL(k_sketch_pairs, grid, block, 0, L.st, a);
-        e = hipGetLastError();
-    }
-    const hipError_t es = hipStreamSynchronize(L.st);
-    if (e == hipSuccess) e = es;
-    pga_upload_lease_give(c);
-    return pga_hip_try_(c, e, fn);
+        hipLaunchKernelGGL(k_sketch_pairs, grid, block, 0, st, a);
+        return hipGetLastError();
+    });
 }
 
 // ---- start candidates (start_candidates.inl) ----------------------------------------------------------------------------------
@@ -774,24 +694,24 @@ extern "C" int pga_start_plan_create(pga_ctx* c, const pga_batch* batch, int64_t
                                      int32_t* count_out, int32_t* chosen_out) {
     if (plan) *plan = nullptr;
     if (!c) return PGA_EINVAL;
-    auto bad = [&](const std::string& msg) { c->err = "pga_start_plan_create: " + msg; return PGA_EINVAL; };
-    if (!batch || !plan || n_genes < 0 || (n_genes > 0 && (!genes || !count_out || !chosen_out))) return bad("bad arguments");
+    DevCall d{c, "pga_start_plan_create"};
+    if (!batch || !plan || n_genes < 0 || (n_genes > 0 && (!genes || !count_out || !chosen_out))) return d.bad("bad arguments");
     const pga_batch_view bv = pga_batch_peek(batch);
-    if (bv.ctx != c) return bad("the batch belongs to another context");
+    if (bv.ctx != c) return d.bad("the batch belongs to another context");
     // ---- validation on the host, before anything is allocated or launched ----
-    if (bv.circular) return bad("the start-score file is not written for circular contigs (the batch carries pga_batch_set_circular flags)");
-    if (const char* why = pga_dev_nodes_refusal(c, batch, bv.n, bv.ct, nullptr)) return bad(why);
+    if (bv.circular) return d.bad("the start-score file is not written for circular contigs (the batch carries pga_batch_set_circular flags)");
+    if (const char* why = pga_dev_nodes_refusal(c, batch, bv.n, bv.ct, nullptr)) return d.bad(why);
     const DevNodes& DN = c->dev_nodes;
     const int NC = bv.n;
     std::vector<StartReq> req((size_t)n_genes);
     for (int64_t g = 0; g < n_genes; g++) {
         const pga_gene& G = genes[g];
-        const std::string who = "gene " + std::to_string(g);
-        if (G.contig < 0 || G.contig >= NC) return bad(who + " names contig " + std::to_string(G.contig) + " of " + std::to_string(NC));
+        auto who = [g] { return "gene " + std::to_string(g); };      // (only a refusal needs the words)
+        if (const int rc = d.contig_known(bv, G, g)) return rc;
         const int32_t n = DN.n[G.contig];
-        if (G.start_ndx < 0 || G.start_ndx >= n) return bad(who + ": start_ndx = " + std::to_string(G.start_ndx) + " lies outside the " + std::to_string(n) + " nodes of contig " + std::to_string(G.contig));
-        if (G.stop_ndx < 0 || G.stop_ndx >= n) return bad(who + ": stop_ndx = " + std::to_string(G.stop_ndx) + " lies outside the " + std::to_string(n) + " nodes of contig " + std::to_string(G.contig));
-        if (G.strand != 1 && G.strand != -1) return bad(who + ": strand = " + std::to_string((int)G.strand) + " is neither 1 nor -1");
+        if (G.start_ndx < 0 || G.start_ndx >= n) return d.bad(who() + ": start_ndx = " + std::to_string(G.start_ndx) + " lies outside the " + std::to_string(n) + " nodes of contig " + std::to_string(G.contig));
+        if (G.stop_ndx < 0 || G.stop_ndx >= n) return d.bad(who() + ": stop_ndx = " + std::to_string(G.stop_ndx) + " lies outside the " + std::to_string(n) + " nodes of contig " + std::to_string(G.contig));
+        if (G.strand != 1 && G.strand != -1) return d.bad(who() + ": strand = " + std::to_string((int)G.strand) + " is neither 1 nor -1");
         req[(size_t)g] = StartReq{G.contig, (int32_t)(DN.off[G.contig] + G.start_ndx), G.strand == 1 ? G.begin : G.end, G.strand};
     }
     pga_start_plan* P = new (std::nothrow) pga_start_plan();
@@ -819,7 +739,7 @@ extern "C" int pga_start_plan_create(pga_ctx* c, const pga_batch* batch, int64_t
     auto fail = [&](const hipError_t err) {
         hipStreamSynchronize(st);
         pga_start_plan_free(c, P);
-        return pga_hip_try_(c, err, "pga_start_plan_create");
+        return pga_hip_try_(c, err, d.fn);
     };
     if (e != hipSuccess) return fail(e);
     std::vector<int64_t> naoff((size_t)NC + 1, 0), ncum((size_t)NC + 1, 0);
@@ -844,15 +764,15 @@ extern "C" int pga_start_plan_create(pga_ctx* c, const pga_batch* batch, int64_t
     std::vector<int64_t>& off = P->h_off;
     for (size_t g = 0; g < G; g++) {
         const pga_gene& R = genes[g];
-        const std::string who = "gene " + std::to_string(g);
+        auto who = [g] { return "gene " + std::to_string(g); };
         if (res[g].x <= 0) {
             pga_start_plan_free(c, P);
             switch (-res[g].x) {
-                case kStartIsStop:   return bad(who + ": start_ndx = " + std::to_string(R.start_ndx) + " is a stop node of contig " + std::to_string(R.contig));
-                case kStartStrand:   return bad(who + ": strand = " + std::to_string((int)R.strand) + " is not the strand of node start_ndx = " + std::to_string(R.start_ndx));
-                case kStartPosition: return bad(who + ": " + (R.strand == 1 ? "begin = " + std::to_string(R.begin) : "end = " + std::to_string(R.end)) +
+                case kStartIsStop:   return d.bad(who() + ": start_ndx = " + std::to_string(R.start_ndx) + " is a stop node of contig " + std::to_string(R.contig));
+                case kStartStrand:   return d.bad(who() + ": strand = " + std::to_string((int)R.strand) + " is not the strand of node start_ndx = " + std::to_string(R.start_ndx));
+                case kStartPosition: return d.bad(who() + ": " + (R.strand == 1 ? "begin = " + std::to_string(R.begin) : "end = " + std::to_string(R.end)) +
                                                 " is not ndx + 1 of node start_ndx = " + std::to_string(R.start_ndx));
-                default:             return bad(who + ": node start_ndx = " + std::to_string(R.start_ndx) + " was not found in the sorted arena");
+                default:             return d.bad(who() + ": node start_ndx = " + std::to_string(R.start_ndx) + " was not found in the sorted arena");
             }
         }
         count_out[g] = res[g].x; chosen_out[g] = res[g].y;
@@ -871,48 +791,43 @@ extern "C" int pga_start_plan_create(pga_ctx* c, const pga_batch* batch, int64_t
 extern "C" int pga_start_plan_write(pga_ctx* c, const pga_start_plan* P, const pga_start_opts* o, void* d_positions, void* d_types, void* d_scores,
                                     int64_t n_positions, int64_t n_types, int64_t n_scores, void* stream) {
     if (!c) return PGA_EINVAL;
-    auto bad = [&](const std::string& msg) { c->err = "pga_start_plan_write: " + msg; return PGA_EINVAL; };
-    if (!P || !o || n_positions < 0 || n_types < 0 || n_scores < 0) return bad("bad arguments");
-    if (P->ctx != c) return bad("the plan belongs to another context");
+    DevCall d{c, "pga_start_plan_write"};
+    if (!P || !o || n_positions < 0 || n_types < 0 || n_scores < 0) return d.bad("bad arguments");
+    if (P->ctx != c) return d.bad("the plan belongs to another context");
     // ---- validation: all of it on the host, before anything is launched ----
-    if (o->index_bytes != 4 && o->index_bytes != 8) return bad("index_bytes must be 4 or 8, not " + std::to_string(o->index_bytes));
-    if (o->score_bytes != 4 && o->score_bytes != 8) return bad("score_bytes must be 4 or 8, not " + std::to_string(o->score_bytes));
-    if (o->layout != PGA_TOKENS_RAGGED && o->layout != PGA_TOKENS_PADDED) return bad("layout must be PGA_TOKENS_RAGGED or PGA_TOKENS_PADDED, not " + std::to_string(o->layout));
+    if (o->index_bytes != 4 && o->index_bytes != 8) return d.bad("index_bytes must be 4 or 8, not " + std::to_string(o->index_bytes));
+    if (o->score_bytes != 4 && o->score_bytes != 8) return d.bad("score_bytes must be 4 or 8, not " + std::to_string(o->score_bytes));
+    if (o->layout != PGA_TOKENS_RAGGED && o->layout != PGA_TOKENS_PADDED) return d.bad("layout must be PGA_TOKENS_RAGGED or PGA_TOKENS_PADDED, not " + std::to_string(o->layout));
     const bool padded = o->layout == PGA_TOKENS_PADDED;
-    if (o->n_fields < 1 || o->n_fields > 7) return bad("n_fields must be 1 .. 7, not " + std::to_string(o->n_fields));
+    if (o->n_fields < 1 || o->n_fields > 7) return d.bad("n_fields must be 1 .. 7, not " + std::to_string(o->n_fields));
     for (int k = 0; k < o->n_fields; k++) {
-        if (o->fields[k] < PGA_START_TOTAL || o->fields[k] > PGA_START_GC_CONT) return bad("fields[" + std::to_string(k) + "] = " + std::to_string(o->fields[k]) + " is no PGA_START_* field");
-        for (int j = 0; j < k; j++) if (o->fields[j] == o->fields[k]) return bad("fields[" + std::to_string(k) + "] repeats fields[" + std::to_string(j) + "]");
+        if (o->fields[k] < PGA_START_TOTAL || o->fields[k] > PGA_START_GC_CONT) return d.bad("fields[" + std::to_string(k) + "] = " + std::to_string(o->fields[k]) + " is no PGA_START_* field");
+        for (int j = 0; j < k; j++) if (o->fields[j] == o->fields[k]) return d.bad("fields[" + std::to_string(k) + "] repeats fields[" + std::to_string(j) + "]");
     }
     if (padded) {
-        if (o->index_bytes == 4 && (o->index_pad < INT32_MIN || o->index_pad > INT32_MAX)) return bad("index_pad = " + std::to_string(o->index_pad) + " does not fit int32");
-        if (o->score_bytes == 4 && std::isfinite(o->score_pad) && std::fabs(o->score_pad) > (double)FLT_MAX) return bad("score_pad = " + std::to_string(o->score_pad) + " does not fit float32");
+        if (o->index_bytes == 4 && (o->index_pad < INT32_MIN || o->index_pad > INT32_MAX)) return d.bad("index_pad = " + std::to_string(o->index_pad) + " does not fit int32");
+        if (o->score_bytes == 4 && std::isfinite(o->score_pad) && std::fabs(o->score_pad) > (double)FLT_MAX) return d.bad("score_pad = " + std::to_string(o->score_pad) + " does not fit float32");
     }
     const DevNodes& DN = c->dev_nodes;
     if (!DN.contigs || DN.serial != P->serial || DN.batch != P->batch)
-        return bad("the node arrays the plan was made on are no longer on record: a later call on the context ran the finder or loaded models");
+        return d.bad("the node arrays the plan was made on are no longer on record: a later call on the context ran the finder or loaded models");
     const int64_t G = P->n_genes, F = o->n_fields;
     int64_t W = 0, S = 0, n_layout = P->total, n_cells = P->total;
     if (padded) {
         W = o->row_width; S = o->row_stride;
-        if (W < P->longest) return bad("row_width = " + std::to_string(W) + " is less than the " + std::to_string(P->longest) + " candidates of gene " + std::to_string(P->longest_g));
-        if (W < 0 || S < W) return bad("row_stride = " + std::to_string(S) + " is less than row_width = " + std::to_string(W));
-        if (G > 1 && S > (INT64_MAX / 64 - W) / (G - 1)) return bad("row_stride = " + std::to_string(S) + " is too large");
-        if (G > 0 && W > 0 && W > (INT64_MAX / 64) / G) return bad("row_width = " + std::to_string(W) + " is too large");
+        if (W < P->longest) return d.bad("row_width = " + std::to_string(W) + " is less than the " + std::to_string(P->longest) + " candidates of gene " + std::to_string(P->longest_g));
+        if (W < 0 || S < W) return d.bad("row_stride = " + std::to_string(S) + " is less than row_width = " + std::to_string(W));
+        if (G > 1 && S > (INT64_MAX / 64 - W) / (G - 1)) return d.bad("row_stride = " + std::to_string(S) + " is too large");
+        if (G > 0 && W > 0 && W > (INT64_MAX / 64) / G) return d.bad("row_width = " + std::to_string(W) + " is too large");
         n_layout = G > 0 ? (G - 1) * S + W : 0;
         n_cells = G * W;
     }
-    if (n_positions < n_layout) return bad("n_positions = " + std::to_string(n_positions) + " is less than the " + std::to_string(n_layout) + " elements of the layout");
-    if (n_types < n_layout) return bad("n_types = " + std::to_string(n_types) + " is less than the " + std::to_string(n_layout) + " elements of the layout");
-    if (n_scores < n_layout * F) return bad("n_scores = " + std::to_string(n_scores) + " is less than the " + std::to_string(n_layout * F) + " elements of the layout");
+    if (n_positions < n_layout) return d.bad("n_positions = " + std::to_string(n_positions) + " is less than the " + std::to_string(n_layout) + " elements of the layout");
+    if (n_types < n_layout) return d.bad("n_types = " + std::to_string(n_types) + " is less than the " + std::to_string(n_layout) + " elements of the layout");
+    if (n_scores < n_layout * F) return d.bad("n_scores = " + std::to_string(n_scores) + " is less than the " + std::to_string(n_layout * F) + " elements of the layout");
     if (n_cells == 0) return PGA_OK;
-    const struct { const char* name; void* p; int eb; } outs[3] = {{"d_positions", d_positions, o->index_bytes}, {"d_types", d_types, o->index_bytes}, {"d_scores", d_scores, o->score_bytes}};
-    for (const auto& x : outs) {
-        if (!x.p) return bad(std::string(x.name) + " is NULL");
-        if ((uintptr_t)x.p % (uintptr_t)x.eb) return bad(std::string(x.name) + " is not aligned to its " + std::to_string(x.eb) + "-byte elements");
-    }
-    if (hipSetDevice(c->device) != hipSuccess) return PGA_EDEVICE;
-    for (const auto& x : outs) if (const int rc = pga_device_memory_(c, x.p, "pga_start_plan_write", x.name)) return rc;
+    if (const int rc = d.destinations({{"d_positions", d_positions, o->index_bytes, d.kRequired}, {"d_types", d_types, o->index_bytes, d.kRequired},
+                                       {"d_scores", d_scores, o->score_bytes, d.kRequired}}, true)) return rc;
     StartArgs a{};
     a.nd = DN.a; a.sval = P->sval; a.grp = P->grp; a.off = P->off;
     a.n_genes = G; a.n_cells = n_cells; a.W = W; a.S = S;
@@ -920,34 +835,28 @@ extern "C" int pga_start_plan_write(pga_ctx* c, const pga_start_plan* P, const p
     a.n_fields = o->n_fields;
     for (int k = 0; k < 7; k++) a.fields[k] = k < o->n_fields ? o->fields[k] : 0;
     a.pos = d_positions; a.typ = d_types; a.sco = d_scores;
-    // the tail of a row call (RowDest::run) without tables to send: behind what the caller's stream holds, complete on return
-    pga_upload_lease L{};
-    { const int rc = pga_upload_lease_take(c, 0, &L); if (rc) return rc; }
-    hipError_t e = hipEventRecord(L.ev, (hipStream_t)stream);
-    if (e == hipSuccess) e = hipStreamWaitEvent(L.st, L.ev, 0);
-    if (e == hipSuccess) {
+    Staging tab;                                                 // (no tables to send)
+    if (const int rc = tab.lease(c)) return rc;
+    return d.run(tab.L, 0, stream, [&](hipStream_t st) {
         const dim3 grid((unsigned)((n_cells + kRowThreads - 1) / kRowThreads)), block(kRowThreads);
         auto scores = [&](auto IB, auto PADDED) {
-            if (o->score_bytes == 4) hipLaunchKernelGGL((k_start_candidates<decltype(IB)::value, 4, decltype(PADDED)::value>), grid, block, 0, L.st, a);
-            else hipLaunchKernelGGL((k_start_candidates<decltype(IB)::value, 8, decltype(PADDED)::value>), grid, block, 0, L.st, a);
+            if (o->score_bytes == 4) hipLaunchKernelGGL((k_start_candidates<decltype(IB)::value, 4, decltype(PADDED)::value>), grid, block, 0, st, a);
+            else hipLaunchKernelGGL((k_start_candidates<decltype(IB)::value, 8, decltype(PADDED)::value>), grid, block, 0, st, a);
         };
         auto layout = [&](auto IB) { if (padded) scores(IB, std::true_type{}); else scores(IB, std::false_type{}); };
         if (o->index_bytes == 4) layout(std::integral_constant<int, 4>{}); else layout(std::integral_constant<int, 8>{});
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipStreamSynchronize(L.st);
-    pga_upload_lease_give(c);
-    return pga_hip_try_(c, e, "pga_start_plan_write");
+        return hipGetLastError();
+    });
 }
 
 extern "C" int pga_start_plan_nodes(pga_ctx* c, const pga_start_plan* P, int32_t* node_out, int64_t n_out) {
     if (!c) return PGA_EINVAL;
-    auto bad = [&](const std::string& msg) { c->err = "pga_start_plan_nodes: " + msg; return PGA_EINVAL; };
-    if (!P || n_out < 0) return bad("bad arguments");
-    if (P->ctx != c) return bad("the plan belongs to another context");
-    if (n_out < P->total) return bad("n_out = " + std::to_string(n_out) + " is less than the " + std::to_string(P->total) + " candidates of the plan");
+    DevCall d{c, "pga_start_plan_nodes"};
+    if (!P || n_out < 0) return d.bad("bad arguments");
+    if (P->ctx != c) return d.bad("the plan belongs to another context");
+    if (n_out < P->total) return d.bad("n_out = " + std::to_string(n_out) + " is less than the " + std::to_string(P->total) + " candidates of the plan");
     if (P->total == 0) return PGA_OK;
-    if (!node_out) return bad("node_out is NULL");
+    if (!node_out) return d.bad("node_out is NULL");
     if (hipSetDevice(c->device) != hipSuccess) return PGA_EDEVICE;
     char* s = nullptr;
     hipError_t e = pga_render_scratch(c, sizeof(uint32_t) * (size_t)P->total, &s);
@@ -958,7 +867,7 @@ extern "C" int pga_start_plan_nodes(pga_ctx* c, const pga_start_plan* P, int32_t
     }
     if (e == hipSuccess) e = hipMemcpyAsync(node_out, s, sizeof(uint32_t) * (size_t)P->total, hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (e != hipSuccess) return pga_hip_try_(c, e, "pga_start_plan_nodes");
+    if (e != hipSuccess) return pga_hip_try_(c, e, d.fn);
     for (int64_t g = 0; g < P->n_genes; g++)            // arena index -> index in the contig's node arrays
         for (int64_t k = P->h_off[(size_t)g]; k < P->h_off[(size_t)g + 1]; k++) node_out[k] = (int32_t)((int64_t)(uint32_t)node_out[k] - P->h_aoff[(size_t)g]);
     return PGA_OK;

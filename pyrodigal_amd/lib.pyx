@@ -2174,8 +2174,8 @@ cdef class GeneFinder:
 
     cdef tuple _find_tensor_batch(self, str method, object sequences, object spec, object out, object stream, bint translate,
                                   object training_infos, object regions, object circular, object sets, object trim_terminal_repeats):
-        """`find_proteins_batch` / `find_labels_batch` / `find_windows_batch` / `find_counts_batch` / `find_groups_batch` / `find_sketches_batch` / `find_starts_batch`: (the `Genes` of
-        `find_genes_batch`, what the rule `spec` wrote on the device)."""
+        """What the seven `find_*_batch` methods with a device-tensor output share (proteins, labels, windows, counts, groups,
+        sketches, starts): (the `Genes` of `find_genes_batch`, what the rule `spec` wrote on the device)."""
         cdef dict tok = {"spec": spec, "out": out, "stream": stream, "result": None, "method": method}
         cdef list circ, tr_search
         cdef object dev, set_ids, tr_params
@@ -2194,8 +2194,9 @@ cdef class GeneFinder:
         return genes, tok["result"]
 
     cdef tuple _batch_options(self, object sequences, object training_infos, object circular, object sets, object trim_terminal_repeats):
-        """The options of `find_genes_batch` / `find_proteins_batch` / `find_labels_batch`, checked against each other and against the number of sequences:
-        (the DeviceSequences or None, the sequences, circular flags, set ids, terminal-repeat search and its parameters)."""
+        """The options of `find_genes_batch` and of the seven `find_*_batch` methods with a device-tensor output, checked against each
+        other and against the number of sequences: (the DeviceSequences or None, the sequences, circular flags, set ids,
+        terminal-repeat search and its parameters)."""
         cdef list circ = None
         cdef object dev = None
         if isinstance(sequences, _DeviceSequences):
@@ -2676,9 +2677,10 @@ cdef class GeneFinder:
         return out
 
     cdef int _device_tensor(self, pga_ctx* ctx, pga_batch* batch, pga_result* res, object per_contig, dict tok) except -1:
-        """What the request's rule makes of the genes of `res` -- their proteins as token ids, or the annotation of every base -- into
-        the request's device tensor while the batch the finder called is resident (through the raw layer's marshalling); `per_contig`:
-        what the rule needs of every contig, tables or lengths.  Leaves the `DeviceProteins` / `DeviceLabels` in `tok`."""
+        """What the request's rule makes of the genes of `res` -- any of the seven rules of `_cabi` (protein tokens, base labels, gene
+        windows, k-mer counts, protein groups, protein sketches, start candidates) -- into the request's device tensors while the batch
+        the finder called is resident (through the rule's `write`, the raw layer's marshalling); `per_contig`: what the rule needs of
+        every contig, tables or lengths (`spec.per_contig`).  Leaves the rule's `Device*` result in `tok`."""
         genes = np.zeros(0, _cabi.GENE_DTYPE)
         if res.n_genes > 0:
             genes = np.frombuffer(PyBytes_FromStringAndSize(<const char*> res.genes, res.n_genes * sizeof(pga_gene)), dtype=_cabi.GENE_DTYPE)
