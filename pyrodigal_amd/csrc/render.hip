@@ -207,11 +207,7 @@ __global__ void __launch_bounds__(256) k_gff(const RenderArgs a, const int write
 }
 
 __device__ __forceinline__ int64_t body_len(const RenderArgs& a, const pga_gene& g, const int protein) {
-    const int64_t n = g.end - g.begin + 1;
-    if (!protein) return n;
-    const bool stop_edge = g.strand == 1 ? g.partial_end : g.partial_begin;
-    const int64_t l = n / 3 - ((!stop_edge && !a.include_stop) ? 1 : 0);
-    return l > 0 ? l : 0;
+    return pga_fmt::body_letters(g.begin, g.end, g.strand, g.partial_begin, g.partial_end, protein, a.include_stop);
 }
 
 // FASTA record headers (lib.pyx:1194-1196 / 1210-1212): '>id_k # begin # end # strand # gene data'; the length pass sizes the
@@ -293,16 +289,11 @@ __global__ void __launch_bounds__(256) k_fa_body(const RenderArgs a, const int p
 // Units of contig c: its header at 2 c + gene_begin[c], gene g at 2 c + 1 + g, ORIGIN at 2 c + 1 + gene_begin[c + 1].
 
 #define GBK_PAD "                     "     // the 21 columns of a qualifier line
-constexpr int64_t kOriginLong = 16666667;   // first ORIGIN line whose position 60 k + 1 has ten digits ('{:>9}' widens)
-
-// ORIGIN of a sequence of n bases: "ORIGIN\n", per 60 bases the position right-aligned in 9 columns and ten-base blocks with a
-// leading space each, then "//\n"
-__device__ __forceinline__ int64_t origin_len(const int64_t n) {
-    const int64_t lines = (n + 59) / 60;
-    return 7 + 9 * lines + (lines > kOriginLong ? lines - kOriginLong : 0) + n + (n + 9) / 10 + lines + 3;
-}
-// first byte of ORIGIN line k (every line before it is full)
-__device__ __forceinline__ int64_t origin_line_at(const int64_t k) { return 7 + 76 * k + (k > kOriginLong ? k - kOriginLong : 0); }
+// the closed forms of ORIGIN (its length, where a line starts) and of a /translation block are in render_fmt.h, where the host shim reaches them
+using pga_fmt::kOriginLong;
+using pga_fmt::origin_len;
+using pga_fmt::origin_line_at;
+using pga_fmt::gbk_tr_bytes;
 
 __device__ void gbk_header(Sink& o, const RenderArgs& a, const int c) {
     const int64_t slen = a.ct[c].len;
@@ -346,7 +337,6 @@ __device__ void gbk_gene_head(Sink& o, const RenderArgs& a, const pga_gene& g, c
 // '/translation="<protein without its stop>"' wrapped by textwrap.wrap(_, 59) (no whitespace in it: 59-character pieces), every
 // piece on a qualifier line: 21 spaces + piece + newline
 __device__ __forceinline__ int64_t gbk_tr_chars(const RenderArgs& a, const pga_gene& g) { return 15 + body_len(a, g, 1); }
-__device__ __forceinline__ int64_t gbk_tr_bytes(const int64_t L) { return L + 22 * ((L + 58) / 59); }
 
 __global__ void __launch_bounds__(256) k_gbk(const RenderArgs a, const int write) {
     const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;

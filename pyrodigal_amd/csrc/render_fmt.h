@@ -94,4 +94,33 @@ PGA_HD bool near_midpoint(const double x, const int nd, const double margin) {
     return (d < 0 ? -d : d) < margin * p;
 }
 
+// ---- closed forms of the renderer's lengths and offsets (render.hip), here so that the host-side shim reaches them ----
+
+// letters of a FASTA record body: the bases begin .. end of a gene FASTA record; the residues of a protein, one per whole codon,
+// without the stop codon's unless the gene runs off the sequence at its stop (partial flags are in sequence orientation) or the
+// stop is asked for
+PGA_HD int64_t body_letters(const int64_t begin, const int64_t end, const int strand, const int partial_begin, const int partial_end,
+                            const int protein, const int include_stop) {
+    const int64_t n = end - begin + 1;
+    if (!protein) return n;
+    const bool stop_edge = strand == 1 ? partial_end != 0 : partial_begin != 0;
+    const int64_t l = n / 3 - ((!stop_edge && !include_stop) ? 1 : 0);
+    return l > 0 ? l : 0;
+}
+
+constexpr int64_t kOriginLong = 16666667;   // first ORIGIN line whose position 60 k + 1 has ten digits ('{:>9}' widens)
+
+// ORIGIN of a sequence of n bases: "ORIGIN\n", per 60 bases the position right-aligned in 9 columns and ten-base blocks with a
+// leading space each, then "//\n"
+PGA_HD int64_t origin_len(const int64_t n) {
+    const int64_t lines = (n + 59) / 60;
+    return 7 + 9 * lines + (lines > kOriginLong ? lines - kOriginLong : 0) + n + (n + 9) / 10 + lines + 3;
+}
+// first byte of ORIGIN line k (every line before it is full)
+PGA_HD int64_t origin_line_at(const int64_t k) { return 7 + 76 * k + (k > kOriginLong ? k - kOriginLong : 0); }
+
+// bytes of a '/translation="..."' string of L characters wrapped into 59-character pieces, every piece on a qualifier line:
+// 21 spaces + piece + newline
+PGA_HD int64_t gbk_tr_bytes(const int64_t L) { return L + 22 * ((L + 58) / 59); }
+
 }  // namespace pga_fmt
