@@ -753,6 +753,64 @@ int  pga_sketch_pairs(pga_ctx*, const int64_t* d_sketch, const int64_t* d_count,
                       const int64_t* d_pairs /* [P, 2] */, int64_t n_pairs, int64_t* d_shared, int64_t* d_union, void* stream);
 int  pga_sketch_passes(pga_ctx*, int64_t* out);
 
+/* Near-identical proteins clustered on the device from their sketches: which pairs of sketch rows are worth comparing, which of them
+ * pass a resemblance threshold, and the connected components of those -- the step behind pga_sketch_proteins for a caller that drops
+ * near-copies before embedding or searching.  It takes sketch tensors, not a batch: the rows of different calls, batches and
+ * processes can be concatenated and clustered together.  Candidate generation is linear in the input, as in linclust.
+ *   Inputs.  sketch [G, size] and count [G], as pga_sketch_proteins leaves them (a count outside 0 .. size is read as the nearest of
+ *     the two, as pga_sketch_pairs reads it).  weight [G] (int64), or NULL, which means all weights are equal.  Options: size (1..64),
+ *     probes (1..size), num, den (1 <= num <= den <= 2^20), min_union (0..size).
+ *   1. Probes.  Record g probes with sketch[g, j] for j < min(probes, count[g]).  Padding behind count[g] is never a probe.  Two
+ *      records with count = 0 are never joined.  A genuine hash equal to INT64_MAX inside the counted entries is a probe like any
+ *      other.
+ *   2. Buckets.  The bucket of hash h is every record that probes with h.  Its centre is the member of greatest weight; on a tie, the
+ *      smallest index.
+ *   3. Candidates.  For each bucket and each member g other than its centre c, the unordered pair (min(c, g), max(c, g)).  The
+ *      candidate set is the distinct such pairs.  It holds at most G * probes pairs.
+ *   4. Acceptance.  Take (shared, m) as pga_sketch_pairs defines them for the pair.  The pair is an edge exactly when
+ *      m >= max(min_union, 1) and shared * den >= num * m.
+ *   5. Edges.  The accepted pairs in ascending (a, b) order, a < b, each once, with their shared and m.  n_edges is the true count.
+ *   6. Clusters.  The connected components of the graph on 0 .. G - 1 with those edges.  Clusters are numbered 0 .. U - 1 in
+ *      increasing order of their smallest member.  cluster[g] is that number.  representative[u] is the member of greatest weight,
+ *      smallest index on a tie.  size[u] is its number of members.
+ *   Two limits.  Single linkage chains: a is joined to c through b although a and c are far apart.  It is meant for high thresholds.
+ *     A pair whose common hashes all lie beyond the first `probes` entries of either row is not proposed.  The edges are exported so
+ *     that a caller can apply a linkage of their own.
+ *   Outputs.  All int64 device memory of the context's device, 8-byte aligned.
+ *       d_cluster        [G], required           the cluster of record g
+ *       d_representative [capacity >= G], NULL   first U elements: each cluster's representative
+ *       d_size           [capacity >= G], NULL   first U elements: the members of each cluster
+ *       d_edges          [edge_capacity, 2]      the first min(edge_capacity, n_edges) edges, (a, b) each
+ *       d_edge_shared    [edge_capacity]         their shared
+ *       d_edge_union     [edge_capacity]         their m
+ *       n_clusters, n_edges   host               U, and the true number of edges whatever edge_capacity is
+ *     d_representative and d_size may be NULL; the three edge arrays may be NULL all together.  Nothing outside the named elements
+ *     is touched.
+ *   Refusals.  PGA_EINVAL, pga_last_error naming the field, all on the host before anything is allocated or launched: an option out
+ *     of range; G above INT32_MAX, or G * probes above INT32_MAX; capacity below G with d_representative or d_size given; a negative
+ *     edge_capacity; a NULL d_sketch, d_count, d_cluster, options or count pointer; edge arrays given only in part; a pointer that is
+ *     not 8-byte aligned; and the device-pointer query on every pointer given.  G = 0 returns PGA_OK with both counts 0 and no launch.
+ *   Ordering and concurrency.  As pga_group_proteins: the call waits for what `stream` holds, works on the context's upload stream,
+ *     and on return the tensors are complete for any stream.  One such call at a time per context.  The work arrays -- 44 bytes per
+ *     probe slot, 32 per record -- are a block the context keeps and grows: a steady run allocates nothing, and the result does not
+ *     depend on what earlier calls left there.
+ *   The result depends on the arguments alone: integers throughout, and every atomic is a max, a min, an add or a compare-and-swap
+ *     whose outcome does not depend on the order of arrival.
+ * pga_cluster_stats: {probes, distinct candidates, edges, clusters} of the context's last pga_cluster_sketches call. */
+typedef struct pga_cluster_opts {
+    int32_t size;               /* s of the sketches */
+    int32_t probes;             /* leading entries of a row that propose pairs */
+    int32_t num, den;           /* the threshold: shared / m >= num / den */
+    int32_t min_union;          /* the least m of an edge */
+    int32_t _pad;
+} pga_cluster_opts;
+int  pga_cluster_sketches(pga_ctx*, const int64_t* d_sketch, const int64_t* d_count, const int64_t* d_weight /* or NULL */, int64_t n,
+                          const pga_cluster_opts*, int64_t* d_cluster /* [n], required */, int64_t* d_representative, int64_t* d_size,
+                          int64_t capacity, int64_t* d_edges /* [edge_capacity, 2] */, int64_t* d_edge_shared, int64_t* d_edge_union,
+                          int64_t edge_capacity, void* stream /* hipStream_t, NULL = the null stream */, int64_t* n_clusters /* host */,
+                          int64_t* n_edges /* host */);
+int  pga_cluster_stats(pga_ctx*, int64_t out[4]);
+
 /* ---- text output ------------------------------------------------------------------ */
 /* GFF, protein FASTA, gene FASTA, GenBank and the start-score file of gene records, rendered on the device from a resident
  * batch: byte for byte what the host writers Genes.write_gff / write_translations / write_genes / write_genbank / write_scores

@@ -4,6 +4,7 @@ There is no CPU implementation behind this module: if the shared library is miss
 gfx950 device is visible, calls raise instead of silently computing elsewhere.
 """
 import ctypes
+import fractions
 import functools
 import os
 
@@ -34,6 +35,7 @@ EXPORTS = [
     "pga_count_kmers", "pga_kmer_counts_chunk",
     "pga_group_proteins", "pga_protein_groups_stats",
     "pga_sketch_proteins", "pga_sketch_pairs", "pga_sketch_passes",
+    "pga_cluster_sketches", "pga_cluster_stats",
 ]
 STAGE_EXTRACT, STAGE_SCORE, STAGE_OVERLAP, STAGE_SEQUENCE = 1, 2, 3, 4
 
@@ -136,6 +138,11 @@ class SketchOpts(ctypes.Structure):
     _fields_ = [("unit", ctypes.c_int32), ("k", ctypes.c_int32), ("size", ctypes.c_int32), ("seed", ctypes.c_uint32),
                 ("include_stop", ctypes.c_int32), ("strict", ctypes.c_int32), ("unknown_residue", ctypes.c_int32), ("_pad", ctypes.c_int32),
                 ("classes", ctypes.c_uint8 * 128)]
+
+
+class ClusterOpts(ctypes.Structure):
+    _fields_ = [("size", ctypes.c_int32), ("probes", ctypes.c_int32), ("num", ctypes.c_int32), ("den", ctypes.c_int32),
+                ("min_union", ctypes.c_int32), ("_pad", ctypes.c_int32)]
 
 
 class StartOpts(ctypes.Structure):
@@ -244,6 +251,9 @@ def load():
     L.pga_sketch_pairs.restype = ctypes.c_int
     L.pga_sketch_pairs.argtypes = [vp, vp, vp, i64, ctypes.c_int32, vp, i64, vp, vp, vp]
     L.pga_sketch_passes.restype = ctypes.c_int; L.pga_sketch_passes.argtypes = [vp, _P(i64)]
+    L.pga_cluster_sketches.restype = ctypes.c_int
+    L.pga_cluster_sketches.argtypes = [vp, vp, vp, vp, i64, _P(ClusterOpts), vp, vp, vp, i64, vp, vp, vp, i64, vp, _P(i64), _P(i64)]
+    L.pga_cluster_stats.restype = ctypes.c_int; L.pga_cluster_stats.argtypes = [vp, _P(i64)]
     L.pga_start_plan_create.restype = ctypes.c_int
     L.pga_start_plan_create.argtypes = [vp, vp, i64, vp, _P(vp), vp, vp]
     L.pga_start_plan_write.restype = ctypes.c_int
@@ -1269,7 +1279,7 @@ def _token_id(value, name):
 
 
 class _TensorRule:
-    """What the seven rules of the device-tensor outputs share.  Every rule gets value semantics over ``_key()`` -- the attributes
+    """What the rules of the device-tensor outputs share.  Every rule gets value semantics over ``_key()`` -- the attributes
     ``_fields`` names -- and pickles through it (``_derive`` restores what the constructor computes from them); it says what one row
     is (``row`` and its ``unit``) and what it needs of every contig of the batch (``per_contig``: ``"tables"`` or ``"lengths"``),
     and has ``write``, the call on raw handles with just that.  Only the rules that write rows of one element type in either
@@ -2352,6 +2362,165 @@ class DeviceSketches:
             _raise(self._L, self._ctx_h, rc, "pga_sketch_pairs")
         return out
 
+    def cluster(self, spec, weights=None, out=None, stream=None):
+        """The rows clustered by resemblance (``pga_cluster_sketches``): ``spec`` is a :class:`ProteinClusters` whose ``sketches``
+        is the rule these rows were made under.  ``weights``: an int64 ``[G]`` device tensor, the heavier member of a bucket or a
+        cluster being its centre or representative; default ``self.windows``, and equal weights where that is ``None``.  ``out``
+        and ``stream`` as in :func:`clusters_into`.  The context of the call that made the sketches must still be open.  Returns a
+        :class:`DeviceClusters`."""
+        if not isinstance(spec, ProteinClusters):
+            raise TypeError("the clustering rule must be a ProteinClusters, not %r" % type(spec).__name__)
+        if spec.sketches != self.spec:
+            raise ValueError("these sketches were made under %r, not under the rule's %r" % (self.spec, spec.sketches))
+        return clusters_into(self._L, self._ctx_h, self.device, self.sketches, self.counts, self.windows if weights is None else weights,
+                             spec, out, stream, sketches=self)
+
+
+class ProteinClusters(_TensorRule):
+    """How ``DeviceSketches.cluster`` / ``Context.cluster_sketches`` / ``find_clusters_batch`` cluster near-identical proteins from
+    their sketches (``pga_cluster_opts``; the rule is in ``pyrodigal_amd.h``): every hash among a row's first ``probes`` entries
+    proposes the row against the heaviest row that holds it too, a proposed pair is an edge when ``m >= max(min_union, 1)`` and
+    ``shared / m >= min_resemblance`` for the ``(shared, m)`` of ``DeviceSketches.compare``, and the clusters are the connected
+    components.  Single linkage chains, so it is meant for high thresholds; a pair whose common hashes all lie beyond the first
+    ``probes`` entries of either row is not proposed.
+
+    ``sketches``: the :class:`ProteinSketches` the rows are made under.  ``probes``: 1 .. ``sketches.size``.  ``min_resemblance``:
+    a ``(num, den)`` pair of ints with ``1 <= num <= den <= 2**20``, or a ``fractions.Fraction`` -- not a float: the comparison is
+    ``shared * den >= num * m`` in integers, so that the result depends on the arguments alone.  ``min_union``: 0 ..
+    ``sketches.size``.  Everything that needs no device is checked here.  Hashable and picklable."""
+
+    def __init__(self, sketches=None, probes=8, min_resemblance=(9, 10), min_union=8):
+        if sketches is None:
+            sketches = ProteinSketches(5, 32)
+        if not isinstance(sketches, ProteinSketches):
+            raise TypeError("sketches must be a ProteinSketches, not %r" % type(sketches).__name__)
+        for name, v in (("probes", probes), ("min_union", min_union)):
+            if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)):
+                raise TypeError(f"{name} must be an int, not {type(v).__name__}")
+        if isinstance(min_resemblance, (float, np.floating)):
+            raise TypeError("min_resemblance must be a (num, den) pair of ints or a fractions.Fraction, not a float: the threshold is "
+                            "applied as shared * den >= num * m in integers, and a float names no such pair (0.9 is not 9 / 10)")
+        if isinstance(min_resemblance, fractions.Fraction):
+            min_resemblance = (min_resemblance.numerator, min_resemblance.denominator)
+        try:
+            num, den = min_resemblance
+        except (TypeError, ValueError):
+            raise TypeError("min_resemblance must be a (num, den) pair of ints or a fractions.Fraction, not %r" % (min_resemblance,)) from None
+        for name, v in (("num", num), ("den", den)):
+            if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)):
+                raise TypeError(f"min_resemblance: {name} must be an int, not {type(v).__name__}")
+        if not 1 <= probes <= sketches.size:
+            raise ValueError(f"probes must be 1 .. the sketch size {sketches.size}, not {probes}")
+        if not 1 <= num <= den <= (1 << 20):
+            raise ValueError(f"min_resemblance must have 1 <= num <= den <= 2**20, not {num} / {den}")
+        if not 0 <= min_union <= sketches.size:
+            raise ValueError(f"min_union must be 0 .. the sketch size {sketches.size}, not {min_union}")
+        self.sketches, self.probes, self.min_resemblance, self.min_union = sketches, int(probes), (int(num), int(den)), int(min_union)
+
+    row, unit = "gene", "clusters"
+    per_contig = property(lambda self: self.sketches.per_contig)
+    dtype, typestr, elem_bytes = "int64", "<i8", 8
+    _fields = ("sketches", "probes", "min_resemblance", "min_union")
+
+    def write(self, L, ctx_h, batch_h, device, genes, tables, out=None, stream=None):
+        # (the finder's call: the sketches into new tensors, the clusters into `out`)
+        sk = sketches_into(L, ctx_h, batch_h, device, len(tables), genes, tables, self.sketches, None, stream)
+        return sk.cluster(self, None, out, stream)
+
+    def __repr__(self):
+        return "pyrodigal_amd.ProteinClusters(%r, probes=%r, min_resemblance=%r, min_union=%r)" % self._key()
+
+    def opts(self):
+        o = ClusterOpts()
+        o.size, o.probes, o.min_union = self.sketches.size, self.probes, self.min_union
+        o.num, o.den = self.min_resemblance
+        return o
+
+
+class DeviceClusters:
+    """Sketch rows clustered by resemblance, in device memory, all int64.  ``cluster``: ``[G]``, the cluster of every row, numbered
+    in increasing order of the clusters' smallest members; ``representatives``: ``[U]``, the heaviest row of every cluster (the
+    smallest index on a tie); ``sizes``: ``[U]``, its members; ``edges``: ``[E, 2]``, the accepted pairs ``(a, b)``, ``a < b``, in
+    ascending order, with ``edge_shared`` and ``edge_union`` ``[E]``, their ``(shared, m)`` -- for a caller's own linkage.
+    ``n_clusters``: U; ``n_edges``: the true number of edges, of which the first ``min(n_edges, capacity of out=)`` were written.
+    Tensors for which ``out=`` gave ``None`` are ``None``.  ``spec``: the :class:`ProteinClusters`; ``sketches``: the
+    :class:`DeviceSketches` that were clustered (``None`` for tensors given to ``Context.cluster_sketches``)."""
+
+    def __init__(self, cluster, representatives, sizes, n_clusters, edges, edge_shared, edge_union, n_edges, spec, sketches, device):
+        self.cluster, self.representatives, self.sizes, self.n_clusters = cluster, representatives, sizes, n_clusters
+        self.edges, self.edge_shared, self.edge_union, self.n_edges = edges, edge_shared, edge_union, n_edges
+        self.spec, self.sketches, self.device = spec, sketches, device
+
+
+def clusters_into(L, ctx_h, device, sketch, count, weight, spec, out=None, stream=None, sketches=None):
+    """``pga_cluster_sketches`` on raw handles (what ``DeviceSketches.cluster`` and ``Context.cluster_sketches`` share): int64
+    device tensors ``sketch [G, size]``, ``count [G]`` and ``weight [G]`` or ``None`` under ``spec`` into the six tensors of
+    ``out`` -- ``(cluster [G], representatives [>= G], sizes [>= G], edges [C, 2], edge_shared [C], edge_union [C])``, contiguous
+    int64 objects with ``__cuda_array_interface__``, ``None`` allowed for the second and third and for the last three together --
+    or into new torch tensors, the edge tensors with room for all ``G * probes`` candidates.  ``stream``: the stream that last
+    used the tensors, as in :class:`DeviceSequences`."""
+    if not isinstance(spec, ProteinClusters):
+        raise TypeError("the clustering rule must be a ProteinClusters, not %r" % type(spec).__name__)
+    shape = _device_array(sketch, "sketches")[1]
+    if len(shape) != 2 or shape[1] != spec.sketches.size:
+        raise ValueError(f"sketches needs shape [G, {spec.sketches.size}], not {list(shape)}")
+    n = shape[0]
+    p_sk, p_cnt = _group_output(sketch, "sketches", (n, spec.sketches.size), True), _group_output(count, "counts", (n,), True)
+    p_w = _group_output(weight, "weights", (n,), False)
+    if out is None:
+        C = n * spec.probes
+        out, stream = _torch_outputs(device, stream, [(n, "int64"), (n, "int64"), (n, "int64"), ((C, 2), "int64"), (C, "int64"), (C, "int64")],
+                                     "six device arrays")
+    out = tuple(out)
+    if len(out) != 6:
+        raise ValueError("out must be (cluster, representatives, sizes, edges, edge_shared, edge_union), %d objects were given" % len(out))
+    cluster, reps, sizes, edges, eshared, eunion = out
+    p_cluster = _group_output(cluster, "cluster", (n,), True)
+    p_reps, p_sizes = _group_output(reps, "representatives", (n,), False), _group_output(sizes, "sizes", (n,), False)
+    capacity = min([_device_array(x, "out")[1][0] for x in (reps, sizes) if x is not None] or [n])
+    given = [x is not None for x in (edges, eshared, eunion)]
+    if any(given) and not all(given):
+        raise ValueError("out: edges, edge_shared and edge_union are given all three or not at all")
+    edge_capacity, p_edges, p_eshared, p_eunion = 0, 0, 0, 0
+    if all(given):
+        eshape = _device_array(edges, "out: edges")[1]
+        if len(eshape) != 2 or eshape[1] != 2:
+            raise ValueError(f"out: edges needs shape [C, 2], not {list(eshape)}")
+        edge_capacity = min(eshape[0], _device_array(eshared, "out: edge_shared")[1][0], _device_array(eunion, "out: edge_union")[1][0])
+        p_edges = _group_output(edges, "edges", (edge_capacity, 2), True)
+        p_eshared, p_eunion = _group_output(eshared, "edge_shared", (edge_capacity,), True), _group_output(eunion, "edge_union", (edge_capacity,), True)
+    n_clusters, n_edges = ctypes.c_int64(0), ctypes.c_int64(0)
+    o = spec.opts()
+    rc = L.pga_cluster_sketches(ctx_h, ctypes.c_void_p(p_sk), ctypes.c_void_p(p_cnt), ctypes.c_void_p(p_w), n, ctypes.byref(o),
+                                ctypes.c_void_p(p_cluster), ctypes.c_void_p(p_reps), ctypes.c_void_p(p_sizes), capacity,
+                                ctypes.c_void_p(p_edges), ctypes.c_void_p(p_eshared), ctypes.c_void_p(p_eunion), edge_capacity,
+                                ctypes.c_void_p(DeviceSequences._stream_of(cluster, stream)), ctypes.byref(n_clusters), ctypes.byref(n_edges))
+    if rc != PGA_OK:
+        _raise(L, ctx_h, rc, "pga_cluster_sketches")
+    U, E = int(n_clusters.value), int(n_edges.value)
+    cut = lambda x, k: None if x is None else (x[:k] if hasattr(x, "__getitem__") else x)      # noqa: E731
+    W = min(E, edge_capacity)
+    return DeviceClusters(cluster, cut(reps, U), cut(sizes, U), U, cut(edges, W), cut(eshared, W), cut(eunion, W), E, spec, sketches, device)
+
+
+def _cluster_sketches(self, sketches, counts, spec, weights=None, out=None, stream=None):
+    """Sketch rows from anywhere -- the ``torch.cat`` of several calls' ``DeviceSketches.sketches`` and ``counts``, say -- clustered
+    on the device (``pga_cluster_sketches``).  ``sketches`` ``[G, spec.sketches.size]`` and ``counts`` ``[G]``: contiguous int64
+    device tensors; ``weights``: one more ``[G]``, or ``None`` for equal weights.  ``out`` and ``stream`` as in
+    :func:`clusters_into`.  Returns a :class:`DeviceClusters`."""
+    return clusters_into(self.L, self.h, self.device, sketches, counts, weights, spec, out, stream)
+
+
+def _cluster_stats(self):
+    """How the context's last ``cluster_sketches`` call went (``pga_cluster_stats``): the probes, the distinct candidate pairs, the
+    edges and the clusters."""
+    out = (ctypes.c_int64 * 4)()
+    rc = self.L.pga_cluster_stats(self.h, out)
+    if rc != PGA_OK:
+        _raise(self.L, self.h, rc, "pga_cluster_stats")
+    return {"probes": int(out[0]), "candidates": int(out[1]), "edges": int(out[2]), "clusters": int(out[3])}
+
+
 
 def sketches_into(L, ctx_h, batch_h, device, n_contigs, genes, tables, spec, out=None, stream=None):
     """``pga_sketch_proteins`` on raw handles (what ``Context.protein_sketches`` and the finder's device call share): the sketches of
@@ -2926,6 +3095,8 @@ Context.protein_groups = _protein_groups
 Context.protein_groups_stats = _protein_groups_stats
 Context.protein_sketches = _protein_sketches
 Context.protein_sketch_passes = _protein_sketch_passes
+Context.cluster_sketches = _cluster_sketches
+Context.cluster_stats = _cluster_stats
 Context.train = _train
 Context.train_batch = _train_batch
 Context.upload = _upload

@@ -77,6 +77,7 @@ extern "C" void pga_destroy(pga_ctx* c) {
     pga_finder_release(c);
     pga_render_release(c);
     pga_start_release(c);
+    pga_cluster_release(c);
     if (c->d_models_raw) hipFree(c->d_models_raw);
     if (c->d_model_const) hipFree(c->d_model_const);
     if (c->ev0) hipEventDestroy(c->ev0);

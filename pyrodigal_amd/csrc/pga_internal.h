@@ -257,12 +257,15 @@ struct pga_ctx {
     int model_scores_nm = 0;
     int64_t group_stats[2] = {0, 0};                   // pga_protein_groups_stats: rounds and differing pairs of the last pga_group_proteins call
     int64_t sketch_passes = -1;                        // pga_sketch_passes: insertions tried in the last pga_sketch_proteins call (PGA_SKETCH_COUNT_PASSES builds), -1: not counted
+    int64_t cluster_stats[4] = {0, 0, 0, 0};           // pga_cluster_stats: probes, distinct candidates, edges and clusters of the last pga_cluster_sketches call
+    char* cluster_dev = nullptr; size_t cluster_cap = 0;   // pga_cluster_sketches (translate.hip): its work arrays, kept across calls and grown as needed
     int poison = -1;                                   // pga_debug_poison: the fill byte of newly acquired float buffers, -1: off
     std::vector<int64_t> render_seqnums;               // pga_render_seqnums: the seqnum of every contig of the batches rendered next (empty: first_seqnum + i)
 };
 void pga_render_release(pga_ctx*);   // render.hip: frees the buffers above
 hipError_t pga_render_scratch(pga_ctx*, size_t bytes, char** d);   // render.hip: render_dev, grown to at least `bytes`
 void pga_start_release(pga_ctx*);    // translate.hip: frees start_blocks, orphans start_plans
+void pga_cluster_release(pga_ctx*);  // translate.hip: frees cluster_dev
 // summary of a segmented launch's flags (host copy, [PGA_SEG_ROUNDS][stride]) into pga_ctx::dp_stats
 void pga_dp_note_stats(pga_ctx* c, const DpSegPlan* plan, const int32_t* h_flags, int stride);
 

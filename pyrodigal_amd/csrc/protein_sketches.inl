@@ -164,9 +164,25 @@ __device__ __forceinline__ int sk_lower(const int64_t row, const int n, const in
     return lo;
 }
 
-// One pair per wave, in a loop.  Lane i holds A[i] and B[i], both rows ascending and distinct.  An element of A lies in B where the
-// search finds it; its rank in the distinct union is its index, plus the elements of B below it, less the common elements below it
-// (a ballot's low bits, A being sorted).  |U| = |A| + |B| - common, m = min(s, |U|), shared = the common elements of rank < m.
+// (shared, m) of rows ia and ib, by a whole wave, the same in every lane (k_sketch_pairs, and k_cluster_accept of protein_clusters.inl).
+// Lane i holds A[i] and B[i], both rows ascending and distinct.  An element of A lies in B where the search finds it; its rank in the
+// distinct union is its index, plus the elements of B below it, less the common elements below it (a ballot's low bits, A being
+// sorted).  |U| = |A| + |B| - common, m = min(s, |U|), shared = the common elements of rank < m.
+__device__ __forceinline__ void sk_pair(const int64_t* __restrict__ sketch, const int64_t* __restrict__ count, const int s, const int64_t ia,
+                                        const int64_t ib, const int lane, int& shared, int& m) {
+    const int ca = (int)min(max(count[ia], (int64_t)0), (int64_t)s), cb = (int)min(max(count[ib], (int64_t)0), (int64_t)s);
+    const int64_t A = lane < ca ? sketch[ia * s + lane] : kSkNone;
+    const int64_t B = lane < cb ? sketch[ib * s + lane] : kSkNone;
+    const int lb = sk_lower(B, cb, A);                         // elements of B below A[lane]
+    const int64_t at = __shfl(B, lb & 63);
+    const bool common = lane < ca && lb < cb && at == A;
+    const unsigned long long cmask = __ballot(common);
+    m = min(s, ca + cb - __popcll(cmask));
+    const int rank = lane + lb - __popcll(cmask & ((1ull << lane) - 1));
+    shared = __popcll(__ballot(common && rank < m));
+}
+
+// One pair per wave, in a loop.
 __global__ void __launch_bounds__(kRowThreads)
 k_sketch_pairs(const SkPairArgs a) {
     const int lane = threadIdx.x & 63;
@@ -177,16 +193,8 @@ k_sketch_pairs(const SkPairArgs a) {
             if (lane == 0) { a.d_shared[p] = -1; a.d_union[p] = -1; }
             continue;
         }
-        const int ca = (int)min(max(a.count[ia], (int64_t)0), (int64_t)a.s), cb = (int)min(max(a.count[ib], (int64_t)0), (int64_t)a.s);
-        const int64_t A = lane < ca ? a.sketch[ia * a.s + lane] : kSkNone;
-        const int64_t B = lane < cb ? a.sketch[ib * a.s + lane] : kSkNone;
-        const int lb = sk_lower(B, cb, A);                     // elements of B below A[lane]
-        const int64_t at = __shfl(B, lb & 63);
-        const bool common = lane < ca && lb < cb && at == A;
-        const unsigned long long cmask = __ballot(common);
-        const int m = min(a.s, ca + cb - __popcll(cmask));
-        const int rank = lane + lb - __popcll(cmask & ((1ull << lane) - 1));
-        const unsigned long long smask = __ballot(common && rank < m);
-        if (lane == 0) { a.d_shared[p] = __popcll(smask); a.d_union[p] = m; }
+        int shared, m;
+        sk_pair(a.sketch, a.count, a.s, ia, ib, lane, shared, m);
+        if (lane == 0) { a.d_shared[p] = shared; a.d_union[p] = m; }
     }
 }

@@ -100,6 +100,7 @@ int64_t gene_residues(const pga_gene& G, const int include_stop) {
 #include "kmer_counts.inl"
 #include "protein_groups.inl"
 #include "protein_sketches.inl"
+#include "protein_clusters.inl"
 #include "start_candidates.inl"
 
 // the records as k_string_digest, k_group_verify and k_sketch read them
@@ -639,6 +640,133 @@ extern "C" int pga_sketch_pairs(pga_ctx* c, const int64_t* d_sketch, const int64
         const dim3 grid((unsigned)std::min<int64_t>((n_pairs + per_block - 1) / per_block, 16384)), block(kRowThreads);
         hipLaunchKernelGGL(k_sketch_pairs, grid, block, 0, st, a);
         return hipGetLastError();
+    });
+}
+
+// ---- clusters of near-identical proteins (protein_clusters.inl) ----------------------------------------------------------------
+void pga_cluster_release(pga_ctx* c) {
+    if (c->cluster_dev) hipFree(c->cluster_dev);
+    c->cluster_dev = nullptr; c->cluster_cap = 0;
+}
+
+extern "C" int pga_cluster_stats(pga_ctx* c, int64_t out[4]) {
+    if (!c || !out) return PGA_EINVAL;
+    memcpy(out, c->cluster_stats, sizeof c->cluster_stats);
+    return PGA_OK;
+}
+
+extern "C" int pga_cluster_sketches(pga_ctx* c, const int64_t* d_sketch, const int64_t* d_count, const int64_t* d_weight, int64_t n,
+                                    const pga_cluster_opts* o, int64_t* d_cluster, int64_t* d_representative, int64_t* d_size, int64_t capacity,
+                                    int64_t* d_edges, int64_t* d_edge_shared, int64_t* d_edge_union, int64_t edge_capacity, void* stream,
+                                    int64_t* n_clusters, int64_t* n_edges) {
+    if (!c) return PGA_EINVAL;
+    DevCall d{c, "pga_cluster_sketches"};
+    // ---- validation: all of it on the host, before anything is allocated or launched ----
+    if (!o || !n_clusters || !n_edges || n < 0) return d.bad("bad arguments");
+    if (o->size < 1 || o->size > 64) return d.bad("size = " + std::to_string(o->size) + " is outside 1 .. 64");
+    if (o->probes < 1 || o->probes > o->size) return d.bad("probes = " + std::to_string(o->probes) + " is outside 1 .. size = " + std::to_string(o->size));
+    if (o->num < 1 || o->den < o->num || o->den > (1 << 20))
+        return d.bad("num / den = " + std::to_string(o->num) + " / " + std::to_string(o->den) + " is outside 1 <= num <= den <= 2^20");
+    if (o->min_union < 0 || o->min_union > o->size) return d.bad("min_union = " + std::to_string(o->min_union) + " is outside 0 .. size = " + std::to_string(o->size));
+    if (n > INT32_MAX) return d.bad("more than 2^31 - 1 records");
+    if (n * o->probes > INT32_MAX) return d.bad("more than 2^31 - 1 probes: " + std::to_string(n) + " records of " + std::to_string(o->probes));
+    if (capacity < 0 || ((d_representative || d_size) && capacity < n))
+        return d.bad("capacity = " + std::to_string(capacity) + " is less than the " + std::to_string(n) + " records");
+    const int n_edge_arrays = (d_edges ? 1 : 0) + (d_edge_shared ? 1 : 0) + (d_edge_union ? 1 : 0);
+    if (n_edge_arrays != 0 && n_edge_arrays != 3) return d.bad("d_edges, d_edge_shared and d_edge_union are given all three or not at all");
+    if (edge_capacity < 0) return d.bad("edge_capacity = " + std::to_string(edge_capacity) + " is negative");
+    memset(c->cluster_stats, 0, sizeof c->cluster_stats);
+    if (n == 0) { *n_clusters = 0; *n_edges = 0; return PGA_OK; }
+    if (const int rc = d.destinations({{"d_sketch", d_sketch, 8, d.kRequired}, {"d_count", d_count, 8, d.kRequired}, {"d_weight", d_weight, 8, d.kOptional},
+                                       {"d_cluster", d_cluster, 8, d.kRequired}, {"d_representative", d_representative, 8, d.kOptional},
+                                       {"d_size", d_size, 8, d.kOptional}, {"d_edges", d_edges, 8, d.kOptional},
+                                       {"d_edge_shared", d_edge_shared, 8, d.kOptional}, {"d_edge_union", d_edge_union, 8, d.kOptional}})) return rc;
+    // ---- the work arrays: a block the context keeps and grows; every element that is read was written by this call ----
+    const size_t G = (size_t)n, T = G * (size_t)o->probes;
+    const int iG = (int)n, iT = (int)T;
+    int pair_bits = 33;                                          // 32 + the bits of G: the key behind every pair is G << 32
+    while (pair_bits < 63 && (G >> (pair_bits - 32)) != 0) pair_bits++;
+    size_t sort_b = 0, keys_b = 0, max_b = 0, sum_b = 0, sum_g = 0;
+    hipcub::DeviceRadixSort::SortPairs(nullptr, sort_b, (uint64_t*)nullptr, (uint64_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr, iT, 0, 64, (hipStream_t)nullptr);
+    hipcub::DeviceRadixSort::SortKeys(nullptr, keys_b, (uint64_t*)nullptr, (uint64_t*)nullptr, iT, 0, pair_bits, (hipStream_t)nullptr);
+    hipcub::DeviceScan::InclusiveScan(nullptr, max_b, (uint32_t*)nullptr, (uint32_t*)nullptr, GrpMax{}, iT, (hipStream_t)nullptr);
+    hipcub::DeviceScan::ExclusiveSum(nullptr, sum_b, (uint32_t*)nullptr, (uint32_t*)nullptr, iT, (hipStream_t)nullptr);
+    hipcub::DeviceScan::ExclusiveSum(nullptr, sum_g, (int32_t*)nullptr, (int32_t*)nullptr, iG, (hipStream_t)nullptr);
+    const size_t tmp_b = std::max(std::max(sort_b, keys_b), std::max(max_b, std::max(sum_b, sum_g)));
+    Staging work(256);                                           // (only its offsets: the block is the context's own)
+    const size_t p_key = work.take(8 * T), p_skey = work.take(8 * T), p_wmax = work.take(8 * T), p_idx = work.take(4 * T), p_sidx = work.take(4 * T);
+    const size_t p_start = work.take(4 * T), p_runstart = work.take(4 * T), p_centre = work.take(4 * T);
+    const size_t p_rw = work.take(8 * G), p_parent = work.take(4 * G), p_root = work.take(4 * G), p_isroot = work.take(4 * G), p_number = work.take(4 * G);
+    const size_t p_cnt = work.take(4 * G), p_rep = work.take(4 * G), p_tmp = work.take(tmp_b + 1);
+    Staging tab(256);
+    const size_t p_small = tab.take(256);
+    if (const int rc = tab.lease(c)) return rc;                  // (one such call at a time per context from here on)
+    if (c->cluster_cap < work.bytes()) {
+        pga_cluster_release(c);
+        const size_t want = work.bytes() + work.bytes() / 4 + 4096;
+        if (hipMalloc((void**)&c->cluster_dev, want) != hipSuccess) {
+            (void)hipGetLastError();
+            c->cluster_dev = nullptr;
+            pga_upload_lease_give(c);
+            c->err = "pga_cluster_sketches: no device memory for " + std::to_string(want) + " bytes of work arrays";
+            return PGA_ENOMEM;
+        }
+        c->cluster_cap = want;
+    }
+    char* const W = c->cluster_dev;
+    volatile long long* const h_small = tab.pin<volatile long long>(p_small);
+    ClArgs a{};
+    a.sketch = d_sketch; a.count = d_count; a.weight = d_weight; a.n = n; a.slots = (int64_t)T;
+    a.s = o->size; a.probes = o->probes; a.num = o->num; a.den = o->den; a.min_union = o->min_union;
+    a.key = (uint64_t*)(W + p_key); a.skey = (uint64_t*)(W + p_skey); a.idx = (uint32_t*)(W + p_idx); a.sidx = (uint32_t*)(W + p_sidx);
+    a.start = (uint32_t*)(W + p_start); a.runstart = (uint32_t*)(W + p_runstart);
+    a.wmax = (unsigned long long*)(W + p_wmax); a.centre = (uint32_t*)(W + p_centre);
+    a.parent = (int32_t*)(W + p_parent); a.root = (int32_t*)(W + p_root); a.isroot = (int32_t*)(W + p_isroot); a.number = (int32_t*)(W + p_number);
+    a.cnt = (int32_t*)(W + p_cnt); a.rw = (unsigned long long*)(W + p_rw); a.rep = (uint32_t*)(W + p_rep);
+    a.small = tab.dev<unsigned long long>(p_small);
+    a.d_cluster = d_cluster; a.d_rep = d_representative; a.d_size = d_size;
+    a.d_edges = d_edges; a.d_eshared = d_edge_shared; a.d_eunion = d_edge_union; a.edge_capacity = edge_capacity;
+    void* const d_tmp = W + p_tmp;
+    const dim3 block(kRowThreads), per_slot((unsigned)((T + kRowThreads - 1) / kRowThreads)), per_rec((unsigned)((G + kRowThreads - 1) / kRowThreads));
+    auto launched = [&]() { return hipGetLastError(); };
+    return d.run(tab.L, 0, stream, [&](hipStream_t st) {
+        size_t tb = tmp_b;
+        hipError_t e = hipMemsetAsync(a.small, 0, 32, st);
+        if (e == hipSuccess) { hipLaunchKernelGGL(k_cluster_probes, dim3(std::min(per_slot.x, 2048u)), block, 0, st, a); e = launched(); }
+        if (e == hipSuccess) e = hipcub::DeviceRadixSort::SortPairs(d_tmp, tb, (const uint64_t*)a.key, a.skey, (const uint32_t*)a.idx, a.sidx, iT, 0, 64, st);
+        if (e == hipSuccess) { hipLaunchKernelGGL(k_cluster_heads, per_slot, block, 0, st, a); e = launched(); }
+        tb = tmp_b;
+        if (e == hipSuccess) e = hipcub::DeviceScan::InclusiveScan(d_tmp, tb, (const uint32_t*)a.start, a.runstart, GrpMax{}, iT, st);
+        if (e == hipSuccess) e = hipMemsetAsync(a.centre, 0xff, 4 * T, st);
+        if (e == hipSuccess && d_weight) {
+            e = hipMemsetAsync(a.wmax, 0, 8 * T, st);
+            if (e == hipSuccess) { hipLaunchKernelGGL(k_cluster_centre<0>, per_slot, block, 0, st, a); e = launched(); }
+        }
+        if (e == hipSuccess) { hipLaunchKernelGGL(k_cluster_centre<1>, per_slot, block, 0, st, a); e = launched(); }
+        if (e == hipSuccess) { hipLaunchKernelGGL(k_cluster_pairs, per_slot, block, 0, st, a); e = launched(); }
+        tb = tmp_b;
+        if (e == hipSuccess) e = hipcub::DeviceRadixSort::SortKeys(d_tmp, tb, (const uint64_t*)a.key, a.skey, iT, 0, pair_bits, st);
+        if (e == hipSuccess) {
+            // a wave per 64 slots, and several rounds of them per wave where there are many: 2 048 workgroups fill the device
+            const int64_t steps = ((int64_t)T + 63) / 64, per_block = kRowThreads / 64;
+            const dim3 grid((unsigned)std::min<int64_t>((steps + per_block - 1) / per_block, 2048));
+            hipLaunchKernelGGL(k_cluster_accept, grid, block, 0, st, a);
+            e = launched();
+        }
+        tb = tmp_b;
+        if (e == hipSuccess) e = hipcub::DeviceScan::ExclusiveSum(d_tmp, tb, (const uint32_t*)a.start, a.runstart, iT, st);
+        if (e == hipSuccess) { hipLaunchKernelGGL(k_cluster_edges, per_slot, block, 0, st, a); e = launched(); }
+        if (e == hipSuccess) { hipLaunchKernelGGL(k_cluster_flatten, per_rec, block, 0, st, a); e = launched(); }
+        tb = tmp_b;
+        if (e == hipSuccess) e = hipcub::DeviceScan::ExclusiveSum(d_tmp, tb, (const int32_t*)a.isroot, a.number, iG, st);
+        if (e == hipSuccess) { hipLaunchKernelGGL(k_cluster_number, per_rec, block, 0, st, a); e = launched(); }
+        if (e == hipSuccess && d_representative) { hipLaunchKernelGGL(k_cluster_representative, per_rec, block, 0, st, a); e = launched(); }
+        if (e == hipSuccess && (d_representative || d_size)) { hipLaunchKernelGGL(k_cluster_emit, per_rec, block, 0, st, a); e = launched(); }
+        if (e == hipSuccess) e = hipMemcpyAsync((void*)h_small, a.small, 32, hipMemcpyDeviceToHost, st);
+        return e;
+    }, [&] {
+        *n_edges = h_small[0]; *n_clusters = h_small[1];
+        c->cluster_stats[0] = h_small[3]; c->cluster_stats[1] = h_small[2]; c->cluster_stats[2] = h_small[0]; c->cluster_stats[3] = h_small[1];
     });
 }
 

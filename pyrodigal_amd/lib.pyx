@@ -2147,6 +2147,28 @@ cdef class GeneFinder:
         return self._find_tensor_batch("find_sketches_batch", sequences, sketches, out, stream, translate, training_infos, regions, circular, sets,
                                        trim_terminal_repeats)
 
+    def find_clusters_batch(self, object sequences, object clusters, *, object out=None, object stream=None, bint translate=False,
+                            object training_infos=None, object regions=None, object circular=None, object sets=None,
+                            object trim_terminal_repeats=None):
+        """`find_genes_batch`, and the genes whose predicted proteins (or bases) are near-copies of each other clustered on the
+        device: returns `(genes, device_clusters)`, the list of `Genes` that `find_genes_batch` returns for the same arguments and a
+        `DeviceClusters`.
+
+        `clusters`: a `ProteinClusters` -- the `ProteinSketches` to sketch under, the probes, the least resemblance and the least
+        union.  Exactly `find_sketches_batch` with `clusters.sketches` followed by `device_sketches.cluster(clusters)`: gene g of
+        the request, contig after contig, gets `cluster[g]`; the clusters are numbered in order of their smallest members,
+        `representatives[u]` is the member with the most valid windows and `sizes[u]` its members; `edges`, `edge_shared` and
+        `edge_union` are the accepted pairs, for a linkage of the caller's own; `device_clusters.sketches` is the `DeviceSketches`.
+        `out`: a `(cluster, representatives, sizes, edges, edge_shared, edge_union)` tuple of int64 device tensors to write
+        (anything with `__cuda_array_interface__`; `None` for the second and third, and for the last three together), omitted:
+        torch tensors allocated under torch's current stream; `stream`: the stream that last used them.  Every option of
+        `find_genes_batch` applies and `sequences` may be a `DeviceSequences`.  The request is a device call of its own: one set of
+        tensors per request, so a request that `training_infos` would split into several device calls is a `ValueError`."""
+        if not isinstance(clusters, _cabi.ProteinClusters):
+            raise TypeError("`clusters` must be a ProteinClusters, not %r" % type(clusters).__name__)
+        return self._find_tensor_batch("find_clusters_batch", sequences, clusters, out, stream, translate, training_infos, regions, circular, sets,
+                                       trim_terminal_repeats)
+
     def find_starts_batch(self, object sequences, object starts, *, object out=None, object stream=None, bint translate=False,
                           object training_infos=None, object regions=None, object circular=None, object sets=None,
                           object trim_terminal_repeats=None):
@@ -2174,8 +2196,8 @@ cdef class GeneFinder:
 
     cdef tuple _find_tensor_batch(self, str method, object sequences, object spec, object out, object stream, bint translate,
                                   object training_infos, object regions, object circular, object sets, object trim_terminal_repeats):
-        """What the seven `find_*_batch` methods with a device-tensor output share (proteins, labels, windows, counts, groups,
-        sketches, starts): (the `Genes` of `find_genes_batch`, what the rule `spec` wrote on the device)."""
+        """What the eight `find_*_batch` methods with a device-tensor output share (proteins, labels, windows, counts, groups,
+        sketches, clusters, starts): (the `Genes` of `find_genes_batch`, what the rule `spec` wrote on the device)."""
         cdef dict tok = {"spec": spec, "out": out, "stream": stream, "result": None, "method": method}
         cdef list circ, tr_search
         cdef object dev, set_ids, tr_params
@@ -2194,7 +2216,7 @@ cdef class GeneFinder:
         return genes, tok["result"]
 
     cdef tuple _batch_options(self, object sequences, object training_infos, object circular, object sets, object trim_terminal_repeats):
-        """The options of `find_genes_batch` and of the seven `find_*_batch` methods with a device-tensor output, checked against each
+        """The options of `find_genes_batch` and of the eight `find_*_batch` methods with a device-tensor output, checked against each
         other and against the number of sequences: (the DeviceSequences or None, the sequences, circular flags, set ids,
         terminal-repeat search and its parameters)."""
         cdef list circ = None
@@ -2677,8 +2699,8 @@ cdef class GeneFinder:
         return out
 
     cdef int _device_tensor(self, pga_ctx* ctx, pga_batch* batch, pga_result* res, object per_contig, dict tok) except -1:
-        """What the request's rule makes of the genes of `res` -- any of the seven rules of `_cabi` (protein tokens, base labels, gene
-        windows, k-mer counts, protein groups, protein sketches, start candidates) -- into the request's device tensors while the batch
+        """What the request's rule makes of the genes of `res` -- any of the eight rules of `_cabi` (protein tokens, base labels, gene
+        windows, k-mer counts, protein groups, protein sketches, protein clusters, start candidates) -- into the request's device tensors while the batch
         the finder called is resident (through the rule's `write`, the raw layer's marshalling); `per_contig`: what the rule needs of
         every contig, tables or lengths (`spec.per_contig`).  Leaves the rule's `Device*` result in `tok`."""
         genes = np.zeros(0, _cabi.GENE_DTYPE)
