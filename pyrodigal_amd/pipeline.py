@@ -2,75 +2,102 @@
 thread per context.  While one batch is in a host-side phase of its call (upload, chain planning, result unpacking)
 the other contexts' kernels run; batches come back in input order.
 
+One pool does this for every entry point (:func:`_in_order`): it hands the items of a lazy source to the contexts' threads, a
+bounded number ahead of the consumer, and yields the results in the order of the source.  :func:`find_genes_stream` runs lists
+of contigs through it, :func:`find_genes_fasta` and :func:`render_fasta` the batches of a file, each through the one step that
+makes a parsed batch resident (:func:`_resident`); contexts and readers belong to these functions, not to the pool.
+
 Measured on one MI355X with BASELINE config 3 batches (1000 x 50 kbp): 1 context 19.3 ms per batch (2.6 Gbp/s),
 2 contexts 15.0 ms per batch (3.3 Gbp/s)."""
+import contextlib
+import io
 import queue
 import threading
 
 from . import _cabi
 
 
-def find_genes_stream(batches, model_blobs, n_contexts=2, device=0, **find_kw):
-    """Yield ``(batch, BatchResult)`` for every batch of ``batches`` (an iterable of lists of contigs), in order.
+def _in_order(items, ctxs, work, ahead):
+    """Yield ``work(ctx, item)`` for every item of ``items``, in the order of ``items``, from one daemon thread per context of
+    ``ctxs``.  ``items`` is pulled lazily, never more than ``ahead`` items beyond the one the consumer waits for.
 
-    ``model_blobs``: the ``struct _training`` blobs to load in every context; ``find_kw`` goes to
-    ``Context.find_genes_batch`` (meta, closed, mask, ...).  At most ``2 * n_contexts`` batches are in flight."""
-    ctxs = [_cabi.Context(device) for _ in range(max(1, n_contexts))]
-    for c in ctxs:
-        c.set_models(list(model_blobs))
-    todo = queue.Queue(maxsize=len(ctxs))           # (index, batch) or None
-    done = {}
+    An exception of ``work`` is raised at its item's place in the order, after the results before it.  Once one is known nothing
+    more is pulled; what was pulled is still handed to ``work`` (which hands a file's arenas back).  However the generator ends
+    -- ``items`` exhausted, an exception of ``work`` or of ``items``, ``close()`` -- the threads are told to stop and joined
+    before control leaves.  Contexts and sources are the caller's: the pool neither configures nor closes them."""
+    ahead = max(1, ahead)                           # (with none ahead nothing would ever be pulled)
+    todo = queue.Queue()                            # (index, item), or None: stop
+    done, failed = {}, []
     cv = threading.Condition()
-    failure = []
 
     def worker(ctx):
-        while True:
-            item = todo.get()
-            if item is None:
-                return
-            i, batch = item
+        for i, item in iter(todo.get, None):
             try:
-                res = ctx.find_genes_batch(batch, **find_kw)
-            except BaseException as e:               # handed to the consumer, which re-raises it
+                res = work(ctx, item)
+            except BaseException as e:              # handed to the consumer, which raises it at place i
                 res = e
-                failure.append(e)
+                failed.append(e)
             with cv:
-                done[i] = (batch, res)
+                done[i] = res
                 cv.notify_all()
 
     threads = [threading.Thread(target=worker, args=(c,), daemon=True) for c in ctxs]
     for t in threads:
         t.start()
     try:
-        nxt, submitted = 0, 0
-        it = iter(batches)
+        it = iter(items)
+        nxt = pulled = 0
         exhausted = False
         while True:
-            while not exhausted and submitted - nxt < 2 * len(ctxs) and not failure:
+            while not exhausted and pulled - nxt < ahead and not failed:
                 try:
-                    b = next(it)
+                    item = next(it)
                 except StopIteration:
                     exhausted = True
                     break
-                todo.put((submitted, b))
-                submitted += 1
-            if nxt == submitted and exhausted:
-                break
+                todo.put((pulled, item))
+                pulled += 1
+            if nxt == pulled and exhausted:
+                return
             with cv:
                 while nxt not in done:
                     cv.wait()
-                batch, res = done.pop(nxt)
+                res = done.pop(nxt)
             nxt += 1
             if isinstance(res, BaseException):
                 raise res
-            yield batch, res
+            yield res
     finally:
         for _ in threads:
             todo.put(None)
         for t in threads:
             t.join()
-        for c in ctxs:
-            c.close()
+
+
+def _fresh_contexts(n_contexts, device, model_blobs):
+    """``n_contexts`` (at least one) new contexts on ``device`` with the models loaded; whoever makes them closes them."""
+    ctxs = [_cabi.Context(device) for _ in range(max(1, n_contexts))]
+    for c in ctxs:
+        c.set_models(list(model_blobs))
+    return ctxs
+
+
+def _close_all(ctxs):
+    for c in ctxs:
+        c.close()
+
+
+def find_genes_stream(batches, model_blobs, n_contexts=2, device=0, **find_kw):
+    """Yield ``(batch, BatchResult)`` for every batch of ``batches`` (an iterable of lists of contigs), in order.
+
+    ``model_blobs``: the ``struct _training`` blobs to load in every context; ``find_kw`` goes to
+    ``Context.find_genes_batch`` (meta, closed, mask, ...).  The batches go through the pool (:func:`_in_order`) on
+    ``n_contexts`` fresh contexts; at most ``2 * n_contexts`` batches are in flight."""
+    ctxs = _fresh_contexts(n_contexts, device, model_blobs)
+    try:
+        yield from _in_order(batches, ctxs, lambda ctx, batch: (batch, ctx.find_genes_batch(batch, **find_kw)), 2 * len(ctxs))
+    finally:
+        _close_all(ctxs)
 
 
 def _attach_masks(batch, ids, lens, regions_by_id, mask_lowercase, seen):
@@ -133,14 +160,58 @@ def header_says_circular(seq_id, description):
     return "circular=true" in d or "topology=circular" in d
 
 
+@contextlib.contextmanager
+def _resident(ctx, pb, circular, regions_by_id, mask_lowercase, seen, trim_option, seen_circular=None, keep_letters=False):
+    """One parsed batch of a file (``PackedRecords``) while it is resident on ``ctx``: uploaded (which hands its arena back to the
+    reader), its masks attached, its circular flags set and its terminal repeats trimmed.  Yields ``(batch to call, match, trim,
+    flags, letters)``: the first three as :func:`trim_terminal_repeats_of` returns them, then the circular flags of the batch to
+    call (None: no circle) and, with ``keep_letters`` and a record that is or may become a circle, a host copy of its letters
+    (read before the upload; a trimmed record is a circle of the bases it keeps).  On exit the trimmed copy, if there is one, and
+    the batch are closed; on any exception the arena goes back as well."""
+    try:
+        ids, n = pb.ids, pb.n
+        lens = [int(x) for x in pb.lens[:n]]
+        flags = circular_flags(circular, ids, pb.descriptions, seen_circular)
+        letters = None
+        if keep_letters and (flags is not None or trim_option is not None):
+            letters = [pb.sequence(k) for k in range(n)]
+        b = ctx.upload_packed(pb)                         # releases the arena
+        try:
+            _attach_masks(b, ids, lens, regions_by_id, mask_lowercase, seen)
+            b.set_circular(flags)
+            t, match, trim = trim_terminal_repeats_of(b, trim_option)
+            try:
+                if t is not b:
+                    flags = [bool(x) for x in t.circular[:n]]
+                    if letters is not None:
+                        letters = [s[:len(s) - int(x)] for s, x in zip(letters, trim)]
+                yield t, match, trim, flags, letters
+            finally:
+                if t is not b:
+                    t.close()
+        finally:
+            b.close()
+    except BaseException:
+        pb.release()
+        raise
+
+
+def _packed_in_order(reader, ctxs, work, max_bases, items_of=iter):
+    """The batches of ``reader`` through the pool: ``work(ctx, item)`` for every item of ``items_of(packed batches)``.  At most
+    ``len(ctxs) + 1`` batches are in flight, and the reader gets one pinned arena more than that, for the batch it is parsing."""
+    ahead = len(ctxs) + 1
+    return _in_order(items_of(reader.packed_batches(max_bases=max_bases, n_arenas=ahead + 1)), ctxs, work, ahead)
+
+
 def find_genes_fasta(path, model_blobs, n_contexts=2, device=0, max_bases=64 << 20, contexts=None, regions_by_id=None,
                      mask_lowercase=False, circular=None, trim_terminal_repeats=None, **find_kw):
     """Genes of every record of a (gzipped) FASTA file: yields ``(ids, descriptions, lengths, BatchResult)`` per batch, in file order.
 
     The reader (C, zlib) parses batch k + 1 into a pinned staging arena while batch k is uploaded from its own arena with one
-    DMA (no host-side packing) and processed; ``n_contexts`` contexts keep the device busy across batches
-    (ref: what the reference's CLI does with a thread pool over records, cli.py:287-302).  `contexts`: contexts the caller keeps
-    across files (models loaded, device buffers grown) instead of `n_contexts` fresh ones.
+    DMA (no host-side packing) and processed (:func:`_resident`); the pool (:func:`_in_order`) keeps the device busy across
+    batches on ``n_contexts`` contexts (ref: what the reference's CLI does with a thread pool over records, cli.py:287-302).
+    `contexts`: contexts the caller keeps across files (models loaded, device buffers grown) instead of `n_contexts` fresh ones;
+    they are left open.
 
     ``regions_by_id``: ``{sequence id: [(begin, end), ...]}``, masked regions (0-based, half-open) of the records with that id (the
     first word of the header); ``mask_lowercase``: runs of lower-case letters are masked (``Batch.set_masks``).
@@ -148,85 +219,22 @@ def find_genes_fasta(path, model_blobs, n_contexts=2, device=0, max_bases=64 << 
     length and ``BatchResult.cuts`` says where each was cut open.  ``trim_terminal_repeats``: ``True`` or a ``TerminalRepeats``: a
     record that ends in a copy of its first bases loses the copy on the device and is called as a circle
     (``BatchResult.terminal_repeats``: the bases each record lost; the yielded lengths are those of the file)."""
+    own = contexts is None
+    ctxs = _fresh_contexts(n_contexts, device, model_blobs) if own else list(contexts)
     seen = set()
-    trim_option = trim_terminal_repeats
-    own = contexts is None             # `contexts`: contexts the caller keeps across files (models loaded, buffers grown)
-    ctxs = [_cabi.Context(device) for _ in range(max(1, n_contexts))] if own else list(contexts)
-    if own:
-        for c in ctxs:
-            c.set_models(list(model_blobs))
-    todo = queue.Queue(maxsize=len(ctxs))
-    done, failure = {}, []
-    cv = threading.Condition()
 
-    def worker(ctx):
-        while True:
-            item = todo.get()
-            if item is None:
-                return
-            i, pb = item
-            try:
-                meta = (pb.ids, pb.descriptions, pb.lens)
-                lens = [int(x) for x in pb.lens[:pb.n]]
-                b = ctx.upload_packed(pb)                 # releases the arena
-                try:
-                    _attach_masks(b, meta[0], lens, regions_by_id, mask_lowercase, seen)
-                    b.set_circular(circular_flags(circular, meta[0], meta[1]))
-                    t, _, trim = trim_terminal_repeats_of(b, trim_option)
-                    try:
-                        r = ctx.find_genes(t, **find_kw)
-                    finally:
-                        if t is not b:
-                            t.close()
-                    r.terminal_repeats = trim
-                    res = (meta, r)
-                finally:
-                    b.close()
-            except BaseException as e:
-                pb.release()
-                res = e
-                failure.append(e)
-            with cv:
-                done[i] = res
-                cv.notify_all()
+    def work(ctx, pb):
+        with _resident(ctx, pb, circular, regions_by_id, mask_lowercase, seen, trim_terminal_repeats) as (t, _, trim, _, _):
+            r = ctx.find_genes(t, **find_kw)
+        r.terminal_repeats = trim
+        return pb.ids, pb.descriptions, pb.lens, r
 
-    threads = [threading.Thread(target=worker, args=(c,), daemon=True) for c in ctxs]
-    for t in threads:
-        t.start()
-    reader = _cabi.FastaReader(path)
     try:
-        nxt, submitted = 0, 0
-        it = reader.packed_batches(max_bases=max_bases, n_arenas=len(ctxs) + 2)
-        exhausted = False
-        while True:
-            while not exhausted and submitted - nxt < len(ctxs) + 1 and not failure:
-                try:
-                    pb = next(it)
-                except StopIteration:
-                    exhausted = True
-                    break
-                todo.put((submitted, pb))
-                submitted += 1
-            if nxt == submitted and exhausted:
-                break
-            with cv:
-                while nxt not in done:
-                    cv.wait()
-                res = done.pop(nxt)
-            nxt += 1
-            if isinstance(res, BaseException):
-                raise res
-            (ids, descs, lens), r = res
-            yield ids, descs, lens, r
+        with _cabi.FastaReader(path) as reader:
+            yield from _packed_in_order(reader, ctxs, work, max_bases)
     finally:
-        for _ in threads:
-            todo.put(None)
-        for t in threads:
-            t.join()
-        reader.close()
         if own:
-            for c in ctxs:
-                c.close()
+            _close_all(ctxs)
 
 
 def plan_set_calls(ids, lens, sets_by_id, max_bases):
@@ -258,53 +266,36 @@ def plan_set_calls(ids, lens, sets_by_id, max_bases):
 def _render_fasta_sets(path, ctxs, formats, sinks, stats, sets_by_id, *, max_bases, meta, descriptions, first_seqnum, unbinned_model,
                        regions_by_id, mask_lowercase, want_nodes, seen, find_kw):
     """:func:`render_fasta` with ``sets_by_id``: the file is read whole, the device calls are packed from whole sets
-    (:func:`plan_set_calls`), every call is rendered while it is resident, and the text is written in file order at the end."""
+    (:func:`plan_set_calls`) and go through the pool (:func:`_in_order`) all at once, every call is rendered while it is resident,
+    and the text is written in file order at the end.  When several calls fail, the first of them in call order is raised."""
     with _cabi.FastaReader(path) as reader:
         records = [rec for batch in reader.batches() for rec in batch]
     ids = [r[0] for r in records]
     lens = [len(r[2]) for r in records]
     labels, calls, unmatched = plan_set_calls(ids, lens, sets_by_id, max_bases)
     text = {name: [b""] * len(records) for name in formats}
-    todo = queue.Queue()
-    for call in calls:
-        todo.put(call)
-    failure = []
-    lock = threading.Lock()
 
-    def worker(ctx):
-        while not failure:
-            try:
-                call = todo.get_nowait()
-            except queue.Empty:
-                return
-            try:
-                b = ctx.upload([records[i][2] for i in call])
-                try:
-                    cids = [ids[i] for i in call]
-                    _attach_masks(b, cids, [lens[i] for i in call], regions_by_id, mask_lowercase, seen)
-                    b.set_sets([labels[i] for i in call])
-                    r = ctx.find_genes(b, meta=meta, want_nodes=want_nodes, **find_kw)
-                    out = ctx.render_genes(b, r, cids, formats, meta=meta, descriptions=descriptions, unbinned_model=unbinned_model,
-                                           seqnums=[first_seqnum + i for i in call])
-                finally:
-                    b.close()
-                with lock:
-                    for name, t in out.items():
-                        for k, i in enumerate(call):
-                            text[name][i] = t.contig(k)
-                        stats["fallback"] += t.fallback
-                        stats["kernel_ms"][name] += t.kernel_ms
-                    stats["genes"] += len(r.genes)
-            except BaseException as e:
-                failure.append(e)
+    def work(ctx, call):
+        b = ctx.upload([records[i][2] for i in call])
+        try:
+            cids = [ids[i] for i in call]
+            _attach_masks(b, cids, [lens[i] for i in call], regions_by_id, mask_lowercase, seen)
+            b.set_sets([labels[i] for i in call])
+            r = ctx.find_genes(b, meta=meta, want_nodes=want_nodes, **find_kw)
+            out = ctx.render_genes(b, r, cids, formats, meta=meta, descriptions=descriptions, unbinned_model=unbinned_model,
+                                   seqnums=[first_seqnum + i for i in call])
+        finally:
+            b.close()
+        return call, len(r.genes), out
 
-    threads = [threading.Thread(target=worker, args=(c,), daemon=True) for c in ctxs]
-    for t in threads:
-        t.start()
-    for t in threads:
-        t.join()
-    if failure:
-        raise failure[0]
+    with contextlib.closing(_in_order(calls, ctxs, work, len(calls))) as results:
+        for call, n_genes, out in results:
+            for name, t in out.items():
+                for k, i in enumerate(call):
+                    text[name][i] = t.contig(k)
+                stats["fallback"] += t.fallback
+                stats["kernel_ms"][name] += t.kernel_ms
+            stats["genes"] += n_genes
     for name in formats:
         for piece in text[name]:
             sinks[name].write(piece)
@@ -318,9 +309,7 @@ def _render_fasta_sets(path, ctxs, formats, sinks, stats, sets_by_id, *, max_bas
 def _host_genbank(ctx, result, ids, letters, flags, options, meta, first_seqnum):
     """The GenBank text of a batch that holds circular records, by the host writer (the device renderer does not write locations
     across the origin): one ``Genes.write_genbank`` per record."""
-    import io
-    from . import lib
-    from ._cabi import RenderedText
+    from . import lib                   # not at module level: the command line's --help does not load the Cython layer
     tinfs = {}
     out = io.StringIO()
     offs = [0]
@@ -337,7 +326,7 @@ def _host_genbank(ctx, result, ids, letters, flags, options, meta, first_seqnum)
                                         cut=int(result.cuts[i]) if circ else None)
         genes.write_genbank(out, ids[i], **options)
         offs.append(len(out.getvalue().encode("utf-8")))
-    return RenderedText(out.getvalue().encode("utf-8"), offs, 0, 0.0)
+    return _cabi.RenderedText(out.getvalue().encode("utf-8"), offs, 0, 0.0)
 
 
 def render_fasta(path, model_blobs, *, gff=None, faa=None, fna=None, gbk=None, scores=None, n_contexts=2, device=0, max_bases=64 << 20,
@@ -350,9 +339,10 @@ def render_fasta(path, model_blobs, *, gff=None, faa=None, fna=None, gbk=None, s
     record.  With ``scores`` the genes are found with ``want_nodes="device"``: the node arrays stay on the device for the
     renderer.
 
-    Runs like :func:`find_genes_fasta` (the C reader fills pinned arenas, ``n_contexts`` contexts side by side), but every batch
-    is rendered on the device while it is still resident (``Context.render_genes``) and only its text comes back: memory stays
-    bounded by the batch size.  Sequence ids are the first word of the headers, seqnums count records from ``first_seqnum``.
+    Runs like :func:`find_genes_fasta` (the C reader fills pinned arenas, the same pool over ``n_contexts`` fresh contexts, the
+    same resident step per batch), but every batch is rendered on the device while it is still resident
+    (``Context.render_genes``) and only its text comes back, to be written by the calling thread: memory stays bounded by the
+    batch size.Sequence ids are the first word of the headers, seqnums count records from ``first_seqnum``.
     ``*_options``: the writer's keyword arguments of that format; ``unbinned_model``: see ``Context.render_genes``; ``find_kw``
     goes to ``Context.find_genes``.  ``regions_by_id`` / ``mask_lowercase``: more mask sources, as :func:`find_genes_fasta` takes
     them.  ``circular``: the records that are circles (:func:`circular_flags`): called across the origin, ``topology=circular``
@@ -400,115 +390,53 @@ def render_fasta(path, model_blobs, *, gff=None, faa=None, fna=None, gbk=None, s
         import datetime
         formats["gbk"]["date"] = datetime.date.today()       # one date for the whole file
     want_nodes = "device" if scores is not None else False
-    ctxs = [_cabi.Context(device) for _ in range(max(1, n_contexts))]
-    for c in ctxs:
-        c.set_models(list(model_blobs))
-    if sets_by_id is not None:
-        try:
+    ctxs = _fresh_contexts(n_contexts, device, model_blobs)
+    try:
+        if sets_by_id is not None:
             return _render_fasta_sets(path, ctxs, formats, sinks, stats, dict(sets_by_id), max_bases=max_bases, meta=meta,
                                       descriptions=descriptions, first_seqnum=first_seqnum, unbinned_model=unbinned_model,
                                       regions_by_id=regions_by_id, mask_lowercase=mask_lowercase, want_nodes=want_nodes, seen=seen,
                                       find_kw=find_kw)
-        finally:
-            for c in ctxs:
-                c.close()
-    todo = queue.Queue(maxsize=len(ctxs))
-    done, failure = {}, []
-    cv = threading.Condition()
 
-    def worker(ctx):
-        while True:
-            item = todo.get()
-            if item is None:
-                return
-            i, seqnum, pb = item
-            try:
-                ids, n, total = pb.ids, pb.n, pb.total
-                lens = [int(x) for x in pb.lens[:pb.n]]
-                flags = circular_flags(circular, ids, pb.descriptions, seen_circular)
-                host_gbk = (flags is not None or trim_option is not None) and "gbk" in formats
-                letters = [pb.sequence(k) for k in range(n)] if host_gbk else None     # (the arena is released by the upload)
-                b = ctx.upload_packed(pb)                 # releases the arena
-                found = None
-                try:
-                    _attach_masks(b, ids, lens, regions_by_id, mask_lowercase, seen)
-                    b.set_circular(flags)
-                    t, match, trim = trim_terminal_repeats_of(b, trim_option)
-                    try:
-                        if match is not None:
-                            found = [(ids[k], lens[k], int(match[k]), int(trim[k])) for k in range(n)]
-                        if t is not b:                    # a trimmed record is a circle of the bases it keeps
-                            flags = [bool(x) for x in t.circular[:n]]
-                            if letters is not None:
-                                letters = [s[:len(s) - int(x)] for s, x in zip(letters, trim)]
-                        host_gbk = host_gbk and flags is not None
-                        r = ctx.find_genes(t, meta=meta, want_nodes=want_nodes, **find_kw)
-                        dev_formats = {k: v for k, v in formats.items() if not (host_gbk and k == "gbk")}
-                        text = {}
-                        if dev_formats:
-                            text = ctx.render_genes(t, r, ids, dev_formats, meta=meta, descriptions=descriptions, first_seqnum=seqnum,
-                                                    unbinned_model=unbinned_model)
-                        if host_gbk:
-                            text["gbk"] = _host_genbank(ctx, r, ids, letters, flags, formats["gbk"], meta, seqnum)
-                    finally:
-                        if t is not b:
-                            t.close()
-                finally:
-                    b.close()
-                res = (n, total, len(r.genes), text, found)
-            except BaseException as e:
-                pb.release()
-                res = e
-                failure.append(e)
-            with cv:
-                done[i] = res
-                cv.notify_all()
-
-    threads = [threading.Thread(target=worker, args=(c,), daemon=True) for c in ctxs]
-    for t in threads:
-        t.start()
-    reader = _cabi.FastaReader(path)
-    try:
-        nxt, submitted, seqnum = 0, 0, first_seqnum
-        it = reader.packed_batches(max_bases=max_bases, n_arenas=len(ctxs) + 2)
-        exhausted = False
-        while True:
-            while not exhausted and submitted - nxt < len(ctxs) + 1 and not failure:
-                try:
-                    pb = next(it)
-                except StopIteration:
-                    exhausted = True
-                    break
-                todo.put((submitted, seqnum, pb))
+        def numbered(batches):              # (seqnum of its first record, batch)
+            seqnum = first_seqnum
+            for pb in batches:
+                yield seqnum, pb
                 seqnum += pb.n
-                submitted += 1
-            if nxt == submitted and exhausted:
-                break
-            with cv:
-                while nxt not in done:
-                    cv.wait()
-                res = done.pop(nxt)
-            nxt += 1
-            if isinstance(res, BaseException):
-                raise res
-            n, total, n_genes, text, found = res
-            if found is not None:
-                stats["terminal_repeat_records"].extend(found)
-                stats["terminal_repeats"].extend(x for x in found if x[2] > 0)
-            for name, t in text.items():
-                sinks[name].write(t.data)
-                stats["fallback"] += t.fallback
-                stats["kernel_ms"][name] += t.kernel_ms
-            stats["records"] += n; stats["bases"] += total; stats["genes"] += n_genes
+
+        def work(ctx, item):
+            seqnum, pb = item
+            ids, n = pb.ids, pb.n
+            lens = [int(x) for x in pb.lens[:n]]
+            with _resident(ctx, pb, circular, regions_by_id, mask_lowercase, seen, trim_option, seen_circular,
+                           keep_letters="gbk" in formats) as (t, match, trim, flags, letters):
+                found = None
+                if match is not None:
+                    found = [(ids[k], lens[k], int(match[k]), int(trim[k])) for k in range(n)]
+                host_gbk = "gbk" in formats and flags is not None
+                r = ctx.find_genes(t, meta=meta, want_nodes=want_nodes, **find_kw)
+                dev_formats = {k: v for k, v in formats.items() if not (host_gbk and k == "gbk")}
+                text = {}
+                if dev_formats:
+                    text = ctx.render_genes(t, r, ids, dev_formats, meta=meta, descriptions=descriptions, first_seqnum=seqnum,
+                                            unbinned_model=unbinned_model)
+                if host_gbk:
+                    text["gbk"] = _host_genbank(ctx, r, ids, letters, flags, formats["gbk"], meta, seqnum)
+            return n, pb.total, len(r.genes), text, found
+
+        with _cabi.FastaReader(path) as reader, contextlib.closing(_packed_in_order(reader, ctxs, work, max_bases, numbered)) as results:
+            for n, total, n_genes, text, found in results:
+                if found is not None:
+                    stats["terminal_repeat_records"].extend(found)
+                    stats["terminal_repeats"].extend(x for x in found if x[2] > 0)
+                for name, t in text.items():
+                    sinks[name].write(t.data)
+                    stats["fallback"] += t.fallback
+                    stats["kernel_ms"][name] += t.kernel_ms
+                stats["records"] += n; stats["bases"] += total; stats["genes"] += n_genes
         stats["regions_unmatched"] = sorted(set(regions_by_id or ()) - seen)
         listed = circular if circular is not None and not isinstance(circular, bool) and not callable(circular) else ()
         stats["circular_unmatched"] = sorted(set(listed) - seen_circular)
         return stats
     finally:
-        for _ in threads:
-            todo.put(None)
-        for t in threads:
-            t.join()
-        reader.close()
-        for c in ctxs:
-            c.close()
+        _close_all(ctxs)
