@@ -2,7 +2,7 @@
 // Pass 1 is the ordinary call on the whole batch; its gene records stay on the device and only say where NOT to cut: the widest
 // stretch no gene covers, in the middle half of the record.  Pass 2 calls the contig rotated to start at that cut, closed; its records
 // are mapped back to the record's coordinates (a gene across the origin ends beyond the contig's length) and spliced, on the device,
-// into the records pass 1 found for the linear contigs of the batch.  Included by finder.hip behind find_impl_cov.
+// into the records pass 1 found for the linear contigs of the batch.  Included by finder.hip behind find_impl.
 
 // ---- the cut rule (host arithmetic; the device kernels below implement the same order) ------------------------------------------
 // a gap [gb, gb + w) of a contig of L bases; mid = gb + w / 2 (= (gb + ge) / 2)
@@ -287,7 +287,7 @@ static int find_circular(pga_ctx* c, const pga_batch* batch, const pga_params* p
     // pass 1: the ordinary call; the records stay where they are
     GeneKeep k1{"d_genes_pass1"};
     pga_result* r1 = nullptr;
-    int rc = find_impl_cov(c, batch, pp, 0, 0, &r1, model_of_contig, nullptr, nullptr, &k1);
+    int rc = find_impl(c, batch, pp, 0, 0, &r1, model_of_contig, nullptr, nullptr, &k1);
     if (rc) return rc;
     ResultOwner* R1 = reinterpret_cast<ResultOwner*>(r1);
     struct Guard { ResultOwner* r; ~Guard() { delete r; } } guard1{R1}, guard2{nullptr};
@@ -377,7 +377,7 @@ static int find_circular(pga_ctx* c, const pga_batch* batch, const pga_params* p
         P2.closed = 1;
         if (model_of_contig) for (int j = 0; j < NR; j++) moc2.push_back(model_of_contig[circ[j]]);
         pga_result* r2 = nullptr;
-        rc = find_impl_cov(c, b2, &P2, 0, 0, &r2, model_of_contig ? moc2.data() : nullptr, nullptr, nullptr, &k2);
+        rc = find_impl(c, b2, &P2, 0, 0, &r2, model_of_contig ? moc2.data() : nullptr, nullptr, nullptr, &k2);
         if (rc) return rc;
         R2 = reinterpret_cast<ResultOwner*>(r2);
         guard2.r = R2;

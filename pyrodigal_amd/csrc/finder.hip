@@ -9,6 +9,7 @@
 #include "pipeline.h"
 #include "dpw_core.h"
 #include "dev_common.h"
+#include "find_plan.h"
 
 #include <math.h>
 #include <stdio.h>
@@ -262,8 +263,10 @@ int ensure_pin(pga_ctx* c, const char* name, size_t bytes, void** out, bool fp =
     *out = b.p;
     return PGA_OK;
 }
-#define DEVBUF(var, type, name, count) type* var; { void* p__; int rc__ = ensure_dev(c, name, sizeof(type) * (size_t)(count) + 64, &p__, std::is_floating_point<type>::value); if (rc__) return rc__; var = (type*)p__; }
-#define PINBUF(var, type, name, count) type* var; { void* p__; int rc__ = ensure_pin(c, name, sizeof(type) * (size_t)(count) + 64, &p__, std::is_floating_point<type>::value); if (rc__) return rc__; var = (type*)p__; }
+#define DEVBUF(var, type, name, count) type* var; DEVSET(var, type, name, count)
+#define DEVSET(var, type, name, count) { void* p__; int rc__ = ensure_dev(c, name, sizeof(type) * (size_t)(count) + 64, &p__, std::is_floating_point<type>::value); if (rc__) return rc__; var = (type*)p__; }
+#define PINSET(var, type, name, count) { void* p__; int rc__ = ensure_pin(c, name, sizeof(type) * (size_t)(count) + 64, &p__, std::is_floating_point<type>::value); if (rc__) return rc__; var = (type*)p__; }
+#define PINBUF(var, type, name, count) type* var; PINSET(var, type, name, count)
 
 // ---- tail: nodes of one contig for its winning model (device functions; one thread walks a contig's path) ----
 struct NodeView {
@@ -1544,35 +1547,124 @@ static int fetch_mask_union(pga_ctx* c, ResultOwner* R, const int32_t* h_moff, c
     return PGA_OK;
 }
 
-// stage 0 = the whole path; PGA_STAGE_* = stop after that stage and return the node arrays (single chain per
-// contig scored with model 0; P.meta then only selects the meta-mode start penalties of Nodes.score)
-// model_of_contig (single mode: the path and the SCORE / OVERLAP stages; nullptr = model 0 everywhere): contig i is scored with that
-// loaded model, its nodes extracted under that model's translation table -- the groups of meta mode, one chain per contig.
-// tt_of_contig (EXTRACT stage; nullptr = tt_override everywhere): contig i is extracted under that table.  At most 4 tables.
-// coding (stage 0, single mode; nullptr otherwise): coding[i] = bases of contig i inside at least one of its genes, counted where the
-// gene records are (pga_find_coding_bases); the records are then not copied back and the result holds no genes.
-// keep (stage 0; nullptr otherwise): a pass of a circular call (circular.inl) -- the gene records stay on the device, in the buffer
-// `keep->buf`, and the result holds none; `keep` reports where they are (nothing when the call found no node at all).
+// where a pass of a circular call (circular.inl) leaves its gene records on the device: find_impl's `keep`
 struct GeneKeep { const char* buf; pga_gene* d_genes = nullptr; int64_t n_genes = 0; };
-static int find_impl_cov(pga_ctx* c, const pga_batch* batch, const pga_params* pp, const int stage, const int tt_override, pga_result** out,
-                         const int32_t* model_of_contig, const int32_t* tt_of_contig, int64_t* coding, GeneKeep* keep = nullptr) {
+namespace {
+
+// a per-group device buffer: `base` with the group's number behind it
+int group_dev(pga_ctx* c, const char* base, const int g, const size_t bytes, void** out, const bool fp = false) {
+    char nm[32];
+    snprintf(nm, sizeof nm, "%s%d", base, g);
+    return ensure_dev(c, nm, bytes, out, fp);
+}
+#define GROUPBUF(dst, ptr_type, base, bytes, fp) { void* p__; int rc__ = group_dev(c, base, g, bytes, &p__, fp); if (rc__) return rc__; dst = (ptr_type)p__; }
+#define GBUF(field, type, count) GROUPBUF(ga[g].field, type*, #field, sizeof(type) * (size_t)(count) + 64, std::is_floating_point<type>::value)
+
+struct TailBufs;
+// the per-tile counts and offsets of one group's extraction (nodes, stop nodes)
+struct GroupTiles { int32_t* count; int32_t* off; int32_t* scount; int32_t* soff; };
+
+// The state of one finder call: what more than one phase of find_impl reads.  The phases are its member functions, called in order;
+// what only one phase needs is a local of that phase.  The vectors that uploads on the stream read live here, so they outlive it.
+struct FindCall : pga_plan::ChainPlan, pga_plan::RescorePlan, pga_plan::GatherPlan<WinDesc> {
+    // ---- inputs and mode flags (check_call)
+    pga_ctx* c = nullptr; FinderState* f = nullptr; hipStream_t st = nullptr;
+    const pga_batch* batch = nullptr; pga_params P{};
+    int stage = 0, tt_override = 0;
+    const int32_t* model_of_contig = nullptr; const int32_t* tt_of_contig = nullptr; int64_t* coding = nullptr; GeneKeep* keep = nullptr;
+    bool meta_run = false, use_sets = false, per_contig = false, multi = false, mask_union = false;
+    int NC = 0, NM = 0, NG = 0, NS = 0; int64_t total = 0;
+    std::vector<int> cgrp, gtt;             // a translation-table group per contig, the table of every group (multi)
+    std::vector<int32_t> set_of;            // contig sets: dense ids
+    ResultOwner* R = nullptr;               // the call's until publish_result hands it over
+    StageTimer* tm = nullptr;
+    // ---- sequence, masks, extraction: device views and what the extraction read back
+    uint8_t* d_dig = nullptr; ContigDesc* d_ct = nullptr; int32_t* d_p16 = nullptr;
+    int32_t* d_xa = nullptr; int32_t* h_xa = nullptr; size_t xa_words = 0;
+    int32_t* d_cnt = nullptr; int32_t* h_cnt = nullptr; int32_t* d_cbase = nullptr; int32_t* h_cbase = nullptr;
+    int32_t* d_sbase = nullptr; int32_t* h_sbase = nullptr; uint8_t* d_enabled = nullptr; uint8_t* h_enabled = nullptr;
+    int32_t* d_tile_first = nullptr; int32_t* d_tile_last = nullptr; GroupTiles d_tile{};
+    GroupArrays ga[4];
+    MaskList masks{nullptr, nullptr}; int32_t* h_moff = nullptr; const int2* d_union_iv = nullptr;
+    int64_t group_nodes[4] = {0, 0, 0, 0};
+    // ---- the plan of the connection scoring (the chains themselves: ChainPlan)
+    int NCH = 0;
+    bool use_wave = false, seg_wave = false, wave_prep = false, use_sched = false, segmented = false, lean_gather = false, direct_gather = false;
+    DpSegPlan seg_plan; DpSegDev seg_dev{}; int64_t dp_slots = 0;
+    std::vector<int32_t> h_bbase, dp_order;
+    int max_batches[4] = {0, 0, 0, 0};
+    ChainArrays ca{}; DpBuffers dp{}; DpwGroupPtrs wgroups{}; DpwBuffers wbuf{};
+    double* h_maxscore = nullptr; int32_t* h_maxidx = nullptr; int32_t* h_ipath = nullptr; uint32_t* h_scur = nullptr;
+    // ---- the call plan on the device (upload_plan) and its pinned mirror
+    std::vector<int64_t> ovl_blk0;
+    uint8_t* d_conv = nullptr; uint8_t* h_conv = nullptr; int2* d_cc = nullptr; int2* h_cc = nullptr; int32_t* d_bbase = nullptr;
+    int32_t* d_dp_order = nullptr; ChainDesc* d_chains = nullptr; const int32_t* d_ovl_blk = nullptr;
+    // ---- scoring
+    std::vector<int32_t> cs_tk[4], cs_en[4];    // alive until the stream is synchronized
+    ScoreParams sp{};
+    // ---- winners (their plans: RescorePlan, GatherPlan), the gathered arena and its pinned mirror, the tail
+    std::vector<int> win_chain;
+    OutArrays o{}, h{}; size_t arena_dp = 0, arena_all = 0; int max_n = 0;      // max_n: nodes of the longest winner
+    std::vector<int32_t> tracef; std::vector<uint8_t> elim;
+    std::vector<TailDesc> tdv; std::vector<TpSeg> segs;
+
+    ~FindCall() { delete R; }
+
+    // group g's node and stop-node offsets per contig (NC + 1 entries), on the host and on the device
+    const int32_t* h_cb(const int g) const { return h_cbase + (size_t)g * (NC + 1); }
+    const int32_t* h_sb(const int g) const { return h_sbase + (size_t)g * (NC + 1); }
+    int32_t* d_cb(const int g) const { return d_cbase + (size_t)g * (NC + 1); }
+    int32_t* d_sb(const int g) const { return d_sbase + (size_t)g * (NC + 1); }
+    int contig_nodes(const int g, const int i) const { return h_cb(g)[i + 1] - h_cb(g)[i]; }
+    int group_stops(const int g) const { return h_sb(g)[NC]; }
+    GroupTiles tiles(const int g) const {
+        const size_t at = (size_t)g * (batch->n_tiles + 1);
+        return GroupTiles{d_tile.count + at, d_tile.off + at, d_tile.scount + at, d_tile.soff + at};
+    }
+    // does group g have chains, and nodes in them?
+    bool group_has_work(const int g) const { return g_c0[g + 1] > g_c0[g] && g_n0[g + 1] > g_n0[g]; }
+
+    void contig_counts() {      // the contigs' GC content and unknown bases into the result
+        for (int i = 0; i < NC; i++) { R->contigs[i].gc = batch->ct[i].len > 0 ? (double)h_cnt[i] / (double)batch->ct[i].len : 0.0; R->contigs[i].n_unknown = h_cnt[NC + i]; }
+    }
+    int sync() { HT(c, hipGetLastError()); HT(c, hipStreamSynchronize(st)); return PGA_OK; }      // what the launches left, then the stream
+    int stop_clock() {       // the call's device time: e_start (run_sequence_and_masks) to here, waited for
+        HT(c, hipEventRecord(f->e_stop, st));
+        if (const int rc = sync()) return rc;
+        float ms = 0; HT(c, hipEventElapsedTime(&ms, f->e_start, f->e_stop)); R->pub.t_total_ms = ms;
+        return PGA_OK;
+    }
+    int publish_result(pga_result** out) { ResultOwner* const r = R; return publish(r, R, P, out); }
+
+    // the phases, in the order find_impl calls them
+    int check_call(pga_ctx* c_, const pga_batch* batch_, const pga_params* pp, pga_result** out);
+    int run_sequence_and_masks(); int return_sequence_stage(pga_result** out); int run_extract(); int place_nodes(); int plan_chains();
+    int plan_connection_scoring(); int prepare_wave(int64_t dp_cap); void order_starts(); int upload_plan(); int score_groups();
+    int return_stage_nodes(pga_result** out); int score_connections(); void pick_winners(); int rescore_winners(); int gather_winners();
+    int64_t contig_results(const int32_t* n_genes, int64_t* gene_begin);
+    int run_host_tail(); int run_device_tail(bool par_tail); int launch_tail_paths(const TailBufs& t); int launch_tail_tweaks(TailBufs& t);
+    int copy_out_nodes(); void keep_device_nodes();
+};
+
+// the argument checks, the translation-table groups, the dense set ids, the result
+int FindCall::check_call(pga_ctx* c_, const pga_batch* batch_, const pga_params* pp, pga_result** out) {
+    c = c_; batch = batch_;
     if (out) *out = nullptr;
     if (c) c->dev_nodes.clear();        // this call reuses the arena the last one kept on the device
     if (!c || !out || !pp || !batch || batch->ctx != c) {
         if (c) c->err = "pga_find_genes: bad arguments";
         return PGA_EINVAL;
     }
-    const int32_t n_contigs = batch->n;
     if (!c->finder) { int rc0 = pga_finder_models_changed(c); if (rc0) return rc0; }
-    const bool meta_run = pp->meta && stage == 0;
-    const bool use_sets = meta_run && !batch->sets.empty();      // one GC window and one model per set of contigs
-    const bool per_contig = model_of_contig != nullptr && !pp->meta && stage != PGA_STAGE_EXTRACT && stage != PGA_STAGE_SEQUENCE;
+    meta_run = pp->meta && stage == 0;
+    use_sets = meta_run && !batch->sets.empty();      // one GC window and one model per set of contigs
+    per_contig = model_of_contig != nullptr && !pp->meta && stage != PGA_STAGE_EXTRACT && stage != PGA_STAGE_SEQUENCE;
     const bool per_contig_tt = tt_of_contig != nullptr && stage == PGA_STAGE_EXTRACT;
     // meta mode over an empty bin collection is legal and finds nothing (ref: tests/test_gene_finder.py:316-324)
     if (c->n_models <= 0 && !meta_run && stage != PGA_STAGE_EXTRACT && stage != PGA_STAGE_SEQUENCE) { c->err = "pga_find_genes: no model loaded (call pga_set_models first)"; return PGA_EINVAL; }
-    const pga_params P = *pp;
+    P = *pp;
     // the caller's intervals and runs of lower-case letters (pga_batch_set_regions / _set_mask_case) join the runs of unknown bases
-    const bool mask_union = batch->mask_case != 0 || !batch->regions.empty();
+    mask_union = batch->mask_case != 0 || !batch->regions.empty();
     if ((P.mask || batch->mask_case) && P.min_mask < 0) { c->err = "pga_find_genes: min_mask must be positive"; return PGA_EINVAL; }   // ref: lib.pyx:5175-5176
     if (!P.closed && P.min_edge_gene > 0 && P.min_edge_gene < 4) {
         // with open ends and min_edge_gene <= 3 the reference emits a start node AND the virtual edge stop node at the same
@@ -1585,1238 +1677,1140 @@ static int find_impl_cov(pga_ctx* c, const pga_batch* batch, const pga_params* p
         return PGA_EINVAL;
     }
     HT(c, hipSetDevice(c->device));
-    FinderState* f = c->finder;
-    hipStream_t st = c->stream;
+    f = c->finder;
+    st = c->stream;
+    NC = batch->n;
     // a translation-table group per contig (per_contig: its model's group; per_contig_tt: a group per distinct table of the call)
-    const bool multi = per_contig || per_contig_tt;
-    std::vector<int> cgrp, gtt;
+    multi = per_contig || per_contig_tt;
     if (per_contig) {
         gtt = f->group_tt;
-        for (int i = 0; i < n_contigs; i++) cgrp.push_back(f->model_group[model_of_contig[i]]);
+        for (int i = 0; i < NC; i++) cgrp.push_back(f->model_group[model_of_contig[i]]);
     } else if (per_contig_tt) {
-        for (int i = 0; i < n_contigs; i++) {
+        for (int i = 0; i < NC; i++) {
             int g = (int)(std::find(gtt.begin(), gtt.end(), tt_of_contig[i]) - gtt.begin());
             if (g == (int)gtt.size()) gtt.push_back(tt_of_contig[i]);
             cgrp.push_back(g);
         }
     }
-    const int NC = n_contigs, NM = c->n_models, NG = meta_run ? (int)f->group_tt.size() : (multi ? std::max(1, (int)gtt.size()) : 1);
+    NM = c->n_models; NG = meta_run ? (int)f->group_tt.size() : (multi ? std::max(1, (int)gtt.size()) : 1);
     if (NG > 4) { c->err = "pga_find_genes: more than 4 distinct translation tables loaded"; return PGA_EINVAL; }
     if (const char* fault = getenv("PGA_FAULT_CONTIG_LEN")) {
         // diagnostics: a call that carries a contig of exactly this many bases fails (the host layer's error paths under test)
         const long fl = atol(fault);
         for (int i = 0; i < NC; i++) if ((long)batch->ct[i].len == fl) { c->err = "pga_find_genes: fault injected by PGA_FAULT_CONTIG_LEN"; return PGA_EDEVICE; }
     }
-
-    // contig sets: dense ids in order of first appearance, a contig without a label a set of its own
-    std::vector<int32_t> set_of;
-    int NS = 0;
     if (use_sets) {
-        set_of.resize((size_t)NC);
-        std::unordered_map<int32_t, int32_t> dense;
-        for (int i = 0; i < NC; i++) {
-            const int32_t lab = batch->sets[(size_t)i];
-            if (lab < 0) { set_of[(size_t)i] = NS++; continue; }
-            auto it = dense.find(lab);
-            if (it == dense.end()) it = dense.emplace(lab, NS++).first;
-            set_of[(size_t)i] = it->second;
-        }
+        NS = pga_plan::dense_set_ids(batch->sets.data(), NC, set_of);
         c->set_model.assign((size_t)NC, -1);
         c->set_score.assign((size_t)NC, std::numeric_limits<double>::quiet_NaN());
         c->model_scores.assign((size_t)NC * (size_t)NM, std::numeric_limits<double>::quiet_NaN());
         c->model_scores_nm = NM;
     }
-
-    ResultOwner* R = new (std::nothrow) ResultOwner();
+    R = new (std::nothrow) ResultOwner();
     if (!R) return PGA_ENOMEM;
-    struct Guard { ResultOwner* r; ~Guard() { delete r; } } guard{R};
     R->contigs.assign(NC, pga_contig_result{-1, 0, 0, 0, 0, 0.0, 0.0});
     R->mask_off.assign(NC + 1, 0);
     R->has_masks = P.mask || mask_union;
     memset(&R->pub, 0, sizeof R->pub);
     R->pub.n_contigs = NC;
+    total = batch->total;
+    return PGA_OK;
+}
 
-    const std::vector<ContigDesc>& ct = batch->ct;
-    const int64_t total = batch->total;
-    StageTimer tm;
+// digitize, the GC prefix, and both mask paths
+int FindCall::run_sequence_and_masks() {
+    const char* d_seq = batch->d_seq;
+    DEVSET(d_dig, uint8_t, "d_dig", total + 16);
+    DEVSET(d_ct, ContigDesc, "d_ct", NC + 1);
+    // What the host reads back after the extraction -- the staging-overflow flag, the contigs' GC / unknown counts, the node and stop-node
+    // offsets of every group, the groups a contig is extracted under -- sits in ONE device allocation and ONE pinned one with the same
+    // layout: one read-back instead of five, one memset instead of two (round 6: a lone 20 kbp call was 56 launches, 31 of them the
+    // runtime's own copy and fill kernels).  Word 0 is the overflow flag.
+    const size_t xa_cnt = 4, xa_cbase = xa_cnt + 2 * (size_t)NC, xa_sbase = xa_cbase + (size_t)NG * (NC + 1), xa_en = xa_sbase + (size_t)NG * (NC + 1);
+    xa_words = xa_en + ((size_t)NG * NC + 3) / 4 + 1;
+    DEVSET(d_xa, int32_t, "d_extract_info", xa_words);
+    PINSET(h_xa, int32_t, "h_extract_info", xa_words);
+    d_cnt = d_xa + xa_cnt; h_cnt = h_xa + xa_cnt;
+    const int64_t gc_blocks = pga_gc_blocks(total);
+    DEVSET(d_p16, int32_t, "d_gc_p16", total / 16 + 2);
+    DEVBUF(d_gc_bsum, int32_t, "d_gc_bsum", gc_blocks + 1);
+    DEVBUF(d_gc_boff, int32_t, "d_gc_boff", gc_blocks + 1);
+    d_cbase = d_xa + xa_cbase; h_cbase = h_xa + xa_cbase;
+    DEVSET(d_tile_first, int32_t, "d_tile_first", (size_t)6 * batch->n_tiles);
+    DEVSET(d_tile_last, int32_t, "d_tile_last", (size_t)6 * batch->n_tiles);
+    DEVSET(d_tile.count, int32_t, "d_tile_count", (size_t)NG * (batch->n_tiles + 1));
+    DEVSET(d_tile.off, int32_t, "d_tile_off", (size_t)NG * (batch->n_tiles + 1));
+    DEVSET(d_tile.scount, int32_t, "d_tile_scount", (size_t)NG * (batch->n_tiles + 1));
+    DEVSET(d_tile.soff, int32_t, "d_tile_soff", (size_t)NG * (batch->n_tiles + 1));
+    d_sbase = d_xa + xa_sbase; h_sbase = h_xa + xa_sbase;
+    d_enabled = (uint8_t*)(d_xa + xa_en); h_enabled = (uint8_t*)(h_xa + xa_en);
 
-    if (NC > 0 && total > 0) {
-        const char* d_seq = batch->d_seq;
-        DEVBUF(d_dig, uint8_t, "d_dig", total + 16);
-        DEVBUF(d_ct, ContigDesc, "d_ct", NC + 1);
-        // What the host reads back after the extraction -- the staging-overflow flag, the contigs' GC / unknown counts, the node and stop-node
-        // offsets of every group, the groups a contig is extracted under -- sits in ONE device allocation and ONE pinned one with the same
-        // layout: one read-back instead of five, one memset instead of two (round 6: a lone 20 kbp call was 56 launches, 31 of them the
-        // runtime's own copy and fill kernels).
-        const size_t xa_cnt = 4, xa_cbase = xa_cnt + 2 * (size_t)NC, xa_sbase = xa_cbase + (size_t)NG * (NC + 1), xa_en = xa_sbase + (size_t)NG * (NC + 1);
-        const size_t xa_words = xa_en + ((size_t)NG * NC + 3) / 4 + 1;
-        DEVBUF(d_xa, int32_t, "d_extract_info", xa_words);
-        PINBUF(h_xa, int32_t, "h_extract_info", xa_words);
-        int32_t* const d_st_overflow = d_xa; int32_t* const h_st_overflow = h_xa;
-        int32_t* const d_cnt = d_xa + xa_cnt; int32_t* const h_cnt = h_xa + xa_cnt;
-        const int64_t gc_blocks = pga_gc_blocks(total);
-        DEVBUF(d_p16, int32_t, "d_gc_p16", total / 16 + 2);
-        DEVBUF(d_gc_bsum, int32_t, "d_gc_bsum", gc_blocks + 1);
-        DEVBUF(d_gc_boff, int32_t, "d_gc_boff", gc_blocks + 1);
-        int32_t* const d_cbase = d_xa + xa_cbase; int32_t* const h_cbase = h_xa + xa_cbase;
-        DEVBUF(d_tile_first, int32_t, "d_tile_first", (size_t)6 * batch->n_tiles);
-        DEVBUF(d_tile_last, int32_t, "d_tile_last", (size_t)6 * batch->n_tiles);
-        DEVBUF(d_tile_count, int32_t, "d_tile_count", (size_t)NG * (batch->n_tiles + 1));
-        DEVBUF(d_tile_off, int32_t, "d_tile_off", (size_t)NG * (batch->n_tiles + 1));
-        DEVBUF(d_tile_scount, int32_t, "d_tile_scount", (size_t)NG * (batch->n_tiles + 1));
-        DEVBUF(d_tile_soff, int32_t, "d_tile_soff", (size_t)NG * (batch->n_tiles + 1));
-        int32_t* const d_sbase = d_xa + xa_sbase; int32_t* const h_sbase = h_xa + xa_sbase;
-        uint8_t* const d_enabled = (uint8_t*)(d_xa + xa_en); uint8_t* const h_enabled = (uint8_t*)(h_xa + xa_en);
+    for (int g = 0; g < NG; g++) {
+        GBUF(df, uint8_t, total + 16)
+        GBUF(c16, int32_t, (size_t)batch->n_tiles * 192 + 2)
+        ga[g].tile0 = batch->d_tile0;
+        ga[g].ndx = nullptr; ga[g].stop_val = nullptr; ga[g].type = nullptr; ga[g].strand = nullptr; ga[g].edge0 = nullptr; ga[g].gc_cont = nullptr;
+    }
 
-        GroupArrays ga[4];
-        for (int g = 0; g < NG; g++) {
-            char nm[32];
-#define GBUF(field, type, count) { snprintf(nm, sizeof nm, #field "%d", g); void* p__; int rc__ = ensure_dev(c, nm, sizeof(type) * (size_t)(count) + 64, &p__, std::is_floating_point<type>::value); if (rc__) return rc__; ga[g].field = (type*)p__; }
-            GBUF(df, uint8_t, total + 16)
-            GBUF(c16, int32_t, (size_t)batch->n_tiles * 192 + 2)
-            ga[g].tile0 = batch->d_tile0;
-            ga[g].ndx = nullptr; ga[g].stop_val = nullptr; ga[g].type = nullptr; ga[g].strand = nullptr; ga[g].edge0 = nullptr; ga[g].gc_cont = nullptr;
-        }
-
-        HT(c, hipEventRecord(f->e_start, st));
-        HT(c, hipMemcpyAsync(d_ct, ct.data(), sizeof(ContigDesc) * (NC + 1), hipMemcpyHostToDevice, st));
-        HT(c, hipMemsetAsync(d_xa, 0, sizeof(int32_t) * xa_cbase, st));          // the overflow flag and the counts
-        pga_launch_digitize(d_seq, d_dig, total, d_ct, NC, d_cnt, d_cnt + NC, st);
-        pga_launch_gc_prefix(d_dig, total, d_gc_bsum, d_gc_boff, d_p16, st);
-        MaskList masks{nullptr, nullptr};
-        int32_t* h_moff = nullptr; const int2* d_union_iv = nullptr;
-        if (mask_union) {
-            // Several sources: their union per contig is built on the device (pga_launch_mask_union) and the extraction is launched behind
-            // it without a word from the host.  The list comes back for pga_result.masks with the extraction's own read-back.
-            const int64_t per_source = total / std::max(1, P.min_mask) + NC + 1;       // qualifying runs of one kind
-            const int64_t most = std::min<int64_t>((P.mask ? per_source : 0) + (batch->mask_case ? per_source : 0) + (int64_t)batch->regions.size(),
-                                                   total / 2 + NC + 1);               // disjoint runs that do not touch
-            const int cap = (int)std::min<int64_t>(most, (int64_t)1 << 28);
-            DEVBUF(d_bits, uint32_t, "d_mask_bits", 2 * pga_mask_words(total) + 2);
-            DEVBUF(d_mcounts, int32_t, "d_mask_counts", 4 * (pga_mask_waves(total) + 1));
-            DEVBUF(d_moff, int32_t, "d_mask_off", NC + 2);
-            DEVBUF(d_miv, int2, "d_mask_iv", cap + 1);
-            PINBUF(h_moff_, int32_t, "h_mask_off", NC + 2);
-            pga_launch_mask_union(d_dig, d_seq, total, d_ct, NC, batch->d_tiles, batch->n_tiles, P.mask, batch->mask_case, P.min_mask, batch->d_regions,
-                                  (int)batch->regions.size(), d_bits, d_mcounts, d_moff, d_miv, cap, st);
-            HT(c, hipMemcpyAsync(h_moff_, d_moff, sizeof(int32_t) * (NC + 1), hipMemcpyDeviceToHost, st));
-            h_moff = h_moff_; d_union_iv = d_miv;
-            masks = MaskList{d_moff, d_miv};
-        } else if (P.mask) {
-            // masked regions: found on the device, ordered on the host (a handful of intervals)
-            const int cap = (int)std::min<int64_t>(total / std::max(1, P.min_mask) + NC + 1, (int64_t)1 << 28);
-            DEVBUF(d_runs, MaskRun, "d_mask_runs", cap + 1);
-            DEVBUF(d_nruns, int32_t, "d_mask_count", 4);
-            DEVBUF(d_moff, int32_t, "d_mask_off", NC + 2);
-            DEVBUF(d_miv, int2, "d_mask_iv", cap + 1);
-            pga_launch_find_masks(d_dig, d_ct, NC, batch->d_tiles, batch->n_tiles, P.min_mask, d_runs, d_nruns, cap, st);
-            int32_t nruns = 0;
-            HT(c, hipMemcpyAsync(&nruns, d_nruns, 4, hipMemcpyDeviceToHost, st));
-            HT(c, hipStreamSynchronize(st));
-            nruns = std::min(nruns, cap);
-            std::vector<MaskRun> runs((size_t)nruns);
-            if (nruns > 0) HT(c, hipMemcpy(runs.data(), d_runs, sizeof(MaskRun) * nruns, hipMemcpyDeviceToHost));
-            std::sort(runs.begin(), runs.end(), [](const MaskRun& a, const MaskRun& b) { return a.contig != b.contig ? a.contig < b.contig : a.begin < b.begin; });
-            std::vector<int32_t> moff(NC + 1, 0);
-            std::vector<int2> miv((size_t)nruns + 1);
-            for (int k = 0; k < nruns; k++) { moff[runs[k].contig + 1]++; miv[k] = make_int2(runs[k].begin, runs[k].end); }
-            for (int i = 0; i < NC; i++) moff[i + 1] += moff[i];
-            R->mask_off = moff;
-            R->masks.resize(2 * (size_t)nruns);
-            for (int k = 0; k < nruns; k++) { R->masks[2 * k] = runs[k].begin; R->masks[2 * k + 1] = runs[k].end; }
-            HT(c, hipMemcpy(d_moff, moff.data(), sizeof(int32_t) * (NC + 1), hipMemcpyHostToDevice));
-            if (nruns > 0) HT(c, hipMemcpy(d_miv, miv.data(), sizeof(int2) * nruns, hipMemcpyHostToDevice));
-            masks = MaskList{d_moff, d_miv};
-        }
-        if (stage == PGA_STAGE_SEQUENCE) {
-            HT(c, hipMemcpyAsync(h_cnt, d_cnt, sizeof(int32_t) * 2 * (size_t)NC, hipMemcpyDeviceToHost, st));
-            HT(c, hipGetLastError());
-            HT(c, hipStreamSynchronize(st));
-            for (int i = 0; i < NC; i++) {
-                R->contigs[i].gc = ct[i].len > 0 ? (double)h_cnt[i] / (double)ct[i].len : 0.0;
-                R->contigs[i].n_unknown = h_cnt[NC + i];
-            }
-            if (h_moff) { const int rc = fetch_mask_union(c, R, h_moff, d_union_iv, NC); if (rc) return rc; }
-            return publish(R, guard.r, P, out);
-        }
-        // meta mode: a contig is extracted under a translation table only if a model with that table lies in its GC window
-        // (contig sets: in its SET's window -- the labels go up, two integers per set are summed on the device)
-        if (meta_run && NM > 0 && use_sets) {
-            DEVBUF(d_set_of, int32_t, "d_set_of", 3 * (size_t)NC + 1);      // the dense ids, then the pooled (G+C count, length) pairs
-            HT(c, hipMemcpyAsync(d_set_of, set_of.data(), sizeof(int32_t) * (size_t)NC, hipMemcpyHostToDevice, st));
-            pga_launch_group_enable_sets(d_ct, NC, d_cnt, d_set_of, d_set_of + NC, f->d_model_gc, f->d_model_grp, NM, NG, d_enabled, st);
-        } else if (meta_run && NM > 0) {
-            pga_launch_group_enable(d_ct, NC, d_cnt, f->d_model_gc, f->d_model_grp, NM, NG, d_enabled, st);
-        }
-        // per-contig models: a contig is extracted under its own model's translation table only
-        if (multi) {
-            for (int g = 0; g < NG; g++) for (int i = 0; i < NC; i++) h_enabled[(size_t)g * NC + i] = cgrp[i] == g;
-            HT(c, hipMemcpyAsync(d_enabled, h_enabled, (size_t)NG * NC, hipMemcpyHostToDevice, st));
-        }
-        // Staging of the extraction: one slot per two positions of a tile (sequence has a node every 25 positions or so; the full
-        // two-slots-per-position staging was half of a context's memory).  A tile that does not fit raises a flag, the batch is then
-        // extracted again with full staging, and the context keeps that (PGA_STAGE_FULL=1: from the start).
-        if (getenv("PGA_STAGE_FULL")) f->stage_full = true;
-        bool stage_full = f->stage_full;
-        // Stop values of the extraction: a thread of k_extract_tile lists up to four per strand in LDS and a pool of the workgroup takes the
-        // rest; a tile that exhausts the pool (a full tile of (GT)n) raises bit 1 of the flag and the batch is extracted again with a
-        // value for every position.  That choice is the batch's, the context does not keep it.  (PGA_EXTRACT_C=1 .. 4 / PGA_EXTRACT_POOL=
-        // 0 .. 128: fewer list slots / pool entries, so that the tests reach the pool and the second pass on small inputs; PGA_EXTRACT_C=0:
-        // a value for every position from the start)
-        int ex_c = getenv("PGA_EXTRACT_C") ? std::max(0, std::min(4, atoi(getenv("PGA_EXTRACT_C")))) : 4;
-        const int ex_pool = getenv("PGA_EXTRACT_POOL") ? std::max(0, std::min(128, atoi(getenv("PGA_EXTRACT_POOL")))) : 128;
-        c->extract_passes = 0;
-        for (;;) {
-            const bool half = !stage_full;
-            // (PGA_STAGE_SHIFT=5: one slot per 32 positions, so that ordinary sequence overflows and the tests see the second pass)
-            const int shift = half ? std::max(1, std::min(8, getenv("PGA_STAGE_SHIFT") ? atoi(getenv("PGA_STAGE_SHIFT")) : 1)) : 0;
-            const int64_t st_slots = half ? (total >> shift) + (int64_t)PGA_STAGE_SLACK * batch->n_tiles + 8 : 2 * total + 2;
-            for (int g = 0; g < NG; g++) {
-                char nm[32];
-                GBUF(st_ndx, int32_t, st_slots) GBUF(st_sv, int32_t, st_slots) GBUF(st_info, uint8_t, st_slots)
-                ga[g].st_half = shift; ga[g].st_overflow = d_st_overflow;
-            }
-            if (c->extract_passes > 0) HT(c, hipMemsetAsync(d_st_overflow, 0, sizeof(int32_t), st));      // (the first pass: cleared with the counts)
-            for (int g = 0; g < NG; g++) {
-                const int tt = meta_run ? f->group_tt[g] : multi ? gtt[g] : (stage == PGA_STAGE_EXTRACT ? tt_override : c->models[0].trans_table);
-                pga_launch_extract(d_dig, total, d_ct, NC, tt, P, ga[g], batch->d_tiles, batch->n_tiles, batch->d_tile0, d_tile_first, d_tile_last,
-                                   d_tile_count + (size_t)g * (batch->n_tiles + 1), d_tile_off + (size_t)g * (batch->n_tiles + 1), d_cbase + (size_t)g * (NC + 1),
-                                   d_tile_scount + (size_t)g * (batch->n_tiles + 1), d_tile_soff + (size_t)g * (batch->n_tiles + 1), d_sbase + (size_t)g * (NC + 1),
-                                   masks, st, ((meta_run && NM > 0) || multi) ? d_enabled + (size_t)g * NC : nullptr, ex_c, ex_pool);
-            }
-            HT(c, hipMemcpyAsync(h_xa, d_xa, sizeof(int32_t) * xa_words, hipMemcpyDeviceToHost, st));      // flag, counts, offsets, enabled groups
-            HT(c, hipGetLastError());
-            HT(c, hipStreamSynchronize(st));
-            c->extract_passes++;
-            const bool staging_overflow = half && (h_st_overflow[0] & 1), pool_exhausted = ex_c > 0 && (h_st_overflow[0] & 2);
-            if (!staging_overflow && !pool_exhausted) break;
-            if (pool_exhausted) ex_c = 0;
-            if (staging_overflow) {
-                stage_full = true;
-                if (!getenv("PGA_STAGE_SHIFT")) f->stage_full = true;       // (the test knob leaves the context as it was)
-            }
-        }
-        if (h_moff) { const int rc = fetch_mask_union(c, R, h_moff, d_union_iv, NC); if (rc) return rc; }
-
-        tm.mark("extract+sync");
-        // ---- topology buffers; the nodes go to their places and get their GC content while the host plans the chains: neither kernel
-        //      reads anything of the plan (round 6: the device sat idle through the 0.7 ms of planning of a 6 250-contig call)
-        int64_t group_nodes[4] = {0, 0, 0, 0};
-        for (int g = 0; g < NG; g++) {
-            char nm[32];
-            group_nodes[g] = h_cbase[(size_t)g * (NC + 1) + NC];
-            const int64_t n = group_nodes[g] + 1;
-            GBUF(ndx, int32_t, n) GBUF(stop_val, int32_t, n) GBUF(type, uint8_t, n) GBUF(strand, int8_t, n) GBUF(edge0, uint8_t, n) GBUF(gc_cont, float, n) GBUF(contig_of, int32_t, n)
-            GBUF(stop_list, int32_t, (int64_t)h_sbase[(size_t)g * (NC + 1) + NC] + 1)
-            GBUF(start_list, int32_t, group_nodes[g] - (int64_t)h_sbase[(size_t)g * (NC + 1) + NC] + 1)
-            GBUF(ovl_topo, uint32_t, (int64_t)h_sbase[(size_t)g * (NC + 1) + NC] + 1)
-            GBUF(srank, int32_t, n + 4)
-        }
-        for (int g = 0; g < NG; g++) {
-            pga_launch_place(d_ct, batch->d_tiles, batch->n_tiles, d_tile_off + (size_t)g * (batch->n_tiles + 1),
-                             d_tile_soff + (size_t)g * (batch->n_tiles + 1), ga[g], st);
-            pga_launch_orf_gc(d_ct, NC, d_dig, d_p16, ga[g], (int)group_nodes[g], d_cbase + (size_t)g * (NC + 1), st);
-        }
-        // ---- plan the (contig, model) chains (ref: lib.pyx:5335-5362) ------------------------
-        std::vector<std::vector<ChainDesc>> gch(NG);     // per group, in (contig, model) order
-        std::vector<double> mgc((size_t)NM); std::vector<int> mtt((size_t)NM);     // the models are 558 KB apart: keep what the loop reads together
-        for (int m = 0; m < NM; m++) { mgc[m] = c->models[m].gc; mtt[m] = c->models[m].trans_table; }
-        for (int g = 0; g < NG; g++) gch[g].reserve(meta_run ? (size_t)NC * 6 : (size_t)NC);
-        // contig sets: the same pooled numbers the device summed (integers, exact), one division per set
-        std::vector<double> set_gc;
-        if (use_sets) {
-            std::vector<int64_t> sum((size_t)2 * NS, 0);
-            for (int i = 0; i < NC; i++) { sum[2 * (size_t)set_of[i]] += h_cnt[i]; sum[2 * (size_t)set_of[i] + 1] += ct[i].len; }
-            set_gc.resize((size_t)NS);
-            for (int s = 0; s < NS; s++) set_gc[(size_t)s] = sum[2 * (size_t)s + 1] > 0 ? (double)sum[2 * (size_t)s] / (double)sum[2 * (size_t)s + 1] : 0.0;
-        }
-        for (int i = 0; i < NC; i++) {
-            const int L = ct[i].len;
-            double gc = L > 0 ? (double)h_cnt[i] / (double)L : 0.0;
-            R->contigs[i].gc = gc;
-            R->contigs[i].n_unknown = h_cnt[NC + i];
-            if (!meta_run) {
-                const int m = per_contig ? model_of_contig[i] : 0, g = multi ? cgrp[i] : 0;
-                const int32_t* cb = h_cbase + (size_t)g * (NC + 1);
-                ChainDesc ch{0, cb[i], cb[i + 1] - cb[i], m, i, 1};
-                ch.group = g;
-                gch[g].push_back(ch);
-                continue;
-            }
-            if (use_sets) gc = set_gc[(size_t)set_of[i]];           // (the contig's own gc is in the result already)
-            const double low = fmin(0.65, 0.88495 * gc - 0.0102337), high = fmax(0.35, 0.86596 * gc + 0.1131991);
-            int tt_prev = -1;
-            for (int m = 0; m < NM; m++) {
-                if (mgc[m] < low || mgc[m] > high) continue;
-                const int g = f->model_group[m];
-                if (!h_enabled[(size_t)g * NC + i]) { c->err = "pga_find_genes: host and device disagree on a GC window"; return PGA_EDEVICE; }
-                const int32_t* cb = h_cbase + (size_t)g * (NC + 1);
-                ChainDesc ch{0, cb[i], cb[i + 1] - cb[i], m, i, mtt[m] != tt_prev ? 1 : 0};
-                ch.group = g;
-                tt_prev = mtt[m];
-                gch[g].push_back(ch);
-            }
-        }
-        std::vector<ChainDesc> chains;
-        { size_t tot = 0; for (int g = 0; g < NG; g++) tot += gch[g].size(); chains.reserve(tot); }
-        std::vector<int> g_c0(NG + 1, 0);
-        std::vector<int64_t> g_n0(NG + 1, 0);
-        int64_t tot_chain_nodes = 0, tot_chain_stops = 0;
-        std::vector<int64_t> g_s0(NG + 1, 0);            // (chain, stop node) pairs before the chains of group g
-        for (int g = 0; g < NG; g++) {
-            g_c0[g] = (int)chains.size(); g_n0[g] = tot_chain_nodes;
-            for (ChainDesc& ch : gch[g]) {
-                ch.off = tot_chain_nodes; tot_chain_nodes += ch.n;
-                ch.soff = tot_chain_stops;
-                const int32_t* sb = h_sbase + (size_t)ch.group * (NC + 1);
-                tot_chain_stops += sb[ch.contig + 1] - sb[ch.contig];
-                chains.push_back(ch);
-            }
-            g_s0[g + 1] = tot_chain_stops;
-        }
-        g_c0[NG] = (int)chains.size(); g_n0[NG] = tot_chain_nodes;
-        const int NCH = (int)chains.size();
-        R->pub.node_passes = tot_chain_nodes;
-        R->pub.n_chains = NCH;
-        // space for the fresh re-scores of winners that were not `first` (at most one per contig)
-        int64_t max_rescore = 0;
-        if (meta_run) for (int g = 0; g < NG; g++) max_rescore += h_cbase[(size_t)g * (NC + 1) + NC];   // loose bound: every node once per group
-        const int64_t chain_cap = tot_chain_nodes + max_rescore + 64;
-
-        // ---- chain buffers ---------------------------------------------------------------------
-        ChainArrays ca;
-        {
-            DEVBUF(a0, double, "ca_cscore", chain_cap) DEVBUF(a1, double, "ca_sscore", chain_cap) DEVBUF(a2, double, "ca_rscore", chain_cap)
-            DEVBUF(a3, double, "ca_uscore", chain_cap) DEVBUF(a4, double, "ca_tscore", chain_cap) DEVBUF(a5, double, "ca_mot_score", chain_cap)
-            DEVBUF(a6, int32_t, "ca_star_ptr", 3 * chain_cap) DEVBUF(a7, int32_t, "ca_mot_ndx", chain_cap) DEVBUF(a8, uint8_t, "ca_rbs", 2 * chain_cap)
-            DEVBUF(a9, uint8_t, "ca_edge", chain_cap) DEVBUF(a10, uint8_t, "ca_mot_len", chain_cap) DEVBUF(a11, uint8_t, "ca_mot_spacer", chain_cap)
-            DEVBUF(a12, uint8_t, "ca_mot_spacendx", chain_cap)
-            int64_t max_contig_nodes = 0;
-            for (int g = 0; g < NG; g++) for (int i = 0; i < NC; i++)
-                max_contig_nodes = std::max<int64_t>(max_contig_nodes, h_cbase[(size_t)g * (NC + 1) + i + 1] - h_cbase[(size_t)g * (NC + 1) + i]);
-            DEVBUF(a13, double, "ca_cscore_raw", chain_cap + max_contig_nodes + 64)
-            ca = ChainArrays{a0, a1, a2, a3, a4, a5, a13, a6, a7, a8, a9, a10, a11, a12, a13 + chain_cap};
-        }
-        // few long chains: their walks are cut into segments that run side by side (dp.hip "segmented chains")
-        DpSegPlan seg_plan;
-        // many chains: one wavefront each, records and far-field structures of dp_wave.hip
-        const bool use_wave = stage == 0 && pga_dp_use_wave(NCH);
-        // Round 6 -- few LONG chains whose segments the wave-batch kernel walks (dp.hip, launch_dp_segmented): a wavefront per segment, 2048
-        // segments at once where the chain kernel's workgroup per compute unit allows 252.  Every segment pays the same 4096-node warm-up and
-        // a wavefront walks a node more slowly than the sixteen of a chain-kernel workgroup, so this pays where the chains are long enough --
-        // from PGA_DP_SEG_WAVE_MIN (2.5 M) nodes in chains of 16 k nodes or more; PGA_DP_SEG_WAVE=1 / 0: always / never (tests).
-        bool seg_wave = false;
-        if (stage == 0 && !use_wave && pga_dpw_use_sched() && !getenv("PGA_DP_KERNEL")) {
-            int64_t cand = 0;
-            const int min_chain = std::max(256, getenv("PGA_DP_SEG_MIN") ? atoi(getenv("PGA_DP_SEG_MIN")) : 16384);      // (as pga_dp_plan)
-            for (int k = 0; k < NCH; k++) if (chains[(size_t)k].n >= min_chain) cand += chains[(size_t)k].n;
-            const char* e = getenv("PGA_DP_SEG_WAVE");
-            const char* m = getenv("PGA_DP_SEG_WAVE_MIN");
-            seg_wave = e ? atoi(e) != 0 : cand >= (m ? atoll(m) : 2500000ll);
-        }
-        // what the wave-batch kernel reads -- topology, step schedule, cs, extras -- is made for its own launches and for such segments
-        bool wave_prep = use_wave || seg_wave;
-        // the step schedule of the wave-batch scorer: one header per 64-node batch of every contig of a group (dpw_core.h)
-        bool use_sched = wave_prep && pga_dpw_use_sched();
-        std::vector<int32_t> h_bbase;
-        if (use_sched) {
-            h_bbase.resize((size_t)NG * (NC + 1));
-            for (int g = 0; g < NG; g++) {
-                const int32_t* cb = h_cbase + (size_t)g * (NC + 1);
-                int32_t* bb = h_bbase.data() + (size_t)g * (NC + 1);
-                bb[0] = 0;
-                for (int i = 0; i < NC; i++) bb[i + 1] = bb[i] + ((cb[i + 1] - cb[i] + 63) >> 6);
-            }
-            for (ChainDesc& ch : chains) ch.sched_b0 = h_bbase[(size_t)ch.group * (NC + 1) + ch.contig];
-        }
-        int max_batches[4] = {0, 0, 0, 0};
-        if (use_sched) for (int g = 0; g < NG; g++) for (int i = 0; i < NC; i++)
-            max_batches[g] = std::max(max_batches[g], h_bbase[(size_t)g * (NC + 1) + i + 1] - h_bbase[(size_t)g * (NC + 1) + i]);
-        bool segmented = stage == 0 && !use_wave && pga_dp_plan(chains.data(), NCH, tot_chain_nodes, seg_plan, seg_wave);
-        if (seg_wave && !segmented) { seg_wave = false; wave_prep = use_wave; use_sched = false; h_bbase.clear(); }       // (nothing to cut after all)
-        // lean: the tail runs on the device and nobody asked for node arrays, so only what the tail writes is gathered; direct: it
-        // also reads the winners' node fields where the scorers left them.  (One definition: the scorers skip the star_ptr fill under
-        // exactly the condition under which the tail never looks at it.)
-        const bool lean_gather = !P.want_nodes && !(getenv("PGA_TAIL") && strcmp(getenv("PGA_TAIL"), "host") == 0) && !getenv("PGA_FULL_GATHER");
-        const bool direct_gather = lean_gather && !getenv("PGA_GATHER_ALL_DP");
-        const int64_t dp_cap = tot_chain_nodes + seg_plan.extra + 1;
-        const int64_t dp_slots = NCH + (int64_t)seg_plan.segs.size() + 1;
-        // records and far-field arrays of the tree / chain kernels (sub-chains walked by the wave-batch kernel need none of their own)
-        const int64_t tree_cap = use_wave ? 1 : (seg_wave ? tot_chain_nodes + 1 : dp_cap);
-        DpBuffers dp;
-        {
-            DEVBUF(b0, DpSrc, "dp_src", tree_cap) DEVBUF(b1, DpTgt, "dp_tgt", tree_cap)
-            DEVBUF(b2, double, "dp_score", dp_cap) DEVBUF(b3, int32_t, "dp_traceb", dp_cap)
-            DEVBUF(b4, int32_t, "dp_tbn", dp_cap) DEVBUF(b5, int8_t, "dp_ov", dp_cap)
-            // (what the host reads back of a chain -- best gene end, its score, the path's start -- in one allocation: one read-back)
-            DEVBUF(b7, double, "dp_chain_results", 2 * dp_slots + 2)
-            int32_t* const b6 = (int32_t*)(b7 + dp_slots); int32_t* const b8 = b6 + dp_slots;
-            DEVBUF(b9, double, "dp_A", tree_cap) DEVBUF(b10, double, "dp_V0", tree_cap) DEVBUF(b11, double, "dp_V1", tree_cap)
-            DEVBUF(b12, double, "dp_V2", tree_cap) DEVBUF(b13, double, "dp_hv", tree_cap) DEVBUF(b14, int32_t, "dp_hi", tree_cap)
-            dp = DpBuffers{b0, b1, b2, b3, b4, b5, b6, b7, b8, b9, {b10, b11, b12}, b13, b14, nullptr};
-        }
-        DpwGroupPtrs wgroups{};
-        DpwBuffers wbuf{};
-        if (wave_prep) {
-            for (int g = 0; g < NG; g++) {
-                char nm[32];
-                const int64_t n = group_nodes[g] + 1;
-#define WBUF(field, type) { snprintf(nm, sizeof nm, "dpw_" #field "%d", g); void* p__; int rc__ = ensure_dev(c, nm, sizeof(type) * (size_t)n + 64, &p__, std::is_floating_point<type>::value); if (rc__) return rc__; wgroups.g[g].field = (type*)p__; }
-                WBUF(kf, uint8_t) WBUF(lo, int32_t) WBUF(q1, int32_t) WBUF(q2, int32_t)
-#undef WBUF
-                wgroups.g[g].ndx = ga[g].ndx; wgroups.g[g].stop_val = ga[g].stop_val; wgroups.g[g].srank = ga[g].srank;
-                if (use_sched) {
-                    // headers: one per batch; lists: DPW_SCHED_STRIDE 32-byte slots per batch (what does not fit is counted and the launch
-                    // falls back to k_dpw_dyn)
-                    const int64_t nbat = h_bbase[(size_t)g * (NC + 1) + NC];
-                    void* p__; int rc__;
-                    snprintf(nm, sizeof nm, "dpw_shdr%d", g); rc__ = ensure_dev(c, nm, sizeof(DpwSchedHdr) * (size_t)(nbat + 1), &p__); if (rc__) return rc__; wgroups.g[g].shdr = (DpwSchedHdr*)p__;
-                    snprintf(nm, sizeof nm, "dpw_sent%d", g); rc__ = ensure_dev(c, nm, sizeof(DpwSlot) * (size_t)DPW_SCHED_STRIDE * (size_t)(nbat + 1) + 256, &p__); if (rc__) return rc__; wgroups.g[g].sent = (uint4*)p__;
-                    snprintf(nm, sizeof nm, "dpw_scur%d", g); rc__ = ensure_dev(c, nm, 64, &p__); if (rc__) return rc__; wgroups.g[g].scur = (uint32_t*)p__;
-                }
-            }
-            DEVBUF(w0, double, "dpw_cs", dp_cap + 2) DEVBUF(w1, DpwExt, "dpw_ext", tot_chain_stops + 4)      /* one extras record per (chain, stop node) pair */ DEVBUF(w2, double, "dpw_sfxv", dp_cap) DEVBUF(w3, int32_t, "dpw_sfxi", dp_cap)
-            wbuf = DpwBuffers{w0, w1, w2, w3};
-            // the topology of every group now: it reads the placed nodes and nothing of the plan, and runs under the rest of the planning
-            // (start order, the copy of the plan, the coding-score tasks)
-            for (int g = 0; g < NG; g++) {
-                if (g_c0[g + 1] - g_c0[g] == 0 || g_n0[g + 1] - g_n0[g] == 0 || stage == PGA_STAGE_EXTRACT) continue;
-                int max_nodes_g = 0;
-                for (int i = 0; i < NC; i++) max_nodes_g = std::max(max_nodes_g, h_cbase[(size_t)g * (NC + 1) + i + 1] - h_cbase[(size_t)g * (NC + 1) + i]);
-                if (g < 4) HT(c, hipEventRecord(f->e_aux[4 * g], st));
-                pga_launch_dpw_topo(wgroups.g[g], ga[g].type, ga[g].strand, d_cbase + (size_t)g * (NC + 1), NC, (int)group_nodes[g], st, max_nodes_g);
-                if (g < 4) HT(c, hipEventRecord(f->e_aux[4 * g + 1], st));
-            }
-        }
-        DpSegDev seg_dev{};
-        if (segmented) {
-            DEVBUF(seg_arena, char, "dp_seg_arena", pga_dp_seg_bytes(seg_plan, NCH, tot_chain_nodes));
-            HT(c, pga_dp_seg_bind(seg_plan, NCH, tot_chain_nodes, seg_arena, st, &seg_dev));
-            if (seg_wave) { seg_dev.wave_groups = &wgroups; seg_dev.wave_buf = &wbuf; }
-        }
-        // start order of the wave-batch scorer: longest chains first (counting sort on nodes / 64 = walk batches)
-        int32_t* d_dp_order = nullptr;
-        std::vector<int32_t> dp_order;
-        if (use_wave && NCH > 1 && !getenv("PGA_DP_NO_ORDER")) {
-            std::vector<int32_t> lens((size_t)NCH);
-            for (int k = 0; k < NCH; k++) lens[(size_t)k] = chains[k].n;
-            dp_order.resize((size_t)NCH);
-            pga_dp_start_order(NCH, lens.data(), dp_order.data());
-            // Workgroups go to the eight XCDs in turn (b % 8), each with an L2 of its own, and the chains of a contig (one per model of
-            // the same translation table) read the same topology arrays.  So every (contig, table) goes to ONE XCD -- the one with
-            // the fewest nodes so far, in start order -- and workgroup 8 k + x takes the k-th chain of XCD x's queue; queues that end
-            // early are filled up with -1 (the workgroup returns at once).  PGA_DP_XCD=0: the order as it is.
-            // Only where the premise holds -- a device of eight XCDs (an MI355X in its default SPX mode; a partitioned one reports fewer) --
-            // and where the queues come out even: a handful of keys, or one contig far longer than the rest, would leave XCDs idle
-            // behind one long queue, and the plain longest-first order is the better one then.
-            static std::atomic<int> xcc_of[64];      // per device: 0 = not asked yet
-            int n_xcc = xcc_of[c->device & 63].load();
-            if (n_xcc == 0) {
-                int v = 0;
-                n_xcc = (hipDeviceGetAttribute(&v, hipDeviceAttributeNumberOfXccs, c->device) == hipSuccess && v > 0) ? v : 8;
-                xcc_of[c->device & 63].store(n_xcc);
-            }
-            if (!(getenv("PGA_DP_XCD") && atoi(getenv("PGA_DP_XCD")) == 0) && NCH >= 64 && n_xcc == 8) {
-                std::vector<int32_t> key((size_t)NCH), by_xcd((size_t)NCH * 8);
-                for (int k = 0; k < NCH; k++) key[(size_t)k] = chains[(size_t)k].group * NC + chains[(size_t)k].contig;
-                const int64_t nb = pga_dp_xcd_order(NCH, dp_order.data(), lens.data(), key.data(), NC * NG, by_xcd.data(), (int64_t)by_xcd.size());
-                int64_t load[8] = {0, 0, 0, 0, 0, 0, 0, 0}, total = 0, heaviest = 0;
-                for (int64_t k = 0; k < nb; k++) if (by_xcd[(size_t)k] >= 0) { load[k & 7] += lens[(size_t)by_xcd[(size_t)k]]; total += lens[(size_t)by_xcd[(size_t)k]]; }
-                for (int q = 0; q < 8; q++) heaviest = std::max(heaviest, load[q]);
-                if (nb > 0 && heaviest * 8 <= total + total * 3 / 10) { by_xcd.resize((size_t)nb); dp_order.swap(by_xcd); }       // within 1.3 x the mean
-            }
-        }
-        PINBUF(h_maxscore, double, "h_chain_results", 2 * dp_slots + 2);
-        int32_t* const h_maxidx = (int32_t*)(h_maxscore + dp_slots); int32_t* const h_ipath = h_maxidx + dp_slots;
-        PINBUF(h_scur, uint32_t, "h_dpw_scur", 16);
-        // the workgroups of k_ovl_stops take 256 (chain, stop node) pairs each: the chain of a workgroup's first pair, relative to its group's
-        // first chain, comes with the plan (a search on the device was three dependent loads in front of everything the workgroup does)
-        std::vector<int64_t> ovl_blk0((size_t)NG + 1, 0);
-        for (int g = 0; g < NG; g++) ovl_blk0[(size_t)g + 1] = ovl_blk0[(size_t)g] + (g_s0[g + 1] - g_s0[g] + 255) / 256;
-        // The plan of the call goes to the device in ONE copy (round 6; it was four copies and a memset): the cleared flags "scoring turned a
-        // start node into an edge node", per group and contig the run of chains scored on it, the batches before each contig (step
-        // schedule), the start order of the connection scoring, the chains -- one pinned staging area, one device area, the same layout.
-        // (Behind the chains the device area has room for the re-score chains of the winners, which are uploaded later.)
-        const size_t pa_conv = 0, pa_cc = (((size_t)NG * NC + 1) + 7) & ~(size_t)7, pa_bb = pa_cc + sizeof(int2) * (size_t)2 * NG * NC,
-                     pa_ord = pa_bb + ((sizeof(int32_t) * (h_bbase.size() + 1) + 7) & ~(size_t)7),
-                     pa_blk = pa_ord + ((sizeof(int32_t) * (dp_order.size() + 1) + 7) & ~(size_t)7),
-                     pa_ch = pa_blk + ((sizeof(int32_t) * ((size_t)ovl_blk0[NG] + 1) + 7) & ~(size_t)7), pa_copy = pa_ch + sizeof(ChainDesc) * (size_t)NCH;
-        DEVBUF(d_plan, char, "d_call_plan", pa_copy + sizeof(ChainDesc) * ((size_t)NC + 2));
-        PINBUF(h_plan, char, "h_call_plan", pa_copy + 64);
-        uint8_t* const d_conv = (uint8_t*)(d_plan + pa_conv);
-        int2* const d_cc = (int2*)(d_plan + pa_cc); int2* const h_cc = (int2*)(h_plan + pa_cc);
-        int32_t* const d_bbase = use_sched ? (int32_t*)(d_plan + pa_bb) : nullptr;
-        if (!dp_order.empty()) d_dp_order = (int32_t*)(d_plan + pa_ord);
-        ChainDesc* const d_chains = (ChainDesc*)(d_plan + pa_ch);
-        memset(h_plan + pa_conv, 0, pa_cc);
-        // per group and contig: the contiguous run of chains (models) scored on that contig
-        for (size_t k = 0; k < (size_t)2 * NG * NC; k++) h_cc[k] = make_int2(0, 0);
-        for (int k = 0; k < NCH; k++) {
-            const int g = chains[k].group;
-            int2& e = h_cc[(size_t)g * NC + chains[k].contig];
-            if (e.y == 0) e.x = k;
-            e.y++;
-        }
-        if (use_sched && !h_bbase.empty()) memcpy(h_plan + pa_bb, h_bbase.data(), sizeof(int32_t) * h_bbase.size());
-        if (!dp_order.empty()) memcpy(h_plan + pa_ord, dp_order.data(), sizeof(int32_t) * dp_order.size());
-        if (NCH > 0) memcpy(h_plan + pa_ch, chains.data(), sizeof(ChainDesc) * (size_t)NCH);
-        const int32_t* const d_ovl_blk = (const int32_t*)(d_plan + pa_blk);
-        {
-            int32_t* const h_blk = (int32_t*)(h_plan + pa_blk);
-            for (int g = 0; g < NG; g++) {
-                int k = g_c0[g];
-                const int64_t nb = ovl_blk0[(size_t)g + 1] - ovl_blk0[(size_t)g];
-                for (int64_t b = 0; b < nb; b++) {
-                    const int64_t p0 = g_s0[g] + 256 * b;
-                    while (k + 1 < g_c0[g + 1] && chains[(size_t)k + 1].soff <= p0) k++;
-                    h_blk[ovl_blk0[(size_t)g] + b] = k - g_c0[g];
-                }
-            }
-        }
-        HT(c, hipMemcpyAsync(d_plan, h_plan, pa_copy, hipMemcpyHostToDevice, st));
-
-        tm.mark("plan+alloc");
-        std::vector<int32_t> cs_tk[4], cs_en[4];
-        ScoreParams sp{P.closed, P.meta, P.max_overlap, NM, nullptr, nullptr};
-        PINBUF(h_conv, uint8_t, "h_conv_flag", (size_t)NG * NC + 1);
-        const pga_training* d_models = (const pga_training*)c->d_models_raw;
-        for (int g = 0; g < NG; g++) {
-            const int nch = g_c0[g + 1] - g_c0[g];
-            const int64_t nn = g_n0[g + 1] - g_n0[g];
-            if (nch == 0 || nn == 0 || stage == PGA_STAGE_EXTRACT) continue;
-            // the ORF walks of the coding score run from hexamer tables in LDS, contigs bucketed by the four table columns they need
-            // (PGA_CS_LDS=0: the global-memory form)
-            const void* d_cs_tasks = nullptr; const void* d_cs_entries = nullptr; int n_cs_tasks = 0;
-            const char* cs_env = getenv("PGA_CS_LDS");
-            const char* cs_tn = getenv("PGA_CS_TASK_NODES");
-            const int cs_task_nodes = cs_tn && atoi(cs_tn) >= 256 && atoi(cs_tn) <= 8192 ? atoi(cs_tn) : 5120;     // several tasks per CU and launch (swept again at the end of round 6, one box: 4096 629 us per launch, 4864 581, 5120 586, 5376 584, 5632 600, 6144 592)
-            // PGA_CS_LDS=2 (tests): the LDS form whatever the size of the launch
-            // (single mode as well: one table column, a genome is cut into tasks of `cs_task_nodes` nodes)
-            // (the global-memory form walks every ORF on one lane through the texture path: a launch takes as long as its longest ORF,
-            //  a few hundred microseconds on high-GC sequence whatever its size -- so small launches take the LDS form as well)
-            if (!(cs_env && atoi(cs_env) == 0) && !f->gil_stride.empty()) {
-                std::vector<int32_t>& tk = cs_tk[g]; std::vector<int32_t>& en = cs_en[g];     // alive until the stream is synchronized
-                if (pga_cs_tasks(h_cc + (size_t)g * NC, NC, chains.data(), h_cbase + (size_t)g * (NC + 1), f->model_rank.data(), cs_task_nodes, tk, en) && !tk.empty()) {
-                    char nm1[32], nm2[32];
-                    snprintf(nm1, sizeof nm1, "cs_tasks%d", g); snprintf(nm2, sizeof nm2, "cs_entries%d", g);
-                    void* p1; void* p2;
-                    { int rc__ = ensure_dev(c, nm1, tk.size() * 4 + 64, &p1); if (rc__) return rc__; }
-                    { int rc__ = ensure_dev(c, nm2, en.size() * 4 + 64, &p2); if (rc__) return rc__; }
-                    HT(c, hipMemcpyAsync(p1, tk.data(), tk.size() * 4, hipMemcpyHostToDevice, st));
-                    HT(c, hipMemcpyAsync(p2, en.data(), en.size() * 4, hipMemcpyHostToDevice, st));
-                    d_cs_tasks = p1; d_cs_entries = p2; n_cs_tasks = (int)(tk.size() / 4);
-                }
-            }
-            sp.conv_flag = meta_run ? d_conv + (size_t)g * NC : nullptr;
-            // overlapping starts over (chain, stop node) pairs; for the wave-batch scorer the same pass builds the stops' extras and
-            // the start scorer leaves cscore + sscore, so its per-chain preparation is done when scoring is
-            StopLaunch sl;
-            sl.sbase = d_sbase + (size_t)g * (NC + 1); sl.soff_begin = g_s0[g]; sl.n_pairs = g_s0[g + 1] - g_s0[g];
-            sl.n_stops = h_sbase[(size_t)g * (NC + 1) + NC];
-            // (the path proper; a stage-level call returns the node arrays after any stage, so there every node keeps its thread)
-            sl.starts_only = stage == 0 && !(getenv("PGA_SS_STARTS_ONLY") && atoi(getenv("PGA_SS_STARTS_ONLY")) == 0);
-            sl.n_starts = (int32_t)(group_nodes[g] - sl.n_stops);
-            sl.blk_chain = d_ovl_blk + ovl_blk0[(size_t)g];
-            // the model-major start scoring: its records, chains and tiles live in the context (PGA_SS_MM=0: the model loop).  With one
-            // model loaded the model loop has nothing to walk (one staging, one barrier per workgroup) and stays: on a 200 Mbp genome the
-            // two kernels took 2 ms more (k_mm_place writes a chain's thousands of tiles from one thread)
-            if (sl.starts_only && sl.n_starts > 0 && NM > 1 && !(getenv("PGA_SS_MM") && atoi(getenv("PGA_SS_MM")) == 0)) {
-                std::vector<int64_t> mm_items;
-                sl.mm_tiles = pga_mm_tiles(chains.data() + g_c0[g], nch, h_cbase + (size_t)g * (NC + 1), h_sbase + (size_t)g * (NC + 1), NM, mm_items);
-                char nm[32];
-                void* p__;
-                snprintf(nm, sizeof nm, "ss_rec%d", g);
-                { int rc__ = ensure_dev(c, nm, PGA_SS_REC_BYTES * (size_t)sl.n_starts + 64, &p__); if (rc__) return rc__; sl.mm_rec = p__; }
-                snprintf(nm, sizeof nm, "ss_mmchain%d", g);
-                { int rc__ = ensure_dev(c, nm, PGA_SS_MMCHAIN_BYTES * (size_t)nch + 64, &p__); if (rc__) return rc__; sl.mm_chain = p__; }
-                snprintf(nm, sizeof nm, "ss_mmtile%d", g);
-                { int rc__ = ensure_dev(c, nm, PGA_SS_MMTILE_BYTES * (size_t)sl.mm_tiles + 64, &p__); if (rc__) return rc__; sl.mm_tile = p__; }
-                snprintf(nm, sizeof nm, "ss_mmscratch%d", g);
-                { int rc__ = ensure_dev(c, nm, pga_mm_scratch_bytes(NM, nch), &p__); if (rc__) return rc__; sl.mm_scratch = p__; }
-            }
-            sp.cs_out = nullptr;
-            if (wave_prep) {
-                sl.topo_q2 = wgroups.g[g].q2; sl.ext = wbuf.ext; sp.cs_out = wbuf.cs;
-                if (use_wave) {
-                    // (direct mode: the tail reads star_ptr only at the stop nodes, which k_ovl_stops always writes)
-                    sl.fill_star_ptr = !(stage == 0 && direct_gather);
-                    // (the path proper, node arrays not asked for: a stop node's zero scores are read by nobody -- ScoreParams::lean_stops)
-                    sp.lean_stops = (stage == 0 && direct_gather && sl.starts_only && !getenv("PGA_SS_FULL_STOPS")) ? 1 : 0;
-                }       // (segments walked by the wave-batch kernel: the re-scoring and verifying kernels read the node arrays in full)
-            }
-            pga_launch_score(d_chains + g_c0[g], nch, g_n0[g], nn, d_dig, d_ct, ga[g], d_models, f->d_msc, c->d_model_const, ca, sp,
-                             d_chains, d_cc + (size_t)g * NC, d_cbase + (size_t)g * (NC + 1), NC, (int)group_nodes[g], f->d_sd_lut, st, 0,
-                             (meta_run || per_contig || n_cs_tasks > 0) ? f->d_gil + f->gil_off[g] : nullptr, (meta_run || per_contig || n_cs_tasks > 0) ? f->gil_stride[g] : 0, f->d_model_rank,
-                             d_cs_tasks, n_cs_tasks, d_cs_entries, &sl);
-            if (wave_prep && use_sched) {
-                // (behind the scoring launches: the schedule's headers carry the stop nodes' ranks, which k_ovl_topo writes there)
-                if (g < 4) HT(c, hipEventRecord(f->e_aux[4 * g + 2], st));
-                pga_launch_dpw_sched(wgroups.g[g], d_cbase + (size_t)g * (NC + 1), d_bbase + (size_t)g * (NC + 1), NC, max_batches[g], st);
-                if (g < 4) HT(c, hipEventRecord(f->e_aux[4 * g + 3], st));
-                HT(c, hipMemcpyAsync(h_scur + 2 * g, wgroups.g[g].scur, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-            }
-            NodeArrays na{ga[g].ndx, ga[g].stop_val, ga[g].type, ga[g].strand, ca.cscore, ca.sscore, ca.rscore, ca.uscore, ca.star_ptr};
-            if (!use_wave && stage == 0) pga_launch_dp_prepare(d_chains + g_c0[g], nch, g_n0[g], nn, na, c->d_model_const, dp, st);
-        }
-        if (stage != 0) {
-            // ---- stage-level call: bring the node arrays home as they are now and stop ---------------
-            const int64_t nn = tot_chain_nodes;          // every group's nodes; a contig's chain sits at the same offset in both layouts
-            PINBUF(hs_i32, int32_t, "hs_i32", 6 * nn + 8);         // ndx, stop_val, mot_ndx, star_ptr[3]
-            PINBUF(hs_f64, double, "hs_f64", 6 * nn + 8);          // cscore, sscore, rscore, uscore, tscore, mot_score
-            PINBUF(hs_u8, uint8_t, "hs_u8", 10 * nn + 8);          // type, strand, edge, rbs[2], mot_len, mot_spacer, mot_spacendx
-            PINBUF(hs_f32, float, "hs_f32", nn + 8);
-            const bool scored = stage >= PGA_STAGE_SCORE;
-            for (int g = 0; g < NG; g++) {
-                const int64_t gn = group_nodes[g], o = g_n0[g];
-                if (gn == 0) continue;
-                HT(c, hipMemcpyAsync(hs_i32 + o, ga[g].ndx, 4 * gn, hipMemcpyDeviceToHost, st));
-                HT(c, hipMemcpyAsync(hs_i32 + nn + o, ga[g].stop_val, 4 * gn, hipMemcpyDeviceToHost, st));
-                HT(c, hipMemcpyAsync(hs_u8 + o, ga[g].type, gn, hipMemcpyDeviceToHost, st));
-                HT(c, hipMemcpyAsync(hs_u8 + nn + o, ga[g].strand, gn, hipMemcpyDeviceToHost, st));
-                if (!scored) HT(c, hipMemcpyAsync(hs_u8 + 2 * nn + o, ga[g].edge0, gn, hipMemcpyDeviceToHost, st));
-                if (scored) HT(c, hipMemcpyAsync(hs_f32 + o, ga[g].gc_cont, 4 * gn, hipMemcpyDeviceToHost, st));
-            }
-            if (nn > 0) {
-                if (scored) {
-                    HT(c, hipMemcpyAsync(hs_u8 + 2 * nn, ca.edge, nn, hipMemcpyDeviceToHost, st));
-                    HT(c, hipMemcpyAsync(hs_i32 + 2 * nn, ca.mot_ndx, 4 * nn, hipMemcpyDeviceToHost, st));
-                    HT(c, hipMemcpyAsync(hs_i32 + 3 * nn, ca.star_ptr, 12 * nn, hipMemcpyDeviceToHost, st));
-                    double* const src64[6] = {ca.cscore, ca.sscore, ca.rscore, ca.uscore, ca.tscore, ca.mot_score};
-                    for (int q = 0; q < 6; q++) HT(c, hipMemcpyAsync(hs_f64 + q * nn, src64[q], 8 * nn, hipMemcpyDeviceToHost, st));
-                    HT(c, hipMemcpyAsync(hs_u8 + 3 * nn, ca.rbs, 2 * nn, hipMemcpyDeviceToHost, st));
-                    HT(c, hipMemcpyAsync(hs_u8 + 5 * nn, ca.mot_len, nn, hipMemcpyDeviceToHost, st));
-                    HT(c, hipMemcpyAsync(hs_u8 + 6 * nn, ca.mot_spacer, nn, hipMemcpyDeviceToHost, st));
-                    HT(c, hipMemcpyAsync(hs_u8 + 7 * nn, ca.mot_spacendx, nn, hipMemcpyDeviceToHost, st));
-                }
-            }
-            HT(c, hipGetLastError());
-            HT(c, hipStreamSynchronize(st));
-            f->last.d_dig = d_dig; f->last.ga = ga[0]; f->last.ca = ca; f->last.n_nodes = (int)nn; f->last.len = ct[0].len;
-            R->nodes.resize(NC);
-            for (int i = 0; i < NC; i++) {
-                pga_nodes& N = R->nodes[i];
-                const int g = multi ? cgrp[i] : 0;
-                const int32_t* cb = h_cbase + (size_t)g * (NC + 1);
-                const int64_t oo = g_n0[g] + cb[i]; const int n = cb[i + 1] - cb[i];
-                R->contigs[i].model = stage == PGA_STAGE_EXTRACT ? -1 : (per_contig ? model_of_contig[i] : 0); R->contigs[i].n_nodes = n;
-                if (int rc = alloc_nodes(R, N, n)) return rc;
-                memcpy(N.ndx, hs_i32 + oo, 4 * (size_t)n); memcpy(N.stop_val, hs_i32 + nn + oo, 4 * (size_t)n);
-                memcpy(N.type, hs_u8 + oo, n); memcpy(N.strand, hs_u8 + nn + oo, n); memcpy(N.edge, hs_u8 + 2 * nn + oo, n);
-                for (int j = 0; j < n; j++) { N.traceb[j] = -1; N.tracef[j] = -1; N.ov_mark[j] = -1; }    // ref: reset_node_scores
-                if (!scored) continue;
-                memcpy(N.mot_ndx, hs_i32 + 2 * nn + oo, 4 * (size_t)n);
-                if (stage >= PGA_STAGE_OVERLAP) memcpy(N.star_ptr, hs_i32 + 3 * nn + 3 * oo, 12 * (size_t)n);
-                double* const dst64[6] = {N.cscore, N.sscore, N.rscore, N.uscore, N.tscore, N.mot_score};
-                for (int q = 0; q < 6; q++) memcpy(dst64[q], hs_f64 + q * nn + oo, 8 * (size_t)n);
-                memcpy(N.rbs, hs_u8 + 3 * nn + 2 * oo, 2 * (size_t)n); memcpy(N.mot_len, hs_u8 + 5 * nn + oo, n);
-                memcpy(N.mot_spacer, hs_u8 + 6 * nn + oo, n); memcpy(N.mot_spacendx, hs_u8 + 7 * nn + oo, n);
-                memcpy(N.gc_cont, hs_f32 + oo, 4 * (size_t)n);
-            }
-            return publish(R, guard.r, P, out);
-        }
-        PINBUF(h_segflags, int32_t, "h_segflags", (size_t)(PGA_SEG_ROUNDS + 2) * NCH + 1);      // [rounds][chains] flags, [chains] spine sizes, [chains] a round's verdict
-        if (segmented && !(getenv("PGA_DP_SEG_READBACK") && atoi(getenv("PGA_DP_SEG_READBACK")) == 0)) seg_dev.h_round = h_segflags + (size_t)(PGA_SEG_ROUNDS + 1) * NCH;
-        // one DP launch over the chains of every group: chains are independent, the more in flight the better
-        HT(c, hipEventRecord(f->e_dp0[0], st));
-        if (use_wave) {
-            // PGA_DP_PROFILE=1: cycles per batch phase of every 64th chain (a synchronising debug aid)
-            if (getenv("PGA_DP_PROFILE")) {
-                DEVBUF(d_prof, unsigned long long, "dp_prof", 16);
-                HT(c, hipMemsetAsync(d_prof, 0, 128, st));
-                dp.prof = d_prof;
-            }
-            pga_launch_dp_wave(d_chains, NCH, wgroups, c->d_model_const, dp, wbuf, st, d_dp_order, (int)dp_order.size(), use_sched);
-            if (dp.prof != nullptr) {
-                unsigned long long pr[16];
-                HT(c, hipStreamSynchronize(st));
-                HT(c, hipMemcpy(pr, dp.prof, 128, hipMemcpyDeviceToHost));
-                const double nbp = pr[7] ? (double)pr[7] : 1.0;
-                fprintf(stderr, "[pga dp profile] %s, %d chains, batches sampled=%llu, cycles/batch: load=%.0f near steps=%.0f far gene ends=%.0f "
-                                "carries=%.0f chains=%.0f walk=%.0f finalize=%.0f | total=%.0f\n", use_sched ? "k_dp_wave" : "k_dpw_dyn", NCH, pr[7], pr[0] / nbp, pr[1] / nbp, pr[2] / nbp, pr[3] / nbp,
-                        pr[4] / nbp, pr[5] / nbp, pr[6] / nbp, (pr[0] + pr[1] + pr[2] + pr[3] + pr[4] + pr[5] + pr[6]) / nbp);
-                dp.prof = nullptr;
-            }
-        }
-        else pga_launch_dp(d_chains, NCH, c->d_model_const, dp, 1, st, segmented ? &seg_dev : nullptr);
-        HT(c, hipEventRecord(f->e_dp1[0], st));
-        HT(c, hipMemcpyAsync(h_maxscore, dp.max_score, sizeof(double) * 2 * (size_t)dp_slots, hipMemcpyDeviceToHost, st));       // scores, indices, path starts
-        if (meta_run) HT(c, hipMemcpyAsync(h_conv, d_conv, (size_t)NG * NC, hipMemcpyDeviceToHost, st));
-        if (segmented) {
-            HT(c, hipMemcpyAsync(h_segflags, seg_dev.flags, sizeof(int32_t) * PGA_SEG_ROUNDS * NCH, hipMemcpyDeviceToHost, st));
-            HT(c, hipMemcpyAsync(h_segflags + (size_t)PGA_SEG_ROUNDS * NCH, seg_dev.nsp, sizeof(int32_t) * NCH, hipMemcpyDeviceToHost, st));
-        }
-        HT(c, hipGetLastError());
+    HT(c, hipEventRecord(f->e_start, st));
+    HT(c, hipMemcpyAsync(d_ct, batch->ct.data(), sizeof(ContigDesc) * (NC + 1), hipMemcpyHostToDevice, st));
+    HT(c, hipMemsetAsync(d_xa, 0, sizeof(int32_t) * xa_cbase, st));          // the overflow flag and the counts
+    pga_launch_digitize(d_seq, d_dig, total, d_ct, NC, d_cnt, d_cnt + NC, st);
+    pga_launch_gc_prefix(d_dig, total, d_gc_bsum, d_gc_boff, d_p16, st);
+    if (mask_union) {
+        // Several sources: their union per contig is built on the device (pga_launch_mask_union) and the extraction is launched behind
+        // it without a word from the host.  The list comes back for pga_result.masks with the extraction's own read-back.
+        const int64_t per_source = total / std::max(1, P.min_mask) + NC + 1;       // qualifying runs of one kind
+        const int64_t most = std::min<int64_t>((P.mask ? per_source : 0) + (batch->mask_case ? per_source : 0) + (int64_t)batch->regions.size(),
+                                               total / 2 + NC + 1);               // disjoint runs that do not touch
+        const int cap = (int)std::min<int64_t>(most, (int64_t)1 << 28);
+        DEVBUF(d_bits, uint32_t, "d_mask_bits", 2 * pga_mask_words(total) + 2);
+        DEVBUF(d_mcounts, int32_t, "d_mask_counts", 4 * (pga_mask_waves(total) + 1));
+        DEVBUF(d_moff, int32_t, "d_mask_off", NC + 2);
+        DEVBUF(d_miv, int2, "d_mask_iv", cap + 1);
+        PINBUF(h_moff_, int32_t, "h_mask_off", NC + 2);
+        pga_launch_mask_union(d_dig, d_seq, total, d_ct, NC, batch->d_tiles, batch->n_tiles, P.mask, batch->mask_case, P.min_mask, batch->d_regions,
+                              (int)batch->regions.size(), d_bits, d_mcounts, d_moff, d_miv, cap, st);
+        HT(c, hipMemcpyAsync(h_moff_, d_moff, sizeof(int32_t) * (NC + 1), hipMemcpyDeviceToHost, st));
+        h_moff = h_moff_; d_union_iv = d_miv;
+        masks = MaskList{d_moff, d_miv};
+    } else if (P.mask) {
+        // masked regions: found on the device, ordered on the host (a handful of intervals)
+        const int cap = (int)std::min<int64_t>(total / std::max(1, P.min_mask) + NC + 1, (int64_t)1 << 28);
+        DEVBUF(d_runs, MaskRun, "d_mask_runs", cap + 1);
+        DEVBUF(d_nruns, int32_t, "d_mask_count", 4);
+        DEVBUF(d_moff, int32_t, "d_mask_off", NC + 2);
+        DEVBUF(d_miv, int2, "d_mask_iv", cap + 1);
+        pga_launch_find_masks(d_dig, d_ct, NC, batch->d_tiles, batch->n_tiles, P.min_mask, d_runs, d_nruns, cap, st);
+        int32_t nruns = 0;
+        HT(c, hipMemcpyAsync(&nruns, d_nruns, 4, hipMemcpyDeviceToHost, st));
         HT(c, hipStreamSynchronize(st));
-        uint32_t sched_missed = 0;
-        double dp_first_ms = 0.0;
-        if (use_sched) {
-            // a schedule that did not fit its buffer (node-dense input: more than two slots per node on average): the same launch again
-            // with the kernel that works the lane masks out itself
-            uint32_t missed = 0;
-            for (int g = 0; g < NG; g++) if (g_c0[g + 1] > g_c0[g] && g_n0[g + 1] > g_n0[g]) missed += h_scur[2 * g + 1];
-            sched_missed = missed;
-            if (getenv("PGA_DPW_SCHED_DEBUG")) for (int g = 0; g < NG; g++) fprintf(stderr, "[pga dpw sched] group %d: %u batches missed\n", g, h_scur[2 * g + 1]);
-            if (missed && use_wave) {      // (segments walked by the wave-batch kernel: a missed batch ends its segment's claims, the verification does the rest)
-                // (the first launch's time counts: t_dp_ms covers both)
-                { float ms = 0; HT(c, hipEventElapsedTime(&ms, f->e_dp0[0], f->e_dp1[0])); dp_first_ms = ms; }
-                HT(c, hipEventRecord(f->e_dp0[0], st));
-                pga_launch_dp_wave(d_chains, NCH, wgroups, c->d_model_const, dp, wbuf, st, d_dp_order, (int)dp_order.size(), false);
-                HT(c, hipEventRecord(f->e_dp1[0], st));
-                HT(c, hipMemcpyAsync(h_maxscore, dp.max_score, sizeof(double) * 2 * (size_t)dp_slots, hipMemcpyDeviceToHost, st));
-                HT(c, hipGetLastError());
-                HT(c, hipStreamSynchronize(st));
-            }
-        }
-        pga_dp_note_stats(c, segmented ? &seg_plan : nullptr, h_segflags, NCH);
-        c->dp_stats[6] = use_sched ? 1 : 0; c->dp_stats[7] = (int32_t)sched_missed;
-        if (segmented && getenv("PGA_DP_SEG_DEBUG")) {
-            fprintf(stderr, "[pga dp-seg] %d chains cut into %d segments (<= %d nodes each); nodes rejected per round: %d %d %d; walked serially: %d; spine:",
-                    seg_dev.n_big, seg_dev.n_segs, seg_dev.max_seg_nodes, c->dp_stats[2], c->dp_stats[3], c->dp_stats[4], c->dp_stats[5]);
-            for (int k : seg_plan.big) fprintf(stderr, " %d/%d", h_segflags[(size_t)PGA_SEG_ROUNDS * NCH + k], chains[(size_t)k].n);
-            fprintf(stderr, "\n");
-        }
-        { float ms = 0; HT(c, hipEventElapsedTime(&ms, f->e_dp0[0], f->e_dp1[0])); R->pub.t_dp_ms = NCH > 0 ? ms + dp_first_ms : 0.0; }
-        c->dp_timings[0] = R->pub.t_dp_ms; c->dp_timings[1] = c->dp_timings[2] = c->dp_timings[3] = 0.0;
-        if (wave_prep) for (int g = 0; g < NG && g < 4; g++) {
-            if (!(g_c0[g + 1] > g_c0[g] && g_n0[g + 1] > g_n0[g])) continue;
-            float ms = 0;
-            if (hipEventElapsedTime(&ms, f->e_aux[4 * g], f->e_aux[4 * g + 1]) == hipSuccess) c->dp_timings[1] += ms;
-            if (use_sched && hipEventElapsedTime(&ms, f->e_aux[4 * g + 2], f->e_aux[4 * g + 3]) == hipSuccess) c->dp_timings[2] += ms;
-        }
+        nruns = std::min(nruns, cap);
+        std::vector<MaskRun> runs((size_t)nruns);
+        if (nruns > 0) HT(c, hipMemcpy(runs.data(), d_runs, sizeof(MaskRun) * nruns, hipMemcpyDeviceToHost));
+        std::sort(runs.begin(), runs.end(), [](const MaskRun& a, const MaskRun& b) { return a.contig != b.contig ? a.contig < b.contig : a.begin < b.begin; });
+        std::vector<int32_t> moff(NC + 1, 0);
+        std::vector<int2> miv((size_t)nruns + 1);
+        for (int k = 0; k < nruns; k++) { moff[runs[k].contig + 1]++; miv[k] = make_int2(runs[k].begin, runs[k].end); }
+        for (int i = 0; i < NC; i++) moff[i + 1] += moff[i];
+        R->mask_off = moff;
+        R->masks.resize(2 * (size_t)nruns);
+        for (int k = 0; k < nruns; k++) { R->masks[2 * k] = runs[k].begin; R->masks[2 * k + 1] = runs[k].end; }
+        HT(c, hipMemcpy(d_moff, moff.data(), sizeof(int32_t) * (NC + 1), hipMemcpyHostToDevice));
+        if (nruns > 0) HT(c, hipMemcpy(d_miv, miv.data(), sizeof(int2) * nruns, hipMemcpyHostToDevice));
+        masks = MaskList{d_moff, d_miv};
+    }
+    return PGA_OK;
+}
 
-        tm.mark("score+dp+sync");
-        // ---- pick the winning model per contig (ref: lib.pyx:5364-5367, strict '>' from -100) ---
-        std::vector<int> win_chain(NC, -1);
-        {
-            // the reference visits the models of a contig in model order and keeps a strictly better one: the winner is the
-            // highest score, the lowest model among equals -- one pass over the chains, whatever group they sit in
-            if (!P.meta) { for (int k = NCH - 1; k >= 0; k--) win_chain[chains[k].contig] = k; }
-            else if (use_sets) {
-                // Contig sets: a contig contributes its path score under a model iff it has nodes and a path there; S_m of a set is the
-                // sum of its members' contributions in batch order; the set's model is the largest S_m above -100, the lowest index among
-                // equals; a member that contributed under it is called from that chain, the others have no genes.
-                std::vector<double>& ms = c->model_scores;           // [contig][model], NaN: no contribution
-                std::vector<int32_t> chain_of((size_t)NC * NM, -1);
-                for (int k = 0; k < NCH; k++) {
-                    const ChainDesc& ch = chains[k];
-                    if (ch.n <= 0 || h_ipath[k] < 0) continue;
-                    ms[(size_t)ch.contig * NM + ch.model] = h_maxscore[k];
-                    chain_of[(size_t)ch.contig * NM + ch.model] = k;
-                }
-                std::vector<double> S((size_t)NS * NM, 0.0);
-                std::vector<uint8_t> has((size_t)NS * NM, 0);
-                for (int i = 0; i < NC; i++) {
-                    const size_t s0 = (size_t)set_of[i] * NM;
-                    for (int m = 0; m < NM; m++) {
-                        if (chain_of[(size_t)i * NM + m] < 0) continue;
-                        const double v = ms[(size_t)i * NM + m];
-                        if (has[s0 + m]) S[s0 + m] += v; else { S[s0 + m] = v; has[s0 + m] = 1; }
-                    }
-                }
-                std::vector<int32_t> W((size_t)NS, -1);
-                for (int s = 0; s < NS; s++) {
-                    double best = -100.0;
-                    for (int m = 0; m < NM; m++) if (has[(size_t)s * NM + m] && S[(size_t)s * NM + m] > best) { best = S[(size_t)s * NM + m]; W[(size_t)s] = m; }
-                }
-                for (int i = 0; i < NC; i++) {
-                    const int w = W[(size_t)set_of[i]];
-                    if (w < 0) continue;
-                    c->set_model[(size_t)i] = w; c->set_score[(size_t)i] = S[(size_t)set_of[i] * NM + w];
-                    win_chain[i] = chain_of[(size_t)i * NM + w];
-                }
-            }
-            else {
-                std::vector<double> best(NC, -100.0);
-                for (int k = 0; k < NCH; k++) {
-                    const ChainDesc& ch = chains[k];
-                    if (ch.n <= 0 || h_ipath[k] < 0) continue;
-                    const int w = win_chain[ch.contig];
-                    if (h_maxscore[k] > best[ch.contig] || (w >= 0 && h_maxscore[k] == best[ch.contig] && ch.model < chains[w].model)) {
-                        best[ch.contig] = h_maxscore[k]; win_chain[ch.contig] = k;
-                    }
-                }
+// PGA_STAGE_SEQUENCE: the contigs' GC and unknown counts (and the masks), and stop
+int FindCall::return_sequence_stage(pga_result** out) {
+    HT(c, hipMemcpyAsync(h_cnt, d_cnt, sizeof(int32_t) * 2 * (size_t)NC, hipMemcpyDeviceToHost, st));
+    if (const int rc = sync()) return rc;
+    contig_counts();
+    if (h_moff) { const int rc = fetch_mask_union(c, R, h_moff, d_union_iv, NC); if (rc) return rc; }
+    return publish_result(out);
+}
+
+// the group-enable launch and the extraction loop with its staging and pool retries
+int FindCall::run_extract() {
+    // meta mode: a contig is extracted under a translation table only if a model with that table lies in its GC window
+    // (contig sets: in its SET's window -- the labels go up, two integers per set are summed on the device)
+    if (meta_run && NM > 0 && use_sets) {
+        DEVBUF(d_set_of, int32_t, "d_set_of", 3 * (size_t)NC + 1);      // the dense ids, then the pooled (G+C count, length) pairs
+        HT(c, hipMemcpyAsync(d_set_of, set_of.data(), sizeof(int32_t) * (size_t)NC, hipMemcpyHostToDevice, st));
+        pga_launch_group_enable_sets(d_ct, NC, d_cnt, d_set_of, d_set_of + NC, f->d_model_gc, f->d_model_grp, NM, NG, d_enabled, st);
+    } else if (meta_run && NM > 0) {
+        pga_launch_group_enable(d_ct, NC, d_cnt, f->d_model_gc, f->d_model_grp, NM, NG, d_enabled, st);
+    }
+    // per-contig models: a contig is extracted under its own model's translation table only
+    if (multi) {
+        for (int g = 0; g < NG; g++) for (int i = 0; i < NC; i++) h_enabled[(size_t)g * NC + i] = cgrp[i] == g;
+        HT(c, hipMemcpyAsync(d_enabled, h_enabled, (size_t)NG * NC, hipMemcpyHostToDevice, st));
+    }
+    // Staging of the extraction: one slot per two positions of a tile (sequence has a node every 25 positions or so; the full
+    // two-slots-per-position staging was half of a context's memory).  A tile that does not fit raises a flag, the batch is then
+    // extracted again with full staging, and the context keeps that (PGA_STAGE_FULL=1: from the start).
+    if (getenv("PGA_STAGE_FULL")) f->stage_full = true;
+    bool stage_full = f->stage_full;
+    // Stop values of the extraction: a thread of k_extract_tile lists up to four per strand in LDS and a pool of the workgroup takes the
+    // rest; a tile that exhausts the pool (a full tile of (GT)n) raises bit 1 of the flag and the batch is extracted again with a
+    // value for every position.  That choice is the batch's, the context does not keep it.  (PGA_EXTRACT_C=1 .. 4 / PGA_EXTRACT_POOL=
+    // 0 .. 128: fewer list slots / pool entries, so that the tests reach the pool and the second pass on small inputs; PGA_EXTRACT_C=0:
+    // a value for every position from the start)
+    int ex_c = getenv("PGA_EXTRACT_C") ? std::max(0, std::min(4, atoi(getenv("PGA_EXTRACT_C")))) : 4;
+    const int ex_pool = getenv("PGA_EXTRACT_POOL") ? std::max(0, std::min(128, atoi(getenv("PGA_EXTRACT_POOL")))) : 128;
+    int32_t* const d_st_overflow = d_xa; const int32_t* const h_st_overflow = h_xa;
+    c->extract_passes = 0;
+    for (;;) {
+        const bool half = !stage_full;
+        // (PGA_STAGE_SHIFT=5: one slot per 32 positions, so that ordinary sequence overflows and the tests see the second pass)
+        const int shift = half ? std::max(1, std::min(8, getenv("PGA_STAGE_SHIFT") ? atoi(getenv("PGA_STAGE_SHIFT")) : 1)) : 0;
+        const int64_t st_slots = half ? (total >> shift) + (int64_t)PGA_STAGE_SLACK * batch->n_tiles + 8 : 2 * total + 2;
+        for (int g = 0; g < NG; g++) {
+            GBUF(st_ndx, int32_t, st_slots) GBUF(st_sv, int32_t, st_slots) GBUF(st_info, uint8_t, st_slots)
+            ga[g].st_half = shift; ga[g].st_overflow = d_st_overflow;
+        }
+        if (c->extract_passes > 0) HT(c, hipMemsetAsync(d_st_overflow, 0, sizeof(int32_t), st));      // (the first pass: cleared with the counts)
+        for (int g = 0; g < NG; g++) {
+            const int tt = meta_run ? f->group_tt[g] : multi ? gtt[g] : (stage == PGA_STAGE_EXTRACT ? tt_override : c->models[0].trans_table);
+            const GroupTiles t = tiles(g);
+            pga_launch_extract(d_dig, total, d_ct, NC, tt, P, ga[g], batch->d_tiles, batch->n_tiles, batch->d_tile0, d_tile_first, d_tile_last,
+                               t.count, t.off, d_cb(g), t.scount, t.soff, d_sb(g),
+                               masks, st, ((meta_run && NM > 0) || multi) ? d_enabled + (size_t)g * NC : nullptr, ex_c, ex_pool);
+        }
+        HT(c, hipMemcpyAsync(h_xa, d_xa, sizeof(int32_t) * xa_words, hipMemcpyDeviceToHost, st));      // flag, counts, offsets, enabled groups
+        if (const int rc = sync()) return rc;
+        c->extract_passes++;
+        const bool staging_overflow = half && (h_st_overflow[0] & 1), pool_exhausted = ex_c > 0 && (h_st_overflow[0] & 2);
+        if (!staging_overflow && !pool_exhausted) break;
+        if (pool_exhausted) ex_c = 0;
+        if (staging_overflow) {
+            stage_full = true;
+            if (!getenv("PGA_STAGE_SHIFT")) f->stage_full = true;       // (the test knob leaves the context as it was)
+        }
+    }
+    if (h_moff) { const int rc = fetch_mask_union(c, R, h_moff, d_union_iv, NC); if (rc) return rc; }
+    return PGA_OK;
+}
+
+// ---- topology buffers; the nodes go to their places and get their GC content while the host plans the chains: neither kernel
+//      reads anything of the plan (round 6: the device sat idle through the 0.7 ms of planning of a 6 250-contig call)
+int FindCall::place_nodes() {
+    for (int g = 0; g < NG; g++) {
+        group_nodes[g] = h_cb(g)[NC];
+        const int64_t n = group_nodes[g] + 1;
+        GBUF(ndx, int32_t, n) GBUF(stop_val, int32_t, n) GBUF(type, uint8_t, n) GBUF(strand, int8_t, n) GBUF(edge0, uint8_t, n) GBUF(gc_cont, float, n) GBUF(contig_of, int32_t, n)
+        GBUF(stop_list, int32_t, (int64_t)group_stops(g) + 1)
+        GBUF(start_list, int32_t, group_nodes[g] - (int64_t)group_stops(g) + 1)
+        GBUF(ovl_topo, uint32_t, (int64_t)group_stops(g) + 1)
+        GBUF(srank, int32_t, n + 4)
+    }
+    for (int g = 0; g < NG; g++) {
+        pga_launch_place(d_ct, batch->d_tiles, batch->n_tiles, tiles(g).off, tiles(g).soff, ga[g], st);
+        pga_launch_orf_gc(d_ct, NC, d_dig, d_p16, ga[g], (int)group_nodes[g], d_cb(g), st);
+    }
+    return PGA_OK;
+}
+
+// ---- plan the (contig, model) chains (ref: lib.pyx:5335-5362; the arithmetic: find_plan.h) ------------------------
+int FindCall::plan_chains() {
+    std::vector<double> mgc((size_t)NM); std::vector<int> mtt((size_t)NM);     // the models are 558 KB apart: keep what the loop reads together
+    for (int m = 0; m < NM; m++) { mgc[m] = c->models[m].gc; mtt[m] = c->models[m].trans_table; }
+    contig_counts();
+    const pga_plan::ChainPlanIn in{NC, NM, NG, meta_run, batch->ct.data(), h_cnt, h_cbase, h_sbase, h_enabled, mgc.data(), mtt.data(), f->model_group.data(),
+                                   per_contig ? model_of_contig : nullptr, multi ? cgrp.data() : nullptr, use_sets ? set_of.data() : nullptr, NS};
+    if (!pga_plan::plan_chains(in, *this)) { c->err = "pga_find_genes: host and device disagree on a GC window"; return PGA_EDEVICE; }
+    NCH = (int)chains.size();
+    R->pub.node_passes = tot_chain_nodes;
+    R->pub.n_chains = NCH;
+    return PGA_OK;
+}
+
+// the wave / segmented / schedule decisions, the chain, DP and wave buffers, the early topology launches, the start order
+int FindCall::plan_connection_scoring() {
+    // space for the fresh re-scores of winners that were not `first` (at most one per contig)
+    int64_t max_rescore = 0;
+    if (meta_run) for (int g = 0; g < NG; g++) max_rescore += h_cb(g)[NC];   // loose bound: every node once per group
+    const int64_t chain_cap = tot_chain_nodes + max_rescore + 64;
+
+    // ---- chain buffers ---------------------------------------------------------------------
+    {
+        DEVBUF(a0, double, "ca_cscore", chain_cap) DEVBUF(a1, double, "ca_sscore", chain_cap) DEVBUF(a2, double, "ca_rscore", chain_cap)
+        DEVBUF(a3, double, "ca_uscore", chain_cap) DEVBUF(a4, double, "ca_tscore", chain_cap) DEVBUF(a5, double, "ca_mot_score", chain_cap)
+        DEVBUF(a6, int32_t, "ca_star_ptr", 3 * chain_cap) DEVBUF(a7, int32_t, "ca_mot_ndx", chain_cap) DEVBUF(a8, uint8_t, "ca_rbs", 2 * chain_cap)
+        DEVBUF(a9, uint8_t, "ca_edge", chain_cap) DEVBUF(a10, uint8_t, "ca_mot_len", chain_cap) DEVBUF(a11, uint8_t, "ca_mot_spacer", chain_cap)
+        DEVBUF(a12, uint8_t, "ca_mot_spacendx", chain_cap)
+        int64_t max_contig_nodes = 0;
+        for (int g = 0; g < NG; g++) for (int i = 0; i < NC; i++) max_contig_nodes = std::max<int64_t>(max_contig_nodes, contig_nodes(g, i));
+        DEVBUF(a13, double, "ca_cscore_raw", chain_cap + max_contig_nodes + 64)
+        ca = ChainArrays{a0, a1, a2, a3, a4, a5, a13, a6, a7, a8, a9, a10, a11, a12, a13 + chain_cap};
+    }
+    // few long chains: their walks are cut into segments that run side by side (dp.hip "segmented chains": seg_plan)
+    // many chains: one wavefront each, records and far-field structures of dp_wave.hip
+    use_wave = stage == 0 && pga_dp_use_wave(NCH);
+    // Round 6 -- few LONG chains whose segments the wave-batch kernel walks (dp.hip, launch_dp_segmented): a wavefront per segment, 2048
+    // segments at once where the chain kernel's workgroup per compute unit allows 252.  Every segment pays the same 4096-node warm-up and
+    // a wavefront walks a node more slowly than the sixteen of a chain-kernel workgroup, so this pays where the chains are long enough --
+    // from PGA_DP_SEG_WAVE_MIN (2.5 M) nodes in chains of 16 k nodes or more; PGA_DP_SEG_WAVE=1 / 0: always / never (tests).
+    seg_wave = false;
+    if (stage == 0 && !use_wave && pga_dpw_use_sched() && !getenv("PGA_DP_KERNEL")) {
+        int64_t cand = 0;
+        const int min_chain = std::max(256, getenv("PGA_DP_SEG_MIN") ? atoi(getenv("PGA_DP_SEG_MIN")) : 16384);      // (as pga_dp_plan)
+        for (int k = 0; k < NCH; k++) if (chains[(size_t)k].n >= min_chain) cand += chains[(size_t)k].n;
+        const char* e = getenv("PGA_DP_SEG_WAVE");
+        const char* m = getenv("PGA_DP_SEG_WAVE_MIN");
+        seg_wave = e ? atoi(e) != 0 : cand >= (m ? atoll(m) : 2500000ll);
+    }
+    // what the wave-batch kernel reads -- topology, step schedule, cs, extras -- is made for its own launches and for such segments
+    wave_prep = use_wave || seg_wave;
+    // the step schedule of the wave-batch scorer: one header per 64-node batch of every contig of a group (dpw_core.h)
+    use_sched = wave_prep && pga_dpw_use_sched();
+    if (use_sched) {
+        h_bbase.resize((size_t)NG * (NC + 1));
+        for (int g = 0; g < NG; g++) {
+            int32_t* bb = h_bbase.data() + (size_t)g * (NC + 1);
+            bb[0] = 0;
+            for (int i = 0; i < NC; i++) bb[i + 1] = bb[i] + ((contig_nodes(g, i) + 63) >> 6);
+        }
+        for (ChainDesc& ch : chains) ch.sched_b0 = h_bbase[(size_t)ch.group * (NC + 1) + ch.contig];
+    }
+    if (use_sched) for (int g = 0; g < NG; g++) for (int i = 0; i < NC; i++)
+        max_batches[g] = std::max(max_batches[g], h_bbase[(size_t)g * (NC + 1) + i + 1] - h_bbase[(size_t)g * (NC + 1) + i]);
+    segmented = stage == 0 && !use_wave && pga_dp_plan(chains.data(), NCH, tot_chain_nodes, seg_plan, seg_wave);
+    if (seg_wave && !segmented) { seg_wave = false; wave_prep = use_wave; use_sched = false; h_bbase.clear(); }       // (nothing to cut after all)
+    // lean: the tail runs on the device and nobody asked for node arrays, so only what the tail writes is gathered; direct: it
+    // also reads the winners' node fields where the scorers left them.  (One definition: the scorers skip the star_ptr fill under
+    // exactly the condition under which the tail never looks at it.)
+    lean_gather = !P.want_nodes && !(getenv("PGA_TAIL") && strcmp(getenv("PGA_TAIL"), "host") == 0) && !getenv("PGA_FULL_GATHER");
+    direct_gather = lean_gather && !getenv("PGA_GATHER_ALL_DP");
+    const int64_t dp_cap = tot_chain_nodes + seg_plan.extra + 1;
+    dp_slots = NCH + (int64_t)seg_plan.segs.size() + 1;
+    // records and far-field arrays of the tree / chain kernels (sub-chains walked by the wave-batch kernel need none of their own)
+    const int64_t tree_cap = use_wave ? 1 : (seg_wave ? tot_chain_nodes + 1 : dp_cap);
+    {
+        DEVBUF(b0, DpSrc, "dp_src", tree_cap) DEVBUF(b1, DpTgt, "dp_tgt", tree_cap)
+        DEVBUF(b2, double, "dp_score", dp_cap) DEVBUF(b3, int32_t, "dp_traceb", dp_cap)
+        DEVBUF(b4, int32_t, "dp_tbn", dp_cap) DEVBUF(b5, int8_t, "dp_ov", dp_cap)
+        // (what the host reads back of a chain -- best gene end, its score, the path's start -- in one allocation: one read-back)
+        DEVBUF(b7, double, "dp_chain_results", 2 * dp_slots + 2)
+        int32_t* const b6 = (int32_t*)(b7 + dp_slots); int32_t* const b8 = b6 + dp_slots;
+        DEVBUF(b9, double, "dp_A", tree_cap) DEVBUF(b10, double, "dp_V0", tree_cap) DEVBUF(b11, double, "dp_V1", tree_cap)
+        DEVBUF(b12, double, "dp_V2", tree_cap) DEVBUF(b13, double, "dp_hv", tree_cap) DEVBUF(b14, int32_t, "dp_hi", tree_cap)
+        dp = DpBuffers{b0, b1, b2, b3, b4, b5, b6, b7, b8, b9, {b10, b11, b12}, b13, b14, nullptr};
+    }
+    if (wave_prep) { const int rc = prepare_wave(dp_cap); if (rc) return rc; }
+    if (segmented) {
+        DEVBUF(seg_arena, char, "dp_seg_arena", pga_dp_seg_bytes(seg_plan, NCH, tot_chain_nodes));
+        HT(c, pga_dp_seg_bind(seg_plan, NCH, tot_chain_nodes, seg_arena, st, &seg_dev));
+        if (seg_wave) { seg_dev.wave_groups = &wgroups; seg_dev.wave_buf = &wbuf; }
+    }
+    order_starts();
+    PINSET(h_maxscore, double, "h_chain_results", 2 * dp_slots + 2);
+    h_maxidx = (int32_t*)(h_maxscore + dp_slots); h_ipath = h_maxidx + dp_slots;
+    PINSET(h_scur, uint32_t, "h_dpw_scur", 16);
+    return PGA_OK;
+}
+
+// the buffers of the wave-batch scorer and the topology of every group
+int FindCall::prepare_wave(const int64_t dp_cap) {
+    for (int g = 0; g < NG; g++) {
+        const int64_t n = group_nodes[g] + 1;
+#define WBUF(field, type) GROUPBUF(wgroups.g[g].field, type*, "dpw_" #field, sizeof(type) * (size_t)n + 64, std::is_floating_point<type>::value)
+        WBUF(kf, uint8_t) WBUF(lo, int32_t) WBUF(q1, int32_t) WBUF(q2, int32_t)
+#undef WBUF
+        wgroups.g[g].ndx = ga[g].ndx; wgroups.g[g].stop_val = ga[g].stop_val; wgroups.g[g].srank = ga[g].srank;
+        if (use_sched) {
+            // headers: one per batch; lists: DPW_SCHED_STRIDE 32-byte slots per batch (what does not fit is counted and the launch
+            // falls back to k_dpw_dyn)
+            const int64_t nbat = h_bbase[(size_t)g * (NC + 1) + NC];
+            GROUPBUF(wgroups.g[g].shdr, DpwSchedHdr*, "dpw_shdr", sizeof(DpwSchedHdr) * (size_t)(nbat + 1), false)
+            GROUPBUF(wgroups.g[g].sent, uint4*, "dpw_sent", sizeof(DpwSlot) * (size_t)DPW_SCHED_STRIDE * (size_t)(nbat + 1) + 256, false)
+            GROUPBUF(wgroups.g[g].scur, uint32_t*, "dpw_scur", 64, false)
+        }
+    }
+    DEVBUF(w0, double, "dpw_cs", dp_cap + 2) DEVBUF(w1, DpwExt, "dpw_ext", tot_chain_stops + 4)      /* one extras record per (chain, stop node) pair */ DEVBUF(w2, double, "dpw_sfxv", dp_cap) DEVBUF(w3, int32_t, "dpw_sfxi", dp_cap)
+    wbuf = DpwBuffers{w0, w1, w2, w3};
+    // the topology of every group now: it reads the placed nodes and nothing of the plan, and runs under the rest of the planning
+    // (start order, the copy of the plan, the coding-score tasks)
+    for (int g = 0; g < NG; g++) {
+        if (!group_has_work(g) || stage == PGA_STAGE_EXTRACT) continue;
+        int max_nodes_g = 0;
+        for (int i = 0; i < NC; i++) max_nodes_g = std::max(max_nodes_g, contig_nodes(g, i));
+        if (g < 4) HT(c, hipEventRecord(f->e_aux[4 * g], st));
+        pga_launch_dpw_topo(wgroups.g[g], ga[g].type, ga[g].strand, d_cb(g), NC, (int)group_nodes[g], st, max_nodes_g);
+        if (g < 4) HT(c, hipEventRecord(f->e_aux[4 * g + 1], st));
+    }
+    return PGA_OK;
+}
+
+// start order of the wave-batch scorer: longest chains first (counting sort on nodes / 64 = walk batches)
+void FindCall::order_starts() {
+    if (!(use_wave && NCH > 1 && !getenv("PGA_DP_NO_ORDER"))) return;
+    std::vector<int32_t> lens((size_t)NCH);
+    for (int k = 0; k < NCH; k++) lens[(size_t)k] = chains[k].n;
+    dp_order.resize((size_t)NCH);
+    pga_dp_start_order(NCH, lens.data(), dp_order.data());
+    // Workgroups go to the eight XCDs in turn (b % 8), each with an L2 of its own, and the chains of a contig (one per model of
+    // the same translation table) read the same topology arrays.  So every (contig, table) goes to ONE XCD -- the one with
+    // the fewest nodes so far, in start order -- and workgroup 8 k + x takes the k-th chain of XCD x's queue; queues that end
+    // early are filled up with -1 (the workgroup returns at once).  PGA_DP_XCD=0: the order as it is.
+    // Only where the premise holds -- a device of eight XCDs (an MI355X in its default SPX mode; a partitioned one reports fewer) --
+    // and where the queues come out even: a handful of keys, or one contig far longer than the rest, would leave XCDs idle
+    // behind one long queue, and the plain longest-first order is the better one then.
+    static std::atomic<int> xcc_of[64];      // per device: 0 = not asked yet
+    int n_xcc = xcc_of[c->device & 63].load();
+    if (n_xcc == 0) {
+        int v = 0;
+        n_xcc = (hipDeviceGetAttribute(&v, hipDeviceAttributeNumberOfXccs, c->device) == hipSuccess && v > 0) ? v : 8;
+        xcc_of[c->device & 63].store(n_xcc);
+    }
+    if (!(getenv("PGA_DP_XCD") && atoi(getenv("PGA_DP_XCD")) == 0) && NCH >= 64 && n_xcc == 8) {
+        std::vector<int32_t> key((size_t)NCH), by_xcd((size_t)NCH * 8);
+        for (int k = 0; k < NCH; k++) key[(size_t)k] = chains[(size_t)k].group * NC + chains[(size_t)k].contig;
+        const int64_t nb = pga_dp_xcd_order(NCH, dp_order.data(), lens.data(), key.data(), NC * NG, by_xcd.data(), (int64_t)by_xcd.size());
+        int64_t load[8] = {0, 0, 0, 0, 0, 0, 0, 0}, sum = 0, heaviest = 0;
+        for (int64_t k = 0; k < nb; k++) if (by_xcd[(size_t)k] >= 0) { load[k & 7] += lens[(size_t)by_xcd[(size_t)k]]; sum += lens[(size_t)by_xcd[(size_t)k]]; }
+        for (int q = 0; q < 8; q++) heaviest = std::max(heaviest, load[q]);
+        if (nb > 0 && heaviest * 8 <= sum + sum * 3 / 10) { by_xcd.resize((size_t)nb); dp_order.swap(by_xcd); }       // within 1.3 x the mean
+    }
+}
+
+// The plan of the call goes to the device in ONE copy (round 6; it was four copies and a memset): the cleared flags "scoring turned a
+// start node into an edge node", per group and contig the run of chains scored on it, the batches before each contig (step
+// schedule), the start order of the connection scoring, the chains -- one pinned staging area, one device area, the same layout.
+// (Behind the chains the device area has room for the re-score chains of the winners, which are uploaded later.)
+int FindCall::upload_plan() {
+    // the workgroups of k_ovl_stops take 256 (chain, stop node) pairs each: the chain of a workgroup's first pair, relative to its group's
+    // first chain, comes with the plan (a search on the device was three dependent loads in front of everything the workgroup does)
+    ovl_blk0.assign((size_t)NG + 1, 0);
+    for (int g = 0; g < NG; g++) ovl_blk0[(size_t)g + 1] = ovl_blk0[(size_t)g] + (g_s0[g + 1] - g_s0[g] + 255) / 256;
+    const size_t pa_conv = 0, pa_cc = (((size_t)NG * NC + 1) + 7) & ~(size_t)7, pa_bb = pa_cc + sizeof(int2) * (size_t)2 * NG * NC,
+                 pa_ord = pa_bb + ((sizeof(int32_t) * (h_bbase.size() + 1) + 7) & ~(size_t)7),
+                 pa_blk = pa_ord + ((sizeof(int32_t) * (dp_order.size() + 1) + 7) & ~(size_t)7),
+                 pa_ch = pa_blk + ((sizeof(int32_t) * ((size_t)ovl_blk0[NG] + 1) + 7) & ~(size_t)7), pa_copy = pa_ch + sizeof(ChainDesc) * (size_t)NCH;
+    DEVBUF(d_plan, char, "d_call_plan", pa_copy + sizeof(ChainDesc) * ((size_t)NC + 2));
+    PINBUF(h_plan, char, "h_call_plan", pa_copy + 64);
+    d_conv = (uint8_t*)(d_plan + pa_conv);
+    d_cc = (int2*)(d_plan + pa_cc); h_cc = (int2*)(h_plan + pa_cc);
+    d_bbase = use_sched ? (int32_t*)(d_plan + pa_bb) : nullptr;
+    if (!dp_order.empty()) d_dp_order = (int32_t*)(d_plan + pa_ord);
+    d_chains = (ChainDesc*)(d_plan + pa_ch);
+    memset(h_plan + pa_conv, 0, pa_cc);
+    // per group and contig: the contiguous run of chains (models) scored on that contig
+    for (size_t k = 0; k < (size_t)2 * NG * NC; k++) h_cc[k] = make_int2(0, 0);
+    for (int k = 0; k < NCH; k++) {
+        const int g = chains[k].group;
+        int2& e = h_cc[(size_t)g * NC + chains[k].contig];
+        if (e.y == 0) e.x = k;
+        e.y++;
+    }
+    if (use_sched && !h_bbase.empty()) memcpy(h_plan + pa_bb, h_bbase.data(), sizeof(int32_t) * h_bbase.size());
+    if (!dp_order.empty()) memcpy(h_plan + pa_ord, dp_order.data(), sizeof(int32_t) * dp_order.size());
+    if (NCH > 0) memcpy(h_plan + pa_ch, chains.data(), sizeof(ChainDesc) * (size_t)NCH);
+    d_ovl_blk = (const int32_t*)(d_plan + pa_blk);
+    int32_t* const h_blk = (int32_t*)(h_plan + pa_blk);
+    for (int g = 0; g < NG; g++) {
+        int k = g_c0[g];
+        const int64_t nb = ovl_blk0[(size_t)g + 1] - ovl_blk0[(size_t)g];
+        for (int64_t b = 0; b < nb; b++) {
+            const int64_t p0 = g_s0[g] + 256 * b;
+            while (k + 1 < g_c0[g + 1] && chains[(size_t)k + 1].soff <= p0) k++;
+            h_blk[ovl_blk0[(size_t)g] + b] = k - g_c0[g];
+        }
+    }
+    HT(c, hipMemcpyAsync(d_plan, h_plan, pa_copy, hipMemcpyHostToDevice, st));
+    return PGA_OK;
+}
+
+// node scoring of every group that has work; the wave-batch scorer's schedule, or the chain kernels' records, behind it
+int FindCall::score_groups() {
+    sp = ScoreParams{P.closed, P.meta, P.max_overlap, NM, nullptr, nullptr};
+    PINSET(h_conv, uint8_t, "h_conv_flag", (size_t)NG * NC + 1);
+    for (int g = 0; g < NG; g++) {
+        const int nch = g_c0[g + 1] - g_c0[g];
+        const int64_t nn = g_n0[g + 1] - g_n0[g];
+        if (!group_has_work(g) || stage == PGA_STAGE_EXTRACT) continue;
+        // the ORF walks of the coding score run from hexamer tables in LDS, contigs bucketed by the four table columns they need
+        // (PGA_CS_LDS=0: the global-memory form)
+        const void* d_cs_tasks = nullptr; const void* d_cs_entries = nullptr; int n_cs_tasks = 0;
+        const char* cs_env = getenv("PGA_CS_LDS");
+        const char* cs_tn = getenv("PGA_CS_TASK_NODES");
+        const int cs_task_nodes = cs_tn && atoi(cs_tn) >= 256 && atoi(cs_tn) <= 8192 ? atoi(cs_tn) : 5120;     // several tasks per CU and launch (swept again at the end of round 6, one box: 4096 629 us per launch, 4864 581, 5120 586, 5376 584, 5632 600, 6144 592)
+        // PGA_CS_LDS=2 (tests): the LDS form whatever the size of the launch
+        // (single mode as well: one table column, a genome is cut into tasks of `cs_task_nodes` nodes)
+        // (the global-memory form walks every ORF on one lane through the texture path: a launch takes as long as its longest ORF,
+        //  a few hundred microseconds on high-GC sequence whatever its size -- so small launches take the LDS form as well)
+        if (!(cs_env && atoi(cs_env) == 0) && !f->gil_stride.empty()) {
+            std::vector<int32_t>& tk = cs_tk[g]; std::vector<int32_t>& en = cs_en[g];     // alive until the stream is synchronized
+            if (pga_cs_tasks(h_cc + (size_t)g * NC, NC, chains.data(), h_cb(g), f->model_rank.data(), cs_task_nodes, tk, en) && !tk.empty()) {
+                void* p1; void* p2;
+                GROUPBUF(p1, void*, "cs_tasks", tk.size() * 4 + 64, false)
+                GROUPBUF(p2, void*, "cs_entries", en.size() * 4 + 64, false)
+                HT(c, hipMemcpyAsync(p1, tk.data(), tk.size() * 4, hipMemcpyHostToDevice, st));
+                HT(c, hipMemcpyAsync(p2, en.data(), en.size() * 4, hipMemcpyHostToDevice, st));
+                d_cs_tasks = p1; d_cs_entries = p2; n_cs_tasks = (int)(tk.size() / 4);
             }
         }
-        // ---- fresh re-score of winners that were not the first model of their group (ref: lib.pyx:5380-5394)
-        std::vector<ChainDesc> rescore;
-        std::vector<std::vector<ChainDesc>> rs_g(NG);
-        std::vector<int64_t> fin_off(NC, -1);
-        int64_t rs_nodes = 0;
-        for (int i = 0; i < NC; i++) {
+        sp.conv_flag = meta_run ? d_conv + (size_t)g * NC : nullptr;
+        // overlapping starts over (chain, stop node) pairs; for the wave-batch scorer the same pass builds the stops' extras and
+        // the start scorer leaves cscore + sscore, so its per-chain preparation is done when scoring is
+        StopLaunch sl;
+        sl.sbase = d_sb(g); sl.soff_begin = g_s0[g]; sl.n_pairs = g_s0[g + 1] - g_s0[g];
+        sl.n_stops = group_stops(g);
+        // (the path proper; a stage-level call returns the node arrays after any stage, so there every node keeps its thread)
+        sl.starts_only = stage == 0 && !(getenv("PGA_SS_STARTS_ONLY") && atoi(getenv("PGA_SS_STARTS_ONLY")) == 0);
+        sl.n_starts = (int32_t)(group_nodes[g] - sl.n_stops);
+        sl.blk_chain = d_ovl_blk + ovl_blk0[(size_t)g];
+        // the model-major start scoring: its records, chains and tiles live in the context (PGA_SS_MM=0: the model loop).  With one
+        // model loaded the model loop has nothing to walk (one staging, one barrier per workgroup) and stays: on a 200 Mbp genome the
+        // two kernels took 2 ms more (k_mm_place writes a chain's thousands of tiles from one thread)
+        if (sl.starts_only && sl.n_starts > 0 && NM > 1 && !(getenv("PGA_SS_MM") && atoi(getenv("PGA_SS_MM")) == 0)) {
+            std::vector<int64_t> mm_items;
+            sl.mm_tiles = pga_mm_tiles(chains.data() + g_c0[g], nch, h_cb(g), h_sb(g), NM, mm_items);
+            GROUPBUF(sl.mm_rec, void*, "ss_rec", PGA_SS_REC_BYTES * (size_t)sl.n_starts + 64, false)
+            GROUPBUF(sl.mm_chain, void*, "ss_mmchain", PGA_SS_MMCHAIN_BYTES * (size_t)nch + 64, false)
+            GROUPBUF(sl.mm_tile, void*, "ss_mmtile", PGA_SS_MMTILE_BYTES * (size_t)sl.mm_tiles + 64, false)
+            GROUPBUF(sl.mm_scratch, void*, "ss_mmscratch", pga_mm_scratch_bytes(NM, nch), false)
+        }
+        sp.cs_out = nullptr;
+        if (wave_prep) {
+            sl.topo_q2 = wgroups.g[g].q2; sl.ext = wbuf.ext; sp.cs_out = wbuf.cs;
+            if (use_wave) {
+                // (direct mode: the tail reads star_ptr only at the stop nodes, which k_ovl_stops always writes)
+                sl.fill_star_ptr = !(stage == 0 && direct_gather);
+                // (the path proper, node arrays not asked for: a stop node's zero scores are read by nobody -- ScoreParams::lean_stops)
+                sp.lean_stops = (stage == 0 && direct_gather && sl.starts_only && !getenv("PGA_SS_FULL_STOPS")) ? 1 : 0;
+            }       // (segments walked by the wave-batch kernel: the re-scoring and verifying kernels read the node arrays in full)
+        }
+        const bool gil = meta_run || per_contig || n_cs_tasks > 0;
+        pga_launch_score(d_chains + g_c0[g], nch, g_n0[g], nn, d_dig, d_ct, ga[g], (const pga_training*)c->d_models_raw, f->d_msc, c->d_model_const, ca, sp,
+                         d_chains, d_cc + (size_t)g * NC, d_cb(g), NC, (int)group_nodes[g], f->d_sd_lut, st, 0,
+                         gil ? f->d_gil + f->gil_off[g] : nullptr, gil ? f->gil_stride[g] : 0, f->d_model_rank,
+                         d_cs_tasks, n_cs_tasks, d_cs_entries, &sl);
+        if (wave_prep && use_sched) {
+            // (behind the scoring launches: the schedule's headers carry the stop nodes' ranks, which k_ovl_topo writes there)
+            if (g < 4) HT(c, hipEventRecord(f->e_aux[4 * g + 2], st));
+            pga_launch_dpw_sched(wgroups.g[g], d_cb(g), d_bbase + (size_t)g * (NC + 1), NC, max_batches[g], st);
+            if (g < 4) HT(c, hipEventRecord(f->e_aux[4 * g + 3], st));
+            HT(c, hipMemcpyAsync(h_scur + 2 * g, wgroups.g[g].scur, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        }
+        NodeArrays na{ga[g].ndx, ga[g].stop_val, ga[g].type, ga[g].strand, ca.cscore, ca.sscore, ca.rscore, ca.uscore, ca.star_ptr};
+        if (!use_wave && stage == 0) pga_launch_dp_prepare(d_chains + g_c0[g], nch, g_n0[g], nn, na, c->d_model_const, dp, st);
+    }
+    return PGA_OK;
+}
+
+// what both copy-outs of node arrays (the stage-level one, the winners') fill alike; every source points at the contig's first node
+void copy_node_topology(pga_nodes& N, const int n, const int32_t* ndx, const int32_t* stop_val, const uint8_t* type, const int8_t* strand, const uint8_t* edge) {
+    memcpy(N.ndx, ndx, 4 * (size_t)n); memcpy(N.stop_val, stop_val, 4 * (size_t)n);
+    memcpy(N.type, type, n); memcpy(N.strand, strand, n); memcpy(N.edge, edge, n);
+}
+void copy_node_scores(pga_nodes& N, const int n, const double* const src64[6] /* cscore, sscore, rscore, uscore, tscore, mot_score */, const int32_t* mot_ndx,
+                      const uint8_t* rbs, const uint8_t* mot_len, const uint8_t* mot_spacer, const uint8_t* mot_spacendx, const float* gc_cont) {
+    double* const dst64[6] = {N.cscore, N.sscore, N.rscore, N.uscore, N.tscore, N.mot_score};
+    for (int q = 0; q < 6; q++) memcpy(dst64[q], src64[q], 8 * (size_t)n);
+    memcpy(N.mot_ndx, mot_ndx, 4 * (size_t)n); memcpy(N.rbs, rbs, 2 * (size_t)n); memcpy(N.mot_len, mot_len, n);
+    memcpy(N.mot_spacer, mot_spacer, n); memcpy(N.mot_spacendx, mot_spacendx, n); memcpy(N.gc_cont, gc_cont, 4 * (size_t)n);
+}
+void reset_dp_fields(pga_nodes& N, const int n) { for (int j = 0; j < n; j++) { N.traceb[j] = -1; N.tracef[j] = -1; N.ov_mark[j] = -1; } }    // ref: reset_node_scores
+
+// ---- stage-level call: bring the node arrays home as they are now and stop ---------------
+int FindCall::return_stage_nodes(pga_result** out) {
+    const int64_t nn = tot_chain_nodes;          // every group's nodes; a contig's chain sits at the same offset in both layouts
+    PINBUF(hs_i32, int32_t, "hs_i32", 6 * nn + 8);         // ndx, stop_val, mot_ndx, star_ptr[3]
+    PINBUF(hs_f64, double, "hs_f64", 6 * nn + 8);          // cscore, sscore, rscore, uscore, tscore, mot_score
+    PINBUF(hs_u8, uint8_t, "hs_u8", 10 * nn + 8);          // type, strand, edge, rbs[2], mot_len, mot_spacer, mot_spacendx
+    PINBUF(hs_f32, float, "hs_f32", nn + 8);
+    const bool scored = stage >= PGA_STAGE_SCORE;
+    for (int g = 0; g < NG; g++) {
+        const int64_t gn = group_nodes[g], o = g_n0[g];
+        if (gn == 0) continue;
+        HT(c, hipMemcpyAsync(hs_i32 + o, ga[g].ndx, 4 * gn, hipMemcpyDeviceToHost, st));
+        HT(c, hipMemcpyAsync(hs_i32 + nn + o, ga[g].stop_val, 4 * gn, hipMemcpyDeviceToHost, st));
+        HT(c, hipMemcpyAsync(hs_u8 + o, ga[g].type, gn, hipMemcpyDeviceToHost, st));
+        HT(c, hipMemcpyAsync(hs_u8 + nn + o, ga[g].strand, gn, hipMemcpyDeviceToHost, st));
+        if (!scored) HT(c, hipMemcpyAsync(hs_u8 + 2 * nn + o, ga[g].edge0, gn, hipMemcpyDeviceToHost, st));
+        if (scored) HT(c, hipMemcpyAsync(hs_f32 + o, ga[g].gc_cont, 4 * gn, hipMemcpyDeviceToHost, st));
+    }
+    if (nn > 0 && scored) {
+        HT(c, hipMemcpyAsync(hs_u8 + 2 * nn, ca.edge, nn, hipMemcpyDeviceToHost, st));
+        HT(c, hipMemcpyAsync(hs_i32 + 2 * nn, ca.mot_ndx, 4 * nn, hipMemcpyDeviceToHost, st));
+        HT(c, hipMemcpyAsync(hs_i32 + 3 * nn, ca.star_ptr, 12 * nn, hipMemcpyDeviceToHost, st));
+        double* const src64[6] = {ca.cscore, ca.sscore, ca.rscore, ca.uscore, ca.tscore, ca.mot_score};
+        for (int q = 0; q < 6; q++) HT(c, hipMemcpyAsync(hs_f64 + q * nn, src64[q], 8 * nn, hipMemcpyDeviceToHost, st));
+        HT(c, hipMemcpyAsync(hs_u8 + 3 * nn, ca.rbs, 2 * nn, hipMemcpyDeviceToHost, st));
+        HT(c, hipMemcpyAsync(hs_u8 + 5 * nn, ca.mot_len, nn, hipMemcpyDeviceToHost, st));
+        HT(c, hipMemcpyAsync(hs_u8 + 6 * nn, ca.mot_spacer, nn, hipMemcpyDeviceToHost, st));
+        HT(c, hipMemcpyAsync(hs_u8 + 7 * nn, ca.mot_spacendx, nn, hipMemcpyDeviceToHost, st));
+    }
+    if (const int rc = sync()) return rc;
+    f->last.d_dig = d_dig; f->last.ga = ga[0]; f->last.ca = ca; f->last.n_nodes = (int)nn; f->last.len = batch->ct[0].len;
+    R->nodes.resize(NC);
+    for (int i = 0; i < NC; i++) {
+        pga_nodes& N = R->nodes[i];
+        const int g = multi ? cgrp[i] : 0;
+        const int64_t oo = g_n0[g] + h_cb(g)[i]; const int n = contig_nodes(g, i);
+        R->contigs[i].model = stage == PGA_STAGE_EXTRACT ? -1 : (per_contig ? model_of_contig[i] : 0); R->contigs[i].n_nodes = n;
+        if (int rc = alloc_nodes(R, N, n)) return rc;
+        copy_node_topology(N, n, hs_i32 + oo, hs_i32 + nn + oo, hs_u8 + oo, (const int8_t*)(hs_u8 + nn + oo), hs_u8 + 2 * nn + oo);
+        reset_dp_fields(N, n);
+        if (!scored) continue;
+        if (stage >= PGA_STAGE_OVERLAP) memcpy(N.star_ptr, hs_i32 + 3 * nn + 3 * oo, 12 * (size_t)n);
+        const double* const src64[6] = {hs_f64 + oo, hs_f64 + nn + oo, hs_f64 + 2 * nn + oo, hs_f64 + 3 * nn + oo, hs_f64 + 4 * nn + oo, hs_f64 + 5 * nn + oo};
+        copy_node_scores(N, n, src64, hs_i32 + 2 * nn + oo, hs_u8 + 3 * nn + 2 * oo, hs_u8 + 5 * nn + oo, hs_u8 + 6 * nn + oo, hs_u8 + 7 * nn + oo, hs_f32 + oo);
+    }
+    return publish_result(out);
+}
+
+// one DP launch over the chains of every group (chains are independent, the more in flight the better), the read-back, the relaunch
+// when a step schedule did not fit, the statistics and timings
+int FindCall::score_connections() {
+    PINBUF(h_segflags, int32_t, "h_segflags", (size_t)(PGA_SEG_ROUNDS + 2) * NCH + 1);      // [rounds][chains] flags, [chains] spine sizes, [chains] a round's verdict
+    if (segmented && !(getenv("PGA_DP_SEG_READBACK") && atoi(getenv("PGA_DP_SEG_READBACK")) == 0)) seg_dev.h_round = h_segflags + (size_t)(PGA_SEG_ROUNDS + 1) * NCH;
+    HT(c, hipEventRecord(f->e_dp0[0], st));
+    if (use_wave) {
+        // PGA_DP_PROFILE=1: cycles per batch phase of every 64th chain (a synchronising debug aid)
+        if (getenv("PGA_DP_PROFILE")) {
+            DEVBUF(d_prof, unsigned long long, "dp_prof", 16);
+            HT(c, hipMemsetAsync(d_prof, 0, 128, st));
+            dp.prof = d_prof;
+        }
+        pga_launch_dp_wave(d_chains, NCH, wgroups, c->d_model_const, dp, wbuf, st, d_dp_order, (int)dp_order.size(), use_sched);
+        if (dp.prof != nullptr) {
+            unsigned long long pr[16];
+            HT(c, hipStreamSynchronize(st));
+            HT(c, hipMemcpy(pr, dp.prof, 128, hipMemcpyDeviceToHost));
+            const double nbp = pr[7] ? (double)pr[7] : 1.0;
+            fprintf(stderr, "[pga dp profile] %s, %d chains, batches sampled=%llu, cycles/batch: load=%.0f near steps=%.0f far gene ends=%.0f "
+                            "carries=%.0f chains=%.0f walk=%.0f finalize=%.0f | total=%.0f\n", use_sched ? "k_dp_wave" : "k_dpw_dyn", NCH, pr[7], pr[0] / nbp, pr[1] / nbp, pr[2] / nbp, pr[3] / nbp,
+                    pr[4] / nbp, pr[5] / nbp, pr[6] / nbp, (pr[0] + pr[1] + pr[2] + pr[3] + pr[4] + pr[5] + pr[6]) / nbp);
+            dp.prof = nullptr;
+        }
+    }
+    else pga_launch_dp(d_chains, NCH, c->d_model_const, dp, 1, st, segmented ? &seg_dev : nullptr);
+    HT(c, hipEventRecord(f->e_dp1[0], st));
+    HT(c, hipMemcpyAsync(h_maxscore, dp.max_score, sizeof(double) * 2 * (size_t)dp_slots, hipMemcpyDeviceToHost, st));       // scores, indices, path starts
+    if (meta_run) HT(c, hipMemcpyAsync(h_conv, d_conv, (size_t)NG * NC, hipMemcpyDeviceToHost, st));
+    if (segmented) {
+        HT(c, hipMemcpyAsync(h_segflags, seg_dev.flags, sizeof(int32_t) * PGA_SEG_ROUNDS * NCH, hipMemcpyDeviceToHost, st));
+        HT(c, hipMemcpyAsync(h_segflags + (size_t)PGA_SEG_ROUNDS * NCH, seg_dev.nsp, sizeof(int32_t) * NCH, hipMemcpyDeviceToHost, st));
+    }
+    if (const int rc = sync()) return rc;
+    uint32_t sched_missed = 0;
+    double dp_first_ms = 0.0;
+    if (use_sched) {
+        // a schedule that did not fit its buffer (node-dense input: more than two slots per node on average): the same launch again
+        // with the kernel that works the lane masks out itself
+        for (int g = 0; g < NG; g++) if (group_has_work(g)) sched_missed += h_scur[2 * g + 1];
+        if (getenv("PGA_DPW_SCHED_DEBUG")) for (int g = 0; g < NG; g++) fprintf(stderr, "[pga dpw sched] group %d: %u batches missed\n", g, h_scur[2 * g + 1]);
+        if (sched_missed && use_wave) {      // (segments walked by the wave-batch kernel: a missed batch ends its segment's claims, the verification does the rest)
+            // (the first launch's time counts: t_dp_ms covers both)
+            { float ms = 0; HT(c, hipEventElapsedTime(&ms, f->e_dp0[0], f->e_dp1[0])); dp_first_ms = ms; }
+            HT(c, hipEventRecord(f->e_dp0[0], st));
+            pga_launch_dp_wave(d_chains, NCH, wgroups, c->d_model_const, dp, wbuf, st, d_dp_order, (int)dp_order.size(), false);
+            HT(c, hipEventRecord(f->e_dp1[0], st));
+            HT(c, hipMemcpyAsync(h_maxscore, dp.max_score, sizeof(double) * 2 * (size_t)dp_slots, hipMemcpyDeviceToHost, st));
+            if (const int rc = sync()) return rc;
+        }
+    }
+    pga_dp_note_stats(c, segmented ? &seg_plan : nullptr, h_segflags, NCH);
+    c->dp_stats[6] = use_sched ? 1 : 0; c->dp_stats[7] = (int32_t)sched_missed;
+    if (segmented && getenv("PGA_DP_SEG_DEBUG")) {
+        fprintf(stderr, "[pga dp-seg] %d chains cut into %d segments (<= %d nodes each); nodes rejected per round: %d %d %d; walked serially: %d; spine:",
+                seg_dev.n_big, seg_dev.n_segs, seg_dev.max_seg_nodes, c->dp_stats[2], c->dp_stats[3], c->dp_stats[4], c->dp_stats[5]);
+        for (int k : seg_plan.big) fprintf(stderr, " %d/%d", h_segflags[(size_t)PGA_SEG_ROUNDS * NCH + k], chains[(size_t)k].n);
+        fprintf(stderr, "\n");
+    }
+    { float ms = 0; HT(c, hipEventElapsedTime(&ms, f->e_dp0[0], f->e_dp1[0])); R->pub.t_dp_ms = NCH > 0 ? ms + dp_first_ms : 0.0; }
+    c->dp_timings[0] = R->pub.t_dp_ms; c->dp_timings[1] = c->dp_timings[2] = c->dp_timings[3] = 0.0;
+    if (wave_prep) for (int g = 0; g < NG && g < 4; g++) {
+        if (!group_has_work(g)) continue;
+        float ms = 0;
+        if (hipEventElapsedTime(&ms, f->e_aux[4 * g], f->e_aux[4 * g + 1]) == hipSuccess) c->dp_timings[1] += ms;
+        if (use_sched && hipEventElapsedTime(&ms, f->e_aux[4 * g + 2], f->e_aux[4 * g + 3]) == hipSuccess) c->dp_timings[2] += ms;
+    }
+    return PGA_OK;
+}
+
+// ---- pick the winning model per contig (the rules: find_plan.h) ---
+void FindCall::pick_winners() {
+    pga_plan::pick_winners(NC, NM, P.meta != 0, chains.data(), NCH, h_maxscore, h_ipath, use_sets ? set_of.data() : nullptr, NS,
+                           c->model_scores.data(), c->set_model.data(), c->set_score.data(), win_chain);
+}
+
+// ---- fresh re-score of winners that were not the first model of their group (who: find_plan.h)
+int FindCall::rescore_winners() {
+    pga_plan::plan_rescore(NC, NG, P.meta != 0, chains.data(), win_chain.data(), h_conv, f->model_group.data(), tot_chain_nodes, *this);
+    if (rescore.empty()) return PGA_OK;
+    HT(c, hipMemcpyAsync(d_chains + NCH, rescore.data(), sizeof(ChainDesc) * rescore.size(), hipMemcpyHostToDevice, st));
+    int2* h_cc2 = h_cc + (size_t)NG * NC;
+    for (size_t k = 0; k < rescore.size(); k++)
+        h_cc2[(size_t)f->model_group[rescore[k].model] * NC + rescore[k].contig] = make_int2(NCH + (int)k, 1);
+    HT(c, hipMemcpyAsync(d_cc + (size_t)NG * NC, h_cc2, sizeof(int2) * (size_t)NG * NC, hipMemcpyHostToDevice, st));
+    sp.conv_flag = nullptr; sp.cs_out = nullptr;
+    for (int g = 0; g < NG; g++) {
+        const int nch = r_c0[g + 1] - r_c0[g]; const int64_t nn = r_n0[g + 1] - r_n0[g];
+        if (nch == 0 || nn == 0) continue;
+        pga_launch_score(d_chains + NCH + r_c0[g], nch, r_n0[g], nn, d_dig, d_ct, ga[g], (const pga_training*)c->d_models_raw, f->d_msc, c->d_model_const, ca, sp,
+                         d_chains, d_cc + (size_t)NG * NC + (size_t)g * NC, d_cb(g), NC, (int)group_nodes[g], f->d_sd_lut, st, 1);
+    }
+    return PGA_OK;
+}
+
+// ---- gather the winners (the layout: find_plan.h) ------------------------------------------------
+// the winners' final-pass fields only travel to the gathered arrays when somebody reads more of them than the two nodes
+// of every gene: the caller (node arrays) or the host tail's attribute fetch (PGA_FULL_GATHER=1 keeps the full gather: tests)
+int FindCall::gather_winners() {
+    pga_plan::plan_gather(NC, NG, chains.data(), win_chain.data(), fin_off.data(), *this);
+    // one device arena (and a pinned mirror, used only when the caller asks for the node arrays)
+    {
+        const size_t n = (size_t)out_nodes + 1;
+        size_t off = 0;
+        auto reserve = [&](size_t elem, size_t mult) { const size_t at = off; off += ((elem * mult * n + 255) / 256) * 256; return at; };
+#define OFFS(field, type, mult) const size_t at_##field = reserve(sizeof(type), mult);
+        OFFS(ndx, int32_t, 1) OFFS(stop_val, int32_t, 1) OFFS(type, uint8_t, 1) OFFS(strand, int8_t, 1)
+        OFFS(edge_dp, uint8_t, 1) OFFS(cscore_dp, double, 1) OFFS(sscore_dp, double, 1) OFFS(rscore_dp, double, 1) OFFS(uscore_dp, double, 1) OFFS(tscore_dp, double, 1)
+        OFFS(star_ptr, int32_t, 3) OFFS(traceb, int32_t, 1) OFFS(ov_mark, int8_t, 1) OFFS(score, double, 1)
+        arena_dp = off;
+        OFFS(gc_cont, float, 1)
+        OFFS(edge, uint8_t, 1) OFFS(cscore, double, 1) OFFS(sscore, double, 1) OFFS(rscore, double, 1) OFFS(uscore, double, 1) OFFS(tscore, double, 1) OFFS(mot_score, double, 1)
+        OFFS(mot_ndx, int32_t, 1) OFFS(rbs, uint8_t, 2) OFFS(mot_len, uint8_t, 1) OFFS(mot_spacer, uint8_t, 1) OFFS(mot_spacendx, uint8_t, 1)
+        arena_all = off;
+        void* dp__; void* hp__;
+        { int rc__ = ensure_dev(c, "o_arena", arena_all + 256, &dp__); if (rc__) return rc__; }
+        { int rc__ = ensure_pin(c, "h_arena", arena_all + 256, &hp__); if (rc__) return rc__; }
+        char* db = (char*)dp__; char* hb = (char*)hp__;
+#define OB(field, type) o.field = (type*)(db + at_##field); h.field = (type*)(hb + at_##field);
+        OB(ndx, int32_t) OB(stop_val, int32_t) OB(type, uint8_t) OB(strand, int8_t) OB(gc_cont, float)
+        OB(edge_dp, uint8_t) OB(cscore_dp, double) OB(sscore_dp, double) OB(rscore_dp, double) OB(uscore_dp, double) OB(tscore_dp, double)
+        OB(star_ptr, int32_t) OB(traceb, int32_t) OB(ov_mark, int8_t) OB(score, double)
+        OB(edge, uint8_t) OB(cscore, double) OB(sscore, double) OB(rscore, double) OB(uscore, double) OB(tscore, double) OB(mot_score, double)
+        OB(mot_ndx, int32_t) OB(rbs, uint8_t) OB(mot_len, uint8_t) OB(mot_spacer, uint8_t) OB(mot_spacendx, uint8_t)
+    }
+    // lean and the device tail: gather only what the tail writes
+    o.direct = direct_gather ? 1 : 0;
+    for (int g = 0; g < 4; g++) {
+        const bool in = g < NG;
+        o.g_ndx[g] = in ? ga[g].ndx : nullptr; o.g_stop_val[g] = in ? ga[g].stop_val : nullptr;
+        o.g_type[g] = in ? ga[g].type : nullptr; o.g_strand[g] = in ? ga[g].strand : nullptr;
+    }
+    o.c_edge = ca.edge; o.c_cscore = ca.cscore; o.c_rscore = ca.rscore; o.c_uscore = ca.uscore; o.c_tscore = ca.tscore;
+    o.c_star_ptr = ca.star_ptr; o.d_score = dp.score;
+    h.direct = 0;
+    size_t nwin = 0; for (int g = 0; g < NG; g++) nwin += wg[g].size();
+    DEVBUF(d_win, WinDesc, "d_win", nwin + 1);
+    size_t k0 = 0;
+    for (int g = 0; g < NG; g++) {
+        if (wg[g].empty()) continue;
+        HT(c, hipMemcpyAsync(d_win + k0, wg[g].data(), sizeof(WinDesc) * wg[g].size(), hipMemcpyHostToDevice, st));
+        const int64_t nn = w_o0[g + 1] - w_o0[g];
+        if (nn > 0)
+            hipLaunchKernelGGL(k_gather_winners, dim3((unsigned)((nn + 255) / 256)), dim3(256), 0, st, d_win + k0, (int)wg[g].size(), w_o0[g], nn, ga[g], ca, dp, o, lean_gather ? 1 : 0);
+        k0 += wg[g].size();
+    }
+    for (int i = 0; i < NC; i++) if (win_chain[i] >= 0) max_n = std::max(max_n, chains[win_chain[i]].n);
+    return PGA_OK;
+}
+
+// the contigs of the result from the winners and the genes the tail found per contig; gene_begin (or nullptr): a copy of every contig's first gene
+int64_t FindCall::contig_results(const int32_t* n_genes, int64_t* gene_begin) {
+    int64_t ngenes = 0;
+    for (int i = 0; i < NC; i++) {
+        pga_contig_result& cr = R->contigs[i];
+        const int k = win_chain[i];
+        if (gene_begin) gene_begin[i] = ngenes;
+        cr.gene_begin = ngenes; cr.n_genes = n_genes[i];
+        ngenes += cr.n_genes;
+        if (k < 0) { cr.model = -1; continue; }
+        cr.model = chains[k].model; cr.n_nodes = chains[k].n;
+        cr.score = P.meta ? 0.0 : (h_ipath[k] >= 0 ? h_maxscore[k] : 0.0);
+    }
+    return ngenes;
+}
+
+// PGA_TAIL=host (a cross-check): the winners' DP-pass fields come home and host threads walk them -- traceback untangling, bad-gene
+// elimination, gene list, start tweaks per contig; the fields of every gene's two nodes come with a second, small gather
+int FindCall::run_host_tail() {
+    tracef.assign((size_t)out_nodes + 1, -1);
+    elim.assign((size_t)out_nodes + 1, 0);
+    if (out_nodes > 0)
+        HT(c, hipMemcpyAsync(h.ndx, o.ndx, P.want_nodes == 1 ? arena_all : arena_dp, hipMemcpyDeviceToHost, st));   // arena starts at `ndx`
+    if (const int rc = stop_clock()) return rc;
+
+    tm->mark("gather+d2h+sync");
+    // ---- host tail per contig ------------------------------------------------------------------
+    std::vector<std::vector<GeneRec>> cg(NC);
+    std::unique_ptr<int32_t[]> pathbuf(new int32_t[(size_t)out_nodes + 1]);      // written before it is read: no zero fill
+    std::atomic<int> next(0);
+    auto worker = [&]() {
+        for (;;) {
+            const int i = next.fetch_add(1);
+            if (i >= NC) break;
             const int k = win_chain[i];
             if (k < 0) continue;
-            // a later model of a run sees the edge flags its predecessors left (lib.pyx:2424-2434); where the contig has no start
-            // node that scoring turns into an edge node, that state is the fresh one and the winning pass already is the re-score
-            if (!P.meta || chains[k].first || !h_conv[(size_t)f->model_group[chains[k].model] * NC + i]) { fin_off[i] = chains[k].off; continue; }
-            ChainDesc ch = chains[k]; ch.first = 1;
-            ch.raw_off = chains[k].off;                 // same contig, same model: the ORF walk of the winning pass stands
-            rs_g[f->model_group[ch.model]].push_back(ch);
-        }
-        std::vector<int> r_c0(NG + 1, 0); std::vector<int64_t> r_n0(NG + 1, 0);
-        for (int g = 0; g < NG; g++) {
-            r_c0[g] = (int)rescore.size(); r_n0[g] = tot_chain_nodes + rs_nodes;
-            for (ChainDesc ch : rs_g[g]) { ch.off = tot_chain_nodes + rs_nodes; fin_off[ch.contig] = ch.off; rs_nodes += ch.n; rescore.push_back(ch); }
-        }
-        r_c0[NG] = (int)rescore.size(); r_n0[NG] = tot_chain_nodes + rs_nodes;
-        if (!rescore.empty()) {
-            HT(c, hipMemcpyAsync(d_chains + NCH, rescore.data(), sizeof(ChainDesc) * rescore.size(), hipMemcpyHostToDevice, st));
-            int2* h_cc2 = h_cc + (size_t)NG * NC;
-            for (size_t k = 0; k < rescore.size(); k++)
-                h_cc2[(size_t)f->model_group[rescore[k].model] * NC + rescore[k].contig] = make_int2(NCH + (int)k, 1);
-            HT(c, hipMemcpyAsync(d_cc + (size_t)NG * NC, h_cc2, sizeof(int2) * (size_t)NG * NC, hipMemcpyHostToDevice, st));
-            sp.conv_flag = nullptr; sp.cs_out = nullptr;
-            for (int g = 0; g < NG; g++) {
-                const int nch = r_c0[g + 1] - r_c0[g]; const int64_t nn = r_n0[g + 1] - r_n0[g];
-                if (nch == 0 || nn == 0) continue;
-                pga_launch_score(d_chains + NCH + r_c0[g], nch, r_n0[g], nn, d_dig, d_ct, ga[g], d_models, f->d_msc, c->d_model_const, ca, sp,
-                                 d_chains, d_cc + (size_t)NG * NC + (size_t)g * NC, d_cbase + (size_t)g * (NC + 1), NC, (int)group_nodes[g], f->d_sd_lut, st, 1);
+            const int64_t oo = out_off[i];
+            NodeView v{chains[k].n, h.ndx + oo, h.stop_val + oo, h.type + oo, h.strand + oo, h.edge_dp + oo,
+                       h.cscore_dp + oo, h.sscore_dp + oo, h.rscore_dp + oo, h.uscore_dp + oo, h.tscore_dp + oo,
+                       h.star_ptr + 3 * oo, h.traceb + oo, tracef.data() + oo, h.ov_mark + oo, h.score + oo, elim.data() + oo};
+            const int mx = h_maxidx[k];
+            const double st_wt = c->models[chains[k].model].st_wt;
+            const bool sub = NC == 1 && getenv("PGA_TIMING");
+            auto now = [] { return std::chrono::steady_clock::now(); };
+            auto t0 = now(), t1 = t0, t2 = t0, t3 = t0;
+            if (v.n > 0 && mx >= 0) {
+                int32_t* pl = pathbuf.get() + oo;
+                const int cnt = untangle(v, mx, pl);
+                t1 = now();
+                if (v.traceb[mx] != -1) {
+                    if (NC < 4) eliminate_bad_genes_mt(v, pl, cnt, st_wt, f->pool, 16); else eliminate_bad_genes(v, pl, cnt, st_wt);
+                    t2 = now();
+                    cg[i].resize((size_t)cnt / 2 + 2);           // two path nodes per gene
+                    cg[i].resize((size_t)extract_genes(v, pl, cnt, cg[i].data()));
+                }
+            }
+            t3 = now();
+            tweak_final_starts(v, cg[i], st_wt, P.max_overlap, NC < 4 ? 32 : 1, &f->pool);
+            if (sub) {
+                auto ms = [](auto a, auto b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
+                fprintf(stderr, "[pga timing] host tail: untangle=%.2f eliminate=%.2f extract=%.2f tweak=%.2f ms\n", ms(t0, t1), ms(t1, t2), ms(t2, t3), ms(t3, now()));
             }
         }
+    };
+    auto run_parallel = [&](const std::function<void()>& fn) {
+        int nt = (int)std::min<unsigned>(std::max(1u, std::thread::hardware_concurrency()), 32u);
+        if (NC < 4) nt = 1;
+        if (nt == 1) fn(); else f->pool.run(fn, nt);
+    };
+    run_parallel(worker);
+    // the tail moved start scores (eliminate_bad_genes): the arena kept on the device must say what the host copy says
+    if (P.want_nodes && out_nodes > 0)
+        HT(c, hipMemcpyAsync(o.sscore_dp, h.sscore_dp, sizeof(double) * (size_t)out_nodes, hipMemcpyHostToDevice, st));
+    tm->mark("host_tail");
+    // ---- results -----------------------------------------------------------------------------------
+    std::vector<int32_t> n_genes((size_t)NC);
+    for (int i = 0; i < NC; i++) n_genes[i] = (int32_t)cg[i].size();
+    const int64_t ngenes = contig_results(n_genes.data(), nullptr);
+    R->genes.resize((size_t)ngenes);
+    // fields of the gene's start / stop nodes as of the final pass: a second, small gather
+    PINBUF(h_gidx, int64_t, "h_gidx", 2 * ngenes + 1);
+    PINBUF(h_attr, GeneNodeAttr, "h_attr", 2 * ngenes + 1);
+    if (ngenes > 0) {
+        DEVBUF(d_gidx, int64_t, "d_gidx", 2 * ngenes + 1);
+        DEVBUF(d_attr, GeneNodeAttr, "d_attr", 2 * ngenes + 1);
+        for (int i = 0; i < NC; i++) {
+            int64_t gi = R->contigs[i].gene_begin;
+            for (const GeneRec& gr : cg[i]) { h_gidx[2 * gi] = out_off[i] + gr.start_ndx; h_gidx[2 * gi + 1] = out_off[i] + gr.stop_ndx; gi++; }
+        }
+        HT(c, hipMemcpyAsync(d_gidx, h_gidx, sizeof(int64_t) * 2 * ngenes, hipMemcpyHostToDevice, st));
+        hipLaunchKernelGGL(k_gather_gene_nodes, dim3((unsigned)((2 * ngenes + 255) / 256)), dim3(256), 0, st, d_gidx, (int)(2 * ngenes), o, d_attr);
+        HT(c, hipMemcpyAsync(h_attr, d_attr, sizeof(GeneNodeAttr) * 2 * ngenes, hipMemcpyDeviceToHost, st));
+        if (const int rc = sync()) return rc;
+    }
+    tm->mark("gene_attrs");
+    std::atomic<int> next2(0);
+    auto filler = [&]() {
+        for (;;) {
+            const int i = next2.fetch_add(1);
+            if (i >= NC) break;
+            const int k = win_chain[i];
+            if (k < 0) continue;
+            const int64_t oo = out_off[i];
+            const bool single = !P.meta;
+            int64_t gi = R->contigs[i].gene_begin;
+            for (const GeneRec& gr : cg[i]) {
+                pga_gene& G = R->genes[(size_t)gi];
+                const GeneNodeAttr& as = h_attr[2 * gi]; const GeneNodeAttr& ae = h_attr[2 * gi + 1];
+                gi++;
+                memset(&G, 0, sizeof G);
+                const int64_t sn = oo + gr.start_ndx, en = oo + gr.stop_ndx;
+                G.contig = i; G.begin = gr.begin; G.end = gr.end; G.start_ndx = gr.start_ndx; G.stop_ndx = gr.stop_ndx;
+                G.strand = h.strand[sn];
+                // single mode keeps the nodes of the DP pass (ref: lib.pyx:5296-5311); meta mode re-scores (5380-5394)
+                const uint8_t se = single ? h.edge_dp[sn] : as.edge, ee = single ? h.edge_dp[en] : ae.edge;
+                G.partial_begin = G.strand == 1 ? se : ee; G.partial_end = G.strand == 1 ? ee : se;
+                G.start_type = se ? 3 : h.type[sn];
+                G.rbs[0] = as.rbs0; G.rbs[1] = as.rbs1;
+                G.mot_len = as.mot_len; G.mot_spacer = as.mot_spacer; G.mot_ndx = as.mot_ndx; G.mot_score = as.mot_score;
+                G.gc_cont = as.gc_cont;
+                G.cscore = single ? h.cscore_dp[sn] : as.cscore; G.sscore = single ? h.sscore_dp[sn] : as.sscore;
+                G.rscore = single ? h.rscore_dp[sn] : as.rscore; G.uscore = single ? h.uscore_dp[sn] : as.uscore;
+                G.tscore = single ? h.tscore_dp[sn] : as.tscore;
+            }
+        }
+    };
+    run_parallel(filler);
+    if (coding) {
+        // the records are on the host already, so they are counted here -- a union of intervals per contig, the same definition as
+        // k_cover_genes / k_count_cover
+        std::vector<std::pair<int32_t, int32_t>> iv;
+        for (int i = 0; i < NC; i++) {
+            iv.clear();
+            const int32_t len = batch->ct[i].len;
+            for (const GeneRec& gr : cg[i]) {
+                const int32_t b = std::max<int32_t>(gr.begin, 1), e = std::min<int32_t>(gr.end, len);
+                if (b <= e) iv.emplace_back(b, e);
+            }
+            std::sort(iv.begin(), iv.end());
+            int64_t n = 0; int32_t hi = 0;          // positions 1 .. hi are already counted
+            for (const auto& x : iv) {
+                if (x.second <= hi) continue;
+                n += x.second - std::max(x.first - 1, hi);
+                hi = x.second;
+            }
+            coding[i] = n;
+        }
+    }
+    return PGA_OK;
+}
+
+// the work arrays of the device tail
+struct TailBufs {
+    TailDesc* d_td; int32_t* d_tracef; uint8_t* d_elim; GeneRec* d_gene0; GeneRec* d_gene1; GeneRec* d_gene2; int32_t* d_ngenes;
+    int32_t* d_path; uint8_t* d_changed; int32_t* d_nchanged;
+    int64_t n_slots; unsigned init_blocks;
+};
+
+// PGA_TAIL=par (the default): traceback untangling, bad-gene elimination and the gene list of every winning chain by parallel steps
+// over the gathered nodes (tail.inl)
+int FindCall::launch_tail_paths(const TailBufs& t) {
+    bool tail_inited = false;
+    for (int i = 0; i < NC; i++) if (win_chain[i] >= 0 && chains[win_chain[i]].n > 0) segs.push_back(TpSeg{out_off[i], chains[win_chain[i]].n, i});
+    std::sort(segs.begin(), segs.end(), [](const TpSeg& a, const TpSeg& b) { return a.off < b.off; });
+    if (!segs.empty() && out_nodes > 0) {
+        if (out_nodes >= (1ll << 30)) { c->err = "pga_find_genes: more than 2^30 nodes in the winning chains of one batch"; return PGA_EINVAL; }
+        int levels = 1;
+        while ((1ll << levels) < max_n) levels++;
+        const unsigned nblk = (unsigned)((out_nodes + 255) / 256);
+        const bool tp_steps = getenv("PGA_TP_STEPS") != nullptr;      // the many-launch form also for short chains (cross-check)
+        const bool tp_one = max_n <= TP_SMALL_MAX && !tp_steps;
+        const int64_t tpn = tp_one ? 0 : out_nodes;                   // the per-node work arrays of the many-launch form
+        DEVBUF(tp_seg, TpSeg, "tp_seg", segs.size()) DEVBUF(tp_up, int32_t, "tp_up", (size_t)2 * tpn)
+        DEVBUF(tp_mark, uint8_t, "tp_mark", tpn) DEVBUF(tp_slots, int32_t, "tp_slots", tpn)
+        DEVBUF(tp_ins, int32_t, "tp_ins", 2 * tpn) DEVBUF(tp_excl, int32_t, "tp_excl", tpn + 1)
+        DEVBUF(tp_bsum, int32_t, "tp_bsum", nblk + 1) DEVBUF(tp_cnt, int32_t, "tp_cnt", segs.size())
+        HT(c, hipMemcpyAsync(tp_seg, segs.data(), sizeof(TpSeg) * segs.size(), hipMemcpyHostToDevice, st));
+        hipLaunchKernelGGL(k_tail_init, dim3(t.init_blocks), dim3(256), 0, st, t.d_tracef, t.d_elim, out_nodes, t.d_nchanged, t.d_ngenes, NC,
+                           tp_one ? (int32_t*)nullptr : tp_cnt, (int)segs.size());
+        tail_inited = true;
+        const TpWork tw{tp_seg, (int)segs.size(), out_nodes, levels, tp_up, tp_mark, tp_slots, tp_ins, tp_excl, tp_bsum, tp_cnt};
+        const dim3 grid(nblk), blk(256);
+        if (tp_one) {
+            const int cap = (int)((max_n + 63) & ~63ll);
+            hipLaunchKernelGGL(k_tp_small, dim3((unsigned)segs.size()), dim3(max_n <= 2048 ? 64 : 256), sizeof(int32_t) * 3 * (size_t)cap, st, tw, t.d_td, o,
+                               t.d_tracef, t.d_elim, t.d_gene0, t.d_ngenes, cap);
+        } else {
+            hipLaunchKernelGGL(k_tp_init, grid, blk, 0, st, tw, t.d_td, o);
+            // pointer jumping: 2^levels >= the longest chain; eight hops per launch while three levels or more are left (PGA_TP_JUMP8=0: doubling only)
+            {
+                const bool j8 = !(getenv("PGA_TP_JUMP8") && atoi(getenv("PGA_TP_JUMP8")) == 0);
+                int k = 0;
+                for (int left = levels; left > 0; k++) {
+                    const int32_t* in = tp_up + (size_t)(k & 1) * out_nodes; int32_t* outp = tp_up + (size_t)((k + 1) & 1) * out_nodes;
+                    if (j8 && left >= 3) { hipLaunchKernelGGL(k_tp_jump8, grid, blk, 0, st, tw, in, outp); left -= 3; }
+                    else { hipLaunchKernelGGL(k_tp_jump, grid, blk, 0, st, tw, in, outp); left -= 1; }
+                }
+            }
+            hipLaunchKernelGGL(k_tp_slots, grid, blk, 0, st, tw, t.d_td, o);
+            hipLaunchKernelGGL(k_tp_scan1, grid, blk, 0, st, tw);
+            hipLaunchKernelGGL(k_tp_scan2, dim3(1), dim3(1024), 0, st, tw, (int)nblk);
+            hipLaunchKernelGGL(k_tp_scan3, grid, blk, 0, st, tw);
+            hipLaunchKernelGGL(k_tp_fill, grid, blk, 0, st, tw, o, t.d_path);
+            hipLaunchKernelGGL(k_tp_link, grid, blk, 0, st, tw, o, t.d_path, t.d_tracef);
+            hipLaunchKernelGGL(k_tp_elim_a, grid, blk, 0, st, tw, t.d_td, o, t.d_path);
+            hipLaunchKernelGGL(k_tp_elim_b, grid, blk, 0, st, tw, t.d_td, o, t.d_path, t.d_elim);
+            // a workgroup per contig: wide for genomes, narrow when there are many short paths
+            if (max_n >= 32768 && segs.size() <= 64 && !getenv("PGA_TP_EXTRACT_ONE")) {
+                // genomes: a workgroup per chunk of 1024 path positions (k_tp_extract: one workgroup per contig, 400 rounds)
+                const int chunks = (max_n + 1023) / 1024;
+                DEVBUF(tp_xsum, TpChunkSum, "tp_xsum", (size_t)chunks * segs.size() + 1);
+                const dim3 xg((unsigned)chunks, (unsigned)segs.size());
+                hipLaunchKernelGGL(k_tp_extract_sum, xg, dim3(1024), 0, st, tw, t.d_td, o, t.d_path, t.d_elim, tp_xsum, chunks);
+                hipLaunchKernelGGL(k_tp_extract_chunk, xg, dim3(1024), 0, st, tw, t.d_td, o, t.d_path, t.d_elim, (const TpChunkSum*)tp_xsum, chunks, t.d_gene0,
+                                   t.d_ngenes);
+            } else
+                hipLaunchKernelGGL(k_tp_extract, dim3((unsigned)segs.size()), dim3(max_n >= 32768 ? 1024 : 256), 0, st, tw, t.d_td, o, t.d_path, t.d_elim,
+                                   t.d_gene0, t.d_ngenes);
+        }
+    }
+    // (no winning chain at all: the counters the tweaks read still start from zero)
+    if (!tail_inited) hipLaunchKernelGGL(k_tail_init, dim3(t.init_blocks), dim3(256), 0, st, t.d_tracef, t.d_elim, out_nodes, t.d_nchanged, t.d_ngenes, NC, (int32_t*)nullptr, 0);
+    return PGA_OK;
+}
+
+// the start tweaks of every gene and their fix-up; t.d_gene2 holds the final records afterwards
+int FindCall::launch_tail_tweaks(TailBufs& t) {
+    if (max_n >= 32768 && NC <= 1024)       // genomes: a wavefront per gene (at most n / 2 + 2 genes per contig)
+        hipLaunchKernelGGL(k_tail_tweak_wave, dim3((unsigned)((max_n / 2 + 2 + 3) / 4), (unsigned)NC), dim3(256), 0, st, t.d_td, NC, o, t.d_tracef,
+                           t.d_elim, t.d_gene0, t.d_gene1, t.d_ngenes, P.max_overlap, t.d_changed, t.d_nchanged);
+    else if (NC >= 256 && !getenv("PGA_TWEAK_SLOTS")) {   // many contigs: one thread per gene of the batch, packed
+        DEVBUF(d_gpre, int32_t, "d_gene_prefix", NC + 2);
+        hipLaunchKernelGGL(k_gene_prefix, dim3(1), dim3(1024), 0, st, t.d_ngenes, NC, d_gpre);
+        hipLaunchKernelGGL(k_tail_tweak_packed, dim3(1024), dim3(256), 0, st, t.d_td, NC, o, t.d_tracef, t.d_elim, t.d_gene0, t.d_gene1, t.d_ngenes,
+                           P.max_overlap, t.d_changed, t.d_nchanged, d_gpre);
+    } else
+        hipLaunchKernelGGL(k_tail_tweak, dim3((unsigned)((t.n_slots + 255) / 256)), dim3(256), 0, st, t.d_td, NC, t.n_slots, o, t.d_tracef, t.d_elim,
+                           t.d_gene0, t.d_gene1, t.d_ngenes, P.max_overlap, t.d_changed, t.d_nchanged);
+    DEVSET(t.d_gene2, GeneRec, "d_gene2", t.n_slots + 1);
+    DEVBUF(d_chfin, uint8_t, "d_chfin", t.n_slots + 1);
+    hipLaunchKernelGGL(k_tail_tweak_fixup, dim3(NC), dim3(max_n >= 32768 ? 1024 : 128), 0, st, t.d_td, NC, o, t.d_tracef, t.d_elim, t.d_gene0, t.d_gene1,
+                       t.d_ngenes, P.max_overlap, t.d_changed, t.d_nchanged, t.d_gene2, d_chfin);
+    return PGA_OK;
+}
+
+// ---- tail on the device: traceback untangling, bad-gene elimination, gene list, start tweaks ----------
+// The tail is a pointer chase per contig.  PGA_TAIL=device: one device thread per contig; par (the default): launch_tail_paths.
+int FindCall::run_device_tail(const bool par_tail) {
+    tm->mark("gather");
+    tdv.resize(NC);
+    int64_t n_slots = 0;
+    for (int i = 0; i < NC; i++) {
+        const int k = win_chain[i];
+        TailDesc& d = tdv[i];
+        d.out_off = k >= 0 ? out_off[i] : 0; d.gene_off = n_slots;
+        d.n = k >= 0 ? chains[k].n : 0; d.mx = k >= 0 ? h_maxidx[k] : -1;
+        d.st_wt = k >= 0 ? c->models[chains[k].model].st_wt : 0.0;
+        d.fin_off = k >= 0 ? fin_off[i] : 0; d.topo_off = k >= 0 ? chains[k].topo_off : 0;
+        d.group = k >= 0 ? chains[k].group : 0; d._pad = 0;
+        d.dp_off = k >= 0 ? chains[k].off : 0;
+        n_slots += d.n / 2 + 2;
+    }
+    DEVBUF(d_td, TailDesc, "d_taildesc", NC + 1);
+    DEVBUF(d_tracef, int32_t, "d_tracef", out_nodes + 1);
+    DEVBUF(d_elim, uint8_t, "d_elim", out_nodes + 1);
+    DEVBUF(d_gene0, GeneRec, "d_gene0", n_slots + 1);
+    DEVBUF(d_gene1, GeneRec, "d_gene1", n_slots + 1);
+    DEVBUF(d_ngenes, int32_t, "d_ngenes", NC + 1);
+    DEVBUF(d_gbegin, int64_t, "d_gbegin", NC + 1);
+    PINBUF(h_ngenes, int32_t, "h_ngenes", NC + 1);
+    PINBUF(h_gbegin, int64_t, "h_gbegin", NC + 1);
+    HT(c, hipMemcpyAsync(d_td, tdv.data(), sizeof(TailDesc) * NC, hipMemcpyHostToDevice, st));
+    DEVBUF(d_path, int32_t, "d_path", out_nodes + 1);
+    DEVBUF(d_changed, uint8_t, "d_changed", n_slots + 1);
+    DEVBUF(d_nchanged, int32_t, "d_nchanged", NC + 1);
+    TailBufs t{d_td, d_tracef, d_elim, d_gene0, d_gene1, nullptr, d_ngenes, d_path, d_changed, d_nchanged, n_slots,
+               (unsigned)std::min<int64_t>(2048, (std::max<int64_t>(out_nodes, NC) + 256) / 256)};
+    if (!par_tail) {
+        hipLaunchKernelGGL(k_tail_init, dim3(t.init_blocks), dim3(256), 0, st, d_tracef, d_elim, out_nodes, d_nchanged, (int32_t*)nullptr, NC, (int32_t*)nullptr, 0);
+        hipLaunchKernelGGL(k_tail_path, dim3((NC + 63) / 64), dim3(64), 0, st, d_td, NC, o, d_tracef, d_elim, d_path, d_gene0, d_ngenes);
+    } else if (const int rc = launch_tail_paths(t)) return rc;
+    if (const int rc = launch_tail_tweaks(t)) return rc;
+    HT(c, hipMemcpyAsync(h_ngenes, d_ngenes, sizeof(int32_t) * NC, hipMemcpyDeviceToHost, st));
+    if (const int rc = sync()) return rc;
+    tm->mark("tail");
+    // ---- results --------------------------------------------------------------------------------------
+    const int64_t ngenes = contig_results(h_ngenes, h_gbegin);
+    pga_gene* const genes_out = coding || keep ? nullptr : R->gene_records((size_t)ngenes);
+    pga_gene* d_genes = nullptr;
+    if (ngenes > 0) {
+        DEVBUF(d_genes_out, pga_gene, keep ? keep->buf : "d_genes_out", ngenes + 1);
+        d_genes = d_genes_out;
+        HT(c, hipMemcpyAsync(d_gbegin, h_gbegin, sizeof(int64_t) * NC, hipMemcpyHostToDevice, st));
+        GcPtrs gcs{};
+        for (int g = 0; g < NG; g++) gcs.p[g] = ga[g].gc_cont;
+        hipLaunchKernelGGL(k_emit_genes, dim3((unsigned)((n_slots + 255) / 256)), dim3(256), 0, st, d_td, NC, n_slots, o, t.d_gene2, d_ngenes,
+                           d_gbegin, P.meta ? 0 : 1, d_genes, lean_gather ? 1 : 0, ca, gcs);
+        if (genes_out) HT(c, hipMemcpyAsync(genes_out, d_genes, sizeof(pga_gene) * (size_t)ngenes, hipMemcpyDeviceToHost, st));
+        if (keep) { keep->d_genes = d_genes; keep->n_genes = ngenes; }
+    }
+    if (coding) {
+        // the coverage of the resident records: one bit per base of the batch, then a popcount per contig; NC counts come back
+        const int64_t words = total / 32 + 2;
+        DEVBUF(d_cover, uint32_t, "d_cover", words);
+        DEVBUF(d_coding, int64_t, "d_coding", NC + 1);
+        PINBUF(h_coding, int64_t, "h_coding", NC + 1);
+        HT(c, hipMemsetAsync(d_cover, 0, sizeof(uint32_t) * (size_t)words, st));
+        if (ngenes > 0)
+            hipLaunchKernelGGL(k_cover_genes, dim3((unsigned)((ngenes + 3) / 4)), dim3(256), 0, st, d_genes, ngenes, d_ct, NC, d_cover);
+        hipLaunchKernelGGL(k_count_cover, dim3((unsigned)NC), dim3(256), 0, st, d_cover, d_ct, d_coding);
+        HT(c, hipMemcpyAsync(h_coding, d_coding, sizeof(int64_t) * NC, hipMemcpyDeviceToHost, st));
+        if (const int rc = sync()) return rc;
+        memcpy(coding, h_coding, sizeof(int64_t) * NC);
+    }
+    if (P.want_nodes == 1 && out_nodes > 0) {
+        tracef.resize((size_t)out_nodes + 1); elim.resize((size_t)out_nodes + 1);
+        HT(c, hipMemcpyAsync(h.ndx, o.ndx, arena_all, hipMemcpyDeviceToHost, st));   // arena starts at `ndx`
+        HT(c, hipMemcpyAsync(tracef.data(), d_tracef, sizeof(int32_t) * (size_t)out_nodes, hipMemcpyDeviceToHost, st));
+        HT(c, hipMemcpyAsync(elim.data(), d_elim, (size_t)out_nodes, hipMemcpyDeviceToHost, st));
+    }
+    if (const int rc = stop_clock()) return rc;
+    tm->mark("genes+d2h");
+    return PGA_OK;
+}
+
+// the winners' node arrays for the caller (want_nodes 1)
+int FindCall::copy_out_nodes() {
+    R->nodes.resize(NC);
+    for (int i = 0; i < NC; i++) {
+        pga_nodes& N = R->nodes[i];
+        memset(&N, 0, sizeof N);
+        const int k = win_chain[i];
+        if (k < 0) continue;
+        const int n = chains[k].n; const int64_t oo = out_off[i];
+        const bool single = !P.meta;
+        if (int rc = alloc_nodes(R, N, n)) return rc;
+        // single mode: nodes as left by the DP + eliminate_bad_genes (ref: lib.pyx:5296-5311); meta mode: fresh re-score, DP fields
+        // reset (ref: lib.pyx:5380-5394)
+        copy_node_topology(N, n, h.ndx + oo, h.stop_val + oo, h.type + oo, h.strand + oo, (single ? h.edge_dp : h.edge) + oo);
+        const double* const src64[6] = {(single ? h.cscore_dp : h.cscore) + oo, (single ? h.sscore_dp : h.sscore) + oo, (single ? h.rscore_dp : h.rscore) + oo,
+                                        (single ? h.uscore_dp : h.uscore) + oo, (single ? h.tscore_dp : h.tscore) + oo, h.mot_score + oo};
+        copy_node_scores(N, n, src64, h.mot_ndx + oo, h.rbs + 2 * oo, h.mot_len + oo, h.mot_spacer + oo, h.mot_spacendx + oo, h.gc_cont + oo);
+        if (single) {
+            memcpy(N.score, h.score + oo, 8 * (size_t)n); memcpy(N.traceb, h.traceb + oo, 4 * (size_t)n); memcpy(N.tracef, tracef.data() + oo, 4 * (size_t)n);
+            memcpy(N.ov_mark, h.ov_mark + oo, n); memcpy(N.elim, elim.data() + oo, n); memcpy(N.star_ptr, h.star_ptr + 3 * oo, 12 * (size_t)n);
+        } else reset_dp_fields(N, n);
+    }
+    return PGA_OK;
+}
+
+// the arena stays on the device for pga_render_genes until the next finder call (want_nodes 1 and PGA_NODES_DEVICE)
+void FindCall::keep_device_nodes() {
+    DevNodes& D = c->dev_nodes;
+    D.off.assign(NC, 0); D.n.assign(NC, 0); D.len.resize(NC);
+    for (int i = 0; i < NC; i++) {
+        D.len[i] = batch->ct[i].len;
+        if (win_chain[i] >= 0) { D.off[i] = out_off[i]; D.n[i] = chains[win_chain[i]].n; }
+    }
+    D.total = out_nodes;
+    const bool single = !P.meta;
+    D.a = DevNodeArrays{o.ndx, o.stop_val, o.type, o.strand, o.gc_cont,
+                        single ? o.edge_dp : o.edge, single ? o.cscore_dp : o.cscore, single ? o.sscore_dp : o.sscore,
+                        single ? o.rscore_dp : o.rscore, single ? o.uscore_dp : o.uscore, single ? o.tscore_dp : o.tscore,
+                        o.mot_score, o.mot_ndx, o.rbs, o.mot_len, o.mot_spacer};
+    D.batch = batch;
+    D.contigs = R->contigs.data();
+}
+
+}  // namespace
+
+// The driver of every entry point: the phases of a call in order (FindCall above).
+// stage 0 = the whole path; PGA_STAGE_* = stop after that stage and return the node arrays (single chain per
+// contig scored with model 0; P.meta then only selects the meta-mode start penalties of Nodes.score)
+// model_of_contig (single mode: the path and the SCORE / OVERLAP stages; nullptr = model 0 everywhere): contig i is scored with that
+// loaded model, its nodes extracted under that model's translation table -- the groups of meta mode, one chain per contig.
+// tt_of_contig (EXTRACT stage; nullptr = tt_override everywhere): contig i is extracted under that table.  At most 4 tables.
+// coding (stage 0, single mode; nullptr otherwise): coding[i] = bases of contig i inside at least one of its genes, counted where the
+// gene records are (pga_find_coding_bases); the records are then not copied back and the result holds no genes.
+// keep (stage 0; nullptr otherwise): a pass of a circular call (circular.inl) -- the gene records stay on the device, in the buffer
+// `keep->buf`, and the result holds none; `keep` reports where they are (nothing when the call found no node at all).
+static int find_impl(pga_ctx* c, const pga_batch* batch, const pga_params* pp, const int stage, const int tt_override, pga_result** out,
+                     const int32_t* model_of_contig, const int32_t* tt_of_contig, int64_t* coding = nullptr, GeneKeep* keep = nullptr) {
+    FindCall s;
+    s.stage = stage; s.tt_override = tt_override; s.model_of_contig = model_of_contig; s.tt_of_contig = tt_of_contig; s.coding = coding; s.keep = keep;
+    if (const int rc = s.check_call(c, batch, pp, out)) return rc;
+    StageTimer tm;
+    s.tm = &tm;
+    if (s.NC > 0 && s.total > 0) {
+        if (const int rc = s.run_sequence_and_masks()) return rc;
+        if (stage == PGA_STAGE_SEQUENCE) return s.return_sequence_stage(out);
+        if (const int rc = s.run_extract()) return rc;
+        tm.mark("extract+sync");
+        if (const int rc = s.place_nodes()) return rc;
+        if (const int rc = s.plan_chains()) return rc;
+        if (const int rc = s.plan_connection_scoring()) return rc;
+        if (const int rc = s.upload_plan()) return rc;
+        tm.mark("plan+alloc");
+        if (const int rc = s.score_groups()) return rc;
+        if (stage != 0) return s.return_stage_nodes(out);
+        if (const int rc = s.score_connections()) return rc;
+        tm.mark("score+dp+sync");
+        s.pick_winners();
+        if (const int rc = s.rescore_winners()) return rc;
         tm.mark("winners+rescore_launch");
-        // ---- gather the winners and bring them home ------------------------------------------------
-        // the winners' final-pass fields only travel to the gathered arrays when somebody reads more of them than the two nodes
-        // of every gene: the caller (node arrays) or the host tail's attribute fetch (PGA_FULL_GATHER=1 keeps the full gather: tests)
-        std::vector<std::vector<WinDesc>> wg(NG);
-        std::vector<int64_t> out_off(NC, 0);
-        int64_t out_nodes = 0;
-        std::vector<int64_t> w_o0(NG + 1, 0);
-        // output order: group-major then contig, so each group's launch covers a contiguous output range
-        for (int g = 0; g < NG; g++) {
-            w_o0[g] = out_nodes;
-            for (int i = 0; i < NC; i++) {
-                const int k = win_chain[i];
-                if (k < 0 || chains[k].group != g) continue;
-                out_off[i] = out_nodes;
-                wg[g].push_back(WinDesc{out_nodes, chains[k].off, fin_off[i], chains[k].topo_off, chains[k].n, 0});
-                out_nodes += chains[k].n;
-            }
-        }
-        w_o0[NG] = out_nodes;
-        // one device arena (and a pinned mirror, used only when the caller asks for the node arrays)
-        OutArrays o, h;
-        size_t arena_dp = 0, arena_all = 0;
-        {
-            const size_t n = (size_t)out_nodes + 1;
-            size_t off = 0;
-            auto reserve = [&](size_t elem, size_t mult) { const size_t at = off; off += ((elem * mult * n + 255) / 256) * 256; return at; };
-#define OFFS(field, type, mult) const size_t at_##field = reserve(sizeof(type), mult);
-            OFFS(ndx, int32_t, 1) OFFS(stop_val, int32_t, 1) OFFS(type, uint8_t, 1) OFFS(strand, int8_t, 1)
-            OFFS(edge_dp, uint8_t, 1) OFFS(cscore_dp, double, 1) OFFS(sscore_dp, double, 1) OFFS(rscore_dp, double, 1) OFFS(uscore_dp, double, 1) OFFS(tscore_dp, double, 1)
-            OFFS(star_ptr, int32_t, 3) OFFS(traceb, int32_t, 1) OFFS(ov_mark, int8_t, 1) OFFS(score, double, 1)
-            arena_dp = off;
-            OFFS(gc_cont, float, 1)
-            OFFS(edge, uint8_t, 1) OFFS(cscore, double, 1) OFFS(sscore, double, 1) OFFS(rscore, double, 1) OFFS(uscore, double, 1) OFFS(tscore, double, 1) OFFS(mot_score, double, 1)
-            OFFS(mot_ndx, int32_t, 1) OFFS(rbs, uint8_t, 2) OFFS(mot_len, uint8_t, 1) OFFS(mot_spacer, uint8_t, 1) OFFS(mot_spacendx, uint8_t, 1)
-            arena_all = off;
-            void* dp__; void* hp__;
-            { int rc__ = ensure_dev(c, "o_arena", arena_all + 256, &dp__); if (rc__) return rc__; }
-            { int rc__ = ensure_pin(c, "h_arena", arena_all + 256, &hp__); if (rc__) return rc__; }
-            char* db = (char*)dp__; char* hb = (char*)hp__;
-#define OB(field, type) o.field = (type*)(db + at_##field); h.field = (type*)(hb + at_##field);
-            OB(ndx, int32_t) OB(stop_val, int32_t) OB(type, uint8_t) OB(strand, int8_t) OB(gc_cont, float)
-            OB(edge_dp, uint8_t) OB(cscore_dp, double) OB(sscore_dp, double) OB(rscore_dp, double) OB(uscore_dp, double) OB(tscore_dp, double)
-            OB(star_ptr, int32_t) OB(traceb, int32_t) OB(ov_mark, int8_t) OB(score, double)
-            OB(edge, uint8_t) OB(cscore, double) OB(sscore, double) OB(rscore, double) OB(uscore, double) OB(tscore, double) OB(mot_score, double)
-            OB(mot_ndx, int32_t) OB(rbs, uint8_t) OB(mot_len, uint8_t) OB(mot_spacer, uint8_t) OB(mot_spacendx, uint8_t)
-        }
-        // lean and the device tail: gather only what the tail writes
-        o.direct = direct_gather ? 1 : 0;
-        for (int g = 0; g < 4; g++) {
-            const bool in = g < NG;
-            o.g_ndx[g] = in ? ga[g].ndx : nullptr; o.g_stop_val[g] = in ? ga[g].stop_val : nullptr;
-            o.g_type[g] = in ? ga[g].type : nullptr; o.g_strand[g] = in ? ga[g].strand : nullptr;
-        }
-        o.c_edge = ca.edge; o.c_cscore = ca.cscore; o.c_rscore = ca.rscore; o.c_uscore = ca.uscore; o.c_tscore = ca.tscore;
-        o.c_star_ptr = ca.star_ptr; o.d_score = dp.score;
-        h.direct = 0;
-        size_t nwin = 0; for (int g = 0; g < NG; g++) nwin += wg[g].size();
-        DEVBUF(d_win, WinDesc, "d_win", nwin + 1);
-        {
-            size_t k0 = 0;
-            for (int g = 0; g < NG; g++) {
-                if (wg[g].empty()) continue;
-                HT(c, hipMemcpyAsync(d_win + k0, wg[g].data(), sizeof(WinDesc) * wg[g].size(), hipMemcpyHostToDevice, st));
-                const int64_t nn = w_o0[g + 1] - w_o0[g];
-                if (nn > 0)
-                    hipLaunchKernelGGL(k_gather_winners, dim3((unsigned)((nn + 255) / 256)), dim3(256), 0, st, d_win + k0, (int)wg[g].size(), w_o0[g], nn, ga[g], ca, dp, o, lean_gather ? 1 : 0);
-                k0 += wg[g].size();
-            }
-        }
-        // The tail (traceback untangling, bad-gene elimination, gene list, start tweaks) is a pointer chase per
-        // contig.  Many small contigs: one device thread each, only the genes come home.  Few or very long contigs:
-        // a single device thread would crawl (one memory round trip per step), so their DP-pass fields come home
-        // and host threads walk them.
-        int max_n = 0;
-        for (int i = 0; i < NC; i++) if (win_chain[i] >= 0) max_n = std::max(max_n, chains[win_chain[i]].n);
+        if (const int rc = s.gather_winners()) return rc;
+        // The tail (traceback untangling, bad-gene elimination, gene list, start tweaks) is a pointer chase per contig:
         // PGA_TAIL = host | device (one thread per contig) | par (tail.inl, the default)
         const char* tail_env = getenv("PGA_TAIL");
         const bool device_tail = tail_env ? strcmp(tail_env, "host") != 0 : true;
         if (keep && !device_tail) { c->err = "pga_find_genes: circular contigs are called with the device tail only (PGA_TAIL=host is set)"; return PGA_EINVAL; }
-        const bool par_tail = device_tail && !(tail_env && strcmp(tail_env, "device") == 0);
-        std::vector<int32_t> tracef;
-        std::vector<uint8_t> elim;
-        if (!device_tail) {
-            tracef.assign((size_t)out_nodes + 1, -1);
-            elim.assign((size_t)out_nodes + 1, 0);
-            if (out_nodes > 0)
-                HT(c, hipMemcpyAsync(h.ndx, o.ndx, P.want_nodes == 1 ? arena_all : arena_dp, hipMemcpyDeviceToHost, st));   // arena starts at `ndx`
-            HT(c, hipEventRecord(f->e_stop, st));
-            HT(c, hipGetLastError());
-            HT(c, hipStreamSynchronize(st));
-            { float ms = 0; HT(c, hipEventElapsedTime(&ms, f->e_start, f->e_stop)); R->pub.t_total_ms = ms; }
-
-            tm.mark("gather+d2h+sync");
-            // ---- host tail per contig ------------------------------------------------------------------
-            std::vector<std::vector<GeneRec>> cg(NC);
-            std::unique_ptr<int32_t[]> pathbuf(new int32_t[(size_t)out_nodes + 1]);      // written before it is read: no zero fill
-            std::atomic<int> next(0);
-            auto worker = [&]() {
-                for (;;) {
-                    const int i = next.fetch_add(1);
-                    if (i >= NC) break;
-                    const int k = win_chain[i];
-                    if (k < 0) continue;
-                    const int64_t oo = out_off[i];
-                    NodeView v{chains[k].n, h.ndx + oo, h.stop_val + oo, h.type + oo, h.strand + oo, h.edge_dp + oo,
-                               h.cscore_dp + oo, h.sscore_dp + oo, h.rscore_dp + oo, h.uscore_dp + oo, h.tscore_dp + oo,
-                               h.star_ptr + 3 * oo, h.traceb + oo, tracef.data() + oo, h.ov_mark + oo, h.score + oo, elim.data() + oo};
-                    const int mx = h_maxidx[k];
-                    const double st_wt = c->models[chains[k].model].st_wt;
-                    const bool sub = NC == 1 && getenv("PGA_TIMING");
-                    auto now = [] { return std::chrono::steady_clock::now(); };
-                    auto t0 = now(), t1 = t0, t2 = t0, t3 = t0;
-                    if (v.n > 0 && mx >= 0) {
-                        int32_t* pl = pathbuf.get() + oo;
-                        const int cnt = untangle(v, mx, pl);
-                        t1 = now();
-                        if (v.traceb[mx] != -1) {
-                            if (NC < 4) eliminate_bad_genes_mt(v, pl, cnt, st_wt, f->pool, 16); else eliminate_bad_genes(v, pl, cnt, st_wt);
-                            t2 = now();
-                            cg[i].resize((size_t)cnt / 2 + 2);           // two path nodes per gene
-                            cg[i].resize((size_t)extract_genes(v, pl, cnt, cg[i].data()));
-                        }
-                    }
-                    t3 = now();
-                    tweak_final_starts(v, cg[i], st_wt, P.max_overlap, NC < 4 ? 32 : 1, &f->pool);
-                    if (sub) {
-                        auto ms = [](auto a, auto b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
-                        fprintf(stderr, "[pga timing] host tail: untangle=%.2f eliminate=%.2f extract=%.2f tweak=%.2f ms\n", ms(t0, t1), ms(t1, t2), ms(t2, t3), ms(t3, now()));
-                    }
-                }
-            };
-            auto run_parallel = [&](const std::function<void()>& fn) {
-                int nt = (int)std::min<unsigned>(std::max(1u, std::thread::hardware_concurrency()), 32u);
-                if (NC < 4) nt = 1;
-                if (nt == 1) fn(); else f->pool.run(fn, nt);
-            };
-            run_parallel(worker);
-            // the tail moved start scores (eliminate_bad_genes): the arena kept on the device must say what the host copy says
-            if (P.want_nodes && out_nodes > 0)
-                HT(c, hipMemcpyAsync(o.sscore_dp, h.sscore_dp, sizeof(double) * (size_t)out_nodes, hipMemcpyHostToDevice, st));
-            tm.mark("host_tail");
-            // ---- results -----------------------------------------------------------------------------------
-            int64_t ngenes = 0;
-            for (int i = 0; i < NC; i++) {
-                pga_contig_result& cr = R->contigs[i];
-                const int k = win_chain[i];
-                cr.gene_begin = ngenes; cr.n_genes = (int32_t)cg[i].size();
-                ngenes += cr.n_genes;
-                if (k < 0) { cr.model = -1; continue; }
-                cr.model = chains[k].model; cr.n_nodes = chains[k].n;
-                cr.score = P.meta ? 0.0 : (h_ipath[k] >= 0 ? h_maxscore[k] : 0.0);
-            }
-            R->genes.resize((size_t)ngenes);
-            // fields of the gene's start / stop nodes as of the final pass: a second, small gather
-            PINBUF(h_gidx, int64_t, "h_gidx", 2 * ngenes + 1);
-            PINBUF(h_attr, GeneNodeAttr, "h_attr", 2 * ngenes + 1);
-            if (ngenes > 0) {
-                DEVBUF(d_gidx, int64_t, "d_gidx", 2 * ngenes + 1);
-                DEVBUF(d_attr, GeneNodeAttr, "d_attr", 2 * ngenes + 1);
-                for (int i = 0; i < NC; i++) {
-                    int64_t gi = R->contigs[i].gene_begin;
-                    for (const GeneRec& gr : cg[i]) { h_gidx[2 * gi] = out_off[i] + gr.start_ndx; h_gidx[2 * gi + 1] = out_off[i] + gr.stop_ndx; gi++; }
-                }
-                HT(c, hipMemcpyAsync(d_gidx, h_gidx, sizeof(int64_t) * 2 * ngenes, hipMemcpyHostToDevice, st));
-                hipLaunchKernelGGL(k_gather_gene_nodes, dim3((unsigned)((2 * ngenes + 255) / 256)), dim3(256), 0, st, d_gidx, (int)(2 * ngenes), o, d_attr);
-                HT(c, hipMemcpyAsync(h_attr, d_attr, sizeof(GeneNodeAttr) * 2 * ngenes, hipMemcpyDeviceToHost, st));
-                HT(c, hipGetLastError());
-                HT(c, hipStreamSynchronize(st));
-            }
-            tm.mark("gene_attrs");
-            std::atomic<int> next2(0);
-            auto filler = [&]() {
-                for (;;) {
-                    const int i = next2.fetch_add(1);
-                    if (i >= NC) break;
-                    const int k = win_chain[i];
-                    if (k < 0) continue;
-                    const int64_t oo = out_off[i];
-                    const bool single = !P.meta;
-                    int64_t gi = R->contigs[i].gene_begin;
-                    for (const GeneRec& gr : cg[i]) {
-                        pga_gene& G = R->genes[(size_t)gi];
-                        const GeneNodeAttr& as = h_attr[2 * gi]; const GeneNodeAttr& ae = h_attr[2 * gi + 1];
-                        gi++;
-                        memset(&G, 0, sizeof G);
-                        const int64_t sn = oo + gr.start_ndx, en = oo + gr.stop_ndx;
-                        G.contig = i; G.begin = gr.begin; G.end = gr.end; G.start_ndx = gr.start_ndx; G.stop_ndx = gr.stop_ndx;
-                        G.strand = h.strand[sn];
-                        // single mode keeps the nodes of the DP pass (ref: lib.pyx:5296-5311); meta mode re-scores (5380-5394)
-                        const uint8_t se = single ? h.edge_dp[sn] : as.edge, ee = single ? h.edge_dp[en] : ae.edge;
-                        G.partial_begin = G.strand == 1 ? se : ee; G.partial_end = G.strand == 1 ? ee : se;
-                        G.start_type = se ? 3 : h.type[sn];
-                        G.rbs[0] = as.rbs0; G.rbs[1] = as.rbs1;
-                        G.mot_len = as.mot_len; G.mot_spacer = as.mot_spacer; G.mot_ndx = as.mot_ndx; G.mot_score = as.mot_score;
-                        G.gc_cont = as.gc_cont;
-                        G.cscore = single ? h.cscore_dp[sn] : as.cscore; G.sscore = single ? h.sscore_dp[sn] : as.sscore;
-                        G.rscore = single ? h.rscore_dp[sn] : as.rscore; G.uscore = single ? h.uscore_dp[sn] : as.uscore;
-                        G.tscore = single ? h.tscore_dp[sn] : as.tscore;
-                    }
-                }
-            };
-            run_parallel(filler);
-            if (coding) {
-                // host tail (PGA_TAIL=host): the records are on the host already, so they are counted here -- a union of intervals per
-                // contig, the same definition as k_cover_genes / k_count_cover
-                std::vector<std::pair<int32_t, int32_t>> iv;
-                for (int i = 0; i < NC; i++) {
-                    iv.clear();
-                    const int32_t len = ct[i].len;
-                    for (const GeneRec& gr : cg[i]) {
-                        const int32_t b = std::max<int32_t>(gr.begin, 1), e = std::min<int32_t>(gr.end, len);
-                        if (b <= e) iv.emplace_back(b, e);
-                    }
-                    std::sort(iv.begin(), iv.end());
-                    int64_t n = 0; int32_t hi = 0;          // positions 1 .. hi are already counted
-                    for (const auto& x : iv) {
-                        if (x.second <= hi) continue;
-                        n += x.second - std::max(x.first - 1, hi);
-                        hi = x.second;
-                    }
-                    coding[i] = n;
-                }
-            }
-        } else {
-            tm.mark("gather");
-            // ---- tail on the device: traceback untangling, bad-gene elimination, gene list, start tweaks ----------
-            std::vector<TailDesc> tdv(NC);
-            int64_t n_slots = 0;
-            for (int i = 0; i < NC; i++) {
-                const int k = win_chain[i];
-                TailDesc& d = tdv[i];
-                d.out_off = k >= 0 ? out_off[i] : 0; d.gene_off = n_slots;
-                d.n = k >= 0 ? chains[k].n : 0; d.mx = k >= 0 ? h_maxidx[k] : -1;
-                d.st_wt = k >= 0 ? c->models[chains[k].model].st_wt : 0.0;
-                d.fin_off = k >= 0 ? fin_off[i] : 0; d.topo_off = k >= 0 ? chains[k].topo_off : 0;
-                d.group = k >= 0 ? chains[k].group : 0; d._pad = 0;
-                d.dp_off = k >= 0 ? chains[k].off : 0;
-                n_slots += d.n / 2 + 2;
-            }
-            DEVBUF(d_td, TailDesc, "d_taildesc", NC + 1);
-            DEVBUF(d_tracef, int32_t, "d_tracef", out_nodes + 1);
-            DEVBUF(d_elim, uint8_t, "d_elim", out_nodes + 1);
-            DEVBUF(d_gene0, GeneRec, "d_gene0", n_slots + 1);
-            DEVBUF(d_gene1, GeneRec, "d_gene1", n_slots + 1);
-            DEVBUF(d_ngenes, int32_t, "d_ngenes", NC + 1);
-            DEVBUF(d_gbegin, int64_t, "d_gbegin", NC + 1);
-            PINBUF(h_ngenes, int32_t, "h_ngenes", NC + 1);
-            PINBUF(h_gbegin, int64_t, "h_gbegin", NC + 1);
-            HT(c, hipMemcpyAsync(d_td, tdv.data(), sizeof(TailDesc) * NC, hipMemcpyHostToDevice, st));
-            DEVBUF(d_path, int32_t, "d_path", out_nodes + 1);
-            DEVBUF(d_changed, uint8_t, "d_changed", n_slots + 1);
-            DEVBUF(d_nchanged, int32_t, "d_nchanged", NC + 1);
-            const unsigned init_blocks = (unsigned)std::min<int64_t>(2048, (std::max<int64_t>(out_nodes, NC) + 256) / 256);
-            if (!par_tail) {
-                hipLaunchKernelGGL(k_tail_init, dim3(init_blocks), dim3(256), 0, st, d_tracef, d_elim, out_nodes, d_nchanged, (int32_t*)nullptr, NC, (int32_t*)nullptr, 0);
-                hipLaunchKernelGGL(k_tail_path, dim3((NC + 63) / 64), dim3(64), 0, st, d_td, NC, o, d_tracef, d_elim, d_path, d_gene0, d_ngenes);
-            } else {
-                std::vector<TpSeg> segs;
-                bool tail_inited = false;
-                for (int i = 0; i < NC; i++) if (win_chain[i] >= 0 && chains[win_chain[i]].n > 0) segs.push_back(TpSeg{out_off[i], chains[win_chain[i]].n, i});
-                std::sort(segs.begin(), segs.end(), [](const TpSeg& a, const TpSeg& b) { return a.off < b.off; });
-                if (!segs.empty() && out_nodes > 0) {
-                    if (out_nodes >= (1ll << 30)) { c->err = "pga_find_genes: more than 2^30 nodes in the winning chains of one batch"; return PGA_EINVAL; }
-                    int levels = 1;
-                    while ((1ll << levels) < max_n) levels++;
-                    const unsigned nblk = (unsigned)((out_nodes + 255) / 256);
-                    const bool tp_steps = getenv("PGA_TP_STEPS") != nullptr;      // the many-launch form also for short chains (cross-check)
-                    const bool tp_one = max_n <= TP_SMALL_MAX && !tp_steps;
-                    const int64_t tpn = tp_one ? 0 : out_nodes;                   // the per-node work arrays of the many-launch form
-                    DEVBUF(tp_seg, TpSeg, "tp_seg", segs.size()) DEVBUF(tp_up, int32_t, "tp_up", (size_t)2 * tpn)
-                    DEVBUF(tp_mark, uint8_t, "tp_mark", tpn) DEVBUF(tp_slots, int32_t, "tp_slots", tpn)
-                    DEVBUF(tp_ins, int32_t, "tp_ins", 2 * tpn) DEVBUF(tp_excl, int32_t, "tp_excl", tpn + 1)
-                    DEVBUF(tp_bsum, int32_t, "tp_bsum", nblk + 1) DEVBUF(tp_cnt, int32_t, "tp_cnt", segs.size())
-                    HT(c, hipMemcpyAsync(tp_seg, segs.data(), sizeof(TpSeg) * segs.size(), hipMemcpyHostToDevice, st));
-                    hipLaunchKernelGGL(k_tail_init, dim3(init_blocks), dim3(256), 0, st, d_tracef, d_elim, out_nodes, d_nchanged, d_ngenes, NC,
-                                       tp_one ? (int32_t*)nullptr : tp_cnt, (int)segs.size());
-                    tail_inited = true;
-                    const TpWork tw{tp_seg, (int)segs.size(), out_nodes, levels, tp_up, tp_mark, tp_slots, tp_ins, tp_excl, tp_bsum, tp_cnt};
-                    const dim3 grid(nblk), blk(256);
-                    if (tp_one) {
-                        const int cap = (int)((max_n + 63) & ~63ll);
-                        hipLaunchKernelGGL(k_tp_small, dim3((unsigned)segs.size()), dim3(max_n <= 2048 ? 64 : 256), sizeof(int32_t) * 3 * (size_t)cap, st, tw, d_td, o,
-                                           d_tracef, d_elim, d_gene0, d_ngenes, cap);
-                    } else {
-                    hipLaunchKernelGGL(k_tp_init, grid, blk, 0, st, tw, d_td, o);
-                    // pointer jumping: 2^levels >= the longest chain; eight hops per launch while three levels or more are left (PGA_TP_JUMP8=0: doubling only)
-                    {
-                        const bool j8 = !(getenv("PGA_TP_JUMP8") && atoi(getenv("PGA_TP_JUMP8")) == 0);
-                        int k = 0;
-                        for (int left = levels; left > 0; k++) {
-                            const int32_t* in = tp_up + (size_t)(k & 1) * out_nodes; int32_t* outp = tp_up + (size_t)((k + 1) & 1) * out_nodes;
-                            if (j8 && left >= 3) { hipLaunchKernelGGL(k_tp_jump8, grid, blk, 0, st, tw, in, outp); left -= 3; }
-                            else { hipLaunchKernelGGL(k_tp_jump, grid, blk, 0, st, tw, in, outp); left -= 1; }
-                        }
-                    }
-                    hipLaunchKernelGGL(k_tp_slots, grid, blk, 0, st, tw, d_td, o);
-                    hipLaunchKernelGGL(k_tp_scan1, grid, blk, 0, st, tw);
-                    hipLaunchKernelGGL(k_tp_scan2, dim3(1), dim3(1024), 0, st, tw, (int)nblk);
-                    hipLaunchKernelGGL(k_tp_scan3, grid, blk, 0, st, tw);
-                    hipLaunchKernelGGL(k_tp_fill, grid, blk, 0, st, tw, o, d_path);
-                    hipLaunchKernelGGL(k_tp_link, grid, blk, 0, st, tw, o, d_path, d_tracef);
-                    hipLaunchKernelGGL(k_tp_elim_a, grid, blk, 0, st, tw, d_td, o, d_path);
-                    hipLaunchKernelGGL(k_tp_elim_b, grid, blk, 0, st, tw, d_td, o, d_path, d_elim);
-                    // a workgroup per contig: wide for genomes, narrow when there are many short paths
-                    if (max_n >= 32768 && segs.size() <= 64 && !getenv("PGA_TP_EXTRACT_ONE")) {
-                        // genomes: a workgroup per chunk of 1024 path positions (k_tp_extract: one workgroup per contig, 400 rounds)
-                        const int chunks = (max_n + 1023) / 1024;
-                        DEVBUF(tp_xsum, TpChunkSum, "tp_xsum", (size_t)chunks * segs.size() + 1);
-                        const dim3 xg((unsigned)chunks, (unsigned)segs.size());
-                        hipLaunchKernelGGL(k_tp_extract_sum, xg, dim3(1024), 0, st, tw, d_td, o, d_path, d_elim, tp_xsum, chunks);
-                        hipLaunchKernelGGL(k_tp_extract_chunk, xg, dim3(1024), 0, st, tw, d_td, o, d_path, d_elim, (const TpChunkSum*)tp_xsum, chunks, d_gene0,
-                                           d_ngenes);
-                    } else
-                    hipLaunchKernelGGL(k_tp_extract, dim3((unsigned)segs.size()), dim3(max_n >= 32768 ? 1024 : 256), 0, st, tw, d_td, o, d_path, d_elim,
-                                       d_gene0, d_ngenes);
-                    }
-                }
-                // (no winning chain at all: the counters the tweaks read still start from zero)
-                if (!tail_inited) hipLaunchKernelGGL(k_tail_init, dim3(init_blocks), dim3(256), 0, st, d_tracef, d_elim, out_nodes, d_nchanged, d_ngenes, NC, (int32_t*)nullptr, 0);
-            }
-            if (max_n >= 32768 && NC <= 1024)       // genomes: a wavefront per gene (at most n / 2 + 2 genes per contig)
-                hipLaunchKernelGGL(k_tail_tweak_wave, dim3((unsigned)((max_n / 2 + 2 + 3) / 4), (unsigned)NC), dim3(256), 0, st, d_td, NC, o, d_tracef,
-                                   d_elim, d_gene0, d_gene1, d_ngenes, P.max_overlap, d_changed, d_nchanged);
-            else if (NC >= 256 && !getenv("PGA_TWEAK_SLOTS")) {   // many contigs: one thread per gene of the batch, packed
-                DEVBUF(d_gpre, int32_t, "d_gene_prefix", NC + 2);
-                hipLaunchKernelGGL(k_gene_prefix, dim3(1), dim3(1024), 0, st, d_ngenes, NC, d_gpre);
-                hipLaunchKernelGGL(k_tail_tweak_packed, dim3(1024), dim3(256), 0, st, d_td, NC, o, d_tracef, d_elim, d_gene0, d_gene1, d_ngenes,
-                                   P.max_overlap, d_changed, d_nchanged, d_gpre);
-            } else
-                hipLaunchKernelGGL(k_tail_tweak, dim3((unsigned)((n_slots + 255) / 256)), dim3(256), 0, st, d_td, NC, n_slots, o, d_tracef, d_elim,
-                                   d_gene0, d_gene1, d_ngenes, P.max_overlap, d_changed, d_nchanged);
-            DEVBUF(d_gene2, GeneRec, "d_gene2", n_slots + 1);
-            DEVBUF(d_chfin, uint8_t, "d_chfin", n_slots + 1);
-            hipLaunchKernelGGL(k_tail_tweak_fixup, dim3(NC), dim3(max_n >= 32768 ? 1024 : 128), 0, st, d_td, NC, o, d_tracef, d_elim, d_gene0, d_gene1,
-                               d_ngenes, P.max_overlap, d_changed, d_nchanged, d_gene2, d_chfin);
-            HT(c, hipMemcpyAsync(h_ngenes, d_ngenes, sizeof(int32_t) * NC, hipMemcpyDeviceToHost, st));
-            HT(c, hipGetLastError());
-            HT(c, hipStreamSynchronize(st));
-            tm.mark("tail");
-            // ---- results --------------------------------------------------------------------------------------
-            int64_t ngenes = 0;
-            for (int i = 0; i < NC; i++) {
-                pga_contig_result& cr = R->contigs[i];
-                const int k = win_chain[i];
-                h_gbegin[i] = ngenes;
-                cr.gene_begin = ngenes; cr.n_genes = h_ngenes[i];
-                ngenes += cr.n_genes;
-                if (k < 0) { cr.model = -1; continue; }
-                cr.model = chains[k].model; cr.n_nodes = chains[k].n;
-                cr.score = P.meta ? 0.0 : (h_ipath[k] >= 0 ? h_maxscore[k] : 0.0);
-            }
-            pga_gene* const genes_out = coding || keep ? nullptr : R->gene_records((size_t)ngenes);
-            pga_gene* d_genes = nullptr;
-            if (ngenes > 0) {
-                DEVBUF(d_genes_out, pga_gene, keep ? keep->buf : "d_genes_out", ngenes + 1);
-                d_genes = d_genes_out;
-                HT(c, hipMemcpyAsync(d_gbegin, h_gbegin, sizeof(int64_t) * NC, hipMemcpyHostToDevice, st));
-                GcPtrs gcs{};
-                for (int g = 0; g < NG; g++) gcs.p[g] = ga[g].gc_cont;
-                hipLaunchKernelGGL(k_emit_genes, dim3((unsigned)((n_slots + 255) / 256)), dim3(256), 0, st, d_td, NC, n_slots, o, d_gene2, d_ngenes,
-                                   d_gbegin, P.meta ? 0 : 1, d_genes, lean_gather ? 1 : 0, ca, gcs);
-                if (genes_out) HT(c, hipMemcpyAsync(genes_out, d_genes, sizeof(pga_gene) * (size_t)ngenes, hipMemcpyDeviceToHost, st));
-                if (keep) { keep->d_genes = d_genes; keep->n_genes = ngenes; }
-            }
-            if (coding) {
-                // the coverage of the resident records: one bit per base of the batch, then a popcount per contig; NC counts come back
-                const int64_t words = total / 32 + 2;
-                DEVBUF(d_cover, uint32_t, "d_cover", words);
-                DEVBUF(d_coding, int64_t, "d_coding", NC + 1);
-                PINBUF(h_coding, int64_t, "h_coding", NC + 1);
-                HT(c, hipMemsetAsync(d_cover, 0, sizeof(uint32_t) * (size_t)words, st));
-                if (ngenes > 0)
-                    hipLaunchKernelGGL(k_cover_genes, dim3((unsigned)((ngenes + 3) / 4)), dim3(256), 0, st, d_genes, ngenes, d_ct, NC, d_cover);
-                hipLaunchKernelGGL(k_count_cover, dim3((unsigned)NC), dim3(256), 0, st, d_cover, d_ct, d_coding);
-                HT(c, hipMemcpyAsync(h_coding, d_coding, sizeof(int64_t) * NC, hipMemcpyDeviceToHost, st));
-                HT(c, hipGetLastError());
-                HT(c, hipStreamSynchronize(st));
-                memcpy(coding, h_coding, sizeof(int64_t) * NC);
-            }
-            if (P.want_nodes == 1 && out_nodes > 0) {
-                tracef.resize((size_t)out_nodes + 1); elim.resize((size_t)out_nodes + 1);
-                HT(c, hipMemcpyAsync(h.ndx, o.ndx, arena_all, hipMemcpyDeviceToHost, st));   // arena starts at `ndx`
-                HT(c, hipMemcpyAsync(tracef.data(), d_tracef, sizeof(int32_t) * (size_t)out_nodes, hipMemcpyDeviceToHost, st));
-                HT(c, hipMemcpyAsync(elim.data(), d_elim, (size_t)out_nodes, hipMemcpyDeviceToHost, st));
-            }
-            HT(c, hipEventRecord(f->e_stop, st));
-            HT(c, hipGetLastError());
-            HT(c, hipStreamSynchronize(st));
-            { float ms = 0; HT(c, hipEventElapsedTime(&ms, f->e_start, f->e_stop)); R->pub.t_total_ms = ms; }
-            tm.mark("genes+d2h");
-
-        }
-        if (P.want_nodes == 1) {
-            R->nodes.resize(NC);
-            for (int i = 0; i < NC; i++) {
-                pga_nodes& N = R->nodes[i];
-                memset(&N, 0, sizeof N);
-                const int k = win_chain[i];
-                if (k < 0) continue;
-                const int n = chains[k].n; const int64_t oo = out_off[i];
-                const bool single = !P.meta;
-                if (int rc = alloc_nodes(R, N, n)) return rc;
-                memcpy(N.ndx, h.ndx + oo, 4 * n); memcpy(N.stop_val, h.stop_val + oo, 4 * n); memcpy(N.type, h.type + oo, n); memcpy(N.strand, h.strand + oo, n);
-                memcpy(N.gc_cont, h.gc_cont + oo, 4 * n); memcpy(N.rbs, h.rbs + 2 * oo, 2 * n); memcpy(N.mot_ndx, h.mot_ndx + oo, 4 * n);
-                memcpy(N.mot_len, h.mot_len + oo, n); memcpy(N.mot_spacer, h.mot_spacer + oo, n); memcpy(N.mot_spacendx, h.mot_spacendx + oo, n);
-                memcpy(N.mot_score, h.mot_score + oo, 8 * n);
-                if (single) {   // nodes as left by the DP + eliminate_bad_genes (ref: lib.pyx:5296-5311)
-                    memcpy(N.edge, h.edge_dp + oo, n); memcpy(N.cscore, h.cscore_dp + oo, 8 * n); memcpy(N.sscore, h.sscore_dp + oo, 8 * n);
-                    memcpy(N.rscore, h.rscore_dp + oo, 8 * n); memcpy(N.uscore, h.uscore_dp + oo, 8 * n); memcpy(N.tscore, h.tscore_dp + oo, 8 * n);
-                    memcpy(N.score, h.score + oo, 8 * n); memcpy(N.traceb, h.traceb + oo, 4 * n); memcpy(N.tracef, tracef.data() + oo, 4 * n);
-                    memcpy(N.ov_mark, h.ov_mark + oo, n); memcpy(N.elim, elim.data() + oo, n); memcpy(N.star_ptr, h.star_ptr + 3 * oo, 12 * n);
-                } else {        // fresh re-score, DP fields reset (ref: lib.pyx:5380-5394)
-                    memcpy(N.edge, h.edge + oo, n); memcpy(N.cscore, h.cscore + oo, 8 * n); memcpy(N.sscore, h.sscore + oo, 8 * n);
-                    memcpy(N.rscore, h.rscore + oo, 8 * n); memcpy(N.uscore, h.uscore + oo, 8 * n); memcpy(N.tscore, h.tscore + oo, 8 * n);
-                    for (int j = 0; j < n; j++) { N.traceb[j] = -1; N.tracef[j] = -1; N.ov_mark[j] = -1; }
-                }
-            }
-        }
-        if (P.want_nodes) {
-            // the arena stays on the device for pga_render_genes until the next finder call (want_nodes 1 and PGA_NODES_DEVICE)
-            DevNodes& D = c->dev_nodes;
-            D.off.assign(NC, 0); D.n.assign(NC, 0); D.len.resize(NC);
-            for (int i = 0; i < NC; i++) {
-                D.len[i] = batch->ct[i].len;
-                if (win_chain[i] >= 0) { D.off[i] = out_off[i]; D.n[i] = chains[win_chain[i]].n; }
-            }
-            D.total = out_nodes;
-            const bool single = !P.meta;
-            D.a = DevNodeArrays{o.ndx, o.stop_val, o.type, o.strand, o.gc_cont,
-                                single ? o.edge_dp : o.edge, single ? o.cscore_dp : o.cscore, single ? o.sscore_dp : o.sscore,
-                                single ? o.rscore_dp : o.rscore, single ? o.uscore_dp : o.uscore, single ? o.tscore_dp : o.tscore,
-                                o.mot_score, o.mot_ndx, o.rbs, o.mot_len, o.mot_spacer};
-            D.batch = batch;
-            D.contigs = R->contigs.data();
-        }
+        if (const int rc = device_tail ? s.run_device_tail(!(tail_env && strcmp(tail_env, "device") == 0)) : s.run_host_tail()) return rc;
+        if (s.P.want_nodes == 1) { if (const int rc = s.copy_out_nodes()) return rc; }
+        if (s.P.want_nodes) s.keep_device_nodes();
     }
     tm.mark("results");
-    return publish(R, guard.r, P, out);
+    return s.publish_result(out);
 }
 
-static int find_impl(pga_ctx* c, const pga_batch* batch, const pga_params* pp, const int stage, const int tt_override, pga_result** out,
-                     const int32_t* model_of_contig, const int32_t* tt_of_contig) {
-    return find_impl_cov(c, batch, pp, stage, tt_override, out, model_of_contig, tt_of_contig, nullptr);
-}
 
 #include "train.inl"
 #include "circular.inl"
@@ -2898,7 +2892,7 @@ extern "C" int pga_find_coding_bases(pga_ctx* c, const pga_batch* batch, const p
     pga_params P = *pp;
     P.want_nodes = 0;                       // nothing of the nodes is kept or gathered for the host
     pga_result* r = nullptr;
-    const int rc = find_impl_cov(c, batch, &P, 0, 0, &r, model_of_contig, nullptr, coding_bases);
+    const int rc = find_impl(c, batch, &P, 0, 0, &r, model_of_contig, nullptr, coding_bases);
     if (rc != PGA_OK) return rc;
     for (int i = 0; i < batch->n; i++) { n_genes[i] = r->contigs[i].n_genes; score[i] = r->contigs[i].score; }
     pga_result_free(r);

@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "../../include/pyrodigal_amd.h"
+#include "find_pods.h"     // ContigDesc, ChainDesc
 
 #define PGA_MAX_NODE_DIST 500   // ref: _connection.h:5 / dprog.h
 #define PGA_MAX_OPP_OVLP  200
@@ -47,26 +48,6 @@ struct ModelConst {
     double st_wt;
     double negc;        // -0.15 * st_wt                       (ref: _connection.h:43-49)
     double igm[64];     // (2 - d/60) * 0.15 * st_wt, d = 0..60  (ref: _connection.h:73-75), host-computed
-};
-// One DP chain = one (contig, model) pass.
-struct ChainDesc {
-    int64_t off;        // first element of the chain in the per-chain arrays (scores, DP records)
-    int64_t topo_off;   // first element of the contig's nodes in the topology arrays of its group
-    int32_t n;          // node count
-    int32_t model;
-    int32_t contig;
-    int32_t first;      // 1: first model scored after (re-)extraction (edge flags not yet converted;
-                        //    ref: lib.pyx:2424-2434 mutates node.edge, which persists to the next bin)
-    // connection scoring of a SEGMENT of a chain (dp.hip "segmented chains"): the sub-chain reads the records of the
-    // chain it belongs to, from node `rebase` on, and keeps its own results at `off`
-    int64_t rec_off = -1;   // first DpSrc / DpTgt record of the sub-chain; -1: the chain's own, at `off`
-    int32_t rebase = 0;     // chain index of the sub-chain's node 0: index fields of DpTgt are shifted down by it
-    int32_t group = 0;      // translation-table group of the chain's model: whose topology arrays `topo_off` indexes (dp_wave.hip)
-    int64_t raw_off = -1;   // node scoring: read the raw coding scores of the chain at this offset (same contig, same model)
-                            // instead of the chain's own; -1: its own
-    int64_t soff = 0;       // stop nodes of the chains before this one (in launch order): its first slot in a launch over (chain, stop) pairs
-    int32_t sched_b0 = 0;   // wave-batch scorer: first 64-node batch of the chain's contig in its group's step schedule (dpw_core.h)
-    int32_t _pad0 = 0;
 };
 
 // Node fields in device memory (struct of arrays; each pointer covers the whole batch).

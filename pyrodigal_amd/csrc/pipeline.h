@@ -2,13 +2,6 @@
 #pragma once
 #include "pga_internal.h"
 
-// One contig of the batch: `len` bases starting at byte `base` of the concatenated batch buffers.
-struct ContigDesc {
-    int64_t base;
-    int32_t len;
-    int32_t _pad;
-};
-
 // One 3072-position tile of one contig (forward coordinates; every position of a contig of three bases or more lies in one) for the extraction kernels.
 #define PGA_STAGE_SLACK 8     // extra staging slots of every tile under GroupArrays::st_half
 struct TileDesc {

@@ -414,9 +414,6 @@ void tr_build_coverage_map(const unsigned int* real /* [4][4][4096] */, int* goo
 
 }  // namespace
 
-static int find_impl(pga_ctx* c, const pga_batch* batch, const pga_params* pp, const int stage, const int tt_override, pga_result** out,
-                     const int32_t* model_of_contig, const int32_t* tt_of_contig);
-
 // ref: lib.pyx:5236-5279 (GeneFinder._train) for every sequence of the batch at once: sequence g is genome g (the host layer
 // joins the contigs of a genome with the reference's spacer), trained with tts[g], sws[g], fns[g].  One device pass per stage or
 // round for all genomes; status[g] is PGA_OK or what a single-genome training would have returned.
