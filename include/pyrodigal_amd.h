@@ -811,6 +811,65 @@ int  pga_cluster_sketches(pga_ctx*, const int64_t* d_sketch, const int64_t* d_co
                           int64_t* n_edges /* host */);
 int  pga_cluster_stats(pga_ctx*, int64_t out[4]);
 
+/* Edges verified against the proteins themselves: an exact, integer, banded edit distance for pairs of token rows, a threshold on
+ * it, and the connected components of a caller's edge list -- the step behind pga_cluster_sketches for a caller who wants to know
+ * that two proteins are 90 % identical, not that their sketches say so.  The rows are tokens from anywhere: the tokens of
+ * pga_translate_genes_tokens or pga_gene_windows in either layout, or several calls' tensors joined.
+ *   Inputs (pga_align_pairs).  d_tokens: device memory of n_elems elements of elem_bytes 1, 4 or 8; it need only be element-aligned.
+ *     row_begin [G] and row_len [G]: host int64 arrays, row g is tokens[row_begin[g] .. row_begin[g] + row_len[g]).  d_pairs [P, 2]:
+ *     int64, device -- in practice the edges of pga_cluster_sketches.  Options: max_distance (0 .. 255), num, den
+ *     (1 <= num <= den <= 2^20).
+ *   Outputs.  d_distance [P]: int64, required.  d_pass [P]: int64, or NULL.  Nothing outside the named elements is touched.
+ *   For pair p = (a, b):
+ *   1. If a or b lies outside 0 .. G - 1: distance = -1 and pass = 0.  This is the convention of pga_sketch_pairs; nothing is read for
+ *      such a pair.
+ *   2. Otherwise let ed be the unit-cost Levenshtein distance of the two rows.  Elements are compared for equality over all their
+ *      bits.  bos, eos and pad are elements like any other.  a == b gives 0, and two empty rows give 0.
+ *   3. distance = min(ed, max_distance + 1).  The value max_distance + 1 means "more than max_distance".  The band is an implementation
+ *      detail and not part of the rule.  By Ukkonen's argument, a DP confined to diagonals |j - i| <= max_distance finds every distance
+ *      <= max_distance exactly.  |len_a - len_b| > max_distance decides a pair without a DP.
+ *   4. pass = 1 exactly when distance <= max_distance and distance * den <= (den - num) * max(len_a, len_b).  That is identity over
+ *      the longer row, 1 - ed / longer >= num / den, in integers.  The result depends on the arguments alone.
+ *   Refusals.  PGA_EINVAL, pga_last_error naming the row or field, all on the host before anything is allocated or launched:
+ *     elem_bytes; max_distance, num, den; G or P above INT32_MAX; a row that does not lie inside 0 .. n_elems, or whose length is
+ *     outside 0 .. 2^30; a NULL d_pairs or d_distance (d_tokens where a row has an element); a pointer that is not aligned to its
+ *     elements; and the device-pointer query on every pointer given.  P = 0 returns PGA_OK without a launch.
+ *   Ordering and concurrency.  As pga_sketch_pairs: the call waits for what `stream` holds, works on the context's upload stream, and
+ *     on return the tensors are complete for any stream.  One such call at a time per context; row_begin and row_len go through the
+ *     upload lease, and a steady run allocates nothing.
+ * pga_align_stats: {pairs, pairs decided without a DP, pairs that ran the DP, pairs that passed} of the context's last
+ * pga_align_pairs call.
+ *
+ * pga_cluster_edges: the connected components of a caller's edge list -- the edges of pga_cluster_sketches filtered by any rule,
+ * d_pass of pga_align_pairs among them.
+ *   Inputs.  d_edges [E, 2]: int64.  d_keep [E]: int64 or NULL; nonzero means use the edge, NULL means use all.  n: the number of
+ *     records.  d_weight [n]: int64 or NULL, which means all weights are equal.
+ *   Outputs.  d_cluster [n], required.  d_representative and d_size: optional, with capacity >= n.  *n_clusters.  *n_used: the kept
+ *     edges with both indices in 0 .. n - 1.
+ *   A kept edge with an index out of range is ignored and not counted.  a == b is counted and joins nothing.
+ *   Clusters.  The connected components of the graph on 0 .. n - 1 with the used edges.  Clusters are numbered 0 .. U - 1 in
+ *     increasing order of their smallest member.  cluster[g] is that number.  representative[u] is the member of greatest weight,
+ *     smallest index on a tie.  size[u] is its number of members.
+ *   Refusals.  PGA_EINVAL, all on the host before anything is allocated or launched: n or E negative or above INT32_MAX; capacity
+ *     below n with d_representative or d_size given; a NULL d_cluster or count pointer (d_edges where E > 0); a pointer that is not
+ *     8-byte aligned; and the device-pointer query on every pointer given.  n = 0 returns PGA_OK with both counts 0 and no launch.
+ *   Ordering, concurrency and work memory: those of pga_cluster_sketches, whose block of the context it shares (32 bytes per
+ *     record).  The result depends on the arguments alone. */
+typedef struct pga_align_opts {
+    int32_t elem_bytes;         /* 1, 4 or 8 */
+    int32_t max_distance;       /* 0 .. 255 */
+    int32_t num, den;           /* the threshold: 1 - distance / longer >= num / den */
+} pga_align_opts;
+int  pga_align_pairs(pga_ctx*, const void* d_tokens, int64_t n_elems, const int64_t* row_begin /* host [G] */,
+                     const int64_t* row_len /* host [G] */, int64_t n_rows, const int64_t* d_pairs /* [P, 2] */, int64_t n_pairs,
+                     const pga_align_opts*, int64_t* d_distance /* [P] */, int64_t* d_pass /* [P] or NULL */,
+                     void* stream /* hipStream_t, NULL = the null stream */);
+int  pga_align_stats(pga_ctx*, int64_t out[4]);
+int  pga_cluster_edges(pga_ctx*, const int64_t* d_edges /* [E, 2] */, const int64_t* d_keep /* [E] or NULL */, int64_t n_edges,
+                       int64_t n, const int64_t* d_weight /* [n] or NULL */, int64_t* d_cluster /* [n], required */,
+                       int64_t* d_representative, int64_t* d_size, int64_t capacity, void* stream, int64_t* n_clusters /* host */,
+                       int64_t* n_used /* host */);
+
 /* ---- text output ------------------------------------------------------------------ */
 /* GFF, protein FASTA, gene FASTA, GenBank and the start-score file of gene records, rendered on the device from a resident
  * batch: byte for byte what the host writers Genes.write_gff / write_translations / write_genes / write_genbank / write_scores

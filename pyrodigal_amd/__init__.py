@@ -13,7 +13,8 @@ _LIB_NAMES = ("GeneFinder", "Genes", "Gene", "Nodes", "Node", "Sequence", "Train
               "IDEAL_SINGLE_GENOME", "TerminalRepeats")
 _CABI_NAMES = ("DeviceSequences", "ProteinTokens", "DeviceProteins", "BaseLabels", "DeviceLabels", "GeneWindows",
                "DeviceWindows", "StartCandidates", "DeviceStarts", "KmerCounts", "DeviceCounts", "ProteinGroups", "DeviceGroups",
-               "ProteinSketches", "DeviceSketches", "ProteinClusters", "DeviceClusters")
+               "ProteinSketches", "DeviceSketches", "ProteinClusters", "DeviceClusters",
+               "ProteinAlignments", "VerifiedClusters", "DeviceVerifiedClusters")
 __all__ = list(_LIB_NAMES) + ["TableSelection"] + list(_CABI_NAMES)
 
 from .tables import TableSelection      # pure Python: the result of GeneFinder.select_translation_table

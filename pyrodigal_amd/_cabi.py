@@ -36,6 +36,7 @@ EXPORTS = [
     "pga_group_proteins", "pga_protein_groups_stats",
     "pga_sketch_proteins", "pga_sketch_pairs", "pga_sketch_passes",
     "pga_cluster_sketches", "pga_cluster_stats",
+    "pga_align_pairs", "pga_align_stats", "pga_cluster_edges",
 ]
 STAGE_EXTRACT, STAGE_SCORE, STAGE_OVERLAP, STAGE_SEQUENCE = 1, 2, 3, 4
 
@@ -143,6 +144,10 @@ class SketchOpts(ctypes.Structure):
 class ClusterOpts(ctypes.Structure):
     _fields_ = [("size", ctypes.c_int32), ("probes", ctypes.c_int32), ("num", ctypes.c_int32), ("den", ctypes.c_int32),
                 ("min_union", ctypes.c_int32), ("_pad", ctypes.c_int32)]
+
+
+class AlignOpts(ctypes.Structure):
+    _fields_ = [("elem_bytes", ctypes.c_int32), ("max_distance", ctypes.c_int32), ("num", ctypes.c_int32), ("den", ctypes.c_int32)]
 
 
 class StartOpts(ctypes.Structure):
@@ -254,6 +259,11 @@ def load():
     L.pga_cluster_sketches.restype = ctypes.c_int
     L.pga_cluster_sketches.argtypes = [vp, vp, vp, vp, i64, _P(ClusterOpts), vp, vp, vp, i64, vp, vp, vp, i64, vp, _P(i64), _P(i64)]
     L.pga_cluster_stats.restype = ctypes.c_int; L.pga_cluster_stats.argtypes = [vp, _P(i64)]
+    L.pga_align_pairs.restype = ctypes.c_int
+    L.pga_align_pairs.argtypes = [vp, vp, i64, vp, vp, i64, vp, i64, _P(AlignOpts), vp, vp, vp]
+    L.pga_align_stats.restype = ctypes.c_int; L.pga_align_stats.argtypes = [vp, _P(i64)]
+    L.pga_cluster_edges.restype = ctypes.c_int
+    L.pga_cluster_edges.argtypes = [vp, vp, vp, i64, i64, vp, vp, vp, vp, i64, vp, _P(i64), _P(i64)]
     L.pga_start_plan_create.restype = ctypes.c_int
     L.pga_start_plan_create.argtypes = [vp, vp, i64, vp, _P(vp), vp, vp]
     L.pga_start_plan_write.restype = ctypes.c_int
@@ -1448,12 +1458,32 @@ class DeviceProteins:
     ``gene_begin``: the genes of contig i are rows ``gene_begin[i] .. gene_begin[i + 1]`` (``None`` when the records were not in
     contig order); ``proteins[i]``: contig i's rows or slice as a view of ``tokens``."""
 
-    def __init__(self, tokens, lengths, offsets, gene_begin, device):
+    def __init__(self, tokens, lengths, offsets, gene_begin, device, L=None, ctx_h=None):
         self.tokens, self.lengths, self.offsets, self.gene_begin, self.device = tokens, lengths, offsets, gene_begin, device
+        self._L, self._ctx_h = L, ctx_h
 
     @property
     def proteins(self):
         return _gene_views(self, self.tokens)
+
+    def align(self, pairs, spec, out=None, stream=None):
+        """``(distance, passed)`` of every pair of proteins (``pga_align_pairs``): ``pairs`` is a contiguous int64 ``[P, 2]`` device
+        tensor of gene indices -- the ``edges`` of a :class:`DeviceClusters`, say -- and ``spec`` a :class:`ProteinAlignments`.
+        ``distance[p]`` is the edit distance of the two token rows, specials included, capped at ``spec.max_distance + 1``;
+        ``passed[p]`` is 1 where it is within ``max_distance`` and the identity over the longer row is at least
+        ``spec.min_identity``; a pair with an index outside ``0 .. G - 1`` gets -1 and 0.  Either layout: the pad of a padded
+        tensor is not read.  ``out``: two contiguous int64 ``[P]`` objects with ``__cuda_array_interface__`` (``None`` for the
+        second), omitted: torch tensors.  The context of the call that made the tokens must still be open."""
+        if self._L is None:
+            raise ValueError("this DeviceProteins names no context: use Context.align_pairs")
+        n = len(self.lengths)
+        if self.offsets is not None:
+            begin = np.ascontiguousarray(self.offsets[:n], np.int64)
+        else:
+            shape, strides = _device_array(self.tokens, "tokens")[1:]
+            eb = np.dtype(str(self.tokens.__cuda_array_interface__["typestr"])).itemsize
+            begin = np.arange(n, dtype=np.int64) * (strides[0] // eb if n > 1 else (shape[1] if len(shape) > 1 else 0))
+        return align_into(self._L, self._ctx_h, self.device, self.tokens, begin, self.lengths, pairs, spec, out, stream)
 
     def cu_seqlens(self):
         """The exclusive scan of ``lengths`` as an int32 tensor on the tokens' device (torch)."""
@@ -1563,7 +1593,7 @@ def tokens_into(L, ctx_h, batch_h, device, n_contigs, genes, tables, spec, out=N
     args = (batch_h, n, ctypes.c_void_p(genes.ctypes.data), p_tab)
     out, off, len_out = _rows_into(L, ctx_h, "pga_translate_genes_tokens", args, spec, lens, device, out, stream)
     assert np.array_equal(len_out, lens)
-    return DeviceProteins(out, lens, off, _gene_begin(genes, n_contigs), device)
+    return DeviceProteins(out, lens, off, _gene_begin(genes, n_contigs), device, L, ctx_h)
 
 
 def _translate_tokens(self, batch, result_or_genes, spec, out=None, tables=None, stream=None):
@@ -2446,10 +2476,28 @@ class DeviceClusters:
     Tensors for which ``out=`` gave ``None`` are ``None``.  ``spec``: the :class:`ProteinClusters`; ``sketches``: the
     :class:`DeviceSketches` that were clustered (``None`` for tensors given to ``Context.cluster_sketches``)."""
 
-    def __init__(self, cluster, representatives, sizes, n_clusters, edges, edge_shared, edge_union, n_edges, spec, sketches, device):
+    def __init__(self, cluster, representatives, sizes, n_clusters, edges, edge_shared, edge_union, n_edges, spec, sketches, device,
+                 L=None, ctx_h=None):
         self.cluster, self.representatives, self.sizes, self.n_clusters = cluster, representatives, sizes, n_clusters
         self.edges, self.edge_shared, self.edge_union, self.n_edges = edges, edge_shared, edge_union, n_edges
         self.spec, self.sketches, self.device = spec, sketches, device
+        self._L, self._ctx_h = L, ctx_h
+
+    def relink(self, keep=None, weights=None, out=None, stream=None):
+        """The components of the rows under the ``edges`` that ``keep`` names (``pga_cluster_edges``): ``keep`` is an int64 ``[E]``
+        device tensor, nonzero where the edge is used -- the ``passed`` of ``DeviceProteins.align(self.edges, ...)``, say -- or
+        ``None`` for all of them.  ``weights`` defaults as in ``DeviceSketches.cluster``: the ``windows`` of the sketches that were
+        clustered, and equal weights where there are none.  ``out``: ``(cluster [G], representatives [>= G], sizes [>= G])``,
+        ``None`` allowed for the last two; omitted: torch tensors.  Returns ``(cluster, representatives, sizes, n_clusters,
+        n_used)``.  The context of the call that made the clusters must still be open."""
+        if self._L is None:
+            raise ValueError("this DeviceClusters names no context: use Context.cluster_edges")
+        if self.edges is None:
+            raise ValueError("this DeviceClusters has no edges: out= left them out")
+        if weights is None and self.sketches is not None:
+            weights = self.sketches.windows
+        n = _device_array(self.cluster, "cluster")[1][0]
+        return edges_into(self._L, self._ctx_h, self.device, self.edges, n, keep, weights, out, stream)
 
 
 def clusters_into(L, ctx_h, device, sketch, count, weight, spec, out=None, stream=None, sketches=None):
@@ -2500,7 +2548,8 @@ def clusters_into(L, ctx_h, device, sketch, count, weight, spec, out=None, strea
     U, E = int(n_clusters.value), int(n_edges.value)
     cut = lambda x, k: None if x is None else (x[:k] if hasattr(x, "__getitem__") else x)      # noqa: E731
     W = min(E, edge_capacity)
-    return DeviceClusters(cluster, cut(reps, U), cut(sizes, U), U, cut(edges, W), cut(eshared, W), cut(eunion, W), E, spec, sketches, device)
+    return DeviceClusters(cluster, cut(reps, U), cut(sizes, U), U, cut(edges, W), cut(eshared, W), cut(eunion, W), E, spec, sketches, device,
+                          L, ctx_h)
 
 
 def _cluster_sketches(self, sketches, counts, spec, weights=None, out=None, stream=None):
@@ -2519,6 +2568,211 @@ def _cluster_stats(self):
     if rc != PGA_OK:
         _raise(self.L, self.h, rc, "pga_cluster_stats")
     return {"probes": int(out[0]), "candidates": int(out[1]), "edges": int(out[2]), "clusters": int(out[3])}
+
+
+class ProteinAlignments(_TensorRule):
+    """How ``DeviceProteins.align`` / ``Context.align_pairs`` / ``find_verified_clusters_batch`` check a pair of token rows against
+    each other (``pga_align_opts``; the rule is in ``pyrodigal_amd.h``): the unit-cost edit distance of the two rows, exact up to
+    ``max_distance`` and ``max_distance + 1`` beyond it, and a pair passes when the distance is at most ``max_distance`` and the
+    identity over the longer row, ``1 - distance / longer``, is at least ``min_identity``.
+
+    ``max_distance``: 0 .. 255.  ``min_identity``: a ``(num, den)`` pair of ints with ``1 <= num <= den <= 2**20``, or a
+    ``fractions.Fraction`` -- not a float: the comparison is ``distance * den <= (den - num) * longer`` in integers, so that the
+    result depends on the arguments alone.  Everything that needs no device is checked here.  Hashable and picklable."""
+
+    def __init__(self, max_distance=32, min_identity=(9, 10)):
+        if isinstance(max_distance, (bool, np.bool_)) or not isinstance(max_distance, (int, np.integer)):
+            raise TypeError(f"max_distance must be an int, not {type(max_distance).__name__}")
+        if isinstance(min_identity, (float, np.floating)):
+            raise TypeError("min_identity must be a (num, den) pair of ints or a fractions.Fraction, not a float: the threshold is "
+                            "applied as distance * den <= (den - num) * longer in integers, and a float names no such pair (0.9 is not 9 / 10)")
+        if isinstance(min_identity, fractions.Fraction):
+            min_identity = (min_identity.numerator, min_identity.denominator)
+        try:
+            num, den = min_identity
+        except (TypeError, ValueError):
+            raise TypeError("min_identity must be a (num, den) pair of ints or a fractions.Fraction, not %r" % (min_identity,)) from None
+        for name, v in (("num", num), ("den", den)):
+            if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)):
+                raise TypeError(f"min_identity: {name} must be an int, not {type(v).__name__}")
+        if not 0 <= max_distance <= 255:
+            raise ValueError(f"max_distance must be 0 .. 255, not {max_distance}")
+        if not 1 <= num <= den <= (1 << 20):
+            raise ValueError(f"min_identity must have 1 <= num <= den <= 2**20, not {num} / {den}")
+        self.max_distance, self.min_identity = int(max_distance), (int(num), int(den))
+
+    row, unit = "pair", "distances"
+    dtype, typestr, elem_bytes = "int64", "<i8", 8
+    _fields = ("max_distance", "min_identity")
+
+    def __repr__(self):
+        return "pyrodigal_amd.ProteinAlignments(max_distance=%r, min_identity=%r)" % self._key()
+
+    def opts(self, elem_bytes):
+        o = AlignOpts()
+        o.elem_bytes, o.max_distance = int(elem_bytes), self.max_distance
+        o.num, o.den = self.min_identity
+        return o
+
+
+def _host_rows(values, name):
+    """``row_begin`` / ``row_len`` as a contiguous int64 array: an integer numpy array as it is, anything else through ``_host_ints``."""
+    if isinstance(values, np.ndarray) and values.dtype.kind in "iu" and values.ndim == 1:
+        return np.ascontiguousarray(values, np.int64)
+    return _host_ints(values, name)
+
+
+def align_into(L, ctx_h, device, tokens, row_begin, row_len, pairs, spec, out=None, stream=None):
+    """``pga_align_pairs`` on raw handles (what ``DeviceProteins.align`` and ``Context.align_pairs`` share): ``tokens`` is a device
+    tensor of uint8, int32 or int64 elements with a contiguous last dimension, row g its elements ``row_begin[g] .. row_begin[g] +
+    row_len[g]`` (host integers, counted from the tensor's first element), ``pairs`` a contiguous int64 ``[P, 2]`` device tensor.
+    ``out``: ``(distance [P], passed [P])``, contiguous int64 objects with ``__cuda_array_interface__``, ``None`` allowed for the
+    second; omitted: torch tensors.  Returns ``(distance, passed)``."""
+    if not isinstance(spec, ProteinAlignments):
+        raise TypeError("the alignment rule must be a ProteinAlignments, not %r" % type(spec).__name__)
+    p_tok, tshape, tstrides = _device_array(tokens, "tokens")
+    typestr = str(tokens.__cuda_array_interface__["typestr"])
+    if typestr not in _DEVICE_DTYPES:
+        raise TypeError(f"tokens has dtype {typestr}: the rows are uint8, int32 or int64 elements")
+    eb = _DEVICE_DTYPES[typestr]
+    if any(st < 0 or st % eb for st in tstrides) or (tshape and tshape[-1] > 1 and tstrides[-1] != eb):
+        raise ValueError("tokens needs a contiguous last dimension and rows a whole, positive number of elements apart")
+    n_elems = 0 if not tshape or 0 in tshape else 1 + sum((n - 1) * (st // eb) for n, st in zip(tshape, tstrides))
+    begin, lens = _host_rows(row_begin, "row_begin"), _host_rows(row_len, "row_len")
+    if len(begin) != len(lens):
+        raise ValueError(f"row_begin has {len(begin)} entries and row_len {len(lens)}")
+    shape = _device_array(pairs, "pairs")[1]
+    if len(shape) != 2 or shape[1] != 2:
+        raise ValueError(f"pairs needs shape [P, 2], not {list(shape)}")
+    P = shape[0]
+    p_pairs = _group_output(pairs, "pairs", (P, 2), True)
+    if out is None:
+        out, stream = _torch_outputs(device, stream, [(P, "int64"), (P, "int64")], "two device arrays")
+    out = tuple(out)
+    if len(out) != 2:
+        raise ValueError("out must be (distance, passed), %d objects were given" % len(out))
+    p_dist, p_pass = _group_output(out[0], "distance", (P,), True), _group_output(out[1], "passed", (P,), False)
+    o = spec.opts(eb)
+    rc = L.pga_align_pairs(ctx_h, ctypes.c_void_p(p_tok), n_elems, ctypes.c_void_p(begin.ctypes.data), ctypes.c_void_p(lens.ctypes.data), len(lens),
+                           ctypes.c_void_p(p_pairs), P, ctypes.byref(o), ctypes.c_void_p(p_dist), ctypes.c_void_p(p_pass),
+                           ctypes.c_void_p(DeviceSequences._stream_of(out[0], stream)))
+    if rc != PGA_OK:
+        _raise(L, ctx_h, rc, "pga_align_pairs")
+    return out
+
+
+def _align_pairs(self, tokens, row_begin, row_len, pairs, spec, out=None, stream=None):
+    """Rows of tokens from anywhere -- the ``torch.cat`` of several calls' ``DeviceProteins.tokens``, the tokens of
+    ``gene_windows`` -- compared pair by pair on the device (``pga_align_pairs``).  ``tokens``: a device tensor of uint8, int32 or
+    int64 elements; ``row_begin`` and ``row_len``: host integers, row g being elements ``row_begin[g] .. row_begin[g] + row_len[g]``
+    of it; ``pairs``: a contiguous int64 ``[P, 2]`` device tensor; ``spec``: a :class:`ProteinAlignments`.  ``out`` and ``stream``
+    as in :func:`align_into`.  Returns ``(distance, passed)``."""
+    return align_into(self.L, self.h, self.device, tokens, row_begin, row_len, pairs, spec, out, stream)
+
+
+def _align_stats(self):
+    """How the context's last ``align_pairs`` call went (``pga_align_stats``): the pairs, those decided without a DP (an index out
+    of range, a pair of a row with itself, lengths further apart than ``max_distance``), those that ran the DP, and those that passed."""
+    out = (ctypes.c_int64 * 4)()
+    rc = self.L.pga_align_stats(self.h, out)
+    if rc != PGA_OK:
+        _raise(self.L, self.h, rc, "pga_align_stats")
+    return {"pairs": int(out[0]), "decided": int(out[1]), "aligned": int(out[2]), "passed": int(out[3])}
+
+
+def edges_into(L, ctx_h, device, edges, n, keep=None, weights=None, out=None, stream=None):
+    """``pga_cluster_edges`` on raw handles (what ``DeviceClusters.relink`` and ``Context.cluster_edges`` share): the components of
+    the records ``0 .. n - 1`` under the int64 ``[E, 2]`` device tensor ``edges``, of which ``keep`` (int64 ``[E]``, or ``None``:
+    all) names the ones to use; ``weights``: int64 ``[n]`` or ``None``.  ``out``: ``(cluster [n], representatives [>= n], sizes
+    [>= n])``, ``None`` allowed for the last two; omitted: torch tensors.  Returns ``(cluster, representatives, sizes, n_clusters,
+    n_used)``, the second and third cut to the clusters."""
+    if isinstance(n, (bool, np.bool_)) or not isinstance(n, (int, np.integer)):
+        raise TypeError(f"n must be an int, not {type(n).__name__}")
+    n = int(n)
+    if n < 0:
+        raise ValueError(f"n must not be negative: {n}")
+    shape = _device_array(edges, "edges")[1]
+    if len(shape) != 2 or shape[1] != 2:
+        raise ValueError(f"edges needs shape [E, 2], not {list(shape)}")
+    E = shape[0]
+    p_edges = _group_output(edges, "edges", (E, 2), True)
+    p_keep, p_w = _group_output(keep, "keep", (E,), False), _group_output(weights, "weights", (n,), False)
+    if out is None:
+        out, stream = _torch_outputs(device, stream, [(n, "int64"), (n, "int64"), (n, "int64")], "three device arrays")
+    out = tuple(out)
+    if len(out) != 3:
+        raise ValueError("out must be (cluster, representatives, sizes), %d objects were given" % len(out))
+    cluster, reps, sizes = out
+    p_cluster = _group_output(cluster, "cluster", (n,), True)
+    p_reps, p_sizes = _group_output(reps, "representatives", (n,), False), _group_output(sizes, "sizes", (n,), False)
+    capacity = min([_device_array(x, "out")[1][0] for x in (reps, sizes) if x is not None] or [n])
+    n_clusters, n_used = ctypes.c_int64(0), ctypes.c_int64(0)
+    rc = L.pga_cluster_edges(ctx_h, ctypes.c_void_p(p_edges), ctypes.c_void_p(p_keep), E, n, ctypes.c_void_p(p_w), ctypes.c_void_p(p_cluster),
+                             ctypes.c_void_p(p_reps), ctypes.c_void_p(p_sizes), capacity,
+                             ctypes.c_void_p(DeviceSequences._stream_of(cluster, stream)), ctypes.byref(n_clusters), ctypes.byref(n_used))
+    if rc != PGA_OK:
+        _raise(L, ctx_h, rc, "pga_cluster_edges")
+    U = int(n_clusters.value)
+    cut = lambda x: None if x is None else (x[:U] if hasattr(x, "__getitem__") else x)      # noqa: E731
+    return cluster, cut(reps), cut(sizes), U, int(n_used.value)
+
+
+def _cluster_edges(self, edges, n, keep=None, weights=None, out=None, stream=None):
+    """The connected components of the records ``0 .. n - 1`` under an edge list of the caller's, on the device
+    (``pga_cluster_edges``): numbering, representatives and sizes as ``cluster_sketches`` gives them.  ``edges``: a contiguous int64
+    ``[E, 2]`` device tensor; ``keep``: int64 ``[E]``, nonzero where the edge is used, ``None``: all; ``weights``: int64 ``[n]`` or
+    ``None``.  An edge with an index outside ``0 .. n - 1`` is ignored.  ``out`` and ``stream`` as in :func:`edges_into`.  Returns
+    ``(cluster, representatives, sizes, n_clusters, n_used)``."""
+    return edges_into(self.L, self.h, self.device, edges, n, keep, weights, out, stream)
+
+
+class VerifiedClusters(_TensorRule):
+    """How ``find_verified_clusters_batch`` clusters near-identical proteins and checks every edge against the proteins themselves:
+    ``clusters`` (a :class:`ProteinClusters` over the protein unit) proposes and accepts pairs from the sketches, ``alignments`` (a
+    :class:`ProteinAlignments`) decides each accepted pair by the edit distance of the two proteins' tokens under ``tokens`` (a
+    :class:`ProteinTokens`; default: the 20 amino acids and X as uint8, ragged), and the clusters are the components of the pairs
+    that passed.  Hashable and picklable."""
+
+    def __init__(self, clusters=None, alignments=None, tokens=None):
+        clusters = ProteinClusters() if clusters is None else clusters
+        alignments = ProteinAlignments() if alignments is None else alignments
+        tokens = ProteinTokens(AMINO_ACIDS + "X", dtype="uint8", layout="ragged") if tokens is None else tokens
+        for name, v, cls in (("clusters", clusters, ProteinClusters), ("alignments", alignments, ProteinAlignments), ("tokens", tokens, ProteinTokens)):
+            if not isinstance(v, cls):
+                raise TypeError("%s must be a %s, not %r" % (name, cls.__name__, type(v).__name__))
+        if clusters.sketches.of != "protein":
+            raise ValueError("clusters.sketches sketches the %r unit: the edges are verified on the proteins' tokens, so the sketches must "
+                             "be those of the proteins (unit=\"protein\")" % (clusters.sketches.of,))
+        self.clusters, self.alignments, self.tokens = clusters, alignments, tokens
+
+    row, unit, per_contig = "gene", "clusters", "tables"
+    dtype, typestr, elem_bytes = "int64", "<i8", 8
+    _fields = ("clusters", "alignments", "tokens")
+
+    def write(self, L, ctx_h, batch_h, device, genes, tables, out=None, stream=None):
+        # (the finder's call: tokens, sketches, candidate clusters and distances into new tensors, the verified clusters into `out`)
+        proteins = tokens_into(L, ctx_h, batch_h, device, len(tables), genes, tables, self.tokens, None, stream)
+        sk = sketches_into(L, ctx_h, batch_h, device, len(tables), genes, tables, self.clusters.sketches, None, stream)
+        cand = sk.cluster(self.clusters, None, None, stream)
+        distance, passed = proteins.align(cand.edges, self.alignments, None, stream)
+        cluster, reps, sizes, U, used = cand.relink(passed, None, out, stream)
+        return DeviceVerifiedClusters(cluster, reps, sizes, U, distance, passed, used, cand, proteins, self)
+
+    def __repr__(self):
+        return "pyrodigal_amd.VerifiedClusters(%r, %r, %r)" % self._key()
+
+
+class DeviceVerifiedClusters:
+    """Clusters of proteins whose every edge was verified by edit distance, in device memory, all int64.  ``cluster`` ``[G]``,
+    ``representatives`` ``[U]``, ``sizes`` ``[U]`` and ``n_clusters`` as in :class:`DeviceClusters`, over the edges that passed;
+    ``edge_distance`` and ``edge_passed``: ``[E]``, the distance and the verdict of every edge of ``candidates.edges``;
+    ``n_passed``: how many passed.  ``candidates``: the :class:`DeviceClusters` of the sketch stage, with its ``edges``;
+    ``proteins``: the :class:`DeviceProteins` that were aligned; ``spec``: the :class:`VerifiedClusters`."""
+
+    def __init__(self, cluster, representatives, sizes, n_clusters, edge_distance, edge_passed, n_passed, candidates, proteins, spec):
+        self.cluster, self.representatives, self.sizes, self.n_clusters = cluster, representatives, sizes, n_clusters
+        self.edge_distance, self.edge_passed, self.n_passed = edge_distance, edge_passed, n_passed
+        self.candidates, self.proteins, self.spec = candidates, proteins, spec
 
 
 
@@ -3097,6 +3351,9 @@ Context.protein_sketches = _protein_sketches
 Context.protein_sketch_passes = _protein_sketch_passes
 Context.cluster_sketches = _cluster_sketches
 Context.cluster_stats = _cluster_stats
+Context.align_pairs = _align_pairs
+Context.align_stats = _align_stats
+Context.cluster_edges = _cluster_edges
 Context.train = _train
 Context.train_batch = _train_batch
 Context.upload = _upload

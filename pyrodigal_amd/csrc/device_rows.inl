@@ -1,7 +1,7 @@
 // The host side that the calls which write device tensors share, and the rows some of them write.  DevCall: the
 // refusals, the shared checks of records, tables and destinations, and the tail of a call -- for all of pga_translate_genes_tokens,
-// pga_label_bases, pga_gene_windows, pga_count_kmers, pga_group_proteins, pga_sketch_proteins, pga_sketch_pairs, pga_cluster_sketches and
-// the pga_start_plan_* calls.  Staging: the tables of a call laid out in the upload lease.  RowDest, on top of DevCall: rows of 1-, 4- or
+// pga_label_bases, pga_gene_windows, pga_count_kmers, pga_group_proteins, pga_sketch_proteins, pga_sketch_pairs, pga_cluster_sketches,
+// pga_align_pairs, pga_cluster_edges and the pga_start_plan_* calls.  Staging: the tables of a call laid out in the upload lease.  RowDest, on top of DevCall: rows of 1-, 4- or
 // 8-byte elements in a caller's tensor, ragged or padded, at any element alignment, which k_translate_tokens (translate_tokens.inl),
 // k_label_bases (label_bases.inl) and k_gene_windows (gene_windows.inl) write.  Included by translate.hip, inside its anonymous
 // namespace, in front of the kernel files.

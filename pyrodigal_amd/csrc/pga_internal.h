@@ -239,7 +239,8 @@ struct pga_ctx {
     int64_t group_stats[2] = {0, 0};                   // pga_protein_groups_stats: rounds and differing pairs of the last pga_group_proteins call
     int64_t sketch_passes = -1;                        // pga_sketch_passes: insertions tried in the last pga_sketch_proteins call (PGA_SKETCH_COUNT_PASSES builds), -1: not counted
     int64_t cluster_stats[4] = {0, 0, 0, 0};           // pga_cluster_stats: probes, distinct candidates, edges and clusters of the last pga_cluster_sketches call
-    char* cluster_dev = nullptr; size_t cluster_cap = 0;   // pga_cluster_sketches (translate.hip): its work arrays, kept across calls and grown as needed
+    char* cluster_dev = nullptr; size_t cluster_cap = 0;   // pga_cluster_sketches and pga_cluster_edges (translate.hip): their work arrays, kept across calls and grown as needed
+    int64_t align_stats[4] = {0, 0, 0, 0};             // pga_align_stats: pairs, decided without a DP, ran the DP and passed in the last pga_align_pairs call
     int poison = -1;                                   // pga_debug_poison: the fill byte of newly acquired float buffers, -1: off
     std::vector<int64_t> render_seqnums;               // pga_render_seqnums: the seqnum of every contig of the batches rendered next (empty: first_seqnum + i)
 };

@@ -101,6 +101,7 @@ int64_t gene_residues(const pga_gene& G, const int include_stop) {
 #include "protein_groups.inl"
 #include "protein_sketches.inl"
 #include "protein_clusters.inl"
+#include "protein_alignments.inl"
 #include "start_candidates.inl"
 
 // the records as k_string_digest, k_group_verify and k_sketch read them
@@ -649,6 +650,22 @@ void pga_cluster_release(pga_ctx* c) {
     c->cluster_dev = nullptr; c->cluster_cap = 0;
 }
 
+// the context's block, grown to at least `bytes`, for a call that holds the upload lease: the lease goes back when there is no memory
+static int pga_cluster_block(pga_ctx* c, const char* fn, const size_t bytes) {
+    if (c->cluster_cap >= bytes) return PGA_OK;
+    pga_cluster_release(c);
+    const size_t want = bytes + bytes / 4 + 4096;
+    if (hipMalloc((void**)&c->cluster_dev, want) != hipSuccess) {
+        (void)hipGetLastError();
+        c->cluster_dev = nullptr;
+        pga_upload_lease_give(c);
+        c->err = std::string(fn) + ": no device memory for " + std::to_string(want) + " bytes of work arrays";
+        return PGA_ENOMEM;
+    }
+    c->cluster_cap = want;
+    return PGA_OK;
+}
+
 extern "C" int pga_cluster_stats(pga_ctx* c, int64_t out[4]) {
     if (!c || !out) return PGA_EINVAL;
     memcpy(out, c->cluster_stats, sizeof c->cluster_stats);
@@ -701,18 +718,7 @@ extern "C" int pga_cluster_sketches(pga_ctx* c, const int64_t* d_sketch, const i
     Staging tab(256);
     const size_t p_small = tab.take(256);
     if (const int rc = tab.lease(c)) return rc;                  // (one such call at a time per context from here on)
-    if (c->cluster_cap < work.bytes()) {
-        pga_cluster_release(c);
-        const size_t want = work.bytes() + work.bytes() / 4 + 4096;
-        if (hipMalloc((void**)&c->cluster_dev, want) != hipSuccess) {
-            (void)hipGetLastError();
-            c->cluster_dev = nullptr;
-            pga_upload_lease_give(c);
-            c->err = "pga_cluster_sketches: no device memory for " + std::to_string(want) + " bytes of work arrays";
-            return PGA_ENOMEM;
-        }
-        c->cluster_cap = want;
-    }
+    if (const int rc = pga_cluster_block(c, "pga_cluster_sketches", work.bytes())) return rc;
     char* const W = c->cluster_dev;
     volatile long long* const h_small = tab.pin<volatile long long>(p_small);
     ClArgs a{};
@@ -767,6 +773,135 @@ extern "C" int pga_cluster_sketches(pga_ctx* c, const int64_t* d_sketch, const i
     }, [&] {
         *n_edges = h_small[0]; *n_clusters = h_small[1];
         c->cluster_stats[0] = h_small[3]; c->cluster_stats[1] = h_small[2]; c->cluster_stats[2] = h_small[0]; c->cluster_stats[3] = h_small[1];
+    });
+}
+
+// ---- edges verified by edit distance, and the components of a caller's edges (protein_alignments.inl) ---------------------------
+extern "C" int pga_align_stats(pga_ctx* c, int64_t out[4]) {
+    if (!c || !out) return PGA_EINVAL;
+    memcpy(out, c->align_stats, sizeof c->align_stats);
+    return PGA_OK;
+}
+
+extern "C" int pga_align_pairs(pga_ctx* c, const void* d_tokens, int64_t n_elems, const int64_t* row_begin, const int64_t* row_len, int64_t n_rows,
+                               const int64_t* d_pairs, int64_t n_pairs, const pga_align_opts* o, int64_t* d_distance, int64_t* d_pass, void* stream) {
+    if (!c) return PGA_EINVAL;
+    DevCall d{c, "pga_align_pairs"};
+    // ---- validation: all of it on the host, before anything is allocated or launched ----
+    if (!o || n_elems < 0 || n_rows < 0 || n_pairs < 0 || (n_rows > 0 && (!row_begin || !row_len))) return d.bad("bad arguments");
+    const int eb = o->elem_bytes;
+    if (eb != 1 && eb != 4 && eb != 8) return d.bad("elem_bytes must be 1, 4 or 8, not " + std::to_string(eb));
+    if (o->max_distance < 0 || o->max_distance > 255) return d.bad("max_distance = " + std::to_string(o->max_distance) + " is outside 0 .. 255");
+    if (o->num < 1 || o->den < o->num || o->den > (1 << 20))
+        return d.bad("num / den = " + std::to_string(o->num) + " / " + std::to_string(o->den) + " is outside 1 <= num <= den <= 2^20");
+    if (n_rows > INT32_MAX) return d.bad("more than 2^31 - 1 rows");
+    if (n_pairs > INT32_MAX) return d.bad("more than 2^31 - 1 pairs");
+    bool any_elem = false;
+    for (int64_t g = 0; g < n_rows; g++) {
+        const int64_t b = row_begin[g], n = row_len[g];
+        if (n < 0 || n > ((int64_t)1 << 30)) return d.bad("row " + std::to_string(g) + " has length " + std::to_string(n) + ", outside 0 .. 2^30");
+        if (b < 0 || b > n_elems - n)
+            return d.bad("row " + std::to_string(g) + " is elements " + std::to_string(b) + " .. " + std::to_string(b) + " + " + std::to_string(n) +
+                         ", outside the " + std::to_string(n_elems) + " of the tensor");
+        any_elem |= n > 0;
+    }
+    memset(c->align_stats, 0, sizeof c->align_stats);
+    if (n_pairs == 0) return PGA_OK;
+    if (const int rc = d.destinations({{"d_tokens", d_tokens, eb, any_elem ? d.kRequired : d.kUnread}, {"d_pairs", d_pairs, 8, d.kRequired},
+                                       {"d_distance", d_distance, 8, d.kRequired}, {"d_pass", d_pass, 8, d.kOptional}})) return rc;
+    // ---- the lease: the rows' offsets and lengths, and behind them the counters ----
+    const size_t G = (size_t)n_rows;
+    Staging tab(256);
+    const size_t p_beg = tab.put(row_begin, sizeof(int64_t) * G), p_len = tab.put(row_len, sizeof(int64_t) * G), p_small = tab.take(256);
+    if (const int rc = tab.lease(c)) return rc;
+    memset(tab.pin<char>(p_small), 0, 256);
+    volatile long long* const h_small = tab.pin<volatile long long>(p_small);
+    AlArgs a{};
+    a.tokens = d_tokens; a.begin = tab.dev<const int64_t>(p_beg); a.len = tab.dev<const int64_t>(p_len);
+    a.pairs = d_pairs; a.n_rows = n_rows; a.n_pairs = n_pairs;
+    a.K = o->max_distance; a.num = o->num; a.den = o->den;
+    a.d_distance = d_distance; a.d_pass = d_pass;
+    a.small = tab.dev<unsigned long long>(p_small);
+    // a lane holds R diagonals of the band's 2 K + 1: the least R of 1, 2, 4, 8 with 64 R of them or more
+    const int R = a.K <= 31 ? 1 : a.K <= 63 ? 2 : a.K <= 127 ? 4 : 8;
+    return d.run(tab.L, tab.bytes(), stream, [&](hipStream_t st) {
+        const int64_t per_block = kRowThreads / 64;
+        const dim3 grid((unsigned)std::min<int64_t>((n_pairs + per_block - 1) / per_block, 16384)), block(kRowThreads);
+        auto launch = [&](auto EB) {
+            constexpr int E = decltype(EB)::value;
+            if (R == 1) hipLaunchKernelGGL((k_align_pairs<E, 1>), grid, block, 0, st, a);
+            else if (R == 2) hipLaunchKernelGGL((k_align_pairs<E, 2>), grid, block, 0, st, a);
+            else if (R == 4) hipLaunchKernelGGL((k_align_pairs<E, 4>), grid, block, 0, st, a);
+            else hipLaunchKernelGGL((k_align_pairs<E, 8>), grid, block, 0, st, a);
+        };
+        if (eb == 1) launch(std::integral_constant<int, 1>{});
+        else if (eb == 4) launch(std::integral_constant<int, 4>{});
+        else launch(std::integral_constant<int, 8>{});
+        hipError_t e = hipGetLastError();
+        if (e == hipSuccess) e = hipMemcpyAsync((void*)h_small, a.small, 32, hipMemcpyDeviceToHost, st);
+        return e;
+    }, [&] {
+        c->align_stats[0] = n_pairs; c->align_stats[1] = h_small[0]; c->align_stats[2] = h_small[1]; c->align_stats[3] = h_small[2];
+    });
+}
+
+extern "C" int pga_cluster_edges(pga_ctx* c, const int64_t* d_edges, const int64_t* d_keep, int64_t n_edges, int64_t n, const int64_t* d_weight,
+                                 int64_t* d_cluster, int64_t* d_representative, int64_t* d_size, int64_t capacity, void* stream,
+                                 int64_t* n_clusters, int64_t* n_used) {
+    if (!c) return PGA_EINVAL;
+    DevCall d{c, "pga_cluster_edges"};
+    // ---- validation: all of it on the host, before anything is allocated or launched ----
+    if (!n_clusters || !n_used || n < 0 || n_edges < 0) return d.bad("bad arguments");
+    if (n > INT32_MAX) return d.bad("more than 2^31 - 1 records");
+    if (n_edges > INT32_MAX) return d.bad("more than 2^31 - 1 edges");
+    if (capacity < 0 || ((d_representative || d_size) && capacity < n))
+        return d.bad("capacity = " + std::to_string(capacity) + " is less than the " + std::to_string(n) + " records");
+    if (n == 0) { *n_clusters = 0; *n_used = 0; return PGA_OK; }
+    if (const int rc = d.destinations({{"d_edges", d_edges, 8, n_edges > 0 ? d.kRequired : d.kUnread}, {"d_keep", d_keep, 8, n_edges > 0 ? d.kOptional : d.kUnread},
+                                       {"d_weight", d_weight, 8, d.kOptional}, {"d_cluster", d_cluster, 8, d.kRequired},
+                                       {"d_representative", d_representative, 8, d.kOptional}, {"d_size", d_size, 8, d.kOptional}})) return rc;
+    // ---- the work arrays: the per-record part of pga_cluster_sketches' block; every element that is read was written by this call ----
+    const size_t G = (size_t)n;
+    const int iG = (int)n;
+    size_t tmp_b = 0;
+    hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_b, (int32_t*)nullptr, (int32_t*)nullptr, iG, (hipStream_t)nullptr);
+    Staging work(256);                                           // (only its offsets: the block is the context's own)
+    const size_t p_rw = work.take(8 * G), p_parent = work.take(4 * G), p_root = work.take(4 * G), p_isroot = work.take(4 * G), p_number = work.take(4 * G);
+    const size_t p_cnt = work.take(4 * G), p_rep = work.take(4 * G), p_tmp = work.take(tmp_b + 1);
+    Staging tab(256);
+    const size_t p_small = tab.take(256);
+    if (const int rc = tab.lease(c)) return rc;                  // (one such call at a time per context from here on)
+    if (const int rc = pga_cluster_block(c, "pga_cluster_edges", work.bytes())) return rc;
+    char* const W = c->cluster_dev;
+    memset(tab.pin<char>(p_small), 0, 256);
+    volatile long long* const h_small = tab.pin<volatile long long>(p_small);
+    ClArgs a{};
+    a.weight = d_weight; a.n = n;
+    a.parent = (int32_t*)(W + p_parent); a.root = (int32_t*)(W + p_root); a.isroot = (int32_t*)(W + p_isroot); a.number = (int32_t*)(W + p_number);
+    a.cnt = (int32_t*)(W + p_cnt); a.rw = (unsigned long long*)(W + p_rw); a.rep = (uint32_t*)(W + p_rep);
+    a.small = tab.dev<unsigned long long>(p_small);
+    a.d_cluster = d_cluster; a.d_rep = d_representative; a.d_size = d_size;
+    void* const d_tmp = W + p_tmp;
+    const dim3 block(kRowThreads), per_rec((unsigned)((G + kRowThreads - 1) / kRowThreads));
+    auto launched = [&]() { return hipGetLastError(); };
+    return d.run(tab.L, tab.bytes(), stream, [&](hipStream_t st) {
+        size_t tb = tmp_b;
+        hipError_t e = hipSuccess;
+        hipLaunchKernelGGL(k_edges_reset, per_rec, block, 0, st, a); e = launched();
+        if (e == hipSuccess && n_edges > 0) {
+            const dim3 grid((unsigned)std::min<int64_t>((n_edges + kRowThreads - 1) / kRowThreads, 2048));
+            hipLaunchKernelGGL(k_edges_join, grid, block, 0, st, a, d_edges, d_keep, n_edges);
+            e = launched();
+        }
+        if (e == hipSuccess) { hipLaunchKernelGGL(k_cluster_flatten, per_rec, block, 0, st, a); e = launched(); }
+        if (e == hipSuccess) e = hipcub::DeviceScan::ExclusiveSum(d_tmp, tb, (const int32_t*)a.isroot, a.number, iG, st);
+        if (e == hipSuccess) { hipLaunchKernelGGL(k_cluster_number, per_rec, block, 0, st, a); e = launched(); }
+        if (e == hipSuccess && d_representative) { hipLaunchKernelGGL(k_cluster_representative, per_rec, block, 0, st, a); e = launched(); }
+        if (e == hipSuccess && (d_representative || d_size)) { hipLaunchKernelGGL(k_cluster_emit, per_rec, block, 0, st, a); e = launched(); }
+        if (e == hipSuccess) e = hipMemcpyAsync((void*)h_small, a.small, 32, hipMemcpyDeviceToHost, st);
+        return e;
+    }, [&] {
+        *n_used = h_small[0]; *n_clusters = h_small[1];
     });
 }
 

@@ -2169,6 +2169,30 @@ cdef class GeneFinder:
         return self._find_tensor_batch("find_clusters_batch", sequences, clusters, out, stream, translate, training_infos, regions, circular, sets,
                                        trim_terminal_repeats)
 
+    def find_verified_clusters_batch(self, object sequences, object verified, *, object out=None, object stream=None,
+                                     bint translate=False, object training_infos=None, object regions=None, object circular=None,
+                                     object sets=None, object trim_terminal_repeats=None):
+        """`find_genes_batch`, and the genes whose predicted proteins are near-copies of each other clustered on the device with
+        every edge checked against the proteins themselves: returns `(genes, device_verified_clusters)`, the list of `Genes` that
+        `find_genes_batch` returns for the same arguments and a `DeviceVerifiedClusters`.
+
+        `verified`: a `VerifiedClusters` -- the `ProteinClusters` that proposes pairs from the sketches, the `ProteinAlignments`
+        that decides them and the `ProteinTokens` the proteins are compared as.  Exactly `find_proteins_batch` with
+        `verified.tokens`, `find_clusters_batch` with `verified.clusters`, `device_proteins.align(device_clusters.edges,
+        verified.alignments)` and `device_clusters.relink(keep=passed)`, all in one device call on the resident batch: `cluster[g]`,
+        `representatives[u]` and `sizes[u]` are the components under the edges that passed, numbered as `find_clusters_batch`
+        numbers them; `edge_distance` and `edge_passed` say what became of every edge of `candidates.edges`; `candidates` is the
+        `DeviceClusters` of the sketch stage and `proteins` the `DeviceProteins`.  `out`: a `(cluster, representatives, sizes)`
+        triple of int64 device tensors to write (anything with `__cuda_array_interface__`; `None` for the last two), omitted:
+        torch tensors allocated under torch's current stream; the tokens, sketches and edge tensors are always new torch tensors.
+        `stream`: the stream that last used `out`.  Every option of `find_genes_batch` applies and `sequences` may be a
+        `DeviceSequences`.  The request is a device call of its own: one set of tensors per request, so a request that
+        `training_infos` would split into several device calls is a `ValueError`."""
+        if not isinstance(verified, _cabi.VerifiedClusters):
+            raise TypeError("`verified` must be a VerifiedClusters, not %r" % type(verified).__name__)
+        return self._find_tensor_batch("find_verified_clusters_batch", sequences, verified, out, stream, translate, training_infos, regions,
+                                       circular, sets, trim_terminal_repeats)
+
     def find_starts_batch(self, object sequences, object starts, *, object out=None, object stream=None, bint translate=False,
                           object training_infos=None, object regions=None, object circular=None, object sets=None,
                           object trim_terminal_repeats=None):
@@ -2196,8 +2220,8 @@ cdef class GeneFinder:
 
     cdef tuple _find_tensor_batch(self, str method, object sequences, object spec, object out, object stream, bint translate,
                                   object training_infos, object regions, object circular, object sets, object trim_terminal_repeats):
-        """What the eight `find_*_batch` methods with a device-tensor output share (proteins, labels, windows, counts, groups,
-        sketches, clusters, starts): (the `Genes` of `find_genes_batch`, what the rule `spec` wrote on the device)."""
+        """What the nine `find_*_batch` methods with a device-tensor output share (proteins, labels, windows, counts, groups,
+        sketches, clusters, verified clusters, starts): (the `Genes` of `find_genes_batch`, what the rule `spec` wrote on the device)."""
         cdef dict tok = {"spec": spec, "out": out, "stream": stream, "result": None, "method": method}
         cdef list circ, tr_search
         cdef object dev, set_ids, tr_params
@@ -2216,7 +2240,7 @@ cdef class GeneFinder:
         return genes, tok["result"]
 
     cdef tuple _batch_options(self, object sequences, object training_infos, object circular, object sets, object trim_terminal_repeats):
-        """The options of `find_genes_batch` and of the eight `find_*_batch` methods with a device-tensor output, checked against each
+        """The options of `find_genes_batch` and of the nine `find_*_batch` methods with a device-tensor output, checked against each
         other and against the number of sequences: (the DeviceSequences or None, the sequences, circular flags, set ids,
         terminal-repeat search and its parameters)."""
         cdef list circ = None
@@ -2699,8 +2723,8 @@ cdef class GeneFinder:
         return out
 
     cdef int _device_tensor(self, pga_ctx* ctx, pga_batch* batch, pga_result* res, object per_contig, dict tok) except -1:
-        """What the request's rule makes of the genes of `res` -- any of the eight rules of `_cabi` (protein tokens, base labels, gene
-        windows, k-mer counts, protein groups, protein sketches, protein clusters, start candidates) -- into the request's device tensors while the batch
+        """What the request's rule makes of the genes of `res` -- any of the nine rules of `_cabi` (protein tokens, base labels, gene
+        windows, k-mer counts, protein groups, protein sketches, protein clusters, verified clusters, start candidates) -- into the request's device tensors while the batch
         the finder called is resident (through the rule's `write`, the raw layer's marshalling); `per_contig`: what the rule needs of
         every contig, tables or lengths (`spec.per_contig`).  Leaves the rule's `Device*` result in `tok`."""
         genes = np.zeros(0, _cabi.GENE_DTYPE)
