@@ -53,8 +53,7 @@ extern "C" int pga_create(int device, pga_ctx** out) {
         // gene records (round 6: those records now sit in pinned memory).  Once per process; PGA_MALLOPT=0 leaves the allocator alone.
         static std::once_flag once;
         std::call_once(once, [] {
-            const char* e = getenv("PGA_MALLOPT");
-            if (e && atoi(e) == 0) return;
+            if (!pga_knobs::process_knobs().mallopt) return;
             mallopt(M_MMAP_THRESHOLD, 32 << 20);
             mallopt(M_TRIM_THRESHOLD, 512 << 20);
         });
@@ -227,6 +226,7 @@ static int score_connections_impl(pga_ctx* c, int32_t n, const int32_t* ndx, con
                                   const int32_t* star_ptr, double st_wt, int final, const double* gc_score, const double* bias,
                                   double* score, int32_t* traceb, int8_t* ov_mark, int32_t* max_index, double* kernel_ms) {
     if (n < 0) return fail(c, PGA_EINVAL, "pga_score_connections: negative node count");
+    const Knobs kn = read_knobs();
     if (max_index) *max_index = -1;
     if (kernel_ms) *kernel_ms = 0.0;
     if (n == 0) return PGA_OK;
@@ -241,8 +241,8 @@ static int score_connections_impl(pga_ctx* c, int32_t n, const int32_t* ndx, con
     ChainDesc ch{0, 0, n, 0, 0, 1};
     // a long chain is cut into segments walked side by side (dp.hip "segmented chains")
     DpSegPlan seg_plan;
-    const bool use_wave = final && pga_dp_use_wave(1);          // one chain: only when PGA_DP_KERNEL=wave asks for it
-    const bool segmented = final && !use_wave && pga_dp_plan(&ch, 1, n, seg_plan);
+    const bool use_wave = final && pga_dp_use_wave(kn, 1);          // one chain: only when PGA_DP_KERNEL=wave asks for it
+    const bool segmented = final && !use_wave && pga_dp_plan(kn, &ch, 1, n, seg_plan);
     const size_t N = (size_t)n + (size_t)seg_plan.extra, NS = 1 + seg_plan.segs.size();
     HIP_TRY(c, db.alloc(&nd.ndx, N)); HIP_TRY(c, db.alloc(&nd.stop_val, N)); HIP_TRY(c, db.alloc(&nd.type, N));
     HIP_TRY(c, db.alloc(&nd.strand, N)); HIP_TRY(c, db.alloc(&nd.cscore, N)); HIP_TRY(c, db.alloc(&nd.sscore, N));
@@ -253,7 +253,7 @@ static int score_connections_impl(pga_ctx* c, int32_t n, const int32_t* ndx, con
     HIP_TRY(c, db.alloc(&buf.A, N)); HIP_TRY(c, db.alloc(&buf.V[0], N)); HIP_TRY(c, db.alloc(&buf.V[1], N)); HIP_TRY(c, db.alloc(&buf.V[2], N));
     HIP_TRY(c, db.alloc(&buf.hv, N)); HIP_TRY(c, db.alloc(&buf.hi, N));
     buf.prof = nullptr;
-    if (getenv("PGA_DP_PROFILE")) { HIP_TRY(c, db.alloc(&buf.prof, 16)); HIP_TRY(c, hipMemsetAsync(buf.prof, 0, 128, c->stream)); }
+    if (kn.dp_profile) { HIP_TRY(c, db.alloc(&buf.prof, 16)); HIP_TRY(c, hipMemsetAsync(buf.prof, 0, 128, c->stream)); }
     HIP_TRY(c, db.alloc(&d_chain, 1)); HIP_TRY(c, db.alloc(&d_mc, 1));
     hipStream_t st = c->stream;
 #define UP(dst, srcp, bytes) HIP_TRY(c, hipMemcpyAsync(dst, srcp, bytes, hipMemcpyHostToDevice, st))
@@ -288,13 +288,13 @@ static int score_connections_impl(pga_ctx* c, int32_t n, const int32_t* ndx, con
         HIP_TRY(c, db.alloc(&d_cbase, 2));
         HIP_TRY(c, hipMemcpyAsync(d_cbase, h_cbase, sizeof h_cbase, hipMemcpyHostToDevice, st));
         wg.g[0].ndx = nd.ndx; wg.g[0].stop_val = nd.stop_val;
-        bool sched = pga_dpw_use_sched();
+        bool sched = kn.dpw_sched;
         const int nbat = (n + 63) >> 6;
         if (sched) {
             // the schedule's buffers exist before the topology kernel runs: it is that kernel which clears scur (the overflow count)
             HIP_TRY(c, db.alloc(&wg.g[0].shdr, (size_t)nbat + 1)); HIP_TRY(c, db.alloc(&wg.g[0].sent, 2 * (size_t)DPW_SCHED_STRIDE * ((size_t)nbat + 1) + 16)); HIP_TRY(c, db.alloc(&wg.g[0].scur, 16));
         }
-        pga_launch_dpw_topo(wg.g[0], nd.type, nd.strand, d_cbase, 1, n, st, n);
+        pga_launch_dpw_topo(kn, wg.g[0], nd.type, nd.strand, d_cbase, 1, n, st, n);
         pga_launch_dpw_chain(d_chain, 1, 0, n, na, wg.g[0], d_mc, wb, st);
         if (sched) {
             // the step schedule of this one contig (the chain's sched_b0 is 0); a buffer it does not fit sends the launch to k_dpw_dyn
@@ -303,7 +303,7 @@ static int score_connections_impl(pga_ctx* c, int32_t n, const int32_t* ndx, con
             uint32_t h_cur[2] = {0, 0};
             HIP_TRY(c, db.alloc(&d_bbase, 2));
             HIP_TRY(c, hipMemcpyAsync(d_bbase, h_bbase, sizeof h_bbase, hipMemcpyHostToDevice, st));
-            pga_launch_dpw_sched(wg.g[0], d_cbase, d_bbase, 1, nbat, st);
+            pga_launch_dpw_sched(kn, wg.g[0], d_cbase, d_bbase, 1, nbat, st);
             HIP_TRY(c, hipMemcpyAsync(h_cur, wg.g[0].scur, sizeof h_cur, hipMemcpyDeviceToHost, st));
             HIP_TRY(c, hipStreamSynchronize(st));
             if (h_cur[1] != 0) sched = false;
@@ -315,7 +315,7 @@ static int score_connections_impl(pga_ctx* c, int32_t n, const int32_t* ndx, con
     } else {
         pga_launch_dp_prepare(d_chain, 1, 0, n, na, d_mc, buf, st, final);
         HIP_TRY(c, hipEventRecord(c->ev0, st));
-        pga_launch_dp(d_chain, 1, d_mc, buf, final, st, segmented ? &seg_dev : nullptr);
+        pga_launch_dp(kn, d_chain, 1, d_mc, buf, final, st, segmented ? &seg_dev : nullptr);
         HIP_TRY(c, hipEventRecord(c->ev1, st));
     }
     HIP_TRY(c, hipGetLastError());

@@ -275,7 +275,7 @@ k_circ_splice(const CircSplice* __restrict__ sp, const int32_t* __restrict__ whi
 }
 
 // ---- the call ----------------------------------------------------------------------------------------------------------------------
-static int find_circular(pga_ctx* c, const pga_batch* batch, const pga_params* pp, pga_result** out, const int32_t* model_of_contig) {
+static int find_circular(const Knobs& kn, pga_ctx* c, const pga_batch* batch, const pga_params* pp, pga_result** out, const int32_t* model_of_contig) {
     if (out) *out = nullptr;
     if (!pp || !out) { c->err = "pga_find_genes: bad arguments"; return PGA_EINVAL; }
     const int NC = batch->n;
@@ -287,7 +287,7 @@ static int find_circular(pga_ctx* c, const pga_batch* batch, const pga_params* p
     // pass 1: the ordinary call; the records stay where they are
     GeneKeep k1{"d_genes_pass1"};
     pga_result* r1 = nullptr;
-    int rc = find_impl(c, batch, pp, 0, 0, &r1, model_of_contig, nullptr, nullptr, &k1);
+    int rc = find_impl(kn, c, batch, pp, 0, 0, &r1, model_of_contig, nullptr, nullptr, &k1);
     if (rc) return rc;
     ResultOwner* R1 = reinterpret_cast<ResultOwner*>(r1);
     struct Guard { ResultOwner* r; ~Guard() { delete r; } } guard1{R1}, guard2{nullptr};
@@ -377,7 +377,7 @@ static int find_circular(pga_ctx* c, const pga_batch* batch, const pga_params* p
         P2.closed = 1;
         if (model_of_contig) for (int j = 0; j < NR; j++) moc2.push_back(model_of_contig[circ[j]]);
         pga_result* r2 = nullptr;
-        rc = find_impl(c, b2, &P2, 0, 0, &r2, model_of_contig ? moc2.data() : nullptr, nullptr, nullptr, &k2);
+        rc = find_impl(kn, c, b2, &P2, 0, 0, &r2, model_of_contig ? moc2.data() : nullptr, nullptr, nullptr, &k2);
         if (rc) return rc;
         R2 = reinterpret_cast<ResultOwner*>(r2);
         guard2.r = R2;
@@ -406,7 +406,7 @@ static int find_circular(pga_ctx* c, const pga_batch* batch, const pga_params* p
             ngenes += cr.n_genes;
         }
     }
-    pga_gene* const genes_out = R1->gene_records((size_t)ngenes);
+    pga_gene* const genes_out = R1->gene_records((size_t)ngenes, kn.pageable_results);
     if (ngenes > 0) {
         DEVBUF(d_final, pga_gene, "circ_genes", ngenes + 1);
         DEVBUF(d_sp, CircSplice, "circ_splice", NC + 1);

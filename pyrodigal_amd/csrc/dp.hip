@@ -1301,13 +1301,8 @@ k_seg_leaves(const ChainDesc* __restrict__ chains, const int32_t* __restrict__ b
 // (parents in earlier batches come from an LDS ring, parents in the same batch are met one after the other through
 // v_readlane), and every other node is scored afterwards, one parallel pass per height class (k_seg_leaves).
 // A later round restarts at the first node the verification rejected: everything before it is already exact.
-#define PGA_SEG_HEIGHT 4          // default; PGA_DP_SEG_HEIGHT = 2 .. 24 (seg_height()): a higher bar means a shorter spine and more leaf passes
-                                  // (measured on configs 2 and 5: 8 changes nothing, 12 and 16 are 3-8 % slower -- the spine is mostly the path itself)
-static int seg_height() {
-    static int h = 0;
-    if (!h) { const char* e = getenv("PGA_DP_SEG_HEIGHT"); h = e ? atoi(e) : PGA_SEG_HEIGHT; if (h < 2 || h > 24) h = PGA_SEG_HEIGHT; }
-    return h;
-}
+// PGA_SEG_HEIGHT: Knobs::dp_seg_height, 4 by default, read once per process: a higher bar means a shorter spine and more leaf passes
+// (measured on configs 2 and 5: 8 changes nothing, 12 and 16 are 3-8 % slower -- the spine is mostly the path itself)
 #define PGA_RS_RING 4096
 
 __device__ __forceinline__ int64_t seg_tile(const ChainDesc& cd, const int chain, const int i) { return (cd.off >> 6) + chain + (i >> 6); }
@@ -1644,21 +1639,16 @@ void pga_launch_dp_prepare(const ChainDesc* d_chains, int n_chains, int64_t node
                        d_chains, n_chains, node_begin, total_nodes, nodes, d_models, buf.src, buf.tgt, final);
 }
 
-bool pga_dp_use_wave(int n_chains) {
-    const char* kern = getenv("PGA_DP_KERNEL");
-    if (kern && *kern) return strcmp(kern, "wave") == 0;
+bool pga_dp_use_wave(const Knobs& kn, int n_chains) {
+    if (kn.dp_kernel != Knobs::by_shape) return kn.dp_kernel == Knobs::wave;
     return n_chains >= 2048;
 }
-static int env_int(const char* name, int dflt) {
-    const char* e = getenv(name);
-    return (e && *e) ? atoi(e) : dflt;
-}
 
-bool pga_dp_plan(const ChainDesc* h, int n_chains, int64_t tot_nodes, DpSegPlan& plan, const bool wave_walk) {
+bool pga_dp_plan(const Knobs& kn, const ChainDesc* h, int n_chains, int64_t tot_nodes, DpSegPlan& plan, const bool wave_walk) {
     plan = DpSegPlan();
-    if (n_chains <= 0 || n_chains >= 2048 || getenv("PGA_DP_KERNEL") || env_int("PGA_DP_SEG", 1) == 0) return false;
-    const int min_chain = std::max(256, env_int("PGA_DP_SEG_MIN", 16384));
-    const int warm = std::max(64, env_int("PGA_DP_SEG_WARM", 4096));      // 2048 left 8 (config 5) / 938 (config 2) nodes for a second round; 4096 none
+    if (n_chains <= 0 || n_chains >= 2048 || kn.dp_kernel_set || !kn.dp_seg) return false;
+    const int min_chain = kn.dp_seg_min;
+    const int warm = kn.dp_seg_warm;      // 2048 left 8 (config 5) / 938 (config 2) nodes for a second round; 4096 none
     int64_t cand = 0;
     for (int c = 0; c < n_chains; c++) if (h[c].n >= min_chain) cand += h[c].n;
     if (cand == 0) return false;
@@ -1676,13 +1666,13 @@ bool pga_dp_plan(const ChainDesc* h, int n_chains, int64_t tot_nodes, DpSegPlan&
         }
         return k;
     };
-    int64_t len = env_int("PGA_DP_SEG_LEN", 0);
-    if (len <= 0) {
+    int64_t len = kn.dp_seg_len;
+    if (!kn.dp_seg_len_set) {
         // what the short chains leave of the compute units, but never less than a quarter of them: a batch of one genome and
         // hundreds of small contigs still cuts the genome (its segments then share the chip with the small chains' workgroups)
         // (wave_walk: a wavefront per segment, four to a SIMD -- 4096 at once (a wavefront takes 18.5 us per 64-node batch with two on a SIMD, 26 us with six: measured on config 5, 2048 / 4096 / 6144 segments: 11.8 / 11.4 / 11.6 ms of connection scoring), however long the chains that are not cut: those go to the chain
         //  kernel in a launch of their own)
-        const int64_t slots = wave_walk ? std::max(64, env_int("PGA_DP_SEG_WSLOTS", 4096)) : std::max(64, env_int("PGA_DP_SEG_SLOTS", 256) - 4);
+        const int64_t slots = wave_walk ? kn.dp_seg_wslots : kn.dp_seg_slots;
         const int64_t budget = wave_walk ? slots : std::max<int64_t>(slots / 4, slots - n_short);
         len = std::max<int64_t>(512, ((cand + budget - 1) / budget + 63) & ~63ll);
         for (int it = 0; count_segs(len) > budget && len < cand; it++) len += it < 256 ? 64 : std::max<int64_t>(64, (len / 8) & ~63ll);
@@ -1769,6 +1759,7 @@ hipError_t pga_dp_seg_bind(const DpSegPlan& plan, int n_chains, int64_t tot_node
 // C-ABI view of the plan (include/pyrodigal_amd.h): pure host arithmetic, usable without a device
 extern "C" int pga_dp_plan_summary(int32_t n_chains, const int32_t* nodes_per_chain, int64_t out[4]) {
     if (n_chains < 0 || (n_chains > 0 && !nodes_per_chain) || !out) return PGA_EINVAL;
+    const Knobs kn = read_knobs();
     std::vector<ChainDesc> h((size_t)n_chains);
     int64_t tot = 0;
     for (int c = 0; c < n_chains; c++) {
@@ -1777,7 +1768,7 @@ extern "C" int pga_dp_plan_summary(int32_t n_chains, const int32_t* nodes_per_ch
         tot += nodes_per_chain[c];
     }
     DpSegPlan plan;
-    pga_dp_plan(h.data(), n_chains, tot, plan);
+    pga_dp_plan(kn, h.data(), n_chains, tot, plan);
     out[0] = (int64_t)plan.big.size(); out[1] = (int64_t)plan.segs.size(); out[2] = plan.max_seg_nodes; out[3] = plan.extra;
     // every node of a cut chain belongs to exactly one segment, segments are in order and start their walk at most `warm` early
     for (size_t k = 0; k < plan.segs.size(); k++) {
@@ -1811,7 +1802,7 @@ static void launch_dp_segmented(const ChainDesc* d_chains, int n_chains, const M
         const dim3 per_node(blocks(sg.max_big_n), sg.n_big);
         hipMemsetAsync(sg.hb, 0, sizeof(uint32_t) * (size_t)sg.n_nodes, st);
         hipLaunchKernelGGL(k_seg_weights, per_node, blk, 0, st, d_chains, sg.big, gate, buf.src, buf.tgt, d_models, buf, sg.ctb, sg.cw, sg.hb);
-        const int H = seg_height();
+        const int H = pga_knobs::process_knobs().dp_seg_height;
         for (int k = 2; k <= H; k++)
             hipLaunchKernelGGL(k_seg_height, per_node, blk, 0, st, d_chains, sg.big, gate, (const int32_t*)buf.traceb, sg.hb, k);
         hipLaunchKernelGGL(k_spine_count, per_node, blk, 0, st, d_chains, sg.big, gate, (const uint32_t*)sg.hb, sg.tmask, H);
@@ -1843,7 +1834,7 @@ static void launch_dp_segmented(const ChainDesc* d_chains, int n_chains, const M
                        (const int32_t*)(sg.flags + (size_t)(PGA_SEG_ROUNDS - 1) * n_chains), (const int32_t*)nullptr);
 }
 
-void pga_launch_dp(const ChainDesc* d_chains, int n_chains, const ModelConst* d_models, DpBuffers buf,
+void pga_launch_dp(const Knobs& kn, const ChainDesc* d_chains, int n_chains, const ModelConst* d_models, DpBuffers buf,
                    int final, hipStream_t st, const DpSegDev* seg) {
     if (n_chains <= 0) return;
     if (final && seg != nullptr && seg->n_segs > 0) { launch_dp_segmented(d_chains, n_chains, d_models, buf, st, *seg); return; }
@@ -1854,12 +1845,11 @@ void pga_launch_dp(const ChainDesc* d_chains, int n_chains, const ModelConst* d_
     }
 #define PGA_DP_LAUNCH(WAVES) hipLaunchKernelGGL(k_dp_chain<WAVES>, dim3(n_chains), dim3(64 * WAVES), 0, st, d_chains, buf.src, buf.tgt, \
         d_models, buf.score, buf.traceb, buf.tbn, buf.ov_mark, buf.max_index, buf.max_score, buf.ipath)
-    const char* kern = getenv("PGA_DP_KERNEL");
-    if (!kern || strcmp(kern, "scan") != 0) {
+    if (kn.dp_kernel != Knobs::scan) {
         // many chains: one wave each fills the chip; few chains: latency-bound, 3 cooperating waves per chain
         bool mw = n_chains < 2048;
-        if (kern && strcmp(kern, "tree1") == 0) mw = false;
-        if (kern && strcmp(kern, "tree3") == 0) mw = true;
+        if (kn.dp_kernel == Knobs::tree1) mw = false;
+        if (kn.dp_kernel == Knobs::tree3) mw = true;
         if (mw) hipLaunchKernelGGL(k_dp_tree_mw, dim3(n_chains), dim3(64 * PGA_MW_WAVES), 0, st, d_chains, buf.src, buf.tgt, d_models, buf,
                                    (const int32_t*)nullptr, (const int32_t*)nullptr);
         else hipLaunchKernelGGL(k_dp_tree, dim3(n_chains), dim3(64), 0, st, d_chains, buf.src, buf.tgt, d_models, buf);
@@ -1868,7 +1858,7 @@ void pga_launch_dp(const ChainDesc* d_chains, int n_chains, const ModelConst* d_
     // PGA_DP_KERNEL=scan: the window-scanning kernels (kept as an independent cross-check of the tree kernel)
     // few chains: latency-bound, give each chain a whole workgroup; many chains: one wave each fills the chip
     int waves = n_chains >= 4096 ? 1 : (n_chains >= 1024 ? 4 : 16);
-    if (const char* e = getenv("PGA_DP_WAVES")) { const int v = atoi(e); if (v == 1 || v == 4 || v == 16) waves = v; }   // tuning / tests
+    if (kn.dp_waves) waves = kn.dp_waves;   // tuning / tests
     if (waves == 1) PGA_DP_LAUNCH(1);
     else if (waves == 4) PGA_DP_LAUNCH(4);
     else PGA_DP_LAUNCH(16);

@@ -1275,12 +1275,12 @@ k_dp_wave(const ChainDesc* __restrict__ chains, DpwGroupPtrs groups, const doubl
 
 }  // namespace
 
-void pga_launch_dpw_topo(const DpwTopoArrays& ta, const uint8_t* type, const int8_t* strand, const int32_t* d_cbase, int n_contigs, int n_nodes,
+void pga_launch_dpw_topo(const Knobs& kn, const DpwTopoArrays& ta, const uint8_t* type, const int8_t* strand, const int32_t* d_cbase, int n_contigs, int n_nodes,
                          hipStream_t st, int max_contig_nodes) {
     if (n_nodes <= 0) return;
-    const int walk = getenv("PGA_DPW_TOPO_WALK") ? atoi(getenv("PGA_DPW_TOPO_WALK")) : 0;
+    const bool walk = kn.dpw_topo_walk;
     // contigs that fit: a workgroup per contig on LDS copies of its node arrays (PGA_DPW_TOPO_LDS=0: the per-node kernel on global memory)
-    const bool lds = max_contig_nodes > 0 && max_contig_nodes <= TOPO_LDS_NODES && !walk && !(getenv("PGA_DPW_TOPO_LDS") && atoi(getenv("PGA_DPW_TOPO_LDS")) == 0);
+    const bool lds = max_contig_nodes > 0 && max_contig_nodes <= TOPO_LDS_NODES && !walk && kn.dpw_topo_lds;
     if (lds) {
         // (up to 12 * TOPO_LDS_NODES + 32 bytes of dynamic LDS next to 2.3 KB of static: past the 64 KB a kernel may use unasked)
         static std::atomic<bool> attr_set[64];
@@ -1313,24 +1313,17 @@ void pga_launch_dp_wave_sub(const ChainDesc* d_subs, int n_subs, const DpwGroupP
                        d_models, buf, wb.sfxv, wb.sfxi, d_slot);
 }
 
-bool pga_dpw_use_sched() {
-    const char* e = getenv("PGA_DPW_SCHED");        // 0: every launch by k_dpw_dyn (cross-check)
-    return e ? (atoi(e) != 0) : true;
-}
-
-void pga_launch_dpw_sched(const DpwTopoArrays& ta, const int32_t* d_cbase, const int32_t* d_bbase, int n_contigs, int max_batches, hipStream_t st) {
+void pga_launch_dpw_sched(const Knobs& kn, const DpwTopoArrays& ta, const int32_t* d_cbase, const int32_t* d_bbase, int n_contigs, int max_batches, hipStream_t st) {
     // (ta.scur is cleared by the topology kernel, which always runs in front of this one: the caller sets ta.scur before that launch)
     if (n_contigs <= 0 || max_batches <= 0) return;
-    const char* fm = getenv("PGA_DPW_SCHED_MISS");
-    hipLaunchKernelGGL(k_dpw_sched, dim3((unsigned)n_contigs, (unsigned)((max_batches + 15) / 16)), dim3(256), 0, st, d_cbase, d_bbase, ta, (fm && atoi(fm)) ? 1 : 0);
+    hipLaunchKernelGGL(k_dpw_sched, dim3((unsigned)n_contigs, (unsigned)((max_batches + 15) / 16)), dim3(256), 0, st, d_cbase, d_bbase, ta, kn.dpw_sched_miss ? 1 : 0);
 }
 
 void pga_launch_dp_wave(const ChainDesc* d_chains, int n_chains, const DpwGroupPtrs& groups, const ModelConst* d_models, DpBuffers buf,
                         const DpwBuffers& wb, hipStream_t st, const int32_t* d_order, int n_blocks, bool scheduled) {
     if (n_chains <= 0) return;
     if (n_blocks <= 0 || d_order == nullptr) n_blocks = n_chains;
-    static int occ = 0;
-    if (!occ) { const char* e = getenv("PGA_DPW_OCC"); occ = e ? atoi(e) : 6; if (occ < 4 || occ > 6) occ = 6; }
+    const int occ = pga_knobs::process_knobs().dpw_occ;
 #define DPW_LAUNCH(K) hipLaunchKernelGGL(K, dim3((unsigned)n_blocks), dim3(64), 0, st, d_chains, groups, (const double*)wb.cs, (const DpwExt*)wb.ext, \
                                          d_models, buf, wb.sfxv, wb.sfxi, d_order)
     if (scheduled) { if (occ == 5) DPW_LAUNCH(k_dp_wave<5>); else if (occ == 6) DPW_LAUNCH(k_dp_wave<6>); else DPW_LAUNCH(k_dp_wave<4>); }

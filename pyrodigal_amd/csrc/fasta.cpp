@@ -32,6 +32,7 @@
 #include <vector>
 
 #include "../../include/pyrodigal_amd.h"
+#include "knobs.h"
 
 namespace {
 
@@ -336,6 +337,7 @@ static const char* compression_of(const unsigned char* m, size_t n) {
 extern "C" int pga_fasta_open(const char* path, pga_fasta** out) {
     if (out) *out = nullptr;
     if (!path || !out) return PGA_EINVAL;
+    const Knobs kn = read_knobs();
     pga_fasta* f = new (std::nothrow) pga_fasta();
     if (!f) return PGA_ENOMEM;
     const int fd = open(path, O_RDONLY);
@@ -351,14 +353,14 @@ extern "C" int pga_fasta_open(const char* path, pga_fasta** out) {
         return PGA_EINVAL;
     }
     const bool gz = got >= 2 && magic[0] == 0x1f && magic[1] == 0x8b;
-    if (!gz && regular && sb.st_size > 0 && !getenv("PGA_FASTA_NO_MMAP")) {
+    if (!gz && regular && sb.st_size > 0 && !kn.fasta_no_mmap) {
         void* m = mmap(nullptr, (size_t)sb.st_size, PROT_READ, MAP_PRIVATE, fd, 0);
         if (m != MAP_FAILED) {
             (void)madvise(m, (size_t)sb.st_size, MADV_SEQUENTIAL);
             f->map = (const char*)m; f->map_len = (size_t)sb.st_size; f->fd = fd;
             const unsigned hw = std::thread::hardware_concurrency();
             f->threads = (int)std::max(1u, std::min(16u, hw / 4));
-            if (const char* e = getenv("PGA_FASTA_THREADS")) f->threads = std::max(1, atoi(e));
+            if (kn.fasta_threads) f->threads = kn.fasta_threads;
             *out = f;
             return PGA_OK;
         }

@@ -118,7 +118,7 @@ namespace {
 
 struct StageTimer {
     bool on; std::chrono::steady_clock::time_point t0, tbegin; const char* names[32]; double ms[32]; int n = 0;
-    StageTimer() : on(getenv("PGA_TIMING") != nullptr), t0(std::chrono::steady_clock::now()), tbegin(t0) {}
+    explicit StageTimer(const bool on_) : on(on_), t0(std::chrono::steady_clock::now()), tbegin(t0) {}
     void mark(const char* name) {
         if (!on || n >= 32) return;
         auto t1 = std::chrono::steady_clock::now();
@@ -143,7 +143,7 @@ static std::mutex g_cache_mu;
 static std::vector<CachedBlock> g_cache[2];          // 0: device, 1: pinned
 static size_t g_cached[2] = {0, 0};
 static size_t cache_limit(int kind) {
-    static const size_t gb = [] { const char* e = getenv("PGA_CACHE_GB"); return e ? (size_t)std::max(0, atoi(e)) : (size_t)16; }();
+    const size_t gb = (size_t)pga_knobs::process_knobs().cache_gb;
     return kind == 0 ? gb << 30 : std::min<size_t>(gb << 30, (size_t)2 << 30);
 }
 static void* cache_take(int kind, int dev, size_t want, size_t* cap, size_t roomy = 2) {
@@ -1014,9 +1014,9 @@ struct ResultOwner {
         if (pin_genes != nullptr) cache_put_result(pin_genes, pin_cap);
     }
     // room for n gene records; pinned when the result is large enough for it to matter
-    pga_gene* gene_records(const size_t n) {
+    pga_gene* gene_records(const size_t n, const bool pageable /* Knobs::pageable_results */) {
         const size_t bytes = n * sizeof(pga_gene);
-        if (bytes < ((size_t)256 << 10) || getenv("PGA_PAGEABLE_RESULTS")) { genes.resize(n); return genes.data(); }
+        if (bytes < ((size_t)256 << 10) || pageable) { genes.resize(n); return genes.data(); }
         size_t cap = 0;
         void* p = cache_take(1, -1, bytes, &cap, 8);         // (a block up to eight times the size will do: results vary, pinned allocations cost milliseconds)
         if (p == nullptr) {
@@ -1070,7 +1070,7 @@ void fill_model_score_const(ModelScoreConst* m, const pga_training* t) {   // re
 
 void pga_finder_release(pga_ctx* c) {
     if (!c->finder) return;
-    if (getenv("PGA_PRINT_BUFFERS")) {
+    if (read_knobs().print_buffers) {
         // diagnostics: what this context held on the device, largest first
         std::vector<std::pair<size_t, std::string>> v; size_t tot = 0;
         for (auto& kv : c->finder->dev) if (kv.second.p) { v.push_back({kv.second.cap, kv.first}); tot += kv.second.cap; }
@@ -1409,7 +1409,7 @@ extern "C" int pga_batch_create(pga_ctx* c, int32_t n_contigs, const char* const
             // would idle until the first one is complete.  In turn, the first batch is on the device after one eighth of that time and
             // the uploads of the others run under its kernels.  (PGA_UPLOAD_TURNS=0: no turns.)
             static std::mutex upload_turns[64];        // one per device: only contexts that share a link take turns
-            static const bool turns = !(getenv("PGA_UPLOAD_TURNS") && atoi(getenv("PGA_UPLOAD_TURNS")) == 0);
+            const bool turns = pga_knobs::process_knobs().upload_turns;
             std::unique_lock<std::mutex> turn(upload_turns[c->device & 63], std::defer_lock);
             if (turns && total >= (8 << 20)) turn.lock();
             if (threads == 1) work(); else c->finder->up_pool.run(work, threads);
@@ -1568,6 +1568,7 @@ struct GroupTiles { int32_t* count; int32_t* off; int32_t* scount; int32_t* soff
 // what only one phase needs is a local of that phase.  The vectors that uploads on the stream read live here, so they outlive it.
 struct FindCall : pga_plan::ChainPlan, pga_plan::RescorePlan, pga_plan::GatherPlan<WinDesc> {
     // ---- inputs and mode flags (check_call)
+    Knobs kn{};             // the run-time knobs as the entry point read them: one reading for every phase
     pga_ctx* c = nullptr; FinderState* f = nullptr; hipStream_t st = nullptr;
     const pga_batch* batch = nullptr; pga_params P{};
     int stage = 0, tt_override = 0;
@@ -1621,6 +1622,14 @@ struct FindCall : pga_plan::ChainPlan, pga_plan::RescorePlan, pga_plan::GatherPl
         const size_t at = (size_t)g * (batch->n_tiles + 1);
         return GroupTiles{d_tile.count + at, d_tile.off + at, d_tile.scount + at, d_tile.soff + at};
     }
+    // what the three scoring launchers share for `n_chains` chains of group g (pipeline.h)
+    ScoreGroup score_group(const int g, const ChainDesc* d_first, const int n_chains, const int64_t node_begin, const int64_t n_nodes, const int2* d_contig_chains) const {
+        ScoreGroup s;
+        s.d_chains = d_first; s.n_chains = n_chains; s.node_begin = node_begin; s.total = n_nodes;
+        s.d_all_chains = d_chains; s.d_contig_chains = d_contig_chains; s.d_node_contig_base = d_cb(g); s.n_contigs = NC; s.group_nodes = (int)group_nodes[g];
+        s.d_dig = d_dig; s.d_ct = d_ct; s.ga = &ga[g]; s.ca = &ca; s.d_models = (const pga_training*)c->d_models_raw; s.st = st;
+        return s;
+    }
     // does group g have chains, and nodes in them?
     bool group_has_work(const int g) const { return g_c0[g + 1] > g_c0[g] && g_n0[g + 1] > g_n0[g]; }
 
@@ -1637,7 +1646,7 @@ struct FindCall : pga_plan::ChainPlan, pga_plan::RescorePlan, pga_plan::GatherPl
     int publish_result(pga_result** out) { ResultOwner* const r = R; return publish(r, R, P, out); }
 
     // the phases, in the order find_impl calls them
-    int check_call(pga_ctx* c_, const pga_batch* batch_, const pga_params* pp, pga_result** out);
+    int check_call(const Knobs& kn_, pga_ctx* c_, const pga_batch* batch_, const pga_params* pp, pga_result** out);
     int run_sequence_and_masks(); int return_sequence_stage(pga_result** out); int run_extract(); int place_nodes(); int plan_chains();
     int plan_connection_scoring(); int prepare_wave(int64_t dp_cap); void order_starts(); int upload_plan(); int score_groups();
     int return_stage_nodes(pga_result** out); int score_connections(); void pick_winners(); int rescore_winners(); int gather_winners();
@@ -1647,8 +1656,8 @@ struct FindCall : pga_plan::ChainPlan, pga_plan::RescorePlan, pga_plan::GatherPl
 };
 
 // the argument checks, the translation-table groups, the dense set ids, the result
-int FindCall::check_call(pga_ctx* c_, const pga_batch* batch_, const pga_params* pp, pga_result** out) {
-    c = c_; batch = batch_;
+int FindCall::check_call(const Knobs& kn_, pga_ctx* c_, const pga_batch* batch_, const pga_params* pp, pga_result** out) {
+    kn = kn_; c = c_; batch = batch_;
     if (out) *out = nullptr;
     if (c) c->dev_nodes.clear();        // this call reuses the arena the last one kept on the device
     if (!c || !out || !pp || !batch || batch->ctx != c) {
@@ -1694,9 +1703,9 @@ int FindCall::check_call(pga_ctx* c_, const pga_batch* batch_, const pga_params*
     }
     NM = c->n_models; NG = meta_run ? (int)f->group_tt.size() : (multi ? std::max(1, (int)gtt.size()) : 1);
     if (NG > 4) { c->err = "pga_find_genes: more than 4 distinct translation tables loaded"; return PGA_EINVAL; }
-    if (const char* fault = getenv("PGA_FAULT_CONTIG_LEN")) {
+    if (kn.fault_contig_len_set) {
         // diagnostics: a call that carries a contig of exactly this many bases fails (the host layer's error paths under test)
-        const long fl = atol(fault);
+        const long fl = kn.fault_contig_len;
         for (int i = 0; i < NC; i++) if ((long)batch->ct[i].len == fl) { c->err = "pga_find_genes: fault injected by PGA_FAULT_CONTIG_LEN"; return PGA_EDEVICE; }
     }
     if (use_sets) {
@@ -1831,21 +1840,21 @@ int FindCall::run_extract() {
     // Staging of the extraction: one slot per two positions of a tile (sequence has a node every 25 positions or so; the full
     // two-slots-per-position staging was half of a context's memory).  A tile that does not fit raises a flag, the batch is then
     // extracted again with full staging, and the context keeps that (PGA_STAGE_FULL=1: from the start).
-    if (getenv("PGA_STAGE_FULL")) f->stage_full = true;
+    if (kn.stage_full) f->stage_full = true;
     bool stage_full = f->stage_full;
     // Stop values of the extraction: a thread of k_extract_tile lists up to four per strand in LDS and a pool of the workgroup takes the
     // rest; a tile that exhausts the pool (a full tile of (GT)n) raises bit 1 of the flag and the batch is extracted again with a
     // value for every position.  That choice is the batch's, the context does not keep it.  (PGA_EXTRACT_C=1 .. 4 / PGA_EXTRACT_POOL=
     // 0 .. 128: fewer list slots / pool entries, so that the tests reach the pool and the second pass on small inputs; PGA_EXTRACT_C=0:
     // a value for every position from the start)
-    int ex_c = getenv("PGA_EXTRACT_C") ? std::max(0, std::min(4, atoi(getenv("PGA_EXTRACT_C")))) : 4;
-    const int ex_pool = getenv("PGA_EXTRACT_POOL") ? std::max(0, std::min(128, atoi(getenv("PGA_EXTRACT_POOL")))) : 128;
+    int ex_c = kn.extract_c;
+    const int ex_pool = kn.extract_pool;
     int32_t* const d_st_overflow = d_xa; const int32_t* const h_st_overflow = h_xa;
     c->extract_passes = 0;
     for (;;) {
         const bool half = !stage_full;
         // (PGA_STAGE_SHIFT=5: one slot per 32 positions, so that ordinary sequence overflows and the tests see the second pass)
-        const int shift = half ? std::max(1, std::min(8, getenv("PGA_STAGE_SHIFT") ? atoi(getenv("PGA_STAGE_SHIFT")) : 1)) : 0;
+        const int shift = half ? kn.stage_shift : 0;
         const int64_t st_slots = half ? (total >> shift) + (int64_t)PGA_STAGE_SLACK * batch->n_tiles + 8 : 2 * total + 2;
         for (int g = 0; g < NG; g++) {
             GBUF(st_ndx, int32_t, st_slots) GBUF(st_sv, int32_t, st_slots) GBUF(st_info, uint8_t, st_slots)
@@ -1867,7 +1876,7 @@ int FindCall::run_extract() {
         if (pool_exhausted) ex_c = 0;
         if (staging_overflow) {
             stage_full = true;
-            if (!getenv("PGA_STAGE_SHIFT")) f->stage_full = true;       // (the test knob leaves the context as it was)
+            if (!kn.stage_shift_set) f->stage_full = true;       // (the test knob leaves the context as it was)
         }
     }
     if (h_moff) { const int rc = fetch_mask_union(c, R, h_moff, d_union_iv, NC); if (rc) return rc; }
@@ -1928,24 +1937,21 @@ int FindCall::plan_connection_scoring() {
     }
     // few long chains: their walks are cut into segments that run side by side (dp.hip "segmented chains": seg_plan)
     // many chains: one wavefront each, records and far-field structures of dp_wave.hip
-    use_wave = stage == 0 && pga_dp_use_wave(NCH);
-    // Round 6 -- few LONG chains whose segments the wave-batch kernel walks (dp.hip, launch_dp_segmented): a wavefront per segment, 2048
+    use_wave = stage == 0 && pga_dp_use_wave(kn, NCH);
+    // Round 6 -- few LONG chains whose segments the wave-batch kernel walks (dp.hip, launch_dp_segmented): a wavefront per segment, 4096
     // segments at once where the chain kernel's workgroup per compute unit allows 252.  Every segment pays the same 4096-node warm-up and
     // a wavefront walks a node more slowly than the sixteen of a chain-kernel workgroup, so this pays where the chains are long enough --
     // from PGA_DP_SEG_WAVE_MIN (2.5 M) nodes in chains of 16 k nodes or more; PGA_DP_SEG_WAVE=1 / 0: always / never (tests).
     seg_wave = false;
-    if (stage == 0 && !use_wave && pga_dpw_use_sched() && !getenv("PGA_DP_KERNEL")) {
+    if (stage == 0 && !use_wave && kn.dpw_sched && !kn.dp_kernel_set) {
         int64_t cand = 0;
-        const int min_chain = std::max(256, getenv("PGA_DP_SEG_MIN") ? atoi(getenv("PGA_DP_SEG_MIN")) : 16384);      // (as pga_dp_plan)
-        for (int k = 0; k < NCH; k++) if (chains[(size_t)k].n >= min_chain) cand += chains[(size_t)k].n;
-        const char* e = getenv("PGA_DP_SEG_WAVE");
-        const char* m = getenv("PGA_DP_SEG_WAVE_MIN");
-        seg_wave = e ? atoi(e) != 0 : cand >= (m ? atoll(m) : 2500000ll);
+        for (int k = 0; k < NCH; k++) if (chains[(size_t)k].n >= kn.dp_seg_min) cand += chains[(size_t)k].n;
+        seg_wave = kn.dp_seg_wave_set ? kn.dp_seg_wave : cand >= kn.dp_seg_wave_min;
     }
     // what the wave-batch kernel reads -- topology, step schedule, cs, extras -- is made for its own launches and for such segments
     wave_prep = use_wave || seg_wave;
     // the step schedule of the wave-batch scorer: one header per 64-node batch of every contig of a group (dpw_core.h)
-    use_sched = wave_prep && pga_dpw_use_sched();
+    use_sched = wave_prep && kn.dpw_sched;
     if (use_sched) {
         h_bbase.resize((size_t)NG * (NC + 1));
         for (int g = 0; g < NG; g++) {
@@ -1957,13 +1963,13 @@ int FindCall::plan_connection_scoring() {
     }
     if (use_sched) for (int g = 0; g < NG; g++) for (int i = 0; i < NC; i++)
         max_batches[g] = std::max(max_batches[g], h_bbase[(size_t)g * (NC + 1) + i + 1] - h_bbase[(size_t)g * (NC + 1) + i]);
-    segmented = stage == 0 && !use_wave && pga_dp_plan(chains.data(), NCH, tot_chain_nodes, seg_plan, seg_wave);
+    segmented = stage == 0 && !use_wave && pga_dp_plan(kn, chains.data(), NCH, tot_chain_nodes, seg_plan, seg_wave);
     if (seg_wave && !segmented) { seg_wave = false; wave_prep = use_wave; use_sched = false; h_bbase.clear(); }       // (nothing to cut after all)
     // lean: the tail runs on the device and nobody asked for node arrays, so only what the tail writes is gathered; direct: it
     // also reads the winners' node fields where the scorers left them.  (One definition: the scorers skip the star_ptr fill under
     // exactly the condition under which the tail never looks at it.)
-    lean_gather = !P.want_nodes && !(getenv("PGA_TAIL") && strcmp(getenv("PGA_TAIL"), "host") == 0) && !getenv("PGA_FULL_GATHER");
-    direct_gather = lean_gather && !getenv("PGA_GATHER_ALL_DP");
+    lean_gather = !P.want_nodes && kn.tail != Knobs::host && !kn.full_gather;
+    direct_gather = lean_gather && !kn.gather_all_dp;
     const int64_t dp_cap = tot_chain_nodes + seg_plan.extra + 1;
     dp_slots = NCH + (int64_t)seg_plan.segs.size() + 1;
     // records and far-field arrays of the tree / chain kernels (sub-chains walked by the wave-batch kernel need none of their own)
@@ -2018,7 +2024,7 @@ int FindCall::prepare_wave(const int64_t dp_cap) {
         int max_nodes_g = 0;
         for (int i = 0; i < NC; i++) max_nodes_g = std::max(max_nodes_g, contig_nodes(g, i));
         if (g < 4) HT(c, hipEventRecord(f->e_aux[4 * g], st));
-        pga_launch_dpw_topo(wgroups.g[g], ga[g].type, ga[g].strand, d_cb(g), NC, (int)group_nodes[g], st, max_nodes_g);
+        pga_launch_dpw_topo(kn, wgroups.g[g], ga[g].type, ga[g].strand, d_cb(g), NC, (int)group_nodes[g], st, max_nodes_g);
         if (g < 4) HT(c, hipEventRecord(f->e_aux[4 * g + 1], st));
     }
     return PGA_OK;
@@ -2026,7 +2032,7 @@ int FindCall::prepare_wave(const int64_t dp_cap) {
 
 // start order of the wave-batch scorer: longest chains first (counting sort on nodes / 64 = walk batches)
 void FindCall::order_starts() {
-    if (!(use_wave && NCH > 1 && !getenv("PGA_DP_NO_ORDER"))) return;
+    if (!(use_wave && NCH > 1 && !kn.dp_no_order)) return;
     std::vector<int32_t> lens((size_t)NCH);
     for (int k = 0; k < NCH; k++) lens[(size_t)k] = chains[k].n;
     dp_order.resize((size_t)NCH);
@@ -2045,7 +2051,7 @@ void FindCall::order_starts() {
         n_xcc = (hipDeviceGetAttribute(&v, hipDeviceAttributeNumberOfXccs, c->device) == hipSuccess && v > 0) ? v : 8;
         xcc_of[c->device & 63].store(n_xcc);
     }
-    if (!(getenv("PGA_DP_XCD") && atoi(getenv("PGA_DP_XCD")) == 0) && NCH >= 64 && n_xcc == 8) {
+    if (kn.dp_xcd && NCH >= 64 && n_xcc == 8) {
         std::vector<int32_t> key((size_t)NCH), by_xcd((size_t)NCH * 8);
         for (int k = 0; k < NCH; k++) key[(size_t)k] = chains[(size_t)k].group * NC + chains[(size_t)k].contig;
         const int64_t nb = pga_dp_xcd_order(NCH, dp_order.data(), lens.data(), key.data(), NC * NG, by_xcd.data(), (int64_t)by_xcd.size());
@@ -2106,6 +2112,7 @@ int FindCall::upload_plan() {
 // node scoring of every group that has work; the wave-batch scorer's schedule, or the chain kernels' records, behind it
 int FindCall::score_groups() {
     sp = ScoreParams{P.closed, P.meta, P.max_overlap, NM, nullptr, nullptr};
+    sp.models_per_pass = kn.ss_models_per_pass;
     PINSET(h_conv, uint8_t, "h_conv_flag", (size_t)NG * NC + 1);
     for (int g = 0; g < NG; g++) {
         const int nch = g_c0[g + 1] - g_c0[g];
@@ -2114,16 +2121,13 @@ int FindCall::score_groups() {
         // the ORF walks of the coding score run from hexamer tables in LDS, contigs bucketed by the four table columns they need
         // (PGA_CS_LDS=0: the global-memory form)
         const void* d_cs_tasks = nullptr; const void* d_cs_entries = nullptr; int n_cs_tasks = 0;
-        const char* cs_env = getenv("PGA_CS_LDS");
-        const char* cs_tn = getenv("PGA_CS_TASK_NODES");
-        const int cs_task_nodes = cs_tn && atoi(cs_tn) >= 256 && atoi(cs_tn) <= 8192 ? atoi(cs_tn) : 5120;     // several tasks per CU and launch (swept again at the end of round 6, one box: 4096 629 us per launch, 4864 581, 5120 586, 5376 584, 5632 600, 6144 592)
-        // PGA_CS_LDS=2 (tests): the LDS form whatever the size of the launch
-        // (single mode as well: one table column, a genome is cut into tasks of `cs_task_nodes` nodes)
+        // kn.cs_task_nodes: several tasks per CU and launch (swept again at the end of round 6, one box: 4096 629 us per launch, 4864 581, 5120 586, 5376 584, 5632 600, 6144 592)
+        // (single mode as well: one table column, a genome is cut into tasks of that many nodes)
         // (the global-memory form walks every ORF on one lane through the texture path: a launch takes as long as its longest ORF,
         //  a few hundred microseconds on high-GC sequence whatever its size -- so small launches take the LDS form as well)
-        if (!(cs_env && atoi(cs_env) == 0) && !f->gil_stride.empty()) {
+        if (kn.cs_lds && !f->gil_stride.empty()) {
             std::vector<int32_t>& tk = cs_tk[g]; std::vector<int32_t>& en = cs_en[g];     // alive until the stream is synchronized
-            if (pga_cs_tasks(h_cc + (size_t)g * NC, NC, chains.data(), h_cb(g), f->model_rank.data(), cs_task_nodes, tk, en) && !tk.empty()) {
+            if (pga_cs_tasks(h_cc + (size_t)g * NC, NC, chains.data(), h_cb(g), f->model_rank.data(), kn.cs_task_nodes, tk, en) && !tk.empty()) {
                 void* p1; void* p2;
                 GROUPBUF(p1, void*, "cs_tasks", tk.size() * 4 + 64, false)
                 GROUPBUF(p2, void*, "cs_entries", en.size() * 4 + 64, false)
@@ -2133,45 +2137,56 @@ int FindCall::score_groups() {
             }
         }
         sp.conv_flag = meta_run ? d_conv + (size_t)g * NC : nullptr;
-        // overlapping starts over (chain, stop node) pairs; for the wave-batch scorer the same pass builds the stops' extras and
-        // the start scorer leaves cscore + sscore, so its per-chain preparation is done when scoring is
-        StopLaunch sl;
-        sl.sbase = d_sb(g); sl.soff_begin = g_s0[g]; sl.n_pairs = g_s0[g + 1] - g_s0[g];
-        sl.n_stops = group_stops(g);
+        const ScoreGroup grp = score_group(g, d_chains + g_c0[g], nch, g_n0[g], nn, d_cc + (size_t)g * NC);
+        const int32_t n_stops = group_stops(g), n_starts = (int32_t)(group_nodes[g] - n_stops);
         // (the path proper; a stage-level call returns the node arrays after any stage, so there every node keeps its thread)
-        sl.starts_only = stage == 0 && !(getenv("PGA_SS_STARTS_ONLY") && atoi(getenv("PGA_SS_STARTS_ONLY")) == 0);
-        sl.n_starts = (int32_t)(group_nodes[g] - sl.n_stops);
-        sl.blk_chain = d_ovl_blk + ovl_blk0[(size_t)g];
+        const bool starts_only = stage == 0 && kn.ss_starts_only;
+        StartScoreLaunch ss(grp);
+        ss.form = starts_only ? StartScoreLaunch::listed_loop : StartScoreLaunch::all_nodes;
+        ss.d_sd_lut = f->d_sd_lut; ss.n_starts = n_starts; ss.n_stops = n_stops; ss.sbase = d_sb(g);
+        ss.mm_tile_items = kn.ss_mm_tile; ss.profile = kn.ss_profile;
         // the model-major start scoring: its records, chains and tiles live in the context (PGA_SS_MM=0: the model loop).  With one
         // model loaded the model loop has nothing to walk (one staging, one barrier per workgroup) and stays: on a 200 Mbp genome the
         // two kernels took 2 ms more (k_mm_place writes a chain's thousands of tiles from one thread)
-        if (sl.starts_only && sl.n_starts > 0 && NM > 1 && !(getenv("PGA_SS_MM") && atoi(getenv("PGA_SS_MM")) == 0)) {
+        if (starts_only && n_starts > 0 && NM > 1 && kn.ss_mm) {
             std::vector<int64_t> mm_items;
-            sl.mm_tiles = pga_mm_tiles(chains.data() + g_c0[g], nch, h_cb(g), h_sb(g), NM, mm_items);
-            GROUPBUF(sl.mm_rec, void*, "ss_rec", PGA_SS_REC_BYTES * (size_t)sl.n_starts + 64, false)
-            GROUPBUF(sl.mm_chain, void*, "ss_mmchain", PGA_SS_MMCHAIN_BYTES * (size_t)nch + 64, false)
-            GROUPBUF(sl.mm_tile, void*, "ss_mmtile", PGA_SS_MMTILE_BYTES * (size_t)sl.mm_tiles + 64, false)
-            GROUPBUF(sl.mm_scratch, void*, "ss_mmscratch", pga_mm_scratch_bytes(NM, nch), false)
+            ss.mm_tiles = pga_mm_tiles(chains.data() + g_c0[g], nch, h_cb(g), h_sb(g), NM, kn.ss_mm_tile, mm_items);
+            GROUPBUF(ss.mm_rec, void*, "ss_rec", PGA_SS_REC_BYTES * (size_t)n_starts + 64, false)
+            GROUPBUF(ss.mm_chain, void*, "ss_mmchain", PGA_SS_MMCHAIN_BYTES * (size_t)nch + 64, false)
+            GROUPBUF(ss.mm_tile, void*, "ss_mmtile", PGA_SS_MMTILE_BYTES * (size_t)ss.mm_tiles + 64, false)
+            GROUPBUF(ss.mm_scratch, void*, "ss_mmscratch", pga_mm_scratch_bytes(NM, nch), false)
+            if (ss.mm_tiles > 0) ss.form = StartScoreLaunch::model_major;      // (no start node in any chain's contig: nothing to tile)
         }
+        // overlapping starts over (chain, stop node) pairs; for the wave-batch scorer the same pass builds the stops' extras and
+        // the start scorer leaves cscore + sscore, so its per-chain preparation is done when scoring is
+        OverlapLaunch ov(grp);
+        ov.form = OverlapLaunch::stop_pairs; ov.d_mc = c->d_model_const; ov.max_overlap = sp.max_overlap;
+        ov.sbase = d_sb(g); ov.soff_begin = g_s0[g]; ov.n_pairs = g_s0[g + 1] - g_s0[g]; ov.n_stops = n_stops;
+        ov.blk_chain = kn.ovl_search ? nullptr : d_ovl_blk + ovl_blk0[(size_t)g];
         sp.cs_out = nullptr;
         if (wave_prep) {
-            sl.topo_q2 = wgroups.g[g].q2; sl.ext = wbuf.ext; sp.cs_out = wbuf.cs;
+            ov.topo_q2 = wgroups.g[g].q2; ov.ext = wbuf.ext; ov.cs_out = sp.cs_out = wbuf.cs;
             if (use_wave) {
                 // (direct mode: the tail reads star_ptr only at the stop nodes, which k_ovl_stops always writes)
-                sl.fill_star_ptr = !(stage == 0 && direct_gather);
+                ov.fill_star_ptr = !(stage == 0 && direct_gather);
                 // (the path proper, node arrays not asked for: a stop node's zero scores are read by nobody -- ScoreParams::lean_stops)
-                sp.lean_stops = (stage == 0 && direct_gather && sl.starts_only && !getenv("PGA_SS_FULL_STOPS")) ? 1 : 0;
+                sp.lean_stops = (stage == 0 && direct_gather && starts_only && !kn.ss_full_stops) ? 1 : 0;
             }       // (segments walked by the wave-batch kernel: the re-scoring and verifying kernels read the node arrays in full)
         }
+        ss.sp = sp;       // (final for this group; the member keeps cs_out and lean_stops for the re-score of the winners)
         const bool gil = meta_run || per_contig || n_cs_tasks > 0;
-        pga_launch_score(d_chains + g_c0[g], nch, g_n0[g], nn, d_dig, d_ct, ga[g], (const pga_training*)c->d_models_raw, f->d_msc, c->d_model_const, ca, sp,
-                         d_chains, d_cc + (size_t)g * NC, d_cb(g), NC, (int)group_nodes[g], f->d_sd_lut, st, 0,
-                         gil ? f->d_gil + f->gil_off[g] : nullptr, gil ? f->gil_stride[g] : 0, f->d_model_rank,
-                         d_cs_tasks, n_cs_tasks, d_cs_entries, &sl);
+        CodingScoreLaunch cs(grp);
+        cs.form = n_cs_tasks > 0 ? CodingScoreLaunch::lds_tasks : CodingScoreLaunch::global_memory;
+        cs.d_msc = f->d_msc; cs.d_gil = gil ? f->d_gil + f->gil_off[g] : nullptr; cs.il_stride = gil ? f->gil_stride[g] : 0; cs.d_rank = f->d_model_rank;
+        cs.d_cs_tasks = d_cs_tasks; cs.n_cs_tasks = n_cs_tasks; cs.d_cs_entries = d_cs_entries;
+        cs.cs_wave = kn.cs_wave; cs.qclasses = kn.cs_qclasses; cs.profile = kn.cs_profile;
+        pga_launch_coding_score(cs);
+        if (!pga_launch_start_scores(ss)) { c->err = "pga_find_genes: the start scoring was planned in a form whose buffers are missing"; return PGA_EDEVICE; }
+        pga_launch_overlapping_starts(ov);
         if (wave_prep && use_sched) {
             // (behind the scoring launches: the schedule's headers carry the stop nodes' ranks, which k_ovl_topo writes there)
             if (g < 4) HT(c, hipEventRecord(f->e_aux[4 * g + 2], st));
-            pga_launch_dpw_sched(wgroups.g[g], d_cb(g), d_bbase + (size_t)g * (NC + 1), NC, max_batches[g], st);
+            pga_launch_dpw_sched(kn, wgroups.g[g], d_cb(g), d_bbase + (size_t)g * (NC + 1), NC, max_batches[g], st);
             if (g < 4) HT(c, hipEventRecord(f->e_aux[4 * g + 3], st));
             HT(c, hipMemcpyAsync(h_scur + 2 * g, wgroups.g[g].scur, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
         }
@@ -2247,11 +2262,11 @@ int FindCall::return_stage_nodes(pga_result** out) {
 // when a step schedule did not fit, the statistics and timings
 int FindCall::score_connections() {
     PINBUF(h_segflags, int32_t, "h_segflags", (size_t)(PGA_SEG_ROUNDS + 2) * NCH + 1);      // [rounds][chains] flags, [chains] spine sizes, [chains] a round's verdict
-    if (segmented && !(getenv("PGA_DP_SEG_READBACK") && atoi(getenv("PGA_DP_SEG_READBACK")) == 0)) seg_dev.h_round = h_segflags + (size_t)(PGA_SEG_ROUNDS + 1) * NCH;
+    if (segmented && kn.dp_seg_readback) seg_dev.h_round = h_segflags + (size_t)(PGA_SEG_ROUNDS + 1) * NCH;
     HT(c, hipEventRecord(f->e_dp0[0], st));
     if (use_wave) {
         // PGA_DP_PROFILE=1: cycles per batch phase of every 64th chain (a synchronising debug aid)
-        if (getenv("PGA_DP_PROFILE")) {
+        if (kn.dp_profile) {
             DEVBUF(d_prof, unsigned long long, "dp_prof", 16);
             HT(c, hipMemsetAsync(d_prof, 0, 128, st));
             dp.prof = d_prof;
@@ -2268,7 +2283,7 @@ int FindCall::score_connections() {
             dp.prof = nullptr;
         }
     }
-    else pga_launch_dp(d_chains, NCH, c->d_model_const, dp, 1, st, segmented ? &seg_dev : nullptr);
+    else pga_launch_dp(kn, d_chains, NCH, c->d_model_const, dp, 1, st, segmented ? &seg_dev : nullptr);
     HT(c, hipEventRecord(f->e_dp1[0], st));
     HT(c, hipMemcpyAsync(h_maxscore, dp.max_score, sizeof(double) * 2 * (size_t)dp_slots, hipMemcpyDeviceToHost, st));       // scores, indices, path starts
     if (meta_run) HT(c, hipMemcpyAsync(h_conv, d_conv, (size_t)NG * NC, hipMemcpyDeviceToHost, st));
@@ -2283,7 +2298,7 @@ int FindCall::score_connections() {
         // a schedule that did not fit its buffer (node-dense input: more than two slots per node on average): the same launch again
         // with the kernel that works the lane masks out itself
         for (int g = 0; g < NG; g++) if (group_has_work(g)) sched_missed += h_scur[2 * g + 1];
-        if (getenv("PGA_DPW_SCHED_DEBUG")) for (int g = 0; g < NG; g++) fprintf(stderr, "[pga dpw sched] group %d: %u batches missed\n", g, h_scur[2 * g + 1]);
+        if (kn.dpw_sched_debug) for (int g = 0; g < NG; g++) fprintf(stderr, "[pga dpw sched] group %d: %u batches missed\n", g, h_scur[2 * g + 1]);
         if (sched_missed && use_wave) {      // (segments walked by the wave-batch kernel: a missed batch ends its segment's claims, the verification does the rest)
             // (the first launch's time counts: t_dp_ms covers both)
             { float ms = 0; HT(c, hipEventElapsedTime(&ms, f->e_dp0[0], f->e_dp1[0])); dp_first_ms = ms; }
@@ -2296,7 +2311,7 @@ int FindCall::score_connections() {
     }
     pga_dp_note_stats(c, segmented ? &seg_plan : nullptr, h_segflags, NCH);
     c->dp_stats[6] = use_sched ? 1 : 0; c->dp_stats[7] = (int32_t)sched_missed;
-    if (segmented && getenv("PGA_DP_SEG_DEBUG")) {
+    if (segmented && kn.dp_seg_debug) {
         fprintf(stderr, "[pga dp-seg] %d chains cut into %d segments (<= %d nodes each); nodes rejected per round: %d %d %d; walked serially: %d; spine:",
                 seg_dev.n_big, seg_dev.n_segs, seg_dev.max_seg_nodes, c->dp_stats[2], c->dp_stats[3], c->dp_stats[4], c->dp_stats[5]);
         for (int k : seg_plan.big) fprintf(stderr, " %d/%d", h_segflags[(size_t)PGA_SEG_ROUNDS * NCH + k], chains[(size_t)k].n);
@@ -2332,8 +2347,16 @@ int FindCall::rescore_winners() {
     for (int g = 0; g < NG; g++) {
         const int nch = r_c0[g + 1] - r_c0[g]; const int64_t nn = r_n0[g + 1] - r_n0[g];
         if (nch == 0 || nn == 0) continue;
-        pga_launch_score(d_chains + NCH + r_c0[g], nch, r_n0[g], nn, d_dig, d_ct, ga[g], (const pga_training*)c->d_models_raw, f->d_msc, c->d_model_const, ca, sp,
-                         d_chains, d_cc + (size_t)NG * NC + (size_t)g * NC, d_cb(g), NC, (int)group_nodes[g], f->d_sd_lut, st, 1);
+        // no coding-score launch: the raw coding score of a start depends on the model only, not on which model of the group was scored
+        // first on the contig, so the fresh re-score of a winning model (ref: lib.pyx:5380-5394) reads it where the winning pass left
+        // it (ChainDesc::raw_off) instead of walking every ORF again
+        const ScoreGroup grp = score_group(g, d_chains + NCH + r_c0[g], nch, r_n0[g], nn, d_cc + (size_t)NG * NC + (size_t)g * NC);
+        StartScoreLaunch ss(grp);          // (a thread per node)
+        ss.sp = sp; ss.d_sd_lut = f->d_sd_lut; ss.profile = kn.ss_profile;
+        if (!pga_launch_start_scores(ss)) { c->err = "pga_find_genes: the re-score of the winners could not be launched"; return PGA_EDEVICE; }
+        OverlapLaunch ov(grp);             // (k_overlapping_starts over every node)
+        ov.d_mc = c->d_model_const; ov.max_overlap = sp.max_overlap;
+        pga_launch_overlapping_starts(ov);
     }
     return PGA_OK;
 }
@@ -2435,7 +2458,7 @@ int FindCall::run_host_tail() {
                        h.star_ptr + 3 * oo, h.traceb + oo, tracef.data() + oo, h.ov_mark + oo, h.score + oo, elim.data() + oo};
             const int mx = h_maxidx[k];
             const double st_wt = c->models[chains[k].model].st_wt;
-            const bool sub = NC == 1 && getenv("PGA_TIMING");
+            const bool sub = NC == 1 && kn.timing;
             auto now = [] { return std::chrono::steady_clock::now(); };
             auto t0 = now(), t1 = t0, t2 = t0, t3 = t0;
             if (v.n > 0 && mx >= 0) {
@@ -2562,7 +2585,7 @@ int FindCall::launch_tail_paths(const TailBufs& t) {
         int levels = 1;
         while ((1ll << levels) < max_n) levels++;
         const unsigned nblk = (unsigned)((out_nodes + 255) / 256);
-        const bool tp_steps = getenv("PGA_TP_STEPS") != nullptr;      // the many-launch form also for short chains (cross-check)
+        const bool tp_steps = kn.tp_steps;      // the many-launch form also for short chains (cross-check)
         const bool tp_one = max_n <= TP_SMALL_MAX && !tp_steps;
         const int64_t tpn = tp_one ? 0 : out_nodes;                   // the per-node work arrays of the many-launch form
         DEVBUF(tp_seg, TpSeg, "tp_seg", segs.size()) DEVBUF(tp_up, int32_t, "tp_up", (size_t)2 * tpn)
@@ -2583,7 +2606,7 @@ int FindCall::launch_tail_paths(const TailBufs& t) {
             hipLaunchKernelGGL(k_tp_init, grid, blk, 0, st, tw, t.d_td, o);
             // pointer jumping: 2^levels >= the longest chain; eight hops per launch while three levels or more are left (PGA_TP_JUMP8=0: doubling only)
             {
-                const bool j8 = !(getenv("PGA_TP_JUMP8") && atoi(getenv("PGA_TP_JUMP8")) == 0);
+                const bool j8 = kn.tp_jump8;
                 int k = 0;
                 for (int left = levels; left > 0; k++) {
                     const int32_t* in = tp_up + (size_t)(k & 1) * out_nodes; int32_t* outp = tp_up + (size_t)((k + 1) & 1) * out_nodes;
@@ -2600,7 +2623,7 @@ int FindCall::launch_tail_paths(const TailBufs& t) {
             hipLaunchKernelGGL(k_tp_elim_a, grid, blk, 0, st, tw, t.d_td, o, t.d_path);
             hipLaunchKernelGGL(k_tp_elim_b, grid, blk, 0, st, tw, t.d_td, o, t.d_path, t.d_elim);
             // a workgroup per contig: wide for genomes, narrow when there are many short paths
-            if (max_n >= 32768 && segs.size() <= 64 && !getenv("PGA_TP_EXTRACT_ONE")) {
+            if (max_n >= 32768 && segs.size() <= 64 && !kn.tp_extract_one) {
                 // genomes: a workgroup per chunk of 1024 path positions (k_tp_extract: one workgroup per contig, 400 rounds)
                 const int chunks = (max_n + 1023) / 1024;
                 DEVBUF(tp_xsum, TpChunkSum, "tp_xsum", (size_t)chunks * segs.size() + 1);
@@ -2623,7 +2646,7 @@ int FindCall::launch_tail_tweaks(TailBufs& t) {
     if (max_n >= 32768 && NC <= 1024)       // genomes: a wavefront per gene (at most n / 2 + 2 genes per contig)
         hipLaunchKernelGGL(k_tail_tweak_wave, dim3((unsigned)((max_n / 2 + 2 + 3) / 4), (unsigned)NC), dim3(256), 0, st, t.d_td, NC, o, t.d_tracef,
                            t.d_elim, t.d_gene0, t.d_gene1, t.d_ngenes, P.max_overlap, t.d_changed, t.d_nchanged);
-    else if (NC >= 256 && !getenv("PGA_TWEAK_SLOTS")) {   // many contigs: one thread per gene of the batch, packed
+    else if (NC >= 256 && !kn.tweak_slots) {   // many contigs: one thread per gene of the batch, packed
         DEVBUF(d_gpre, int32_t, "d_gene_prefix", NC + 2);
         hipLaunchKernelGGL(k_gene_prefix, dim3(1), dim3(1024), 0, st, t.d_ngenes, NC, d_gpre);
         hipLaunchKernelGGL(k_tail_tweak_packed, dim3(1024), dim3(256), 0, st, t.d_td, NC, o, t.d_tracef, t.d_elim, t.d_gene0, t.d_gene1, t.d_ngenes,
@@ -2680,7 +2703,7 @@ int FindCall::run_device_tail(const bool par_tail) {
     tm->mark("tail");
     // ---- results --------------------------------------------------------------------------------------
     const int64_t ngenes = contig_results(h_ngenes, h_gbegin);
-    pga_gene* const genes_out = coding || keep ? nullptr : R->gene_records((size_t)ngenes);
+    pga_gene* const genes_out = coding || keep ? nullptr : R->gene_records((size_t)ngenes, kn.pageable_results);
     pga_gene* d_genes = nullptr;
     if (ngenes > 0) {
         DEVBUF(d_genes_out, pga_gene, keep ? keep->buf : "d_genes_out", ngenes + 1);
@@ -2773,12 +2796,12 @@ void FindCall::keep_device_nodes() {
 // gene records are (pga_find_coding_bases); the records are then not copied back and the result holds no genes.
 // keep (stage 0; nullptr otherwise): a pass of a circular call (circular.inl) -- the gene records stay on the device, in the buffer
 // `keep->buf`, and the result holds none; `keep` reports where they are (nothing when the call found no node at all).
-static int find_impl(pga_ctx* c, const pga_batch* batch, const pga_params* pp, const int stage, const int tt_override, pga_result** out,
+static int find_impl(const Knobs& kn, pga_ctx* c, const pga_batch* batch, const pga_params* pp, const int stage, const int tt_override, pga_result** out,
                      const int32_t* model_of_contig, const int32_t* tt_of_contig, int64_t* coding = nullptr, GeneKeep* keep = nullptr) {
     FindCall s;
     s.stage = stage; s.tt_override = tt_override; s.model_of_contig = model_of_contig; s.tt_of_contig = tt_of_contig; s.coding = coding; s.keep = keep;
-    if (const int rc = s.check_call(c, batch, pp, out)) return rc;
-    StageTimer tm;
+    if (const int rc = s.check_call(kn, c, batch, pp, out)) return rc;
+    StageTimer tm(kn.timing);
     s.tm = &tm;
     if (s.NC > 0 && s.total > 0) {
         if (const int rc = s.run_sequence_and_masks()) return rc;
@@ -2800,10 +2823,9 @@ static int find_impl(pga_ctx* c, const pga_batch* batch, const pga_params* pp, c
         if (const int rc = s.gather_winners()) return rc;
         // The tail (traceback untangling, bad-gene elimination, gene list, start tweaks) is a pointer chase per contig:
         // PGA_TAIL = host | device (one thread per contig) | par (tail.inl, the default)
-        const char* tail_env = getenv("PGA_TAIL");
-        const bool device_tail = tail_env ? strcmp(tail_env, "host") != 0 : true;
+        const bool device_tail = kn.tail != Knobs::host;
         if (keep && !device_tail) { c->err = "pga_find_genes: circular contigs are called with the device tail only (PGA_TAIL=host is set)"; return PGA_EINVAL; }
-        if (const int rc = device_tail ? s.run_device_tail(!(tail_env && strcmp(tail_env, "device") == 0)) : s.run_host_tail()) return rc;
+        if (const int rc = device_tail ? s.run_device_tail(kn.tail == Knobs::par) : s.run_host_tail()) return rc;
         if (s.P.want_nodes == 1) { if (const int rc = s.copy_out_nodes()) return rc; }
         if (s.P.want_nodes) s.keep_device_nodes();
     }
@@ -2818,6 +2840,7 @@ static int find_impl(pga_ctx* c, const pga_batch* batch, const pga_params* pp, c
 #include "terminal_repeat.inl"
 
 extern "C" int pga_find_genes(pga_ctx* c, const pga_batch* batch, const pga_params* pp, pga_result** out) {
+    const Knobs kn = read_knobs();
     const auto t0 = std::chrono::steady_clock::now();
     const bool circular = c && batch && batch->ctx == c && !batch->circular.empty();
     if (c) { c->last_cuts.clear(); c->set_model.clear(); c->set_score.clear(); c->model_scores.clear(); c->model_scores_nm = 0; }
@@ -2826,8 +2849,8 @@ extern "C" int pga_find_genes(pga_ctx* c, const pga_batch* batch, const pga_para
         if (circular) { c->err = "pga_find_genes: the batch carries both set labels (pga_batch_set_sets) and circular flags (pga_batch_set_circular)"; return PGA_EINVAL; }
         if (!pp->meta) { c->err = "pga_find_genes: set labels (pga_batch_set_sets) are a meta-mode feature (params->meta must be 1)"; return PGA_EINVAL; }
     }
-    const int rc = circular ? find_circular(c, batch, pp, out, nullptr) : find_impl(c, batch, pp, 0, 0, out, nullptr, nullptr);
-    if (getenv("PGA_TIMING")) fprintf(stderr, "[pga timing] pga_find_genes wall=%.2fms\n", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
+    const int rc = circular ? find_circular(kn, c, batch, pp, out, nullptr) : find_impl(kn, c, batch, pp, 0, 0, out, nullptr, nullptr);
+    if (kn.timing) fprintf(stderr, "[pga timing] pga_find_genes wall=%.2fms\n", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
     return rc;
 }
 
@@ -2837,7 +2860,7 @@ extern "C" int pga_nodes_stage(pga_ctx* c, const pga_batch* batch, const pga_par
         if (c) c->err = "pga_nodes_stage: unknown stage";
         return PGA_EINVAL;
     }
-    return find_impl(c, batch, pp, stage, translation_table, out, nullptr, nullptr);
+    return find_impl(read_knobs(), c, batch, pp, stage, translation_table, out, nullptr, nullptr);
 }
 
 extern "C" int pga_find_genes_models(pga_ctx* c, const pga_batch* batch, const pga_params* pp, const int32_t* model_of_contig, pga_result** out) {
@@ -2856,8 +2879,9 @@ extern "C" int pga_find_genes_models(pga_ctx* c, const pga_batch* batch, const p
         c->err = "pga_find_genes_models: the batch carries both set labels (pga_batch_set_sets) and circular flags (pga_batch_set_circular)";
         return PGA_EINVAL;
     }
-    if (batch->ctx == c && !batch->circular.empty()) return find_circular(c, batch, pp, out, model_of_contig);
-    return find_impl(c, batch, pp, 0, 0, out, model_of_contig, nullptr);
+    const Knobs kn = read_knobs();
+    if (batch->ctx == c && !batch->circular.empty()) return find_circular(kn, c, batch, pp, out, model_of_contig);
+    return find_impl(kn, c, batch, pp, 0, 0, out, model_of_contig, nullptr);
 }
 
 extern "C" int pga_train(pga_ctx* c, const pga_batch* batch, const pga_params* pp, int translation_table, double start_weight,
@@ -2892,7 +2916,7 @@ extern "C" int pga_find_coding_bases(pga_ctx* c, const pga_batch* batch, const p
     pga_params P = *pp;
     P.want_nodes = 0;                       // nothing of the nodes is kept or gathered for the host
     pga_result* r = nullptr;
-    const int rc = find_impl(c, batch, &P, 0, 0, &r, model_of_contig, nullptr, coding_bases);
+    const int rc = find_impl(read_knobs(), c, batch, &P, 0, 0, &r, model_of_contig, nullptr, coding_bases);
     if (rc != PGA_OK) return rc;
     for (int i = 0; i < batch->n; i++) { n_genes[i] = r->contigs[i].n_genes; score[i] = r->contigs[i].score; }
     pga_result_free(r);

@@ -10,6 +10,7 @@
 
 #include "../../include/pyrodigal_amd.h"
 #include "find_pods.h"     // ContigDesc, ChainDesc
+#include "knobs.h"         // Knobs: the run-time knobs, read once per call
 
 #define PGA_MAX_NODE_DIST 500   // ref: _connection.h:5 / dprog.h
 #define PGA_MAX_OPP_OVLP  200
@@ -106,9 +107,9 @@ struct DpSegDev {        // device copies + workspace; all owned by the caller
     const struct DpwGroupPtrs* wave_groups = nullptr;
     const struct DpwBuffers* wave_buf = nullptr;
 };
-// false: nothing to segment (plan left empty).  wave_walk: the segments are walked by the wave-batch kernel (a wavefront each: PGA_DP_SEG_WSLOTS,
-// 4096, of them at once) instead of the chain kernel (a workgroup each: PGA_DP_SEG_SLOTS, 256)
-bool pga_dp_plan(const ChainDesc* h_chains, int n_chains, int64_t tot_nodes, DpSegPlan& plan, bool wave_walk = false);
+// false: nothing to segment (plan left empty).  wave_walk: the segments are walked by the wave-batch kernel (a wavefront each:
+// Knobs::dp_seg_wslots of them at once) instead of the chain kernel (a workgroup each: Knobs::dp_seg_slots)
+bool pga_dp_plan(const Knobs& kn, const ChainDesc* h_chains, int n_chains, int64_t tot_nodes, DpSegPlan& plan, bool wave_walk = false);
 // device workspace of a segmented launch: its size, and its layout inside `arena` + the upload of the plan (the plan must
 // stay alive until the copies on `st` are done)
 size_t pga_dp_seg_bytes(const DpSegPlan& plan, int n_chains, int64_t tot_nodes);
@@ -129,14 +130,14 @@ struct DpwGroupPtrs { DpwTopoArrays g[4]; };
 // node, or dense by (chain, stop) pair: DpwTopoArrays::srank)
 struct DpwBuffers { double* cs; DpwExt* ext; double* sfxv; int32_t* sfxi; };
 // which connection scorer a final-pass launch over n_chains chains uses (PGA_DP_KERNEL overrides: wave | tree1 | tree3 | scan)
-bool pga_dp_use_wave(int n_chains);
+bool pga_dp_use_wave(const Knobs& kn, int n_chains);
 // max_contig_nodes (0: unknown): the most nodes any contig of the group holds -- contigs that fit are staged in LDS, a workgroup each
-void pga_launch_dpw_topo(const DpwTopoArrays& ta, const uint8_t* type, const int8_t* strand, const int32_t* d_cbase, int n_contigs, int n_nodes,
+void pga_launch_dpw_topo(const Knobs& kn, const DpwTopoArrays& ta, const uint8_t* type, const int8_t* strand, const int32_t* d_cbase, int n_contigs, int n_nodes,
                          hipStream_t st, int max_contig_nodes = 0);
 // the step schedule of a group (after pga_launch_dpw_topo): d_bbase[c] = 64-node batches of the contigs before contig c; max_batches: of
 // the contig with the most nodes; ta.sent holds DPW_SCHED_STRIDE slots per batch.  ta.scur is NOT cleared here: the topology
 // kernel clears it, so ta.scur must be set (allocated) when pga_launch_dpw_topo is called
-void pga_launch_dpw_sched(const DpwTopoArrays& ta, const int32_t* d_cbase, const int32_t* d_bbase, int n_contigs, int max_batches, hipStream_t st);
+void pga_launch_dpw_sched(const Knobs& kn, const DpwTopoArrays& ta, const int32_t* d_cbase, const int32_t* d_bbase, int n_contigs, int max_batches, hipStream_t st);
 // chains[0..n_chains) of ONE group, contiguous in `off` from node_begin
 void pga_launch_dpw_chain(const ChainDesc* d_chains, int n_chains, int64_t node_begin, int64_t total_nodes, const NodeArrays& nodes,
                           const DpwTopoArrays& ta, const ModelConst* d_models, const DpwBuffers& wb, hipStream_t st);
@@ -146,7 +147,6 @@ void pga_launch_dpw_chain(const ChainDesc* d_chains, int n_chains, int64_t node_
 void pga_launch_dp_wave(const ChainDesc* d_chains, int n_chains, const DpwGroupPtrs& groups, const ModelConst* d_models, DpBuffers buf,
                         const DpwBuffers& wb, hipStream_t st, const int32_t* d_order = nullptr, int n_blocks = 0 /* entries of d_order; < 0 = filler */,
                         bool scheduled = false);
-bool pga_dpw_use_sched();
 // the sub-chains of a segmented launch (DpSegPlan::p1_chains, the first n_segs of them) by the scheduled kernel; results to d_slot[k]
 void pga_launch_dp_wave_sub(const ChainDesc* d_subs, int n_subs, const DpwGroupPtrs& groups, const ModelConst* d_models, DpBuffers buf,
                             const DpwBuffers& wb, hipStream_t st, const int32_t* d_slot);
@@ -157,7 +157,7 @@ void pga_launch_dp_prepare(const ChainDesc* d_chains, int n_chains, int64_t node
                            const NodeArrays& nodes, const ModelConst* d_models, DpBuffers buf, hipStream_t st, int final = 1);
 // seg != nullptr (from a non-empty plan): max_index / max_score / ipath need n_chains + n_segs entries and every per-node
 // array plan.extra more elements
-void pga_launch_dp(const ChainDesc* d_chains, int n_chains, const ModelConst* d_models, DpBuffers buf,
+void pga_launch_dp(const Knobs& kn, const ChainDesc* d_chains, int n_chains, const ModelConst* d_models, DpBuffers buf,
                    int final, hipStream_t st, const DpSegDev* seg = nullptr);
 
 struct FinderState;   // finder.hip

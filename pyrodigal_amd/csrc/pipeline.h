@@ -98,33 +98,8 @@ void pga_launch_extract(const uint8_t* d_dig, int64_t total, const ContigDesc* d
                                              more raises bit 1 of *ga.st_overflow (bit 0: the half-density staging did not fit) */);
 void pga_launch_place(const ContigDesc* d_ct, const TileDesc* d_tiles, int n_tiles, const int32_t* d_tile_off, const int32_t* d_tile_soff,
                       const GroupArrays& ga, hipStream_t st);
-// Overlapping starts over (chain, stop node) pairs instead of over every chain node (pga_launch_score with `stops`):
-struct StopLaunch {
-    const int32_t* sbase = nullptr;     // per contig of the group: first entry of ga.stop_list (n_contigs + 1)
-    int64_t soff_begin = 0, n_pairs = 0; // ChainDesc::soff of the launch's first chain; (chain, stop) pairs of its chains
-    int32_t n_stops = 0;                 // stop nodes of the group (entries of ga.stop_list)
-    // the wave-batch scorer's 64-byte extras of every stop node, built in the same pass (nullptr: not wanted)
-    const int32_t* topo_q2 = nullptr; void* ext = nullptr;
-    // star_ptr of the nodes that are no stop nodes is -1: the launcher fills the chains' range first -- unless nobody will read it
-    // (the wave-batch scorer takes the extras, the tail asks for stop nodes only, the caller does not want the node arrays)
-    bool fill_star_ptr = true;
-    // the start scorer runs over ga.start_list (n_starts entries) instead of over every node (its workgroups clear the fields of the
-    // stop nodes between their start nodes at the end)
-    bool starts_only = false; int32_t n_starts = 0;
-    // per workgroup of k_ovl_stops (256 pairs from soff_begin on): the chain of its first pair, relative to the launch's first chain
-    // (the caller's plan; nullptr: the workgroup searches)
-    const int32_t* blk_chain = nullptr;
-    // the listed start scoring as a per-start prologue and a model-major pass over (chain, start) items (k_start_prologue,
-    // k_score_starts_mm; PGA_SS_MM=0 or mm_tiles == 0: the model loop of k_score_starts).  The caller sizes the context's buffers:
-    void* mm_rec = nullptr;              // SsStartRec per start node of the group (n_starts)
-    void* mm_chain = nullptr;            // SsMmChain per chain of the launch (n_chains)
-    void* mm_tile = nullptr;             // SsMmTile per tile (mm_tiles)
-    void* mm_scratch = nullptr;          // pga_mm_scratch_bytes(n_models, n_chains)
-    int32_t mm_tiles = 0;                // sum over models of ceil(items of the model / pga_mm_tile_items()) (pga_mm_tiles)
-};
-// (chain, start) items of the model-major start scoring: tiles of pga_mm_tile_items() items of one model each
-int pga_mm_tile_items();
-int32_t pga_mm_tiles(const ChainDesc* h_chains, int n_chains, const int32_t* h_cbase, const int32_t* h_sbase, int n_models, std::vector<int64_t>& scratch);
+// (chain, start) items of the model-major start scoring: tiles of `tile` (Knobs::ss_mm_tile) items of one model each
+int32_t pga_mm_tiles(const ChainDesc* h_chains, int n_chains, const int32_t* h_cbase, const int32_t* h_sbase, int n_models, int tile, std::vector<int64_t>& scratch);
 size_t pga_mm_scratch_bytes(int n_models, int n_chains);
 constexpr size_t PGA_SS_REC_BYTES = 32, PGA_SS_MMCHAIN_BYTES = 32, PGA_SS_MMTILE_BYTES = 16;
 // per (group, contig): is any model of the group inside the contig's GC window?  (meta mode)
@@ -150,17 +125,60 @@ void pga_launch_mask_union(const uint8_t* d_dig, const char* d_seq, int64_t tota
 int pga_extract_tile_size();
 void pga_launch_orf_gc(const ContigDesc* d_ct, int n_contigs, const uint8_t* d_dig, const int32_t* d_p16, const GroupArrays& ga,
                        int n_nodes_total, const int32_t* d_node_contig_base, hipStream_t st);
-// chains[0..n_chains): the chains of ONE translation-table group, contiguous in `off` from node_begin
-void pga_launch_score(const ChainDesc* d_chains, int n_chains, int64_t node_begin, int64_t total, const uint8_t* d_dig,
-                      const ContigDesc* d_ct, const GroupArrays& ga, const pga_training* d_models,
-                      const ModelScoreConst* d_msc, const ModelConst* d_mc, const ChainArrays& ca, ScoreParams sp,
-                      const ChainDesc* d_all_chains /* indexed by contig_chains[].x */, const int2* d_contig_chains /* per contig: first chain, count */,
-                      const int32_t* d_node_contig_base, int n_contigs, int group_nodes, const unsigned* d_sd_lut, hipStream_t st,
-                      int reuse_raw_cscore = 0 /* 1: the chains read the raw coding scores another chain left (ChainDesc::raw_off): no ORF walk */,
-                      const double* d_gil = nullptr /* hexamer tables of the group's models, interleaved: [4096][il_stride] */, int il_stride = 0,
-                      const int32_t* d_rank = nullptr /* model -> column of d_gil */,
-                      const void* d_cs_tasks = nullptr, int n_cs_tasks = 0, const void* d_cs_entries = nullptr /* pga_cs_tasks: ORF walks from LDS tables */,
-                      const StopLaunch* stops = nullptr);
+// ---- node scoring of one translation-table group: three launchers, every choice of form made by the caller (FindCall::score_groups,
+//      rescore_winners in finder.hip; DESIGN.md "Run-time knobs").  Each takes the group's chains plus what only it reads.
+struct ScoreGroup {
+    const ChainDesc* d_chains = nullptr; int n_chains = 0; int64_t node_begin = 0, total = 0;      // the chains of the launch, contiguous in `off` from node_begin, and their nodes
+    const ChainDesc* d_all_chains = nullptr; const int2* d_contig_chains = nullptr;                // per contig of the group: first chain (an index into d_all_chains), count
+    const int32_t* d_node_contig_base = nullptr; int n_contigs = 0; int group_nodes = 0;
+    const uint8_t* d_dig = nullptr; const ContigDesc* d_ct = nullptr; const GroupArrays* ga = nullptr; const ChainArrays* ca = nullptr;
+    const pga_training* d_models = nullptr; hipStream_t st = nullptr;
+};
+// (the argument structs are built from the group and filled by name: a field that moves cannot change what a caller passes)
+struct CodingScoreLaunch : ScoreGroup {
+    explicit CodingScoreLaunch(const ScoreGroup& g) : ScoreGroup(g) {}
+    // lds_tasks: ORF walks from hexamer tables in LDS (k_coding_score_quads over the tasks of pga_cs_tasks); global_memory: k_coding_score
+    enum Form { lds_tasks, global_memory } form = global_memory;
+    const ModelScoreConst* d_msc = nullptr;
+    const double* d_gil = nullptr; int il_stride = 0; const int32_t* d_rank = nullptr;      // hexamer tables of the group's models, interleaved: [4096][il_stride]; model -> column
+    const void* d_cs_tasks = nullptr; int n_cs_tasks = 0; const void* d_cs_entries = nullptr;
+    int cs_wave = 0, qclasses = 0; bool profile = false;                                    // Knobs::cs_wave, cs_qclasses, cs_profile
+};
+struct StartScoreLaunch : ScoreGroup {
+    explicit StartScoreLaunch(const ScoreGroup& g) : ScoreGroup(g) {}
+    // model_major: a per-start prologue and a model-major pass over (chain, start) items (k_start_prologue, k_mm_*, k_score_starts_mm,
+    // k_clear_stops); listed_loop: the model loop of k_score_starts over ga->start_list (its workgroups clear the fields of the stop nodes
+    // between their start nodes at the end); all_nodes: the same kernel with a thread per node
+    enum Form { model_major, listed_loop, all_nodes } form = all_nodes;
+    ScoreParams sp{}; const unsigned* d_sd_lut = nullptr;
+    int32_t n_starts = 0, n_stops = 0; const int32_t* sbase = nullptr;      // entries of ga->start_list / ga->stop_list; per contig: first entry of ga->stop_list (n_contigs + 1)
+    // model_major: the context's buffers, sized by the caller
+    void* mm_rec = nullptr;                      // SsStartRec per start node of the group (n_starts)
+    void* mm_chain = nullptr;                    // SsMmChain per chain of the launch (n_chains)
+    void* mm_tile = nullptr;                     // SsMmTile per tile (mm_tiles)
+    void* mm_scratch = nullptr;                  // pga_mm_scratch_bytes(n_models, n_chains)
+    int32_t mm_tiles = 0; int mm_tile_items = 0; // pga_mm_tiles(.., mm_tile_items, ..): the one value sizes the tiles and launches them
+    bool profile = false;                        // Knobs::ss_profile
+};
+struct OverlapLaunch : ScoreGroup {
+    explicit OverlapLaunch(const ScoreGroup& g) : ScoreGroup(g) {}
+    // stop_pairs: over (chain, stop node) pairs (k_ovl_topo, k_ovl_stops); every_node: k_overlapping_starts (the re-score)
+    enum Form { stop_pairs, every_node } form = every_node;
+    const ModelConst* d_mc = nullptr; int32_t max_overlap = 0;
+    const int32_t* sbase = nullptr; int64_t soff_begin = 0, n_pairs = 0; int32_t n_stops = 0;      // ChainDesc::soff of the launch's first chain; (chain, stop) pairs of its chains
+    // the wave-batch scorer's 64-byte extras of every stop node, built in the same pass (ext nullptr: not wanted), from cs_out = cscore + sscore
+    const int32_t* topo_q2 = nullptr; void* ext = nullptr; const double* cs_out = nullptr;
+    // star_ptr of the nodes that are no stop nodes is -1: the launcher fills the chains' range first -- unless nobody will read it
+    // (the wave-batch scorer takes the extras, the tail asks for stop nodes only, the caller does not want the node arrays)
+    bool fill_star_ptr = true;
+    // per workgroup of k_ovl_stops (256 pairs from soff_begin on): the chain of its first pair, relative to the launch's first chain
+    // (the caller's plan; nullptr, Knobs::ovl_search: the workgroup searches)
+    const int32_t* blk_chain = nullptr;
+};
+void pga_launch_coding_score(const CodingScoreLaunch& a);
+// false, and nothing launched: the form the caller chose lacks its list or its buffers
+bool pga_launch_start_scores(const StartScoreLaunch& a);
+void pga_launch_overlapping_starts(const OverlapLaunch& a);
 // host: the tasks of the LDS form of the coding score for one group (pipeline.hip); false = models are not neighbours in the table
 bool pga_cs_tasks(const int2* h_cc, int n_contigs, const ChainDesc* h_chains, const int32_t* h_cbase, const int32_t* model_rank, int task_nodes,
                   std::vector<int32_t>& tasks, std::vector<int32_t>& entries);

@@ -1564,7 +1564,7 @@ constexpr int CS_TASK_MAX_CUTS = 64;
 // what the walks of a task need of one of its entries, staged in LDS once (a stop node then costs one round trip, not four)
 struct CsEnt { int64_t base; int32_t len, tbase, ccx, ccy, m0, first, tile0, _pad; };
 constexpr int CS_CLASSES = 12;                         // ORF length classes of a round
-constexpr int CS_WAVE = 2048;                          // ORFs longer than this take a whole wave (orf_wave); the others walk 64 to a wave
+// (cs_wave, Knobs::cs_wave, 2048: ORFs longer than this take a whole wave (orf_wave); the others walk 64 to a wave)
 __global__ void __launch_bounds__(CS_TASK_THREADS)
 k_coding_score_quads(const CsTask* __restrict__ tasks, const CsEntry* __restrict__ entries, const ChainDesc* __restrict__ chains,
                      const int2* __restrict__ contig_chains, const int32_t* __restrict__ node_contig_base,
@@ -2304,7 +2304,7 @@ static_assert(sizeof(SsMmTile) == PGA_SS_MMTILE_BYTES, "SsMmTile");
 constexpr unsigned long long SS_ITEM_MASK = (1ull << 40) - 1ull;
 // a model's counter of k_mm_count on a 128-byte line of its own: sixteen counters on two lines serialised 26 000 atomics (41 us per launch)
 constexpr int SS_CNT_STRIDE = 16;
-constexpr int SS_TILE_DEFAULT = 1024;      // items per tile (PGA_SS_MM_TILE: 256 / 512 / 1024)
+// (items per tile: Knobs::ss_mm_tile, 1024 -- or 256 / 512)
 
 // The start scorer's model, one per workgroup: the RBS table (SD models) or the small motif tables (the others), never both
 struct StartModelMm {
@@ -2906,7 +2906,7 @@ __global__ void __launch_bounds__(256)
 k_ovl_stops(const ChainDesc* __restrict__ chains, int n_chains, int64_t soff_begin, int64_t n_pairs, GroupArrays ga,
             const int32_t* __restrict__ cbase, const int32_t* __restrict__ sbase, const ModelConst* __restrict__ mcs, ChainArrays ca, int maxov,
             const int32_t* __restrict__ topo_q2, DpwExt* __restrict__ ext, const double* __restrict__ css /* or nullptr: cscore + sscore per chain node */,
-            const int32_t* __restrict__ blk_chain /* or nullptr: the chain of every workgroup's first pair (StopLaunch::blk_chain) */) {
+            const int32_t* __restrict__ blk_chain /* or nullptr: the chain of every workgroup's first pair (OverlapLaunch::blk_chain) */) {
     __shared__ int s_c0;
     const int64_t blk0 = soff_begin + (int64_t)blockIdx.x * blockDim.x;
     const int64_t p = blk0 + threadIdx.x;
@@ -3337,15 +3337,8 @@ void pga_launch_sd_lut(unsigned* d_lut, hipStream_t st) {
 }
 
 // Tiles of the model-major start scoring (k_mm_scan lays them out the same way): per model, its items -- the start nodes of the
-// contigs of its chains -- in runs of pga_mm_tile_items().  `items` is the caller's scratch.
-int pga_mm_tile_items() {
-    // PGA_SS_MM_TILE: items (threads) per workgroup of k_score_starts_mm
-    const char* e = getenv("PGA_SS_MM_TILE");
-    const int v = e ? atoi(e) : 0;
-    return v == 256 || v == 512 || v == 1024 ? v : SS_TILE_DEFAULT;
-}
-int32_t pga_mm_tiles(const ChainDesc* h_chains, int n_chains, const int32_t* h_cbase, const int32_t* h_sbase, int n_models, std::vector<int64_t>& items) {
-    const int tile = pga_mm_tile_items();
+// contigs of its chains -- in runs of `tile` (Knobs::ss_mm_tile).  `items` is the caller's scratch.
+int32_t pga_mm_tiles(const ChainDesc* h_chains, int n_chains, const int32_t* h_cbase, const int32_t* h_sbase, int n_models, int tile, std::vector<int64_t>& items) {
     items.assign((size_t)n_models, 0);
     for (int k = 0; k < n_chains; k++) {
         const int c = h_chains[k].contig;
@@ -3359,122 +3352,118 @@ size_t pga_mm_scratch_bytes(int n_models, int n_chains) {
     return sizeof(unsigned long long) * SS_CNT_STRIDE * (size_t)n_models + sizeof(int32_t) * (((size_t)3 * n_models + 1) & ~(size_t)1) + sizeof(int2) * (size_t)n_chains + 64;
 }
 
-void pga_launch_score(const ChainDesc* d_chains, int n_chains, int64_t node_begin, int64_t total, const uint8_t* d_dig,
-                      const ContigDesc* d_ct, const GroupArrays& ga, const pga_training* d_models,
-                      const ModelScoreConst* d_msc, const ModelConst* d_mc, const ChainArrays& ca, ScoreParams sp,
-                      const ChainDesc* d_all_chains, const int2* d_contig_chains, const int32_t* d_node_contig_base, int n_contigs,
-                      int group_nodes, const unsigned* d_sd_lut, hipStream_t st, int reuse_raw_cscore, const double* d_gil, int il_stride,
-                      const int32_t* d_rank, const void* d_cs_tasks, int n_cs_tasks, const void* d_cs_entries, const StopLaunch* stops) {
-    if (total <= 0 || n_chains <= 0) return;
-    const dim3 grid(nblocks(total, 256)), blk(256);
-    if (group_nodes > 0 && !reuse_raw_cscore && n_cs_tasks > 0) {
+// PGA_CS_PROFILE / PGA_SS_PROFILE (synchronising debug aids): sixteen wave-cycle counters per kind and device, allocated once and
+// cleared on the stream in front of a launch; profile_read waits for the launch and brings them home.
+// (allocations belong to ONE device: they are keyed by the device that is current -- contexts of several GPUs may live in one process)
+enum ProfileKind { PROF_CS, PROF_SS };
+static unsigned long long* profile_begin(const ProfileKind kind, hipStream_t st) {
+    static std::atomic<unsigned long long*> prof_of[2][64];
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    dev &= 63;
+    unsigned long long* d_prof = prof_of[kind][dev].load();
+    if (!d_prof) { (void)hipMalloc((void**)&d_prof, 16 * sizeof(unsigned long long)); prof_of[kind][dev].store(d_prof); }
+    (void)hipMemsetAsync(d_prof, 0, 16 * sizeof(unsigned long long), st);
+    return d_prof;
+}
+static void profile_read(const unsigned long long* d_prof, hipStream_t st, unsigned long long (&h)[16]) {
+    (void)hipStreamSynchronize(st);
+    (void)hipMemcpy(h, d_prof, sizeof h, hipMemcpyDeviceToHost);
+}
+
+void pga_launch_coding_score(const CodingScoreLaunch& a) {
+    if (a.total <= 0 || a.n_chains <= 0 || a.group_nodes <= 0) return;
+    if (a.form == CodingScoreLaunch::lds_tasks) {
         // the ORF walks against hexamer tables in LDS (tasks built by the caller, pga_cs_tasks)
-        // function attributes and allocations belong to ONE device: both are keyed by the device that is current
-        // (contexts of several GPUs may live in one process)
+        // (function attributes belong to ONE device, like the profile buffers above)
         static std::atomic<bool> attr_set[64];
-        static std::atomic<unsigned long long*> prof_of[64];
         int dev = 0;
         (void)hipGetDevice(&dev);
         dev &= 63;
         const size_t lds = sizeof(double) * 4096 * 4;
-        int cs_wave = CS_WAVE;
-        if (const char* e = getenv("PGA_CS_WAVE")) cs_wave = atoi(e) >= 64 ? atoi(e) : CS_WAVE;
         if (!attr_set[dev].load()) {
             hipFuncSetAttribute((const void*)k_coding_score_quads, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
             attr_set[dev].store(true);
         }
-        const bool profiling = getenv("PGA_CS_PROFILE") != nullptr;
-        unsigned long long* d_prof = prof_of[dev].load();
-        if (profiling) {
-            if (!d_prof) { (void)hipMalloc((void**)&d_prof, 16 * sizeof(unsigned long long)); prof_of[dev].store(d_prof); }
-            (void)hipMemsetAsync(d_prof, 0, 16 * sizeof(unsigned long long), st);
-        }
-        hipLaunchKernelGGL(k_coding_score_quads, dim3((unsigned)n_cs_tasks), dim3(CS_TASK_THREADS), lds, st, (const CsTask*)d_cs_tasks,
-                           (const CsEntry*)d_cs_entries, d_all_chains, d_contig_chains, d_node_contig_base, d_dig, d_ct, ga, d_models, d_msc, ca,
-                           d_gil, il_stride, d_rank, cs_wave, profiling ? d_prof : nullptr, (getenv("PGA_CS_QCLASSES") && atoi(getenv("PGA_CS_QCLASSES")) == 4) ? 4 : 3);
-        if (profiling) {
+        unsigned long long* const d_prof = a.profile ? profile_begin(PROF_CS, a.st) : nullptr;
+        hipLaunchKernelGGL(k_coding_score_quads, dim3((unsigned)a.n_cs_tasks), dim3(CS_TASK_THREADS), lds, a.st, (const CsTask*)a.d_cs_tasks,
+                           (const CsEntry*)a.d_cs_entries, a.d_all_chains, a.d_contig_chains, a.d_node_contig_base, a.d_dig, a.d_ct, *a.ga, a.d_models, a.d_msc, *a.ca,
+                           a.d_gil, a.il_stride, a.d_rank, a.cs_wave, d_prof, a.qclasses);
+        if (a.profile) {
             unsigned long long h[16];
-            (void)hipStreamSynchronize(st);
-            (void)hipMemcpy(h, d_prof, sizeof h, hipMemcpyDeviceToHost);
+            profile_read(d_prof, a.st, h);
             fprintf(stderr, "[pga cs-profile] %d tasks (%llu workgroups, %llu batches of 64): wave-cycles  stage %.3g  list %.3g  one-wave ORFs %.3g  "
                             "four-to-a-wave %.3g  64-to-a-wave %.3g (lookup %.3g  first loads %.3g  walk %.3g  penalties %.3g)  end barrier %.3g\n",
-                    n_cs_tasks, h[7], h[8], (double)h[0], (double)h[1], (double)h[2], (double)h[3], (double)h[4], (double)h[9], (double)h[10], (double)h[11],
+                    a.n_cs_tasks, h[7], h[8], (double)h[0], (double)h[1], (double)h[2], (double)h[3], (double)h[4], (double)h[9], (double)h[10], (double)h[11],
                     (double)h[12], (double)h[5]);
         }
-        reuse_raw_cscore = 1;           // done: skip the global-memory form below
+    } else
+        hipLaunchKernelGGL(k_coding_score, dim3(nblocks(a.group_nodes, 256)), dim3(256), 0, a.st, a.d_all_chains, a.d_contig_chains, a.d_node_contig_base,
+                           a.n_contigs, 0, a.group_nodes, a.d_dig, a.d_ct, *a.ga, a.d_models, a.d_msc, *a.ca, a.d_gil, a.il_stride, a.d_rank);
+}
+
+bool pga_launch_start_scores(const StartScoreLaunch& a) {
+    if (a.total <= 0 || a.n_chains <= 0 || a.group_nodes <= 0) return true;
+    const dim3 blk(256);
+    const bool mm = a.form == StartScoreLaunch::model_major, listed = a.form != StartScoreLaunch::all_nodes;
+    // (the caller decides; what it decided must have its list and its buffers)
+    if (listed && a.ga->start_list == nullptr) return false;
+    if (mm && (a.n_starts <= 0 || a.mm_tiles <= 0 || !a.mm_rec || !a.mm_chain || !a.mm_tile || !a.mm_scratch)) return false;
+    ScoreParams sp = a.sp;
+    if (a.profile) sp.prof = profile_begin(PROF_SS, a.st);
+    // (a fifth wavefront per SIMD costs 96 bytes of scratch per lane and 10 % of the kernel's time: four)
+    const int n_items = listed ? a.n_starts : a.group_nodes;
+    // the listed launches: prologue, model-major order, scoring, the stop nodes' zeros (listed_loop: the model loop of k_score_starts over the list)
+    if (mm) {
+        const int nm = sp.n_models, tile = a.mm_tile_items;
+        unsigned long long* const d_cnt = (unsigned long long*)a.mm_scratch;
+        int32_t* const d_base = (int32_t*)(d_cnt + (size_t)SS_CNT_STRIDE * nm);
+        int2* const d_slot = (int2*)(d_base + (((size_t)3 * nm + 1) & ~(size_t)1));
+        (void)hipMemsetAsync(d_cnt, 0, sizeof(unsigned long long) * SS_CNT_STRIDE * (size_t)nm, a.st);
+        hipLaunchKernelGGL(k_start_prologue, dim3(nblocks(n_items, 256)), blk, 0, a.st, a.d_contig_chains, a.d_node_contig_base, a.n_contigs, a.d_dig, a.d_ct, *a.ga, sp,
+                           (const int32_t*)a.ga->start_list, n_items, (SsStartRec*)a.mm_rec);
+        hipLaunchKernelGGL(k_mm_count, dim3(nblocks(a.n_chains, 256)), blk, 0, a.st, a.d_chains, a.n_chains, a.d_node_contig_base, a.sbase, nm, d_cnt, d_slot);
+        hipLaunchKernelGGL(k_mm_scan, dim3(1), blk, 0, a.st, (const unsigned long long*)d_cnt, nm, tile, d_base);
+        hipLaunchKernelGGL(k_mm_place, dim3(nblocks(a.n_chains, 256)), blk, 0, a.st, a.d_chains, a.n_chains, a.d_node_contig_base, a.sbase, a.d_ct,
+                           (const unsigned long long*)d_cnt, (const int2*)d_slot, (const int32_t*)d_base, nm, tile, a.d_models, (SsMmChain*)a.mm_chain, (SsMmTile*)a.mm_tile);
+        const SsMmTile* const d_tl = (const SsMmTile*)a.mm_tile; const SsMmChain* const d_mc = (const SsMmChain*)a.mm_chain;
+        const SsStartRec* const d_rec = (const SsStartRec*)a.mm_rec;
+        const dim3 grid_mm((unsigned)a.mm_tiles);
+        if (tile == 1024) hipLaunchKernelGGL(k_score_starts_mm<1024>, grid_mm, dim3(1024), 0, a.st, d_tl, d_mc, d_rec, a.d_models, *a.ca, sp, a.d_sd_lut);
+        else if (tile == 512) hipLaunchKernelGGL(k_score_starts_mm<512>, grid_mm, dim3(512), 0, a.st, d_tl, d_mc, d_rec, a.d_models, *a.ca, sp, a.d_sd_lut);
+        else hipLaunchKernelGGL(k_score_starts_mm<256>, grid_mm, blk, 0, a.st, d_tl, d_mc, d_rec, a.d_models, *a.ca, sp, a.d_sd_lut);
+        if (a.n_stops > 0)
+            hipLaunchKernelGGL(k_clear_stops, dim3(nblocks(a.n_stops, 256)), blk, 0, a.st, a.d_all_chains, a.d_contig_chains, a.d_node_contig_base, *a.ga, *a.ca, sp,
+                               a.n_stops);
+    } else if (n_items > 0)
+        hipLaunchKernelGGL(k_score_starts<4>, dim3(nblocks(n_items, 256)), blk, 0, a.st, a.d_all_chains, a.d_contig_chains, a.d_node_contig_base, a.n_contigs,
+                           a.group_nodes, a.d_dig, a.d_ct, *a.ga, a.d_models, *a.ca, sp, a.d_sd_lut, listed ? (const int32_t*)a.ga->start_list : (const int32_t*)nullptr, n_items);
+    if (!a.profile) return true;
+    unsigned long long h[16];
+    profile_read(sp.prof, a.st, h);
+    if (mm)
+        fprintf(stderr, "[pga ss-profile] model-major, %d starts, %d tiles: wave-cycles  stage %.3g  chain + record %.3g  upstream + RBS / motif search %.3g  "
+                        "scores %.3g  stores %.3g\n", n_items, a.mm_tiles, (double)h[0], (double)h[1], (double)h[2], (double)h[3], (double)h[4]);
+    else
+        fprintf(stderr, "[pga ss-profile] %d nodes: wave-cycles  locate %.3g  node + upstream window %.3g  barrier + edge scan %.3g | per model: next model %.3g  "
+                        "chain %.3g  upstream + RBS / motif search %.3g  scores %.3g  finish + stores (slot 8) %.3g  stage %.3g  barrier %.3g (slot 7 unused %.3g)\n",
+                a.group_nodes, (double)h[0], (double)h[1], (double)h[2], (double)h[3], (double)h[4], (double)h[5], (double)h[6], (double)h[8],
+                (double)h[9], (double)h[10], (double)h[7]);
+    return true;
+}
+
+void pga_launch_overlapping_starts(const OverlapLaunch& a) {
+    if (a.total <= 0 || a.n_chains <= 0) return;
+    const dim3 blk(256);
+    if (a.form == OverlapLaunch::every_node) {
+        hipLaunchKernelGGL(k_overlapping_starts, dim3(nblocks(a.total, 256)), blk, 0, a.st, a.d_chains, a.n_chains, a.node_begin, a.total, *a.ga, a.d_mc, *a.ca, a.max_overlap);
+        return;
     }
-    // the raw coding score of a start depends on the model only, not on which model of the group was scored first on the
-    // contig: the fresh re-score of a winning model (ref: lib.pyx:5380-5394) reads it where the winning pass left it
-    // (ChainDesc::raw_off) instead of walking every ORF again
-    if (group_nodes > 0 && !reuse_raw_cscore)
-        hipLaunchKernelGGL(k_coding_score, dim3(nblocks(group_nodes, 256)), blk, 0, st, d_all_chains, d_contig_chains, d_node_contig_base,
-                           n_contigs, 0, group_nodes, d_dig, d_ct, ga, d_models, d_msc, ca, d_gil, il_stride, d_rank);
-    if (group_nodes > 0) {
-        if (const char* e = getenv("PGA_SS_MODELS_PER_PASS")) { const int v = atoi(e); if (v >= 1 && v <= 512) sp.models_per_pass = v; }
-        // PGA_SS_PROFILE=1: wave-cycles per phase of the start scorer (a synchronising debug aid)
-        static std::atomic<unsigned long long*> ss_prof_of[64];
-        const bool ss_profiling = getenv("PGA_SS_PROFILE") != nullptr;
-        if (ss_profiling) {
-            int dev = 0; (void)hipGetDevice(&dev); dev &= 63;
-            unsigned long long* d_prof = ss_prof_of[dev].load();
-            if (!d_prof) { (void)hipMalloc((void**)&d_prof, 16 * sizeof(unsigned long long)); ss_prof_of[dev].store(d_prof); }
-            (void)hipMemsetAsync(d_prof, 0, 16 * sizeof(unsigned long long), st);
-            sp.prof = d_prof;
-        }
-        // (a fifth wavefront per SIMD costs 96 bytes of scratch per lane and 10 % of the kernel's time: four)
-        const bool listed = stops != nullptr && stops->starts_only && ga.start_list != nullptr;
-        const int n_items = listed ? stops->n_starts : group_nodes;
-        // the listed launches: prologue, model-major order, scoring, the stop nodes' zeros (PGA_SS_MM=0: the model loop)
-        const bool mm = listed && n_items > 0 && stops->mm_tiles > 0 && stops->mm_rec != nullptr && !(getenv("PGA_SS_MM") && atoi(getenv("PGA_SS_MM")) == 0);
-        if (mm) {
-            const int nm = sp.n_models;
-            unsigned long long* const d_cnt = (unsigned long long*)stops->mm_scratch;
-            int32_t* const d_base = (int32_t*)(d_cnt + (size_t)SS_CNT_STRIDE * nm);
-            int2* const d_slot = (int2*)(d_base + (((size_t)3 * nm + 1) & ~(size_t)1));
-            (void)hipMemsetAsync(d_cnt, 0, sizeof(unsigned long long) * SS_CNT_STRIDE * (size_t)nm, st);
-            hipLaunchKernelGGL(k_start_prologue, dim3(nblocks(n_items, 256)), blk, 0, st, d_contig_chains, d_node_contig_base, n_contigs, d_dig, d_ct, ga, sp,
-                               (const int32_t*)ga.start_list, n_items, (SsStartRec*)stops->mm_rec);
-            hipLaunchKernelGGL(k_mm_count, dim3(nblocks(n_chains, 256)), blk, 0, st, d_chains, n_chains, d_node_contig_base, stops->sbase, nm, d_cnt, d_slot);
-            const int tile = pga_mm_tile_items();
-            hipLaunchKernelGGL(k_mm_scan, dim3(1), blk, 0, st, (const unsigned long long*)d_cnt, nm, tile, d_base);
-            hipLaunchKernelGGL(k_mm_place, dim3(nblocks(n_chains, 256)), blk, 0, st, d_chains, n_chains, d_node_contig_base, stops->sbase, d_ct,
-                               (const unsigned long long*)d_cnt, (const int2*)d_slot, (const int32_t*)d_base, nm, tile, d_models, (SsMmChain*)stops->mm_chain, (SsMmTile*)stops->mm_tile);
-            const SsMmTile* const d_tl = (const SsMmTile*)stops->mm_tile; const SsMmChain* const d_mc = (const SsMmChain*)stops->mm_chain;
-            const SsStartRec* const d_rec = (const SsStartRec*)stops->mm_rec;
-            const dim3 grid_mm((unsigned)stops->mm_tiles);
-            if (tile == 1024) hipLaunchKernelGGL(k_score_starts_mm<1024>, grid_mm, dim3(1024), 0, st, d_tl, d_mc, d_rec, d_models, ca, sp, d_sd_lut);
-            else if (tile == 512) hipLaunchKernelGGL(k_score_starts_mm<512>, grid_mm, dim3(512), 0, st, d_tl, d_mc, d_rec, d_models, ca, sp, d_sd_lut);
-            else hipLaunchKernelGGL(k_score_starts_mm<256>, grid_mm, blk, 0, st, d_tl, d_mc, d_rec, d_models, ca, sp, d_sd_lut);
-            if (stops->n_stops > 0)
-                hipLaunchKernelGGL(k_clear_stops, dim3(nblocks(stops->n_stops, 256)), blk, 0, st, d_all_chains, d_contig_chains, d_node_contig_base, ga, ca, sp,
-                                   stops->n_stops);
-        } else if (n_items > 0)
-            hipLaunchKernelGGL(k_score_starts<4>, dim3(nblocks(n_items, 256)), blk, 0, st, d_all_chains, d_contig_chains, d_node_contig_base, n_contigs,
-                               group_nodes, d_dig, d_ct, ga, d_models, ca, sp, d_sd_lut, listed ? (const int32_t*)ga.start_list : (const int32_t*)nullptr, n_items);
-        if (ss_profiling && mm) {
-            unsigned long long h[16];
-            (void)hipStreamSynchronize(st);
-            (void)hipMemcpy(h, sp.prof, sizeof h, hipMemcpyDeviceToHost);
-            fprintf(stderr, "[pga ss-profile] model-major, %d starts, %d tiles: wave-cycles  stage %.3g  chain + record %.3g  upstream + RBS / motif search %.3g  "
-                            "scores %.3g  stores %.3g\n", n_items, stops->mm_tiles, (double)h[0], (double)h[1], (double)h[2], (double)h[3], (double)h[4]);
-        } else if (ss_profiling) {
-            unsigned long long h[16];
-            (void)hipStreamSynchronize(st);
-            (void)hipMemcpy(h, sp.prof, sizeof h, hipMemcpyDeviceToHost);
-            fprintf(stderr, "[pga ss-profile] %d nodes: wave-cycles  locate %.3g  node + upstream window %.3g  barrier + edge scan %.3g | per model: next model %.3g  "
-                            "chain %.3g  upstream + RBS / motif search %.3g  scores %.3g  finish + stores (slot 8) %.3g  stage %.3g  barrier %.3g (slot 7 unused %.3g)\n",
-                    group_nodes, (double)h[0], (double)h[1], (double)h[2], (double)h[3], (double)h[4], (double)h[5], (double)h[6], (double)h[8],
-                    (double)h[9], (double)h[10], (double)h[7]);
-        }
-    }
-    if (stops != nullptr) {
-        if (stops->fill_star_ptr) (void)hipMemsetAsync(ca.star_ptr + 3 * node_begin, 0xff, sizeof(int32_t) * 3 * (size_t)total, st);
-        if (stops->n_pairs > 0 && stops->n_stops > 0)
-            hipLaunchKernelGGL(k_ovl_topo, dim3(nblocks(stops->n_stops, 256)), blk, 0, st, ga, d_node_contig_base, stops->sbase, n_contigs, stops->n_stops,
-                               sp.max_overlap);
-        if (stops->n_pairs > 0)
-            hipLaunchKernelGGL(k_ovl_stops, dim3(nblocks(stops->n_pairs, 256)), blk, 0, st, d_chains, n_chains, stops->soff_begin, stops->n_pairs, ga,
-                               d_node_contig_base, stops->sbase, d_mc, ca, sp.max_overlap, stops->topo_q2, (DpwExt*)stops->ext,
-                               stops->ext != nullptr ? (const double*)sp.cs_out : nullptr, getenv("PGA_OVL_SEARCH") ? nullptr : stops->blk_chain);
-    } else hipLaunchKernelGGL(k_overlapping_starts, grid, blk, 0, st, d_chains, n_chains, node_begin, total, ga, d_mc, ca, sp.max_overlap);
+    if (a.fill_star_ptr) (void)hipMemsetAsync(a.ca->star_ptr + 3 * a.node_begin, 0xff, sizeof(int32_t) * 3 * (size_t)a.total, a.st);
+    if (a.n_pairs > 0 && a.n_stops > 0)
+        hipLaunchKernelGGL(k_ovl_topo, dim3(nblocks(a.n_stops, 256)), blk, 0, a.st, *a.ga, a.d_node_contig_base, a.sbase, a.n_contigs, a.n_stops, a.max_overlap);
+    if (a.n_pairs > 0)
+        hipLaunchKernelGGL(k_ovl_stops, dim3(nblocks(a.n_pairs, 256)), blk, 0, a.st, a.d_chains, a.n_chains, a.soff_begin, a.n_pairs, *a.ga,
+                           a.d_node_contig_base, a.sbase, a.d_mc, *a.ca, a.max_overlap, a.topo_q2, (DpwExt*)a.ext,
+                           a.ext != nullptr ? a.cs_out : nullptr, a.blk_chain);
 }

@@ -417,7 +417,7 @@ void tr_build_coverage_map(const unsigned int* real /* [4][4][4096] */, int* goo
 // ref: lib.pyx:5236-5279 (GeneFinder._train) for every sequence of the batch at once: sequence g is genome g (the host layer
 // joins the contigs of a genome with the reference's spacer), trained with tts[g], sws[g], fns[g].  One device pass per stage or
 // round for all genomes; status[g] is PGA_OK or what a single-genome training would have returned.
-static int train_body(pga_ctx* c, const pga_batch* batch, const pga_params* pp, const int32_t* tts, const double* sws, const int32_t* fns,
+static int train_body(const Knobs& kn, pga_ctx* c, const pga_batch* batch, const pga_params* pp, const int32_t* tts, const double* sws, const int32_t* fns,
                       int upto, pga_training* out, int32_t* status, bool& models_replaced) {
     if (!c || !batch || !pp || !out || !status || !tts || !sws || !fns || batch->ctx != c || batch->n < 1) {
         if (c) c->err = "pga_train_batch: bad arguments";
@@ -439,7 +439,7 @@ static int train_body(pga_ctx* c, const pga_batch* batch, const pga_params* pp, 
     hipStream_t st = c->stream;
     // ---- nodes (ref: lib.pyx:5252-5257): extraction + sort of every genome under its own table, through the stage-level path
     pga_result* r1 = nullptr;
-    if (int rc = find_impl(c, batch, &P, PGA_STAGE_EXTRACT, tts[0], &r1, nullptr, tts)) return rc;
+    if (int rc = find_impl(kn, c, batch, &P, PGA_STAGE_EXTRACT, tts[0], &r1, nullptr, tts)) return rc;
     struct Free { pga_result* r; ~Free() { if (r) pga_result_free(r); } } fr1{r1};
     FinderState* f = c->finder;
     const uint8_t* d_dig = f->last.d_dig;            // the batch's digits, genome g at ct[g].base
@@ -522,7 +522,7 @@ static int train_body(pga_ctx* c, const pga_batch* batch, const pga_params* pp, 
     HT(c, hipMemcpyAsync(d_mc, mcv.data(), sizeof(ModelConst) * G, hipMemcpyHostToDevice, st));
     NodeArrays na{d_ndx, d_sv, d_type, d_strand, d_gcb, d_gcb, d_gcb, d_gcb, d_star, d_gcb};   // scores are not read when final = 0
     pga_launch_dp_prepare(d_chain, G, 0, N, na, d_mc, dp, st, 0);
-    pga_launch_dp(d_chain, G, d_mc, dp, 0, st);
+    pga_launch_dp(kn, d_chain, G, d_mc, dp, 0, st);
     std::vector<int32_t> traceb((size_t)N), tracef((size_t)N, -1), star((size_t)3 * N), path((size_t)N + 1), mx((size_t)G, -1);
     std::vector<int8_t> ovm((size_t)N);
     std::vector<uint8_t> elim((size_t)N, 0);
@@ -580,7 +580,7 @@ static int train_body(pga_ctx* c, const pga_batch* batch, const pga_params* pp, 
     std::vector<int32_t> moc((size_t)G);
     for (int g = 0; g < G; g++) moc[g] = g;
     pga_result* r2 = nullptr;
-    if (int rc = find_impl(c, batch, &P, PGA_STAGE_SCORE, tts[0], &r2, moc.data(), nullptr)) return rc;
+    if (int rc = find_impl(kn, c, batch, &P, PGA_STAGE_SCORE, tts[0], &r2, moc.data(), nullptr)) return rc;
     Free fr2{r2};
     f = c->finder;
     d_dig = f->last.d_dig;
@@ -747,10 +747,11 @@ static int train_body(pga_ctx* c, const pga_batch* batch, const pga_params* pp, 
 static int train_impl(pga_ctx* c, const pga_batch* batch, const pga_params* pp, const int32_t* tts, const double* sws, const int32_t* fns,
                       int upto, pga_training* out, int32_t* status) {
     if (!c) return PGA_EINVAL;
+    const Knobs kn = read_knobs();      // once for the whole training call, its two finder passes included
     c->dev_nodes.clear();               // training runs the finder: it reuses the node arena of the last find
     const std::vector<pga_training> saved = c->models;
     bool replaced = false;
-    const int rc = train_body(c, batch, pp, tts, sws, fns, upto, out, status, replaced);
+    const int rc = train_body(kn, c, batch, pp, tts, sws, fns, upto, out, status, replaced);
     if (replaced) {
         const std::string err = c->err;
         std::vector<const pga_training*> ptrs;

@@ -333,6 +333,7 @@ extern "C" int pga_kmer_counts_chunk(void) { return kCntChunk; }
 extern "C" int pga_count_kmers(pga_ctx* c, const pga_batch* batch, int64_t n_genes, const pga_gene* genes, const pga_count_opts* o, void* d_out,
                                int64_t n_out_elems, void* stream, int64_t* win_out) {
     if (!c) return PGA_EINVAL;
+    const Knobs kn = read_knobs();
     RowDest d{c, "pga_count_kmers"};
     if (!batch || !o || n_genes < 0 || n_out_elems < 0) return d.bad("bad arguments");
     const pga_batch_view bv = pga_batch_peek(batch);
@@ -406,10 +407,8 @@ extern "C" int pga_count_kmers(pga_ctx* c, const pga_batch* batch, int64_t n_gen
     // many bins; a piece per wave where the pieces are short and four histograms fit
     bool direct = summed && pieces > 0 && total_win / pieces < n_bins / 4;
     bool per_wave = pieces > 0 && total_win / pieces <= kCntSweep;
-    if (const char* e = getenv("PGA_KMER_COUNTS_FORM")) {
-        if (strstr(e, "direct")) direct = true; else if (strstr(e, "lds")) direct = false;
-        if (strstr(e, "wave")) per_wave = true; else if (strstr(e, "group")) per_wave = false;
-    }
+    if (kn.kmer_direct >= 0) direct = kn.kmer_direct != 0;
+    if (kn.kmer_per_wave >= 0) per_wave = kn.kmer_per_wave != 0;
     if (!direct && 4 * n_bins > kCntMaxBins) per_wave = false;
     std::vector<int32_t> zero;
     if (summed || direct) { zero.resize((size_t)R); std::iota(zero.begin(), zero.end(), 0); for (auto& w : rows) w.bits |= 2u; }
@@ -449,6 +448,7 @@ extern "C" int pga_group_proteins(pga_ctx* c, const pga_batch* batch, int64_t n_
                                   const pga_group_opts* o, int64_t* d_group, int64_t* d_representative, int64_t* d_size, int64_t* d_digest,
                                   int64_t capacity, void* stream, int64_t* n_groups) {
     if (!c) return PGA_EINVAL;
+    const Knobs kn = read_knobs();
     DevCall d{c, "pga_group_proteins"};
     if (!batch || !o || !n_groups || n_genes < 0 || (n_genes > 0 && !genes)) return d.bad("bad arguments");
     const pga_batch_view bv = pga_batch_peek(batch);
@@ -465,13 +465,8 @@ extern "C" int pga_group_proteins(pga_ctx* c, const pga_batch* batch, int64_t n_
         if (const int rc = d.tables_known(bv, table_of_contig)) return rc;
     }
     for (int64_t g = 0; g < n_genes; g++) if (const int rc = d.record_inside(bv, genes[g], g)) return rc;
-    int key_bits = 61;
-    if (const char* e = getenv("PGA_PROTEIN_GROUPS_KEY_BITS")) {
-        char* end = nullptr;
-        const long k = strtol(e, &end, 10);
-        if (end == e || *end || k < 1 || k > 61) return d.bad(std::string("PGA_PROTEIN_GROUPS_KEY_BITS must be 1 .. 61, not \"") + e + "\"");
-        key_bits = (int)k;
-    }
+    const int key_bits = kn.protein_groups_key_bits;
+    if (key_bits == 0) return d.bad("PGA_PROTEIN_GROUPS_KEY_BITS must be a number, 1 .. 61");
     c->group_stats[0] = c->group_stats[1] = 0;
     if (n_genes == 0) { *n_groups = 0; return PGA_OK; }
     if (const int rc = d.destinations({{"d_group", d_group, 8, d.kRequired}, {"d_representative", d_representative, 8, d.kOptional},
