@@ -258,7 +258,9 @@ def seeded_regions(genome_len, genes, n=80, seed=11, spacing=25000, longest=2000
 
 
 def test_real_bases_under_a_mask(lib):
-    """There is no oracle for masked regions whose bases are known: the reference can only mask runs of N.  What must hold instead:
+    """The reference can only mask runs of N; the oracle for masked regions whose bases are known is tests/extract_ref.py, the sweep
+    restated with the mask list as an argument (tests/test_extract_shapes_gpu.py::test_named_regions_over_known_bases holds the
+    device against it, the boundary case of DESIGN.md 4.9 included).  What must hold on a whole genome, whatever the nodes are:
     no gene touches a region, the calls change, nothing else in the batch changes, the sequence statistics and the printed letters
     are those of the unmasked input, and lower-casing the regions is the same as naming them."""
     genome = read_fasta("GCF_001457455.1_NCTC11397_genomic.fna.gz")[0][1].upper().encode()
