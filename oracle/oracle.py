@@ -29,6 +29,11 @@ NODE_DTYPE = np.dtype(
     align=True,
 )
 DP_EVENTS = ("ties", "zero_joins", "frame_ties", "best_end_ties", "ovl_ties", "joins")   # order of PO_EV_* in prodigal_oracle.h
+DP_EDGES = ("fs_fb", "rb_rs", "fs_rs", "fb_fs", "rs_rb", "fs_fs", "fs_fs_star", "rs_rs", "rs_rs_star", "fs_rb_apart", "fs_rb_ovlp",
+            "fs_rb_half", "fs_rb_bnd", "tri_ovlp0", "tri_ovlp200", "tri_n3", "tri_traceb", "tri_no_traceb", "tri_best", "artifact",
+            "igm_adj2", "igm_adj1", "igm_far", "igm_ovl", "igm_oper", "igm_oper_ovl", "igm_quarter", "igm_quarter_ovl",
+            "ovl_f_skip", "ovl_f_maxov", "ovl_f_stopval", "ovl_r_skip", "ovl_r_maxov", "ovl_r_stopval", "ovl_edge_stop",
+            "ovl_best")                                                                   # order of PO_EDGE_* in prodigal_oracle.h
 GENE_DTYPE = np.dtype([("begin", "i4"), ("end", "i4"), ("start_ndx", "i4"), ("stop_ndx", "i4")])
 
 
@@ -80,6 +85,8 @@ def lib():
         L.po_dprog_raw.restype = None; L.po_dprog_raw.argtypes = [vp, vp, i32]
         L.po_find_max_index.restype = i32; L.po_find_max_index.argtypes = [vp]
         L.po_dp_events.restype = None; L.po_dp_events.argtypes = [vp, vp]
+        L.po_dp_edges.restype = None; L.po_dp_edges.argtypes = [vp, vp]
+        L.po_dp_window.restype = i32; L.po_dp_window.argtypes = [vp, i32, vp, vp]
         L.po_eliminate_bad_genes.argtypes = [vp, i32, vp]
         L.po_extract_genes.restype = i32; L.po_extract_genes.argtypes = [vp, i32]
         L.po_tweak_final_starts.argtypes = [vp, vp, i32]
@@ -228,6 +235,18 @@ class Oracle:
         out = np.zeros(len(DP_EVENTS), np.int64)
         self.L.po_dp_events(self.h, out.ctypes.data)
         return dict(zip(DP_EVENTS, (int(v) for v in out)))
+
+    def dp_edges(self):
+        """{comparison: (evaluated with lhs - rhs = -1, = 0, = +1)} of the last overlapping_starts / dprog_raw (po_dp_edges)."""
+        out = np.zeros((len(DP_EDGES), 3), np.int64)
+        self.L.po_dp_edges(self.h, out.ctypes.data)
+        return {k: tuple(int(v) for v in row) for k, row in zip(DP_EDGES, out)}
+
+    def dp_window(self, i):
+        """(first candidate source of target i, did the giant-ORF walk run, the node it landed on) of dprog_raw (po_dp_window)."""
+        walked, landed = ctypes.c_int(0), ctypes.c_int(0)
+        lo = self.L.po_dp_window(self.h, int(i), ctypes.byref(walked), ctypes.byref(landed))
+        return lo, bool(walked.value), landed.value
 
     def eliminate_bad_genes(self, ipath, tinf):
         self.L.po_eliminate_bad_genes(self.h, ipath, tinf.ptr)

@@ -39,6 +39,7 @@ struct po_ctx {
     int      ipath;
     double   path_score;
     int64_t  ev[PO_EV_COUNT];   /* events that the tie rules decided (po_dp_events); no result depends on them */
+    int64_t  edge[PO_EDGE_COUNT][3];   /* comparisons decided one below, at and one above their threshold (po_dp_edges); likewise */
 };
 
 /* ---------------------------------------------------------------- sequence */
@@ -107,6 +108,10 @@ po_gene* po_genes(po_ctx* c) { return c->gen; }
 double po_last_path_score(const po_ctx* c) { return c->path_score; }
 int po_last_ipath(const po_ctx* c) { return c->ipath; }
 void po_dp_events(const po_ctx* c, int64_t out[PO_EV_COUNT]) { memcpy(out, c->ev, sizeof c->ev); }
+void po_dp_edges(const po_ctx* c, int64_t out[PO_EDGE_COUNT][3]) { memcpy(out, c->edge, sizeof c->edge); }
+/* one evaluation of the comparison `id` with lhs - rhs = d */
+static inline void edge_at(int64_t (*eg)[3], int id, int64_t d) { if (eg && d >= -1 && d <= 1) eg[id][d + 1]++; }
+static inline void edge_sign(int64_t (*eg)[3], int id, double d) { if (eg) eg[id][d < 0 ? 0 : d > 0 ? 2 : 1]++; }
 
 /* base `i` of strand-local coordinates; reverse strand is virtual.
  * ref: _sequence.h:45-55 */
@@ -558,10 +563,13 @@ void po_score_nodes(po_ctx* c, const po_training* t, int closed, int is_meta) {
 /* ---------------------------------------------------- connection scoring */
 
 /* ref: _connection.h:52-78 */
-static double igm_same(const po_node* a, const po_node* b, double st_wt) {
+static double igm_same(const po_node* a, const po_node* b, double st_wt, int64_t (*eg)[3]) {
     int dist = abs(a->ndx - b->ndx);
     int ovl = a->ndx + 2 * a->strand >= b->ndx;
     double r = 0.0;
+    edge_at(eg, PO_EDGE_IGM_ADJ2, a->ndx + 2 - b->ndx); edge_at(eg, PO_EDGE_IGM_ADJ1, a->ndx - (b->ndx + 1));
+    edge_at(eg, PO_EDGE_IGM_FAR, dist - 3 * OPER_DIST); edge_at(eg, PO_EDGE_IGM_OVL, a->ndx + 2 * a->strand - b->ndx);
+    if (dist <= 3 * OPER_DIST) { edge_at(eg, ovl ? PO_EDGE_IGM_OPER_OVL : PO_EDGE_IGM_OPER, dist - OPER_DIST); edge_at(eg, ovl ? PO_EDGE_IGM_QUARTER_OVL : PO_EDGE_IGM_QUARTER, dist - OPER_DIST / 4); }
     if (a->ndx + 2 == b->ndx || a->ndx == b->ndx + 1) {
         if (a->strand == 1) { if (b->rscore < 0) r -= b->rscore; if (b->uscore < 0) r -= b->uscore; }
         else                { if (a->rscore < 0) r -= a->rscore; if (a->uscore < 0) r -= a->uscore; }
@@ -571,43 +579,56 @@ static double igm_same(const po_node* a, const po_node* b, double st_wt) {
     return r;
 }
 static inline double igm_diff(double st_wt) { return -0.15 * st_wt; }   /* ref: _connection.h:43-49 */
-static double igm(const po_node* a, const po_node* b, double st_wt) {  /* ref: _connection.h:81-91 */
-    return a->strand == b->strand ? igm_same(a, b, st_wt) : igm_diff(st_wt);
+static double igm(const po_node* a, const po_node* b, double st_wt, int64_t (*eg)[3]) {  /* ref: _connection.h:81-91 */
+    return a->strand == b->strand ? igm_same(a, b, st_wt, eg) : igm_diff(st_wt);
 }
 
 /* ref: lib.pyx:2279-2329 (Nodes._record_overlapping_starts) */
 void po_overlapping_starts(po_ctx* c, const po_training* t, int flag, int maxov) {
     const int nn = c->nn; po_node* nod = c->nod;
     c->ev[PO_EV_OVL_TIES] = 0;
+    int64_t (*eg)[3] = c->edge;
+    memset(eg[PO_EDGE_OVL_FIRST], 0, sizeof(int64_t[3]) * (PO_EDGE_COUNT - PO_EDGE_OVL_FIRST));
     for (int i = 0; i < nn; i++) {
         po_node* s = &nod[i];
         s->star_ptr[0] = s->star_ptr[1] = s->star_ptr[2] = -1;
+        if (s->type == T_STOP && s->edge == 1) eg[PO_EDGE_OVL_EDGE_STOP][1]++;
         if (s->type != T_STOP || s->edge == 1) continue;
         double best = -100; int kept = 0;   /* kept: candidates that took the place so far (event counter only) */
         if (s->strand == 1) {
             for (int j = i + 3; j >= 0; j--) {
-                if (j >= nn || nod[j].ndx > s->ndx + 2) continue;
+                if (j >= nn) continue;
+                if (nod[j].strand == 1 && nod[j].type != T_STOP) edge_at(eg, PO_EDGE_OVL_F_SKIP, nod[j].ndx - (s->ndx + 2));
+                if (nod[j].ndx > s->ndx + 2) continue;
+                edge_at(eg, PO_EDGE_OVL_F_MAXOV, nod[j].ndx + maxov - s->ndx);
                 if (nod[j].ndx + maxov < s->ndx) break;
                 if (nod[j].strand != 1 || nod[j].type == T_STOP) continue;
+                edge_at(eg, PO_EDGE_OVL_F_STOPVAL, nod[j].stop_val - s->ndx);
                 if (nod[j].stop_val <= s->ndx) continue;
                 int f = nod[j].ndx % 3;
                 if (flag == 0) { if (s->star_ptr[f] == -1) s->star_ptr[f] = j; }
                 else {
-                    double v = nod[j].cscore + nod[j].sscore + igm_same(s, &nod[j], t->st_wt);
+                    double v = nod[j].cscore + nod[j].sscore + igm_same(s, &nod[j], t->st_wt, eg);
+                    if (kept) edge_sign(eg, PO_EDGE_OVL_BEST, v - best);
                     if (v == best && kept) c->ev[PO_EV_OVL_TIES]++;
                     if (v > best) { s->star_ptr[f] = j; best = v; kept++; }
                 }
             }
         } else {
             for (int j = i - 3; j < nn; j++) {
-                if (j < 0 || nod[j].ndx < s->ndx - 2) continue;
+                if (j < 0) continue;
+                if (nod[j].strand == -1 && nod[j].type != T_STOP) edge_at(eg, PO_EDGE_OVL_R_SKIP, nod[j].ndx - (s->ndx - 2));
+                if (nod[j].ndx < s->ndx - 2) continue;
+                edge_at(eg, PO_EDGE_OVL_R_MAXOV, nod[j].ndx - maxov - s->ndx);
                 if (nod[j].ndx - maxov > s->ndx) break;
                 if (nod[j].strand != -1 || nod[j].type == T_STOP) continue;
+                edge_at(eg, PO_EDGE_OVL_R_STOPVAL, nod[j].stop_val - s->ndx);
                 if (nod[j].stop_val >= s->ndx) continue;
                 int f = nod[j].ndx % 3;
                 if (flag == 0) { if (s->star_ptr[f] == -1) s->star_ptr[f] = j; }
                 else {
-                    double v = nod[j].cscore + nod[j].sscore + igm_same(&nod[j], s, t->st_wt);
+                    double v = nod[j].cscore + nod[j].sscore + igm_same(&nod[j], s, t->st_wt, eg);
+                    if (kept) edge_sign(eg, PO_EDGE_OVL_BEST, v - best);
                     if (v == best && kept) c->ev[PO_EV_OVL_TIES]++;
                     if (v > best) { s->star_ptr[f] = j; best = v; kept++; }
                 }
@@ -622,7 +643,7 @@ static inline double gc_bias_score(const po_node* n, const po_training* t) {
 
 /* One candidate connection j -> i.  kind of i: 0 fwd start, 1 fwd stop, 2 rev start, 3 rev stop.
  * ref: _connection.h:94-140, 143-202, 205-267, 270-367 (the four split scorers) */
-static void connect(po_node* nod, int j, int i, int kind, const po_training* t, int final, int64_t* ev) {
+static void connect(po_node* nod, int j, int i, int kind, const po_training* t, int final, int64_t* ev, int64_t (*eg)[3]) {
     const po_node* a = &nod[j]; po_node* b = &nod[i]; const po_node* n3;
     const int a_fs = a->strand == 1 && a->type == T_STOP;      /* forward stop  */
     const int a_rb = a->strand != 1 && a->type != T_STOP;      /* reverse start */
@@ -631,37 +652,45 @@ static void connect(po_node* nod, int j, int i, int kind, const po_training* t, 
     int left = a->ndx, right = b->ndx, ovlp = 0, maxfr = -1;
     double score = 0.0, mod = 0.0;
 
-    if (a->traceb == -1 && (a_fs || a_rb)) return;             /* edge artifacts */
+    if (a->traceb == -1 && (a_fs || a_rb)) { eg[PO_EDGE_ARTIFACT][1]++; return; }             /* edge artifacts */
 
     switch (kind) {
     case 0:
-        if (a_fs) { left += 2; if (left >= right) return; if (final) score = igm_same(a, b, t->st_wt); }
+        if (a_fs) { left += 2; edge_at(eg, PO_EDGE_FS_FB, left - right); if (left >= right) return; if (final) score = igm_same(a, b, t->st_wt, eg); }
         else if (a_rb) { if (left >= right) return; if (final) score = igm_diff(t->st_wt); }
         break;
     case 1:
         if (a_fb) {
+            edge_at(eg, PO_EDGE_FB_FS, b->stop_val - a->ndx);
             if (b->stop_val >= a->ndx) return;
             right += 2;
             if (final) score = a->cscore + a->sscore; else mod = gc_bias_score(a, t);
         } else if (a_fs) {
+            edge_at(eg, PO_EDGE_FS_FS, b->stop_val - a->ndx);
             if (b->stop_val >= a->ndx) return;
+            eg[PO_EDGE_FS_FS_STAR][a->star_ptr[b->ndx % 3] == -1 ? 0 : 2]++;
             if (a->star_ptr[b->ndx % 3] == -1) return;
             n3 = &nod[a->star_ptr[b->ndx % 3]];
             left = n3->ndx; right += 2;
-            if (final) score = n3->cscore + n3->sscore + igm(a, n3, t->st_wt); else mod = gc_bias_score(n3, t);
+            if (final) score = n3->cscore + n3->sscore + igm(a, n3, t->st_wt, eg); else mod = gc_bias_score(n3, t);
         }
         break;
     case 2:
         if (a_rs) {
+            edge_at(eg, PO_EDGE_RS_RB, a->stop_val - b->ndx);
             if (a->stop_val <= b->ndx) return;
             left -= 2;
             if (final) score = b->cscore + b->sscore; else mod = gc_bias_score(b, t);
         } else if (a_fs) {
+            edge_at(eg, PO_EDGE_FS_RB_APART, (b->stop_val - 2) - (a->ndx + 2));
             if (b->stop_val - 2 >= a->ndx + 2) return;
             ovlp = (a->ndx + 2) - (b->stop_val - 2) + 1;
+            edge_at(eg, PO_EDGE_FS_RB_OVLP, ovlp - MAX_OPP_OVLP);
             if (ovlp >= MAX_OPP_OVLP) return;
+            edge_at(eg, PO_EDGE_FS_RB_HALF, (a->ndx - b->stop_val) - (b->ndx - a->ndx + 3));
             if ((a->ndx - b->stop_val) >= (b->ndx - a->ndx + 3)) return;
             int bnd = a->traceb == -1 ? 0 : nod[a->traceb].ndx;
+            edge_at(eg, PO_EDGE_FS_RB_BND, (a->ndx - b->stop_val) - (b->stop_val - 3 - bnd));
             if ((a->ndx - b->stop_val) >= (b->stop_val - 3 - bnd)) return;
             left = b->stop_val - 2;
             if (final) score = b->cscore + b->sscore + igm_diff(t->st_wt); else mod = gc_bias_score(b, t);
@@ -670,34 +699,42 @@ static void connect(po_node* nod, int j, int i, int kind, const po_training* t, 
     default:
         if (a_fs) {
             left += 2; right -= 2;
+            edge_at(eg, PO_EDGE_FS_RS, left - right);
             if (left >= right) return;
             double maxval = 0.0, cur;
             for (int k = 0; k < 3; k++) {
                 if (b->star_ptr[k] == -1) continue;
                 n3 = &nod[b->star_ptr[k]];
                 ovlp = left - n3->stop_val + 3;
+                edge_at(eg, PO_EDGE_TRI_OVLP0, ovlp); edge_at(eg, PO_EDGE_TRI_OVLP200, ovlp - MAX_OPP_OVLP);
                 if (ovlp <= 0 || ovlp >= MAX_OPP_OVLP) continue;
+                edge_at(eg, PO_EDGE_TRI_N3, ovlp - (n3->ndx - left));
                 if (ovlp >= n3->ndx - left) continue;
-                if (a->traceb == -1) continue;
+                if (a->traceb == -1) { eg[PO_EDGE_TRI_NO_TRACEB][1]++; continue; }
+                edge_at(eg, PO_EDGE_TRI_TRACEB, ovlp - (n3->stop_val - nod[a->traceb].ndx - 2));
                 if (ovlp >= n3->stop_val - nod[a->traceb].ndx - 2) continue;
-                cur = n3->cscore + n3->sscore + igm(n3, b, t->st_wt);
+                cur = n3->cscore + n3->sscore + igm(n3, b, t->st_wt, eg);
+                edge_sign(eg, PO_EDGE_TRI_BEST, (final ? cur : gc_bias_score(n3, t)) - maxval);
                 if (maxfr != -1 && (final ? cur : gc_bias_score(n3, t)) == maxval) ev[PO_EV_FRAME_TIES]++;
                 if ((final && cur > maxval) || (!final && gc_bias_score(n3, t) > maxval)) { maxfr = k; maxval = cur; }
             }
             if (maxfr != -1) {
                 n3 = &nod[b->star_ptr[maxfr]];
-                if (final) score = n3->cscore + n3->sscore + igm(n3, b, t->st_wt); else mod = gc_bias_score(n3, t);
+                if (final) score = n3->cscore + n3->sscore + igm(n3, b, t->st_wt, NULL); else mod = gc_bias_score(n3, t);
             } else if (final) score = igm_diff(t->st_wt);
         } else if (a_rb) {
             right -= 2;
+            edge_at(eg, PO_EDGE_RB_RS, left - right);
             if (left >= right) return;
-            if (final) score = igm_same(a, b, t->st_wt);
+            if (final) score = igm_same(a, b, t->st_wt, eg);
         } else if (a_rs) {
+            edge_at(eg, PO_EDGE_RS_RS, a->stop_val - b->ndx);
             if (a->stop_val <= b->ndx) return;
+            eg[PO_EDGE_RS_RS_STAR][b->star_ptr[a->ndx % 3] == -1 ? 0 : 2]++;
             if (b->star_ptr[a->ndx % 3] == -1) return;
             n3 = &nod[b->star_ptr[a->ndx % 3]];
             left -= 2; right = n3->ndx;
-            if (final) score = n3->cscore + n3->sscore + igm(n3, b, t->st_wt); else mod = gc_bias_score(n3, t);
+            if (final) score = n3->cscore + n3->sscore + igm(n3, b, t->st_wt, eg); else mod = gc_bias_score(n3, t);
         }
     }
     if (!final) score = ((double)(right - left + 1 - ovlp * 2)) * mod;
@@ -737,6 +774,20 @@ static void skippable(const uint8_t* restrict st, const uint8_t* restrict ty, co
     }
 }
 
+/* First candidate source of target i (ref: lib.pyx:1221-1233): 500 nodes back; for a forward stop or a reverse start whose ORF begins
+ * before that node, back to the node whose position is the ORF's other end (`walked`, `landed`: where that walk ended, 0 if no node has
+ * that position); then another 500 back. */
+static int window_start(const po_node* nod, int i, int* walked, int* landed) {
+    int lo = i < MAX_NODE_DIST ? 0 : i - MAX_NODE_DIST;
+    int kind = 2 * (nod[i].strand != 1) + (nod[i].type == T_STOP);
+    *walked = 0; *landed = lo;
+    if ((kind == 2 || kind == 1) && nod[lo].ndx > nod[i].stop_val) {
+        while (lo > 0 && nod[lo].ndx != nod[i].stop_val) lo--;
+        *walked = 1; *landed = lo;
+    }
+    return lo < MAX_NODE_DIST ? 0 : lo - MAX_NODE_DIST;
+}
+
 /* ref: lib.pyx:1205-1311 (_score_connections, _find_max_index, _disentangle_overlaps,
  * _max_forward_pointers, _dynamic_programming) and _connection.h:386-408 */
 /* the connection loop alone: node score / traceb / ov_mark before any traceback fix-up
@@ -747,15 +798,18 @@ void po_dprog_raw(po_ctx* c, const po_training* t, int final) {
     index_nodes(c);
     c->ev[PO_EV_TIES] = c->ev[PO_EV_ZERO_JOINS] = c->ev[PO_EV_FRAME_TIES] = c->ev[PO_EV_JOINS] = 0;
     for (int i = 0; i < nn; i++) { nod[i].score = 0; nod[i].traceb = -1; nod[i].tracef = -1; }
+    memset(c->edge, 0, sizeof(int64_t[3]) * PO_EDGE_OVL_FIRST);
     for (int i = 0; i < nn; i++) {
-        int lo = i < MAX_NODE_DIST ? 0 : i - MAX_NODE_DIST;
-        int kind = 2 * (nod[i].strand != 1) + (nod[i].type == T_STOP);
-        if ((kind == 2 || kind == 1) && nod[lo].ndx > nod[i].stop_val)
-            while (lo > 0 && nod[lo].ndx != nod[i].stop_val) lo--;
-        lo = lo < MAX_NODE_DIST ? 0 : lo - MAX_NODE_DIST;
+        int kind = 2 * (nod[i].strand != 1) + (nod[i].type == T_STOP), walked, landed;
+        int lo = window_start(nod, i, &walked, &landed);
         skippable(c->k_strand, c->k_type, c->k_frame, lo, i, c->k_skip);
-        for (int j = lo; j < i; j++) if (!c->k_skip[j]) connect(nod, j, i, kind, t, final, c->ev);
+        for (int j = lo; j < i; j++) if (!c->k_skip[j]) connect(nod, j, i, kind, t, final, c->ev, c->edge);
     }
+}
+
+int po_dp_window(const po_ctx* c, int i, int* walked, int* landed) {
+    if (i < 0 || i >= c->nn) return -1;
+    return window_start(c->nod, i, walked, landed);
 }
 
 /* ref: lib.pyx:1239-1251 (_find_max_index) */
@@ -817,8 +871,8 @@ void po_eliminate_bad_genes(po_ctx* c, int ipath, const po_training* t) {
     int head = p;
     for (; nod[p].tracef != -1; p = nod[p].tracef) {
         int f = nod[p].tracef;
-        if (nod[p].strand == 1 && nod[p].type == T_STOP) nod[f].sscore += igm(&nod[p], &nod[f], t->st_wt);
-        if (nod[p].strand == -1 && nod[p].type != T_STOP) nod[p].sscore += igm(&nod[p], &nod[f], t->st_wt);
+        if (nod[p].strand == 1 && nod[p].type == T_STOP) nod[f].sscore += igm(&nod[p], &nod[f], t->st_wt, NULL);
+        if (nod[p].strand == -1 && nod[p].type != T_STOP) nod[p].sscore += igm(&nod[p], &nod[f], t->st_wt, NULL);
     }
     for (p = head; nod[p].tracef != -1; p = nod[p].tracef) {
         int f = nod[p].tracef;
@@ -861,10 +915,10 @@ void po_tweak_final_starts(po_ctx* c, const po_training* t, int maxov) {
         double sc = nod[ndx].sscore + nod[ndx].cscore, ig = 0.0;
         int prev_fwd = i > 0 && nod[g[i - 1].start_ndx].strand == 1, prev_rev = i > 0 && nod[g[i - 1].start_ndx].strand == -1;
         int next_fwd = i < ng - 1 && nod[g[i + 1].start_ndx].strand == 1, next_rev = i < ng - 1 && nod[g[i + 1].start_ndx].strand == -1;
-        if (nod[ndx].strand == 1 && prev_fwd) ig = igm_same(&nod[g[i - 1].stop_ndx], &nod[ndx], w);
+        if (nod[ndx].strand == 1 && prev_fwd) ig = igm_same(&nod[g[i - 1].stop_ndx], &nod[ndx], w, NULL);
         if (nod[ndx].strand == 1 && prev_rev) ig = igm_diff(w);
         if (nod[ndx].strand == -1 && next_fwd) ig = igm_diff(w);
-        if (nod[ndx].strand == -1 && next_rev) ig = igm_same(&nod[ndx], &nod[g[i + 1].stop_ndx], w);
+        if (nod[ndx].strand == -1 && next_rev) ig = igm_same(&nod[ndx], &nod[g[i + 1].stop_ndx], w, NULL);
 
         int mi[2] = {-1, -1}; double ms[2] = {0, 0}, mg[2] = {0, 0};
         for (int j = ndx - 100; j < ndx + 100; j++) {
@@ -873,7 +927,7 @@ void po_tweak_final_starts(po_ctx* c, const po_training* t, int maxov) {
             double tg = 0.0;
             if (nod[j].strand == 1 && prev_fwd) {
                 if (nod[g[i - 1].stop_ndx].ndx - nod[j].ndx > maxov) continue;
-                tg = igm_same(&nod[g[i - 1].stop_ndx], &nod[j], w);
+                tg = igm_same(&nod[g[i - 1].stop_ndx], &nod[j], w, NULL);
             }
             if (nod[j].strand == 1 && prev_rev) {
                 if (nod[g[i - 1].start_ndx].ndx - nod[j].ndx >= 0) continue;
@@ -885,7 +939,7 @@ void po_tweak_final_starts(po_ctx* c, const po_training* t, int maxov) {
             }
             if (nod[j].strand == -1 && next_rev) {
                 if (nod[j].ndx - nod[g[i + 1].stop_ndx].ndx > maxov) continue;
-                tg = igm_same(&nod[j], &nod[g[i + 1].stop_ndx], w);
+                tg = igm_same(&nod[j], &nod[g[i + 1].stop_ndx], w, NULL);
             }
             double cs = nod[j].cscore + nod[j].sscore;
             if (mi[0] == -1) { mi[0] = j; ms[0] = cs; mg[0] = tg; }

@@ -125,6 +125,36 @@ int  po_train_upto(po_ctx*, po_training* out, const po_params*, int force_nonsd,
 enum { PO_EV_TIES = 0, PO_EV_ZERO_JOINS, PO_EV_FRAME_TIES, PO_EV_BEST_END_TIES, PO_EV_OVL_TIES, PO_EV_JOINS, PO_EV_COUNT };
 void   po_dp_events(const po_ctx*, int64_t out[PO_EV_COUNT]);
 
+/* How often each integer comparison of the connection scoring and of po_overlapping_starts was evaluated with lhs - rhs equal to
+ * -1, 0 and +1 (out[id][0..2]) in the last calls on this context: which inputs decide a rule AT its threshold.  Counters only.
+ *   FS_FB / RB_RS / FS_RS      `left(+2) >= right(-2)` of forward stop -> forward start, reverse start -> reverse stop, forward stop ->
+ *                              reverse stop (ref: _connection.h:94-140, 270-367)
+ *   FB_FS / RS_RB              `stop_val >= ndx` / `stop_val <= ndx` of the gene connections
+ *   FS_FS / RS_RS              the same of the operon rules; *_STAR: [0] star_ptr of the frame was -1, [2] it was not
+ *   FS_RB_APART / _OVLP / _HALF / _BND   the four tests of forward stop -> reverse start, in the reference's order
+ *   TRI_OVLP0 / _OVLP200 / _N3 / _TRACEB the tests of a frame of the triple overlap; TRI_NO_TRACEB [1]: the source had no traceb;
+ *                              TRI_BEST: sign of (candidate - best so far), [0] below, [1] equal, [2] above (strict `>` takes it)
+ *   ARTIFACT [1]               a never-reached forward stop or reverse start was refused as a source
+ *   IGM_ADJ2 / IGM_ADJ1        `a.ndx + 2 == b.ndx` / `a.ndx == b.ndx + 1`; IGM_FAR `dist > 180`; IGM_OVL `a.ndx + 2 strand >= b.ndx`;
+ *                              IGM_OPER `dist <= 60` and IGM_QUARTER `dist < 15` without overlap, *_OVL with it (dist <= 180 only)
+ *   OVL_F_* / OVL_R_*          forward / reverse stop of po_overlapping_starts: _SKIP `ndx > s.ndx + 2` (`< s.ndx - 2`) on starts of the
+ *                              strand, _MAXOV the break, _STOPVAL `stop_val <= s.ndx` (`>=`); OVL_EDGE_STOP [1]: an edge stop, which
+ *                              takes none; OVL_BEST: sign of (candidate - best so far) from the second kept candidate on
+ * The entries before PO_EDGE_OVL_FIRST are cleared by po_dprog_raw, the others by po_overlapping_starts (whose igm_same calls count
+ * into IGM_* as well: read them after po_dprog_raw for the sum of the two only if no clear lies between). */
+enum { PO_EDGE_FS_FB = 0, PO_EDGE_RB_RS, PO_EDGE_FS_RS, PO_EDGE_FB_FS, PO_EDGE_RS_RB, PO_EDGE_FS_FS, PO_EDGE_FS_FS_STAR, PO_EDGE_RS_RS,
+       PO_EDGE_RS_RS_STAR, PO_EDGE_FS_RB_APART, PO_EDGE_FS_RB_OVLP, PO_EDGE_FS_RB_HALF, PO_EDGE_FS_RB_BND, PO_EDGE_TRI_OVLP0,
+       PO_EDGE_TRI_OVLP200, PO_EDGE_TRI_N3, PO_EDGE_TRI_TRACEB, PO_EDGE_TRI_NO_TRACEB, PO_EDGE_TRI_BEST, PO_EDGE_ARTIFACT,
+       PO_EDGE_IGM_ADJ2, PO_EDGE_IGM_ADJ1, PO_EDGE_IGM_FAR, PO_EDGE_IGM_OVL, PO_EDGE_IGM_OPER, PO_EDGE_IGM_OPER_OVL,
+       PO_EDGE_IGM_QUARTER, PO_EDGE_IGM_QUARTER_OVL,
+       PO_EDGE_OVL_FIRST, PO_EDGE_OVL_F_SKIP = PO_EDGE_OVL_FIRST, PO_EDGE_OVL_F_MAXOV, PO_EDGE_OVL_F_STOPVAL, PO_EDGE_OVL_R_SKIP,
+       PO_EDGE_OVL_R_MAXOV, PO_EDGE_OVL_R_STOPVAL, PO_EDGE_OVL_EDGE_STOP, PO_EDGE_OVL_BEST, PO_EDGE_COUNT };
+void   po_dp_edges(const po_ctx*, int64_t out[PO_EDGE_COUNT][3]);
+
+/* First candidate source of target i in po_dprog_raw (ref: lib.pyx:1221-1233); *walked: the giant-ORF walk ran, *landed: the node it
+ * ended on (0 where no node has the position looked for), else the node 500 back.  -1 for an index out of range. */
+int    po_dp_window(const po_ctx*, int i, int* walked, int* landed);
+
 double po_last_path_score(const po_ctx*);  /* nodes[ipath].score of last winning DP */
 int    po_last_ipath(const po_ctx*);
 

@@ -78,6 +78,47 @@ def inject(seq, family, st_wt, seed, closed=False, tt=11, star_flag=1):
     return inject_into(extracted(seq, closed, tt), family, st_wt, seed, tt, star_flag)
 
 
+def node_index(nodes, kind, ndx):
+    """Index of the node of a kind ("fb" / "fs" / "rb" / "rs": strand and start / stop) at a position; exactly one must exist."""
+    strand, is_stop = (1 if kind[0] == "f" else -1), kind[1] == "s"
+    hit = np.flatnonzero((nodes["ndx"] == ndx) & (nodes["strand"] == strand) & ((nodes["type"] == 3) == is_stop))
+    assert len(hit) == 1, (kind, ndx, hit)
+    return int(hit[0])
+
+
+def inject_assigned(o, named, default, st_wt, max_overlap=60, tt=11, final=True, reverse=False):
+    """`inject_into` with a designed assignment instead of a family: `named` = [(kind, ndx, {field: value})] for the nodes a design
+    names, `default` = {"start": {field: value}, "stop": {...}} for every other node.  Returns (before, ref, ref_max, events, edges); `final = False`
+    runs the training pass on gc_score = (|cscore| / 16, |sscore|, 0.25) of the same assignment under the bias (1, 1, 1): every frame score
+    is positive, so genes connect."""
+    o.reset_scores()
+    t = blank_training(st_wt, tt)
+    live = o.nodes(copy=False)
+    is_stop = live["type"] == 3
+    for f in SCORE_FIELDS:
+        live[f] = np.where(is_stop, default["stop"][f], default["start"][f])
+    for kind, ndx, values in named:
+        k = node_index(live, kind, ndx)
+        for f, v in values.items():
+            live[f][k] = v
+    if not final:
+        t.bias[:] = (1.0, 1.0, 1.0)
+        live["gc_score"] = np.stack([np.abs(live["cscore"]) / 16, np.abs(live["sscore"]), np.full(len(live), 0.25)], axis=1)
+    o.overlapping_starts(t, 1 if final else 0, max_overlap)
+    events, edges = o.dp_events(), o.dp_edges()
+    before = o.nodes()
+    o.dprog_raw(t, final)
+    ref = o.nodes()
+    ref_max = o.find_max_index()
+    events.update({k: v for k, v in o.dp_events().items() if k != "ovl_ties"})
+    for k, v in o.dp_edges().items():              # the scoring pass clears its own counters, not those of overlapping_starts
+        if k.startswith("igm_"):                   # igm_same is priced in both passes
+            edges[k] = tuple(a + b for a, b in zip(edges[k], v))
+        elif not k.startswith("ovl_"):
+            edges[k] = v
+    return before, ref, ref_max, events, edges
+
+
 def inject_training(seq, family, bias, seed, closed=False, st_wt=4.35, tt=11):
     """The training pass (final = 0): gc_score drawn from `family` (pm1 or quant), the frame bias set to `bias`, star_ptr as
     `overlapping_starts(flag = 0)` leaves it.  Returns (before, ref, ref_max, events); ref is the state after `dprog_raw(t, False)`."""
