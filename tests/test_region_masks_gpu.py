@@ -14,6 +14,7 @@ import numpy as np
 import pytest
 
 from oracle import oracle as orc
+from tests.mask_ref import runs_of, union          # (the reference of every reported list, shared with tests/mask_shapes.py)
 from tests.test_finder_gpu import _with_unknown_runs, compare_contig
 from tests.util import golden_path, read_fasta, synthetic_contig
 
@@ -53,27 +54,6 @@ def masking_inputs():
             synthetic_contig(3000, 0.5, 73),
             synthetic_contig(5000, 0.5, 74) + b"NNN",
             b"N" * 400, b""]
-
-
-def union(intervals):
-    """Sorted, disjoint, touching intervals joined: the reference for every reported list (numpy, vectorised for the scale test)."""
-    a = np.asarray(intervals, dtype=np.int64).reshape(-1, 2)
-    if not len(a):
-        return np.zeros((0, 2), np.int32)
-    a = a[np.argsort(a[:, 0], kind="stable")]
-    reach = np.maximum.accumulate(a[:, 1])
-    first = np.concatenate([[True], a[1:, 0] > reach[:-1]])
-    idx = np.flatnonzero(first)
-    return np.stack([a[idx, 0], np.maximum.reduceat(a[:, 1], idx)], axis=1).astype(np.int32)
-
-
-def runs_of(flags, min_len):
-    """[begin, end) of the runs of set flags that are at least min_len long or reach the end (the rule of ref lib.pyx:699-713)."""
-    f = np.concatenate([[0], np.asarray(flags, np.int8), [0]])
-    d = np.diff(f)
-    b, e = np.flatnonzero(d == 1), np.flatnonzero(d == -1)
-    keep = (e - b >= min_len) | (e == len(flags))
-    return np.stack([b[keep], e[keep]], axis=1).astype(np.int32)
 
 
 def recs(genes):
