@@ -910,9 +910,19 @@ constexpr int CSQ_SERIAL_MAX = 256;                    // k_coding_score_quads: 
 struct OrfCtx {
     const uint8_t* d;             // GroupArrays::df of the contig: digit | forward-node flag << 4 | reverse-node flag << 5, by position
     const int32_t* c16;           // GroupArrays::c16 of the contig: entry g = index (in the group) of the first node at or after position 16 g
-    int tbase, p, q, L, strand, step, ncod;
+    int tbase, p, strand, step, ncod;
     int kstop;                    // index of the ORF's stop node in its contig
     int2 cc;
+    // lane src's ORF in every lane of the wavefront
+    __device__ __forceinline__ OrfCtx of_lane(const int src) const {
+        auto bc = [&](const int v) { return __builtin_amdgcn_readlane(v, src); };
+        auto bc64 = [&](const unsigned long long v) { return ((unsigned long long)(unsigned)bc((int)(unsigned)(v >> 32)) << 32) | (unsigned)bc((int)(unsigned)v); };
+        OrfCtx w;
+        w.d = (const uint8_t*)bc64((unsigned long long)d); w.c16 = (const int32_t*)bc64((unsigned long long)c16);
+        w.tbase = bc(tbase); w.p = bc(p); w.strand = bc(strand); w.step = bc(step); w.ncod = bc(ncod); w.kstop = bc(kstop);
+        w.cc.x = bc(cc.x); w.cc.y = bc(cc.y);
+        return w;
+    }
     // the walk's own strand has a node at position j / that node's index in the contig
     __device__ __forceinline__ bool node_at(const int j) const { return (d[j] >> (strand == 1 ? 4 : 5)) & 1; }
     // (a count: the first node of the sixteen positions from j & ~15 on, plus the nodes -- either strand -- at the positions before j, which
@@ -961,183 +971,107 @@ __device__ __forceinline__ int orf_codons(const int p, const int q, const int st
     return xmax >= p + 3 ? (xmax - (p + 3)) / 3 + 1 : 0;
 }
 
-// one lane, one (short) ORF
-// gil / il_stride / rank: the hexamer tables of the group's models interleaved, gil[hexamer * il_stride + rank[model]].  The
-// models scored on a contig usually are neighbours in that order (a GC window over bins sorted by GC): their values for one
-// hexamer then sit side by side and come in with one 16-byte load per pair instead of one 8-byte gather per model -- every
-// lane walks its own ORF, so what a load costs is its address, not its width.
-__device__ __forceinline__ void orf_serial(const OrfCtx& o, const ChainDesc* __restrict__ chains, const pga_training* __restrict__ models,
-                           const ModelScoreConst* __restrict__ msc, const ChainArrays& ca, const double* __restrict__ gil, const int il_stride,
-                           const int32_t* __restrict__ rank, const double* quad = nullptr, const int m_lo = 0, const int m_hi = 0x7fffffff) {
-    // quad != nullptr: the tables of the four models [m_lo, m_lo + 4) of the contig sit interleaved in LDS, quad[hexamer * 4 + m]
-    const uint8_t* __restrict__ d = o.d;
-    const int strand = o.strand, step = o.step, p = o.p;
-    const int m_end = min(o.cc.y, m_hi);
-    for (int m0 = m_lo; m0 < m_end; m0 += CS_MODELS) {
-        const int nm = min(CS_MODELS, m_end - m0);
-        const double* gdc[CS_MODELS]; double* csp[CS_MODELS]; const ModelScoreConst* mcp[CS_MODELS];
-#pragma unroll
-        for (int m = 0; m < CS_MODELS; m++) {
-            const ChainDesc ch = chains[o.cc.x + m0 + (m < nm ? m : 0)];
-            gdc[m] = models[ch.model].gene_dc; csp[m] = ca.cscore_raw + ch.off; mcp[m] = &msc[ch.model];
-        }
-        double sum[CS_MODELS];
-#pragma unroll
-        for (int m = 0; m < CS_MODELS; m++) sum[m] = 0.0;
-        int far = -1, mer = 0;
-        unsigned long long sm0 = 0, sm1 = 0, sm2 = 0;           // codons below CS_LONG = 192 that are start nodes; beyond, the second pass reads the flags again
-        // neighbours in the interleaved table?
-        const int r0 = rank[chains[o.cc.x + m0].model];
-        bool side_by_side = gil != nullptr;
-#pragma unroll
-        for (int m = 1; m < CS_MODELS; m++) if (m < nm) side_by_side = side_by_side && rank[chains[o.cc.x + m0 + m].model] == r0 + m;
-        const double* __restrict__ row0 = gil + r0;
-        // one codon: its hexamer `mer` joins the sums; a start node (k = its index in the contig) keeps the sums so far
-        auto visit = [&](const int ci, const bool isnode, const int k) {
-            if (quad != nullptr) {
-                const double* q4 = quad + 4 * mer;               // one 32-byte row of LDS: two ds_read_b128
-                sum[0] += q4[0]; sum[1] += q4[1]; sum[2] += q4[2]; sum[3] += q4[3];
-            } else if (side_by_side) {
-                struct P2 { double a, b; } u, v;
-                const double* __restrict__ rp = row0 + (size_t)mer * il_stride;
-                __builtin_memcpy(&u, rp, 16);
-                sum[0] += u.a; sum[1] += u.b;                     // sums of models the lane does not have are never stored
-                if (nm > 2) { __builtin_memcpy(&v, rp + 2, 16); sum[2] += v.a; sum[3] += v.b; }
-            } else {
-#pragma unroll
-                for (int m = 0; m < CS_MODELS; m++) if (m < nm) sum[m] += gdc[m][mer];      // a load only where the lane has a model m
-            }
-            if (isnode) {
-#pragma unroll
-                for (int m = 0; m < CS_MODELS; m++) if (m < nm) csp[m][k] = sum[m];
-                far = ci;
-                if (ci < 64) sm0 |= 1ull << ci; else if (ci < 128) sm1 |= 1ull << (ci - 64); else if (ci < CS_LONG) sm2 |= 1ull << (ci - 128);
-            }
-        };
-        if (o.ncod > 0) {
-            const int j = p + step; mer = hexamer(d, j, strand);
-            const bool isnode = o.node_at(j);
-            visit(0, isnode, isnode ? o.node_index(j) : 0);
-        }
-        // Five codons at a time: their 15 bases and the start flags of those positions are 16 contiguous bytes of GroupArrays::df,
-        // one (unaligned) load instead of four byte loads per codon -- every lane walks its own ORF, so each load
-        // instruction costs the address path 64 distinct lines whatever its width.  Nothing a group needs is loaded while the
-        // group is walked: its bytes were asked for two groups earlier, and the node indices of its flagged positions one group
-        // earlier (from the flags, by then in registers) -- in lock step some lane meets a start node at nearly every codon, and
-        // a load there would make every codon wait out a memory round trip.
-        struct W16 { unsigned long long a, b; };
-        auto group_lo = [&](const int c0) { return strand == 1 ? p - 3 * (c0 + 5) : p + 3 * c0 + 1; };       // lowest position of the group
-        auto byte_of = [](const W16& w, const int k) { return (unsigned)((k < 8 ? w.a >> (8 * k) : w.b >> (8 * (k - 8))) & 0xffull); };
-        auto flag_off = [&](const int u) { return strand == 1 ? 12 - 3 * u : 3 * u + 2; };                 // offset of codon u's node flag in the group
-        const int fbit = strand == 1 ? 4 : 5;
-        // the index of the walk's node at offset k of a group starting at lo: a reverse node follows the forward node of its position
-        auto node_of = [&](const W16& w, const int lo, const int k) { return o.node_index(lo + k) + o.tbase; };
-        W16 D1{0, 0}, D2{0, 0};
-        int kq[5] = {0, 0, 0, 0, 0};
-        const int ncod = o.ncod;
-        // prologue: the bytes of the first and the second group; then the node indices of the first
-        if (ncod > 1 && group_lo(1) >= 0) __builtin_memcpy(&D1, d + group_lo(1), 16);
-        if (ncod > 6 && group_lo(6) >= 0) __builtin_memcpy(&D2, d + group_lo(6), 16);
-        if (ncod > 1 && group_lo(1) >= 0) {
-#pragma unroll
-            for (int u = 0; u < 5; u++) if (1 + u < ncod && ((byte_of(D1, flag_off(u)) >> fbit) & 1u)) kq[u] = node_of(D1, group_lo(1), flag_off(u));
-        }
-        for (int c0 = 1; c0 < ncod; c0 += 5) {
-            const int lo = group_lo(c0);
-            if (lo < 0) {
-                // the group hangs over the contig's first base (only codons beyond the ORF do): byte loads
-                for (int ci = c0; ci < min(c0 + 5, ncod); ci++) {
-                    const int j = p + step * (ci + 1);
-                    const int lo3 = (d[j] & 3) | ((d[j + 1] & 3) << 2) | ((d[j + 2] & 3) << 4);          // strand == 1 here
-                    mer = ((mer << 6) & 0xfc0) | lo3;
-                    const bool isnode = o.node_at(j);
-                    visit(ci, isnode, isnode ? o.node_index(j) : 0);
-                }
-                continue;
-            }
-            // everything of this group is here; ask for what the next groups need
-            const W16 B = D1;
-            int kc[5];
-#pragma unroll
-            for (int u = 0; u < 5; u++) kc[u] = kq[u] - o.tbase;
-            D1 = D2;
-            if (c0 + 5 < ncod) {
-                const int lo1 = group_lo(c0 + 5);
-                if (lo1 >= 0) {
-#pragma unroll
-                    for (int u = 0; u < 5; u++) if (c0 + 5 + u < ncod && ((byte_of(D1, flag_off(u)) >> fbit) & 1u)) kq[u] = node_of(D1, lo1, flag_off(u));
-                }
-                if (c0 + 10 < ncod) { const int lo2 = group_lo(c0 + 10); if (lo2 >= 0) __builtin_memcpy(&D2, d + lo2, 16); }
-            }
-            auto bytes_at = [](const W16& w, const int k) {          // the (up to 8) bytes from offset k on, k <= 13
-                return k < 8 ? (w.a >> (8 * k)) | (k ? w.b << (64 - 8 * k) : 0ull) : w.b >> (8 * (k - 8));
-            };
-#pragma unroll
-            for (int u = 0; u < 5; u++) {
-                const int ci = c0 + u;
-                if (ci >= ncod) break;
-                const int k = strand == 1 ? 12 - 3 * u : 3 * u;             // offset of the codon's lowest position
-                const unsigned t3 = (unsigned)bytes_at(B, k);
-                const int b0 = t3 & 7, b1 = (t3 >> 8) & 7, b2 = (t3 >> 16) & 7;
-                // rolling update: the three bases nearest to the walk direction are new (ref: _sequence.h:207-220)
-                const int lo3 = strand == 1 ? (b0 & 3) | ((b1 & 3) << 2) | ((b2 & 3) << 4)
-                                            : (comp2(b2) & 3) | ((comp2(b1) & 3) << 2) | ((comp2(b0) & 3) << 4);
-                mer = ((mer << 6) & 0xfc0) | lo3;
-                visit(ci, ((byte_of(B, flag_off(u)) >> fbit) & 1u) != 0, kc[u]);
-            }
-        }
-        if (far < 0) continue;
-        double run_c[CS_MODELS], run_l[CS_MODELS];
-#pragma unroll
-        for (int m = 0; m < CS_MODELS; m++) { run_c[m] = -10000.0; run_l[m] = -10000.0; }
-        // the start nodes from the outermost inwards: codons from CS_LONG on by their flags (one 16-byte load per group of five, as
-        // in the first pass), the others from the masks
-        int ci = far, fc0 = -1;
-        W16 G2{0, 0};
-        while (ci >= 0) {
-            if (ci >= CS_LONG) {
-                const int c0 = 1 + 5 * ((ci - 1) / 5), u = ci - c0;
-                const int lo = group_lo(c0);
-                bool isnode;
-                if (lo < 0) isnode = o.node_at(p + step * (ci + 1));
-                else {
-                    if (c0 != fc0) { __builtin_memcpy(&G2, d + lo, 16); fc0 = c0; }
-                    const int kn = strand == 1 ? 12 - 3 * u : 3 * u + 2;
-                    isnode = ((byte_of(G2, kn) >> fbit) & 1u) != 0;
-                }
-                if (!isnode) { ci--; continue; }
-            } else {
-                const int wsel = ci >> 6;
-                const unsigned long long bits = (wsel == 2 ? sm2 : (wsel == 1 ? sm1 : sm0)) & ((2ull << (ci & 63)) - 1ull);
-                if (!bits) { ci = wsel * 64 - 1; continue; }
-                ci = wsel * 64 + 63 - __builtin_clzll(bits);
-            }
-            const int j = p + step * (ci + 1);
-            const int k = o.node_index(j);
-#pragma unroll
-            for (int m = 0; m < CS_MODELS; m++) {
-                if (m >= nm) continue;
-                double cs = csp[m][k];
-                if (cs > run_c[m]) run_c[m] = cs; else cs -= (run_c[m] - cs);
-                double lfac = length_factor(mcp[m], ci + 2);
-                if (lfac > run_l[m]) run_l[m] = lfac; else lfac -= fmax(fmin(run_l[m] - lfac, lfac), 0.0);
-                if (lfac > 3.0 && cs < 0.5 * lfac) cs = 0.5 * lfac;
-                cs += lfac;
-                csp[m][k] = cs;
-            }
-            ci--;
-        }
-    }
+// the ORF of stop node t (index in the group) of a contig: digits from `base` on, `len` bases, first node tbase, first tile tile0,
+// chains cc (first, count)
+__device__ __forceinline__ OrfCtx orf_ctx(const GroupArrays& ga, const int t, const int64_t base, const int len, const int tbase, const int tile0,
+                                          const int2 cc) {
+    OrfCtx o;
+    o.cc = cc;
+    o.d = ga.df + base;
+    o.strand = ga.strand[t];
+    o.c16 = ga.c16 + (size_t)tile0 * 192;
+    o.tbase = tbase;
+    o.p = ga.ndx[t]; o.kstop = t - tbase;
+    o.step = o.strand == 1 ? -3 : 3;
+    o.ncod = cc.y <= 0 ? 0 : orf_codons(o.p, ga.stop_val[t], o.strand, len);
+    return o;
 }
 
-// orf_serial for k_coding_score_quads: the four table columns [m0, m0 + 4) of the contig's quad sit in LDS (quad[hexamer * 4 + m]).
-// Same sums, same order; written for instruction count, because 64 ORFs walk in lock step and whatever one lane needs at a
-// codon every lane pays for: a group's 16 bases become sixteen 2-bit digits once (in walk order on either strand), its flags
-// sixteen bits; a start node stores all four sums without asking which columns the contig has (the others go to
-// ChainArrays::cs_sink); nothing is loaded inside a group (see orf_serial).
-__device__ __forceinline__ void orf_serial_quad(const OrfCtx& o, const ChainDesc* __restrict__ chains, const ModelScoreConst* __restrict__ msc,
-                                                const ChainArrays& ca, const double* __restrict__ quad, const int m0,
-                                                unsigned long long* __restrict__ prof = nullptr) {
+// Passes 2 and 3 at one start node (ref: lib.pyx:2182-2239): cs = the sum the walk stored, lfac = the length factor of the start's
+// ORF, run_c / run_l = the largest sum / factor among the starts further out (updated here: the walk that prices its starts one
+// after the other passes its running maxima, the walks with a start per lane copies of their exclusive maxima).  Branches, not
+// fmax: v_max_f64 wants its inputs canonicalised, 154 more VALU instructions in k_coding_score_quads.
+__device__ __forceinline__ double cs_penalty(double cs, double lfac, double& run_c, double& run_l) {
+    if (cs > run_c) run_c = cs; else cs -= (run_c - cs);
+    if (lfac > run_l) run_l = lfac; else lfac -= fmax(fmin(run_l - lfac, lfac), 0.0);
+    if (lfac > 3.0 && cs < 0.5 * lfac) cs = 0.5 * lfac;
+    return cs + lfac;
+}
+
+// The (up to) CS_MODELS models [m0, m0 + nm) of a contig: where their sums go and their length factors.  A column the contig lacks
+// stores to ChainArrays::cs_sink (unconditional stores instead of a divergent branch per column) and borrows column m0's factors,
+// which price what nobody reads.
+struct CsModels { double* csp[CS_MODELS]; const ModelScoreConst* mcp[CS_MODELS]; int nm; };
+__device__ __forceinline__ CsModels cs_models(const ChainDesc* __restrict__ chains, const int2 cc, const int m0, const ModelScoreConst* __restrict__ msc,
+                                              const ChainArrays& ca) {
+    CsModels s;
+    s.nm = max(0, min(CS_MODELS, cc.y - m0));
+#pragma unroll
+    for (int m = 0; m < CS_MODELS; m++) {
+        const ChainDesc ch = chains[cc.x + m0 + (m < s.nm ? m : 0)];
+        s.csp[m] = m < s.nm ? ca.cscore_raw + ch.off : ca.cs_sink; s.mcp[m] = &msc[ch.model];
+    }
+    return s;
+}
+
+// Where the table values of a hexamer come from: add() = all four columns onto a lane's sums, at() = one of them.
+// the four columns of a task interleaved in LDS, quad[hexamer * 4 + m]
+struct TabLds {
+    const double* quad;
+    __device__ __forceinline__ void add(double (&sum)[CS_MODELS], const int mer) const {
+        const double* q4 = quad + 4 * mer;                   // one 32-byte row of LDS: two ds_read_b128
+        sum[0] += q4[0]; sum[1] += q4[1]; sum[2] += q4[2]; sum[3] += q4[3];
+    }
+    __device__ __forceinline__ double at(const int m, const int mer) const { return quad[4 * mer + m]; }
+};
+// The hexamer tables of the group's models interleaved in global memory, gil[hexamer * il_stride + rank[model]].  The models scored
+// on a contig usually are neighbours in that order (a GC window over bins sorted by GC): their values for one hexamer then sit side
+// by side and come in with one 16-byte load per pair instead of one 8-byte gather per model -- every lane walks its own ORF, so what
+// a load costs is its address, not its width.
+struct TabPairs {
+    const double* row0; int il_stride, nm;
+    __device__ __forceinline__ void add(double (&sum)[CS_MODELS], const int mer) const {
+        struct P2 { double a, b; } u, v;
+        const double* __restrict__ rp = row0 + (size_t)mer * il_stride;
+        __builtin_memcpy(&u, rp, 16);
+        sum[0] += u.a; sum[1] += u.b;                         // sums of models the lane does not have go to the sink
+        if (nm > 2) { __builtin_memcpy(&v, rp + 2, 16); sum[2] += v.a; sum[3] += v.b; }
+    }
+};
+// may models [m0, m0 + nm) of a contig be read as pairs?  (neighbours, and both halves of every pair inside the table's row)
+__device__ __forceinline__ bool tab_pairs_ok(const ChainDesc* __restrict__ chains, const int32_t* __restrict__ rank, const int2 cc, const int m0, const int nm,
+                                             const int il_stride) {
+    const int r0 = rank[chains[cc.x + m0].model];
+    bool ok = r0 + (nm > 2 ? 3 : 1) < il_stride;
+#pragma unroll
+    for (int m = 1; m < CS_MODELS; m++) if (m < nm) ok = ok && rank[chains[cc.x + m0 + m].model] == r0 + m;
+    return ok;
+}
+// one gather per model from its own table: any set of models
+struct TabGather {
+    const double* gdc[CS_MODELS]; int nm;
+    __device__ __forceinline__ void add(double (&sum)[CS_MODELS], const int mer) const {
+#pragma unroll
+        for (int m = 0; m < CS_MODELS; m++) if (m < nm) sum[m] += gdc[m][mer];      // a load only where the lane has a model m
+    }
+    __device__ __forceinline__ double at(const int m, const int mer) const { return gdc[m][mer]; }
+};
+__device__ __forceinline__ TabGather tab_gather(const ChainDesc* __restrict__ chains, const pga_training* __restrict__ models, const int2 cc, const int m0,
+                                                const int nm) {
+    TabGather t;
+    t.nm = nm;
+#pragma unroll
+    for (int m = 0; m < CS_MODELS; m++) t.gdc[m] = models[chains[cc.x + m0 + (m < nm ? m : 0)].model].gene_dc;
+    return t;
+}
+
+// One lane, one ORF of at most CSQ_SERIAL_MAX codons, the sums of the models `md` from the table `tab`.  Written for instruction
+// count, because 64 ORFs walk in lock step and whatever one lane needs at a codon every lane pays for: a group's 16 bases become
+// sixteen 2-bit digits once (in walk order on either strand), its flags sixteen bits; a start node stores all four sums without
+// asking which columns the contig has (CsModels); nothing is loaded inside a group but the table values.
+// The lanes that call must be the leading lanes of the wavefront, or all of it (see ncod_max below).
+template <class Tab>
+__device__ __forceinline__ void orf_serial(const OrfCtx& o, const CsModels& md, const Tab& tab, unsigned long long* __restrict__ prof = nullptr) {
     unsigned long long tq = prof ? __builtin_readcyclecounter() : 0;
     auto qmark = [&](const int slot) {
         if (!prof) return;
@@ -1148,13 +1082,8 @@ __device__ __forceinline__ void orf_serial_quad(const OrfCtx& o, const ChainDesc
     const uint8_t* __restrict__ d = o.d;
     const int strand = o.strand, step = o.step, p = o.p, ncod = o.ncod;
     const bool fwd = strand == 1;
-    const int nm = max(0, min(CS_MODELS, o.cc.y - m0));
-    double* csp[CS_MODELS]; const ModelScoreConst* mcp[CS_MODELS];
-#pragma unroll
-    for (int m = 0; m < CS_MODELS; m++) {
-        const ChainDesc ch = chains[o.cc.x + m0 + (m < nm ? m : 0)];
-        csp[m] = m < nm ? ca.cscore_raw + ch.off : ca.cs_sink; mcp[m] = &msc[ch.model];
-    }
+    const auto& csp = md.csp; const auto& mcp = md.mcp;
+    const int nm = md.nm;
     double sum[CS_MODELS];
 #pragma unroll
     for (int m = 0; m < CS_MODELS; m++) sum[m] = 0.0;
@@ -1162,8 +1091,7 @@ __device__ __forceinline__ void orf_serial_quad(const OrfCtx& o, const ChainDesc
     unsigned long long sm0 = 0, sm1 = 0, sm2 = 0, sm3 = 0;  // the codons that are start nodes (every ORF walked here has at most CSQ_SERIAL_MAX = 256)
     // one codon (ci is the same in every lane): its hexamer joins the sums; a start node (k = its index in the contig) keeps them
     auto visit = [&](const int ci, const bool isnode, const int k) {
-        const double* q4 = quad + 4 * mer;                   // one 32-byte row of LDS: two ds_read_b128
-        sum[0] += q4[0]; sum[1] += q4[1]; sum[2] += q4[2]; sum[3] += q4[3];
+        tab.add(sum, mer);
         if (isnode) { csp[0][k] = sum[0]; csp[1][k] = sum[1]; csp[2][k] = sum[2]; csp[3][k] = sum[3]; }
         far = isnode ? ci : far; kfar = isnode ? k : kfar;
         const unsigned long long bit = isnode ? 1ull << (ci & 63) : 0ull;
@@ -1215,6 +1143,10 @@ __device__ __forceinline__ void orf_serial_quad(const OrfCtx& o, const ChainDesc
     if (ncod > 6 && group_lo(6) >= 0) __builtin_memcpy(&D2, d + group_lo(6), 16);
     qmark(10);
     // the group counter is the same in every lane (scalar): a lane whose ORF has ended idles through the rest, loading nothing
+    // but table values.  Both call sites are divergent, so the exchange below also asks lanes that are switched off, which answer
+    // zero or something stale: harmless, because a lane's own ncod takes part in its maximum and the switched-off lanes are the
+    // trailing ones (k_coding_score_quads) or none (k_coding_score) -- every switched-on lane on the way from a lane to the first
+    // one, whose maximum counts, then is switched on as well, and whatever a switched-off lane adds only lengthens the idling.
     int ncod_max = ncod;
 #pragma unroll
     for (int m = 32; m >= 1; m >>= 1) ncod_max = max(ncod_max, __shfl_xor(ncod_max, m, 64));
@@ -1254,8 +1186,8 @@ __device__ __forceinline__ void orf_serial_quad(const OrfCtx& o, const ChainDesc
     double run_c[CS_MODELS], run_l[CS_MODELS];
 #pragma unroll
     for (int m = 0; m < CS_MODELS; m++) { run_c[m] = -10000.0; run_l[m] = -10000.0; }
-    // The start nodes from the outermost inwards.  Every ORF that walks here has at most CS_LONG codons (the 64-to-a-wave classes
-    // of k_coding_score_quads), so the masks hold all of its start nodes and the outermost one's index is at hand (kfar).  What a
+    // The start nodes from the outermost inwards.  Every ORF that walks here has at most CSQ_SERIAL_MAX codons (the 64-to-a-wave
+    // classes of k_coding_score_quads; k_coding_score stops at CS_LONG), so the masks hold all of its start nodes and the outermost one's index is at hand (kfar).  What a
     // start node costs is round trips: its index (two loads), then per model the sum the walk stored and the length factor.  Asked
     // for one after the other -- a store of one model stands between the loads of the next, and the compiler must assume they
     // meet -- that was five trips per start node; here the next start node's index is asked for first, then all of this one's
@@ -1286,13 +1218,7 @@ __device__ __forceinline__ void orf_serial_quad(const OrfCtx& o, const ChainDesc
 #pragma unroll
         for (int m = 0; m < CS_MODELS; m++) { csn[m] = c1 >= 0 ? csp[m][k1] : 0.0; lf[m] = length_factor(mcp[m], ci + 2); }
 #pragma unroll
-        for (int m = 0; m < CS_MODELS; m++) {
-            double c = cs[m], lfac = lf[m];
-            if (c > run_c[m]) run_c[m] = c; else c -= (run_c[m] - c);
-            if (lfac > run_l[m]) run_l[m] = lfac; else lfac -= fmax(fmin(run_l[m] - lfac, lfac), 0.0);
-            if (lfac > 3.0 && c < 0.5 * lfac) c = 0.5 * lfac;
-            cs[m] = c + lfac;
-        }
+        for (int m = 0; m < CS_MODELS; m++) cs[m] = cs_penalty(cs[m], lf[m], run_c[m], run_l[m]);
 #pragma unroll
         for (int m = 0; m < CS_MODELS; m++) if (m < nm) csp[m][k] = cs[m];
 #pragma unroll
@@ -1302,80 +1228,64 @@ __device__ __forceinline__ void orf_serial_quad(const OrfCtx& o, const ChainDesc
     qmark(12);
 }
 
-// the whole wavefront, one (long) ORF; `o` is wave-uniform
-__device__ __forceinline__ void orf_wave(const OrfCtx& o, const int lane, const ChainDesc* __restrict__ chains, const pga_training* __restrict__ models,
-                         const ModelScoreConst* __restrict__ msc, const ChainArrays& ca, const double* quad = nullptr, const int m_lo = 0,
-                         const int m_hi = 0x7fffffff) {
+// the whole wavefront, one (long) ORF, the sums of the models `md` from the table `tab`; all of them wave-uniform
+template <class Tab>
+__device__ __forceinline__ void orf_wave(const OrfCtx& o, const int lane, const CsModels& md, const Tab& tab) {
     const double NEG_INF = -__builtin_huge_val();
     const int strand = o.strand, step = o.step, p = o.p, ncod = o.ncod;
-    const int m_end = min(o.cc.y, m_hi);
-    for (int m0 = m_lo; m0 < m_end; m0 += CS_MODELS) {
-        const int nm = min(CS_MODELS, m_end - m0);
-        const double* gdc[CS_MODELS]; double* csp[CS_MODELS]; const ModelScoreConst* mcp[CS_MODELS];
+    const auto& csp = md.csp; const auto& mcp = md.mcp;
+    const int nm = md.nm;
+    double sum[CS_MODELS];
 #pragma unroll
-        for (int m = 0; m < CS_MODELS; m++) {
-            const ChainDesc ch = chains[o.cc.x + m0 + (m < nm ? m : 0)];
-            gdc[m] = models[ch.model].gene_dc; csp[m] = ca.cscore_raw + ch.off; mcp[m] = &msc[ch.model];
-        }
-        double sum[CS_MODELS];
+    for (int m = 0; m < CS_MODELS; m++) sum[m] = 0.0;
+    bool any_start = false;
+    for (int c0 = 0; c0 < ncod; c0 += 64) {
+        const int ci = c0 + lane;
+        const bool valid = ci < ncod;
+        const int x = p + step * (ci + 1);
+        const int mer = valid ? hexamer(o.d, x, strand) : 0;
+        const bool fl = valid && o.node_at(x);
+        const int k = fl ? o.node_index(x) : 0;
+        double v[CS_MODELS], pref[CS_MODELS];
 #pragma unroll
-        for (int m = 0; m < CS_MODELS; m++) sum[m] = 0.0;
-        bool any_start = false;
-        for (int c0 = 0; c0 < ncod; c0 += 64) {
-            const int ci = c0 + lane;
-            const bool valid = ci < ncod;
-            const int x = p + step * (ci + 1);
-            const int mer = valid ? hexamer(o.d, x, strand) : 0;
-            const bool fl = valid && o.node_at(x);
-            const int k = fl ? o.node_index(x) : 0;
-            double v[CS_MODELS], pref[CS_MODELS];
-#pragma unroll
-            for (int m = 0; m < CS_MODELS; m++) { v[m] = (valid && m < nm) ? (quad != nullptr ? quad[4 * mer + m] : gdc[m][mer]) : 0.0; pref[m] = 0.0; }
-            const int nv = min(64, ncod - c0);
-            for (int l = 0; l < nv; l++) {
-#pragma unroll
-                for (int m = 0; m < CS_MODELS; m++) {
-                    if (m >= nm) break;
-                    sum[m] += readlane_f64_pl(v[m], l);
-                    pref[m] = lane == l ? sum[m] : pref[m];
-                }
-            }
-            if (fl) {
-#pragma unroll
-                for (int m = 0; m < CS_MODELS; m++) if (m < nm) csp[m][k] = pref[m];
-            }
-            any_start = any_start || __any(fl);
-        }
-        if (!any_start) continue;
-        double carry_c[CS_MODELS], carry_l[CS_MODELS];
-#pragma unroll
-        for (int m = 0; m < CS_MODELS; m++) { carry_c[m] = -10000.0; carry_l[m] = -10000.0; }
-        for (int c0 = ((ncod - 1) >> 6) << 6; c0 >= 0; c0 -= 64) {
-            const int ci = c0 + (63 - lane);            // lane order = outermost first
-            const bool valid = ci < ncod;
-            const int x = p + step * (ci + 1);
-            const bool fl = valid && o.node_at(x);
-            const int k = fl ? o.node_index(x) : 0;
+        for (int m = 0; m < CS_MODELS; m++) { v[m] = (valid && m < nm) ? tab.at(m, mer) : 0.0; pref[m] = 0.0; }
+        const int nv = min(64, ncod - c0);
+        for (int l = 0; l < nv; l++) {
 #pragma unroll
             for (int m = 0; m < CS_MODELS; m++) {
                 if (m >= nm) break;
-                const double cs0 = fl ? csp[m][k] : NEG_INF;
-                const double lf0 = fl ? length_factor(mcp[m], ci + 2) : NEG_INF;
-                const double inc_c = wave_incl_max(cs0, lane), inc_l = wave_incl_max(lf0, lane);
-                double ex_c = __shfl_up(inc_c, 1, 64), ex_l = __shfl_up(inc_l, 1, 64);
-                if (lane == 0) { ex_c = NEG_INF; ex_l = NEG_INF; }
-                const double run_c = fmax(ex_c, carry_c[m]), run_l = fmax(ex_l, carry_l[m]);
-                if (fl) {
-                    double cs = cs0, lfac = lf0;
-                    if (!(cs > run_c)) cs -= (run_c - cs);
-                    if (!(lfac > run_l)) lfac -= fmax(fmin(run_l - lfac, lfac), 0.0);
-                    if (lfac > 3.0 && cs < 0.5 * lfac) cs = 0.5 * lfac;
-                    cs += lfac;
-                    csp[m][k] = cs;
-                }
-                carry_c[m] = fmax(carry_c[m], readlane_f64_pl(inc_c, 63));
-                carry_l[m] = fmax(carry_l[m], readlane_f64_pl(inc_l, 63));
+                sum[m] += readlane_f64_pl(v[m], l);
+                pref[m] = lane == l ? sum[m] : pref[m];
             }
+        }
+        if (fl) {
+#pragma unroll
+            for (int m = 0; m < CS_MODELS; m++) if (m < nm) csp[m][k] = pref[m];
+        }
+        any_start = any_start || __any(fl);
+    }
+    if (!any_start) return;
+    double carry_c[CS_MODELS], carry_l[CS_MODELS];
+#pragma unroll
+    for (int m = 0; m < CS_MODELS; m++) { carry_c[m] = -10000.0; carry_l[m] = -10000.0; }
+    for (int c0 = ((ncod - 1) >> 6) << 6; c0 >= 0; c0 -= 64) {
+        const int ci = c0 + (63 - lane);            // lane order = outermost first
+        const bool valid = ci < ncod;
+        const int x = p + step * (ci + 1);
+        const bool fl = valid && o.node_at(x);
+        const int k = fl ? o.node_index(x) : 0;
+#pragma unroll
+        for (int m = 0; m < CS_MODELS; m++) {
+            if (m >= nm) break;
+            const double cs0 = fl ? csp[m][k] : NEG_INF;
+            const double lf0 = fl ? length_factor(mcp[m], ci + 2) : NEG_INF;
+            const double inc_c = wave_incl_max(cs0, lane), inc_l = wave_incl_max(lf0, lane);
+            double ex_c = __shfl_up(inc_c, 1, 64), ex_l = __shfl_up(inc_l, 1, 64);
+            if (lane == 0) { ex_c = NEG_INF; ex_l = NEG_INF; }
+            double run_c = fmax(ex_c, carry_c[m]), run_l = fmax(ex_l, carry_l[m]);        // of the starts further out: copies, nobody reads them back
+            if (fl) csp[m][k] = cs_penalty(cs0, lf0, run_c, run_l);
+            carry_c[m] = fmax(carry_c[m], readlane_f64_pl(inc_c, 63));
+            carry_l[m] = fmax(carry_l[m], readlane_f64_pl(inc_l, 63));
         }
     }
 }
@@ -1389,13 +1299,9 @@ __device__ __forceinline__ void orf_quarter(const OrfCtx& o, const bool has, con
     const double NEG_INF = -__builtin_huge_val();
     const int sl = lane & 15, gb = lane & 48;
     const int strand = o.strand, step = o.step, p = o.p, ncod = has ? o.ncod : 0;
-    const int nm = has ? max(0, min(CS_MODELS, o.cc.y - m0)) : 0;
-    double* csp[CS_MODELS]; const ModelScoreConst* mcp[CS_MODELS];
-#pragma unroll
-    for (int m = 0; m < CS_MODELS; m++) {
-        const ChainDesc ch = chains[has ? o.cc.x + m0 + (m < nm ? m : 0) : 0];
-        csp[m] = ca.cscore_raw + ch.off; mcp[m] = &msc[ch.model];
-    }
+    const CsModels md = cs_models(chains, has ? o.cc : make_int2(0, 0), has ? m0 : 0, msc, ca);       // (no ORF: no model, chain 0's pointers unused)
+    const auto& csp = md.csp; const auto& mcp = md.mcp;
+    const int nm = md.nm;
     double carry[CS_MODELS];
 #pragma unroll
     for (int m = 0; m < CS_MODELS; m++) carry[m] = 0.0;
@@ -1462,15 +1368,8 @@ __device__ __forceinline__ void orf_quarter(const OrfCtx& o, const bool has, con
             }
             double ex_c = __shfl_up(inc_c, 1, 16), ex_l = __shfl_up(inc_l, 1, 16);
             if (sl == 0) { ex_c = NEG_INF; ex_l = NEG_INF; }
-            const double run_c = fmax(ex_c, carry_c[m]), run_l = fmax(ex_l, carry_l[m]);
-            if (mine) {
-                double cs = cs0, lfac = lf0;
-                if (!(cs > run_c)) cs -= (run_c - cs);
-                if (!(lfac > run_l)) lfac -= fmax(fmin(run_l - lfac, lfac), 0.0);
-                if (lfac > 3.0 && cs < 0.5 * lfac) cs = 0.5 * lfac;
-                cs += lfac;
-                csp[m][k] = cs;
-            }
+            double run_c = fmax(ex_c, carry_c[m]), run_l = fmax(ex_l, carry_l[m]);            // of the starts further out: copies, nobody reads them back
+            if (mine) csp[m][k] = cs_penalty(cs0, lf0, run_c, run_l);
             carry_c[m] = fmax(carry_c[m], __shfl(inc_c, gb | 15, 64));
             carry_l[m] = fmax(carry_l[m], __shfl(inc_l, gb | 15, 64));
         }
@@ -1480,7 +1379,7 @@ __device__ __forceinline__ void orf_quarter(const OrfCtx& o, const bool has, con
 __global__ void __launch_bounds__(256)
 k_coding_score(const ChainDesc* __restrict__ chains, const int2* __restrict__ contig_chains /* per contig: first chain, count */,
                const int32_t* __restrict__ node_contig_base, int n_contigs, int node_begin, int n_nodes,
-               const uint8_t* __restrict__ dig, const ContigDesc* __restrict__ ct, GroupArrays ga,
+               const ContigDesc* __restrict__ ct, GroupArrays ga,
                const pga_training* __restrict__ models, const ModelScoreConst* __restrict__ msc, ChainArrays ca,
                const double* __restrict__ gil, int il_stride, const int32_t* __restrict__ rank) {
     __shared__ int s_list[256];
@@ -1504,47 +1403,35 @@ k_coding_score(const ChainDesc* __restrict__ chains, const int2* __restrict__ co
         const int t = s_list[threadIdx.x];             // topology index of my stop node
         int lo = 0, hi = n_contigs - 1;
         while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (node_contig_base[mid] <= t) lo = mid; else hi = mid - 1; }
-        const int c = lo;
-        o.cc = contig_chains[c];
-        const ContigDesc cd = ct[c];
-        o.d = ga.df + cd.base;
-        o.strand = ga.strand[t];
-        o.c16 = ga.c16 + (size_t)ga.tile0[c] * 192;
-        o.tbase = node_contig_base[c];
-        o.p = ga.ndx[t]; o.q = ga.stop_val[t]; o.L = cd.len;
-        o.step = o.strand == 1 ? -3 : 3;
-        // codons of the ORF in walk order: x(ci) = p + step * (ci + 1), ci = 0 .. ncod-1
-        if (o.strand == 1) {
-            const int lowb = max(o.q + 1, 0);
-            const int xmin = lowb + (((o.p - lowb) % 3) + 3) % 3;
-            o.ncod = xmin <= o.p - 3 ? (o.p - 3 - xmin) / 3 + 1 : 0;
-        } else {
-            const int highb = min(o.q - 1, o.L - 1);
-            const int xmax = highb - (((highb - o.p) % 3) + 3) % 3;
-            o.ncod = xmax >= o.p + 3 ? (xmax - (o.p + 3)) / 3 + 1 : 0;
-        }
-        if (o.cc.y <= 0) o.ncod = 0;
+        const ContigDesc cd = ct[lo];
+        o = orf_ctx(ga, t, cd.base, cd.len, node_contig_base[lo], ga.tile0[lo], contig_chains[lo]);
     }
     const bool is_long = mine && o.ncod > CS_LONG;
-    if (mine && !is_long && o.ncod > 0) orf_serial(o, chains, models, msc, ca, gil, il_stride, rank);
+    // The short ORFs, a lane each, CS_MODELS columns of their contigs at a time.  The whole wavefront calls the walk (orf_serial
+    // wants that, or leading lanes): a lane with nothing to walk in a round brings an empty ORF without models.  Pair loads where
+    // every lane that walks may (they need neighbours), else gathers, for the whole wavefront alike: the values are the same.
+    const int ncols = mine && !is_long && o.ncod > 0 ? o.cc.y : 0;
+    for (int m0 = 0; __any(m0 < ncols); m0 += CS_MODELS) {
+        const bool walks = m0 < ncols;
+        OrfCtx s = o;
+        if (!walks) { s.ncod = 0; s.cc = make_int2(0, 0); }
+        const int sm0 = walks ? m0 : 0;
+        const CsModels md = cs_models(chains, s.cc, sm0, msc, ca);
+        if (gil != nullptr && __all(!walks || tab_pairs_ok(chains, rank, s.cc, sm0, md.nm, il_stride)))
+            orf_serial(s, md, TabPairs{gil + (walks ? rank[chains[s.cc.x + sm0].model] : 0), il_stride, md.nm});
+        else
+            orf_serial(s, md, tab_gather(chains, models, s.cc, sm0, md.nm));
+    }
     // long ORFs of this wave, one after the other, all 64 lanes on each
     unsigned long long longs = __ballot(is_long);
     while (longs) {
         const int src = __builtin_ctzll(longs);
         longs &= longs - 1ull;
-        OrfCtx w;
-        const unsigned long long pd = (unsigned long long)o.d, pp = (unsigned long long)o.c16;
-        auto bc64 = [&](unsigned long long v) {
-            const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)v, src);
-            const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(v >> 32), src);
-            return ((unsigned long long)hi << 32) | lo;
-        };
-        w.d = (const uint8_t*)bc64(pd); w.c16 = (const int32_t*)bc64(pp);
-        w.tbase = __builtin_amdgcn_readlane(o.tbase, src); w.p = __builtin_amdgcn_readlane(o.p, src); w.q = __builtin_amdgcn_readlane(o.q, src);
-        w.L = __builtin_amdgcn_readlane(o.L, src); w.strand = __builtin_amdgcn_readlane(o.strand, src); w.step = __builtin_amdgcn_readlane(o.step, src);
-        w.ncod = __builtin_amdgcn_readlane(o.ncod, src);
-        w.cc.x = __builtin_amdgcn_readlane(o.cc.x, src); w.cc.y = __builtin_amdgcn_readlane(o.cc.y, src);
-        orf_wave(w, lane, chains, models, msc, ca);
+        const OrfCtx w = o.of_lane(src);
+        for (int m0 = 0; m0 < w.cc.y; m0 += CS_MODELS) {
+            const CsModels md = cs_models(chains, w.cc, m0, msc, ca);
+            orf_wave(w, lane, md, tab_gather(chains, models, w.cc, m0, md.nm));
+        }
     }
 }
 
@@ -1568,9 +1455,8 @@ constexpr int CS_CLASSES = 12;                         // ORF length classes of 
 __global__ void __launch_bounds__(CS_TASK_THREADS)
 k_coding_score_quads(const CsTask* __restrict__ tasks, const CsEntry* __restrict__ entries, const ChainDesc* __restrict__ chains,
                      const int2* __restrict__ contig_chains, const int32_t* __restrict__ node_contig_base,
-                     const uint8_t* __restrict__ dig, const ContigDesc* __restrict__ ct, GroupArrays ga,
-                     const pga_training* __restrict__ models, const ModelScoreConst* __restrict__ msc, ChainArrays ca,
-                     const double* __restrict__ gil, int il_stride, const int32_t* __restrict__ rank, const int cs_wave, unsigned long long* __restrict__ prof,
+                     const ContigDesc* __restrict__ ct, GroupArrays ga, const ModelScoreConst* __restrict__ msc, ChainArrays ca,
+                     const double* __restrict__ gil, int il_stride, const int cs_wave, unsigned long long* __restrict__ prof,
                      const int q_classes /* length classes 1 .. q_classes go four to a wave: 4 = ORFs beyond 192 codons, 3 = beyond 256 */) {
     extern __shared__ __attribute__((aligned(16))) double s_quad[];                  // [4096][4]
     __shared__ int s_pre[CS_TASK_MAX_ENTRIES + 1];      // first node (task-local numbering) of every entry
@@ -1661,40 +1547,29 @@ k_coding_score_quads(const CsTask* __restrict__ tasks, const CsEntry* __restrict
         mark(1);
         const int cnt = s_count, n_long = s_cls[0];       // after the placement s_cls[k] is where class k ends
         auto orf_of = [&](const int packed, int& m0) {
-            OrfCtx o{};
             const int lo = packed >> 13, loc = base + (packed & 8191);
             const CsEnt en = s_ent[lo];
             m0 = en.m0;
-            const int tt = en.tbase + en.first + (loc - s_pre[lo]);
-            o.cc = make_int2(en.ccx, en.ccy);
-            o.d = ga.df + en.base;
-            o.strand = ga.strand[tt];
-            o.c16 = ga.c16 + (size_t)en.tile0 * 192;
-            o.tbase = en.tbase;
-            o.p = ga.ndx[tt]; o.q = ga.stop_val[tt]; o.L = en.len; o.kstop = tt - en.tbase;
-            o.step = o.strand == 1 ? -3 : 3;
-            o.ncod = o.cc.y <= 0 ? 0 : orf_codons(o.p, o.q, o.strand, o.L);
-            return o;
+            return orf_ctx(ga, en.tbase + en.first + (loc - s_pre[lo]), en.base, en.len, en.tbase, en.tile0, make_int2(en.ccx, en.ccy));
         };
-        // Waves pull work until the round is empty (no wave waits for another before the end of the round).
-        // long ORFs (the first n_long entries): one per wave at a time, all 64 lanes on each
-        for (;;) {
+        const TabLds tab{s_quad};
+        // Waves pull work until the round is empty (no wave waits for another before the end of the round): the next n entries
+        // of the list, counted by `next`
+        auto pull = [&](int* const next, const int n) {
             int k = 0;
-            if (lane == 0) k = atomicAdd(&s_next_long, 1);
-            k = __builtin_amdgcn_readfirstlane(k);
-            if (k >= n_long) break;
+            if (lane == 0) k = atomicAdd(next, n);
+            return __builtin_amdgcn_readfirstlane(k);
+        };
+        // long ORFs (the first n_long entries): one per wave at a time, all 64 lanes on each
+        for (int k; (k = pull(&s_next_long, 1)) < n_long;) {
             int m0;
             const OrfCtx w = orf_of(s_list[k], m0);          // the same entry in every lane
-            if (w.ncod > 0) orf_wave(w, lane, chains, models, msc, ca, s_quad, m0, m0 + 4);
+            if (w.ncod > 0) orf_wave(w, lane, cs_models(chains, w.cc, m0, msc, ca), tab);
         }
         mark(2);
         // long ORFs, four to a wave
         const int q_end = s_qend;
-        for (;;) {
-            int k = 0;
-            if (lane == 0) k = atomicAdd(&s_next_q, 4);
-            k = __builtin_amdgcn_readfirstlane(k);
-            if (k >= q_end) break;
+        for (int k; (k = pull(&s_next_q, 4)) < q_end;) {
             const int e = k + (lane >> 4);
             int m0 = 0;
             OrfCtx o{};
@@ -1704,16 +1579,12 @@ k_coding_score_quads(const CsTask* __restrict__ tasks, const CsEntry* __restrict
         }
         mark(3);
         // the others, 64 of similar length per wave, longest class first
-        for (;;) {
-            int lb = 0;
-            if (lane == 0) lb = atomicAdd(&s_next, 64);
-            lb = __builtin_amdgcn_readfirstlane(lb);
-            if (lb >= cnt) break;
+        for (int lb; (lb = pull(&s_next, 64)) < cnt;) {
             if (lb + lane < cnt) {
                 int m0;
                 const OrfCtx o = orf_of(s_list[lb + lane], m0);
                 if (prof && lane == 0) atomicAdd(&prof[9], __builtin_readcyclecounter() - tp);
-                if (o.ncod > 0) orf_serial_quad(o, chains, msc, ca, s_quad, m0, prof);
+                if (o.ncod > 0) orf_serial(o, cs_models(chains, o.cc, m0, msc, ca), tab, prof);
             }
             if (prof && lane == 0) atomicAdd(&prof[8], 1ull);
         }
@@ -3387,8 +3258,8 @@ void pga_launch_coding_score(const CodingScoreLaunch& a) {
         }
         unsigned long long* const d_prof = a.profile ? profile_begin(PROF_CS, a.st) : nullptr;
         hipLaunchKernelGGL(k_coding_score_quads, dim3((unsigned)a.n_cs_tasks), dim3(CS_TASK_THREADS), lds, a.st, (const CsTask*)a.d_cs_tasks,
-                           (const CsEntry*)a.d_cs_entries, a.d_all_chains, a.d_contig_chains, a.d_node_contig_base, a.d_dig, a.d_ct, *a.ga, a.d_models, a.d_msc, *a.ca,
-                           a.d_gil, a.il_stride, a.d_rank, a.cs_wave, d_prof, a.qclasses);
+                           (const CsEntry*)a.d_cs_entries, a.d_all_chains, a.d_contig_chains, a.d_node_contig_base, a.d_ct, *a.ga, a.d_msc, *a.ca,
+                           a.d_gil, a.il_stride, a.cs_wave, d_prof, a.qclasses);
         if (a.profile) {
             unsigned long long h[16];
             profile_read(d_prof, a.st, h);
@@ -3399,7 +3270,7 @@ void pga_launch_coding_score(const CodingScoreLaunch& a) {
         }
     } else
         hipLaunchKernelGGL(k_coding_score, dim3(nblocks(a.group_nodes, 256)), dim3(256), 0, a.st, a.d_all_chains, a.d_contig_chains, a.d_node_contig_base,
-                           a.n_contigs, 0, a.group_nodes, a.d_dig, a.d_ct, *a.ga, a.d_models, a.d_msc, *a.ca, a.d_gil, a.il_stride, a.d_rank);
+                           a.n_contigs, 0, a.group_nodes, a.d_ct, *a.ga, a.d_models, a.d_msc, *a.ca, a.d_gil, a.il_stride, a.d_rank);
 }
 
 bool pga_launch_start_scores(const StartScoreLaunch& a) {

@@ -16,11 +16,11 @@ pytestmark = pytest.mark.gpu
 
 KNOBS = ("PGA_CS_LDS", "PGA_CS_WAVE", "PGA_CS_QCLASSES", "PGA_CS_TASK_NODES")
 VARIANTS = {
-    "default": {},                                                  # LDS form: orf_wave above 2048, orf_quarter 257 .. 2048, orf_serial_quad below
-    "global": {"PGA_CS_LDS": "0"},                                  # k_coding_score: orf_serial up to CS_LONG = 192, orf_wave above
+    "default": {},                                                  # LDS form: orf_wave above 2048, orf_quarter 257 .. 2048, orf_serial (tables in LDS) below
+    "global": {"PGA_CS_LDS": "0"},                                  # k_coding_score: orf_serial (tables in global memory) up to CS_LONG = 192, orf_wave above
     "wave64": {"PGA_CS_WAVE": "64"},                                # everything above 64 codons to orf_wave
     "nowave": {"PGA_CS_WAVE": "100000"},                            # nothing to orf_wave: the longest ORFs through orf_quarter
-    "qclasses4": {"PGA_CS_QCLASSES": "4"},                          # 193 .. 256 from orf_serial_quad to orf_quarter
+    "qclasses4": {"PGA_CS_QCLASSES": "4"},                          # 193 .. 256 from orf_serial to orf_quarter
     "pieces256": {"PGA_CS_TASK_NODES": "256"},                      # contigs cut into pieces of 256 nodes
     "pieces256+wave64": {"PGA_CS_TASK_NODES": "256", "PGA_CS_WAVE": "64"},
 }
