@@ -2,14 +2,15 @@
 // mode (ref: lib.pyx:5281-5469).  Host orchestration only; every per-base / per-node stage runs in
 // the HIP kernels of pipeline.hip and dp.hip.  The tail of the reference's _dynamic_programming
 // (traceback untangling), eliminate_bad_genes, Genes._extract and Genes._tweak_final_starts runs on
-// the device as well (tail.inl and the k_tail_* kernels below); the same functions, compiled for the
-// host too, remain as a cross-check (PGA_TAIL=host: one contig per worker thread over the winning
+// the device as well (the kernels of tail.inl over the rules of tail_rules.h); the same rules, compiled
+// for the host too, remain as a cross-check (PGA_TAIL=host: one contig per worker thread over the winning
 // models' nodes brought home).
 #include "pga_internal.h"
 #include "pipeline.h"
 #include "dpw_core.h"
 #include "dev_common.h"
 #include "find_plan.h"
+#include "tail_rules.h"
 
 #include <math.h>
 #include <stdio.h>
@@ -268,223 +269,26 @@ int ensure_pin(pga_ctx* c, const char* name, size_t bytes, void** out, bool fp =
 #define PINSET(var, type, name, count) { void* p__; int rc__ = ensure_pin(c, name, sizeof(type) * (size_t)(count) + 64, &p__, std::is_floating_point<type>::value); if (rc__) return rc__; var = (type*)p__; }
 #define PINBUF(var, type, name, count) type* var; PINSET(var, type, name, count)
 
-// ---- tail: nodes of one contig for its winning model (device functions; one thread walks a contig's path) ----
-struct NodeView {
-    int n;
-    const int32_t* ndx; const int32_t* stop_val; const uint8_t* type; const int8_t* strand; const uint8_t* edge;
-    double* cscore; double* sscore; const double* rscore; const double* uscore; const double* tscore;
-    const int32_t* star_ptr; int32_t* traceb; int32_t* tracef; int8_t* ov_mark; const double* score; uint8_t* elim;
-};
-struct GeneRec { int begin, end, start_ndx, stop_ndx; };
-
-__host__ __device__ inline bool is_stop_n(const NodeView& v, int i) { return v.type[i] == PGA_T_STOP; }
-
-// ref: _connection.h:52-78
-__host__ __device__ double igm_same_h(const NodeView& v, int a, int b, double st_wt) {
-    const int dist = abs(v.ndx[a] - v.ndx[b]);
-    const bool ovl = v.ndx[a] + 2 * v.strand[a] >= v.ndx[b];
-    double r = 0.0;
-    if (v.ndx[a] + 2 == v.ndx[b] || v.ndx[a] == v.ndx[b] + 1) {
-        if (v.strand[a] == 1) { if (v.rscore[b] < 0) r -= v.rscore[b]; if (v.uscore[b] < 0) r -= v.uscore[b]; }
-        else                  { if (v.rscore[a] < 0) r -= v.rscore[a]; if (v.uscore[a] < 0) r -= v.uscore[a]; }
-    }
-    if (dist > 3 * PGA_OPER_DIST) r -= 0.15 * st_wt;
-    else if ((dist <= PGA_OPER_DIST && !ovl) || dist * 4 < PGA_OPER_DIST) r += (2.0 - (double)dist / PGA_OPER_DIST) * 0.15 * st_wt;
-    return r;
-}
-__host__ __device__ inline double igm_h(const NodeView& v, int a, int b, double st_wt) {   // ref: _connection.h:81-91
-    return v.strand[a] == v.strand[b] ? igm_same_h(v, a, b, st_wt) : -0.15 * st_wt;
-}
-
-// The reference walks down from node `from` until it meets a node at position `pos` (the other end of the ORF, which
-// always exists): positions are sorted, so the first hit of that walk is the LAST node at or below `from` with
-// ndx == pos, which a binary search finds in O(log n) loads instead of one dependent load per node of the gene.
-__host__ __device__ inline int walk_down_to(const NodeView& v, int from, int pos) {
-    int a = 0, b = from + 1;                      // first index in [0, from] with ndx > pos
-    while (a < b) { const int m = (a + b) >> 1; if (v.ndx[m] <= pos) a = m + 1; else b = m; }
-    return a - 1;
-}
-
-// ref: lib.pyx:1253-1295 (_disentangle_overlaps, _max_forward_pointers)
-__host__ __device__ int untangle(NodeView& v, int mx, int32_t* __restrict__ path) {
-    // Every test reads its operands first, unconditionally: the loads of one step then leave together instead of one
-    // round trip per `&&`.
-    for (int p = mx, nx = v.traceb[p]; nx != -1; p = nx, nx = v.traceb[p]) {
-        const int sp = v.strand[p], sn = v.strand[nx], ov = v.ov_mark[p], np = v.ndx[p], nn = v.ndx[nx];
-        const bool stp = is_stop_n(v, p), stn = is_stop_n(v, nx);
-        if ((sp == -1) & stp & (sn == 1) & stn & (ov != -1) & (np > nn)) {
-            const int tmp = v.star_ptr[3 * p + ov];
-            const int k = walk_down_to(v, tmp, v.stop_val[tmp]);
-            v.traceb[p] = tmp; v.traceb[tmp] = k; v.ov_mark[k] = -1; v.traceb[k] = nx;
-            nx = tmp;                                  // the walk continues through the nodes just spliced in
-        }
-    }
-    for (int p = mx, nx = v.traceb[p]; nx != -1; p = nx, nx = v.traceb[p]) {
-        const int sp = v.strand[p], sn = v.strand[nx], np = v.ndx[p], nn = v.ndx[nx];
-        const bool stp = is_stop_n(v, p), stn = is_stop_n(v, nx);
-        const bool p_rb = sp == -1 && !stp, p_fs = sp == 1 && stp, p_rs = sp == -1 && stp;
-        const bool n_fs = sn == 1 && stn, n_rs = sn == -1 && stn;
-        int ins = -1;
-        if (p_rb && n_fs) ins = walk_down_to(v, p, v.stop_val[p]);
-        if (p_fs && n_fs) ins = v.star_ptr[3 * nx + np % 3];
-        if (p_rs && n_rs) ins = v.star_ptr[3 * p + nn % 3];
-        if (ins != -1) { v.traceb[p] = ins; v.traceb[ins] = nx; nx = ins; }
-    }
-    // forward pointers; the nodes of the path are also listed (from mx back to its head) so that the later passes
-    // read them with independent loads instead of chasing pointers again
-    int cnt = 0;
-    int p = mx;
-    for (; v.traceb[p] != -1; p = v.traceb[p]) { path[cnt++] = p; v.tracef[v.traceb[p]] = p; }
-    path[cnt++] = p;
-    return cnt;
-}
-
-// Prodigal dprog.c eliminate_bad_genes (call sites ref: lib.pyx:5308, 5369).  path[cnt-1] is the head of the path,
-// path[0] its last node (ipath).
-__host__ __device__ void eliminate_bad_genes(NodeView& v, const int32_t* __restrict__ path, int cnt, double st_wt) {
-    for (int q = cnt - 1; q >= 1; q--) {
-        const int p = path[q], f = path[q - 1];
-        const int sp = v.strand[p]; const bool stp = is_stop_n(v, p);
-        if (sp == 1 && stp) v.sscore[f] += igm_h(v, p, f, st_wt);
-        if (sp == -1 && !stp) v.sscore[p] += igm_h(v, p, f, st_wt);
-    }
-    for (int q = cnt - 1; q >= 1; q--) {
-        const int p = path[q], f = path[q - 1];
-        const int sp = v.strand[p]; const bool stp = is_stop_n(v, p);
-        const double gp = v.cscore[p] + v.sscore[p], gf = v.cscore[f] + v.sscore[f];
-        if (sp == 1 && !stp && gp < 0) { v.elim[p] = 1; v.elim[f] = 1; }
-        if (sp == -1 && stp && gf < 0) { v.elim[p] = 1; v.elim[f] = 1; }
-    }
-}
-
-// The same on several host threads (long paths): every node's start score receives at most two terms, in path order
-// (as the node after a forward stop, then as a reverse start), so nodes are independent; the elimination pass reads the
-// finished scores.
-void eliminate_bad_genes_mt(NodeView& v, const int32_t* path, int cnt, double st_wt, WorkerPool& pool, int threads) {
+// ---- tail on host threads (PGA_TAIL=host): the rules are tail_rules.h's, here is only how long paths and gene lists are split ----
+// eliminate_bad_genes on several threads: path positions are independent in either loop (elim_add_terms); the second loop reads
+// the finished scores.
+void eliminate_bad_genes_mt(const NodeView& v, const int32_t* path, int cnt, double st_wt, WorkerPool& pool, int threads) {
     if (cnt < 4096 || threads <= 1) { eliminate_bad_genes(v, path, cnt, st_wt); return; }
     std::atomic<int> next(cnt - 1);
-    const std::function<void()> add = [&]() {
+    bool marking = false;
+    const std::function<void()> work = [&]() {          // 512 path positions at a time, from the head
+        const int lo = marking ? 1 : 0;                  // a pair is path[q], path[q - 1]
         for (;;) {
             const int hi = next.fetch_sub(512);
-            if (hi < 0) break;
-            for (int q = hi; q > hi - 512 && q >= 0; q--) {          // node x = path[q]
-                const int x = path[q];
-                if (q + 1 <= cnt - 1) {                               // x follows p = path[q + 1]
-                    const int p = path[q + 1];
-                    if (v.strand[p] == 1 && is_stop_n(v, p)) v.sscore[x] += igm_h(v, p, x, st_wt);
-                }
-                if (q >= 1 && v.strand[x] == -1 && !is_stop_n(v, x)) v.sscore[x] += igm_h(v, x, path[q - 1], st_wt);
+            if (hi < lo) break;
+            for (int q = hi; q > hi - 512 && q >= lo; q--) {
+                if (marking) elim_mark_pair(v, path, q); else elim_add_terms(v, path, cnt, q, st_wt);
             }
         }
     };
-    pool.run(add, threads);
-    next.store(cnt - 1);
-    const std::function<void()> mark = [&]() {
-        for (;;) {
-            const int hi = next.fetch_sub(512);
-            if (hi < 1) break;
-            for (int q = hi; q > hi - 512 && q >= 1; q--) {
-                const int p = path[q], f = path[q - 1];
-                const int sp = v.strand[p]; const bool stp = is_stop_n(v, p);
-                const double gp = v.cscore[p] + v.sscore[p], gf = v.cscore[f] + v.sscore[f];
-                if (sp == 1 && !stp && gp < 0) { v.elim[p] = 1; v.elim[f] = 1; }
-                if (sp == -1 && stp && gf < 0) { v.elim[p] = 1; v.elim[f] = 1; }
-            }
-        }
-    };
-    pool.run(mark, threads);
-}
-
-// ref: lib.pyx:3231-3270 (Genes._extract); returns the number of genes written to `out`
-__host__ __device__ int extract_genes(const NodeView& v, const int32_t* __restrict__ path, int cnt, GeneRec* out) {
-    int b = 0, e = 0, s = 0, t = 0, ng = 0;
-    for (int q = cnt - 1; q >= 0; q--) {
-        const int p = path[q];
-        const int el = v.elim[p], sp = v.strand[p], np = v.ndx[p]; const bool stp = is_stop_n(v, p);
-        if (el == 1) continue;
-        if (sp == 1) {
-            if (!stp) { b = np + 1; s = p; }
-            else { e = np + 3; t = p; out[ng++] = GeneRec{b, e, s, t}; }
-        } else {
-            if (!stp) { e = np + 1; s = p; out[ng++] = GeneRec{b, e, s, t}; }
-            else { b = np - 1; t = p; }
-        }
-    }
-    return ng;
-}
-
-// ref: lib.pyx:3272-3401 (Genes._tweak_final_starts)
-// one gene; `prev` / `next` are its neighbours as the reference's in-order loop would see them
-// (prev already tweaked, next not yet)
-__host__ __device__ void tweak_one(const NodeView& v, const GeneRec* prev, GeneRec& cur, const GeneRec* next, double w, int maxov) {
-    const int nn = v.n;
-    {
-        const int ndx = cur.start_ndx;
-        const double sc = v.sscore[ndx] + v.cscore[ndx];
-        double ig = 0.0;
-        const bool prev_fwd = prev && v.strand[prev->start_ndx] == 1, prev_rev = prev && v.strand[prev->start_ndx] == -1;
-        const bool next_fwd = next && v.strand[next->start_ndx] == 1, next_rev = next && v.strand[next->start_ndx] == -1;
-        if (v.strand[ndx] == 1 && prev_fwd) ig = igm_same_h(v, prev->stop_ndx, ndx, w);
-        if (v.strand[ndx] == 1 && prev_rev) ig = -0.15 * w;
-        if (v.strand[ndx] == -1 && next_fwd) ig = -0.15 * w;
-        if (v.strand[ndx] == -1 && next_rev) ig = igm_same_h(v, ndx, next->stop_ndx, w);
-        int mi[2] = {-1, -1}; double ms[2] = {0, 0}, mg[2] = {0, 0};
-        const int sv_ndx = v.stop_val[ndx];
-        // the 200 neighbours forty at a time: what rules nearly all of them out (a stop node, or a node of another ORF) is asked for
-        // in one go -- one memory round trip per forty candidates instead of one per candidate, on the device one thread walks them
-        constexpr int TWB = 40;             // 200 = 5 x 40
-        for (int j0 = ndx - 100; j0 < ndx + 100; j0 += TWB) {
-          unsigned long long pass = 0;          // start nodes of the gene's own ORF among the forty, then taken in index order
-#pragma unroll
-          for (int q = 0; q < TWB; q++) {
-            const int j = j0 + q;
-            const int jj = j < 0 ? 0 : (j >= nn ? nn - 1 : j);
-            const bool ok = !(is_stop_n(v, jj) | (v.stop_val[jj] != sv_ndx)) && j >= 0 && j < nn && j != ndx;
-            pass |= (unsigned long long)ok << q;
-          }
-          while (pass) {
-            const int q = __builtin_ctzll(pass);
-            pass &= pass - 1ull;
-            const int j = j0 + q;
-            double tg = 0.0;
-            if (v.strand[j] == 1 && prev_fwd) {
-                if (v.ndx[prev->stop_ndx] - v.ndx[j] > maxov) continue;
-                tg = igm_same_h(v, prev->stop_ndx, j, w);
-            }
-            if (v.strand[j] == 1 && prev_rev) { if (v.ndx[prev->start_ndx] - v.ndx[j] >= 0) continue; tg = -0.15 * w; }
-            if (v.strand[j] == -1 && next_fwd) { if (v.ndx[j] - v.ndx[next->start_ndx] >= 0) continue; tg = -0.15 * w; }
-            if (v.strand[j] == -1 && next_rev) {
-                if (v.ndx[j] - v.ndx[next->stop_ndx] > maxov) continue;
-                tg = igm_same_h(v, j, next->stop_ndx, w);
-            }
-            const double cs = v.cscore[j] + v.sscore[j];
-            if (mi[0] == -1) { mi[0] = j; ms[0] = cs; mg[0] = tg; }
-            else if (cs + tg > ms[0]) { mi[1] = mi[0]; ms[1] = ms[0]; mg[1] = mg[0]; mi[0] = j; ms[0] = cs; mg[0] = tg; }
-            else if (mi[1] == -1 || cs + tg > ms[1]) { mi[1] = j; ms[1] = cs; mg[1] = tg; }
-          }
-        }
-        for (int k = 0; k < 2; k++) {
-            const int m = mi[k];
-            if (m == -1) continue;
-            if (v.tscore[m] < v.tscore[ndx] && ms[k] - v.tscore[m] >= sc - v.tscore[ndx] + w && v.rscore[m] > v.rscore[ndx] &&
-                v.uscore[m] > v.uscore[ndx] && v.cscore[m] > v.cscore[ndx] && abs(v.ndx[m] - v.ndx[ndx]) > 15) {
-                ms[k] += v.tscore[ndx] - v.tscore[m];
-            } else if (abs(v.ndx[m] - v.ndx[ndx]) <= 15 && v.rscore[m] + v.tscore[m] > v.rscore[ndx] + v.tscore[ndx] &&
-                       v.edge[ndx] == 0 && v.edge[m] == 0) {
-                if (v.cscore[ndx] > v.cscore[m]) ms[k] += v.cscore[ndx] - v.cscore[m];
-                if (v.uscore[ndx] > v.uscore[m]) ms[k] += v.uscore[ndx] - v.uscore[m];
-                if (ig > mg[k]) ms[k] += ig - mg[k];
-            } else ms[k] = -1000.0;
-        }
-        int pick = -1;
-        for (int k = 0; k < 2; k++) {
-            if (mi[k] == -1) continue;
-            if (pick == -1 && ms[k] + mg[k] > sc + ig) pick = k;
-            else if (pick >= 0 && ms[k] + mg[k] > ms[pick] + mg[pick]) pick = k;
-        }
-        if (pick != -1 && v.strand[mi[pick]] == 1) { cur.start_ndx = mi[pick]; cur.begin = v.ndx[mi[pick]] + 1; }
-        else if (pick != -1 && v.strand[mi[pick]] == -1) { cur.start_ndx = mi[pick]; cur.end = v.ndx[mi[pick]] + 1; }
-    }
+    pool.run(work, threads);
+    next.store(cnt - 1); marking = true;
+    pool.run(work, threads);
 }
 
 // In-order semantics of the reference loop, evaluated in parallel when a contig has many genes: every
@@ -514,7 +318,7 @@ void tweak_final_starts(const NodeView& v, std::vector<GeneRec>& g, double w, in
     }
 }
 
-// ---- tail kernels --------------------------------------------------------------------------------------
+// ---- tail kernels (tail.inl): what they are handed --------------------------------------------------------------------------------------
 struct OutArrays;
 struct TailDesc {          // one per contig
     int64_t out_off;       // first node of the contig's winning chain in the gathered arrays
@@ -586,369 +390,8 @@ k_gather_winners(const WinDesc* __restrict__ wd, int n_win, int64_t out_begin, i
 struct GeneNodeAttr {
     double cscore, sscore, rscore, uscore, tscore, mot_score;
     float gc_cont; int32_t mot_ndx;
-    uint8_t edge, rbs0, rbs1, mot_len, mot_spacer, _pad[3];
+    uint8_t edge, rbs[2], mot_len, mot_spacer, _pad[3];
 };
-__global__ void __launch_bounds__(256)
-k_gather_gene_nodes(const int64_t* __restrict__ idx, int n, OutArrays o, GeneNodeAttr* __restrict__ out) {
-    const int t = blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= n) return;
-    const int64_t g = idx[t];
-    GeneNodeAttr a;
-    a.cscore = o.cscore[g]; a.sscore = o.sscore[g]; a.rscore = o.rscore[g]; a.uscore = o.uscore[g]; a.tscore = o.tscore[g];
-    a.mot_score = o.mot_score[g]; a.gc_cont = o.gc_cont[g]; a.mot_ndx = o.mot_ndx[g];
-    a.edge = o.edge[g]; a.rbs0 = o.rbs[2 * g]; a.rbs1 = o.rbs[2 * g + 1]; a.mot_len = o.mot_len[g]; a.mot_spacer = o.mot_spacer[g];
-    a._pad[0] = a._pad[1] = a._pad[2] = 0;
-    out[t] = a;
-}
-
-__device__ inline NodeView node_view(const TailDesc& d, const OutArrays& o, int32_t* tracef, uint8_t* elim) {
-    const int64_t oo = d.out_off;
-    if (o.direct) {
-        const int64_t t = d.topo_off, a = d.dp_off; const int g = d.group;
-        return NodeView{d.n, o.g_ndx[g] + t, o.g_stop_val[g] + t, o.g_type[g] + t, o.g_strand[g] + t, o.c_edge + a,
-                        const_cast<double*>(o.c_cscore) + a, o.sscore_dp + oo, o.c_rscore + a, o.c_uscore + a, o.c_tscore + a,
-                        o.c_star_ptr + 3 * a, o.traceb + oo, tracef + oo, o.ov_mark + oo, o.d_score + a, elim + oo};
-    }
-    return NodeView{d.n, o.ndx + oo, o.stop_val + oo, o.type + oo, o.strand + oo, o.edge_dp + oo,
-                    o.cscore_dp + oo, o.sscore_dp + oo, o.rscore_dp + oo, o.uscore_dp + oo, o.tscore_dp + oo,
-                    o.star_ptr + 3 * oo, o.traceb + oo, tracef + oo, o.ov_mark + oo, o.score + oo, elim + oo};
-}
-
-// One thread per contig: untangle the traceback, eliminate bad genes, list the genes
-// (ref: lib.pyx:1253-1311, 5308 / 5369, 3231-3270).  A path is a pointer chase, so contigs are the parallel axis.
-__global__ void __launch_bounds__(64)
-k_tail_path(const TailDesc* __restrict__ td, int n_contigs, OutArrays o, int32_t* tracef, uint8_t* elim, int32_t* __restrict__ path,
-            GeneRec* __restrict__ genes, int32_t* __restrict__ n_genes) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n_contigs) return;
-    const TailDesc d = td[i];
-    int ng = 0;
-    if (d.n > 0 && d.mx >= 0) {
-        NodeView v = node_view(d, o, tracef, elim);
-        int32_t* pl = path + d.out_off;                  // at most n entries
-        const int cnt = untangle(v, d.mx, pl);
-        if (v.traceb[d.mx] != -1) {                      // ipath != -1
-            eliminate_bad_genes(v, pl, cnt, d.st_wt);
-            ng = extract_genes(v, pl, cnt, genes + d.gene_off);
-        }
-    }
-    n_genes[i] = ng;
-}
-
-__device__ inline int contig_of_slot(const TailDesc* __restrict__ td, int n_contigs, int64_t slot) {
-    int lo = 0, hi = n_contigs - 1;
-    while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (td[mid].gene_off <= slot) lo = mid; else hi = mid - 1; }
-    return lo;
-}
-
-// ref: lib.pyx:3272-3401 (Genes._tweak_final_starts).  The reference loop runs in gene order: gene i sees its
-// predecessor already tweaked and its successor untouched.  Here every gene is first tweaked against its ORIGINAL
-// neighbours (one thread per gene), then one thread per contig redoes, in order, the genes whose predecessor did
-// change (tweaks are rare).
-__global__ void __launch_bounds__(256)
-k_tail_tweak(const TailDesc* __restrict__ td, int n_contigs, int64_t n_slots, OutArrays o, int32_t* tracef, uint8_t* elim,
-             const GeneRec* __restrict__ orig, GeneRec* __restrict__ out, const int32_t* __restrict__ n_genes, int maxov,
-             uint8_t* __restrict__ changed, int32_t* __restrict__ n_changed) {
-    const int64_t slot = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (slot >= n_slots) return;
-    const int c = contig_of_slot(td, n_contigs, slot);
-    const TailDesc d = td[c];
-    const int g = (int)(slot - d.gene_off), ng = n_genes[c];
-    if (g >= ng) return;
-    const NodeView v = node_view(d, o, tracef, elim);
-    const GeneRec* base = orig + d.gene_off;
-    GeneRec cur = base[g];
-    tweak_one(v, g > 0 ? &base[g - 1] : nullptr, cur, g < ng - 1 ? &base[g + 1] : nullptr, d.st_wt, maxov);
-    out[slot] = cur;
-    // only a reverse-strand predecessor hands its START to the next gene's tweak (a forward one hands its stop, which
-    // never moves): that is the one case the in-order pass has to revisit
-    const bool moved = cur.start_ndx != base[g].start_ndx && v.strand[cur.start_ndx] == -1;
-    changed[slot] = moved ? 1 : 0;
-    if (moved) atomicAdd(&n_changed[c], 1);
-}
-// The same over the genes themselves instead of over their (mostly empty) slots: gene number q of the batch is gene q - gpre[c]
-// of the contig c with gpre[c] <= q < gpre[c + 1] (gpre = running sum of n_genes, k_gene_prefix).  With many short contigs the
-// genes are a few per contig: one thread per slot leaves a handful of busy lanes in each of twenty thousand wavefronts, each of
-// which takes as long as its slowest lane; packed, the same lanes fill a few hundred.
-// the tail's starting state in one launch (it was four or five memsets): tracef = -1, elim = 0 for every gathered node; the per-contig
-// counters of changed genes and of genes; the per-chain counters of the many-launch path
-__global__ void __launch_bounds__(256)
-k_tail_init(int32_t* __restrict__ tracef, uint8_t* __restrict__ elim, const int64_t n_nodes, int32_t* __restrict__ nchanged, int32_t* __restrict__ ngenes /* or nullptr */,
-            const int n_contigs, int32_t* __restrict__ seg_cnt /* or nullptr */, const int n_segs) {
-    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, stride = (int64_t)gridDim.x * blockDim.x;
-    for (int64_t k = t; k <= n_nodes; k += stride) { tracef[k] = -1; elim[k] = 0; }
-    for (int64_t k = t; k <= n_contigs; k += stride) { nchanged[k] = 0; if (ngenes != nullptr) ngenes[k] = 0; }
-    if (seg_cnt != nullptr) for (int64_t k = t; k < n_segs; k += stride) seg_cnt[k] = 0;
-}
-
-__global__ void __launch_bounds__(1024)
-k_gene_prefix(const int32_t* __restrict__ n_genes, int n_contigs, int32_t* __restrict__ gpre) {
-    __shared__ int s_w[16];
-    __shared__ int s_carry;
-    const int t = threadIdx.x, lane = t & 63, w = t >> 6;
-    if (t == 0) s_carry = 0;
-    __syncthreads();
-    for (int base = 0; base < n_contigs; base += 1024) {
-        const int v = base + t < n_contigs ? n_genes[base + t] : 0;
-        int inc = v;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) { const int x = __shfl_up(inc, o, 64); if (lane >= o) inc += x; }
-        if (lane == 63) s_w[w] = inc;
-        __syncthreads();
-        int run = s_carry + inc - v;
-        for (int k = 0; k < w; k++) run += s_w[k];
-        if (base + t < n_contigs) gpre[base + t] = run;
-        __syncthreads();
-        if (t == 1023) s_carry = run + v;
-        __syncthreads();
-    }
-    if (t == 0) gpre[n_contigs] = s_carry;
-}
-__global__ void __launch_bounds__(256)
-k_tail_tweak_packed(const TailDesc* __restrict__ td, int n_contigs, OutArrays o, int32_t* tracef, uint8_t* elim,
-                    const GeneRec* __restrict__ orig, GeneRec* __restrict__ out, const int32_t* __restrict__ n_genes, int maxov,
-                    uint8_t* __restrict__ changed, int32_t* __restrict__ n_changed, const int32_t* __restrict__ gpre) {
-    const int total = gpre[n_contigs];
-    for (int q = blockIdx.x * blockDim.x + threadIdx.x; q < total; q += gridDim.x * blockDim.x) {
-        int lo = 0, hi = n_contigs - 1;
-        while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (gpre[mid] <= q) lo = mid; else hi = mid - 1; }
-        const int c = lo, g = q - gpre[c], ng = n_genes[c];
-        const TailDesc d = td[c];
-        const NodeView v = node_view(d, o, tracef, elim);
-        const GeneRec* base = orig + d.gene_off;
-        GeneRec cur = base[g];
-        tweak_one(v, g > 0 ? &base[g - 1] : nullptr, cur, g < ng - 1 ? &base[g + 1] : nullptr, d.st_wt, maxov);
-        out[d.gene_off + g] = cur;
-        const bool moved = cur.start_ndx != base[g].start_ndx && v.strand[cur.start_ndx] == -1;
-        changed[d.gene_off + g] = moved ? 1 : 0;
-        if (moved) atomicAdd(&n_changed[c], 1);
-    }
-}
-// tweak_one with the wavefront on ONE gene: the 200 candidate nodes are filtered and priced by the lanes (that is where the
-// memory traffic is), the few that pass are then merged one after the other in index order, as the reference's loop
-// meets them -- its two-best bookkeeping depends on that order.  Every lane returns the same record.
-__device__ void tweak_one_wave(const NodeView& v, const GeneRec* prev, GeneRec& cur, const GeneRec* next, double w, int maxov, const int lane) {
-    const int nn = v.n;
-    const int ndx = cur.start_ndx;
-    const double sc = v.sscore[ndx] + v.cscore[ndx];
-    double ig = 0.0;
-    const bool prev_fwd = prev && v.strand[prev->start_ndx] == 1, prev_rev = prev && v.strand[prev->start_ndx] == -1;
-    const bool next_fwd = next && v.strand[next->start_ndx] == 1, next_rev = next && v.strand[next->start_ndx] == -1;
-    if (v.strand[ndx] == 1 && prev_fwd) ig = igm_same_h(v, prev->stop_ndx, ndx, w);
-    if (v.strand[ndx] == 1 && prev_rev) ig = -0.15 * w;
-    if (v.strand[ndx] == -1 && next_fwd) ig = -0.15 * w;
-    if (v.strand[ndx] == -1 && next_rev) ig = igm_same_h(v, ndx, next->stop_ndx, w);
-    int mi[2] = {-1, -1}; double ms[2] = {0, 0}, mg[2] = {0, 0};
-    const int sv_ndx = v.stop_val[ndx];
-    for (int base = ndx - 100; base < ndx + 100; base += 64) {
-        const int j = base + lane;
-        bool cand = j >= 0 && j < nn && j != ndx && j < ndx + 100;
-        double tg = 0.0, cs = 0.0;
-        if (cand) cand = !(is_stop_n(v, j) | (v.stop_val[j] != sv_ndx));
-        if (cand) {
-            const int sj = v.strand[j];
-            if (sj == 1 && prev_fwd) {
-                if (v.ndx[prev->stop_ndx] - v.ndx[j] > maxov) cand = false;
-                else tg = igm_same_h(v, prev->stop_ndx, j, w);
-            }
-            if (cand && sj == 1 && prev_rev) { if (v.ndx[prev->start_ndx] - v.ndx[j] >= 0) cand = false; else tg = -0.15 * w; }
-            if (cand && sj == -1 && next_fwd) { if (v.ndx[j] - v.ndx[next->start_ndx] >= 0) cand = false; else tg = -0.15 * w; }
-            if (cand && sj == -1 && next_rev) {
-                if (v.ndx[j] - v.ndx[next->stop_ndx] > maxov) cand = false;
-                else tg = igm_same_h(v, j, next->stop_ndx, w);
-            }
-            if (cand) cs = v.cscore[j] + v.sscore[j];
-        }
-        unsigned long long m = __ballot(cand);
-        while (m) {
-            const int k = __builtin_ctzll(m);
-            m &= m - 1ull;
-            const int jk = base + k;
-            const double csk = __shfl(cs, k, 64), tgk = __shfl(tg, k, 64);
-            if (mi[0] == -1) { mi[0] = jk; ms[0] = csk; mg[0] = tgk; }
-            else if (csk + tgk > ms[0]) { mi[1] = mi[0]; ms[1] = ms[0]; mg[1] = mg[0]; mi[0] = jk; ms[0] = csk; mg[0] = tgk; }
-            else if (mi[1] == -1 || csk + tgk > ms[1]) { mi[1] = jk; ms[1] = csk; mg[1] = tgk; }
-        }
-    }
-    for (int k = 0; k < 2; k++) {
-        const int m = mi[k];
-        if (m == -1) continue;
-        if (v.tscore[m] < v.tscore[ndx] && ms[k] - v.tscore[m] >= sc - v.tscore[ndx] + w && v.rscore[m] > v.rscore[ndx] &&
-            v.uscore[m] > v.uscore[ndx] && v.cscore[m] > v.cscore[ndx] && abs(v.ndx[m] - v.ndx[ndx]) > 15) {
-            ms[k] += v.tscore[ndx] - v.tscore[m];
-        } else if (abs(v.ndx[m] - v.ndx[ndx]) <= 15 && v.rscore[m] + v.tscore[m] > v.rscore[ndx] + v.tscore[ndx] &&
-                   v.edge[ndx] == 0 && v.edge[m] == 0) {
-            if (v.cscore[ndx] > v.cscore[m]) ms[k] += v.cscore[ndx] - v.cscore[m];
-            if (v.uscore[ndx] > v.uscore[m]) ms[k] += v.uscore[ndx] - v.uscore[m];
-            if (ig > mg[k]) ms[k] += ig - mg[k];
-        } else ms[k] = -1000.0;
-    }
-    int pick = -1;
-    for (int k = 0; k < 2; k++) {
-        if (mi[k] == -1) continue;
-        if (pick == -1 && ms[k] + mg[k] > sc + ig) pick = k;
-        else if (pick >= 0 && ms[k] + mg[k] > ms[pick] + mg[pick]) pick = k;
-    }
-    if (pick != -1 && v.strand[mi[pick]] == 1) { cur.start_ndx = mi[pick]; cur.begin = v.ndx[mi[pick]] + 1; }
-    else if (pick != -1 && v.strand[mi[pick]] == -1) { cur.start_ndx = mi[pick]; cur.end = v.ndx[mi[pick]] + 1; }
-}
-
-// k_tail_tweak for long contigs: a genome has few thousand genes, too few for one thread each to hide the latency of a
-// 200-candidate scan, so every gene gets a wavefront (tweak_one_wave); blockIdx.y = contig, four genes per workgroup.
-__global__ void __launch_bounds__(256)
-k_tail_tweak_wave(const TailDesc* __restrict__ td, int n_contigs, OutArrays o, int32_t* tracef, uint8_t* elim,
-                  const GeneRec* __restrict__ orig, GeneRec* __restrict__ out, const int32_t* __restrict__ n_genes, int maxov,
-                  uint8_t* __restrict__ changed, int32_t* __restrict__ n_changed) {
-    const int c = blockIdx.y, lane = threadIdx.x & 63;
-    const int g = blockIdx.x * 4 + (threadIdx.x >> 6), ng = n_genes[c];
-    if (g >= ng) return;
-    const TailDesc d = td[c];
-    const NodeView v = node_view(d, o, tracef, elim);
-    const GeneRec* base = orig + d.gene_off;
-    GeneRec cur = base[g];
-    GeneRec prev{}, nxt{};
-    if (g > 0) prev = base[g - 1];
-    if (g < ng - 1) nxt = base[g + 1];
-    tweak_one_wave(v, g > 0 ? &prev : nullptr, cur, g < ng - 1 ? &nxt : nullptr, d.st_wt, maxov, lane);
-    if (lane != 0) return;
-    out[d.gene_off + g] = cur;
-    const bool moved = cur.start_ndx != base[g].start_ndx && v.strand[cur.start_ndx] == -1;
-    changed[d.gene_off + g] = moved ? 1 : 0;
-    if (moved) atomicAdd(&n_changed[c], 1);
-}
-
-// The in-order pass over the genes whose predecessor moved (the reference's loop semantics, ref: lib.pyx:3272-3401): one
-// workgroup per contig, windows of 64 genes.  A window only depends on the one before it through its first gene's
-// predecessor, and only if that predecessor -- the last gene of the window before -- was itself redone: so every wavefront
-// first runs its windows assuming it was not (phase 1, all windows side by side), then one wavefront goes over the
-// windows in order and redoes, from their parallel-pass state, those whose assumption failed (phase 2, rare).  Within a
-// window genes are taken in order; a redone gene's 200 candidates are priced by the lanes (tweak_one_wave).
-//   par / ch0   the parallel pass (k_tail_tweak): records against the ORIGINAL neighbours, "start moved on the reverse strand"
-//   fin / chf   the final records and flags
-#define PGA_FIX_MAXWIN 4096
-__global__ void __launch_bounds__(1024)
-k_tail_tweak_fixup(const TailDesc* __restrict__ td, int n_contigs, OutArrays o, int32_t* tracef, uint8_t* elim,
-                   const GeneRec* __restrict__ orig, const GeneRec* __restrict__ par_all, const int32_t* __restrict__ n_genes, int maxov,
-                   const uint8_t* __restrict__ ch0_all, const int32_t* __restrict__ n_changed, GeneRec* __restrict__ fin_all,
-                   uint8_t* __restrict__ chf_all) {
-    __shared__ uint8_t s_redone[PGA_FIX_MAXWIN];
-    const int c = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nwaves = blockDim.x >> 6;
-    if (c >= n_contigs) return;
-    const TailDesc d = td[c];
-    const int ng = n_genes[c];
-    const GeneRec* ob = orig + d.gene_off; const GeneRec* par = par_all + d.gene_off; const uint8_t* ch0 = ch0_all + d.gene_off;
-    GeneRec* fin = fin_all + d.gene_off; uint8_t* chf = chf_all + d.gene_off;
-    for (int g = threadIdx.x; g < ng; g += blockDim.x) { fin[g] = par[g]; chf[g] = ch0[g]; }
-    if (n_changed[c] == 0 || ng < 2) return;
-    __threadfence_block();
-    __syncthreads();
-    const NodeView v = node_view(d, o, tracef, elim);
-    const int nwin = (ng - 1 + 63) >> 6;                  // genes 1 .. ng-1
-    // one window, in gene order; `assume`: its first gene's predecessor is as the parallel pass left it.  Returns whether the
-    // window's last gene was redone (then the next window may not assume that).
-    auto run_window = [&](const int w, const bool assume) -> bool {
-        const int g0 = 1 + (w << 6), g1 = min(ng, g0 + 64);
-        const int g = g0 + lane;
-        if (!assume) {
-            if (g < g1) { fin[g] = par[g]; chf[g] = ch0[g]; }
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-        }
-        const int pf = g < g1 ? ((lane == 0 && !assume) ? chf[g - 1] : ch0[g - 1]) : 0;
-        unsigned long long mask = __ballot(pf != 0);
-        bool last = false;
-        while (mask) {
-            const int k = __builtin_ctzll(mask);
-            mask &= mask - 1ull;
-            const int gg = g0 + k;
-            GeneRec cur = ob[gg];
-            const GeneRec prev = (k == 0 && assume) ? par[gg - 1] : fin[gg - 1];
-            GeneRec nxt{};
-            if (gg < ng - 1) nxt = ob[gg + 1];
-            tweak_one_wave(v, &prev, cur, gg < ng - 1 ? &nxt : nullptr, d.st_wt, maxov, lane);
-            const int nf = cur.start_ndx != ob[gg].start_ndx && v.strand[cur.start_ndx] == -1;
-            if (lane == 0) { fin[gg] = cur; chf[gg] = (uint8_t)nf; }
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");     // fin[gg] is read back by all lanes if gg + 1 is redone
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-            // the next gene's predecessor flag is this gene's new flag
-            if (gg + 1 < g1) { if (nf) mask |= 1ull << (k + 1); else mask &= ~(1ull << (k + 1)); }
-            if (gg == g1 - 1) last = true;
-        }
-        return last;
-    };
-    if (nwin <= PGA_FIX_MAXWIN) {
-        for (int w = wave; w < nwin; w += nwaves) { const bool r = run_window(w, true); if (lane == 0) s_redone[w] = r; }
-        __threadfence_block();
-        __syncthreads();
-        if (wave == 0)
-            for (int w = 1; w < nwin; w++)
-                if (s_redone[w - 1]) { const bool r = run_window(w, false); if (lane == 0) s_redone[w] = r; __builtin_amdgcn_wave_barrier(); }
-    } else if (wave == 0) {
-        for (int w = 0; w < nwin; w++) run_window(w, false);       // a contig of more than 262 k genes: plainly in order
-    }
-}
-
-// The public gene records, packed in (contig, gene) order (ref: lib.pyx:2644-2830 for what Gene reads).
-__global__ void __launch_bounds__(256)
-k_emit_genes(const TailDesc* __restrict__ td, int n_contigs, int64_t n_slots, OutArrays o, const GeneRec* __restrict__ fin,
-             const int32_t* __restrict__ n_genes, const int64_t* __restrict__ gene_begin, int single, pga_gene* __restrict__ out,
-             const int lean, ChainArrays ca, GcPtrs gcs) {
-    const int64_t slot = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (slot >= n_slots) return;
-    const int c = contig_of_slot(td, n_contigs, slot);
-    const TailDesc d = td[c];
-    const int g = (int)(slot - d.gene_off);
-    if (g >= n_genes[c]) return;
-    const GeneRec gr = fin[slot];
-    const int64_t sn = d.out_off + gr.start_ndx, en = d.out_off + gr.stop_ndx;
-    pga_gene G;
-    memset(&G, 0, sizeof G);
-    G.contig = c; G.begin = gr.begin; G.end = gr.end; G.start_ndx = gr.start_ndx; G.stop_ndx = gr.stop_ndx;
-    if (o.direct) {
-        // (lean as well) the DP pass's read-only fields were not gathered either
-        const int64_t ts = d.topo_off + gr.start_ndx, as = d.dp_off + gr.start_ndx, ae = d.dp_off + gr.stop_ndx;
-        const int64_t fs = d.fin_off + gr.start_ndx, fe = d.fin_off + gr.stop_ndx;
-        G.strand = o.g_strand[d.group][ts];
-        const uint8_t se = single ? o.c_edge[as] : ca.edge[fs], ee = single ? o.c_edge[ae] : ca.edge[fe];
-        G.partial_begin = G.strand == 1 ? se : ee; G.partial_end = G.strand == 1 ? ee : se;
-        G.start_type = se ? 3 : o.g_type[d.group][ts];
-        G.rbs[0] = ca.rbs[2 * fs]; G.rbs[1] = ca.rbs[2 * fs + 1];
-        G.mot_len = ca.mot_len[fs]; G.mot_spacer = ca.mot_spacer[fs]; G.mot_ndx = ca.mot_ndx[fs]; G.mot_score = ca.mot_score[fs];
-        G.gc_cont = gcs.p[d.group][ts];
-        G.cscore = single ? o.c_cscore[as] : ca.cscore[fs]; G.sscore = single ? o.sscore_dp[sn] : ca.sscore[fs];
-        G.rscore = single ? o.c_rscore[as] : ca.rscore[fs]; G.uscore = single ? o.c_uscore[as] : ca.uscore[fs];
-        G.tscore = single ? o.c_tscore[as] : ca.tscore[fs];
-        out[gene_begin[c] + g] = G;
-        return;
-    }
-    G.strand = o.strand[sn];
-    // single mode keeps the nodes of the DP pass (ref: lib.pyx:5296-5311); meta mode re-scores (5380-5394)
-    if (lean) {
-        // the winners were gathered without their final-pass fields: the start node's sit where the scorer wrote them
-        const int64_t fs = d.fin_off + gr.start_ndx, fe = d.fin_off + gr.stop_ndx;
-        const uint8_t se = single ? o.edge_dp[sn] : ca.edge[fs], ee = single ? o.edge_dp[en] : ca.edge[fe];
-        G.partial_begin = G.strand == 1 ? se : ee; G.partial_end = G.strand == 1 ? ee : se;
-        G.start_type = se ? 3 : o.type[sn];
-        G.rbs[0] = ca.rbs[2 * fs]; G.rbs[1] = ca.rbs[2 * fs + 1];
-        G.mot_len = ca.mot_len[fs]; G.mot_spacer = ca.mot_spacer[fs]; G.mot_ndx = ca.mot_ndx[fs]; G.mot_score = ca.mot_score[fs];
-        G.gc_cont = gcs.p[d.group][d.topo_off + gr.start_ndx];
-        G.cscore = single ? o.cscore_dp[sn] : ca.cscore[fs]; G.sscore = single ? o.sscore_dp[sn] : ca.sscore[fs];
-        G.rscore = single ? o.rscore_dp[sn] : ca.rscore[fs]; G.uscore = single ? o.uscore_dp[sn] : ca.uscore[fs];
-        G.tscore = single ? o.tscore_dp[sn] : ca.tscore[fs];
-        out[gene_begin[c] + g] = G;
-        return;
-    }
-    const uint8_t se = single ? o.edge_dp[sn] : o.edge[sn], ee = single ? o.edge_dp[en] : o.edge[en];
-    G.partial_begin = G.strand == 1 ? se : ee; G.partial_end = G.strand == 1 ? ee : se;
-    G.start_type = se ? 3 : o.type[sn];
-    G.rbs[0] = o.rbs[2 * sn]; G.rbs[1] = o.rbs[2 * sn + 1];
-    G.mot_len = o.mot_len[sn]; G.mot_spacer = o.mot_spacer[sn]; G.mot_ndx = o.mot_ndx[sn]; G.mot_score = o.mot_score[sn];
-    G.gc_cont = o.gc_cont[sn];
-    G.cscore = single ? o.cscore_dp[sn] : o.cscore[sn]; G.sscore = single ? o.sscore_dp[sn] : o.sscore[sn];
-    G.rscore = single ? o.rscore_dp[sn] : o.rscore[sn]; G.uscore = single ? o.uscore_dp[sn] : o.uscore[sn];
-    G.tscore = single ? o.tscore_dp[sn] : o.tscore[sn];
-    out[gene_begin[c] + g] = G;
-}
 
 // Coding bases (pga_find_coding_bases): the positions [begin, end] of every gene record, clipped to its contig, set in a bitmap of
 // one bit per base of the batch (bit ct[contig].base + position - 1).  A wavefront per gene, its lanes over the 32-bit words the
@@ -2522,23 +1965,14 @@ int FindCall::run_host_tail() {
             const bool single = !P.meta;
             int64_t gi = R->contigs[i].gene_begin;
             for (const GeneRec& gr : cg[i]) {
-                pga_gene& G = R->genes[(size_t)gi];
                 const GeneNodeAttr& as = h_attr[2 * gi]; const GeneNodeAttr& ae = h_attr[2 * gi + 1];
-                gi++;
-                memset(&G, 0, sizeof G);
                 const int64_t sn = oo + gr.start_ndx, en = oo + gr.stop_ndx;
-                G.contig = i; G.begin = gr.begin; G.end = gr.end; G.start_ndx = gr.start_ndx; G.stop_ndx = gr.stop_ndx;
-                G.strand = h.strand[sn];
-                // single mode keeps the nodes of the DP pass (ref: lib.pyx:5296-5311); meta mode re-scores (5380-5394)
-                const uint8_t se = single ? h.edge_dp[sn] : as.edge, ee = single ? h.edge_dp[en] : ae.edge;
-                G.partial_begin = G.strand == 1 ? se : ee; G.partial_end = G.strand == 1 ? ee : se;
-                G.start_type = se ? 3 : h.type[sn];
-                G.rbs[0] = as.rbs0; G.rbs[1] = as.rbs1;
-                G.mot_len = as.mot_len; G.mot_spacer = as.mot_spacer; G.mot_ndx = as.mot_ndx; G.mot_score = as.mot_score;
-                G.gc_cont = as.gc_cont;
-                G.cscore = single ? h.cscore_dp[sn] : as.cscore; G.sscore = single ? h.sscore_dp[sn] : as.sscore;
-                G.rscore = single ? h.rscore_dp[sn] : as.rscore; G.uscore = single ? h.uscore_dp[sn] : as.uscore;
-                G.tscore = single ? h.tscore_dp[sn] : as.tscore;
+                GeneSrc s;          // the DP pass came home with the winners; the final pass's fields of the two nodes are in `as` and `ae`
+                s.topology(h.strand, h.type, sn);
+                if (single) s.scores(h.edge_dp, h.cscore_dp, h.sscore_dp, h.rscore_dp, h.uscore_dp, h.tscore_dp, sn, en, sn);
+                else { s.scores(&as.edge, &as.cscore, &as.sscore, &as.rscore, &as.uscore, &as.tscore, 0, 0, 0); s.edge_e = &ae.edge; }
+                s.motifs(as.rbs, &as.mot_len, &as.mot_spacer, &as.mot_ndx, &as.mot_score, 0, &as.gc_cont, 0);
+                R->genes[(size_t)gi++] = gene_record(i, gr, s);
             }
         }
     };

@@ -1,4 +1,4 @@
-"""Deterministic inputs that put the traceback tail (pyrodigal_amd/csrc/tail.inl, the k_tail_tweak* kernels of finder.hip) at its
+"""Deterministic inputs that put the traceback tail (pyrodigal_amd/csrc/tail.inl over the rules of tail_rules.h) at its
 edges: the inputs of tests/test_tail_cpu.py, which proves with tests/tail_ref.py what they contain, and of
 tests/test_tail_shapes_gpu.py, which compares the device on them.  A helper module, not a test.
 

@@ -68,6 +68,11 @@ def compare_contig(res, i, seq, o, models, meta, closed=False, max_overlap=60):
         assert np.array_equal(gg["cscore"].view(np.uint64), s["cscore"].view(np.uint64))
         assert np.array_equal(gg["sscore"].view(np.uint64), s["sscore"].view(np.uint64))
         assert np.array_equal(gg["start_type"], np.where(s["edge"] != 0, 3, s["type"]))
+        # the gene's left end is its start node on the forward strand, its stop node on the reverse strand (ref: lib.pyx:2644-2830)
+        t = on[og["stop_ndx"]]
+        fwd = s["strand"] == 1
+        assert np.array_equal(gg["partial_begin"] != 0, np.where(fwd, s["edge"], t["edge"]) != 0)
+        assert np.array_equal(gg["partial_end"] != 0, np.where(fwd, t["edge"], s["edge"]) != 0)
     return len(gg)
 
 

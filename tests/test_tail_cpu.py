@@ -3,15 +3,16 @@ restates the traceback tail (ref: lib.pyx:1253-1311, 3231-3401, Prodigal dprog.c
 side of every rule an input reaches; tests/tail_shapes.py builds the inputs.  Every run below first compares tail_ref with the
 oracle's staged calls (dprog, eliminate_bad_genes, extract_genes, tweak_final_starts): traceb, tracef, ov_mark, elim, the start
 scores as bit patterns, the gene list before and after the tweak.  Then the populations are asserted per series, so that the GPU
-test compares the device on inputs that are known to reach both sides of each rule, once per writing of it:
+test compares the device on inputs that are known to reach both sides of each rule.  The rules have one text each
+(pyrodigal_amd/csrc/tail_rules.h); what differs between the forms is who enumerates, once per enumeration:
 
   splices, elimination      k_tp_small (chains of at most 4 096 nodes), k_tp_slots .. k_tp_elim_b (PGA_TP_STEPS or longer chains),
-                            untangle / eliminate_bad_genes (PGA_TAIL=device, host): the splice and the elimination series are short
-                            enough for the first and run under every form
-  gene list                 k_tp_small with 64 and 256 threads, k_tp_extract with 256 and 1 024, k_tp_extract_sum / _chunk: one
-                            contig of the gene-list series each
-  start tweaks              tweak_one (k_tail_tweak, k_tail_tweak_packed), tweak_one_wave (k_tail_tweak_wave, k_tail_tweak_fixup): the
-                            tweak batch runs under all four
+                            the serial walks untangle / eliminate_bad_genes (PGA_TAIL=device, host): the splice and the
+                            elimination series are short enough for the first and run under every form
+  gene list                 tp_extract_rounds with 64 and 256 threads (k_tp_small), with 256 and 1 024 (k_tp_extract),
+                            k_tp_extract_sum / _chunk, the serial extract_genes: one contig of the gene-list series each
+  start tweaks              a thread per gene (tweak_one: k_tail_tweak, k_tail_tweak_packed, the host), a wavefront per gene
+                            (tweak_one_wave: k_tail_tweak_wave, k_tail_tweak_fixup): the tweak batch runs under all
 
 Populations that were sought and not found are asserted to be ABSENT, so that nobody takes them for covered."""
 import functools

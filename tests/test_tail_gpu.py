@@ -57,6 +57,25 @@ def test_long_gene_dense_contig_single_mode(ctx, monkeypatch, gc, seed, closed):
         assert np.array_equal(runs[mode].nodes[0]["sscore"].view(np.uint64), runs["par"].nodes[0]["sscore"].view(np.uint64)), mode
 
 
+def test_host_tail_on_several_threads(ctx, monkeypatch):
+    """The host tail leaves its serial forms only for a single long contig: eliminate_bad_genes_mt from 4 096 path positions,
+    tweak_final_starts from 2 048 genes, both with fewer than four contigs.  planted(3_009_000, 0.55, 302) is the shortest such
+    genome, in steps of 1 kbp, with 2 048 genes under the NCTC11397 model in single mode with open ends (3 008 000 bases: 2 047);
+    its path has two positions per gene.  The oracle counts 2 048 genes on 153 630 nodes, in 1.6 s on the CPU."""
+    seq = planted(3_009_000, 0.55, 302)
+    tinf = orc.Training.load(golden_path("GCF_001457455.1_NCTC11397_genomic.tinf_closed.bin.gz"))
+    ctx.set_models([tinf.buf])
+    par = ctx.find_genes_batch([seq], want_nodes=True, meta=False)
+    n = compare_contig(par, 0, seq, orc.Oracle(seq), [tinf], meta=False)
+    assert n == 2048
+    monkeypatch.setenv("PGA_TAIL", "host")
+    host = ctx.find_genes_batch([seq], want_nodes=True, meta=False)
+    assert host.genes.tobytes() == par.genes.tobytes()
+    for k in ("traceb", "tracef", "ov_mark", "elim"):
+        assert np.array_equal(host.nodes[0][k], par.nodes[0][k]), k
+    assert np.array_equal(host.nodes[0]["sscore"].view(np.uint64), par.nodes[0]["sscore"].view(np.uint64))
+
+
 def test_degenerate_batch(ctx, monkeypatch):
     """Empty contigs, contigs without nodes, without genes, one-gene contigs and a long one in the same batch."""
     from pyrodigal_amd import benchdata

@@ -1,18 +1,19 @@
-"""GPU parity of the traceback tail (pyrodigal_amd/csrc/tail.inl, the k_tail_tweak* kernels and tweak_one* of finder.hip) on the
+"""GPU parity of the traceback tail (the kernels of pyrodigal_amd/csrc/tail.inl over the rules of tail_rules.h) on the
 input series of tests/tail_shapes.py, whose populations tests/test_tail_cpu.py proves on the CPU: every splice class, both
 elimination rules, paths longer than a wave, a round and a chunk of the gene list, the gene whose in-order start tweak differs
 from the parallel one at every place of the fix-up's 64-gene windows, and the node and contig counts at which the launch forms
 switch (ref: lib.pyx:1253-1311, 3231-3401, Prodigal dprog.c eliminate_bad_genes).
 
 Everything is compared with the CPU oracle, field by field (compare_contig of test_finder_gpu.py) -- never only one form with
-another, since the forms share their helpers.  Every series runs under every form that can take it, and each test asserts from
+another, since the forms share their rules (tail_rules.h: a wrong rule is wrong in every form).  Every series runs under every form that can take it, and each test asserts from
 what is observable (the node count of the longest contig, the number of contigs) that the intended form ran:
 
   default                              k_tp_small up to 4 096 nodes (64 threads up to 2 048), the many-launch form beyond
   PGA_TP_STEPS=1                       the many-launch form for short chains too; PGA_TP_JUMP8=0: pointer doubling only
   PGA_TP_EXTRACT_ONE=1                 from 32 768 nodes: k_tp_extract with 1 024 threads instead of the chunked gene list
   PGA_TWEAK_SLOTS=1                    from 256 contigs: k_tail_tweak instead of k_tail_tweak_packed
-  PGA_TAIL=device, PGA_TAIL=host       one thread per contig; host threads"""
+  PGA_TAIL=device, PGA_TAIL=host       one thread per contig; host threads
+  PGA_GATHER_ALL_DP=1, PGA_FULL_GATHER=1   without node arrays: k_emit_genes reads gathered copies, not the scorers' arrays"""
 import pytest
 
 from oracle import oracle as orc
@@ -21,7 +22,7 @@ from tests.test_finder_gpu import compare_contig
 
 pytestmark = pytest.mark.gpu
 
-ENV = ("PGA_TAIL", "PGA_TP_STEPS", "PGA_TP_JUMP8", "PGA_TP_EXTRACT_ONE", "PGA_TWEAK_SLOTS")
+ENV = ("PGA_TAIL", "PGA_TP_STEPS", "PGA_TP_JUMP8", "PGA_TP_EXTRACT_ONE", "PGA_TWEAK_SLOTS", "PGA_GATHER_ALL_DP", "PGA_FULL_GATHER")
 FORMS = {
     "default": {},
     "steps": {"PGA_TP_STEPS": "1"},
@@ -30,6 +31,8 @@ FORMS = {
     "tweak_slots": {"PGA_TWEAK_SLOTS": "1"},
     "device": {"PGA_TAIL": "device"},
     "host": {"PGA_TAIL": "host"},
+    "gather_all_dp": {"PGA_GATHER_ALL_DP": "1"},
+    "full_gather": {"PGA_FULL_GATHER": "1"},
 }
 SHORT_FORMS = ("default", "steps", "steps_doubling", "device", "host")     # what differs for chains of at most 4 096 nodes
 LONG_FORMS = ("default", "extract_one", "steps_doubling", "device", "host")  # ... and from 32 768 nodes
@@ -253,6 +256,23 @@ def test_tweaks_one_wavefront_per_gene(ctx, monkeypatch):
     use(monkeypatch, "extract_one")
     res, n = check(ctx, [long_one] + ts.tweak_series(), "tweak", False, 60, False)
     assert longest(res) == 32768
+
+
+# ---- gene records ------------------------------------------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("form", ["gather_all_dp", "full_gather"])
+def test_gene_records_from_gathered_fields(ctx, monkeypatch, form):
+    """Without node arrays k_emit_genes reads the scorers' own arrays (the other tests' want_nodes=False).  PGA_GATHER_ALL_DP gathers
+    the DP pass's fields all the same (the tail and the records' topology and single-mode scores then come from the gathered
+    copies, the final-pass fields from the scorers), PGA_FULL_GATHER the final pass's too (every field from the gathered copies):
+    the splice series, the smallest input with every record field in both modes, single mode (the DP pass's scores) and meta mode
+    (the final pass's), open and closed ends."""
+    use(monkeypatch, form)
+    seqs = ts.splice_series()
+    for tag in ("nctc", "meta"):
+        for closed in (False, True):
+            res, n = check(ctx, seqs, tag, closed, 60, want_nodes=False)
+            assert len(seqs) == 5 and n >= 240
 
 
 # ---- launch edges ------------------------------------------------------------------------------------------------------------------------------
