@@ -1,21 +1,60 @@
-// Device helpers shared by dp.hip and pipeline.hip.
+// Device helpers shared by dp.hip, dp_wave.hip and pipeline.hip: the ones that need intrinsics (the scalar rules of connection
+// scoring -- sel3, igm_apart, igm_same, the window start -- are in dpw_core.h, which the host model compiles too).
 #pragma once
 #include "pga_internal.h"
 
-// General _intergenic_mod_same (ref: _connection.h:52-78); a = n1, b = n2, both on strand a_strand.
-// igm_tab[d] = (2 - d/60) * 0.15 * st_wt for d = 0..60 (host-computed, ModelConst::igm).
-__device__ __forceinline__ double igm_same_dev(int a_ndx, int a_strand, double a_r, double a_u,
-                                               int b_ndx, double b_r, double b_u, double st_wt, const double* igm_tab) {
-    const int dist = abs(a_ndx - b_ndx);
-    const bool ovl = a_ndx + 2 * a_strand >= b_ndx;
-    double r = 0.0;
-    if (a_ndx + 2 == b_ndx || a_ndx == b_ndx + 1) {
-        if (a_strand == 1) { if (b_r < 0) r -= b_r; if (b_u < 0) r -= b_u; }
-        else               { if (a_r < 0) r -= a_r; if (a_u < 0) r -= a_u; }
+// v of lane `lane`, the same in every lane (two v_readlane)
+__device__ __forceinline__ double readlane_f64(double v, int lane) {
+    return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), lane), __builtin_amdgcn_readlane(__double2loint(v), lane));
+}
+
+// Cross-lane moves through the data-parallel primitives of the vector ALU (DPP) instead of ds_bpermute: a lone wavefront waits out
+// the full LDS round trip of every __shfl, six of them in a row per scan, and these scans sit on the serial path of a chain.
+// CTRL: 0x111 .. 0x11f row_shr:1 .. 15, 0x138 wave_shr:1, 0x142 row_bcast15, 0x143 row_bcast31, 0x140 row_mirror, 0x141 row_half_mirror,
+// quad_perm otherwise.  Lanes that receive nothing (shifted in from outside the row, or masked out by ROW_MASK) get `old`.
+template <int CTRL, int ROW_MASK = 0xf>
+__device__ __forceinline__ double dpp_f64(const double old, const double v) {
+    const int hi = __builtin_amdgcn_update_dpp(__double2hiint(old), __double2hiint(v), CTRL, ROW_MASK, 0xf, false);
+    const int lo = __builtin_amdgcn_update_dpp(__double2loint(old), __double2loint(v), CTRL, ROW_MASK, 0xf, false);
+    return __hiloint2double(hi, lo);
+}
+template <int CTRL, int ROW_MASK = 0xf>
+__device__ __forceinline__ int dpp_i32(const int old, const int v) { return __builtin_amdgcn_update_dpp(old, v, CTRL, ROW_MASK, 0xf, false); }
+
+// wave-wide minimum of an int, the same in every lane
+__device__ __forceinline__ int wave_min_i32(int v) {
+    const int BIG = 0x7fffffff;
+    v = min(v, dpp_i32<0xb1>(BIG, v));             // quad_perm [1, 0, 3, 2]
+    v = min(v, dpp_i32<0x4e>(BIG, v));             // quad_perm [2, 3, 0, 1]
+    v = min(v, dpp_i32<0x141>(BIG, v));            // row_half_mirror
+    v = min(v, dpp_i32<0x140>(BIG, v));            // row_mirror: every lane holds its row's minimum
+    v = min(v, dpp_i32<0x142, 0xa>(BIG, v));       // row_bcast15 into rows 1 and 3
+    v = min(v, dpp_i32<0x143, 0xc>(BIG, v));       // row_bcast31 into rows 2 and 3: lane 63 holds the minimum
+    return __builtin_amdgcn_readlane(v, 63);
+}
+
+// Lexicographic (value, index) order: ties go to the larger index.  Its maximum is the reference's ascending ">=" scan
+// (ref: _connection.h:135-139) in a form that does not depend on the order of the candidates, so partial maxima over disjoint
+// source sets merge exactly.
+__device__ __forceinline__ bool lex_gt(const double ov, const int oi, const double v, const int i) { return ov > v || (ov == v && oi > i); }
+__device__ __forceinline__ void lex_max(double& v, int& i, const double ov, const int oi) {
+    const bool c = lex_gt(ov, oi, v, i);
+    v = c ? ov : v; i = c ? oi : i;
+}
+// The same over the lanes whose numbers differ in the bits LO .. HI (powers of two) only, by xor butterfly: <1, 4> leaves every
+// lane the maximum of its block of 8, <8, 32> after that the wave's, <1, 32> the wave's at once.  `carry`: further values of the
+// lane that holds the maximum.  Every lane of the wave must call it.
+template <int LO, int HI, class... Carry>
+__device__ __forceinline__ void wave_lexmax(double& v, int& i, Carry&... carry) {
+#pragma unroll
+    for (int m = LO; m <= HI; m <<= 1) {
+        const double ov = __shfl_xor(v, m, 64); const int oi = __shfl_xor(i, m, 64);
+        auto other = [m](const auto x) { return __shfl_xor(x, m, 64); };
+        auto sel = [](const bool c, const auto a, const auto b) { return c ? a : b; };
+        const bool c = lex_gt(ov, oi, v, i);
+        ((carry = sel(c, other(carry), carry)), ...);
+        lex_max(v, i, ov, oi);
     }
-    if (dist > 3 * PGA_OPER_DIST) r -= 0.15 * st_wt;
-    else if ((dist <= PGA_OPER_DIST && !ovl) || dist * 4 < PGA_OPER_DIST) r += igm_tab[dist];
-    return r;
 }
 
 // chain containing global chain-node index g (chains sorted by off)

@@ -24,11 +24,19 @@
 // Few long chains (one genome) do not fill the chip with one serial walk each: they are cut into segments that are
 // walked speculatively side by side, re-scored exactly and verified node by node -- see "Segmented chains" below.
 //
+// One text per rule: pair_rule<FINAL, Src> is the only statement of "is j a predecessor of i, and what is the connection
+// worth", for the wave-uniform sources of the scanning kernels (LaneAcc), the per-lane exact pairs of the tree and segment
+// kernels (GlobalAcc, ClaimAcc) and the training pass (FINAL = false); static_pair / dyn_weight restate it for the serial
+// wave of k_dp_tree_mw and say so at their head.  The steps around it -- load_target, walk_batch, far_values, track_end,
+// publish_max, levbase_of -- exist once; the scalar helpers shared with dp_wave.hip are in dpw_core.h, the intrinsic ones
+// (readlane_f64, wave_min_i32, lex_max, wave_lexmax) in dev_common.h.
+//
 // Arithmetic: IEEE double, compiled with -ffp-contract=off, same operation order as the
 // reference; (2 - d/60)*0.15*st_wt comes from a host-computed 61-entry table.
 
 #include "pga_internal.h"
 #include "dev_common.h"
+#include "dpw_core.h"      // the scalar rules shared with the wave-batch scorer: dpw_sel3, dpw_igm_apart, dpw_igm_same, dpw_window_lo
 
 #include <limits.h>
 #include <stdlib.h>
@@ -37,30 +45,6 @@
 #include <algorithm>
 
 namespace {
-
-__device__ __forceinline__ double readlane_f64(double v, int lane) {
-    int lo = __builtin_amdgcn_readlane(__double2loint(v), lane);
-    int hi = __builtin_amdgcn_readlane(__double2hiint(v), lane);
-    return __hiloint2double(hi, lo);
-}
-
-__device__ __forceinline__ int wave_min_i32(int v) {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v = min(v, __shfl_xor(v, m, 64));
-    return v;
-}
-
-__device__ __forceinline__ double sel3(int k, double a, double b, double c) { return k == 0 ? a : (k == 1 ? b : c); }
-__device__ __forceinline__ int sel3i(int k, int a, int b, int c) { return k == 0 ? a : (k == 1 ? b : c); }
-
-// _intergenic_mod_same for two same-strand nodes `dist` apart that neither overlap nor touch
-// (ref: _connection.h:52-78 with overlap == 0 and no adjacency bonus)
-__device__ __forceinline__ double igm_apart(int d, double negc, const double* s_igm) {
-    double r = 0.0;
-    if (d > 3 * PGA_OPER_DIST) r = negc;
-    else if (d <= PGA_OPER_DIST && d >= 0) r = s_igm[d];
-    return r;
-}
 
 // One thread per node: build DpSrc / DpTgt (ref: lib.pyx:1126-1162 `_index`, 1221-1233 window,
 // and the n3 terms of _connection.h:166-176, 296-325, 345-356).
@@ -102,25 +86,14 @@ k_dp_prepare(const ChainDesc* __restrict__ chains, int n_chains, int64_t node_be
         const double cs3 = cs_c[p] + cs_s[p];
         double ig;
         if (!rev)   // F3 source j = i, n3 = forward start: igm(j, n3)       (ref: _connection.h:170-174)
-            ig = (strand[p] == 1) ? igm_same_dev(my_ndx, 1, rsc[i], usc[i], ndx[p], rsc[p], usc[p], mc->st_wt, mc->igm) : mc->negc;
+            ig = (strand[p] == 1) ? dpw_igm_same(my_ndx, 1, rsc[i], usc[i], ndx[p], rsc[p], usc[p], mc->st_wt, mc->igm) : mc->negc;
         else        // R3 target i, n3 = reverse start: igm(n3, i)          (ref: _connection.h:313-320, 353-355)
-            ig = (strand[p] == -1) ? igm_same_dev(ndx[p], -1, rsc[p], usc[p], my_ndx, rsc[i], usc[i], mc->st_wt, mc->igm) : mc->negc;
+            ig = (strand[p] == -1) ? dpw_igm_same(ndx[p], -1, rsc[p], usc[p], my_ndx, rsc[i], usc[i], mc->st_wt, mc->igm) : mc->negc;
         s.x[k] = cs3 + ig;
         t.n3ndx[k] = ndx[p]; t.n3stop[k] = stopv[p];
     }
     s.meta = meta;
-    // window start (ref: lib.pyx:1221-1233): 500 nodes back, stretched to the far end of a giant ORF,
-    // then another 500.  The reference's walk-down stops at the highest index whose ndx equals
-    // stop_val, or at 0; positions are sorted, so a binary search finds the same index.
-    int lo = i < PGA_MAX_NODE_DIST ? 0 : i - PGA_MAX_NODE_DIST;
-    // (positions ascend and a position holds at most two nodes: node k - 2 d - 2 and everything before it lies more than d
-    //  positions left of node k -- a search for position v starts there, not at 0: ten steps instead of twenty-three on a genome)
-    if ((kind == 2 || kind == 1) && ndx[lo] > my_stop) {
-        int a = max(0, lo - 2 * max(0, ndx[lo] - my_stop) - 2), b = lo;            // find last p in [0, lo) with ndx[p] <= my_stop
-        while (a < b) { int m = (a + b) >> 1; if (ndx[m] <= my_stop) a = m + 1; else b = m; }
-        lo = (a > 0 && ndx[a - 1] == my_stop) ? a - 1 : 0;
-    }
-    lo = lo < PGA_MAX_NODE_DIST ? 0 : lo - PGA_MAX_NODE_DIST;
+    const int lo = dpw_window_lo(ndx, i, kind, my_stop);
     t.lo = lo; t.p_near = lo;
     for (int k = 0; k < 3; k++) { t.a[k] = 0; t.b[k] = 0; t.c[k] = -1; t._pad[k] = 0; }
     // static index ranges over the sorted positions of nodes [0, i)
@@ -158,6 +131,7 @@ struct Target {
     int a0, a1, a2, b0, b1, b2, c0, c1, c2;
     double cs, csd, x0, x1, x2;
     int n3n0, n3n1, n3n2, n3s0, n3s1, n3s2;
+    int n3a, n3b, n3c;                // training pass only: DpSrc::n3src of the node itself, a source of its own batch
 };
 // Per-lane copy of one candidate source (lane k holds source t0+k); fields are broadcast with
 // v_readlane when the wave visits that source.
@@ -168,65 +142,102 @@ struct SrcLane {
 };
 struct Best { double val; int tb, ov, tbn; };   // running result of a target + ndx of its traceb node
 
-// "val >= best" of the reference's ascending scan (ref: _connection.h:135-139), written as a
-// lexicographic (value, index) maximum so that partial results over disjoint source sets merge exactly.
+// "val >= best" of the reference's ascending scan (ref: _connection.h:135-139): lex_max of dev_common.h on (val, tb), with
+// what goes with the winner (one branch around the four moves: as selects they cost k_dp_verify 130 instructions)
 __device__ __forceinline__ void take(Best& b, bool ok, double val, int j, int mf, int s_ndx) {
-    if (ok && (val > b.val || (val == b.val && j > b.tb))) { b.val = val; b.tb = j; b.ov = mf; b.tbn = s_ndx; }
+    if (ok && lex_gt(val, j, b.val, b.tb)) { b.val = val; b.tb = j; b.ov = mf; b.tbn = s_ndx; }
 }
 
-// Visit source j = lane k of S for all 64 targets of the wave.
-// One call = one iteration of the loop in _connection.h:386-408, with the six skip conditions of
-// impl/generic.h:29-36 folded into the per-kind predicates; a wave-wide vote (__any, i.e. a ballot)
-// drops the source before any floating-point work when no lane can connect to it.
+__device__ __forceinline__ bool gene_end(const int kind) { return kind == 1 || kind == 2; }      // forward stop, reverse start
+// A gene end that was never reached connects to nothing (ref: _connection.h:110-114).  tb: its traceb, or the ndx of its traceb
+// node -- either is -1 exactly when it has none.
+__device__ __forceinline__ bool dead_source(const int kind, const int tb) { return gene_end(kind) && tb == -1; }
+
+// Where pair_rule reads a source from.  `uniform` (a compile-time property): the source is the same for every lane of the wave,
+// so the lanes can vote on it.
+// Per lane: source j's records in global memory (a final node).
+struct GlobalAcc {
+    static constexpr bool uniform = false;
+    const DpSrc* __restrict__ src; const double* score; const int* tbn;
+    __device__ __forceinline__ int meta(int j) const { return src[j].meta; }
+    __device__ __forceinline__ int ndx(int j) const { return src[j].ndx; }
+    __device__ __forceinline__ int stop_val(int j) const { return src[j].stop_val; }
+    __device__ __forceinline__ double cs(int j) const { return src[j].cs; }
+    __device__ __forceinline__ double x(int j, int f) const { return src[j].x[f]; }
+    __device__ __forceinline__ int n3(int j, int f) const { return src[j].n3src[f]; }
+    __device__ __forceinline__ double sc(int j) const { return score[j]; }
+    __device__ __forceinline__ int tb_ndx(int j) const { return tbn[j]; }      // ndx of the source's own traceb node, -1: none
+};
+// ... whose own traceb is the one a claim names, not the one in memory (k_seg_weights)
+struct ClaimAcc : GlobalAcc {
+    int claim_tbn;
+    __device__ __forceinline__ int tb_ndx(int) const { return claim_tbn; }
+};
+// Wave-uniform: the source is lane k of S; each field is fetched with v_readlane where the rule uses it.
+struct LaneAcc {
+    static constexpr bool uniform = true;
+    const SrcLane& S; const int k;
+    __device__ __forceinline__ int meta(int) const { return __builtin_amdgcn_readlane(S.meta, k); }
+    __device__ __forceinline__ int ndx(int) const { return __builtin_amdgcn_readlane(S.ndx, k); }
+    __device__ __forceinline__ int stop_val(int) const { return __builtin_amdgcn_readlane(S.stop_val, k); }
+    __device__ __forceinline__ double cs(int) const { return readlane_f64(S.cs, k); }
+    __device__ __forceinline__ double x(int, int f) const { return dpw_sel3(f, readlane_f64(S.x0, k), readlane_f64(S.x1, k), readlane_f64(S.x2, k)); }
+    __device__ __forceinline__ int n3(int, int f) const {
+        return dpw_sel3i(f, __builtin_amdgcn_readlane(S.n3a, k), __builtin_amdgcn_readlane(S.n3b, k), __builtin_amdgcn_readlane(S.n3c, k));
+    }
+    __device__ __forceinline__ double sc(int) const { return readlane_f64(S.score, k); }
+    __device__ __forceinline__ int tb_ndx(int) const { return __builtin_amdgcn_readlane(S.tbn, k); }
+};
+
+// THE pair rule: is source j a predecessor of target T, and what is the connection worth.  One call = one iteration of the
+// loop in _connection.h:386-408, with the six skip conditions of impl/generic.h:29-36 folded into the per-kind predicates.
+// The answer goes to put(ok, w, mf): ok = the connection is allowed, w its weight, mf the ov_mark it leaves.
+// A uniform source (LaneAcc) is put to a wave-wide vote (__any, i.e. a ballot) that drops it before any floating-point work
+// when no lane can connect to it -- put() is then not called at all; its caller's visit mask has dropped the dead sources.
+// A per-lane source (GlobalAcc) has no vote, and a dead one never reaches put().
 // FINAL = false is the training pass (ref: the `final` flag of _connection.h:94-367): same admissibility, but a connection
 // is worth (right - left + 1 - 2 overlap) x (bias . gc_score of one of its nodes), 0 for intergenic steps.  In that
-// pass S.cs / T.cs hold the node's own factor, S.x* / T.x* those of its overlapping starts, S.n3* their positions.
-template <bool FINAL = true>
-__device__ __forceinline__ void visit_source(const int k, const int j, const SrcLane& S, const Target& T,
-                                             const double negc, const double* s_igm, Best& B, const double st_wt = 0.0) {
-    const int s_meta = __builtin_amdgcn_readlane(S.meta, k);
-    const int s_ndx = __builtin_amdgcn_readlane(S.ndx, k);
+// pass cs holds the node's own factor, x those of its overlapping starts, n3 their positions.
+template <bool FINAL, class Src, class Put>
+__device__ __forceinline__ void pair_rule(const int j, const Src& S, const Target& T, const double negc, const double* s_igm,
+                                          const double st_wt, Put&& put) {
+    const int s_meta = S.meta(j), s_ndx = S.ndx(j);
     const int sk = PGA_KIND(s_meta), sf = PGA_FRAME(s_meta);
-    const bool inwin = (j >= T.lo) && (j < T.i);
+    if (!Src::uniform && dead_source(sk, S.tb_ndx(j))) return;
+    auto nobody = [](const bool ok) { return Src::uniform && !__any(ok); };
+    bool ok = (j >= T.lo) && (j < T.i);
+    double w; int mf = -1;
     if (sk == 0) {
         // 5'fwd -> 3'fwd: a gene (ref: _connection.h:166-174; skip condition 5: same frame only)
-        const bool ok = inwin && T.kind == 1 && T.frame == sf && T.stop_val < s_ndx;
-        if (!__any(ok)) return;
-        const double w = FINAL ? readlane_f64(S.cs, k) : (double)(T.ndx + 2 - s_ndx + 1) * readlane_f64(S.cs, k);
-        take(B, ok, readlane_f64(S.score, k) + w, j, -1, s_ndx);
+        ok = ok && T.kind == 1 && T.frame == sf && T.stop_val < s_ndx;
+        if (nobody(ok)) return;
+        w = FINAL ? S.cs(j) : (double)(T.ndx + 2 - s_ndx + 1) * S.cs(j);
     } else if (sk == 2) {
         // 5'rev -> 5'fwd (ref: :125-130) and 5'rev -> 3'rev (ref: :337-342)
         const bool a = T.kind == 0 && s_ndx < T.ndx;
         const bool b = T.kind == 3 && s_ndx < T.ndx - 2;
-        const bool ok = inwin && (a || b);
-        if (!__any(ok)) return;
-        const double w = !FINAL ? 0.0 : (b ? igm_apart(T.ndx - s_ndx, negc, s_igm) : negc);
-        take(B, ok, readlane_f64(S.score, k) + w, j, -1, s_ndx);
+        ok = ok && (a || b);
+        if (nobody(ok)) return;
+        w = !FINAL ? 0.0 : (b ? dpw_igm_apart(T.ndx - s_ndx, negc, s_igm) : negc);
     } else if (sk == 3) {
         // 3'rev -> 5'rev: a gene (ref: :228-235; skip condition 6) and 3'rev -> 3'rev operon (ref: :345-356)
-        const int s_stop = __builtin_amdgcn_readlane(S.stop_val, k);
+        const int s_stop = S.stop_val(j);
         const bool a = T.kind == 2 && T.frame == sf && s_stop > T.ndx;
         const bool b = T.kind == 3 && s_stop > T.ndx && PGA_SPVALID(T.meta, sf);
-        const bool ok = inwin && (a || b);
-        if (!__any(ok)) return;
-        double w = a ? T.cs : sel3(sf, T.x0, T.x1, T.x2);
-        if (!FINAL) w = (double)((a ? T.ndx : sel3i(sf, T.n3n0, T.n3n1, T.n3n2)) - (s_ndx - 2) + 1) * w;
-        take(B, ok, readlane_f64(S.score, k) + w, j, -1, s_ndx);
+        ok = ok && (a || b);
+        if (nobody(ok)) return;
+        w = a ? T.cs : dpw_sel3(sf, T.x0, T.x1, T.x2);
+        if (!FINAL) w = (double)((a ? T.ndx : dpw_sel3i(sf, T.n3n0, T.n3n1, T.n3n2)) - (s_ndx - 2) + 1) * w;
     } else {
         // forward stop as source: connects to all four target kinds
-        const int tbnj = __builtin_amdgcn_readlane(S.tbn, k);
-        const double sj = readlane_f64(S.score, k);
-        bool ok = inwin; double w; int mf = -1;
+        const int tbnj = S.tb_ndx(j);
         if (T.kind == 0) {            // 3'fwd -> 5'fwd intergenic (ref: :117-124)
             ok = ok && (s_ndx + 2 < T.ndx);
-            w = FINAL ? igm_apart(T.ndx - s_ndx, negc, s_igm) : 0.0;
+            w = FINAL ? dpw_igm_apart(T.ndx - s_ndx, negc, s_igm) : 0.0;
         } else if (T.kind == 1) {     // 3'fwd -> 3'fwd operon through j's overlapping start (ref: :177-188)
             ok = ok && T.stop_val < s_ndx && PGA_SPVALID(s_meta, T.frame);
-            w = sel3(T.frame, readlane_f64(S.x0, k), readlane_f64(S.x1, k), readlane_f64(S.x2, k));
-            if (!FINAL) {
-                const int n3 = sel3i(T.frame, __builtin_amdgcn_readlane(S.n3a, k), __builtin_amdgcn_readlane(S.n3b, k), __builtin_amdgcn_readlane(S.n3c, k));
-                w = (double)(T.ndx + 2 - n3 + 1) * w;
-            }
+            w = S.x(j, T.frame);
+            if (!FINAL) w = (double)(T.ndx + 2 - S.n3(j, T.frame) + 1) * w;
         } else if (T.kind == 2) {     // 3'fwd -> 5'rev overlapping opposite 3' ends (ref: :238-254)
             const int ovlp = (s_ndx + 2) - (T.stop_val - 2) + 1;
             ok = ok && !(T.stop_val - 2 >= s_ndx + 2) && ovlp < PGA_MAX_OPP_OVLP
@@ -240,97 +251,37 @@ __device__ __forceinline__ void visit_source(const int k, const int j, const Src
             int ovlp_last = 0;        // training pass: the reference's `ovlp` keeps the value of the last candidate it looked at
 #pragma unroll
             for (int q = 0; q < 3; q++) {
-                const int n3s = sel3i(q, T.n3s0, T.n3s1, T.n3s2), n3n = sel3i(q, T.n3n0, T.n3n1, T.n3n2);
-                const double xq = sel3(q, T.x0, T.x1, T.x2);
+                const int n3s = dpw_sel3i(q, T.n3s0, T.n3s1, T.n3s2), n3n = dpw_sel3i(q, T.n3n0, T.n3n1, T.n3n2);
+                const double xq = dpw_sel3(q, T.x0, T.x1, T.x2);
                 const int ovlp = left - n3s + 3;
                 const bool valid = PGA_SPVALID(T.meta, q) != 0;
                 if (valid) ovlp_last = ovlp;
                 const bool adm = valid && ovlp > 0 && ovlp < PGA_MAX_OPP_OVLP && ovlp < n3n - left && ovlp < n3s - tbnj - 2;
-                if (FINAL) { if (adm && xq > maxval) { mf = q; maxval = xq; } }
-                else if (adm && xq > maxval) {
-                    // the reference compares the factor but remembers the gene-finding value, here the bare intergenic term
-                    mf = q; maxval = igm_same_dev(n3n, -1, 0.0, 0.0, T.ndx, 0.0, 0.0, st_wt, s_igm);
+                if (adm && xq > maxval) {
+                    // training pass: the reference compares the factor but remembers the gene-finding value, here the bare intergenic term
+                    mf = q; maxval = FINAL ? xq : dpw_igm_same(n3n, -1, 0.0, 0.0, T.ndx, 0.0, 0.0, st_wt, s_igm);
                 }
             }
             if (FINAL) w = mf != -1 ? maxval : negc;
-            else w = (double)(right - left + 1 - ovlp_last * 2) * (mf != -1 ? sel3(mf, T.x0, T.x1, T.x2) : 0.0);
+            else w = (double)(right - left + 1 - ovlp_last * 2) * (mf != -1 ? dpw_sel3(mf, T.x0, T.x1, T.x2) : 0.0);
         }
-        take(B, ok, sj + w, j, mf, s_ndx);
     }
+    put(ok, w, mf);
 }
 
-// Per-lane (non-uniform) evaluation of one (source j, target) pair: same arithmetic as visit_source,
-// every field loaded by the lane itself.  Used for the few pairs that need the exact pairwise term.
-// Source fields of final nodes, read from global memory.
-struct GlobalAcc {
-    const DpSrc* __restrict__ src; const double* score; const int* tbn;
-    __device__ __forceinline__ int meta(int j) const { return src[j].meta; }
-    __device__ __forceinline__ int ndx(int j) const { return src[j].ndx; }
-    __device__ __forceinline__ int stop_val(int j) const { return src[j].stop_val; }
-    __device__ __forceinline__ double cs(int j) const { return src[j].cs; }
-    __device__ __forceinline__ double x(int j, int f) const { return src[j].x[f]; }
-    __device__ __forceinline__ double sc(int j) const { return score[j]; }
-    __device__ __forceinline__ int tb_ndx(int j) const { return tbn[j]; }
-};
-// weight of the pair alone: ok = the connection is allowed, w its weight, mf the ov_mark it leaves; tbnj = ndx of the
-// source's own traceb node (-1: none)
-template <class Acc>
-__device__ __forceinline__ void pair_weight(const int j, const Acc& S, const int tbnj, const Target& T, const double negc, const double* s_igm,
-                                            bool& ok, double& w, int& mf) {
-    const int s_meta = S.meta(j), s_ndx = S.ndx(j);
-    const int sk = PGA_KIND(s_meta), sf = PGA_FRAME(s_meta);
-    ok = false; w = 0.0; mf = -1;
-    if ((sk == 1 || sk == 2) && tbnj == -1) return;
-    ok = (j >= T.lo) && (j < T.i);
-    if (sk == 0) {
-        ok = ok && T.kind == 1 && T.frame == sf && T.stop_val < s_ndx;
-        w = S.cs(j);
-    } else if (sk == 2) {
-        const bool a = T.kind == 0 && s_ndx < T.ndx;
-        const bool b = T.kind == 3 && s_ndx < T.ndx - 2;
-        ok = ok && (a || b);
-        w = b ? igm_apart(T.ndx - s_ndx, negc, s_igm) : negc;
-    } else if (sk == 3) {
-        const int s_stop = S.stop_val(j);
-        const bool a = T.kind == 2 && T.frame == sf && s_stop > T.ndx;
-        const bool b = T.kind == 3 && s_stop > T.ndx && PGA_SPVALID(T.meta, sf);
-        ok = ok && (a || b);
-        w = a ? T.cs : sel3(sf, T.x0, T.x1, T.x2);
-    } else {
-        if (T.kind == 0) {
-            ok = ok && (s_ndx + 2 < T.ndx);
-            w = igm_apart(T.ndx - s_ndx, negc, s_igm);
-        } else if (T.kind == 1) {
-            ok = ok && T.stop_val < s_ndx && PGA_SPVALID(s_meta, T.frame);
-            w = S.x(j, T.frame);
-        } else if (T.kind == 2) {
-            const int ovlp = (s_ndx + 2) - (T.stop_val - 2) + 1;
-            ok = ok && !(T.stop_val - 2 >= s_ndx + 2) && ovlp < PGA_MAX_OPP_OVLP
-                    && (s_ndx - T.stop_val) < (T.ndx - s_ndx + 3)
-                    && (s_ndx - T.stop_val) < (T.stop_val - 3 - tbnj);
-            w = T.csd;
-        } else {
-            const int left = s_ndx + 2, right = T.ndx - 2;
-            ok = ok && left < right;
-            double maxval = 0.0;
-#pragma unroll
-            for (int q = 0; q < 3; q++) {
-                const int n3s = sel3i(q, T.n3s0, T.n3s1, T.n3s2), n3n = sel3i(q, T.n3n0, T.n3n1, T.n3n2);
-                const double cur = sel3(q, T.x0, T.x1, T.x2);
-                const int ovlp = left - n3s + 3;
-                const bool tk = PGA_SPVALID(T.meta, q) && ovlp > 0 && ovlp < PGA_MAX_OPP_OVLP && ovlp < n3n - left
-                                && ovlp < n3s - tbnj - 2 && cur > maxval;
-                if (tk) { mf = q; maxval = cur; }
-            }
-            w = mf != -1 ? maxval : negc;
-        }
-    }
+// Visit source j = lane k of S for all 64 targets of the wave.
+template <bool FINAL = true>
+__device__ __forceinline__ void visit_source(const int k, const int j, const SrcLane& S, const Target& T,
+                                             const double negc, const double* s_igm, Best& B, const double st_wt = 0.0) {
+    const LaneAcc L{S, k};
+    pair_rule<FINAL>(j, L, T, negc, s_igm, st_wt,
+                     [&](const bool ok, const double w, const int mf) { take(B, ok, L.sc(j) + w, j, mf, L.ndx(j)); });
 }
+// One (source j, target) pair per lane, every field loaded by the lane itself: the few pairs that need the exact pairwise term.
 template <class Acc>
 __device__ __forceinline__ void pair_eval(const int j, const Acc& S, const Target& T, const double negc, const double* s_igm, Best& B) {
-    bool ok; double w; int mf;
-    pair_weight(j, S, S.tb_ndx(j), T, negc, s_igm, ok, w, mf);
-    if (ok) take(B, true, S.sc(j) + w, j, mf, S.ndx(j));
+    pair_rule<true>(j, S, T, negc, s_igm, 0.0,
+                    [&](const bool ok, const double w, const int mf) { if (ok) take(B, true, S.sc(j) + w, j, mf, S.ndx(j)); });
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -369,6 +320,7 @@ __device__ __forceinline__ ChainPtrs chain_ptrs(const ChainDesc& cd, const DpSrc
     return P;
 }
 
+template <bool FINAL = true>
 __device__ __forceinline__ void load_target(Target& T, const ChainPtrs& P, int i0, int lane, int n, double negc) {
     T.i = i0 + lane;
     const bool act = T.i < n;
@@ -382,6 +334,7 @@ __device__ __forceinline__ void load_target(Target& T, const ChainPtrs& P, int i
     T.lo = mt.lo; T.p_near = mt.p_near;
     T.a0 = mt.a[0]; T.a1 = mt.a[1]; T.a2 = mt.a[2]; T.b0 = mt.b[0]; T.b1 = mt.b[1]; T.b2 = mt.b[2];
     T.c0 = mt.c[0]; T.c1 = mt.c[1]; T.c2 = mt.c[2];
+    if (!FINAL) { T.n3a = me.n3src[0]; T.n3b = me.n3src[1]; T.n3c = me.n3src[2]; }
     if (P.rebase > 0) {
         // chain indices -> sub-chain indices; what lies before the sub-chain does not exist for it: a range starts at 0 at
         // the earliest, a single node that lies before it becomes "none"
@@ -496,14 +449,14 @@ __device__ __forceinline__ void far_field(const Target& T, int clo, int chi, con
 #pragma unroll
             for (int k = 0; k < 3; k++) {
                 if (!PGA_SPVALID(T.meta, k)) continue;
-                const int zb = min(sel3i(k, T.b0, T.b1, T.b2), chi);
-                for (int j = max(sel3i(k, T.a0, T.a1, T.a2), clo); j < zb; j++)
+                const int zb = min(dpw_sel3i(k, T.b0, T.b1, T.b2), chi);
+                for (int j = max(dpw_sel3i(k, T.a0, T.a1, T.a2), clo); j < zb; j++)
                     if (PGA_KIND(P.src[j].meta) == 1) pair_eval(j, G, T, negc, s_igm, B);
             }
             // (4) the reverse stop of each frame whose ORF covers this node (ref: _connection.h:345-356)
 #pragma unroll
             for (int f = 0; f < 3; f++) {
-                const int j = sel3i(f, T.c0, T.c1, T.c2);
+                const int j = dpw_sel3i(f, T.c0, T.c1, T.c2);
                 if (j >= clo && j < chi) pair_eval(j, G, T, negc, s_igm, B);
             }
         }
@@ -522,6 +475,32 @@ __device__ __forceinline__ void far_field(const Target& T, int clo, int chi, con
     }
 }
 
+// What a final node (score val; alive: it has a traceb) leaves for later targets -- see "Tree kernels" above: a for far gene
+// begins, v0..v2 towards the forward stops of each frame; -inf where it offers nothing.
+struct FarValues { double a, v0, v1, v2; };
+__device__ __forceinline__ FarValues far_values(const int meta, const double val, const bool alive, const double cs,
+                                                const double x0, const double x1, const double x2, const double negc) {
+    const double NEG_INF = -__builtin_huge_val();
+    const int kind = PGA_KIND(meta), frame = PGA_FRAME(meta);
+    FarValues F{NEG_INF, NEG_INF, NEG_INF, NEG_INF};
+    if (kind == 0) {
+        const double g = val + cs;
+        if (frame == 0) F.v0 = g; else if (frame == 1) F.v1 = g; else F.v2 = g;
+    } else if (gene_end(kind) && alive) {
+        F.a = val + negc;
+        if (kind == 1) {
+            if (PGA_SPVALID(meta, 0)) F.v0 = val + x0;
+            if (PGA_SPVALID(meta, 1)) F.v1 = val + x1;
+            if (PGA_SPVALID(meta, 2)) F.v2 = val + x2;
+        }
+    }
+    return F;
+}
+// running _find_max_index of a lane: the last gene end with the highest score so far (ref: lib.pyx:1239-1251)
+__device__ __forceinline__ void track_end(const int kind, const double val, const int i, const int tb, double& end_best, int& end_idx, int& end_tb) {
+    if (gene_end(kind) && val >= end_best) { end_best = val; end_idx = i; end_tb = tb; }
+}
+
 // The batch [i0, i0+64) is final in wave registers: store it with its far-field candidate values and
 // extend the tree.  Returns nothing; updates the running _find_max_index state.
 // PART selects what this call stores (the chain kernel deals the parts to different waves):
@@ -535,27 +514,16 @@ __device__ __forceinline__ void finalize_batch(const Target& T, const Best& B, i
                                                const int* s_levbase, const double negc,
                                                double& end_best, int& end_idx, int& end_tb, RingLds* ring = nullptr) {
     const double NEG_INF = -__builtin_huge_val();
-    const bool act = T.i >= 0;
     double a_val = NEG_INF;
-    if (act) {
+    if (T.i >= 0) {
         const bool alive = B.tb != -1;
         if (PART & 1) {
             P.score[T.i] = B.val; P.traceb[T.i] = B.tb; P.ovm[T.i] = (int8_t)B.ov; P.tbn[T.i] = alive ? B.tbn : -1;
-            if ((T.kind == 1 || T.kind == 2) && B.val >= end_best) { end_best = B.val; end_idx = T.i; end_tb = B.tb; }
+            track_end(T.kind, B.val, T.i, B.tb, end_best, end_idx, end_tb);
         }
-        double v0 = NEG_INF, v1 = NEG_INF, v2 = NEG_INF;
-        if (T.kind == 0) {
-            const double g = B.val + T.cs;
-            if (T.frame == 0) v0 = g; else if (T.frame == 1) v1 = g; else v2 = g;
-        } else if (T.kind == 1 && alive) {
-            a_val = B.val + negc;
-            if (PGA_SPVALID(T.meta, 0)) v0 = B.val + T.x0;
-            if (PGA_SPVALID(T.meta, 1)) v1 = B.val + T.x1;
-            if (PGA_SPVALID(T.meta, 2)) v2 = B.val + T.x2;
-        } else if (T.kind == 2 && alive) {
-            a_val = B.val + negc;
-        }
-        if (PART & 4) { P.V0[T.i] = v0; P.V1[T.i] = v1; P.V2[T.i] = v2; }
+        const FarValues F = far_values(T.meta, B.val, alive, T.cs, T.x0, T.x1, T.x2, negc);
+        a_val = F.a;
+        if (PART & 4) { P.V0[T.i] = F.v0; P.V1[T.i] = F.v1; P.V2[T.i] = F.v2; }
         if (PART & 2) {
             P.A[T.i] = a_val;
             if (ring) { ring->A[T.i & (PGA_RING - 1)] = a_val; ring->ndx[T.i & (PGA_RING - 1)] = T.ndx; }
@@ -563,69 +531,58 @@ __device__ __forceinline__ void finalize_batch(const Target& T, const Best& B, i
     }
     if (!(PART & 24) || i0 + 64 > n) return;
     double rv = a_val; int ri = i0 + lane;
-#pragma unroll
-    for (int m = 1; m <= 4; m <<= 1) {
-        const double ov2 = __shfl_xor(rv, m, 64); const int oi = __shfl_xor(ri, m, 64);
-        if (ov2 > rv || (ov2 == rv && oi > ri)) { rv = ov2; ri = oi; }
-    }
+    wave_lexmax<1, 4>(rv, ri);
     const int tile_no = i0 >> 6;
     if ((PART & 8) && (lane & 7) == 0) {
         P.hv[s_levbase[1] + (i0 >> 3) + (lane >> 3)] = rv; P.hi[s_levbase[1] + (i0 >> 3) + (lane >> 3)] = ri;
         if (ring) { ring->l1v[((i0 >> 3) + (lane >> 3)) & (PGA_RING_BLOCKS - 1)] = rv; ring->l1i[((i0 >> 3) + (lane >> 3)) & (PGA_RING_BLOCKS - 1)] = ri; }
     }
     if (!(PART & 16)) return;
-#pragma unroll
-    for (int m = 8; m <= 32; m <<= 1) {
-        const double ov2 = __shfl_xor(rv, m, 64); const int oi = __shfl_xor(ri, m, 64);
-        if (ov2 > rv || (ov2 == rv && oi > ri)) { rv = ov2; ri = oi; }
-    }
+    wave_lexmax<8, 32>(rv, ri);
     if (lane == 0) { P.hv[s_levbase[2] + tile_no] = rv; P.hi[s_levbase[2] + tile_no] = ri; }
     // higher levels: a block of 8 children closes when its last child does
     int child = tile_no, lev = 2;
     while ((child & 7) == 7 && (lev + 1) * 3 < 31 && (n >> (3 * (lev + 1))) > 0) {
         double cv = NEG_INF; int ci = -1;
         if (lane < 8) { cv = P.hv[s_levbase[lev] + child - 7 + lane]; ci = P.hi[s_levbase[lev] + child - 7 + lane]; }
-#pragma unroll
-        for (int m = 1; m <= 4; m <<= 1) {
-            const double ov2 = __shfl_xor(cv, m, 64); const int oi = __shfl_xor(ci, m, 64);
-            if (ov2 > cv || (ov2 == cv && oi > ci)) { cv = ov2; ci = oi; }
-        }
+        wave_lexmax<1, 4>(cv, ci);
         child >>= 3; lev++;
         if (lane == 0) { P.hv[s_levbase[lev] + child] = cv; P.hi[s_levbase[lev] + child] = ci; }
     }
 }
 
-__device__ __forceinline__ void init_levbase(int* s_levbase, int n) {
+// first entry of tree level lev (>= 1) in hv / hi: the levels lie one behind the other, level l has n >> 3 l entries
+__device__ __forceinline__ int levbase_of(const int lev, const int n) {
     int base = 0;
-    s_levbase[0] = 0;
-    for (int lev = 1; lev < 12; lev++) { s_levbase[lev] = base; base += (lev * 3 < 31) ? (n >> (3 * lev)) : 0; }
+    for (int l = 1; l < lev; l++) base += (l * 3 < 31) ? (n >> (3 * l)) : 0;
+    return base;
+}
+__device__ __forceinline__ void init_levbase(int* s_levbase, int n) {
+    for (int lev = 0; lev < 12; lev++) s_levbase[lev] = levbase_of(lev, n);
 }
 
+// _find_max_index of a chain: the highest score among gene ends, ties to the largest index (ref: lib.pyx:1239-1251, 1311)
+__device__ __forceinline__ void publish_end(const double end_best, const int end_idx, const int end_tb, const DpBuffers& buf, const int slot) {
+    buf.max_index[slot] = end_idx; buf.max_score[slot] = end_idx >= 0 ? end_best : 0.0;
+    buf.ipath[slot] = (end_idx >= 0 && end_tb != -1) ? end_idx : -1;
+}
+// ... from the lanes' running states
 __device__ __forceinline__ void publish_max(double end_best, int end_idx, int end_tb, int lane, const DpBuffers& buf, const int slot) {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) {
-        const double ob = __shfl_xor(end_best, m, 64);
-        const int oi = __shfl_xor(end_idx, m, 64);
-        const int ot = __shfl_xor(end_tb, m, 64);
-        if (ob > end_best || (ob == end_best && oi > end_idx)) { end_best = ob; end_idx = oi; end_tb = ot; }
-    }
-    if (lane == 0) {   // highest score among gene ends, ties to the largest index (ref: lib.pyx:1239-1251, 1311)
-        buf.max_index[slot] = end_idx; buf.max_score[slot] = end_idx >= 0 ? end_best : 0.0;
-        buf.ipath[slot] = (end_idx >= 0 && end_tb != -1) ? end_idx : -1;
-    }
+    wave_lexmax<1, 32>(end_best, end_idx, end_tb);
+    if (lane == 0) publish_end(end_best, end_idx, end_tb, buf, slot);
 }
 
 // In-batch walk, general form: source k's registers are broadcast and every pair is evaluated in full.
-__device__ __forceinline__ void walk_batch(const Target& T, Best& B, int i0, int n, const double negc, const double* s_igm) {
+template <bool FINAL = true>
+__device__ __forceinline__ void walk_batch(const Target& T, Best& B, int i0, int n, const double negc, const double* s_igm, const double st_wt = 0.0) {
     const int kmax = min(63, n - 1 - i0);
     for (int k = 0; k < kmax; k++) {
-        const int sk = PGA_KIND(__builtin_amdgcn_readlane(T.meta, k));
-        const int tbk = __builtin_amdgcn_readlane(B.tb, k);
-        if ((sk == 1 || sk == 2) && tbk == -1) continue;
+        if (dead_source(PGA_KIND(__builtin_amdgcn_readlane(T.meta, k)), __builtin_amdgcn_readlane(B.tb, k))) continue;
         SrcLane S;
         S.ndx = T.ndx; S.stop_val = T.stop_val; S.meta = T.meta; S.tbn = B.tbn;
         S.cs = T.cs; S.x0 = T.x0; S.x1 = T.x1; S.x2 = T.x2; S.score = B.val;
-        visit_source(k, i0 + k, S, T, negc, s_igm, B);
+        if (!FINAL) { S.n3a = T.n3a; S.n3b = T.n3b; S.n3c = T.n3c; }
+        visit_source<FINAL>(k, i0 + k, S, T, negc, s_igm, B, st_wt);
     }
 }
 
@@ -680,8 +637,8 @@ __device__ __forceinline__ RevRegs rev_regs(const Target& T) {
         R.okhi = T.ndx - 4;
 #pragma unroll
         for (int q = 0; q < 3; q++) {
-            const int n3s = sel3i(q, T.n3s0, T.n3s1, T.n3s2), n3n = sel3i(q, T.n3n0, T.n3n1, T.n3n2);
-            if (PGA_SPVALID(T.meta, q) && sel3(q, T.x0, T.x1, T.x2) > 0.0) {
+            const int n3s = dpw_sel3i(q, T.n3s0, T.n3s1, T.n3s2), n3n = dpw_sel3i(q, T.n3n0, T.n3n1, T.n3n2);
+            if (PGA_SPVALID(T.meta, q) && dpw_sel3(q, T.x0, T.x1, T.x2) > 0.0) {
                 const int lo = n3s - 5;
                 const int hi = min(min(n3s + PGA_MAX_OPP_OVLP - 5, (n3n + n3s - 6) >> 1), R.okhi);
                 if (q == 0) { R.lo0 = lo; R.hi0 = hi; } else if (q == 1) { R.lo1 = lo; R.hi1 = hi; } else { R.lo2 = lo; R.hi2 = hi; }
@@ -694,6 +651,18 @@ __device__ __forceinline__ RevRegs rev_regs(const Target& T) {
     return R;
 }
 
+// pair_rule once more, in a form of its own for the serial wave of k_dp_tree_mw (FINAL only): cut into a part that does not
+// depend on scores (static_pair, rev_regs: computed by the helper waves a batch ahead) and a part of one comparison per
+// candidate that does (dyn_regs, dyn_weight: all the serial wave has left to do).  What restates what:
+//   static_pair, sk == 0 / 2 / 3          the three branches of pair_rule of the same source kinds, ok and w as there
+//   static_pair, sk == 1, T.kind 0 / 1    the intergenic and operon cases of the forward-stop branch (ok0 / ok1, g / sxf)
+//   rev_regs + the `flags` of static_pair the tests of the forward-stop branch that read positions only: T.kind == 2 its
+//                                         ovlp / distance tests, T.kind == 3 `left < right` (okhi) and, per candidate q,
+//                                         ovlp > 0, ovlp < MAX_OPP_OVLP, ovlp < n3n - left -- as intervals on s_ndx
+//   dyn_regs + dyn_weight                 what reads tbnj (`< T.stop_val - 3 - tbnj`, `ovlp < n3s - tbnj - 2`) and the
+//                                         `xq > maxval` choice among the admitted candidates, mf as ov1 - 1
+// Nothing but the tests ties the two forms together: `tree3` against `scan1/4/16` in VARIANTS (tests/test_dp_shapes_gpu.py,
+// tests/test_dp_ties_gpu.py) runs every designed shape through both.
 // Static part of a pair: source = lane k of batch S (chain index j), target = this lane of batch T.
 // Weight and admissibility that do not depend on the source's running state.  What remains dynamic is
 // a forward-stop source (position s_ndx, its traceb node at tbnj) towards a reverse target: it goes
@@ -731,12 +700,12 @@ __device__ __forceinline__ void static_pair(const int k, const int j, const Targ
         const bool b = (T.kind == 3) & (s_stop > T.ndx) & (PGA_SPVALID(T.meta, sf) != 0);
         ok = inwin & (a | b);
         const double tx0 = T.x0, tx1 = T.x1, tx2 = T.x2;
-        const double xs = sel3(sf, tx0, tx1, tx2);      // uniform choice
+        const double xs = dpw_sel3(sf, tx0, tx1, tx2);      // uniform choice
         w = a ? T.cs : xs;
     } else {
         const double sx0 = readlane_f64(S.x0, k), sx1 = readlane_f64(S.x1, k), sx2 = readlane_f64(S.x2, k);
         const double g = igm_apart_sel(T.ndx - s_ndx, negc, s_igm);
-        const double sxf = sel3(T.frame, sx0, sx1, sx2);
+        const double sxf = dpw_sel3(T.frame, sx0, sx1, sx2);
         const bool ok0 = s_ndx + 2 < T.ndx;
         const bool ok1 = (T.stop_val < s_ndx) & (((s_meta >> (4 + T.frame)) & 1) != 0);
         const bool ok2 = s_ndx < R.okhi;         // a reverse start is admissible only through its candidate
@@ -948,7 +917,7 @@ k_dp_tree_mw(const ChainDesc* __restrict__ chains, const DpSrc* __restrict__ g_s
             //   lk   in-batch source taken last (| (ov_mark + 1) << 8), -1 while the pre-walk result stands
             // Rows k >= kmax of the weight tile are NaN, so every batch runs the same 64 steps.
             const unsigned long long dynm = __ballot(s_dyn[slot][lane] != 0ull);
-            const bool endlane = T.kind == 1 || T.kind == 2;
+            const bool endlane = gene_end(T.kind);
             // ndx of the pre-walk traceb node: in the previous batch (LDS), or found by the early far-field wave
             const int tbn_pre = B.tb < 0 ? -1 : (B.tb >= i0 - 64 ? s_fin.ndx[B.tb - (i0 - 64)] : s_etbn[slot][lane]);
             if (endlane && B.tb < 0) bv = -__builtin_huge_val();
@@ -1003,7 +972,7 @@ k_dp_tree_mw(const ChainDesc* __restrict__ chains, const DpSrc* __restrict__ g_s
             s_fin.score[lane] = B.val; s_fin.ndx[lane] = T.ndx; s_fin.tbn[lane] = B.tb != -1 ? B.tbn : -1;
             s_fin.tb[lane] = B.tb; s_fin.ov[lane] = B.ov;
             s_fin.meta[lane] = T.meta; s_fin.cs[lane] = T.cs; s_fin.x0[lane] = T.x0; s_fin.x1[lane] = T.x1; s_fin.x2[lane] = T.x2;
-            const unsigned long long dm = __ballot(endlane && B.tb == -1);
+            const unsigned long long dm = __ballot(dead_source(T.kind, B.tb));
             if (lane == 0) s_fin.dead = dm;
             if (nx < n) T = Tnext;
             if (prof && lane == 0) {
@@ -1091,8 +1060,7 @@ k_dp_tree_mw(const ChainDesc* __restrict__ chains, const DpSrc* __restrict__ g_s
 template <int W, bool FINAL = true>
 __global__ void __launch_bounds__(64 * W)
 k_dp_chain(const ChainDesc* __restrict__ chains, const DpSrc* __restrict__ g_src, const DpTgt* __restrict__ g_tgt,
-           const ModelConst* __restrict__ models, double* g_score, int32_t* g_traceb, int32_t* g_tbn, int8_t* g_ov,
-           int32_t* __restrict__ max_index, double* __restrict__ max_score, int32_t* __restrict__ ipath) {
+           const ModelConst* __restrict__ models, DpBuffers buf) {
     __shared__ double s_igm[64];
     __shared__ double s_pval[W > 1 ? W : 1][64];
     __shared__ int s_ptb[W > 1 ? W : 1][64], s_pov[W > 1 ? W : 1][64], s_ptbn[W > 1 ? W : 1][64];
@@ -1103,30 +1071,13 @@ k_dp_chain(const ChainDesc* __restrict__ chains, const DpSrc* __restrict__ g_src
     if (wave == 0) s_igm[lane] = mc->igm[lane];
     __syncthreads();
     const double negc = mc->negc, st_wt = mc->st_wt;
-    const DpSrc* __restrict__ src = g_src + cd.off;
-    const DpTgt* __restrict__ tgt = g_tgt + cd.off;
-    double* score = g_score + cd.off; int32_t* traceb = g_traceb + cd.off;
-    int32_t* tbn = g_tbn + cd.off; int8_t* ovm = g_ov + cd.off;
+    const ChainPtrs P = chain_ptrs(cd, g_src, g_tgt, buf);
 
     double end_best = -1.0; int end_idx = -1, end_tb = -1;     // _find_max_index (ref: lib.pyx:1239-1251)
 
     for (int i0 = 0; i0 < n; i0 += 64) {
         Target T;
-        T.i = i0 + lane;
-        const bool act = T.i < n;
-        DpSrc me;
-        {
-            const int ii = act ? T.i : n - 1;
-            me = src[ii]; const DpTgt mt = tgt[ii];
-            T.kind = PGA_KIND(me.meta); T.frame = PGA_FRAME(me.meta); T.meta = me.meta;
-            T.ndx = me.ndx; T.stop_val = me.stop_val; T.cs = me.cs; T.csd = me.cs + negc;
-            T.x0 = me.x[0]; T.x1 = me.x[1]; T.x2 = me.x[2];
-            T.n3n0 = mt.n3ndx[0]; T.n3n1 = mt.n3ndx[1]; T.n3n2 = mt.n3ndx[2];
-            T.n3s0 = mt.n3stop[0]; T.n3s1 = mt.n3stop[1]; T.n3s2 = mt.n3stop[2];
-            T.lo = act ? mt.lo : INT_MAX;
-            T.a0 = me.n3src[0]; T.a1 = me.n3src[1]; T.a2 = me.n3src[2];     // carried for the in-batch walk of the training pass
-            if (!act) T.i = -1;       // j < T.i is never true: lane stays idle
-        }
+        load_target<FINAL>(T, P, i0, lane, n, negc);
         Best B{0.0, -1, -1, -1};
         const int wlo = wave_min_i32(T.lo);
 
@@ -1135,14 +1086,12 @@ k_dp_chain(const ChainDesc* __restrict__ chains, const DpSrc* __restrict__ g_src
             const int sidx = t0 + lane;                       // < i0 <= n
             SrcLane S;
             {
-                const DpSrc r = src[sidx];
+                const DpSrc r = P.src[sidx];
                 S.ndx = r.ndx; S.stop_val = r.stop_val; S.meta = r.meta; S.cs = r.cs; S.x0 = r.x[0]; S.x1 = r.x[1]; S.x2 = r.x[2];
-                S.n3a = r.n3src[0]; S.n3b = r.n3src[1]; S.n3c = r.n3src[2];
-                S.score = score[sidx]; S.tbn = tbn[sidx];
+                if (!FINAL) { S.n3a = r.n3src[0]; S.n3b = r.n3src[1]; S.n3c = r.n3src[2]; }
+                S.score = P.score[sidx]; S.tbn = P.tbn[sidx];
             }
-            const int sk = PGA_KIND(S.meta);
-            const bool dead = (sk == 1 || sk == 2) && S.tbn == -1;   // gene end never reached: connects to nothing (ref: :110-114)
-            unsigned long long visit = __ballot(sidx >= wlo && !dead);
+            unsigned long long visit = __ballot(sidx >= wlo && !dead_source(PGA_KIND(S.meta), S.tbn));
             while (visit) {
                 const int k = __builtin_ctzll(visit);
                 visit &= visit - 1;
@@ -1156,43 +1105,18 @@ k_dp_chain(const ChainDesc* __restrict__ chains, const DpSrc* __restrict__ g_src
         if (wave == 0) {
             if (W > 1) {
 #pragma unroll 4
-                for (int w = 1; w < W; w++) {
-                    const double v = s_pval[w][lane]; const int t = s_ptb[w][lane];
-                    if (t != -1 && (v > B.val || (v == B.val && t > B.tb))) { B.val = v; B.tb = t; B.ov = s_pov[w][lane]; B.tbn = s_ptbn[w][lane]; }
-                }
+                for (int w = 1; w < W; w++) take(B, s_ptb[w][lane] != -1, s_pval[w][lane], s_ptb[w][lane], s_pov[w][lane], s_ptbn[w][lane]);
             }
             // ---- phase I: sources inside this batch are the lanes themselves
-            const int kmax = min(63, n - 1 - i0);
-            for (int k = 0; k < kmax; k++) {
-                const int sk = PGA_KIND(__builtin_amdgcn_readlane(T.meta, k));
-                const int tbk = __builtin_amdgcn_readlane(B.tb, k);
-                if ((sk == 1 || sk == 2) && tbk == -1) continue;
-                SrcLane S;
-                S.ndx = T.ndx; S.stop_val = T.stop_val; S.meta = T.meta; S.tbn = B.tbn;
-                S.cs = T.cs; S.x0 = T.x0; S.x1 = T.x1; S.x2 = T.x2; S.score = B.val;
-                S.n3a = T.a0; S.n3b = T.a1; S.n3c = T.a2;
-                visit_source<FINAL>(k, i0 + k, S, T, negc, s_igm, B, st_wt);
-            }
-            if (act) {
-                score[T.i] = B.val; traceb[T.i] = B.tb; ovm[T.i] = (int8_t)B.ov; tbn[T.i] = B.tb < 0 ? -1 : B.tbn;
-                if ((T.kind == 1 || T.kind == 2) && B.val >= end_best) { end_best = B.val; end_idx = T.i; end_tb = B.tb; }
+            walk_batch<FINAL>(T, B, i0, n, negc, s_igm, st_wt);
+            if (T.i >= 0) {
+                P.score[T.i] = B.val; P.traceb[T.i] = B.tb; P.ovm[T.i] = (int8_t)B.ov; P.tbn[T.i] = B.tb < 0 ? -1 : B.tbn;
+                track_end(T.kind, B.val, T.i, B.tb, end_best, end_idx, end_tb);
             }
         }
         if (W > 1) __syncthreads();      // the batch's stores are visible to the whole workgroup from here on
     }
-    if (wave != 0) return;
-    // highest score among gene-end nodes, ties to the largest index (the reference scans from the end with '>')
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) {
-        const double ob = __shfl_xor(end_best, m, 64);
-        const int oi = __shfl_xor(end_idx, m, 64);
-        const int ot = __shfl_xor(end_tb, m, 64);
-        if (ob > end_best || (ob == end_best && oi > end_idx)) { end_best = ob; end_idx = oi; end_tb = ot; }
-    }
-    if (lane == 0) {
-        max_index[blockIdx.x] = end_idx; max_score[blockIdx.x] = end_idx >= 0 ? end_best : 0.0;
-        ipath[blockIdx.x] = (end_idx >= 0 && end_tb != -1) ? end_idx : -1;
-    }
+    if (wave == 0) publish_max(end_best, end_idx, end_tb, lane, buf, blockIdx.x);
 }
 
 
@@ -1253,9 +1177,9 @@ k_seg_weights(const ChainDesc* __restrict__ chains, const int32_t* __restrict__ 
         int t2 = ctb[tb];
         if (t2 >= tb || t2 < 0) t2 = -1;
         const int tbnj = t2 >= 0 ? P.src[t2].ndx : -1;
-        const GlobalAcc G{P.src, nullptr, nullptr};
-        bool ok;
-        pair_weight(tb, G, tbnj, T, negc, s_igm, ok, w, mf);
+        const ClaimAcc G{{P.src, nullptr, nullptr}, tbnj};
+        bool ok = false;
+        pair_rule<true>(tb, G, T, negc, s_igm, 0.0, [&](const bool o, const double pw, const int m) { ok = o; w = pw; mf = m; });
         if (ok) tbn = P.src[tb].ndx; else { tb = -1; w = 0.0; mf = -1; }
     }
     P.traceb[i] = tb; P.ovm[i] = (int8_t)mf; P.tbn[i] = tbn; g_cw[cd.off + i] = w;
@@ -1484,13 +1408,7 @@ k_dp_rescore(const ChainDesc* __restrict__ chains, const int32_t* __restrict__ b
     }
 }
 
-__device__ __forceinline__ int levbase_of(const int lev, const int n) {     // init_levbase, one entry
-    int base = 0;
-    for (int l = 1; l < lev; l++) base += (l * 3 < 31) ? (n >> (3 * l)) : 0;
-    return base;
-}
-
-// far-field candidate values of every node (finalize_batch's A and V) and the two lowest tree levels, from the
+// far-field candidate values of every node (far_values: A and V) and the two lowest tree levels, from the
 // exact scores; one wave per 64 nodes
 __global__ void __launch_bounds__(256)
 k_seg_build_far(const ChainDesc* __restrict__ chains, const int32_t* __restrict__ big, const int32_t* __restrict__ gate,
@@ -1503,50 +1421,26 @@ k_seg_build_far(const ChainDesc* __restrict__ chains, const int32_t* __restrict_
     const int i = blockIdx.x * blockDim.x + threadIdx.x, lane = threadIdx.x & 63;
     const int i0 = i - lane;
     if (i0 >= n) return;
-    const double NEG_INF = -__builtin_huge_val();
     const double negc = models[cd.model].negc;
     const ChainPtrs P = chain_ptrs(cd, g_src, g_tgt, buf);
-    double a_val = NEG_INF;
-    double ev = -1.0; int ei = -1;              // _find_max_index over this tile: gene ends, ties to the larger index
+    double a_val = -__builtin_huge_val();
+    double ev = -1.0; int ei = -1, etb = -1;    // _find_max_index over this tile
     if (i < n) {
         const DpSrc me = P.src[i];
-        const int kind = PGA_KIND(me.meta), frame = PGA_FRAME(me.meta);
         const double val = P.score[i];
-        if (kind == 1 || kind == 2) { ev = val; ei = i; }
-        const bool alive = P.traceb[i] != -1;
-        double v0 = NEG_INF, v1 = NEG_INF, v2 = NEG_INF;
-        if (kind == 0) {
-            const double g = val + me.cs;
-            if (frame == 0) v0 = g; else if (frame == 1) v1 = g; else v2 = g;
-        } else if (kind == 1 && alive) {
-            a_val = val + negc;
-            if (PGA_SPVALID(me.meta, 0)) v0 = val + me.x[0];
-            if (PGA_SPVALID(me.meta, 1)) v1 = val + me.x[1];
-            if (PGA_SPVALID(me.meta, 2)) v2 = val + me.x[2];
-        } else if (kind == 2 && alive) {
-            a_val = val + negc;
-        }
-        P.A[i] = a_val; P.V0[i] = v0; P.V1[i] = v1; P.V2[i] = v2;
+        const int tb = P.traceb[i];
+        track_end(PGA_KIND(me.meta), val, i, tb, ev, ei, etb);
+        const FarValues F = far_values(me.meta, val, tb != -1, me.cs, me.x[0], me.x[1], me.x[2], negc);
+        a_val = F.a;
+        P.A[i] = F.a; P.V0[i] = F.v0; P.V1[i] = F.v1; P.V2[i] = F.v2;
     }
     double rv = a_val; int ri = i;
-#pragma unroll
-    for (int m = 1; m <= 4; m <<= 1) {
-        const double ov2 = __shfl_xor(rv, m, 64); const int oi = __shfl_xor(ri, m, 64);
-        if (ov2 > rv || (ov2 == rv && oi > ri)) { rv = ov2; ri = oi; }
-    }
+    wave_lexmax<1, 4>(rv, ri);
     if ((lane & 7) == 0 && i + 8 <= n) { P.hv[levbase_of(1, n) + (i >> 3)] = rv; P.hi[levbase_of(1, n) + (i >> 3)] = ri; }
-#pragma unroll
-    for (int m = 8; m <= 32; m <<= 1) {
-        const double ov2 = __shfl_xor(rv, m, 64); const int oi = __shfl_xor(ri, m, 64);
-        if (ov2 > rv || (ov2 == rv && oi > ri)) { rv = ov2; ri = oi; }
-    }
+    wave_lexmax<8, 32>(rv, ri);
     if (lane == 0 && i0 + 64 <= n) { P.hv[levbase_of(2, n) + (i0 >> 6)] = rv; P.hi[levbase_of(2, n) + (i0 >> 6)] = ri; }
-#pragma unroll
-    for (int m = 1; m <= 32; m <<= 1) {
-        const double ov2 = __shfl_xor(ev, m, 64); const int oi = __shfl_xor(ei, m, 64);
-        if (ov2 > ev || (ov2 == ev && oi > ei)) { ev = ov2; ei = oi; }
-    }
-    if (lane == 0) { const int64_t tq = (cd.off >> 6) + chain + (i0 >> 6); g_tv[tq] = ev; g_ti[tq] = ei; }
+    wave_lexmax<1, 32>(ev, ei);
+    if (lane == 0) { const int64_t tq = seg_tile(cd, chain, i0); g_tv[tq] = ev; g_ti[tq] = ei; }
 }
 
 // the tree levels above that, and _find_max_index (ref: lib.pyx:1239-1251); one workgroup per chain
@@ -1566,8 +1460,7 @@ k_seg_build_upper(const ChainDesc* __restrict__ chains, const int32_t* __restric
         for (int e = t; e < m; e += 256) {
             double bv = P.hv[cb + 8 * e]; int bi = P.hi[cb + 8 * e];
             for (int q = 1; q < 8; q++) {
-                const double v = P.hv[cb + 8 * e + q]; const int ix = P.hi[cb + 8 * e + q];
-                if (v > bv || (v == bv && ix > bi)) { bv = v; bi = ix; }
+                lex_max(bv, bi, P.hv[cb + 8 * e + q], P.hi[cb + 8 * e + q]);
             }
             P.hv[ob + e] = bv; P.hi[ob + e] = bi;
         }
@@ -1575,25 +1468,17 @@ k_seg_build_upper(const ChainDesc* __restrict__ chains, const int32_t* __restric
         __syncthreads();
     }
     double eb = -1.0; int ei = -1;
-    const int64_t tq0 = (cd.off >> 6) + chain;
-    for (int q = t; q < ((n + 63) >> 6); q += 256) {
-        const double v = g_tv[tq0 + q]; const int ix = g_ti[tq0 + q];
-        if (v > eb || (v == eb && ix > ei)) { eb = v; ei = ix; }
-    }
+    const int64_t tq0 = seg_tile(cd, chain, 0);
+    for (int q = t; q < ((n + 63) >> 6); q += 256) lex_max(eb, ei, g_tv[tq0 + q], g_ti[tq0 + q]);
     s_v[t] = eb; s_i[t] = ei;
     __syncthreads();
     for (int h = 128; h >= 1; h >>= 1) {
-        if (t < h) {
-            const double v = s_v[t + h]; const int ix = s_i[t + h];
-            if (v > s_v[t] || (v == s_v[t] && ix > s_i[t])) { s_v[t] = v; s_i[t] = ix; }
-        }
+        if (t < h) lex_max(s_v[t], s_i[t], s_v[t + h], s_i[t + h]);
         __syncthreads();
     }
     if (t == 0) {
         const int end_idx = s_i[0];
-        const int end_tb = end_idx >= 0 ? P.traceb[end_idx] : -1;
-        buf.max_index[chain] = end_idx; buf.max_score[chain] = end_idx >= 0 ? s_v[0] : 0.0;
-        buf.ipath[chain] = (end_idx >= 0 && end_tb != -1) ? end_idx : -1;
+        publish_end(s_v[0], end_idx, end_idx >= 0 ? P.traceb[end_idx] : -1, buf, chain);
     }
 }
 
@@ -1839,14 +1724,12 @@ void pga_launch_dp(const Knobs& kn, const ChainDesc* d_chains, int n_chains, con
     if (n_chains <= 0) return;
     if (final && seg != nullptr && seg->n_segs > 0) { launch_dp_segmented(d_chains, n_chains, d_models, buf, st, *seg); return; }
     if (!final) {     // training pass: once per genome, the window-scanning kernel is plenty
-        hipLaunchKernelGGL((k_dp_chain<16, false>), dim3(n_chains), dim3(64 * 16), 0, st, d_chains, buf.src, buf.tgt, d_models,
-                           buf.score, buf.traceb, buf.tbn, buf.ov_mark, buf.max_index, buf.max_score, buf.ipath);
+        hipLaunchKernelGGL((k_dp_chain<16, false>), dim3(n_chains), dim3(64 * 16), 0, st, d_chains, buf.src, buf.tgt, d_models, buf);
         return;
     }
-#define PGA_DP_LAUNCH(WAVES) hipLaunchKernelGGL(k_dp_chain<WAVES>, dim3(n_chains), dim3(64 * WAVES), 0, st, d_chains, buf.src, buf.tgt, \
-        d_models, buf.score, buf.traceb, buf.tbn, buf.ov_mark, buf.max_index, buf.max_score, buf.ipath)
+#define PGA_DP_LAUNCH(WAVES) hipLaunchKernelGGL(k_dp_chain<WAVES>, dim3(n_chains), dim3(64 * WAVES), 0, st, d_chains, buf.src, buf.tgt, d_models, buf)
     if (kn.dp_kernel != Knobs::scan) {
-        // many chains: one wave each fills the chip; few chains: latency-bound, 3 cooperating waves per chain
+        // many chains: one wave each fills the chip; few chains: latency-bound, 16 cooperating waves per chain (k_dp_tree_mw)
         bool mw = n_chains < 2048;
         if (kn.dp_kernel == Knobs::tree1) mw = false;
         if (kn.dp_kernel == Knobs::tree3) mw = true;

@@ -30,9 +30,6 @@
 
 namespace {
 
-__device__ __forceinline__ double rl_f64(double v, int lane) {
-    return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), lane), __builtin_amdgcn_readlane(__double2loint(v), lane));
-}
 __device__ __forceinline__ int rl_i32(int v, int lane) { return __builtin_amdgcn_readlane(v, lane); }
 
 // contig of group node g (first-node offsets, n_contigs + 1 entries)
@@ -210,11 +207,6 @@ k_dpw_chain(const ChainDesc* __restrict__ chains, int n_chains, int64_t node_beg
     ext[g] = e;
 }
 
-// lexicographic (value, index) maximum: ties go to the larger index
-__device__ __forceinline__ void lex_max(double& v, int& i, const double ov, const int oi) {
-    const bool c = ov > v || (ov == v && oi > i);
-    v = c ? ov : v; i = c ? oi : i;
-}
 // inclusive prefix (lower lanes first) of the lexicographic maximum
 __device__ __forceinline__ void wave_prefix_lexmax(double& v, int& i, const int lane) {
 #pragma unroll
@@ -230,18 +222,6 @@ __device__ __forceinline__ void wave_suffix_lexmax(double& v, int& i, const int 
         if (lane + d < 64) lex_max(v, i, ov, oi);
     }
 }
-// Cross-lane moves through the data-parallel primitives of the vector ALU (DPP) instead of ds_bpermute: a lone wavefront waits out
-// the full LDS round trip of every __shfl, six of them in a row per scan, and these scans sit on the serial path of a chain.
-// CTRL: 0x111 .. 0x11f row_shr:1 .. 15, 0x138 wave_shr:1, 0x142 row_bcast15, 0x143 row_bcast31, 0x140 row_mirror, 0x141 row_half_mirror,
-// quad_perm otherwise.  Lanes that receive nothing (shifted in from outside the row, or masked out by ROW_MASK) get `old`.
-template <int CTRL, int ROW_MASK = 0xf>
-__device__ __forceinline__ double dpp_f64(const double old, const double v) {
-    const int hi = __builtin_amdgcn_update_dpp(__double2hiint(old), __double2hiint(v), CTRL, ROW_MASK, 0xf, false);
-    const int lo = __builtin_amdgcn_update_dpp(__double2loint(old), __double2loint(v), CTRL, ROW_MASK, 0xf, false);
-    return __hiloint2double(hi, lo);
-}
-template <int CTRL, int ROW_MASK = 0xf>
-__device__ __forceinline__ int dpp_i32(const int old, const int v) { return __builtin_amdgcn_update_dpp(old, v, CTRL, ROW_MASK, 0xf, false); }
 // (no NaNs, and a zero of either sign is never compared with the other here: v_max_f64 gives what `b > a ? b : a` gives, in one instruction)
 __device__ __forceinline__ double fmax_nn(const double a, const double b) { return __builtin_fmax(a, b); }
 
@@ -254,7 +234,7 @@ __device__ __forceinline__ double wave_max_f64(double v) {
     v = fmax_nn(v, dpp_f64<0x140>(NI, v));            // row_mirror: every lane holds its row's maximum
     v = fmax_nn(v, dpp_f64<0x142, 0xa>(NI, v));       // row_bcast15 into rows 1 and 3
     v = fmax_nn(v, dpp_f64<0x143, 0xc>(NI, v));       // row_bcast31 into rows 2 and 3: lane 63 holds the maximum
-    return rl_f64(v, 63);
+    return readlane_f64(v, 63);
 }
 // inclusive prefix maximum (lower lanes first), values only
 __device__ __forceinline__ double wave_prefix_max_f64(double v, const int lane) {
@@ -267,18 +247,6 @@ __device__ __forceinline__ double wave_prefix_max_f64(double v, const int lane) 
     v = fmax_nn(v, dpp_f64<0x143, 0xc>(NI, v));       // rows 2 and 3 take the total of rows 0 and 1
     return v;
 }
-// wave-wide minimum of an int, the same in every lane
-__device__ __forceinline__ int wave_min_i32(int v) {
-    const int BIG = 0x7fffffff;
-    v = min(v, dpp_i32<0xb1>(BIG, v));
-    v = min(v, dpp_i32<0x4e>(BIG, v));
-    v = min(v, dpp_i32<0x141>(BIG, v));
-    v = min(v, dpp_i32<0x140>(BIG, v));
-    v = min(v, dpp_i32<0x142, 0xa>(BIG, v));
-    v = min(v, dpp_i32<0x143, 0xc>(BIG, v));
-    return rl_i32(v, 63);
-}
-
 struct WavePtrs {
     const int32_t* __restrict__ ndx; const int32_t* __restrict__ stopv; const uint8_t* __restrict__ kf;
     const int32_t* __restrict__ lo; const int32_t* __restrict__ q1; const int32_t* __restrict__ q2;
@@ -374,7 +342,7 @@ __device__ __forceinline__ void wave_step(const SrcRegs& R, const int u, const i
         if (!ok) return;
         ok &= vote(T.stop_val < rl_i32(R.ndx, u));
         if (!ok) return;
-        val = rl_f64(R.score, u) + rl_f64(R.cs, u);
+        val = readlane_f64(R.score, u) + readlane_f64(R.cs, u);
         take = ok & vote(val >= L.val);
     } else if (sk == 2) {
         // reverse start, a gene end: every later gene begin (ref: :125-130, 337-342)
@@ -383,7 +351,7 @@ __device__ __forceinline__ void wave_step(const SrcRegs& R, const int u, const i
         const int s_ndx = rl_i32(R.ndx, u);
         ok &= vote(s_ndx < key_r5);
         if (!ok) return;
-        const double s_score = rl_f64(R.score, u);
+        const double s_score = readlane_f64(R.score, u);
         val = s_score + M.negc;
         const lanemask tab = ok & W.k3 & vote(T.ndx - s_ndx <= 3 * DPW_OPER_DIST);     // reverse stops nearby: the distance term
         if (tab) { if (in_mask(tab)) val = s_score + dpw_igm_apart(T.ndx - s_ndx, M.negc, M.igm); }
@@ -394,7 +362,7 @@ __device__ __forceinline__ void wave_step(const SrcRegs& R, const int u, const i
         if (!ok) return;
         ok &= vote(rl_i32(R.stop_val, u) > T.ndx);
         if (!ok) return;
-        const double s_score = rl_f64(R.score, u);
+        const double s_score = readlane_f64(R.score, u);
         const bool r5t = in_mask(W.k2);
         // sf is uniform: three scalar branches instead of a register-indexed select
         // (the empty asm statements keep the branches apart: merged, they become a select over a private array in scratch)
@@ -406,7 +374,7 @@ __device__ __forceinline__ void wave_step(const SrcRegs& R, const int u, const i
         // forward stop, a gene end: all four kinds (ref: :117-124, 177-188, 238-254, 288-336); dpw_step_f3 with `win` for
         // its window test
         const int s_ndx = rl_i32(R.ndx, u), s_vm = sp >> 4;
-        const double s_score = rl_f64(R.score, u);
+        const double s_score = readlane_f64(R.score, u);
         bool ok = in_mask(win);
         double w; int ov1 = 0;
         if (T.kind == 0) {
@@ -414,7 +382,7 @@ __device__ __forceinline__ void wave_step(const SrcRegs& R, const int u, const i
             w = dpw_igm_apart(T.ndx - s_ndx, M.negc, M.igm);
         } else if (T.kind == 1) {
             ok = ok && T.stop_val < s_ndx && ((s_vm >> T.frame) & 1) != 0;
-            w = dpw_sel3(T.frame, rl_f64(R.x0, u), rl_f64(R.x1, u), rl_f64(R.x2, u));
+            w = dpw_sel3(T.frame, readlane_f64(R.x0, u), readlane_f64(R.x1, u), readlane_f64(R.x2, u));
         } else {
             const int lhs = tbn_of() + s_ndx + 7;
             const bool c0 = (s_ndx > T.dlo0) & (s_ndx < T.dhi0) & (lhs < T.drhs0);
@@ -779,14 +747,14 @@ k_dpw_dyn(const ChainDesc* __restrict__ chains, DpwGroupPtrs groups, const doubl
                 if (!cand) return tagk;
                 cand &= vote(T.ndx > rl_i32(T.stop_val, k));
                 if (!cand) return tagk;
-                double bv = rl_f64(L.val, k);
+                double bv = readlane_f64(L.val, k);
                 int bi = tagk < 0 ? -1 : (tagk & DPW_TAG_MASK), bt = tagk;
                 bool changed = false;
                 const double offer = L.val + T.cs;                  // what each lane would offer as a forward start (one vector add)
                 while (cand) {
                     const int c = __builtin_ctzll(cand);
                     cand &= cand - 1ull;
-                    const double v = rl_f64(offer, c);
+                    const double v = readlane_f64(offer, c);
                     if (v > bv || (v == bv && i0 + c > bi)) { bv = v; bi = i0 + c; bt = i0 + c; changed = true; }
                 }
                 if (changed && lane == k) { L.val = bv; L.tag = bt; }
@@ -835,7 +803,7 @@ k_dpw_dyn(const ChainDesc* __restrict__ chains, DpwGroupPtrs groups, const doubl
             const lanemask rec = vote(has && O.a == pv) & (below | (1ull << lane));
             const int pi = rec ? i0 + 63 - __builtin_clzll(rec) : -1;
             ppv = pv; ppi = pi;
-            const double bmv = rl_f64(pv, 63); const int bmi = rl_i32(pi, 63);
+            const double bmv = readlane_f64(pv, 63); const int bmi = rl_i32(pi, 63);
             s2v = s1v; s2i = s1i;
             double nv = dpp_f64<0x138>(NEG_INF, s1v); int ni = dpp_i32<0x138>(-1, s1i);      // wave_shr:1, lane 0 takes the empty entry
             lex_max(nv, ni, bmv, bmi);
@@ -863,13 +831,13 @@ k_dpw_dyn(const ChainDesc* __restrict__ chains, DpwGroupPtrs groups, const doubl
                     const double m = wave_max_f64(v);
                     const lanemask at = some & vote(v == m);               // a later node wins a tie
                     const int wl = 63 - __builtin_clzll(at);
-                    const double mv = rl_f64(v, wl);                       // the same value, in scalar registers
+                    const double mv = readlane_f64(v, wl);                       // the same value, in scalar registers
                     if (u >= 0 || mv >= rv) { rv = mv; ri = i0 + wl; rn = rl_i32(T.ndx, wl); }
                 } else if (u >= 0) { rv = NEG_INF; ri = -1; rn = -1; }
                 const lanemask mr = vote(r3n && T.frame == f);
                 if (mr) {
                     const int w = 63 - __builtin_clzll(mr);
-                    const int li = i0 + w, ls = rl_i32(T.stop_val, w), ln = rl_i32(T.ndx, w); const double lv = rl_f64(B.val, w);
+                    const int li = i0 + w, ls = rl_i32(T.stop_val, w), ln = rl_i32(T.ndx, w); const double lv = readlane_f64(B.val, w);
                     if (f == 0) { l3i0 = li; l3s0 = ls; l3n0 = ln; l3v0 = lv; } else if (f == 1) { l3i1 = li; l3s1 = ls; l3n1 = ln; l3v1 = lv; }
                     else { l3i2 = li; l3s2 = ls; l3n2 = ln; l3v2 = lv; }
                 }
@@ -1221,7 +1189,7 @@ k_dp_wave(const ChainDesc* __restrict__ chains, DpwGroupPtrs groups, const doubl
             const lanemask rec = vote(has && av == pv) & upto;
             const int pi = rec ? i0 + 63 - __builtin_clzll(rec) : -1;
             s_ppv[ln] = pv; s_ppi[ln] = pi;
-            const double bmv = rl_f64(pv, 63); const int bmi = rl_i32(pi, 63);
+            const double bmv = readlane_f64(pv, 63); const int bmi = rl_i32(pi, 63);
             // S2 := S1, S1 := S1 moved up a lane with the block's maximum merged in: the new S1 goes where S2 was, the buffers swap roles
             const int pb = b & 1;
             double nv = ln > 0 ? s_blkv[pb][(ln - 1) & 63] : NEG_INF; int ni = ln > 0 ? s_blki[pb][(ln - 1) & 63] : -1;

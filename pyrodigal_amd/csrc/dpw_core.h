@@ -80,6 +80,22 @@ DPW_HD double dpw_igm_same(int a_ndx, int a_strand, double a_r, double a_u, int 
 //        the 3' end of this gene (DPW_NONE: none before stop_val + MAX_OPP_OVLP)
 struct DpwTopo { uint8_t kf; int32_t lo, q1, q2; };
 
+// Window start of node i (ref: lib.pyx:1221-1233): 500 nodes back, stretched to the far end of a giant ORF, then another 500.
+// The reference's walk-down stops at the highest index whose position equals stop_val, or at 0; positions are sorted, so a
+// binary search finds the same index.  (Positions ascend and a position holds at most two nodes: everything before node
+// lo - 2 d - 2 lies more than d positions left of node lo, so the search starts there, not at 0: ten steps instead of
+// twenty-three on a genome.)
+DPW_HD int dpw_window_lo(const int32_t* ndx, const int i, const int kind, const int my_stop) {
+    int lo = i < DPW_MAX_NODE_DIST ? 0 : i - DPW_MAX_NODE_DIST;
+    if ((kind == 2 || kind == 1) && ndx[lo] > my_stop) {
+        int a = lo - 2 * (ndx[lo] - my_stop) - 2, b = lo;            // find the last p in [0, lo) with ndx[p] <= my_stop
+        if (a < 0) a = 0;
+        while (a < b) { const int m = (a + b) >> 1; if (ndx[m] <= my_stop) a = m + 1; else b = m; }
+        lo = (a > 0 && ndx[a - 1] == my_stop) ? a - 1 : 0;
+    }
+    return lo < DPW_MAX_NODE_DIST ? 0 : lo - DPW_MAX_NODE_DIST;
+}
+
 // `f3` (device, optional): a forward stop's q2 and operon bits when the caller has them already (k_dpw_topo finds the next forward stop
 // of every frame from bit masks of its workgroup's nodes instead of walking the nodes eight at a time)
 struct DpwF3Hint { int q2, bits; };
@@ -90,16 +106,7 @@ DPW_HD DpwTopo dpw_topo_node(const int32_t* ndx, const int32_t* stopv, const uin
     const bool rev = strand[i] != 1, stop = type[i] == 3;
     const int kind = (rev ? 2 : 0) | (stop ? 1 : 0);
     int kf = kind | ((my_ndx % 3) << 2);
-    int lo = i < DPW_MAX_NODE_DIST ? 0 : i - DPW_MAX_NODE_DIST;
-    if ((kind == 2 || kind == 1) && ndx[lo] > my_stop) {
-        // the reference walks down to the highest index whose position equals stop_val, or to 0
-        // (a position holds at most two nodes: everything before node lo - 2 d - 2 lies more than d positions left of node lo)
-        int a = lo - 2 * (ndx[lo] - my_stop) - 2, b = lo;
-        if (a < 0) a = 0;
-        while (a < b) { const int m = (a + b) >> 1; if (ndx[m] <= my_stop) a = m + 1; else b = m; }
-        lo = (a > 0 && ndx[a - 1] == my_stop) ? a - 1 : 0;
-    }
-    lo = lo < DPW_MAX_NODE_DIST ? 0 : lo - DPW_MAX_NODE_DIST;
+    const int lo = dpw_window_lo(ndx, i, kind, my_stop);
     t.lo = lo; t.q1 = 0; t.q2 = 0;
     if (kind == 0 || kind == 3) {
         // first index in [0, i) with ndx >= my_ndx - 3 * OPER_DIST (positions ascend): a handful of nodes back, so look at the
@@ -255,7 +262,8 @@ DPW_HD void dpw_pair(const DpwS& S, const DpwT& T, const DpwModel& M, bool& ok, 
                 const int dlo = dpw_sel3i(q, T.dlo0, T.dlo1, T.dlo2), dhi = dpw_sel3i(q, T.dhi0, T.dhi1, T.dhi2);
                 const double cur = dpw_sel3(q, T.x0, T.x1, T.x2);
                 // (the interval form of the reference's four overlap tests, see DpwLT; an empty interval: no such start, or one worth nothing)
-                const bool tk = (dlo != INT_MAX) & (S.ndx > dlo) & (S.ndx < dhi) & (S.tbn + S.ndx + 7 < 2 * (dlo + 5)) & (cur > maxval);
+                const int drhs = dlo != INT_MAX ? 2 * dlo + 10 : INT_MIN;      // (as dpw_lean: no arithmetic on the empty interval's INT_MAX)
+                const bool tk = (S.ndx > dlo) & (S.ndx < dhi) & (S.tbn + S.ndx + 7 < drhs) & (cur > maxval);
                 if (tk) { mf = q; maxval = cur; }
             }
             w = mf != -1 ? maxval : M.negc;

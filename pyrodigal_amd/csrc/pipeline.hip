@@ -2646,8 +2646,8 @@ __device__ __forceinline__ void overlapping_starts_of(const OvlChain& C, const i
         // the RBS / upstream scores of the start only enter when the two nodes are adjacent (_connection.h:60-66): asked for then only
         const bool adj = fwd ? (my + 2 == nj || my == nj + 1) : (nj + 2 == my || nj == my + 1);
         const double rj = adj ? rs[j] : 0.0, uj = adj ? us[j] : 0.0;
-        const double v = fwd ? csj + igm_same_dev(my, 1, rs_i, us_i, nj, rj, uj, mc->st_wt, mc->igm)
-                             : csj + igm_same_dev(nj, -1, rj, uj, my, rs_i, us_i, mc->st_wt, mc->igm);
+        const double v = fwd ? csj + dpw_igm_same(my, 1, rs_i, us_i, nj, rj, uj, mc->st_wt, mc->igm)
+                             : csj + dpw_igm_same(nj, -1, rj, uj, my, rs_i, us_i, mc->st_wt, mc->igm);
         if (v > best) { const int f = nj % 3; if (f == 0) sp0 = j; else if (f == 1) sp1 = j; else sp2 = j; best = v; }
     }
 }
@@ -2724,8 +2724,8 @@ __device__ __forceinline__ void overlapping_starts_ahead(const OvlChain& C, cons
         // the RBS / upstream scores of the start only enter when the two nodes are adjacent (_connection.h:60-66)
         const bool adj = fwd ? (my + 2 == nj || my == nj + 1) : (nj + 2 == my || nj == my + 1);
         const double rj = adj ? rj0 : 0.0, uj = adj ? uj0 : 0.0;
-        const double v = fwd ? csj + igm_same_dev(my, 1, 0.0, 0.0, nj, rj, uj, mc->st_wt, mc->igm)
-                             : csj + igm_same_dev(nj, -1, rj, uj, my, 0.0, 0.0, mc->st_wt, mc->igm);
+        const double v = fwd ? csj + dpw_igm_same(my, 1, 0.0, 0.0, nj, rj, uj, mc->st_wt, mc->igm)
+                             : csj + dpw_igm_same(nj, -1, rj, uj, my, 0.0, 0.0, mc->st_wt, mc->igm);
         if (v > best) {
             const int f = nj % 3; best = v;
             if (f == 0) { sp[0] = j; K.v[0] = v; K.nd[0] = nj; K.sv[0] = svj; K.q2[0] = q2j; }

@@ -720,6 +720,35 @@ def ahead_series():
     return out
 
 
+DEAD_END_GAP = 141         # nodes between the forward stop and its target: two batches, so every kernel meets it as a stored far value
+DEAD_END_TAIL = 121        # nodes behind the target: 266 in all, a chain that the shrunk segment plan cuts
+
+
+def dead_end_series():
+    """The operon design at d = 13 -- gene A, gene B whose start lies 13 bases before A's end codon -- with B's ORF so long that
+    DEAD_END_GAP reverse nodes lie between A's stop and B's: the tree kernels and the segment kernels then take what A's stop offers
+    B's from the values stored when A's stop became final (`far_values`: V[frame] = score + x[frame]), not from a pair rule.
+    DEAD_END_TAIL more reverse nodes follow, so that the shrunk segment plan cuts the chain and rebuilds those values (k_seg_build_far).
+    `alive`: A's start is worth 100, its stop is reached and B's stop continues from it through B's start.  `dead`: A's start
+    costs the default 50, its stop is never reached and offers nothing (ref: _connection.h:110-114) although 0 + x is more than
+    B's own start gives; B's stop takes B's start."""
+    out = []
+    for state in ("alive", "dead"):
+        lay = Layout(1200)
+        lay.gene("a", 180, 300, 1)
+        at = lay.run("pad", 330, DEAD_END_GAP - 1, -1)
+        xB = 300 - 13
+        yB = xB + 3 * ((at + 40 - xB) // 3 + 1)
+        lay.gene("b", xB, yB, 1)
+        lay.run("tail", yB + 40, DEAD_END_TAIL - 1, -1)
+        scores = {"bb": dict(cscore=7.0, sscore=0.5)}
+        if state == "alive":
+            scores["ab"] = dict(cscore=100.0)
+        out.append(shape("dead_end/+/%s" % state, lay, scores, ("as", "bs", state == "alive"), "dead_end/+", state,
+                         dict(refused_traceb="bb", index={"as": 2, "bs": 3 + DEAD_END_GAP}, dead_end=state)))
+    return out
+
+
 LDS_STATIC = 3 * (6144 // 64) * 8 + 4 * 4      # s_m and s_cnt of k_dpw_topo_lds
 LDS_FIRST_OVER = (65536 - LDS_STATIC - 32) // 12 + 1       # the first node count at which 12 n + 32 dynamic bytes and the static ones pass 64 KB
 LDS_DYNAMIC_OVER = (65536 - 32) // 12 + 1                  # ... at which the dynamic bytes alone do
@@ -788,4 +817,4 @@ def all_shapes():
     pairs = all_pair_shapes()
     out = pairs + [mirrored(s) for s in pairs if s.series and s.series.split("/")[0] in ("igm", "fs_rb", "triple", "operon60")]
     out += [padded(s, 0) for s in pairs if s.probe] + [padded(s, 63) for s in pairs if s.probe and s.max_overlap == 60]
-    return out + edge_stop_series() + window_series() + window_lo_series() + segment_series() + giant_series() + lane_series() + dense_series() + size_series() + ahead_series()
+    return out + edge_stop_series() + window_series() + window_lo_series() + segment_series() + giant_series() + lane_series() + dense_series() + size_series() + ahead_series() + dead_end_series()

@@ -194,6 +194,26 @@ def test_indices_lanes_and_chain_lengths_are_what_the_designs_claim(solved):
     assert any((x[2]["star_ptr"][(x[2]["type"] == 3) & (x[2]["edge"] == 0)] >= 0).any() for x in edge)
 
 
+def test_a_dead_forward_stop_offers_its_operon_value_to_nobody(solved):
+    """dead_end/+: the target lies more than two batches behind the forward stop, whose own value plus its overlapping start's is more
+    than the target's own start gives -- in `alive` the target takes it, in `dead` (the stop has no traceb) it may not."""
+    seen = set()
+    for s, o, before, ref, ref_max, ev, eg in solved:
+        if "dead_end" not in s.meta:
+            continue
+        si, ti, bi = (index_of(ref, s.nodes[k]) for k in ("as", "bs", "bb"))
+        assert ti - si > 128 and ref["strand"][si + 1:ti].max() == -1              # nothing but reverse nodes between them
+        offer = (before["cscore"][bi] + before["sscore"][bi]) + igm_same_ref(13, True, ST_WT)
+        own = ref["score"][bi] + (before["cscore"][bi] + before["sscore"][bi])
+        assert before["star_ptr"][si][int(ref["ndx"][ti]) % 3] == bi and 0.0 + offer > own > 0.0, s.name
+        if s.meta["dead_end"] == "alive":
+            assert ref["traceb"][si] >= 0 and ref["traceb"][ti] == si and ref["score"][ti] == ref["score"][si] + offer
+        else:
+            assert ref["traceb"][si] == -1 and ref["score"][si] == 0.0 and ref["traceb"][ti] == bi and ref["score"][ti] == own
+        seen.add(s.meta["dead_end"])
+    assert seen == {"alive", "dead"}
+
+
 def test_the_host_model_on_every_shape(model, solved):
     for s, o, before, ref, ref_max, ev, eg in solved:
         try:
